@@ -14,8 +14,18 @@ touched a GPU).  Images are independent, so every rank decodes its own images (w
 `--mode grid` shards ONE 16384x16384 grid by tile rows and gathers the RGB row slabs to rank 0
 with one RCCL collective (timed separately, checked bit for bit against the one-rank result).
 
-Parity gate: before timing, one randomly chosen image of EVERY rank is checked bit-exactly against the CPU oracle
+A plain run (`--gpus N --steps K --warmup W`) does only what the headline needs: it builds the batch, runs one untimed step
+and W warm-up steps, times K steps (`ms_per_step`, with the per-kernel HIP-event times of those same steps) and prints the
+line.  `--full` adds everything else, as the default run did before the option existed: the RCCL self-test at N = 1, the
+parity gate, the side clocks (D, E, pipelined E, CPU baseline, real content, configs 2-5 variants, HDR) at N = 1 and the
+per-rank D / E and config-3 legs at N > 1 (`--quick` still leaves the side clocks out of a `--full` run).
+
+Parity gate (`--full`): before timing, one randomly chosen image of EVERY rank is checked bit-exactly against the CPU oracle
 (oracle/liboracle.so; and against the real reference decoder oracle/_ref when it is present).
+
+`--dump-outputs DIR`: after the timed steps, the RGB24 images of the last step are written to DIR as .npy (a fixed, seeded
+sample of whole rows plus a checksum of every row; see dump_outputs).  The inputs are seeded, so two builds run with the
+same arguments can be compared array for array.
 """
 import argparse
 import ctypes as C
@@ -165,6 +175,45 @@ def timed_steps(torch, gb, st, steps, dist=None):
             k_ms[q] += ms[q]
     gb.batch.set_profiling(0)
     return elapsed, [m / steps for m in k_ms]
+
+
+DUMP_BUDGET_BYTES = 60_000_000  # all arrays of --dump-outputs together (kept under 64 MB)
+DUMP_SEED = 20240611
+DUMP_MAX_ROWS = 1024
+
+
+def dump_outputs(path, rgbs, width, height, suffix=""):
+    """--dump-outputs: the RGB24 images a caller of the timed path receives (u8 [>= height, >= 3 * width] device tensors, one per
+    image) as float arrays under `path`, DUMP_BUDGET_BYTES at most:
+      rgb_row_checksums.npy  float64 [images, bands]: sum over x of v[y, x] * (x % 251 + 1) for every row y of every image (exact),
+                             summed over bands of rows - one row per band unless the images are too many to fit half the budget
+      rgb_rows.npy           float32 [R, 3 * width]: R whole rows, (image, row) drawn with a fixed seed (R <= DUMP_MAX_ROWS)
+      rgb_rows_index.npy     float64 [R, 2]: the (image, row) of each sampled row
+    `suffix` tells the ranks' files apart at N > 1."""
+    import numpy as np
+    import torch
+    os.makedirs(path, exist_ok=True)
+    n, w3 = len(rgbs), 3 * width
+    dev = rgbs[0].device
+    weights = torch.arange(w3, dtype=torch.int64, device=dev) % 251 + 1
+    band = 1
+    while n * -(-height // band) * 8 > DUMP_BUDGET_BYTES // 2:
+        band *= 2
+    bands = -(-height // band)
+    sums = np.zeros((n, bands), np.float64)
+    for i, im in enumerate(rgbs):
+        rows = torch.zeros(bands * band, dtype=torch.int64, device=dev)
+        for y0 in range(0, height, 1024):  # (int64 products of 1024 rows at a time)
+            y1 = min(height, y0 + 1024)
+            rows[y0:y1] = (im[y0:y1, :w3].to(torch.int64) * weights).sum(dim=1)
+        sums[i] = rows.view(bands, band).sum(dim=1).cpu().numpy()
+    nrows = int(min(DUMP_MAX_ROWS, n * height, (DUMP_BUDGET_BYTES - sums.nbytes) // (4 * w3 + 16)))
+    flat = np.sort(np.random.default_rng(DUMP_SEED).choice(n * height, size=nrows, replace=False))
+    index = np.stack([flat // height, flat % height], axis=1)
+    sample = (torch.stack([rgbs[i][y, :w3] for i, y in index]).cpu().numpy() if nrows else np.zeros((0, w3))).astype(np.float32)
+    np.save(os.path.join(path, f"rgb_row_checksums{suffix}.npy"), sums)
+    np.save(os.path.join(path, f"rgb_rows{suffix}.npy"), sample)
+    np.save(os.path.join(path, f"rgb_rows_index{suffix}.npy"), index.astype(np.float64))
 
 
 # names as rocprofv3 lists them (the headline workload - 8-bit 4:2:0 without rare syntax - runs the split-chain
@@ -329,10 +378,14 @@ def main():
                     "the reconstruction kernel's end-of-launch tail amortises with the batch)")
     ap.add_argument("--dist-backend", default="nccl", help="torch.distributed backend (nccl = RCCL; gloo only to exercise the N>1 code path on one GPU)")
     ap.add_argument("--allow-shared-gpu", action="store_true", help="let several ranks share one GPU (functional test of the N>1 path only; the JSON says so)")
-    ap.add_argument("--cpu-seconds", type=float, default=10.0, help="budget of each cpu_baseline leg")
-    ap.add_argument("--quick", action="store_true", help="headline only: skip the side clocks (D, E, pipelined E, CPU baseline, real content, configs 4 / 5)")
+    ap.add_argument("--cpu-seconds", type=float, default=10.0, help="budget of each cpu_baseline leg (--full)")
+    ap.add_argument("--full", action="store_true", help="everything beside the headline: RCCL self-test, parity gate, side clocks (D, E, pipelined E, "
+                    "CPU baseline, real content, configs 2-5 variants, HDR) at N = 1, per-rank D / E and config-3 legs at N > 1")
+    ap.add_argument("--quick", action="store_true", help="with --full: skip the side clocks (D, E, pipelined E, CPU baseline, real content, configs 4 / 5)")
     ap.add_argument("--no-e2e", action="store_true", help="alias of --quick (profiling runs)")
-    ap.add_argument("--no-parity", action="store_true")
+    ap.add_argument("--no-parity", action="store_true", help="skip the parity gate (batch mode, --full) / the self-check (grid mode)")
+    ap.add_argument("--dump-outputs", metavar="DIR", help="after the timed steps, write the last step's RGB24 images (seeded row sample + row checksums) "
+                    "to DIR as .npy")
     ap.add_argument("--grid-chunk-rows", type=int, default=0, help="--mode grid: tile rows per chunk a rank decodes and hands to the gather (0 = its whole slab: "
                     "32 tiles per launch sit deep in the few-pictures regime of the chain kernel, profiles/r05_launcher_check.txt)")
     ap.add_argument("--group", type=int, default=0, help="images per filter + colour group (hm_batch_set_colour; 0 = the whole batch per kernel launch)")
@@ -341,6 +394,8 @@ def main():
         args.quick = True
     if args.gpus < 1:
         raise SystemExit("--gpus must be >= 1")
+    if args.steps < 1 or args.warmup < 0:
+        raise SystemExit("--steps must be >= 1 and --warmup >= 0")
     if "WORLD_SIZE" not in os.environ and args.gpus > 1:
         raise SystemExit(launch_ranks(args))
     run(args)
@@ -377,7 +432,7 @@ def run(args):
         if dist.get_world_size() != args.gpus:
             raise SystemExit(f"only {dist.get_world_size()} of {args.gpus} ranks joined")
     dist_info = None
-    if world == 1 and args.dist_backend == "nccl":
+    if args.full and world == 1 and args.dist_backend == "nccl":
         dist_info = rccl_selftest(torch, pkg, dev)
     st = torch.cuda.current_stream().cuda_stream
     if args.mode == "grid":
@@ -388,18 +443,19 @@ def run(args):
     NT = GRID_COLS * GRID_ROWS
     first_image = rank * B
     gb = GridBatch(pkg, dev, GRID_COLS, GRID_ROWS, TILE, OUT_W, OUT_H)
-    keep = min(B, 256)            # coded tiles of the first images are kept for the end-to-end legs
+    side_clocks = args.full and not args.quick
+    keep = min(B, 256) if side_clocks else 0  # coded tiles of the first images are kept for the end-to-end legs
     rng = random.Random(1234 + rank)
     check_image = rng.randrange(B)  # parity gate: a random image of every rank
     kept, check = [], None
-    keep_blobs = world == 1 and not args.quick  # (the variant legs of the single-GPU run build batches of their own from them)
+    keep_blobs = world == 1 and side_clocks  # (the variant legs of the single-GPU run build batches of their own from them)
     all_blobs = []
     seeds = (1200000 + 48 * (first_image + k // NT) + k % NT for k in range(B * NT))
-    made = make_streams(capi, seeds)
+    made = make_streams(capi, seeds, keep_data=args.full)  # (the coded bytes: the parity gate's reference decode and the side legs)
     for j in range(B):
         tiles = [next(made) for _ in range(NT)]
         gb.add_image([b for _, b in tiles])
-        if keep_blobs or (world > 1 and j < SHARE_IMAGES):
+        if keep_blobs or (world > 1 and side_clocks and j < SHARE_IMAGES):
             all_blobs.append([b for _, b in tiles])
         if j < keep:
             kept.append([d for d, _ in tiles])
@@ -408,12 +464,12 @@ def run(args):
     gb.finish(st, args.group)
     strides = (gb.ys, gb.cs, gb.os)
 
-    # ---- parity gate ----
-    parity = "skipped"
+    # ---- parity gate (--full); the step runs in every run, untimed ----
+    parity = "skipped" if args.full else "not run (the parity gate is part of --full)"
     gb.step(st)
     torch.cuda.synchronize()
     ok = 1
-    if not args.no_parity:
+    if args.full and not args.no_parity:
         import numpy as np
         import orc
         got = gb.images[check_image]["rgb"].cpu().numpy()
@@ -425,7 +481,7 @@ def run(args):
             ok = int(np.array_equal(exp[:OUT_H, :OUT_W * 3], exp2[:OUT_H, :OUT_W * 3]))
             parity = "bit-exact vs oracle and reference libde265"
         parity += f" (image {check_image} of rank {rank}; one random image of every rank is checked)"
-    if dist:
+    if dist and args.full:
         t = torch.tensor([ok], dtype=torch.int32, device=dev if args.dist_backend == "nccl" else "cpu")
         dist.all_reduce(t, op=dist.ReduceOp.MIN)
         ok = int(t.item())
@@ -441,9 +497,11 @@ def run(args):
         tt = torch.tensor([elapsed], dtype=torch.float64, device=dev if args.dist_backend == "nccl" else "cpu")
         dist.all_reduce(tt, op=dist.ReduceOp.MAX)
         elapsed = float(tt.item())
+    if args.dump_outputs:  # (before any leg below writes into the images)
+        dump_outputs(args.dump_outputs, [im["rgb"] for im in gb.images], OUT_W, OUT_H, f"_rank{rank}" if world > 1 else "")
 
     out = {}
-    if world > 1 and not args.quick:
+    if world > 1 and side_clocks:
         multi_rank_legs(out, args, torch, pkg, dev, dev_index, st, gb, kept, dist, rank, world)
         share_leg_all_ranks(out, args, torch, pkg, dev, st, all_blobs, dist, rank, world)
     if rank == 0:
@@ -473,7 +531,7 @@ def run(args):
         if world > ndev:
             out["config"]["shared_gpu"] = f"{world} ranks on {ndev} GPU(s): functional run of the N>1 path, not a scaling number"
         gb.batch.check()  # (a reconstruction wave that gave up a bounded wait would have flagged its launch)
-        if not args.quick and world == 1:  # the side clocks belong to the single-GPU run
+        if side_clocks and world == 1:  # the side clocks belong to the single-GPU run
             side_legs(out, args, torch, pkg, dev, st, gb, kept, strides, stream_b, all_blobs)
             try:
                 out["end_to_end_MP_per_s"] = out["end_to_end_pipelined"]["MP_per_s"]
@@ -1423,6 +1481,8 @@ def run_grid(args, torch, pkg, dev, dist, rank, world, st, shared):
         finish_gather(pending[b])
     barrier_sync()
     piped_s = time.perf_counter() - t0
+    if args.dump_outputs and rank == 0:  # the root's image of the last grid (the legs below decode the same grid again)
+        dump_outputs(args.dump_outputs, [images[(args.steps - 1) % NB]], W, H)
     # ---- one grid at a time: decode, then gather (the latency a single caller sees) ----
     n_g = max(1, min(args.steps, 5))
     barrier_sync()

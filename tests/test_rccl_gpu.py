@@ -129,7 +129,7 @@ def test_image_batch_sharded_over_the_gpus_that_are_there(world):
     w = 2 if world == "two_gpus" else n
     if n < 2 or (world == "all_gpus" and n == 2):
         pytest.skip(f"{n} GPU(s) visible: nothing beyond the other cases to run")
-    res = _bench_ranks(w, ["--quick", "--images", "8", "--steps", "2", "--warmup", "1"], timeout=1800)
+    res = _bench_ranks(w, ["--full", "--quick", "--images", "8", "--steps", "2", "--warmup", "1"], timeout=1800)
     assert "error" not in res, res
     assert res["n_gpus"] == w and res["dist"]["backend"] == "nccl" and res["dist"]["world_size"] == w
     assert "bit-exact" in res["config"]["parity"], res["config"]

@@ -3,7 +3,7 @@
 # usage (repo root, on the GPU box): tools/gpu_round.sh <tag> <action> [<action> ...]
 #   tests        python -m pytest tests -m gpu -x -q
 #   smoke        __graft_entry__.smoke()
-#   bench        python3 bench.py (the default line) -> <tag>_bench.json
+#   bench        python3 bench.py --full (the headline and every side leg) -> <tag>_bench.json
 #   quick        bench.py --quick --steps 10 (headline kernels only)
 #   stats        rocprofv3 --kernel-trace --stats of bench.py --quick -> <tag>_kernel_stats.csv
 #   traffic      tools/pmc_traffic.sh (TCC FETCH_SIZE / WRITE_SIZE passes at the bench's load: PMC_IMAGES, default 384) -> <tag>_pmc_traffic.json
@@ -23,7 +23,7 @@ for a in "$@"; do
   case $a in
   tests)   timeout 1500 python3 -m pytest tests -m gpu -x -q > $log 2>&1; tail -3 $log ;;
   smoke)   timeout 300 python3 -c "import __graft_entry__ as g; g.smoke()" > $log 2>&1; tail -2 $log ;;
-  bench)   timeout 900 python3 bench.py > gpurun_out/${tag}_bench.json 2> $log; tail -c 600 gpurun_out/${tag}_bench.json ;;
+  bench)   timeout 900 python3 bench.py --full > ${log%.log}.json 2> $log; tail -c 600 ${log%.log}.json ;;
   quick)   timeout 600 python3 bench.py --quick --steps 10 2> $log | tail -1 | python3 -c "import json,sys; d=json.loads(sys.stdin.read()); print(d['value'], {k: v['ms_per_step'] for k, v in d['kernels'].items()}, d['roofline']['frac'])" ;;
   stats)   rm -rf /tmp/prof_$tag; (cd /tmp && timeout 900 rocprofv3 --kernel-trace --stats -d /tmp/prof_$tag --output-format csv -- python3 $OLDPWD/bench.py --quick --no-parity --steps 10 > $OLDPWD/$log 2>&1)
            f=$(find /tmp/prof_$tag -name "*kernel_stats.csv" | head -1); [ -n "$f" ] && cp $f gpurun_out/${tag}_kernel_stats.csv && head -8 $f ;;

@@ -6,5 +6,5 @@ cd heif-decoder-lib_amd/csrc && rm -f build/hip_chain.o && make HIPFLAGS="--offl
 echo "== GPU tests under -DHM_CHAIN_LATE=1 (without the zero-scratch test)"
 timeout 1500 python3 -m pytest tests -m gpu -x -q --deselect tests/test_chain_modes_gpu.py::test_hot_path_kernels_hold_their_registers_without_a_spill 2>&1 | tail -3
 echo "== bench parity gate + counters under -DHM_CHAIN_LATE=1"
-python3 bench.py --quick --steps 5 2>/dev/null | tail -1 | python3 -c "import json,sys; d=json.loads(sys.stdin.read()); print(d['value'], d['config'].get('parity'), {k: v['ms_per_step'] for k, v in d['kernels'].items()})"
+python3 bench.py --full --quick --steps 5 2>/dev/null | tail -1 | python3 -c "import json,sys; d=json.loads(sys.stdin.read()); print(d['value'], d['config'].get('parity'), {k: v['ms_per_step'] for k, v in d['kernels'].items()})"
 cd heif-decoder-lib_amd/csrc && rm -f build/hip_chain.o && make >/dev/null 2>&1
