@@ -185,6 +185,35 @@ void heif_context_set_threads(struct heif_context* ctx, const struct heif_image_
   if (in_handle->info.is_grid) { ctx->max_decoding_threads = nthreads; ctx->max_decoder_threads = 0; }
   else { ctx->max_decoding_threads = 0; ctx->max_decoder_threads = nthreads; }
 }
+// fork API (context.cc:459-491): movie flag, frame count (= the number of top-level images), duration, and per top-level image
+// what its handle reports.  (The fork writes img_params unchecked; a NULL array with images to describe is refused here.)
+struct heif_error heif_context_get_heif_params(struct heif_context* ctx, struct libheif_parameters* params)
+{
+  if (!ctx || !params) return err(heif_error_Usage_error, heif_suberror_Null_pointer_argument, "NULL passed");
+  if (!ctx->file) return err(heif_error_Invalid_input, heif_suberror_Unspecified, "No file loaded");
+  hm_sequence_info si;
+  int rc = hm_file_sequence_info(ctx->file, &si);
+  if (rc) return from_status(rc);
+  const int n = hm_file_top_level_images(ctx->file, nullptr, 0);
+  if (n < 0) return from_status(n);
+  params->movie_flag = si.is_sequence != 0;
+  params->frame_count = (uint32_t)n;
+  params->movie_duration = si.is_sequence ? (uint32_t)si.duration : 0; // (the fork's field is 32 bits: mvhd's duration truncated)
+  if (n == 0) return ok();
+  if (!params->img_params) return err(heif_error_Usage_error, heif_suberror_Null_pointer_argument, "NULL img_params");
+  std::vector<heif_item_id> ids((size_t)n);
+  hm_file_top_level_images(ctx->file, ids.data(), n);
+  for (int i = 0; i < n; i++) {
+    hm_image_info info;
+    if ((rc = hm_file_image_info(ctx->file, ids[(size_t)i], &info))) return from_status(rc);
+    image_parameters& p = params->img_params[i];
+    p.img_width = (uint32_t)info.width;
+    p.img_height = (uint32_t)info.height;
+    p.img_bitdepth = (uint32_t)info.bit_depth;
+    p.alpha_flag = info.has_alpha != 0;
+  }
+  return ok();
+}
 // Extension (not in libheif): the HIP devices heif_decode_image may use for ONE grid of this context - its tile rows are cut
 // into a slab per listed device (hm_decode_item_devices; context.cc:2361-2401's tile fan-out across GPUs instead of threads).
 // n = 0 restores the default (the calling thread's current device).

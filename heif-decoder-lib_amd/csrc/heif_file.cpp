@@ -65,6 +65,7 @@ bool next_box(Rd& r, Box& b)
 
 const Item* HeifFile::item(uint32_t id) const
 {
+  if (movie_mode_) return id >= 1 && id <= movie_.frame_count ? &movie_.frame : nullptr;
   auto it = items_.find(id);
   return it == items_.end() ? nullptr : &it->second;
 }
@@ -95,6 +96,11 @@ std::vector<uint32_t> HeifFile::top_level_images() const
 {
   // images that are not tiles / thumbnails / auxiliary images of another item
   std::vector<uint32_t> out;
+  if (movie_mode_) { // every sample, in track order (context.cc:664-673)
+    out.resize(movie_.frame_count);
+    for (uint32_t k = 0; k < movie_.frame_count; k++) out[k] = k + 1;
+    return out;
+  }
   for (const auto& kv : items_) {
     const Item& it = kv.second;
     if (it.type != "hvc1" && it.type != "grid") continue;
@@ -117,18 +123,35 @@ bool HeifFile::parse(const uint8_t* data, size_t size, HeifError& err)
   refs_.clear();
   idat_.clear();
   primary_ = 0;
+  movie_mode_ = false;
+  movie_ = Movie();
   Rd r(data, size);
   Box b;
-  bool have_ftyp = false, have_meta = false;
+  bool have_ftyp = false, movie_brand = false;
+  std::vector<Box> metas;
+  const Box* moov = nullptr;
+  Box moov_box;
   while (next_box(r, b)) {
-    if (b.type == "ftyp") have_ftyp = true;
-    else if (b.type == "meta") {
-      if (!parse_meta(b.body, b.size, err)) return false;
-      have_meta = true;
+    if (b.type == "ftyp") {
+      have_ftyp = true;
+      // compatible brands only, not the major brand (Box_ftyp::has_compatible_brand, box.cc:1057-1085)
+      for (size_t o = 8; o + 4 <= b.size; o += 4)
+        if (!std::memcmp(b.body + o, "hevc", 4) || !std::memcmp(b.body + o, "hevx", 4)) movie_brand = true;
     }
+    else if (b.type == "meta") metas.push_back(b);
+    else if (b.type == "moov" && !moov) { moov_box = b; moov = &moov_box; }
   }
+  // the fork's movie mode (file.cc:474-483): the brand and a 'moov' box; 'meta' is then not read (context.cc:435-437)
+  if (movie_brand && moov) {
+    if (!parse_moov(moov->body, moov->size, err)) return false;
+    movie_mode_ = true;
+    primary_ = 1;
+    return true;
+  }
+  for (const Box& m : metas)
+    if (!parse_meta(m.body, m.size, err)) return false;
   if (!have_ftyp) { err = {HM_ERR_BITSTREAM, "no ftyp box: not a HEIF file"}; return false; }
-  if (!have_meta) { err = {HM_ERR_BITSTREAM, "no meta box"}; return false; }
+  if (metas.empty()) { err = {HM_ERR_BITSTREAM, "no meta box"}; return false; }
   if (!primary_ || !items_.count(primary_)) { err = {HM_ERR_BITSTREAM, "no primary item"}; return false; }
   return true;
 }
@@ -334,6 +357,7 @@ bool HeifFile::item_data(uint32_t id, std::vector<uint8_t>& out, HeifError& err)
 
 bool HeifFile::hevc_data(uint32_t id, std::vector<uint8_t>& out, HeifError& err) const
 {
+  if (movie_mode_) return movie_sample(id, out, err);
   const Item* it = item(id);
   if (!it || it->type != "hvc1") { err = {HM_ERR_INVALID_ARG, "item is not an hvc1 image"}; return false; }
   if (!it->props.hvcc.present) { err = {HM_ERR_BITSTREAM, "hvc1 item without hvcC property"}; return false; }
@@ -378,6 +402,188 @@ bool HeifFile::grid_info(uint32_t id, GridInfo& g, HeifError& err) const
   g.height = rd(4 + field);
   g.tiles = references(id, "dimg");
   if ((int)g.tiles.size() != g.rows * g.cols) { err = {HM_ERR_BITSTREAM, "grid: number of dimg references != rows*cols"}; return false; }
+  return true;
+}
+
+// ---- the fork's movie mode ---------------------------------------------------------------------------------------
+// The box layouts below are the fork's parsers (box.cc), which differ from ISO/IEC 14496-12 where noted.  The fork also
+// insists on a 'meta' box beside 'moov' (file.cc:486-553) that it then does not use; a movie file without one is read here.
+
+namespace {
+
+// the first child box of the given type inside a container body (Box::get_child_box)
+bool child(const uint8_t* p, size_t n, const char* type, Box& out)
+{
+  Rd r(p, n);
+  Box b;
+  while (next_box(r, b))
+    if (b.type == type) { out = b; return true; }
+  return false;
+}
+
+} // namespace
+
+bool HeifFile::parse_moov(const uint8_t* p, size_t n, HeifError& err)
+{
+  Movie& M = movie_;
+  auto missing = [&](const char* t) { err = {HM_ERR_BITSTREAM, std::string("movie: no '") + t + "' box"}; return false; };
+  auto truncated = [&](const char* t) { err = {HM_ERR_BITSTREAM, std::string("movie: truncated '") + t + "' box"}; return false; };
+  // every box the fork requires of a movie track (file.cc:557-627), found the way it finds them: first child of its type
+  Box mvhd, trak, tkhd, mdia, mdhd, minf, vmhd, stbl, stsd, hvc1, hvcc, stsz, stts, stsc, stco, stss, ccst;
+  if (!child(p, n, "mvhd", mvhd)) return missing("mvhd");
+  if (!child(p, n, "trak", trak)) return missing("trak");
+  if (!child(trak.body, trak.size, "tkhd", tkhd)) return missing("tkhd");
+  if (!child(trak.body, trak.size, "mdia", mdia)) return missing("mdia");
+  if (!child(mdia.body, mdia.size, "mdhd", mdhd)) return missing("mdhd");
+  if (!child(mdia.body, mdia.size, "minf", minf)) return missing("minf");
+  if (!child(minf.body, minf.size, "vmhd", vmhd)) return missing("vmhd");
+  if (!child(minf.body, minf.size, "stbl", stbl)) return missing("stbl");
+  if (!child(stbl.body, stbl.size, "stsd", stsd)) return missing("stsd");
+  if (stsd.size < 8) return truncated("stsd");
+  if (!child(stsd.body + 8, stsd.size - 8, "hvc1", hvc1)) return missing("hvc1"); // (FullBox header + entry_count, box.cc:1562-1567)
+
+  { // mvhd (box.cc:1214-1249): version 1 has 64-bit times and duration
+    Rd d(mvhd.body, mvhd.size);
+    const int ver = (int)d.u(1); d.skip(3);
+    if (ver == 1) { d.skip(8 + 8 + 4); M.duration = d.u(8); }
+    else { d.skip(4 + 4 + 4); M.duration = d.u(4); }
+    d.skip(4 + 2 + 2 + 8 + 36 + 24 + 4);
+    if (!d.ok) return truncated("mvhd");
+  }
+  { // tkhd (box.cc:1324-1362): width and height are 16.16 fixed point
+    Rd d(tkhd.body, tkhd.size);
+    const int ver = (int)d.u(1); d.skip(3);
+    d.skip(ver == 1 ? 8 + 8 + 4 + 4 + 8 : 4 + 4 + 4 + 4 + 4);
+    d.skip(8 + 2 + 2 + 2 + 2 + 36);
+    const uint32_t w = (uint32_t)d.u(4), h = (uint32_t)d.u(4);
+    if (!d.ok) return truncated("tkhd");
+    M.width = w >> 16; M.height = h >> 16;
+  }
+  const uint8_t* hvc1_children = nullptr;
+  size_t hvc1_children_n = 0;
+  { // hvc1 sample entry (box.cc:1616-1647): the fork reads compressorname as a NUL-terminated string and then skips
+    // 32 - strlen - 1 bytes - 32 bytes in all when the NUL lies within them, a failed read when it does not
+    Rd d(hvc1.body, hvc1.size);
+    d.skip(6 + 2 + 2 + 2 + 12 + 2 + 2 + 4 + 4 + 4 + 2);
+    size_t len = 0;
+    while (d.pos + len < d.n && d.p[d.pos + len]) len++;
+    if (!d.ok || d.pos + len >= d.n || len > 31) return truncated("hvc1");
+    d.skip(32);
+    d.skip(2 + 2); // depth, pre_defined
+    if (!d.ok) return truncated("hvc1");
+    hvc1_children = d.p + d.pos;
+    hvc1_children_n = d.left();
+  }
+  if (!child(hvc1_children, hvc1_children_n, "hvcC", hvcc)) return missing("hvcC");
+  if (!child(hvc1_children, hvc1_children_n, "ccst", ccst)) return missing("ccst");
+  if (!child(stbl.body, stbl.size, "stsz", stsz)) return missing("stsz");
+  if (!child(stbl.body, stbl.size, "stts", stts)) return missing("stts");
+  if (!child(stbl.body, stbl.size, "stsc", stsc)) return missing("stsc");
+  if (!child(stbl.body, stbl.size, "stco", stco)) return missing("stco");
+  if (!child(stbl.body, stbl.size, "stss", stss)) return missing("stss");
+
+  Item& F = M.frame;
+  F.id = 0;
+  F.type = "hvc1";
+  { // hvcC (codecs/hevc.cc:32-110): the arrays are kept apart - frame k takes unit k-1 of each; empty units are dropped
+    HvcC& h = F.props.hvcc;
+    Rd d(hvcc.body, hvcc.size);
+    d.skip(1 + 1 + 4 + 6 + 1 + 2 + 1);
+    h.chroma_format = (int)(d.u(1) & 3);
+    h.bit_depth_luma = (int)(d.u(1) & 7) + 8;
+    h.bit_depth_chroma = (int)(d.u(1) & 7) + 8;
+    d.skip(2);
+    h.length_size = (int)(d.u(1) & 3) + 1;
+    const int arrays = (int)d.u(1);
+    for (int a = 0; a < arrays && d.ok; a++) {
+      d.skip(1);
+      const int nn = (int)d.u(2);
+      std::vector<std::vector<uint8_t>> units;
+      for (int j = 0; j < nn && d.ok; j++) {
+        const size_t len = (size_t)d.u(2);
+        if (d.left() < len) { d.ok = false; break; }
+        if (len) units.emplace_back(d.p + d.pos, d.p + d.pos + len);
+        d.pos += len;
+      }
+      for (const auto& u : units) h.nals.push_back(u);
+      M.nal_arrays.push_back(std::move(units));
+    }
+    if (!d.ok) return truncated("hvcC");
+    h.present = true;
+  }
+  F.props.ispe_width = (int)M.width;
+  F.props.ispe_height = (int)M.height;
+  uint32_t stsz_count = 0;
+  { // stsz (box.cc:1765-1781): entries only when the constant size is 0
+    Rd d(stsz.body, stsz.size);
+    d.skip(4);
+    M.sample_size = (uint32_t)d.u(4);
+    stsz_count = (uint32_t)d.u(4);
+    if (!d.ok) return truncated("stsz");
+    if (M.sample_size == 0) {
+      if (d.left() / 4 < stsz_count) return truncated("stsz");
+      M.entry_size.resize(stsz_count);
+      for (uint32_t k = 0; k < stsz_count; k++) M.entry_size[k] = (uint32_t)d.u(4);
+    }
+  }
+  { // stsc (box.cc:1894-1910): exactly one entry (context.cc:654-676); its samples_per_chunk is the frame count
+    Rd d(stsc.body, stsc.size);
+    d.skip(4);
+    const uint32_t entries = (uint32_t)d.u(4);
+    if (!d.ok || d.left() / 12 < entries) return truncated("stsc");
+    if (entries != 1) { err = {HM_ERR_BITSTREAM, "'stsc' box more than one chunk"}; return false; }
+    d.skip(4);
+    M.frame_count = (uint32_t)d.u(4);
+  }
+  { // stco (box.cc:1944-1952): the fork reads the entry count and the first offset only
+    Rd d(stco.body, stco.size);
+    d.skip(4 + 4);
+    M.chunk_offset = (uint32_t)d.u(4);
+    if (!d.ok) return truncated("stco");
+  }
+  // The fork's stsz lookups (box.cc:1718-1744) index the entries with the sample number unchecked: a table shorter
+  // than the frame count is read out of bounds there - refused here.
+  if (M.sample_size == 0 && stsz_count < M.frame_count) {
+    err = {HM_ERR_BITSTREAM, "movie: 'stsz' has " + std::to_string(stsz_count) + " entries for " + std::to_string(M.frame_count) + " samples"};
+    return false;
+  }
+  if (M.frame_count == 0) { err = {HM_ERR_BITSTREAM, "no primary item"}; return false; } // (image 1 is the primary one)
+  // Every sample holds at least one byte: a track of more samples than the file has bytes cannot lie inside it (and
+  // would make the list of images larger than the file).
+  if (M.frame_count > size_) { err = {HM_ERR_BITSTREAM, "movie: more samples than bytes in the file"}; return false; }
+  if (M.sample_size == 0) {
+    M.sample_start.resize(M.frame_count);
+    uint64_t o = 0;
+    for (uint32_t k = 0; k < M.frame_count; k++) { M.sample_start[k] = o; o += M.entry_size[k]; }
+  }
+  return true;
+}
+
+// what the fork hands its decoder for sample ID `id` (file.cc:1154-1244 with Box_hvcC::get_header, codecs/hevc.cc:196-224):
+// unit id-1 of every hvcC NAL array (the array's last unit when it is shorter), each with a 4-byte length, then the
+// sample's bytes as they are stored
+bool HeifFile::movie_sample(uint32_t id, std::vector<uint8_t>& out, HeifError& err) const
+{
+  const Movie& M = movie_;
+  if (id < 1 || id > M.frame_count) { err = {HM_ERR_INVALID_ARG, "item is not an hvc1 image"}; return false; }
+  out.clear();
+  for (const auto& arr : M.nal_arrays) {
+    // (an empty array: the fork takes unit -1 of it - refused)
+    if (arr.empty()) { err = {HM_ERR_BITSTREAM, "movie: hvcC NAL array without units"}; return false; }
+    const std::vector<uint8_t>& nal = (size_t)(id - 1) < arr.size() ? arr[id - 1] : arr.back();
+    const uint32_t n = (uint32_t)nal.size();
+    out.push_back((uint8_t)(n >> 24)); out.push_back((uint8_t)(n >> 16)); out.push_back((uint8_t)(n >> 8)); out.push_back((uint8_t)n);
+    out.insert(out.end(), nal.begin(), nal.end());
+  }
+  const uint32_t k = id - 1;
+  const uint64_t size = M.sample_size ? M.sample_size : M.entry_size[k];
+  const uint64_t start = (uint64_t)M.chunk_offset + (M.sample_size ? (uint64_t)M.sample_size * k : M.sample_start[k]);
+  // (64-bit sums here; the fork's 32-bit ones could only wrap past 4 GiB)
+  if (start > size_ || size > size_ - start) {
+    err = {HM_ERR_BITSTREAM, "movie: sample " + std::to_string(id) + " lies outside the file (file position " + std::to_string(start) + ")"};
+    return false;
+  }
+  out.insert(out.end(), data_ + start, data_ + start + size);
   return true;
 }
 

@@ -2,6 +2,8 @@
 // Counterpart of the parts of libheif/file.cc, box.cc and codecs/hevc.cc the hot path needs:
 // item locations (iloc), item infos (iinf), references (iref: dimg/auxl/thmb), properties
 // (ipco/ipma: hvcC, ispe, pixi, colr, irot, imir, clap, auxC), primary item (pitm), idat.
+// Movie mode (the fork's image sequences): a 'moov' track of HEVC-intra samples, each sample a top-level image
+// (file.cc:474-483, 1154-1244; context.cc:646-700 of the reference).
 #ifndef HM_HEIF_FILE_H
 #define HM_HEIF_FILE_H
 
@@ -71,6 +73,20 @@ struct GridInfo {
   std::vector<uint32_t> tiles; // item ids, row-major
 };
 
+// The fork's movie mode: ftyp lists the compatible brand 'hevc' or 'hevx' and a 'moov' box exists; 'meta' is then
+// ignored.  Every sample of the (first) track is an image: IDs 1..frame_count, ID 1 the primary one.
+struct Movie {
+  uint32_t frame_count = 0;        // samples_per_chunk of the one 'stsc' entry (context.cc:654-676)
+  uint64_t duration = 0;           // mvhd duration (box.cc:1214-1230)
+  uint32_t width = 0, height = 0;  // tkhd width / height >> 16: every frame's handle size (context.cc:678-700)
+  uint32_t chunk_offset = 0;       // the first 'stco' offset: where sample 0 starts (box.cc:1944-1952)
+  uint32_t sample_size = 0;        // 'stsz' constant size, 0 = per entry
+  std::vector<uint64_t> sample_start; // per-entry 'stsz': start of sample k relative to chunk_offset (prefix sums)
+  std::vector<uint32_t> entry_size;
+  std::vector<std::vector<std::vector<uint8_t>>> nal_arrays; // hvcC NAL arrays of the 'hvc1' sample entry, in order
+  Item frame;                      // what every frame looks like as an item (hvc1, hvcC, ispe = tkhd size)
+};
+
 class HeifFile {
  public:
   // parses the box structure; returns false and fills err on malformed input
@@ -90,11 +106,17 @@ class HeifFile {
   // the auxiliary image that is the alpha channel of image `id` (0 if none): an 'auxl' reference to `id` from an item
   // whose auxC names an alpha type (context.cc:885-945)
   uint32_t alpha_item_of(uint32_t id) const;
+  bool is_movie() const { return movie_mode_; }
+  const Movie& movie() const { return movie_; }
 
  private:
   struct Ref { std::string type; uint32_t from; std::vector<uint32_t> to; };
   bool parse_meta(const uint8_t* p, size_t n, HeifError& err);
   bool parse_iprp(const uint8_t* p, size_t n, HeifError& err);
+  bool parse_moov(const uint8_t* p, size_t n, HeifError& err);
+  bool movie_sample(uint32_t id, std::vector<uint8_t>& out, HeifError& err) const;
+  bool movie_mode_ = false;
+  Movie movie_;
   const uint8_t* data_ = nullptr;
   size_t size_ = 0;
   uint32_t primary_ = 0;

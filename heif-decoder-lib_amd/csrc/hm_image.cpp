@@ -14,6 +14,7 @@
 #include <cstdio>
 #include <cstdlib>
 #include <cstring>
+#include <map>
 #include <memory>
 #include <thread>
 #include <vector>
@@ -365,6 +366,28 @@ int plan_item(const hm_file* f, uint32_t id, ItemPlan& P)
   return HM_OK;
 }
 
+// the failure of a coded picture whose entropy decode (or data) failed, as the image decode reports it
+int tile_failure(const ItemPlan& P, int i) { return hm_fail(P.status[i], "tile %d (item %u): %s", i, P.tiles[i].id, P.messages[i].c_str()); }
+
+// The colour profile a decoded picture carries: what the libde265 plugin attaches from the VUI (decoder_libde265.cc:339-362),
+// unless the item has a 'colr' nclx (context.cc:1844-1852).  heif_nclx_color_profile_set_* (heif.cc:1811-1905) stores
+// "unspecified" for a code point it does not know and returns an error, which the plugin turns into a decoding warning
+// (*warn, HM_WARN_UNKNOWN_*) - or, with strict_decoding, into a failure (HEIF_WARN_OR_FAIL, decoder_libde265.cc:339-357).
+int picture_profile(const hm_pic* h, const hm::Item* ti, int strict, hm::NclxProfile& tp, int& warn)
+{
+  tp = hm::NclxProfile();
+  tp.present = true; tp.primaries = h->colour_primaries; tp.transfer = h->transfer_characteristics;
+  tp.matrix = h->matrix_coeffs; tp.full_range = h->full_range;
+  warn = 0;
+  if (!hm_nclx_code_known(0, tp.primaries)) { tp.primaries = 2; warn |= HM_WARN_UNKNOWN_PRIMARIES; }
+  if (!hm_nclx_code_known(1, tp.transfer)) { tp.transfer = 2; warn |= HM_WARN_UNKNOWN_TRANSFER; }
+  if (!hm_nclx_code_known(2, tp.matrix)) { tp.matrix = 2; warn |= HM_WARN_UNKNOWN_MATRIX; }
+  if (warn && strict)
+    return hm_fail(HM_ERR_BITSTREAM, "Unknown NCLX %s (strict decoding)", (warn & 1) ? "color primaries" : (warn & 2) ? "transfer characteristics" : "matrix coefficients");
+  if (ti && ti->props.colr.present) tp = ti->props.colr;
+  return HM_OK;
+}
+
 // decode_image_planar for an hvc1 item or a grid (context.cc:1729-2020) once the host entropy decode of its coded
 // pictures is done: one GPU batch, then the item's irot / imir / clap.  Asynchronous on `s`.
 // attach: the caller will convert the planes to params->out_format as they come out of this function (no alpha plane, nothing
@@ -377,7 +400,7 @@ int planar_from_blobs(const hm_file* f, ItemPlan& P, const hm_decode_params* par
   hm::HeifError err;
   const int nt = (int)P.tiles.size();
   for (int i = 0; i < nt; i++)
-    if (P.status[i]) return hm_fail(P.status[i], "tile %d (item %u): %s", i, P.tiles[i].id, P.messages[i].c_str());
+    if (P.status[i]) return tile_failure(P, i);
   for (size_t i = 0; i < P.tile_alpha.size(); i++)
     if (P.alpha_status[i]) return hm_fail(P.alpha_status[i], "alpha image of tile %d (item %u): %s", P.tile_alpha[i].tile, P.tile_alpha[i].id, P.alpha_messages[i].c_str());
   const bool is_grid = P.is_grid;
@@ -418,21 +441,12 @@ int planar_from_blobs(const hm_file* f, ItemPlan& P, const hm_decode_params* par
   for (int i = 0; i < nt; i++) {
     const hm_pic* h = reinterpret_cast<const hm_pic*>(P.blobs[i].p);
     const hm::Item* ti = f->file.item(P.tiles[i].id);
-    hm::NclxProfile tp; // what the libde265 plugin attaches (decoder_libde265.cc:339-362) ...
-    tp.present = true; tp.primaries = h->colour_primaries; tp.transfer = h->transfer_characteristics;
-    tp.matrix = h->matrix_coeffs; tp.full_range = h->full_range;
-    // heif_nclx_color_profile_set_* (heif.cc:1811-1905) stores "unspecified" for a code point it does not know and
-    // returns an error, which the plugin turns into a decoding warning - or, with strict_decoding, into a failure
-    // (HEIF_WARN_OR_FAIL, decoder_libde265.cc:339-357).  The warnings of grid tiles die with the tile images.
+    hm::NclxProfile tp;
     int warn = 0;
-    if (!hm_nclx_code_known(0, tp.primaries)) { tp.primaries = 2; warn |= HM_WARN_UNKNOWN_PRIMARIES; }
-    if (!hm_nclx_code_known(1, tp.transfer)) { tp.transfer = 2; warn |= HM_WARN_UNKNOWN_TRANSFER; }
-    if (!hm_nclx_code_known(2, tp.matrix)) { tp.matrix = 2; warn |= HM_WARN_UNKNOWN_MATRIX; }
-    if (warn && params->strict_decoding)
-      return hm_fail(HM_ERR_BITSTREAM, "Unknown NCLX %s (strict decoding)", (warn & 1) ? "color primaries" : (warn & 2) ? "transfer characteristics" : "matrix coefficients");
-    if (!is_grid) I.warnings |= warn;
+    const int prc = picture_profile(h, ti, params->strict_decoding, tp, warn);
+    if (prc) return prc;
+    if (!is_grid) I.warnings |= warn; // (the warnings of grid tiles die with the tile images)
     if (h->concealed_ctbs) I.warnings |= HM_WARN_CONCEALED; // (damaged slice data, HM_PARSE_CONCEAL: of a grid's tiles too - the image is the caller's)
-    if (ti && ti->props.colr.present) tp = ti->props.colr; // ... unless the item has a 'colr' nclx (context.cc:1844-1852)
     if (i == 0) native = tp;
     tile_profile[i] = tp;
   }
@@ -659,66 +673,32 @@ void job_parse_tile(DecodeJob& j, int k, int row_threads)
   int& status = tile_alpha ? P.alpha_status[k] : P.status[k];
   std::string& message = tile_alpha ? P.alpha_messages[k] : P.messages[k];
   Blob& blob = tile_alpha ? P.alpha_blobs[k] : P.blobs[k];
+  parse_picture(j.f, id, j.few_pictures != 0, j.params.strict_decoding, row_threads, blob, status, message);
+}
+
+void parse_picture(const hm_file* f, uint32_t id, bool few_pictures, int strict, int row_threads, Blob& blob, int& status, std::string& message)
+{
   std::vector<uint8_t> data;
   hm::HeifError e;
-  if (!j.f->file.hevc_data(id, data, e)) { status = e.status; message = e.message; return; }
+  if (!f->file.hevc_data(id, data, e)) { status = e.status; message = e.message; return; }
   hm_parse_options po;
   po.annexb = 0; po.threads = row_threads;
-  po.record_order = (j.few_pictures ? HM_RECORDS_SPLIT : HM_RECORDS_AUTO) | (j.params.strict_decoding ? 0 : HM_PARSE_CONCEAL);
+  po.record_order = (few_pictures ? HM_RECORDS_SPLIT : HM_RECORDS_AUTO) | (strict ? 0 : HM_PARSE_CONCEAL);
   const int rc = hm_hevc_parse_opts(data.data(), data.size(), &po, &blob.p, &blob.n);
   if (rc) { status = rc; message = hm_last_error(); }
 }
 
-// Everything after the host entropy decode, queued on j.s without waiting: GPU batch(es), transforms, alpha, colour
-// conversion (HeifContext::decode_image_user, context.cc:1516-1600) and the copy to (pinned) host memory.
-int job_enqueue(DecodeJob& j, hm_decoded* out)
+// The output half of decode_image_user (context.cc:1516-1600) for a decoded image on the device: the result's fields, the colour
+// conversion (unless the batch did it: I.rgb_attached), the alpha plane, and the copy to params->ext_dst or to pinned host
+// planes - all queued on `s`.  `dout` and `alpha_sdr` must live until the stream has drained.
+int emit_image(const hm_decode_params* params, hipStream_t s, PlanarImage& I, const DevPlane* alpha, int alpha_bd, DevMem& dout,
+               DevPlane& alpha_sdr, hm_decoded* out)
 {
-  const hm_file* f = j.f;
-  const hm_decode_params* params = &j.params;
-  hipStream_t s = j.s;
-  std::memset(out, 0, sizeof(*out));
-  j.enqueued = true; // from here on the destructor drains the stream before buffers are released
-  Lap lap;
-  PlanarImage &I = j.I, &A = j.A;
-  int rc = planar_from_blobs(f, j.item[0], params, s, I, /*attach=*/j.n_items == 1);
-  if (rc) return rc;
-  // ---- alpha channel: the auxiliary image's Y plane becomes the alpha plane, scaled nearest-neighbour if its size
-  //      differs (context.cc:2029-2078) ----
-  const DevPlane* alpha = nullptr;
-  if (j.n_items > 1) {
-    if ((rc = planar_from_blobs(f, j.item[1], params, s, A))) return rc;
-    // what the colour ops refuse is refused before more work is queued: an 8-bit image's chain to RGBA has no op that
-    // changes the alpha plane's depth and the interleave wants 8 bits (rgb2rgb.cc:81-84); a deeper image's chain runs
-    // Op_to_sdr_planes, which brings a deeper alpha plane to 8 bits too (hdr_sdr.cc:176-195)
-    if (params->out_format == HM_OUT_RGBA && A.bd != 8 && I.bd == 8) return hm_fail(HM_ERR_UNSUPPORTED, "alpha plane of %d bits with an 8-bit image and an RGBA target", A.bd);
-    // RRGGBBAA: the alpha plane travels through the image's depth op (Op_to_hdr_planes reads every plane as 8 bit) or is
-    // copied as 16-bit words (rgb2rgb.cc:207-211, yuv2rgb.cc:575-592): only planes of the image's own depth class work
-    if ((params->out_format == HM_OUT_RRGGBBAA_BE || params->out_format == HM_OUT_RRGGBBAA_LE) && (A.bd > 8) != (I.bd > 8))
-      return hm_fail(HM_ERR_UNSUPPORTED, "alpha plane of %d bits with a %d-bit image and an RRGGBBAA target", A.bd, I.bd);
-    alpha = &A.P[0];
-    if (A.w != I.w || A.h != I.h) {
-      if ((rc = alloc_plane(j.alpha_scaled, I.w, I.h, A.bd > 8 ? 2 : 1))) return rc;
-      if ((rc = hm_launch_scale_nn(A.bd > 8 ? 2 : 1, A.P[0].mem.p, A.P[0].stride, A.w, A.h, j.alpha_scaled.mem.p, j.alpha_scaled.stride, I.w, I.h, s))) return rc;
-      alpha = &j.alpha_scaled;
-    }
-    out->has_alpha = 1;
-  }
-  else if (I.tile_alpha_bd) {
-    // the canvas' own alpha plane (tiles with alpha images); an alpha image of the grid item itself - handled above -
-    // replaces it (transfer_plane_from_image_as, context.cc:2072)
-    if (params->out_format == HM_OUT_RGBA && I.tile_alpha_bd != 8 && I.bd == 8) return hm_fail(HM_ERR_UNSUPPORTED, "alpha plane of %d bits with an 8-bit image and an RGBA target", I.tile_alpha_bd);
-    if ((params->out_format == HM_OUT_RRGGBBAA_BE || params->out_format == HM_OUT_RRGGBBAA_LE) && (I.tile_alpha_bd > 8) != (I.bd > 8))
-      return hm_fail(HM_ERR_UNSUPPORTED, "alpha plane of %d bits with a %d-bit image and an RRGGBBAA target", I.tile_alpha_bd, I.bd);
-    alpha = &I.tile_alpha;
-    out->has_alpha = 1;
-  }
-  const int alpha_bd = j.n_items > 1 ? A.bd : I.tile_alpha_bd;
-  lap("planar decode queued");
+  int rc;
   DevPlane (&P)[3] = I.P;
   const int img_w = I.w, img_h = I.h, chroma = I.chroma, bd = I.bd;
   const hm::NclxProfile& native = I.native;
   const bool is_grid = I.is_grid;
-  DevMem& dout = j.dout;
 
   out->width = img_w; out->height = img_h; out->bit_depth = bd; out->chroma = chroma;
   out->warnings = I.warnings;
@@ -770,9 +750,9 @@ int job_enqueue(DecodeJob& j, hm_decoded* out)
     if (alpha && params->out_format == HM_OUT_RGBA) {
       const DevPlane* a8 = alpha;
       if (alpha_bd > 8) { // (a deeper image only, see above) Op_to_sdr_planes on the alpha plane
-        if ((rc = alloc_plane(j.alpha_sdr, img_w, img_h, 1))) return rc;
-        if ((rc = hm_launch_to_sdr(alpha->mem.p, alpha->stride, j.alpha_sdr.mem.p, j.alpha_sdr.stride, img_w, img_h, alpha_bd, s))) return rc;
-        a8 = &j.alpha_sdr;
+        if ((rc = alloc_plane(alpha_sdr, img_w, img_h, 1))) return rc;
+        if ((rc = hm_launch_to_sdr(alpha->mem.p, alpha->stride, alpha_sdr.mem.p, alpha_sdr.stride, img_w, img_h, alpha_bd, s))) return rc;
+        a8 = &alpha_sdr;
       }
       if ((rc = hm_launch_set_alpha(dout.p, cd.out_stride, img_w, img_h, a8->mem.p, a8->stride, s))) return rc;
     }
@@ -809,6 +789,56 @@ int job_enqueue(DecodeJob& j, hm_decoded* out)
       if (e != hipSuccess) return hm_check_hip(e, "D2H");
     }
   }
+  return HM_OK;
+}
+
+// Everything after the host entropy decode, queued on j.s without waiting: GPU batch(es), transforms, alpha, colour
+// conversion (HeifContext::decode_image_user, context.cc:1516-1600) and the copy to (pinned) host memory.
+int job_enqueue(DecodeJob& j, hm_decoded* out)
+{
+  const hm_file* f = j.f;
+  const hm_decode_params* params = &j.params;
+  hipStream_t s = j.s;
+  std::memset(out, 0, sizeof(*out));
+  j.enqueued = true; // from here on the destructor drains the stream before buffers are released
+  Lap lap;
+  PlanarImage &I = j.I, &A = j.A;
+  int rc = planar_from_blobs(f, j.item[0], params, s, I, /*attach=*/j.n_items == 1);
+  if (rc) return rc;
+  // ---- alpha channel: the auxiliary image's Y plane becomes the alpha plane, scaled nearest-neighbour if its size
+  //      differs (context.cc:2029-2078) ----
+  const DevPlane* alpha = nullptr;
+  if (j.n_items > 1) {
+    if ((rc = planar_from_blobs(f, j.item[1], params, s, A))) return rc;
+    // what the colour ops refuse is refused before more work is queued: an 8-bit image's chain to RGBA has no op that
+    // changes the alpha plane's depth and the interleave wants 8 bits (rgb2rgb.cc:81-84); a deeper image's chain runs
+    // Op_to_sdr_planes, which brings a deeper alpha plane to 8 bits too (hdr_sdr.cc:176-195)
+    if (params->out_format == HM_OUT_RGBA && A.bd != 8 && I.bd == 8) return hm_fail(HM_ERR_UNSUPPORTED, "alpha plane of %d bits with an 8-bit image and an RGBA target", A.bd);
+    // RRGGBBAA: the alpha plane travels through the image's depth op (Op_to_hdr_planes reads every plane as 8 bit) or is
+    // copied as 16-bit words (rgb2rgb.cc:207-211, yuv2rgb.cc:575-592): only planes of the image's own depth class work
+    if ((params->out_format == HM_OUT_RRGGBBAA_BE || params->out_format == HM_OUT_RRGGBBAA_LE) && (A.bd > 8) != (I.bd > 8))
+      return hm_fail(HM_ERR_UNSUPPORTED, "alpha plane of %d bits with a %d-bit image and an RRGGBBAA target", A.bd, I.bd);
+    alpha = &A.P[0];
+    if (A.w != I.w || A.h != I.h) {
+      if ((rc = alloc_plane(j.alpha_scaled, I.w, I.h, A.bd > 8 ? 2 : 1))) return rc;
+      if ((rc = hm_launch_scale_nn(A.bd > 8 ? 2 : 1, A.P[0].mem.p, A.P[0].stride, A.w, A.h, j.alpha_scaled.mem.p, j.alpha_scaled.stride, I.w, I.h, s))) return rc;
+      alpha = &j.alpha_scaled;
+    }
+    out->has_alpha = 1;
+  }
+  else if (I.tile_alpha_bd) {
+    // the canvas' own alpha plane (tiles with alpha images); an alpha image of the grid item itself - handled above -
+    // replaces it (transfer_plane_from_image_as, context.cc:2072)
+    if (params->out_format == HM_OUT_RGBA && I.tile_alpha_bd != 8 && I.bd == 8) return hm_fail(HM_ERR_UNSUPPORTED, "alpha plane of %d bits with an 8-bit image and an RGBA target", I.tile_alpha_bd);
+    if ((params->out_format == HM_OUT_RRGGBBAA_BE || params->out_format == HM_OUT_RRGGBBAA_LE) && (I.tile_alpha_bd > 8) != (I.bd > 8))
+      return hm_fail(HM_ERR_UNSUPPORTED, "alpha plane of %d bits with a %d-bit image and an RRGGBBAA target", I.tile_alpha_bd, I.bd);
+    alpha = &I.tile_alpha;
+    out->has_alpha = 1;
+  }
+  const int alpha_bd = j.n_items > 1 ? A.bd : I.tile_alpha_bd;
+  lap("planar decode queued");
+  rc = emit_image(params, s, I, alpha, alpha_bd, j.dout, j.alpha_sdr, out);
+  if (rc) return rc;
   lap("colour + D2H queued");
   return HM_OK;
 }
@@ -874,6 +904,209 @@ int hm_decode_item(const hm_file* f, uint32_t id, const hm_decode_params* params
     hm_decoded_free(out);
   }
   return rc;
+}
+
+} // extern "C"
+
+// ---- image sequences: many frames, one batch ------------------------------------------------------------------------
+// The fork decodes the samples of a movie track one by one, each with a fresh decoder (context.cc:1603-1727).  Every sample is an
+// independent intra picture, so hm_decode_sequence puts `count` of them into ONE device batch instead: their entropy decode is
+// spread over the host crew like a grid's tiles, one upload, the reconstruction kernels and the fused tail run once over all
+// frames, and each frame is then copied out on its own.  The colour conversion attached to a batch has one description for
+// all its images (hm_batch_set_colour), so frames are grouped by what that description holds - picture size, depth, chroma
+// format and the colour profile of the VUI - and each group is a batch of its own (a sequence written by one encoder is one
+// group).  Frames whose conversion cannot be attached (native planar output, monochrome pictures) share one batch without
+// conversion, and what converts them runs behind it, per frame, as in hm_decode_item.
+namespace {
+
+struct SeqFrame {
+  ItemPlan P;        // one coded picture
+  PlanarImage I;     // its planes on the device (I.batch stays empty: the group owns the batch)
+  DevMem dout;       // converted pixels when the conversion is not attached
+  DevPlane alpha_sdr; // (unused: frames carry no alpha)
+  hm_colour_desc cd{};
+  bool attach = false;
+  int group = -1;
+};
+
+struct SeqGroup {
+  std::unique_ptr<hm_batch, void (*)(hm_batch*)> batch{nullptr, hm_batch_destroy};
+  std::vector<int> frames;
+  bool attach = false;
+};
+
+} // namespace
+
+extern "C" {
+
+int hm_file_sequence_info(const hm_file* f, hm_sequence_info* info)
+{
+  if (!f || !info) return hm_fail(HM_ERR_INVALID_ARG, "null argument");
+  std::memset(info, 0, sizeof(*info));
+  if (!f->file.is_movie()) return HM_OK;
+  info->is_sequence = 1;
+  info->frame_count = f->file.movie().frame_count;
+  info->duration = f->file.movie().duration;
+  return HM_OK;
+}
+
+int hm_decode_sequence(const hm_file* f, uint32_t first, int32_t count, const hm_decode_params* params, const hm_frame_dest* dests,
+                       hm_decoded* out, int32_t* failed_frame)
+{
+  if (failed_frame) *failed_frame = -1;
+  if (!f || !params || !out) return hm_fail(HM_ERR_INVALID_ARG, "null argument");
+  if (count <= 0) return hm_fail(HM_ERR_INVALID_ARG, "frame count %d", count);
+  for (int k = 0; k < count; k++) std::memset(&out[k], 0, sizeof(out[k]));
+  if (!f->file.is_movie()) return hm_fail(HM_ERR_INVALID_ARG, "the file is not an image sequence");
+  const uint32_t n_frames = f->file.movie().frame_count;
+  if (first < 1 || (uint64_t)first + (uint64_t)count - 1 > n_frames)
+    return hm_fail(HM_ERR_INVALID_ARG, "frames %u..%llu outside 1..%u", first, (unsigned long long)first + count - 1, n_frames);
+  if (params->ext_dst) return hm_fail(HM_ERR_INVALID_ARG, "params->ext_dst: a sequence takes its caller buffers from dests");
+  if (params->out_format) {
+    const int obpp = hm_out_bytes_per_pixel(params->out_format);
+    if (obpp < 0) return obpp;
+  }
+  hipStream_t s = (hipStream_t)params->stream;
+  Lap lap;
+
+  // ---- host: the entropy decode of every frame on the crew (the few-pictures record order below 65 frames, as a
+  //      grid's tiles get it in hm_decode_item) ----
+  std::vector<std::unique_ptr<SeqFrame>> F((size_t)count);
+  for (int k = 0; k < count; k++) {
+    F[k].reset(new SeqFrame());
+    const int rc = plan_item(f, first + (uint32_t)k, F[k]->P);
+    if (rc) { if (failed_frame) *failed_frame = k; return rc; }
+  }
+  const bool few = count <= 64;
+  int nthreads = params->host_threads > 0 ? params->host_threads : 1;
+  const int row_threads = nthreads > count ? nthreads / count : 1;
+  if (nthreads > count) nthreads = count;
+  std::atomic<int> next{0};
+  auto worker = [&]() {
+    for (;;) {
+      const int k = next.fetch_add(1);
+      if (k >= count) break;
+      ItemPlan& P = F[k]->P;
+      parse_picture(f, P.tiles[0].id, few, params->strict_decoding, row_threads, P.blobs[0], P.status[0], P.messages[0]);
+    }
+  };
+  Crew::instance().run(nthreads, worker);
+  lap("sequence: host entropy decode done");
+
+  // ---- every check that can fail on a frame's data, frame by frame in order, before anything is queued: the first broken
+  //      frame fails the call with its own status and message (those of hm_decode_item on it) and no caller buffer is touched ----
+  for (int k = 0; k < count; k++) {
+    SeqFrame& Fr = *F[k];
+    auto fail = [&](int rc) { if (failed_frame) *failed_frame = k; return rc; };
+    if (Fr.P.status[0]) return fail(tile_failure(Fr.P, 0));
+    const hm_pic* h = reinterpret_cast<const hm_pic*>(Fr.P.blobs[0].p);
+    PlanarImage& I = Fr.I;
+    int warn = 0;
+    const int prc = picture_profile(h, f->file.item(Fr.P.id), params->strict_decoding, I.native, warn);
+    if (prc) return fail(prc);
+    I.warnings = warn | (h->concealed_ctbs ? HM_WARN_CONCEALED : 0);
+    I.w = h->width - h->crop_left - h->crop_right; I.h = h->height - h->crop_top - h->crop_bottom;
+    I.chroma = h->chroma_format; I.bd = h->bit_depth_y; I.is_grid = false;
+    if (params->out_format) { // (the request job_enqueue hands to the conversion: a single image keeps its own nclx)
+      const int bps = I.bd > 8 ? 2 : 1, cw = I.chroma == 3 ? I.w : (I.w + 1) / 2;
+      hm_colour_desc& cd = Fr.cd;
+      cd.width = I.w; cd.height = I.h; cd.bit_depth = I.bd; cd.chroma = I.chroma;
+      cd.has_nclx = 1; cd.matrix = I.native.matrix; cd.primaries = I.native.primaries; cd.full_range = I.native.full_range;
+      cd.out_format = params->out_format;
+      cd.chroma_upsampling = params->chroma_upsampling;
+      cd.y_stride = hm_plane_stride(I.w, bps);
+      cd.cb_stride = cd.cr_stride = I.chroma ? hm_plane_stride(cw, bps) : 0;
+      cd.out_stride = hm_plane_stride(I.w, hm_out_bytes_per_pixel(params->out_format));
+      const int pipe = hm_colour_pipeline(&cd); // (the conversion's own refusal, with its message)
+      if (pipe < 0) return fail(pipe);
+      Fr.attach = I.chroma != 0;
+    }
+  }
+
+  // ---- groups: one batch per colour description (see above) ----
+  std::vector<std::unique_ptr<SeqGroup>> groups;
+  {
+    std::map<std::vector<int32_t>, int> index;
+    for (int k = 0; k < count; k++) {
+      SeqFrame& Fr = *F[k];
+      std::vector<int32_t> key{Fr.attach ? 1 : 0};
+      if (Fr.attach) {
+        const hm_colour_desc& cd = Fr.cd;
+        key.insert(key.end(), {cd.width, cd.height, cd.bit_depth, cd.chroma, cd.matrix, cd.primaries, cd.full_range});
+      }
+      auto it = index.find(key);
+      if (it == index.end()) {
+        it = index.emplace(key, (int)groups.size()).first;
+        groups.emplace_back(new SeqGroup());
+        groups.back()->attach = Fr.attach;
+      }
+      Fr.group = it->second;
+      groups[(size_t)it->second]->frames.push_back(k);
+    }
+  }
+  struct Drain { // (declared behind everything the queued work uses: destroyed first, it drains the stream before they go)
+    hipStream_t s; bool on = false;
+    ~Drain() { if (on) hipStreamSynchronize(s); }
+  } drain{s};
+  auto release_all = [&](int rc) {
+    if (drain.on) hipStreamSynchronize(s);
+    for (int k = 0; k < count; k++) { hm_decoded_free(&out[k]); std::memset(&out[k], 0, sizeof(out[k])); }
+    return rc;
+  };
+
+  // ---- device: planes, one batch per group, the conversion attached where it can be ----
+  int rc = HM_OK;
+  for (std::unique_ptr<SeqGroup>& G : groups) {
+    hm_batch* b = nullptr;
+    if ((rc = hm_batch_create(&b))) return release_all(rc);
+    G->batch.reset(b);
+    std::vector<const void*> ys, cbs, crs;
+    std::vector<void*> outs;
+    for (int k : G->frames) {
+      SeqFrame& Fr = *F[k];
+      PlanarImage& I = Fr.I;
+      const int bps = I.bd > 8 ? 2 : 1;
+      const int cw = I.chroma == 3 ? I.w : (I.w + 1) / 2, chh = I.chroma == 1 ? (I.h + 1) / 2 : I.h;
+      if ((rc = alloc_plane(I.P[0], I.w, I.h, bps))) return release_all(rc);
+      if (I.chroma != 0 && ((rc = alloc_plane(I.P[1], cw, chh, bps)) || (rc = alloc_plane(I.P[2], cw, chh, bps)))) return release_all(rc);
+      hm_tile_dest d;
+      std::memset(&d, 0, sizeof(d));
+      for (int c = 0; c < 3; c++) { d.plane[c] = I.P[c].mem.p; d.pitch[c] = I.P[c].stride; }
+      d.canvas_width = I.w; d.canvas_height = I.h;
+      const int idx = hm_batch_add_trusted(b, Fr.P.blobs[0].p, Fr.P.blobs[0].n, &d);
+      if (idx < 0) return release_all(idx);
+      drain.on = true;
+      for (int c = 0; c < 3; c++) // (as hm_decode_item does: the planes' padding leaves the device zeroed)
+        if (I.P[c].mem.p) hipMemsetAsync(I.P[c].mem.p, 0, plane_bytes(I.P[c]), s);
+      if (G->attach) {
+        if ((rc = I.rgb.alloc((size_t)Fr.cd.out_stride * mem_rows(I.h)))) return release_all(rc);
+        ys.push_back(I.P[0].mem.p); cbs.push_back(I.P[1].mem.p); crs.push_back(I.P[2].mem.p); outs.push_back(I.rgb.p);
+      }
+    }
+    if ((rc = hm_batch_upload(b, s))) return release_all(rc);
+    if (G->attach) {
+      const SeqFrame& F0 = *F[(size_t)G->frames[0]];
+      const bool ok = hm_batch_set_colour(b, &F0.cd, (int)G->frames.size(), ys.data(), cbs.data(), crs.data(), outs.data(), 0) == HM_OK;
+      for (int k : G->frames) F[k]->I.rgb_attached = ok;
+    }
+    if ((rc = hm_batch_execute(b, 3, s))) return release_all(rc);
+  }
+  lap("sequence: batches queued");
+  // ---- per frame: the conversion where it was not attached, and the copy out (to the frame's caller buffer if it has one) ----
+  for (int k = 0; k < count; k++) {
+    SeqFrame& Fr = *F[k];
+    hm_decode_params pk = *params;
+    if (dests) { pk.ext_dst = dests[k].ext_dst; pk.ext_dst_len = dests[k].ext_dst_len; pk.ext_dst_stride = dests[k].ext_dst_stride; }
+    if ((rc = emit_image(&pk, s, Fr.I, nullptr, 0, Fr.dout, Fr.alpha_sdr, &out[k]))) return release_all(rc);
+  }
+  lap("sequence: colour + D2H queued");
+  const hipError_t e = hipStreamSynchronize(s);
+  drain.on = false;
+  if (e != hipSuccess) return release_all(hm_check_hip(e, "kernel execution"));
+  for (std::unique_ptr<SeqGroup>& G : groups)
+    if ((rc = hm_batch_check(G->batch.get()))) return release_all(rc);
+  lap("sequence: stream drained");
+  return HM_OK;
 }
 
 } // extern "C"

@@ -121,6 +121,8 @@ int job_plan(DecodeJob& j);
 int job_tile_count(const DecodeJob& j);
 void job_parse_tile(DecodeJob& j, int k, int row_threads = 1); // k = 0 .. job_tile_count - 1 (main image tiles first, then alpha); thread-safe per tile;
                                                                 // row_threads > 1: WPP rows of this picture in parallel (hm_hevc_parse_mt)
+// the entropy decode of one coded picture (hvc1 item or movie sample `id`) into `blob`, or its failure in status / message
+void parse_picture(const hm_file* f, uint32_t id, bool few_pictures, int strict, int row_threads, Blob& blob, int& status, std::string& message);
 int job_enqueue(DecodeJob& j, hm_decoded* out);
 int job_complete(DecodeJob& j, hm_decoded* out);
 

@@ -354,6 +354,37 @@ HM_API void     hm_decoded_free(hm_decoded* d);
 HM_API void     hm_host_free(void* plane);
 
 /* ------------------------------------------------------------------------- */
+/* Image sequences: the fork's movie mode (a 'moov' track of HEVC-intra samples) */
+/* ------------------------------------------------------------------------- */
+
+/* A file whose ftyp lists the compatible brand 'hevc' or 'hevx' and that holds a 'moov' box is read the way the fork reads it
+ * (libheif/file.cc:474-483, context.cc:646-700): every sample of the track is a top-level image, IDs 1..frame_count, ID 1 the
+ * primary one; 'meta' is ignored.  hm_file_image_info, hm_file_item_hevc_data and hm_decode_item work on the frames like on
+ * hvc1 items (width / height: the track header's, the decoded image: the picture's own size). */
+typedef struct hm_sequence_info {
+  int32_t  is_sequence;        /* 1: movie mode                                                               */
+  uint32_t frame_count;        /* samples_per_chunk of the track's one 'stsc' entry                            */
+  uint64_t duration;           /* 'mvhd' duration, in its timescale (libheif_parameters.movie_duration)         */
+} hm_sequence_info;
+/* fills *info; a file that is not a sequence gives is_sequence = 0 (not an error) */
+HM_API int hm_file_sequence_info(const hm_file* f, hm_sequence_info* info);
+/* where one frame of hm_decode_sequence goes: the role of params->ext_dst for that frame (NULL = pinned host memory) */
+typedef struct hm_frame_dest {
+  void*    ext_dst;
+  uint32_t ext_dst_len;
+  uint32_t ext_dst_stride;
+} hm_frame_dest;
+/* Decode frames first .. first + count - 1 of a sequence in ONE device batch on params->stream: their entropy decode shares
+ * params->host_threads, one upload, the reconstruction and filter kernels (and the colour conversion) run once over all
+ * frames; out[k] receives frame first + k exactly as hm_decode_item would give it (free each with hm_decoded_free).
+ * dests (NULL, or `count` entries) replaces params->ext_dst, which must be NULL.  A frame whose data fails fails the call
+ * with that frame's status and message (hm_last_error) before anything is queued - no caller buffer is written -, and
+ * *failed_frame (may be NULL) = its index k; -1 when the failure is not one frame's.  On any failure every out[k] is
+ * empty; after a device failure the caller buffers' contents are undefined. */
+HM_API int hm_decode_sequence(const hm_file* f, uint32_t first, int32_t count, const hm_decode_params* params, const hm_frame_dest* dests,
+                              hm_decoded* out, int32_t* failed_frame);
+
+/* ------------------------------------------------------------------------- */
 /* Pipelined decode: many HEIF files in flight (host parse || H2D || kernels || D2H) */
 /* ------------------------------------------------------------------------- */
 

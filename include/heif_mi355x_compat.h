@@ -128,6 +128,23 @@ HMC_API struct heif_error heif_context_get_image_handle(struct heif_context* ctx
  * single image they go to the decoder (max_decoder_threads -> new_decoder(&dec, nthreads)); here both feed the host
  * entropy decode (tile-parallel for grids, sub-stream parallel inside one picture) */
 HMC_API void heif_context_set_threads(struct heif_context* ctx, const struct heif_image_handle* in_handle, int nthreads);
+/* fork API (heif.h:672-686, 1012; context.cc:459-491): what the fork's Android caller asks before it decodes frame by frame.
+ * The caller allocates img_params for heif_context_get_number_of_top_level_images() entries; the call fills one per top-level
+ * image in list order - the handle's width and height, the luma depth, whether it has an alpha channel.  A movie file (image
+ * sequence: 'moov' track, brand 'hevc' / 'hevx') has movie_flag set, one entry per frame and the 'mvhd' duration. */
+struct image_parameters {
+  bool alpha_flag;
+  uint32_t img_width;
+  uint32_t img_height;
+  uint32_t img_bitdepth;
+};
+struct libheif_parameters {
+  bool movie_flag;
+  uint32_t frame_count;
+  uint32_t movie_duration;
+  struct image_parameters* img_params;
+};
+HMC_API struct heif_error heif_context_get_heif_params(struct heif_context* ctx, struct libheif_parameters* params);
 /* extension of this library (no libheif counterpart): the HIP devices one grid of this context is spread over, a slab of
  * tile rows per listed device (context.cc:2361-2401's fan-out of the tiles, across GPUs); n = 0: the current device */
 HMC_API void heif_mi355x_context_set_devices(struct heif_context* ctx, const int* devices, int n);
