@@ -1720,7 +1720,9 @@ static int launch_chain_impl(const hm_dev_pic* d_pics, int n_pics, int log2_ctb,
   // distance of the old rule, wherever the CTU above-right is available.  Where it is not (a slice that ends in the middle of the row above) a CTU has no
   // such block and a band may finish CTU j while the band above still works on j + 1, whose corner sample lies in j's columns of the line: per hand-over one
   // CTU of distance instead of two.  Two hand-overs (W = 3) are enough; W >= 4 is what runs (the alternating ring, MODE 4, has 2 W - 1 in between: always).
-  // tools/stress_cuts.py hunts for such races (3 600 executes per run in 15 cuts: none, also with the rule forced in the short rings - its tiles are one slice each).
+  // tools/stress_cuts.py hunts for such races (3 600 executes per run in 15 cuts: none, also with the rule forced in the short rings - its tiles were one slice
+  // each; it now also takes tiles whose slices end in the middle of CTU rows: none in 20 runs per cut), and tests/test_chain_modes_gpu.py runs rings of 4 and 8
+  // such bands with the early start on them, 20 executes of one batch.
   L.early = hm_knob(HM_KNOB_CHAIN_EARLY) != 0 && !(ring_w && ring_w < 4 && !alt_kinds()) ? 1 : 0;
 #ifdef HM_CHAIN_EARLY_FORCE // (negative control of tools/stress_cuts.py: the early start also where a ring's line reuse forbids it)
   L.early = 1;

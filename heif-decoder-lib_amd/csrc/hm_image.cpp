@@ -1345,11 +1345,21 @@ static int decode_grid_cut(const hm_file* f, uint32_t id, const hm_decode_params
       if (plan.blobs[i].p && reinterpret_cast<const hm_pic*>(plan.blobs[i].p)->concealed_ctbs) tile_warnings |= HM_WARN_CONCEALED;
     return HM_OK;
   };
-  auto take_blobs = [&](Slab& S) {
+  // (slabs are taken in order: slab 0 - tile 0 of the grid - first)
+  auto take_blobs = [&](Slab& S) -> int {
     const int t_first = S.row0 * plan.cols, t_n = S.rows * plan.cols;
     for (int k = 0; k < t_n; k++) { S.P.blobs[k].p = plan.blobs[t_first + k].p; S.P.blobs[k].n = plan.blobs[t_first + k].n; plan.blobs[t_first + k].p = nullptr; plan.blobs[t_first + k].n = 0; }
     const hm_pic* h0 = reinterpret_cast<const hm_pic*>(S.P.blobs[0].p);
     if (&S == slabs[0].get()) { bd = h0->bit_depth_y; chroma = h0->chroma_format; }
+    // every tile against tile 0 of the WHOLE grid, in the order and with the messages of the one-batch decode (planar_from_blobs
+    // compares a slab's tiles with the slab's own first tile only: a later tile row of another depth or chroma format would
+    // otherwise come back HM_OK under slab 0's metadata)
+    for (int k = 0; k < t_n; k++) {
+      const hm_pic* h = reinterpret_cast<const hm_pic*>(S.P.blobs[k].p);
+      if (h->chroma_format != chroma) return hm_fail(HM_ERR_BITSTREAM, "Image tile has different chroma format than combined image");
+      if (h->bit_depth_y != bd) return hm_fail(HM_ERR_BITSTREAM, "Image tile has different pixel depth than combined image");
+    }
+    return HM_OK;
   };
   auto give_up = [&](int src) { // (whatever is in flight is waited for before the destination goes back)
     for (const std::unique_ptr<Slab>& S : slabs) slab_finish(*S);
@@ -1382,7 +1392,7 @@ static int decode_grid_cut(const hm_file* f, uint32_t id, const hm_decode_params
         for (int i = t_first; i < t_first + t_n; i++)
           if (plan.blobs[i].p && reinterpret_cast<const hm_pic*>(plan.blobs[i].p)->concealed_ctbs) tile_warnings |= HM_WARN_CONCEALED;
         trace_mark("slab parsed, row", S.row0);
-        take_blobs(S);
+        if (const int trc = take_blobs(S)) { parse_rc = trc; parse_msg = hm_last_error(); return; } // (the slabs in front are drained below)
         slab_enqueue(f, params, S, dst + (size_t)S.y0 * dst_stride, dst_stride, img_w);
         if (S.rc) return; // (reported below)
       }
@@ -1425,7 +1435,8 @@ static int decode_grid_cut(const hm_file* f, uint32_t id, const hm_decode_params
   }
   else {
     if ((rc = parse_range(0, nt))) return give_up(rc);
-    for (const std::unique_ptr<Slab>& S : slabs) take_blobs(*S);
+    for (const std::unique_ptr<Slab>& S : slabs)
+      if ((rc = take_blobs(*S))) return give_up(rc);
     // every slab on its device: the first on this thread, the others on threads of their own
     std::vector<std::thread> threads;
     for (size_t k = 1; k < slabs.size(); k++) {

@@ -18,7 +18,7 @@ extern "C" {
 //   chain_ring (-1)        W >= 2: the ring of W waves per picture in one workgroup; 0: never
 //   chain_alt (1)          0: the one-chain waves of a ring keep their kind of chain
 //   chain_np (0)           pictures per workgroup of the wave-per-picture cut
-//   chain_debug (0)        print the launcher's choice to stderr
+//   chain_debug (0)        print the launchers' choices (k_chain, k_residual, k_recon) to stderr
 //   chain_split (1)        0: the partial last round of a wave per picture stays in the one launch; 1 / 2: a launch of its own beside
 //                          the full rounds (queued first / second)
 //   resid_segs (0)         runs of CTUs a row of k_residual is cut into

@@ -32,6 +32,7 @@
 
 #include <hip/hip_runtime.h>
 #include <stdint.h>
+#include <stdio.h>
 #include <stdlib.h>
 #include <type_traits>
 
@@ -464,6 +465,8 @@ extern "C" int hm_launch_recon(const hm_dev_pic* d_pics, int n_pics, int log2_ct
   }
   const int lds_bytes = total(nw);
   const int n_lines = nw > 2 ? nw : 2;
+  if (hm_knob(HM_KNOB_CHAIN_DEBUG)) fprintf(stderr, "[k_recon] %d pictures of CTB %d, %d-byte samples, %d waves per picture%s\n", n_pics, 1 << log2_ctb, pix_bytes, nw,
+                                                rare_syntax ? ", rare syntax" : "");
   if (lds_bytes > 160 * 1024) return hm_fail(HM_ERR_UNSUPPORTED, "CTU staging does not fit LDS (%d bytes)", lds_bytes);
   const void* fn = nullptr;
   // RARE = true: the variant that also carries the rarely used syntax (HM_PIC_RARE_SYNTAX: scaling lists); the

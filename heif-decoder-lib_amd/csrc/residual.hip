@@ -21,6 +21,7 @@
 //     rows), 16x16 / 32x32 blocks in 64-sample trips with the sums cut at the last non-zero row / column.
 // Pictures with rare syntax (scaling lists, PCM, bypass, 4:4:4, range-extension tools) keep their residual inside
 // recon.hip's RARE kernel.  Integer work, HBM traffic = levels in + 2 bytes per residual sample out: no MFMA.
+#include <cstdio>
 #include <cstdlib>
 
 #include "recon_common.h"
@@ -608,6 +609,7 @@ extern "C" int hm_launch_residual(const hm_dev_pic* d_pics, int n_pics, int max_
   units *= segs;
   const long groups = (units + R_WAVES - 1) / R_WAVES;
   if (groups > 0x7FFFFFFFL) return hm_fail(HM_ERR_UNSUPPORTED, "too many CTB rows in one launch");
+  if (hm_knob(HM_KNOB_CHAIN_DEBUG)) fprintf(stderr, "[k_residual] %d pictures, every CTU row in %d segments\n", n_pics, segs);
   int a_n = n_pics, a_h = max_ctb_h;
   void* args[] = {(void*)&d_pics, &a_n, &a_h, &segs};
   hipError_t e = hipLaunchKernel(reinterpret_cast<const void*>(k_residual), dim3((unsigned)groups), dim3(R_WAVES * 64), args, R_TABLES + R_WAVES * R_WAVE, s);

@@ -86,6 +86,25 @@ CASES.update({
     "conf_window_422_10": dict(seed=6100014, width=200, height=136, conf_right=8, conf_bottom=6, chroma_format=2, bit_depth=10),
 })
 
+# slice / tile structure at the bench's tile shape (16 CTU rows of CTB 32: rings of 4 and 8 bands of k_chain get bands of their
+# own): slices that end in the middle of a CTU row - the CTU above-right of the next row's CTUs unavailable, no OP_FAR block
+# in their records -, dependent segments, loop filters stopped at slice / tile borders, uniform and explicit tiles, WPP with
+# slices; 10-bit 4:2:2 with CTB 64 and 4:0:0 with CTB 16; and two rare-syntax tiles (PCM, transquant bypass, scaling lists)
+CASES.update({
+    "tile512_slices": dict(seed=6300001, slices=40, **TILE),
+    "tile512_slices_dependent_nolf": dict(seed=6300002, slices=80, dependent=400, pps_lf_across_slices_off=1, **TILE),
+    "tile512_tiles_uniform_slices": dict(seed=6300003, tile_cols=4, tile_rows=4, lf_across_tiles=0, slices=30, slice_lf_random=1, **TILE),
+    "tile512_tiles_explicit_slices": dict(seed=6300004, tile_cols=3, tile_rows=5, tiles_uniform=0, lf_across_tiles=0, slices=100, dependent=300,
+                                          **TILE),
+    "tile512_wpp_slices": dict(seed=6300005, wpp=1, slices=100, dependent=500, slice_qp_random=1, **TILE),
+    "tile512_422_10_ctb64_tiles": dict(seed=6300006, **dict(TILE, log2_ctb=6), chroma_format=2, bit_depth=10, tile_cols=2, tile_rows=2,
+                                       lf_across_tiles=0, slices=60),
+    "tile512_mono_ctb16_slices": dict(seed=6300007, **dict(TILE, log2_ctb=4), chroma_format=0, slices=50, dependent=300),
+    "tile512_rare": dict(seed=6300008, scaling_list=2, pcm=200, pcm_bits_y=7, pcm_bits_c=6, pcm_loop_filter_disable=0, tq_bypass=150, **TILE),
+    "tile512_rare_422_10_slices": dict(seed=6300009, **dict(TILE, log2_ctb=6), chroma_format=2, bit_depth=10, scaling_list=3, pcm=200,
+                                       pcm_bits_y=9, pcm_bits_c=8, pcm_loop_filter_disable=1, tq_bypass=200, slices=60),
+})
+
 # range-extension coding tools (sps.cc:1375-1390, pps.cc:47-142; slice.cc:3143-3177, 3425-3432, 3565-3655, 3774-3805,
 # 3809-3864, 3928-3957; transform.cc:251-285, 427-466, 566-643; intrapred.cc:307-326 of the reference).  rext_sps bits:
 # 1 transform_skip_rotation, 2 transform_skip_context, 4 implicit_rdpcm, 8 explicit_rdpcm, 16 extended_precision,
@@ -108,7 +127,7 @@ CASES.update({
 # oracle/_ref, and what x86 / ARM users run) filters luma edges between ordinary units with the SSE / NEON kernel, its
 # scalar build leaves them unfiltered (fallback-postfilter.h:85-124 reads the flags with the opposite polarity).  The
 # fixtures and the product follow the SIMD build; tools/make_fixtures.py does not require the scalar build to agree.
-SIMD_BUILD_ONLY = {"pcm_nofilter", "tq_bypass", "yuv444_rare", "slices_444_pcm"}
+SIMD_BUILD_ONLY = {"pcm_nofilter", "tq_bypass", "yuv444_rare", "slices_444_pcm", "tile512_rare"}
 
 
 def stream(name):

@@ -7,6 +7,12 @@ import numpy as np
 def decode_pictures(pkg, blobs, stages=3, dests=None):
     """Decode a batch of command streams on cuda:0; every picture gets its own canvas of the size of its conformance
     window (what a decoder plugin hands out).  Returns list of [Y, Cb, Cr] uint16 arrays."""
+    return decode_pictures_repeatedly(pkg, blobs, stages, 1)[0]
+
+
+def decode_pictures_repeatedly(pkg, blobs, stages=3, executes=1):
+    """decode_pictures with the batch uploaded once and executed `executes` times, the canvases cleared before every execute:
+    a list (one entry per execute) of lists of [Y, Cb, Cr] uint16 arrays."""
     import torch
     capi = pkg.capi
     dev = torch.device("cuda:0")
@@ -34,18 +40,25 @@ def decode_pictures(pkg, blobs, stages=3, dests=None):
         outs.append((planes, bps))
     st = torch.cuda.current_stream().cuda_stream
     batch.upload(st)
-    batch.execute(stages, st)
-    torch.cuda.synchronize()
-    batch.check()
-    res = []
-    for planes, bps in outs:
-        pic = []
-        for (t, pitch, pw, ph) in planes:
-            a = t.cpu().numpy()
-            if bps == 1:
-                pic.append(a[:, :pw].astype(np.uint16))
-            else:
-                pic.append(a[:, :pw * 2].copy().view(np.uint16).reshape(ph, pw))
-        res.append(pic)
+    runs = []
+    for k in range(executes):
+        if k:
+            for planes, _ in outs:
+                for t, *_ in planes:
+                    t.zero_()
+        batch.execute(stages, st)
+        torch.cuda.synchronize()
+        batch.check()
+        res = []
+        for planes, bps in outs:
+            pic = []
+            for (t, pitch, pw, ph) in planes:
+                a = t.cpu().numpy()
+                if bps == 1:
+                    pic.append(a[:, :pw].astype(np.uint16))
+                else:
+                    pic.append(a[:, :pw * 2].copy().view(np.uint16).reshape(ph, pw))
+            res.append(pic)
+        runs.append(res)
     batch.close()
-    return res
+    return runs

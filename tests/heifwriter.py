@@ -53,10 +53,15 @@ def _transform_box(t):
     raise ValueError(kind)
 
 
+def _per(v, k):
+    return v[k] if isinstance(v, (list, tuple)) else v
+
+
 def write_heic(pictures, size, grid=None, chroma_format=1, bit_depth=8, colr=None, sizes=None, transforms=None, aux=None, icc=None,
                tile_transforms=None):
     """pictures: list of [len][NAL] strings (each with VPS/SPS/PPS first); size: (w,h) of one picture
-    (sizes: optional per-picture override of the declared ispe).
+    (sizes: optional per-picture override of the declared ispe; chroma_format / bit_depth: one value for all pictures or a list with
+    one per picture - what their 'hvcC' says).
     grid: None for a single image, or (rows, cols, out_w, out_h).  colr: optional per-tile nclx tuple.
     icc: optional (b"prof" | b"rICC", profile bytes) attached to every coded image item as a second 'colr' box.
     tile_transforms: optional {picture index: [transforms]} - transformative properties of individual grid tile items."""
@@ -76,7 +81,7 @@ def write_heic(pictures, size, grid=None, chroma_format=1, bit_depth=8, colr=Non
         params = [n for n in nals if ((n[0] >> 1) & 0x3F) in (32, 33, 34)]
         vcl = [n for n in nals if ((n[0] >> 1) & 0x3F) not in (32, 33, 34)]
         payload = b"".join(struct.pack(">I", len(n)) + n for n in vcl)
-        a = [0x8000 | prop(_hvcc(params, chroma_format, bit_depth))]  # essential
+        a = [0x8000 | prop(_hvcc(params, _per(chroma_format, k), _per(bit_depth, k)))]  # essential
         a.append(prop(_full(b"ispe", 0, 0, struct.pack(">II", *(sizes[k] if sizes else size)))))
         if colr is not None:
             a.append(prop(_colr(colr)))
@@ -104,13 +109,13 @@ def write_heic(pictures, size, grid=None, chroma_format=1, bit_depth=8, colr=Non
     # by default they belong to the primary item
     for entry in (aux or []):
         lp, asize, urn = entry[:3]
-        aux_cf = entry[3] if len(entry) > 3 else chroma_format  # chroma_format_idc of the auxiliary picture (0 = monochrome)
+        aux_cf = entry[3] if len(entry) > 3 else _per(chroma_format, 0)  # chroma_format_idc of the auxiliary picture (0 = monochrome)
         aid = len(items) + 1
         nals = split_nals(lp)
         params = [n for n in nals if ((n[0] >> 1) & 0x3F) in (32, 33, 34)]
         vcl = [n for n in nals if ((n[0] >> 1) & 0x3F) not in (32, 33, 34)]
         items.append((aid, b"hvc1", b"".join(struct.pack(">I", len(n)) + n for n in vcl)))
-        aux_bd = entry[4] if len(entry) > 4 else bit_depth
+        aux_bd = entry[4] if len(entry) > 4 else _per(bit_depth, 0)
         assoc[aid] = [0x8000 | prop(_hvcc(params, aux_cf, aux_bd)), prop(_full(b"ispe", 0, 0, struct.pack(">II", *asize))),
                       0x8000 | prop(_full(b"auxC", 0, 0, urn.encode() + b"\0"))]
         target = entry[5] if len(entry) > 5 else primary  # item the auxiliary image belongs to (6th element: e.g. a grid tile's item id = picture index + 1)

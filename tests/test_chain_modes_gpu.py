@@ -2,6 +2,7 @@
 chain - must all give the oracle's pictures, for every picture class that can take the split-chain path
 (HM_QUAD_CLASS=1 sends all of them there); and the waits between waves are bounded: with the first band's progress
 withheld (fault injection) the launch is flagged, hm_batch_check reports HM_ERR_INTERNAL, nothing hangs."""
+import json
 import os
 import subprocess
 import sys
@@ -218,3 +219,119 @@ def test_the_launcher_stays_near_the_best_cut(cls):
     rows = json.loads(r.stdout.strip().splitlines()[-1])["rows"]
     for row in rows:
         assert row["ratio"] < 1.15, (cls, row["tiles"], row["ratio"], row["best_forced"], row["auto_ms"], row["best_ms"])
+
+
+# ---- every cut on pictures with structure: several slices (ending in the middle of a CTU row: no OP_FAR block behind the CTUs below
+# the end), dependent segments, HEVC tiles, WPP with slices (chain_mode_check.py: the set `structure`), reconstruction only and in full,
+# against the oracle and the reference decoder's fingerprints.  One process per group of cuts; the stderr of every decode says which
+# cut ran (HM_CHAIN_DEBUG).
+
+# the 8-bit 4:2:0 512 x 512 tiles of CTB 32 with slices: 16 CTU rows, a ring of 4 or 8 bands with one chain each fits one workgroup
+SLICED512 = ["tile512_slices", "tile512_slices_dependent_nolf", "tile512_tiles_uniform_slices", "tile512_tiles_explicit_slices", "tile512_wpp_slices"]
+EARLY = "a CTU starts when the CTU above it is done"
+
+
+def _run_cuts(cuts, *names, env_extra=None, timeout=600):
+    """chain_mode_check.py once per entry of `cuts` (in one process) -> {(entry, picture name): that decode's stderr}"""
+    env = {"HM_CHECK_CUTS": json.dumps(cuts), "HM_CHECK_STAGES": "0,3", "HM_CHAIN_DEBUG": "1", "HM_QUAD_CLASS": "1"}
+    env.update(env_extra or {})
+    r = _run(env, *names, timeout=timeout)
+    assert r.returncode == 0 and "OK" in r.stdout, r.stdout + r.stderr[-4000:]
+    out, key = {}, None
+    for line in r.stderr.splitlines():
+        if line.startswith("[check] cut "):
+            cut, key = int(line.split()[2]), None
+        elif line.startswith("[check] "):
+            key = (cut, line.split()[1])
+            out.setdefault(key, "")
+        elif key is not None:
+            out[key] += line + "\n"
+    assert {c for c, _ in out} == set(range(len(cuts))), sorted(out)
+    return out
+
+
+def _launches(text, kernel="k_chain"):
+    return [ln for ln in text.splitlines() if ln.startswith(f"[{kernel}] ") and " pictures" in ln]
+
+
+def test_every_cut_on_pictures_with_structure():
+    """a wave per picture / per pair of CTU rows / per row / per chain of a row, the last with and without the early CTU start (MODE 5 and 3)"""
+    want = {0: "(one per picture)", 1: "(one per pair of CTU rows)", 2: "(one per CTU row)", 3: "(one per chain of a CTU row)"}
+    cuts = [{"chain_pairs": p, "chain_early": e} for p in (0, 1, 2, 3) for e in (1, 0)]
+    out = _run_cuts(cuts, "structure")
+    for (n, name), text in out.items():
+        p, e = cuts[n]["chain_pairs"], cuts[n]["chain_early"]
+        launches = _launches(text)
+        assert launches, (cuts[n], name, text)
+        mono = "mono" in name
+        for ln in launches:
+            assert want[2 if p == 3 and mono else p] in ln, (cuts[n], name, ln)  # (4:0:0: one chain per row already)
+        # (the early start: the kernels of one chain per wave - a wave per chain, or per row of a 4:0:0 picture)
+        assert (EARLY in text) == (e == 1 and (p == 3 or (p == 2 and mono))), (cuts[n], name, text)
+
+
+def test_waves_that_take_row_pairs_in_turn_on_pictures_with_structure():
+    cuts = [{"chain_share": w} for w in (2, 3, 4)]
+    out = _run_cuts(cuts, "structure")
+    for (n, name), text in out.items():
+        launches = _launches(text)
+        assert launches and not any("(one per picture)" in ln for ln in launches), (cuts[n], name, text)
+        if name.startswith("tile512") and "ctb64" not in name:  # (8 or 32 CTU rows: more pairs than waves)
+            assert all("taking its pairs of CTU rows in turn" in ln for ln in launches), (cuts[n], name, text)
+
+
+def test_rings_on_pictures_with_structure():
+    """rings of 2, 3, 4, 8 bands of row pairs / rows / chains, the one-chain rings also with fixed kinds of chain (chain_alt 0)"""
+    cuts = [{"chain_ring": w, "chain_pairs": p} for p in (1, 2, 3) for w in (2, 3, 4, 8)]
+    cuts += [{"chain_ring": w, "chain_pairs": 3, "chain_alt": 0} for w in (2, 3, 4, 8)]
+    out = _run_cuts(cuts, "structure")
+    for (n, name), text in out.items():
+        c = cuts[n]
+        if name in SLICED512 and c["chain_pairs"] == 3 and "in a ring" in text:  # the early start: alternating rings, rings of at least 4 bands
+            assert (EARLY in text) == (c.get("chain_alt", 1) == 1 or c["chain_ring"] >= 4), (c, name, text)
+    for n in range(len(cuts)):  # (a ring whose waves do not fit one workgroup's LDS falls back to a wave per picture: not every class takes every ring)
+        assert any("in a ring" in text for (k, _), text in out.items() if k == n), cuts[n]
+
+
+def test_early_start_in_non_alternating_rings_on_sliced_tiles():
+    """The configuration the launcher allows by argument only (chain.hip: EARLY): rings of 4 and 8 bands with one chain each and fixed
+    kinds, the early CTU start (MODE 5: a few pictures), on 512 x 512 tiles whose slices end in the middle of CTU rows - where a band may
+    finish CTU j one CTU behind the band above instead of two.  One uploaded batch, 20 executes, every output compared each time."""
+    cuts = [{"chain_ring": w, "chain_pairs": 3, "chain_alt": 0} for w in (4, 8)]
+    out = _run_cuts(cuts, *SLICED512, env_extra={"HM_CHECK_EXECUTES": "20"}, timeout=900)
+    for (n, name), text in out.items():
+        w = cuts[n]["chain_ring"]
+        assert f"a picture's {2 * w} waves in one workgroup" in text and EARLY in text, (cuts[n], name, text)
+
+
+def test_pictures_per_workgroup_on_pictures_with_structure():
+    cuts = [{"chain_np": k} for k in (2, 6, 16)] + [{"chain_np": k, "chain_pairs": p} for p in (1, 3) for k in (2, 6, 16)]
+    out = _run_cuts(cuts, "structure")
+    for n, c in enumerate(cuts):
+        assert any(f", {c['chain_np']} waves per workgroup" in ln for (k, _), text in out.items() if k == n for ln in _launches(text)), c
+
+
+def test_residual_segments_on_pictures_with_structure():
+    cuts = [{"resid_segs": s} for s in (2, 5, 16)]
+    out = _run_cuts(cuts, "structure")
+    for (n, name), text in out.items():
+        launches = _launches(text, "k_residual")
+        assert launches and all(f"in {cuts[n]['resid_segs']} segments" in ln for ln in launches), (cuts[n], name, text)
+
+
+def test_sliced_and_tiled_pictures_of_different_sizes_in_one_launch():
+    cuts = [{}, {"chain_pairs": 1}, {"chain_pairs": 3}, {"chain_share": 3}, {"chain_ring": 4, "chain_pairs": 2},
+            {"chain_ring": 8, "chain_pairs": 3, "chain_alt": 0}, {"chain_ring": 3, "chain_pairs": 3}]
+    out = _run_cuts(cuts, "mixed_structure")
+    for (n, name), text in out.items():
+        assert len(_launches(text)) == 2, (cuts[n], text)  # (one class: one launch per decode - stages 0 and 3)
+        if "chain_ring" in cuts[n]:
+            assert "in a ring" in text, (cuts[n], text)
+
+
+@pytest.mark.parametrize("copies, waves", [(300, 8), (1100, 4), (2048, 2)])
+def test_the_ring_the_launcher_chooses_for_a_sliced_tile(copies, waves):
+    """test_the_ring_the_launcher_chooses on a tile whose slices end in the middle of CTU rows: the resident rings and the rings in rounds"""
+    r = _run({"HM_CHECK_COPIES": str(copies), "HM_CHECK_STAGES": "0,3", "HM_CHAIN_DEBUG": "1"}, "tile512_slices", timeout=900)
+    assert r.returncode == 0 and "OK" in r.stdout, r.stdout + r.stderr[-3000:]
+    assert f"a picture's {waves} waves in one workgroup" in r.stderr, r.stderr[-3000:]

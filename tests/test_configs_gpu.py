@@ -205,6 +205,48 @@ def test_a_broken_tile_fails_the_slabbed_decode_like_the_one_batch_decode(hm_hoo
         assert np.array_equal(got[("img", slab_rows)][0], got[("img", 0)][0])
 
 
+@pytest.mark.parametrize("odd", ["10bit", "422"])
+def test_a_grid_with_tile_rows_of_another_format_fails_however_it_is_cut(hm_hooks, odd):
+    """A grid of 4 tile rows x 2 columns whose last two tile rows are 10-bit (or 4:2:2) must fail as the one-batch decode and the reference
+    (context.cc) fail it - HM_ERR_BITSTREAM, "Image tile has different pixel depth / chroma format than combined image" - however it reaches the
+    device: one batch (grid_slab_rows 0, host_threads >= tiles), slabs of tile rows under the entropy decode (host_threads 1: the default slab
+    height and grid_slab_rows 1 / 2), two slabs through hm_decode_item_devices([0, 0]).  The slabs compared their tiles with their own first
+    tile only: the ones whose tiles agree among themselves came back HM_OK, with slab 0's depth and chroma format."""
+    import ctypes as C
+    L = hm_hooks
+    rows, cols = 4, 2
+    fmt = [dict(bit_depth=10) if odd == "10bit" else dict(chroma_format=2)] * (cols * 2)
+    fmt = [{}] * (cols * 2) + fmt  # (the last two tile rows)
+    tiles = [synthutil.picture(6950000 + t, **dict(TILE, width=256, height=256, **fmt[t]), vui=1, full_range=1, matrix=6) for t in range(rows * cols)]
+    data = heifwriter.write_heic(tiles, (256, 256), grid=(rows, cols, 512, 1024), bit_depth=[f.get("bit_depth", 8) for f in fmt],
+                                 chroma_format=[f.get("chroma_format", 1) for f in fmt])
+    f = pipeline.HeifFile(L, data)
+    L.hm_decode_item_devices.argtypes = [C.c_void_p, C.c_uint32, C.c_void_p, C.POINTER(C.c_int32), C.c_int, C.c_void_p]
+    got = {}
+    try:
+        for slab_rows, threads in ((0, 1), (-1, 8), (-1, 1), (1, 1), (2, 1)):
+            assert L.hm_debug_set(b"grid_slab_rows", slab_rows) == 0
+            prm = pipeline.DecodeParams(10, threads, 0, 0, None, None, 0, 0, 0, 0)
+            d = pipeline.Decoded()
+            rc = L.hm_decode_item(f.h, f.primary(), C.byref(prm), C.byref(d))
+            got[(slab_rows, threads)] = (rc, L.hm_last_error().decode())
+            if rc == 0:
+                L.hm_decoded_free(C.byref(d))
+        assert L.hm_debug_set(b"grid_slab_rows", -1) == 0
+        prm = pipeline.DecodeParams(10, 4, 0, 0, None, None, 0, 0, 0, 0)
+        d = pipeline.Decoded()
+        rc = L.hm_decode_item_devices(f.h, f.primary(), C.byref(prm), (C.c_int32 * 2)(0, 0), 2, C.byref(d))
+        got["devices"] = (rc, L.hm_last_error().decode())
+        if rc == 0:
+            L.hm_decoded_free(C.byref(d))
+    finally:
+        L.hm_debug_set(b"grid_slab_rows", -1)
+        f.close()
+    want = "different pixel depth" if odd == "10bit" else "different chroma format"
+    assert got[(0, 1)][0] == -3 and want in got[(0, 1)][1], got  # HM_ERR_BITSTREAM
+    assert all(v == got[(0, 1)] for v in got.values()), got
+
+
 def test_grids_decoded_by_several_threads_at_once(hm):
     """r06: hm_decode_item on a grid runs a queueing thread of its own beside the parsing crew (slabs under the entropy decode) - three caller
     threads decode three different grids at the same time, four times each: every image equals the one decoded alone (the crew takes one

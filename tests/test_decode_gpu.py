@@ -233,3 +233,70 @@ def test_corrupted_but_parsable_streams(pkg, hm):
             exp, _ = orc.oracle_decode(blob, bits, crop=True)
             for c in range(len(exp)):
                 assert np.array_equal(g[c], exp[c]), f"{tag} stages {bits} plane {c}"
+
+
+# ---- k_recon: the kernel of a picture in decode order (chain_mode_check.py in a process of its own: the launcher's choices on stderr,
+# the waves per picture forced through the test library's knobs)
+
+import re  # noqa: E402
+import subprocess  # noqa: E402
+import sys  # noqa: E402
+
+RARE_SYNTAX = 0x100 | 0x200 | 0x400 | 0x800 | 0x2000 | 0x4000 | 0x8000 | 0x10000 | 0x20000  # HM_PIC_RARE_SYNTAX (hm_stream.h)
+HERE = os.path.dirname(os.path.abspath(__file__))
+
+
+def _check(env_extra, *names, timeout=600):
+    env = dict(os.environ)
+    env.update(env_extra)
+    env["PYTHONPATH"] = os.pathsep.join([os.path.dirname(HERE), HERE, env.get("PYTHONPATH", "")])
+    r = subprocess.run([sys.executable, os.path.join(HERE, "chain_mode_check.py"), *names], env=env, capture_output=True, text=True, timeout=timeout)
+    assert r.returncode == 0 and "OK" in r.stdout, r.stdout + r.stderr[-4000:]
+    return r.stderr
+
+
+def _recon_launches(stderr):
+    """[k_recon] lines -> [(pictures, CTB size, bytes per sample, waves per picture, rare syntax)]"""
+    out = []
+    for m in re.finditer(r"^\[k_recon\] (\d+) pictures of CTB (\d+), (\d)-byte samples, (\d+) waves per picture(, rare syntax)?$", stderr, re.M):
+        out.append((int(m[1]), int(m[2]), int(m[3]), int(m[4]), m[5] is not None))
+    return out
+
+
+def test_decode_order_records_of_ordinary_pictures(pkg):
+    """HM_RECORDS_DECODE_ORDER (a public parse option): an ordinary picture parsed so is a class without rare syntax and without split chains
+    (batch.cpp) - k_recon<Pix, L2, false>, which nothing else launches.  Every non-rare corpus case and the structure sweep, at stages 0 / 1 / 3:
+    the oracle's pictures and the reference decoder's fingerprints; between them all six instantiations ran (8 / 16-bit samples x CTB 16 / 32 / 64),
+    and neither k_residual nor k_chain."""
+    names = [n for n in sorted(corpus.CASES) if not pkg.capi.stream_header(pkg.capi.parse_hevc(corpus.stream(n)))["flags"] & RARE_SYNTAX]
+    assert len(names) > 40
+    err = _check({"HM_CHECK_ORDER": "2", "HM_CHECK_STAGES": "0,1,3", "HM_CHECK_COPIES": "1", "HM_CHAIN_DEBUG": "1"}, *names, "structure_sweep")
+    assert "[k_chain]" not in err and "[k_residual]" not in err, err[-3000:]
+    plain = {(ctb, bps) for _, ctb, bps, _, rare in _recon_launches(err) if not rare}
+    assert plain == {(ctb, bps) for ctb in (16, 32, 64) for bps in (1, 2)}, plain
+
+
+def test_waves_per_picture_of_k_recon():
+    """k_recon with 1, 2, 3, 4, 8 waves per picture (forced: knob recon_waves) on the rare-syntax sweep and the rare-syntax 512 x 512 tiles"""
+    cuts = [{"recon_waves": w} for w in (1, 2, 3, 4, 8)]
+    err = _check({"HM_CHECK_CUTS": json.dumps(cuts), "HM_CHECK_STAGES": "0,3", "HM_CHAIN_DEBUG": "1"}, "rare_sweep", "rare512")
+    parts = err.split("[check] cut ")[1:]
+    assert len(parts) == len(cuts)
+    for c, part in zip(cuts, parts):
+        launches = _recon_launches(part)
+        assert launches and all(rare for *_, rare in launches), part[-2000:]
+        waves = [nw for _, _, _, nw, _ in launches]
+        assert max(waves) <= c["recon_waves"], (c, waves)  # (fewer where a picture has fewer useful waves or the LDS holds fewer)
+        if c["recon_waves"] <= 4:
+            assert c["recon_waves"] in waves, (c, waves)
+
+
+@pytest.mark.parametrize("copies", [300, 1100])
+def test_many_pictures_with_rare_syntax(copies):
+    """k_recon's waves per picture for many pictures (recon.hip: above 256 pictures the count that puts the most waves on a CU, above 1024 four
+    at most): hundreds of copies of the rare-syntax 512 x 512 tiles, every picture the oracle's"""
+    err = _check({"HM_CHECK_COPIES": str(copies), "HM_CHECK_STAGES": "0,3", "HM_CHAIN_DEBUG": "1"}, "rare512", timeout=900)
+    launches = _recon_launches(err)
+    assert {(n, rare) for n, *_, rare in launches} == {(copies, True)}, launches
+    if copies > 1024:
+        assert all(nw <= 4 for _, _, _, nw, _ in launches), launches
