@@ -16,6 +16,11 @@ HM_OUT_RGB, HM_OUT_RGBA, HM_OUT_RRGGBB_BE, HM_OUT_RRGGBB_LE = 10, 11, 12, 14
 HM_OUT_RRGGBBAA_BE, HM_OUT_RRGGBBAA_LE = 13, 15
 HM_PIPE_INT420, HM_PIPE_FLOAT, HM_PIPE_BILINEAR_FLOAT, HM_PIPE_TO_HDR_FLOAT, HM_PIPE_MONO = 1, 2, 3, 4, 5
 HM_PIPE_SDR_INT420, HM_PIPE_FLOAT_SDR, HM_PIPE_FLOAT_HDR = 6, 7, 8
+HM_PIPE_PLANAR = 10
+# planar YCbCr targets; HM_OUT_YCBCR_8BIT: or-ed where no convert_hdr_to_8bit field exists (ColourDesc, pipeline config)
+HM_OUT_YCBCR_420, HM_OUT_YCBCR_422, HM_OUT_YCBCR_444, HM_OUT_YCBCR_8BIT = 0x101, 0x102, 0x103, 0x200
+HM_PLANAR_UNFUSED = 1
+HM_DETAIL_NO_COLOUR_CHAIN = 2
 
 
 class HmError(RuntimeError):
@@ -28,6 +33,11 @@ class ColourDesc(C.Structure):
     _fields_ = [(n, C.c_int32) for n in (
         "width", "height", "bit_depth", "chroma", "has_nclx", "matrix", "primaries",
         "full_range", "out_format", "y_stride", "cb_stride", "cr_stride", "out_stride", "chroma_upsampling", "has_alpha")]
+
+
+class Planes(C.Structure):
+    """hm_planes: Y, Cb, Cr, alpha device pointers and their strides in bytes"""
+    _fields_ = [("plane", C.c_void_p * 4), ("stride", C.c_int32 * 4)]
 
 
 _lib = None
@@ -57,6 +67,7 @@ def lib():
         L.hm_version.restype = C.c_char_p
         L.hm_colour_convert.argtypes = [C.POINTER(ColourDesc), C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]
         L.hm_colour_pipeline.argtypes = [C.POINTER(ColourDesc)]
+        L.hm_colour_convert_planar.argtypes = [C.POINTER(ColourDesc), C.POINTER(Planes), C.c_int, C.POINTER(Planes), C.c_int, C.c_void_p]
         L.hm_ycbcr_coefficients.argtypes = [C.c_int, C.c_int, C.c_int, C.POINTER(C.c_float)]
         bind_decode(L)
         _lib = L

@@ -267,10 +267,11 @@ struct heif_error heif_decode_image(const struct heif_image_handle* in, struct h
   if (opt) {
     prm.ignore_transformations = opt->ignore_transformations;
     if (opt->version >= 3) prm.strict_decoding = opt->strict_decoding; // heif.cc:1100-1103
-    // convert_hdr_to_8bit (heif.cc:1105, context.cc:1550): output_bpp = 8 for convert_colorspace().  Of the targets this
-    // API offers it changes nothing: no conversion runs for a native (undefined / YCbCr) target ("TODO: check BPP
-    // changed", context.cc:1551), interleaved RGB / RGBA are 8 bit whatever is asked, and RRGGBB[AA] targets are "> 8
-    // bit, 10 if the request says 8 or less" (colorconversion.cc:566-585).  Accepted and carried for the record.
+    // convert_hdr_to_8bit (heif.cc:1105, context.cc:1550): output_bpp = 8 for convert_colorspace().  Interleaved RGB / RGBA are
+    // 8 bit whatever is asked and RRGGBB[AA] targets are "> 8 bit, 10 if the request says 8 or less" (colorconversion.cc:566-585);
+    // a planar YCbCr target of another chroma format than the image's comes back with 8-bit planes (Op_to_sdr_planes in the
+    // chain).  A target of the image's own colourspace and chroma format converts nothing, deeper planes included ("TODO: check
+    // BPP changed", context.cc:1551).
     if (opt->version >= 2) prm.convert_hdr_to_8bit = opt->convert_hdr_to_8bit;
     if (opt->decoder_id && std::strcmp(opt->decoder_id, "mi355x") != 0)
       return err(heif_error_Unsupported_feature, heif_suberror_Unsupported_codec, "this build only carries the 'mi355x' HEVC decoder");
@@ -289,8 +290,19 @@ struct heif_error heif_decode_image(const struct heif_image_handle* in, struct h
       default: return err(heif_error_Unsupported_feature, heif_suberror_Unsupported_color_conversion, "only interleaved RGB targets are on the GPU path");
     }
   }
-  else if (!(colorspace == heif_colorspace_undefined || colorspace == heif_colorspace_YCbCr))
+  else if (colorspace == heif_colorspace_undefined || colorspace == heif_colorspace_YCbCr) {
+    // planar YCbCr at the chroma format asked for (context.cc:1538-1564); heif_chroma_undefined: the image's own
+    if (chroma == heif_chroma_420 || chroma == heif_chroma_422 || chroma == heif_chroma_444) {
+      // undefined colourspace = the image's own: a monochrome image then has a monochrome target with a colour chroma format,
+      // for which the pipeline search finds no chain
+      if (colorspace == heif_colorspace_undefined && in->info.chroma == 0)
+        return err(heif_error_Unsupported_feature, heif_suberror_Unsupported_color_conversion, "no colour conversion from a monochrome image to a monochrome target with a colour chroma format");
+      out_format = chroma == heif_chroma_420 ? HM_OUT_YCBCR_420 : (chroma == heif_chroma_422 ? HM_OUT_YCBCR_422 : HM_OUT_YCBCR_444);
+    }
+  }
+  else
     return err(heif_error_Unsupported_feature, heif_suberror_Unsupported_color_conversion, "unsupported target colorspace");
+  const bool planar_out = out_format == 0 || out_format == HM_OUT_YCBCR_420 || out_format == HM_OUT_YCBCR_422 || out_format == HM_OUT_YCBCR_444;
   prm.out_format = out_format;
   const bool want_ext = opt && opt->ext_dst_enable && opt->ext_dst && out_format == heif_chroma_interleaved_RGBA;
   if (want_ext) { prm.ext_dst = opt->ext_dst; prm.ext_dst_len = opt->ext_dst_len; prm.ext_dst_stride = opt->ext_dst_stride; }
@@ -299,7 +311,11 @@ struct heif_error heif_decode_image(const struct heif_image_handle* in, struct h
   const std::vector<int32_t>& devs = in->ctx->devices;
   const int rc = devs.empty() ? hm_decode_item(in->ctx->file, in->id, &prm, &dec)
                               : hm_decode_item_devices(in->ctx->file, in->id, &prm, devs.data(), (int)devs.size(), &dec);
-  if (rc) return from_status(rc);
+  if (rc) {
+    if (rc == HM_ERR_UNSUPPORTED && hm_last_error_detail() == HM_DETAIL_NO_COLOUR_CHAIN) // convert_colorspace() returned no image
+      return err(heif_error_Unsupported_feature, heif_suberror_Unsupported_color_conversion, hm_last_error());
+    return from_status(rc);
+  }
   std::unique_ptr<heif_image> img(new (std::nothrow) heif_image());
   if (!img) { hm_decoded_free(&dec); return err(heif_error_Memory_allocation_error, heif_suberror_Unspecified, "out of memory"); }
   img->width = dec.width; img->height = dec.height;
@@ -310,7 +326,7 @@ struct heif_error heif_decode_image(const struct heif_image_handle* in, struct h
     else p->mem = (uint8_t*)prm.ext_dst;                                                              // external RGBA buffer
     img->planes[ch] = std::move(p);
   };
-  if (out_format == 0) {
+  if (planar_out) { // (dec describes the planes as converted: chroma format, depth, plane sizes)
     // the plugin creates a monochrome image for 4:0:0 pictures (decoder_libde265.cc:97-110)
     img->colorspace = dec.chroma == 0 ? heif_colorspace_monochrome : heif_colorspace_YCbCr;
     img->chroma = (heif_chroma)dec.chroma;

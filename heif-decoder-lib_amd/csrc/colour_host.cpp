@@ -6,6 +6,7 @@
 // Compiled with -ffp-contract=off: the coefficient floats must be produced by the same
 // sequence of binary32 operations as nclx.cc:152-171.
 #include <cmath>
+#include <cstdio>
 #include <cstring>
 
 #include "hm_colour_plan.h"
@@ -83,6 +84,18 @@ hm_colour_desc second_step_desc(const hm_colour_desc* d)
   return n;
 }
 
+} // namespace
+
+int hm_colour_no_chain(const hm_colour_desc* d)
+{
+  char msg[256];
+  std::snprintf(msg, sizeof(msg), "no colour conversion: the reference finds no chain of operations from %d-bit chroma format %d (matrix %d) to output format %d",
+                d->bit_depth, d->chroma, d->has_nclx ? d->matrix : 2, d->out_format);
+  return hm_fail_detail(HM_ERR_UNSUPPORTED, HM_DETAIL_NO_COLOUR_CHAIN, msg);
+}
+
+namespace {
+
 int validate(const hm_colour_desc* d)
 {
   if (!d) return hm_fail(HM_ERR_INVALID_ARG, "null colour descriptor");
@@ -94,6 +107,8 @@ int validate(const hm_colour_desc* d)
 }
 
 } // namespace
+
+int hm_colour_validate(const hm_colour_desc* d) { return validate(d); }
 
 static int convert_planes(const hm_colour_desc* d, const hm_colour_plan& plan, bool own_profile_gone, const void* d_y, const void* d_cb, const void* d_cr,
                           void* d_out, hipStream_t s);
@@ -135,6 +150,39 @@ int hm_ycbcr_coefficients(int has_nclx, int matrix, int primaries, float out[4])
   return HM_OK;
 }
 
+} // extern "C"
+
+void hm_colour_request_of(const hm_colour_desc* d, hm_colour_request* rq)
+{
+  std::memset(rq, 0, sizeof(*rq));
+  rq->chroma = d->chroma; rq->bit_depth = d->bit_depth; rq->has_alpha = d->has_alpha != 0;
+  rq->has_nclx = d->has_nclx != 0; rq->matrix = d->matrix; rq->primaries = d->primaries; rq->transfer = 2; rq->full_range = d->full_range != 0;
+  rq->out_format = d->out_format;
+  if (hm_out_is_planar(d->out_format)) {
+    rq->out_format = d->out_format & ~HM_OUT_YCBCR_8BIT;
+    rq->output_bits = (d->out_format & HM_OUT_YCBCR_8BIT) ? 8 : 0;
+  }
+  rq->forced_bilinear = d->chroma_upsampling == HM_UPSAMPLE_BILINEAR;
+}
+
+void hm_rgb_to_ycbcr_coefficients(int matrix, int primaries, float c[9]) // nclx.cc:175-198, 201-218
+{
+  float Kr, Kb;
+  luma_weights(matrix, primaries, Kr, Kb);
+  if (Kb != 0 || Kr != 0) {
+    c[0] = Kr; c[1] = 1 - Kr - Kb; c[2] = Kb;
+    c[3] = -Kr / (1 - Kb) / 2; c[4] = -(1 - Kr - Kb) / (1 - Kb) / 2; c[5] = 0.5f;
+    c[6] = 0.5f; c[7] = -(1 - Kr - Kb) / (1 - Kr) / 2; c[8] = -Kb / (1 - Kr) / 2;
+  }
+  else {
+    c[0] = 0.299f; c[1] = 0.587f; c[2] = 0.114f;
+    c[3] = -0.168735f; c[4] = -0.331264f; c[5] = 0.5f;
+    c[6] = 0.5f; c[7] = -0.418688f; c[8] = -0.081312f;
+  }
+}
+
+extern "C" {
+
 // the reference's chain for this conversion (colour_search.cpp) as work for the fused kernels
 static int plan_for(const hm_colour_desc* d, hm_colour_plan* plan)
 {
@@ -145,15 +193,10 @@ static int plan_for(const hm_colour_desc* d, hm_colour_plan* plan)
     default: return hm_fail(HM_ERR_UNSUPPORTED, "output format %d", d->out_format);
   }
   hm_colour_request rq;
-  std::memset(&rq, 0, sizeof(rq));
-  rq.chroma = d->chroma; rq.bit_depth = d->bit_depth; rq.has_alpha = d->has_alpha != 0;
-  rq.has_nclx = d->has_nclx != 0; rq.matrix = d->matrix; rq.primaries = d->primaries; rq.transfer = 2; rq.full_range = d->full_range != 0;
-  rq.out_format = d->out_format;
-  rq.forced_bilinear = d->chroma_upsampling == HM_UPSAMPLE_BILINEAR;
+  hm_colour_request_of(d, &rq);
   const int st = hm_colour_make_plan(&rq, plan);
   if (st == HM_PLAN_NO_CHAIN)
-    return hm_fail(HM_ERR_UNSUPPORTED, "no colour conversion: the reference finds no chain of operations from %d-bit chroma format %d (matrix %d) to output format %d",
-                   d->bit_depth, d->chroma, d->has_nclx ? d->matrix : 2, d->out_format);
+    return hm_colour_no_chain(d);
   if (st != HM_PLAN_OK)
     return hm_fail(HM_ERR_UNSUPPORTED, "the reference's chain for %d-bit chroma format %d -> output format %d (%d operations) is not on the GPU path",
                    d->bit_depth, d->chroma, d->out_format, plan->n_ops);
@@ -166,11 +209,7 @@ int hm_colour_chain(const hm_colour_desc* d, int* ops, int max_ops)
   int rc = validate(d);
   if (rc) return rc;
   hm_colour_request rq;
-  std::memset(&rq, 0, sizeof(rq));
-  rq.chroma = d->chroma; rq.bit_depth = d->bit_depth; rq.has_alpha = d->has_alpha != 0;
-  rq.has_nclx = d->has_nclx != 0; rq.matrix = d->matrix; rq.primaries = d->primaries; rq.transfer = 2; rq.full_range = d->full_range != 0;
-  rq.out_format = d->out_format;
-  rq.forced_bilinear = d->chroma_upsampling == HM_UPSAMPLE_BILINEAR;
+  hm_colour_request_of(d, &rq);
   int chain[HM_COLOUR_MAX_OPS];
   const int n = hm_colour_search(&rq, chain);
   for (int i = 0; i < n && i < max_ops; i++) ops[i] = chain[i];
@@ -180,6 +219,10 @@ int hm_colour_chain(const hm_colour_desc* d, int* ops, int max_ops)
 // The chain by its shape (the labels predate the search and stay for callers / tests that ask "which kernels run"):
 int hm_colour_pipeline(const hm_colour_desc* d)
 {
+  if (d && hm_out_is_planar(d->out_format)) { // (the planar executor's own refusals, with their messages)
+    const int rc = hm_colour_planar_check(d);
+    return rc ? rc : HM_PIPE_PLANAR;
+  }
   hm_colour_plan p;
   const int rc = plan_for(d, &p);
   if (rc) return rc;

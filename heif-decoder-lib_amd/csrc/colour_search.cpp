@@ -11,6 +11,7 @@
 // fused kernels.  oracle/pipeline_search.py is the independent restatement the tests hold this one against.
 //
 // Operations are data here (a table of predicates and state edits), not classes: OpKind + one switch.
+#include <cstdio>
 #include <cstring>
 #include <vector>
 
@@ -234,9 +235,10 @@ int hm_colour_search(const hm_colour_request* rq, int ops_out[HM_COLOUR_MAX_OPS]
   if (in.p.transfer == 2) in.p.transfer = 13;
   // target state (colorconversion.cc:534-585)
   CState tg = in;
-  tg.space = SP_RGB;
-  tg.layout = rq->out_format;
-  const bool interleaved = rq->out_format >= L_RGB;
+  const bool planar = hm_out_is_planar(rq->out_format); // planar YCbCr at the requested chroma format, alpha kept
+  tg.space = planar ? SP_YCBCR : SP_RGB;
+  tg.layout = planar ? hm_out_planar_chroma(rq->out_format) : rq->out_format;
+  const bool interleaved = !planar && rq->out_format >= L_RGB;
   tg.alpha = interleaved ? (rq->out_format == L_RGBA || rq->out_format == L_RRGGBBAA_BE || rq->out_format == L_RRGGBBAA_LE) : in.alpha;
   if (rq->output_bits) tg.bits = rq->output_bits;
   if (rq->out_format == L_RGB || rq->out_format == L_RGBA) tg.bits = 8;
@@ -340,4 +342,44 @@ int hm_colour_make_plan(const hm_colour_request* rq, hm_colour_plan* plan)
   if (plan->core == HM_CORE_MONO && (plan->post || plan->bilinear)) return HM_PLAN_UNSUPPORTED;
   if (plan->core == HM_CORE_INT420 && (plan->post || plan->bilinear)) return HM_PLAN_UNSUPPORTED;
   return HM_PLAN_OK;
+}
+
+// The chain of a planar target as the planar executor runs it (colour_planar.cpp): any order of the operations below.
+int hm_colour_make_planar_plan(const hm_colour_request* rq, int ops[HM_COLOUR_MAX_OPS], int* n_ops)
+{
+  *n_ops = 0;
+  const int n = hm_colour_search(rq, ops);
+  if (n < 0) return HM_PLAN_NO_CHAIN;
+  *n_ops = n;
+  for (int i = 0; i < n; i++)
+    switch (ops[i]) {
+      case HM_OP_YCBCR_TO_RGB_8: case HM_OP_YCBCR_TO_RGB_16: case HM_OP_RGB_TO_YCBCR_8: case HM_OP_RGB_TO_YCBCR_16:
+      case HM_OP_MONO_TO_YCBCR420: case HM_OP_DROP_ALPHA_PLANE: case HM_OP_TO_HDR_PLANES: case HM_OP_TO_SDR_PLANES:
+      case HM_OP_BILINEAR_420_8: case HM_OP_BILINEAR_420_16: case HM_OP_BILINEAR_422_8: case HM_OP_BILINEAR_422_16:
+      case HM_OP_AVERAGE_420_8: case HM_OP_AVERAGE_420_16: case HM_OP_AVERAGE_422_8: case HM_OP_AVERAGE_422_16: break;
+      default: return HM_PLAN_UNSUPPORTED;
+    }
+  return HM_PLAN_OK;
+}
+
+const char* hm_colour_op_name(int op)
+{
+  static const char* const names[HM_OP_COUNT] = {
+    "Op_RGB_to_RGB24_32", "Op_RGB24_32_to_RGB", "Op_YCbCr_to_RGB<uint16_t>", "Op_YCbCr_to_RGB<uint8_t>", "Op_YCbCr420_to_RGB24",
+    "Op_YCbCr420_to_RGB32", "Op_YCbCr420_to_RRGGBBaa", "Op_RGB_HDR_to_RRGGBBaa_BE", "Op_RGB_to_RRGGBBaa_BE", "Op_mono_to_YCbCr420",
+    "Op_mono_to_RGB24_32", "Op_RRGGBBaa_swap_endianness", "Op_RRGGBBaa_BE_to_RGB_HDR", "Op_RGB24_32_to_YCbCr", "Op_RGB_to_YCbCr<uint8_t>",
+    "Op_RGB_to_YCbCr<uint16_t>", "Op_RRGGBBxx_HDR_to_YCbCr420", "Op_RGB24_32_to_YCbCr444_GBR", "Op_drop_alpha_plane", "Op_to_hdr_planes",
+    "Op_to_sdr_planes", "Op_YCbCr420_bilinear_to_YCbCr444<uint8_t>", "Op_YCbCr420_bilinear_to_YCbCr444<uint16_t>",
+    "Op_YCbCr422_bilinear_to_YCbCr444<uint8_t>", "Op_YCbCr422_bilinear_to_YCbCr444<uint16_t>", "Op_YCbCr444_to_YCbCr420_average<uint8_t>",
+    "Op_YCbCr444_to_YCbCr420_average<uint16_t>", "Op_YCbCr444_to_YCbCr422_average<uint8_t>", "Op_YCbCr444_to_YCbCr422_average<uint16_t>",
+    "Op_Any_RGB_to_YCbCr_420_Sharp", "Op_RGBA_GENERAL_to_RGB_GENTRAL<uint8_t>", "Op_RGBA_GENERAL_to_RGB_GENTRAL<uint16_t>"};
+  return (op >= 0 && op < HM_OP_COUNT) ? names[op] : "?";
+}
+
+void hm_colour_chain_string(const int* ops, int n, char* buf, int size)
+{
+  int at = 0;
+  buf[0] = 0;
+  for (int i = 0; i < n && at < size - 1; i++)
+    at += std::snprintf(buf + at, (size_t)(size - at), "%s%s", i ? " -> " : "", hm_colour_op_name(ops[i]));
 }

@@ -47,7 +47,8 @@ enum hm_colour_op {
 typedef struct hm_colour_request {
   int chroma, bit_depth, has_alpha;            // the image: HM_CHROMA_*, sample depth, alpha plane present
   int has_nclx, matrix, primaries, transfer, full_range;
-  int out_format;                              // HM_OUT_* (== enum heif_chroma of the interleaved targets)
+  int out_format;                              // HM_OUT_* (== enum heif_chroma of the interleaved targets), or a planar
+                                               // HM_OUT_YCBCR_* code without the HM_OUT_YCBCR_8BIT flag (that is output_bits)
   int output_bits;                             // convert_colorspace()'s output_bpp: 8 with convert_hdr_to_8bit, else 0
   int forced_bilinear;                         // only_use_preferred_chroma_algorithm with bilinear upsampling
 } hm_colour_request;
@@ -67,5 +68,25 @@ typedef struct hm_colour_plan {
 
 int hm_colour_search(const hm_colour_request* rq, int ops_out[HM_COLOUR_MAX_OPS]);
 int hm_colour_make_plan(const hm_colour_request* rq, hm_colour_plan* plan);
+
+// planar YCbCr targets (HM_OUT_YCBCR_*): the chain runs operation by operation (colour_planar.cpp)
+static inline int hm_out_is_planar(int out_format)
+{
+  const int c = out_format & ~HM_OUT_YCBCR_8BIT;
+  return c == HM_OUT_YCBCR_420 || c == HM_OUT_YCBCR_422 || c == HM_OUT_YCBCR_444;
+}
+static inline int hm_out_planar_chroma(int out_format) { return out_format & 3; } // HM_CHROMA_420 / _422 / _444
+// the chain of a planar target; HM_PLAN_UNSUPPORTED when it holds an operation outside the set the planar executor runs
+int hm_colour_make_planar_plan(const hm_colour_request* rq, int ops[HM_COLOUR_MAX_OPS], int* n_ops);
+const char* hm_colour_op_name(int op); // the reference's class name of an hm_colour_op
+// "Op_a -> Op_b" into buf
+void hm_colour_chain_string(const int* ops, int n, char* buf, int size);
+// the request of a descriptor (colour_host.cpp)
+void hm_colour_request_of(const hm_colour_desc* d, hm_colour_request* rq);
+int hm_colour_validate(const hm_colour_desc* d);  // size, depth and chroma format of a descriptor
+int hm_colour_no_chain(const hm_colour_desc* d);  // records "no colour conversion ..." with HM_DETAIL_NO_COLOUR_CHAIN; returns HM_ERR_UNSUPPORTED
+int hm_colour_planar_check(const hm_colour_desc* d); // colour_planar.cpp: HM_OK when hm_colour_convert_planar would run this request
+// RGB_to_YCbCr_coefficients of nclx.cc:175-198, row by row
+void hm_rgb_to_ycbcr_coefficients(int matrix, int primaries, float out[9]);
 
 #endif

@@ -21,6 +21,7 @@
 
 #include "clap.h"
 #include "hm_image_job.h"
+#include "hm_planar.h"
 
 using namespace hm_img;
 
@@ -542,7 +543,7 @@ int planar_from_blobs(const hm_file* f, ItemPlan& P, const hm_decode_params* par
     if (Pl[c].mem.p) hipMemsetAsync(Pl[c].mem.p, 0, plane_bytes(Pl[c]), s);
   if ((rc = hm_batch_upload(batch, s))) return rc;
   I.rgb_attached = false;
-  if (attach && params->out_format != 0 && chroma != 0 && own.empty() && own_alpha.empty() && I.tile_alpha_bd == 0 &&
+  if (attach && params->out_format != 0 && !hm_out_is_planar(params->out_format) && chroma != 0 && own.empty() && own_alpha.empty() && I.tile_alpha_bd == 0 &&
       (params->ignore_transformations || it->props.transforms.empty())) {
     hm_colour_desc cd; // (exactly the request job_enqueue / run_slab would hand to hm_colour_convert)
     std::memset(&cd, 0, sizeof(cd));
@@ -706,8 +707,12 @@ int emit_image(const hm_decode_params* params, hipStream_t s, PlanarImage& I, co
   out->has_nclx = is_grid ? 0 : 1;
   out->primaries = native.primaries; out->transfer = native.transfer; out->matrix = native.matrix; out->full_range = native.full_range;
   hipError_t e;
-  if (params->out_format == 0) { // native planar YCbCr
-    out->out_format = 0;
+  // a planar YCbCr target converts when the image's chroma format or colourspace differs from it, and only then
+  // (context.cc:1538-1552: "different_chroma || different_colorspace"; the depth alone - convert_hdr_to_8bit - does not)
+  const bool planar_target = hm_out_is_planar(params->out_format);
+  const bool as_decoded = params->out_format == 0 || (planar_target && chroma != 0 && chroma == hm_out_planar_chroma(params->out_format));
+  if (as_decoded) { // native planar YCbCr
+    out->out_format = params->out_format;
     for (int c = 0; c < 3; c++) {
       if (!P[c].mem.p) continue; // monochrome image: Y only
       const size_t sz = plane_bytes(P[c]);
@@ -726,6 +731,49 @@ int emit_image(const hm_decode_params* params, hipStream_t s, PlanarImage& I, co
       e = hipMemcpyAsync(out->alpha, alpha->mem.p, sz, hipMemcpyDeviceToHost, s);
       if (e != hipSuccess) return hm_check_hip(e, "D2H");
     }
+  }
+  else if (planar_target) { // the reference's chain to that chroma format, operation by operation (colour_planar.cpp)
+    hm_colour_desc cd;
+    std::memset(&cd, 0, sizeof(cd));
+    cd.width = img_w; cd.height = img_h; cd.bit_depth = bd; cd.chroma = chroma;
+    cd.has_nclx = out->has_nclx; cd.matrix = native.matrix; cd.primaries = native.primaries; cd.full_range = native.full_range;
+    cd.out_format = params->out_format | (params->convert_hdr_to_8bit ? HM_OUT_YCBCR_8BIT : 0);
+    cd.chroma_upsampling = params->chroma_upsampling;
+    cd.has_alpha = alpha ? 1 : 0;
+    cd.y_stride = P[0].stride; cd.cb_stride = P[1].stride; cd.cr_stride = P[2].stride;
+    hm_planar_image src, res;
+    for (int c = 0; c < 3; c++) { src.p[c] = P[c].mem.p; src.stride[c] = P[c].stride; }
+    if (alpha) { src.p[3] = alpha->mem.p; src.stride[3] = alpha->stride; src.alpha_bits = alpha_bd; }
+    std::vector<void*> temps;
+    rc = hm_planar_convert(&cd, &src, nullptr, &res, temps, 0, s);
+    for (void* t : temps) { I.retired.emplace_back(new DevMem()); I.retired.back()->p = t; } // (released once the stream has drained)
+    if (rc) return rc;
+    out->out_format = params->out_format;
+    out->chroma = res.chroma; out->bit_depth = res.bits;
+    for (int c = 0; c < 3; c++) { // (planes the chain passed through are copied from where they are: the decoded image's own)
+      const int pw = c == 0 || res.chroma == 3 ? img_w : (img_w + 1) / 2, ph = c == 0 || res.chroma != 1 ? img_h : (img_h + 1) / 2;
+      const size_t sz = (size_t)res.stride[c] * mem_rows(ph);
+      out->plane[c] = (uint8_t*)hm_pool_pinned_alloc(sz);
+      if (!out->plane[c]) return hm_fail(HM_ERR_NOMEM, "out of memory");
+      out->stride[c] = res.stride[c];
+      e = hipMemcpyAsync(out->plane[c], res.p[c], sz, hipMemcpyDeviceToHost, s);
+      if (e != hipSuccess) return hm_check_hip(e, "D2H");
+      out->plane_width[c] = pw; out->plane_height[c] = ph;
+    }
+    if (res.p[3]) {
+      const size_t sz = (size_t)res.stride[3] * mem_rows(img_h);
+      out->alpha = (uint8_t*)hm_pool_pinned_alloc(sz);
+      if (!out->alpha) return hm_fail(HM_ERR_NOMEM, "out of memory");
+      out->alpha_stride = res.stride[3];
+      e = hipMemcpyAsync(out->alpha, res.p[3], sz, hipMemcpyDeviceToHost, s);
+      if (e != hipSuccess) return hm_check_hip(e, "D2H");
+    }
+    // the converted image carries the output state's profile, as below
+    out->has_nclx = 1;
+    if (is_grid) { out->primaries = 2; out->transfer = 2; out->matrix = 2; out->full_range = 1; }
+    if (out->primaries == 2) out->primaries = 1;
+    if (out->transfer == 2) out->transfer = 13;
+    if (out->matrix == 2) out->matrix = 6;
   }
   else {
     hm_colour_desc cd;
@@ -962,7 +1010,8 @@ int hm_decode_sequence(const hm_file* f, uint32_t first, int32_t count, const hm
   if (first < 1 || (uint64_t)first + (uint64_t)count - 1 > n_frames)
     return hm_fail(HM_ERR_INVALID_ARG, "frames %u..%llu outside 1..%u", first, (unsigned long long)first + count - 1, n_frames);
   if (params->ext_dst) return hm_fail(HM_ERR_INVALID_ARG, "params->ext_dst: a sequence takes its caller buffers from dests");
-  if (params->out_format) {
+  const bool planar_target = hm_out_is_planar(params->out_format);
+  if (params->out_format && !planar_target) {
     const int obpp = hm_out_bytes_per_pixel(params->out_format);
     if (obpp < 0) return obpp;
   }
@@ -1007,7 +1056,18 @@ int hm_decode_sequence(const hm_file* f, uint32_t first, int32_t count, const hm
     I.warnings = warn | (h->concealed_ctbs ? HM_WARN_CONCEALED : 0);
     I.w = h->width - h->crop_left - h->crop_right; I.h = h->height - h->crop_top - h->crop_bottom;
     I.chroma = h->chroma_format; I.bd = h->bit_depth_y; I.is_grid = false;
-    if (params->out_format) { // (the request job_enqueue hands to the conversion: a single image keeps its own nclx)
+    if (planar_target) { // converted frame by frame behind the batch (emit_image); its refusals come here, before anything is queued
+      if (I.chroma == 0 || I.chroma != hm_out_planar_chroma(params->out_format)) {
+        hm_colour_desc& cd = Fr.cd;
+        cd.width = I.w; cd.height = I.h; cd.bit_depth = I.bd; cd.chroma = I.chroma;
+        cd.has_nclx = 1; cd.matrix = I.native.matrix; cd.primaries = I.native.primaries; cd.full_range = I.native.full_range;
+        cd.out_format = params->out_format | (params->convert_hdr_to_8bit ? HM_OUT_YCBCR_8BIT : 0);
+        cd.chroma_upsampling = params->chroma_upsampling;
+        const int pipe = hm_colour_pipeline(&cd);
+        if (pipe < 0) return fail(pipe);
+      }
+    }
+    else if (params->out_format) { // (the request job_enqueue hands to the conversion: a single image keeps its own nclx)
       const int bps = I.bd > 8 ? 2 : 1, cw = I.chroma == 3 ? I.w : (I.w + 1) / 2;
       hm_colour_desc& cd = Fr.cd;
       cd.width = I.w; cd.height = I.h; cd.bit_depth = I.bd; cd.chroma = I.chroma;
@@ -1239,7 +1299,7 @@ static int decode_grid_cut(const hm_file* f, uint32_t id, const hm_decode_params
   const int nt = (int)plan.tiles.size();
   int nthreads = params->host_threads > 0 ? params->host_threads : 1;
   if (nthreads > nt) nthreads = nt;
-  const bool cut = (pipelined || n_devices > 1) && plan.is_grid && plan.rows >= 2 && params->out_format != 0 && hm_out_bytes_per_pixel(params->out_format) > 0 &&
+  const bool cut = (pipelined || n_devices > 1) && plan.is_grid && plan.rows >= 2 && params->out_format != 0 && !hm_out_is_planar(params->out_format) && hm_out_bytes_per_pixel(params->out_format) > 0 &&
                    params->chroma_upsampling == 0 && !f->file.alpha_item_of(id) && plan.tile_alpha.empty() &&
                    (params->ignore_transformations || !it || it->props.transforms.empty()) && ih > 0 && (ih % 2) == 0 && params->stream == nullptr;
   // The whole-grid geometry checks of the one-device path (planar_from_blobs: context.cc:2299-2359) look at the grid BEFORE it is

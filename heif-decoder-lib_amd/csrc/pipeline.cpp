@@ -26,6 +26,7 @@
 
 #include <sched.h>
 
+#include "hm_colour_plan.h"
 #include "hm_image_job.h"
 
 using namespace hm_img;
@@ -204,6 +205,10 @@ int hm_pipeline_submit(hm_pipeline* p, const uint8_t* heif, size_t size, uint32_
     im->job.id = item_id ? item_id : hm_file_primary_item(im->file);
     std::memset(&im->job.params, 0, sizeof(im->job.params));
     im->job.params.out_format = p->cfg.out_format;
+    if (hm_out_is_planar(p->cfg.out_format)) { // hm_decode_params has one encoding: the flag of the config becomes its field
+      im->job.params.out_format = p->cfg.out_format & ~HM_OUT_YCBCR_8BIT;
+      im->job.params.convert_hdr_to_8bit = (p->cfg.out_format & HM_OUT_YCBCR_8BIT) != 0;
+    }
     im->job.params.chroma_upsampling = p->cfg.chroma_upsampling;
     im->job.params.ignore_transformations = p->cfg.ignore_transformations;
     im->job.params.strict_decoding = p->cfg.strict_decoding;

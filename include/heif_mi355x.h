@@ -55,7 +55,8 @@ HM_API const char* hm_last_error(void);
 /* What kind of failure the calling thread's last error was, where callers branch on more than the status: the decoder plugin
  * maps HM_DETAIL_END_OF_DATA - a [length][NAL] record that runs past the pushed bytes - to heif_suberror_End_of_data as the
  * reference's plugin does (libheif/plugins/decoder_libde265.cc:276-292).  Set by the call that failed, HM_DETAIL_NONE otherwise. */
-typedef enum hm_error_detail { HM_DETAIL_NONE = 0, HM_DETAIL_END_OF_DATA = 1 } hm_error_detail;
+typedef enum hm_error_detail { HM_DETAIL_NONE = 0, HM_DETAIL_END_OF_DATA = 1,
+  HM_DETAIL_NO_COLOUR_CHAIN = 2 /* convert_colorspace() finds no chain: heif_suberror_Unsupported_color_conversion */ } hm_error_detail;
 HM_API int hm_last_error_detail(void);
 HM_API const char* hm_version(void);
 /* number of visible HIP devices (0 if none); does not initialise a context */
@@ -69,6 +70,13 @@ HM_API int hm_device_count(void);
 enum {
   HM_CHROMA_MONO = 0, HM_CHROMA_420 = 1, HM_CHROMA_422 = 2, HM_CHROMA_444 = 3,
   HM_OUT_RGB = 10, HM_OUT_RGBA = 11, HM_OUT_RRGGBB_BE = 12, HM_OUT_RRGGBBAA_BE = 13, HM_OUT_RRGGBB_LE = 14, HM_OUT_RRGGBBAA_LE = 15,
+  /* planar YCbCr at the chroma format the caller asks for (heif_colorspace_YCbCr with heif_chroma_420 / _422 / _444): the
+   * decoded planes go through the chain convert_colorspace() finds for that target; a target that equals the image's own
+   * format converts nothing.  Low two bits = HM_CHROMA_* of the target. */
+  HM_OUT_YCBCR_420 = 0x101, HM_OUT_YCBCR_422 = 0x102, HM_OUT_YCBCR_444 = 0x103,
+  /* or-ed to a planar code where no convert_hdr_to_8bit field exists (hm_colour_desc, hm_pipeline_config):
+   * convert_colorspace()'s output_bpp = 8.  hm_decode_params callers may set convert_hdr_to_8bit instead. */
+  HM_OUT_YCBCR_8BIT = 0x200,
 };
 
 typedef struct hm_colour_desc {
@@ -77,7 +85,7 @@ typedef struct hm_colour_desc {
   int32_t chroma;               /* HM_CHROMA_MONO (d_cb / d_cr unused) / _420 / _422 / _444      */
   int32_t has_nclx;             /* 0: image carries no nclx (every grid canvas) => defaults     */
   int32_t matrix, primaries, full_range; /* the attached nclx (ignored when !has_nclx)          */
-  int32_t out_format;           /* HM_OUT_*                                                     */
+  int32_t out_format;           /* HM_OUT_* (a planar HM_OUT_YCBCR_* code: hm_colour_convert_planar only)  */
   int32_t y_stride, cb_stride, cr_stride, out_stride; /* bytes                                  */
   int32_t chroma_upsampling;    /* 0 / HM_UPSAMPLE_NEAREST: whatever convert_colorspace() would pick (nearest
                                    neighbour ops); HM_UPSAMPLE_BILINEAR: the caller set
@@ -97,7 +105,8 @@ enum { HM_PIPE_INT420 = 1, HM_PIPE_FLOAT = 2, HM_PIPE_BILINEAR_FLOAT = 3, HM_PIP
        HM_PIPE_SDR_INT420 = 6,  /* Op_to_sdr_planes -> Op_YCbCr420_to_RGB24/32: > 8-bit full-range 4:2:0 to 8-bit RGB      */
        HM_PIPE_FLOAT_SDR = 7,   /* Op_YCbCr_to_RGB<u16> -> Op_to_sdr_planes -> Op_RGB_to_RGB24_32: other > 8-bit images     */
        HM_PIPE_FLOAT_HDR = 8,   /* Op_YCbCr_to_RGB<u8> -> Op_to_hdr_planes -> Op_RGB_HDR_to_RRGGBBaa_BE [-> swap]          */
-       HM_PIPE_GENERIC = 9 };   /* any other combination of [depth change] [bilinear] core op [depth change]               */
+       HM_PIPE_GENERIC = 9,     /* any other combination of [depth change] [bilinear] core op [depth change]               */
+       HM_PIPE_PLANAR = 10 };   /* a planar HM_OUT_YCBCR_* target: the chain runs operation by operation (hm_colour_convert_planar) */
 HM_API int hm_colour_pipeline(const hm_colour_desc* d); /* HM_PIPE_* or negative status */
 /* the chain itself: the reference's operations by their position in its pool (ColorConversionPipeline::init_ops,
  * colorconversion.cc:218-255); returns the number of operations (0: nothing to convert), -1 when there is no chain */
@@ -105,7 +114,7 @@ HM_API int hm_colour_chain(const hm_colour_desc* d, int* ops, int max_ops);
 
 /* Observable libheif plane stride for a plane `width` pixels wide (pixelimage.cc:139-218). */
 HM_API int hm_plane_stride(int width, int bytes_per_pixel);
-/* bytes per output pixel of an HM_OUT_* format (3,4,6,8) */
+/* bytes per output pixel of an interleaved HM_OUT_* format (3,4,6,8); the planar codes have none (HM_ERR_UNSUPPORTED) */
 HM_API int hm_out_bytes_per_pixel(int out_format);
 
 /* float32 coefficients exactly as nclx.cc:152-171 computes them: r_cr, g_cb, g_cr, b_cb */
@@ -119,6 +128,27 @@ HM_API int hm_colour_convert(const hm_colour_desc* d, const void* d_y, const voi
  * pointers (host arrays).  The integer 4:2:0 chain covers up to 32 images per kernel launch. */
 HM_API int hm_colour_convert_batch(const hm_colour_desc* d, int n, const void* const* d_y, const void* const* d_cb,
                                    const void* const* d_cr, void* const* d_out, void* stream);
+
+/* Planar targets (d->out_format = HM_OUT_YCBCR_* [| HM_OUT_YCBCR_8BIT]): device planes to device planes through the
+ * reference's chain for that target, operation by operation - chroma up-sampling (bilinear) and down-sampling (average),
+ * Op_YCbCr_to_RGB / Op_RGB_to_YCbCr on planes, Op_mono_to_YCbCr420, the depth changes.  A chain that holds any other
+ * operation is refused with HM_ERR_UNSUPPORTED and a message that names it; no chain: HM_ERR_UNSUPPORTED with
+ * hm_last_error_detail() == HM_DETAIL_NO_COLOUR_CHAIN.
+ * in / out: [0..2] Y, Cb, Cr, [3] the alpha plane (NULL: none; d->has_alpha says whether the image has one, and a
+ * depth change converts it like the others).  in_alpha_bits: the alpha plane's sample depth (0 = the image's); the
+ * planes of `out` have the target's size and depth: chroma (w+1)/2 and (h+1)/2 where sub-sampled, 8 bits with
+ * HM_OUT_YCBCR_8BIT, else d->bit_depth; d->y_stride / cb_stride / cr_stride describe `in`.  Quirk kept from
+ * Op_YCbCr444_to_YCbCr422_average (chroma_sampling.cc:398-403): with an odd width the reference never writes the last
+ * chroma sample of the last row; the copied sample is written there.
+ * flags: HM_PLANAR_UNFUSED runs Op_YCbCr_to_RGB -> Op_RGB_to_YCbCr as two kernels over planar RGB instead of the
+ * fused one (same pixels; the checker's second path).  Asynchronous on `stream` except for chains that need
+ * temporaries, which return after the stream has drained. */
+typedef struct hm_planes {
+  void*   plane[4];
+  int32_t stride[4];
+} hm_planes;
+enum { HM_PLANAR_UNFUSED = 1 };
+HM_API int hm_colour_convert_planar(const hm_colour_desc* d, const hm_planes* in, int in_alpha_bits, const hm_planes* out, int flags, void* stream);
 
 /* ------------------------------------------------------------------------- */
 /* Host entropy decode: HEVC intra picture -> GPU command stream (hm_stream.h) */
@@ -285,7 +315,8 @@ typedef struct hm_image_info {
 } hm_image_info;
 
 typedef struct hm_decode_params {
-  int32_t out_format;          /* 0 = native planar YCbCr, else HM_OUT_* (== enum heif_chroma)   */
+  int32_t out_format;          /* 0 = native planar YCbCr, else HM_OUT_* (interleaved: == enum heif_chroma; planar:
+                                  HM_OUT_YCBCR_420 / _422 / _444)                                  */
   int32_t host_threads;        /* entropy-decode threads (heif_context_set_threads semantics)    */
   int32_t ignore_transformations;
   int32_t chroma_upsampling;   /* 0 = default op selection, HM_UPSAMPLE_BILINEAR = forced bilinear (see hm_colour_desc) */
@@ -310,7 +341,7 @@ typedef struct hm_decoded {
   /* alpha channel of the image (an auxiliary image item, context.cc:2029-2078): interleaved RGBA output carries it in
    * byte 3; native planar output gets it as a fourth plane (same size as the image, same sample width) */
   int32_t has_alpha;
-  uint8_t* alpha;              /* pinned host memory like plane[], NULL unless out_format == 0 && has_alpha */
+  uint8_t* alpha;              /* pinned host memory like plane[], NULL unless has_alpha and the output is planar */
   int32_t alpha_stride;
   int32_t warnings;            /* HM_WARN_*: what heif_image_get_decoding_warnings reports (heif.cc:1223-1245)     */
 } hm_decoded;
