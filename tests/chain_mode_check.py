@@ -4,7 +4,9 @@ Prints OK, or the first difference; exit status 0 / 1; 3 = hm_batch_check report
 
 Besides corpus names and the special pictures below, the arguments may name a SET of corpus pictures: `structure` (several slices,
 dependent segments, tiles, WPP with slices, conformance windows - the non-rare structure cases and the 512 x 512 tiles with
-structure), `rare512` (the rare-syntax 512 x 512 tiles).  A picture of the corpus is also held against the reference decoder's
+structure), `rare512` (the rare-syntax 512 x 512 tiles); `extreme_sweep`, `extreme512`, `extreme_large` are the pictures of
+corpus.extreme_sweep / extreme_tiles / extreme_large; every picture of `extreme_sweep` is also held against the fingerprints of the
+reference's scalar build (tests/golden/extreme.json).  A picture of the corpus is also held against the reference decoder's
 fingerprint of it (tests/golden/synth.json) at stages 0, 1 and 3.  More variables of the environment:
   HM_CHECK_COPIES    copies of every picture in its batch (default 3)
   HM_CHECK_STAGES    the stages to run, comma-separated (default 3)
@@ -26,6 +28,7 @@ import orc
 
 HERE = os.path.dirname(os.path.abspath(__file__))
 SYNTH = json.load(open(os.path.join(HERE, "golden", "synth.json")))
+EXTREME = json.load(open(os.path.join(HERE, "golden", "extreme.json")))["cases"]  # corpus.extreme_sweep: the reference's scalar build
 STAGE_NAMES = {0: "recon", 1: "deblock", 3: "full"}
 
 TILE512_STRUCTURE = ["tile512_slices", "tile512_slices_dependent_nolf", "tile512_tiles_uniform_slices", "tile512_tiles_explicit_slices",
@@ -81,6 +84,10 @@ def main():
         elif name == "structure_sweep":  # slices, tiles, WPP of every chroma format, depth and CTB size in one batch
             import synthutil
             batches[name] = [parse(synthutil.picture(seed, **kw)) for seed, kw in corpus.structure_sweep(64)]
+        elif name in ("extreme_sweep", "extreme512", "extreme_large"):  # levels / QPs / scaling factors at the edges of the residual arithmetic
+            import synthutil
+            cases = {"extreme_sweep": lambda: corpus.extreme_sweep(len(EXTREME)), "extreme512": corpus.extreme_tiles, "extreme_large": corpus.extreme_large}[name]()
+            batches[name] = [parse(synthutil.picture(seed, **kw)) for seed, kw in cases] * (1 if name == "extreme_sweep" else copies)
         elif name == "mixed":  # pictures of one class and different sizes in one launch (the cut follows the tallest; short ones leave waves idle)
             batches[name] = [parse(corpus.stream(n)) for n in ("tile512_a", "ragged", "dense_lowqp", "no_deblock", "tile512_b", "ragged")] * 2
         elif name == "mixed_structure":  # ... the same with slices, dependent segments, tiles and WPP with slices (8-bit 4:2:0, CTB 32)
@@ -124,6 +131,13 @@ def main():
                 if name in corpus.CASES and stages in STAGE_NAMES and fingerprint(runs[0][0]) != SYNTH[name][STAGE_NAMES[stages]]:
                     print(f"{tag}{name}: stages {stages}: not the reference decoder's fingerprint")
                     return 1
+                # every picture of the extreme sweep against the fingerprint of the reference's scalar build - in whatever record order
+                # HM_CHECK_ORDER forced, which the CPU suite's comparison of parser + oracle with the reference does not cover
+                if name == "extreme_sweep" and stages in STAGE_NAMES:
+                    for (seed, _), pic in zip(corpus.extreme_sweep(len(EXTREME)), runs[0]):
+                        if fingerprint(pic) != EXTREME[str(seed)][STAGE_NAMES[stages]]:
+                            print(f"{tag}{name}: stages {stages}: seed {seed}: not the fingerprint of the reference's scalar build")
+                            return 1
     print("OK")
     return 0
 

@@ -221,3 +221,107 @@ def rext_large():
                              rext_sps=[7, 135, 167, 39][i % 4], log2_max_ts=5, tq_bypass=[0, 300][i % 2], cross_component=int(i % 4 in (0, 2)),
                              chroma_qp_list=[0, 3][i % 2], big_levels=200, wpp=i % 2, qp=[24, 30, 36][i % 3], max_th_depth_intra=[0, 1, 2][i % 3]))
             for i in range(12)]
+
+
+def extreme_sweep(n, first_seed=13000, pcmf_8bit=False):
+    """(seed, parameters) of a seeded sweep over the arithmetic edges of the residual path: levels over the whole range a
+    conforming stream may carry (level_span), QpY over -QpBdOffset .. 51 with its wrap (qp_span), scaling matrices pinned
+    at 1 and 255 (scaling_span) - crossed with what selects a kernel path: bit depth, chroma format, CTB size, slice QP
+    (1 / 26 / 51), 16x16 and 32x32 blocks (no_split), density from DC-only blocks to every group of four, transform skip
+    (rotation, context, implicit RDPCM, blocks up to 32x32), persistent Rice, cross-component prediction, scaling lists, PCM
+    and transquant bypass next to ordinary units.  The reference's SCALAR build is the ground truth (tests/golden/
+    extreme.json): its SIMD build differs where 16-bit saturating instructions round otherwise.
+    8-bit pictures whose draws hold transquant bypass or unfiltered PCM (9 of the first 144 cases) take the reference's "pcmf"
+    deblocking branch, where its two builds disagree and the product follows the SIMD build (SIMD_BUILD_ONLY above): in the
+    sweep proper they run without those two tools (which run at 10 and 12 bit); pcmf_8bit=True returns exactly these cases WITH
+    their draws - the residual is held against the scalar build at the reconstruction stage, where the builds' deblocking
+    does not enter, and the kernels against the oracle at every stage."""
+    out = []
+    for seed in range(first_seed, first_seed + n):
+        r = seed * 2654435761 % (1 << 32)
+        i = seed - first_seed
+        pick = lambda k, opts: opts[(r >> k) % len(opts)]
+        # (the three depths, four chroma formats and three CTB sizes in turn: all 36 combinations within 36 cases)
+        kw = dict(bit_depth=[8, 10, 12][i % 3], chroma_format=[1, 3, 0, 2][(i // 3) % 4], log2_ctb=[5, 4, 6][(i // 12) % 3],
+                  width=pick(0, [64, 96, 128, 72]), height=pick(2, [64, 40, 96, 72]), qp=pick(4, [1, 26, 51, 26, 12, 40]),
+                  no_split=pick(7, [0, 1, 0]), density=pick(9, [3, 20, 60, 100, 90]), transform_skip=pick(12, [1, 0, 1]),
+                  scaling_list=pick(14, [0, 0, 2, 3, 0]), scaling_span=500, cu_qp_delta=1, qp_span=pick(17, [1, 1, 0]),
+                  diff_cu_qp_delta_depth=pick(18, [1, 0, 2]), level_span=pick(20, [60, 250, 600, 1000]),
+                  rext_sps=pick(22, [0, 1 | 2 | 4, 128, 0, 1 | 2 | 4 | 128, 4, 1]), log2_max_ts=pick(25, [0, 0, 3, 5]),
+                  pcm=pick(27, [0, 0, 150]), tq_bypass=pick(29, [0, 0, 200]), wpp=pick(31, [0, 1]), sign_hiding=pick(6, [1, 1, 0]))
+        kw["cross_component"] = int(kw["chroma_format"] == 3 and seed % 3 != 0)
+        kw["diff_cu_qp_delta_depth"] = min(kw["diff_cu_qp_delta_depth"], kw["log2_ctb"] - 3)
+        if (i // 36) % 2 == 0:
+            # every other run of 36 cases: no rare syntax, so that whatever is not 4:4:4 takes the split chains (k_residual + k_chain);
+            # the others go out in decode order (k_recon)
+            kw.update(scaling_list=0, pcm=0, tq_bypass=0, log2_max_ts=0, rext_sps=kw["rext_sps"] & 128)
+        if not kw["transform_skip"]:
+            kw["log2_max_ts"] = 0
+        if kw["pcm"]:
+            kw.update(pcm_bits_y=max(1, kw["bit_depth"] - seed % 3), pcm_bits_c=max(1, kw["bit_depth"] - seed % 4), pcm_loop_filter_disable=seed % 2)
+        pcmf = kw["bit_depth"] == 8 and bool(kw["tq_bypass"] or (kw["pcm"] and kw["pcm_loop_filter_disable"]))
+        if pcmf_8bit:
+            if pcmf:
+                out.append((seed, kw))
+            continue
+        if kw["bit_depth"] == 8:
+            kw.update(tq_bypass=0, pcm_loop_filter_disable=0)  # (the "pcmf" branch: see above)
+        out.append((seed, kw))
+    return out
+
+
+def single_ctb_cases(n_per_shape, first_seed=14000, n_wrap_per_shape=60):
+    """(seed, parameters) of pictures of ONE CTB whose first transform block of every component has no neighbours at all: every intra
+    mode then predicts the constant 1 << (bit_depth - 1) (8.4.4.2.2), and the block's samples are clip(that + residual) -
+    the residual arithmetic alone, observable (tests/residual_ref.py).  The smallest pictures that hold a first block of 4x4
+    (8x8 picture, NxN allowed), 8x8, 16x16 (no_split) and 32x32 (32x32 and 64x64 pictures: CTB 32 and CTB 64), every bit depth
+    and chroma format, the slice QP over its whole range, flat scaling and pinned scaling lists, transform skip with
+    rotation, transquant bypass.  No implicit RDPCM, cross-component prediction or PCM (the sweep holds those).
+    Behind them n_wrap_per_shape pictures per shape of the one regime in which the flat product wraps int32: 12 bit, slice QP 51
+    (qP up to 75), every coded remaining level over the whole range, no rare syntax - so that all but 4:4:4 go out as split
+    chains and the wrap reaches k_residual's DC-only, 4x4, 8x8 and large-block paths where residual_ref sees it."""
+    shapes = [dict(width=8, height=8, log2_ctb=4, no_split=0), dict(width=8, height=8, log2_ctb=4, no_split=1),
+              dict(width=16, height=16, log2_ctb=4, no_split=1), dict(width=32, height=32, log2_ctb=5, no_split=1),
+              dict(width=64, height=64, log2_ctb=6, no_split=1)]
+    out = []
+    seed = first_seed
+    for shape in shapes:
+        for k in range(n_per_shape):
+            r = seed * 2654435761 % (1 << 32)
+            pick = lambda s, opts: opts[(r >> s) % len(opts)]
+            bd = [8, 10, 12][k % 3]
+            kw = dict(shape, bit_depth=bd, chroma_format=[1, 3, 2, 0][(k // 3) % 4], qp=pick(3, [1, 8, 17, 26, 35, 44, 51, 51]),
+                      density=pick(7, [100, 60, 30, 100]), level_span=pick(10, [30, 120, 400, 1000]), qp_span=pick(12, [0, 1]), cu_qp_delta=1,
+                      diff_cu_qp_delta_depth=0, transform_skip=pick(14, [1, 0]), rext_sps=pick(16, [0, 1, 128]), log2_max_ts=pick(18, [0, 0, 5]),
+                      scaling_list=pick(21, [0, 0, 2]), scaling_span=600, tq_bypass=pick(23, [0, 0, 0, 150]) if bd > 8 else 0,
+                      sao=0, deblock_disable=1, sign_hiding=pick(25, [1, 0]))
+            if not kw["transform_skip"]:
+                kw["log2_max_ts"] = 0
+            out.append((seed, kw))
+            seed += 1
+    seed = first_seed + 100000
+    for shape in shapes:
+        for k in range(n_wrap_per_shape):
+            out.append((seed, dict(shape, bit_depth=12, chroma_format=[1, 2, 0, 3][k % 4], qp=51, density=[100, 60, 30][k % 3], level_span=1000,
+                                   qp_span=k % 2, cu_qp_delta=1, diff_cu_qp_delta_depth=0, transform_skip=(k // 4) % 2, rext_sps=[0, 128][(k // 8) % 2],
+                                   sao=0, deblock_disable=1, sign_hiding=(k // 2) % 2)))
+            seed += 1
+    return out
+
+
+def extreme_tiles():
+    """512 x 512 tiles of the classes that take the split chains, with levels, QPs and 16x16 / 32x32 blocks at the edges of the
+    residual arithmetic: the int16 residual slab and the hand-over lines between waves carry rail values"""
+    base = dict(width=512, height=512, cu_qp_delta=1, qp_span=1, sao=1, sign_hiding=1)
+    return [(15000, dict(base, log2_ctb=5, qp=30, density=60, level_span=250)),
+            (15001, dict(base, log2_ctb=5, bit_depth=12, qp=51, density=90, level_span=600, no_split=1, transform_skip=0)),
+            (15002, dict(base, log2_ctb=6, bit_depth=10, chroma_format=2, qp=12, density=60, level_span=400, rext_sps=128)),
+            (15003, dict(base, log2_ctb=4, chroma_format=0, qp=44, density=100, level_span=1000, no_split=1))]
+
+
+def extreme_large():
+    """one large single picture per class with the same knobs (many waves per picture)"""
+    return [(15100, dict(width=1600, height=1024, log2_ctb=5, qp=26, density=50, level_span=300, qp_span=1, cu_qp_delta=1)),
+            (15101, dict(width=1536, height=1024, log2_ctb=6, bit_depth=12, chroma_format=2, qp=51, density=70, level_span=600, qp_span=1, cu_qp_delta=1, no_split=1)),
+            (15102, dict(width=1920, height=1080, log2_ctb=4, bit_depth=10, qp=8, density=60, level_span=400, qp_span=1, cu_qp_delta=1, rext_sps=128)),
+            (15103, dict(width=1536, height=1024, log2_ctb=6, chroma_format=0, qp=40, density=90, level_span=1000, qp_span=1, cu_qp_delta=1))]

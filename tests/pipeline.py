@@ -176,8 +176,8 @@ def cpu_decode(hm, tiles, tile_w, tile_h, canvas_w, canvas_h, cols, is_grid, out
     first = None
     canv = None
     for i, data in enumerate(tiles):
-        if decoder == "ref":
-            planes, info = orc.ref_decode(data, 0)
+        if decoder in ("ref", "ref_scalar"):  # (ref_scalar: the reference's scalar build - where its SIMD build rounds otherwise)
+            planes, info = orc.ref_decode(data, orc.REF_F_SCALAR if decoder == "ref_scalar" else 0)
         else:
             blob = hevcutil.parse_concealing(hm, data)[0] if decoder == "oracle_concealing" else hevcutil.parse(hm, data)
             planes, info = orc.oracle_decode(blob, 3)

@@ -187,6 +187,12 @@ struct SynthParams {
   int32_t sao_scale_y, sao_scale_c; // log2_sao_offset_scale_luma / chroma (<= bit_depth - 10)
   int32_t big_levels;          // per-mille chance of a long coeff_abs_level_remaining prefix (exercises the Rice adaptation)
   int32_t no_split;            // 1: no coding-quadtree / NxN / transform-tree split is ever chosen (one transform unit per CTB where the syntax allows)
+  // --- arithmetic edges of the residual path (all 0 = the draws of the streams above, byte for byte) ---
+  int32_t level_span;          // per-mille chance that a coeff_abs_level_remaining is drawn log-uniformly over the whole range a conforming
+                               // stream may carry (|level| up to 32767), at every QP; the other levels stay small
+  int32_t qp_span;             // 1: cu_qp_delta_abs over its whole range (suffix included), both signs free: QpY walks over
+                               // -QpBdOffset .. 51 and wraps (8-283)
+  int32_t scaling_span;        // per-mille chance that an explicitly coded scaling matrix is pinned at 1 / at 255 / at a mix of both, DC included
 };
 
 // entropy-coder adaptor for SliceWalker: chooses every bin, encodes it, returns it
@@ -296,22 +302,87 @@ class EncoderEC {
       case K_SPLIT_TF: return P.no_split ? 0 : rng_.chance(idx >= 5 ? 550 : (idx == 4 ? 400 : 300));
       case K_CBF_LUMA: return rng_.chance(7 * d);
       case K_CBF_CHROMA: return rng_.chance(5 * d);
-      case K_QP_DELTA: return idx >= 3 ? 0 : rng_.chance(idx == 0 ? 350 : 400);
-      case K_QP_DELTA_SUFFIX: return 0;
-      case K_QP_SIGN: return idx > 2 ? 1 : (idx < -2 ? 0 : (int)(rng_.next() & 1)); // keep QpY near the slice QP
+      case K_QP_DELTA:
+        if (P.qp_span) {
+          // cu_qp_delta_abs drawn whole, then written bin by bin: 0 .. 25 + QpBdOffset / 2, the largest value both signs may
+          // carry (7.4.9.14: CuQpDeltaVal in -(26 + QpBdOffset / 2) .. 25 + QpBdOffset / 2)
+          if (idx == 0) qp_abs_ = rng_.chance(250) ? 0 : 1 + (int)(rng_.next() % (uint64_t)(25 + 3 * (P.bit_depth - 8)));
+          return qp_abs_ > idx; // prefix: truncated unary, cMax 5
+        }
+        return idx >= 3 ? 0 : rng_.chance(idx == 0 ? 350 : 400);
+      case K_QP_DELTA_SUFFIX: {
+        if (!P.qp_span) return 0;
+        // EG0 of cu_qp_delta_abs - 5: k ones, a zero, k bits (idx < 32: the unary part, 32 + b: bit b)
+        const int rest = qp_abs_ - 5 + 1;
+        int k = 0;
+        while ((rest >> (k + 1)) != 0) k++;
+        return idx < 32 ? idx < k : ((rest - (1 << k)) >> (idx - 32)) & 1;
+      }
+      case K_QP_SIGN:
+        if (P.qp_span) return (int)(rng_.next() & 1);
+        return idx > 2 ? 1 : (idx < -2 ? 0 : (int)(rng_.next() & 1)); // keep QpY near the slice QP
       case K_TSKIP: return rng_.chance(P.rext_sps ? 400 : 150);
       case K_CHROMA_QP_OFFSET_FLAG: return rng_.chance(600);
       case K_RES_SCALE_ABS: return (idx & 256) ? 0 : rng_.chance(idx == 0 ? 600 : 500); // (bit 8: a unit the product refuses with a scale, Q17)
-      case K_LAST_PREFIX: return rng_.chance(520);
+      case K_LAST_PREFIX:
+        if (P.level_span) { // per coordinate: at the origin (DC-only blocks: half of the draws), as ever, or far out (the last group of four)
+          if ((idx & 255) == 0) last_bias_ = (int)(rng_.next() % 4);
+          return rng_.chance(last_bias_ <= 1 ? 60 : (last_bias_ == 2 ? 520 : 930));
+        }
+        return rng_.chance(520);
       case K_CSBF: return rng_.chance(5 * d);
       case K_SIG: return rng_.chance(4 * d + 50);
-      case K_GT1: return rng_.chance(300);
-      case K_GT2: return rng_.chance(300);
+      // (level_span: a remaining level is coded only behind greater1 [and greater2 for the first such level of a sub-block])
+      case K_GT1: return rng_.chance(P.level_span ? 700 : 300);
+      case K_GT2: return rng_.chance(P.level_span ? 700 : 300);
+      case K_CALR_SUFFIX:
+        if (calr_ >= 0) return (calr_suffix_ >> idx) & 1;
+        return (int)(rng_.next() & 1);
       case K_CALR_PREFIX: {
-        // keep |level| small (<= 8, <= 3 at very high QP): real encoders do not emit levels whose
-        // dequantised value saturates int16, and in that regime the reference's own SIMD and
-        // scalar builds disagree
+        // Without level_span: keep |level| small (<= 8, <= 3 at very high QP): real encoders do not emit levels whose
+        // dequantised value saturates int16, and in that regime the reference's own SIMD and scalar builds disagree
+        // (DESIGN.md Q10).  The blessed corpus (tests/golden/synth.json) stays there.
+        // With level_span: that regime is the subject (corpus.extreme_sweep, tests/golden/extreme.json: the reference's
+        // SCALAR build is the ground truth).  A remaining level is then drawn whole - with a uniform bit length, i.e.
+        // roughly log-uniformly - and written bin by bin.  The cap: the reference reads up to 64 prefix bins
+        // (slice.cc:2638-2673), shifts an int by them and stores baseLevel + remaining through an int16_t cast
+        // (slice.cc:3665) without a check; a conforming stream carries coefficients in -32768 .. 32767 (7.4.9.11).  The
+        // sign is drawn before the level, or hidden, so the magnitude is capped at 32767: remaining <= 32767 - 3
+        // (baseLevel <= 3).  -32768 itself is not produced.
         const int prefix = idx & 15, rice = idx >> 4;
+        if (P.level_span) {
+          // (a run of prefix bins is counted here: beyond 15 bins the walker's hint overlaps the Rice parameter)
+          if (!calr_run_) {
+            calr_run_ = true;
+            calr_pos_ = 0;
+            calr_ = -1;
+            if (rng_.chance(P.level_span)) {
+              const int bits = 1 + (int)(rng_.next() % 15);                       // 1 .. 15
+              calr_ = (int)(rng_.next() & ((1u << bits) - 1)) | (1 << (bits - 1)); // that many significant bits
+              if (calr_ > 32767 - 3) calr_ = 32767 - 3;
+              // 9.3.3.11: prefix and suffix of that value at this Rice parameter
+              if ((calr_ >> rice) < 4) { calr_prefix_ = calr_ >> rice; calr_suffix_ = calr_ & ((1 << rice) - 1); }
+              else {
+                const int q = (calr_ >> rice) - 2;
+                int e = 0;
+                while ((q >> (e + 1)) != 0) e++;
+                calr_prefix_ = 3 + e;
+                calr_suffix_ = calr_ - (((1 << e) + 2) << rice);
+              }
+            }
+          }
+          if (calr_ >= 0) {
+            const int b = calr_pos_++ < calr_prefix_;
+            if (!b) calr_run_ = false;
+            return b;
+          }
+          // (else: a small level by the rules below; calr_run_ ends with the first 0 bin)
+          int b;
+          const int mp = rice >= 2 ? 0 : 2;
+          b = prefix >= mp ? 0 : rng_.chance(350);
+          if (!b) calr_run_ = false;
+          return b;
+        }
         const int maxprefix = P.qp >= 40 ? 0 : (rice >= 2 ? 0 : 2);
         if (P.big_levels && P.qp < 40 && rice < 6 && prefix < 5 + (rice < 2 ? 2 : 0)) return prefix < 3 ? rng_.chance(P.big_levels) : rng_.chance(500);
         return prefix >= maxprefix ? 0 : rng_.chance(350);
@@ -322,11 +393,15 @@ class EncoderEC {
   Rng rng_;
   const SynthParams& P;
   ContextSet cs_;
+  // values drawn whole and written bin by bin (qp_span, level_span)
+  int qp_abs_ = 0, last_bias_ = 1;
+  bool calr_run_ = false;
+  int calr_ = -1, calr_pos_ = 0, calr_prefix_ = 0, calr_suffix_ = 0;
 };
 
 // §7.3.4 scaling_list_data with seeded random content: every matrix is either predicted (default list or an
 // earlier matrix of the same size) or coded explicitly as a smooth random walk (values 1..255, wrapping deltas allowed).
-void write_scaling_list_data(BitWriter& w, Rng& rng)
+void write_scaling_list_data(BitWriter& w, Rng& rng, int span)
 {
   for (int sizeId = 0; sizeId < 4; sizeId++)
     for (int matrixId = 0; matrixId < 6; matrixId += (sizeId == 3) ? 3 : 1) {
@@ -339,13 +414,17 @@ void write_scaling_list_data(BitWriter& w, Rng& rng)
       w.flag(1);
       const int coefNum = sizeId == 0 ? 16 : 64;
       int next = 8;
+      // scaling_span: 1 all entries 1, 2 all 255, 3 each entry 1 or 255 - the DC entry of the large matrices included
+      const int pin = (span && rng.chance(span)) ? 1 + (int)(rng.next() % 3) : 0;
       if (sizeId > 1) {
-        const int dc = 1 + (int)(rng.next() % 255);    // scaling_list_dc_coef_minus8 + 8 in 1..255
+        int dc = 1 + (int)(rng.next() % 255);          // scaling_list_dc_coef_minus8 + 8 in 1..255
+        if (pin) dc = pin == 1 ? 1 : (pin == 2 ? 255 : ((rng.next() & 1) ? 255 : 1));
         w.se(dc - 8);
         next = dc;
       }
       for (int i = 0; i < coefNum; i++) {
         int target = next + (int)(rng.next() % 25) - 10 + (rng.chance(30) ? (int)(rng.next() % 200) - 100 : 0);
+        if (pin) target = pin == 1 ? 1 : (pin == 2 ? 255 : ((rng.next() & 1) ? 255 : 1));
         target = target < 1 ? 1 : (target > 255 ? 255 : target);
         int d = target - next;                          // -254..254
         const int wrapped = d < 0 ? d + 256 : d - 256;  // the same value through the modulo-256 wrap
@@ -416,7 +495,7 @@ __attribute__((visibility("default"))) int hm_synth_picture(const SynthParams* p
     w.flag(p.scaling_list != 0); // scaling_list_enabled_flag
     if (p.scaling_list) {
       w.flag(p.scaling_list == 2); // sps_scaling_list_data_present_flag
-      if (p.scaling_list == 2) write_scaling_list_data(w, hdr_rng);
+      if (p.scaling_list == 2) write_scaling_list_data(w, hdr_rng, p.scaling_span);
     }
     w.flag(0);                 // amp
     w.flag(p.sao != 0);
@@ -492,7 +571,7 @@ __attribute__((visibility("default"))) int hm_synth_picture(const SynthParams* p
     w.flag(p.deblock_disable != 0);
     if (!p.deblock_disable) { w.se(p.beta_offset_div2); w.se(p.tc_offset_div2); }
     w.flag(p.scaling_list == 3); // pps_scaling_list_data_present
-    if (p.scaling_list == 3) write_scaling_list_data(w, hdr_rng);
+    if (p.scaling_list == 3) write_scaling_list_data(w, hdr_rng, p.scaling_span);
     w.flag(0);                 // lists_modification_present
     w.ue(0);                   // log2_parallel_merge_level_minus2
     w.flag(0);                 // slice_segment_header_extension_present

@@ -387,21 +387,30 @@ def test_config3_batch_of_12mp_grids(pkg, hm):
     assert [list(sh.image_shard(1024, r, 8))[0] for r in range(8)] == [128 * r for r in range(8)]
 
 
-@pytest.mark.parametrize("shape", [(8, 6, 4032, 3024), (3, 2, 1500, 1000), (2, 2, 1001, 999), (2, 2, 1024, 1024), (1, 1, 512, 512)],
-                         ids=["12mp_crop64x48", "crop_not_16_aligned", "odd_canvas", "no_crop", "single_tile"])
+# tiles with levels over the whole int16 range and QpY over its whole range (level_span, qp_span): flat black / white areas next to
+# full-swing edges - the packed 16-bit deblocking / SAO arithmetic of the fused tails on rail-valued samples
+LEVEL_SPAN_TILES = dict(level_span=300, qp_span=1, density=80)
+
+
+@pytest.mark.parametrize("shape", [(8, 6, 4032, 3024), (3, 2, 1500, 1000), (2, 2, 1001, 999), (2, 2, 1024, 1024), (1, 1, 512, 512),
+                                   (3, 2, 1500, 1000, LEVEL_SPAN_TILES)],
+                         ids=["12mp_crop64x48", "crop_not_16_aligned", "odd_canvas", "no_crop", "single_tile", "level_span_tiles"])
 @pytest.mark.parametrize("stages", [3, 1, 2, 0], ids=["deblock+sao", "deblock", "sao", "none"])
 def test_fused_tail_equals_separate_kernels(pkg, hm, shape, stages):
     """hm_batch_set_colour: the fused kernel (deblocking + SAO + paste + colour, filters.hip k_tail420) against the four
     separate kernels on the same batch - 3 images of different tiles, every filter-stage combination, canvases cropped
-    at 16-aligned and unaligned widths; the 12 MP shape is also checked against the CPU flow."""
+    at 16-aligned and unaligned widths; the 12 MP shape is also checked against the CPU flow, and so are the level_span tiles
+    (the oracle's tiles, themselves held against the reference's scalar build: its SIMD build rounds 8-bit 4x4 transform-skip
+    blocks otherwise there, Q10)."""
     import bench
     import orc
     import torch
-    cols, rows, w, h = shape
+    cols, rows, w, h = shape[:4]
+    over = shape[4] if len(shape) > 4 else {}
     dev = torch.device("cuda:0")
     st = torch.cuda.current_stream().cuda_stream
     n_images = 3
-    made = list(bench.make_streams(pkg.capi, (7700000 + 31 * k for k in range(n_images * cols * rows))))
+    made = list(bench.make_streams(pkg.capi, (7700000 + 31 * k for k in range(n_images * cols * rows)), **over))
     out = []
     for group in (0, -1):  # 0: fused where possible, -1: never
         gb = bench.GridBatch(pkg, dev, cols, rows, 512, w, h)
@@ -419,6 +428,16 @@ def test_fused_tail_equals_separate_kernels(pkg, hm, shape, stages):
         tiles = made[:cols * rows]
         exp = bench.cpu_grid_image([d for d, _ in tiles], [b for _, b in tiles], cols, rows, 512, w, h, (gb.ys, gb.cs, gb.os), orc.have_ref())
         assert np.array_equal(out[0][0], exp[:h, :w * 3])
+    if over and stages == 3:
+        tiles = made[:cols * rows]
+        assert out[0][0].min() == 0 and out[0][0].max() == 255  # (the rails are there)
+        exp = bench.cpu_grid_image([d for d, _ in tiles], [b for _, b in tiles], cols, rows, 512, w, h, (gb.ys, gb.cs, gb.os), False)
+        assert np.array_equal(out[0][0], exp[:h, :w * 3]), "level_span tiles: fused tail differs from the CPU flow (oracle)"
+        if orc.have_ref():  # ... whose tiles are those of the reference's scalar build
+            for d, b in tiles:
+                ref, _ = orc.ref_decode(d, orc.REF_F_SCALAR)
+                mine, _ = orc.oracle_decode(b, 3, crop=True)
+                assert all(np.array_equal(m, r) for m, r in zip(mine, ref))
 
 
 @pytest.mark.parametrize("shape", [(8, 6, 4032, 3024), (3, 2, 1500, 1000)], ids=["12mp_crop64x48", "crop_not_16_aligned"])
@@ -529,6 +548,12 @@ FLOAT_TAIL_CLASSES = {
     "hdr_420_9_full_rgb24": (9, 1, 1, 9, "HM_OUT_RGB", 3, False, 5),
     "hdr_420_11_ctb16_rgba": (11, 1, 1, 9, "HM_OUT_RGBA", 4, False, 4),
     "hdr_420_11_ctb64_grid_rgb24": (11, 1, 1, 1, "HM_OUT_RGB", 3, True, 6),
+    # tiles with levels / QpY over their whole ranges (9th element: synthesiser parameters): k_tailf on 8-, 10- and 12-bit input and
+    # k_tail420's 16-bit instantiation on 10-bit input, on flat black / white areas next to full-swing edges
+    "level_span_422_8_rgb24": (8, 2, 1, 6, "HM_OUT_RGB", 3, False, 5, LEVEL_SPAN_TILES),
+    "level_span_config4_422_10_rrggbb_le": (10, 2, 0, 9, "HM_OUT_RRGGBB_LE", 6, False, 5, LEVEL_SPAN_TILES),
+    "level_span_422_12_rrggbb_le": (12, 2, 1, 6, "HM_OUT_RRGGBB_LE", 6, False, 5, LEVEL_SPAN_TILES),
+    "level_span_hdr_420_10_ctb16_rgb24": (10, 1, 1, 9, "HM_OUT_RGB", 3, False, 4, LEVEL_SPAN_TILES),
 }
 
 
@@ -544,12 +569,13 @@ def test_fused_float_tail_equals_separate_kernels(pkg, hm, name, stages):
     bd, cf, full, matrix, fmt, obpp = FLOAT_TAIL_CLASSES[name][:6]
     grid = len(FLOAT_TAIL_CLASSES[name]) > 6 and FLOAT_TAIL_CLASSES[name][6]
     log2_ctb = FLOAT_TAIL_CLASSES[name][7] if len(FLOAT_TAIL_CLASSES[name]) > 7 else 5
+    over = FLOAT_TAIL_CLASSES[name][8] if len(FLOAT_TAIL_CLASSES[name]) > 8 else {}
     dev = torch.device("cuda:0")
     st = torch.cuda.current_stream().cuda_stream
     cols, rows, tw, th, w, h = 3, 2, 256, 192, 700, 330
     bps = 2 if bd > 8 else 1
     datas = [synthutil.picture(8100000 + 7 * k, width=tw, height=th, chroma_format=cf, bit_depth=bd, log2_ctb=log2_ctb, qp=28, vui=1,
-                               full_range=full, matrix=matrix, primaries=1, slices=(30 if k % 3 == 0 else 0)) for k in range(2 * cols * rows)]
+                               full_range=full, matrix=matrix, primaries=1, slices=(30 if k % 3 == 0 else 0), **over) for k in range(2 * cols * rows)]
     blobs = [capi.parse_hevc(d) for d in datas]
     ys, cs, os_ = L.hm_plane_stride(w, bps), L.hm_plane_stride((w + 1) // 2, bps), L.hm_plane_stride(w, obpp)
     ch = (h + 1) // 2 if cf == 1 else h
@@ -591,7 +617,8 @@ def test_fused_float_tail_equals_separate_kernels(pkg, hm, name, stages):
         # (no rescale: the canvas carries the tiles' own profile), converted along the chain the reference's search picks
         for j in range(2):
             tiles = datas[j * cols * rows:(j + 1) * cols * rows]
-            for decoder in ["oracle"] + (["ref"] if orc.have_ref() else []):
+            # (level_span tiles: the reference's scalar build - its SIMD build rounds 8-bit 4x4 transform-skip blocks otherwise there, Q10)
+            for decoder in ["oracle"] + ([("ref_scalar" if over else "ref")] if orc.have_ref() else []):
                 exp, _, _ = pipeline.cpu_decode(hm, tiles, tw, th, w, h, cols, grid, getattr(capi, fmt), decoder=decoder)
                 assert np.array_equal(out[0][j], exp[:h, :w * obpp]), f"{name}, image {j}: fused float tail differs from the CPU flow ({decoder})"
 

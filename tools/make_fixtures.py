@@ -6,6 +6,9 @@ and the reference decoder build oracle/_ref):
                             reference's own test material, re-framed, never source code
   tests/golden/decode.json  FNV-1a-64 fingerprints of the planes the REAL reference decoder
                             (libde265, oracle/_ref) produces for each fixture, per stage
+  tests/golden/extreme.json (a plain run rewrites it with the others; `make_fixtures.py extreme` writes this file alone) the same fingerprints of the reference's
+                            SCALAR build for corpus.extreme_sweep - levels, QPs and scaling factors at the edges of the
+                            residual arithmetic -, and beside them where its default (SIMD) build decodes otherwise
 """
 import json
 import os
@@ -89,5 +92,55 @@ def main():
     json.dump(synth, open(os.path.join(ROOT, "tests", "golden", "synth.json"), "w"), indent=1, sort_keys=True)
 
 
+EXTREME_CASES = 144
+
+
+def extreme():
+    """corpus.extreme_sweep: fingerprints of the reference's scalar build at the three stages; and, at the reconstruction
+    stage, in which plane and block class its default build differs (every class is a quirk of DESIGN.md 3)"""
+    import collections
+    import numpy as np
+    import corpus
+    import residual_ref as rr
+    import synthutil
+    import __graft_entry__ as g
+    capi = g.load_package().capi
+    cases, classes, differing = {}, collections.Counter(), []
+    for seed, kw in corpus.extreme_sweep(EXTREME_CASES):
+        data = synthutil.picture(seed, **kw)
+        entry = {"bytes": len(data), "stream_fnv": f"{orc.load().orc_fnv1a64(data, len(data), 0):016x}"}
+        for stage, flags in (("recon", orc.REF_F_NO_DEBLOCK | orc.REF_F_NO_SAO), ("deblock", orc.REF_F_NO_SAO), ("full", 0)):
+            planes, _ = orc.ref_decode(data, flags | orc.REF_F_SCALAR)
+            entry[stage] = fingerprint(planes)
+            if stage == "recon":
+                simd, _ = orc.ref_decode(data, flags)
+                if any(not np.array_equal(a, b) for a, b in zip(simd, planes)):
+                    differing.append(seed)
+                    P = rr.Picture(capi.parse_hevc(data, record_order=2))
+                    origin = set()
+                    for rec in P.records():  # per plane, the first block in decode order in which a sample differs (later ones may inherit it through prediction)
+                        if rec["cidx"] in origin:
+                            continue
+                        nT = 1 << rec["log2"]
+                        a, b = (p[rec["cidx"]][rec["y"]:rec["y"] + nT, rec["x"]:rec["x"] + nT] for p in (simd, planes))
+                        if not np.array_equal(a, b):
+                            kind = "pcm" if rec["pcm"] else "no residual" if not rec["cbf"] else "bypass" if rec["bypass"] else \
+                                "transform skip" if rec["tskip"] else "DST" if nT == 4 and rec["cidx"] == 0 else "DCT"
+                            origin.add(rec["cidx"])
+                            classes[f"{P.bit_depth}-bit plane {rec['cidx']} {nT}x{nT} {kind}"] += 1
+        cases[str(seed)] = entry
+    out = {"cases": cases,
+           "simd_vs_scalar": {"stage": "recon", "cases": len(cases), "cases_that_differ": len(differing), "seeds": differing,
+                              "blocks_that_differ_by_class": dict(sorted(classes.items()))}}
+    json.dump(out, open(os.path.join(ROOT, "tests", "golden", "extreme.json"), "w"), indent=1, sort_keys=True)
+    print("extreme:", len(cases), "cases;", len(differing), "decoded differently by the default build:", dict(sorted(classes.items())))
+
+
 if __name__ == "__main__":
-    main()
+    if sys.argv[1:] == ["extreme"]:
+        sys.path.insert(0, ROOT)
+        extreme()
+    else:
+        main()
+        sys.path.insert(0, ROOT)
+        extreme()
