@@ -20,6 +20,10 @@ HM_PIPE_PLANAR = 10
 # planar YCbCr targets; HM_OUT_YCBCR_8BIT: or-ed where no convert_hdr_to_8bit field exists (ColourDesc, pipeline config)
 HM_OUT_YCBCR_420, HM_OUT_YCBCR_422, HM_OUT_YCBCR_444, HM_OUT_YCBCR_8BIT = 0x101, 0x102, 0x103, 0x200
 HM_PLANAR_UNFUSED = 1
+# device-resident output (hm_device_dest)
+HM_DEV_LAYOUT_HWC, HM_DEV_LAYOUT_CHW = 0, 1
+HM_DEV_U8, HM_DEV_U16, HM_DEV_F16, HM_DEV_F32 = 0, 1, 2, 3
+HM_PIPELINE_FULL = 1
 HM_DETAIL_NO_COLOUR_CHAIN = 2
 
 
@@ -109,6 +113,101 @@ def bind_decode(L):
     L.hm_batch_get_timings4.argtypes = [C.c_void_p, C.c_int, C.POINTER(C.c_float)]
     L.hm_batch_get_timings5.argtypes = [C.c_void_p, C.c_int, C.POINTER(C.c_float)]
     L.hm_batch_algorithmic_bytes.argtypes = [C.c_void_p, C.POINTER(C.c_uint64), C.POINTER(C.c_uint64)]
+
+
+class ImageInfo(C.Structure):
+    """hm_image_info"""
+    _fields_ = [(n, C.c_int32) for n in "width height bit_depth chroma is_grid grid_rows grid_cols tile_width tile_height has_transforms has_alpha coded_width coded_height has_nclx".split()]
+
+
+class DecodeParams(C.Structure):
+    """hm_decode_params"""
+    _fields_ = [("out_format", C.c_int32), ("host_threads", C.c_int32), ("ignore_transformations", C.c_int32),
+                ("chroma_upsampling", C.c_int32), ("stream", C.c_void_p), ("ext_dst", C.c_void_p),
+                ("ext_dst_len", C.c_uint32), ("ext_dst_stride", C.c_uint32), ("strict_decoding", C.c_int32),
+                ("convert_hdr_to_8bit", C.c_int32)]
+
+
+class Decoded(C.Structure):
+    """hm_decoded"""
+    _fields_ = [(n, C.c_int32) for n in "width height bit_depth chroma out_format has_nclx primaries transfer matrix full_range used_ext_dst".split()] + \
+               [("plane", C.POINTER(C.c_uint8) * 3), ("stride", C.c_int32 * 3), ("plane_width", C.c_int32 * 3), ("plane_height", C.c_int32 * 3),
+                ("has_alpha", C.c_int32), ("alpha", C.POINTER(C.c_uint8)), ("alpha_stride", C.c_int32), ("warnings", C.c_int32)]
+
+
+class DeviceDest(C.Structure):
+    """hm_device_dest: caller-owned device memory the pixels of a decode go to"""
+    _fields_ = [("ptr", C.c_void_p), ("len", C.c_uint64), ("layout", C.c_int32), ("dtype", C.c_int32),
+                ("row_pitch", C.c_int64), ("plane_pitch", C.c_int64), ("scale", C.c_float * 4), ("bias", C.c_float * 4)]
+
+
+class SequenceInfo(C.Structure):
+    """hm_sequence_info"""
+    _fields_ = [("is_sequence", C.c_int32), ("frame_count", C.c_uint32), ("duration", C.c_uint64)]
+
+
+class PipelineConfig(C.Structure):
+    """hm_pipeline_config"""
+    _fields_ = [(n, C.c_int32) for n in "host_threads max_in_flight out_format chroma_upsampling ignore_transformations strict_decoding device cpu_first cpu_count".split()]
+
+
+class PipelineResult(C.Structure):
+    """hm_pipeline_result"""
+    _fields_ = [("tag", C.c_uint64), ("status", C.c_int32), ("image", Decoded), ("handle", C.c_void_p)]
+
+
+_image_lib = None
+
+
+def image_lib():
+    """The library once more, as a ctypes object of its own with the image-level entry points bound to the structures above (the
+    same loaded library as lib(): ctypes keeps argtypes per object, and callers of lib() bind these entry points to structure
+    classes of their own)."""
+    global _image_lib
+    if _image_lib is None:
+        lib()
+        L = C.CDLL(LIB_PATH)
+        L.hm_status_string.restype = C.c_char_p
+        L.hm_last_error.restype = C.c_char_p
+        bind_image(L)
+        _image_lib = L
+    return _image_lib
+
+
+def check_image(status):
+    if status < 0:
+        L = image_lib()
+        raise HmError(status, f"{L.hm_status_string(status).decode()}: {L.hm_last_error().decode()}")
+    return status
+
+
+def bind_image(L):
+    """argtypes of the file / image / sequence / pipeline entry points and of the device-destination ones."""
+    L.hm_file_open.argtypes = [C.c_char_p, C.c_size_t, C.POINTER(C.c_void_p)]
+    L.hm_file_close.argtypes = [C.c_void_p]
+    L.hm_file_close.restype = None
+    L.hm_file_primary_item.argtypes = [C.c_void_p]
+    L.hm_file_primary_item.restype = C.c_uint32
+    L.hm_file_image_info.argtypes = [C.c_void_p, C.c_uint32, C.POINTER(ImageInfo)]
+    L.hm_file_sequence_info.argtypes = [C.c_void_p, C.POINTER(SequenceInfo)]
+    L.hm_decode_item.argtypes = [C.c_void_p, C.c_uint32, C.POINTER(DecodeParams), C.POINTER(Decoded)]
+    L.hm_decoded_free.argtypes = [C.POINTER(Decoded)]
+    L.hm_decoded_free.restype = None
+    L.hm_device_dest_bytes.argtypes = [C.c_int, C.c_int, C.c_int, C.POINTER(DeviceDest)]
+    L.hm_device_dest_bytes.restype = C.c_int64
+    L.hm_to_tensor.argtypes = [C.c_int, C.c_int, C.c_int, C.c_void_p, C.c_int, C.POINTER(DeviceDest), C.c_void_p]
+    L.hm_decode_item_to_device.argtypes = [C.c_void_p, C.c_uint32, C.POINTER(DecodeParams), C.POINTER(DeviceDest), C.POINTER(Decoded)]
+    L.hm_decode_sequence_to_device.argtypes = [C.c_void_p, C.c_uint32, C.c_int32, C.POINTER(DecodeParams), C.POINTER(DeviceDest),
+                                               C.POINTER(Decoded), C.POINTER(C.c_int32)]
+    L.hm_pipeline_create.argtypes = [C.POINTER(PipelineConfig), C.POINTER(C.c_void_p)]
+    L.hm_pipeline_destroy.argtypes = [C.c_void_p]
+    L.hm_pipeline_destroy.restype = None
+    L.hm_pipeline_submit.argtypes = [C.c_void_p, C.c_char_p, C.c_size_t, C.c_uint32, C.c_uint64]
+    L.hm_pipeline_submit_to_device.argtypes = [C.c_void_p, C.c_char_p, C.c_size_t, C.c_uint32, C.c_uint64, C.POINTER(DeviceDest)]
+    L.hm_pipeline_pending.argtypes = [C.c_void_p]
+    L.hm_pipeline_next.argtypes = [C.c_void_p, C.POINTER(PipelineResult)]
+    L.hm_pipeline_release.argtypes = [C.c_void_p, C.POINTER(PipelineResult)]
+    L.hm_pipeline_release.restype = None
 
 
 class ParseOptions(C.Structure):

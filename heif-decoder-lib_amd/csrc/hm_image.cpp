@@ -692,8 +692,9 @@ void parse_picture(const hm_file* f, uint32_t id, bool few_pictures, int strict,
 // The output half of decode_image_user (context.cc:1516-1600) for a decoded image on the device: the result's fields, the colour
 // conversion (unless the batch did it: I.rgb_attached), the alpha plane, and the copy to params->ext_dst or to pinned host
 // planes - all queued on `s`.  `dout` and `alpha_sdr` must live until the stream has drained.
+// dest (may be NULL): caller-owned device memory the interleaved pixels go to instead (hm_device_dest); nothing is copied to the host then.
 int emit_image(const hm_decode_params* params, hipStream_t s, PlanarImage& I, const DevPlane* alpha, int alpha_bd, DevMem& dout,
-               DevPlane& alpha_sdr, hm_decoded* out)
+               DevPlane& alpha_sdr, hm_decoded* out, const hm_device_dest* dest = nullptr)
 {
   int rc;
   DevPlane (&P)[3] = I.P;
@@ -711,6 +712,10 @@ int emit_image(const hm_decode_params* params, hipStream_t s, PlanarImage& I, co
   // (context.cc:1538-1552: "different_chroma || different_colorspace"; the depth alone - convert_hdr_to_8bit - does not)
   const bool planar_target = hm_out_is_planar(params->out_format);
   const bool as_decoded = params->out_format == 0 || (planar_target && chroma != 0 && chroma == hm_out_planar_chroma(params->out_format));
+  if (dest) { // (the entry points have refused all of this already, against the size the file declares: here it is the decoded size)
+    hm_dest_plan dp;
+    if ((rc = hm_dest_resolve(params->out_format, img_w, img_h, dest, &dp)) || (rc = hm_dest_check_len(dest, &dp))) return rc;
+  }
   if (as_decoded) { // native planar YCbCr
     out->out_format = params->out_format;
     for (int c = 0; c < 3; c++) {
@@ -821,7 +826,14 @@ int emit_image(const hm_decode_params* params, hipStream_t s, PlanarImage& I, co
     if (bd > 8 && (params->out_format == HM_OUT_RGB || params->out_format == HM_OUT_RGBA)) out->bit_depth = 8;
     out->stride[0] = cd.out_stride;
     out->plane_width[0] = img_w; out->plane_height[0] = img_h;
-    if (params->ext_dst && params->ext_dst_stride >= (uint32_t)(img_w * obpp) &&
+    if (dest) { // the image's w x h x C elements and nothing else: a 2-D device copy or k_to_tensor (devdest.cpp)
+      if ((rc = hm_dest_write(dest, params->out_format, img_w, img_h, 0, img_h, dout.p, cd.out_stride, s))) return rc;
+      hm_dest_plan dp;
+      if ((rc = hm_dest_resolve(params->out_format, img_w, img_h, dest, &dp))) return rc;
+      out->used_ext_dst = 1;
+      out->stride[0] = (int32_t)std::min<int64_t>(dp.row_pitch, 0x7FFFFFFF);
+    }
+    else if (params->ext_dst && params->ext_dst_stride >= (uint32_t)(img_w * obpp) &&
         (size_t)params->ext_dst_len >= (size_t)params->ext_dst_stride * (size_t)img_h) {
       // caller-provided destination (fork API heif_decoding_options_add_external_dest)
       e = hipMemcpy2DAsync(params->ext_dst, params->ext_dst_stride, dout.p, cd.out_stride, (size_t)img_w * obpp, img_h,
@@ -885,10 +897,27 @@ int job_enqueue(DecodeJob& j, hm_decoded* out)
   }
   const int alpha_bd = j.n_items > 1 ? A.bd : I.tile_alpha_bd;
   lap("planar decode queued");
-  rc = emit_image(params, s, I, alpha, alpha_bd, j.dout, j.alpha_sdr, out);
+  rc = emit_image(params, s, I, alpha, alpha_bd, j.dout, j.alpha_sdr, out, j.has_dest ? &j.dest : nullptr);
   if (rc) return rc;
   lap("colour + D2H queued");
   return HM_OK;
+}
+
+int check_device_request(const hm_file* f, uint32_t id, const hm_decode_params* params, const hm_device_dest* dest)
+{
+  if (params->ext_dst) return hm_fail(HM_ERR_INVALID_ARG, "params->ext_dst must be NULL with a device destination");
+  int rc = hm_dest_check_static(params->out_format, dest);
+  if (rc) return rc;
+  if (!dest->ptr) return hm_fail(HM_ERR_INVALID_ARG, "device destination: null ptr");
+  hm_image_info info;
+  if (hm_file_image_info(f, id, &info) == HM_OK) { // (a file that fails here fails the decode with its own message)
+    const int w = params->ignore_transformations ? info.coded_width : info.width, h = params->ignore_transformations ? info.coded_height : info.height;
+    hm_dest_plan dp;
+    if (w > 0 && h > 0 && ((rc = hm_dest_resolve(params->out_format, w, h, dest, &dp)) || (rc = hm_dest_check_len(dest, &dp)))) return rc;
+  }
+  int n_dev = 0;
+  if (hipGetDeviceCount(&n_dev) != hipSuccess || n_dev == 0) { (void)hipGetLastError(); return hm_fail(HM_ERR_NO_DEVICE, "no HIP device available"); }
+  return hm_dest_check_pointer(dest);
 }
 
 int job_complete(DecodeJob& j, hm_decoded*)
@@ -908,21 +937,39 @@ int job_complete(DecodeJob& j, hm_decoded*)
 
 extern "C" {
 
-static int decode_grid_cut(const hm_file* f, uint32_t id, const hm_decode_params* params, const int32_t* devices, int n_devices, bool pipelined, hm_decoded* out, bool* applicable); // (below, behind the slabs)
+static int decode_grid_cut(const hm_file* f, uint32_t id, const hm_decode_params* params, const int32_t* devices, int n_devices, bool pipelined, hm_decoded* out, bool* applicable,
+                           const hm_device_dest* dest = nullptr); // (below, behind the slabs)
+static int decode_item(const hm_file* f, uint32_t id, const hm_decode_params* params, const hm_device_dest* dest, hm_decoded* out);
 
 int hm_decode_item(const hm_file* f, uint32_t id, const hm_decode_params* params, hm_decoded* out)
 {
   if (!f || !params || !out) return hm_fail(HM_ERR_INVALID_ARG, "null argument");
+  return decode_item(f, id, params, nullptr, out);
+}
+
+int hm_decode_item_to_device(const hm_file* f, uint32_t id, const hm_decode_params* params, const hm_device_dest* dest, hm_decoded* out)
+{
+  if (!f || !params || !dest || !out) return hm_fail(HM_ERR_INVALID_ARG, "null argument");
+  std::memset(out, 0, sizeof(*out));
+  const int rc = check_device_request(f, id, params, dest); // refused before any work is queued: the destination is not written
+  if (rc) return rc;
+  return decode_item(f, id, params, dest, out);
+}
+
+// dest (may be NULL): the pixels go to caller-owned device memory
+static int decode_item(const hm_file* f, uint32_t id, const hm_decode_params* params, const hm_device_dest* dest, hm_decoded* out)
+{
   std::memset(out, 0, sizeof(*out)); // (whatever fails below: nothing of an earlier call is left in it)
   { // (r06) a grid of more tiles than parsing threads, to interleaved pixels: slab by slab under the entropy decode (decode_grid_cut)
     bool applicable = false;
-    const int prc = decode_grid_cut(f, id, params, nullptr, 1, /*pipelined=*/true, out, &applicable);
+    const int prc = decode_grid_cut(f, id, params, nullptr, 1, /*pipelined=*/true, out, &applicable, dest);
     if (prc || applicable) return prc;
   }
   std::memset(out, 0, sizeof(*out));
   Lap lap;
   DecodeJob job;
   job.f = f; job.id = id; job.params = *params; job.s = (hipStream_t)params->stream;
+  if (dest) { job.dest = *dest; job.has_dest = true; }
   int rc = job_plan(job);
   if (rc) return rc;
   // ---- host: entropy-decode every coded picture (CABAC on the CPU, spread over threads like the reference's
@@ -998,8 +1045,26 @@ int hm_file_sequence_info(const hm_file* f, hm_sequence_info* info)
   return HM_OK;
 }
 
+static int decode_sequence(const hm_file* f, uint32_t first, int32_t count, const hm_decode_params* params, const hm_frame_dest* dests,
+                           const hm_device_dest* ddests, hm_decoded* out, int32_t* failed_frame);
+
 int hm_decode_sequence(const hm_file* f, uint32_t first, int32_t count, const hm_decode_params* params, const hm_frame_dest* dests,
                        hm_decoded* out, int32_t* failed_frame)
+{
+  return decode_sequence(f, first, count, params, dests, nullptr, out, failed_frame);
+}
+
+int hm_decode_sequence_to_device(const hm_file* f, uint32_t first, int32_t count, const hm_decode_params* params, const hm_device_dest* dests,
+                                 hm_decoded* out, int32_t* failed_frame)
+{
+  if (failed_frame) *failed_frame = -1;
+  if (!dests) return hm_fail(HM_ERR_INVALID_ARG, "null argument");
+  return decode_sequence(f, first, count, params, nullptr, dests, out, failed_frame);
+}
+
+// ddests (NULL, or `count` entries): every frame goes to caller-owned device memory
+static int decode_sequence(const hm_file* f, uint32_t first, int32_t count, const hm_decode_params* params, const hm_frame_dest* dests,
+                           const hm_device_dest* ddests, hm_decoded* out, int32_t* failed_frame)
 {
   if (failed_frame) *failed_frame = -1;
   if (!f || !params || !out) return hm_fail(HM_ERR_INVALID_ARG, "null argument");
@@ -1010,6 +1075,19 @@ int hm_decode_sequence(const hm_file* f, uint32_t first, int32_t count, const hm
   if (first < 1 || (uint64_t)first + (uint64_t)count - 1 > n_frames)
     return hm_fail(HM_ERR_INVALID_ARG, "frames %u..%llu outside 1..%u", first, (unsigned long long)first + count - 1, n_frames);
   if (params->ext_dst) return hm_fail(HM_ERR_INVALID_ARG, "params->ext_dst: a sequence takes its caller buffers from dests");
+  if (ddests) { // what can be refused without the frames' sizes (those: below, behind the entropy decode, before anything is queued)
+    for (int k = 0; k < count; k++) {
+      const int rc = hm_dest_check_static(params->out_format, &ddests[k]);
+      if (rc) return rc;
+      if (!ddests[k].ptr) return hm_fail(HM_ERR_INVALID_ARG, "device destination of frame %d: null ptr", k);
+    }
+    int n_dev = 0;
+    if (hipGetDeviceCount(&n_dev) != hipSuccess || n_dev == 0) { (void)hipGetLastError(); return hm_fail(HM_ERR_NO_DEVICE, "no HIP device available"); }
+    for (int k = 0; k < count; k++) {
+      const int rc = hm_dest_check_pointer(&ddests[k]);
+      if (rc) return rc;
+    }
+  }
   const bool planar_target = hm_out_is_planar(params->out_format);
   if (params->out_format && !planar_target) {
     const int obpp = hm_out_bytes_per_pixel(params->out_format);
@@ -1056,6 +1134,12 @@ int hm_decode_sequence(const hm_file* f, uint32_t first, int32_t count, const hm
     I.warnings = warn | (h->concealed_ctbs ? HM_WARN_CONCEALED : 0);
     I.w = h->width - h->crop_left - h->crop_right; I.h = h->height - h->crop_top - h->crop_bottom;
     I.chroma = h->chroma_format; I.bd = h->bit_depth_y; I.is_grid = false;
+    if (ddests) {
+      hm_dest_plan dp;
+      int drc = hm_dest_resolve(params->out_format, I.w, I.h, &ddests[k], &dp);
+      if (!drc) drc = hm_dest_check_len(&ddests[k], &dp);
+      if (drc) return fail(drc);
+    }
     if (planar_target) { // converted frame by frame behind the batch (emit_image); its refusals come here, before anything is queued
       if (I.chroma == 0 || I.chroma != hm_out_planar_chroma(params->out_format)) {
         hm_colour_desc& cd = Fr.cd;
@@ -1157,7 +1241,7 @@ int hm_decode_sequence(const hm_file* f, uint32_t first, int32_t count, const hm
     SeqFrame& Fr = *F[k];
     hm_decode_params pk = *params;
     if (dests) { pk.ext_dst = dests[k].ext_dst; pk.ext_dst_len = dests[k].ext_dst_len; pk.ext_dst_stride = dests[k].ext_dst_stride; }
-    if ((rc = emit_image(&pk, s, Fr.I, nullptr, 0, Fr.dout, Fr.alpha_sdr, &out[k]))) return release_all(rc);
+    if ((rc = emit_image(&pk, s, Fr.I, nullptr, 0, Fr.dout, Fr.alpha_sdr, &out[k], ddests ? &ddests[k] : nullptr))) return release_all(rc);
   }
   lap("sequence: colour + D2H queued");
   const hipError_t e = hipStreamSynchronize(s);
@@ -1197,7 +1281,12 @@ struct Slab {
 
 // Queue one slab on its device: decode + convert + the copy to dst (row 0 of the slab), all on a stream of its own.  Returns
 // without waiting; slab_finish waits and reports.  Runs on any thread (it makes the slab's device current).
-void slab_enqueue(const hm_file* f, const hm_decode_params* params, Slab& S, uint8_t* dst, size_t dst_stride, int canvas_w)
+// ddest (may be NULL): the slab's rows go to the caller's device memory instead (canvas_h: the height of the whole image); the kernel that
+// writes them is row-local, so every layout cuts into slabs like the host copy does.  dest_ready: recorded on params->stream when the
+// call came in - the slab's stream is non-blocking and knows nothing of that stream, so the write (not the decode in front of it) waits
+// for whatever the caller had queued on the destination by then.
+void slab_enqueue(const hm_file* f, const hm_decode_params* params, Slab& S, uint8_t* dst, size_t dst_stride, int canvas_w,
+                  const hm_device_dest* ddest = nullptr, int canvas_h = 0, hipEvent_t dest_ready = nullptr)
 {
   auto fail = [&](int rc) { S.rc = rc; S.message = hm_last_error(); };
   trace_mark("slab enqueue begins, row", S.row0);
@@ -1227,7 +1316,11 @@ void slab_enqueue(const hm_file* f, const hm_decode_params* params, Slab& S, uin
       rc = dout.alloc((size_t)cd.out_stride * mem_rows(S.h));
       if (!rc) rc = hm_colour_convert(&cd, I.P[0].mem.p, I.P[1].mem.p, I.P[2].mem.p, dout.p, S.s);
     }
-    if (!rc) {
+    if (!rc && ddest) {
+      if (dest_ready) rc = hm_check_hip(hipStreamWaitEvent(S.s, dest_ready, 0), "wait for the caller's stream");
+      if (!rc) rc = hm_dest_write(ddest, params->out_format, canvas_w, canvas_h, S.y0, S.h, dout.p, cd.out_stride, S.s);
+    }
+    else if (!rc) {
       e = hipMemcpy2DAsync(dst, dst_stride, dout.p, cd.out_stride, (size_t)canvas_w * obpp, (size_t)S.h, hipMemcpyDeviceToHost, S.s);
       rc = hm_check_hip(e, "D2H of a slab");
     }
@@ -1287,7 +1380,8 @@ int hm_plan_device_slabs(int grid_rows, int n_devices, int32_t* first, int32_t* 
 // slab k run under the entropy decode of the slabs behind it (one 12 MP grid of 48 tiles on 16 threads: ~2.3 ms of entropy decode,
 // behind which 0.43 ms of queueing, 0.7 ms of kernels and 0.66 ms of copy used to start).
 // *applicable = false (and nothing touched) when the item does not cut this way.
-static int decode_grid_cut(const hm_file* f, uint32_t id, const hm_decode_params* params, const int32_t* devices, int n_devices, bool pipelined, hm_decoded* out, bool* applicable)
+static int decode_grid_cut(const hm_file* f, uint32_t id, const hm_decode_params* params, const int32_t* devices, int n_devices, bool pipelined, hm_decoded* out, bool* applicable,
+                           const hm_device_dest* ddest)
 {
   *applicable = false;
   ItemPlan plan;
@@ -1368,7 +1462,19 @@ static int decode_grid_cut(const hm_file* f, uint32_t id, const hm_decode_params
   const int img_w = plan.canvas_w, img_h = plan.canvas_h;
   uint8_t* dst = nullptr;
   size_t dst_stride = 0;
-  if (params->ext_dst && params->ext_dst_stride >= (uint32_t)(img_w * obpp) && (size_t)params->ext_dst_len >= (size_t)params->ext_dst_stride * (size_t)img_h) {
+  struct DestReady { // the caller's work on the destination so far, as an event the slabs' streams wait for before they write
+    hipEvent_t e = nullptr;
+    ~DestReady() { if (e) hipEventDestroy(e); } // (behind slab_finish of every slab on each way out: nothing waits for it any more)
+  } dest_ready;
+  if (ddest) { // (pipelined, one device) caller-owned device memory: checked against the grid's size before the first slab is queued
+    hm_dest_plan dp;
+    if ((rc = hm_dest_resolve(params->out_format, img_w, img_h, ddest, &dp)) || (rc = hm_dest_check_len(ddest, &dp))) return rc;
+    dst_stride = (size_t)dp.row_pitch;
+    if ((rc = hm_check_hip(hipEventCreateWithFlags(&dest_ready.e, hipEventDisableTiming), "hipEventCreate"))) return rc;
+    if ((rc = hm_check_hip(hipEventRecord(dest_ready.e, (hipStream_t)params->stream), "hipEventRecord on the caller's stream"))) return rc;
+    out->used_ext_dst = 1;
+  }
+  else if (params->ext_dst && params->ext_dst_stride >= (uint32_t)(img_w * obpp) && (size_t)params->ext_dst_len >= (size_t)params->ext_dst_stride * (size_t)img_h) {
     dst = (uint8_t*)params->ext_dst; dst_stride = params->ext_dst_stride;
     out->used_ext_dst = 1;
   }
@@ -1453,7 +1559,7 @@ static int decode_grid_cut(const hm_file* f, uint32_t id, const hm_decode_params
           if (plan.blobs[i].p && reinterpret_cast<const hm_pic*>(plan.blobs[i].p)->concealed_ctbs) tile_warnings |= HM_WARN_CONCEALED;
         trace_mark("slab parsed, row", S.row0);
         if (const int trc = take_blobs(S)) { parse_rc = trc; parse_msg = hm_last_error(); return; } // (the slabs in front are drained below)
-        slab_enqueue(f, params, S, dst + (size_t)S.y0 * dst_stride, dst_stride, img_w);
+        slab_enqueue(f, params, S, ddest ? nullptr : dst + (size_t)S.y0 * dst_stride, dst_stride, img_w, ddest, img_h, dest_ready.e);
         if (S.rc) return; // (reported below)
       }
     };
@@ -1522,7 +1628,7 @@ static int decode_grid_cut(const hm_file* f, uint32_t id, const hm_decode_params
   out->has_nclx = 1; out->primaries = 1; out->transfer = 13; out->matrix = 6; out->full_range = 1;
   if (bd == 8 && obpp >= 6) out->bit_depth = 10;
   if (bd > 8 && (params->out_format == HM_OUT_RGB || params->out_format == HM_OUT_RGBA)) out->bit_depth = 8;
-  out->stride[0] = (int32_t)dst_stride;
+  out->stride[0] = (int32_t)std::min<size_t>(dst_stride, 0x7FFFFFFF);
   out->plane_width[0] = img_w; out->plane_height[0] = img_h;
   out->warnings = tile_warnings;
   return HM_OK;

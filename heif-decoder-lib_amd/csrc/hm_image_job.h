@@ -13,6 +13,7 @@
 #include <vector>
 
 #include "heif_file.h"
+#include "hm_devdest.h"
 #include "hm_internal.h"
 #include "hm_stream.h"
 
@@ -102,6 +103,8 @@ struct DecodeJob {
   const hm_file* f = nullptr;
   uint32_t id = 0;
   hm_decode_params params{};
+  hm_device_dest dest{};  // caller-owned device memory the pixels go to instead of pinned host memory (has_dest; hm_decode_params
+  bool has_dest = false;  // keeps its layout, so the destination travels beside the job's copy of it)
   hipStream_t s = nullptr;
   ItemPlan item[2];   // [0] the image, [1] its alpha auxiliary image
   int n_items = 0;
@@ -124,6 +127,9 @@ void job_parse_tile(DecodeJob& j, int k, int row_threads = 1); // k = 0 .. job_t
 // the entropy decode of one coded picture (hvc1 item or movie sample `id`) into `blob`, or its failure in status / message
 void parse_picture(const hm_file* f, uint32_t id, bool few_pictures, int strict, int row_threads, Blob& blob, int& status, std::string& message);
 int job_enqueue(DecodeJob& j, hm_decoded* out);
+// everything about a device destination that can be refused before the entropy decode: the request itself, the destination against
+// the size the file declares for the item, a device, the pointer (hm_image.cpp)
+int check_device_request(const hm_file* f, uint32_t id, const hm_decode_params* params, const hm_device_dest* dest);
 int job_complete(DecodeJob& j, hm_decoded* out);
 
 } // namespace hm_img

@@ -182,9 +182,23 @@ void hm_pipeline_destroy(hm_pipeline* p)
   delete p;
 }
 
+static int submit(hm_pipeline* p, const uint8_t* heif, size_t size, uint32_t item_id, uint64_t tag, const hm_device_dest* dest);
+
 int hm_pipeline_submit(hm_pipeline* p, const uint8_t* heif, size_t size, uint32_t item_id, uint64_t tag)
 {
   if (!p || !heif) return hm_fail(HM_ERR_INVALID_ARG, "null argument");
+  return submit(p, heif, size, item_id, tag, nullptr);
+}
+
+int hm_pipeline_submit_to_device(hm_pipeline* p, const uint8_t* heif, size_t size, uint32_t item_id, uint64_t tag, const hm_device_dest* dest)
+{
+  if (!p || !heif || !dest) return hm_fail(HM_ERR_INVALID_ARG, "null argument");
+  return submit(p, heif, size, item_id, tag, dest);
+}
+
+// dest (may be NULL): the image's pixels go to caller-owned device memory of the pipeline's device
+static int submit(hm_pipeline* p, const uint8_t* heif, size_t size, uint32_t item_id, uint64_t tag, const hm_device_dest* dest)
+{
   hipStream_t stream = nullptr;
   {
     // back-pressure first (before the file is copied and its boxes parsed: a caller that retries HM_PIPELINE_FULL would
@@ -212,7 +226,15 @@ int hm_pipeline_submit(hm_pipeline* p, const uint8_t* heif, size_t size, uint32_
     im->job.params.chroma_upsampling = p->cfg.chroma_upsampling;
     im->job.params.ignore_transformations = p->cfg.ignore_transformations;
     im->job.params.strict_decoding = p->cfg.strict_decoding;
-    rc = job_plan(im->job);
+    if (dest) { // refused here, before anything is queued: the destination is not written
+      int prev = -1;
+      hipGetDevice(&prev);
+      hipSetDevice(p->cfg.device); // (the pointer must belong to the device the crew works on)
+      rc = check_device_request(im->file, im->job.id, &im->job.params, dest);
+      if (prev >= 0) hipSetDevice(prev);
+      im->job.dest = *dest; im->job.has_dest = true;
+    }
+    if (!rc) rc = job_plan(im->job);
   }
   if (rc) { delete im; give_back(); return rc; }
   const int nt = job_tile_count(im->job);

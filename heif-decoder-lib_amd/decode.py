@@ -1,0 +1,213 @@
+"""HEIF bytes -> CUDA tensor, without the pixels leaving the device (hm_decode_item_to_device / hm_pipeline_submit_to_device).
+
+    img = decode_to_tensor(open("a.heic", "rb").read())                           # 3 x H x W float32
+    batch = decode_batch_to_tensor(files, dtype=torch.float16, scale=1 / 255)     # N x 3 x H x W
+
+Layouts: "chw" (one plane per channel) and "hwc" (the target's own interleaving).  dtypes: torch.uint8 / torch.uint16 (must be
+the target's own sample type: 8-bit "rgb" / "rgba", 16-bit "rrggbb_le" / "rrggbbaa_le" ...), torch.float16, torch.float32;
+floats are sample * scale[c] + bias[c], rounded after each step.  What the library refuses raises capi.HmError."""
+import ctypes as C
+import os
+
+from . import capi
+
+OUT_FORMATS = {"rgb": capi.HM_OUT_RGB, "rgba": capi.HM_OUT_RGBA, "rrggbb_le": capi.HM_OUT_RRGGBB_LE, "rrggbb_be": capi.HM_OUT_RRGGBB_BE,
+               "rrggbbaa_le": capi.HM_OUT_RRGGBBAA_LE, "rrggbbaa_be": capi.HM_OUT_RRGGBBAA_BE}
+LAYOUTS = {"hwc": capi.HM_DEV_LAYOUT_HWC, "chw": capi.HM_DEV_LAYOUT_CHW}
+
+
+def _out_format(out_format):
+    if isinstance(out_format, str):
+        if out_format.lower() not in OUT_FORMATS:
+            raise ValueError(f"out_format {out_format!r}: one of {sorted(OUT_FORMATS)}")
+        return OUT_FORMATS[out_format.lower()]
+    return int(out_format)
+
+
+def _dtype_code(dtype):
+    import torch
+    codes = {torch.uint8: capi.HM_DEV_U8, torch.uint16: capi.HM_DEV_U16, torch.float16: capi.HM_DEV_F16, torch.float32: capi.HM_DEV_F32}
+    if dtype not in codes:
+        raise ValueError(f"dtype {dtype}: one of torch.uint8, torch.uint16, torch.float16, torch.float32")
+    return codes[dtype]
+
+
+def _channels(fmt):
+    L = capi.image_lib()
+    obpp = capi.check_image(L.hm_out_bytes_per_pixel(fmt))
+    return obpp // (2 if obpp >= 6 else 1)
+
+
+def _per_channel(v, default):
+    if v is None:
+        v = default
+    if isinstance(v, (int, float)):
+        v = [float(v)] * 4
+    v = [float(x) for x in v]
+    if not 1 <= len(v) <= 4:
+        raise ValueError("scale / bias: a number or up to four per-channel values")
+    return v + [default] * (4 - len(v))
+
+
+def _layout(layout):
+    if str(layout).lower() not in LAYOUTS:
+        raise ValueError(f"layout {layout!r}: 'chw' or 'hwc'")
+    return LAYOUTS[str(layout).lower()]
+
+
+def _shape(layout, c, h, w):
+    return (c, h, w) if layout == capi.HM_DEV_LAYOUT_CHW else (h, w, c)
+
+
+def _dest_of(t, layout, dtype_code, c, scale, bias):
+    """hm_device_dest of one image-shaped view `t` (C x H x W or H x W x C): its strides become the pitches"""
+    es = t.element_size()
+    if layout == capi.HM_DEV_LAYOUT_CHW:
+        ok = t.stride(2) == 1 or t.shape[2] == 1
+        row, plane = t.stride(1) * es, t.stride(0) * es
+    else:
+        ok = (t.stride(2) == 1 or t.shape[2] == 1) and (t.stride(1) == c or t.shape[1] == 1)
+        row, plane = t.stride(0) * es, 0
+    if not ok or row < 0 or plane < 0:
+        raise ValueError("out: the pixels of a row must be contiguous (only the row and plane strides are free)")
+    d = capi.DeviceDest()
+    d.ptr = t.data_ptr()
+    d.len = t.untyped_storage().nbytes() - t.storage_offset() * es
+    d.layout, d.dtype = layout, dtype_code
+    d.row_pitch, d.plane_pitch = row, plane
+    for k in range(4):
+        d.scale[k], d.bias[k] = scale[k], bias[k]
+    return d
+
+
+def _default_threads():
+    return max(1, min(16, os.cpu_count() or 1))
+
+
+class _File:
+    def __init__(self, data):
+        self.L = capi.image_lib()
+        self.h = C.c_void_p()
+        capi.check_image(self.L.hm_file_open(data, len(data), C.byref(self.h)))
+
+    def size(self, item_id):
+        iid = item_id or self.L.hm_file_primary_item(self.h)
+        info = capi.ImageInfo()
+        capi.check_image(self.L.hm_file_image_info(self.h, iid, C.byref(info)))
+        return iid, info.width, info.height
+
+    def close(self):
+        if self.h:
+            self.L.hm_file_close(self.h)
+            self.h = C.c_void_p()
+
+
+def decode_to_tensor(data, item_id=0, out_format="rgb", layout="chw", dtype=None, scale=None, bias=None, out=None, stream=None,
+                     host_threads=None):
+    """Decode one image of a HEIF file (bytes; item_id 0 = the primary item) into a CUDA tensor: C x H x W ("chw") or H x W x C
+    ("hwc").  dtype defaults to torch.float32 (out's dtype when out is given).  out: a CUDA tensor of that shape to write into;
+    its row (and plane) stride is honoured, bytes between rows are left alone.  stream: a torch.cuda.Stream or a raw stream
+    handle (default: the current stream).  Returns when the pixels are in place."""
+    import torch
+    L = capi.image_lib()
+    fmt, lay = _out_format(out_format), _layout(layout)
+    if dtype is None:
+        dtype = out.dtype if out is not None else torch.float32
+    code, c = _dtype_code(dtype), _channels(fmt)
+    f = _File(data)
+    try:
+        iid, w, h = f.size(item_id)
+        shape = _shape(lay, c, h, w)
+        if out is None:
+            out = torch.empty(shape, dtype=dtype, device="cuda")
+        else:
+            if not out.is_cuda or out.dtype != dtype:
+                raise ValueError(f"out: a CUDA tensor of dtype {dtype} is needed, got {out.dtype} on {out.device}")
+            if tuple(out.shape) != shape:
+                raise ValueError(f"out: shape {tuple(out.shape)} does not match the image's {shape}")
+        dest = _dest_of(out, lay, code, c, _per_channel(scale, 1.0), _per_channel(bias, 0.0))
+        if stream is None:
+            stream = torch.cuda.current_stream(out.device)
+        handle = stream.cuda_stream if hasattr(stream, "cuda_stream") else int(stream)
+        prm = capi.DecodeParams(fmt, host_threads or _default_threads(), 0, 0, handle or None, None, 0, 0, 0, 0)
+        d = capi.Decoded()
+        with torch.cuda.device(out.device):
+            capi.check_image(L.hm_decode_item_to_device(f.h, iid, C.byref(prm), C.byref(dest), C.byref(d)))
+        if (d.width, d.height) != (w, h):  # (the library checked the destination against the decoded size: nothing else was written)
+            raise capi.HmError(-3, f"the decoded image is {d.width} x {d.height}, the file declares {w} x {h}")
+        L.hm_decoded_free(C.byref(d))
+        return out
+    finally:
+        f.close()
+
+
+def decode_batch_to_tensor(files, item_id=0, out_format="rgb", layout="chw", dtype=None, scale=None, bias=None, out=None,
+                           host_threads=None, max_in_flight=4):
+    """Decode N equally sized HEIF files through ONE hm_pipeline (the entropy decode of one file runs under the kernels of
+    another) into one N x C x H x W ("chw") or N x H x W x C ("hwc") CUDA tensor, each image into its slice.  files: bytes
+    objects or paths.  A file of another size than the first (or than `out`) raises ValueError naming it."""
+    import torch
+    L = capi.image_lib()
+    fmt, lay = _out_format(out_format), _layout(layout)
+    if dtype is None:
+        dtype = out.dtype if out is not None else torch.float32
+    code, c = _dtype_code(dtype), _channels(fmt)
+    sc, bi = _per_channel(scale, 1.0), _per_channel(bias, 0.0)
+    names, datas = [], []
+    for k, entry in enumerate(files):
+        if isinstance(entry, (bytes, bytearray, memoryview)):
+            names.append(f"files[{k}]")
+            datas.append(bytes(entry))
+        else:
+            names.append(os.fspath(entry))
+            with open(entry, "rb") as fh:
+                datas.append(fh.read())
+    if not datas:
+        raise ValueError("files: empty")
+    ids, size = [], None
+    if out is not None:
+        if out.dim() != 4 or not out.is_cuda or out.dtype != dtype or out.shape[0] != len(datas):
+            raise ValueError(f"out: a 4-D CUDA tensor of dtype {dtype} with {len(datas)} images is needed")
+        s = tuple(out.shape[1:])
+        size = (s[2], s[1]) if lay == capi.HM_DEV_LAYOUT_CHW else (s[1], s[0])
+        if s != _shape(lay, c, size[1], size[0]):
+            raise ValueError(f"out: shape {tuple(out.shape)} does not hold {c}-channel images in layout {layout!r}")
+    for name, data in zip(names, datas):
+        f = _File(data)
+        try:
+            iid, w, h = f.size(item_id)
+        finally:
+            f.close()
+        if size is None:
+            size = (w, h)
+        if (w, h) != size:
+            raise ValueError(f"{name}: the image is {w} x {h}, the batch is {size[0]} x {size[1]}")
+        ids.append(iid)
+    if out is None:
+        out = torch.empty((len(datas),) + _shape(lay, c, size[1], size[0]), dtype=dtype, device="cuda")
+    cfg = capi.PipelineConfig(host_threads or _default_threads(), max(1, int(max_in_flight)), fmt, 0, 0, 0, out.device.index, 0, 0)
+    pipe = C.c_void_p()
+    with torch.cuda.device(out.device):
+        torch.cuda.current_stream().synchronize()  # (the pipeline works on streams of its own: `out` must be ready for them)
+        capi.check_image(L.hm_pipeline_create(C.byref(cfg), C.byref(pipe)))
+        try:
+            def take():
+                r = capi.PipelineResult()
+                capi.check_image(L.hm_pipeline_next(pipe, C.byref(r)))
+                tag, status = r.tag, r.status
+                detail = L.hm_last_error().decode() if status else ""
+                L.hm_pipeline_release(pipe, C.byref(r))
+                if status:
+                    raise capi.HmError(status, f"{names[tag]}: {detail}")
+            for k, data in enumerate(datas):
+                dest = _dest_of(out[k], lay, code, c, sc, bi)
+                while True:
+                    rc = capi.check_image(L.hm_pipeline_submit_to_device(pipe, data, len(data), ids[k], k, C.byref(dest)))
+                    if rc != capi.HM_PIPELINE_FULL:
+                        break
+                    take()
+            while L.hm_pipeline_pending(pipe):
+                take()
+        finally:
+            L.hm_pipeline_destroy(pipe)
+    return out

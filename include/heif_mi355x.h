@@ -456,6 +456,54 @@ HM_API int  hm_pipeline_next(hm_pipeline* p, hm_pipeline_result* res);
 /* give the image's pinned planes and its slot back */
 HM_API void hm_pipeline_release(hm_pipeline* p, hm_pipeline_result* res);
 
+/* ------------------------------------------------------------------------- */
+/* Device-resident output: decode into caller-owned GPU memory, with tensor layouts */
+/* ------------------------------------------------------------------------- */
+
+/* The image-level entry points above end in a copy to host memory.  These put the pixels of an interleaved RGB target
+ * (HM_OUT_RGB / _RGBA / _RRGGBB_* / _RRGGBBAA_*) into device memory of the caller instead - in the target's own
+ * interleaving (HWC) or one plane per channel (CHW), as the target's integers or as float32 / float16 with a scale and a
+ * bias per channel - for callers that go on working on the same GPU.  A "sample" is a byte of an 8-bit target, a 16-bit
+ * word of a 16-bit target.
+ *   HWC with the target's integer type: exactly the bytes hm_decode_item puts into plane[0] (byte order of _BE included).
+ *   CHW, or a float dtype: samples are taken as values - _BE targets are refused (ask for _LE), an integer dtype must be
+ *   the target's (HM_DEV_U8 / HM_DEV_U16); floats are  __fadd_rn(__fmul_rn((float)v, scale[c]), bias[c])  (no fused
+ *   multiply-add), HM_DEV_F16 that value through __float2half_rn (denormals kept).
+ * Refused with HM_ERR_INVALID_ARG, before any work is queued and without a byte of the destination written: a pointer
+ * that is not device memory of the decoding device, len below hm_device_dest_bytes, pitches below the tight value,
+ * ptr or pitches that are not multiples of the element size.  HM_ERR_UNSUPPORTED ("not supported with a device
+ * destination"): out_format 0 and the planar HM_OUT_YCBCR_* targets.  Only the width x height x channels elements of
+ * the image are written: no pitch padding, nothing behind the last row. */
+enum { HM_DEV_LAYOUT_HWC = 0,   /* the out_format's own interleaving: rows of pixels                     */
+       HM_DEV_LAYOUT_CHW = 1 }; /* one plane per channel (R, G, B[, A])                                   */
+enum { HM_DEV_U8 = 0, HM_DEV_U16 = 1, HM_DEV_F16 = 2, HM_DEV_F32 = 3 };
+typedef struct hm_device_dest {
+  void*    ptr;          /* device memory of the device the decode runs on                              */
+  uint64_t len;          /* bytes available at ptr                                                      */
+  int32_t  layout, dtype;
+  int64_t  row_pitch;    /* bytes between rows; 0 = tight                                               */
+  int64_t  plane_pitch;  /* CHW: bytes between channel planes; 0 = row_pitch * height                   */
+  float    scale[4], bias[4]; /* float dtypes only: out = sample * scale[c] + bias[c]                   */
+} hm_device_dest;
+/* bytes the destination must hold for a width x height image (last-row / last-plane form: HWC
+ * row_pitch * (h-1) + w*C*elem, CHW plane_pitch * (C-1) + row_pitch * (h-1) + w*elem), or the negative status of a
+ * combination that is refused.  Pure host arithmetic: no device needed; d->ptr and d->len are not looked at. */
+HM_API int64_t hm_device_dest_bytes(int out_format, int width, int height, const hm_device_dest* d);
+/* The tensor step on its own, for callers of the low-level API (hm_colour_convert / hm_batch_set_colour leave interleaved
+ * pixels on the device): rows of width * bytes-per-pixel bytes at d_src, src_stride bytes apart, go to `dest` under the
+ * rules above.  Asynchronous on `stream`. */
+HM_API int hm_to_tensor(int out_format, int width, int height, const void* d_src, int src_stride, const hm_device_dest* dest, void* stream);
+/* hm_decode_item with the pixels going to `dest`: returns when they are in place (the work runs on params->stream).
+ * `out` is filled as for an ext_dst decode: used_ext_dst = 1, every plane[] NULL, stride[0] = the row pitch in use.
+ * params->ext_dst must be NULL. */
+HM_API int hm_decode_item_to_device(const hm_file* f, uint32_t id, const hm_decode_params* params, const hm_device_dest* dest, hm_decoded* out);
+/* hm_decode_sequence with one hm_device_dest per frame (e.g. `count` offsets into one N x C x H x W allocation) */
+HM_API int hm_decode_sequence_to_device(const hm_file* f, uint32_t first, int32_t count, const hm_decode_params* params, const hm_device_dest* dests,
+                                        hm_decoded* out, int32_t* failed_frame);
+/* hm_pipeline_submit with a destination (copied): when hm_pipeline_next hands the result out, the pixels are complete in
+ * device memory, which must stay valid until then.  A destination that is refused fails the submit or the image's result. */
+HM_API int hm_pipeline_submit_to_device(hm_pipeline* p, const uint8_t* heif, size_t size, uint32_t item_id, uint64_t tag, const hm_device_dest* dest);
+
 #ifdef __cplusplus
 }
 #endif
