@@ -23,6 +23,8 @@ HM_PLANAR_UNFUSED = 1
 # device-resident output (hm_device_dest)
 HM_DEV_LAYOUT_HWC, HM_DEV_LAYOUT_CHW = 0, 1
 HM_DEV_U8, HM_DEV_U16, HM_DEV_F16, HM_DEV_F32 = 0, 1, 2, 3
+# views (hm_device_view): a rectangle of the image at a size of the caller's choice
+HM_VIEW_TRIANGLE, HM_VIEW_NEAREST = 0, 1
 HM_PIPELINE_FULL = 1
 HM_DETAIL_NO_COLOUR_CHAIN = 2
 
@@ -141,6 +143,11 @@ class DeviceDest(C.Structure):
                 ("row_pitch", C.c_int64), ("plane_pitch", C.c_int64), ("scale", C.c_float * 4), ("bias", C.c_float * 4)]
 
 
+class DeviceView(C.Structure):
+    """hm_device_view: crop rectangle (0, 0, 0, 0 = the whole image), output size (0, 0 = the crop's own), filter"""
+    _fields_ = [(n, C.c_int32) for n in "crop_x crop_y crop_w crop_h out_w out_h filter".split()]
+
+
 class SequenceInfo(C.Structure):
     """hm_sequence_info"""
     _fields_ = [("is_sequence", C.c_int32), ("frame_count", C.c_uint32), ("duration", C.c_uint64)]
@@ -204,6 +211,11 @@ def bind_image(L):
     L.hm_pipeline_destroy.restype = None
     L.hm_pipeline_submit.argtypes = [C.c_void_p, C.c_char_p, C.c_size_t, C.c_uint32, C.c_uint64]
     L.hm_pipeline_submit_to_device.argtypes = [C.c_void_p, C.c_char_p, C.c_size_t, C.c_uint32, C.c_uint64, C.POINTER(DeviceDest)]
+    L.hm_decode_item_to_device_view.argtypes = [C.c_void_p, C.c_uint32, C.POINTER(DecodeParams), C.POINTER(DeviceView), C.POINTER(DeviceDest), C.POINTER(Decoded)]
+    L.hm_pipeline_submit_to_device_view.argtypes = [C.c_void_p, C.c_char_p, C.c_size_t, C.c_uint32, C.c_uint64, C.POINTER(DeviceView), C.POINTER(DeviceDest)]
+    L.hm_resample_to_tensor.argtypes = [C.c_int, C.c_int, C.c_int, C.c_void_p, C.c_int, C.POINTER(DeviceView), C.POINTER(DeviceDest), C.c_void_p]
+    L.hm_plan_view.argtypes = [C.c_void_p, C.c_uint32, C.POINTER(DecodeParams), C.POINTER(DeviceView), C.POINTER(C.c_int32 * 4)]
+    L.hm_view_filter_taps.argtypes = [C.c_int, C.c_int, C.c_int, C.c_int, C.POINTER(C.c_int32), C.POINTER(C.c_float), C.c_int]
     L.hm_pipeline_pending.argtypes = [C.c_void_p]
     L.hm_pipeline_next.argtypes = [C.c_void_p, C.POINTER(PipelineResult)]
     L.hm_pipeline_release.argtypes = [C.c_void_p, C.POINTER(PipelineResult)]

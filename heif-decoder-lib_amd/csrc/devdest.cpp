@@ -1,6 +1,11 @@
 // devdest.cpp — device-resident output: the arithmetic and the refusals of hm_device_dest, and the step that writes the colour
 // stage's interleaved pixels into it (a 2-D device copy for HWC with the target's own integer type, k_to_tensor otherwise).
+// Views (hm_device_view): the refusals, the tap tables and the step that writes a resampled rectangle (kernels: resample.hip).
+#include <algorithm>
 #include <cstring>
+#include <mutex>
+#include <new>
+#include <vector>
 
 #include "hm_colour_plan.h"
 #include "hm_devdest.h"
@@ -119,6 +124,188 @@ int hm_dest_write(const hm_device_dest* d, int out_format, int w, int h, int y0,
     return hm_check_hip(e, "copy to the device destination");
   }
   return hm_launch_to_tensor(&p, src, src_stride, w, rows, dst, d->scale, d->bias, s);
+}
+
+// ---- views ----------------------------------------------------------------------------------------------------------------------
+
+// the taps of output index j on an axis of n -> m, all in double (the contract of include/heif_mi355x.h): returns their count,
+// *first the first source index, w[0 .. count) the normalised weights when w is given (count <= 2 * 256 + 2)
+static int axis_taps(int n, int m, int j, int* first, float* w)
+{
+  const double s = (double)n / (double)m, fs = s > 1.0 ? s : 1.0, c = ((double)j + 0.5) * s;
+  int lo = (int)(c - fs + 0.5), hi = (int)(c + fs + 0.5);
+  if (lo < 0) lo = 0;
+  if (hi > n) hi = n;
+  *first = lo;
+  if (!w) return hi - lo;
+  double W = 0.0;
+  for (int i = lo; i < hi; i++) {
+    const double x = ((double)i + 0.5 - c) / fs, wi = 1.0 - (x < 0 ? -x : x);
+    W += wi > 0.0 ? wi : 0.0;
+  }
+  for (int i = lo; i < hi; i++) {
+    const double x = ((double)i + 0.5 - c) / fs, wi = 1.0 - (x < 0 ? -x : x);
+    w[i - lo] = (float)((wi > 0.0 ? wi : 0.0) / W);
+  }
+  return hi - lo;
+}
+
+static int check_axis(int n, int m, const char* what)
+{
+  if (n < 1 || n > 32768) return hm_fail(HM_ERR_INVALID_ARG, "view: source %s %d", what, n);
+  if (m < 1 || m > 32768) return hm_fail(HM_ERR_INVALID_ARG, "view: output %s %d is not in 1 .. 32768", what, m);
+  if ((int64_t)n > (int64_t)256 * m) return hm_fail(HM_ERR_INVALID_ARG, "view: %s %d -> %d is a reduction by more than 256", what, n, m);
+  return HM_OK;
+}
+
+int hm_view_filter_taps(int n_in, int n_out, int filter, int j, int32_t* first, float* weights, int cap)
+{
+  if (!first || (cap > 0 && !weights)) return hm_fail(HM_ERR_INVALID_ARG, "null argument");
+  if (filter != HM_VIEW_TRIANGLE && filter != HM_VIEW_NEAREST) return hm_fail(HM_ERR_INVALID_ARG, "view: unknown filter %d", filter);
+  const int rc = check_axis(n_in, n_out, "extent");
+  if (rc) return rc;
+  if (j < 0 || j >= n_out) return hm_fail(HM_ERR_INVALID_ARG, "view: output index %d of %d", j, n_out);
+  if (filter == HM_VIEW_NEAREST) {
+    *first = j * n_in / n_out;
+    if (cap > 0) weights[0] = 1.0f;
+    return 1;
+  }
+  float w[2 * 256 + 4];
+  int f0 = 0;
+  const int n = axis_taps(n_in, n_out, j, &f0, w);
+  *first = f0;
+  for (int i = 0; i < n && i < cap; i++) weights[i] = w[i];
+  return n;
+}
+
+int hm_view_resolve(int out_format, int src_w, int src_h, const hm_device_view* v, hm_view_plan* vp)
+{
+  if (!v || !vp) return hm_fail(HM_ERR_INVALID_ARG, "null view");
+  std::memset(vp, 0, sizeof(*vp));
+  if (v->filter != HM_VIEW_TRIANGLE && v->filter != HM_VIEW_NEAREST) return hm_fail(HM_ERR_INVALID_ARG, "view: unknown filter %d", v->filter);
+  if (v->crop_w == 0 && v->crop_h == 0) {
+    if (v->crop_x || v->crop_y) return hm_fail(HM_ERR_INVALID_ARG, "view: crop origin %d, %d with an empty crop", v->crop_x, v->crop_y);
+    vp->x = vp->y = 0; vp->w = src_w; vp->h = src_h;
+  }
+  else {
+    if (v->crop_w <= 0 || v->crop_h <= 0) return hm_fail(HM_ERR_INVALID_ARG, "view: crop extent %d x %d is not positive", v->crop_w, v->crop_h);
+    if (v->crop_x < 0 || v->crop_y < 0 || (int64_t)v->crop_x + v->crop_w > src_w || (int64_t)v->crop_y + v->crop_h > src_h)
+      return hm_fail(HM_ERR_INVALID_ARG, "view: crop %d x %d at %d, %d is not inside the %d x %d image", v->crop_w, v->crop_h, v->crop_x, v->crop_y, src_w, src_h);
+    vp->x = v->crop_x; vp->y = v->crop_y; vp->w = v->crop_w; vp->h = v->crop_h;
+  }
+  vp->filter = v->filter;
+  vp->crop_only = v->out_w == 0 && v->out_h == 0;
+  vp->ow = vp->crop_only ? vp->w : v->out_w;
+  vp->oh = vp->crop_only ? vp->h : v->out_h;
+  int rc;
+  if ((rc = check_axis(vp->w, vp->ow, "width")) || (rc = check_axis(vp->h, vp->oh, "height"))) return rc;
+  const bool be = out_format == HM_OUT_RRGGBB_BE || out_format == HM_OUT_RRGGBBAA_BE;
+  if (be && !vp->crop_only && vp->filter == HM_VIEW_TRIANGLE)
+    return hm_fail(HM_ERR_INVALID_ARG, "view: a big-endian target has no sample values to resample: ask for the _LE format");
+  return HM_OK;
+}
+
+void hm_view_scratch_free(hm_view_scratch* sc)
+{
+  for (int i = 0; i < 2; i++) { if (sc->dev[i]) hm_pool_device_free(sc->dev[i]); sc->dev[i] = nullptr; }
+  if (sc->pinned) hm_pool_pinned_free(sc->pinned);
+  sc->pinned = nullptr;
+}
+
+int hm_view_write(const hm_device_dest* d, int out_format, const hm_view_plan* vp, const void* src, int src_stride, hipStream_t s, hm_view_scratch* sc)
+{
+  hm_dest_plan p;
+  int rc = hm_dest_resolve(out_format, vp->ow, vp->oh, d, &p);
+  if (!rc) rc = hm_dest_check_len(d, &p);
+  if (rc) return rc;
+  const int obpp = p.channels * p.sample_bytes;
+  const uint8_t* origin = (const uint8_t*)src + (size_t)vp->y * src_stride + (size_t)vp->x * obpp;
+  if (vp->crop_only) // the rectangle's bytes: the 2-D copy or k_to_tensor on the offset source
+    return hm_dest_write(d, out_format, vp->w, vp->h, 0, vp->h, origin, src_stride, s);
+  if (vp->filter == HM_VIEW_NEAREST)
+    return hm_launch_view_nearest(&p, origin, src_stride, vp->w, vp->h, vp->ow, vp->oh, d->ptr, d->scale, d->bias, s);
+  // tap tables of both axes in one pinned block and one upload: first[m], count[m], weights[taps][m] per axis
+  int tx = 0, ty = 0, f0;
+  for (int j = 0; j < vp->ow; j++) tx = std::max(tx, axis_taps(vp->w, vp->ow, j, &f0, nullptr));
+  for (int k = 0; k < vp->oh; k++) ty = std::max(ty, axis_taps(vp->h, vp->oh, k, &f0, nullptr));
+  const size_t words_x = (size_t)vp->ow * (2 + tx), words_y = (size_t)vp->oh * (2 + ty), bytes = (words_x + words_y) * 4;
+  int32_t* host = (int32_t*)hm_pool_pinned_alloc(bytes);
+  if (!host) return hm_fail(HM_ERR_NOMEM, "out of memory");
+  sc->pinned = host;
+  float w[2 * 256 + 4];
+  auto fill = [&](int32_t* base, int n, int m, int taps) {
+    float* wt = reinterpret_cast<float*>(base + 2 * (size_t)m);
+    for (int j = 0; j < m; j++) {
+      const int cnt = axis_taps(n, m, j, &base[j], w);
+      base[m + j] = cnt;
+      for (int i = 0; i < taps; i++) wt[(size_t)i * m + j] = i < cnt ? w[i] : 0.0f;
+    }
+  };
+  fill(host, vp->w, vp->ow, tx);
+  fill(host + words_x, vp->h, vp->oh, ty);
+  const bool chw = p.layout == HM_DEV_LAYOUT_CHW;
+  const int64_t E = chw ? vp->ow : (int64_t)vp->ow * p.channels, pitch = (E + 15) / 16 * 16, plane = pitch * vp->h;
+  if (!(sc->dev[0] = hm_pool_device_alloc(bytes)) || !(sc->dev[1] = hm_pool_device_alloc((size_t)plane * (chw ? p.channels : 1) * sizeof(float)))) return HM_ERR_NO_DEVICE;
+  if ((rc = hm_check_hip(hipMemcpyAsync(sc->dev[0], host, bytes, hipMemcpyHostToDevice, s), "upload of the tap tables"))) return rc;
+  hm_resample_args a;
+  std::memset(&a, 0, sizeof(a));
+  a.sample_bytes = p.sample_bytes; a.channels = p.channels;
+  a.src = origin; a.src_stride = src_stride;
+  a.n_w = vp->w; a.n_h = vp->h; a.ow = vp->ow; a.oh = vp->oh;
+  const int32_t* dx = (const int32_t*)sc->dev[0];
+  const int32_t* dy = dx + words_x;
+  a.ax.first = dx; a.ax.count = dx + vp->ow; a.ax.weights = reinterpret_cast<const float*>(dx + 2 * (size_t)vp->ow); a.ax.m = vp->ow; a.ax.taps = tx;
+  a.ay.first = dy; a.ay.count = dy + vp->oh; a.ay.weights = reinterpret_cast<const float*>(dy + 2 * (size_t)vp->oh); a.ay.m = vp->oh; a.ay.taps = ty;
+  a.tmp = (float*)sc->dev[1]; a.tmp_pitch = pitch; a.tmp_plane = plane;
+  return hm_launch_resample(&p, &a, d->ptr, d->scale, d->bias, s);
+}
+
+// hm_resample_to_tensor returns before its kernels have run: the blocks they work on go back to the pools once the stream has
+// passed them.  The stream's host function only hands them to this list (no HIP call there); the next call releases them.
+namespace {
+std::mutex g_done_mu;
+std::vector<hm_view_scratch> g_done;
+void scratch_done(void* arg)
+{
+  hm_view_scratch* sc = static_cast<hm_view_scratch*>(arg);
+  { std::lock_guard<std::mutex> g(g_done_mu); g_done.push_back(*sc); }
+  delete sc;
+}
+void release_done()
+{
+  std::vector<hm_view_scratch> v;
+  { std::lock_guard<std::mutex> g(g_done_mu); v.swap(g_done); }
+  for (hm_view_scratch& sc : v) hm_view_scratch_free(&sc);
+}
+} // namespace
+
+int hm_resample_to_tensor(int out_format, int src_w, int src_h, const void* d_src, int src_stride, const hm_device_view* view, const hm_device_dest* dest, void* stream)
+{
+  if (!d_src || !dest || !view) return hm_fail(HM_ERR_INVALID_ARG, "null argument");
+  int rc = hm_dest_check_static(out_format, dest);
+  if (rc) return rc;
+  if (src_w <= 0 || src_h <= 0 || src_w > 32768 || src_h > 32768) return hm_fail(HM_ERR_INVALID_ARG, "image size %d x %d", src_w, src_h);
+  hm_view_plan vp;
+  if ((rc = hm_view_resolve(out_format, src_w, src_h, view, &vp))) return rc;
+  hm_dest_plan p;
+  if ((rc = hm_dest_resolve(out_format, vp.ow, vp.oh, dest, &p)) || (rc = hm_dest_check_len(dest, &p))) return rc;
+  if (src_stride < src_w * hm_out_bytes_per_pixel(out_format)) return hm_fail(HM_ERR_INVALID_ARG, "src_stride %d below the bytes of a row", src_stride);
+  if (p.sample_bytes == 2 && (((uintptr_t)d_src | (unsigned)src_stride) & 1)) return hm_fail(HM_ERR_INVALID_ARG, "16-bit samples at an odd address or stride");
+  int n_dev = 0;
+  if (hipGetDeviceCount(&n_dev) != hipSuccess || n_dev == 0) { (void)hipGetLastError(); return hm_fail(HM_ERR_NO_DEVICE, "no HIP device available"); }
+  if ((rc = hm_dest_check_pointer(dest))) return rc;
+  release_done();
+  hm_view_scratch* sc = new (std::nothrow) hm_view_scratch();
+  if (!sc) return hm_fail(HM_ERR_NOMEM, "out of memory");
+  rc = hm_view_write(dest, out_format, &vp, d_src, src_stride, (hipStream_t)stream, sc);
+  if (!sc->dev[0] && !sc->dev[1] && !sc->pinned) { delete sc; return rc; }
+  if (hipLaunchHostFunc((hipStream_t)stream, scratch_done, sc) != hipSuccess) { // (never on a healthy runtime: wait, then release here)
+    (void)hipGetLastError();
+    hipStreamSynchronize((hipStream_t)stream);
+    hm_view_scratch_free(sc);
+    delete sc;
+  }
+  return rc;
 }
 
 } // extern "C"

@@ -32,6 +32,36 @@ int hm_dest_write(const hm_device_dest* d, int out_format, int w, int h, int y0,
 int hm_launch_to_tensor(const hm_dest_plan* p, const void* src, int src_stride, int w, int rows, void* dst, const float scale[4], const float bias[4],
                         hipStream_t s);
 
+// ---- views (hm_device_view): a rectangle of the image at a size of the caller's choice.  devdest.cpp holds the checks and the tap
+//      tables, resample.hip the kernels ----
+typedef struct hm_view_plan {
+  int32_t x, y, w, h;    // the crop, inside the source
+  int32_t ow, oh;        // the size written
+  int32_t filter;
+  int32_t crop_only;     // out_w == out_h == 0: the bytes of the rectangle
+} hm_view_plan;
+// device / pinned blocks a view write works on; they must live until the stream has passed the write (hm_view_scratch_free)
+typedef struct hm_view_scratch { void* dev[2]; void* pinned; } hm_view_scratch;
+void hm_view_scratch_free(hm_view_scratch* sc);
+// the view against a src_w x src_h image and the target: every refusal of the view itself
+int hm_view_resolve(int out_format, int src_w, int src_h, const hm_device_view* v, hm_view_plan* vp);
+// the rectangle vp of `src` (interleaved pixels of out_format, row 0 = image row 0) into the destination, which has been checked
+// against vp->ow x vp->oh; asynchronous on `s`
+int hm_view_write(const hm_device_dest* d, int out_format, const hm_view_plan* vp, const void* src, int src_stride, hipStream_t s, hm_view_scratch* sc);
+
+// one axis' taps as the kernels read them: first[m], count[m], weights[taps][m] (tap-major: consecutive outputs are neighbours)
+typedef struct hm_view_axis { const int32_t* first; const int32_t* count; const float* weights; int32_t m, taps; } hm_view_axis;
+typedef struct hm_resample_args {
+  int32_t sample_bytes, channels;       // of the source
+  const void* src; int32_t src_stride;  // at the crop's origin
+  int32_t n_w, n_h, ow, oh;
+  hm_view_axis ax, ay;                  // device pointers
+  float* tmp; int64_t tmp_pitch, tmp_plane; // the horizontal pass' float32 rows (elements), laid out like the destination
+} hm_resample_args;
+int hm_launch_resample(const hm_dest_plan* p, const hm_resample_args* a, void* dst, const float scale[4], const float bias[4], hipStream_t s);
+int hm_launch_view_nearest(const hm_dest_plan* p, const void* src, int src_stride, int n_w, int n_h, int ow, int oh, void* dst, const float scale[4],
+                           const float bias[4], hipStream_t s);
+
 #ifdef __cplusplus
 }
 #endif

@@ -640,11 +640,71 @@ int planar_from_blobs(const hm_file* f, ItemPlan& P, const hm_decode_params* par
 
 namespace hm_img {
 
+// The sub-grid of tile rows and columns a view's crop intersects, where decoding only those tiles provably changes no pixel of the
+// crop: the item is a grid, no transformation is applied on it or on a covered tile, neither it nor a tile has an alpha image, chroma
+// up-sampling is the default one (the colour ops then read chroma at x >> 1, y >> 1) and the sub-grid's origin is even in every
+// subsampled direction (an odd one moves a column / row further out).  t = first tile row, row count, first tile column, column count;
+// origin and size of the sub-grid's canvas in x0, y0, w, h.  false: the whole item is decoded (t = the whole grid).
+// Item properties only: no coded picture is looked at.
+bool view_subgrid(const hm_file* f, uint32_t id, const hm_decode_params* params, const hm_device_view* v, int32_t t[4], int* x0, int* y0, int* w, int* h)
+{
+  t[0] = 0; t[1] = 1; t[2] = 0; t[3] = 1;
+  const hm::Item* it = f->file.item(id);
+  if (!it || it->type != "grid") return false;
+  hm::GridInfo g;
+  hm::HeifError err;
+  if (!f->file.grid_info(id, g, err) || g.rows < 1 || g.cols < 1 || g.tiles.size() != (size_t)g.rows * g.cols) return false;
+  t[1] = g.rows; t[3] = g.cols;
+  if (!v || (v->crop_w == 0 && v->crop_h == 0)) return false;
+  if (params->chroma_upsampling != 0 || hm_out_is_planar(params->out_format) || params->out_format == 0) return false;
+  if (!params->ignore_transformations && !it->props.transforms.empty()) return false;
+  if (f->file.alpha_item_of(id)) return false;
+  const int gw = (int)g.width, gh = (int)g.height;
+  if (v->crop_w <= 0 || v->crop_h <= 0 || v->crop_x < 0 || v->crop_y < 0 || (int64_t)v->crop_x + v->crop_w > gw || (int64_t)v->crop_y + v->crop_h > gh) return false;
+  const hm::Item* t0 = f->file.item(g.tiles[0]);
+  if (!t0 || !t0->props.hvcc.present) return false;
+  const int iw = t0->props.ispe_width, ih = t0->props.ispe_height, chroma = t0->props.hvcc.chroma_format;
+  if (iw <= 0 || ih <= 0 || (int64_t)iw * g.cols < gw || (int64_t)ih * g.rows < gh) return false;
+  for (uint32_t tid : g.tiles)
+    if (f->file.alpha_item_of(tid)) return false;
+  int c0 = v->crop_x / iw, c1 = (v->crop_x + v->crop_w - 1) / iw, r0 = v->crop_y / ih, r1 = (v->crop_y + v->crop_h - 1) / ih;
+  if ((chroma == 1 || chroma == 2) && ((c0 * iw) & 1)) c0--; // (odd tile width, odd column: the column before starts even)
+  if (chroma == 1 && ((r0 * ih) & 1)) r0--;
+  for (int r = r0; r <= r1; r++)
+    for (int c = c0; c <= c1; c++) {
+      const hm::Item* ti = f->file.item(g.tiles[(size_t)r * g.cols + c]);
+      if (!ti || ti->type != "hvc1" || ti->props.ispe_width != iw || ti->props.ispe_height != ih) return false;
+      if (!params->ignore_transformations && !ti->props.transforms.empty()) return false;
+    }
+  t[0] = r0; t[1] = r1 - r0 + 1; t[2] = c0; t[3] = c1 - c0 + 1;
+  *x0 = c0 * iw; *y0 = r0 * ih;
+  *w = std::min(t[3] * iw, gw - *x0); *h = std::min(t[1] * ih, gh - *y0);
+  return true;
+}
+
 int job_plan(DecodeJob& j)
 {
   int rc = plan_item(j.f, j.id, j.item[0]);
   if (rc) return rc;
   j.n_items = 1;
+  j.view_dx = j.view_dy = 0;
+  j.sub_tiles[0] = 0; j.sub_tiles[1] = j.item[0].rows; j.sub_tiles[2] = 0; j.sub_tiles[3] = j.item[0].cols;
+  int sx = 0, sy = 0, sw = 0, sh = 0;
+  if (j.has_view && view_subgrid(j.f, j.id, &j.params, &j.view, j.sub_tiles, &sx, &sy, &sw, &sh)) {
+    // the sub-grid becomes a grid of its own (what a slab is for tile rows): everything behind sees an ordinary smaller grid
+    ItemPlan& P = j.item[0];
+    const int32_t* t = j.sub_tiles;
+    std::vector<TilePlan> sub;
+    for (int r = t[0]; r < t[0] + t[1]; r++)
+      for (int c = t[2]; c < t[2] + t[3]; c++) sub.push_back(P.tiles[(size_t)r * P.cols + c]);
+    P.tiles.swap(sub);
+    P.rows = t[1]; P.cols = t[3]; P.canvas_w = sw; P.canvas_h = sh;
+    P.blobs.clear(); P.blobs.resize(P.tiles.size());
+    P.status.assign(P.tiles.size(), HM_OK);
+    P.messages.assign(P.tiles.size(), std::string());
+    j.view_dx = sx; j.view_dy = sy;
+    return HM_OK; // (no alpha image on the item: view_subgrid)
+  }
   // the alpha channel: an auxiliary image decoded like any image (context.cc:2029-2078)
   const uint32_t alpha_id = j.f->file.alpha_item_of(j.id);
   if (alpha_id) {
@@ -694,7 +754,8 @@ void parse_picture(const hm_file* f, uint32_t id, bool few_pictures, int strict,
 // planes - all queued on `s`.  `dout` and `alpha_sdr` must live until the stream has drained.
 // dest (may be NULL): caller-owned device memory the interleaved pixels go to instead (hm_device_dest); nothing is copied to the host then.
 int emit_image(const hm_decode_params* params, hipStream_t s, PlanarImage& I, const DevPlane* alpha, int alpha_bd, DevMem& dout,
-               DevPlane& alpha_sdr, hm_decoded* out, const hm_device_dest* dest = nullptr)
+               DevPlane& alpha_sdr, hm_decoded* out, const hm_device_dest* dest = nullptr, const hm_device_view* view = nullptr,
+               hm_view_scratch* view_scratch = nullptr)
 {
   int rc;
   DevPlane (&P)[3] = I.P;
@@ -712,9 +773,13 @@ int emit_image(const hm_decode_params* params, hipStream_t s, PlanarImage& I, co
   // (context.cc:1538-1552: "different_chroma || different_colorspace"; the depth alone - convert_hdr_to_8bit - does not)
   const bool planar_target = hm_out_is_planar(params->out_format);
   const bool as_decoded = params->out_format == 0 || (planar_target && chroma != 0 && chroma == hm_out_planar_chroma(params->out_format));
+  hm_view_plan vp; // view: a rectangle of the image at vp.ow x vp.oh goes to the destination (the resampling step instead of hm_dest_write)
+  std::memset(&vp, 0, sizeof(vp));
+  vp.ow = img_w; vp.oh = img_h;
   if (dest) { // (the entry points have refused all of this already, against the size the file declares: here it is the decoded size)
     hm_dest_plan dp;
-    if ((rc = hm_dest_resolve(params->out_format, img_w, img_h, dest, &dp)) || (rc = hm_dest_check_len(dest, &dp))) return rc;
+    if (view && (rc = hm_view_resolve(params->out_format, img_w, img_h, view, &vp))) return rc;
+    if ((rc = hm_dest_resolve(params->out_format, vp.ow, vp.oh, dest, &dp)) || (rc = hm_dest_check_len(dest, &dp))) return rc;
   }
   if (as_decoded) { // native planar YCbCr
     out->out_format = params->out_format;
@@ -827,9 +892,14 @@ int emit_image(const hm_decode_params* params, hipStream_t s, PlanarImage& I, co
     out->stride[0] = cd.out_stride;
     out->plane_width[0] = img_w; out->plane_height[0] = img_h;
     if (dest) { // the image's w x h x C elements and nothing else: a 2-D device copy or k_to_tensor (devdest.cpp)
-      if ((rc = hm_dest_write(dest, params->out_format, img_w, img_h, 0, img_h, dout.p, cd.out_stride, s))) return rc;
+      if (view) {
+        if ((rc = hm_view_write(dest, params->out_format, &vp, dout.p, cd.out_stride, s, view_scratch))) return rc;
+        out->width = vp.ow; out->height = vp.oh;
+        out->plane_width[0] = vp.ow; out->plane_height[0] = vp.oh;
+      }
+      else if ((rc = hm_dest_write(dest, params->out_format, img_w, img_h, 0, img_h, dout.p, cd.out_stride, s))) return rc;
       hm_dest_plan dp;
-      if ((rc = hm_dest_resolve(params->out_format, img_w, img_h, dest, &dp))) return rc;
+      if ((rc = hm_dest_resolve(params->out_format, vp.ow, vp.oh, dest, &dp))) return rc;
       out->used_ext_dst = 1;
       out->stride[0] = (int32_t)std::min<int64_t>(dp.row_pitch, 0x7FFFFFFF);
     }
@@ -897,13 +967,15 @@ int job_enqueue(DecodeJob& j, hm_decoded* out)
   }
   const int alpha_bd = j.n_items > 1 ? A.bd : I.tile_alpha_bd;
   lap("planar decode queued");
-  rc = emit_image(params, s, I, alpha, alpha_bd, j.dout, j.alpha_sdr, out, j.has_dest ? &j.dest : nullptr);
+  hm_device_view shifted = j.view; // (the crop inside the sub-grid that was decoded)
+  if (j.has_view && (shifted.crop_w || shifted.crop_h)) { shifted.crop_x -= j.view_dx; shifted.crop_y -= j.view_dy; }
+  rc = emit_image(params, s, I, alpha, alpha_bd, j.dout, j.alpha_sdr, out, j.has_dest ? &j.dest : nullptr, j.has_view ? &shifted : nullptr, &j.view_scratch);
   if (rc) return rc;
   lap("colour + D2H queued");
   return HM_OK;
 }
 
-int check_device_request(const hm_file* f, uint32_t id, const hm_decode_params* params, const hm_device_dest* dest)
+int check_device_request(const hm_file* f, uint32_t id, const hm_decode_params* params, const hm_device_dest* dest, const hm_device_view* view)
 {
   if (params->ext_dst) return hm_fail(HM_ERR_INVALID_ARG, "params->ext_dst must be NULL with a device destination");
   int rc = hm_dest_check_static(params->out_format, dest);
@@ -913,7 +985,10 @@ int check_device_request(const hm_file* f, uint32_t id, const hm_decode_params* 
   if (hm_file_image_info(f, id, &info) == HM_OK) { // (a file that fails here fails the decode with its own message)
     const int w = params->ignore_transformations ? info.coded_width : info.width, h = params->ignore_transformations ? info.coded_height : info.height;
     hm_dest_plan dp;
-    if (w > 0 && h > 0 && ((rc = hm_dest_resolve(params->out_format, w, h, dest, &dp)) || (rc = hm_dest_check_len(dest, &dp)))) return rc;
+    hm_view_plan vp;
+    vp.ow = w; vp.oh = h;
+    if (view && w > 0 && h > 0 && (rc = hm_view_resolve(params->out_format, w, h, view, &vp))) return rc;
+    if (w > 0 && h > 0 && ((rc = hm_dest_resolve(params->out_format, vp.ow, vp.oh, dest, &dp)) || (rc = hm_dest_check_len(dest, &dp)))) return rc;
   }
   int n_dev = 0;
   if (hipGetDeviceCount(&n_dev) != hipSuccess || n_dev == 0) { (void)hipGetLastError(); return hm_fail(HM_ERR_NO_DEVICE, "no HIP device available"); }
@@ -939,7 +1014,7 @@ extern "C" {
 
 static int decode_grid_cut(const hm_file* f, uint32_t id, const hm_decode_params* params, const int32_t* devices, int n_devices, bool pipelined, hm_decoded* out, bool* applicable,
                            const hm_device_dest* dest = nullptr); // (below, behind the slabs)
-static int decode_item(const hm_file* f, uint32_t id, const hm_decode_params* params, const hm_device_dest* dest, hm_decoded* out);
+static int decode_item(const hm_file* f, uint32_t id, const hm_decode_params* params, const hm_device_dest* dest, hm_decoded* out, const hm_device_view* view = nullptr);
 
 int hm_decode_item(const hm_file* f, uint32_t id, const hm_decode_params* params, hm_decoded* out)
 {
@@ -956,11 +1031,30 @@ int hm_decode_item_to_device(const hm_file* f, uint32_t id, const hm_decode_para
   return decode_item(f, id, params, dest, out);
 }
 
-// dest (may be NULL): the pixels go to caller-owned device memory
-static int decode_item(const hm_file* f, uint32_t id, const hm_decode_params* params, const hm_device_dest* dest, hm_decoded* out)
+int hm_decode_item_to_device_view(const hm_file* f, uint32_t id, const hm_decode_params* params, const hm_device_view* view, const hm_device_dest* dest, hm_decoded* out)
+{
+  if (!f || !params || !view || !dest || !out) return hm_fail(HM_ERR_INVALID_ARG, "null argument");
+  std::memset(out, 0, sizeof(*out));
+  const int rc = check_device_request(f, id, params, dest, view); // refused before any work is queued: the destination is not written
+  if (rc) return rc;
+  return decode_item(f, id, params, dest, out, view);
+}
+
+int hm_plan_view(const hm_file* f, uint32_t id, const hm_decode_params* params, const hm_device_view* view, int32_t tiles[4])
+{
+  if (!f || !params || !view || !tiles) return hm_fail(HM_ERR_INVALID_ARG, "null argument");
+  if (!f->file.item(id)) return hm_fail(HM_ERR_INVALID_ARG, "no item %u", id);
+  int x0, y0, w, h;
+  view_subgrid(f, id, params, view, tiles, &x0, &y0, &w, &h);
+  return HM_OK;
+}
+
+// dest (may be NULL): the pixels go to caller-owned device memory; view (may be NULL, with dest only): a rectangle of them, resampled -
+// always as one job (its plan is reduced to the tiles the crop touches), never slab by slab
+static int decode_item(const hm_file* f, uint32_t id, const hm_decode_params* params, const hm_device_dest* dest, hm_decoded* out, const hm_device_view* view)
 {
   std::memset(out, 0, sizeof(*out)); // (whatever fails below: nothing of an earlier call is left in it)
-  { // (r06) a grid of more tiles than parsing threads, to interleaved pixels: slab by slab under the entropy decode (decode_grid_cut)
+  if (!view) { // (r06) a grid of more tiles than parsing threads, to interleaved pixels: slab by slab under the entropy decode (decode_grid_cut)
     bool applicable = false;
     const int prc = decode_grid_cut(f, id, params, nullptr, 1, /*pipelined=*/true, out, &applicable, dest);
     if (prc || applicable) return prc;
@@ -970,6 +1064,7 @@ static int decode_item(const hm_file* f, uint32_t id, const hm_decode_params* pa
   DecodeJob job;
   job.f = f; job.id = id; job.params = *params; job.s = (hipStream_t)params->stream;
   if (dest) { job.dest = *dest; job.has_dest = true; }
+  if (view) { job.view = *view; job.has_view = true; }
   int rc = job_plan(job);
   if (rc) return rc;
   // ---- host: entropy-decode every coded picture (CABAC on the CPU, spread over threads like the reference's

@@ -105,6 +105,14 @@ struct DecodeJob {
   hm_decode_params params{};
   hm_device_dest dest{};  // caller-owned device memory the pixels go to instead of pinned host memory (has_dest; hm_decode_params
   bool has_dest = false;  // keeps its layout, so the destination travels beside the job's copy of it)
+  // a view of the image goes to the destination (hm_device_view): job_plan reduces item[0] to the sub-grid of tiles the crop touches
+  // where that changes no pixel - sub_tiles = its first tile row, row count, first tile column, column count in the whole grid -
+  // and the crop moves by the sub-grid's origin (view_dx, view_dy)
+  hm_device_view view{};
+  bool has_view = false;
+  int view_dx = 0, view_dy = 0;
+  int32_t sub_tiles[4] = {0, 0, 0, 0};
+  hm_view_scratch view_scratch{}; // tap tables and the intermediate of the resampling step
   hipStream_t s = nullptr;
   ItemPlan item[2];   // [0] the image, [1] its alpha auxiliary image
   int n_items = 0;
@@ -117,7 +125,11 @@ struct DecodeJob {
   bool enqueued = false;
   // everything above is touched by asynchronous work: the stream is drained before any of it is released (the pool may
   // hand a freed block to another thread at once)
-  ~DecodeJob() { if (enqueued) hipStreamSynchronize(s); }
+  ~DecodeJob()
+  {
+    if (enqueued) hipStreamSynchronize(s);
+    hm_view_scratch_free(&view_scratch);
+  }
 };
 
 int job_plan(DecodeJob& j);
@@ -129,7 +141,8 @@ void parse_picture(const hm_file* f, uint32_t id, bool few_pictures, int strict,
 int job_enqueue(DecodeJob& j, hm_decoded* out);
 // everything about a device destination that can be refused before the entropy decode: the request itself, the destination against
 // the size the file declares for the item, a device, the pointer (hm_image.cpp)
-int check_device_request(const hm_file* f, uint32_t id, const hm_decode_params* params, const hm_device_dest* dest);
+// view (may be NULL): the destination is judged against the view's output size, the crop against the declared size
+int check_device_request(const hm_file* f, uint32_t id, const hm_decode_params* params, const hm_device_dest* dest, const hm_device_view* view = nullptr);
 int job_complete(DecodeJob& j, hm_decoded* out);
 
 } // namespace hm_img

@@ -182,7 +182,7 @@ void hm_pipeline_destroy(hm_pipeline* p)
   delete p;
 }
 
-static int submit(hm_pipeline* p, const uint8_t* heif, size_t size, uint32_t item_id, uint64_t tag, const hm_device_dest* dest);
+static int submit(hm_pipeline* p, const uint8_t* heif, size_t size, uint32_t item_id, uint64_t tag, const hm_device_dest* dest, const hm_device_view* view = nullptr);
 
 int hm_pipeline_submit(hm_pipeline* p, const uint8_t* heif, size_t size, uint32_t item_id, uint64_t tag)
 {
@@ -196,8 +196,16 @@ int hm_pipeline_submit_to_device(hm_pipeline* p, const uint8_t* heif, size_t siz
   return submit(p, heif, size, item_id, tag, dest);
 }
 
-// dest (may be NULL): the image's pixels go to caller-owned device memory of the pipeline's device
-static int submit(hm_pipeline* p, const uint8_t* heif, size_t size, uint32_t item_id, uint64_t tag, const hm_device_dest* dest)
+int hm_pipeline_submit_to_device_view(hm_pipeline* p, const uint8_t* heif, size_t size, uint32_t item_id, uint64_t tag, const hm_device_view* view,
+                                      const hm_device_dest* dest)
+{
+  if (!p || !heif || !view || !dest) return hm_fail(HM_ERR_INVALID_ARG, "null argument");
+  return submit(p, heif, size, item_id, tag, dest, view);
+}
+
+// dest (may be NULL): the image's pixels go to caller-owned device memory of the pipeline's device; view (may be NULL, with dest only):
+// a rectangle of them, resampled - job_plan then queues only the coded pictures the crop touches
+static int submit(hm_pipeline* p, const uint8_t* heif, size_t size, uint32_t item_id, uint64_t tag, const hm_device_dest* dest, const hm_device_view* view)
 {
   hipStream_t stream = nullptr;
   {
@@ -230,9 +238,10 @@ static int submit(hm_pipeline* p, const uint8_t* heif, size_t size, uint32_t ite
       int prev = -1;
       hipGetDevice(&prev);
       hipSetDevice(p->cfg.device); // (the pointer must belong to the device the crew works on)
-      rc = check_device_request(im->file, im->job.id, &im->job.params, dest);
+      rc = check_device_request(im->file, im->job.id, &im->job.params, dest, view);
       if (prev >= 0) hipSetDevice(prev);
       im->job.dest = *dest; im->job.has_dest = true;
+      if (view) { im->job.view = *view; im->job.has_view = true; }
     }
     if (!rc) rc = job_plan(im->job);
   }

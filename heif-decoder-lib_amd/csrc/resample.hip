@@ -1,0 +1,239 @@
+// resample.hip — a view (hm_device_view) of the colour stage's interleaved pixels into a tensor in caller-owned device memory (gfx950):
+// a rectangle of the image, resampled to the size the caller asks for, as u8 / u16 / f16 / f32 in CHW or HWC.
+//   k_resample_h     the horizontal pass: rows of the crop -> float32 rows of out_w.  A lane sits on one (output column, source row)
+//                    pair and walks its taps over contiguous source bytes; a wave is 64 consecutive columns of ONE row, and the tap
+//                    table is tap-major (weights[tap][column]), so the wave's weight reads and its stores are contiguous.  The
+//                    intermediate is laid out like the destination: one plane per channel for CHW, interleaved for HWC.
+//   k_resample_v     the vertical pass, fused with dtype, layout, scale and bias: a wave is 64 consecutive element groups of ONE output
+//                    row (of one plane), so its taps are wave-uniform and the intermediate reads and the tensor stores coalesce.  A lane's
+//                    group is 16 bytes of output (one 16-byte store) where pointer and pitches allow, one element otherwise.
+//   k_view_nearest   HM_VIEW_NEAREST: the sample at j * n / m is moved (through scale and bias for float destinations), no intermediate.
+// The sums run tap by tap in float32 with separately rounded multiply and add (-ffp-contract=off, __fmul_rn / __fadd_rn): a float32
+// restatement on the host is exact.  Nothing but the out_w x out_h x C elements of the view is ever stored.
+#include <hip/hip_runtime.h>
+#include <hip/hip_fp16.h>
+#include <stdint.h>
+
+#include <type_traits>
+
+#include "hm_devdest.h"
+
+namespace {
+
+struct Affine { float scale[4], bias[4]; };
+
+// the vertical sum r to an element of the destination
+template <typename OutT> __device__ __forceinline__ OutT finish(float r, float sc, float bi);
+template <> __device__ __forceinline__ uint8_t finish<uint8_t>(float r, float, float) { const int v = (int)__fadd_rn(r, 0.5f); return (uint8_t)min(max(v, 0), 255); }
+template <> __device__ __forceinline__ uint16_t finish<uint16_t>(float r, float, float) { const int v = (int)__fadd_rn(r, 0.5f); return (uint16_t)min(max(v, 0), 65535); }
+template <> __device__ __forceinline__ float finish<float>(float r, float sc, float bi) { return __fadd_rn(__fmul_rn(r, sc), bi); }
+template <> __device__ __forceinline__ __half finish<__half>(float r, float sc, float bi) { return __float2half_rn(__fadd_rn(__fmul_rn(r, sc), bi)); }
+
+// a sample that is moved, not computed (k_to_tensor's rule)
+template <typename OutT> __device__ __forceinline__ OutT moved(unsigned v, float sc, float bi);
+template <> __device__ __forceinline__ uint8_t moved<uint8_t>(unsigned v, float, float) { return (uint8_t)v; }
+template <> __device__ __forceinline__ uint16_t moved<uint16_t>(unsigned v, float, float) { return (uint16_t)v; }
+template <> __device__ __forceinline__ float moved<float>(unsigned v, float sc, float bi) { return __fadd_rn(__fmul_rn((float)v, sc), bi); }
+template <> __device__ __forceinline__ __half moved<__half>(unsigned v, float sc, float bi) { return __float2half_rn(__fadd_rn(__fmul_rn((float)v, sc), bi)); }
+
+// SB: bytes per source sample (little-endian), C: channels, CHW: the intermediate has one plane per channel.
+// grid: x = groups of 64 output columns, y = groups of 4 source rows.  src points at the crop's origin.
+template <int SB, int C, bool CHW>
+__global__ __launch_bounds__(256) void k_resample_h(const uint8_t* __restrict__ src, int src_stride, int n_h, int ow, const int32_t* __restrict__ first,
+                                                    const int32_t* __restrict__ count, const float* __restrict__ wts, float* __restrict__ tmp,
+                                                    long long pitch, long long plane)
+{
+  typedef typename std::conditional<SB == 1, uint8_t, uint16_t>::type InT;
+  const int j = blockIdx.x * 64 + (threadIdx.x & 63), y = blockIdx.y * 4 + (threadIdx.x >> 6);
+  if (j >= ow || y >= n_h) return;
+  const InT* in = reinterpret_cast<const InT*>(src + (size_t)y * src_stride) + (size_t)first[j] * C;
+  const int n = count[j];
+  float t[C];
+#pragma unroll
+  for (int c = 0; c < C; c++) t[c] = 0.0f;
+  for (int i = 0; i < n; i++) {
+    const float w = wts[(size_t)i * ow + j];
+#pragma unroll
+    for (int c = 0; c < C; c++) t[c] = __fadd_rn(t[c], __fmul_rn(w, (float)in[i * C + c]));
+  }
+  float* o = tmp + (long long)y * pitch;
+#pragma unroll
+  for (int c = 0; c < C; c++) {
+    if (CHW) o[(long long)c * plane + j] = t[c];
+    else o[(size_t)j * C + c] = t[c];
+  }
+}
+
+// P: elements of one row per lane (16 bytes of output, or 1), C: channels of an interleaved row (HWC), 0 = one plane per channel
+// (CHW: blockIdx.z is the channel).  E: elements per row (out_w, or out_w * C).  grid: x = groups of 64 lanes, y = groups of 4
+// output rows, z = planes.  The intermediate's pitch is a multiple of 16 elements, so a ragged last group loads whole vectors
+// (of padding nobody stores).
+template <typename OutT, int P, int C>
+__global__ __launch_bounds__(256) void k_resample_v(const float* __restrict__ tmp, long long pitch, long long plane, int E, int oh,
+                                                    const int32_t* __restrict__ first, const int32_t* __restrict__ count, const float* __restrict__ wts,
+                                                    uint8_t* __restrict__ dst, long long row_pitch, long long plane_pitch, Affine a)
+{
+  const int k = blockIdx.y * 4 + (threadIdx.x >> 6), pl = blockIdx.z;
+  if (k >= oh) return;
+  const int e0 = (blockIdx.x * 64 + (threadIdx.x & 63)) * P;
+  if (e0 >= E) return;
+  const int y0 = first[k], n = count[k]; // (the same in every lane of the wave)
+  const float* col = tmp + (long long)pl * plane + (long long)y0 * pitch + e0;
+  float acc[P];
+#pragma unroll
+  for (int q = 0; q < P; q++) acc[q] = 0.0f;
+  for (int i = 0; i < n; i++) {
+    const float w = wts[(size_t)i * oh + k];
+    float v[P];
+    if constexpr (P == 1) v[0] = col[0];
+    else {
+#pragma unroll
+      for (int q = 0; q < P / 4; q++) {
+        const float4 f = reinterpret_cast<const float4*>(col)[q];
+        v[4 * q] = f.x; v[4 * q + 1] = f.y; v[4 * q + 2] = f.z; v[4 * q + 3] = f.w;
+      }
+    }
+#pragma unroll
+    for (int q = 0; q < P; q++) acc[q] = __fadd_rn(acc[q], __fmul_rn(w, v[q]));
+    col += pitch;
+  }
+  OutT o[P];
+#pragma unroll
+  for (int q = 0; q < P; q++) {
+    const int c = C == 0 ? pl : (e0 + q) % (C == 0 ? 1 : C);
+    o[q] = finish<OutT>(acc[q], a.scale[c], a.bias[c]);
+  }
+  OutT* op = reinterpret_cast<OutT*>(dst + (long long)pl * plane_pitch + (long long)k * row_pitch) + e0;
+  if (P > 1 && e0 + P <= E) {
+    uint4 pk;
+    __builtin_memcpy(&pk, o, 16);
+    *reinterpret_cast<uint4*>(op) = pk;
+    return;
+  }
+  const int left = E - e0 < P ? E - e0 : P;
+  for (int q = 0; q < left; q++) op[q] = o[q];
+}
+
+// HM_VIEW_NEAREST: out pixel (j, k) is source pixel (j * n_w / ow, k * n_h / oh).  grid: x = groups of 64 columns, y = groups of 4 rows.
+template <typename InT, typename OutT>
+__global__ __launch_bounds__(256) void k_view_nearest(const uint8_t* __restrict__ src, int src_stride, int n_w, int n_h, int ow, int oh, int C, int chw,
+                                                      uint8_t* __restrict__ dst, long long row_pitch, long long plane_pitch, Affine a)
+{
+  const int j = blockIdx.x * 64 + (threadIdx.x & 63), k = blockIdx.y * 4 + (threadIdx.x >> 6);
+  if (j >= ow || k >= oh) return;
+  const int sx = j * n_w / ow, sy = k * n_h / oh;
+  const InT* in = reinterpret_cast<const InT*>(src + (size_t)sy * src_stride) + (size_t)sx * C;
+  uint8_t* orow = dst + (long long)k * row_pitch;
+  for (int c = 0; c < C; c++) {
+    const OutT o = moved<OutT>(in[c], a.scale[c], a.bias[c]);
+    OutT* op = chw ? reinterpret_cast<OutT*>(orow + (long long)c * plane_pitch) + j : reinterpret_cast<OutT*>(orow) + (size_t)j * C + c;
+    *op = o;
+  }
+}
+
+#define HM_V_SET(T) \
+  (const void*)k_resample_v<T, 16 / (int)sizeof(T), 0>, (const void*)k_resample_v<T, 16 / (int)sizeof(T), 3>, (const void*)k_resample_v<T, 16 / (int)sizeof(T), 4>, \
+  (const void*)k_resample_v<T, 1, 0>, (const void*)k_resample_v<T, 1, 3>, (const void*)k_resample_v<T, 1, 4>
+// every instance the launchers below can pick (hm_debug_kernel_regs)
+const void* const g_instances[] = {
+  (const void*)k_resample_h<1, 3, true>, (const void*)k_resample_h<1, 3, false>, (const void*)k_resample_h<1, 4, true>, (const void*)k_resample_h<1, 4, false>,
+  (const void*)k_resample_h<2, 3, true>, (const void*)k_resample_h<2, 3, false>, (const void*)k_resample_h<2, 4, true>, (const void*)k_resample_h<2, 4, false>,
+  HM_V_SET(uint8_t), HM_V_SET(uint16_t), HM_V_SET(__half), HM_V_SET(float),
+  (const void*)k_view_nearest<uint8_t, uint8_t>, (const void*)k_view_nearest<uint8_t, __half>, (const void*)k_view_nearest<uint8_t, float>,
+  (const void*)k_view_nearest<uint16_t, uint16_t>, (const void*)k_view_nearest<uint16_t, __half>, (const void*)k_view_nearest<uint16_t, float>,
+};
+#undef HM_V_SET
+
+template <int SB, int C>
+void launch_h(bool chw, const hm_resample_args* r, hipStream_t s)
+{
+  const dim3 grid((unsigned)((r->ow + 63) / 64), (unsigned)((r->n_h + 3) / 4)), block(256);
+  const uint8_t* src = (const uint8_t*)r->src;
+  if (chw)
+    hipLaunchKernelGGL((k_resample_h<SB, C, true>), grid, block, 0, s, src, r->src_stride, r->n_h, r->ow, r->ax.first, r->ax.count, r->ax.weights, r->tmp,
+                       (long long)r->tmp_pitch, (long long)r->tmp_plane);
+  else
+    hipLaunchKernelGGL((k_resample_h<SB, C, false>), grid, block, 0, s, src, r->src_stride, r->n_h, r->ow, r->ax.first, r->ax.count, r->ax.weights, r->tmp,
+                       (long long)r->tmp_pitch, (long long)r->tmp_plane);
+}
+
+template <typename OutT, int P, int C>
+void launch_v_inst(const hm_dest_plan* p, const hm_resample_args* r, uint8_t* dst, const Affine& a, hipStream_t s)
+{
+  const int E = C == 0 ? r->ow : r->ow * C, groups = (E + P - 1) / P;
+  const dim3 grid((unsigned)((groups + 63) / 64), (unsigned)((r->oh + 3) / 4), (unsigned)(C == 0 ? p->channels : 1)), block(256);
+  hipLaunchKernelGGL((k_resample_v<OutT, P, C>), grid, block, 0, s, (const float*)r->tmp, (long long)r->tmp_pitch, (long long)r->tmp_plane, E, r->oh, r->ay.first,
+                     r->ay.count, r->ay.weights, dst, (long long)p->row_pitch, (long long)p->plane_pitch, a);
+}
+
+template <typename OutT>
+void launch_v(const hm_dest_plan* p, const hm_resample_args* r, uint8_t* dst, const Affine& a, hipStream_t s)
+{
+  constexpr int P = 16 / (int)sizeof(OutT);
+  const bool chw = p->layout == HM_DEV_LAYOUT_CHW;
+  const bool vec = ((uintptr_t)dst % 16) == 0 && (p->row_pitch % 16) == 0 && (!chw || (p->plane_pitch % 16) == 0);
+  if (chw) { if (vec) launch_v_inst<OutT, P, 0>(p, r, dst, a, s); else launch_v_inst<OutT, 1, 0>(p, r, dst, a, s); }
+  else if (p->channels == 3) { if (vec) launch_v_inst<OutT, P, 3>(p, r, dst, a, s); else launch_v_inst<OutT, 1, 3>(p, r, dst, a, s); }
+  else { if (vec) launch_v_inst<OutT, P, 4>(p, r, dst, a, s); else launch_v_inst<OutT, 1, 4>(p, r, dst, a, s); }
+}
+
+template <typename InT, typename OutT>
+void launch_nearest(const hm_dest_plan* p, const uint8_t* src, int src_stride, int n_w, int n_h, int ow, int oh, uint8_t* dst, const Affine& a, hipStream_t s)
+{
+  const dim3 grid((unsigned)((ow + 63) / 64), (unsigned)((oh + 3) / 4)), block(256);
+  hipLaunchKernelGGL((k_view_nearest<InT, OutT>), grid, block, 0, s, src, src_stride, n_w, n_h, ow, oh, p->channels, p->layout == HM_DEV_LAYOUT_CHW ? 1 : 0, dst,
+                     (long long)p->row_pitch, (long long)p->plane_pitch, a);
+}
+
+Affine affine_of(const float scale[4], const float bias[4])
+{
+  Affine a;
+  for (int c = 0; c < 4; c++) { a.scale[c] = scale[c]; a.bias[c] = bias[c]; }
+  return a;
+}
+
+} // namespace
+
+extern "C" const void* hm_resample_kernel_of(int index) // (test_hooks.cpp: hm_debug_kernel_regs)
+{
+  return index >= 0 && index < (int)(sizeof(g_instances) / sizeof(g_instances[0])) ? g_instances[index] : nullptr;
+}
+
+// both passes of a resampled view; `dst` = the destination's first element.  The intermediate is laid out like the destination
+// (r->tmp_plane apart per channel for CHW, interleaved rows for HWC), its pitch a multiple of 16 elements.
+extern "C" int hm_launch_resample(const hm_dest_plan* p, const hm_resample_args* r, void* dst, const float scale[4], const float bias[4], hipStream_t s)
+{
+  if (r->ow <= 0 || r->oh <= 0 || r->n_w <= 0 || r->n_h <= 0) return HM_OK;
+  if ((r->tmp_pitch % 16) || (r->tmp_plane % 4) || ((uintptr_t)r->tmp % 16)) return hm_fail(HM_ERR_INTERNAL, "k_resample: misaligned intermediate");
+  const bool chw = p->layout == HM_DEV_LAYOUT_CHW;
+  if (r->sample_bytes == 1) { if (r->channels == 3) launch_h<1, 3>(chw, r, s); else launch_h<1, 4>(chw, r, s); }
+  else { if (r->channels == 3) launch_h<2, 3>(chw, r, s); else launch_h<2, 4>(chw, r, s); }
+  int rc = hm_check_hip(hipGetLastError(), "k_resample_h launch");
+  if (rc) return rc;
+  const Affine a = affine_of(scale, bias);
+  uint8_t* out = (uint8_t*)dst;
+  switch (p->dtype) {
+    case HM_DEV_U8: launch_v<uint8_t>(p, r, out, a, s); break;
+    case HM_DEV_U16: launch_v<uint16_t>(p, r, out, a, s); break;
+    case HM_DEV_F16: launch_v<__half>(p, r, out, a, s); break;
+    case HM_DEV_F32: launch_v<float>(p, r, out, a, s); break;
+    default: return hm_fail(HM_ERR_INTERNAL, "k_resample_v: no kernel for dtype %d", p->dtype);
+  }
+  return hm_check_hip(hipGetLastError(), "k_resample_v launch");
+}
+
+extern "C" int hm_launch_view_nearest(const hm_dest_plan* p, const void* src, int src_stride, int n_w, int n_h, int ow, int oh, void* dst, const float scale[4],
+                                      const float bias[4], hipStream_t s)
+{
+  if (ow <= 0 || oh <= 0) return HM_OK;
+  const Affine a = affine_of(scale, bias);
+  const uint8_t* in = (const uint8_t*)src;
+  uint8_t* out = (uint8_t*)dst;
+  const bool wide = p->sample_bytes == 2;
+  if (p->dtype == HM_DEV_U8 && !wide) launch_nearest<uint8_t, uint8_t>(p, in, src_stride, n_w, n_h, ow, oh, out, a, s);
+  else if (p->dtype == HM_DEV_U16 && wide) launch_nearest<uint16_t, uint16_t>(p, in, src_stride, n_w, n_h, ow, oh, out, a, s);
+  else if (p->dtype == HM_DEV_F16) { if (wide) launch_nearest<uint16_t, __half>(p, in, src_stride, n_w, n_h, ow, oh, out, a, s); else launch_nearest<uint8_t, __half>(p, in, src_stride, n_w, n_h, ow, oh, out, a, s); }
+  else if (p->dtype == HM_DEV_F32) { if (wide) launch_nearest<uint16_t, float>(p, in, src_stride, n_w, n_h, ow, oh, out, a, s); else launch_nearest<uint8_t, float>(p, in, src_stride, n_w, n_h, ow, oh, out, a, s); }
+  else return hm_fail(HM_ERR_INTERNAL, "k_view_nearest: no kernel for dtype %d on %d-byte samples", p->dtype, p->sample_bytes);
+  return hm_check_hip(hipGetLastError(), "k_view_nearest launch");
+}

@@ -13,6 +13,7 @@ extern "C" const void* hm_chain_kernel_of(int log2_ctb, int bytes_per_sample, in
 extern "C" const void* hm_residual_kernel();                                             // residual.hip
 extern "C" const void* hm_tail420_kernel();                                              // filters.hip
 extern "C" const void* hm_tail420_kernel16();
+extern "C" const void* hm_resample_kernel_of(int index);                                    // resample.hip: NULL behind the last instance
 
 extern "C" {
 
@@ -26,6 +27,7 @@ __attribute__((visibility("default"))) int hm_debug_kernel_regs(int which, int a
   else if (which == 1) fn = hm_tail420_kernel();
   else if (which == 2) fn = hm_chain_kernel_of(a, b, c);
   else if (which == 3) fn = hm_tail420_kernel16();
+  else if (which == 4) fn = hm_resample_kernel_of(a); // (the view kernels: a = 0, 1, ... until the call fails)
   hipFuncAttributes fa;
   if (!fn || !out || hipFuncGetAttributes(&fa, fn) != hipSuccess) return -1;
   out[0] = fa.numRegs;

@@ -5,7 +5,9 @@
 
 Layouts: "chw" (one plane per channel) and "hwc" (the target's own interleaving).  dtypes: torch.uint8 / torch.uint16 (must be
 the target's own sample type: 8-bit "rgb" / "rgba", 16-bit "rrggbb_le" / "rrggbbaa_le" ...), torch.float16, torch.float32;
-floats are sample * scale[c] + bias[c], rounded after each step.  What the library refuses raises capi.HmError."""
+floats are sample * scale[c] + bias[c], rounded after each step.  crop=(x, y, w, h) and size=(w, h) ask for a rectangle of the image,
+resampled (filter "triangle": antialiased bilinear, or "nearest") in the step that writes the tensor; of a grid only the tiles the
+rectangle touches are decoded.  What the library refuses raises capi.HmError."""
 import ctypes as C
 import os
 
@@ -14,6 +16,7 @@ from . import capi
 OUT_FORMATS = {"rgb": capi.HM_OUT_RGB, "rgba": capi.HM_OUT_RGBA, "rrggbb_le": capi.HM_OUT_RRGGBB_LE, "rrggbb_be": capi.HM_OUT_RRGGBB_BE,
                "rrggbbaa_le": capi.HM_OUT_RRGGBBAA_LE, "rrggbbaa_be": capi.HM_OUT_RRGGBBAA_BE}
 LAYOUTS = {"hwc": capi.HM_DEV_LAYOUT_HWC, "chw": capi.HM_DEV_LAYOUT_CHW}
+FILTERS = {"triangle": capi.HM_VIEW_TRIANGLE, "nearest": capi.HM_VIEW_NEAREST}
 
 
 def _out_format(out_format):
@@ -80,6 +83,29 @@ def _dest_of(t, layout, dtype_code, c, scale, bias):
     return d
 
 
+def _view_of(crop, size, filter, w, h):
+    """(hm_device_view or None, width, height written) for an image of w x h"""
+    if crop is None and size is None:
+        return None, w, h
+    if str(filter).lower() not in FILTERS:
+        raise ValueError(f"filter {filter!r}: one of {sorted(FILTERS)}")
+    v = capi.DeviceView()
+    v.filter = FILTERS[str(filter).lower()]
+    if crop is not None:
+        x, y, cw, ch = (int(t) for t in crop)
+        if cw <= 0 or ch <= 0:
+            raise ValueError(f"crop {tuple(crop)}: (x, y, w, h) with a positive extent")
+        v.crop_x, v.crop_y, v.crop_w, v.crop_h = x, y, cw, ch
+        w, h = cw, ch
+    if size is not None:
+        ow, oh = (int(t) for t in size)
+        if ow <= 0 or oh <= 0:
+            raise ValueError(f"size {tuple(size)}: (w, h) with a positive extent")
+        v.out_w, v.out_h = ow, oh
+        w, h = ow, oh
+    return v, w, h
+
+
 def _default_threads():
     return max(1, min(16, os.cpu_count() or 1))
 
@@ -103,11 +129,12 @@ class _File:
 
 
 def decode_to_tensor(data, item_id=0, out_format="rgb", layout="chw", dtype=None, scale=None, bias=None, out=None, stream=None,
-                     host_threads=None):
+                     host_threads=None, crop=None, size=None, filter="triangle"):
     """Decode one image of a HEIF file (bytes; item_id 0 = the primary item) into a CUDA tensor: C x H x W ("chw") or H x W x C
     ("hwc").  dtype defaults to torch.float32 (out's dtype when out is given).  out: a CUDA tensor of that shape to write into;
     its row (and plane) stride is honoured, bytes between rows are left alone.  stream: a torch.cuda.Stream or a raw stream
-    handle (default: the current stream).  Returns when the pixels are in place."""
+    handle (default: the current stream).  crop: (x, y, w, h), a rectangle of the image; size: (w, h), what it is resampled to
+    (H and W of the tensor are then the size's, or the crop's); filter: "triangle" or "nearest".  Returns when the pixels are in place."""
     import torch
     L = capi.image_lib()
     fmt, lay = _out_format(out_format), _layout(layout)
@@ -117,6 +144,7 @@ def decode_to_tensor(data, item_id=0, out_format="rgb", layout="chw", dtype=None
     f = _File(data)
     try:
         iid, w, h = f.size(item_id)
+        view, w, h = _view_of(crop, size, filter, w, h)
         shape = _shape(lay, c, h, w)
         if out is None:
             out = torch.empty(shape, dtype=dtype, device="cuda")
@@ -132,7 +160,10 @@ def decode_to_tensor(data, item_id=0, out_format="rgb", layout="chw", dtype=None
         prm = capi.DecodeParams(fmt, host_threads or _default_threads(), 0, 0, handle or None, None, 0, 0, 0, 0)
         d = capi.Decoded()
         with torch.cuda.device(out.device):
-            capi.check_image(L.hm_decode_item_to_device(f.h, iid, C.byref(prm), C.byref(dest), C.byref(d)))
+            if view is None:
+                capi.check_image(L.hm_decode_item_to_device(f.h, iid, C.byref(prm), C.byref(dest), C.byref(d)))
+            else:
+                capi.check_image(L.hm_decode_item_to_device_view(f.h, iid, C.byref(prm), C.byref(view), C.byref(dest), C.byref(d)))
         if (d.width, d.height) != (w, h):  # (the library checked the destination against the decoded size: nothing else was written)
             raise capi.HmError(-3, f"the decoded image is {d.width} x {d.height}, the file declares {w} x {h}")
         L.hm_decoded_free(C.byref(d))
@@ -142,10 +173,12 @@ def decode_to_tensor(data, item_id=0, out_format="rgb", layout="chw", dtype=None
 
 
 def decode_batch_to_tensor(files, item_id=0, out_format="rgb", layout="chw", dtype=None, scale=None, bias=None, out=None,
-                           host_threads=None, max_in_flight=4):
+                           host_threads=None, max_in_flight=4, size=None, crops=None, filter="triangle"):
     """Decode N equally sized HEIF files through ONE hm_pipeline (the entropy decode of one file runs under the kernels of
     another) into one N x C x H x W ("chw") or N x H x W x C ("hwc") CUDA tensor, each image into its slice.  files: bytes
-    objects or paths.  A file of another size than the first (or than `out`) raises ValueError naming it."""
+    objects or paths.  A file of another size than the first (or than `out`) raises ValueError naming it.
+    size: (w, h) - files of different sizes are accepted then, each resampled into its slice; crops: one (x, y, w, h) or None per
+    file, the rectangle of that file that is resampled (needs size)."""
     import torch
     L = capi.image_lib()
     fmt, lay = _out_format(out_format), _layout(layout)
@@ -164,7 +197,14 @@ def decode_batch_to_tensor(files, item_id=0, out_format="rgb", layout="chw", dty
                 datas.append(fh.read())
     if not datas:
         raise ValueError("files: empty")
-    ids, size = [], None
+    if crops is not None and size is None:
+        raise ValueError("crops: needs size (the slices of one tensor are equally sized)")
+    if crops is not None and len(crops) != len(datas):
+        raise ValueError(f"crops: {len(crops)} entries for {len(datas)} files")
+    resized = size is not None
+    views = [None] * len(datas)
+    ids, size = [], (None if size is None else (int(size[0]), int(size[1])))
+    want = size
     if out is not None:
         if out.dim() != 4 or not out.is_cuda or out.dtype != dtype or out.shape[0] != len(datas):
             raise ValueError(f"out: a 4-D CUDA tensor of dtype {dtype} with {len(datas)} images is needed")
@@ -172,12 +212,16 @@ def decode_batch_to_tensor(files, item_id=0, out_format="rgb", layout="chw", dty
         size = (s[2], s[1]) if lay == capi.HM_DEV_LAYOUT_CHW else (s[1], s[0])
         if s != _shape(lay, c, size[1], size[0]):
             raise ValueError(f"out: shape {tuple(out.shape)} does not hold {c}-channel images in layout {layout!r}")
-    for name, data in zip(names, datas):
+        if resized and size != want:
+            raise ValueError(f"out: shape {tuple(out.shape)} does not hold images of size {want[0]} x {want[1]}")
+    for k, (name, data) in enumerate(zip(names, datas)):
         f = _File(data)
         try:
             iid, w, h = f.size(item_id)
         finally:
             f.close()
+        if resized:
+            views[k], w, h = _view_of(crops[k] if crops is not None else None, size, filter, w, h)
         if size is None:
             size = (w, h)
         if (w, h) != size:
@@ -202,7 +246,10 @@ def decode_batch_to_tensor(files, item_id=0, out_format="rgb", layout="chw", dty
             for k, data in enumerate(datas):
                 dest = _dest_of(out[k], lay, code, c, sc, bi)
                 while True:
-                    rc = capi.check_image(L.hm_pipeline_submit_to_device(pipe, data, len(data), ids[k], k, C.byref(dest)))
+                    if views[k] is None:
+                        rc = capi.check_image(L.hm_pipeline_submit_to_device(pipe, data, len(data), ids[k], k, C.byref(dest)))
+                    else:
+                        rc = capi.check_image(L.hm_pipeline_submit_to_device_view(pipe, data, len(data), ids[k], k, C.byref(views[k]), C.byref(dest)))
                     if rc != capi.HM_PIPELINE_FULL:
                         break
                     take()

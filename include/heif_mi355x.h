@@ -504,6 +504,53 @@ HM_API int hm_decode_sequence_to_device(const hm_file* f, uint32_t first, int32_
  * device memory, which must stay valid until then.  A destination that is refused fails the submit or the image's result. */
 HM_API int hm_pipeline_submit_to_device(hm_pipeline* p, const uint8_t* heif, size_t size, uint32_t item_id, uint64_t tag, const hm_device_dest* dest);
 
+/* ------------------------------------------------------------------------- */
+/* Views: a rectangle of the image, at a size of the caller's choice, into the destination */
+/* ------------------------------------------------------------------------- */
+
+/* "This rectangle of the image, at this size, in this tensor": crop and resampling are fused into the step that writes the
+ * destination, and of a grid only the tiles the rectangle touches are entropy-decoded, uploaded and reconstructed (where that
+ * provably changes no pixel: no transformation applied on the item or a covered tile, no alpha image, default chroma
+ * up-sampling, a sub-grid origin that is even in every subsampled direction - hm_plan_view tells; everything else decodes the
+ * whole item and applies the view at the end, with identical bytes).  A coded picture outside the sub-grid is not looked at:
+ * damage there neither fails the call nor sets HM_WARN_CONCEALED.
+ * Per axis, n = crop extent, m = output extent, in double:  s = n / m, fs = max(s, 1), c = (j + 0.5) * s,
+ * lo = max(0, (int)(c - fs + 0.5)), hi = min(n, (int)(c + fs + 0.5)), w_i = max(0, 1 - |(i + 0.5 - c) / fs|) for i in [lo, hi),
+ * table entry (float)(w_i / W) with W the sum of the w_i in increasing i (the antialiased bilinear filter of PIL and of
+ * torch.nn.functional.interpolate(mode="bilinear", antialias=True); taps never leave the crop: "crop, then resize").
+ * Per channel (alpha like any other, no premultiplication), in float32 without fused multiply-add: horizontally
+ * t = 0, t = t + w * (float)v for i increasing, then vertically the same over the t, giving r; integer destinations store
+ * min(max((int)(r + 0.5f), 0), peak) with peak 255 / 65535, float destinations r * scale[c] + bias[c] (r not rounded first).
+ * HM_VIEW_NEAREST moves the sample at j * n / m (int arithmetic).  out_w == out_h == 0 is the crop alone: the bytes of the full
+ * decode's rectangle.  The crop alone and HM_VIEW_NEAREST to HWC with the target's own integer type move bytes: _BE targets allowed.
+ * Refused with HM_ERR_INVALID_ARG before any work is queued, the destination unwritten: a crop with a non-positive extent or
+ * not inside the image, an output extent below 1 or above 32768, n / m above 256 on an axis, an unknown filter,
+ * HM_VIEW_TRIANGLE with a _BE target (ask for _LE), and whatever hm_decode_item_to_device refuses, judged against out_w x out_h. */
+enum { HM_VIEW_TRIANGLE = 0,   /* antialiased bilinear, defined above */
+       HM_VIEW_NEAREST  = 1 }; /* the reference's scale_nearest_neighbor index rule (pixelimage.cc:1232-1251) */
+typedef struct hm_device_view {
+  int32_t crop_x, crop_y, crop_w, crop_h;  /* rectangle of the image as hm_decode_item hands it out (after irot / imir /
+                                              clap unless ignore_transformations); crop_w == crop_h == 0: the whole image */
+  int32_t out_w, out_h;                    /* size written to the destination; 0, 0 = the crop's own size (crop only) */
+  int32_t filter;
+} hm_device_view;
+/* hm_decode_item_to_device with `dest` sized for out_w x out_h (hm_device_dest_bytes of that size); out->width / height: the
+ * size written.  warnings: of the coded pictures that were decoded; a grid's profile fields: of the first tile decoded. */
+HM_API int hm_decode_item_to_device_view(const hm_file* f, uint32_t id, const hm_decode_params* params, const hm_device_view* view,
+                                         const hm_device_dest* dest, hm_decoded* out);
+/* the pipeline form: images of different sizes into the slices of one N x C x H x W allocation */
+HM_API int hm_pipeline_submit_to_device_view(hm_pipeline* p, const uint8_t* heif, size_t size, uint32_t item_id, uint64_t tag,
+                                             const hm_device_view* view, const hm_device_dest* dest);
+/* The step on its own, on interleaved pixels that are on the device already (as hm_to_tensor).  Asynchronous on `stream`. */
+HM_API int hm_resample_to_tensor(int out_format, int src_w, int src_h, const void* d_src, int src_stride, const hm_device_view* view,
+                                 const hm_device_dest* dest, void* stream);
+/* Host arithmetic: tiles[] = first tile row, row count, first tile column, column count a view decode of this item will
+ * entropy-decode; a single image, or a view that is not reduced: the whole grid (0, rows, 0, cols). */
+HM_API int hm_plan_view(const hm_file* f, uint32_t id, const hm_decode_params* params, const hm_device_view* view, int32_t tiles[4]);
+/* Host arithmetic: the taps of output index j on one axis of n_in -> n_out.  Returns their count (or a negative status),
+ * *first = the first source index, weights[0 .. min(count, cap)) = the weights the kernels use. */
+HM_API int hm_view_filter_taps(int n_in, int n_out, int filter, int j, int32_t* first, float* weights, int cap);
+
 #ifdef __cplusplus
 }
 #endif
