@@ -6,7 +6,7 @@ Besides corpus names and the special pictures below, the arguments may name a SE
 dependent segments, tiles, WPP with slices, conformance windows - the non-rare structure cases and the 512 x 512 tiles with
 structure), `rare512` (the rare-syntax 512 x 512 tiles); `extreme_sweep`, `extreme512`, `extreme_large` are the pictures of
 corpus.extreme_sweep / extreme_tiles / extreme_large; every picture of `extreme_sweep` is also held against the fingerprints of the
-reference's scalar build (tests/golden/extreme.json).  A picture of the corpus is also held against the reference decoder's
+reference's scalar build (tests/golden/extreme.json); `intra512` are the tiles of corpus.intra_tiles.  A picture of the corpus is also held against the reference decoder's
 fingerprint of it (tests/golden/synth.json) at stages 0, 1 and 3.  More variables of the environment:
   HM_CHECK_COPIES    copies of every picture in its batch (default 3)
   HM_CHECK_STAGES    the stages to run, comma-separated (default 3)
@@ -88,6 +88,9 @@ def main():
             import synthutil
             cases = {"extreme_sweep": lambda: corpus.extreme_sweep(len(EXTREME)), "extreme512": corpus.extreme_tiles, "extreme_large": corpus.extreme_large}[name]()
             batches[name] = [parse(synthutil.picture(seed, **kw)) for seed, kw in cases] * (1 if name == "extreme_sweep" else copies)
+        elif name == "intra512":  # corpus.intra_tiles: half of the coding units calm - smooth borders cross every cut
+            import synthutil
+            batches[name] = [parse(synthutil.picture(seed, **kw)) for seed, kw in corpus.intra_tiles()] * copies
         elif name == "mixed":  # pictures of one class and different sizes in one launch (the cut follows the tallest; short ones leave waves idle)
             batches[name] = [parse(corpus.stream(n)) for n in ("tile512_a", "ragged", "dense_lowqp", "no_deblock", "tile512_b", "ragged")] * 2
         elif name == "mixed_structure":  # ... the same with slices, dependent segments, tiles and WPP with slices (8-bit 4:2:0, CTB 32)

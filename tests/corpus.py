@@ -325,3 +325,91 @@ def extreme_large():
             (15101, dict(width=1536, height=1024, log2_ctb=6, bit_depth=12, chroma_format=2, qp=51, density=70, level_span=600, qp_span=1, cu_qp_delta=1, no_split=1)),
             (15102, dict(width=1920, height=1080, log2_ctb=4, bit_depth=10, qp=8, density=60, level_span=400, qp_span=1, cu_qp_delta=1, rext_sps=128)),
             (15103, dict(width=1536, height=1024, log2_ctb=6, chroma_format=0, qp=40, density=90, level_span=1000, qp_span=1, cu_qp_delta=1))]
+
+
+def intra_sweep(n, first_seed=16000):
+    """(seed, parameters) of a seeded sweep for intra sample prediction: small pictures whose sizes cut blocks at the right and
+    bottom edges (72, 40, 136, 200), calm coding units (no residual: the picture holds the prediction itself, and smooth but
+    non-flat borders for the units next to them) among noisy ones, crossed with what selects a path of the prediction: bit
+    depth, chroma format, CTB size, whole 16x16 / 32x32 blocks (no_split, with 32x32 or 16x16 as the largest transform),
+    strong intra smoothing, intra_smoothing_disabled, implicit RDPCM with transquant bypass (10 / 12 bit), level_span on a
+    share of the cases (predictions from neighbours at 0 and at the maximum), slices with and without dependent segments,
+    tiles that stop prediction at their borders, WPP.  Every other run of 48 cases has no rare syntax and takes the split
+    chains unless it is 4:4:4; the others go out in decode order.  Quirk Q9 and the 8-bit "pcmf" branch stay excluded, as in
+    extreme_sweep."""
+    out = []
+    for seed in range(first_seed, first_seed + n):
+        # (a multiplicative hash alone leaves its low bits a function of the seed's low bits, which choose depth, format and CTB size below)
+        r = seed * 2654435761 % (1 << 32)
+        r = (r ^ (r >> 15)) * 2246822519 % (1 << 32)
+        r ^= r >> 13
+        i = seed - first_seed
+        pick = lambda k, opts: opts[(r >> k) % len(opts)]
+        # (8 bit in every other case - its split chains are the class with the packed-pair kernels -, the four chroma formats and three
+        # CTB sizes in turn: all combinations within 48 cases)
+        kw = dict(bit_depth=[8, 10, 8, 12][i % 4], chroma_format=[1, 3, 0, 2][(i // 4) % 4], log2_ctb=[5, 4, 6][(i // 16) % 3],
+                  no_split=pick(5, [0, 1, 1, 1]), calm=pick(7, [0, 300, 700, 500]), density=pick(9, [20, 60, 100]), strong_intra=pick(11, [1, 1, 0]),
+                  qp=pick(13, [22, 30, 38, 27]), cu_qp_delta=1, level_span=pick(15, [0, 300, 1000, 600]), rext_sps=pick(17, [4, 32, 36, 4]),
+                  tq_bypass=pick(20, [0, 250]), slices=pick(22, [0, 60, 150, 300]), dependent=pick(24, [0, 400]), log2_max_tb=pick(26, [5, 5, 4]),
+                  sign_hiding=pick(28, [1, 0]), mode_span=pick(29, [0, 800, 800, 400]))
+        if kw["level_span"] == 1000:
+            kw.update(density=100, qp=45)  # residuals far beyond the sample range: neighbours at 0 and at the maximum side by side
+        # whole blocks on the larger pictures (few blocks each), split ones on the smaller
+        kw.update(width=pick(0, [136, 192, 200, 72]), height=pick(3, [128, 56, 72, 104])) if kw["no_split"] else \
+            kw.update(width=pick(0, [64, 72, 40, 72]), height=pick(3, [64, 40, 56, 72]))
+        if (i // 48) % 2 == 0:
+            kw.update(rext_sps=0, tq_bypass=0)  # no rare syntax: split chains (k_residual + k_chain) for all but 4:4:4
+        if not kw["no_split"]:
+            kw["log2_max_tb"] = 5
+        if not kw["slices"]:
+            kw["dependent"] = 0
+        elif kw["slices"] == 300 and not kw["no_split"]:
+            # two CTBs a row and short slices: a slice that starts above-right of a row's first CTB leaves it that neighbour alone
+            kw.update(width=2 << kw["log2_ctb"], height=72)
+        if i % 5 == 3:
+            kw.update(tile_cols=2, tile_rows=2, lf_across_tiles=0, tiles_uniform=i % 2)
+        elif i % 7 == 2:
+            kw.update(wpp=1)
+        if i >= 768:
+            # behind the crossed cases, two families aimed at the cells of the census that 768 crossed cases leave empty
+            j = i - 768
+            if j % 2 == 0:  # small split pictures with neighbours at both rails and short slices: the clip of modes 10 / 26, missing corners
+                kw = dict(bit_depth=[8, 10, 8, 12][(j // 2) % 4], chroma_format=[1, 0, 2, 1][(j // 8) % 4], log2_ctb=[5, 4, 6][(j // 2) % 3], width=72, height=72,
+                          calm=300, density=100, qp=45, level_span=1000, cu_qp_delta=1, slices=150, rext_sps=[0, 4][(j // 4) % 2])
+                if j % 8 == 2:  # ... and the same on whole 16x16 luma blocks of 8-bit split chains (32x32 units, 16x16 transforms)
+                    kw.update(bit_depth=8, chroma_format=[1, 0][(j // 8) % 2], log2_ctb=5, no_split=1, log2_max_tb=4, rext_sps=0, width=136, height=72)
+                if j % 16 == 6:  # ... and on 8x8 luma blocks of the deeper split chains (32x32 units, 8x8 transforms)
+                    kw.update(bit_depth=[10, 12][(j // 16) % 2], chroma_format=[1, 0][(j // 32) % 2], log2_ctb=5, no_split=1, log2_max_tb=3, rext_sps=0, width=136, height=72)
+            else:           # whole 32x32 luma / 16x16 chroma blocks with residuals, modes drawn whole
+                kw = dict(bit_depth=[8, 10][(j // 2) % 2], chroma_format=1, log2_ctb=5, width=200, height=128, no_split=1, calm=200, density=100,
+                          qp=30, cu_qp_delta=1, mode_span=800)
+        if kw["log2_ctb"] == 4 and kw["bit_depth"] == 8 and kw["chroma_format"] in (1, 2):
+            kw["log2_ctb"] = 5  # quirk Q9 (see rare_syntax_sweep)
+        if kw["bit_depth"] == 8:
+            kw["tq_bypass"] = 0  # (the "pcmf" branch: see extreme_sweep)
+        out.append((seed, kw))
+    return out
+
+
+def intra_single_ctb_cases(n, first_seed=17000):
+    """(seed, parameters) of pictures of ONE CTB - the smallest shape at which each block size exists: CTB 16 / 32 / 64, every bit
+    depth and chroma format, whole blocks and split ones, most coding units calm"""
+    out = []
+    for i in range(n):
+        ctb = [4, 5, 6][i % 3]
+        kw = dict(width=1 << ctb, height=1 << ctb, log2_ctb=ctb, bit_depth=[8, 10, 12][(i // 3) % 3], chroma_format=[1, 3, 0, 2][(i // 9) % 4],
+                  no_split=(i // 36) % 2, calm=[800, 600][(i // 72) % 2], density=[60, 100][i % 2], strong_intra=1, qp=[24, 34][(i // 2) % 2], cu_qp_delta=1)
+        if ctb == 4 and kw["bit_depth"] == 8 and kw["chroma_format"] in (1, 2):
+            kw.update(sao=0)  # (quirk Q9 is one of SAO: these pictures are compared at the reconstruction stage only)
+        out.append((first_seed + i, kw))
+    return out
+
+
+def intra_tiles():
+    """512 x 512 tiles for the forced cuts of the prediction chains: half of their coding units calm, so that what a wave hands
+    to the next one - border lines, corner samples - is a smooth ramp or a smear and not noise"""
+    base = dict(width=512, height=512, cu_qp_delta=1, sao=1, sign_hiding=1, calm=500, density=60)
+    return [(18000, dict(base, log2_ctb=5, qp=27, no_split=1)),
+            (18001, dict(base, log2_ctb=6, bit_depth=10, chroma_format=2, qp=30)),
+            (18002, dict(base, log2_ctb=4, chroma_format=0, qp=33, no_split=1)),
+            (18003, dict(base, log2_ctb=5, qp=27, slices=40, dependent=300))]

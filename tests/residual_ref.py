@@ -86,7 +86,8 @@ def clip16(v):
 
 # ---- reading a command stream (decode order: hm_tu) ---------------------------------------------------------------------
 PIC_SCALING_LIST, PIC_SPLIT_CHAINS, PIC_TS_ROTATION, PIC_IMPLICIT_RDPCM, PIC_CROSS_COMPONENT = 0x100, 0x1000, 0x2000, 0x4000, 0x10000
-TU_CBF, TU_TSKIP, MODE_BYPASS, MODE_PCM = 0x20, 0x40, 0x40, 0x80
+PIC_STRONG_INTRA, PIC_NO_INTRA_SMOOTHING = 0x1, 0x8000
+TU_CBF, TU_TSKIP, TU_AVAIL_TL, MODE_BYPASS, MODE_PCM = 0x20, 0x40, 0x80, 0x40, 0x80
 
 
 def scaling_offset(log2, cidx):  # HM_SCALING_OFFSET
@@ -115,14 +116,15 @@ class Picture:
         for a in (range(self.n_ctbs) if ctb is None else [ctb]):
             tu_first, tu_count = struct.unpack_from("<IH", self.blob, self.off_ctbs + 52 * a)
             for t in range(tu_first, tu_first + tu_count):
-                x, y, info, pm, qp, qpy, n, first = struct.unpack_from("<BBBBBbHI", self.blob, self.off_tus + 16 * t)
+                x, y, info, pm, qp, qpy, n, first, a_l, a_bl, a_t, a_tr = struct.unpack_from("<BBBBBbHI4B", self.blob, self.off_tus + 16 * t)
                 cidx = (info >> 3) & 3
                 cx, cy = (a % self.ctb_w) << self.log2_ctb, (a // self.ctb_w) << self.log2_ctb
                 if cidx:
                     cx, cy = cx // sw, cy // sh
                 yield dict(x=cx + x, y=cy + y, log2=info & 7, cidx=cidx, cbf=bool(info & TU_CBF), tskip=bool(info & TU_TSKIP),
                            mode=pm & 0x3F, bypass=bool(pm & MODE_BYPASS), pcm=bool(pm & MODE_PCM), qp=qp, qpy=qpy,
-                           levels=self.coeffs[first:first + n])
+                           levels=self.coeffs[first:first + n], avail_left=a_l, avail_bottom_left=a_bl, avail_top=a_t, avail_top_right=a_tr,
+                           avail_tl=bool(info & TU_AVAIL_TL))
 
 
 # ---- the arithmetic ---------------------------------------------------------------------------------------------------------

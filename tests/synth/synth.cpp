@@ -193,6 +193,11 @@ struct SynthParams {
   int32_t qp_span;             // 1: cu_qp_delta_abs over its whole range (suffix included), both signs free: QpY walks over
                                // -QpBdOffset .. 51 and wraps (8-283)
   int32_t scaling_span;        // per-mille chance that an explicitly coded scaling matrix is pinned at 1 / at 255 / at a mix of both, DC included
+  // --- intra prediction on smooth borders (0 = the draws of the streams above, byte for byte) ---
+  int32_t calm;                // per-mille chance, drawn once per coding unit, that every cbf flag of the unit is 0: the unit then holds
+                               // its prediction alone (ramps, smears), next to units with residuals
+  int32_t mode_span;           // per-mille chance, per bin, that prev_intra_luma_pred_flag is 0 (the luma mode is then rem_intra_luma_pred_mode,
+                               // uniform over the 32 modes that are no candidate) and that intra_chroma_pred_mode is 4 (the luma mode)
 };
 
 // entropy-coder adaptor for SliceWalker: chooses every bin, encodes it, returns it
@@ -298,10 +303,16 @@ class EncoderEC {
       case K_SPLIT_CU: return P.no_split ? 0 : rng_.chance(idx >= 6 ? 900 : (idx == 5 ? 650 : 450));
       case K_TQ_BYPASS: return rng_.chance(P.tq_bypass);
       case K_PART_MODE: return (idx == 1 || P.no_split) ? 1 : rng_.chance(600);
-      case K_PREV_INTRA: return rng_.chance(550);
+      case K_PREV_INTRA:
+        if (P.calm && idx == 0) cu_calm_ = rng_.chance(P.calm); // (the first bin of every coding unit that is not PCM)
+        if (P.mode_span && rng_.chance(P.mode_span)) return 0;
+        return rng_.chance(550);
+      case K_CHROMA_MODE:
+        if (P.mode_span && idx == 0 && rng_.chance(P.mode_span)) return 0;
+        return (int)(rng_.next() & 1);
       case K_SPLIT_TF: return P.no_split ? 0 : rng_.chance(idx >= 5 ? 550 : (idx == 4 ? 400 : 300));
-      case K_CBF_LUMA: return rng_.chance(7 * d);
-      case K_CBF_CHROMA: return rng_.chance(5 * d);
+      case K_CBF_LUMA: return cu_calm_ ? 0 : rng_.chance(7 * d);
+      case K_CBF_CHROMA: return cu_calm_ ? 0 : rng_.chance(5 * d);
       case K_QP_DELTA:
         if (P.qp_span) {
           // cu_qp_delta_abs drawn whole, then written bin by bin: 0 .. 25 + QpBdOffset / 2, the largest value both signs may
@@ -395,7 +406,7 @@ class EncoderEC {
   ContextSet cs_;
   // values drawn whole and written bin by bin (qp_span, level_span)
   int qp_abs_ = 0, last_bias_ = 1;
-  bool calr_run_ = false;
+  bool calr_run_ = false, cu_calm_ = false;
   int calr_ = -1, calr_pos_ = 0, calr_prefix_ = 0, calr_suffix_ = 0;
 };
 

@@ -9,6 +9,7 @@ and the reference decoder build oracle/_ref):
   tests/golden/extreme.json (a plain run rewrites it with the others; `make_fixtures.py extreme` writes this file alone) the same fingerprints of the reference's
                             SCALAR build for corpus.extreme_sweep - levels, QPs and scaling factors at the edges of the
                             residual arithmetic -, and beside them where its default (SIMD) build decodes otherwise
+  tests/golden/intra.json   (`make_fixtures.py intra` writes it, and only that sub-command) the same for corpus.intra_sweep
 """
 import json
 import os
@@ -136,10 +137,55 @@ def extreme():
     print("extreme:", len(cases), "cases;", len(differing), "decoded differently by the default build:", dict(sorted(classes.items())))
 
 
+INTRA_CASES = 1104
+
+
+def intra():
+    """corpus.intra_sweep: fingerprints of the reference's scalar build at the three stages (level_span is in play: DESIGN.md
+    Q10); and, at the reconstruction stage, the class of the first block per plane in which its default build differs"""
+    import collections
+    import numpy as np
+    import corpus
+    import residual_ref as rr
+    import synthutil
+    import __graft_entry__ as g
+    capi = g.load_package().capi
+    cases, classes, differing = {}, collections.Counter(), []
+    for seed, kw in corpus.intra_sweep(INTRA_CASES):
+        data = synthutil.picture(seed, **kw)
+        entry = {"stream_fnv": f"{orc.load().orc_fnv1a64(data, len(data), 0):016x}"}
+        for stage, flags in (("recon", orc.REF_F_NO_DEBLOCK | orc.REF_F_NO_SAO), ("deblock", orc.REF_F_NO_SAO), ("full", 0)):
+            planes, _ = orc.ref_decode(data, flags | orc.REF_F_SCALAR)
+            entry[stage] = fingerprint(planes)
+            if stage == "recon":
+                simd, _ = orc.ref_decode(data, flags)
+                if any(not np.array_equal(a, b) for a, b in zip(simd, planes)):
+                    differing.append(seed)
+                    P = rr.Picture(capi.parse_hevc(data, record_order=2))
+                    origin = set()
+                    for rec in P.records():  # per plane, the first block in decode order in which a sample differs
+                        nT = 1 << rec["log2"]
+                        a, b = (p[rec["cidx"]][rec["y"]:rec["y"] + nT, rec["x"]:rec["x"] + nT] for p in (simd, planes))
+                        if rec["cidx"] not in origin and not np.array_equal(a, b):
+                            origin.add(rec["cidx"])
+                            kind = "pcm" if rec["pcm"] else "no residual" if not rec["cbf"] else "bypass" if rec["bypass"] else \
+                                "transform skip" if rec["tskip"] else "DST" if nT == 4 and rec["cidx"] == 0 else "DCT"
+                            classes[f"level_span {kw['level_span']}: {kind}"] += 1
+        cases[str(seed)] = entry
+    out = {"cases": cases,
+           "simd_vs_scalar": {"stage": "recon", "cases": len(cases), "cases_that_differ": len(differing), "seeds": differing,
+                              "first_blocks_that_differ_by_class": dict(sorted(classes.items()))}}
+    json.dump(out, open(os.path.join(ROOT, "tests", "golden", "intra.json"), "w"), indent=0, sort_keys=True, separators=(",", ":"))
+    print("intra:", len(cases), "cases;", len(differing), "decoded differently by the default build:", dict(sorted(classes.items())))
+
+
 if __name__ == "__main__":
     if sys.argv[1:] == ["extreme"]:
         sys.path.insert(0, ROOT)
         extreme()
+    elif sys.argv[1:] == ["intra"]:
+        sys.path.insert(0, ROOT)
+        intra()
     else:
         main()
         sys.path.insert(0, ROOT)
