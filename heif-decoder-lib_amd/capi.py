@@ -25,6 +25,7 @@ HM_DEV_LAYOUT_HWC, HM_DEV_LAYOUT_CHW = 0, 1
 HM_DEV_U8, HM_DEV_U16, HM_DEV_F16, HM_DEV_F32 = 0, 1, 2, 3
 # views (hm_device_view): a rectangle of the image at a size of the caller's choice
 HM_VIEW_TRIANGLE, HM_VIEW_NEAREST = 0, 1
+HM_VIEW_CUBIC, HM_VIEW_LANCZOS3 = 16, 17
 HM_PIPELINE_FULL = 1
 HM_DETAIL_NO_COLOUR_CHAIN = 2
 

@@ -2,6 +2,7 @@
 // stage's interleaved pixels into it (a 2-D device copy for HWC with the target's own integer type, k_to_tensor otherwise).
 // Views (hm_device_view): the refusals, the tap tables and the step that writes a resampled rectangle (kernels: resample.hip).
 #include <algorithm>
+#include <cmath>
 #include <cstring>
 #include <mutex>
 #include <new>
@@ -128,41 +129,68 @@ int hm_dest_write(const hm_device_dest* d, int out_format, int w, int h, int y0,
 
 // ---- views ----------------------------------------------------------------------------------------------------------------------
 
-// the taps of output index j on an axis of n -> m, all in double (the contract of include/heif_mi355x.h): returns their count,
-// *first the first source index, w[0 .. count) the normalised weights when w is given (count <= 2 * 256 + 2)
-static int axis_taps(int n, int m, int j, int* first, float* w)
+// the kernel function k of a resampling filter at x (include/heif_mi355x.h), in double, every operation rounded on its own
+static double filter_k(int filter, double x)
 {
-  const double s = (double)n / (double)m, fs = s > 1.0 ? s : 1.0, c = ((double)j + 0.5) * s;
-  int lo = (int)(c - fs + 0.5), hi = (int)(c + fs + 0.5);
+  if (x < 0) x = -x;
+  if (filter == HM_VIEW_CUBIC) { // Keys, a = -0.5
+    if (x < 1.0) return (1.5 * x - 2.5) * x * x + 1.0;
+    if (x < 2.0) return ((-0.5 * x + 2.5) * x - 4.0) * x + 2.0;
+    return 0.0;
+  }
+  if (filter == HM_VIEW_LANCZOS3) {
+    if (x == 0.0) return 1.0;
+    if (x >= 3.0) return 0.0;
+    const double p = 3.14159265358979323846 * x, q = p / 3.0;
+    return (std::sin(p) / p) * (std::sin(q) / q);
+  }
+  const double wi = 1.0 - x; // HM_VIEW_TRIANGLE
+  return wi > 0.0 ? wi : 0.0;
+}
+
+// the support a of a filter and the strongest reduction n / m it takes: (2 a fs + 1) taps must fit HM_VIEW_MAX_TAPS
+enum { HM_VIEW_MAX_TAPS = 2 * 256 + 2 };
+static double filter_support(int filter) { return filter == HM_VIEW_CUBIC ? 2.0 : filter == HM_VIEW_LANCZOS3 ? 3.0 : 1.0; }
+static int filter_max_reduction(int filter) { return filter == HM_VIEW_CUBIC ? 128 : filter == HM_VIEW_LANCZOS3 ? 85 : 256; }
+static const char* filter_name(int filter) { return filter == HM_VIEW_CUBIC ? "HM_VIEW_CUBIC" : filter == HM_VIEW_LANCZOS3 ? "HM_VIEW_LANCZOS3" : "HM_VIEW_TRIANGLE"; }
+static bool filter_known(int filter) { return filter == HM_VIEW_TRIANGLE || filter == HM_VIEW_NEAREST || filter == HM_VIEW_CUBIC || filter == HM_VIEW_LANCZOS3; }
+static bool filter_resamples(int filter) { return filter != HM_VIEW_NEAREST; }
+
+// the taps of output index j on an axis of n -> m, all in double (the contract of include/heif_mi355x.h): returns their count,
+// *first the first source index, w[0 .. count) the normalised weights when w is given (count <= HM_VIEW_MAX_TAPS: check_axis has
+// bounded n / m for the filter; a count beyond it is reported, never written)
+static int axis_taps(int n, int m, int filter, int j, int* first, float* w)
+{
+  const double s = (double)n / (double)m, fs = s > 1.0 ? s : 1.0, c = ((double)j + 0.5) * s, r = filter_support(filter) * fs;
+  int lo = (int)(c - r + 0.5), hi = (int)(c + r + 0.5);
   if (lo < 0) lo = 0;
   if (hi > n) hi = n;
   *first = lo;
+  if (hi - lo > HM_VIEW_MAX_TAPS) return hm_fail(HM_ERR_INTERNAL, "view: %d taps on an axis of %d -> %d (%s)", hi - lo, n, m, filter_name(filter));
   if (!w) return hi - lo;
   double W = 0.0;
-  for (int i = lo; i < hi; i++) {
-    const double x = ((double)i + 0.5 - c) / fs, wi = 1.0 - (x < 0 ? -x : x);
-    W += wi > 0.0 ? wi : 0.0;
-  }
-  for (int i = lo; i < hi; i++) {
-    const double x = ((double)i + 0.5 - c) / fs, wi = 1.0 - (x < 0 ? -x : x);
-    w[i - lo] = (float)((wi > 0.0 ? wi : 0.0) / W);
-  }
+  for (int i = lo; i < hi; i++) W += filter_k(filter, ((double)i + 0.5 - c) / fs);
+  for (int i = lo; i < hi; i++) w[i - lo] = (float)(filter_k(filter, ((double)i + 0.5 - c) / fs) / W);
   return hi - lo;
 }
 
-static int check_axis(int n, int m, const char* what)
+static int check_axis(int n, int m, int filter, const char* what)
 {
   if (n < 1 || n > 32768) return hm_fail(HM_ERR_INVALID_ARG, "view: source %s %d", what, n);
   if (m < 1 || m > 32768) return hm_fail(HM_ERR_INVALID_ARG, "view: output %s %d is not in 1 .. 32768", what, m);
-  if ((int64_t)n > (int64_t)256 * m) return hm_fail(HM_ERR_INVALID_ARG, "view: %s %d -> %d is a reduction by more than 256", what, n, m);
+  const int most = filter_max_reduction(filter);
+  if ((int64_t)n > (int64_t)most * m) {
+    if (most == 256) return hm_fail(HM_ERR_INVALID_ARG, "view: %s %d -> %d is a reduction by more than 256", what, n, m);
+    return hm_fail(HM_ERR_INVALID_ARG, "view: %s %d -> %d is a reduction by more than %d, the most %s takes", what, n, m, most, filter_name(filter));
+  }
   return HM_OK;
 }
 
 int hm_view_filter_taps(int n_in, int n_out, int filter, int j, int32_t* first, float* weights, int cap)
 {
   if (!first || (cap > 0 && !weights)) return hm_fail(HM_ERR_INVALID_ARG, "null argument");
-  if (filter != HM_VIEW_TRIANGLE && filter != HM_VIEW_NEAREST) return hm_fail(HM_ERR_INVALID_ARG, "view: unknown filter %d", filter);
-  const int rc = check_axis(n_in, n_out, "extent");
+  if (!filter_known(filter)) return hm_fail(HM_ERR_INVALID_ARG, "view: unknown filter %d", filter);
+  const int rc = check_axis(n_in, n_out, filter, "extent");
   if (rc) return rc;
   if (j < 0 || j >= n_out) return hm_fail(HM_ERR_INVALID_ARG, "view: output index %d of %d", j, n_out);
   if (filter == HM_VIEW_NEAREST) {
@@ -170,9 +198,9 @@ int hm_view_filter_taps(int n_in, int n_out, int filter, int j, int32_t* first, 
     if (cap > 0) weights[0] = 1.0f;
     return 1;
   }
-  float w[2 * 256 + 4];
+  float w[HM_VIEW_MAX_TAPS + 2];
   int f0 = 0;
-  const int n = axis_taps(n_in, n_out, j, &f0, w);
+  const int n = axis_taps(n_in, n_out, filter, j, &f0, w);
   *first = f0;
   for (int i = 0; i < n && i < cap; i++) weights[i] = w[i];
   return n;
@@ -182,7 +210,7 @@ int hm_view_resolve(int out_format, int src_w, int src_h, const hm_device_view* 
 {
   if (!v || !vp) return hm_fail(HM_ERR_INVALID_ARG, "null view");
   std::memset(vp, 0, sizeof(*vp));
-  if (v->filter != HM_VIEW_TRIANGLE && v->filter != HM_VIEW_NEAREST) return hm_fail(HM_ERR_INVALID_ARG, "view: unknown filter %d", v->filter);
+  if (!filter_known(v->filter)) return hm_fail(HM_ERR_INVALID_ARG, "view: unknown filter %d", v->filter);
   if (v->crop_w == 0 && v->crop_h == 0) {
     if (v->crop_x || v->crop_y) return hm_fail(HM_ERR_INVALID_ARG, "view: crop origin %d, %d with an empty crop", v->crop_x, v->crop_y);
     vp->x = vp->y = 0; vp->w = src_w; vp->h = src_h;
@@ -198,9 +226,9 @@ int hm_view_resolve(int out_format, int src_w, int src_h, const hm_device_view* 
   vp->ow = vp->crop_only ? vp->w : v->out_w;
   vp->oh = vp->crop_only ? vp->h : v->out_h;
   int rc;
-  if ((rc = check_axis(vp->w, vp->ow, "width")) || (rc = check_axis(vp->h, vp->oh, "height"))) return rc;
+  if ((rc = check_axis(vp->w, vp->ow, vp->filter, "width")) || (rc = check_axis(vp->h, vp->oh, vp->filter, "height"))) return rc;
   const bool be = out_format == HM_OUT_RRGGBB_BE || out_format == HM_OUT_RRGGBBAA_BE;
-  if (be && !vp->crop_only && vp->filter == HM_VIEW_TRIANGLE)
+  if (be && !vp->crop_only && filter_resamples(vp->filter))
     return hm_fail(HM_ERR_INVALID_ARG, "view: a big-endian target has no sample values to resample: ask for the _LE format");
   return HM_OK;
 }
@@ -225,24 +253,34 @@ int hm_view_write(const hm_device_dest* d, int out_format, const hm_view_plan* v
   if (vp->filter == HM_VIEW_NEAREST)
     return hm_launch_view_nearest(&p, origin, src_stride, vp->w, vp->h, vp->ow, vp->oh, d->ptr, d->scale, d->bias, s);
   // tap tables of both axes in one pinned block and one upload: first[m], count[m], weights[taps][m] per axis
+  const int filt = vp->filter;
   int tx = 0, ty = 0, f0;
-  for (int j = 0; j < vp->ow; j++) tx = std::max(tx, axis_taps(vp->w, vp->ow, j, &f0, nullptr));
-  for (int k = 0; k < vp->oh; k++) ty = std::max(ty, axis_taps(vp->h, vp->oh, k, &f0, nullptr));
+  for (int j = 0; j < vp->ow; j++) { const int cnt = axis_taps(vp->w, vp->ow, filt, j, &f0, nullptr); if (cnt < 0) return cnt; tx = std::max(tx, cnt); }
+  for (int k = 0; k < vp->oh; k++) { const int cnt = axis_taps(vp->h, vp->oh, filt, k, &f0, nullptr); if (cnt < 0) return cnt; ty = std::max(ty, cnt); }
   const size_t words_x = (size_t)vp->ow * (2 + tx), words_y = (size_t)vp->oh * (2 + ty), bytes = (words_x + words_y) * 4;
   int32_t* host = (int32_t*)hm_pool_pinned_alloc(bytes);
   if (!host) return hm_fail(HM_ERR_NOMEM, "out of memory");
   sc->pinned = host;
-  float w[2 * 256 + 4];
+  float w[HM_VIEW_MAX_TAPS + 2];
   auto fill = [&](int32_t* base, int n, int m, int taps) {
     float* wt = reinterpret_cast<float*>(base + 2 * (size_t)m);
     for (int j = 0; j < m; j++) {
-      const int cnt = axis_taps(n, m, j, &base[j], w);
+      const int cnt = axis_taps(n, m, filt, j, &base[j], w);
       base[m + j] = cnt;
       for (int i = 0; i < taps; i++) wt[(size_t)i * m + j] = i < cnt ? w[i] : 0.0f;
     }
   };
   fill(host, vp->w, vp->ow, tx);
   fill(host + words_x, vp->h, vp->oh, ty);
+  // the staged horizontal pass (k_resample_h_staged) loads the run first[j0] .. first[j63] + count[j63] of a wave's 64 columns: both
+  // ends must not fall as j rises, and every window must lie inside the crop
+  const bool staged = (filt == HM_VIEW_CUBIC || filt == HM_VIEW_LANCZOS3) && hm_knob(HM_KNOB_VIEW_H_STAGED) != 0;
+  if (staged)
+    for (int j = 0; j < vp->ow; j++) {
+      const int lo = host[j], hi = lo + host[vp->ow + j];
+      if (lo < 0 || hi > vp->w || hi <= lo || (j && (lo < host[j - 1] || hi < host[j - 1] + host[vp->ow + j - 1])))
+        return hm_fail(HM_ERR_INTERNAL, "view: the windows of columns %d and %d are not in order", j - 1, j);
+    }
   const bool chw = p.layout == HM_DEV_LAYOUT_CHW;
   const int64_t E = chw ? vp->ow : (int64_t)vp->ow * p.channels, pitch = (E + 15) / 16 * 16, plane = pitch * vp->h;
   if (!(sc->dev[0] = hm_pool_device_alloc(bytes)) || !(sc->dev[1] = hm_pool_device_alloc((size_t)plane * (chw ? p.channels : 1) * sizeof(float)))) return HM_ERR_NO_DEVICE;
@@ -257,6 +295,7 @@ int hm_view_write(const hm_device_dest* d, int out_format, const hm_view_plan* v
   a.ax.first = dx; a.ax.count = dx + vp->ow; a.ax.weights = reinterpret_cast<const float*>(dx + 2 * (size_t)vp->ow); a.ax.m = vp->ow; a.ax.taps = tx;
   a.ay.first = dy; a.ay.count = dy + vp->oh; a.ay.weights = reinterpret_cast<const float*>(dy + 2 * (size_t)vp->oh); a.ay.m = vp->oh; a.ay.taps = ty;
   a.tmp = (float*)sc->dev[1]; a.tmp_pitch = pitch; a.tmp_plane = plane;
+  a.staged = staged ? 1 : 0; a.stage_px = hm_knob(HM_KNOB_VIEW_STAGE_PX);
   return hm_launch_resample(&p, &a, d->ptr, d->scale, d->bias, s);
 }
 

@@ -57,6 +57,8 @@ typedef struct hm_resample_args {
   int32_t n_w, n_h, ow, oh;
   hm_view_axis ax, ay;                  // device pointers
   float* tmp; int64_t tmp_pitch, tmp_plane; // the horizontal pass' float32 rows (elements), laid out like the destination
+  int32_t staged;                       // the horizontal pass stages its source run in LDS (k_resample_h_staged: HM_VIEW_CUBIC, HM_VIEW_LANCZOS3)
+  int32_t stage_px;                     // > 0: at most that many pixels per staged chunk (knob view_stage_px: tests)
 } hm_resample_args;
 int hm_launch_resample(const hm_dest_plan* p, const hm_resample_args* a, void* dst, const float scale[4], const float bias[4], hipStream_t s);
 int hm_launch_view_nearest(const hm_dest_plan* p, const void* src, int src_stride, int n_w, int n_h, int ow, int oh, void* dst, const float scale[4],

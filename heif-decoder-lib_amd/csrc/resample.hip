@@ -4,6 +4,8 @@
 //                    pair and walks its taps over contiguous source bytes; a wave is 64 consecutive columns of ONE row, and the tap
 //                    table is tap-major (weights[tap][column]), so the wave's weight reads and its stores are contiguous.  The
 //                    intermediate is laid out like the destination: one plane per channel for CHW, interleaved for HWC.
+//   k_resample_h_staged  the same sums in the same order for HM_VIEW_CUBIC / HM_VIEW_LANCZOS3 (2 and 3 times the taps): the contiguous run of
+//                    source bytes a wave's 64 columns read goes to LDS once, in 16-byte loads, and the lanes take their taps from there.
 //   k_resample_v     the vertical pass, fused with dtype, layout, scale and bias: a wave is 64 consecutive element groups of ONE output
 //                    row (of one plane), so its taps are wave-uniform and the intermediate reads and the tensor stores coalesce.  A lane's
 //                    group is 16 bytes of output (one 16-byte store) where pointer and pitches allow, one element otherwise.
@@ -56,6 +58,107 @@ __global__ __launch_bounds__(256) void k_resample_h(const uint8_t* __restrict__ 
 #pragma unroll
     for (int c = 0; c < C; c++) t[c] = __fadd_rn(t[c], __fmul_rn(w, (float)in[i * C + c]));
   }
+  float* o = tmp + (long long)y * pitch;
+#pragma unroll
+  for (int c = 0; c < C; c++) {
+    if (CHW) o[(long long)c * plane + j] = t[c];
+    else o[(size_t)j * C + c] = t[c];
+  }
+}
+
+// k_resample_h with the source run staged in LDS.  The 64 columns of a wave read the pixels first[c0] .. first[c63] + count[c63] of
+// their row: one contiguous run (the windows' ends do not fall as the column rises: hm_view_write checks the table).  A workgroup is
+// four waves on four consecutive rows of the same 64 columns, so the run's extent - and with it every trip count and barrier below -
+// is the same in all of them.  Per chunk of at most chunk_px pixels each wave loads its row's bytes with 16-byte loads from the
+// 16-byte-aligned addresses inside the chunk (the partial units at its head and tail byte by byte: nothing outside the run is
+// read) into its own quarter of the LDS array, then every lane takes those of its taps that lie in the chunk, tap 0 first: chunks
+// and taps both rise, so the order of a lane's sum is that of k_resample_h and the result is the same bit for bit.
+// LDS image of a row: byte b of the chunk, counted from the aligned address below its first byte, sits at b + 4 * (b / 128) - one
+// pad dword behind every 32 -, so lanes whose windows start 64, 128 or 256 bytes apart meet 32 different banks, not 2 or 1.
+constexpr int STAGE_DATA = 3712;                          // bytes of a row's chunk, alignment head included (a multiple of 128)
+constexpr int STAGE_ROW = STAGE_DATA + STAGE_DATA / 32;   // ... with the pad dwords: 3828
+constexpr int STAGE_ROW_PITCH = 3840;                     // 4 rows = 15 360 B = 12 of gfx950's 1 280-byte LDS granules
+static_assert(STAGE_ROW <= STAGE_ROW_PITCH && STAGE_DATA % 128 == 0 && STAGE_ROW_PITCH % 16 == 0, "LDS image of a staged row");
+__device__ __forceinline__ int stage_at(int b) { return b + ((b >> 7) << 2); }
+
+template <int SB, int C, bool CHW>
+__global__ __launch_bounds__(256) void k_resample_h_staged(const uint8_t* __restrict__ src, int src_stride, int n_h, int ow, const int32_t* __restrict__ first,
+                                                           const int32_t* __restrict__ count, const float* __restrict__ wts, float* __restrict__ tmp,
+                                                           long long pitch, long long plane, int chunk_px)
+{
+  typedef typename std::conditional<SB == 1, uint8_t, uint16_t>::type InT;
+  constexpr int PB = SB * C; // bytes per pixel
+  __shared__ __attribute__((aligned(16))) uint8_t lds[4 * STAGE_ROW_PITCH];
+  const int lane = threadIdx.x & 63, wv = threadIdx.x >> 6;
+  const int j0 = blockIdx.x * 64, j = j0 + lane, y = blockIdx.y * 4 + wv;
+  const int jl = min(j0 + 63, ow - 1);
+  const int p_end = first[jl] + count[jl]; // (the same in every lane of the workgroup, as p below)
+  int p = first[j0];
+  const bool row = y < n_h, col = j < ow;
+  const int fj = col ? first[j] : 0, nj = col ? count[j] : 0;
+  uint8_t* buf = lds + wv * STAGE_ROW_PITCH;
+  const uint8_t* rowp = src + (size_t)(row ? y : 0) * src_stride;
+  float t[C];
+#pragma unroll
+  for (int c = 0; c < C; c++) t[c] = 0.0f;
+  while (p < p_end) {
+    const int q = min(p_end, p + chunk_px); // pixels [p, q) of the row: (q - p) * PB + 15 <= STAGE_DATA (the launcher)
+    const uint8_t* a = rowp + (size_t)p * PB;
+    const int head = (int)((uintptr_t)a & 15);
+    if (row) {
+      const uint8_t* g = a - head;               // LDS byte b = the byte at g + b; the run is b in [head, total)
+      const int total = head + (q - p) * PB;
+      const int u1 = total >> 4;                 // 16-byte units [head ? 1 : 0, u1) lie inside the run
+#pragma unroll 4
+      for (int u = (head ? 1 : 0) + lane; u < u1; u += 64) {
+        const uint4 v = *reinterpret_cast<const uint4*>(g + 16 * u);
+        uint32_t* o = reinterpret_cast<uint32_t*>(buf + stage_at(16 * u)); // (a unit never straddles a pad)
+        o[0] = v.x; o[1] = v.y; o[2] = v.z; o[3] = v.w;
+      }
+      if (lane < 16) { // the partial unit at the head
+        if (head && lane >= head && lane < total) buf[stage_at(lane)] = g[lane];
+      }
+      else if (lane < 32) { // ... and at the tail
+        const int b = 16 * u1 + lane - 16;
+        if (b >= head && b < total) buf[stage_at(b)] = g[b];
+      }
+    }
+    __syncthreads();
+    if (row && col) {
+      const int i0 = max(0, p - fj), i1 = min(nj, q - fj);
+      constexpr int G = C == 4 ? 2 : 4; // taps whose weights and samples are in flight together (at most 64 VGPRs), summed in the taps' order
+      int i = i0;
+      for (; i + G <= i1; i += G) {
+        float w[G];
+        InT v[G][C];
+#pragma unroll
+        for (int k = 0; k < G; k++) w[k] = wts[(size_t)(i + k) * ow + j];
+#pragma unroll
+        for (int k = 0; k < G; k++) {
+          const int b = head + (fj + i + k - p) * PB;
+#pragma unroll
+          for (int c = 0; c < C; c++) v[k][c] = *reinterpret_cast<const InT*>(buf + stage_at(b + c * SB));
+        }
+#pragma unroll
+        for (int k = 0; k < G; k++) {
+#pragma unroll
+          for (int c = 0; c < C; c++) t[c] = __fadd_rn(t[c], __fmul_rn(w[k], (float)v[k][c]));
+        }
+      }
+      for (; i < i1; i++) {
+        const float w = wts[(size_t)i * ow + j];
+        const int b = head + (fj + i - p) * PB;
+#pragma unroll
+        for (int c = 0; c < C; c++) {
+          const InT v = *reinterpret_cast<const InT*>(buf + stage_at(b + c * SB));
+          t[c] = __fadd_rn(t[c], __fmul_rn(w, (float)v));
+        }
+      }
+    }
+    __syncthreads();
+    p = q;
+  }
+  if (!row || !col) return;
   float* o = tmp + (long long)y * pitch;
 #pragma unroll
   for (int c = 0; c < C; c++) {
@@ -143,6 +246,11 @@ const void* const g_instances[] = {
   (const void*)k_view_nearest<uint16_t, uint16_t>, (const void*)k_view_nearest<uint16_t, __half>, (const void*)k_view_nearest<uint16_t, float>,
 };
 #undef HM_V_SET
+// ... and of the staged horizontal pass, a list of its own (hm_debug_kernel_regs, code 5)
+const void* const g_staged_instances[] = {
+  (const void*)k_resample_h_staged<1, 3, true>, (const void*)k_resample_h_staged<1, 3, false>, (const void*)k_resample_h_staged<1, 4, true>, (const void*)k_resample_h_staged<1, 4, false>,
+  (const void*)k_resample_h_staged<2, 3, true>, (const void*)k_resample_h_staged<2, 3, false>, (const void*)k_resample_h_staged<2, 4, true>, (const void*)k_resample_h_staged<2, 4, false>,
+};
 
 template <int SB, int C>
 void launch_h(bool chw, const hm_resample_args* r, hipStream_t s)
@@ -155,6 +263,21 @@ void launch_h(bool chw, const hm_resample_args* r, hipStream_t s)
   else
     hipLaunchKernelGGL((k_resample_h<SB, C, false>), grid, block, 0, s, src, r->src_stride, r->n_h, r->ow, r->ax.first, r->ax.count, r->ax.weights, r->tmp,
                        (long long)r->tmp_pitch, (long long)r->tmp_plane);
+}
+
+template <int SB, int C>
+void launch_h_staged(bool chw, const hm_resample_args* r, hipStream_t s)
+{
+  const dim3 grid((unsigned)((r->ow + 63) / 64), (unsigned)((r->n_h + 3) / 4)), block(256);
+  const uint8_t* src = (const uint8_t*)r->src;
+  constexpr int most = (STAGE_DATA - 15) / (SB * C); // pixels of a chunk behind the longest alignment head
+  const int chunk_px = r->stage_px > 0 && r->stage_px < most ? r->stage_px : most;
+  if (chw)
+    hipLaunchKernelGGL((k_resample_h_staged<SB, C, true>), grid, block, 0, s, src, r->src_stride, r->n_h, r->ow, r->ax.first, r->ax.count, r->ax.weights, r->tmp,
+                       (long long)r->tmp_pitch, (long long)r->tmp_plane, chunk_px);
+  else
+    hipLaunchKernelGGL((k_resample_h_staged<SB, C, false>), grid, block, 0, s, src, r->src_stride, r->n_h, r->ow, r->ax.first, r->ax.count, r->ax.weights, r->tmp,
+                       (long long)r->tmp_pitch, (long long)r->tmp_plane, chunk_px);
 }
 
 template <typename OutT, int P, int C>
@@ -199,6 +322,11 @@ extern "C" const void* hm_resample_kernel_of(int index) // (test_hooks.cpp: hm_d
   return index >= 0 && index < (int)(sizeof(g_instances) / sizeof(g_instances[0])) ? g_instances[index] : nullptr;
 }
 
+extern "C" const void* hm_resample_staged_kernel_of(int index) // (test_hooks.cpp: hm_debug_kernel_regs)
+{
+  return index >= 0 && index < (int)(sizeof(g_staged_instances) / sizeof(g_staged_instances[0])) ? g_staged_instances[index] : nullptr;
+}
+
 // both passes of a resampled view; `dst` = the destination's first element.  The intermediate is laid out like the destination
 // (r->tmp_plane apart per channel for CHW, interleaved rows for HWC), its pitch a multiple of 16 elements.
 extern "C" int hm_launch_resample(const hm_dest_plan* p, const hm_resample_args* r, void* dst, const float scale[4], const float bias[4], hipStream_t s)
@@ -206,7 +334,11 @@ extern "C" int hm_launch_resample(const hm_dest_plan* p, const hm_resample_args*
   if (r->ow <= 0 || r->oh <= 0 || r->n_w <= 0 || r->n_h <= 0) return HM_OK;
   if ((r->tmp_pitch % 16) || (r->tmp_plane % 4) || ((uintptr_t)r->tmp % 16)) return hm_fail(HM_ERR_INTERNAL, "k_resample: misaligned intermediate");
   const bool chw = p->layout == HM_DEV_LAYOUT_CHW;
-  if (r->sample_bytes == 1) { if (r->channels == 3) launch_h<1, 3>(chw, r, s); else launch_h<1, 4>(chw, r, s); }
+  if (r->staged) {
+    if (r->sample_bytes == 1) { if (r->channels == 3) launch_h_staged<1, 3>(chw, r, s); else launch_h_staged<1, 4>(chw, r, s); }
+    else { if (r->channels == 3) launch_h_staged<2, 3>(chw, r, s); else launch_h_staged<2, 4>(chw, r, s); }
+  }
+  else if (r->sample_bytes == 1) { if (r->channels == 3) launch_h<1, 3>(chw, r, s); else launch_h<1, 4>(chw, r, s); }
   else { if (r->channels == 3) launch_h<2, 3>(chw, r, s); else launch_h<2, 4>(chw, r, s); }
   int rc = hm_check_hip(hipGetLastError(), "k_resample_h launch");
   if (rc) return rc;

@@ -14,6 +14,7 @@ extern "C" const void* hm_residual_kernel();                                    
 extern "C" const void* hm_tail420_kernel();                                              // filters.hip
 extern "C" const void* hm_tail420_kernel16();
 extern "C" const void* hm_resample_kernel_of(int index);                                    // resample.hip: NULL behind the last instance
+extern "C" const void* hm_resample_staged_kernel_of(int index);                             // ... the instances of k_resample_h_staged
 
 extern "C" {
 
@@ -28,6 +29,7 @@ __attribute__((visibility("default"))) int hm_debug_kernel_regs(int which, int a
   else if (which == 2) fn = hm_chain_kernel_of(a, b, c);
   else if (which == 3) fn = hm_tail420_kernel16();
   else if (which == 4) fn = hm_resample_kernel_of(a); // (the view kernels: a = 0, 1, ... until the call fails)
+  else if (which == 5) fn = hm_resample_staged_kernel_of(a); // (k_resample_h_staged; out[1] counts scratch, not LDS)
   hipFuncAttributes fa;
   if (!fn || !out || hipFuncGetAttributes(&fa, fn) != hipSuccess) return -1;
   out[0] = fa.numRegs;

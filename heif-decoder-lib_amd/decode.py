@@ -6,7 +6,7 @@
 Layouts: "chw" (one plane per channel) and "hwc" (the target's own interleaving).  dtypes: torch.uint8 / torch.uint16 (must be
 the target's own sample type: 8-bit "rgb" / "rgba", 16-bit "rrggbb_le" / "rrggbbaa_le" ...), torch.float16, torch.float32;
 floats are sample * scale[c] + bias[c], rounded after each step.  crop=(x, y, w, h) and size=(w, h) ask for a rectangle of the image,
-resampled (filter "triangle": antialiased bilinear, or "nearest") in the step that writes the tensor; of a grid only the tiles the
+resampled (filter "triangle": antialiased bilinear, "bicubic", "lanczos3" or "nearest") in the step that writes the tensor; of a grid only the tiles the
 rectangle touches are decoded.  What the library refuses raises capi.HmError."""
 import ctypes as C
 import os
@@ -16,7 +16,7 @@ from . import capi
 OUT_FORMATS = {"rgb": capi.HM_OUT_RGB, "rgba": capi.HM_OUT_RGBA, "rrggbb_le": capi.HM_OUT_RRGGBB_LE, "rrggbb_be": capi.HM_OUT_RRGGBB_BE,
                "rrggbbaa_le": capi.HM_OUT_RRGGBBAA_LE, "rrggbbaa_be": capi.HM_OUT_RRGGBBAA_BE}
 LAYOUTS = {"hwc": capi.HM_DEV_LAYOUT_HWC, "chw": capi.HM_DEV_LAYOUT_CHW}
-FILTERS = {"triangle": capi.HM_VIEW_TRIANGLE, "nearest": capi.HM_VIEW_NEAREST}
+FILTERS = {"triangle": capi.HM_VIEW_TRIANGLE, "nearest": capi.HM_VIEW_NEAREST, "bicubic": capi.HM_VIEW_CUBIC, "lanczos3": capi.HM_VIEW_LANCZOS3}
 
 
 def _out_format(out_format):
@@ -134,7 +134,7 @@ def decode_to_tensor(data, item_id=0, out_format="rgb", layout="chw", dtype=None
     ("hwc").  dtype defaults to torch.float32 (out's dtype when out is given).  out: a CUDA tensor of that shape to write into;
     its row (and plane) stride is honoured, bytes between rows are left alone.  stream: a torch.cuda.Stream or a raw stream
     handle (default: the current stream).  crop: (x, y, w, h), a rectangle of the image; size: (w, h), what it is resampled to
-    (H and W of the tensor are then the size's, or the crop's); filter: "triangle" or "nearest".  Returns when the pixels are in place."""
+    (H and W of the tensor are then the size's, or the crop's); filter: "triangle", "bicubic", "lanczos3" or "nearest".  Returns when the pixels are in place."""
     import torch
     L = capi.image_lib()
     fmt, lay = _out_format(out_format), _layout(layout)

@@ -514,20 +514,33 @@ HM_API int hm_pipeline_submit_to_device(hm_pipeline* p, const uint8_t* heif, siz
  * up-sampling, a sub-grid origin that is even in every subsampled direction - hm_plan_view tells; everything else decodes the
  * whole item and applies the view at the end, with identical bytes).  A coded picture outside the sub-grid is not looked at:
  * damage there neither fails the call nor sets HM_WARN_CONCEALED.
- * Per axis, n = crop extent, m = output extent, in double:  s = n / m, fs = max(s, 1), c = (j + 0.5) * s,
- * lo = max(0, (int)(c - fs + 0.5)), hi = min(n, (int)(c + fs + 0.5)), w_i = max(0, 1 - |(i + 0.5 - c) / fs|) for i in [lo, hi),
- * table entry (float)(w_i / W) with W the sum of the w_i in increasing i (the antialiased bilinear filter of PIL and of
- * torch.nn.functional.interpolate(mode="bilinear", antialias=True); taps never leave the crop: "crop, then resize").
+ * Per axis, n = crop extent, m = output extent, a = the filter's support (1 HM_VIEW_TRIANGLE, 2 HM_VIEW_CUBIC, 3 HM_VIEW_LANCZOS3),
+ * in double:  s = n / m, fs = max(s, 1), c = (j + 0.5) * s, lo = max(0, (int)(c - a * fs + 0.5)), hi = min(n, (int)(c + a * fs + 0.5)),
+ * w_i = k((i + 0.5 - c) / fs) for i in [lo, hi), table entry (float)(w_i / W) with W the sum of the w_i in increasing i (taps never
+ * leave the crop: "crop, then resize").  The kernel function k of x, with every operation rounded on its own, on |x|:
+ *   HM_VIEW_TRIANGLE  max(0, 1 - x): the antialiased bilinear filter of PIL and of torch.nn.functional.interpolate(mode="bilinear",
+ *                     antialias=True);
+ *   HM_VIEW_CUBIC     Keys' cubic with a = -0.5, PIL's BICUBIC and torch's interpolate(mode="bicubic", antialias=True):
+ *                     x < 1: (1.5 * x - 2.5) * x * x + 1;  1 <= x < 2: ((-0.5 * x + 2.5) * x - 4) * x + 2;  otherwise 0;
+ *   HM_VIEW_LANCZOS3  x == 0: 1;  x < 3: (sin(p) / p) * (sin(q) / q) with p = pi * x (pi = 3.14159265358979323846), q = p / 3 and the
+ *                     C library's sin;  otherwise 0.
  * Per channel (alpha like any other, no premultiplication), in float32 without fused multiply-add: horizontally
  * t = 0, t = t + w * (float)v for i increasing, then vertically the same over the t, giving r; integer destinations store
  * min(max((int)(r + 0.5f), 0), peak) with peak 255 / 65535, float destinations r * scale[c] + bias[c] (r not rounded first).
+ * The cubic and Lanczos weights are negative in places, so r can lie below 0 and above the peak (overshoot at hard edges): the
+ * conversion (int)(r + 0.5f) is towards zero - a negative r + 0.5f above -1 becomes 0 - and both clamps act; a float destination
+ * receives the overshoot as it is.
  * HM_VIEW_NEAREST moves the sample at j * n / m (int arithmetic).  out_w == out_h == 0 is the crop alone: the bytes of the full
  * decode's rectangle.  The crop alone and HM_VIEW_NEAREST to HWC with the target's own integer type move bytes: _BE targets allowed.
  * Refused with HM_ERR_INVALID_ARG before any work is queued, the destination unwritten: a crop with a non-positive extent or
- * not inside the image, an output extent below 1 or above 32768, n / m above 256 on an axis, an unknown filter,
- * HM_VIEW_TRIANGLE with a _BE target (ask for _LE), and whatever hm_decode_item_to_device refuses, judged against out_w x out_h. */
+ * not inside the image, an output extent below 1 or above 32768, a reduction n / m on an axis above 256 (HM_VIEW_TRIANGLE,
+ * HM_VIEW_NEAREST), above 128 (HM_VIEW_CUBIC) or above 85 (HM_VIEW_LANCZOS3) - no output has more than 2 * 256 + 2 taps -, an
+ * unknown filter, a resampling filter (every one but HM_VIEW_NEAREST) with a _BE target (ask for _LE), and whatever
+ * hm_decode_item_to_device refuses, judged against out_w x out_h. */
 enum { HM_VIEW_TRIANGLE = 0,   /* antialiased bilinear, defined above */
-       HM_VIEW_NEAREST  = 1 }; /* the reference's scale_nearest_neighbor index rule (pixelimage.cc:1232-1251) */
+       HM_VIEW_NEAREST  = 1,   /* the reference's scale_nearest_neighbor index rule (pixelimage.cc:1232-1251) */
+       HM_VIEW_CUBIC    = 16,  /* antialiased bicubic (Keys, a = -0.5), defined above */
+       HM_VIEW_LANCZOS3 = 17 };/* antialiased Lanczos with three lobes, defined above */
 typedef struct hm_device_view {
   int32_t crop_x, crop_y, crop_w, crop_h;  /* rectangle of the image as hm_decode_item hands it out (after irot / imir /
                                               clap unless ignore_transformations); crop_w == crop_h == 0: the whole image */
