@@ -12,4 +12,4 @@ The directory name contains hyphens, so import it with ``load_package()`` from
 from . import capi  # noqa: F401
 from . import shard  # noqa: F401
 from .capi import lib, HmError  # noqa: F401
-from .decode import decode_to_tensor, decode_batch_to_tensor  # noqa: F401
+from .decode import decode_to_tensor, decode_batch_to_tensor, decode_sequence_to_tensor  # noqa: F401

@@ -207,6 +207,8 @@ def bind_image(L):
     L.hm_decode_item_to_device.argtypes = [C.c_void_p, C.c_uint32, C.POINTER(DecodeParams), C.POINTER(DeviceDest), C.POINTER(Decoded)]
     L.hm_decode_sequence_to_device.argtypes = [C.c_void_p, C.c_uint32, C.c_int32, C.POINTER(DecodeParams), C.POINTER(DeviceDest),
                                                C.POINTER(Decoded), C.POINTER(C.c_int32)]
+    L.hm_decode_frames_to_device_view.argtypes = [C.c_void_p, C.POINTER(C.c_uint32), C.c_int32, C.POINTER(DecodeParams), C.POINTER(DeviceView),
+                                                  C.POINTER(DeviceDest), C.POINTER(Decoded), C.POINTER(C.c_int32)]
     L.hm_pipeline_create.argtypes = [C.POINTER(PipelineConfig), C.POINTER(C.c_void_p)]
     L.hm_pipeline_destroy.argtypes = [C.c_void_p]
     L.hm_pipeline_destroy.restype = None

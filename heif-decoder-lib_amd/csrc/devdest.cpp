@@ -10,6 +10,7 @@
 
 #include "hm_colour_plan.h"
 #include "hm_devdest.h"
+#include "hm_view_batch.h"
 
 extern "C" {
 
@@ -240,25 +241,16 @@ void hm_view_scratch_free(hm_view_scratch* sc)
   sc->pinned = nullptr;
 }
 
-int hm_view_write(const hm_device_dest* d, int out_format, const hm_view_plan* vp, const void* src, int src_stride, hipStream_t s, hm_view_scratch* sc)
+// the tap tables of both axes of a resampled view in one pinned block (sc->pinned, `extra` bytes more behind them): first[m],
+// count[m], weights[taps][m] per axis, tap-major.  *staged: the horizontal pass may stage its source run in LDS.
+static int view_tables(const hm_view_plan* vp, size_t extra, hm_view_scratch* sc, size_t* words_x_out, size_t* words_y_out, int* tx_out, int* ty_out, bool* staged_out)
 {
-  hm_dest_plan p;
-  int rc = hm_dest_resolve(out_format, vp->ow, vp->oh, d, &p);
-  if (!rc) rc = hm_dest_check_len(d, &p);
-  if (rc) return rc;
-  const int obpp = p.channels * p.sample_bytes;
-  const uint8_t* origin = (const uint8_t*)src + (size_t)vp->y * src_stride + (size_t)vp->x * obpp;
-  if (vp->crop_only) // the rectangle's bytes: the 2-D copy or k_to_tensor on the offset source
-    return hm_dest_write(d, out_format, vp->w, vp->h, 0, vp->h, origin, src_stride, s);
-  if (vp->filter == HM_VIEW_NEAREST)
-    return hm_launch_view_nearest(&p, origin, src_stride, vp->w, vp->h, vp->ow, vp->oh, d->ptr, d->scale, d->bias, s);
-  // tap tables of both axes in one pinned block and one upload: first[m], count[m], weights[taps][m] per axis
   const int filt = vp->filter;
   int tx = 0, ty = 0, f0;
   for (int j = 0; j < vp->ow; j++) { const int cnt = axis_taps(vp->w, vp->ow, filt, j, &f0, nullptr); if (cnt < 0) return cnt; tx = std::max(tx, cnt); }
   for (int k = 0; k < vp->oh; k++) { const int cnt = axis_taps(vp->h, vp->oh, filt, k, &f0, nullptr); if (cnt < 0) return cnt; ty = std::max(ty, cnt); }
   const size_t words_x = (size_t)vp->ow * (2 + tx), words_y = (size_t)vp->oh * (2 + ty), bytes = (words_x + words_y) * 4;
-  int32_t* host = (int32_t*)hm_pool_pinned_alloc(bytes);
+  int32_t* host = (int32_t*)hm_pool_pinned_alloc(bytes + extra);
   if (!host) return hm_fail(HM_ERR_NOMEM, "out of memory");
   sc->pinned = host;
   float w[HM_VIEW_MAX_TAPS + 2];
@@ -281,6 +273,28 @@ int hm_view_write(const hm_device_dest* d, int out_format, const hm_view_plan* v
       if (lo < 0 || hi > vp->w || hi <= lo || (j && (lo < host[j - 1] || hi < host[j - 1] + host[vp->ow + j - 1])))
         return hm_fail(HM_ERR_INTERNAL, "view: the windows of columns %d and %d are not in order", j - 1, j);
     }
+  *words_x_out = words_x; *words_y_out = words_y; *tx_out = tx; *ty_out = ty; *staged_out = staged;
+  return HM_OK;
+}
+
+int hm_view_write(const hm_device_dest* d, int out_format, const hm_view_plan* vp, const void* src, int src_stride, hipStream_t s, hm_view_scratch* sc)
+{
+  hm_dest_plan p;
+  int rc = hm_dest_resolve(out_format, vp->ow, vp->oh, d, &p);
+  if (!rc) rc = hm_dest_check_len(d, &p);
+  if (rc) return rc;
+  const int obpp = p.channels * p.sample_bytes;
+  const uint8_t* origin = (const uint8_t*)src + (size_t)vp->y * src_stride + (size_t)vp->x * obpp;
+  if (vp->crop_only) // the rectangle's bytes: the 2-D copy or k_to_tensor on the offset source
+    return hm_dest_write(d, out_format, vp->w, vp->h, 0, vp->h, origin, src_stride, s);
+  if (vp->filter == HM_VIEW_NEAREST)
+    return hm_launch_view_nearest(&p, origin, src_stride, vp->w, vp->h, vp->ow, vp->oh, d->ptr, d->scale, d->bias, s);
+  size_t words_x = 0, words_y = 0;
+  int tx = 0, ty = 0;
+  bool staged = false;
+  if ((rc = view_tables(vp, 0, sc, &words_x, &words_y, &tx, &ty, &staged))) return rc;
+  const size_t bytes = (words_x + words_y) * 4;
+  int32_t* host = (int32_t*)sc->pinned;
   const bool chw = p.layout == HM_DEV_LAYOUT_CHW;
   const int64_t E = chw ? vp->ow : (int64_t)vp->ow * p.channels, pitch = (E + 15) / 16 * 16, plane = pitch * vp->h;
   if (!(sc->dev[0] = hm_pool_device_alloc(bytes)) || !(sc->dev[1] = hm_pool_device_alloc((size_t)plane * (chw ? p.channels : 1) * sizeof(float)))) return HM_ERR_NO_DEVICE;
@@ -297,6 +311,97 @@ int hm_view_write(const hm_device_dest* d, int out_format, const hm_view_plan* v
   a.tmp = (float*)sc->dev[1]; a.tmp_pitch = pitch; a.tmp_plane = plane;
   a.staged = staged ? 1 : 0; a.stage_px = hm_knob(HM_KNOB_VIEW_STAGE_PX);
   return hm_launch_resample(&p, &a, d->ptr, d->scale, d->bias, s);
+}
+
+// one group of a batched view write: frames idx[0 .. m) of `it` share the plan p, the view and everything else of the key
+static int view_write_group(const hm_view_item* it, const int* idx, int m, const hm_dest_plan& p, hipStream_t s, hm_view_scratch* sc)
+{
+  const hm_view_plan* vp = &it[idx[0]].vp;
+  const hm_device_dest* d0 = it[idx[0]].dest;
+  const int obpp = p.channels * p.sample_bytes;
+  const bool chw = p.layout == HM_DEV_LAYOUT_CHW;
+  const int planes = chw ? p.channels : 1;
+  size_t words_x = 0, words_y = 0;
+  int tx = 0, ty = 0, rc;
+  bool staged = false;
+  // ONE pinned block and one upload: the tap tables, then the frames' source origins and destinations
+  if ((rc = view_tables(vp, 16 + 16 * (size_t)m, sc, &words_x, &words_y, &tx, &ty, &staged))) return rc;
+  const hm_view_block lay = hm_view_block_layout((int64_t)words_x, (int64_t)words_y, m);
+  uint8_t* host = (uint8_t*)sc->pinned;
+  const void** hsrc = reinterpret_cast<const void**>(host + lay.src_off);
+  void** hdst = reinterpret_cast<void**>(host + lay.dst_off);
+  bool vec = true;
+  for (int i = 0; i < m; i++) {
+    const hm_view_item& f = it[idx[i]];
+    hsrc[i] = (const uint8_t*)f.src + (size_t)vp->y * f.src_stride + (size_t)vp->x * obpp;
+    hdst[i] = f.dest->ptr;
+    vec = vec && ((uintptr_t)f.dest->ptr % 16) == 0;
+  }
+  vec = vec && (p.row_pitch % 16) == 0 && (!chw || (p.plane_pitch % 16) == 0);
+  // the intermediate of one chunk of frames, reused chunk after chunk in stream order
+  const int64_t E = chw ? vp->ow : (int64_t)vp->ow * p.channels, pitch = (E + 15) / 16 * 16, plane = pitch * vp->h, frame_stride = plane * planes;
+  const int64_t bound = hm_knob(HM_KNOB_VIEW_BATCH_BYTES);
+  const int per_chunk = (int)std::min<int64_t>(m, hm_view_chunk_frames(vp->ow, vp->h, p.channels, planes, bound));
+  if (!(sc->dev[0] = hm_pool_device_alloc((size_t)lay.bytes)) || !(sc->dev[1] = hm_pool_device_alloc((size_t)frame_stride * per_chunk * sizeof(float)))) return HM_ERR_NO_DEVICE;
+  if ((rc = hm_check_hip(hipMemcpyAsync(sc->dev[0], host, (size_t)lay.bytes, hipMemcpyHostToDevice, s), "upload of the tap tables"))) return rc;
+  hm_resample_args a;
+  std::memset(&a, 0, sizeof(a));
+  a.sample_bytes = p.sample_bytes; a.channels = p.channels;
+  a.src = nullptr; a.src_stride = it[idx[0]].src_stride;
+  a.n_w = vp->w; a.n_h = vp->h; a.ow = vp->ow; a.oh = vp->oh;
+  const int32_t* dx = (const int32_t*)sc->dev[0];
+  const int32_t* dy = dx + words_x;
+  a.ax.first = dx; a.ax.count = dx + vp->ow; a.ax.weights = reinterpret_cast<const float*>(dx + 2 * (size_t)vp->ow); a.ax.m = vp->ow; a.ax.taps = tx;
+  a.ay.first = dy; a.ay.count = dy + vp->oh; a.ay.weights = reinterpret_cast<const float*>(dy + 2 * (size_t)vp->oh); a.ay.m = vp->oh; a.ay.taps = ty;
+  a.tmp = (float*)sc->dev[1]; a.tmp_pitch = pitch; a.tmp_plane = plane;
+  a.staged = staged ? 1 : 0; a.stage_px = hm_knob(HM_KNOB_VIEW_STAGE_PX);
+  const void* const* dsrc = reinterpret_cast<const void* const*>((const uint8_t*)sc->dev[0] + lay.src_off);
+  void* const* ddst = reinterpret_cast<void* const*>((uint8_t*)sc->dev[0] + lay.dst_off);
+  for (int c0 = 0; c0 < m; c0 += per_chunk) {
+    hm_resample_batch b;
+    b.srcs = dsrc + c0; b.dsts = ddst + c0;
+    b.frames = std::min(per_chunk, m - c0);
+    b.vec = vec ? 1 : 0;
+    b.frame_stride = frame_stride;
+    if ((rc = hm_launch_resample_batch(&p, &a, &b, d0->scale, d0->bias, s))) return rc;
+  }
+  return HM_OK;
+}
+
+int hm_view_write_batch(int out_format, const hm_view_item* it, int n, hipStream_t s, hm_view_scratch* sc)
+{
+  if (n <= 0) return HM_OK;
+  std::vector<hm_dest_plan> plans((size_t)n);
+  for (int k = 0; k < n; k++) { // every destination, before anything is queued
+    int rc = hm_dest_resolve(out_format, it[k].vp.ow, it[k].vp.oh, it[k].dest, &plans[k]);
+    if (!rc) rc = hm_dest_check_len(it[k].dest, &plans[k]);
+    if (rc) return rc;
+  }
+  const bool batched = hm_knob(HM_KNOB_VIEW_BATCH) != 0;
+  std::vector<hm_view_batch_key> keys;
+  std::vector<std::vector<int>> members;
+  for (int k = 0; k < n; k++) {
+    const hm_view_plan& vp = it[k].vp;
+    if (!batched || vp.crop_only || vp.filter == HM_VIEW_NEAREST) { // what exists, frame by frame
+      const int rc = hm_view_write(it[k].dest, out_format, &vp, it[k].src, it[k].src_stride, s, &sc[k]);
+      if (rc) return rc;
+      continue;
+    }
+    const hm_dest_plan& p = plans[k];
+    const int32_t crop[4] = {vp.x, vp.y, vp.w, vp.h};
+    hm_view_batch_key key;
+    hm_view_batch_key_make(&key, crop, vp.ow, vp.oh, vp.filter, p.sample_bytes, p.channels, p.layout, p.dtype, it[k].src_stride, p.row_pitch, p.plane_pitch,
+                           (uintptr_t)it[k].dest->ptr, p.layout == HM_DEV_LAYOUT_CHW, it[k].dest->scale, it[k].dest->bias);
+    size_t g = 0;
+    while (g < keys.size() && !hm_view_batch_key_equal(&keys[g], &key)) g++;
+    if (g == keys.size()) { keys.push_back(key); members.emplace_back(); }
+    members[g].push_back(k);
+  }
+  for (const std::vector<int>& m : members) { // (a group's blocks hang on the scratch entry of its first frame: unused otherwise)
+    const int rc = view_write_group(it, m.data(), (int)m.size(), plans[(size_t)m[0]], s, &sc[m[0]]);
+    if (rc) return rc;
+  }
+  return HM_OK;
 }
 
 // hm_resample_to_tensor returns before its kernels have run: the blocks they work on go back to the pools once the stream has

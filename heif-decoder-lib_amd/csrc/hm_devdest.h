@@ -49,6 +49,15 @@ int hm_view_resolve(int out_format, int src_w, int src_h, const hm_device_view* 
 // against vp->ow x vp->oh; asynchronous on `s`
 int hm_view_write(const hm_device_dest* d, int out_format, const hm_view_plan* vp, const void* src, int src_stride, hipStream_t s, hm_view_scratch* sc);
 
+// one frame of a batched view write: hm_view_write's arguments
+typedef struct hm_view_item { const hm_device_dest* dest; hm_view_plan vp; const void* src; int32_t src_stride; } hm_view_item;
+// hm_view_write over n frames (a sequence under one view).  Frames that agree in crop, output size, filter, sample format,
+// source stride, the destination's layout, dtype, pitches, scale, bias and 16-byte alignment form a group: one pair of tap tables,
+// one upload (tables + the frames' pointers), one bounded intermediate, and per chunk of frames one launch per pass
+// (hm_view_batch.h holds the arithmetic).  The crop alone and HM_VIEW_NEAREST stay calls of hm_view_write per frame, and so does
+// everything with knob view_batch = 0.  Every destination is checked before anything is queued.  sc: n zeroed entries.
+int hm_view_write_batch(int out_format, const hm_view_item* items, int n, hipStream_t s, hm_view_scratch* sc);
+
 // one axis' taps as the kernels read them: first[m], count[m], weights[taps][m] (tap-major: consecutive outputs are neighbours)
 typedef struct hm_view_axis { const int32_t* first; const int32_t* count; const float* weights; int32_t m, taps; } hm_view_axis;
 typedef struct hm_resample_args {
@@ -61,6 +70,14 @@ typedef struct hm_resample_args {
   int32_t stage_px;                     // > 0: at most that many pixels per staged chunk (knob view_stage_px: tests)
 } hm_resample_args;
 int hm_launch_resample(const hm_dest_plan* p, const hm_resample_args* a, void* dst, const float scale[4], const float bias[4], hipStream_t s);
+// the frames of one chunk of a batched view write: device arrays of the frames' source origins and destinations
+typedef struct hm_resample_batch {
+  const void* const* srcs; void* const* dsts;
+  int32_t frames;
+  int32_t vec;            // every destination takes 16-byte stores
+  int64_t frame_stride;   // elements of the intermediate per frame
+} hm_resample_batch;
+int hm_launch_resample_batch(const hm_dest_plan* p, const hm_resample_args* a, const hm_resample_batch* b, const float scale[4], const float bias[4], hipStream_t s);
 int hm_launch_view_nearest(const hm_dest_plan* p, const void* src, int src_stride, int n_w, int n_h, int ow, int oh, void* dst, const float scale[4],
                            const float bias[4], hipStream_t s);
 

@@ -753,9 +753,10 @@ void parse_picture(const hm_file* f, uint32_t id, bool few_pictures, int strict,
 // conversion (unless the batch did it: I.rgb_attached), the alpha plane, and the copy to params->ext_dst or to pinned host
 // planes - all queued on `s`.  `dout` and `alpha_sdr` must live until the stream has drained.
 // dest (may be NULL): caller-owned device memory the interleaved pixels go to instead (hm_device_dest); nothing is copied to the host then.
+// view_later (may be NULL, with view): the view is not written here, only described there - the caller writes it with those of other images.
 int emit_image(const hm_decode_params* params, hipStream_t s, PlanarImage& I, const DevPlane* alpha, int alpha_bd, DevMem& dout,
                DevPlane& alpha_sdr, hm_decoded* out, const hm_device_dest* dest = nullptr, const hm_device_view* view = nullptr,
-               hm_view_scratch* view_scratch = nullptr)
+               hm_view_scratch* view_scratch = nullptr, hm_view_item* view_later = nullptr)
 {
   int rc;
   DevPlane (&P)[3] = I.P;
@@ -893,7 +894,8 @@ int emit_image(const hm_decode_params* params, hipStream_t s, PlanarImage& I, co
     out->plane_width[0] = img_w; out->plane_height[0] = img_h;
     if (dest) { // the image's w x h x C elements and nothing else: a 2-D device copy or k_to_tensor (devdest.cpp)
       if (view) {
-        if ((rc = hm_view_write(dest, params->out_format, &vp, dout.p, cd.out_stride, s, view_scratch))) return rc;
+        if (view_later) { view_later->dest = dest; view_later->vp = vp; view_later->src = dout.p; view_later->src_stride = cd.out_stride; } // (a sequence: hm_view_write_batch)
+        else if ((rc = hm_view_write(dest, params->out_format, &vp, dout.p, cd.out_stride, s, view_scratch))) return rc;
         out->width = vp.ow; out->height = vp.oh;
         out->plane_width[0] = vp.ow; out->plane_height[0] = vp.oh;
       }
@@ -1140,13 +1142,13 @@ int hm_file_sequence_info(const hm_file* f, hm_sequence_info* info)
   return HM_OK;
 }
 
-static int decode_sequence(const hm_file* f, uint32_t first, int32_t count, const hm_decode_params* params, const hm_frame_dest* dests,
-                           const hm_device_dest* ddests, hm_decoded* out, int32_t* failed_frame);
+static int decode_sequence(const hm_file* f, const uint32_t* frames, uint32_t first, int32_t count, const hm_decode_params* params, const hm_frame_dest* dests,
+                           const hm_device_dest* ddests, const hm_device_view* view, hm_decoded* out, int32_t* failed_frame);
 
 int hm_decode_sequence(const hm_file* f, uint32_t first, int32_t count, const hm_decode_params* params, const hm_frame_dest* dests,
                        hm_decoded* out, int32_t* failed_frame)
 {
-  return decode_sequence(f, first, count, params, dests, nullptr, out, failed_frame);
+  return decode_sequence(f, nullptr, first, count, params, dests, nullptr, nullptr, out, failed_frame);
 }
 
 int hm_decode_sequence_to_device(const hm_file* f, uint32_t first, int32_t count, const hm_decode_params* params, const hm_device_dest* dests,
@@ -1154,12 +1156,22 @@ int hm_decode_sequence_to_device(const hm_file* f, uint32_t first, int32_t count
 {
   if (failed_frame) *failed_frame = -1;
   if (!dests) return hm_fail(HM_ERR_INVALID_ARG, "null argument");
-  return decode_sequence(f, first, count, params, nullptr, dests, out, failed_frame);
+  return decode_sequence(f, nullptr, first, count, params, nullptr, dests, nullptr, out, failed_frame);
 }
 
-// ddests (NULL, or `count` entries): every frame goes to caller-owned device memory
-static int decode_sequence(const hm_file* f, uint32_t first, int32_t count, const hm_decode_params* params, const hm_frame_dest* dests,
-                           const hm_device_dest* ddests, hm_decoded* out, int32_t* failed_frame)
+int hm_decode_frames_to_device_view(const hm_file* f, const uint32_t* frames, int32_t count, const hm_decode_params* params, const hm_device_view* view,
+                                    const hm_device_dest* dests, hm_decoded* out, int32_t* failed_frame)
+{
+  if (failed_frame) *failed_frame = -1;
+  if (!frames || !dests) return hm_fail(HM_ERR_INVALID_ARG, "null argument");
+  return decode_sequence(f, frames, 0, count, params, nullptr, dests, view, out, failed_frame);
+}
+
+// frames (NULL: first .. first + count - 1): the 1-based IDs of the frames, in any order, repeats allowed.
+// ddests (NULL, or `count` entries): every frame goes to caller-owned device memory; view (NULL, or with ddests): the same rectangle
+// of every frame, resampled, in one batched write behind the frames' conversions (hm_view_write_batch)
+static int decode_sequence(const hm_file* f, const uint32_t* frames, uint32_t first, int32_t count, const hm_decode_params* params, const hm_frame_dest* dests,
+                           const hm_device_dest* ddests, const hm_device_view* view, hm_decoded* out, int32_t* failed_frame)
 {
   if (failed_frame) *failed_frame = -1;
   if (!f || !params || !out) return hm_fail(HM_ERR_INVALID_ARG, "null argument");
@@ -1167,8 +1179,16 @@ static int decode_sequence(const hm_file* f, uint32_t first, int32_t count, cons
   for (int k = 0; k < count; k++) std::memset(&out[k], 0, sizeof(out[k]));
   if (!f->file.is_movie()) return hm_fail(HM_ERR_INVALID_ARG, "the file is not an image sequence");
   const uint32_t n_frames = f->file.movie().frame_count;
-  if (first < 1 || (uint64_t)first + (uint64_t)count - 1 > n_frames)
+  if (frames) {
+    for (int k = 0; k < count; k++)
+      if (frames[k] < 1 || frames[k] > n_frames) {
+        if (failed_frame) *failed_frame = k;
+        return hm_fail(HM_ERR_INVALID_ARG, "frames[%d] = %u outside 1..%u", k, frames[k], n_frames);
+      }
+  }
+  else if (first < 1 || (uint64_t)first + (uint64_t)count - 1 > n_frames)
     return hm_fail(HM_ERR_INVALID_ARG, "frames %u..%llu outside 1..%u", first, (unsigned long long)first + count - 1, n_frames);
+  auto frame_id = [&](int k) { return frames ? frames[k] : first + (uint32_t)k; };
   if (params->ext_dst) return hm_fail(HM_ERR_INVALID_ARG, "params->ext_dst: a sequence takes its caller buffers from dests");
   if (ddests) { // what can be refused without the frames' sizes (those: below, behind the entropy decode, before anything is queued)
     for (int k = 0; k < count; k++) {
@@ -1176,6 +1196,16 @@ static int decode_sequence(const hm_file* f, uint32_t first, int32_t count, cons
       if (rc) return rc;
       if (!ddests[k].ptr) return hm_fail(HM_ERR_INVALID_ARG, "device destination of frame %d: null ptr", k);
     }
+    if (view) // the view and each destination against the size the track declares (the decoded size: below), as hm_decode_item_to_device_view
+      for (int k = 0; k < count; k++) {
+        hm_image_info info;
+        if (hm_file_image_info(f, frame_id(k), &info) != HM_OK || info.width <= 0 || info.height <= 0) continue; // (such a frame fails below with its own message)
+        hm_view_plan vp;
+        hm_dest_plan dp;
+        int rc = hm_view_resolve(params->out_format, info.width, info.height, view, &vp);
+        if (!rc && !(rc = hm_dest_resolve(params->out_format, vp.ow, vp.oh, &ddests[k], &dp))) rc = hm_dest_check_len(&ddests[k], &dp);
+        if (rc) { if (failed_frame) *failed_frame = k; return rc; }
+      }
     int n_dev = 0;
     if (hipGetDeviceCount(&n_dev) != hipSuccess || n_dev == 0) { (void)hipGetLastError(); return hm_fail(HM_ERR_NO_DEVICE, "no HIP device available"); }
     for (int k = 0; k < count; k++) {
@@ -1196,7 +1226,7 @@ static int decode_sequence(const hm_file* f, uint32_t first, int32_t count, cons
   std::vector<std::unique_ptr<SeqFrame>> F((size_t)count);
   for (int k = 0; k < count; k++) {
     F[k].reset(new SeqFrame());
-    const int rc = plan_item(f, first + (uint32_t)k, F[k]->P);
+    const int rc = plan_item(f, frame_id(k), F[k]->P);
     if (rc) { if (failed_frame) *failed_frame = k; return rc; }
   }
   const bool few = count <= 64;
@@ -1231,7 +1261,10 @@ static int decode_sequence(const hm_file* f, uint32_t first, int32_t count, cons
     I.chroma = h->chroma_format; I.bd = h->bit_depth_y; I.is_grid = false;
     if (ddests) {
       hm_dest_plan dp;
-      int drc = hm_dest_resolve(params->out_format, I.w, I.h, &ddests[k], &dp);
+      hm_view_plan vp;
+      vp.ow = I.w; vp.oh = I.h;
+      int drc = view ? hm_view_resolve(params->out_format, I.w, I.h, view, &vp) : HM_OK; // (against the frame's own decoded size)
+      if (!drc) drc = hm_dest_resolve(params->out_format, vp.ow, vp.oh, &ddests[k], &dp);
       if (!drc) drc = hm_dest_check_len(&ddests[k], &dp);
       if (drc) return fail(drc);
     }
@@ -1283,6 +1316,12 @@ static int decode_sequence(const hm_file* f, uint32_t first, int32_t count, cons
       groups[(size_t)it->second]->frames.push_back(k);
     }
   }
+  struct ViewBlocks { // what the batched view write works on: released once the stream has drained (Drain goes first)
+    std::vector<hm_view_scratch> sc;
+    ~ViewBlocks() { for (hm_view_scratch& x : sc) hm_view_scratch_free(&x); }
+  } view_blocks;
+  std::vector<hm_view_item> view_items;
+  if (view && ddests) { view_blocks.sc.assign((size_t)count, hm_view_scratch{}); view_items.assign((size_t)count, hm_view_item{}); }
   struct Drain { // (declared behind everything the queued work uses: destroyed first, it drains the stream before they go)
     hipStream_t s; bool on = false;
     ~Drain() { if (on) hipStreamSynchronize(s); }
@@ -1336,8 +1375,12 @@ static int decode_sequence(const hm_file* f, uint32_t first, int32_t count, cons
     SeqFrame& Fr = *F[k];
     hm_decode_params pk = *params;
     if (dests) { pk.ext_dst = dests[k].ext_dst; pk.ext_dst_len = dests[k].ext_dst_len; pk.ext_dst_stride = dests[k].ext_dst_stride; }
-    if ((rc = emit_image(&pk, s, Fr.I, nullptr, 0, Fr.dout, Fr.alpha_sdr, &out[k], ddests ? &ddests[k] : nullptr))) return release_all(rc);
+    const bool viewed = view && ddests;
+    if ((rc = emit_image(&pk, s, Fr.I, nullptr, 0, Fr.dout, Fr.alpha_sdr, &out[k], ddests ? &ddests[k] : nullptr, viewed ? view : nullptr, nullptr,
+                         viewed ? &view_items[(size_t)k] : nullptr))) return release_all(rc);
   }
+  // ---- the view of every frame: one pair of tap tables and one launch per pass for all frames that share them ----
+  if (view && ddests && (rc = hm_view_write_batch(params->out_format, view_items.data(), count, s, view_blocks.sc.data()))) return release_all(rc);
   lap("sequence: colour + D2H queued");
   const hipError_t e = hipStreamSynchronize(s);
   drain.on = false;

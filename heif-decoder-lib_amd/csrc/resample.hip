@@ -9,6 +9,8 @@
 //   k_resample_v     the vertical pass, fused with dtype, layout, scale and bias: a wave is 64 consecutive element groups of ONE output
 //                    row (of one plane), so its taps are wave-uniform and the intermediate reads and the tensor stores coalesce.  A lane's
 //                    group is 16 bytes of output (one 16-byte store) where pointer and pitches allow, one element otherwise.
+//   k_resample_h_batch, k_resample_h_staged_batch, k_resample_v_batch  the same three passes over the frames of a sequence in one launch
+//                    each (grid z): the per-frame pointers come from arrays, everything else is shared.  Same sums, same order, same bytes.
 //   k_view_nearest   HM_VIEW_NEAREST: the sample at j * n / m is moved (through scale and bias for float destinations), no intermediate.
 // The sums run tap by tap in float32 with separately rounded multiply and add (-ffp-contract=off, __fmul_rn / __fadd_rn): a float32
 // restatement on the host is exact.  Nothing but the out_w x out_h x C elements of the view is ever stored.
@@ -19,10 +21,16 @@
 #include <type_traits>
 
 #include "hm_devdest.h"
+#include "hm_view_batch.h"
 
 namespace {
 
 struct Affine { float scale[4], bias[4]; };
+
+// A pointer a kernel loads from memory is a generic one to the compiler (a kernel argument is known to point to global memory):
+// the batched kernels read their per-frame pointers as pointers to global memory, so that the loads and stores through them are
+// the global ones of the unbatched kernels, not flat ones that might alias LDS.
+typedef __attribute__((address_space(1))) uint8_t GlobalBytes;
 
 // the vertical sum r to an element of the destination
 template <typename OutT> __device__ __forceinline__ OutT finish(float r, float sc, float bi);
@@ -41,9 +49,9 @@ template <> __device__ __forceinline__ __half moved<__half>(unsigned v, float sc
 // SB: bytes per source sample (little-endian), C: channels, CHW: the intermediate has one plane per channel.
 // grid: x = groups of 64 output columns, y = groups of 4 source rows.  src points at the crop's origin.
 template <int SB, int C, bool CHW>
-__global__ __launch_bounds__(256) void k_resample_h(const uint8_t* __restrict__ src, int src_stride, int n_h, int ow, const int32_t* __restrict__ first,
-                                                    const int32_t* __restrict__ count, const float* __restrict__ wts, float* __restrict__ tmp,
-                                                    long long pitch, long long plane)
+__device__ __forceinline__ void resample_h_body(const uint8_t* __restrict__ src, int src_stride, int n_h, int ow, const int32_t* __restrict__ first,
+                                                const int32_t* __restrict__ count, const float* __restrict__ wts, float* __restrict__ tmp,
+                                                long long pitch, long long plane)
 {
   typedef typename std::conditional<SB == 1, uint8_t, uint16_t>::type InT;
   const int j = blockIdx.x * 64 + (threadIdx.x & 63), y = blockIdx.y * 4 + (threadIdx.x >> 6);
@@ -66,6 +74,28 @@ __global__ __launch_bounds__(256) void k_resample_h(const uint8_t* __restrict__ 
   }
 }
 
+template <int SB, int C, bool CHW>
+__global__ __launch_bounds__(256) void k_resample_h(const uint8_t* __restrict__ src, int src_stride, int n_h, int ow, const int32_t* __restrict__ first,
+                                                    const int32_t* __restrict__ count, const float* __restrict__ wts, float* __restrict__ tmp,
+                                                    long long pitch, long long plane)
+{
+  resample_h_body<SB, C, CHW>(src, src_stride, n_h, ow, first, count, wts, tmp, pitch, plane);
+}
+
+// The batched form (hm_view_write_batch: the frames of a sequence under one view): blockIdx.z is the frame within the chunk.  Its
+// source origin comes from the pointer array - one read per workgroup at an address that depends on blockIdx.z alone, so a scalar
+// load into SGPRs, made once, before the tap loop - and its rows of the intermediate lie frame_stride elements behind the frame
+// before.  Everything else, the order of the sum included, is k_resample_h's.
+template <int SB, int C, bool CHW>
+__global__ __launch_bounds__(256) void k_resample_h_batch(const uint8_t* const* __restrict__ srcs, int src_stride, int n_h, int ow,
+                                                          const int32_t* __restrict__ first, const int32_t* __restrict__ count,
+                                                          const float* __restrict__ wts, float* __restrict__ tmp, long long pitch, long long plane,
+                                                          long long frame_stride)
+{
+  const uint8_t* src = (const uint8_t*)(const GlobalBytes*)reinterpret_cast<const uintptr_t*>(srcs)[blockIdx.z];
+  resample_h_body<SB, C, CHW>(src, src_stride, n_h, ow, first, count, wts, tmp + (long long)blockIdx.z * frame_stride, pitch, plane);
+}
+
 // k_resample_h with the source run staged in LDS.  The 64 columns of a wave read the pixels first[c0] .. first[c63] + count[c63] of
 // their row: one contiguous run (the windows' ends do not fall as the column rises: hm_view_write checks the table).  A workgroup is
 // four waves on four consecutive rows of the same 64 columns, so the run's extent - and with it every trip count and barrier below -
@@ -82,13 +112,12 @@ static_assert(STAGE_ROW <= STAGE_ROW_PITCH && STAGE_DATA % 128 == 0 && STAGE_ROW
 __device__ __forceinline__ int stage_at(int b) { return b + ((b >> 7) << 2); }
 
 template <int SB, int C, bool CHW>
-__global__ __launch_bounds__(256) void k_resample_h_staged(const uint8_t* __restrict__ src, int src_stride, int n_h, int ow, const int32_t* __restrict__ first,
-                                                           const int32_t* __restrict__ count, const float* __restrict__ wts, float* __restrict__ tmp,
-                                                           long long pitch, long long plane, int chunk_px)
+__device__ __forceinline__ void resample_h_staged_body(uint8_t* lds, const uint8_t* __restrict__ src, int src_stride, int n_h, int ow,
+                                                       const int32_t* __restrict__ first, const int32_t* __restrict__ count, const float* __restrict__ wts,
+                                                       float* __restrict__ tmp, long long pitch, long long plane, int chunk_px)
 {
   typedef typename std::conditional<SB == 1, uint8_t, uint16_t>::type InT;
   constexpr int PB = SB * C; // bytes per pixel
-  __shared__ __attribute__((aligned(16))) uint8_t lds[4 * STAGE_ROW_PITCH];
   const int lane = threadIdx.x & 63, wv = threadIdx.x >> 6;
   const int j0 = blockIdx.x * 64, j = j0 + lane, y = blockIdx.y * 4 + wv;
   const int jl = min(j0 + 63, ow - 1);
@@ -167,16 +196,44 @@ __global__ __launch_bounds__(256) void k_resample_h_staged(const uint8_t* __rest
   }
 }
 
+template <int SB, int C, bool CHW>
+__global__ __launch_bounds__(256) void k_resample_h_staged(const uint8_t* __restrict__ src, int src_stride, int n_h, int ow, const int32_t* __restrict__ first,
+                                                           const int32_t* __restrict__ count, const float* __restrict__ wts, float* __restrict__ tmp,
+                                                           long long pitch, long long plane, int chunk_px)
+{
+  __shared__ __attribute__((aligned(16))) uint8_t lds[4 * STAGE_ROW_PITCH];
+  resample_h_staged_body<SB, C, CHW>(lds, src, src_stride, n_h, ow, first, count, wts, tmp, pitch, plane, chunk_px);
+}
+
+// The batched form: blockIdx.z is the frame within the chunk, its source origin a scalar load from the pointer array before
+// anything else, its intermediate frame_stride elements behind the frame before (as k_resample_h_batch).  The barriers stay
+// uniform: the extent of the run, the chunks it is cut into and so every trip count depend on the workgroup's 64 columns
+// (first[], count[], chunk_px) alone, which all frames share - blockIdx.z enters the addresses only, and a workgroup lies inside
+// one frame.  (The alignment head of a chunk depends on the frame's source address; it moves bytes inside the LDS image, not a
+// trip count: a chunk fits behind the longest head, 15 bytes, whatever the address.)
+// waves_per_eu(8): without the hint the compiler schedules this form into 78-80 VGPRs (6 waves per SIMD); with it into 49-56,
+// the staged kernel's own budget, still without scratch.
+template <int SB, int C, bool CHW>
+__global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(8))) void k_resample_h_staged_batch(const uint8_t* const* __restrict__ srcs, int src_stride, int n_h, int ow,
+                                                                 const int32_t* __restrict__ first, const int32_t* __restrict__ count,
+                                                                 const float* __restrict__ wts, float* __restrict__ tmp, long long pitch, long long plane,
+                                                                 int chunk_px, long long frame_stride)
+{
+  __shared__ __attribute__((aligned(16))) uint8_t lds[4 * STAGE_ROW_PITCH];
+  const uint8_t* src = (const uint8_t*)(const GlobalBytes*)reinterpret_cast<const uintptr_t*>(srcs)[blockIdx.z];
+  resample_h_staged_body<SB, C, CHW>(lds, src, src_stride, n_h, ow, first, count, wts, tmp + (long long)blockIdx.z * frame_stride, pitch, plane, chunk_px);
+}
+
 // P: elements of one row per lane (16 bytes of output, or 1), C: channels of an interleaved row (HWC), 0 = one plane per channel
 // (CHW: blockIdx.z is the channel).  E: elements per row (out_w, or out_w * C).  grid: x = groups of 64 lanes, y = groups of 4
 // output rows, z = planes.  The intermediate's pitch is a multiple of 16 elements, so a ragged last group loads whole vectors
 // (of padding nobody stores).
 template <typename OutT, int P, int C>
-__global__ __launch_bounds__(256) void k_resample_v(const float* __restrict__ tmp, long long pitch, long long plane, int E, int oh,
-                                                    const int32_t* __restrict__ first, const int32_t* __restrict__ count, const float* __restrict__ wts,
-                                                    uint8_t* __restrict__ dst, long long row_pitch, long long plane_pitch, Affine a)
+__device__ __forceinline__ void resample_v_body(int pl, const float* __restrict__ tmp, long long pitch, long long plane, int E, int oh,
+                                                const int32_t* __restrict__ first, const int32_t* __restrict__ count, const float* __restrict__ wts,
+                                                uint8_t* __restrict__ dst, long long row_pitch, long long plane_pitch, const Affine& a)
 {
-  const int k = blockIdx.y * 4 + (threadIdx.x >> 6), pl = blockIdx.z;
+  const int k = blockIdx.y * 4 + (threadIdx.x >> 6);
   if (k >= oh) return;
   const int e0 = (blockIdx.x * 64 + (threadIdx.x & 63)) * P;
   if (e0 >= E) return;
@@ -217,6 +274,30 @@ __global__ __launch_bounds__(256) void k_resample_v(const float* __restrict__ tm
   for (int q = 0; q < left; q++) op[q] = o[q];
 }
 
+template <typename OutT, int P, int C>
+__global__ __launch_bounds__(256) void k_resample_v(const float* __restrict__ tmp, long long pitch, long long plane, int E, int oh,
+                                                    const int32_t* __restrict__ first, const int32_t* __restrict__ count, const float* __restrict__ wts,
+                                                    uint8_t* __restrict__ dst, long long row_pitch, long long plane_pitch, Affine a)
+{
+  resample_v_body<OutT, P, C>((int)blockIdx.z, tmp, pitch, plane, E, oh, first, count, wts, dst, row_pitch, plane_pitch, a);
+}
+
+// The batched form: blockIdx.z = frame * planes + plane (planes: the channels of a CHW destination, 1 for HWC).  The frame's
+// destination comes from the pointer array (a scalar load: the address depends on blockIdx.z alone), its intermediate lies
+// frame_stride elements behind the frame before.  Pitches, scale, bias and the store width P are those of the whole launch:
+// hm_view_write_batch groups frames by them.
+template <typename OutT, int P, int C>
+__global__ __launch_bounds__(256) void k_resample_v_batch(const float* __restrict__ tmp, long long pitch, long long plane, int E, int oh,
+                                                          const int32_t* __restrict__ first, const int32_t* __restrict__ count,
+                                                          const float* __restrict__ wts, uint8_t* const* __restrict__ dsts, long long row_pitch,
+                                                          long long plane_pitch, Affine a, int planes, long long frame_stride)
+{
+  int fr = blockIdx.z, pl = 0;
+  if (C == 0) hm_view_z_split((int)blockIdx.z, planes, &fr, &pl);
+  uint8_t* dst = (uint8_t*)(GlobalBytes*)reinterpret_cast<const uintptr_t*>(dsts)[fr];
+  resample_v_body<OutT, P, C>(pl, tmp + (long long)fr * frame_stride, pitch, plane, E, oh, first, count, wts, dst, row_pitch, plane_pitch, a);
+}
+
 // HM_VIEW_NEAREST: out pixel (j, k) is source pixel (j * n_w / ow, k * n_h / oh).  grid: x = groups of 64 columns, y = groups of 4 rows.
 template <typename InT, typename OutT>
 __global__ __launch_bounds__(256) void k_view_nearest(const uint8_t* __restrict__ src, int src_stride, int n_w, int n_h, int ow, int oh, int C, int chw,
@@ -251,6 +332,19 @@ const void* const g_staged_instances[] = {
   (const void*)k_resample_h_staged<1, 3, true>, (const void*)k_resample_h_staged<1, 3, false>, (const void*)k_resample_h_staged<1, 4, true>, (const void*)k_resample_h_staged<1, 4, false>,
   (const void*)k_resample_h_staged<2, 3, true>, (const void*)k_resample_h_staged<2, 3, false>, (const void*)k_resample_h_staged<2, 4, true>, (const void*)k_resample_h_staged<2, 4, false>,
 };
+
+// ... and of the batched forms (hm_view_write_batch), a list of its own (hm_debug_kernel_regs, code 6): 8 horizontal, 8 staged, 24 vertical
+#define HM_VB_SET(T) \
+  (const void*)k_resample_v_batch<T, 16 / (int)sizeof(T), 0>, (const void*)k_resample_v_batch<T, 16 / (int)sizeof(T), 3>, (const void*)k_resample_v_batch<T, 16 / (int)sizeof(T), 4>, \
+  (const void*)k_resample_v_batch<T, 1, 0>, (const void*)k_resample_v_batch<T, 1, 3>, (const void*)k_resample_v_batch<T, 1, 4>
+const void* const g_batch_instances[] = {
+  (const void*)k_resample_h_batch<1, 3, true>, (const void*)k_resample_h_batch<1, 3, false>, (const void*)k_resample_h_batch<1, 4, true>, (const void*)k_resample_h_batch<1, 4, false>,
+  (const void*)k_resample_h_batch<2, 3, true>, (const void*)k_resample_h_batch<2, 3, false>, (const void*)k_resample_h_batch<2, 4, true>, (const void*)k_resample_h_batch<2, 4, false>,
+  (const void*)k_resample_h_staged_batch<1, 3, true>, (const void*)k_resample_h_staged_batch<1, 3, false>, (const void*)k_resample_h_staged_batch<1, 4, true>, (const void*)k_resample_h_staged_batch<1, 4, false>,
+  (const void*)k_resample_h_staged_batch<2, 3, true>, (const void*)k_resample_h_staged_batch<2, 3, false>, (const void*)k_resample_h_staged_batch<2, 4, true>, (const void*)k_resample_h_staged_batch<2, 4, false>,
+  HM_VB_SET(uint8_t), HM_VB_SET(uint16_t), HM_VB_SET(__half), HM_VB_SET(float),
+};
+#undef HM_VB_SET
 
 template <int SB, int C>
 void launch_h(bool chw, const hm_resample_args* r, hipStream_t s)
@@ -308,6 +402,49 @@ void launch_nearest(const hm_dest_plan* p, const uint8_t* src, int src_stride, i
                      (long long)p->row_pitch, (long long)p->plane_pitch, a);
 }
 
+// the batched launches: grid z = the frames of the chunk (horizontal), frames x planes (vertical)
+template <int SB, int C>
+void launch_h_batch(bool chw, const hm_resample_args* r, const hm_resample_batch* b, hipStream_t s)
+{
+  const dim3 grid((unsigned)((r->ow + 63) / 64), (unsigned)((r->n_h + 3) / 4), (unsigned)b->frames), block(256);
+  const uint8_t* const* srcs = (const uint8_t* const*)b->srcs;
+  if (r->staged) {
+    constexpr int most = (STAGE_DATA - 15) / (SB * C); // (as launch_h_staged)
+    const int chunk_px = r->stage_px > 0 && r->stage_px < most ? r->stage_px : most;
+    if (chw)
+      hipLaunchKernelGGL((k_resample_h_staged_batch<SB, C, true>), grid, block, 0, s, srcs, r->src_stride, r->n_h, r->ow, r->ax.first, r->ax.count, r->ax.weights, r->tmp,
+                         (long long)r->tmp_pitch, (long long)r->tmp_plane, chunk_px, (long long)b->frame_stride);
+    else
+      hipLaunchKernelGGL((k_resample_h_staged_batch<SB, C, false>), grid, block, 0, s, srcs, r->src_stride, r->n_h, r->ow, r->ax.first, r->ax.count, r->ax.weights, r->tmp,
+                         (long long)r->tmp_pitch, (long long)r->tmp_plane, chunk_px, (long long)b->frame_stride);
+  }
+  else if (chw)
+    hipLaunchKernelGGL((k_resample_h_batch<SB, C, true>), grid, block, 0, s, srcs, r->src_stride, r->n_h, r->ow, r->ax.first, r->ax.count, r->ax.weights, r->tmp,
+                       (long long)r->tmp_pitch, (long long)r->tmp_plane, (long long)b->frame_stride);
+  else
+    hipLaunchKernelGGL((k_resample_h_batch<SB, C, false>), grid, block, 0, s, srcs, r->src_stride, r->n_h, r->ow, r->ax.first, r->ax.count, r->ax.weights, r->tmp,
+                       (long long)r->tmp_pitch, (long long)r->tmp_plane, (long long)b->frame_stride);
+}
+
+template <typename OutT, int P, int C>
+void launch_v_batch_inst(const hm_dest_plan* p, const hm_resample_args* r, const hm_resample_batch* b, const Affine& a, hipStream_t s)
+{
+  const int E = C == 0 ? r->ow : r->ow * C, groups = (E + P - 1) / P, planes = C == 0 ? p->channels : 1;
+  const dim3 grid((unsigned)((groups + 63) / 64), (unsigned)((r->oh + 3) / 4), (unsigned)(b->frames * planes)), block(256);
+  hipLaunchKernelGGL((k_resample_v_batch<OutT, P, C>), grid, block, 0, s, (const float*)r->tmp, (long long)r->tmp_pitch, (long long)r->tmp_plane, E, r->oh, r->ay.first,
+                     r->ay.count, r->ay.weights, (uint8_t* const*)b->dsts, (long long)p->row_pitch, (long long)p->plane_pitch, a, planes, (long long)b->frame_stride);
+}
+
+template <typename OutT>
+void launch_v_batch(const hm_dest_plan* p, const hm_resample_args* r, const hm_resample_batch* b, const Affine& a, hipStream_t s)
+{
+  constexpr int P = 16 / (int)sizeof(OutT);
+  const bool chw = p->layout == HM_DEV_LAYOUT_CHW, vec = b->vec != 0;
+  if (chw) { if (vec) launch_v_batch_inst<OutT, P, 0>(p, r, b, a, s); else launch_v_batch_inst<OutT, 1, 0>(p, r, b, a, s); }
+  else if (p->channels == 3) { if (vec) launch_v_batch_inst<OutT, P, 3>(p, r, b, a, s); else launch_v_batch_inst<OutT, 1, 3>(p, r, b, a, s); }
+  else { if (vec) launch_v_batch_inst<OutT, P, 4>(p, r, b, a, s); else launch_v_batch_inst<OutT, 1, 4>(p, r, b, a, s); }
+}
+
 Affine affine_of(const float scale[4], const float bias[4])
 {
   Affine a;
@@ -325,6 +462,11 @@ extern "C" const void* hm_resample_kernel_of(int index) // (test_hooks.cpp: hm_d
 extern "C" const void* hm_resample_staged_kernel_of(int index) // (test_hooks.cpp: hm_debug_kernel_regs)
 {
   return index >= 0 && index < (int)(sizeof(g_staged_instances) / sizeof(g_staged_instances[0])) ? g_staged_instances[index] : nullptr;
+}
+
+extern "C" const void* hm_resample_batch_kernel_of(int index) // (test_hooks.cpp: hm_debug_kernel_regs)
+{
+  return index >= 0 && index < (int)(sizeof(g_batch_instances) / sizeof(g_batch_instances[0])) ? g_batch_instances[index] : nullptr;
 }
 
 // both passes of a resampled view; `dst` = the destination's first element.  The intermediate is laid out like the destination
@@ -352,6 +494,30 @@ extern "C" int hm_launch_resample(const hm_dest_plan* p, const hm_resample_args*
     default: return hm_fail(HM_ERR_INTERNAL, "k_resample_v: no kernel for dtype %d", p->dtype);
   }
   return hm_check_hip(hipGetLastError(), "k_resample_v launch");
+}
+
+// both passes over the b->frames frames of one chunk (hm_view_write_batch): r->src is not looked at, r->tmp is the chunk's
+// intermediate (b->frame_stride elements per frame), p the plan every frame of the group shares
+extern "C" int hm_launch_resample_batch(const hm_dest_plan* p, const hm_resample_args* r, const hm_resample_batch* b, const float scale[4], const float bias[4],
+                                        hipStream_t s)
+{
+  if (r->ow <= 0 || r->oh <= 0 || r->n_w <= 0 || r->n_h <= 0 || b->frames <= 0) return HM_OK;
+  if ((r->tmp_pitch % 16) || (r->tmp_plane % 4) || (b->frame_stride % 4) || ((uintptr_t)r->tmp % 16)) return hm_fail(HM_ERR_INTERNAL, "k_resample: misaligned intermediate");
+  const bool chw = p->layout == HM_DEV_LAYOUT_CHW;
+  if ((int64_t)b->frames * (chw ? p->channels : 1) > 65535) return hm_fail(HM_ERR_INTERNAL, "k_resample: %d frames in one launch", b->frames);
+  if (r->sample_bytes == 1) { if (r->channels == 3) launch_h_batch<1, 3>(chw, r, b, s); else launch_h_batch<1, 4>(chw, r, b, s); }
+  else { if (r->channels == 3) launch_h_batch<2, 3>(chw, r, b, s); else launch_h_batch<2, 4>(chw, r, b, s); }
+  int rc = hm_check_hip(hipGetLastError(), "k_resample_h_batch launch");
+  if (rc) return rc;
+  const Affine a = affine_of(scale, bias);
+  switch (p->dtype) {
+    case HM_DEV_U8: launch_v_batch<uint8_t>(p, r, b, a, s); break;
+    case HM_DEV_U16: launch_v_batch<uint16_t>(p, r, b, a, s); break;
+    case HM_DEV_F16: launch_v_batch<__half>(p, r, b, a, s); break;
+    case HM_DEV_F32: launch_v_batch<float>(p, r, b, a, s); break;
+    default: return hm_fail(HM_ERR_INTERNAL, "k_resample_v: no kernel for dtype %d", p->dtype);
+  }
+  return hm_check_hip(hipGetLastError(), "k_resample_v_batch launch");
 }
 
 extern "C" int hm_launch_view_nearest(const hm_dest_plan* p, const void* src, int src_stride, int n_w, int n_h, int ow, int oh, void* dst, const float scale[4],

@@ -2,6 +2,7 @@
 
     img = decode_to_tensor(open("a.heic", "rb").read())                           # 3 x H x W float32
     batch = decode_batch_to_tensor(files, dtype=torch.float16, scale=1 / 255)     # N x 3 x H x W
+    clip = decode_sequence_to_tensor(movie, frames=range(1, 65, 4), size=(224, 224))   # 16 x 3 x 224 x 224
 
 Layouts: "chw" (one plane per channel) and "hwc" (the target's own interleaving).  dtypes: torch.uint8 / torch.uint16 (must be
 the target's own sample type: 8-bit "rgb" / "rgba", 16-bit "rrggbb_le" / "rrggbbaa_le" ...), torch.float16, torch.float32;
@@ -258,3 +259,93 @@ def decode_batch_to_tensor(files, item_id=0, out_format="rgb", layout="chw", dty
         finally:
             L.hm_pipeline_destroy(pipe)
     return out
+
+
+def _frame_ids(frames, n_frames):
+    """the 1-based frame IDs `frames` asks for (None: all, a range, or a list) of a sequence of n_frames"""
+    if frames is None:
+        ids = list(range(1, n_frames + 1))
+    else:
+        ids = []
+        for k, v in enumerate(frames):
+            if isinstance(v, bool) or not hasattr(v, "__index__"):
+                raise ValueError(f"frames[{k}] = {v!r}: 1-based frame IDs (integers) are needed")
+            v = v.__index__()
+            if not 1 <= v <= n_frames:
+                raise ValueError(f"frames[{k}] = {v}: the sequence has frames 1..{n_frames}")
+            ids.append(v)
+    if not ids:
+        raise ValueError("frames: empty")
+    return ids
+
+
+def decode_sequence_to_tensor(data, frames=None, out_format="rgb", layout="chw", dtype=None, scale=None, bias=None, out=None, stream=None,
+                              host_threads=None, crop=None, size=None, filter="triangle"):
+    """Decode frames of an image sequence (bytes of a file with a 'moov' track) into one CUDA tensor, T x C x H x W ("chw") or
+    T x H x W x C ("hwc"), in ONE device batch (hm_decode_frames_to_device_view).  frames: None (all), a range or a list of 1-based
+    frame IDs, in any order, repeats allowed - range(1, n + 1, 4) is every fourth frame.  crop / size / filter: the same rectangle
+    of every frame, resampled, as in decode_to_tensor; without them every frame must have the size of the first.  out: a CUDA
+    tensor of that shape; the row and plane strides of each of its slices are honoured.  Returns when the pixels are in place."""
+    import torch
+    L = capi.image_lib()
+    fmt, lay = _out_format(out_format), _layout(layout)
+    if dtype is None:
+        dtype = out.dtype if out is not None else torch.float32
+    code, c = _dtype_code(dtype), _channels(fmt)
+    sc, bi = _per_channel(scale, 1.0), _per_channel(bias, 0.0)
+    f = _File(data)
+    try:
+        info = capi.SequenceInfo()
+        capi.check_image(L.hm_file_sequence_info(f.h, C.byref(info)))
+        if not info.is_sequence:
+            raise capi.HmError(-1, "the file is not an image sequence")
+        ids = _frame_ids(frames, info.frame_count)
+        view, w, h = None, None, None
+        for k, fid in enumerate(ids):
+            _, fw, fh = f.size(fid)
+            v, vw, vh = _view_of(crop, size, filter, fw, fh)
+            if view is None:
+                view, w, h = v, vw, vh
+            if (vw, vh) != (w, h):
+                raise ValueError(f"frames[{k}] (frame {fid}) is {vw} x {vh}, the first is {w} x {h}: give a size")
+        shape = (len(ids),) + _shape(lay, c, h, w)
+        if out is None:
+            out = torch.empty(shape, dtype=dtype, device="cuda")
+        else:
+            if tuple(out.shape) != shape:
+                raise ValueError(f"out: shape {tuple(out.shape)} does not match the frames' {shape}")
+            if not out.is_cuda or out.dtype != dtype:
+                raise ValueError(f"out: a CUDA tensor of dtype {dtype} is needed, got {out.dtype} on {out.device}")
+        n = len(ids)
+        dests = (capi.DeviceDest * n)(*[_dest_of(out[k], lay, code, c, sc, bi) for k in range(n)])
+        if stream is None:
+            stream = torch.cuda.current_stream(out.device)
+        handle = stream.cuda_stream if hasattr(stream, "cuda_stream") else int(stream)
+        prm = capi.DecodeParams(fmt, host_threads or _default_threads(), 0, 0, handle or None, None, 0, 0, 0, 0)
+        res = (capi.Decoded * n)()
+        failed = C.c_int32(-1)
+        with torch.cuda.device(out.device):
+            rc = L.hm_decode_frames_to_device_view(f.h, (C.c_uint32 * n)(*ids), n, C.byref(prm), C.byref(view) if view is not None else None, dests, res,
+                                                   C.byref(failed))
+        if rc < 0:
+            detail = f"{L.hm_status_string(rc).decode()}: {L.hm_last_error().decode()}"
+            k = failed.value
+            if k >= 0 and view is None and "device destination:" in detail:
+                # a slice shaped for the size the track declares does not hold this frame's picture: find its own size (one host
+                # decode, on this path only) and name it
+                one = capi.Decoded()
+                if L.hm_decode_item(f.h, ids[k], C.byref(prm), C.byref(one)) == 0:
+                    fw, fh = one.width, one.height
+                    L.hm_decoded_free(C.byref(one))
+                    if (fw, fh) != (w, h):
+                        raise ValueError(f"frames[{k}] (frame {ids[k]}) is {fw} x {fh}, the track declares {w} x {h}: give a size")
+            raise capi.HmError(rc, f"frames[{k}] (frame {ids[k]}): {detail}" if k >= 0 else detail)
+        sizes = [(res[k].width, res[k].height) for k in range(n)]
+        for k in range(n):
+            L.hm_decoded_free(C.byref(res[k]))
+        for k in range(n):  # (a track declares one size for all its samples; a smaller picture was written into the corner of its slice)
+            if sizes[k] != (w, h):
+                raise ValueError(f"frames[{k}] (frame {ids[k]}) is {sizes[k][0]} x {sizes[k][1]}, the track declares {w} x {h}: give a size")
+        return out
+    finally:
+        f.close()

@@ -554,6 +554,19 @@ HM_API int hm_decode_item_to_device_view(const hm_file* f, uint32_t id, const hm
 /* the pipeline form: images of different sizes into the slices of one N x C x H x W allocation */
 HM_API int hm_pipeline_submit_to_device_view(hm_pipeline* p, const uint8_t* heif, size_t size, uint32_t item_id, uint64_t tag,
                                              const hm_device_view* view, const hm_device_dest* dest);
+/* The sequence form: frames[0 .. count) are 1-based frame IDs of a sequence, in any order, repeats allowed (every k-th frame of
+ * a track: a temporal stride).  All of them are decoded in ONE device batch, as by hm_decode_sequence_to_device, and the ONE view
+ * is taken of every frame - resolved against that frame's own decoded size - into dests[k], which is sized for out_w x out_h (the
+ * crop's size when out_w == out_h == 0); out[k].width / height: the size written.  Frames that agree in crop, output size and in
+ * their destination's layout, dtype, pitches, scale, bias and 16-byte alignment (the frames of a clip into the slices of one
+ * T x C x H x W allocation do) share their two tap tables and one kernel launch per resampling pass; the bytes are those of `count`
+ * calls of hm_decode_item_to_device_view.  view == NULL: hm_decode_sequence_to_device on those frames.
+ * Refused before anything is queued, every destination unwritten: what hm_decode_sequence_to_device and
+ * hm_decode_item_to_device_view refuse (HM_ERR_UNSUPPORTED for out_format 0 and the planar HM_OUT_YCBCR_* targets), a frame ID
+ * outside 1 .. frame_count, a file that is not a sequence.  *failed_frame (may be NULL) = the index k into frames[] when the
+ * failure is one frame's - its data, its destination, a view that does not fit that frame's size -, -1 otherwise. */
+HM_API int hm_decode_frames_to_device_view(const hm_file* f, const uint32_t* frames, int32_t count, const hm_decode_params* params,
+                                           const hm_device_view* view, const hm_device_dest* dests, hm_decoded* out, int32_t* failed_frame);
 /* The step on its own, on interleaved pixels that are on the device already (as hm_to_tensor).  Asynchronous on `stream`. */
 HM_API int hm_resample_to_tensor(int out_format, int src_w, int src_h, const void* d_src, int src_stride, const hm_device_view* view,
                                  const hm_device_dest* dest, void* stream);
