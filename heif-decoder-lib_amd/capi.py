@@ -23,6 +23,8 @@ HM_PLANAR_UNFUSED = 1
 # device-resident output (hm_device_dest)
 HM_DEV_LAYOUT_HWC, HM_DEV_LAYOUT_CHW = 0, 1
 HM_DEV_U8, HM_DEV_U16, HM_DEV_F16, HM_DEV_F32 = 0, 1, 2, 3
+# device-resident planar YCbCr (hm_device_planes)
+HM_DEV_PLANES_SEPARATE, HM_DEV_PLANES_SEMI = 0, 1
 # views (hm_device_view): a rectangle of the image at a size of the caller's choice
 HM_VIEW_TRIANGLE, HM_VIEW_NEAREST = 0, 1
 HM_VIEW_CUBIC, HM_VIEW_LANCZOS3 = 16, 17
@@ -144,6 +146,17 @@ class DeviceDest(C.Structure):
                 ("row_pitch", C.c_int64), ("plane_pitch", C.c_int64), ("scale", C.c_float * 4), ("bias", C.c_float * 4)]
 
 
+class DevicePlane(C.Structure):
+    """hm_device_plane: one plane of an hm_device_planes"""
+    _fields_ = [("ptr", C.c_void_p), ("len", C.c_uint64), ("row_pitch", C.c_int64)]
+
+
+class DevicePlanes(C.Structure):
+    """hm_device_planes: caller-owned device memory the planes of a planar YCbCr decode go to (Y, Cb | CbCr, Cr, alpha)"""
+    _fields_ = [("plane", DevicePlane * 4), ("layout", C.c_int32), ("dtype", C.c_int32), ("msb_aligned", C.c_int32), ("reserved", C.c_int32),
+                ("scale", C.c_float * 4), ("bias", C.c_float * 4)]
+
+
 class DeviceView(C.Structure):
     """hm_device_view: crop rectangle (0, 0, 0, 0 = the whole image), output size (0, 0 = the crop's own), filter"""
     _fields_ = [(n, C.c_int32) for n in "crop_x crop_y crop_w crop_h out_w out_h filter".split()]
@@ -219,6 +232,14 @@ def bind_image(L):
     L.hm_resample_to_tensor.argtypes = [C.c_int, C.c_int, C.c_int, C.c_void_p, C.c_int, C.POINTER(DeviceView), C.POINTER(DeviceDest), C.c_void_p]
     L.hm_plan_view.argtypes = [C.c_void_p, C.c_uint32, C.POINTER(DecodeParams), C.POINTER(DeviceView), C.POINTER(C.c_int32 * 4)]
     L.hm_view_filter_taps.argtypes = [C.c_int, C.c_int, C.c_int, C.c_int, C.POINTER(C.c_int32), C.POINTER(C.c_float), C.c_int]
+    L.hm_device_planes_bytes.argtypes = [C.c_int, C.c_int, C.c_int, C.c_int, C.POINTER(DevicePlanes), C.POINTER(C.c_int64 * 4)]
+    L.hm_device_planes_bytes.restype = C.c_int64
+    L.hm_planes_to_tensor.argtypes = [C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, C.POINTER(C.c_void_p * 4), C.POINTER(C.c_int32 * 4), C.POINTER(DevicePlanes),
+                                      C.c_void_p]
+    L.hm_decode_item_to_device_planes.argtypes = [C.c_void_p, C.c_uint32, C.POINTER(DecodeParams), C.POINTER(DevicePlanes), C.POINTER(Decoded)]
+    L.hm_decode_frames_to_device_planes.argtypes = [C.c_void_p, C.POINTER(C.c_uint32), C.c_int32, C.POINTER(DecodeParams), C.POINTER(DevicePlanes),
+                                                    C.POINTER(Decoded), C.POINTER(C.c_int32)]
+    L.hm_pipeline_submit_to_device_planes.argtypes = [C.c_void_p, C.c_char_p, C.c_size_t, C.c_uint32, C.c_uint64, C.POINTER(DevicePlanes)]
     L.hm_pipeline_pending.argtypes = [C.c_void_p]
     L.hm_pipeline_next.argtypes = [C.c_void_p, C.POINTER(PipelineResult)]
     L.hm_pipeline_release.argtypes = [C.c_void_p, C.POINTER(PipelineResult)]

@@ -1,8 +1,10 @@
 // devdest.cpp — device-resident output: the arithmetic and the refusals of hm_device_dest, and the step that writes the colour
 // stage's interleaved pixels into it (a 2-D device copy for HWC with the target's own integer type, k_to_tensor otherwise).
+// Planar YCbCr (hm_device_planes): the arithmetic and the refusals, and the step that writes the decoded planes (kernel: planes.hip).
 // Views (hm_device_view): the refusals, the tap tables and the step that writes a resampled rectangle (kernels: resample.hip).
 #include <algorithm>
 #include <cmath>
+#include <cstdio>
 #include <cstring>
 #include <mutex>
 #include <new>
@@ -72,21 +74,24 @@ int hm_dest_check_len(const hm_device_dest* d, const hm_dest_plan* p)
   return HM_OK;
 }
 
-int hm_dest_check_pointer(const hm_device_dest* d)
+// `ptr` is device memory of the current device; what: "device destination: ptr", "device planes: plane[1].ptr"
+static int check_device_pointer(const void* ptr, const char* what)
 {
   int cur = 0;
   if (hipGetDevice(&cur) != hipSuccess) return hm_fail(HM_ERR_NO_DEVICE, "no current HIP device");
   hipPointerAttribute_t at;
   std::memset(&at, 0, sizeof(at));
-  const hipError_t e = hipPointerGetAttributes(&at, d->ptr);
+  const hipError_t e = hipPointerGetAttributes(&at, ptr);
   if (e != hipSuccess) {
     (void)hipGetLastError(); // (an unknown pointer is an answer, not a sticky error)
-    return hm_fail(HM_ERR_INVALID_ARG, "device destination: ptr is not memory the HIP runtime knows (host memory?)");
+    return hm_fail(HM_ERR_INVALID_ARG, "%s is not memory the HIP runtime knows (host memory?)", what);
   }
-  if (at.type != hipMemoryTypeDevice) return hm_fail(HM_ERR_INVALID_ARG, "device destination: ptr is not device memory (memory type %d)", (int)at.type);
-  if (at.device != cur) return hm_fail(HM_ERR_INVALID_ARG, "device destination: ptr belongs to device %d, the decode runs on device %d", at.device, cur);
+  if (at.type != hipMemoryTypeDevice) return hm_fail(HM_ERR_INVALID_ARG, "%s is not device memory (memory type %d)", what, (int)at.type);
+  if (at.device != cur) return hm_fail(HM_ERR_INVALID_ARG, "%s belongs to device %d, the decode runs on device %d", what, at.device, cur);
   return HM_OK;
 }
+
+int hm_dest_check_pointer(const hm_device_dest* d) { return check_device_pointer(d->ptr, "device destination: ptr"); }
 
 int64_t hm_device_dest_bytes(int out_format, int width, int height, const hm_device_dest* d)
 {
@@ -126,6 +131,169 @@ int hm_dest_write(const hm_device_dest* d, int out_format, int w, int h, int y0,
     return hm_check_hip(e, "copy to the device destination");
   }
   return hm_launch_to_tensor(&p, src, src_stride, w, rows, dst, d->scale, d->bias, s);
+}
+
+// ---- planar YCbCr (hm_device_planes) --------------------------------------------------------------------------------------------
+
+static int planes_elem(int dtype) { return dtype == HM_DEV_U8 ? 1 : dtype == HM_DEV_F32 ? 4 : 2; }
+
+int hm_planes_check_static(const hm_device_planes* d)
+{
+  if (!d) return hm_fail(HM_ERR_INVALID_ARG, "null device planes");
+  if (d->layout != HM_DEV_PLANES_SEPARATE && d->layout != HM_DEV_PLANES_SEMI) return hm_fail(HM_ERR_INVALID_ARG, "device planes: unknown layout %d", d->layout);
+  if (d->dtype < HM_DEV_U8 || d->dtype > HM_DEV_F32) return hm_fail(HM_ERR_INVALID_ARG, "device planes: unknown dtype %d", d->dtype);
+  if (d->reserved) return hm_fail(HM_ERR_INVALID_ARG, "device planes: reserved is %d, not 0", d->reserved);
+  if (d->msb_aligned != 0 && d->msb_aligned != 1) return hm_fail(HM_ERR_INVALID_ARG, "device planes: msb_aligned is %d, not 0 or 1", d->msb_aligned);
+  if (d->msb_aligned && d->dtype != HM_DEV_U16) return hm_fail(HM_ERR_INVALID_ARG, "device planes: msb_aligned with dtype %d (HM_DEV_U16 only)", d->dtype);
+  if (d->layout == HM_DEV_PLANES_SEMI && (d->plane[2].ptr || d->plane[2].len || d->plane[2].row_pitch))
+    return hm_fail(HM_ERR_INVALID_ARG, "device planes: plane[2] must be all zero with HM_DEV_PLANES_SEMI (Cb and Cr share plane[1])");
+  const int elem = planes_elem(d->dtype);
+  for (int c = 0; c < 4; c++) {
+    const hm_device_plane& pl = d->plane[c];
+    if (pl.row_pitch < 0) return hm_fail(HM_ERR_INVALID_ARG, "device planes: plane[%d].row_pitch is negative", c);
+    if ((uintptr_t)pl.ptr % (unsigned)elem) return hm_fail(HM_ERR_INVALID_ARG, "device planes: plane[%d].ptr is not a multiple of the element size %d", c, elem);
+    if (pl.row_pitch % elem) return hm_fail(HM_ERR_INVALID_ARG, "device planes: plane[%d].row_pitch %lld is not a multiple of the element size %d", c, (long long)pl.row_pitch, elem);
+  }
+  return HM_OK;
+}
+
+int hm_planes_resolve(int chroma, int bits, int w, int h, int alpha_bits, const hm_device_planes* d, hm_planes_plan* p)
+{
+  const int rc = hm_planes_check_static(d);
+  if (rc) return rc;
+  if (chroma < HM_CHROMA_MONO || chroma > HM_CHROMA_444) return hm_fail(HM_ERR_INVALID_ARG, "device planes: chroma format %d", chroma);
+  if (bits < 8 || bits > 16) return hm_fail(HM_ERR_INVALID_ARG, "device planes: bit depth %d", bits);
+  if (alpha_bits > 0 && (alpha_bits < 8 || alpha_bits > 16)) return hm_fail(HM_ERR_INVALID_ARG, "device planes: alpha bit depth %d", alpha_bits);
+  if (w <= 0 || h <= 0 || w > 32768 || h > 32768) return hm_fail(HM_ERR_INVALID_ARG, "device planes: image size %d x %d", w, h);
+  std::memset(p, 0, sizeof(*p));
+  p->layout = d->layout; p->dtype = d->dtype; p->elem = planes_elem(d->dtype);
+  p->chroma = chroma; p->bits = bits;
+  if (d->dtype == HM_DEV_U8 && bits != 8) return hm_fail(HM_ERR_INVALID_ARG, "device planes: dtype HM_DEV_U8 does not hold the %d-bit samples of the result", bits);
+  if (d->dtype == HM_DEV_U16 && bits == 8) return hm_fail(HM_ERR_INVALID_ARG, "device planes: dtype HM_DEV_U16 with the 8-bit samples of the result (HM_DEV_U8 holds them)");
+  p->shift = d->msb_aligned ? 16 - bits : 0;
+  const bool semi = d->layout == HM_DEV_PLANES_SEMI;
+  if (chroma == HM_CHROMA_MONO)
+    for (int c = 1; c <= 2; c++)
+      if (d->plane[c].ptr || d->plane[c].len || d->plane[c].row_pitch) return hm_fail(HM_ERR_INVALID_ARG, "device planes: plane[%d] must be all zero for a 4:0:0 result (Y only)", c);
+  const bool want_alpha = d->plane[3].ptr != nullptr;
+  if (want_alpha && alpha_bits == 0) return hm_fail(HM_ERR_INVALID_ARG, "device planes: plane[3] is given, but the image has no alpha plane");
+  if (want_alpha && alpha_bits > 0 && (d->dtype == HM_DEV_U8 || d->dtype == HM_DEV_U16) && (alpha_bits > 8) != (d->dtype == HM_DEV_U16))
+    return hm_fail(HM_ERR_UNSUPPORTED, "device planes: alpha plane of %d bits with integer dtype %d", alpha_bits, d->dtype);
+  p->alpha_bits = want_alpha && alpha_bits > 0 ? alpha_bits : 0;
+  const int cw = chroma == HM_CHROMA_444 ? w : (w + 1) / 2, ch = chroma == HM_CHROMA_420 ? (h + 1) / 2 : h;
+  for (int c = 0; c < 4; c++) {
+    auto& pl = p->pl[c];
+    // (the alpha plane is sized whether it is written or not: hm_device_planes_bytes reports it)
+    pl.present = c == 0 || (c == 3 ? want_alpha : chroma != HM_CHROMA_MONO && !(semi && c == 2));
+    if (c != 3 && !pl.present) continue;
+    pl.width = c == 0 || c == 3 ? w : cw;
+    pl.height = c == 0 || c == 3 ? h : ch;
+    pl.elems = semi && c == 1 ? 2 * pl.width : pl.width;
+    pl.tight = (int64_t)pl.elems * p->elem;
+    pl.pitch = d->plane[c].row_pitch ? d->plane[c].row_pitch : pl.tight;
+    if (pl.pitch < pl.tight) return hm_fail(HM_ERR_INVALID_ARG, "device planes: plane[%d].row_pitch %lld below the %lld bytes of a row", c, (long long)pl.pitch, (long long)pl.tight);
+    if (pl.pitch > ((int64_t)1 << 40)) return hm_fail(HM_ERR_INVALID_ARG, "device planes: plane[%d].row_pitch %lld", c, (long long)pl.pitch);
+    pl.bytes = pl.pitch * (pl.height - 1) + pl.tight;
+    pl.vec = ((uintptr_t)d->plane[c].ptr % 16) == 0 && (pl.pitch % 16) == 0;
+    if (pl.present) p->bytes += pl.bytes;
+  }
+  return HM_OK;
+}
+
+int hm_planes_check_len(const hm_device_planes* d, const hm_planes_plan* p)
+{
+  for (int c = 0; c < 4; c++) {
+    if (!p->pl[c].present) continue;
+    if (!d->plane[c].ptr) return hm_fail(HM_ERR_INVALID_ARG, "device planes: plane[%d].ptr is null", c);
+    if (d->plane[c].len < (uint64_t)p->pl[c].bytes)
+      return hm_fail(HM_ERR_INVALID_ARG, "device planes: plane[%d].len %llu below the %lld bytes the plane needs", c, (unsigned long long)d->plane[c].len, (long long)p->pl[c].bytes);
+  }
+  for (int a = 0; a < 4; a++)
+    for (int b = a + 1; b < 4; b++) {
+      if (!p->pl[a].present || !p->pl[b].present) continue;
+      const uintptr_t a0 = (uintptr_t)d->plane[a].ptr, b0 = (uintptr_t)d->plane[b].ptr;
+      if (a0 < b0 + (uint64_t)p->pl[b].bytes && b0 < a0 + (uint64_t)p->pl[a].bytes)
+        return hm_fail(HM_ERR_INVALID_ARG, "device planes: the bytes of plane[%d] and plane[%d] overlap", a, b);
+    }
+  return HM_OK;
+}
+
+int hm_planes_check_pointer(const hm_device_planes* d, const hm_planes_plan* p)
+{
+  for (int c = 0; c < 4; c++) {
+    if (!p->pl[c].present) continue;
+    char what[48];
+    std::snprintf(what, sizeof(what), "device planes: plane[%d].ptr", c);
+    const int rc = check_device_pointer(d->plane[c].ptr, what);
+    if (rc) return rc;
+  }
+  return HM_OK;
+}
+
+int64_t hm_device_planes_bytes(int chroma, int bits, int width, int height, const hm_device_planes* d, int64_t need[4])
+{
+  if (!d) return hm_fail(HM_ERR_INVALID_ARG, "null argument");
+  hm_planes_plan p;
+  const int rc = hm_planes_resolve(chroma, bits, width, height, -1, d, &p);
+  if (rc) return rc;
+  for (int c = 0; c < 4 && need; c++) need[c] = p.pl[c].bytes;
+  return p.bytes;
+}
+
+int hm_planes_write(const hm_device_planes* d, int chroma, int bits, int w, int h, int alpha_bits, const void* const src[4], const int32_t stride[4],
+                    hipStream_t s, int64_t pitches[4])
+{
+  hm_planes_plan p;
+  int rc = hm_planes_resolve(chroma, bits, w, h, alpha_bits, d, &p);
+  if (!rc) rc = hm_planes_check_len(d, &p);
+  if (!rc) rc = hm_planes_check_pointer(d, &p); // (an entry point may not have known the result's format: the launch relies on none of them)
+  if (rc) return rc;
+  const bool semi = p.layout == HM_DEV_PLANES_SEMI;
+  hm_planes_args a;
+  std::memset(&a, 0, sizeof(a));
+  int y_end = 0;
+  for (int c = 0; c < 4; c++) {
+    if (pitches) pitches[c] = p.pl[c].present ? p.pl[c].pitch : 0;
+    if (p.pl[c].present) {
+      hm_plane_desc& pd = a.pl[c];
+      const int sbits = c == 3 ? p.alpha_bits : bits, sb = sbits > 8 ? 2 : 1;
+      const bool pair = semi && c == 1;
+      for (int k = c; k <= (pair ? 2 : c); k++) {
+        if (!src[k]) return hm_fail(HM_ERR_INVALID_ARG, "device planes: source plane %d is null", k);
+        if (stride[k] < p.pl[c].width * sb) return hm_fail(HM_ERR_INVALID_ARG, "device planes: source stride %d of plane %d below the bytes of a row", stride[k], k);
+        if (sb == 2 && (((uintptr_t)src[k] | (unsigned)stride[k]) & 1)) return hm_fail(HM_ERR_INVALID_ARG, "16-bit samples at an odd address or stride");
+      }
+      pd.src0 = (const uint8_t*)src[c]; pd.stride0 = stride[c];
+      pd.scale0 = d->scale[c]; pd.bias0 = d->bias[c];
+      bool vec = p.pl[c].vec && ((uintptr_t)src[c] % 16) == 0 && (stride[c] % 16) == 0;
+      if (pair) {
+        pd.src1 = (const uint8_t*)src[2]; pd.stride1 = stride[2];
+        pd.scale1 = d->scale[2]; pd.bias1 = d->bias[2];
+        vec = vec && ((uintptr_t)src[2] % 16) == 0 && (stride[2] % 16) == 0;
+      }
+      pd.dst = (uint8_t*)d->plane[c].ptr; pd.pitch = p.pl[c].pitch;
+      pd.w = p.pl[c].width; pd.h = p.pl[c].height;
+      pd.sample_bytes = sb; pd.pair = pair ? 1 : 0; pd.vec = vec ? 1 : 0;
+      pd.shift = d->msb_aligned ? 16 - sbits : 0;
+      y_end += (pd.h + 3) / 4;
+    }
+    a.y_end[c] = y_end;
+  }
+  return hm_launch_planes_to_tensor(&a, p.dtype, s);
+}
+
+int hm_planes_to_tensor(int chroma, int bits, int width, int height, int alpha_bits, const void* const d_src[4], const int32_t src_stride[4],
+                        const hm_device_planes* planes, void* stream)
+{
+  if (!d_src || !src_stride || !planes) return hm_fail(HM_ERR_INVALID_ARG, "null argument");
+  if (alpha_bits < 0) return hm_fail(HM_ERR_INVALID_ARG, "device planes: alpha bit depth %d", alpha_bits);
+  hm_planes_plan p;
+  int rc = hm_planes_resolve(chroma, bits, width, height, alpha_bits, planes, &p);
+  if (!rc) rc = hm_planes_check_len(planes, &p);
+  if (rc) return rc;
+  int n_dev = 0;
+  if (hipGetDeviceCount(&n_dev) != hipSuccess || n_dev == 0) { (void)hipGetLastError(); return hm_fail(HM_ERR_NO_DEVICE, "no HIP device available"); }
+  return hm_planes_write(planes, chroma, bits, width, height, alpha_bits, d_src, src_stride, (hipStream_t)stream, nullptr);
 }
 
 // ---- views ----------------------------------------------------------------------------------------------------------------------

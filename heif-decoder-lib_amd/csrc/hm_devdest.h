@@ -32,6 +32,53 @@ int hm_dest_write(const hm_device_dest* d, int out_format, int w, int h, int y0,
 int hm_launch_to_tensor(const hm_dest_plan* p, const void* src, int src_stride, int w, int rows, void* dst, const float scale[4], const float bias[4],
                         hipStream_t s);
 
+// ---- planar YCbCr (hm_device_planes): the decoded planes themselves, one destination per plane.  devdest.cpp holds the checks,
+//      planes.hip the kernel ----
+typedef struct hm_planes_plan {
+  int32_t layout, dtype, elem;
+  int32_t chroma, bits, alpha_bits; // of the result; alpha_bits 0: no alpha plane is written
+  int32_t shift;                    // msb_aligned: 16 - bits (the alpha plane: 16 - alpha_bits), else 0
+  struct {
+    int32_t present;                // written: Y always, Cb / Cr (SEMI: CbCr in [1]) unless 4:0:0, alpha when it exists and plane[3].ptr is given
+    int32_t width, height;          // samples of the source plane(s)
+    int32_t elems;                  // elements of a destination row: width, the interleaved plane 2 * width
+    int32_t vec;                    // ptr and pitch take 16-byte stores
+    int64_t pitch, tight, bytes;    // bytes: the pitch in use, of a row's elements, pitch * (height - 1) + tight
+  } pl[4];
+  int64_t bytes;                    // the sum over the planes that are present
+} hm_planes_plan;
+// what depends on nothing but the destination: layout, dtype, reserved, msb_aligned, alignment of the pointers and pitches
+int hm_planes_check_static(const hm_device_planes* d);
+// ... and what depends on the result's format: chroma (HM_CHROMA_*), bits, luma size, alpha_bits (0: the image has no alpha plane,
+// < 0: not known yet - the plane is sized when plane[3].ptr is given, its depth class is not judged).  d->plane[].len is NOT compared.
+int hm_planes_resolve(int chroma, int bits, int w, int h, int alpha_bits, const hm_device_planes* d, hm_planes_plan* p);
+// null pointers, len against the plan, and planes whose byte ranges overlap
+int hm_planes_check_len(const hm_device_planes* d, const hm_planes_plan* p);
+// every plane that is written is device memory of the current device
+int hm_planes_check_pointer(const hm_device_planes* d, const hm_planes_plan* p);
+// the planes src[0 .. 2] (Y, Cb, Cr) and src[3] (alpha, with alpha_bits > 0) of a w x h image, strides in bytes, samples of 1 byte (8 bits) or
+// 2, into the destination: ONE launch of k_planes_to_tensor, asynchronous on `s`.  Everything - resolve, len and overlap, the pointers -
+// is checked again before the launch.
+// pitches (may be NULL): the pitches in use.
+int hm_planes_write(const hm_device_planes* d, int chroma, int bits, int w, int h, int alpha_bits, const void* const src[4], const int32_t stride[4],
+                    hipStream_t s, int64_t pitches[4]);
+
+// one plane of a launch; pair: the interleaved CbCr plane (src0 = Cb, src1 = Cr, scale0 / bias0 and scale1 / bias1 theirs)
+typedef struct hm_plane_desc {
+  const uint8_t* src0; const uint8_t* src1;
+  uint8_t* dst;
+  long long pitch;
+  int32_t stride0, stride1;
+  int32_t w, h;            // samples of a source row, rows (0: the plane is absent)
+  int32_t sample_bytes, pair, vec, shift;
+  float scale0, bias0, scale1, bias1;
+} hm_plane_desc;
+typedef struct hm_planes_args {
+  hm_plane_desc pl[4];
+  int32_t y_end[4];        // blockIdx.y below y_end[p] (and not below y_end[p - 1]) works on plane p: running sums of (h + 3) / 4
+} hm_planes_args;
+int hm_launch_planes_to_tensor(const hm_planes_args* a, int dtype, hipStream_t s);
+
 // ---- views (hm_device_view): a rectangle of the image at a size of the caller's choice.  devdest.cpp holds the checks and the tap
 //      tables, resample.hip the kernels ----
 typedef struct hm_view_plan {

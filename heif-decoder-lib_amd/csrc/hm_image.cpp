@@ -754,9 +754,11 @@ void parse_picture(const hm_file* f, uint32_t id, bool few_pictures, int strict,
 // planes - all queued on `s`.  `dout` and `alpha_sdr` must live until the stream has drained.
 // dest (may be NULL): caller-owned device memory the interleaved pixels go to instead (hm_device_dest); nothing is copied to the host then.
 // view_later (may be NULL, with view): the view is not written here, only described there - the caller writes it with those of other images.
+// planes (may be NULL; a planar result only): caller-owned device memory the planes go to instead (hm_device_planes), one launch of
+// k_planes_to_tensor in place of the pinned allocations and the copies to the host.
 int emit_image(const hm_decode_params* params, hipStream_t s, PlanarImage& I, const DevPlane* alpha, int alpha_bd, DevMem& dout,
                DevPlane& alpha_sdr, hm_decoded* out, const hm_device_dest* dest = nullptr, const hm_device_view* view = nullptr,
-               hm_view_scratch* view_scratch = nullptr, hm_view_item* view_later = nullptr)
+               hm_view_scratch* view_scratch = nullptr, hm_view_item* view_later = nullptr, const hm_device_planes* planes = nullptr)
 {
   int rc;
   DevPlane (&P)[3] = I.P;
@@ -782,19 +784,36 @@ int emit_image(const hm_decode_params* params, hipStream_t s, PlanarImage& I, co
     if (view && (rc = hm_view_resolve(params->out_format, img_w, img_h, view, &vp))) return rc;
     if ((rc = hm_dest_resolve(params->out_format, vp.ow, vp.oh, dest, &dp)) || (rc = hm_dest_check_len(dest, &dp))) return rc;
   }
+  if (planes && !as_decoded && !planar_target) return hm_fail(HM_ERR_INTERNAL, "device planes with the interleaved output format %d", params->out_format);
+  // the planes of a planar result into the caller's device memory (checked against the result's own format before the launch)
+  auto write_planes = [&](int rchroma, int rbits, const void* const src[4], const int32_t stride[4], int abits) {
+    int64_t pitch[4];
+    const int wrc = hm_planes_write(planes, rchroma, rbits, img_w, img_h, abits, src, stride, s, pitch);
+    if (wrc) return wrc;
+    out->used_ext_dst = 1;
+    for (int c = 0; c < 3; c++) out->stride[c] = (int32_t)std::min<int64_t>(pitch[c], 0x7FFFFFFF);
+    out->alpha_stride = (int32_t)std::min<int64_t>(pitch[3], 0x7FFFFFFF);
+    return (int)HM_OK;
+  };
   if (as_decoded) { // native planar YCbCr
     out->out_format = params->out_format;
     for (int c = 0; c < 3; c++) {
       if (!P[c].mem.p) continue; // monochrome image: Y only
+      out->plane_width[c] = P[c].w; out->plane_height[c] = P[c].h;
+      if (planes) continue;
       const size_t sz = plane_bytes(P[c]);
       out->plane[c] = (uint8_t*)hm_pool_pinned_alloc(sz);
       if (!out->plane[c]) return hm_fail(HM_ERR_NOMEM, "out of memory");
       out->stride[c] = P[c].stride;
       e = hipMemcpyAsync(out->plane[c], P[c].mem.p, sz, hipMemcpyDeviceToHost, s);
       if (e != hipSuccess) return hm_check_hip(e, "D2H");
-      out->plane_width[c] = P[c].w; out->plane_height[c] = P[c].h;
     }
-    if (alpha) {
+    if (planes) {
+      const void* src[4] = {P[0].mem.p, P[1].mem.p, P[2].mem.p, alpha ? alpha->mem.p : nullptr};
+      const int32_t stride[4] = {P[0].stride, P[1].stride, P[2].stride, alpha ? alpha->stride : 0};
+      if ((rc = write_planes(chroma, bd, src, stride, alpha ? alpha_bd : 0))) return rc;
+    }
+    else if (alpha) {
       const size_t sz = plane_bytes(*alpha);
       out->alpha = (uint8_t*)hm_pool_pinned_alloc(sz);
       if (!out->alpha) return hm_fail(HM_ERR_NOMEM, "out of memory");
@@ -823,15 +842,20 @@ int emit_image(const hm_decode_params* params, hipStream_t s, PlanarImage& I, co
     out->chroma = res.chroma; out->bit_depth = res.bits;
     for (int c = 0; c < 3; c++) { // (planes the chain passed through are copied from where they are: the decoded image's own)
       const int pw = c == 0 || res.chroma == 3 ? img_w : (img_w + 1) / 2, ph = c == 0 || res.chroma != 1 ? img_h : (img_h + 1) / 2;
+      out->plane_width[c] = pw; out->plane_height[c] = ph;
+      if (planes) continue;
       const size_t sz = (size_t)res.stride[c] * mem_rows(ph);
       out->plane[c] = (uint8_t*)hm_pool_pinned_alloc(sz);
       if (!out->plane[c]) return hm_fail(HM_ERR_NOMEM, "out of memory");
       out->stride[c] = res.stride[c];
       e = hipMemcpyAsync(out->plane[c], res.p[c], sz, hipMemcpyDeviceToHost, s);
       if (e != hipSuccess) return hm_check_hip(e, "D2H");
-      out->plane_width[c] = pw; out->plane_height[c] = ph;
     }
-    if (res.p[3]) {
+    if (planes) {
+      const int32_t stride[4] = {res.stride[0], res.stride[1], res.stride[2], res.stride[3]};
+      if ((rc = write_planes(res.chroma, res.bits, res.p, stride, res.p[3] ? (res.alpha_bits ? res.alpha_bits : res.bits) : 0))) return rc;
+    }
+    else if (res.p[3]) {
       const size_t sz = (size_t)res.stride[3] * mem_rows(img_h);
       out->alpha = (uint8_t*)hm_pool_pinned_alloc(sz);
       if (!out->alpha) return hm_fail(HM_ERR_NOMEM, "out of memory");
@@ -971,7 +995,8 @@ int job_enqueue(DecodeJob& j, hm_decoded* out)
   lap("planar decode queued");
   hm_device_view shifted = j.view; // (the crop inside the sub-grid that was decoded)
   if (j.has_view && (shifted.crop_w || shifted.crop_h)) { shifted.crop_x -= j.view_dx; shifted.crop_y -= j.view_dy; }
-  rc = emit_image(params, s, I, alpha, alpha_bd, j.dout, j.alpha_sdr, out, j.has_dest ? &j.dest : nullptr, j.has_view ? &shifted : nullptr, &j.view_scratch);
+  rc = emit_image(params, s, I, alpha, alpha_bd, j.dout, j.alpha_sdr, out, j.has_dest ? &j.dest : nullptr, j.has_view ? &shifted : nullptr, &j.view_scratch, nullptr,
+                  j.has_planes ? &j.planes : nullptr);
   if (rc) return rc;
   lap("colour + D2H queued");
   return HM_OK;
@@ -997,6 +1022,52 @@ int check_device_request(const hm_file* f, uint32_t id, const hm_decode_params* 
   return hm_dest_check_pointer(dest);
 }
 
+int check_planes_params(const hm_decode_params* params, const hm_device_planes* planes)
+{
+  if (params->ext_dst) return hm_fail(HM_ERR_INVALID_ARG, "params->ext_dst must be NULL with device planes");
+  if (params->out_format != 0 && !hm_out_is_planar(params->out_format)) {
+    if (hm_out_bytes_per_pixel(params->out_format) > 0)
+      return hm_fail(HM_ERR_INVALID_ARG, "device planes take planar YCbCr (out_format 0 or HM_OUT_YCBCR_*): interleaved output format %d goes through hm_decode_item_to_device",
+                     params->out_format);
+    return hm_fail(HM_ERR_INVALID_ARG, "device planes: output format %d is not a planar one", params->out_format);
+  }
+  const int rc = hm_planes_check_static(planes);
+  if (rc) return rc;
+  if (!planes->plane[0].ptr) return hm_fail(HM_ERR_INVALID_ARG, "device planes: plane[0].ptr is null");
+  return HM_OK;
+}
+
+// the chroma format and depth of a planar result for a decoded image of (chroma, bd): what emit_image's branches hand out
+static void planar_result_format(const hm_decode_params* params, int chroma, int bd, int* rchroma, int* rbits)
+{
+  const bool as_decoded = params->out_format == 0 || (chroma != 0 && chroma == hm_out_planar_chroma(params->out_format));
+  *rchroma = as_decoded ? chroma : hm_out_planar_chroma(params->out_format);
+  *rbits = !as_decoded && params->convert_hdr_to_8bit ? 8 : bd;
+}
+
+int check_planes_request(const hm_file* f, uint32_t id, const hm_decode_params* params, const hm_device_planes* planes)
+{
+  int rc = check_planes_params(params, planes);
+  if (rc) return rc;
+  hm_image_info info;
+  hm_planes_plan pp;
+  bool planned = false;
+  if (hm_file_image_info(f, id, &info) == HM_OK) { // (a file that fails here fails the decode with its own message)
+    const int w = params->ignore_transformations ? info.coded_width : info.width, h = params->ignore_transformations ? info.coded_height : info.height;
+    if (w > 0 && h > 0 && info.bit_depth >= 8 && info.bit_depth <= 16 && info.chroma >= 0 && info.chroma <= 3) {
+      int rchroma, rbits;
+      planar_result_format(params, info.chroma, info.bit_depth, &rchroma, &rbits);
+      // (whether there is an alpha plane, and of which depth, is the decode's to say: -1)
+      if ((rc = hm_planes_resolve(rchroma, rbits, w, h, -1, planes, &pp)) || (rc = hm_planes_check_len(planes, &pp))) return rc;
+      planned = true;
+    }
+  }
+  int n_dev = 0;
+  if (hipGetDeviceCount(&n_dev) != hipSuccess || n_dev == 0) { (void)hipGetLastError(); return hm_fail(HM_ERR_NO_DEVICE, "no HIP device available"); }
+  if (planned) return hm_planes_check_pointer(planes, &pp);
+  return HM_OK; // (hm_planes_write checks the pointers against the decoded result before its launch)
+}
+
 int job_complete(DecodeJob& j, hm_decoded*)
 {
   const hipError_t e = hipStreamSynchronize(j.s);
@@ -1016,7 +1087,8 @@ extern "C" {
 
 static int decode_grid_cut(const hm_file* f, uint32_t id, const hm_decode_params* params, const int32_t* devices, int n_devices, bool pipelined, hm_decoded* out, bool* applicable,
                            const hm_device_dest* dest = nullptr); // (below, behind the slabs)
-static int decode_item(const hm_file* f, uint32_t id, const hm_decode_params* params, const hm_device_dest* dest, hm_decoded* out, const hm_device_view* view = nullptr);
+static int decode_item(const hm_file* f, uint32_t id, const hm_decode_params* params, const hm_device_dest* dest, hm_decoded* out, const hm_device_view* view = nullptr,
+                       const hm_device_planes* planes = nullptr);
 
 int hm_decode_item(const hm_file* f, uint32_t id, const hm_decode_params* params, hm_decoded* out)
 {
@@ -1042,6 +1114,15 @@ int hm_decode_item_to_device_view(const hm_file* f, uint32_t id, const hm_decode
   return decode_item(f, id, params, dest, out, view);
 }
 
+int hm_decode_item_to_device_planes(const hm_file* f, uint32_t id, const hm_decode_params* params, const hm_device_planes* planes, hm_decoded* out)
+{
+  if (!f || !params || !planes || !out) return hm_fail(HM_ERR_INVALID_ARG, "null argument");
+  std::memset(out, 0, sizeof(*out));
+  const int rc = check_planes_request(f, id, params, planes); // refused before any work is queued: no plane is written
+  if (rc) return rc;
+  return decode_item(f, id, params, nullptr, out, nullptr, planes);
+}
+
 int hm_plan_view(const hm_file* f, uint32_t id, const hm_decode_params* params, const hm_device_view* view, int32_t tiles[4])
 {
   if (!f || !params || !view || !tiles) return hm_fail(HM_ERR_INVALID_ARG, "null argument");
@@ -1053,7 +1134,9 @@ int hm_plan_view(const hm_file* f, uint32_t id, const hm_decode_params* params, 
 
 // dest (may be NULL): the pixels go to caller-owned device memory; view (may be NULL, with dest only): a rectangle of them, resampled -
 // always as one job (its plan is reduced to the tiles the crop touches), never slab by slab
-static int decode_item(const hm_file* f, uint32_t id, const hm_decode_params* params, const hm_device_dest* dest, hm_decoded* out, const hm_device_view* view)
+// planes (may be NULL, without dest): a planar result goes to caller-owned device memory plane by plane (planar output is one job: the cut below declines it)
+static int decode_item(const hm_file* f, uint32_t id, const hm_decode_params* params, const hm_device_dest* dest, hm_decoded* out, const hm_device_view* view,
+                       const hm_device_planes* planes)
 {
   std::memset(out, 0, sizeof(*out)); // (whatever fails below: nothing of an earlier call is left in it)
   if (!view) { // (r06) a grid of more tiles than parsing threads, to interleaved pixels: slab by slab under the entropy decode (decode_grid_cut)
@@ -1067,6 +1150,7 @@ static int decode_item(const hm_file* f, uint32_t id, const hm_decode_params* pa
   job.f = f; job.id = id; job.params = *params; job.s = (hipStream_t)params->stream;
   if (dest) { job.dest = *dest; job.has_dest = true; }
   if (view) { job.view = *view; job.has_view = true; }
+  if (planes) { job.planes = *planes; job.has_planes = true; }
   int rc = job_plan(job);
   if (rc) return rc;
   // ---- host: entropy-decode every coded picture (CABAC on the CPU, spread over threads like the reference's
@@ -1143,7 +1227,7 @@ int hm_file_sequence_info(const hm_file* f, hm_sequence_info* info)
 }
 
 static int decode_sequence(const hm_file* f, const uint32_t* frames, uint32_t first, int32_t count, const hm_decode_params* params, const hm_frame_dest* dests,
-                           const hm_device_dest* ddests, const hm_device_view* view, hm_decoded* out, int32_t* failed_frame);
+                           const hm_device_dest* ddests, const hm_device_view* view, hm_decoded* out, int32_t* failed_frame, const hm_device_planes* pdests = nullptr);
 
 int hm_decode_sequence(const hm_file* f, uint32_t first, int32_t count, const hm_decode_params* params, const hm_frame_dest* dests,
                        hm_decoded* out, int32_t* failed_frame)
@@ -1167,11 +1251,20 @@ int hm_decode_frames_to_device_view(const hm_file* f, const uint32_t* frames, in
   return decode_sequence(f, frames, 0, count, params, nullptr, dests, view, out, failed_frame);
 }
 
+int hm_decode_frames_to_device_planes(const hm_file* f, const uint32_t* frames, int32_t count, const hm_decode_params* params, const hm_device_planes* planes,
+                                      hm_decoded* out, int32_t* failed_frame)
+{
+  if (failed_frame) *failed_frame = -1;
+  if (!frames || !planes) return hm_fail(HM_ERR_INVALID_ARG, "null argument");
+  return decode_sequence(f, frames, 0, count, params, nullptr, nullptr, nullptr, out, failed_frame, planes);
+}
+
 // frames (NULL: first .. first + count - 1): the 1-based IDs of the frames, in any order, repeats allowed.
+// pdests (NULL, or `count` entries, without ddests): every frame's planar result goes to caller-owned device memory (hm_device_planes)
 // ddests (NULL, or `count` entries): every frame goes to caller-owned device memory; view (NULL, or with ddests): the same rectangle
 // of every frame, resampled, in one batched write behind the frames' conversions (hm_view_write_batch)
 static int decode_sequence(const hm_file* f, const uint32_t* frames, uint32_t first, int32_t count, const hm_decode_params* params, const hm_frame_dest* dests,
-                           const hm_device_dest* ddests, const hm_device_view* view, hm_decoded* out, int32_t* failed_frame)
+                           const hm_device_dest* ddests, const hm_device_view* view, hm_decoded* out, int32_t* failed_frame, const hm_device_planes* pdests)
 {
   if (failed_frame) *failed_frame = -1;
   if (!f || !params || !out) return hm_fail(HM_ERR_INVALID_ARG, "null argument");
@@ -1211,6 +1304,30 @@ static int decode_sequence(const hm_file* f, const uint32_t* frames, uint32_t fi
     for (int k = 0; k < count; k++) {
       const int rc = hm_dest_check_pointer(&ddests[k]);
       if (rc) return rc;
+    }
+  }
+  if (pdests) { // the same for planar destinations
+    for (int k = 0; k < count; k++) {
+      const int rc = check_planes_params(params, &pdests[k]);
+      if (rc) { if (failed_frame) *failed_frame = k; return rc; }
+    }
+    std::vector<hm_planes_plan> plans((size_t)count);
+    std::vector<char> planned((size_t)count, 0);
+    for (int k = 0; k < count; k++) { // against what the track declares (the decoded pictures: below)
+      hm_image_info info;
+      if (hm_file_image_info(f, frame_id(k), &info) != HM_OK || info.width <= 0 || info.height <= 0 || info.bit_depth < 8 || info.bit_depth > 16 || info.chroma < 0 || info.chroma > 3) continue;
+      int rchroma, rbits;
+      planar_result_format(params, info.chroma, info.bit_depth, &rchroma, &rbits);
+      int rc = hm_planes_resolve(rchroma, rbits, info.width, info.height, 0, &pdests[k], &plans[k]); // (frames carry no alpha)
+      if (!rc) rc = hm_planes_check_len(&pdests[k], &plans[k]);
+      if (rc) { if (failed_frame) *failed_frame = k; return rc; }
+      planned[k] = 1;
+    }
+    int n_dev = 0;
+    if (hipGetDeviceCount(&n_dev) != hipSuccess || n_dev == 0) { (void)hipGetLastError(); return hm_fail(HM_ERR_NO_DEVICE, "no HIP device available"); }
+    for (int k = 0; k < count; k++) {
+      const int rc = planned[k] ? hm_planes_check_pointer(&pdests[k], &plans[k]) : HM_OK;
+      if (rc) { if (failed_frame) *failed_frame = k; return rc; }
     }
   }
   const bool planar_target = hm_out_is_planar(params->out_format);
@@ -1266,6 +1383,15 @@ static int decode_sequence(const hm_file* f, const uint32_t* frames, uint32_t fi
       int drc = view ? hm_view_resolve(params->out_format, I.w, I.h, view, &vp) : HM_OK; // (against the frame's own decoded size)
       if (!drc) drc = hm_dest_resolve(params->out_format, vp.ow, vp.oh, &ddests[k], &dp);
       if (!drc) drc = hm_dest_check_len(&ddests[k], &dp);
+      if (drc) return fail(drc);
+    }
+    if (pdests) { // the destination against the picture's own format: the check hm_planes_write repeats before its launch
+      hm_planes_plan pp;
+      int rchroma, rbits;
+      planar_result_format(params, I.chroma, I.bd, &rchroma, &rbits);
+      int drc = hm_planes_resolve(rchroma, rbits, I.w, I.h, 0, &pdests[k], &pp);
+      if (!drc) drc = hm_planes_check_len(&pdests[k], &pp);
+      if (!drc) drc = hm_planes_check_pointer(&pdests[k], &pp);
       if (drc) return fail(drc);
     }
     if (planar_target) { // converted frame by frame behind the batch (emit_image); its refusals come here, before anything is queued
@@ -1377,7 +1503,7 @@ static int decode_sequence(const hm_file* f, const uint32_t* frames, uint32_t fi
     if (dests) { pk.ext_dst = dests[k].ext_dst; pk.ext_dst_len = dests[k].ext_dst_len; pk.ext_dst_stride = dests[k].ext_dst_stride; }
     const bool viewed = view && ddests;
     if ((rc = emit_image(&pk, s, Fr.I, nullptr, 0, Fr.dout, Fr.alpha_sdr, &out[k], ddests ? &ddests[k] : nullptr, viewed ? view : nullptr, nullptr,
-                         viewed ? &view_items[(size_t)k] : nullptr))) return release_all(rc);
+                         viewed ? &view_items[(size_t)k] : nullptr, pdests ? &pdests[k] : nullptr))) return release_all(rc);
   }
   // ---- the view of every frame: one pair of tap tables and one launch per pass for all frames that share them ----
   if (view && ddests && (rc = hm_view_write_batch(params->out_format, view_items.data(), count, s, view_blocks.sc.data()))) return release_all(rc);

@@ -113,6 +113,9 @@ struct DecodeJob {
   int view_dx = 0, view_dy = 0;
   int32_t sub_tiles[4] = {0, 0, 0, 0};
   hm_view_scratch view_scratch{}; // tap tables and the intermediate of the resampling step
+  // a planar result (out_format 0 / HM_OUT_YCBCR_*) goes to caller-owned device memory, plane by plane (has_planes; never together with has_dest)
+  hm_device_planes planes{};
+  bool has_planes = false;
   hipStream_t s = nullptr;
   ItemPlan item[2];   // [0] the image, [1] its alpha auxiliary image
   int n_items = 0;
@@ -143,6 +146,11 @@ int job_enqueue(DecodeJob& j, hm_decoded* out);
 // the size the file declares for the item, a device, the pointer (hm_image.cpp)
 // view (may be NULL): the destination is judged against the view's output size, the crop against the declared size
 int check_device_request(const hm_file* f, uint32_t id, const hm_decode_params* params, const hm_device_dest* dest, const hm_device_view* view = nullptr);
+// the same for a planar destination (hm_device_planes): the request, the planes against what hm_image_info declares (size, and the
+// result's chroma format and depth where the file decides them), a device, the pointers
+int check_planes_request(const hm_file* f, uint32_t id, const hm_decode_params* params, const hm_device_planes* planes);
+// what of it needs no file: params (ext_dst, an interleaved target), the planes' static checks, null pointers of Y
+int check_planes_params(const hm_decode_params* params, const hm_device_planes* planes);
 int job_complete(DecodeJob& j, hm_decoded* out);
 
 } // namespace hm_img

@@ -182,7 +182,8 @@ void hm_pipeline_destroy(hm_pipeline* p)
   delete p;
 }
 
-static int submit(hm_pipeline* p, const uint8_t* heif, size_t size, uint32_t item_id, uint64_t tag, const hm_device_dest* dest, const hm_device_view* view = nullptr);
+static int submit(hm_pipeline* p, const uint8_t* heif, size_t size, uint32_t item_id, uint64_t tag, const hm_device_dest* dest, const hm_device_view* view = nullptr,
+                  const hm_device_planes* planes = nullptr);
 
 int hm_pipeline_submit(hm_pipeline* p, const uint8_t* heif, size_t size, uint32_t item_id, uint64_t tag)
 {
@@ -203,9 +204,17 @@ int hm_pipeline_submit_to_device_view(hm_pipeline* p, const uint8_t* heif, size_
   return submit(p, heif, size, item_id, tag, dest, view);
 }
 
+int hm_pipeline_submit_to_device_planes(hm_pipeline* p, const uint8_t* heif, size_t size, uint32_t item_id, uint64_t tag, const hm_device_planes* planes)
+{
+  if (!p || !heif || !planes) return hm_fail(HM_ERR_INVALID_ARG, "null argument");
+  return submit(p, heif, size, item_id, tag, nullptr, nullptr, planes);
+}
+
 // dest (may be NULL): the image's pixels go to caller-owned device memory of the pipeline's device; view (may be NULL, with dest only):
 // a rectangle of them, resampled - job_plan then queues only the coded pictures the crop touches
-static int submit(hm_pipeline* p, const uint8_t* heif, size_t size, uint32_t item_id, uint64_t tag, const hm_device_dest* dest, const hm_device_view* view)
+// planes (may be NULL, without dest): the planes of the pipeline's planar out_format go to caller-owned device memory
+static int submit(hm_pipeline* p, const uint8_t* heif, size_t size, uint32_t item_id, uint64_t tag, const hm_device_dest* dest, const hm_device_view* view,
+                  const hm_device_planes* planes)
 {
   hipStream_t stream = nullptr;
   {
@@ -242,6 +251,14 @@ static int submit(hm_pipeline* p, const uint8_t* heif, size_t size, uint32_t ite
       if (prev >= 0) hipSetDevice(prev);
       im->job.dest = *dest; im->job.has_dest = true;
       if (view) { im->job.view = *view; im->job.has_view = true; }
+    }
+    if (planes) { // refused here, before anything is queued: no plane is written
+      int prev = -1;
+      hipGetDevice(&prev);
+      hipSetDevice(p->cfg.device);
+      rc = check_planes_request(im->file, im->job.id, &im->job.params, planes);
+      if (prev >= 0) hipSetDevice(prev);
+      im->job.planes = *planes; im->job.has_planes = true;
     }
     if (!rc) rc = job_plan(im->job);
   }

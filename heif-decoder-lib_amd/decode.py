@@ -8,7 +8,12 @@ Layouts: "chw" (one plane per channel) and "hwc" (the target's own interleaving)
 the target's own sample type: 8-bit "rgb" / "rgba", 16-bit "rrggbb_le" / "rrggbbaa_le" ...), torch.float16, torch.float32;
 floats are sample * scale[c] + bias[c], rounded after each step.  crop=(x, y, w, h) and size=(w, h) ask for a rectangle of the image,
 resampled (filter "triangle": antialiased bilinear, "bicubic", "lanczos3" or "nearest") in the step that writes the tensor; of a grid only the tiles the
-rectangle touches are decoded.  What the library refuses raises capi.HmError."""
+rectangle touches are decoded.  What the library refuses raises capi.HmError.
+
+Planar YCbCr stays planar: decode_to_planes / decode_sequence_to_planes / decode_batch_to_planes return (Y, Cb, Cr[, A]) ("planar":
+I420 and its kin) or (Y, CbCr[, A]) ("semiplanar": NV12, P010 with msb_aligned=True) as coded or at the chroma format asked for.
+
+    y, cbcr = decode_to_planes(data, chroma="420", layout="semiplanar")           # NV12: H x W, Hc x Wc x 2, uint8"""
 import ctypes as C
 import os
 
@@ -349,3 +354,252 @@ def decode_sequence_to_tensor(data, frames=None, out_format="rgb", layout="chw",
         return out
     finally:
         f.close()
+
+
+# ---- planar YCbCr (hm_device_planes) -----------------------------------------------------------------------------------------------
+
+PLANE_LAYOUTS = {"planar": capi.HM_DEV_PLANES_SEPARATE, "semiplanar": capi.HM_DEV_PLANES_SEMI}
+PLANAR_TARGETS = {None: 0, "420": capi.HM_OUT_YCBCR_420, "422": capi.HM_OUT_YCBCR_422, "444": capi.HM_OUT_YCBCR_444}
+
+
+def _planes_request(chroma, layout, to_8bit):
+    key = None if chroma is None else str(chroma)
+    if key not in PLANAR_TARGETS:
+        raise ValueError(f"chroma {chroma!r}: None (as coded), '420', '422' or '444'")
+    if str(layout).lower() not in PLANE_LAYOUTS:
+        raise ValueError(f"layout {layout!r}: 'planar' or 'semiplanar'")
+    if to_8bit and key is None:
+        raise ValueError("to_8bit: needs a chroma target (the picture as coded keeps its depth)")
+    return PLANAR_TARGETS[key], PLANE_LAYOUTS[str(layout).lower()]
+
+
+def _result_format(info, fmt, to_8bit):
+    """(chroma format, bits) of the planar result for a file of hm_image_info `info`: a target that equals the coded format converts nothing"""
+    as_coded = fmt == 0 or (info.chroma != 0 and info.chroma == (fmt & 3))
+    return (info.chroma, info.bit_depth) if as_coded else (fmt & 3, 8 if to_8bit else info.bit_depth)
+
+
+def _plane_shapes(chroma, lay, w, h, alpha):
+    """shapes of the tensors of one image: Y, then Cb and Cr (or CbCr), then alpha"""
+    cw, ch = (w if chroma == 3 else (w + 1) // 2), ((h + 1) // 2 if chroma == 1 else h)
+    shapes = [(h, w)]
+    if chroma != 0:
+        shapes += [(ch, cw, 2)] if lay == capi.HM_DEV_PLANES_SEMI else [(ch, cw), (ch, cw)]
+    if alpha:
+        shapes.append((h, w))
+    return shapes
+
+
+def _planes_of(tensors, chroma, lay, alpha, code, msb_aligned, scale, bias):
+    """hm_device_planes of one image's tensors (as _plane_shapes orders them): their row strides become the pitches"""
+    d = capi.DevicePlanes()
+    d.layout, d.dtype, d.msb_aligned = lay, code, 1 if msb_aligned else 0
+    for k in range(4):
+        d.scale[k], d.bias[k] = scale[k], bias[k]
+    slots = [0] + ([] if chroma == 0 else [1] if lay == capi.HM_DEV_PLANES_SEMI else [1, 2]) + ([3] if alpha else [])
+    for t, slot in zip(tensors, slots):
+        es = t.element_size()
+        if t.dim() == 3:
+            ok = (t.stride(2) == 1) and (t.stride(1) == 2 or t.shape[1] == 1)
+        else:
+            ok = t.stride(1) == 1 or t.shape[1] == 1
+        if not ok or t.stride(0) < 0:
+            raise ValueError("out: the elements of a row must be contiguous (only the row stride is free)")
+        d.plane[slot].ptr = t.data_ptr()
+        d.plane[slot].len = t.untyped_storage().nbytes() - t.storage_offset() * es
+        d.plane[slot].row_pitch = t.stride(0) * es if t.shape[0] > 1 else 0
+    return d
+
+
+def _check_out(out, shapes, dtype, lead=()):
+    if len(out) != len(shapes):
+        raise ValueError(f"out: {len(shapes)} tensors are needed, got {len(out)}")
+    for t, shape in zip(out, shapes):
+        if not t.is_cuda or t.dtype != dtype:
+            raise ValueError(f"out: CUDA tensors of dtype {dtype} are needed, got {t.dtype} on {t.device}")
+        if tuple(t.shape) != tuple(lead) + shape:
+            raise ValueError(f"out: shape {tuple(t.shape)} does not match the plane's {tuple(lead) + shape}")
+
+
+def _stream_handle(stream, device):
+    import torch
+    if stream is None:
+        stream = torch.cuda.current_stream(device)
+    return (stream.cuda_stream if hasattr(stream, "cuda_stream") else int(stream)) or None
+
+
+def _info(f, item_id):
+    iid = item_id or f.L.hm_file_primary_item(f.h)
+    info = capi.ImageInfo()
+    capi.check_image(f.L.hm_file_image_info(f.h, iid, C.byref(info)))
+    return iid, info
+
+
+def _default_plane_dtype(bits):
+    import torch
+    return torch.uint8 if bits == 8 else torch.uint16
+
+
+def decode_to_planes(data, item_id=0, chroma=None, layout="planar", dtype=None, to_8bit=False, scale=None, bias=None, out=None, stream=None,
+                     host_threads=None, msb_aligned=False, alpha=True):
+    """Decode one image of a HEIF file into planar YCbCr CUDA tensors: (Y, Cb, Cr[, A]) for layout "planar", (Y, CbCr[, A]) for
+    "semiplanar" (a 4:0:0 picture: (Y[, A])).  Y and A are H x W, Cb and Cr Hc x Wc, CbCr Hc x Wc x 2 (Cb first).  chroma: None = as
+    coded, "420" / "422" / "444" = converted to that format (to_8bit: down to 8 bits on the way).  dtype defaults to torch.uint8 or
+    torch.uint16 by the result's depth (out's dtype when out is given); msb_aligned (torch.uint16): v << (16 - bits), P010.  Floats are
+    sample * scale[c] + bias[c], c = Y, Cb, Cr, A.  out: a tuple of CUDA tensors of those shapes; their row strides are honoured.
+    The alpha plane is returned when the image has one and alpha is true; alpha=False leaves it out (plane[3] NULL) - the way to an
+    integer dtype for an image whose alpha plane is of the other depth class (8 bits beside more than 8), which is refused otherwise."""
+    import torch
+    L = capi.image_lib()
+    fmt, lay = _planes_request(chroma, layout, to_8bit)
+    sc, bi = _per_channel(scale, 1.0), _per_channel(bias, 0.0)
+    f = _File(data)
+    try:
+        iid, info = _info(f, item_id)
+        rchroma, rbits = _result_format(info, fmt, to_8bit)
+        w, h, alpha = info.width, info.height, bool(alpha) and bool(info.has_alpha)
+        if dtype is None:
+            dtype = out[0].dtype if out is not None else _default_plane_dtype(rbits)
+        code = _dtype_code(dtype)
+        shapes = _plane_shapes(rchroma, lay, w, h, alpha)
+        if out is None:
+            out = tuple(torch.empty(shape, dtype=dtype, device="cuda") for shape in shapes)
+        else:
+            out = tuple(out)
+            _check_out(out, shapes, dtype)
+        device = out[0].device
+        planes = _planes_of(out, rchroma, lay, alpha, code, msb_aligned, sc, bi)
+        prm = capi.DecodeParams(fmt, host_threads or _default_threads(), 0, 0, _stream_handle(stream, device), None, 0, 0, 0, 1 if to_8bit else 0)
+        d = capi.Decoded()
+        with torch.cuda.device(device):
+            capi.check_image(L.hm_decode_item_to_device_planes(f.h, iid, C.byref(prm), C.byref(planes), C.byref(d)))
+        L.hm_decoded_free(C.byref(d))
+        return out
+    finally:
+        f.close()
+
+
+def decode_sequence_to_planes(data, frames=None, chroma=None, layout="planar", dtype=None, to_8bit=False, scale=None, bias=None, out=None,
+                              stream=None, host_threads=None, msb_aligned=False):
+    """decode_to_planes over frames of an image sequence in ONE device batch (hm_decode_frames_to_device_planes): a tuple of
+    T x ... tensors, frame k in slice k of each.  frames: None (all), a range or a list of 1-based frame IDs, in any order."""
+    import torch
+    L = capi.image_lib()
+    fmt, lay = _planes_request(chroma, layout, to_8bit)
+    sc, bi = _per_channel(scale, 1.0), _per_channel(bias, 0.0)
+    f = _File(data)
+    try:
+        seq = capi.SequenceInfo()
+        capi.check_image(L.hm_file_sequence_info(f.h, C.byref(seq)))
+        if not seq.is_sequence:
+            raise capi.HmError(-1, "the file is not an image sequence")
+        ids = _frame_ids(frames, seq.frame_count)
+        first = None
+        for k, fid in enumerate(ids):
+            _, info = _info(f, fid)
+            key = (info.width, info.height) + _result_format(info, fmt, to_8bit)
+            if first is None:
+                first = key
+            if key != first:
+                raise ValueError(f"frames[{k}] (frame {fid}) is {key[0]} x {key[1]} (chroma {key[2]}, {key[3]} bits), the first is {first[0]} x {first[1]} "
+                                 f"(chroma {first[2]}, {first[3]} bits)")
+        w, h, rchroma, rbits = first
+        if dtype is None:
+            dtype = out[0].dtype if out is not None else _default_plane_dtype(rbits)
+        code, n = _dtype_code(dtype), len(ids)
+        shapes = _plane_shapes(rchroma, lay, w, h, False)
+        if out is None:
+            out = tuple(torch.empty((n,) + shape, dtype=dtype, device="cuda") for shape in shapes)
+        else:
+            out = tuple(out)
+            _check_out(out, shapes, dtype, (n,))
+        device = out[0].device
+        dests = (capi.DevicePlanes * n)(*[_planes_of([t[k] for t in out], rchroma, lay, False, code, msb_aligned, sc, bi) for k in range(n)])
+        prm = capi.DecodeParams(fmt, host_threads or _default_threads(), 0, 0, _stream_handle(stream, device), None, 0, 0, 0, 1 if to_8bit else 0)
+        res = (capi.Decoded * n)()
+        failed = C.c_int32(-1)
+        with torch.cuda.device(device):
+            rc = L.hm_decode_frames_to_device_planes(f.h, (C.c_uint32 * n)(*ids), n, C.byref(prm), dests, res, C.byref(failed))
+        if rc < 0:
+            detail = f"{L.hm_status_string(rc).decode()}: {L.hm_last_error().decode()}"
+            k = failed.value
+            raise capi.HmError(rc, f"frames[{k}] (frame {ids[k]}): {detail}" if k >= 0 else detail)
+        for k in range(n):
+            L.hm_decoded_free(C.byref(res[k]))
+        return out
+    finally:
+        f.close()
+
+
+def decode_batch_to_planes(files, item_id=0, chroma=None, layout="planar", dtype=None, to_8bit=False, scale=None, bias=None, out=None,
+                           host_threads=None, max_in_flight=4, msb_aligned=False, alpha=True):
+    """decode_to_planes over N files through ONE hm_pipeline: a tuple of N x ... tensors, file k in slice k of each.  files: bytes
+    objects or paths.  A file of another size or format (chroma format, depth, alpha) than the first raises ValueError naming it.
+    alpha=False: no alpha plane is asked for or returned, and files with and without one go together."""
+    import torch
+    L = capi.image_lib()
+    fmt, lay = _planes_request(chroma, layout, to_8bit)
+    sc, bi = _per_channel(scale, 1.0), _per_channel(bias, 0.0)
+    names, datas = [], []
+    for k, entry in enumerate(files):
+        if isinstance(entry, (bytes, bytearray, memoryview)):
+            names.append(f"files[{k}]")
+            datas.append(bytes(entry))
+        else:
+            names.append(os.fspath(entry))
+            with open(entry, "rb") as fh:
+                datas.append(fh.read())
+    if not datas:
+        raise ValueError("files: empty")
+    ids, first = [], None
+    for name, data in zip(names, datas):
+        f = _File(data)
+        try:
+            iid, info = _info(f, item_id)
+        finally:
+            f.close()
+        key = (info.width, info.height) + _result_format(info, fmt, to_8bit) + (bool(alpha) and bool(info.has_alpha),)
+        if first is None:
+            first = key
+        if key != first:
+            raise ValueError(f"{name}: the image is {key[0]} x {key[1]} (chroma {key[2]}, {key[3]} bits, alpha {key[4]}), the batch is "
+                             f"{first[0]} x {first[1]} (chroma {first[2]}, {first[3]} bits, alpha {first[4]})")
+        ids.append(iid)
+    w, h, rchroma, rbits, alpha = first
+    if dtype is None:
+        dtype = out[0].dtype if out is not None else _default_plane_dtype(rbits)
+    code, n = _dtype_code(dtype), len(datas)
+    shapes = _plane_shapes(rchroma, lay, w, h, alpha)
+    if out is None:
+        out = tuple(torch.empty((n,) + shape, dtype=dtype, device="cuda") for shape in shapes)
+    else:
+        out = tuple(out)
+        _check_out(out, shapes, dtype, (n,))
+    device = out[0].device
+    cfg = capi.PipelineConfig(host_threads or _default_threads(), max(1, int(max_in_flight)), fmt | (capi.HM_OUT_YCBCR_8BIT if to_8bit else 0), 0, 0, 0,
+                              device.index, 0, 0)
+    pipe = C.c_void_p()
+    with torch.cuda.device(device):
+        torch.cuda.current_stream().synchronize()  # (the pipeline works on streams of its own: `out` must be ready for them)
+        capi.check_image(L.hm_pipeline_create(C.byref(cfg), C.byref(pipe)))
+        try:
+            def take():
+                r = capi.PipelineResult()
+                capi.check_image(L.hm_pipeline_next(pipe, C.byref(r)))
+                tag, status = r.tag, r.status
+                detail = L.hm_last_error().decode() if status else ""
+                L.hm_pipeline_release(pipe, C.byref(r))
+                if status:
+                    raise capi.HmError(status, f"{names[tag]}: {detail}")
+            for k, data in enumerate(datas):
+                planes = _planes_of([t[k] for t in out], rchroma, lay, alpha, code, msb_aligned, sc, bi)
+                while True:
+                    rc = capi.check_image(L.hm_pipeline_submit_to_device_planes(pipe, data, len(data), ids[k], k, C.byref(planes)))
+                    if rc != capi.HM_PIPELINE_FULL:
+                        break
+                    take()
+            while L.hm_pipeline_pending(pipe):
+                take()
+        finally:
+            L.hm_pipeline_destroy(pipe)
+    return out

@@ -505,6 +505,74 @@ HM_API int hm_decode_sequence_to_device(const hm_file* f, uint32_t first, int32_
 HM_API int hm_pipeline_submit_to_device(hm_pipeline* p, const uint8_t* heif, size_t size, uint32_t item_id, uint64_t tag, const hm_device_dest* dest);
 
 /* ------------------------------------------------------------------------- */
+/* Device-resident planar YCbCr: I420 / NV12 / P010 and their kin in caller-owned GPU memory */
+/* ------------------------------------------------------------------------- */
+
+/* The other half of what the library decodes to - out_format 0 (the picture as coded), HM_OUT_YCBCR_420 / _422 / _444 (the
+ * reference's chain to that chroma format, optionally with convert_hdr_to_8bit), a Y plane alone for 4:0:0 - into device memory of
+ * the caller, one destination per plane, separate or with Cb and Cr interleaved: what an encoder behind a transcode, a video
+ * pipeline that takes NV12 / P010 surfaces or a model that works on luma wants on the device.  hm_device_dest stays an interleaved
+ * RGB destination and hm_decode_item_to_device keeps refusing the planar formats; these entry points take the planar formats only.
+ *   Format and size: the planes written are those hm_decode_item with the same hm_decode_params hands out in plane[0 .. 2] / alpha.
+ *   bits and the chroma format are the result's (out->bit_depth, out->chroma), the plane sizes out->plane_width / height[c] (chroma
+ *   (w + 1) / 2 and (h + 1) / 2 where sub-sampled); the alpha plane has the image's size.  The interleaved plane of
+ *   HM_DEV_PLANES_SEMI has 2 * chroma_width elements per row, Cb first.  A 4:0:0 result writes Y only: plane[1] and plane[2] must be
+ *   all zero then.
+ *   Integer dtypes store the sample: HM_DEV_U8 needs bits == 8, HM_DEV_U16 bits > 8 (little-endian words); msb_aligned stores
+ *   v << (16 - bits), the P010 / P012 convention.  The result's depth is known for certain only after the decode: a mismatch is
+ *   HM_ERR_INVALID_ARG before anything is written, and at the entry point already where hm_image_info decides it.
+ *   Float dtypes:  __fadd_rn(__fmul_rn((float)v, scale[c]), bias[c])  with c = 0 Y, 1 Cb, 2 Cr, 3 alpha (no fused multiply-add),
+ *   HM_DEV_F16 that value through __float2half_rn (denormals kept) - hm_device_dest's rule.
+ *   Alpha: written to plane[3] at the alpha plane's own depth (msb_aligned: v << (16 - that depth)) when plane[3].ptr is non-NULL,
+ *   not written and not looked at otherwise.  With an integer dtype the alpha depth must be in the dtype's class (8, or more than 8
+ *   bits), else HM_ERR_UNSUPPORTED; plane[3] given for an image without alpha: HM_ERR_INVALID_ARG.
+ *   Only plane_width x plane_height elements per plane are written: no pitch padding, nothing behind the last row.
+ * Refused with HM_ERR_INVALID_ARG before any work is queued, every plane unwritten: an unknown layout or dtype, non-zero reserved,
+ * msb_aligned without HM_DEV_U16, a ptr or pitch that is not a multiple of the element size, a pitch below the tight value, len
+ * below the last-row form row_pitch * (rows - 1) + tight, a NULL ptr of a plane that is written, a pointer that is not device
+ * memory of the decoding device, an interleaved HM_OUT_RGB* target (that is hm_decode_item_to_device's), params->ext_dst, two
+ * planes whose byte ranges overlap, and with HM_DEV_PLANES_SEMI a plane[2] that is not all zero.
+ * Views (hm_device_view) with a planar destination do not exist: no entry point here takes one. */
+enum { HM_DEV_PLANES_SEPARATE = 0,  /* Y, Cb, Cr[, A]: one plane each (I420 / I422 / I444 and their 16-bit forms) */
+       HM_DEV_PLANES_SEMI     = 1 };/* Y, CbCr interleaved (Cb first)[, A]: NV12 / NV16 / NV24, P010-style with 16 bits */
+typedef struct hm_device_plane {
+  void*    ptr;          /* device memory of the device the decode runs on                              */
+  uint64_t len;          /* bytes available at ptr                                                      */
+  int64_t  row_pitch;    /* bytes between rows; 0 = tight                                               */
+} hm_device_plane;
+typedef struct hm_device_planes {
+  hm_device_plane plane[4];   /* [0] Y, [1] Cb (SEMI: CbCr), [2] Cr (SEMI: must be all zero), [3] alpha (ptr NULL: not written) */
+  int32_t layout, dtype;      /* HM_DEV_PLANES_*, HM_DEV_U8 / _U16 / _F16 / _F32 */
+  int32_t msb_aligned;        /* HM_DEV_U16 only: store v << (16 - bits), the P010 / P012 convention; otherwise 0 */
+  int32_t reserved;           /* 0 */
+  float   scale[4], bias[4];  /* float dtypes, per component Y, Cb, Cr, A */
+} hm_device_planes;
+/* Bytes the planes must hold for a result of this chroma format (HM_CHROMA_*), depth and luma size: need[c] (may be NULL) =
+ * row_pitch * (rows - 1) + tight per plane - 0 for a plane that does not exist (Cb / Cr of 4:0:0, Cr of HM_DEV_PLANES_SEMI);
+ * need[3] is what an alpha plane takes.  Returns need[0] + need[1] + need[2], plus need[3] when d->plane[3].ptr is non-NULL, or the
+ * negative status of a combination that is refused.  Pure host arithmetic: no device needed; no len and no other ptr is looked at. */
+HM_API int64_t hm_device_planes_bytes(int chroma, int bits, int width, int height, const hm_device_planes* d, int64_t need[4]);
+/* The step on its own, on planes that are on the device already (the sibling of hm_to_tensor): d_src[0 .. 2] Y, Cb, Cr (Cb / Cr
+ * unused for HM_CHROMA_MONO), d_src[3] the alpha plane with alpha_bits > 0 (alpha_bits 0: none), src_stride in bytes; samples are
+ * bytes for 8 bits, little-endian 16-bit words above.  Asynchronous on `stream`. */
+HM_API int hm_planes_to_tensor(int chroma, int bits, int width, int height, int alpha_bits, const void* const d_src[4], const int32_t src_stride[4],
+                               const hm_device_planes* planes, void* stream);
+/* hm_decode_item with the planes going to `planes`: returns when they are in place (the work runs on params->stream).  params->
+ * out_format: 0 or HM_OUT_YCBCR_*.  `out` is filled as for an ext_dst decode: used_ext_dst = 1, every plane[] and alpha NULL,
+ * stride[c] / alpha_stride = the pitches in use (SEMI: stride[2] = 0); plane_width / height, chroma, bit_depth, the nclx fields
+ * and warnings exactly as hm_decode_item sets them. */
+HM_API int hm_decode_item_to_device_planes(const hm_file* f, uint32_t id, const hm_decode_params* params, const hm_device_planes* planes, hm_decoded* out);
+/* The sequence form: frames[0 .. count) are 1-based frame IDs in any order, repeats allowed, decoded in ONE device batch as by
+ * hm_decode_frames_to_device_view, planes[k] the destination of frames[k] (one launch of the plane kernel per frame).  A frame whose
+ * data or destination fails fails the call before anything is written, *failed_frame (may be NULL) = its index k, -1 otherwise. */
+HM_API int hm_decode_frames_to_device_planes(const hm_file* f, const uint32_t* frames, int32_t count, const hm_decode_params* params,
+                                             const hm_device_planes* planes, hm_decoded* out, int32_t* failed_frame);
+/* hm_pipeline_submit with a planar destination (copied); the pipeline's out_format must be 0 or HM_OUT_YCBCR_* [| HM_OUT_YCBCR_8BIT].
+ * The planes are complete when hm_pipeline_next hands the result out. */
+HM_API int hm_pipeline_submit_to_device_planes(hm_pipeline* p, const uint8_t* heif, size_t size, uint32_t item_id, uint64_t tag,
+                                               const hm_device_planes* planes);
+
+/* ------------------------------------------------------------------------- */
 /* Views: a rectangle of the image, at a size of the caller's choice, into the destination */
 /* ------------------------------------------------------------------------- */
 
