@@ -28,6 +28,12 @@
 #include "hm_avail.h"
 
 #include "hm_internal.h"
+#include "residual_tables.h"
+
+// the image of lds[0 .. R_TABLES), worked out at compile time.  With external linkage: the test hook reads it back by symbol, and the
+// runtime finds a device variable in the code object only by a global name (a const at namespace scope is a local one)
+extern __device__ const hm_residual_tables hm_residual_tables_image;
+__device__ const hm_residual_tables hm_residual_tables_image = hm_make_residual_tables();
 
 namespace {
 
@@ -85,6 +91,8 @@ struct BigGeom {
 constexpr int R_MT16 = 16 * BigGeom<4>::MT_STRIDE * 2, R_MT32 = 32 * BigGeom<5>::MT_STRIDE * 2; // bytes
 constexpr int R_TABLES = R_TABLES_SMALL + R_MT16 + R_MT32; // ... + the 16- and 32-point bases as 16-bit rows
 static_assert(R_TABLES % 16 == 0, "the waves' blocks are read 16 bytes at a time");
+static_assert(R_TABLES == HM_RT_BYTES && R_TABLES_SMALL == HM_RT_MT16 && R_TABLES_SMALL + R_MT16 == HM_RT_MT32 &&
+              BigGeom<4>::MT_STRIDE == HM_RT_MT16_STRIDE && BigGeom<5>::MT_STRIDE == HM_RT_MT32_STRIDE, "residual_tables.h lays the image out");
 // maximum of a value < 8 over the active lanes (ballots: one vector compare per bit)
 __device__ __forceinline__ int wave_max3(int v)
 {
@@ -175,7 +183,7 @@ __device__ __forceinline__ void big_residual(int16_t* coeff, int16_t* tmp, const
 #define HM_R_SKIP 0
 #endif
 #define HM_R_ATTR __attribute__((amdgpu_waves_per_eu(HM_R_WPE, HM_R_WPE)))
-__global__ __launch_bounds__(R_WAVES * 64) HM_R_ATTR void k_residual(const hm_dev_pic* __restrict__ pics, int n_pics, int max_ctb_h, int segs)
+__global__ __launch_bounds__(R_WAVES * 64) HM_R_ATTR void k_residual(const hm_dev_pic* __restrict__ pics, int n_pics, int max_ctb_h, int segs, int rpw)
 {
   extern __shared__ __attribute__((aligned(16))) uint8_t lds[];
   const int tid = threadIdx.x, lane = tid & 63, wave = rfl(tid >> 6);
@@ -184,42 +192,32 @@ __global__ __launch_bounds__(R_WAVES * 64) HM_R_ATTR void k_residual(const hm_de
   uint32_t* const w8 = reinterpret_cast<uint32_t*>(lds + 1024 + 256);
   int16_t* const mt16 = reinterpret_cast<int16_t*>(lds + R_TABLES_SMALL);
   int16_t* const mt32 = reinterpret_cast<int16_t*>(lds + R_TABLES_SMALL + R_MT16);
-  for (int i = tid; i < 1024; i += R_WAVES * 64) {
-    const int k = i >> 5, n = i & 31;
-    const int m = (k * (2 * n + 1)) & 127;
-    int v;
-    if (k == 0) v = 64;
-    else if (m <= 32) v = c_dct_mag[m];
-    else if (m <= 64) v = -c_dct_mag[64 - m];
-    else if (m <= 96) v = -c_dct_mag[m - 64];
-    else v = c_dct_mag[128 - m];
-    dct[i] = (int8_t)v;
-  }
-  for (int i = tid; i < 92; i += R_WAVES * 64) { // [70,76) level scale, [76,92) DST (the layout of recon.hip's table)
-    int v = 0;
-    if (i >= 70 && i < 76) v = c_level_scale[i - 70];
-    else if (i >= 76) v = c_dst[(i - 76) >> 2][(i - 76) & 3];
-    tab[i] = (int16_t)v;
-  }
+  // the tables are constants of the code object (residual_tables.h): 272 x 16 bytes, one load and one LDS store per thread (the
+  // first sixteen threads two), requested first so that the zeroing below runs under the load.  They used to be rebuilt here by
+  // every workgroup - ~220 vector instructions per wave and a chain of constant load -> LDS -> barrier -> LDS -> barrier in
+  // front of the first record.
+  const GLOBAL_AS r_u32x4* const image = gptr<r_u32x4>(hm_residual_tables_image.b);
+  constexpr int TABLE_VECS = R_TABLES / 16, EXTRA = TABLE_VECS - R_WAVES * 64;
+  static_assert(EXTRA > 0 && EXTRA <= R_WAVES * 64, "every thread copies one 16-byte piece, the first EXTRA a second one");
+  const r_u32x4 piece = image[tid];
+  r_u32x4 piece2 = {0u, 0u, 0u, 0u};
+  if (tid < EXTRA) piece2 = image[R_WAVES * 64 + tid]; // (waited for inside the branch, which only the first wave enters: both loads are in flight by then)
   uint8_t* const wbase = lds + R_TABLES + (size_t)wave * R_WAVE;
   int16_t* const coeff = reinterpret_cast<int16_t*>(wbase);
   int16_t* const tmp = reinterpret_cast<int16_t*>(wbase + 2048);
   int* const slots = reinterpret_cast<int*>(wbase + 2048 + 1024); // [4][16]
   uint32_t* const lvl = reinterpret_cast<uint32_t*>(wbase + 2048 + 1024 + 4 * 16 * 4); // [R_STAGE]: the chunk's first levels
-  for (int i = lane; i < 1024; i += 64) coeff[i] = 0;
-  slots[lane] = 0;
-  __syncthreads();
-  // 8-point inverse DCT basis as pairs of consecutive inputs (fallback-dct.cc:592-733: M[j][i] = dct[4 j][i])
-  for (int t = tid; t < 32; t += R_WAVES * 64) {
-    const int i = t >> 2, k = t & 3;
-    w8[t] = ((uint32_t)(uint16_t)(int16_t)dct[(4 * (2 * k)) * 32 + i]) | ((uint32_t)(uint16_t)(int16_t)dct[(4 * (2 * k + 1)) * 32 + i] << 16);
+  {
+    // the coefficient block and the gather slots start out zero: three 16-byte stores per lane, the third over the tail of `tmp`
+    // (written before it is read) and `slots`
+    const r_u32x4 zero = {0u, 0u, 0u, 0u};
+    r_u32x4* const z = reinterpret_cast<r_u32x4*>(wbase) + lane;
+    z[0] = zero;
+    z[64] = zero;
+    z[(2048 + 1024 + 4 * 16 * 4) / 16 - 64] = zero;
   }
-  // ... and the 16- / 32-point bases as rows of 16-bit weights: mt[i][j] = M[j][i] = dct[(32 / nT) j][i] (big_residual)
-  for (int t = tid; t < 256 + 1024; t += R_WAVES * 64) {
-    const bool big = t >= 256;
-    const int u = big ? t - 256 : t, i = big ? u >> 5 : u >> 4, j = big ? u & 31 : u & 15;
-    (big ? mt32 + i * BigGeom<5>::MT_STRIDE : mt16 + i * BigGeom<4>::MT_STRIDE)[j] = (int16_t)dct[((big ? 1 : 2) * j) * 32 + i];
-  }
+  reinterpret_cast<r_u32x4*>(lds)[tid] = piece;
+  if (tid < EXTRA) reinterpret_cast<r_u32x4*>(lds)[R_WAVES * 64 + tid] = piece2;
   __syncthreads();
 
   // ---- this wave's unit: (picture, CTB row, chain kind, segment of the row) ----
@@ -228,15 +226,21 @@ __global__ __launch_bounds__(R_WAVES * 64) HM_R_ATTR void k_residual(const hm_de
   // Nothing here depends on the records in front of a CTU except two running sums, and both have a known value at a CTU
   // boundary: the first level of the CTU's first record stands in its header, and the residual slab of a row has room for
   // ctb x ctb samples per CTU, so a segment that starts at CTU x0 packs its residuals from x0 x (CTU size) on.
+  // A batch of many pictures has the opposite problem - a wave lives for five chunks, and what it loads and derives before the
+  // first one (descriptor, stream header, geometry, weights, tables) is the same for the row below: there the launcher gives a
+  // wave rpw = 2 rows of its kind, 2 k and 2 k + 1 (the last wave of a kind of a picture with an odd number of rows has one).
+  // rpw is 1 or 2, nothing else: the wave's second row is its last (row_last below).
   const uint32_t unit = (uint32_t)blockIdx.x * R_WAVES + (uint32_t)wave;
-  const uint32_t per_pic = 2u * (uint32_t)max_ctb_h * (uint32_t)segs;
+  const uint32_t per_pic = 2u * (((uint32_t)max_ctb_h + (uint32_t)rpw - 1u) / (uint32_t)rpw) * (uint32_t)segs;
   const int pic_index = (int)(unit / per_pic);
   if (pic_index >= n_pics) return;
   const int rem = (int)(unit - (uint32_t)pic_index * per_pic);
   const int seg = rem % segs, rk = rem / segs; // (once per wave)
-  const int row = rk >> 1, kind = rk & 1;
+  const int kind = rk & 1;
+  int row = (rk >> 1) * rpw;
   const hm_dev_pic dp = pics[pic_index];
   if (row >= dp.ctb_h || (kind && dp.chroma_format == 0)) return;
+  const int row_last = row + rpw <= dp.ctb_h ? row + rpw - 1 : dp.ctb_h - 1; // the wave's last row
   const int x0 = (int)((long)seg * dp.ctb_w / segs), x1 = (int)((long)(seg + 1) * dp.ctb_w / segs); // the segment's CTUs [x0, x1)
   if (x0 >= x1) return; // (more segments than CTUs)
   const uint8_t* blob = dp.blob;
@@ -253,13 +257,20 @@ __global__ __launch_bounds__(R_WAVES * 64) HM_R_ATTR void k_residual(const hm_de
   const int bd = dp.bit_depth;
   const int maxv = (1 << bd) - 1;
   const ResidGeom RG = resid_geom(dp.ctb_w, dp.ctb_h, dp.log2_ctb, dp.chroma_format);
-  const GLOBAL_AS uint32_t* const q0 = ctbq + HM_CTB_DWORDS * ((size_t)row * dp.ctb_w);
+  const GLOBAL_AS uint32_t* q0 = ctbq + HM_CTB_DWORDS * ((size_t)row * dp.ctb_w);
   const GLOBAL_AS uint32_t* const qs = q0 + HM_CTB_DWORDS * (size_t)x0;       // the segment's first CTU
   const GLOBAL_AS uint32_t* const q1 = q0 + HM_CTB_DWORDS * (size_t)(x1 - 1); // ... and its last
   const uint32_t rec_begin = qs[kind ? 9 : 0];
-  const uint32_t rec_end = q1[kind ? 9 : 0] + (q1[kind ? 10 : 1] & 0xFFFFu);
+  uint32_t rec_end = q1[kind ? 9 : 0] + (q1[kind ? 10 : 1] & 0xFFFFu);
   uint32_t lev_base = qs[kind ? 12 : 11];
-  uint32_t res_base = RG.slab(kind, row) + (uint32_t)x0 * ((kind ? RG.chroma_row : RG.luma_row) / (uint32_t)dp.ctb_w);
+  // the same three of the wave's last row, in the same trip to memory - in front of every store, when nothing has to wait behind
+  // one (for a wave with one row: its own once more)
+  const size_t to_last = HM_CTB_DWORDS * ((size_t)(row_last - row) * dp.ctb_w);
+  const uint32_t nx_begin = qs[to_last + (kind ? 9 : 0)];
+  const uint32_t nx_end = q1[to_last + (kind ? 9 : 0)] + (q1[to_last + (kind ? 10 : 1)] & 0xFFFFu);
+  const uint32_t nx_lev = qs[to_last + (kind ? 12 : 11)];
+  const uint32_t res_per_ctb = (kind ? RG.chroma_row : RG.luma_row) / (uint32_t)dp.ctb_w;
+  uint32_t res_base = RG.slab(kind, row) + (uint32_t)x0 * res_per_ctb;
   int cur_ctb = x0; // CTB (column) of the chunk's first record
 
   // ---- per-lane constants of the 4x4 transform (lane = sample (bx, by) of the block of its 16-lane group) ----
@@ -309,8 +320,9 @@ __global__ __launch_bounds__(R_WAVES * 64) HM_R_ATTR void k_residual(const hm_de
   // the plane geometry of the wave's chain kind, as scalars (selects on the kind otherwise end up in vector registers)
   const int k_lw = rfl(kind ? sub_w : 0), k_lh = rfl(kind ? sub_h : 0);
   const int k_ctb_pw = rfl(m_ctb >> k_lw), k_rem_last = rfl((dp.width >> k_lw) - (dp.ctb_w - 1) * (m_ctb >> k_lw)); // samples of the plane in a CTB column / in the last one
-  const int k_plane_h = rfl(dp.height >> k_lh), k_row_y0 = rfl(row << (dp.log2_ctb - k_lh));
-  for (uint32_t chunk = rec_begin; chunk < rec_end; chunk += 64) {
+  const int k_plane_h = rfl(dp.height >> k_lh);
+  int k_row_y0 = rfl(row << (dp.log2_ctb - k_lh));
+  for (uint32_t chunk = rec_begin; chunk < rec_end; chunk += 64) { // (over the chunks of the wave's rows: see the loop's end)
     const uint32_t ri = chunk + (uint32_t)lane;
     const bool valid = ri < rec_end;
     // pos | info << 8 | pred_mode << 16 | qp << 24, and the level count
@@ -329,7 +341,7 @@ __global__ __launch_bounds__(R_WAVES * 64) HM_R_ATTR void k_residual(const hm_de
     //      counter: a load requested behind a store is only there when the store has been acknowledged, so every wait that follows
     //      a store costs a trip to memory - the chunk used to have two of them (the block map's inputs behind the previous chunk's
     //      residuals, the levels behind the micro-ops and the block map) plus one per pass (see level() below). ----
-    const r_u32x2 ahead = fetch_records(chunk + 64); // the next chunk's records
+    const r_u32x2 ahead = fetch_records(chunk + 64 < rec_end ? chunk + 64 : nx_begin); // the next chunk's records - behind a row's last chunk those of the row below
     // (luma chains, block map: the first records and the flags of the CTBs that may start inside this chunk)
     const int cand = cur_ctb + 1 + lane;
     const bool cand_ok = kind == 0 && cand < x1;
@@ -425,23 +437,31 @@ __global__ __launch_bounds__(R_WAVES * 64) HM_R_ATTR void k_residual(const hm_de
       const int gx = (my_ctb << l4) + x4, gy = (row << l4) + y4; // the block's first cell in the picture's map
       GLOBAL_AS uint16_t* const meta = gptr_w<uint16_t>(dp.meta);
       const int w4 = dp.w4, h4 = dp.h4;
-      // 4x4 and 8x8 blocks: the lane of the record writes its 1 / 4 cells
-#pragma unroll
-      for (int k = 0; k < 4; k++) {
-        const int i = k & 1, j = k >> 1;
-        if (valid && l2 <= 3 && (k == 0 || l2 == 3) && gx + i < w4 && gy + j < h4)
-          meta[(uint32_t)(gx + i) + __umul24((uint32_t)(gy + j), (uint32_t)w4)] = (uint16_t)((i == 0 ? left_ok : 0) | ((j == 0 ? top_ok : 0) << 1) | qword);
+      // A picture's width and height are multiples of 8 (MinCbSizeY >= 8: hevc_headers.cpp, stream_check.cpp), so the map's are even:
+      // the cells of a block of 8x8 and more come in pairs side by side that are one aligned dword of the map, and a pair or a
+      // block's second row lies inside the picture whenever its first cell does.
+      const uint32_t cell = (uint32_t)gx + __umul24((uint32_t)gy, (uint32_t)w4);
+      const uint32_t top2 = (uint32_t)top_ok << 1;
+      const bool inside = valid && gx < w4 && gy < h4;
+      GLOBAL_AS uint32_t* const meta2 = reinterpret_cast<GLOBAL_AS uint32_t*>(meta);
+      // 4x4 blocks: the lane of the record writes its cell; 8x8 blocks: a dword per row of the map
+      if (inside && l2 == 2) meta[cell] = (uint16_t)((uint32_t)left_ok | top2 | qword);
+      if (inside && l2 == 3) {
+        meta2[cell >> 1] = ((uint32_t)left_ok | top2 | qword) | ((top2 | qword) << 16);
+        meta2[(cell + (uint32_t)w4) >> 1] = ((uint32_t)left_ok | qword) | (qword << 16);
       }
-      // 16x16 and 32x32 blocks: one cell per lane
+      // 16x16 and 32x32 blocks: a pair of cells per lane; what the lanes need of the record travels in two words
+      const uint32_t pk = (uint32_t)left_ok | top2 | ((uint32_t)l2 << 2) | qword, gxy = (uint32_t)gx | ((uint32_t)gy << 16);
       for (unsigned long long mb = ballot(valid && l2 >= 4); mb; mb &= mb - 1) {
         const int b = (int)__builtin_ctzll(mb);
-        const int s_l2 = __builtin_amdgcn_readlane(l2, b), s_gx = __builtin_amdgcn_readlane(gx, b), s_gy = __builtin_amdgcn_readlane(gy, b);
-        const int s_left = __builtin_amdgcn_readlane(left_ok, b), s_top = __builtin_amdgcn_readlane(top_ok, b);
-        const uint32_t s_q = (uint32_t)__builtin_amdgcn_readlane((int)qword, b);
-        const int n4 = 1 << (s_l2 - 2);
-        const int i = lane & (n4 - 1), j = lane >> (s_l2 - 2);
-        if (lane < n4 * n4 && s_gx + i < w4 && s_gy + j < h4)
-          meta[(uint32_t)(s_gx + i) + __umul24((uint32_t)(s_gy + j), (uint32_t)w4)] = (uint16_t)((i == 0 ? s_left : 0) | ((j == 0 ? s_top : 0) << 1) | s_q);
+        const uint32_t s_pk = (uint32_t)__builtin_amdgcn_readlane((int)pk, b), s_gxy = (uint32_t)__builtin_amdgcn_readlane((int)gxy, b);
+        const int s_l2 = (int)((s_pk >> 2) & 7), s_gx = (int)(s_gxy & 0xFFFFu), s_gy = (int)(s_gxy >> 16);
+        const uint32_t s_q = s_pk & 0xFF00u;
+        const int i = (lane & ((1 << (s_l2 - 3)) - 1)) << 1, j = lane >> (s_l2 - 3); // first cell of the pair / row inside the block
+        if (lane < (1 << (2 * s_l2 - 5)) && s_gx + i < w4 && s_gy + j < h4) {
+          const uint32_t t = j == 0 ? s_pk & 2u : 0u;
+          meta2[((uint32_t)(s_gx + i) + __umul24((uint32_t)(s_gy + j), (uint32_t)w4)) >> 1] = ((i == 0 ? s_pk & 1u : 0u) | t | s_q) | ((t | s_q) << 16);
+        }
       }
     }
 
@@ -590,12 +610,26 @@ __global__ __launch_bounds__(R_WAVES * 64) HM_R_ATTR void k_residual(const hm_de
       if (((s_r0 >> 8) & HM_TU_LOG2_MASK) == 4) big_residual<4>(coeff, tmp, mt16, tab, cf, (int)s_cnt, qP, bd, resid + s_ro, lane);
       else big_residual<5>(coeff, tmp, mt32, tab, cf, (int)s_cnt, qP, bd, resid + s_ro, lane);
     }
+
+    // ---- behind a row's last chunk the row below: what depends on the row and nothing else is set anew (its first records came
+    //      with this chunk's loads).  A row always has a chunk: every CTB has records in each list (stream_check.cpp). ----
+    if (chunk + 64 >= rec_end && row < row_last) {
+      row = row_last;
+      q0 += to_last;
+      rec_end = nx_end; lev_base = nx_lev;
+      res_base = RG.slab(kind, row) + (uint32_t)x0 * res_per_ctb;
+      cur_ctb = x0;
+      k_row_y0 = rfl(row << (dp.log2_ctb - k_lh));
+      chunk = nx_begin - 64; // (the loop's step makes it the row's first record)
+    }
   }
 }
 
 } // namespace
 
 extern "C" const void* hm_residual_kernel() { return reinterpret_cast<const void*>(k_residual); } // (hm_debug_kernel_regs)
+// (test hook) the table image as the current device holds it, HM_RT_BYTES bytes
+extern "C" int hm_residual_tables_read(void* out) { return hm_check_hip(hipMemcpyFromSymbol(out, HIP_SYMBOL(hm_residual_tables_image), HM_RT_BYTES), "read of k_residual's tables"); }
 
 // Residuals of the pictures of one class with split chains (all of them share max_ctb_h as the grid's row count).
 extern "C" int hm_launch_residual(const hm_dev_pic* d_pics, int n_pics, int max_ctb_h, hipStream_t s)
@@ -606,12 +640,18 @@ extern "C" int hm_launch_residual(const hm_dev_pic* d_pics, int n_pics, int max_
   const int forced = hm_knob(HM_KNOB_RESID_SEGS);
   int segs = forced > 0 ? forced : (int)(8192 / units);
   segs = segs < 1 ? 1 : (segs > 16 ? 16 : segs);
-  units *= segs;
+  // many pictures: two rows of a kind per wave, which pays what a wave does before its first record once for both.  The rule: only
+  // where the halved launch still has the ~8192 waves the segments aim for (the device holds 7168 of them at seven per SIMD) -
+  // below that the rows are the launch's parallelism -, and never with forced segments (a forced count, 1 included, keeps a wave
+  // per row).  Measured at the headline only (589 824 units: k_residual 4.69 -> 4.59 ms, profiles/residual_fixed_costs.txt and
+  // DESIGN.md 5); nothing between the two regimes has been timed.
+  int rpw = forced <= 0 && segs == 1 && units >= 2 * 8192 ? 2 : 1;
+  units = (long)n_pics * 2 * ((max_ctb_h + rpw - 1) / rpw) * segs;
   const long groups = (units + R_WAVES - 1) / R_WAVES;
   if (groups > 0x7FFFFFFFL) return hm_fail(HM_ERR_UNSUPPORTED, "too many CTB rows in one launch");
-  if (hm_knob(HM_KNOB_CHAIN_DEBUG)) fprintf(stderr, "[k_residual] %d pictures, every CTU row in %d segments\n", n_pics, segs);
+  if (hm_knob(HM_KNOB_CHAIN_DEBUG)) fprintf(stderr, "[k_residual] %d pictures, every CTU row in %d segments, %d rows of a kind per wave\n", n_pics, segs, rpw);
   int a_n = n_pics, a_h = max_ctb_h;
-  void* args[] = {(void*)&d_pics, &a_n, &a_h, &segs};
+  void* args[] = {(void*)&d_pics, &a_n, &a_h, &segs, &rpw};
   hipError_t e = hipLaunchKernel(reinterpret_cast<const void*>(k_residual), dim3((unsigned)groups), dim3(R_WAVES * 64), args, R_TABLES + R_WAVES * R_WAVE, s);
   if (e != hipSuccess) return hm_check_hip(e, "k_residual launch");
   return hm_check_hip(hipGetLastError(), "k_residual launch");

@@ -94,6 +94,9 @@ static const char* validate_stream(const uint8_t* blob, size_t size)
         }
         const uint64_t first = pass == 0 ? c.tu_first : c.tu_first_c, count = pass == 0 ? c.tu_count : c.tu_count_c;
         if (first != next) return "records of the CTBs are not contiguous in (row, list, CTB) order";
+        // (split chains: every CTB has records in each of its lists - k_residual counts the CTBs of a chunk by their first records and
+        //  passes from a row to the row below behind the row's last chunk)
+        if (split && count == 0 && (pass == 0 || h.chroma_format != 0)) return "a CTB without records in one of its lists";
         next += count;
         if (next > h.n_tus) return "record range of a CTB";
         if (split && (pass == 0 ? c.coeff_first : c.coeff_first_c) != level_at) return "level index of a CTB's first record";

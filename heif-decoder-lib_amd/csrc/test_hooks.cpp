@@ -7,10 +7,14 @@
 // production library cannot shorten a chain wave's wait bound or make batches refuse a width.
 #include <hip/hip_runtime.h>
 
+#include <cstring>
+
 #include "hm_internal.h"
+#include "residual_tables.h"
 
 extern "C" const void* hm_chain_kernel_of(int log2_ctb, int bytes_per_sample, int mode); // chain.hip
 extern "C" const void* hm_residual_kernel();                                             // residual.hip
+extern "C" int hm_residual_tables_read(void* out);                                       // ... the table image in the current device's memory
 extern "C" const void* hm_tail420_kernel();                                              // filters.hip
 extern "C" const void* hm_tail420_kernel16();
 extern "C" const void* hm_resample_kernel_of(int index);                                    // resample.hip: NULL behind the last instance
@@ -37,6 +41,21 @@ __attribute__((visibility("default"))) int hm_debug_kernel_regs(int which, int a
   out[0] = fa.numRegs;
   out[1] = (int)fa.localSizeBytes;
   return 0;
+}
+
+// k_residual's constant tables (residual_tables.h), HM_RT_BYTES bytes into `out`: from_device = 0 the image as the host compiler
+// worked it out (no HIP call: tests/test_residual_tables.py runs without a GPU), 1 the bytes the kernel reads on the current device
+// -> the size, or < 0
+__attribute__((visibility("default"))) int hm_debug_residual_tables(int from_device, uint8_t* out, int capacity)
+{
+  if (!out || capacity < HM_RT_BYTES) return -1;
+  if (from_device) {
+    const int rc = hm_residual_tables_read(out);
+    return rc < 0 ? rc : HM_RT_BYTES;
+  }
+  static constexpr hm_residual_tables image = hm_make_residual_tables();
+  std::memcpy(out, image.b, HM_RT_BYTES);
+  return HM_RT_BYTES;
 }
 
 } // extern "C"
