@@ -240,6 +240,16 @@ def bind_image(L):
     L.hm_decode_frames_to_device_planes.argtypes = [C.c_void_p, C.POINTER(C.c_uint32), C.c_int32, C.POINTER(DecodeParams), C.POINTER(DevicePlanes),
                                                     C.POINTER(Decoded), C.POINTER(C.c_int32)]
     L.hm_pipeline_submit_to_device_planes.argtypes = [C.c_void_p, C.c_char_p, C.c_size_t, C.c_uint32, C.c_uint64, C.POINTER(DevicePlanes)]
+    L.hm_planes_view_geometry.argtypes = [C.c_int, C.c_int, C.c_int, C.POINTER(DeviceView), C.POINTER(C.c_int32 * 4 * 4), C.POINTER(C.c_int32 * 2 * 4)]
+    L.hm_decode_item_to_device_planes_view.argtypes = [C.c_void_p, C.c_uint32, C.POINTER(DecodeParams), C.POINTER(DeviceView), C.POINTER(DevicePlanes),
+                                                       C.POINTER(Decoded)]
+    L.hm_decode_frames_to_device_planes_view.argtypes = [C.c_void_p, C.POINTER(C.c_uint32), C.c_int32, C.POINTER(DecodeParams), C.POINTER(DeviceView),
+                                                         C.POINTER(DevicePlanes), C.POINTER(Decoded), C.POINTER(C.c_int32)]
+    L.hm_pipeline_submit_to_device_planes_view.argtypes = [C.c_void_p, C.c_char_p, C.c_size_t, C.c_uint32, C.c_uint64, C.POINTER(DeviceView),
+                                                           C.POINTER(DevicePlanes)]
+    L.hm_resample_planes_to_tensor.argtypes = [C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, C.POINTER(C.c_void_p * 4), C.POINTER(C.c_int32 * 4),
+                                               C.POINTER(DeviceView), C.POINTER(DevicePlanes), C.c_void_p]
+    L.hm_plan_planes_view.argtypes = [C.c_void_p, C.c_uint32, C.POINTER(DecodeParams), C.POINTER(DeviceView), C.POINTER(C.c_int32 * 4)]
     L.hm_pipeline_pending.argtypes = [C.c_void_p]
     L.hm_pipeline_next.argtypes = [C.c_void_p, C.POINTER(PipelineResult)]
     L.hm_pipeline_release.argtypes = [C.c_void_p, C.POINTER(PipelineResult)]

@@ -2,6 +2,7 @@
 // stage's interleaved pixels into it (a 2-D device copy for HWC with the target's own integer type, k_to_tensor otherwise).
 // Planar YCbCr (hm_device_planes): the arithmetic and the refusals, and the step that writes the decoded planes (kernel: planes.hip).
 // Views (hm_device_view): the refusals, the tap tables and the step that writes a resampled rectangle (kernels: resample.hip).
+// Planar views (a view into hm_device_planes): the geometry per plane, the refusals and the write step (kernels: planes_view.hip).
 #include <algorithm>
 #include <cmath>
 #include <cstdio>
@@ -12,6 +13,7 @@
 
 #include "hm_colour_plan.h"
 #include "hm_devdest.h"
+#include "hm_planes_view.h"
 #include "hm_view_batch.h"
 
 extern "C" {
@@ -610,6 +612,261 @@ int hm_resample_to_tensor(int out_format, int src_w, int src_h, const void* d_sr
   hm_view_scratch* sc = new (std::nothrow) hm_view_scratch();
   if (!sc) return hm_fail(HM_ERR_NOMEM, "out of memory");
   rc = hm_view_write(dest, out_format, &vp, d_src, src_stride, (hipStream_t)stream, sc);
+  if (!sc->dev[0] && !sc->dev[1] && !sc->pinned) { delete sc; return rc; }
+  if (hipLaunchHostFunc((hipStream_t)stream, scratch_done, sc) != hipSuccess) { // (never on a healthy runtime: wait, then release here)
+    (void)hipGetLastError();
+    hipStreamSynchronize((hipStream_t)stream);
+    hm_view_scratch_free(sc);
+    delete sc;
+  }
+  return rc;
+}
+
+// ---- planar views: every plane an image of its own ------------------------------------------------------------------------------
+
+int hm_planes_view_resolve(int chroma, int w, int h, const hm_device_view* v, hm_planes_view_plan* pv)
+{
+  if (!v || !pv) return hm_fail(HM_ERR_INVALID_ARG, "null view");
+  std::memset(pv, 0, sizeof(*pv));
+  if (chroma < HM_CHROMA_MONO || chroma > HM_CHROMA_444) return hm_fail(HM_ERR_INVALID_ARG, "planar view: chroma format %d", chroma);
+  if (w <= 0 || h <= 0 || w > 32768 || h > 32768) return hm_fail(HM_ERR_INVALID_ARG, "planar view: image size %d x %d", w, h);
+  hm_view_plan vp; // the luma rectangle: hm_device_view's own refusals (no target is big-endian here)
+  int rc = hm_view_resolve(0, w, h, v, &vp);
+  if (rc) return rc;
+  const int bad = hm_pv_geometry(chroma, vp.x, vp.y, vp.w, vp.h, vp.ow, vp.oh, pv->crop, pv->out);
+  if (bad == 1) return hm_fail(HM_ERR_INVALID_ARG, "planar view: crop_x %d is odd, the chroma planes of a 4:2:%d result have half the columns", vp.x, chroma == HM_CHROMA_420 ? 0 : 2);
+  if (bad == 2) return hm_fail(HM_ERR_INVALID_ARG, "planar view: crop_y %d is odd, the chroma planes of a 4:2:0 result have half the rows", vp.y);
+  pv->ow = vp.ow; pv->oh = vp.oh; pv->filter = vp.filter; pv->crop_only = vp.crop_only;
+  if (chroma != HM_CHROMA_MONO) // the reduction limit holds per plane and axis (a chroma axis 255 -> 1 of a luma axis 509 -> 1 ...)
+    if ((rc = check_axis(pv->crop[1][2], pv->out[1][0], pv->filter, "chroma width")) || (rc = check_axis(pv->crop[1][3], pv->out[1][1], pv->filter, "chroma height"))) return rc;
+  return HM_OK;
+}
+
+int hm_planes_view_geometry(int chroma, int width, int height, const hm_device_view* view, int32_t crop[4][4], int32_t out[4][2])
+{
+  if (!view || !crop || !out) return hm_fail(HM_ERR_INVALID_ARG, "null argument");
+  hm_planes_view_plan pv;
+  const int rc = hm_planes_view_resolve(chroma, width, height, view, &pv);
+  if (rc) return rc;
+  std::memcpy(crop, pv.crop, sizeof(pv.crop));
+  std::memcpy(out, pv.out, sizeof(pv.out));
+  return HM_OK;
+}
+
+namespace {
+
+// a frame of a planar view write against its destination: the plan of an ow x oh result, len and overlap, the pointers, the sources
+int planes_view_check(const hm_planes_view_item& f, hm_planes_plan* p)
+{
+  int rc = hm_planes_resolve(f.chroma, f.bits, f.pv.ow, f.pv.oh, f.alpha_bits, f.planes, p);
+  if (!rc) rc = hm_planes_check_len(f.planes, p);
+  if (!rc) rc = hm_planes_check_pointer(f.planes, p);
+  if (rc) return rc;
+  const bool semi = p->layout == HM_DEV_PLANES_SEMI;
+  for (int c = 0; c < 4; c++) {
+    const bool need = c == 0 || (c == 3 ? p->pl[3].present != 0 : f.chroma != HM_CHROMA_MONO);
+    if (!need) continue;
+    const int sb = (c == 3 ? p->alpha_bits : f.bits) > 8 ? 2 : 1;
+    if (!f.src[c]) return hm_fail(HM_ERR_INVALID_ARG, "device planes: source plane %d is null", c);
+    if ((int64_t)f.stride[c] < ((int64_t)f.pv.crop[c][0] + f.pv.crop[c][2]) * sb) return hm_fail(HM_ERR_INVALID_ARG, "device planes: source stride %d of plane %d below the bytes of a row", f.stride[c], c);
+    if (sb == 2 && (((uintptr_t)f.src[c] | (unsigned)f.stride[c]) & 1)) return hm_fail(HM_ERR_INVALID_ARG, "16-bit samples at an odd address or stride");
+    // (the geometry gives every plane the size hm_planes_resolve gives it: the kernels store pv.out, the checks cover p->pl)
+    const int dc = semi && c == 2 ? 1 : c;
+    if (p->pl[dc].width != f.pv.out[c][0] || p->pl[dc].height != f.pv.out[c][1])
+      return hm_fail(HM_ERR_INTERNAL, "planar view: plane %d is %d x %d, the destination's %d x %d", c, f.pv.out[c][0], f.pv.out[c][1], p->pl[dc].width, p->pl[dc].height);
+  }
+  return HM_OK;
+}
+
+const uint8_t* plane_origin(const hm_planes_view_item& f, int c, int sb)
+{
+  return (const uint8_t*)f.src[c] + (size_t)f.pv.crop[c][1] * f.stride[c] + (size_t)f.pv.crop[c][0] * sb;
+}
+
+// one group: frames idx[0 .. m) of `it` share the plan p and everything else of the key
+int planes_view_group(const hm_planes_view_item* it, const int* idx, int m, const hm_planes_plan& p, hipStream_t s, hm_view_scratch* sc)
+{
+  const hm_planes_view_item& f0 = it[idx[0]];
+  const hm_planes_view_plan& pv = f0.pv;
+  const hm_device_planes* d0 = f0.planes;
+  const bool semi = p.layout == HM_DEV_PLANES_SEMI, nearest = pv.filter == HM_VIEW_NEAREST;
+  const int present[4] = {1, p.chroma != HM_CHROMA_MONO, p.chroma != HM_CHROMA_MONO, p.pl[3].present};
+  int sb[4];
+  for (int c = 0; c < 4; c++) sb[c] = (c == 3 ? p.alpha_bits : p.bits) > 8 ? 2 : 1;
+  // the tap tables: one per distinct (n -> m) axis - luma x, luma y, chroma x, chroma y at the most (alpha has luma's)
+  struct Axis { int n, m, taps; size_t at; };
+  std::vector<Axis> axes;
+  int ax[4] = {0, 0, 0, 0}, ay[4] = {0, 0, 0, 0}, rc;
+  size_t words = 0;
+  auto axis_of = [&](int n, int mm) -> int {
+    for (size_t a = 0; a < axes.size(); a++)
+      if (axes[a].n == n && axes[a].m == mm) return (int)a;
+    int taps = 0, f;
+    for (int j = 0; j < mm; j++) { const int cnt = axis_taps(n, mm, pv.filter, j, &f, nullptr); if (cnt < 0) return cnt; taps = std::max(taps, cnt); }
+    axes.push_back({n, mm, taps, words});
+    words += (size_t)mm * (2 + taps);
+    return (int)axes.size() - 1;
+  };
+  if (!nearest)
+    for (int c = 0; c < 4; c++) {
+      if (!present[c]) continue;
+      if ((ax[c] = axis_of(pv.crop[c][2], pv.out[c][0])) < 0) return ax[c];
+      if ((ay[c] = axis_of(pv.crop[c][3], pv.out[c][1])) < 0) return ay[c];
+    }
+  // ONE pinned block and one upload: the tables, then the frames' pointer records
+  const hm_pv_block lay = hm_pv_block_layout((int64_t)words, m);
+  uint8_t* host = (uint8_t*)hm_pool_pinned_alloc((size_t)lay.bytes);
+  if (!host) return hm_fail(HM_ERR_NOMEM, "out of memory");
+  sc->pinned = host;
+  float w[HM_VIEW_MAX_TAPS + 2];
+  for (const Axis& a : axes) {
+    int32_t* base = reinterpret_cast<int32_t*>(host) + a.at;
+    float* wt = reinterpret_cast<float*>(base + 2 * (size_t)a.m);
+    for (int j = 0; j < a.m; j++) {
+      const int cnt = axis_taps(a.n, a.m, pv.filter, j, &base[j], w);
+      base[a.m + j] = cnt;
+      for (int i = 0; i < a.taps; i++) wt[(size_t)i * a.m + j] = i < cnt ? w[i] : 0.0f;
+    }
+  }
+  hm_pv_rec* recs = reinterpret_cast<hm_pv_rec*>(host + lay.rec_off);
+  for (int i = 0; i < m; i++) {
+    const hm_planes_view_item& f = it[idx[i]];
+    std::memset(&recs[i], 0, sizeof(recs[i]));
+    for (int c = 0; c < 4; c++) {
+      if (present[c]) recs[i].src[c] = (uint64_t)(uintptr_t)plane_origin(f, c, sb[c]);
+      if (p.pl[c].present) recs[i].dst[c] = (uint64_t)(uintptr_t)f.planes->plane[c].ptr;
+    }
+  }
+  // the intermediate of one chunk of frames, reused chunk after chunk in stream order
+  int64_t off[4], pitch[4];
+  const int64_t frame_stride = hm_pv_tmp_layout(pv.crop, pv.out, present, off, pitch);
+  const int per_chunk = (int)std::min<int64_t>(m, nearest ? HM_PV_Z_MOST : hm_pv_chunk_frames(frame_stride, hm_knob(HM_KNOB_VIEW_BATCH_BYTES)));
+  if (!(sc->dev[0] = hm_pool_device_alloc((size_t)lay.bytes))) return HM_ERR_NO_DEVICE;
+  if (!nearest && !(sc->dev[1] = hm_pool_device_alloc((size_t)frame_stride * per_chunk * sizeof(float)))) return HM_ERR_NO_DEVICE;
+  if ((rc = hm_check_hip(hipMemcpyAsync(sc->dev[0], host, (size_t)lay.bytes, hipMemcpyHostToDevice, s), "upload of the tap tables"))) return rc;
+  const int32_t* dtab = (const int32_t*)sc->dev[0];
+  const hm_pv_rec* drecs = reinterpret_cast<const hm_pv_rec*>((const uint8_t*)sc->dev[0] + lay.rec_off);
+  auto axis_at = [&](int a) {
+    hm_pv_axis t;
+    const int32_t* base = dtab + axes[(size_t)a].at;
+    t.first = base; t.count = base + axes[(size_t)a].m; t.weights = reinterpret_cast<const float*>(base + 2 * (size_t)axes[(size_t)a].m);
+    return t;
+  };
+  hm_pv_h_args ha;
+  hm_pv_v_args va;
+  std::memset(&ha, 0, sizeof(ha));
+  std::memset(&va, 0, sizeof(va));
+  int h_end = 0, v_end = 0;
+  for (int c = 0; c < 4; c++) {
+    if (present[c] && !nearest) {
+      hm_pv_src_desc& sd = ha.pl[c];
+      sd.ax = axis_at(ax[c]);
+      sd.tmp_off = off[c]; sd.tmp_pitch = pitch[c];
+      sd.stride = f0.stride[c]; sd.n_h = pv.crop[c][3]; sd.ow = pv.out[c][0]; sd.sample_bytes = sb[c];
+      h_end += (sd.n_h + 3) / 4;
+    }
+    ha.y_end[c] = h_end;
+    if (p.pl[c].present) {
+      hm_pv_dst_desc& dd = va.pl[c];
+      const bool pair = semi && c == 1;
+      if (!nearest) dd.ay = axis_at(ay[c]);
+      dd.pitch = p.pl[c].pitch;
+      dd.tmp_off0 = off[c]; dd.tmp_off1 = pair ? off[2] : 0; dd.tmp_pitch = pitch[c];
+      dd.w = pv.out[c][0]; dd.oh = pv.out[c][1];
+      dd.pair = pair ? 1 : 0; dd.vec = p.pl[c].vec;
+      const int sbits = c == 3 ? p.alpha_bits : p.bits;
+      dd.peak = (1 << sbits) - 1; dd.shift = d0->msb_aligned ? 16 - sbits : 0;
+      dd.n_w = pv.crop[c][2]; dd.n_h = pv.crop[c][3]; dd.stride0 = f0.stride[c]; dd.stride1 = pair ? f0.stride[2] : 0; dd.sample_bytes = sb[c];
+      dd.scale0 = d0->scale[c]; dd.bias0 = d0->bias[c];
+      if (pair) { dd.scale1 = d0->scale[2]; dd.bias1 = d0->bias[2]; }
+      v_end += (dd.oh + 3) / 4;
+    }
+    va.y_end[c] = v_end;
+  }
+  ha.tmp = (float*)sc->dev[1]; va.tmp = (const float*)sc->dev[1];
+  ha.frame_stride = va.frame_stride = frame_stride;
+  for (int c0 = 0; c0 < m; c0 += per_chunk) {
+    const int frames = std::min(per_chunk, m - c0);
+    ha.recs = va.recs = drecs + c0;
+    if ((rc = nearest ? hm_launch_planes_view_nearest(&va, p.dtype, frames, s) : hm_launch_planes_resample(&ha, &va, sb[0], p.dtype, frames, s))) return rc;
+  }
+  return HM_OK;
+}
+
+} // namespace
+
+int hm_planes_view_write(hm_planes_view_item* it, int n, hipStream_t s, hm_view_scratch* sc, int* failed)
+{
+  if (failed) *failed = -1;
+  if (n <= 0) return HM_OK;
+  std::vector<hm_planes_plan> plans((size_t)n);
+  for (int k = 0; k < n; k++) { // every destination and source, before anything is queued
+    const int rc = planes_view_check(it[k], &plans[k]);
+    if (rc) { if (failed) *failed = k; return rc; }
+    for (int c = 0; c < 4; c++) it[k].pitches[c] = plans[k].pl[c].present ? plans[k].pl[c].pitch : 0;
+  }
+  std::vector<hm_pv_key> keys;
+  std::vector<std::vector<int>> members;
+  for (int k = 0; k < n; k++) {
+    const hm_planes_view_item& f = it[k];
+    const hm_planes_plan& p = plans[k];
+    if (f.pv.crop_only) { // the samples of the rectangles: k_planes_to_tensor on the offset source planes, no intermediate
+      const void* src[4] = {nullptr, nullptr, nullptr, nullptr};
+      for (int c = 0; c < 4; c++) {
+        const bool need = c == 0 || (c == 3 ? p.pl[3].present != 0 : f.chroma != HM_CHROMA_MONO);
+        if (need) src[c] = plane_origin(f, c, (c == 3 ? p.alpha_bits : f.bits) > 8 ? 2 : 1);
+      }
+      const int rc = hm_planes_write(f.planes, f.chroma, f.bits, f.pv.ow, f.pv.oh, p.alpha_bits, src, f.stride, s, nullptr);
+      if (rc) { if (failed) *failed = k; return rc; }
+      continue;
+    }
+    hm_pv_key key;
+    std::memset(&key, 0, sizeof(key));
+    key.chroma = p.chroma; key.bits = p.bits; key.alpha_bits = p.alpha_bits; key.filter = f.pv.filter;
+    key.layout = p.layout; key.dtype = p.dtype; key.msb_aligned = f.planes->msb_aligned;
+    std::memcpy(key.crop, f.pv.crop, sizeof(key.crop));
+    std::memcpy(key.out, f.pv.out, sizeof(key.out));
+    for (int c = 0; c < 4; c++) {
+      const bool need = c == 0 || (c == 3 ? p.pl[3].present != 0 : f.chroma != HM_CHROMA_MONO);
+      key.stride[c] = need ? f.stride[c] : 0;
+      if (!p.pl[c].present) continue;
+      key.pitch[c] = p.pl[c].pitch;
+      key.vec[c] = hm_pv_vec_class((uintptr_t)f.planes->plane[c].ptr, p.pl[c].pitch);
+    }
+    std::memcpy(key.scale, f.planes->scale, 16);
+    std::memcpy(key.bias, f.planes->bias, 16);
+    size_t g = 0;
+    while (g < keys.size() && !hm_pv_key_equal(&keys[g], &key)) g++;
+    if (g == keys.size()) { keys.push_back(key); members.emplace_back(); }
+    members[g].push_back(k);
+  }
+  for (const std::vector<int>& m : members) { // (a group's blocks hang on the scratch entry of its first frame: unused otherwise)
+    const int rc = planes_view_group(it, m.data(), (int)m.size(), plans[(size_t)m[0]], s, &sc[m[0]]);
+    if (rc) { if (failed) *failed = m[0]; return rc; }
+  }
+  return HM_OK;
+}
+
+int hm_resample_planes_to_tensor(int chroma, int bits, int width, int height, int alpha_bits, const void* const d_src[4], const int32_t src_stride[4],
+                                 const hm_device_view* view, const hm_device_planes* planes, void* stream)
+{
+  if (!d_src || !src_stride || !view || !planes) return hm_fail(HM_ERR_INVALID_ARG, "null argument");
+  if (alpha_bits < 0) return hm_fail(HM_ERR_INVALID_ARG, "device planes: alpha bit depth %d", alpha_bits);
+  hm_planes_view_item f;
+  std::memset(&f, 0, sizeof(f));
+  int rc = hm_planes_check_static(planes);
+  if (!rc) rc = hm_planes_view_resolve(chroma, width, height, view, &f.pv);
+  if (rc) return rc;
+  hm_planes_plan p;
+  if ((rc = hm_planes_resolve(chroma, bits, f.pv.ow, f.pv.oh, alpha_bits, planes, &p)) || (rc = hm_planes_check_len(planes, &p))) return rc;
+  int n_dev = 0;
+  if (hipGetDeviceCount(&n_dev) != hipSuccess || n_dev == 0) { (void)hipGetLastError(); return hm_fail(HM_ERR_NO_DEVICE, "no HIP device available"); }
+  f.planes = planes; f.chroma = chroma; f.bits = bits; f.alpha_bits = alpha_bits;
+  for (int c = 0; c < 4; c++) { f.src[c] = d_src[c]; f.stride[c] = src_stride[c]; }
+  release_done();
+  hm_view_scratch* sc = new (std::nothrow) hm_view_scratch();
+  if (!sc) return hm_fail(HM_ERR_NOMEM, "out of memory");
+  rc = hm_planes_view_write(&f, 1, (hipStream_t)stream, sc, nullptr);
   if (!sc->dev[0] && !sc->dev[1] && !sc->pinned) { delete sc; return rc; }
   if (hipLaunchHostFunc((hipStream_t)stream, scratch_done, sc) != hipSuccess) { // (never on a healthy runtime: wait, then release here)
     (void)hipGetLastError();

@@ -128,6 +128,65 @@ int hm_launch_resample_batch(const hm_dest_plan* p, const hm_resample_args* a, c
 int hm_launch_view_nearest(const hm_dest_plan* p, const void* src, int src_stride, int n_w, int n_h, int ow, int oh, void* dst, const float scale[4],
                            const float bias[4], hipStream_t s);
 
+// ---- planar views: a view (hm_device_view) into planar YCbCr (hm_device_planes), every plane an image of its own.  devdest.cpp
+//      holds the checks and the write step, hm_planes_view.h the index arithmetic, planes_view.hip the kernels ----
+typedef struct hm_planes_view_plan {
+  int32_t crop[4][4], out[4][2]; // per plane (0 Y, 1 Cb, 2 Cr, 3 alpha): the crop x, y, w, h inside that plane and the size written
+  int32_t ow, oh;                // the luma size written: what the destination is checked against
+  int32_t filter, crop_only;
+} hm_planes_view_plan;
+// the view against a w x h result of this chroma format: every refusal of the view itself (crop, origin, filter, reduction per plane and axis)
+int hm_planes_view_resolve(int chroma, int w, int h, const hm_device_view* v, hm_planes_view_plan* pv);
+// one frame of a planar view write: the source planes (row 0 = image row 0) of a result of (chroma, bits, alpha_bits), the view
+// resolved against it, the destination; pitches: filled with the pitches in use
+typedef struct hm_planes_view_item {
+  const hm_device_planes* planes;
+  hm_planes_view_plan pv;
+  int32_t chroma, bits, alpha_bits;
+  const void* src[4]; int32_t stride[4];
+  int64_t pitches[4];
+} hm_planes_view_item;
+// n >= 1 frames.  Frames that agree in the key of hm_planes_view.h form a group: the tap tables of its at most four distinct axes and
+// the frames' pointer records in ONE pinned block and one upload, one bounded float32 intermediate, and per chunk of frames one
+// launch per pass.  The crop alone is hm_planes_write on offset source pointers, frame by frame.  Every destination and source is
+// checked before anything is queued (*failed, may be NULL: the index of the frame that was refused).  sc: n zeroed entries.
+int hm_planes_view_write(hm_planes_view_item* items, int n, hipStream_t s, hm_view_scratch* sc, int* failed);
+
+// one axis' taps of one plane (device pointers): first[m], count[m], weights[taps][m]
+typedef struct hm_pv_axis { const int32_t* first; const int32_t* count; const float* weights; } hm_pv_axis;
+// a SOURCE plane of the horizontal pass
+typedef struct hm_pv_src_desc {
+  hm_pv_axis ax;
+  long long tmp_off, tmp_pitch;  // its region of a frame's intermediate (elements)
+  int32_t stride, n_h, ow;       // bytes between source rows, rows of the crop (0: the plane is absent), columns written
+  int32_t sample_bytes;
+} hm_pv_src_desc;
+typedef struct hm_pv_h_args {
+  hm_pv_src_desc pl[4];
+  int32_t y_end[4];              // running sums of (n_h + 3) / 4
+  const void* recs;              // hm_pv_rec[frames of the chunk]
+  float* tmp; long long frame_stride;
+} hm_pv_h_args;
+// a DESTINATION plane of the vertical pass and of the nearest kernel; pair: the interleaved CbCr plane (0 = Cb, 1 = Cr)
+typedef struct hm_pv_dst_desc {
+  hm_pv_axis ay;
+  long long pitch;               // bytes between destination rows
+  long long tmp_off0, tmp_off1, tmp_pitch;
+  int32_t w, oh;                 // elements (pairs) of a row, rows (0: the plane is absent)
+  int32_t pair, vec, peak, shift;
+  int32_t n_w, n_h, stride0, stride1, sample_bytes; // the nearest kernel: the source crop
+  float scale0, bias0, scale1, bias1;
+} hm_pv_dst_desc;
+typedef struct hm_pv_v_args {
+  hm_pv_dst_desc pl[4];
+  int32_t y_end[4];              // running sums of (oh + 3) / 4
+  const void* recs;
+  const float* tmp; long long frame_stride;
+} hm_pv_v_args;
+// both passes over `frames` frames (grid z); sample_bytes: of the image's own planes (the template instance)
+int hm_launch_planes_resample(const hm_pv_h_args* h, const hm_pv_v_args* v, int sample_bytes, int dtype, int frames, hipStream_t s);
+int hm_launch_planes_view_nearest(const hm_pv_v_args* v, int dtype, int frames, hipStream_t s);
+
 #ifdef __cplusplus
 }
 #endif

@@ -646,7 +646,11 @@ namespace hm_img {
 // subsampled direction (an odd one moves a column / row further out).  t = first tile row, row count, first tile column, column count;
 // origin and size of the sub-grid's canvas in x0, y0, w, h.  false: the whole item is decoded (t = the whole grid).
 // Item properties only: no coded picture is looked at.
-bool view_subgrid(const hm_file* f, uint32_t id, const hm_decode_params* params, const hm_device_view* v, int32_t t[4], int* x0, int* y0, int* w, int* h)
+// planes_view: the view goes to planar YCbCr (hm_device_planes).  Then the reduction covers out_format 0 alone, the picture as coded -
+// a grid's planes are its tiles' planes side by side, so the sub-grid's planes are the rectangle of the whole grid's -, and the
+// HM_OUT_YCBCR_* chains, whose up- and down-sampling operations read neighbours across tile borders, decode the whole item.
+bool view_subgrid(const hm_file* f, uint32_t id, const hm_decode_params* params, const hm_device_view* v, int32_t t[4], int* x0, int* y0, int* w, int* h,
+                  bool planes_view = false)
 {
   t[0] = 0; t[1] = 1; t[2] = 0; t[3] = 1;
   const hm::Item* it = f->file.item(id);
@@ -656,7 +660,7 @@ bool view_subgrid(const hm_file* f, uint32_t id, const hm_decode_params* params,
   if (!f->file.grid_info(id, g, err) || g.rows < 1 || g.cols < 1 || g.tiles.size() != (size_t)g.rows * g.cols) return false;
   t[1] = g.rows; t[3] = g.cols;
   if (!v || (v->crop_w == 0 && v->crop_h == 0)) return false;
-  if (params->chroma_upsampling != 0 || hm_out_is_planar(params->out_format) || params->out_format == 0) return false;
+  if (planes_view ? params->out_format != 0 : (params->chroma_upsampling != 0 || hm_out_is_planar(params->out_format) || params->out_format == 0)) return false;
   if (!params->ignore_transformations && !it->props.transforms.empty()) return false;
   if (f->file.alpha_item_of(id)) return false;
   const int gw = (int)g.width, gh = (int)g.height;
@@ -690,7 +694,7 @@ int job_plan(DecodeJob& j)
   j.view_dx = j.view_dy = 0;
   j.sub_tiles[0] = 0; j.sub_tiles[1] = j.item[0].rows; j.sub_tiles[2] = 0; j.sub_tiles[3] = j.item[0].cols;
   int sx = 0, sy = 0, sw = 0, sh = 0;
-  if (j.has_view && view_subgrid(j.f, j.id, &j.params, &j.view, j.sub_tiles, &sx, &sy, &sw, &sh)) {
+  if (j.has_view && view_subgrid(j.f, j.id, &j.params, &j.view, j.sub_tiles, &sx, &sy, &sw, &sh, j.has_planes)) {
     // the sub-grid becomes a grid of its own (what a slab is for tile rows): everything behind sees an ordinary smaller grid
     ItemPlan& P = j.item[0];
     const int32_t* t = j.sub_tiles;
@@ -755,10 +759,12 @@ void parse_picture(const hm_file* f, uint32_t id, bool few_pictures, int strict,
 // dest (may be NULL): caller-owned device memory the interleaved pixels go to instead (hm_device_dest); nothing is copied to the host then.
 // view_later (may be NULL, with view): the view is not written here, only described there - the caller writes it with those of other images.
 // planes (may be NULL; a planar result only): caller-owned device memory the planes go to instead (hm_device_planes), one launch of
-// k_planes_to_tensor in place of the pinned allocations and the copies to the host.
+// k_planes_to_tensor in place of the pinned allocations and the copies to the host.  With view: the view of every plane of the
+// result (hm_planes_view_write), written here or - planes_later - only described there for the caller's grouped write.
 int emit_image(const hm_decode_params* params, hipStream_t s, PlanarImage& I, const DevPlane* alpha, int alpha_bd, DevMem& dout,
                DevPlane& alpha_sdr, hm_decoded* out, const hm_device_dest* dest = nullptr, const hm_device_view* view = nullptr,
-               hm_view_scratch* view_scratch = nullptr, hm_view_item* view_later = nullptr, const hm_device_planes* planes = nullptr)
+               hm_view_scratch* view_scratch = nullptr, hm_view_item* view_later = nullptr, const hm_device_planes* planes = nullptr,
+               hm_planes_view_item* planes_later = nullptr)
 {
   int rc;
   DevPlane (&P)[3] = I.P;
@@ -788,8 +794,28 @@ int emit_image(const hm_decode_params* params, hipStream_t s, PlanarImage& I, co
   // the planes of a planar result into the caller's device memory (checked against the result's own format before the launch)
   auto write_planes = [&](int rchroma, int rbits, const void* const src[4], const int32_t stride[4], int abits) {
     int64_t pitch[4];
-    const int wrc = hm_planes_write(planes, rchroma, rbits, img_w, img_h, abits, src, stride, s, pitch);
-    if (wrc) return wrc;
+    if (view) { // (the entry points have resolved the view against the size the file declares: here it is the decoded result)
+      hm_planes_view_item item;
+      std::memset(&item, 0, sizeof(item));
+      int vrc = hm_planes_view_resolve(rchroma, img_w, img_h, view, &item.pv);
+      if (vrc) return vrc;
+      item.planes = planes; item.chroma = rchroma; item.bits = rbits; item.alpha_bits = abits;
+      for (int c = 0; c < 4; c++) { item.src[c] = src[c]; item.stride[c] = stride[c]; }
+      if (planes_later) { // the caller's grouped write checks everything again; the pitches in use are known here
+        hm_planes_plan pp;
+        if ((vrc = hm_planes_resolve(rchroma, rbits, item.pv.ow, item.pv.oh, abits, planes, &pp)) || (vrc = hm_planes_check_len(planes, &pp))) return vrc;
+        for (int c = 0; c < 4; c++) item.pitches[c] = pp.pl[c].present ? pp.pl[c].pitch : 0;
+        *planes_later = item;
+      }
+      else if ((vrc = hm_planes_view_write(&item, 1, s, view_scratch, nullptr))) return vrc;
+      for (int c = 0; c < 4; c++) pitch[c] = item.pitches[c];
+      out->width = item.pv.ow; out->height = item.pv.oh;
+      for (int c = 0; c < 3; c++) { out->plane_width[c] = item.pv.out[c][0]; out->plane_height[c] = item.pv.out[c][1]; }
+    }
+    else {
+      const int wrc = hm_planes_write(planes, rchroma, rbits, img_w, img_h, abits, src, stride, s, pitch);
+      if (wrc) return wrc;
+    }
     out->used_ext_dst = 1;
     for (int c = 0; c < 3; c++) out->stride[c] = (int32_t)std::min<int64_t>(pitch[c], 0x7FFFFFFF);
     out->alpha_stride = (int32_t)std::min<int64_t>(pitch[3], 0x7FFFFFFF);
@@ -1045,7 +1071,7 @@ static void planar_result_format(const hm_decode_params* params, int chroma, int
   *rbits = !as_decoded && params->convert_hdr_to_8bit ? 8 : bd;
 }
 
-int check_planes_request(const hm_file* f, uint32_t id, const hm_decode_params* params, const hm_device_planes* planes)
+int check_planes_request(const hm_file* f, uint32_t id, const hm_decode_params* params, const hm_device_planes* planes, const hm_device_view* view)
 {
   int rc = check_planes_params(params, planes);
   if (rc) return rc;
@@ -1057,8 +1083,11 @@ int check_planes_request(const hm_file* f, uint32_t id, const hm_decode_params* 
     if (w > 0 && h > 0 && info.bit_depth >= 8 && info.bit_depth <= 16 && info.chroma >= 0 && info.chroma <= 3) {
       int rchroma, rbits;
       planar_result_format(params, info.chroma, info.bit_depth, &rchroma, &rbits);
+      hm_planes_view_plan pv; // view: the planes are judged against its output size, the crop against the declared size
+      pv.ow = w; pv.oh = h;
+      if (view && (rc = hm_planes_view_resolve(rchroma, w, h, view, &pv))) return rc;
       // (whether there is an alpha plane, and of which depth, is the decode's to say: -1)
-      if ((rc = hm_planes_resolve(rchroma, rbits, w, h, -1, planes, &pp)) || (rc = hm_planes_check_len(planes, &pp))) return rc;
+      if ((rc = hm_planes_resolve(rchroma, rbits, pv.ow, pv.oh, -1, planes, &pp)) || (rc = hm_planes_check_len(planes, &pp))) return rc;
       planned = true;
     }
   }
@@ -1121,6 +1150,25 @@ int hm_decode_item_to_device_planes(const hm_file* f, uint32_t id, const hm_deco
   const int rc = check_planes_request(f, id, params, planes); // refused before any work is queued: no plane is written
   if (rc) return rc;
   return decode_item(f, id, params, nullptr, out, nullptr, planes);
+}
+
+int hm_decode_item_to_device_planes_view(const hm_file* f, uint32_t id, const hm_decode_params* params, const hm_device_view* view, const hm_device_planes* planes,
+                                         hm_decoded* out)
+{
+  if (!f || !params || !view || !planes || !out) return hm_fail(HM_ERR_INVALID_ARG, "null argument");
+  std::memset(out, 0, sizeof(*out));
+  const int rc = check_planes_request(f, id, params, planes, view); // refused before any work is queued: no plane is written
+  if (rc) return rc;
+  return decode_item(f, id, params, nullptr, out, view, planes);
+}
+
+int hm_plan_planes_view(const hm_file* f, uint32_t id, const hm_decode_params* params, const hm_device_view* view, int32_t tiles[4])
+{
+  if (!f || !params || !view || !tiles) return hm_fail(HM_ERR_INVALID_ARG, "null argument");
+  if (!f->file.item(id)) return hm_fail(HM_ERR_INVALID_ARG, "no item %u", id);
+  int x0, y0, w, h;
+  view_subgrid(f, id, params, view, tiles, &x0, &y0, &w, &h, true);
+  return HM_OK;
 }
 
 int hm_plan_view(const hm_file* f, uint32_t id, const hm_decode_params* params, const hm_device_view* view, int32_t tiles[4])
@@ -1229,6 +1277,14 @@ int hm_file_sequence_info(const hm_file* f, hm_sequence_info* info)
 static int decode_sequence(const hm_file* f, const uint32_t* frames, uint32_t first, int32_t count, const hm_decode_params* params, const hm_frame_dest* dests,
                            const hm_device_dest* ddests, const hm_device_view* view, hm_decoded* out, int32_t* failed_frame, const hm_device_planes* pdests = nullptr);
 
+int hm_decode_frames_to_device_planes_view(const hm_file* f, const uint32_t* frames, int32_t count, const hm_decode_params* params, const hm_device_view* view,
+                                           const hm_device_planes* planes, hm_decoded* out, int32_t* failed_frame)
+{
+  if (failed_frame) *failed_frame = -1;
+  if (!frames || !planes || !view) return hm_fail(HM_ERR_INVALID_ARG, "null argument");
+  return decode_sequence(f, frames, 0, count, params, nullptr, nullptr, view, out, failed_frame, planes);
+}
+
 int hm_decode_sequence(const hm_file* f, uint32_t first, int32_t count, const hm_decode_params* params, const hm_frame_dest* dests,
                        hm_decoded* out, int32_t* failed_frame)
 {
@@ -1261,8 +1317,8 @@ int hm_decode_frames_to_device_planes(const hm_file* f, const uint32_t* frames, 
 
 // frames (NULL: first .. first + count - 1): the 1-based IDs of the frames, in any order, repeats allowed.
 // pdests (NULL, or `count` entries, without ddests): every frame's planar result goes to caller-owned device memory (hm_device_planes)
-// ddests (NULL, or `count` entries): every frame goes to caller-owned device memory; view (NULL, or with ddests): the same rectangle
-// of every frame, resampled, in one batched write behind the frames' conversions (hm_view_write_batch)
+// ddests (NULL, or `count` entries): every frame goes to caller-owned device memory; view (NULL, or with ddests or pdests): the same
+// rectangle of every frame, resampled, in one batched write behind the frames' conversions (hm_view_write_batch, hm_planes_view_write)
 static int decode_sequence(const hm_file* f, const uint32_t* frames, uint32_t first, int32_t count, const hm_decode_params* params, const hm_frame_dest* dests,
                            const hm_device_dest* ddests, const hm_device_view* view, hm_decoded* out, int32_t* failed_frame, const hm_device_planes* pdests)
 {
@@ -1318,7 +1374,10 @@ static int decode_sequence(const hm_file* f, const uint32_t* frames, uint32_t fi
       if (hm_file_image_info(f, frame_id(k), &info) != HM_OK || info.width <= 0 || info.height <= 0 || info.bit_depth < 8 || info.bit_depth > 16 || info.chroma < 0 || info.chroma > 3) continue;
       int rchroma, rbits;
       planar_result_format(params, info.chroma, info.bit_depth, &rchroma, &rbits);
-      int rc = hm_planes_resolve(rchroma, rbits, info.width, info.height, 0, &pdests[k], &plans[k]); // (frames carry no alpha)
+      hm_planes_view_plan pv;
+      pv.ow = info.width; pv.oh = info.height;
+      int rc = view ? hm_planes_view_resolve(rchroma, info.width, info.height, view, &pv) : HM_OK;
+      if (!rc) rc = hm_planes_resolve(rchroma, rbits, pv.ow, pv.oh, 0, &pdests[k], &plans[k]); // (frames carry no alpha)
       if (!rc) rc = hm_planes_check_len(&pdests[k], &plans[k]);
       if (rc) { if (failed_frame) *failed_frame = k; return rc; }
       planned[k] = 1;
@@ -1389,7 +1448,10 @@ static int decode_sequence(const hm_file* f, const uint32_t* frames, uint32_t fi
       hm_planes_plan pp;
       int rchroma, rbits;
       planar_result_format(params, I.chroma, I.bd, &rchroma, &rbits);
-      int drc = hm_planes_resolve(rchroma, rbits, I.w, I.h, 0, &pdests[k], &pp);
+      hm_planes_view_plan pv;
+      pv.ow = I.w; pv.oh = I.h;
+      int drc = view ? hm_planes_view_resolve(rchroma, I.w, I.h, view, &pv) : HM_OK; // (against the frame's own decoded size)
+      if (!drc) drc = hm_planes_resolve(rchroma, rbits, pv.ow, pv.oh, 0, &pdests[k], &pp);
       if (!drc) drc = hm_planes_check_len(&pdests[k], &pp);
       if (!drc) drc = hm_planes_check_pointer(&pdests[k], &pp);
       if (drc) return fail(drc);
@@ -1447,7 +1509,9 @@ static int decode_sequence(const hm_file* f, const uint32_t* frames, uint32_t fi
     ~ViewBlocks() { for (hm_view_scratch& x : sc) hm_view_scratch_free(&x); }
   } view_blocks;
   std::vector<hm_view_item> view_items;
+  std::vector<hm_planes_view_item> planes_items;
   if (view && ddests) { view_blocks.sc.assign((size_t)count, hm_view_scratch{}); view_items.assign((size_t)count, hm_view_item{}); }
+  if (view && pdests) { view_blocks.sc.assign((size_t)count, hm_view_scratch{}); planes_items.assign((size_t)count, hm_planes_view_item{}); }
   struct Drain { // (declared behind everything the queued work uses: destroyed first, it drains the stream before they go)
     hipStream_t s; bool on = false;
     ~Drain() { if (on) hipStreamSynchronize(s); }
@@ -1502,11 +1566,22 @@ static int decode_sequence(const hm_file* f, const uint32_t* frames, uint32_t fi
     hm_decode_params pk = *params;
     if (dests) { pk.ext_dst = dests[k].ext_dst; pk.ext_dst_len = dests[k].ext_dst_len; pk.ext_dst_stride = dests[k].ext_dst_stride; }
     const bool viewed = view && ddests;
-    if ((rc = emit_image(&pk, s, Fr.I, nullptr, 0, Fr.dout, Fr.alpha_sdr, &out[k], ddests ? &ddests[k] : nullptr, viewed ? view : nullptr, nullptr,
-                         viewed ? &view_items[(size_t)k] : nullptr, pdests ? &pdests[k] : nullptr))) return release_all(rc);
+    const bool pviewed = view && pdests;
+    if ((rc = emit_image(&pk, s, Fr.I, nullptr, 0, Fr.dout, Fr.alpha_sdr, &out[k], ddests ? &ddests[k] : nullptr, viewed || pviewed ? view : nullptr, nullptr,
+                         viewed ? &view_items[(size_t)k] : nullptr, pdests ? &pdests[k] : nullptr, pviewed ? &planes_items[(size_t)k] : nullptr))) {
+      if (failed_frame && pviewed) *failed_frame = k;
+      return release_all(rc);
+    }
   }
   // ---- the view of every frame: one pair of tap tables and one launch per pass for all frames that share them ----
   if (view && ddests && (rc = hm_view_write_batch(params->out_format, view_items.data(), count, s, view_blocks.sc.data()))) return release_all(rc);
+  if (view && pdests) { // ... and of every frame's planes: the tables of at most four axes per group (hm_planes_view_write)
+    int bad = -1;
+    if ((rc = hm_planes_view_write(planes_items.data(), count, s, view_blocks.sc.data(), &bad))) {
+      if (failed_frame) *failed_frame = bad;
+      return release_all(rc);
+    }
+  }
   lap("sequence: colour + D2H queued");
   const hipError_t e = hipStreamSynchronize(s);
   drain.on = false;

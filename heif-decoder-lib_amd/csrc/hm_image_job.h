@@ -148,7 +148,8 @@ int job_enqueue(DecodeJob& j, hm_decoded* out);
 int check_device_request(const hm_file* f, uint32_t id, const hm_decode_params* params, const hm_device_dest* dest, const hm_device_view* view = nullptr);
 // the same for a planar destination (hm_device_planes): the request, the planes against what hm_image_info declares (size, and the
 // result's chroma format and depth where the file decides them), a device, the pointers
-int check_planes_request(const hm_file* f, uint32_t id, const hm_decode_params* params, const hm_device_planes* planes);
+// view (may be NULL): the planes are judged against the view's output size, the crop against the declared size and the result's chroma format
+int check_planes_request(const hm_file* f, uint32_t id, const hm_decode_params* params, const hm_device_planes* planes, const hm_device_view* view = nullptr);
 // what of it needs no file: params (ext_dst, an interleaved target), the planes' static checks, null pointers of Y
 int check_planes_params(const hm_decode_params* params, const hm_device_planes* planes);
 int job_complete(DecodeJob& j, hm_decoded* out);

@@ -210,7 +210,14 @@ int hm_pipeline_submit_to_device_planes(hm_pipeline* p, const uint8_t* heif, siz
   return submit(p, heif, size, item_id, tag, nullptr, nullptr, planes);
 }
 
-// dest (may be NULL): the image's pixels go to caller-owned device memory of the pipeline's device; view (may be NULL, with dest only):
+int hm_pipeline_submit_to_device_planes_view(hm_pipeline* p, const uint8_t* heif, size_t size, uint32_t item_id, uint64_t tag, const hm_device_view* view,
+                                             const hm_device_planes* planes)
+{
+  if (!p || !heif || !view || !planes) return hm_fail(HM_ERR_INVALID_ARG, "null argument");
+  return submit(p, heif, size, item_id, tag, nullptr, view, planes);
+}
+
+// dest (may be NULL): the image's pixels go to caller-owned device memory of the pipeline's device; view (may be NULL, with dest or planes):
 // a rectangle of them, resampled - job_plan then queues only the coded pictures the crop touches
 // planes (may be NULL, without dest): the planes of the pipeline's planar out_format go to caller-owned device memory
 static int submit(hm_pipeline* p, const uint8_t* heif, size_t size, uint32_t item_id, uint64_t tag, const hm_device_dest* dest, const hm_device_view* view,
@@ -256,9 +263,10 @@ static int submit(hm_pipeline* p, const uint8_t* heif, size_t size, uint32_t ite
       int prev = -1;
       hipGetDevice(&prev);
       hipSetDevice(p->cfg.device);
-      rc = check_planes_request(im->file, im->job.id, &im->job.params, planes);
+      rc = check_planes_request(im->file, im->job.id, &im->job.params, planes, view);
       if (prev >= 0) hipSetDevice(prev);
       im->job.planes = *planes; im->job.has_planes = true;
+      if (view) { im->job.view = *view; im->job.has_view = true; }
     }
     if (!rc) rc = job_plan(im->job);
   }

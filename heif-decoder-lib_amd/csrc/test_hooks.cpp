@@ -20,6 +20,7 @@ extern "C" const void* hm_tail420_kernel16();
 extern "C" const void* hm_resample_kernel_of(int index);                                    // resample.hip: NULL behind the last instance
 extern "C" const void* hm_resample_staged_kernel_of(int index);                             // ... the instances of k_resample_h_staged
 extern "C" const void* hm_resample_batch_kernel_of(int index);                              // ... the batched forms of all three passes
+extern "C" const void* hm_planes_view_kernel_of(int index);                                 // planes_view.hip: NULL behind the last instance
 
 extern "C" {
 
@@ -36,6 +37,7 @@ __attribute__((visibility("default"))) int hm_debug_kernel_regs(int which, int a
   else if (which == 4) fn = hm_resample_kernel_of(a); // (the view kernels: a = 0, 1, ... until the call fails)
   else if (which == 5) fn = hm_resample_staged_kernel_of(a); // (k_resample_h_staged; out[1] counts scratch, not LDS)
   else if (which == 6) fn = hm_resample_batch_kernel_of(a); // (k_resample_h_batch, k_resample_h_staged_batch, k_resample_v_batch)
+  else if (which == 7) fn = hm_planes_view_kernel_of(a); // (k_planes_resample_h, k_planes_resample_v, k_planes_view_nearest)
   hipFuncAttributes fa;
   if (!fn || !out || hipFuncGetAttributes(&fa, fn) != hipSuccess) return -1;
   out[0] = fa.numRegs;

@@ -441,14 +441,17 @@ def _default_plane_dtype(bits):
 
 
 def decode_to_planes(data, item_id=0, chroma=None, layout="planar", dtype=None, to_8bit=False, scale=None, bias=None, out=None, stream=None,
-                     host_threads=None, msb_aligned=False, alpha=True):
+                     host_threads=None, msb_aligned=False, alpha=True, crop=None, size=None, filter="triangle"):
     """Decode one image of a HEIF file into planar YCbCr CUDA tensors: (Y, Cb, Cr[, A]) for layout "planar", (Y, CbCr[, A]) for
     "semiplanar" (a 4:0:0 picture: (Y[, A])).  Y and A are H x W, Cb and Cr Hc x Wc, CbCr Hc x Wc x 2 (Cb first).  chroma: None = as
     coded, "420" / "422" / "444" = converted to that format (to_8bit: down to 8 bits on the way).  dtype defaults to torch.uint8 or
     torch.uint16 by the result's depth (out's dtype when out is given); msb_aligned (torch.uint16): v << (16 - bits), P010.  Floats are
     sample * scale[c] + bias[c], c = Y, Cb, Cr, A.  out: a tuple of CUDA tensors of those shapes; their row strides are honoured.
     The alpha plane is returned when the image has one and alpha is true; alpha=False leaves it out (plane[3] NULL) - the way to an
-    integer dtype for an image whose alpha plane is of the other depth class (8 bits beside more than 8), which is refused otherwise."""
+    integer dtype for an image whose alpha plane is of the other depth class (8 bits beside more than 8), which is refused otherwise.
+    crop: (x, y, w, h) inside the image, x (and y for 4:2:0) even where the chroma is sub-sampled; size: (w, h), the luma size every
+    plane is resampled for, each plane as an image of its own; filter: as decode_to_tensor.  Only the tiles of a grid the crop touches
+    are decoded where the picture is taken as coded."""
     import torch
     L = capi.image_lib()
     fmt, lay = _planes_request(chroma, layout, to_8bit)
@@ -457,7 +460,8 @@ def decode_to_planes(data, item_id=0, chroma=None, layout="planar", dtype=None, 
     try:
         iid, info = _info(f, item_id)
         rchroma, rbits = _result_format(info, fmt, to_8bit)
-        w, h, alpha = info.width, info.height, bool(alpha) and bool(info.has_alpha)
+        alpha = bool(alpha) and bool(info.has_alpha)
+        view, w, h = _view_of(crop, size, filter, info.width, info.height)
         if dtype is None:
             dtype = out[0].dtype if out is not None else _default_plane_dtype(rbits)
         code = _dtype_code(dtype)
@@ -472,7 +476,10 @@ def decode_to_planes(data, item_id=0, chroma=None, layout="planar", dtype=None, 
         prm = capi.DecodeParams(fmt, host_threads or _default_threads(), 0, 0, _stream_handle(stream, device), None, 0, 0, 0, 1 if to_8bit else 0)
         d = capi.Decoded()
         with torch.cuda.device(device):
-            capi.check_image(L.hm_decode_item_to_device_planes(f.h, iid, C.byref(prm), C.byref(planes), C.byref(d)))
+            if view is None:
+                capi.check_image(L.hm_decode_item_to_device_planes(f.h, iid, C.byref(prm), C.byref(planes), C.byref(d)))
+            else:
+                capi.check_image(L.hm_decode_item_to_device_planes_view(f.h, iid, C.byref(prm), C.byref(view), C.byref(planes), C.byref(d)))
         L.hm_decoded_free(C.byref(d))
         return out
     finally:
@@ -480,9 +487,11 @@ def decode_to_planes(data, item_id=0, chroma=None, layout="planar", dtype=None, 
 
 
 def decode_sequence_to_planes(data, frames=None, chroma=None, layout="planar", dtype=None, to_8bit=False, scale=None, bias=None, out=None,
-                              stream=None, host_threads=None, msb_aligned=False):
+                              stream=None, host_threads=None, msb_aligned=False, crop=None, size=None, filter="triangle"):
     """decode_to_planes over frames of an image sequence in ONE device batch (hm_decode_frames_to_device_planes): a tuple of
-    T x ... tensors, frame k in slice k of each.  frames: None (all), a range or a list of 1-based frame IDs, in any order."""
+    T x ... tensors, frame k in slice k of each.  frames: None (all), a range or a list of 1-based frame IDs, in any order.
+    crop / size / filter: the same rectangle of every frame, every plane resampled as an image of its own, in one grouped write
+    (hm_decode_frames_to_device_planes_view)."""
     import torch
     L = capi.image_lib()
     fmt, lay = _planes_request(chroma, layout, to_8bit)
@@ -494,10 +503,13 @@ def decode_sequence_to_planes(data, frames=None, chroma=None, layout="planar", d
         if not seq.is_sequence:
             raise capi.HmError(-1, "the file is not an image sequence")
         ids = _frame_ids(frames, seq.frame_count)
-        first = None
+        first, view = None, None
         for k, fid in enumerate(ids):
             _, info = _info(f, fid)
-            key = (info.width, info.height) + _result_format(info, fmt, to_8bit)
+            v, vw, vh = _view_of(crop, size, filter, info.width, info.height)
+            if view is None:
+                view = v
+            key = (vw, vh) + _result_format(info, fmt, to_8bit)
             if first is None:
                 first = key
             if key != first:
@@ -519,7 +531,10 @@ def decode_sequence_to_planes(data, frames=None, chroma=None, layout="planar", d
         res = (capi.Decoded * n)()
         failed = C.c_int32(-1)
         with torch.cuda.device(device):
-            rc = L.hm_decode_frames_to_device_planes(f.h, (C.c_uint32 * n)(*ids), n, C.byref(prm), dests, res, C.byref(failed))
+            if view is None:
+                rc = L.hm_decode_frames_to_device_planes(f.h, (C.c_uint32 * n)(*ids), n, C.byref(prm), dests, res, C.byref(failed))
+            else:
+                rc = L.hm_decode_frames_to_device_planes_view(f.h, (C.c_uint32 * n)(*ids), n, C.byref(prm), C.byref(view), dests, res, C.byref(failed))
         if rc < 0:
             detail = f"{L.hm_status_string(rc).decode()}: {L.hm_last_error().decode()}"
             k = failed.value
@@ -532,10 +547,12 @@ def decode_sequence_to_planes(data, frames=None, chroma=None, layout="planar", d
 
 
 def decode_batch_to_planes(files, item_id=0, chroma=None, layout="planar", dtype=None, to_8bit=False, scale=None, bias=None, out=None,
-                           host_threads=None, max_in_flight=4, msb_aligned=False, alpha=True):
+                           host_threads=None, max_in_flight=4, msb_aligned=False, alpha=True, size=None, crops=None, filter="triangle"):
     """decode_to_planes over N files through ONE hm_pipeline: a tuple of N x ... tensors, file k in slice k of each.  files: bytes
     objects or paths.  A file of another size or format (chroma format, depth, alpha) than the first raises ValueError naming it.
-    alpha=False: no alpha plane is asked for or returned, and files with and without one go together."""
+    alpha=False: no alpha plane is asked for or returned, and files with and without one go together.
+    size: (w, h) - files of different sizes are accepted then, each resampled into its slice; crops: one (x, y, w, h) or None per
+    file, the rectangle of that file that is resampled (needs size)."""
     import torch
     L = capi.image_lib()
     fmt, lay = _planes_request(chroma, layout, to_8bit)
@@ -551,14 +568,22 @@ def decode_batch_to_planes(files, item_id=0, chroma=None, layout="planar", dtype
                 datas.append(fh.read())
     if not datas:
         raise ValueError("files: empty")
+    if crops is not None and size is None:
+        raise ValueError("crops: needs size (the slices of one tensor are equally sized)")
+    if crops is not None and len(crops) != len(datas):
+        raise ValueError(f"crops: {len(crops)} entries for {len(datas)} files")
+    views = [None] * len(datas)
     ids, first = [], None
-    for name, data in zip(names, datas):
+    for k, (name, data) in enumerate(zip(names, datas)):
         f = _File(data)
         try:
             iid, info = _info(f, item_id)
         finally:
             f.close()
-        key = (info.width, info.height) + _result_format(info, fmt, to_8bit) + (bool(alpha) and bool(info.has_alpha),)
+        fw, fh = info.width, info.height
+        if size is not None:
+            views[k], fw, fh = _view_of(crops[k] if crops is not None else None, size, filter, fw, fh)
+        key = (fw, fh) + _result_format(info, fmt, to_8bit) + (bool(alpha) and bool(info.has_alpha),)
         if first is None:
             first = key
         if key != first:
@@ -594,7 +619,10 @@ def decode_batch_to_planes(files, item_id=0, chroma=None, layout="planar", dtype
             for k, data in enumerate(datas):
                 planes = _planes_of([t[k] for t in out], rchroma, lay, alpha, code, msb_aligned, sc, bi)
                 while True:
-                    rc = capi.check_image(L.hm_pipeline_submit_to_device_planes(pipe, data, len(data), ids[k], k, C.byref(planes)))
+                    if views[k] is None:
+                        rc = capi.check_image(L.hm_pipeline_submit_to_device_planes(pipe, data, len(data), ids[k], k, C.byref(planes)))
+                    else:
+                        rc = capi.check_image(L.hm_pipeline_submit_to_device_planes_view(pipe, data, len(data), ids[k], k, C.byref(views[k]), C.byref(planes)))
                     if rc != capi.HM_PIPELINE_FULL:
                         break
                     take()

@@ -532,7 +532,7 @@ HM_API int hm_pipeline_submit_to_device(hm_pipeline* p, const uint8_t* heif, siz
  * below the last-row form row_pitch * (rows - 1) + tight, a NULL ptr of a plane that is written, a pointer that is not device
  * memory of the decoding device, an interleaved HM_OUT_RGB* target (that is hm_decode_item_to_device's), params->ext_dst, two
  * planes whose byte ranges overlap, and with HM_DEV_PLANES_SEMI a plane[2] that is not all zero.
- * Views (hm_device_view) with a planar destination do not exist: no entry point here takes one. */
+ * Views (hm_device_view) with a planar destination: the _planes_view entry points behind hm_device_view, below. */
 enum { HM_DEV_PLANES_SEPARATE = 0,  /* Y, Cb, Cr[, A]: one plane each (I420 / I422 / I444 and their 16-bit forms) */
        HM_DEV_PLANES_SEMI     = 1 };/* Y, CbCr interleaved (Cb first)[, A]: NV12 / NV16 / NV24, P010-style with 16 bits */
 typedef struct hm_device_plane {
@@ -644,6 +644,54 @@ HM_API int hm_plan_view(const hm_file* f, uint32_t id, const hm_decode_params* p
 /* Host arithmetic: the taps of output index j on one axis of n_in -> n_out.  Returns their count (or a negative status),
  * *first = the first source index, weights[0 .. min(count, cap)) = the weights the kernels use. */
 HM_API int hm_view_filter_taps(int n_in, int n_out, int filter, int j, int32_t* first, float* weights, int cap);
+
+/* ------------------------------------------------------------------------- */
+/* Planar views: a rectangle of the image, at a size of the caller's choice, into I420 / NV12 / P010 planes */
+/* ------------------------------------------------------------------------- */
+
+/* A view into hm_device_planes treats EVERY PLANE AS AN IMAGE OF ITS OWN under hm_device_view's rule: the tap table per axis, the
+ * filters, the float32 sums (tap 0 first, horizontal pass first, no fused multiply-add) and HM_VIEW_NEAREST's index rule are those
+ * stated above; only the geometry per plane and the final store are new.
+ *   Geometry: the result has chroma format `chroma` and luma size W x H; the crop is (x, y, w, h) (the whole image when crop_w ==
+ *   crop_h == 0), the output size ow x oh (the crop's own size when out_w == out_h == 0).  Y and alpha take the crop (x, y, w, h) to
+ *   ow x oh.  Cb and Cr take the crop (x / sx, y / sy, (w + sx - 1) / sx, (h + sy - 1) / sy) of the chroma plane to
+ *   ((ow + sx - 1) / sx, (oh + sy - 1) / sy) - exactly the plane size of an ow x oh result -, with sx = 2 for 4:2:0 / 4:2:2, sy = 2
+ *   for 4:2:0, otherwise 1.  x must be a multiple of sx and y of sy, else HM_ERR_INVALID_ARG; odd extents are fine.  The chroma
+ *   crop always lies inside the chroma plane: (x + w + 1) / 2 <= (W + 1) / 2.  A 4:0:0 result has Y only.  No chroma siting is
+ *   modelled: "each plane on its own".
+ *   Checks: the filter's reduction limit holds per plane and axis; the destination is checked as hm_device_planes is, against an
+ *   ow x oh result: hm_device_planes_bytes(chroma, bits, ow, oh, ...) sizes it.
+ *   Final store: integer dtypes store min(max((int)(r + 0.5f), 0), peak) << shift with peak = (1 << bits) - 1 OF THAT PLANE'S OWN
+ *   DEPTH (1023 for a 10-bit plane, not 65535; the alpha plane: its own depth) and shift = msb_aligned ? 16 - that depth : 0.  Float
+ *   dtypes store r * scale[c] + bias[c], c = Y, Cb, Cr, A, unclamped, rounded as hm_device_planes states.  HM_DEV_PLANES_SEMI:
+ *   element 2 x of a row is the resampled Cb, element 2 x + 1 the resampled Cr.  The crop alone and HM_VIEW_NEAREST move samples
+ *   (<< shift, or through scale and bias).  Only plane_width x plane_height elements per plane are written: no pitch padding,
+ *   nothing behind the last row.  Every refusal happens before any work is queued, with no plane written.
+ * Of a grid decoded as coded (out_format 0) only the tiles the crop touches are decoded, under the conditions of hm_plan_view (no
+ * transformation, no alpha image, the sub-grid's origin moved out to even): hm_plan_planes_view tells.  HM_OUT_YCBCR_* targets decode
+ * the whole item and take the view of the chain's result - the chain's up- and down-sampling operations read neighbours across
+ * tile borders; reducing them is the open step. */
+/* Host arithmetic, no device needed: crop[c] = x, y, w, h inside plane c and out[c] = w, h written, c = 0 Y, 1 Cb, 2 Cr, 3 alpha
+ * (all zero for Cb / Cr of HM_CHROMA_MONO), of `view` on a width x height result of chroma format `chroma`; or the view's refusal. */
+HM_API int hm_planes_view_geometry(int chroma, int width, int height, const hm_device_view* view, int32_t crop[4][4], int32_t out[4][2]);
+/* hm_decode_item_to_device_planes with `planes` sized for out_w x out_h; out->width / height and plane_width / height[c]: the sizes
+ * written.  Crop coordinates are in the image as hm_decode_item hands it out. */
+HM_API int hm_decode_item_to_device_planes_view(const hm_file* f, uint32_t id, const hm_decode_params* params, const hm_device_view* view,
+                                                const hm_device_planes* planes, hm_decoded* out);
+/* The sequence form (hm_decode_frames_to_device_planes with ONE view of every frame): one decode batch, then one grouped write -
+ * frames that agree in the view's geometry and in their destination's layout, dtype, pitches, scale, bias and 16-byte alignment
+ * share their tap tables and one launch per pass.  The bytes are those of `count` item calls. */
+HM_API int hm_decode_frames_to_device_planes_view(const hm_file* f, const uint32_t* frames, int32_t count, const hm_decode_params* params,
+                                                  const hm_device_view* view, const hm_device_planes* planes, hm_decoded* out, int32_t* failed_frame);
+/* the pipeline form: images of different sizes into equally sized surfaces */
+HM_API int hm_pipeline_submit_to_device_planes_view(hm_pipeline* p, const uint8_t* heif, size_t size, uint32_t item_id, uint64_t tag,
+                                                    const hm_device_view* view, const hm_device_planes* planes);
+/* The step on its own, on planes that are on the device already (the sibling of hm_planes_to_tensor and hm_resample_to_tensor):
+ * d_src / src_stride / alpha_bits as hm_planes_to_tensor takes them, of a width x height image.  Asynchronous on `stream`. */
+HM_API int hm_resample_planes_to_tensor(int chroma, int bits, int width, int height, int alpha_bits, const void* const d_src[4], const int32_t src_stride[4],
+                                        const hm_device_view* view, const hm_device_planes* planes, void* stream);
+/* hm_plan_view for a planar view decode of this item (hm_plan_view's own answers for planar formats stay "the whole grid") */
+HM_API int hm_plan_planes_view(const hm_file* f, uint32_t id, const hm_decode_params* params, const hm_device_view* view, int32_t tiles[4]);
 
 #ifdef __cplusplus
 }

@@ -1,0 +1,24 @@
+"""The index arithmetic of a planar view write (csrc/hm_planes_view.h: geometry, the blockIdx.y plane ranges, the lane-group to
+element and pair maps with their ragged tails, the intermediate's layout, grouping key, chunk cut, block layout) in a stand-alone
+host program (tests/host/planes_view_check.cpp) under AddressSanitizer and UndefinedBehaviorSanitizer: no GPU, no library, nothing
+loaded into Python."""
+import os
+import shutil
+import subprocess
+
+import pytest
+
+ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+
+
+def test_planes_view_arithmetic_under_sanitizers(tmp_path):
+    cxx = shutil.which(os.environ.get("CXX", "g++"))
+    if cxx is None:
+        pytest.fail("no C++ compiler: the library itself could not have been built")
+    exe = str(tmp_path / "planes_view_check")
+    src = os.path.join(ROOT, "tests", "host", "planes_view_check.cpp")
+    inc = os.path.join(ROOT, "heif-decoder-lib_amd", "csrc")
+    subprocess.run([cxx, "-std=c++17", "-O1", "-g", "-Wall", "-Werror", "-fsanitize=address,undefined", "-fno-sanitize-recover=all", "-static-libasan", "-static-libubsan", "-I", inc, src, "-o", exe],
+                   check=True)
+    r = subprocess.run([exe], capture_output=True, text=True)
+    assert r.returncode == 0 and "planes view arithmetic: ok" in r.stdout, r.stdout + r.stderr
