@@ -18,6 +18,7 @@
 
 #include "hm_device.h"
 #include "hm_internal.h"
+#include "hm_overlap_plan.h"
 
 namespace {
 
@@ -173,7 +174,8 @@ struct hm_batch {
   }
   hipStream_t copy_stream = nullptr;
   bool copy_inflight = false;
-  int groups = 0;                       // hm_batch_set_concurrency
+  int groups = 0;                       // hm_batch_set_concurrency: 0 automatic (hm_overlap_plan.h), 1 one stream, 2..8 that many groups
+  int last_groups = 1, last_cut = 0;    // what the last execute ran (hm_batch_last_groups)
   std::vector<hipStream_t> aux_streams; // further launch streams of the grouped execute
   std::vector<hipEvent_t> join_evs;
   hipEvent_t fork_ev = nullptr;
@@ -184,7 +186,10 @@ struct hm_batch {
   // per slot: events on the launch stream; the interval that ends at event i belongs to kernel kind[i]
   // (-1 start marker, 0 reconstruction (split chains: the chain kernel), 1 deblocking, 2 SAO + paste, 3 colour conversion,
   //  4 residual pre-pass of the split-chain reconstruction)
-  struct Timeline { std::vector<hipEvent_t> ev; std::vector<int8_t> kind; size_t used = 0; };
+  // spans: the grouped execute - event 0 on the caller's stream in front of the fork, then every group's start marker and
+  // kernel events on the group's own stream, an end marker behind the join; the intervals of one kind overlap between the
+  // groups, batch_timings reports the length of their union
+  struct Timeline { std::vector<hipEvent_t> ev; std::vector<int8_t> kind; size_t used = 0; bool spans = false; };
   std::vector<Timeline> timelines;
   long exec_count = 0;
   bool profiling_per_kernel_only() const { return false; }
@@ -489,6 +494,45 @@ static int batch_prepare(hm_batch* b, size_t* blob_bytes_out)
   return HM_OK;
 }
 
+// The groups hm_batch_execute runs the images of a batch with colour attached in (hm_overlap_plan.h).  The chain launcher is asked
+// for its cut only where the answer can matter: the automatic schedule (hm_chain_plan itself answers small batches at once).
+static hm_overlap_plan overlap_plan_of(hm_batch* b, const Class& c, const hm_dev_pic* dc, int n, int n_img)
+{
+  hm_overlap_in in{};
+  in.n_images = n_img;
+  in.per_image = n_img > 0 ? n / n_img : 0;
+  in.eligible = b->tail_state == 2 ? 1 : 0;
+  in.requested = b->groups;
+  in.min_pics = hm_knob(HM_KNOB_OVERLAP_MIN_PICS);
+  in.forced_cut = hm_knob(HM_KNOB_OVERLAP_CUT);
+  if (in.eligible && in.requested == 0 && n_img >= 2 && c.split) {
+    const SyncRegion r = b->sync_region(dc, n);
+    int per_picture = 0, split_fraction = 0;
+    long resident = 0;
+    if (hm_chain_plan(dc, n, c.log2_ctb, c.chroma_format, c.bit_depth, c.rare, c.max_ctb_w, c.max_ctb_h, r.p, r.bytes, r.err, &per_picture, &resident, &split_fraction) == 1) {
+      in.per_picture = per_picture;
+      in.resident = resident;
+      in.split_fraction = split_fraction;
+    }
+  }
+  hm_overlap_plan p = hm_plan_groups(in);
+  if (p.groups == 2 && in.requested == 0 && in.min_pics <= 0) {
+    // ... and each group on its own must still be a wave per picture (the launcher's ladder is asked, not repeated here)
+    for (int g = 0; g < 2; g++) {
+      const int m = (p.bound[g + 1] - p.bound[g]) * in.per_image;
+      const hm_dev_pic* dk = dc + (size_t)p.bound[g] * in.per_image;
+      const SyncRegion r = b->sync_region(dk, m);
+      int per_picture = 0, split_fraction = 0;
+      long resident = 0;
+      if (hm_chain_plan(dk, m, c.log2_ctb, c.chroma_format, c.bit_depth, c.rare, c.max_ctb_w, c.max_ctb_h, r.p, r.bytes, r.err, &per_picture, &resident, &split_fraction) != 1 || !per_picture) {
+        in.requested = 1;
+        return hm_plan_groups(in);
+      }
+    }
+  }
+  return p;
+}
+
 extern "C" {
 
 // Upload command streams, build descriptors, size the working set.  After this the inputs are
@@ -547,8 +591,11 @@ int hm_batch_execute(hm_batch* b, int stages, void* stream)
     if ((int)b->timelines.size() < b->profiling) b->timelines.resize(b->profiling);
     tl = &b->timelines[(size_t)(b->exec_count % b->profiling)];
     tl->used = 0;
+    tl->spans = false;
   }
-  auto mark = [&](int kind) {
+  b->last_groups = 1;
+  b->last_cut = 0;
+  auto mark_on = [&](int kind, hipStream_t on) {
     if (!tl) return;
     if (tl->used == tl->ev.size()) {
       hipEvent_t ev;
@@ -557,8 +604,9 @@ int hm_batch_execute(hm_batch* b, int stages, void* stream)
       tl->kind.push_back(0);
     }
     tl->kind[tl->used] = (int8_t)kind;
-    hipEventRecord(tl->ev[tl->used++], s);
+    hipEventRecord(tl->ev[tl->used++], on);
   };
+  auto mark = [&](int kind) { mark_on(kind, s); };
   // With a colour conversion attached (hm_batch_set_colour: the pictures were queued image by image, one class) the
   // filters and the conversion can run group of images by group of images, so that what k_deblock writes, k_sao_paste
   // reads and writes and the colour kernel reads is still in the 256 MiB Infinity Cache.  Measured (r02, 384 x 12 MP,
@@ -572,12 +620,13 @@ int hm_batch_execute(hm_batch* b, int stages, void* stream)
     const int per_img = n / n_img;
     const hm_dev_pic* dc = d + c.desc_offset;
     if (b->tail_state == 0) { const int rc0 = decide_tail(b); if (rc0) return rc0; }
-    const int k_groups = b->groups;
-    if (b->tail_state == 2 && k_groups > 1 && n_img >= k_groups) {
-      mark(-1);
-      // hm_batch_set_concurrency: groups of images, one stream each (the caller's and k_groups - 1 of the batch's own), so
-      // that the fused tail of one group runs while the reconstruction of another one drains (profiles/r02_k_groups.txt)
-      const int ns = k_groups;
+    const hm_overlap_plan plan = overlap_plan_of(b, c, dc, n, n_img);
+    if (plan.groups > 1) {
+      // Groups of images, one stream each (the caller's and plan.groups - 1 of the batch's own), so that the fused tail of one
+      // group runs while the reconstruction of another one drains (profiles/batch_overlap.txt).  The cuts are image
+      // boundaries: stream order is all that orders the pastes inside an image.  The streams have the default priority: a
+      // second group on a stream of the lowest priority measured 3.6-5.5 ms SLOWER per step than without (same file).
+      const int ns = plan.groups;
       while ((int)b->aux_streams.size() > ns - 1) { hipStreamDestroy(b->aux_streams.back()); b->aux_streams.pop_back(); hipEventDestroy(b->join_evs.back()); b->join_evs.pop_back(); }
       if ((int)b->aux_streams.size() < ns - 1) {
         for (int k = (int)b->aux_streams.size() + 1; k < ns; k++) {
@@ -590,6 +639,8 @@ int hm_batch_execute(hm_batch* b, int stages, void* stream)
         }
       }
       if (!b->fork_ev && hipEventCreateWithFlags(&b->fork_ev, hipEventDisableTiming) != hipSuccess) return hm_fail(HM_ERR_NO_DEVICE, "hipEventCreate failed");
+      if (tl) tl->spans = true;
+      mark(-1); // (the step's first event: every interval below is measured from it)
       hipError_t he = hipEventRecord(b->fork_ev, s);
       for (hipStream_t t : b->aux_streams)
         if (he == hipSuccess) he = hipStreamWaitEvent(t, b->fork_ev, 0);
@@ -605,19 +656,24 @@ int hm_batch_execute(hm_batch* b, int stages, void* stream)
         return je;
       };
       const TailDstHost* td = (const TailDstHost*)b->d_tail.p;
-      for (int g = 0; g < k_groups; g++) {
-        const int i0 = (int)((long)n_img * g / k_groups), i1 = (int)((long)n_img * (g + 1) / k_groups);
+      for (int g = 0; g < plan.groups; g++) {
+        const int i0 = plan.bound[g], i1 = plan.bound[g + 1];
         const int m = (i1 - i0) * per_img;
         if (m <= 0) continue;
         const hm_dev_pic* dk = dc + (size_t)i0 * per_img;
-        const int si = g % ns;
-        hipStream_t sg = si ? b->aux_streams[(size_t)si - 1] : s;
-        int rc = launch_recon(dk, m, c, sg, b->sync_region(dk, m));
-        if (!rc) rc = launch_tail(b, c, dk, td + (size_t)i0 * per_img, m, stages, sg);
-        if (rc) { join(); return rc; }
+        hipStream_t sg = g ? b->aux_streams[(size_t)g - 1] : s;
+        // (the synchronisation words are the group's own, the sticky error word is the batch's: sync_region; a partial last
+        //  round of the group's chains goes to the second stream chain.hip keeps for the group's stream)
+        mark_on(-1, sg);
+        int rc = launch_recon(dk, m, c, sg, b->sync_region(dk, m), [&] { mark_on(4, sg); });
+        if (!rc) { mark_on(0, sg); rc = launch_tail(b, c, dk, td + (size_t)i0 * per_img, m, stages, sg); }
+        if (rc) { join(); if (tl) tl->used = 0; return rc; }
+        mark_on(2, sg);
       }
-      if ((he = join()) != hipSuccess) return hm_check_hip(he, "join of the launch streams");
-      mark(2); // (the whole step in the tail's slot: per-kernel intervals overlap)
+      if ((he = join()) != hipSuccess) { if (tl) tl->used = 0; return hm_check_hip(he, "join of the launch streams"); }
+      mark(-1); // (behind the join: batch_timings waits for this one)
+      b->last_groups = plan.groups;
+      b->last_cut = plan.bound[1];
       b->exec_count++;
       return HM_OK;
     }
@@ -673,7 +729,9 @@ int hm_batch_execute(hm_batch* b, int stages, void* stream)
 
 // Upload and execute in one call, the H2D copy of chunk i+1 (copy stream) running under the kernels of chunk i (compute
 // stream): the device-inclusive clock becomes max(H2D, kernels) + one chunk instead of their sum.  Pictures are taken
-// in queue order; a batch that mixes picture classes (kernel variants) is handled serially.
+// in queue order; a batch that mixes picture classes (kernel variants) is handled serially.  The chunks stay on the one compute
+// stream: hm_batch_execute's overlapped groups (hm_overlap_plan.h) are not applied here - a chunk's kernels already run under
+// the next chunk's copy, and the chunk boundaries follow the copies, not the chain rounds.
 int hm_batch_upload_execute(hm_batch* b, int stages, int chunks, void* copy_stream, void* stream)
 {
   if (!b) return hm_fail(HM_ERR_INVALID_ARG, "null batch");
@@ -780,17 +838,26 @@ int hm_batch_set_colour(hm_batch* b, const hm_colour_desc* d, int n_images, cons
   return HM_OK;
 }
 
-// Opt-in: hm_batch_execute of a batch that runs the fused tail splits its images into `groups` (2..8) groups and
-// launches each group's two kernels on a stream of its own (the caller's stream waits for all of them), so that one
-// group's tail kernel fills the issue slots the other groups' reconstruction leaves while it drains: +6 % throughput
-// with 2-4 groups on MI355X.  Off (0 / 1) by default: the per-launch times of kernels that run side by side overlap,
-// and hm_batch_get_timings4 then reports the whole step in the tail's slot.
+// hm_batch_execute of a batch that runs the fused tail can split its images into groups and launch each group's kernels on a
+// stream of its own (the caller's stream waits for all of them), so that one group's tail kernel fills the issue slots the
+// other group's reconstruction leaves while it drains.  groups = 0 (the default): automatic - two groups (equal halves, or a
+// first group of whole chain rounds) once the batch is two rounds or more of a wave per picture (hm_overlap_plan.h), one stream below that;
+// 1: always one stream; 2..8: that many equal groups.  The per-kernel times of hm_batch_get_timings* stay filled under
+// overlap: each is the time during which at least one kernel of its kind was running (batch_timings).
 int hm_batch_set_concurrency(hm_batch* b, int groups)
 {
   if (!b || groups < 0 || groups > 8) return hm_fail(HM_ERR_INVALID_ARG, "bad argument");
   b->drain();
   b->groups = groups;
   return HM_OK;
+}
+
+// (test hook) the groups the last execute ran in, and the image index behind the first
+int hm_batch_last_groups(const hm_batch* b, int* first_cut)
+{
+  if (!b) return -1;
+  if (first_cut) *first_cut = b->last_cut;
+  return b->last_groups;
 }
 
 // 1 when the last execute ran the fused tail kernel (deblocking + SAO + paste + colour; its time is reported in the
@@ -809,6 +876,9 @@ int hm_batch_set_profiling(hm_batch* b, int slots)
 // recon, deblock, SAO+paste [, colour conversion when attached].  Synchronises on the recorded events.
 // hm_batch_get_timings5: [4] = the residual pre-pass (k_residual) separately, [0] = the rest of the reconstruction;
 // hm_batch_get_timings4 / hm_batch_get_timings report the two together in [0].
+// An execute that ran groups on streams of their own: every entry is the length of the UNION of its kind's intervals over the
+// groups, measured from the step's first event - the wall time during which at least one kernel of that kind was running (or
+// queued behind its group's previous kernel).  The entries then add up to more than the step.
 static int batch_timings(hm_batch* b, int slot, float ms[5])
 {
   if (!b || !ms) return hm_fail(HM_ERR_INVALID_ARG, "null argument");
@@ -818,6 +888,26 @@ static int batch_timings(hm_batch* b, int slot, float ms[5])
   const hm_batch::Timeline& t = b->timelines[slot];
   hipError_t e = hipEventSynchronize(t.ev[t.used - 1]);
   if (e != hipSuccess) return hm_check_hip(e, "hipEventSynchronize");
+  if (t.spans) {
+    std::vector<std::pair<float, float>> iv[5];
+    for (size_t i = 1; i < t.used; i++) {
+      if (t.kind[i] < 0) continue;
+      float t0 = 0.f, t1 = 0.f; // (i - 1: the event in front of the kernel on its group's stream)
+      if ((e = hipEventElapsedTime(&t0, t.ev[0], t.ev[i - 1])) != hipSuccess || (e = hipEventElapsedTime(&t1, t.ev[0], t.ev[i])) != hipSuccess)
+        return hm_check_hip(e, "hipEventElapsedTime");
+      iv[t.kind[i]].emplace_back(t0, std::max(t0, t1));
+    }
+    for (int q = 0; q < 5; q++) {
+      std::sort(iv[q].begin(), iv[q].end());
+      float end = 0.f;
+      for (size_t k = 0; k < iv[q].size(); k++) {
+        const float from = k ? std::max(iv[q][k].first, end) : iv[q][k].first;
+        if (iv[q][k].second > from) ms[q] += iv[q][k].second - from;
+        end = k ? std::max(end, iv[q][k].second) : iv[q][k].second;
+      }
+    }
+    return HM_OK;
+  }
   for (size_t i = 1; i < t.used; i++) {
     if (t.kind[i] < 0) continue;
     float v = 0.f;

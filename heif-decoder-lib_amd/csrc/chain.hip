@@ -1864,12 +1864,23 @@ std::shared_ptr<AuxStream> aux_stream_of(hipStream_t s)
 }
 } // namespace
 
+// Launches of more pictures than this are looked at as rounds of a wave per picture (the partial-round launch below, hm_chain_plan).
+constexpr int CHAIN_ROUNDS_MIN_PICS = 1024;
+// Can the partial last round of a launch of n_pics pictures get a launch of its own?  -> split_round_fraction (the remainder r behind k
+// full rounds goes if fraction x k x r <= resident), or 0: never (knob chain_split = 0, a forced cut, no synchronisation words, too few
+// pictures).  The one place that decides it: hm_launch_chain acts on it, hm_chain_plan reports it.
+static int split_fraction_of(int n_pics, const uint32_t* d_sync, const uint32_t* d_err)
+{
+  const bool forced = hm_knob(HM_KNOB_CHAIN_PAIRS) >= 0 || hm_knob(HM_KNOB_CHAIN_RING) >= 0 || hm_knob(HM_KNOB_CHAIN_SHARE) >= 2;
+  return hm_knob(HM_KNOB_CHAIN_SPLIT) && !forced && d_sync && d_err && n_pics > CHAIN_ROUNDS_MIN_PICS ? k_tune.split_round_fraction : 0;
+}
+
 extern "C" int hm_launch_chain(const hm_dev_pic* d_pics, int n_pics, int log2_ctb, int chroma_format, int bit_depth, int rare_syntax,
                                int max_ctb_w, int max_ctb_h, uint32_t* d_sync, size_t sync_bytes, uint32_t* d_err, hipStream_t s)
 {
   const int split = hm_knob(HM_KNOB_CHAIN_SPLIT); // 0: never; 1: the remainder's launch first; 2: the full rounds' first
-  const bool forced = hm_knob(HM_KNOB_CHAIN_PAIRS) >= 0 || hm_knob(HM_KNOB_CHAIN_RING) >= 0 || hm_knob(HM_KNOB_CHAIN_SHARE) >= 2;
-  if (split && !forced && d_sync && d_err && n_pics > 1024) {
+  const int fraction = split_fraction_of(n_pics, d_sync, d_err);
+  if (fraction) {
     ChainPlan plan;
     const int q = launch_chain_impl(d_pics, n_pics, log2_ctb, chroma_format, bit_depth, rare_syntax, max_ctb_w, max_ctb_h, d_sync, sync_bytes, d_err, s, &plan);
     if (q <= 0) return q;
@@ -1878,7 +1889,7 @@ extern "C" int hm_launch_chain(const hm_dev_pic* d_pics, int n_pics, int log2_ct
     //  + 512: 9.90 / 7.87, + 1024: 10.11 / 8.80, + 1280: 10.61 / 9.92; two full rounds + 512: 16.10 / 14.44, + 1024: 16.30 / 17.5 - the
     //  later rounds start staggered, a remainder hurts them less: the more full rounds, the smaller the remainder worth a launch)
     const long rounds = n_pics / (plan.resident > 0 ? plan.resident : 1);
-    if (plan.per_picture && n_pics > plan.resident && r > 0 && k_tune.split_round_fraction * rounds * r <= plan.resident) {
+    if (plan.per_picture && n_pics > plan.resident && r > 0 && fraction * rounds * r <= plan.resident) {
       ChainPlan rest; // (only if the remainder alone would not be a wave per picture again)
       const hm_dev_pic* const d_rest = d_pics + (n_pics - r);
       const std::shared_ptr<AuxStream> ax = aux_stream_of(s);
@@ -1899,6 +1910,27 @@ extern "C" int hm_launch_chain(const hm_dev_pic* d_pics, int n_pics, int log2_ct
     }
   }
   return launch_chain_impl(d_pics, n_pics, log2_ctb, chroma_format, bit_depth, rare_syntax, max_ctb_w, max_ctb_h, d_sync, sync_bytes, d_err, s, nullptr);
+}
+
+// The cut hm_launch_chain would take for these pictures, without launching anything (batch.cpp: the overlap plan of
+// hm_batch_execute): *per_picture = a wave per picture, *resident = the waves of it the device holds at once, *split_fraction =
+// split_round_fraction where a partial last round can get a launch of its own (split_fraction_of; 0: it cannot).  At most
+// CHAIN_ROUNDS_MIN_PICS pictures: answered "not a wave per picture" without walking the ladder.
+// 1 = answered, 0 = the chain kernel does not apply, < 0 = error
+extern "C" int hm_chain_plan(const hm_dev_pic* d_pics, int n_pics, int log2_ctb, int chroma_format, int bit_depth, int rare_syntax, int max_ctb_w,
+                             int max_ctb_h, uint32_t* d_sync, size_t sync_bytes, uint32_t* d_err, int* per_picture, long* resident, int* split_fraction)
+{
+  *per_picture = 0;
+  *resident = 0;
+  *split_fraction = 0;
+  if (n_pics <= CHAIN_ROUNDS_MIN_PICS) return 1; // (not rounds of a wave per picture: the ladder is not walked for the few-pictures paths)
+  ChainPlan plan;
+  const int q = launch_chain_impl(d_pics, n_pics, log2_ctb, chroma_format, bit_depth, rare_syntax, max_ctb_w, max_ctb_h, d_sync, sync_bytes, d_err, nullptr, &plan);
+  if (q <= 0) return q;
+  *per_picture = plan.per_picture ? 1 : 0;
+  *resident = plan.resident;
+  *split_fraction = split_fraction_of(n_pics, d_sync, d_err);
+  return 1;
 }
 
 // bytes of the synchronisation buffer hm_launch_chain wants for its wave-per-row-pair mode (0: never uses it)

@@ -66,6 +66,14 @@ int hm_launch_residual(const struct hm_dev_pic* d_pics, int n_pics, int max_ctb_
 // hm_batch_check.  hm_chain_sync_bytes: the size that mode needs.
 int hm_launch_chain(const struct hm_dev_pic* d_pics, int n_pics, int log2_ctb, int chroma_format, int bit_depth, int rare_syntax,
                     int max_ctb_w, int max_ctb_h, uint32_t* d_sync, size_t sync_bytes, uint32_t* d_err, hipStream_t s);
+// ... the cut that call would take, nothing launched: *per_picture (a wave per picture), *resident (the waves of it the device
+// holds at once), *split_fraction (a partial last round of at most 1 / (this x full rounds) of a round gets a launch of its own;
+// 0: never).  1 = answered, 0 = not applicable, < 0 = error
+int hm_chain_plan(const struct hm_dev_pic* d_pics, int n_pics, int log2_ctb, int chroma_format, int bit_depth, int rare_syntax,
+                  int max_ctb_w, int max_ctb_h, uint32_t* d_sync, size_t sync_bytes, uint32_t* d_err, int* per_picture, long* resident,
+                  int* split_fraction);
+// (test hook, test_hooks.cpp) groups of the batch's last hm_batch_execute and the image index behind its first group
+int hm_batch_last_groups(const hm_batch* b, int* first_cut);
 #include "hm_knobs.h" // hm_knob / hm_knob_set
 size_t hm_chain_sync_bytes(int n_pics, int chroma_format, int max_ctb_h);
 int hm_launch_deblock(const struct hm_dev_pic* d_pics, int n_pics, int max_w4, int max_h4, int chroma_format,

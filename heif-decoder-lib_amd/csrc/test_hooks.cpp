@@ -26,6 +26,9 @@ extern "C" {
 
 __attribute__((visibility("default"))) int hm_debug_set(const char* name, int value) { return hm_knob_set(name, value); }
 
+// groups of the batch's last hm_batch_execute (1: the single stream) and the image index behind the first of them (hm_overlap_plan.h)
+__attribute__((visibility("default"))) int hm_debug_batch_groups(const hm_batch* b, int* first_cut) { return hm_batch_last_groups(b, first_cut); }
+
 // registers and scratch of a hot-path kernel as the loaded code object has them (hm_internal.h)
 __attribute__((visibility("default"))) int hm_debug_kernel_regs(int which, int a, int b, int c, int out[2])
 {

@@ -237,15 +237,20 @@ HM_API int  hm_batch_set_colour(hm_batch* b, const hm_colour_desc* d, int n_imag
 /* hm_batch_upload + hm_batch_execute in one call, the command streams split into `chunks` parts: the H2D copy of part
  * i+1 (on `copy_stream`) runs under the kernels of part i (on `stream`).  Asynchronous. */
 HM_API int  hm_batch_upload_execute(hm_batch* b, int stages, int chunks, void* copy_stream, void* stream);
-/* per-kernel timing with HIP events on the launch stream: `slots` execute calls are kept (ring),
+/* per-kernel timing with HIP events on the launch streams: `slots` execute calls are kept (ring),
  * 0 switches it off (default) */
 HM_API int  hm_batch_set_profiling(hm_batch* b, int slots);
-/* Opt-in (0 / 1 = off, up to 8): the images of a batch whose tail is fused are executed as `groups` groups, each on a
- * stream of its own, joined on the caller's stream - the tail kernel of one group runs while the reconstruction of the
- * others drains (about +6 % throughput with 2-4 groups).  Per-kernel timings are not separable in this mode. */
+/* The images of a batch whose tail is fused can be executed as groups, each on a stream of its own, joined on the caller's
+ * stream - the tail kernel of one group runs while the reconstruction of the other drains.
+ * groups = 0 (the default): automatic - two groups of whole images once the batch holds two rounds or more of the chain
+ * kernel's resident waves (about 10 000 tiles of 512 x 512 on an MI355X), one stream below that: single images and small
+ * batches run exactly as with 1; 1: always the caller's stream alone; 2..8: that many equal groups.
+ * The pixels are the same in every mode. */
 HM_API int  hm_batch_set_concurrency(hm_batch* b, int groups);
 /* kernel times in ms of the execute call in `slot` (call index mod slots):
- * [0] reconstruction, [1] deblocking (V+H), [2] SAO+paste.  Waits for that call to finish. */
+ * [0] reconstruction, [1] deblocking (V+H), [2] SAO+paste.  Waits for that call to finish.
+ * An execute that ran in groups: each entry is the time during which at least one kernel of its kind was running on any
+ * of the groups' streams (the union of the groups' intervals), so the entries add up to more than the step. */
 HM_API int  hm_batch_get_timings(hm_batch* b, int slot, float ms[3]);
 /* the same plus [3] the colour conversion attached with hm_batch_set_colour (summed over the groups of images) */
 HM_API int  hm_batch_get_timings4(hm_batch* b, int slot, float ms[4]);

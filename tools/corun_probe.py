@@ -27,7 +27,8 @@ def main():
         gb.add_image([next(made)[1] for _ in range(NT)])
     gb.finish(st, 0)
     res = {}
-    for groups in [int(x) for x in os.environ.get("GROUPS", "0,2,3,4,6,8").split(",")]:
+    # (1: one stream; 0 is the automatic schedule now)
+    for groups in [int(x) for x in os.environ.get("GROUPS", "1,2,3,4,6,8").split(",")]:
         gb.batch.set_concurrency(groups)
         for _ in range(2):
             gb.step(st)
