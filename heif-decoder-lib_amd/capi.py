@@ -162,6 +162,14 @@ class DeviceView(C.Structure):
     _fields_ = [(n, C.c_int32) for n in "crop_x crop_y crop_w crop_h out_w out_h filter".split()]
 
 
+class OverlayInfo(C.Structure):
+    """hm_overlay_info"""
+    _fields_ = [("canvas_width", C.c_int32), ("canvas_height", C.c_int32), ("n_children", C.c_int32), ("background", C.c_uint16 * 4)]
+
+
+HM_ITEM_OTHER, HM_ITEM_HVC1, HM_ITEM_GRID, HM_ITEM_IDEN, HM_ITEM_IOVL = 0, 1, 2, 3, 4
+
+
 class SequenceInfo(C.Structure):
     """hm_sequence_info"""
     _fields_ = [("is_sequence", C.c_int32), ("frame_count", C.c_uint32), ("duration", C.c_uint64)]
@@ -211,6 +219,11 @@ def bind_image(L):
     L.hm_file_primary_item.restype = C.c_uint32
     L.hm_file_image_info.argtypes = [C.c_void_p, C.c_uint32, C.POINTER(ImageInfo)]
     L.hm_file_sequence_info.argtypes = [C.c_void_p, C.POINTER(SequenceInfo)]
+    L.hm_file_top_level_images.argtypes = [C.c_void_p, C.POINTER(C.c_uint32), C.c_int]
+    L.hm_file_item_kind.argtypes = [C.c_void_p, C.c_uint32]
+    L.hm_file_overlay_info.argtypes = [C.c_void_p, C.c_uint32, C.POINTER(OverlayInfo), C.POINTER(C.c_uint32), C.POINTER(C.c_int32), C.c_int]
+    L.hm_file_derived_child.argtypes = [C.c_void_p, C.c_uint32, C.POINTER(C.c_uint32)]
+    L.hm_plan_overlay.argtypes = [C.c_void_p, C.c_uint32, C.POINTER(DecodeParams), C.POINTER(DeviceView), C.POINTER(C.c_int32), C.c_int]
     L.hm_decode_item.argtypes = [C.c_void_p, C.c_uint32, C.POINTER(DecodeParams), C.POINTER(Decoded)]
     L.hm_decoded_free.argtypes = [C.POINTER(Decoded)]
     L.hm_decoded_free.restype = None
@@ -373,3 +386,31 @@ class Batch:
             self.close()
         except Exception:
             pass
+
+
+def overlay_info(file_handle, item_id):
+    """hm_file_overlay_info -> dict(canvas=(w, h), background=[r, g, b, a], layers=[(item id, dx, dy)]) of an 'iovl' item"""
+    L = image_lib()
+    info = OverlayInfo()
+    check_image(L.hm_file_overlay_info(file_handle, item_id, C.byref(info), None, None, 0))
+    n = info.n_children
+    ids, offs = (C.c_uint32 * max(n, 1))(), (C.c_int32 * max(2 * n, 1))()
+    check_image(L.hm_file_overlay_info(file_handle, item_id, C.byref(info), ids, offs, n))
+    return dict(canvas=(info.canvas_width, info.canvas_height), background=list(info.background),
+                layers=[(ids[i], offs[2 * i], offs[2 * i + 1]) for i in range(n)])
+
+
+def derived_child(file_handle, item_id):
+    """hm_file_derived_child: the image an 'iden' item derives from"""
+    child = C.c_uint32()
+    check_image(image_lib().hm_file_derived_child(file_handle, item_id, C.byref(child)))
+    return child.value
+
+
+def plan_overlay(file_handle, item_id, params, view=None):
+    """hm_plan_overlay -> [True / False per layer]: which layers a decode (under `view`) decodes"""
+    L = image_lib()
+    n = check_image(L.hm_plan_overlay(file_handle, item_id, C.byref(params), C.byref(view) if view is not None else None, None, 0))
+    dec = (C.c_int32 * max(n, 1))()
+    check_image(L.hm_plan_overlay(file_handle, item_id, C.byref(params), C.byref(view) if view is not None else None, dec, n))
+    return [bool(dec[i]) for i in range(n)]

@@ -31,6 +31,9 @@ heif_error err(heif_error_code c, heif_suberror_code s, const char* m)
 }
 heif_error from_status(int rc)
 {
+  // derived images: the fork's codes for a bad 'iovl' payload (context.cc:320-358, 2612-2616)
+  if (rc == HM_ERR_BITSTREAM && hm_last_error_detail() == HM_DETAIL_INVALID_OVERLAY_DATA) return err(heif_error_Invalid_input, heif_suberror_Invalid_overlay_data, hm_last_error());
+  if (rc == HM_ERR_UNSUPPORTED && hm_last_error_detail() == HM_DETAIL_UNSUPPORTED_DATA_VERSION) return err(heif_error_Unsupported_feature, heif_suberror_Unsupported_data_version, hm_last_error());
   switch (rc) {
     case HM_ERR_UNSUPPORTED: return err(heif_error_Unsupported_feature, heif_suberror_Unsupported_codec, hm_last_error());
     case HM_ERR_BITSTREAM: return err(heif_error_Invalid_input, heif_suberror_Unspecified, hm_last_error());

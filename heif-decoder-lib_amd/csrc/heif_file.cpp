@@ -1,5 +1,6 @@
 // heif_file.cpp — see heif_file.h.  Written from ISO/IEC 14496-12 and 23008-12 box definitions.
 #include "heif_file.h"
+#include "hm_overlay_plan.h"
 
 #include <cstring>
 
@@ -103,7 +104,7 @@ std::vector<uint32_t> HeifFile::top_level_images() const
   }
   for (const auto& kv : items_) {
     const Item& it = kv.second;
-    if (it.type != "hvc1" && it.type != "grid") continue;
+    if (it.type != "hvc1" && it.type != "grid" && it.type != "iden" && it.type != "iovl") continue;
     bool sub = false;
     for (const Ref& r : refs_) {
       if ((r.type == "thmb" || r.type == "auxl") && r.from == it.id) sub = true;
@@ -403,6 +404,34 @@ bool HeifFile::grid_info(uint32_t id, GridInfo& g, HeifError& err) const
   g.tiles = references(id, "dimg");
   if ((int)g.tiles.size() != g.rows * g.cols) { err = {HM_ERR_BITSTREAM, "grid: number of dimg references != rows*cols"}; return false; }
   return true;
+}
+
+bool HeifFile::overlay_info(uint32_t id, OverlayInfo& o, HeifError& err) const
+{
+  const Item* it = item(id);
+  if (!it || it->type != "iovl") { err = {HM_ERR_INVALID_ARG, "item is not an overlay"}; return false; }
+  std::vector<uint8_t> d;
+  if (!item_data(id, d, err)) return false;
+  o.children = references(id, "dimg");
+  OverlayPayload p;
+  std::string msg;
+  const int rc = parse_overlay_payload(d.data(), d.size(), o.children.size(), p, msg);
+  if (rc) { err = {rc == 2 ? HM_ERR_UNSUPPORTED : HM_ERR_BITSTREAM, msg, rc == 2 ? HM_DETAIL_UNSUPPORTED_DATA_VERSION : HM_DETAIL_INVALID_OVERLAY_DATA}; return false; }
+  if (p.dx.size() != o.children.size()) { err = {HM_ERR_BITSTREAM, "Number of image offsets does not match the number of image references", HM_DETAIL_INVALID_OVERLAY_DATA}; return false; } // context.cc:2612-2616
+  o.width = p.width; o.height = p.height;
+  for (int i = 0; i < 4; i++) o.background[i] = p.background[i];
+  o.dx = p.dx; o.dy = p.dy;
+  return true;
+}
+
+uint32_t HeifFile::derived_child(uint32_t id, HeifError& err) const
+{
+  const Item* it = item(id);
+  if (!it || it->type != "iden") { err = {HM_ERR_INVALID_ARG, "item is not an identity derivation"}; return 0; }
+  const std::vector<uint32_t> r = references(id, "dimg");
+  if (r.size() != 1) { err = {HM_ERR_BITSTREAM, "'iden' image with more than one reference image"}; return 0; } // context.cc:2558-2562 (also: none)
+  if (r[0] == id) { err = {HM_ERR_BITSTREAM, "'iden' image referring to itself"}; return 0; }
+  return r[0];
 }
 
 // ---- the fork's movie mode ---------------------------------------------------------------------------------------

@@ -17,6 +17,7 @@ namespace hm {
 struct HeifError {
   int status;          // hm_status
   std::string message;
+  int detail = 0;      // hm_error_detail
 };
 
 struct NclxProfile {
@@ -73,6 +74,14 @@ struct GridInfo {
   std::vector<uint32_t> tiles; // item ids, row-major
 };
 
+// 'iovl' descriptor + 'dimg' references (context.cc:318-369, 2579-2616): the layers in reference order, bottom first
+struct OverlayInfo {
+  uint32_t width = 0, height = 0;
+  uint16_t background[4] = {0, 0, 0, 0}; // R G B A, 16 bit (the canvas is filled with R G B >> 8; A is ignored)
+  std::vector<uint32_t> children;
+  std::vector<int32_t> dx, dy;
+};
+
 // The fork's movie mode: ftyp lists the compatible brand 'hevc' or 'hevx' and a 'moov' box exists; 'meta' is then
 // ignored.  Every sample of the (first) track is an image: IDs 1..frame_count, ID 1 the primary one.
 struct Movie {
@@ -103,6 +112,10 @@ class HeifFile {
   // 'grid' descriptor + 'dimg' references (context.cc:172-221, 2142-2153)
   bool grid_info(uint32_t id, GridInfo& g, HeifError& err) const;
   std::vector<uint32_t> references(uint32_t from, const char* type) const;
+  // 'iovl' payload (hm_overlay_plan.h) + 'dimg' references
+  bool overlay_info(uint32_t id, OverlayInfo& o, HeifError& err) const;
+  // the one image an 'iden' item derives from (context.cc:2542-2576); 0 and err when the references are not exactly one other item
+  uint32_t derived_child(uint32_t id, HeifError& err) const;
   // the auxiliary image that is the alpha channel of image `id` (0 if none): an 'auxl' reference to `id` from an item
   // whose auxC names an alpha type (context.cc:885-945)
   uint32_t alpha_item_of(uint32_t id) const;

@@ -21,6 +21,7 @@
 
 #include "clap.h"
 #include "hm_image_job.h"
+#include "hm_overlay.h"
 #include "hm_planar.h"
 
 using namespace hm_img;
@@ -168,7 +169,7 @@ class Crew {
   bool quit_ = false;
 };
 
-int fail_from(const hm::HeifError& e) { return hm_fail(e.status, "%s", e.message.c_str()); }
+int fail_from(const hm::HeifError& e) { return e.detail ? hm_fail_detail(e.status, e.detail, e.message.c_str()) : hm_fail(e.status, "%s", e.message.c_str()); }
 
 } // namespace
 
@@ -223,12 +224,31 @@ int hm_file_image_info(const hm_file* f, uint32_t id, hm_image_info* info)
     info->width = it->props.ispe_width;
     info->height = it->props.ispe_height;
   }
-  else return hm_fail(HM_ERR_UNSUPPORTED, "item type '%s' is not an HEVC image or grid", it->type.c_str());
+  else if (it->type == "iden" || it->type == "iovl") {
+    // a derived item: the size its 'ispe' declares; depth and chroma format are those of its first non-virtual child, found
+    // through the first 'dimg' reference of every derived item on the way (context.cc:1377-1407)
+    if (it->props.ispe_width <= 0 || it->props.ispe_height <= 0) return hm_fail(HM_ERR_BITSTREAM, "Image has no 'ispe' property");
+    info->width = it->props.ispe_width;
+    info->height = it->props.ispe_height;
+    uint32_t cur = id;
+    for (int depth = 0;; depth++) {
+      const hm::Item* ci = f->file.item(cur);
+      if (!ci) return hm_fail(HM_ERR_BITSTREAM, "derived image references the missing item %u", cur);
+      if (ci->type != "grid" && ci->type != "iden" && ci->type != "iovl") { first = ci; break; }
+      if (depth > HM_OVL_MAX_DEPTH + 1) return hm_fail(HM_ERR_BITSTREAM, "derived images nested deeper than %d", HM_OVL_MAX_DEPTH);
+      const std::vector<uint32_t> refs = f->file.references(cur, "dimg");
+      if (refs.empty() || refs[0] == cur) return hm_fail(HM_ERR_BITSTREAM, "Derived image does not reference any other image items");
+      cur = refs[0];
+    }
+    if (first->type != "hvc1") return hm_fail(HM_ERR_UNSUPPORTED, "item type '%s' under a derived image is not an HEVC image", first->type.c_str());
+  }
+  else return hm_fail(HM_ERR_UNSUPPORTED, "item type '%s' is not an HEVC image, a grid or a derived image", it->type.c_str());
   if (!first->props.hvcc.present) return hm_fail(HM_ERR_BITSTREAM, "image without hvcC");
   info->bit_depth = first->props.hvcc.bit_depth_luma;
   info->chroma = first->props.hvcc.chroma_format;
   info->has_transforms = (it->props.has_irot || it->props.has_imir || it->props.has_clap) ? 1 : 0;
   info->has_alpha = f->file.alpha_item_of(id) != 0;
+  if (it->type == "iden" || it->type == "iovl") info->has_alpha = 0; // (context.cc:1370-1373)
   if (!info->has_alpha && it->type == "grid") { // (context.cc:1303-1368: a grid has alpha if one of its tiles has)
     hm::GridInfo g;
     hm::HeifError e2;
@@ -327,13 +347,15 @@ struct Lap {
 };
 
 // which coded pictures an image item consists of (context.cc:2120-2160: grid descriptor + dimg references)
-int plan_item(const hm_file* f, uint32_t id, ItemPlan& P)
+// self_grid: an hvc1 item as the 1 x 1 grid of itself (ItemPlan::self_grid)
+int plan_item(const hm_file* f, uint32_t id, ItemPlan& P, bool self_grid = false)
 {
   const hm::Item* it = f->file.item(id);
   if (!it) return hm_fail(HM_ERR_INVALID_ARG, "no item %u", id);
   hm::HeifError err;
   P.id = id;
   P.is_grid = it->type == "grid";
+  P.self_grid = false;
   if (P.is_grid) {
     hm::GridInfo g;
     if (!f->file.grid_info(id, g, err)) return fail_from(err);
@@ -343,7 +365,12 @@ int plan_item(const hm_file* f, uint32_t id, ItemPlan& P)
     P.tiles.resize(g.tiles.size());
     for (size_t i = 0; i < g.tiles.size(); i++) P.tiles[i].id = g.tiles[i];
   }
-  else if (it->type == "hvc1") { P.tiles.resize(1); P.tiles[0].id = id; P.cols = P.rows = 1; }
+  else if (it->type == "hvc1") {
+    P.tiles.resize(1); P.tiles[0].id = id; P.cols = P.rows = 1;
+    if (self_grid) { P.is_grid = P.self_grid = true; P.canvas_w = it->props.ispe_width; P.canvas_h = it->props.ispe_height; }
+  }
+  else if (it->type == "iden" || it->type == "iovl")
+    return hm_fail(HM_ERR_UNSUPPORTED, "derived image item ('%s') is not supported by the pipeline and sequence calls: decode it with hm_decode_item", it->type.c_str());
   else return hm_fail(HM_ERR_UNSUPPORTED, "item type '%s'", it->type.c_str());
   if (P.canvas_w < 0 || P.canvas_h < 0 || (P.is_grid && (P.canvas_w == 0 || P.canvas_h == 0))) return hm_fail(HM_ERR_BITSTREAM, "bad grid size");
   if (P.tiles.empty()) return hm_fail(HM_ERR_BITSTREAM, "image without coded pictures");
@@ -353,7 +380,7 @@ int plan_item(const hm_file* f, uint32_t id, ItemPlan& P)
   P.messages.assign(nt, std::string());
   // alpha auxiliary images of grid tile items: decode_image_planar attaches them to the tile image (context.cc:2029-2078)
   P.tile_alpha.clear();
-  if (P.is_grid)
+  if (P.is_grid && !P.self_grid)
     for (size_t i = 0; i < nt; i++) {
       const uint32_t a = f->file.alpha_item_of(P.tiles[i].id);
       if (!a) continue;
@@ -467,7 +494,7 @@ int planar_from_blobs(const hm_file* f, ItemPlan& P, const hm_decode_params* par
   for (int i = 0; i < nt; i++) {
     hm_tile_dest d;
     std::memset(&d, 0, sizeof(d));
-    const hm::Item* ti = is_grid ? f->file.item(P.tiles[i].id) : nullptr;
+    const hm::Item* ti = is_grid && !P.self_grid ? f->file.item(P.tiles[i].id) : nullptr; // (self_grid: the transformations are the item's, below)
     if (ti && !ti->props.transforms.empty() && !params->ignore_transformations) {
       const hm_pic* h = reinterpret_cast<const hm_pic*>(P.blobs[i].p);
       std::unique_ptr<OwnTile> o(new OwnTile());
@@ -688,7 +715,7 @@ bool view_subgrid(const hm_file* f, uint32_t id, const hm_decode_params* params,
 
 int job_plan(DecodeJob& j)
 {
-  int rc = plan_item(j.f, j.id, j.item[0]);
+  int rc = plan_item(j.f, j.id, j.item[0], j.self_grid);
   if (rc) return rc;
   j.n_items = 1;
   j.view_dx = j.view_dy = 0;
@@ -1112,6 +1139,446 @@ int job_complete(DecodeJob& j, hm_decoded*)
 
 } // namespace hm_img
 
+// ---- derived image items: 'iden' and 'iovl' -------------------------------------------------------------------------------
+// HeifContext::decode_derived_image / decode_overlay_image (context.cc:2542-2675).  A derived item is resolved recursively into
+// the coded images (hvc1 items, grids) under it; the entropy decode of ALL their pictures - tiles and alpha pictures included -
+// runs in one fan-out of the crew; every coded image then goes through the planar path of hm_decode_item on the call's stream (one
+// hm_batch each: merging them is not part of this), and k_overlay (overlay.hip) composes the layers of an overlay in one pass.
+//   iden : the child decoded with the transformation list child ++ iden (also applied to the attached alpha plane)
+//   iovl : layers bottom to top, each clipped to the canvas (DESIGN Q20); children that do not touch the canvas - under a view: the
+//          crop - are not decoded.  A nested overlay is composed into R, G, B planes first and enters as a layer with matrix 0 at
+//          full range (the copy arm of Op_YCbCr_to_RGB).  An hvc1 child for which the reference finds no colour chain (anything but
+//          4:4:4) is decoded as the 1 x 1 grid of itself (DESIGN Q19).
+namespace {
+
+bool is_derived_item(const hm_file* f, uint32_t id)
+{
+  const hm::Item* it = f->file.item(id);
+  return it && (it->type == "iden" || it->type == "iovl");
+}
+
+// the size an image handle reports after `list` (context.cc:810-838): what hm_file_image_info does for an item's own list
+void handle_size_after(const std::vector<hm::Transform>& list, int64_t& w, int64_t& h)
+{
+  for (const hm::Transform& t : list) {
+    if (t.kind == hm::Transform::CleanAperture && t.width_d && t.height_d && t.width_n <= 0x7FFFFFFFu && t.width_d <= 0x7FFFFFFFu &&
+        t.height_n <= 0x7FFFFFFFu && t.height_d <= 0x7FFFFFFFu) {
+      w = hm::Fraction((int32_t)t.width_n, (int32_t)t.width_d).round();
+      h = hm::Fraction((int32_t)t.height_n, (int32_t)t.height_d).round();
+    }
+    else if (t.kind == hm::Transform::Rotate && (t.angle == 90 || t.angle == 270)) std::swap(w, h);
+  }
+}
+
+// the size item `id` will have as a layer, from what the file declares (no picture is looked at): the plan decides with it which
+// children are decoded; the rectangle the kernel gets comes from the decoded size
+int declared_layer_size(const hm_file* f, uint32_t id, bool ignore_transformations, int depth, int64_t& w, int64_t& h)
+{
+  if (depth > HM_OVL_MAX_DEPTH) return hm_fail(HM_ERR_BITSTREAM, "derived images nested deeper than %d", HM_OVL_MAX_DEPTH);
+  const hm::Item* it = f->file.item(id);
+  if (!it) return hm_fail(HM_ERR_BITSTREAM, "derived image references the missing item %u", id);
+  hm::HeifError err;
+  if (it->type == "iden") {
+    const uint32_t child = f->file.derived_child(id, err);
+    if (!child) return fail_from(err);
+    const int rc = declared_layer_size(f, child, ignore_transformations, depth + 1, w, h);
+    if (rc) return rc;
+  }
+  else if (it->type == "iovl") {
+    hm::OverlayInfo o;
+    if (!f->file.overlay_info(id, o, err)) return fail_from(err);
+    w = o.width; h = o.height;
+  }
+  else if (it->type == "grid") {
+    hm::GridInfo g;
+    if (!f->file.grid_info(id, g, err)) return fail_from(err);
+    w = g.width; h = g.height;
+  }
+  else if (it->type == "hvc1") { w = it->props.ispe_width; h = it->props.ispe_height; }
+  else return hm_fail(HM_ERR_UNSUPPORTED, "item type '%s' under a derived image", it->type.c_str());
+  if (!ignore_transformations) handle_size_after(it->props.transforms, w, h);
+  return HM_OK;
+}
+
+// what the kernel (or emit_image) gets of a decoded node
+struct LayerImage {
+  DevPlane* P[3] = {nullptr, nullptr, nullptr}; // Y, Cb, Cr - or G, B, R of a composed overlay
+  DevPlane* alpha = nullptr;
+  int w = 0, h = 0, chroma = 0;
+  int has_nclx = 0, matrix = 2, primaries = 2, full_range = 1;
+};
+
+struct DerivedNode {
+  uint32_t id = 0;
+  bool overlay = false;
+  std::vector<hm::Transform> list; // overlay: its own transformations ++ those of the 'iden' items above; coded: those of the 'iden' items above
+  // a coded image (hvc1 / grid)
+  std::unique_ptr<DecodeJob> job;
+  // an overlay
+  hm::OverlayInfo info;
+  std::vector<std::unique_ptr<DerivedNode>> children; // NULL: the child touches nothing that is asked for and is not decoded
+  DevPlane rgb[3]; // R, G, B of the composed canvas (a nested or transformed overlay)
+};
+
+// everything one call holds; the stream is drained before any of it is released
+struct DerivedRun {
+  const hm_file* f = nullptr;
+  hm_decode_params params{};       // the caller's
+  hm_decode_params child_params{}; // what the coded images are decoded with: native planes, no caller buffer
+  hipStream_t s = nullptr;
+  std::unique_ptr<DerivedNode> root;
+  std::vector<DecodeJob*> jobs;    // every coded image under the root, in decode order
+  std::vector<std::unique_ptr<DevMem>> retired;
+  std::vector<void*> pinned;       // layer tables
+  PlanarImage final_image;
+  DevMem dout;
+  DevPlane alpha_sdr;
+  hm_view_scratch view_scratch{};
+  bool enqueued = false;
+  ~DerivedRun()
+  {
+    if (enqueued) hipStreamSynchronize(s);
+    for (void* p : pinned) hm_pool_pinned_free(p);
+    hm_view_scratch_free(&view_scratch);
+  }
+};
+
+// deepest coded picture (image, tiles, alpha pictures) under a coded image item, from the hvcC boxes
+int declared_depth(const hm_file* f, uint32_t id)
+{
+  const hm::Item* it = f->file.item(id);
+  if (!it) return 0;
+  int bd = 0;
+  auto take = [&](uint32_t pid) {
+    const hm::Item* pi = f->file.item(pid);
+    if (pi && pi->props.hvcc.present) bd = std::max(bd, std::max(pi->props.hvcc.bit_depth_luma, pi->props.hvcc.bit_depth_chroma));
+    const uint32_t a = f->file.alpha_item_of(pid);
+    const hm::Item* ai = a ? f->file.item(a) : nullptr;
+    if (ai && ai->type == "hvc1" && ai->props.hvcc.present) bd = std::max(bd, ai->props.hvcc.bit_depth_luma);
+    if (ai && ai->type == "grid")
+      for (uint32_t t : f->file.references(a, "dimg")) {
+        const hm::Item* ti = f->file.item(t);
+        if (ti && ti->props.hvcc.present) bd = std::max(bd, ti->props.hvcc.bit_depth_luma);
+      }
+  };
+  take(id);
+  if (it->type == "grid")
+    for (uint32_t t : f->file.references(id, "dimg")) take(t);
+  return bd;
+}
+
+// Resolves item `id` into a node.  above: the transformations of the 'iden' items passed on the way down (applied behind the
+// node's own); crop (may be NULL; the root only): the rectangle of the result a view asks for; path: the derived items above
+// (reference cycles).  Every refusal that needs no picture happens here, before a device is needed.
+int build_node(DerivedRun& R, uint32_t id, int depth, const std::vector<hm::Transform>& above, const hm_device_view* crop, std::vector<uint32_t>& path,
+               std::unique_ptr<DerivedNode>& out)
+{
+  const hm_file* f = R.f;
+  if (depth > HM_OVL_MAX_DEPTH) return hm_fail(HM_ERR_BITSTREAM, "derived images nested deeper than %d", HM_OVL_MAX_DEPTH);
+  const hm::Item* it = f->file.item(id);
+  if (!it) return hm_fail(HM_ERR_BITSTREAM, "derived image references the missing item %u", id);
+  for (uint32_t p : path)
+    if (p == id) return hm_fail(HM_ERR_BITSTREAM, "derived image items reference each other in a cycle (item %u)", id);
+  hm::HeifError err;
+  const bool ignore = R.params.ignore_transformations != 0;
+  if (it->type == "iden" || it->type == "iovl") {
+    if (f->file.alpha_item_of(id)) return hm_fail(HM_ERR_UNSUPPORTED, "an alpha auxiliary image attached to the derived item %u ('%s') is not supported", id, it->type.c_str());
+    std::vector<hm::Transform> list;
+    if (!ignore) { list = it->props.transforms; list.insert(list.end(), above.begin(), above.end()); }
+    path.push_back(id);
+    int rc = HM_OK;
+    if (it->type == "iden") {
+      const uint32_t child = f->file.derived_child(id, err);
+      if (!child) return fail_from(err);
+      rc = build_node(R, child, depth + 1, list, nullptr, path, out);
+      path.pop_back();
+      return rc;
+    }
+    std::unique_ptr<DerivedNode> n(new DerivedNode());
+    n->id = id; n->overlay = true; n->list = list;
+    if (!f->file.overlay_info(id, n->info, err)) return fail_from(err);
+    if (n->info.width > 32768 || n->info.height > 32768) return hm_fail(HM_ERR_BITSTREAM, "Image size exceeds the maximum of 32768x32768 (security limit)");
+    const bool use_crop = crop && list.empty() && crop->crop_w > 0 && crop->crop_h > 0;
+    n->children.resize(n->info.children.size());
+    for (size_t i = 0; i < n->info.children.size(); i++) {
+      int64_t w = 0, h = 0;
+      if ((rc = declared_layer_size(f, n->info.children[i], ignore, depth + 1, w, h))) return rc;
+      const hm_ovl_rect r = hm::overlay_clip(n->info.width, n->info.height, w, h, n->info.dx[i], n->info.dy[i], false);
+      const bool touches = use_crop ? hm::overlay_touches(r, crop->crop_x, crop->crop_y, crop->crop_w, crop->crop_h) : hm::overlay_touches(r);
+      if (!touches) continue;
+      if ((rc = build_node(R, n->info.children[i], depth + 1, {}, nullptr, path, n->children[i]))) return rc;
+    }
+    path.pop_back();
+    out = std::move(n);
+    return HM_OK;
+  }
+  if (it->type != "hvc1" && it->type != "grid") return hm_fail(HM_ERR_UNSUPPORTED, "item type '%s' under a derived image", it->type.c_str());
+  const int bd = declared_depth(f, id);
+  if (bd > 8) return hm_fail(HM_ERR_UNSUPPORTED, "derived images over pictures or alpha planes deeper than 8 bits (item %u: %d bits) are not supported", id, bd);
+  std::unique_ptr<DerivedNode> n(new DerivedNode());
+  n->id = id;
+  if (!ignore) n->list = above;
+  n->job.reset(new DecodeJob());
+  DecodeJob& j = *n->job;
+  j.f = f; j.id = id; j.params = R.child_params; j.s = R.s;
+  // Q19: the reference's first conversion has a chain for a 4:4:4 picture only
+  j.self_grid = it->type == "hvc1" && it->props.hvcc.present && it->props.hvcc.chroma_format != 3;
+  const int rc = job_plan(j);
+  if (rc) return rc;
+  R.jobs.push_back(&j);
+  out = std::move(n);
+  return HM_OK;
+}
+
+// the targets a derived item is refused for (no picture is looked at)
+int derived_target_check(const DerivedNode& root, const hm_decode_params* params, bool planes)
+{
+  const int of = params->out_format;
+  if (root.overlay) {
+    if (planes || (of != HM_OUT_RGB && of != HM_OUT_RGBA))
+      return hm_fail(HM_ERR_UNSUPPORTED, "an overlay ('iovl') item decodes to interleaved HM_OUT_RGB / HM_OUT_RGBA only (%s)",
+                     planes ? "device planes asked for" : of == 0 ? "out_format 0 asked for" : hm_out_is_planar(of) ? "a planar HM_OUT_YCBCR_* target asked for" : "an RRGGBB target asked for");
+    return HM_OK;
+  }
+  const bool native = planes || of == 0 || hm_out_is_planar(of);
+  if (native && !root.job->item[0].is_grid)
+    return hm_fail(HM_ERR_UNSUPPORTED, "an 'iden' item over a 4:4:4 coded image has R, G, B planes in the reference: planar and native targets are not supported");
+  return HM_OK;
+}
+
+int derived_prepare(DerivedRun& R, const hm_file* f, uint32_t id, const hm_decode_params* params, const hm_device_view* view, bool planes)
+{
+  R.f = f; R.params = *params; R.s = (hipStream_t)params->stream;
+  R.child_params = *params;
+  R.child_params.out_format = 0; R.child_params.ext_dst = nullptr; R.child_params.ext_dst_len = 0; R.child_params.ext_dst_stride = 0;
+  std::vector<uint32_t> path;
+  int rc = build_node(R, id, 0, {}, view, path, R.root);
+  if (rc) return rc;
+  return derived_target_check(*R.root, params, planes);
+}
+
+// a coded image on the device: hm_decode_item's planar path, its alpha plane at the image's size, then `list`
+int produce_coded(DerivedRun& R, DerivedNode& n, LayerImage& L)
+{
+  DecodeJob& j = *n.job;
+  hipStream_t s = R.s;
+  j.enqueued = true;
+  int rc = planar_from_blobs(R.f, j.item[0], &j.params, s, j.I);
+  if (rc) return rc;
+  DevPlane* alpha = nullptr;
+  if (j.n_items > 1) { // (job_enqueue: the auxiliary image's Y plane, scaled nearest neighbour to the image's size)
+    if ((rc = planar_from_blobs(R.f, j.item[1], &j.params, s, j.A))) return rc;
+    alpha = &j.A.P[0];
+    if (j.A.w != j.I.w || j.A.h != j.I.h) {
+      if ((rc = alloc_plane(j.alpha_scaled, j.I.w, j.I.h, 1))) return rc;
+      if ((rc = hm_launch_scale_nn(1, j.A.P[0].mem.p, j.A.P[0].stride, j.A.w, j.A.h, j.alpha_scaled.mem.p, j.alpha_scaled.stride, j.I.w, j.I.h, s))) return rc;
+      alpha = &j.alpha_scaled;
+    }
+  }
+  else if (j.I.tile_alpha_bd) alpha = &j.I.tile_alpha;
+  if (!n.list.empty()) {
+    int w = j.I.w, h = j.I.h;
+    if ((rc = apply_transforms(n.list, j.I.P, w, h, j.I.chroma, j.I.bd, s, j.I.retired))) return rc;
+    if (alpha) {
+      DevPlane ap[3];
+      ap[0].mem.swap(alpha->mem); ap[0].w = alpha->w; ap[0].h = alpha->h; ap[0].stride = alpha->stride;
+      int aw = j.I.w, ah = j.I.h;
+      rc = apply_transforms(n.list, ap, aw, ah, 0, 8, s, j.I.retired);
+      alpha->mem.swap(ap[0].mem); alpha->w = ap[0].w; alpha->h = ap[0].h; alpha->stride = ap[0].stride;
+      if (rc) return rc;
+    }
+    j.I.w = w; j.I.h = h;
+  }
+  for (int c = 0; c < 3; c++) L.P[c] = j.I.P[c].mem.p ? &j.I.P[c] : nullptr;
+  L.alpha = alpha;
+  L.w = j.I.w; L.h = j.I.h; L.chroma = j.I.chroma;
+  // (emit_image: a grid canvas carries no nclx, a single image its own)
+  L.has_nclx = j.I.is_grid ? 0 : 1;
+  L.matrix = j.I.native.matrix; L.primaries = j.I.native.primaries; L.full_range = j.I.native.full_range;
+  return HM_OK;
+}
+
+void layer_of(const LayerImage& L, const hm_ovl_rect& r, hm_overlay_layer& o)
+{
+  std::memset(&o, 0, sizeof(o));
+  o.rect = r;
+  const DevPlane* pl[4] = {L.P[0], L.P[1], L.P[2], L.alpha};
+  for (int c = 0; c < 4; c++)
+    if (pl[c]) { o.plane[c] = pl[c]->mem.p; o.pitch[c] = pl[c]->stride; o.plane_w[c] = pl[c]->w; o.plane_h[c] = pl[c]->h; }
+  o.width = L.w; o.height = L.h; o.chroma = L.chroma;
+  o.has_nclx = L.has_nclx; o.matrix = L.matrix; o.primaries = L.primaries; o.full_range = L.full_range;
+}
+
+int launch_overlay(DerivedRun& R, const hm_overlay_job& job, const std::vector<hm_overlay_layer>& layers)
+{
+  void* pinned = nullptr;
+  void* device = nullptr;
+  const int rc = hm_launch_overlay(&job, layers.data(), (int)layers.size(), &pinned, &device, R.s);
+  if (pinned) R.pinned.push_back(pinned);
+  if (device) { R.retired.emplace_back(new DevMem()); R.retired.back()->p = device; }
+  return rc;
+}
+
+int produce_node(DerivedRun& R, DerivedNode& n, LayerImage& L);
+
+// the layers of an overlay decoded and composed: interleaved into `interleaved` (out_kind RGB24 / RGBA32, pitch), or into n.rgb
+int compose_overlay(DerivedRun& R, DerivedNode& n, int out_kind, void* interleaved, int pitch)
+{
+  const int cw = (int)n.info.width, ch = (int)n.info.height;
+  std::vector<hm_overlay_layer> layers;
+  int rc;
+  for (size_t i = 0; i < n.children.size(); i++) {
+    if (!n.children[i]) continue;
+    LayerImage L;
+    if ((rc = produce_node(R, *n.children[i], L))) return rc;
+    const hm_ovl_rect r = hm::overlay_clip(cw, ch, L.w, L.h, n.info.dx[i], n.info.dy[i], L.alpha == nullptr);
+    if (!hm::overlay_touches(r)) continue; // (the decoded size differs from the declared one)
+    layers.emplace_back();
+    layer_of(L, r, layers.back());
+  }
+  hm_overlay_job job;
+  std::memset(&job, 0, sizeof(job));
+  job.width = cw; job.height = ch;
+  for (int c = 0; c < 3; c++) job.background[c] = (uint8_t)(n.info.background[c] >> 8); // fill_RGB_16bit, pixelimage.cc:947-1019
+  job.out_kind = out_kind;
+  if (out_kind == HM_OVL_OUT_PLANES) {
+    for (int c = 0; c < 3; c++) {
+      if ((rc = alloc_plane(n.rgb[c], cw, ch, 1))) return rc;
+      job.out[c] = n.rgb[c].mem.p;
+    }
+    job.out_pitch = n.rgb[0].stride;
+  }
+  else { job.out[0] = interleaved; job.out_pitch = pitch; }
+  return launch_overlay(R, job, layers);
+}
+
+int produce_node(DerivedRun& R, DerivedNode& n, LayerImage& L)
+{
+  if (!n.overlay) return produce_coded(R, n, L);
+  int rc = compose_overlay(R, n, HM_OVL_OUT_PLANES, nullptr, 0);
+  if (rc) return rc;
+  int w = (int)n.info.width, h = (int)n.info.height;
+  if (!n.list.empty() && (rc = apply_transforms(n.list, n.rgb, w, h, 3, 8, R.s, R.retired))) return rc;
+  // R, G, B as the planes of a GBR image: Cr -> R, Y -> G, Cb -> B (yuv2rgb.cc:207-212)
+  L.P[0] = &n.rgb[1]; L.P[1] = &n.rgb[2]; L.P[2] = &n.rgb[0];
+  L.alpha = nullptr;
+  L.w = w; L.h = h; L.chroma = 3;
+  L.has_nclx = 1; L.matrix = 0; L.primaries = 2; L.full_range = 1;
+  return HM_OK;
+}
+
+// what a derived item is refused for without looking at a picture (the device entry points ask before they need a device)
+int derived_refusal(const hm_file* f, uint32_t id, const hm_decode_params* params, bool planes)
+{
+  DerivedRun R;
+  return derived_prepare(R, f, id, params, nullptr, planes);
+}
+
+// hm_decode_item and its device forms on a derived item
+int decode_derived(const hm_file* f, uint32_t id, const hm_decode_params* params, const hm_device_dest* dest, const hm_device_view* view, const hm_device_planes* planes,
+                   hm_decoded* out)
+{
+  std::memset(out, 0, sizeof(*out));
+  Lap lap;
+  DerivedRun R;
+  int rc = derived_prepare(R, f, id, params, view, planes != nullptr);
+  if (rc) return rc;
+  // ---- host: the entropy decode of every coded picture under the item, one fan-out ----
+  std::vector<std::pair<DecodeJob*, int>> work;
+  for (DecodeJob* j : R.jobs)
+    for (int k = 0, nk = job_tile_count(*j); k < nk; k++) work.push_back({j, k});
+  const int nt = (int)work.size();
+  for (DecodeJob* j : R.jobs) j->few_pictures = nt <= 64;
+  std::atomic<int> next{0};
+  int nthreads = params->host_threads > 0 ? params->host_threads : 1;
+  const int row_threads = nt > 0 && nthreads > nt ? nthreads / nt : 1;
+  auto worker = [&]() {
+    for (;;) {
+      const int i = next.fetch_add(1);
+      if (i >= nt) break;
+      job_parse_tile(*work[i].first, work[i].second, row_threads);
+    }
+  };
+  if (nthreads > nt) nthreads = nt;
+  if (nt > 0) Crew::instance().run(nthreads, worker);
+  lap("host entropy decode done");
+  // what only the pictures say, before anything is queued: the composition is one of 8-bit samples
+  for (DecodeJob* j : R.jobs)
+    for (int i = 0; i < j->n_items; i++) {
+      ItemPlan& P = j->item[i];
+      for (size_t k = 0; k < P.blobs.size(); k++) {
+        if (P.status[k]) return tile_failure(P, (int)k);
+        const hm_pic* h = reinterpret_cast<const hm_pic*>(P.blobs[k].p);
+        if (h->bit_depth_y > 8 || h->bit_depth_c > 8)
+          return hm_fail(HM_ERR_UNSUPPORTED, "derived images over pictures or alpha planes deeper than 8 bits (item %u: %d bits) are not supported", P.tiles[k].id, (int)h->bit_depth_y);
+        if (i == 0 && P.self_grid != (h->chroma_format != 3) && !P.is_grid)
+          return hm_fail(HM_ERR_BITSTREAM, "item %u: the picture's chroma format differs from its hvcC", P.tiles[k].id);
+      }
+      for (size_t k = 0; k < P.alpha_blobs.size(); k++) {
+        if (P.alpha_status[k]) return hm_fail(P.alpha_status[k], "alpha image of tile %d (item %u): %s", P.tile_alpha[k].tile, P.tile_alpha[k].id, P.alpha_messages[k].c_str());
+        if (reinterpret_cast<const hm_pic*>(P.alpha_blobs[k].p)->bit_depth_y > 8)
+          return hm_fail(HM_ERR_UNSUPPORTED, "derived images over pictures or alpha planes deeper than 8 bits (item %u) are not supported", P.tile_alpha[k].id);
+      }
+    }
+  R.enqueued = true;
+  rc = [&]() -> int {
+  DerivedNode& root = *R.root;
+  PlanarImage& I = R.final_image;
+  if (!root.overlay) { // 'iden' over a coded image: the image itself with the longer list
+    LayerImage L;
+    if ((rc = produce_coded(R, root, L))) return rc;
+    if (L.alpha) out->has_alpha = 1;
+    rc = emit_image(params, R.s, root.job->I, L.alpha, 8, R.dout, R.alpha_sdr, out, dest, view, &R.view_scratch, nullptr, planes);
+    if (L.alpha && !rc) out->has_alpha = 1;
+  }
+  else {
+    const int obpp = params->out_format == HM_OUT_RGBA ? 4 : 3;
+    const int kind = obpp == 4 ? HM_OVL_OUT_RGBA32 : HM_OVL_OUT_RGB24;
+    int w = (int)root.info.width, h = (int)root.info.height;
+    if (root.list.empty()) { // the kernel writes the interleaved result directly
+      const int pitch = hm_plane_stride(w, obpp);
+      if ((rc = I.rgb.alloc((size_t)pitch * mem_rows(h)))) return rc;
+      if ((rc = compose_overlay(R, root, kind, I.rgb.p, pitch))) return rc;
+    }
+    else { // planes, the transformations (as a 4:4:4 image), then the same kernel with that one opaque layer interleaves
+      LayerImage L;
+      if ((rc = produce_node(R, root, L))) return rc;
+      w = L.w; h = L.h;
+      const int pitch = hm_plane_stride(w, obpp);
+      if ((rc = I.rgb.alloc((size_t)pitch * mem_rows(h)))) return rc;
+      std::vector<hm_overlay_layer> one(1);
+      layer_of(L, hm::overlay_clip(w, h, w, h, 0, 0, true), one[0]);
+      hm_overlay_job job;
+      std::memset(&job, 0, sizeof(job));
+      job.width = w; job.height = h; job.out_kind = kind; job.out[0] = I.rgb.p; job.out_pitch = pitch;
+      if ((rc = launch_overlay(R, job, one))) return rc;
+    }
+    // everything behind is hm_decode_item's: the result as an 8-bit 4:4:4 image whose conversion is done (I.rgb_attached) and
+    // which carries no profile of its own, like a grid canvas - the converted image then reports the sRGB defaults
+    I.w = w; I.h = h; I.chroma = 3; I.bd = 8; I.is_grid = true; I.rgb_attached = true;
+    I.native = hm::NclxProfile();
+    rc = emit_image(params, R.s, I, nullptr, 0, R.dout, R.alpha_sdr, out, dest, view, &R.view_scratch, nullptr, nullptr);
+  }
+  return rc;
+  }();
+  if (!rc) {
+    const hipError_t e = hipStreamSynchronize(R.s);
+    if (e != hipSuccess) rc = hm_check_hip(e, "kernel execution");
+  }
+  if (!rc)
+    for (DecodeJob* j : R.jobs)
+      for (PlanarImage* im : {&j->I, &j->A})
+        if (im->batch && !rc) rc = hm_batch_check(im->batch.get());
+  lap("stream drained");
+  if (rc) {
+    hipStreamSynchronize(R.s);
+    hm_decoded_free(out);
+  }
+  return rc;
+}
+
+} // namespace
+
 extern "C" {
 
 static int decode_grid_cut(const hm_file* f, uint32_t id, const hm_decode_params* params, const int32_t* devices, int n_devices, bool pipelined, hm_decoded* out, bool* applicable,
@@ -1129,6 +1596,7 @@ int hm_decode_item_to_device(const hm_file* f, uint32_t id, const hm_decode_para
 {
   if (!f || !params || !dest || !out) return hm_fail(HM_ERR_INVALID_ARG, "null argument");
   std::memset(out, 0, sizeof(*out));
+  if (is_derived_item(f, id)) { const int drc = derived_refusal(f, id, params, false); if (drc) return drc; }
   const int rc = check_device_request(f, id, params, dest); // refused before any work is queued: the destination is not written
   if (rc) return rc;
   return decode_item(f, id, params, dest, out);
@@ -1138,6 +1606,7 @@ int hm_decode_item_to_device_view(const hm_file* f, uint32_t id, const hm_decode
 {
   if (!f || !params || !view || !dest || !out) return hm_fail(HM_ERR_INVALID_ARG, "null argument");
   std::memset(out, 0, sizeof(*out));
+  if (is_derived_item(f, id)) { const int drc = derived_refusal(f, id, params, false); if (drc) return drc; }
   const int rc = check_device_request(f, id, params, dest, view); // refused before any work is queued: the destination is not written
   if (rc) return rc;
   return decode_item(f, id, params, dest, out, view);
@@ -1147,6 +1616,7 @@ int hm_decode_item_to_device_planes(const hm_file* f, uint32_t id, const hm_deco
 {
   if (!f || !params || !planes || !out) return hm_fail(HM_ERR_INVALID_ARG, "null argument");
   std::memset(out, 0, sizeof(*out));
+  if (is_derived_item(f, id)) { const int drc = derived_refusal(f, id, params, true); if (drc) return drc; }
   const int rc = check_planes_request(f, id, params, planes); // refused before any work is queued: no plane is written
   if (rc) return rc;
   return decode_item(f, id, params, nullptr, out, nullptr, planes);
@@ -1157,6 +1627,7 @@ int hm_decode_item_to_device_planes_view(const hm_file* f, uint32_t id, const hm
 {
   if (!f || !params || !view || !planes || !out) return hm_fail(HM_ERR_INVALID_ARG, "null argument");
   std::memset(out, 0, sizeof(*out));
+  if (is_derived_item(f, id)) { const int drc = derived_refusal(f, id, params, true); if (drc) return drc; }
   const int rc = check_planes_request(f, id, params, planes, view); // refused before any work is queued: no plane is written
   if (rc) return rc;
   return decode_item(f, id, params, nullptr, out, view, planes);
@@ -1169,6 +1640,66 @@ int hm_plan_planes_view(const hm_file* f, uint32_t id, const hm_decode_params* p
   int x0, y0, w, h;
   view_subgrid(f, id, params, view, tiles, &x0, &y0, &w, &h, true);
   return HM_OK;
+}
+
+int hm_file_item_kind(const hm_file* f, uint32_t id)
+{
+  if (!f) return hm_fail(HM_ERR_INVALID_ARG, "null file");
+  const hm::Item* it = f->file.item(id);
+  if (!it) return hm_fail(HM_ERR_INVALID_ARG, "no item %u", id);
+  if (it->type == "hvc1") return HM_ITEM_HVC1;
+  if (it->type == "grid") return HM_ITEM_GRID;
+  if (it->type == "iden") return HM_ITEM_IDEN;
+  if (it->type == "iovl") return HM_ITEM_IOVL;
+  return HM_ITEM_OTHER;
+}
+
+int hm_file_overlay_info(const hm_file* f, uint32_t id, hm_overlay_info* info, uint32_t* children, int32_t* offsets, int max_children)
+{
+  if (!f || !info) return hm_fail(HM_ERR_INVALID_ARG, "null argument");
+  std::memset(info, 0, sizeof(*info));
+  const hm::Item* it = f->file.item(id);
+  if (!it) return hm_fail(HM_ERR_INVALID_ARG, "no item %u", id);
+  hm::OverlayInfo o;
+  hm::HeifError err;
+  if (!f->file.overlay_info(id, o, err)) return fail_from(err);
+  info->canvas_width = (int32_t)std::min<uint32_t>(o.width, 0x7FFFFFFFu);
+  info->canvas_height = (int32_t)std::min<uint32_t>(o.height, 0x7FFFFFFFu);
+  for (int c = 0; c < 4; c++) info->background[c] = o.background[c];
+  info->n_children = (int32_t)o.children.size();
+  for (int i = 0; i < (int)o.children.size() && i < max_children; i++) {
+    if (children) children[i] = o.children[i];
+    if (offsets) { offsets[2 * i] = o.dx[i]; offsets[2 * i + 1] = o.dy[i]; }
+  }
+  return HM_OK;
+}
+
+int hm_file_derived_child(const hm_file* f, uint32_t id, uint32_t* child)
+{
+  if (!f || !child) return hm_fail(HM_ERR_INVALID_ARG, "null argument");
+  *child = 0;
+  if (!f->file.item(id)) return hm_fail(HM_ERR_INVALID_ARG, "no item %u", id);
+  hm::HeifError err;
+  const uint32_t c = f->file.derived_child(id, err);
+  if (!c) return fail_from(err);
+  *child = c;
+  return HM_OK;
+}
+
+int hm_plan_overlay(const hm_file* f, uint32_t id, const hm_decode_params* params, const hm_device_view* view, int32_t* decoded, int max_children)
+{
+  if (!f || !params) return hm_fail(HM_ERR_INVALID_ARG, "null argument");
+  const hm::Item* it = f->file.item(id);
+  if (!it) return hm_fail(HM_ERR_INVALID_ARG, "no item %u", id);
+  if (it->type != "iovl") return hm_fail(HM_ERR_INVALID_ARG, "item %u is not an overlay", id);
+  DerivedRun R;
+  R.f = f; R.params = *params; R.child_params = *params; R.child_params.out_format = 0;
+  std::vector<uint32_t> path;
+  const int rc = build_node(R, id, 0, {}, view, path, R.root);
+  if (rc) return rc;
+  const int n = (int)R.root->children.size();
+  for (int i = 0; i < n && i < max_children && decoded; i++) decoded[i] = R.root->children[i] ? 1 : 0;
+  return n;
 }
 
 int hm_plan_view(const hm_file* f, uint32_t id, const hm_decode_params* params, const hm_device_view* view, int32_t tiles[4])
@@ -1187,6 +1718,7 @@ static int decode_item(const hm_file* f, uint32_t id, const hm_decode_params* pa
                        const hm_device_planes* planes)
 {
   std::memset(out, 0, sizeof(*out)); // (whatever fails below: nothing of an earlier call is left in it)
+  if (is_derived_item(f, id)) return decode_derived(f, id, params, dest, view, planes, out);
   if (!view) { // (r06) a grid of more tiles than parsing threads, to interleaved pixels: slab by slab under the entropy decode (decode_grid_cut)
     bool applicable = false;
     const int prc = decode_grid_cut(f, id, params, nullptr, 1, /*pipelined=*/true, out, &applicable, dest);
@@ -1723,6 +2255,7 @@ static int decode_grid_cut(const hm_file* f, uint32_t id, const hm_decode_params
                            const hm_device_dest* ddest)
 {
   *applicable = false;
+  if (is_derived_item(f, id)) return HM_OK; // (not applicable: composed on one device)
   ItemPlan plan;
   int rc = plan_item(f, id, plan);
   if (rc) return rc;

@@ -86,6 +86,9 @@ struct TilePlan { uint32_t id = 0; int x0 = 0, y0 = 0; };
 struct ItemPlan {
   uint32_t id = 0;
   bool is_grid = false;
+  // a coded image decoded as the 1 x 1 grid of itself (DESIGN Q19: an hvc1 child of a derived item for which the reference finds no
+  // colour chain): the grid's paste and profile rules on its one picture; its own transformations stay the item's, not a tile's
+  bool self_grid = false;
   int canvas_w = 0, canvas_h = 0, cols = 0, rows = 0;
   std::vector<TilePlan> tiles;
   std::vector<Blob> blobs;           // command streams, filled by job_parse_tile
@@ -116,6 +119,7 @@ struct DecodeJob {
   // a planar result (out_format 0 / HM_OUT_YCBCR_*) goes to caller-owned device memory, plane by plane (has_planes; never together with has_dest)
   hm_device_planes planes{};
   bool has_planes = false;
+  bool self_grid = false; // item[0] is planned as the 1 x 1 grid of itself (ItemPlan::self_grid)
   hipStream_t s = nullptr;
   ItemPlan item[2];   // [0] the image, [1] its alpha auxiliary image
   int n_items = 0;

@@ -10,6 +10,7 @@
 #include <cstring>
 
 #include "hm_internal.h"
+#include "hm_overlay.h"
 #include "residual_tables.h"
 
 extern "C" const void* hm_chain_kernel_of(int log2_ctb, int bytes_per_sample, int mode); // chain.hip
@@ -21,6 +22,7 @@ extern "C" const void* hm_resample_kernel_of(int index);                        
 extern "C" const void* hm_resample_staged_kernel_of(int index);                             // ... the instances of k_resample_h_staged
 extern "C" const void* hm_resample_batch_kernel_of(int index);                              // ... the batched forms of all three passes
 extern "C" const void* hm_planes_view_kernel_of(int index);                                 // planes_view.hip: NULL behind the last instance
+extern "C" const void* hm_overlay_kernel_of(int index);                                     // overlay.hip: NULL behind the last instance
 
 extern "C" {
 
@@ -41,11 +43,24 @@ __attribute__((visibility("default"))) int hm_debug_kernel_regs(int which, int a
   else if (which == 5) fn = hm_resample_staged_kernel_of(a); // (k_resample_h_staged; out[1] counts scratch, not LDS)
   else if (which == 6) fn = hm_resample_batch_kernel_of(a); // (k_resample_h_batch, k_resample_h_staged_batch, k_resample_v_batch)
   else if (which == 7) fn = hm_planes_view_kernel_of(a); // (k_planes_resample_h, k_planes_resample_v, k_planes_view_nearest)
+  else if (which == 8) fn = hm_overlay_kernel_of(a); // (k_overlay: RGB24, RGBA32, planes)
   hipFuncAttributes fa;
   if (!fn || !out || hipFuncGetAttributes(&fa, fn) != hipSuccess) return -1;
   out[0] = fa.numRegs;
   out[1] = (int)fa.localSizeBytes;
   return 0;
+}
+
+// k_overlay on its own (measurement scripts: tools/bench_overlay.py): the layer table is uploaded and the kernel queued on `stream`;
+// *pinned / *device are the table's blocks, handed back through hm_debug_overlay_release once the stream has drained
+__attribute__((visibility("default"))) int hm_debug_overlay_launch(const hm_overlay_job* job, const hm_overlay_layer* layers, int n, void** pinned, void** device, void* stream)
+{
+  return hm_launch_overlay(job, layers, n, pinned, device, (hipStream_t)stream);
+}
+__attribute__((visibility("default"))) void hm_debug_overlay_release(void* pinned, void* device)
+{
+  if (pinned) hm_pool_pinned_free(pinned);
+  if (device) hm_pool_device_free(device);
 }
 
 // k_residual's constant tables (residual_tables.h), HM_RT_BYTES bytes into `out`: from_device = 0 the image as the host compiler

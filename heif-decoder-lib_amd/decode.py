@@ -253,9 +253,11 @@ def decode_batch_to_tensor(files, item_id=0, out_format="rgb", layout="chw", dty
                 dest = _dest_of(out[k], lay, code, c, sc, bi)
                 while True:
                     if views[k] is None:
-                        rc = capi.check_image(L.hm_pipeline_submit_to_device(pipe, data, len(data), ids[k], k, C.byref(dest)))
+                        rc = L.hm_pipeline_submit_to_device(pipe, data, len(data), ids[k], k, C.byref(dest))
                     else:
-                        rc = capi.check_image(L.hm_pipeline_submit_to_device_view(pipe, data, len(data), ids[k], k, C.byref(views[k]), C.byref(dest)))
+                        rc = L.hm_pipeline_submit_to_device_view(pipe, data, len(data), ids[k], k, C.byref(views[k]), C.byref(dest))
+                    if rc < 0:  # refused at submission (e.g. a derived item: the pipeline takes coded images and grids): name the file
+                        raise capi.HmError(rc, f"{names[k]}: {L.hm_last_error().decode()}")
                     if rc != capi.HM_PIPELINE_FULL:
                         break
                     take()

@@ -56,7 +56,9 @@ HM_API const char* hm_last_error(void);
  * maps HM_DETAIL_END_OF_DATA - a [length][NAL] record that runs past the pushed bytes - to heif_suberror_End_of_data as the
  * reference's plugin does (libheif/plugins/decoder_libde265.cc:276-292).  Set by the call that failed, HM_DETAIL_NONE otherwise. */
 typedef enum hm_error_detail { HM_DETAIL_NONE = 0, HM_DETAIL_END_OF_DATA = 1,
-  HM_DETAIL_NO_COLOUR_CHAIN = 2 /* convert_colorspace() finds no chain: heif_suberror_Unsupported_color_conversion */ } hm_error_detail;
+  HM_DETAIL_NO_COLOUR_CHAIN = 2 /* convert_colorspace() finds no chain: heif_suberror_Unsupported_color_conversion */,
+  HM_DETAIL_INVALID_OVERLAY_DATA = 3 /* an 'iovl' payload that is truncated, has a zero canvas size or too few offsets: heif_suberror_Invalid_overlay_data */,
+  HM_DETAIL_UNSUPPORTED_DATA_VERSION = 4 /* an 'iovl' payload of another version than 0: heif_suberror_Unsupported_data_version */ } hm_error_detail;
 HM_API int hm_last_error_detail(void);
 HM_API const char* hm_version(void);
 /* number of visible HIP devices (0 if none); does not initialise a context */
@@ -308,8 +310,10 @@ HM_API void hm_picture_free(hm_picture* p);
 typedef struct hm_file hm_file;
 
 typedef struct hm_image_info {
-  int32_t width, height;       /* output size (grid: the grid's output size; image: ispe)        */
-  int32_t bit_depth, chroma;   /* from the (first tile's) hvcC                                   */
+  int32_t width, height;       /* output size (grid: the grid's output size; image, 'iden', 'iovl': ispe) */
+  int32_t bit_depth, chroma;   /* from the (first tile's) hvcC; a derived item ('iden', 'iovl'): of its first non-virtual
+                                  child, found through the first reference of every derived item on the way (context.cc:1377-1407);
+                                  is_grid and has_alpha are 0 for a derived item (context.cc:1370-1373)   */
   int32_t is_grid, grid_rows, grid_cols, tile_width, tile_height;
   int32_t has_transforms;      /* irot / imir / clap present on the item                         */
   int32_t has_alpha;           /* an alpha auxiliary image is attached (heif_image_handle_has_alpha_channel) */
@@ -364,6 +368,21 @@ HM_API void     hm_file_close(hm_file* f);
 HM_API uint32_t hm_file_primary_item(const hm_file* f);
 HM_API int      hm_file_top_level_images(const hm_file* f, uint32_t* ids, int max_ids); /* returns the count */
 HM_API int      hm_file_image_info(const hm_file* f, uint32_t id, hm_image_info* info);
+/* what kind of item `id` is: HM_ITEM_*, or a negative status (no such item) */
+enum { HM_ITEM_OTHER = 0, HM_ITEM_HVC1 = 1, HM_ITEM_GRID = 2, HM_ITEM_IDEN = 3, HM_ITEM_IOVL = 4 };
+HM_API int      hm_file_item_kind(const hm_file* f, uint32_t id);
+/* An 'iovl' item (ImageOverlay, context.cc:318-369): the canvas, the 16-bit R G B A background (the canvas is filled with
+ * R G B >> 8; A is ignored) and the layers in reference order, bottom first.  children[i] / offsets[2 i], offsets[2 i + 1]: item ID
+ * and signed (x, y) offset of layer i, for i < min(n_children, max_children); either array may be NULL.
+ * HM_ERR_BITSTREAM: a truncated payload, a zero canvas size; HM_ERR_UNSUPPORTED: a payload version other than 0. */
+typedef struct hm_overlay_info {
+  int32_t canvas_width, canvas_height;
+  int32_t n_children;
+  uint16_t background[4];
+} hm_overlay_info;
+HM_API int      hm_file_overlay_info(const hm_file* f, uint32_t id, hm_overlay_info* info, uint32_t* children, int32_t* offsets, int max_children);
+/* the one image an 'iden' item derives from (context.cc:2542-2576).  HM_ERR_BITSTREAM: not exactly one reference, or one to itself */
+HM_API int      hm_file_derived_child(const hm_file* f, uint32_t id, uint32_t* child);
 /* the auxiliary image item that is the alpha channel of image `id` (context.cc:885-945), 0 if there is none */
 HM_API uint32_t hm_file_alpha_item(const hm_file* f, uint32_t id);
 /* The raw ('prof' / 'rICC') colour profile that goes with image `id` (passed through untouched; *data points into the
@@ -374,14 +393,20 @@ HM_API uint32_t hm_file_alpha_item(const hm_file* f, uint32_t id);
 HM_API int      hm_file_item_icc(const hm_file* f, uint32_t id, int for_handle, uint32_t* type, const uint8_t** data, size_t* size);
 /* the byte string a decoder plugin gets through push_data for an hvc1 item (free with hm_free) */
 HM_API int      hm_file_item_hevc_data(const hm_file* f, uint32_t id, uint8_t** out, size_t* out_size);
-/* decode an hvc1 image or a grid item.  Replaces heif_decode_image (heif.cc:1150-1186 ->
- * context.cc:1516-1600, 2120-2404).  Free the result with hm_decoded_free. */
+/* decode an hvc1 image, a grid or a derived item.  Replaces heif_decode_image (heif.cc:1150-1186 ->
+ * context.cc:1516-1600, 2120-2404, 2542-2675).  Free the result with hm_decoded_free.
+ * Derived items: an 'iden' item is its child decoded with the transformation list child ++ iden; an 'iovl' item is composed on the
+ * device (its layers clipped to the canvas; layers off the canvas are not decoded) and decodes to HM_OUT_RGB / HM_OUT_RGBA only.
+ * HM_ERR_UNSUPPORTED, before any work is queued: pictures or alpha planes deeper than 8 bits under a derived item, an alpha
+ * auxiliary image attached to the derived item itself, an 'iovl' item to out_format 0 / HM_OUT_YCBCR_* / RRGGBB*, an 'iden' item
+ * over a 4:4:4 hvc1 image to out_format 0 / HM_OUT_YCBCR_*.  HM_ERR_BITSTREAM: a bad 'iovl' payload, 'iden' without exactly one
+ * other reference, a reference to a missing item, a reference cycle, nesting deeper than 8.   */
 HM_API int      hm_decode_item(const hm_file* f, uint32_t id, const hm_decode_params* params, hm_decoded* out);
 /* The same with ONE GRID OVER SEVERAL DEVICES of this process: the grid's tile rows are cut into contiguous slabs, one per
  * entry of `devices` (HIP device indices; an index may repeat), each slab is decoded and converted on its device and copied
  * from there straight into its rows of params->ext_dst / of the pinned output plane - the in-process tile fan-out of the
  * reference (context.cc:2281-2294, 2361-2401) across GPUs, without any exchange between them.  Items that do not cut this
- * way (single images, planar output, alpha, transformed grids, forced bilinear up-sampling) are decoded on devices[0].
+ * way (single images, derived items, planar output, alpha, transformed grids, forced bilinear up-sampling) are decoded on devices[0].
  * params->stream must be NULL (every slab runs on a stream of its own).  hm_plan_device_slabs: the cut it uses. */
 HM_API int      hm_decode_item_devices(const hm_file* f, uint32_t id, const hm_decode_params* params, const int32_t* devices, int n_devices, hm_decoded* out);
 HM_API int      hm_plan_device_slabs(int grid_rows, int n_devices, int32_t* first_row, int32_t* row_count);
@@ -500,7 +525,8 @@ HM_API int64_t hm_device_dest_bytes(int out_format, int width, int height, const
 HM_API int hm_to_tensor(int out_format, int width, int height, const void* d_src, int src_stride, const hm_device_dest* dest, void* stream);
 /* hm_decode_item with the pixels going to `dest`: returns when they are in place (the work runs on params->stream).
  * `out` is filled as for an ext_dst decode: used_ext_dst = 1, every plane[] NULL, stride[0] = the row pitch in use.
- * params->ext_dst must be NULL. */
+ * params->ext_dst must be NULL.  A derived item ('iden', 'iovl') is decoded as by hm_decode_item and refused for the same
+ * reasons, before a device is needed. */
 HM_API int hm_decode_item_to_device(const hm_file* f, uint32_t id, const hm_decode_params* params, const hm_device_dest* dest, hm_decoded* out);
 /* hm_decode_sequence with one hm_device_dest per frame (e.g. `count` offsets into one N x C x H x W allocation) */
 HM_API int hm_decode_sequence_to_device(const hm_file* f, uint32_t first, int32_t count, const hm_decode_params* params, const hm_device_dest* dests,
@@ -621,7 +647,9 @@ typedef struct hm_device_view {
   int32_t filter;
 } hm_device_view;
 /* hm_decode_item_to_device with `dest` sized for out_w x out_h (hm_device_dest_bytes of that size); out->width / height: the
- * size written.  warnings: of the coded pictures that were decoded; a grid's profile fields: of the first tile decoded. */
+ * size written.  warnings: of the coded pictures that were decoded; a grid's profile fields: of the first tile decoded. 
+ * A derived item: the view is taken of the composed image; layers of an 'iovl' item without transformations that do not touch
+ * the crop are not decoded (hm_plan_overlay). */
 HM_API int hm_decode_item_to_device_view(const hm_file* f, uint32_t id, const hm_decode_params* params, const hm_device_view* view,
                                          const hm_device_dest* dest, hm_decoded* out);
 /* the pipeline form: images of different sizes into the slices of one N x C x H x W allocation */
@@ -646,6 +674,10 @@ HM_API int hm_resample_to_tensor(int out_format, int src_w, int src_h, const voi
 /* Host arithmetic: tiles[] = first tile row, row count, first tile column, column count a view decode of this item will
  * entropy-decode; a single image, or a view that is not reduced: the whole grid (0, rows, 0, cols). */
 HM_API int hm_plan_view(const hm_file* f, uint32_t id, const hm_decode_params* params, const hm_device_view* view, int32_t tiles[4]);
+/* which layers of overlay `id` a decode (view NULL) or a decode under `view` would decode: decoded[i] = 1 / 0 for i < max_children
+ * (a layer that does not touch the canvas - under a view without transformations on the overlay: the crop - is not decoded).
+ * Returns the number of layers, or a negative status: everything a decode refuses without looking at a picture. */
+HM_API int hm_plan_overlay(const hm_file* f, uint32_t id, const hm_decode_params* params, const hm_device_view* view, int32_t* decoded, int max_children);
 /* Host arithmetic: the taps of output index j on one axis of n_in -> n_out.  Returns their count (or a negative status),
  * *first = the first source index, weights[0 .. min(count, cap)) = the weights the kernels use. */
 HM_API int hm_view_filter_taps(int n_in, int n_out, int filter, int j, int32_t* first, float* weights, int cap);

@@ -38,13 +38,13 @@ enum heif_error_code {
 /* heif.h:142-370 (the sub-codes this path can produce) */
 enum heif_suberror_code {
   heif_suberror_Unspecified = 0, heif_suberror_End_of_data = 100, heif_suberror_No_item_data = 117,
-  heif_suberror_Invalid_grid_data = 118, heif_suberror_Wrong_tile_image_chroma_format = 127,
+  heif_suberror_Invalid_grid_data = 118, heif_suberror_Invalid_overlay_data = 121, heif_suberror_Wrong_tile_image_chroma_format = 127,
   heif_suberror_Invalid_image_size = 129, heif_suberror_Unknown_NCLX_color_primaries = 133,
   heif_suberror_Unknown_NCLX_transfer_characteristics = 134, heif_suberror_Unknown_NCLX_matrix_coefficients = 135,
   heif_suberror_Nonexisting_item_referenced = 2000,
   heif_suberror_Null_pointer_argument = 2001, heif_suberror_Nonexisting_image_channel_referenced = 2002,
   heif_suberror_Unsupported_plugin_version = 2003, heif_suberror_Unsupported_codec = 3000,
-  heif_suberror_Unsupported_image_type = 3001, heif_suberror_Unsupported_color_conversion = 3003,
+  heif_suberror_Unsupported_image_type = 3001, heif_suberror_Unsupported_data_version = 3002, heif_suberror_Unsupported_color_conversion = 3003,
   heif_suberror_Unsupported_bit_depth = 4000
 };
 /* heif.h:373-384 */
