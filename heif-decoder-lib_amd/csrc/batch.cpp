@@ -860,6 +860,9 @@ int hm_batch_last_groups(const hm_batch* b, int* first_cut)
   return b->last_groups;
 }
 
+// (test hook) the fused tail the batch decided on: -1 separate kernels (or nothing decided), 0 the integer 4:2:0 chain (k_tail420), 1 the float chain
+int hm_batch_tail_kind(const hm_batch* b) { return b && b->tail_state == 2 ? b->tail_kind : -1; }
+
 // 1 when the last execute ran the fused tail kernel (deblocking + SAO + paste + colour; its time is reported in the
 // SAO + paste slot of hm_batch_get_timings4, the deblocking and colour slots are 0)
 int hm_batch_tail_fused(const hm_batch* b) { return b && b->tail_state == 2 ? 1 : 0; }

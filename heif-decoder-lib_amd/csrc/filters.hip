@@ -1986,10 +1986,16 @@ extern "C" int hm_launch_sao_paste(const hm_dev_pic* d_pics, int n_pics, int max
 extern "C" const void* hm_tail420_kernel() { return reinterpret_cast<const void*>(k_tail420<3, TAIL_MINW, true>); } // (test_hooks.cpp: hm_debug_kernel_regs)
 extern "C" const void* hm_tail420_kernel16() { return reinterpret_cast<const void*>(k_tail420<3, TAIL_MINW, true, uint16_t>); } // (the HDR class)
 
+// (test hook, test_hooks.cpp: hm_debug_batch_tail) the fused tail kernel the last launch picked, noted where the kernel is launched, and
+// forgotten when it is asked for: 0 none since, 1 k_tail420 on 8-bit samples, 2 on 16-bit samples, 3 + 2 * (CF - 1) + (16-bit samples) k_tailf<Pix, CF>
+static int g_tail_last_launch = 0;
+extern "C" int hm_tail_last_launch() { return __atomic_exchange_n(&g_tail_last_launch, 0, __ATOMIC_RELAXED); }
+
 template <typename Pix>
 static int launch_tail420(const hm_dev_pic* d_pics, const void* d_dsts, int n_pics, int max_w, int max_h, int log2_ctb, int bpp, const int coef[4], int stages, hipStream_t s)
 {
   if (n_pics <= 0) return HM_OK;
+  __atomic_store_n(&g_tail_last_launch, sizeof(Pix) == 1 ? 1 : 2, __ATOMIC_RELAXED);
   const int tiles_x = (max_w + TAIL_TW - 1) / TAIL_TW, tiles_y = (max_h + TAIL_TH - 1) / TAIL_TH;
   const dim3 grid((tiles_x * tiles_y + 7) / 8 * 8, n_pics); // (a multiple of 8: see the tile mapping in the kernel)
   const TailCoef k{coef[0], coef[1], coef[2], coef[3]};
@@ -2022,6 +2028,7 @@ static int launch_tailf(const hm_dev_pic* d_pics, const TailDst* dd, int n_pics,
 {
   const dim3 grid((tiles_x * tiles_y + 7) / 8 * 8, n_pics);
   const int nt = tiles_x * tiles_y;
+  __atomic_store_n(&g_tail_last_launch, 3 + 2 * (CF - 1) + (sizeof(Pix) == 1 ? 0 : 1), __ATOMIC_RELAXED);
   switch (out_format) {
     case HM_OUT_RGB: hipLaunchKernelGGL((k_tailf<Pix, CF, OF_RGB24>), grid, dim3(TF_THREADS), 0, s, d_pics, dd, tiles_x, nt, stages, fp); break;
     case HM_OUT_RGBA: hipLaunchKernelGGL((k_tailf<Pix, CF, OF_RGBA32>), grid, dim3(TF_THREADS), 0, s, d_pics, dd, tiles_x, nt, stages, fp); break;

@@ -74,6 +74,10 @@ int hm_chain_plan(const struct hm_dev_pic* d_pics, int n_pics, int log2_ctb, int
                   int* split_fraction);
 // (test hook, test_hooks.cpp) groups of the batch's last hm_batch_execute and the image index behind its first group
 int hm_batch_last_groups(const hm_batch* b, int* first_cut);
+// (test hook, test_hooks.cpp) the fused tail of the batch: -1 none, 0 the integer 4:2:0 chain, 1 the float chain (batch.cpp: decide_tail); and the
+// kernel that the last launch of a fused tail since the previous call picked (filters.hip: 0 none, 1 / 2 k_tail420 on 8- / 16-bit samples, 3 + 2 * (CF - 1) + (16-bit) k_tailf)
+int hm_batch_tail_kind(const hm_batch* b);
+int hm_tail_last_launch(void);
 #include "hm_knobs.h" // hm_knob / hm_knob_set
 size_t hm_chain_sync_bytes(int n_pics, int chroma_format, int max_ctb_h);
 int hm_launch_deblock(const struct hm_dev_pic* d_pics, int n_pics, int max_w4, int max_h4, int chroma_format,

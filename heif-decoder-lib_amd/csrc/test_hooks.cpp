@@ -31,6 +31,15 @@ __attribute__((visibility("default"))) int hm_debug_set(const char* name, int va
 // groups of the batch's last hm_batch_execute (1: the single stream) and the image index behind the first of them (hm_overlap_plan.h)
 __attribute__((visibility("default"))) int hm_debug_batch_groups(const hm_batch* b, int* first_cut) { return hm_batch_last_groups(b, first_cut); }
 
+// the fused tail of the batch (-1 none, 0 the integer 4:2:0 chain, 1 the float chain) and, in *kernel, the kernel the last launch of a fused tail
+// since the previous call picked: 0 none, 1 / 2 k_tail420 on 8- / 16-bit samples, 3 + 2 * (CF - 1) + (16-bit samples) k_tailf<Pix, CF> (the float chain of 9..11-bit 4:2:0 to
+// RGB24 / RGBA32 runs on k_tail420's 16-bit instantiation: hm_launch_tailf)
+__attribute__((visibility("default"))) int hm_debug_batch_tail(const hm_batch* b, int* kernel)
+{
+  if (kernel) *kernel = hm_tail_last_launch();
+  return hm_batch_tail_kind(b);
+}
+
 // registers and scratch of a hot-path kernel as the loaded code object has them (hm_internal.h)
 __attribute__((visibility("default"))) int hm_debug_kernel_regs(int which, int a, int b, int c, int out[2])
 {

@@ -413,3 +413,104 @@ def intra_tiles():
             (18001, dict(base, log2_ctb=6, bit_depth=10, chroma_format=2, qp=30)),
             (18002, dict(base, log2_ctb=4, chroma_format=0, qp=33, no_split=1)),
             (18003, dict(base, log2_ctb=5, qp=27, slices=40, dependent=300))]
+
+
+def deblock_sweep(n, first_seed=19000):
+    """(seed, parameters) of a seeded sweep for the deblocking filter (tests/deblock_ref.py holds it, decision by decision): pictures of
+    64-200 samples a side whose sizes cut a window at the right and bottom border (72, 40, 136, 200), calm coding units next to noisy ones
+    (smooth sides: the strong filter, dEp / dEq), QpY over its range with cu_qp_delta (QpP != QpQ, odd sums, the table indices clipped
+    at both ends), slice offsets up to +-6 with per-slice overrides and disables, loop filters stopped at slice and tile borders, chroma
+    QP offsets up to +-12, neighbours at both rails (level_span), PCM with and without pcm_loop_filter_disable and transquant bypass
+    (every other run of 72 cases), whole blocks, every chroma format and CTB size, 8, 9, 10, 11 and 12 bit.  The comparisons are at the
+    reconstruction and deblocking stages only, so quirk Q9 (one of SAO) does not enter, and 8-bit pictures of the "pcmf" branch are in:
+    compared with the reference's default build (see SIMD_BUILD_ONLY).  Behind the 288 crossed cases follow cases aimed at the cells of
+    the census (tests/deblockutil.py) that the crossed ones leave empty."""
+    out = []
+    for seed in range(first_seed, first_seed + n):
+        r = seed * 2654435761 % (1 << 32)
+        r = (r ^ (r >> 15)) * 2246822519 % (1 << 32)
+        r ^= r >> 13
+        i = seed - first_seed
+        pick = lambda k, opts: opts[(r >> k) % len(opts)]
+        kw = dict(bit_depth=[8, 10, 11, 12, 8, 9][i % 6], chroma_format=[1, 2, 3, 0][(i // 6) % 4], log2_ctb=[5, 4, 6][(i // 24) % 3],
+                  width=pick(0, [72, 136, 64, 200, 96, 40]), height=pick(3, [72, 40, 64, 136, 96]), calm=pick(6, [0, 500, 800, 300]),
+                  qp=pick(8, [22, 30, 38, 45, 12, 51, 27, 34]), qp_span=pick(11, [0, 1, 0]), cu_qp_delta=1, diff_cu_qp_delta_depth=pick(13, [1, 0, 2]),
+                  beta_offset_div2=pick(15, [0, -6, 6, 3, -2]), tc_offset_div2=pick(18, [0, 6, -6, -3, 2]), deblock_override=pick(21, [0, 1]),
+                  slice_lf_random=pick(22, [0, 1]), pps_lf_across_slices_off=pick(23, [0, 0, 1]), slices=pick(25, [0, 0, 60, 150]),
+                  dependent=pick(27, [0, 400]), cb_qp_offset=pick(1, [0, 12, -12, 5, -7]), cr_qp_offset=pick(4, [0, -12, 12, -3, 8]),
+                  chroma_qp_list=pick(7, [0, 0, 2]), level_span=pick(9, [0, 0, 300, 1000]), no_split=pick(12, [0, 0, 1]),
+                  log2_max_tb=pick(14, [5, 5, 4, 3]), density=pick(16, [20, 60, 100]), sign_hiding=pick(29, [1, 0]))
+        kw["diff_cu_qp_delta_depth"] = min(kw["diff_cu_qp_delta_depth"], kw["log2_ctb"] - 3)
+        if kw["chroma_format"] == 0:
+            kw["chroma_qp_list"] = 0
+        if not kw["slices"]:
+            kw["dependent"] = 0
+        if (i // 72) % 2 == 1:  # rare syntax: the plain scalar filters with their "pcmf" branches
+            kw.update(pcm=pick(19, [0, 200, 300]), pcm_loop_filter_disable=pick(24, [1, 0]), tq_bypass=pick(26, [0, 250, 0, 150]), pcm_log2_max=pick(28, [5, 3, 4]))
+            kw.update(pcm_bits_y=max(1, kw["bit_depth"] - seed % 3), pcm_bits_c=max(1, kw["bit_depth"] - seed % 4))
+        if i % 5 == 3:
+            kw.update(tile_cols=2, tile_rows=2, lf_across_tiles=i % 2, tiles_uniform=(i // 2) % 2, width=max(kw["width"], 136), height=max(kw["height"], 136))
+        elif i % 7 == 2:
+            kw.update(wpp=1)
+        if i >= 288:
+            # aimed cases, five families in turn: (0) flat pictures at the edges of QpY - both ends of both table indices, tc 0 beside beta > 0, QpC
+            # in its three ranges and capped at 51; (1) calm pictures at the rails, half of them at 11 bit - the packed 16-bit filters one bit from
+            # overflow; (2) short slices with overrides and disables, or tiles that stop the filter; (3) PCM (samples of one bit: flat runs that
+            # the filter accepts) and bypass units next to calm ones under a large beta; (4) a large beta over a small tc on smooth ramps - the
+            # strong filter against its 2 tc clip
+            j = i - 288
+            fam, k = j % 5, j // 5
+            bd, cf, ctb = [8, 12, 10, 8, 11, 9, 12, 8][k % 8], pick(1, [1, 2, 3, 0, 1]), pick(4, [4, 5, 6])
+            if fam == 0:
+                kw = dict(bit_depth=bd, chroma_format=cf, log2_ctb=ctb, width=72, height=72, calm=[300, 600][k % 2], qp=[1, 51, 17, 20, 44, 30][k % 6], qp_span=(k // 6) % 2,
+                          cu_qp_delta=1, diff_cu_qp_delta_depth=min(1, ctb - 3), beta_offset_div2=[6, -6, 0, -6, 6, 2][k % 6], tc_offset_div2=[-6, 6, 0, 6, -6, -1][k % 6],
+                          cb_qp_offset=[12, -12, 6][k % 3], cr_qp_offset=[-12, 12, -6][k % 3], density=60)
+            elif fam == 1:
+                kw = dict(bit_depth=[11, 8, 11, 10, 11, 12, 11, 9][k % 8], chroma_format=cf, log2_ctb=ctb, width=72, height=72, calm=[200, 500][k % 2], qp=[45, 51, 38][k % 3], level_span=1000,
+                          density=100, cu_qp_delta=1, tc_offset_div2=[6, 0][(k // 2) % 2], beta_offset_div2=[6, 0][(k // 2) % 2])
+            elif fam == 2:
+                kw = dict(bit_depth=bd, chroma_format=cf, log2_ctb=ctb, width=136, height=72, calm=500, qp=[27, 34, 40][k % 3], cu_qp_delta=1, slices=300, deblock_override=1,
+                          slice_lf_random=1, slice_qp_random=1, density=60, scaling_list=[0, 2][(k // 4) % 2])  # (scaling lists: the rare classes)
+                if k % 3 == 2:
+                    kw.update(tile_cols=2, tile_rows=2, lf_across_tiles=0, slices=0, deblock_override=0, slice_lf_random=0)
+            elif fam == 3:
+                kw = dict(bit_depth=bd, chroma_format=cf, log2_ctb=ctb, width=72, height=72, calm=700, qp=[45, 51][k % 2], beta_offset_div2=6, tc_offset_div2=6, cu_qp_delta=1,
+                          pcm=[700, 0, 600][k % 3], pcm_loop_filter_disable=[1, 0, 0][k % 3], tq_bypass=[0, 300, 150][k % 3], pcm_log2_max=3 + (k // 3) % 2,
+                          pcm_bits_y=1, pcm_bits_c=[1, bd][(k // 6) % 2], density=60)
+                if k % 3 != 1:
+                    kw.update(width=136, height=136)  # (two PCM units side by side, both flat on the lines the decision reads: one unit in 256)
+            else:
+                kw = dict(bit_depth=[8, 12, 8, 12, 10, 8, 11, 9][k % 8], chroma_format=cf, log2_ctb=ctb, width=136, height=72, calm=[800, 600][k % 2], qp=[32, 38, 44][k % 3], beta_offset_div2=6, tc_offset_div2=-6,
+                          cu_qp_delta=1, density=[30, 60][(k // 2) % 2], mode_span=[0, 800][(k // 4) % 2], scaling_list=[0, 2][(k // 8) % 2])  # (scaling lists: the rare classes)
+        if kw["bit_depth"] == 8:
+            kw["transform_skip"] = 0  # (Q10: the reference's builds round 8-bit 4x4 transform-skip blocks differently where levels are large - not a subject here)
+        out.append((seed, kw))
+    return out
+
+
+def deblock_single_edge_cases(first_seed=22000):
+    """(seed, parameters) of the smallest pictures that hold each kind of window of the one-pass deblocking kernels: 16x8 (one vertical edge
+    in a top and a bottom half window), 8x16 (one horizontal edge in a left and a right half window) and 16x16 (the one crossing, where the
+    horizontal edge reads what the vertical edge wrote; the corner windows hold no edge) - one CTB 16 of 8x8 units whose transform tree is
+    not split any further (an NxN unit's 4x4 blocks meet off the 8-sample grid), no SAO, every bit depth and chroma format, QP over its range"""
+    out = []
+    seed = first_seed
+    for w, h in ((16, 8), (8, 16), (16, 16)):
+        for bd in (8, 9, 10, 11, 12):
+            for cf in (1, 2, 3, 0):
+                for k, qp in enumerate((1, 14, 27, 40, 51)):
+                    out.append((seed, dict(width=w, height=h, log2_ctb=4, max_th_depth_intra=0, sao=0, bit_depth=bd, chroma_format=cf, qp=qp, cu_qp_delta=1,
+                                           calm=[0, 500, 800][(seed + k) % 3], density=[60, 100][seed % 2], beta_offset_div2=[0, 3, -3][(seed // 5) % 3],
+                                           tc_offset_div2=[0, -3, 3][(seed // 7) % 3], level_span=[0, 0, 1000][(seed // 3) % 3], transform_skip=int(bd > 8))))  # (8 bit: Q10, see deblock_sweep)
+                    seed += 1
+    return out
+
+
+def deblock_tiles():
+    """512 x 512 tiles for the deblocking phase of the fused tails, half of their coding units calm: 8-bit 4:2:0 of one slice (k_tail420
+    with the edge parameters from the block map's copy in LDS), the same in 40 slices (the general derivation inside the fused tail), 10-bit
+    4:2:0 (k_tail420's 16-bit instantiation) and 10-bit 4:2:2 limited range BT.2020 (k_tailf)"""
+    return [(23000, dict(TILE, calm=500, vui=1, full_range=1, matrix=6)),
+            (23001, dict(TILE, calm=500, vui=1, full_range=1, matrix=6, slices=40)),
+            (23002, dict(TILE, calm=500, bit_depth=10, vui=1, full_range=1, matrix=9, primaries=9)),
+            (23003, dict(TILE, calm=500, bit_depth=10, chroma_format=2, vui=1, full_range=0, matrix=9, primaries=9))]

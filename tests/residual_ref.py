@@ -90,6 +90,13 @@ PIC_STRONG_INTRA, PIC_NO_INTRA_SMOOTHING = 0x1, 0x8000
 TU_CBF, TU_TSKIP, TU_AVAIL_TL, MODE_BYPASS, MODE_PCM = 0x20, 0x40, 0x80, 0x40, 0x80
 
 
+PIC_TILES, PIC_LF_ACROSS_TILES, PIC_PCMF = 0x40, 0x80, 0x200
+CTB_DEBLOCK_LEFT, CTB_DEBLOCK_TOP, CTB_DEBLOCK_OFF = 0x01, 0x02, 0x08
+SLICE_DTYPE = np.dtype([("slice_addr", "<u4"), ("beta_offset_div2", "i1"), ("tc_offset_div2", "i1"), ("deblocking_disabled", "u1"), ("sao_luma", "u1"),
+                        ("sao_chroma", "u1"), ("lf_across_slices", "u1"), ("slice_qp", "i1"), ("reserved", "u1")])
+CTB_DTYPE = np.dtype(dict(names=["tu_first", "tu_count", "slice_idx", "flags"], formats=["<u4", "<u2", "<u2", "u1"], offsets=[0, 4, 6, 8], itemsize=52))
+
+
 def scaling_offset(log2, cidx):  # HM_SCALING_OFFSET
     return {2: 16 * cidx, 3: 48 + 64 * cidx, 4: 240 + 256 * cidx, 5: 1008}[log2]
 
@@ -100,14 +107,24 @@ class Picture:
     def __init__(self, blob):
         self.blob = blob
         self.width, self.height = struct.unpack_from("<HH", blob, 8)
-        self.chroma_format, self.bit_depth, _, self.log2_ctb = struct.unpack_from("<4B", blob, 20)
+        self.crop = struct.unpack_from("<4H", blob, 12)
+        self.chroma_format, self.bit_depth, self.bit_depth_c, self.log2_ctb, self.log2_min_tb, self.log2_min_cb = struct.unpack_from("<6B", blob, 20)
         self.ctb_w, self.ctb_h = struct.unpack_from("<HH", blob, 28)
+        self.cb_qp_offset, self.cr_qp_offset, self.pcm_loop_filter_disabled = struct.unpack_from("<bbB", blob, 32)
         self.flags = struct.unpack_from("<I", blob, 36)[0]
         assert not self.flags & PIC_SPLIT_CHAINS, "parse with record_order = decode order"
         self.n_slices, self.n_ctbs, self.n_tus, self.n_coeffs = struct.unpack_from("<4I", blob, 0x2C)
         self.off_slices, self.off_ctbs, self.off_tus, self.off_coeffs, self.off_scaling = struct.unpack_from("<5I", blob, 0x3C)
         self.scaling = np.frombuffer(blob, np.uint8, 1008 + 1024, self.off_scaling).astype(np.int64) if self.flags & PIC_SCALING_LIST else None
         self.coeffs = np.frombuffer(blob, np.dtype([("pos", "<u2"), ("value", "<i2")]), self.n_coeffs, self.off_coeffs)
+
+    def slices(self):
+        """hm_slice[n_slices] as a structured array"""
+        return np.frombuffer(self.blob, SLICE_DTYPE, self.n_slices, self.off_slices)
+
+    def ctbs(self):
+        """the fields of hm_ctb[n_ctbs] that the loop filters read, as a structured array"""
+        return np.frombuffer(self.blob, CTB_DTYPE, self.n_ctbs, self.off_ctbs)
 
     def records(self, ctb=None):
         """the records of all CTBs (or of one) in decode order: dicts with the block's position in its plane"""

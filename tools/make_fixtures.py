@@ -10,6 +10,9 @@ and the reference decoder build oracle/_ref):
                             SCALAR build for corpus.extreme_sweep - levels, QPs and scaling factors at the edges of the
                             residual arithmetic -, and beside them where its default (SIMD) build decodes otherwise
   tests/golden/intra.json   (`make_fixtures.py intra` writes it, and only that sub-command) the same for corpus.intra_sweep
+  tests/golden/deblock.json (`make_fixtures.py deblock`, and only that sub-command) fingerprints of the reconstruction and deblocking stages for
+                            corpus.deblock_sweep / deblock_single_edge_cases / deblock_tiles: the reference's scalar build, and its default build for
+                            8-bit pictures of the "pcmf" branch; with it profiles/deblock_census.txt, the census of tests/deblockutil.py
 """
 import json
 import os
@@ -179,8 +182,42 @@ def intra():
     print("intra:", len(cases), "cases;", len(differing), "decoded differently by the default build:", dict(sorted(classes.items())))
 
 
+DEBLOCK_SWEEP_CASES = 1488
+
+
+def deblock():
+    """the three deblocking corpora: fingerprints of the reference decoder at the reconstruction and deblocking stages, and the census of the
+    filter's decisions taken with tests/deblock_ref.py on the reference's planes (the model must reproduce them: asserted)"""
+    import corpus
+    import deblockutil as du
+    import residual_ref as rr
+    import synthutil
+    import __graft_entry__ as g
+    capi = g.load_package().capi
+    cases, C = {}, du.Census()
+    todo = corpus.deblock_sweep(DEBLOCK_SWEEP_CASES) + corpus.deblock_single_edge_cases() + corpus.deblock_tiles()
+    for seed, kw in todo:
+        data = synthutil.picture(seed, **kw)
+        P = rr.Picture(capi.parse_hevc(data, record_order=du.DECODE_ORDER))
+        pcmf8 = P.bit_depth == 8 and bool(P.flags & rr.PIC_PCMF)
+        build = 0 if pcmf8 else orc.REF_F_SCALAR
+        before, _ = orc.ref_decode(data, orc.REF_F_NO_DEBLOCK | orc.REF_F_NO_SAO | build)
+        after, _ = orc.ref_decode(data, orc.REF_F_NO_SAO | build)
+        bad = du.first_mismatch(seed, P, before, after, du.quirks_for(default_build=pcmf8), C.noter(du.kernel_class(P.flags, P.bit_depth), P))
+        assert bad is None, bad
+        assert str(seed) not in cases
+        cases[str(seed)] = {"stream_fnv": f"{orc.load().orc_fnv1a64(data, len(data), 0):016x}", "recon": fingerprint(before), "deblock": fingerprint(after)}
+    json.dump({"sweep_cases": DEBLOCK_SWEEP_CASES, "cases": cases}, open(os.path.join(ROOT, "tests", "golden", "deblock.json"), "w"), indent=0, sort_keys=True,
+              separators=(",", ":"))
+    open(os.path.join(ROOT, "profiles", "deblock_census.txt"), "w").write(C.table())
+    print("deblock:", len(cases), "pictures,", C.units, "units on the grid")
+
+
 if __name__ == "__main__":
-    if sys.argv[1:] == ["extreme"]:
+    if sys.argv[1:] == ["deblock"]:
+        sys.path.insert(0, ROOT)
+        deblock()
+    elif sys.argv[1:] == ["extreme"]:
         sys.path.insert(0, ROOT)
         extreme()
     elif sys.argv[1:] == ["intra"]:
