@@ -514,3 +514,140 @@ def deblock_tiles():
             (23001, dict(TILE, calm=500, vui=1, full_range=1, matrix=6, slices=40)),
             (23002, dict(TILE, calm=500, bit_depth=10, vui=1, full_range=1, matrix=9, primaries=9)),
             (23003, dict(TILE, calm=500, bit_depth=10, chroma_format=2, vui=1, full_range=0, matrix=9, primaries=9))]
+
+
+def sao_class_q9(kw):
+    """quirk Q9: 8-bit pictures with CTBs of 16 and sub-sampled chroma, SAO on - the reference's default build overruns there, its scalar build is the truth"""
+    return kw.get("bit_depth", 8) == 8 and kw.get("log2_ctb", 5) == 4 and kw.get("chroma_format", 1) in (1, 2) and kw.get("sao", 1) != 0
+
+
+def sao_class_pcmf8(kw):
+    """8-bit pictures of the "pcmf" branch of the deblocking filter (SIMD_BUILD_ONLY tells why): the reference's default build for input and output alike"""
+    return kw.get("bit_depth", 8) == 8 and bool((kw.get("pcm", 0) and kw.get("pcm_loop_filter_disable", 0)) or kw.get("tq_bypass", 0))
+
+
+def _sao_settle(kw):
+    if kw["bit_depth"] == 8:
+        kw["transform_skip"] = 0  # (Q10, see deblock_sweep)
+    if sao_class_pcmf8(kw) and sao_class_q9(kw):
+        kw["log2_ctb"] = 5        # no picture is in both classes of the reference's builds
+    if kw.get("chroma_format", 1) == 0:
+        kw.pop("sao_scale_c", None)
+    return kw
+
+
+def sao_sweep(n, first_seed=24000):
+    """(seed, parameters) of a seeded sweep for sample adaptive offset (tests/sao_ref.py holds it, sample by sample): pictures of 64x64 to
+    128x96 samples - a sample goes wrong at a border or a rail, not at size.  120 crossed cases over bit depth 8-12, every chroma format and
+    CTB size, with slices whose filter and SAO flags are drawn per slice, tiles, PCM / bypass units every other run of 60, offsets and band
+    positions at the ends of their ranges (sao_span) and levels at the rails.  Behind them follow families aimed at the cells of the census
+    (tests/saoutil.py): (0) short slices with staircase borders inside a CTB row, flags per slice, the PPS flag off in every third; (1) tiles,
+    uniform and not, the filters crossing their borders or not; (2) tiles and slices together; (3) PCM with and without
+    pcm_loop_filter_disable and bypass units; (4) scaled offsets at 11 and 12 bit; (5) samples at both rails under the largest offsets;
+    (6) conformance windows whose left offset is and is not a multiple of 8 in each plane; (7) sizes that are no multiple of the CTB, chroma
+    widths of 8 k + 4; (8) two tiles one above the other whose border the filters cross, cut into slices of a few CTBs with flags of their own: with tiles
+    the reference leaves its fast path, and only there do the slices' flags differ inside a picture without PCM / bypass units - a diagonal neighbour CTB
+    stopped between usable ones and the reverse."""
+    out = []
+    for seed in range(first_seed, first_seed + n):
+        r = seed * 2654435761 % (1 << 32)
+        r = (r ^ (r >> 15)) * 2246822519 % (1 << 32)
+        r ^= r >> 13
+        i = seed - first_seed
+        pick = lambda k, opts: opts[(r >> k) % len(opts)]
+        if i < 120:
+            kw = dict(bit_depth=[8, 9, 10, 11, 12][i % 5], chroma_format=[1, 2, 3, 0][(i // 5) % 4], log2_ctb=[4, 5, 6][(i // 20) % 3],
+                      width=pick(0, [64, 72, 96, 104, 128, 88]), height=pick(3, [64, 72, 96, 80]), calm=pick(6, [0, 500, 300]), qp=pick(8, [22, 30, 38, 45, 27, 34]),
+                      cu_qp_delta=1, slices=pick(11, [0, 60, 150]), slice_lf_random=pick(13, [0, 1]), slice_sao_random=pick(14, [0, 1]),
+                      pps_lf_across_slices_off=pick(15, [0, 0, 1]), dependent=pick(17, [0, 400]), level_span=pick(19, [0, 0, 300, 1000]),
+                      sao_span=pick(21, [0, 300, 600]), density=pick(23, [20, 60, 100]), sign_hiding=pick(25, [1, 0]))
+            if not kw["slices"]:
+                kw["dependent"] = 0
+            if (i // 60) % 2 == 1:  # rare syntax
+                kw.update(pcm=pick(26, [0, 200, 300]), pcm_loop_filter_disable=pick(28, [1, 0]), tq_bypass=pick(29, [0, 250, 0, 150]), pcm_log2_max=pick(30, [5, 3, 4]),
+                          pcm_bits_y=max(1, kw["bit_depth"] - seed % 3), pcm_bits_c=max(1, kw["bit_depth"] - seed % 4))
+            if i % 7 == 3:
+                kw.update(tile_cols=2, tile_rows=2, lf_across_tiles=(i // 7) % 2, tiles_uniform=(i // 14) % 2, width=128, height=96)
+        else:
+            j = i - 120
+            fam, k = j % 9, j // 9
+            bd, cf, ctb = [8, 12, 10, 8, 11, 9, 8, 10][k % 8], [1, 2, 3, 0, 1, 2, 1][k % 7], [4, 5, 6, 4, 5][k % 5]
+            rare = dict(scaling_list=[0, 0, 0, 2][k % 4])  # (scaling lists: the rare classes without PCM / bypass units)
+            kw = dict(bit_depth=bd, chroma_format=cf, log2_ctb=ctb, width=128, height=96, qp=pick(8, [27, 34, 40, 22]), cu_qp_delta=1, density=60,
+                      calm=pick(6, [0, 300]), sao_span=pick(21, [0, 300, 600]))
+            if fam == 0:
+                kw.update(rare, slices=[300, 500, 150][k % 3], slice_lf_random=1, slice_sao_random=(k // 2) % 2, pps_lf_across_slices_off=int(k % 3 == 2), dependent=[0, 300][(k // 3) % 2],
+                          width=[128, 96, 112][k % 3], height=[96, 64, 80][(k // 3) % 3])
+            elif fam == 1:
+                kw.update(rare, tile_cols=[2, 3, 2][k % 3], tile_rows=[2, 2, 3][(k // 3) % 3], lf_across_tiles=k % 2, tiles_uniform=(k // 2) % 2)
+            elif fam == 2:
+                kw.update(rare, tile_cols=2, tile_rows=2, lf_across_tiles=int(k % 3 != 0), tiles_uniform=(k // 2) % 2, slices=[150, 300][k % 2], slice_lf_random=1,
+                          slice_sao_random=(k // 4) % 2, dependent=[0, 300][(k // 3) % 2])
+            elif fam == 3:
+                kw.update(pcm=[300, 0, 400][k % 3], pcm_loop_filter_disable=[1, 0, 0][k % 3], tq_bypass=[0, 300, 150][k % 3], pcm_log2_max=3 + (k // 3) % 3,
+                          pcm_bits_y=max(1, bd - k % 3), pcm_bits_c=max(1, bd - k % 4), slices=[0, 150][(k // 2) % 2], slice_lf_random=1, width=96, height=72,
+                          level_span=[0, 1000][(k // 4) % 2], sao_span=600)
+            elif fam == 4:
+                deep = [12, 11, 12][k % 3]
+                kw.update(rare, bit_depth=deep, sao_scale_y=[deep - 10, 1, 0][(k // 3) % 3], sao_scale_c=[deep - 10, 0, 1][(k // 3) % 3], sao_span=[700, 400][k % 2], level_span=[1000, 300][(k // 2) % 2],
+                          width=96, height=64)
+            elif fam == 5:
+                kw.update(rare, level_span=1000, qp_span=(k // 2) % 2, qp=[51, 45, 48][k % 3], sao_span=[800, 500][k % 2], density=100, calm=0, width=96, height=64,
+                          slices=[0, 100][(k // 4) % 2], slice_lf_random=1)
+                if bd == 12:
+                    kw.update(sao_scale_y=[0, 2][(k // 2) % 2], sao_scale_c=[2, 0][(k // 2) % 2])
+            elif fam == 6:
+                kw.update(rare, conf_left=[8, 0, 6, 16, 2, 24, 12][k % 7], conf_right=[4, 10, 0, 8, 2][k % 5], conf_top=[0, 2, 8, 6][(k // 3) % 4], conf_bottom=[0, 6, 2][(k // 5) % 3],
+                          slices=[0, 150, 300][(k // 2) % 3], slice_lf_random=1, width=[128, 96, 104][k % 3], height=[96, 72][(k // 3) % 2])
+                if (k // 4) % 3 == 2:
+                    kw.update(tile_cols=2, tile_rows=2, lf_across_tiles=0, slices=0)
+            elif fam == 8:
+                kw.update(scaling_list=[0, 2][k % 2], bit_depth=[8, 8, 10, 8, 12, 8, 11, 9][k % 8], log2_ctb=[4, 4, 5][k % 3], tile_cols=1, tile_rows=2, lf_across_tiles=1, slices=[500, 700, 350][k % 3], slice_lf_random=1, sao_span=300,
+                          level_span=[0, 1000][(k // 2) % 2])
+            else:
+                kw.update(rare, width=[72, 88, 104, 120, 80][k % 5], height=[72, 80, 88, 72][(k // 5) % 4], slices=[0, 200][(k // 2) % 2], slice_lf_random=1, slice_sao_random=(k // 4) % 2,
+                          level_span=[0, 1000][(k // 3) % 2])
+        out.append((seed, _sao_settle(kw)))
+    return out
+
+
+def sao_small_cases(first_seed=26000):
+    """(seed, parameters) of pictures of exactly one CTB of 16, 32 and 64 samples (every neighbour CTB is missing: each edge class meets the picture's
+    border on both sides), of 2 x 2 CTBs (one crossing of CTB borders, sliced so that the diagonal CTB and the ones beside it get answers of their own) and
+    of strips one CTB wide / one CTB high, at every bit depth and chroma format"""
+    out = []
+    seed = first_seed
+    for ctb in (4, 5, 6):
+        n = 1 << ctb
+        for shape, (w, h) in enumerate(((n, n), (2 * n, 2 * n), (n, 4 * n if ctb < 6 else 2 * n), (4 * n if ctb < 6 else 2 * n, n))):
+            for bd in (8, 9, 10, 11, 12):
+                for cf in (1, 2, 3, 0):
+                    kw = dict(width=w, height=h, log2_ctb=ctb, bit_depth=bd, chroma_format=cf, qp=[27, 38, 45][seed % 3], cu_qp_delta=1, density=[60, 100][seed % 2],
+                              sao_span=[0, 500, 800][(seed // 2) % 3], level_span=[0, 0, 1000][(seed // 3) % 3], calm=[0, 300][(seed // 5) % 2])
+                    if shape:
+                        kw.update(slices=[0, 400, 600][(seed // 4) % 3], slice_lf_random=1, slice_sao_random=(seed // 8) % 2)
+                    out.append((seed, _sao_settle(kw)))
+                    seed += 1
+    return out
+
+
+SAO_TILE_W, SAO_TILE_H = 192, 144
+
+
+def sao_tiles():
+    """tiles for the SAO phase of the fused tails, one per instance that the test hook hm_debug_batch_tail can name, 192 x 144 samples each (one and a half
+    cells of the fused kernels wide, CTBs cut at the bottom; test_sao_gpu.py tells why this is the smallest useful canvas): k_tail420 on 8-bit samples with
+    CTBs of 16 (UNI off), with CTBs of 32 in one slice (UNI; all_ok in the CTBs off the picture's border), with CTBs of 32 in several slices whose flags stop
+    the filters at their borders (the batch fuses such a picture only while the PPS flag is on: SAO then takes the reference's fast path, and the mask is not
+    0xFF at the picture's border alone), its 16-bit instantiation (a 10-bit picture, compared after its shift to 8 bits: offsets at their largest let most
+    changes survive it), and k_tailf<uint8_t / uint16_t, 4:2:0 / 4:2:2>"""
+    base = dict(width=SAO_TILE_W, height=SAO_TILE_H, log2_ctb=5, qp=30, cu_qp_delta=1, sao=1, sign_hiding=1, calm=300, density=60, vui=1, sao_span=500, transform_skip=0)
+    deep = dict(base, bit_depth=10, transform_skip=1)
+    return [(27000, dict(base, log2_ctb=4, full_range=1, matrix=6)),
+            (27001, dict(base, full_range=1, matrix=6)),
+            (27002, dict(base, full_range=1, matrix=6, slices=40, slice_lf_random=1)),
+            (27003, dict(deep, full_range=1, matrix=9, primaries=9, sao_span=900)),
+            (27004, dict(base, full_range=0, matrix=1)),
+            (27005, dict(deep, full_range=1, matrix=1)),
+            (27006, dict(base, chroma_format=2, full_range=1, matrix=6)),
+            (27007, dict(deep, chroma_format=2, full_range=0, matrix=9, primaries=9))]

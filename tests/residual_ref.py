@@ -94,7 +94,9 @@ PIC_TILES, PIC_LF_ACROSS_TILES, PIC_PCMF = 0x40, 0x80, 0x200
 CTB_DEBLOCK_LEFT, CTB_DEBLOCK_TOP, CTB_DEBLOCK_OFF = 0x01, 0x02, 0x08
 SLICE_DTYPE = np.dtype([("slice_addr", "<u4"), ("beta_offset_div2", "i1"), ("tc_offset_div2", "i1"), ("deblocking_disabled", "u1"), ("sao_luma", "u1"),
                         ("sao_chroma", "u1"), ("lf_across_slices", "u1"), ("slice_qp", "i1"), ("reserved", "u1")])
-CTB_DTYPE = np.dtype(dict(names=["tu_first", "tu_count", "slice_idx", "flags"], formats=["<u4", "<u2", "<u2", "u1"], offsets=[0, 4, 6, 8], itemsize=52))
+SAO_DTYPE = np.dtype([("type", "u1"), ("eo_class", "u1"), ("band_position", "u1"), ("offset", "i1", (4,)), ("reserved", "u1")])  # hm_sao: offsets already scaled
+CTB_DTYPE = np.dtype(dict(names=["tu_first", "tu_count", "slice_idx", "flags", "sao"], formats=["<u4", "<u2", "<u2", "u1", (SAO_DTYPE, (3,))], offsets=[0, 4, 6, 8, 12],
+                          itemsize=52))
 
 
 def scaling_offset(log2, cidx):  # HM_SCALING_OFFSET
@@ -109,6 +111,7 @@ class Picture:
         self.width, self.height = struct.unpack_from("<HH", blob, 8)
         self.crop = struct.unpack_from("<4H", blob, 12)
         self.chroma_format, self.bit_depth, self.bit_depth_c, self.log2_ctb, self.log2_min_tb, self.log2_min_cb = struct.unpack_from("<6B", blob, 20)
+        self.sao_scale_y, self.sao_scale_c = struct.unpack_from("<2B", blob, 26)  # log2_sao_offset_scale_luma / chroma (hm_sao.offset holds them applied)
         self.ctb_w, self.ctb_h = struct.unpack_from("<HH", blob, 28)
         self.cb_qp_offset, self.cr_qp_offset, self.pcm_loop_filter_disabled = struct.unpack_from("<bbB", blob, 32)
         self.flags = struct.unpack_from("<I", blob, 36)[0]

@@ -198,6 +198,9 @@ struct SynthParams {
                                // its prediction alone (ramps, smears), next to units with residuals
   int32_t mode_span;           // per-mille chance, per bin, that prev_intra_luma_pred_flag is 0 (the luma mode is then rem_intra_luma_pred_mode,
                                // uniform over the 32 modes that are no candidate) and that intra_chroma_pred_mode is 4 (the luma mode)
+  // --- SAO at the ends of its tables (0 = the draws of the streams above, byte for byte) ---
+  int32_t sao_span;            // per-mille chance, drawn once per offset, that sao_offset_abs is the largest the bit depth allows (every bin of its
+                               // truncated-unary code 1), and, once per band position, that sao_band_position is 29, 30 or 31 (bands that wrap)
 };
 
 // entropy-coder adaptor for SliceWalker: chooses every bin, encodes it, returns it
@@ -299,7 +302,18 @@ class EncoderEC {
     switch (kind) {
       case K_SAO_MERGE: return rng_.chance(300);
       case K_SAO_TYPE: return idx == 0 ? rng_.chance(700) : rng_.chance(500);
-      case K_SAO_OFFSET: return rng_.chance(450);
+      case K_SAO_OFFSET:
+        if (P.sao_span) {
+          if (idx == 0) sao_full_ = rng_.chance(P.sao_span);
+          if (sao_full_) return 1;
+        }
+        return rng_.chance(450);
+      case K_SAO_BAND: // five bits, the first most significant
+        if (P.sao_span) {
+          if (idx == 0) sao_wrap_ = rng_.chance(P.sao_span) ? 1 + (int)(rng_.next() % 3) : 0; // 29 + (0 .. 2)
+          if (sao_wrap_) return ((28 + sao_wrap_) >> (4 - idx)) & 1;
+        }
+        return (int)(rng_.next() & 1);
       case K_SPLIT_CU: return P.no_split ? 0 : rng_.chance(idx >= 6 ? 900 : (idx == 5 ? 650 : 450));
       case K_TQ_BYPASS: return rng_.chance(P.tq_bypass);
       case K_PART_MODE: return (idx == 1 || P.no_split) ? 1 : rng_.chance(600);
@@ -406,7 +420,8 @@ class EncoderEC {
   ContextSet cs_;
   // values drawn whole and written bin by bin (qp_span, level_span)
   int qp_abs_ = 0, last_bias_ = 1;
-  bool calr_run_ = false, cu_calm_ = false;
+  bool calr_run_ = false, cu_calm_ = false, sao_full_ = false;
+  int sao_wrap_ = 0;
   int calr_ = -1, calr_pos_ = 0, calr_prefix_ = 0, calr_suffix_ = 0;
 };
 

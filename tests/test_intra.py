@@ -30,6 +30,7 @@ STAGES = (("recon", orc.REF_F_NO_DEBLOCK | orc.REF_F_NO_SAO, 0), ("deblock", orc
 # sweep, rext_large, extreme_sweep(144), the extreme tiles and the first large extreme picture - the digest of the parent commit's
 # synthesiser, and the same with both knobs in place
 STREAMS_BEFORE_CALM = "439cd0a6b5f619d907d29857dd1c36d068e00349efc87ed6d3b3b9727b11169a"
+STREAMS_BEFORE_SAO_SPAN = "6103057603e7c4743e1536ad593c6fb68dd5085003eef6a937259337a63136f5"  # (taken at the commit before the knob)
 
 
 def _fp(planes):
@@ -52,6 +53,15 @@ def test_new_knobs_leave_every_existing_stream_alone_and_act():
     assert h.hexdigest() == STREAMS_BEFORE_CALM
     assert synthutil.picture(5, width=64, height=64, calm=500) != synthutil.picture(5, width=64, height=64)
     assert synthutil.picture(5, width=64, height=64, mode_span=800) != synthutil.picture(5, width=64, height=64)
+    # the knob sao_span (offsets and band positions at the ends of their ranges) came with the SAO corpora: the streams of the intra and deblocking corpora too
+    h = hashlib.sha256()
+    for sweep in (corpus.intra_sweep(16), corpus.intra_single_ctb_cases(16), corpus.intra_tiles(), corpus.deblock_sweep(320)[::8], corpus.deblock_single_edge_cases()[::10],
+                  corpus.deblock_tiles()):
+        for seed, kw in sweep:
+            h.update(synthutil.picture(seed, **kw))
+    assert h.hexdigest() == STREAMS_BEFORE_SAO_SPAN
+    assert synthutil.picture(5, width=64, height=64, sao_span=500) != synthutil.picture(5, width=64, height=64)
+    assert synthutil.picture(5, width=64, height=64, sao_span=500, sao=0) == synthutil.picture(5, width=64, height=64, sao=0)
 
 
 @pytest.fixture(scope="module")

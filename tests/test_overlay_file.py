@@ -237,7 +237,7 @@ def test_refusals_come_with_their_status_before_a_device_is_needed(pkg, pics):
     rc, msg = one(nested(9))
     assert rc == BITSTREAM and "nested deeper than 8" in msg
     rc, msg = one(nested(8))  # (8 levels plan; what comes back then is the missing device or a decode, not a refusal of the nesting)
-    assert "nested" not in msg
+    assert rc == 0 or "nested" not in msg  # (a decode that succeeds leaves the message of the refusal before it: hm_last_error is only written on failure)
 
 
 def test_image_info_refusals(pkg, pics):

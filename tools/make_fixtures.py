@@ -13,6 +13,9 @@ and the reference decoder build oracle/_ref):
   tests/golden/deblock.json (`make_fixtures.py deblock`, and only that sub-command) fingerprints of the reconstruction and deblocking stages for
                             corpus.deblock_sweep / deblock_single_edge_cases / deblock_tiles: the reference's scalar build, and its default build for
                             8-bit pictures of the "pcmf" branch; with it profiles/deblock_census.txt, the census of tests/deblockutil.py
+  tests/golden/sao.json     (`make_fixtures.py sao`, and only that sub-command) fingerprints of all four stages (none, deblocking, SAO alone, both) for
+                            corpus.sao_sweep / sao_small_cases / sao_tiles: the reference's scalar build, its default build for 8-bit pictures of the
+                            "pcmf" branch; with it profiles/sao_census.txt, the census of tests/saoutil.py
 """
 import json
 import os
@@ -213,8 +216,37 @@ def deblock():
     print("deblock:", len(cases), "pictures,", C.units, "units on the grid")
 
 
+SAO_SWEEP_CASES = 660
+
+
+def sao():
+    """the three SAO corpora: fingerprints of the reference decoder at all four stages, and the census of the branches of sample adaptive offset taken with
+    tests/sao_ref.py on the reference's planes (the model must reproduce them: asserted)"""
+    import corpus
+    import residual_ref as rr
+    import saoutil as su
+    import synthutil
+    import __graft_entry__ as g
+    capi = g.load_package().capi
+    cases, C = {}, su.Census()
+    for seed, kw in corpus.sao_sweep(SAO_SWEEP_CASES) + corpus.sao_small_cases() + corpus.sao_tiles():
+        data = synthutil.picture(seed, **kw)
+        P = rr.Picture(capi.parse_hevc(data, record_order=su.DECODE_ORDER))
+        assert str(seed) not in cases
+        cases[str(seed)] = dict(su.hold_picture(seed, kw, data, P, C), stream_fnv=f"{orc.load().orc_fnv1a64(data, len(data), 0):016x}")
+    json.dump({"sweep_cases": SAO_SWEEP_CASES, "cases": cases}, open(os.path.join(ROOT, "tests", "golden", "sao.json"), "w"), indent=0, sort_keys=True,
+              separators=(",", ":"))
+    open(os.path.join(ROOT, "profiles", "sao_census.txt"), "w").write(C.table())
+    missing = [(cls, kind, pair) + cell for cls in su.CLASSES for kind in su.KINDS for pair in su.PAIRS for cell in su.required(cls, kind, pair)
+               if not C.seen(cls, kind, pair, cell)]
+    print("sao:", len(cases), "pictures,", C.samples, "samples; required cells still empty:", missing)
+
+
 if __name__ == "__main__":
-    if sys.argv[1:] == ["deblock"]:
+    if sys.argv[1:] == ["sao"]:
+        sys.path.insert(0, ROOT)
+        sao()
+    elif sys.argv[1:] == ["deblock"]:
         sys.path.insert(0, ROOT)
         deblock()
     elif sys.argv[1:] == ["extreme"]:
