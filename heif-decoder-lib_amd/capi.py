@@ -162,6 +162,16 @@ class DeviceView(C.Structure):
     _fields_ = [(n, C.c_int32) for n in "crop_x crop_y crop_w crop_h out_w out_h filter".split()]
 
 
+class DeviceLight(C.Structure):
+    """hm_device_light: H.273 codes of the source (0 = the image's own) and of the result (to_transfer 8 = linear light, to_primaries
+    0 = the source's), the gain on linear light"""
+    _fields_ = [("from_transfer", C.c_int32), ("from_primaries", C.c_int32), ("to_transfer", C.c_int32), ("to_primaries", C.c_int32), ("gain", C.c_float),
+                ("reserved", C.c_int32 * 3)]
+
+
+HM_LIGHT_LINEAR = 8
+
+
 class OverlayInfo(C.Structure):
     """hm_overlay_info"""
     _fields_ = [("canvas_width", C.c_int32), ("canvas_height", C.c_int32), ("n_children", C.c_int32), ("background", C.c_uint16 * 4)]
@@ -245,6 +255,16 @@ def bind_image(L):
     L.hm_resample_to_tensor.argtypes = [C.c_int, C.c_int, C.c_int, C.c_void_p, C.c_int, C.POINTER(DeviceView), C.POINTER(DeviceDest), C.c_void_p]
     L.hm_plan_view.argtypes = [C.c_void_p, C.c_uint32, C.POINTER(DecodeParams), C.POINTER(DeviceView), C.POINTER(C.c_int32 * 4)]
     L.hm_view_filter_taps.argtypes = [C.c_int, C.c_int, C.c_int, C.c_int, C.POINTER(C.c_int32), C.POINTER(C.c_float), C.c_int]
+    L.hm_decode_item_to_device_light.argtypes = [C.c_void_p, C.c_uint32, C.POINTER(DecodeParams), C.POINTER(DeviceView), C.POINTER(DeviceLight), C.POINTER(DeviceDest),
+                                                 C.POINTER(Decoded)]
+    L.hm_decode_frames_to_device_light.argtypes = [C.c_void_p, C.POINTER(C.c_uint32), C.c_int32, C.POINTER(DecodeParams), C.POINTER(DeviceView), C.POINTER(DeviceLight),
+                                                   C.POINTER(DeviceDest), C.POINTER(Decoded), C.POINTER(C.c_int32)]
+    L.hm_pipeline_submit_to_device_light.argtypes = [C.c_void_p, C.c_char_p, C.c_size_t, C.c_uint32, C.c_uint64, C.POINTER(DeviceView), C.POINTER(DeviceLight),
+                                                     C.POINTER(DeviceDest)]
+    L.hm_light_to_tensor.argtypes = [C.c_int, C.c_int, C.c_int, C.c_int, C.c_void_p, C.c_int, C.POINTER(DeviceView), C.POINTER(DeviceLight), C.POINTER(DeviceDest),
+                                     C.c_void_p]
+    L.hm_light_table.argtypes = [C.c_int, C.c_int, C.c_float, C.c_int, C.POINTER(C.c_float)]
+    L.hm_light_matrix.argtypes = [C.c_int, C.c_int, C.POINTER(C.c_float * 9)]
     L.hm_device_planes_bytes.argtypes = [C.c_int, C.c_int, C.c_int, C.c_int, C.POINTER(DevicePlanes), C.POINTER(C.c_int64 * 4)]
     L.hm_device_planes_bytes.restype = C.c_int64
     L.hm_planes_to_tensor.argtypes = [C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, C.POINTER(C.c_void_p * 4), C.POINTER(C.c_int32 * 4), C.POINTER(DevicePlanes),

@@ -3,6 +3,7 @@
 // Planar YCbCr (hm_device_planes): the arithmetic and the refusals, and the step that writes the decoded planes (kernel: planes.hip).
 // Views (hm_device_view): the refusals, the tap tables and the step that writes a resampled rectangle (kernels: resample.hip).
 // Planar views (a view into hm_device_planes): the geometry per plane, the refusals and the write step (kernels: planes_view.hip).
+// Light (hm_device_light): the transfer tables and the gamut matrix in double, the refusals and the write step (kernels: light.hip).
 #include <algorithm>
 #include <cmath>
 #include <cstdio>
@@ -612,6 +613,250 @@ int hm_resample_to_tensor(int out_format, int src_w, int src_h, const void* d_sr
   hm_view_scratch* sc = new (std::nothrow) hm_view_scratch();
   if (!sc) return hm_fail(HM_ERR_NOMEM, "out of memory");
   rc = hm_view_write(dest, out_format, &vp, d_src, src_stride, (hipStream_t)stream, sc);
+  if (!sc->dev[0] && !sc->dev[1] && !sc->pinned) { delete sc; return rc; }
+  if (hipLaunchHostFunc((hipStream_t)stream, scratch_done, sc) != hipSuccess) { // (never on a healthy runtime: wait, then release here)
+    (void)hipGetLastError();
+    hipStreamSynchronize((hipStream_t)stream);
+    hm_view_scratch_free(sc);
+    delete sc;
+  }
+  return rc;
+}
+
+// ---- the light step (hm_device_light) -------------------------------------------------------------------------------------------
+
+namespace {
+
+bool transfer_known(int t) { return t == 1 || t == 4 || t == 5 || t == 6 || t == 8 || t == 13 || t == 14 || t == 15 || t == 16 || t == 18; }
+bool primaries_known(int p) { return p == 1 || p == 5 || p == 6 || p == 7 || p == 9 || p == 12; }
+
+// F_t: the code-to-light function of transfer t at e in [0, 1] (include/heif_mi355x.h), in double
+double light_of_code(int t, double e)
+{
+  switch (t) {
+    case 1: case 6: case 14: case 15: { // BT.709, with the constants that make the two pieces meet
+      const double alpha = 1.09929682680944, beta = 0.018053968510807;
+      return e < 4.5 * beta ? e / 4.5 : std::pow((e + (alpha - 1.0)) / alpha, 1.0 / 0.45);
+    }
+    case 4: return std::pow(e, 2.2);
+    case 5: return std::pow(e, 2.8);
+    case 13: return e <= 0.04045 ? e / 12.92 : std::pow((e + 0.055) / 1.055, 2.4);
+    case 16: { // SMPTE ST 2084 EOTF, 1.0 = 10000 cd/m2
+      const double m1 = 2610.0 / 16384.0, m2 = 2523.0 / 4096.0 * 128.0, c1 = 3424.0 / 4096.0, c2 = 2413.0 / 4096.0 * 32.0, c3 = 2392.0 / 4096.0 * 32.0;
+      const double p = std::pow(e, 1.0 / m2), num = p - c1 > 0.0 ? p - c1 : 0.0;
+      return std::pow(num / (c2 - c3 * p), 1.0 / m1);
+    }
+    case 18: { // BT.2100 HLG: the inverse OETF (scene light, no OOTF)
+      const double a = 0.17883277, b = 1.0 - 4.0 * a, c = 0.5 - a * std::log(4.0 * a);
+      return e <= 0.5 ? e * e / 3.0 : (std::exp((e - c) / a) + b) / 12.0;
+    }
+    default: return e; // 8: linear
+  }
+}
+
+void fill_light_table(int transfer, int bits, double g, bool encode, float* out)
+{
+  const int n = 1 << bits;
+  const double peak = (double)(n - 1);
+  if (!encode) { for (int c = 0; c < n; c++) out[c] = (float)(g * light_of_code(transfer, (double)c / peak)); return; }
+  out[0] = 0.0f; // (never looked at: the count runs over c = 1 .. peak)
+  for (int c = 1; c < n; c++) out[c] = (float)(g * light_of_code(transfer, ((double)c - 0.5) / peak));
+}
+
+// RGB -> XYZ of a set of primaries (H.273 chromaticities, D65 white), row-major
+bool primaries_to_xyz(int code, double M[9])
+{
+  double x[3], y[3];
+  switch (code) {
+    case 1: x[0] = 0.640; y[0] = 0.330; x[1] = 0.300; y[1] = 0.600; x[2] = 0.150; y[2] = 0.060; break;
+    case 5: x[0] = 0.640; y[0] = 0.330; x[1] = 0.290; y[1] = 0.600; x[2] = 0.150; y[2] = 0.060; break;
+    case 6: case 7: x[0] = 0.630; y[0] = 0.340; x[1] = 0.310; y[1] = 0.595; x[2] = 0.155; y[2] = 0.070; break;
+    case 9: x[0] = 0.708; y[0] = 0.292; x[1] = 0.170; y[1] = 0.797; x[2] = 0.131; y[2] = 0.046; break;
+    case 12: x[0] = 0.680; y[0] = 0.320; x[1] = 0.265; y[1] = 0.690; x[2] = 0.150; y[2] = 0.060; break;
+    default: return false;
+  }
+  const double xw = 0.3127, yw = 0.3290;
+  double P[9]; // columns: the primaries' XYZ at Y = 1
+  for (int k = 0; k < 3; k++) { P[k] = x[k] / y[k]; P[3 + k] = 1.0; P[6 + k] = (1.0 - x[k] - y[k]) / y[k]; }
+  const double W[3] = {xw / yw, 1.0, (1.0 - xw - yw) / yw};
+  // S = P^-1 W by Cramer's rule
+  auto det3 = [](const double* a) { return a[0] * (a[4] * a[8] - a[5] * a[7]) - a[1] * (a[3] * a[8] - a[5] * a[6]) + a[2] * (a[3] * a[7] - a[4] * a[6]); };
+  const double d = det3(P);
+  for (int k = 0; k < 3; k++) {
+    double Q[9];
+    std::memcpy(Q, P, sizeof(Q));
+    for (int r = 0; r < 3; r++) Q[3 * r + k] = W[r];
+    const double S = det3(Q) / d;
+    for (int r = 0; r < 3; r++) M[3 * r + k] = P[3 * r + k] * S;
+  }
+  return true;
+}
+
+void invert3(const double a[9], double inv[9])
+{
+  const double c00 = a[4] * a[8] - a[5] * a[7], c01 = a[5] * a[6] - a[3] * a[8], c02 = a[3] * a[7] - a[4] * a[6];
+  const double d = a[0] * c00 + a[1] * c01 + a[2] * c02;
+  inv[0] = c00 / d; inv[1] = (a[2] * a[7] - a[1] * a[8]) / d; inv[2] = (a[1] * a[5] - a[2] * a[4]) / d;
+  inv[3] = c01 / d; inv[4] = (a[0] * a[8] - a[2] * a[6]) / d; inv[5] = (a[2] * a[3] - a[0] * a[5]) / d;
+  inv[6] = c02 / d; inv[7] = (a[1] * a[6] - a[0] * a[7]) / d; inv[8] = (a[0] * a[4] - a[1] * a[3]) / d;
+}
+
+} // namespace
+
+int hm_light_table(int transfer, int bits, float gain, int encode, float* out)
+{
+  if (!out) return hm_fail(HM_ERR_INVALID_ARG, "null argument");
+  if (!transfer_known(transfer)) return hm_fail(HM_ERR_UNSUPPORTED, "light: transfer characteristics %d are not supported", transfer);
+  if (bits < 8 || bits > HM_LIGHT_MAX_BITS) return hm_fail(HM_ERR_UNSUPPORTED, "light: samples of %d bits (8 .. %d are supported)", bits, (int)HM_LIGHT_MAX_BITS);
+  if (!std::isfinite(gain) || !(gain > 0.0f)) return hm_fail(HM_ERR_INVALID_ARG, "light: gain %g is not finite and above 0", (double)gain);
+  fill_light_table(transfer, bits, (double)gain, encode != 0, out);
+  return 1 << bits;
+}
+
+int hm_light_matrix(int from_primaries, int to_primaries, float m[9])
+{
+  if (!m) return hm_fail(HM_ERR_INVALID_ARG, "null argument");
+  if (!primaries_known(from_primaries)) return hm_fail(HM_ERR_UNSUPPORTED, "light: colour primaries %d are not supported", from_primaries);
+  if (!primaries_known(to_primaries)) return hm_fail(HM_ERR_UNSUPPORTED, "light: colour primaries %d are not supported", to_primaries);
+  if (from_primaries == to_primaries) {
+    for (int i = 0; i < 9; i++) m[i] = i % 4 == 0 ? 1.0f : 0.0f;
+    return HM_OK;
+  }
+  double A[9], B[9], Bi[9];
+  primaries_to_xyz(from_primaries, A);
+  primaries_to_xyz(to_primaries, B);
+  invert3(B, Bi);
+  for (int r = 0; r < 3; r++)
+    for (int c = 0; c < 3; c++) m[3 * r + c] = (float)(Bi[3 * r] * A[c] + Bi[3 * r + 1] * A[3 + c] + Bi[3 * r + 2] * A[6 + c]);
+  return HM_OK;
+}
+
+int hm_light_check_static(int out_format, const hm_device_dest* d, const hm_device_light* l, int explicit_from)
+{
+  if (!l) return hm_fail(HM_ERR_INVALID_ARG, "null light step");
+  int rc = hm_dest_check_static(out_format, d);
+  if (rc) return rc;
+  if (l->reserved[0] || l->reserved[1] || l->reserved[2]) return hm_fail(HM_ERR_INVALID_ARG, "light: reserved is not 0");
+  if (!std::isfinite(l->gain) || !(l->gain > 0.0f)) return hm_fail(HM_ERR_INVALID_ARG, "light: gain %g is not finite and above 0", (double)l->gain);
+  if (explicit_from && (l->from_transfer == 0 || l->from_primaries == 0))
+    return hm_fail(HM_ERR_INVALID_ARG, "light: from_transfer and from_primaries must be given: the pixels carry no profile");
+  if (l->from_transfer != 0 && !transfer_known(l->from_transfer)) return hm_fail(HM_ERR_UNSUPPORTED, "light: transfer characteristics %d are not supported", l->from_transfer);
+  if (!transfer_known(l->to_transfer)) return hm_fail(HM_ERR_UNSUPPORTED, "light: transfer characteristics %d are not supported", l->to_transfer);
+  if (l->from_primaries != 0 && !primaries_known(l->from_primaries)) return hm_fail(HM_ERR_UNSUPPORTED, "light: colour primaries %d are not supported", l->from_primaries);
+  if (l->to_primaries != 0 && !primaries_known(l->to_primaries)) return hm_fail(HM_ERR_UNSUPPORTED, "light: colour primaries %d are not supported", l->to_primaries);
+  if (out_format == HM_OUT_RRGGBB_BE || out_format == HM_OUT_RRGGBBAA_BE)
+    return hm_fail(HM_ERR_INVALID_ARG, "light: a big-endian target has no sample values to look up: ask for the _LE format");
+  if (l->to_transfer == HM_LIGHT_LINEAR && (d->dtype == HM_DEV_U8 || d->dtype == HM_DEV_U16))
+    return hm_fail(HM_ERR_INVALID_ARG, "light: linear light needs a float dtype (integer dtype %d)", d->dtype);
+  return HM_OK;
+}
+
+int hm_light_resolve(int out_format, int bits, int img_transfer, int img_primaries, const hm_device_dest* d, const hm_device_light* l, hm_light_plan* lp)
+{
+  int rc = hm_light_check_static(out_format, d, l, 0);
+  if (rc) return rc;
+  std::memset(lp, 0, sizeof(*lp));
+  lp->from_transfer = l->from_transfer ? l->from_transfer : img_transfer;
+  lp->from_primaries = l->from_primaries ? l->from_primaries : img_primaries;
+  if (!transfer_known(lp->from_transfer)) return hm_fail(HM_ERR_UNSUPPORTED, "light: the image's transfer characteristics %d are not supported", lp->from_transfer);
+  if (!primaries_known(lp->from_primaries)) return hm_fail(HM_ERR_UNSUPPORTED, "light: the image's colour primaries %d are not supported", lp->from_primaries);
+  lp->to_transfer = l->to_transfer;
+  lp->to_primaries = l->to_primaries ? l->to_primaries : lp->from_primaries;
+  const int sb = hm_out_bytes_per_pixel(out_format) >= 6 ? 2 : 1;
+  if (sb == 1) bits = 8;
+  if (bits < 8 || bits > HM_LIGHT_MAX_BITS) return hm_fail(HM_ERR_UNSUPPORTED, "light: samples of %d bits (8 .. %d are supported)", bits, (int)HM_LIGHT_MAX_BITS);
+  lp->bits = bits;
+  lp->encode = lp->to_transfer != HM_LIGHT_LINEAR;
+  lp->matrix = lp->to_primaries != lp->from_primaries;
+  lp->gain = l->gain;
+  return hm_light_matrix(lp->from_primaries, lp->to_primaries, lp->m);
+}
+
+int hm_light_write(const hm_device_dest* d, int out_format, int w, int h, const hm_view_plan* vp, const hm_light_plan* lp, const void* src, int src_stride,
+                   hipStream_t s, hm_view_scratch* sc)
+{
+  if (!sc || sc->pinned || sc->dev[0] || sc->dev[1]) return hm_fail(HM_ERR_INTERNAL, "light: no free scratch for the tables");
+  const int ow = vp ? vp->ow : w, oh = vp ? vp->oh : h;
+  hm_dest_plan p;
+  int rc = hm_dest_resolve(out_format, ow, oh, d, &p);
+  if (!rc) rc = hm_dest_check_len(d, &p);
+  if (rc) return rc;
+  const int obpp = p.channels * p.sample_bytes;
+  const int cx = vp ? vp->x : 0, cy = vp ? vp->y : 0, cw = vp ? vp->w : w, ch = vp ? vp->h : h;
+  const uint8_t* origin = (const uint8_t*)src + (size_t)cy * src_stride + (size_t)cx * obpp;
+  const size_t n = (size_t)1 << lp->bits, table_bytes = n * sizeof(float) * (lp->encode ? 2 : 1);
+  const bool resampled = vp && !vp->crop_only && vp->filter != HM_VIEW_NEAREST;
+  hm_light_args la;
+  std::memset(&la, 0, sizeof(la));
+  la.bits = lp->bits; la.encode = lp->encode; la.matrix = lp->matrix;
+  std::memcpy(la.m, lp->m, sizeof(la.m));
+  auto fill = [&](float* host) { // lin, then enc
+    fill_light_table(lp->from_transfer, lp->bits, (double)lp->gain, false, host);
+    if (lp->encode) fill_light_table(lp->to_transfer, lp->bits, (double)lp->gain, true, host + n);
+  };
+  if (!resampled) {
+    float* host = (float*)hm_pool_pinned_alloc(table_bytes);
+    if (!host) return hm_fail(HM_ERR_NOMEM, "out of memory");
+    sc->pinned = host;
+    fill(host);
+    if (!(sc->dev[0] = hm_pool_device_alloc(table_bytes))) return HM_ERR_NO_DEVICE;
+    if ((rc = hm_check_hip(hipMemcpyAsync(sc->dev[0], host, table_bytes, hipMemcpyHostToDevice, s), "upload of the light tables"))) return rc;
+    la.lin = (const float*)sc->dev[0];
+    la.enc = lp->encode ? la.lin + n : nullptr;
+    if (vp && !vp->crop_only) return hm_launch_light_nearest(&p, &la, origin, src_stride, cw, ch, ow, oh, d->ptr, d->scale, d->bias, s);
+    return hm_launch_light_tensor(&p, &la, origin, src_stride, cw, ch, d->ptr, d->scale, d->bias, s);
+  }
+  // ONE pinned block and one upload: the tap tables of both axes, then the light tables
+  size_t words_x = 0, words_y = 0;
+  int tx = 0, ty = 0;
+  bool staged = false;
+  if ((rc = view_tables(vp, table_bytes, sc, &words_x, &words_y, &tx, &ty, &staged))) return rc;
+  const size_t tap_bytes = (words_x + words_y) * 4, bytes = tap_bytes + table_bytes;
+  int32_t* host = (int32_t*)sc->pinned;
+  fill(reinterpret_cast<float*>(host + words_x + words_y));
+  const bool chw = p.layout == HM_DEV_LAYOUT_CHW;
+  const int64_t E = chw ? vp->ow : (int64_t)vp->ow * p.channels, pitch = (E + 15) / 16 * 16, plane = pitch * vp->h;
+  if (!(sc->dev[0] = hm_pool_device_alloc(bytes)) || !(sc->dev[1] = hm_pool_device_alloc((size_t)plane * (chw ? p.channels : 1) * sizeof(float)))) return HM_ERR_NO_DEVICE;
+  if ((rc = hm_check_hip(hipMemcpyAsync(sc->dev[0], host, bytes, hipMemcpyHostToDevice, s), "upload of the tap and light tables"))) return rc;
+  hm_resample_args a;
+  std::memset(&a, 0, sizeof(a));
+  a.sample_bytes = p.sample_bytes; a.channels = p.channels;
+  a.src = origin; a.src_stride = src_stride;
+  a.n_w = vp->w; a.n_h = vp->h; a.ow = vp->ow; a.oh = vp->oh;
+  const int32_t* dx = (const int32_t*)sc->dev[0];
+  const int32_t* dy = dx + words_x;
+  a.ax.first = dx; a.ax.count = dx + vp->ow; a.ax.weights = reinterpret_cast<const float*>(dx + 2 * (size_t)vp->ow); a.ax.m = vp->ow; a.ax.taps = tx;
+  a.ay.first = dy; a.ay.count = dy + vp->oh; a.ay.weights = reinterpret_cast<const float*>(dy + 2 * (size_t)vp->oh); a.ay.m = vp->oh; a.ay.taps = ty;
+  a.tmp = (float*)sc->dev[1]; a.tmp_pitch = pitch; a.tmp_plane = plane;
+  la.lin = reinterpret_cast<const float*>(dy + words_y);
+  la.enc = lp->encode ? la.lin + n : nullptr;
+  return hm_launch_light_resample(&p, &la, &a, d->ptr, d->scale, d->bias, s);
+}
+
+int hm_light_to_tensor(int out_format, int bits, int src_w, int src_h, const void* d_src, int src_stride, const hm_device_view* view, const hm_device_light* light,
+                       const hm_device_dest* dest, void* stream)
+{
+  if (!d_src || !dest || !light) return hm_fail(HM_ERR_INVALID_ARG, "null argument");
+  int rc = hm_light_check_static(out_format, dest, light, 1);
+  if (rc) return rc;
+  if (src_w <= 0 || src_h <= 0 || src_w > 32768 || src_h > 32768) return hm_fail(HM_ERR_INVALID_ARG, "image size %d x %d", src_w, src_h);
+  hm_view_plan vp;
+  std::memset(&vp, 0, sizeof(vp));
+  vp.ow = src_w; vp.oh = src_h;
+  if (view && (rc = hm_view_resolve(out_format, src_w, src_h, view, &vp))) return rc;
+  hm_light_plan lp;
+  if ((rc = hm_light_resolve(out_format, bits, light->from_transfer, light->from_primaries, dest, light, &lp))) return rc;
+  hm_dest_plan p;
+  if ((rc = hm_dest_resolve(out_format, vp.ow, vp.oh, dest, &p)) || (rc = hm_dest_check_len(dest, &p))) return rc;
+  if (src_stride < src_w * hm_out_bytes_per_pixel(out_format)) return hm_fail(HM_ERR_INVALID_ARG, "src_stride %d below the bytes of a row", src_stride);
+  if (p.sample_bytes == 2 && (((uintptr_t)d_src | (unsigned)src_stride) & 1)) return hm_fail(HM_ERR_INVALID_ARG, "16-bit samples at an odd address or stride");
+  int n_dev = 0;
+  if (hipGetDeviceCount(&n_dev) != hipSuccess || n_dev == 0) { (void)hipGetLastError(); return hm_fail(HM_ERR_NO_DEVICE, "no HIP device available"); }
+  if ((rc = hm_dest_check_pointer(dest))) return rc;
+  release_done();
+  hm_view_scratch* sc = new (std::nothrow) hm_view_scratch();
+  if (!sc) return hm_fail(HM_ERR_NOMEM, "out of memory");
+  rc = hm_light_write(dest, out_format, src_w, src_h, view ? &vp : nullptr, &lp, d_src, src_stride, (hipStream_t)stream, sc);
   if (!sc->dev[0] && !sc->dev[1] && !sc->pinned) { delete sc; return rc; }
   if (hipLaunchHostFunc((hipStream_t)stream, scratch_done, sc) != hipSuccess) { // (never on a healthy runtime: wait, then release here)
     (void)hipGetLastError();

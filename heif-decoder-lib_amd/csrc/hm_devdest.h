@@ -128,6 +128,36 @@ int hm_launch_resample_batch(const hm_dest_plan* p, const hm_resample_args* a, c
 int hm_launch_view_nearest(const hm_dest_plan* p, const void* src, int src_stride, int n_w, int n_h, int ow, int oh, void* dst, const float scale[4],
                            const float bias[4], hipStream_t s);
 
+// ---- the light step (hm_device_light): code values to linear light through a table, a gamut matrix, linear floats or a search in a
+//      threshold table.  devdest.cpp holds the tables, the matrix, the checks and the write step, light.hip the kernels ----
+enum { HM_LIGHT_MAX_BITS = 12 }; // both tables of a pointwise kernel sit in LDS: 2 x 16 KB
+typedef struct hm_light_plan {
+  int32_t from_transfer, from_primaries, to_transfer, to_primaries; // H.273 codes, nothing left at 0
+  int32_t bits;          // of the target's samples
+  int32_t encode;        // to_transfer != HM_LIGHT_LINEAR
+  int32_t matrix;        // to_primaries differs from from_primaries
+  float gain;
+  float m[9];
+} hm_light_plan;
+// what depends on the request alone: reserved, gain, the codes (from_* == 0: allowed unless `explicit_from`), the target (no _BE, no
+// planar one), HM_LIGHT_LINEAR with an integer dtype
+int hm_light_check_static(int out_format, const hm_device_dest* d, const hm_device_light* l, int explicit_from);
+// ... and what depends on the image: from_* == 0 become img_transfer / img_primaries (what hm_decoded reports), bits the sample depth
+int hm_light_resolve(int out_format, int bits, int img_transfer, int img_primaries, const hm_device_dest* d, const hm_device_light* l, hm_light_plan* lp);
+// hm_dest_write / hm_view_write under a light step: the w x h image at `src` (vp NULL), or its view vp, into the destination, which
+// has been checked against the size written; asynchronous on `s`.  The tables (and a view's tap tables and intermediate) hang on sc.
+int hm_light_write(const hm_device_dest* d, int out_format, int w, int h, const hm_view_plan* vp, const hm_light_plan* lp, const void* src, int src_stride,
+                   hipStream_t s, hm_view_scratch* sc);
+
+// what the kernels get: device pointers of lin[1 << bits] and (encode) enc[1 << bits]
+typedef struct hm_light_args { const float* lin; const float* enc; int32_t bits, encode, matrix; float m[9]; } hm_light_args;
+int hm_launch_light_tensor(const hm_dest_plan* p, const hm_light_args* la, const void* src, int src_stride, int w, int rows, void* dst, const float scale[4],
+                           const float bias[4], hipStream_t s);
+int hm_launch_light_nearest(const hm_dest_plan* p, const hm_light_args* la, const void* src, int src_stride, int n_w, int n_h, int ow, int oh, void* dst,
+                            const float scale[4], const float bias[4], hipStream_t s);
+int hm_launch_light_resample(const hm_dest_plan* p, const hm_light_args* la, const hm_resample_args* r, void* dst, const float scale[4], const float bias[4],
+                             hipStream_t s);
+
 // ---- planar views: a view (hm_device_view) into planar YCbCr (hm_device_planes), every plane an image of its own.  devdest.cpp
 //      holds the checks and the write step, hm_planes_view.h the index arithmetic, planes_view.hip the kernels ----
 typedef struct hm_planes_view_plan {

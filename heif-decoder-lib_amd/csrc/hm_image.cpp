@@ -788,10 +788,12 @@ void parse_picture(const hm_file* f, uint32_t id, bool few_pictures, int strict,
 // planes (may be NULL; a planar result only): caller-owned device memory the planes go to instead (hm_device_planes), one launch of
 // k_planes_to_tensor in place of the pinned allocations and the copies to the host.  With view: the view of every plane of the
 // result (hm_planes_view_write), written here or - planes_later - only described there for the caller's grouped write.
+// light (may be NULL, with dest): the write of the destination runs the light step (hm_light_write, here, on view_scratch); what
+// of it depends on the image's own profile or depth is refused before a byte of the destination is written.
 int emit_image(const hm_decode_params* params, hipStream_t s, PlanarImage& I, const DevPlane* alpha, int alpha_bd, DevMem& dout,
                DevPlane& alpha_sdr, hm_decoded* out, const hm_device_dest* dest = nullptr, const hm_device_view* view = nullptr,
                hm_view_scratch* view_scratch = nullptr, hm_view_item* view_later = nullptr, const hm_device_planes* planes = nullptr,
-               hm_planes_view_item* planes_later = nullptr)
+               hm_planes_view_item* planes_later = nullptr, const hm_device_light* light = nullptr)
 {
   int rc;
   DevPlane (&P)[3] = I.P;
@@ -970,13 +972,20 @@ int emit_image(const hm_decode_params* params, hipStream_t s, PlanarImage& I, co
     out->stride[0] = cd.out_stride;
     out->plane_width[0] = img_w; out->plane_height[0] = img_h;
     if (dest) { // the image's w x h x C elements and nothing else: a 2-D device copy or k_to_tensor (devdest.cpp)
-      if (view) {
+      if (light) { // ... through the light step, resolved against the profile and depth this image reports: refused before a byte is written
+        hm_light_plan lp;
+        if ((rc = hm_light_resolve(params->out_format, out->bit_depth, out->transfer, out->primaries, dest, light, &lp))) return rc;
+        if ((rc = hm_light_write(dest, params->out_format, img_w, img_h, view ? &vp : nullptr, &lp, dout.p, cd.out_stride, s, view_scratch))) return rc;
+      }
+      else if (view) {
         if (view_later) { view_later->dest = dest; view_later->vp = vp; view_later->src = dout.p; view_later->src_stride = cd.out_stride; } // (a sequence: hm_view_write_batch)
         else if ((rc = hm_view_write(dest, params->out_format, &vp, dout.p, cd.out_stride, s, view_scratch))) return rc;
+      }
+      else if ((rc = hm_dest_write(dest, params->out_format, img_w, img_h, 0, img_h, dout.p, cd.out_stride, s))) return rc;
+      if (view) {
         out->width = vp.ow; out->height = vp.oh;
         out->plane_width[0] = vp.ow; out->plane_height[0] = vp.oh;
       }
-      else if ((rc = hm_dest_write(dest, params->out_format, img_w, img_h, 0, img_h, dout.p, cd.out_stride, s))) return rc;
       hm_dest_plan dp;
       if ((rc = hm_dest_resolve(params->out_format, vp.ow, vp.oh, dest, &dp))) return rc;
       out->used_ext_dst = 1;
@@ -1049,17 +1058,19 @@ int job_enqueue(DecodeJob& j, hm_decoded* out)
   hm_device_view shifted = j.view; // (the crop inside the sub-grid that was decoded)
   if (j.has_view && (shifted.crop_w || shifted.crop_h)) { shifted.crop_x -= j.view_dx; shifted.crop_y -= j.view_dy; }
   rc = emit_image(params, s, I, alpha, alpha_bd, j.dout, j.alpha_sdr, out, j.has_dest ? &j.dest : nullptr, j.has_view ? &shifted : nullptr, &j.view_scratch, nullptr,
-                  j.has_planes ? &j.planes : nullptr);
+                  j.has_planes ? &j.planes : nullptr, nullptr, j.has_light ? &j.light : nullptr);
   if (rc) return rc;
   lap("colour + D2H queued");
   return HM_OK;
 }
 
-int check_device_request(const hm_file* f, uint32_t id, const hm_decode_params* params, const hm_device_dest* dest, const hm_device_view* view)
+int check_device_request(const hm_file* f, uint32_t id, const hm_decode_params* params, const hm_device_dest* dest, const hm_device_view* view,
+                         const hm_device_light* light)
 {
   if (params->ext_dst) return hm_fail(HM_ERR_INVALID_ARG, "params->ext_dst must be NULL with a device destination");
   int rc = hm_dest_check_static(params->out_format, dest);
   if (rc) return rc;
+  if (light && (rc = hm_light_check_static(params->out_format, dest, light, 0))) return rc;
   if (!dest->ptr) return hm_fail(HM_ERR_INVALID_ARG, "device destination: null ptr");
   hm_image_info info;
   if (hm_file_image_info(f, id, &info) == HM_OK) { // (a file that fails here fails the decode with its own message)
@@ -1476,7 +1487,7 @@ int derived_refusal(const hm_file* f, uint32_t id, const hm_decode_params* param
 
 // hm_decode_item and its device forms on a derived item
 int decode_derived(const hm_file* f, uint32_t id, const hm_decode_params* params, const hm_device_dest* dest, const hm_device_view* view, const hm_device_planes* planes,
-                   hm_decoded* out)
+                   hm_decoded* out, const hm_device_light* light = nullptr)
 {
   std::memset(out, 0, sizeof(*out));
   Lap lap;
@@ -1528,7 +1539,7 @@ int decode_derived(const hm_file* f, uint32_t id, const hm_decode_params* params
     LayerImage L;
     if ((rc = produce_coded(R, root, L))) return rc;
     if (L.alpha) out->has_alpha = 1;
-    rc = emit_image(params, R.s, root.job->I, L.alpha, 8, R.dout, R.alpha_sdr, out, dest, view, &R.view_scratch, nullptr, planes);
+    rc = emit_image(params, R.s, root.job->I, L.alpha, 8, R.dout, R.alpha_sdr, out, dest, view, &R.view_scratch, nullptr, planes, nullptr, light);
     if (L.alpha && !rc) out->has_alpha = 1;
   }
   else {
@@ -1557,7 +1568,7 @@ int decode_derived(const hm_file* f, uint32_t id, const hm_decode_params* params
     // which carries no profile of its own, like a grid canvas - the converted image then reports the sRGB defaults
     I.w = w; I.h = h; I.chroma = 3; I.bd = 8; I.is_grid = true; I.rgb_attached = true;
     I.native = hm::NclxProfile();
-    rc = emit_image(params, R.s, I, nullptr, 0, R.dout, R.alpha_sdr, out, dest, view, &R.view_scratch, nullptr, nullptr);
+    rc = emit_image(params, R.s, I, nullptr, 0, R.dout, R.alpha_sdr, out, dest, view, &R.view_scratch, nullptr, nullptr, nullptr, light);
   }
   return rc;
   }();
@@ -1584,7 +1595,7 @@ extern "C" {
 static int decode_grid_cut(const hm_file* f, uint32_t id, const hm_decode_params* params, const int32_t* devices, int n_devices, bool pipelined, hm_decoded* out, bool* applicable,
                            const hm_device_dest* dest = nullptr); // (below, behind the slabs)
 static int decode_item(const hm_file* f, uint32_t id, const hm_decode_params* params, const hm_device_dest* dest, hm_decoded* out, const hm_device_view* view = nullptr,
-                       const hm_device_planes* planes = nullptr);
+                       const hm_device_planes* planes = nullptr, const hm_device_light* light = nullptr);
 
 int hm_decode_item(const hm_file* f, uint32_t id, const hm_decode_params* params, hm_decoded* out)
 {
@@ -1610,6 +1621,17 @@ int hm_decode_item_to_device_view(const hm_file* f, uint32_t id, const hm_decode
   const int rc = check_device_request(f, id, params, dest, view); // refused before any work is queued: the destination is not written
   if (rc) return rc;
   return decode_item(f, id, params, dest, out, view);
+}
+
+int hm_decode_item_to_device_light(const hm_file* f, uint32_t id, const hm_decode_params* params, const hm_device_view* view, const hm_device_light* light,
+                                   const hm_device_dest* dest, hm_decoded* out)
+{
+  if (!f || !params || !light || !dest || !out) return hm_fail(HM_ERR_INVALID_ARG, "null argument");
+  std::memset(out, 0, sizeof(*out));
+  if (is_derived_item(f, id)) { const int drc = derived_refusal(f, id, params, false); if (drc) return drc; }
+  const int rc = check_device_request(f, id, params, dest, view, light); // refused before any work is queued: the destination is not written
+  if (rc) return rc;
+  return decode_item(f, id, params, dest, out, view, nullptr, light);
 }
 
 int hm_decode_item_to_device_planes(const hm_file* f, uint32_t id, const hm_decode_params* params, const hm_device_planes* planes, hm_decoded* out)
@@ -1714,12 +1736,13 @@ int hm_plan_view(const hm_file* f, uint32_t id, const hm_decode_params* params, 
 // dest (may be NULL): the pixels go to caller-owned device memory; view (may be NULL, with dest only): a rectangle of them, resampled -
 // always as one job (its plan is reduced to the tiles the crop touches), never slab by slab
 // planes (may be NULL, without dest): a planar result goes to caller-owned device memory plane by plane (planar output is one job: the cut below declines it)
+// light (may be NULL, with dest): the light step in the write of the destination - one job, as with a view
 static int decode_item(const hm_file* f, uint32_t id, const hm_decode_params* params, const hm_device_dest* dest, hm_decoded* out, const hm_device_view* view,
-                       const hm_device_planes* planes)
+                       const hm_device_planes* planes, const hm_device_light* light)
 {
   std::memset(out, 0, sizeof(*out)); // (whatever fails below: nothing of an earlier call is left in it)
-  if (is_derived_item(f, id)) return decode_derived(f, id, params, dest, view, planes, out);
-  if (!view) { // (r06) a grid of more tiles than parsing threads, to interleaved pixels: slab by slab under the entropy decode (decode_grid_cut)
+  if (is_derived_item(f, id)) return decode_derived(f, id, params, dest, view, planes, out, light);
+  if (!view && !light) { // (r06) a grid of more tiles than parsing threads, to interleaved pixels: slab by slab under the entropy decode (decode_grid_cut)
     bool applicable = false;
     const int prc = decode_grid_cut(f, id, params, nullptr, 1, /*pipelined=*/true, out, &applicable, dest);
     if (prc || applicable) return prc;
@@ -1731,6 +1754,7 @@ static int decode_item(const hm_file* f, uint32_t id, const hm_decode_params* pa
   if (dest) { job.dest = *dest; job.has_dest = true; }
   if (view) { job.view = *view; job.has_view = true; }
   if (planes) { job.planes = *planes; job.has_planes = true; }
+  if (light) { job.light = *light; job.has_light = true; }
   int rc = job_plan(job);
   if (rc) return rc;
   // ---- host: entropy-decode every coded picture (CABAC on the CPU, spread over threads like the reference's
@@ -1807,7 +1831,8 @@ int hm_file_sequence_info(const hm_file* f, hm_sequence_info* info)
 }
 
 static int decode_sequence(const hm_file* f, const uint32_t* frames, uint32_t first, int32_t count, const hm_decode_params* params, const hm_frame_dest* dests,
-                           const hm_device_dest* ddests, const hm_device_view* view, hm_decoded* out, int32_t* failed_frame, const hm_device_planes* pdests = nullptr);
+                           const hm_device_dest* ddests, const hm_device_view* view, hm_decoded* out, int32_t* failed_frame, const hm_device_planes* pdests = nullptr,
+                           const hm_device_light* light = nullptr);
 
 int hm_decode_frames_to_device_planes_view(const hm_file* f, const uint32_t* frames, int32_t count, const hm_decode_params* params, const hm_device_view* view,
                                            const hm_device_planes* planes, hm_decoded* out, int32_t* failed_frame)
@@ -1839,6 +1864,14 @@ int hm_decode_frames_to_device_view(const hm_file* f, const uint32_t* frames, in
   return decode_sequence(f, frames, 0, count, params, nullptr, dests, view, out, failed_frame);
 }
 
+int hm_decode_frames_to_device_light(const hm_file* f, const uint32_t* frames, int32_t count, const hm_decode_params* params, const hm_device_view* view,
+                                     const hm_device_light* light, const hm_device_dest* dests, hm_decoded* out, int32_t* failed_frame)
+{
+  if (failed_frame) *failed_frame = -1;
+  if (!frames || !dests || !light) return hm_fail(HM_ERR_INVALID_ARG, "null argument");
+  return decode_sequence(f, frames, 0, count, params, nullptr, dests, view, out, failed_frame, nullptr, light);
+}
+
 int hm_decode_frames_to_device_planes(const hm_file* f, const uint32_t* frames, int32_t count, const hm_decode_params* params, const hm_device_planes* planes,
                                       hm_decoded* out, int32_t* failed_frame)
 {
@@ -1851,8 +1884,10 @@ int hm_decode_frames_to_device_planes(const hm_file* f, const uint32_t* frames, 
 // pdests (NULL, or `count` entries, without ddests): every frame's planar result goes to caller-owned device memory (hm_device_planes)
 // ddests (NULL, or `count` entries): every frame goes to caller-owned device memory; view (NULL, or with ddests or pdests): the same
 // rectangle of every frame, resampled, in one batched write behind the frames' conversions (hm_view_write_batch, hm_planes_view_write)
+// light (NULL, or with ddests): every frame's write runs the light step, frame by frame (hm_light_write) - no batched form
 static int decode_sequence(const hm_file* f, const uint32_t* frames, uint32_t first, int32_t count, const hm_decode_params* params, const hm_frame_dest* dests,
-                           const hm_device_dest* ddests, const hm_device_view* view, hm_decoded* out, int32_t* failed_frame, const hm_device_planes* pdests)
+                           const hm_device_dest* ddests, const hm_device_view* view, hm_decoded* out, int32_t* failed_frame, const hm_device_planes* pdests,
+                           const hm_device_light* light)
 {
   if (failed_frame) *failed_frame = -1;
   if (!f || !params || !out) return hm_fail(HM_ERR_INVALID_ARG, "null argument");
@@ -1873,7 +1908,8 @@ static int decode_sequence(const hm_file* f, const uint32_t* frames, uint32_t fi
   if (params->ext_dst) return hm_fail(HM_ERR_INVALID_ARG, "params->ext_dst: a sequence takes its caller buffers from dests");
   if (ddests) { // what can be refused without the frames' sizes (those: below, behind the entropy decode, before anything is queued)
     for (int k = 0; k < count; k++) {
-      const int rc = hm_dest_check_static(params->out_format, &ddests[k]);
+      int rc = hm_dest_check_static(params->out_format, &ddests[k]);
+      if (!rc && light) rc = hm_light_check_static(params->out_format, &ddests[k], light, 0);
       if (rc) return rc;
       if (!ddests[k].ptr) return hm_fail(HM_ERR_INVALID_ARG, "device destination of frame %d: null ptr", k);
     }
@@ -1974,6 +2010,13 @@ static int decode_sequence(const hm_file* f, const uint32_t* frames, uint32_t fi
       int drc = view ? hm_view_resolve(params->out_format, I.w, I.h, view, &vp) : HM_OK; // (against the frame's own decoded size)
       if (!drc) drc = hm_dest_resolve(params->out_format, vp.ow, vp.oh, &ddests[k], &dp);
       if (!drc) drc = hm_dest_check_len(&ddests[k], &dp);
+      if (!drc && light) { // (the profile and depth emit_image will report for this frame)
+        hm_light_plan lp;
+        const int obpp = hm_out_bytes_per_pixel(params->out_format);
+        const int bits = obpp >= 6 && I.bd == 8 ? 10 : I.bd;
+        drc = hm_light_resolve(params->out_format, bits, I.native.transfer == 2 ? 13 : I.native.transfer, I.native.primaries == 2 ? 1 : I.native.primaries, &ddests[k],
+                               light, &lp);
+      }
       if (drc) return fail(drc);
     }
     if (pdests) { // the destination against the picture's own format: the check hm_planes_write repeats before its launch
@@ -2042,7 +2085,7 @@ static int decode_sequence(const hm_file* f, const uint32_t* frames, uint32_t fi
   } view_blocks;
   std::vector<hm_view_item> view_items;
   std::vector<hm_planes_view_item> planes_items;
-  if (view && ddests) { view_blocks.sc.assign((size_t)count, hm_view_scratch{}); view_items.assign((size_t)count, hm_view_item{}); }
+  if ((view || light) && ddests) { view_blocks.sc.assign((size_t)count, hm_view_scratch{}); view_items.assign((size_t)count, hm_view_item{}); }
   if (view && pdests) { view_blocks.sc.assign((size_t)count, hm_view_scratch{}); planes_items.assign((size_t)count, hm_planes_view_item{}); }
   struct Drain { // (declared behind everything the queued work uses: destroyed first, it drains the stream before they go)
     hipStream_t s; bool on = false;
@@ -2099,14 +2142,16 @@ static int decode_sequence(const hm_file* f, const uint32_t* frames, uint32_t fi
     if (dests) { pk.ext_dst = dests[k].ext_dst; pk.ext_dst_len = dests[k].ext_dst_len; pk.ext_dst_stride = dests[k].ext_dst_stride; }
     const bool viewed = view && ddests;
     const bool pviewed = view && pdests;
-    if ((rc = emit_image(&pk, s, Fr.I, nullptr, 0, Fr.dout, Fr.alpha_sdr, &out[k], ddests ? &ddests[k] : nullptr, viewed || pviewed ? view : nullptr, nullptr,
-                         viewed ? &view_items[(size_t)k] : nullptr, pdests ? &pdests[k] : nullptr, pviewed ? &planes_items[(size_t)k] : nullptr))) {
-      if (failed_frame && pviewed) *failed_frame = k;
+    const bool lit = light && ddests; // (written here, on the frame's own scratch entry: nothing is left for the batched write)
+    if ((rc = emit_image(&pk, s, Fr.I, nullptr, 0, Fr.dout, Fr.alpha_sdr, &out[k], ddests ? &ddests[k] : nullptr, viewed || pviewed ? view : nullptr,
+                         lit ? &view_blocks.sc[(size_t)k] : nullptr, viewed && !lit ? &view_items[(size_t)k] : nullptr, pdests ? &pdests[k] : nullptr,
+                         pviewed ? &planes_items[(size_t)k] : nullptr, lit ? light : nullptr))) {
+      if (failed_frame && (pviewed || lit)) *failed_frame = k;
       return release_all(rc);
     }
   }
   // ---- the view of every frame: one pair of tap tables and one launch per pass for all frames that share them ----
-  if (view && ddests && (rc = hm_view_write_batch(params->out_format, view_items.data(), count, s, view_blocks.sc.data()))) return release_all(rc);
+  if (view && ddests && !light && (rc = hm_view_write_batch(params->out_format, view_items.data(), count, s, view_blocks.sc.data()))) return release_all(rc);
   if (view && pdests) { // ... and of every frame's planes: the tables of at most four axes per group (hm_planes_view_write)
     int bad = -1;
     if ((rc = hm_planes_view_write(planes_items.data(), count, s, view_blocks.sc.data(), &bad))) {

@@ -115,7 +115,10 @@ struct DecodeJob {
   bool has_view = false;
   int view_dx = 0, view_dy = 0;
   int32_t sub_tiles[4] = {0, 0, 0, 0};
-  hm_view_scratch view_scratch{}; // tap tables and the intermediate of the resampling step
+  hm_view_scratch view_scratch{}; // tap tables and the intermediate of the resampling step, the tables of the light step
+  // a light step in the write of the destination (hm_device_light; with has_dest): the item is decoded as one job, never slab by slab
+  hm_device_light light{};
+  bool has_light = false;
   // a planar result (out_format 0 / HM_OUT_YCBCR_*) goes to caller-owned device memory, plane by plane (has_planes; never together with has_dest)
   hm_device_planes planes{};
   bool has_planes = false;
@@ -149,7 +152,9 @@ int job_enqueue(DecodeJob& j, hm_decoded* out);
 // everything about a device destination that can be refused before the entropy decode: the request itself, the destination against
 // the size the file declares for the item, a device, the pointer (hm_image.cpp)
 // view (may be NULL): the destination is judged against the view's output size, the crop against the declared size
-int check_device_request(const hm_file* f, uint32_t id, const hm_decode_params* params, const hm_device_dest* dest, const hm_device_view* view = nullptr);
+// light (may be NULL): what of the light step depends on the request alone
+int check_device_request(const hm_file* f, uint32_t id, const hm_decode_params* params, const hm_device_dest* dest, const hm_device_view* view = nullptr,
+                         const hm_device_light* light = nullptr);
 // the same for a planar destination (hm_device_planes): the request, the planes against what hm_image_info declares (size, and the
 // result's chroma format and depth where the file decides them), a device, the pointers
 // view (may be NULL): the planes are judged against the view's output size, the crop against the declared size and the result's chroma format

@@ -1,0 +1,453 @@
+// light.hip — the light step (hm_device_light) of a device destination (gfx950): transfer-encoded code values become linear light
+// through a table, change primaries through a 3 x 3 matrix, and are stored as linear floats or re-encoded by a search in a
+// threshold table.  No transcendental function runs here: both tables are built on the host in double (devdest.cpp), so a
+// float32 restatement on the host is exact.
+//   k_light_tensor   the pointwise path, k_to_tensor's streaming shape: a wave takes 64 consecutive pixel groups of ONE row, a lane's
+//                    group is 16 bytes of output per channel plane, 16-byte stores where pointers and pitches allow, the scalar
+//                    instance (lane l takes pixels l, l + 64, ...) otherwise.  The crop alone runs here on the offset source.
+//   k_light_nearest  HM_VIEW_NEAREST: the pixel at (j * n_w / ow, k * n_h / oh) through the same per-pixel step.
+//   k_light_h        k_resample_h's sums in its order with the table lookup in place of the conversion to float (alpha: the
+//                    conversion as it was).  The unstaged form, for all three filters.
+//   k_light_v        the vertical sums of ONE pixel per lane - the matrix needs R, G and B together: a CHW intermediate is read at
+//                    one index of three planes -, then matrix and finish.
+// LDS: lin[1 << bits] and, when re-encoding, enc[1 << bits] behind it (1 KB each at 8 bits, 16 KB each at 12), filled once per
+// workgroup.  The lookups are data-dependent ds_read_b32: lanes that meet the same entry are served by one broadcast, different
+// entries of one bank serialise - a flat image is the best case, noise the worst; no layout of a table changes that.
+// The matrix and the scalars of the step are kernel arguments (SGPRs).  -ffp-contract=off, __fmul_rn / __fadd_rn throughout.
+#include <hip/hip_runtime.h>
+#include <hip/hip_fp16.h>
+#include <stdint.h>
+
+#include <type_traits>
+
+#include "hm_devdest.h"
+
+namespace {
+
+struct Affine { float scale[4], bias[4]; };
+struct Light { const float* lin; const float* enc; int bits, encode, matrix; float m[9]; };
+
+// a (may be NULL) -> lds[0 .. n), b (may be NULL) -> lds[n .. 2 n); every thread of the workgroup comes here
+__device__ __forceinline__ void fill_tables(float* lds, const float* __restrict__ a, const float* __restrict__ b, int n)
+{
+  if (a) for (int i = threadIdx.x; i < n; i += 256) lds[i] = a[i];
+  if (b) for (int i = threadIdx.x; i < n; i += 256) lds[n + i] = b[i];
+  __syncthreads();
+}
+
+// a code value that is stored (k_to_tensor's rule for a sample that is moved)
+template <typename OutT> __device__ __forceinline__ OutT moved(unsigned v, float sc, float bi);
+template <> __device__ __forceinline__ uint8_t moved<uint8_t>(unsigned v, float, float) { return (uint8_t)v; }
+template <> __device__ __forceinline__ uint16_t moved<uint16_t>(unsigned v, float, float) { return (uint16_t)v; }
+template <> __device__ __forceinline__ float moved<float>(unsigned v, float sc, float bi) { return __fadd_rn(__fmul_rn((float)v, sc), bi); }
+template <> __device__ __forceinline__ __half moved<__half>(unsigned v, float sc, float bi) { return __float2half_rn(__fadd_rn(__fmul_rn((float)v, sc), bi)); }
+
+// linear light that is stored (float dtypes: the host refuses HM_LIGHT_LINEAR with an integer one)
+template <typename OutT> __device__ __forceinline__ OutT linear_out(float r, float sc, float bi) { return (OutT)0; }
+template <> __device__ __forceinline__ float linear_out<float>(float r, float sc, float bi) { return __fadd_rn(__fmul_rn(r, sc), bi); }
+template <> __device__ __forceinline__ __half linear_out<__half>(float r, float sc, float bi) { return __float2half_rn(__fadd_rn(__fmul_rn(r, sc), bi)); }
+
+// a resampled alpha value (k_resample_v's finish)
+template <typename OutT> __device__ __forceinline__ OutT alpha_out(float r, float sc, float bi);
+template <> __device__ __forceinline__ uint8_t alpha_out<uint8_t>(float r, float, float) { const int v = (int)__fadd_rn(r, 0.5f); return (uint8_t)min(max(v, 0), 255); }
+template <> __device__ __forceinline__ uint16_t alpha_out<uint16_t>(float r, float, float) { const int v = (int)__fadd_rn(r, 0.5f); return (uint16_t)min(max(v, 0), 65535); }
+template <> __device__ __forceinline__ float alpha_out<float>(float r, float sc, float bi) { return __fadd_rn(__fmul_rn(r, sc), bi); }
+template <> __device__ __forceinline__ __half alpha_out<__half>(float r, float sc, float bi) { return __float2half_rn(__fadd_rn(__fmul_rn(r, sc), bi)); }
+
+// |{c in 1 .. peak : enc[c] <= r}|: enc rises, so the count is the largest c whose threshold r has reached (0: none; a NaN: none)
+__device__ __forceinline__ unsigned encode_of(const float* enc, int bits, float r)
+{
+  int code = 0;
+  for (int step = 1 << (bits - 1); step; step >>= 1) { // (code + step <= peak: the steps sum to it)
+    const int t = code + step;
+    if (enc[t] <= r) code = t;
+  }
+  return (unsigned)code;
+}
+
+__device__ __forceinline__ void gamut(const Light& L, float r[3])
+{
+  if (!L.matrix) return;
+  const float R = r[0], G = r[1], B = r[2];
+  r[0] = __fadd_rn(__fadd_rn(__fmul_rn(L.m[0], R), __fmul_rn(L.m[1], G)), __fmul_rn(L.m[2], B));
+  r[1] = __fadd_rn(__fadd_rn(__fmul_rn(L.m[3], R), __fmul_rn(L.m[4], G)), __fmul_rn(L.m[5], B));
+  r[2] = __fadd_rn(__fadd_rn(__fmul_rn(L.m[6], R), __fmul_rn(L.m[7], G)), __fmul_rn(L.m[8], B));
+}
+
+// linear light r of a colour channel to an element of the destination; enc: the threshold table in LDS
+template <typename OutT> __device__ __forceinline__ OutT colour_out(const Light& L, const float* enc, float r, float sc, float bi)
+{
+  if (L.encode) return moved<OutT>(encode_of(enc, L.bits, r), sc, bi);
+  return linear_out<OutT>(r, sc, bi);
+}
+
+// one pixel that is moved, not resampled: v0 .. v2 its colour samples, v3 its alpha sample (C == 4); lds = lin, then enc
+template <int C, typename OutT>
+__device__ __forceinline__ void pixel(const Light& L, const float* lds, unsigned v0, unsigned v1, unsigned v2, unsigned v3, const Affine& a, OutT o[C])
+{
+  const unsigned peak = (1u << L.bits) - 1u;
+  float r[3] = {lds[min(v0, peak)], lds[min(v1, peak)], lds[min(v2, peak)]};
+  gamut(L, r);
+  const float* enc = lds + (1 << L.bits);
+  o[0] = colour_out<OutT>(L, enc, r[0], a.scale[0], a.bias[0]);
+  o[1] = colour_out<OutT>(L, enc, r[1], a.scale[1], a.bias[1]);
+  o[2] = colour_out<OutT>(L, enc, r[2], a.scale[2], a.bias[2]);
+  if constexpr (C == 4) o[3] = moved<OutT>(v3, a.scale[3], a.bias[3]);
+}
+
+template <int BYTES> struct LoadWord { typedef uint32_t type; };
+template <> struct LoadWord<16> { typedef uint4 type; };
+template <> struct LoadWord<8> { typedef uint2 type; };
+
+// SB: bytes per input sample (1 / 2, little-endian), C: channels, CHW: one plane per channel, VEC: 16-byte accesses allowed (the
+// launcher has checked the alignment of both sides).  grid: x = groups of 64 pixel groups, y = groups of 4 rows; dynamic LDS: the tables.
+template <int SB, int C, typename OutT, bool CHW, bool VEC>
+__global__ __launch_bounds__(256) void k_light_tensor(const uint8_t* __restrict__ src, int src_stride, int w, int h, uint8_t* __restrict__ dst,
+                                                      long long row_pitch, long long plane_pitch, Affine a, Light L)
+{
+  extern __shared__ __attribute__((aligned(16))) float lds[];
+  typedef typename std::conditional<SB == 1, uint8_t, uint16_t>::type InT;
+  constexpr int P = 16 / (int)sizeof(OutT); // pixels per lane
+  constexpr int NB = P * C * SB;            // input bytes per lane
+  fill_tables(lds, L.lin, L.encode ? L.enc : nullptr, 1 << L.bits);
+  const int lane = threadIdx.x & 63, y = blockIdx.y * 4 + (threadIdx.x >> 6);
+  if (y >= h) return;
+  uint8_t* orow = dst + (long long)y * row_pitch;
+  if (!VEC) { // one pixel per lane and step: pixels lane, lane + 64, ... of the wave's 64 * P
+    const InT* irow = reinterpret_cast<const InT*>(src + (size_t)y * src_stride);
+#pragma unroll 1
+    for (int i = 0; i < P; i++) {
+      const int x = (blockIdx.x * P + i) * 64 + lane;
+      if (x >= w) break;
+      const InT* ip = irow + (size_t)x * C;
+      OutT o[C];
+      pixel<C, OutT>(L, lds, ip[0], ip[1], ip[2], C == 4 ? ip[C - 1] : 0u, a, o);
+#pragma unroll
+      for (int c = 0; c < C; c++) {
+        OutT* op = CHW ? reinterpret_cast<OutT*>(orow + (long long)c * plane_pitch) + x : reinterpret_cast<OutT*>(orow) + (size_t)x * C + c;
+        *op = o[c];
+      }
+    }
+    return;
+  }
+  const int x0 = (blockIdx.x * 64 + lane) * P;
+  if (x0 >= w) return;
+  const uint8_t* in = src + (size_t)y * src_stride + (size_t)x0 * (C * SB);
+  if (x0 + P <= w) {
+    typedef typename LoadWord<(NB % 16 == 0) ? 16 : (NB % 8 == 0) ? 8 : 4>::type LW;
+    constexpr int NL = NB / (int)sizeof(LW);
+    LW lw[NL];
+#pragma unroll
+    for (int k = 0; k < NL; k++) lw[k] = reinterpret_cast<const LW*>(in)[k];
+    InT smp[P * C];
+    __builtin_memcpy(smp, lw, NB);
+    OutT o[P * C]; // pixel-major: the row's own order
+#pragma unroll
+    for (int i = 0; i < P; i++) pixel<C, OutT>(L, lds, smp[i * C], smp[i * C + 1], smp[i * C + 2], C == 4 ? smp[i * C + C - 1] : 0u, a, &o[i * C]);
+    if (CHW) {
+#pragma unroll
+      for (int c = 0; c < C; c++) {
+        OutT oc[P];
+#pragma unroll
+        for (int i = 0; i < P; i++) oc[i] = o[i * C + c];
+        uint4 v;
+        __builtin_memcpy(&v, oc, 16);
+        *reinterpret_cast<uint4*>(orow + (long long)c * plane_pitch + (size_t)x0 * sizeof(OutT)) = v;
+      }
+    }
+    else {
+#pragma unroll
+      for (int k = 0; k < C; k++) { // P * C elements in a row: C stores of P elements
+        uint4 v;
+        __builtin_memcpy(&v, &o[k * P], 16);
+        reinterpret_cast<uint4*>(orow + (size_t)x0 * (C * sizeof(OutT)))[k] = v;
+      }
+    }
+    return;
+  }
+  const int n = w - x0 < P ? w - x0 : P; // the ragged last group: element by element
+  const InT* ip = reinterpret_cast<const InT*>(in);
+#pragma unroll 1
+  for (int i = 0; i < n; i++) {
+    OutT o[C];
+    pixel<C, OutT>(L, lds, ip[i * C], ip[i * C + 1], ip[i * C + 2], C == 4 ? ip[i * C + C - 1] : 0u, a, o);
+#pragma unroll
+    for (int c = 0; c < C; c++) {
+      OutT* op = CHW ? reinterpret_cast<OutT*>(orow + (long long)c * plane_pitch) + (x0 + i) : reinterpret_cast<OutT*>(orow) + (size_t)(x0 + i) * C + c;
+      *op = o[c];
+    }
+  }
+}
+
+// HM_VIEW_NEAREST: out pixel (j, k) is source pixel (j * n_w / ow, k * n_h / oh).  grid: x = groups of 64 columns, y = groups of 4 rows.
+template <typename InT, int C, typename OutT>
+__global__ __launch_bounds__(256) void k_light_nearest(const uint8_t* __restrict__ src, int src_stride, int n_w, int n_h, int ow, int oh, int chw,
+                                                       uint8_t* __restrict__ dst, long long row_pitch, long long plane_pitch, Affine a, Light L)
+{
+  extern __shared__ __attribute__((aligned(16))) float lds[];
+  fill_tables(lds, L.lin, L.encode ? L.enc : nullptr, 1 << L.bits);
+  const int j = blockIdx.x * 64 + (threadIdx.x & 63), k = blockIdx.y * 4 + (threadIdx.x >> 6);
+  if (j >= ow || k >= oh) return;
+  const int sx = j * n_w / ow, sy = k * n_h / oh;
+  const InT* in = reinterpret_cast<const InT*>(src + (size_t)sy * src_stride) + (size_t)sx * C;
+  OutT o[C];
+  pixel<C, OutT>(L, lds, in[0], in[1], in[2], C == 4 ? in[C - 1] : 0u, a, o);
+  uint8_t* orow = dst + (long long)k * row_pitch;
+#pragma unroll
+  for (int c = 0; c < C; c++) {
+    OutT* op = chw ? reinterpret_cast<OutT*>(orow + (long long)c * plane_pitch) + j : reinterpret_cast<OutT*>(orow) + (size_t)j * C + c;
+    *op = o[c];
+  }
+}
+
+// k_resample_h with lin[min(v, peak)] in place of (float)v on the colour channels.  grid: x = groups of 64 output columns, y = groups
+// of 4 source rows; src points at the crop's origin; dynamic LDS: lin.
+template <int SB, int C, bool CHW>
+__global__ __launch_bounds__(256) void k_light_h(const uint8_t* __restrict__ src, int src_stride, int n_h, int ow, const int32_t* __restrict__ first,
+                                                 const int32_t* __restrict__ count, const float* __restrict__ wts, float* __restrict__ tmp,
+                                                 long long pitch, long long plane, const float* __restrict__ lin, int bits)
+{
+  extern __shared__ __attribute__((aligned(16))) float lds[];
+  typedef typename std::conditional<SB == 1, uint8_t, uint16_t>::type InT;
+  fill_tables(lds, lin, nullptr, 1 << bits);
+  const unsigned peak = (1u << bits) - 1u;
+  const int j = blockIdx.x * 64 + (threadIdx.x & 63), y = blockIdx.y * 4 + (threadIdx.x >> 6);
+  if (j >= ow || y >= n_h) return;
+  const InT* in = reinterpret_cast<const InT*>(src + (size_t)y * src_stride) + (size_t)first[j] * C;
+  const int n = count[j];
+  float t[C];
+#pragma unroll
+  for (int c = 0; c < C; c++) t[c] = 0.0f;
+  for (int i = 0; i < n; i++) {
+    const float w = wts[(size_t)i * ow + j];
+#pragma unroll
+    for (int c = 0; c < C; c++) {
+      const unsigned v = in[i * C + c];
+      const float a = c < 3 ? lds[min(v, peak)] : (float)v;
+      t[c] = __fadd_rn(t[c], __fmul_rn(w, a));
+    }
+  }
+  float* o = tmp + (long long)y * pitch;
+#pragma unroll
+  for (int c = 0; c < C; c++) {
+    if (CHW) o[(long long)c * plane + j] = t[c];
+    else o[(size_t)j * C + c] = t[c];
+  }
+}
+
+// The vertical pass: a lane is ONE output pixel, a wave 64 consecutive pixels of one output row, so the taps are wave-uniform and
+// the reads of a CHW intermediate coalesce per plane (an HWC one: the wave reads 64 * C consecutive floats in C instructions).
+// grid: x = groups of 64 columns, y = groups of 4 output rows; dynamic LDS: enc when re-encoding.
+template <typename OutT, bool CHW, int C>
+__global__ __launch_bounds__(256) void k_light_v(const float* __restrict__ tmp, long long pitch, long long plane, int ow, int oh,
+                                                 const int32_t* __restrict__ first, const int32_t* __restrict__ count, const float* __restrict__ wts,
+                                                 uint8_t* __restrict__ dst, long long row_pitch, long long plane_pitch, Affine a, Light L)
+{
+  extern __shared__ __attribute__((aligned(16))) float lds[];
+  if (L.encode) fill_tables(lds, L.enc, nullptr, 1 << L.bits); // (uniform: the barrier inside is met by every thread or by none)
+  const int j = blockIdx.x * 64 + (threadIdx.x & 63), k = blockIdx.y * 4 + (threadIdx.x >> 6);
+  if (j >= ow || k >= oh) return;
+  const int y0 = first[k], n = count[k]; // (the same in every lane of the wave)
+  const float* col = tmp + (long long)y0 * pitch + (CHW ? (long long)j : (long long)j * C);
+  float acc[C];
+#pragma unroll
+  for (int c = 0; c < C; c++) acc[c] = 0.0f;
+  for (int i = 0; i < n; i++) {
+    const float w = wts[(size_t)i * oh + k];
+#pragma unroll
+    for (int c = 0; c < C; c++) acc[c] = __fadd_rn(acc[c], __fmul_rn(w, CHW ? col[(long long)c * plane] : col[c]));
+    col += pitch;
+  }
+  gamut(L, acc);
+  OutT o[C];
+#pragma unroll
+  for (int c = 0; c < 3; c++) o[c] = colour_out<OutT>(L, lds, acc[c], a.scale[c], a.bias[c]);
+  if constexpr (C == 4) o[3] = alpha_out<OutT>(acc[3], a.scale[3], a.bias[3]);
+  uint8_t* orow = dst + (long long)k * row_pitch;
+#pragma unroll
+  for (int c = 0; c < C; c++) {
+    OutT* op = CHW ? reinterpret_cast<OutT*>(orow + (long long)c * plane_pitch) + j : reinterpret_cast<OutT*>(orow) + (size_t)j * C + c;
+    *op = o[c];
+  }
+}
+
+// every instance the launchers below can pick (hm_debug_kernel_regs): 48 pointwise, 12 nearest, 8 horizontal, 16 vertical
+#define HM_LT_SET(SB, T) \
+  (const void*)k_light_tensor<SB, 3, T, true, true>, (const void*)k_light_tensor<SB, 3, T, true, false>, (const void*)k_light_tensor<SB, 3, T, false, true>, \
+  (const void*)k_light_tensor<SB, 3, T, false, false>, (const void*)k_light_tensor<SB, 4, T, true, true>, (const void*)k_light_tensor<SB, 4, T, true, false>, \
+  (const void*)k_light_tensor<SB, 4, T, false, true>, (const void*)k_light_tensor<SB, 4, T, false, false>
+#define HM_LN_SET(IN, T) (const void*)k_light_nearest<IN, 3, T>, (const void*)k_light_nearest<IN, 4, T>
+#define HM_LV_SET(T) (const void*)k_light_v<T, true, 3>, (const void*)k_light_v<T, true, 4>, (const void*)k_light_v<T, false, 3>, (const void*)k_light_v<T, false, 4>
+const void* const g_instances[] = {
+  HM_LT_SET(1, uint8_t), HM_LT_SET(1, __half), HM_LT_SET(1, float), HM_LT_SET(2, uint16_t), HM_LT_SET(2, __half), HM_LT_SET(2, float),
+  HM_LN_SET(uint8_t, uint8_t), HM_LN_SET(uint8_t, __half), HM_LN_SET(uint8_t, float), HM_LN_SET(uint16_t, uint16_t), HM_LN_SET(uint16_t, __half), HM_LN_SET(uint16_t, float),
+  (const void*)k_light_h<1, 3, true>, (const void*)k_light_h<1, 3, false>, (const void*)k_light_h<1, 4, true>, (const void*)k_light_h<1, 4, false>,
+  (const void*)k_light_h<2, 3, true>, (const void*)k_light_h<2, 3, false>, (const void*)k_light_h<2, 4, true>, (const void*)k_light_h<2, 4, false>,
+  HM_LV_SET(uint8_t), HM_LV_SET(uint16_t), HM_LV_SET(__half), HM_LV_SET(float),
+};
+#undef HM_LT_SET
+#undef HM_LN_SET
+#undef HM_LV_SET
+
+Affine affine_of(const float scale[4], const float bias[4])
+{
+  Affine a;
+  for (int c = 0; c < 4; c++) { a.scale[c] = scale[c]; a.bias[c] = bias[c]; }
+  return a;
+}
+
+Light light_of(const hm_light_args* la)
+{
+  Light L;
+  L.lin = la->lin; L.enc = la->enc; L.bits = la->bits; L.encode = la->encode; L.matrix = la->matrix;
+  for (int i = 0; i < 9; i++) L.m[i] = la->m[i];
+  return L;
+}
+
+// the tables a pointwise kernel holds in LDS
+size_t tables_bytes(const hm_light_args* la) { return ((size_t)4 << la->bits) * (la->encode ? 2 : 1); }
+
+template <int SB, int C, typename OutT, bool CHW>
+int launch_tensor(const hm_dest_plan* p, const hm_light_args* la, const uint8_t* src, int src_stride, int w, int rows, uint8_t* dst, const Affine& a, hipStream_t s)
+{
+  constexpr int P = 16 / (int)sizeof(OutT);
+  const bool vec = ((uintptr_t)src % 16) == 0 && (src_stride % 16) == 0 && ((uintptr_t)dst % 16) == 0 && (p->row_pitch % 16) == 0 &&
+                   (!CHW || (p->plane_pitch % 16) == 0);
+  const int groups = (w + P - 1) / P;
+  const dim3 grid((unsigned)((groups + 63) / 64), (unsigned)((rows + 3) / 4)), block(256);
+  const Light L = light_of(la);
+  if (vec)
+    hipLaunchKernelGGL((k_light_tensor<SB, C, OutT, CHW, true>), grid, block, tables_bytes(la), s, src, src_stride, w, rows, dst, (long long)p->row_pitch,
+                       (long long)p->plane_pitch, a, L);
+  else
+    hipLaunchKernelGGL((k_light_tensor<SB, C, OutT, CHW, false>), grid, block, tables_bytes(la), s, src, src_stride, w, rows, dst, (long long)p->row_pitch,
+                       (long long)p->plane_pitch, a, L);
+  return hm_check_hip(hipGetLastError(), "k_light_tensor launch");
+}
+
+template <int SB, int C>
+int launch_tensor_dtype(const hm_dest_plan* p, const hm_light_args* la, const uint8_t* src, int src_stride, int w, int rows, uint8_t* dst, const Affine& a, hipStream_t s)
+{
+  typedef typename std::conditional<SB == 1, uint8_t, uint16_t>::type IntT;
+  const bool chw = p->layout == HM_DEV_LAYOUT_CHW;
+  if (p->dtype == HM_DEV_F32) return chw ? launch_tensor<SB, C, float, true>(p, la, src, src_stride, w, rows, dst, a, s) : launch_tensor<SB, C, float, false>(p, la, src, src_stride, w, rows, dst, a, s);
+  if (p->dtype == HM_DEV_F16) return chw ? launch_tensor<SB, C, __half, true>(p, la, src, src_stride, w, rows, dst, a, s) : launch_tensor<SB, C, __half, false>(p, la, src, src_stride, w, rows, dst, a, s);
+  if (p->dtype == (SB == 1 ? HM_DEV_U8 : HM_DEV_U16))
+    return chw ? launch_tensor<SB, C, IntT, true>(p, la, src, src_stride, w, rows, dst, a, s) : launch_tensor<SB, C, IntT, false>(p, la, src, src_stride, w, rows, dst, a, s);
+  return hm_fail(HM_ERR_INTERNAL, "k_light_tensor: no kernel for dtype %d on %d-byte samples", p->dtype, SB);
+}
+
+template <typename InT, typename OutT>
+void launch_nearest(const hm_dest_plan* p, const hm_light_args* la, const uint8_t* src, int src_stride, int n_w, int n_h, int ow, int oh, uint8_t* dst, const Affine& a,
+                    hipStream_t s)
+{
+  const dim3 grid((unsigned)((ow + 63) / 64), (unsigned)((oh + 3) / 4)), block(256);
+  const int chw = p->layout == HM_DEV_LAYOUT_CHW ? 1 : 0;
+  const Light L = light_of(la);
+  if (p->channels == 3)
+    hipLaunchKernelGGL((k_light_nearest<InT, 3, OutT>), grid, block, tables_bytes(la), s, src, src_stride, n_w, n_h, ow, oh, chw, dst, (long long)p->row_pitch,
+                       (long long)p->plane_pitch, a, L);
+  else
+    hipLaunchKernelGGL((k_light_nearest<InT, 4, OutT>), grid, block, tables_bytes(la), s, src, src_stride, n_w, n_h, ow, oh, chw, dst, (long long)p->row_pitch,
+                       (long long)p->plane_pitch, a, L);
+}
+
+template <int SB, int C>
+void launch_h(bool chw, const hm_resample_args* r, const hm_light_args* la, hipStream_t s)
+{
+  const dim3 grid((unsigned)((r->ow + 63) / 64), (unsigned)((r->n_h + 3) / 4)), block(256);
+  const uint8_t* src = (const uint8_t*)r->src;
+  const size_t lds = (size_t)4 << la->bits;
+  if (chw)
+    hipLaunchKernelGGL((k_light_h<SB, C, true>), grid, block, lds, s, src, r->src_stride, r->n_h, r->ow, r->ax.first, r->ax.count, r->ax.weights, r->tmp,
+                       (long long)r->tmp_pitch, (long long)r->tmp_plane, la->lin, la->bits);
+  else
+    hipLaunchKernelGGL((k_light_h<SB, C, false>), grid, block, lds, s, src, r->src_stride, r->n_h, r->ow, r->ax.first, r->ax.count, r->ax.weights, r->tmp,
+                       (long long)r->tmp_pitch, (long long)r->tmp_plane, la->lin, la->bits);
+}
+
+template <typename OutT>
+void launch_v(const hm_dest_plan* p, const hm_resample_args* r, const hm_light_args* la, uint8_t* dst, const Affine& a, hipStream_t s)
+{
+  const dim3 grid((unsigned)((r->ow + 63) / 64), (unsigned)((r->oh + 3) / 4)), block(256);
+  const size_t lds = la->encode ? (size_t)4 << la->bits : 0;
+  const Light L = light_of(la);
+  const bool chw = p->layout == HM_DEV_LAYOUT_CHW;
+#define HM_LV_GO(CHW_, C_) \
+  hipLaunchKernelGGL((k_light_v<OutT, CHW_, C_>), grid, block, lds, s, (const float*)r->tmp, (long long)r->tmp_pitch, (long long)r->tmp_plane, r->ow, r->oh, \
+                     r->ay.first, r->ay.count, r->ay.weights, dst, (long long)p->row_pitch, (long long)p->plane_pitch, a, L)
+  if (chw) { if (p->channels == 3) HM_LV_GO(true, 3); else HM_LV_GO(true, 4); }
+  else { if (p->channels == 3) HM_LV_GO(false, 3); else HM_LV_GO(false, 4); }
+#undef HM_LV_GO
+}
+
+int check_args(const hm_dest_plan* p, const hm_light_args* la)
+{
+  if (!la->lin || (la->encode && !la->enc) || la->bits < 8 || la->bits > 12) return hm_fail(HM_ERR_INTERNAL, "k_light: tables of %d bits", la->bits);
+  if (p->channels != 3 && p->channels != 4) return hm_fail(HM_ERR_INTERNAL, "k_light: %d channels", p->channels);
+  const bool integer = p->dtype == HM_DEV_U8 || p->dtype == HM_DEV_U16;
+  if (integer && (!la->encode || p->dtype != (p->sample_bytes == 1 ? HM_DEV_U8 : HM_DEV_U16)))
+    return hm_fail(HM_ERR_INTERNAL, "k_light: integer dtype %d on %d-byte samples, %s", p->dtype, p->sample_bytes, la->encode ? "re-encoded" : "linear");
+  return HM_OK;
+}
+
+} // namespace
+
+extern "C" const void* hm_light_kernel_of(int index) // (test_hooks.cpp: hm_debug_kernel_regs)
+{
+  return index >= 0 && index < (int)(sizeof(g_instances) / sizeof(g_instances[0])) ? g_instances[index] : nullptr;
+}
+
+// rows [0, rows) of `src` through the light step to `dst` = the destination's first element; asynchronous on `s`
+extern "C" int hm_launch_light_tensor(const hm_dest_plan* p, const hm_light_args* la, const void* src, int src_stride, int w, int rows, void* dst,
+                                      const float scale[4], const float bias[4], hipStream_t s)
+{
+  if (w <= 0 || rows <= 0) return HM_OK;
+  const int rc = check_args(p, la);
+  if (rc) return rc;
+  const Affine a = affine_of(scale, bias);
+  const uint8_t* in = (const uint8_t*)src;
+  uint8_t* out = (uint8_t*)dst;
+  if (p->sample_bytes == 1) return p->channels == 3 ? launch_tensor_dtype<1, 3>(p, la, in, src_stride, w, rows, out, a, s) : launch_tensor_dtype<1, 4>(p, la, in, src_stride, w, rows, out, a, s);
+  return p->channels == 3 ? launch_tensor_dtype<2, 3>(p, la, in, src_stride, w, rows, out, a, s) : launch_tensor_dtype<2, 4>(p, la, in, src_stride, w, rows, out, a, s);
+}
+
+extern "C" int hm_launch_light_nearest(const hm_dest_plan* p, const hm_light_args* la, const void* src, int src_stride, int n_w, int n_h, int ow, int oh, void* dst,
+                                       const float scale[4], const float bias[4], hipStream_t s)
+{
+  if (ow <= 0 || oh <= 0) return HM_OK;
+  const int rc = check_args(p, la);
+  if (rc) return rc;
+  const Affine a = affine_of(scale, bias);
+  const uint8_t* in = (const uint8_t*)src;
+  uint8_t* out = (uint8_t*)dst;
+  const bool wide = p->sample_bytes == 2;
+  if (p->dtype == HM_DEV_U8) launch_nearest<uint8_t, uint8_t>(p, la, in, src_stride, n_w, n_h, ow, oh, out, a, s);
+  else if (p->dtype == HM_DEV_U16) launch_nearest<uint16_t, uint16_t>(p, la, in, src_stride, n_w, n_h, ow, oh, out, a, s);
+  else if (p->dtype == HM_DEV_F16) { if (wide) launch_nearest<uint16_t, __half>(p, la, in, src_stride, n_w, n_h, ow, oh, out, a, s); else launch_nearest<uint8_t, __half>(p, la, in, src_stride, n_w, n_h, ow, oh, out, a, s); }
+  else { if (wide) launch_nearest<uint16_t, float>(p, la, in, src_stride, n_w, n_h, ow, oh, out, a, s); else launch_nearest<uint8_t, float>(p, la, in, src_stride, n_w, n_h, ow, oh, out, a, s); }
+  return hm_check_hip(hipGetLastError(), "k_light_nearest launch");
+}
+
+// both passes of a resampled view under the light step; the intermediate is hm_launch_resample's
+extern "C" int hm_launch_light_resample(const hm_dest_plan* p, const hm_light_args* la, const hm_resample_args* r, void* dst, const float scale[4],
+                                        const float bias[4], hipStream_t s)
+{
+  if (r->ow <= 0 || r->oh <= 0 || r->n_w <= 0 || r->n_h <= 0) return HM_OK;
+  int rc = check_args(p, la);
+  if (rc) return rc;
+  const bool chw = p->layout == HM_DEV_LAYOUT_CHW;
+  if (r->sample_bytes == 1) { if (r->channels == 3) launch_h<1, 3>(chw, r, la, s); else launch_h<1, 4>(chw, r, la, s); }
+  else { if (r->channels == 3) launch_h<2, 3>(chw, r, la, s); else launch_h<2, 4>(chw, r, la, s); }
+  if ((rc = hm_check_hip(hipGetLastError(), "k_light_h launch"))) return rc;
+  const Affine a = affine_of(scale, bias);
+  uint8_t* out = (uint8_t*)dst;
+  switch (p->dtype) {
+    case HM_DEV_U8: launch_v<uint8_t>(p, r, la, out, a, s); break;
+    case HM_DEV_U16: launch_v<uint16_t>(p, r, la, out, a, s); break;
+    case HM_DEV_F16: launch_v<__half>(p, r, la, out, a, s); break;
+    case HM_DEV_F32: launch_v<float>(p, r, la, out, a, s); break;
+    default: return hm_fail(HM_ERR_INTERNAL, "k_light_v: no kernel for dtype %d", p->dtype);
+  }
+  return hm_check_hip(hipGetLastError(), "k_light_v launch");
+}

@@ -183,7 +183,7 @@ void hm_pipeline_destroy(hm_pipeline* p)
 }
 
 static int submit(hm_pipeline* p, const uint8_t* heif, size_t size, uint32_t item_id, uint64_t tag, const hm_device_dest* dest, const hm_device_view* view = nullptr,
-                  const hm_device_planes* planes = nullptr);
+                  const hm_device_planes* planes = nullptr, const hm_device_light* light = nullptr);
 
 int hm_pipeline_submit(hm_pipeline* p, const uint8_t* heif, size_t size, uint32_t item_id, uint64_t tag)
 {
@@ -204,6 +204,13 @@ int hm_pipeline_submit_to_device_view(hm_pipeline* p, const uint8_t* heif, size_
   return submit(p, heif, size, item_id, tag, dest, view);
 }
 
+int hm_pipeline_submit_to_device_light(hm_pipeline* p, const uint8_t* heif, size_t size, uint32_t item_id, uint64_t tag, const hm_device_view* view,
+                                       const hm_device_light* light, const hm_device_dest* dest)
+{
+  if (!p || !heif || !light || !dest) return hm_fail(HM_ERR_INVALID_ARG, "null argument");
+  return submit(p, heif, size, item_id, tag, dest, view, nullptr, light);
+}
+
 int hm_pipeline_submit_to_device_planes(hm_pipeline* p, const uint8_t* heif, size_t size, uint32_t item_id, uint64_t tag, const hm_device_planes* planes)
 {
   if (!p || !heif || !planes) return hm_fail(HM_ERR_INVALID_ARG, "null argument");
@@ -220,8 +227,9 @@ int hm_pipeline_submit_to_device_planes_view(hm_pipeline* p, const uint8_t* heif
 // dest (may be NULL): the image's pixels go to caller-owned device memory of the pipeline's device; view (may be NULL, with dest or planes):
 // a rectangle of them, resampled - job_plan then queues only the coded pictures the crop touches
 // planes (may be NULL, without dest): the planes of the pipeline's planar out_format go to caller-owned device memory
+// light (may be NULL, with dest): the light step in the write of the destination
 static int submit(hm_pipeline* p, const uint8_t* heif, size_t size, uint32_t item_id, uint64_t tag, const hm_device_dest* dest, const hm_device_view* view,
-                  const hm_device_planes* planes)
+                  const hm_device_planes* planes, const hm_device_light* light)
 {
   hipStream_t stream = nullptr;
   {
@@ -254,10 +262,11 @@ static int submit(hm_pipeline* p, const uint8_t* heif, size_t size, uint32_t ite
       int prev = -1;
       hipGetDevice(&prev);
       hipSetDevice(p->cfg.device); // (the pointer must belong to the device the crew works on)
-      rc = check_device_request(im->file, im->job.id, &im->job.params, dest, view);
+      rc = check_device_request(im->file, im->job.id, &im->job.params, dest, view, light);
       if (prev >= 0) hipSetDevice(prev);
       im->job.dest = *dest; im->job.has_dest = true;
       if (view) { im->job.view = *view; im->job.has_view = true; }
+      if (light) { im->job.light = *light; im->job.has_light = true; }
     }
     if (planes) { // refused here, before anything is queued: no plane is written
       int prev = -1;

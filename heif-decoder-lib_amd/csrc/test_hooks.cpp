@@ -23,6 +23,7 @@ extern "C" const void* hm_resample_staged_kernel_of(int index);                 
 extern "C" const void* hm_resample_batch_kernel_of(int index);                              // ... the batched forms of all three passes
 extern "C" const void* hm_planes_view_kernel_of(int index);                                 // planes_view.hip: NULL behind the last instance
 extern "C" const void* hm_overlay_kernel_of(int index);                                     // overlay.hip: NULL behind the last instance
+extern "C" const void* hm_light_kernel_of(int index);                                       // light.hip: NULL behind the last instance
 
 extern "C" {
 
@@ -53,6 +54,7 @@ __attribute__((visibility("default"))) int hm_debug_kernel_regs(int which, int a
   else if (which == 6) fn = hm_resample_batch_kernel_of(a); // (k_resample_h_batch, k_resample_h_staged_batch, k_resample_v_batch)
   else if (which == 7) fn = hm_planes_view_kernel_of(a); // (k_planes_resample_h, k_planes_resample_v, k_planes_view_nearest)
   else if (which == 8) fn = hm_overlay_kernel_of(a); // (k_overlay: RGB24, RGBA32, planes)
+  else if (which == 9) fn = hm_light_kernel_of(a); // (k_light_tensor, k_light_nearest, k_light_h, k_light_v; out[1] counts scratch, not LDS)
   hipFuncAttributes fa;
   if (!fn || !out || hipFuncGetAttributes(&fa, fn) != hipSuccess) return -1;
   out[0] = fa.numRegs;

@@ -8,7 +8,9 @@ Layouts: "chw" (one plane per channel) and "hwc" (the target's own interleaving)
 the target's own sample type: 8-bit "rgb" / "rgba", 16-bit "rrggbb_le" / "rrggbbaa_le" ...), torch.float16, torch.float32;
 floats are sample * scale[c] + bias[c], rounded after each step.  crop=(x, y, w, h) and size=(w, h) ask for a rectangle of the image,
 resampled (filter "triangle": antialiased bilinear, "bicubic", "lanczos3" or "nearest") in the step that writes the tensor; of a grid only the tiles the
-rectangle touches are decoded.  What the library refuses raises capi.HmError.
+rectangle touches are decoded.  light=True asks for linear light (the image's own transfer function undone by a table, floats only);
+light=dict(to_transfer="srgb", to_primaries="bt709", gain=1.0, from_transfer=..., from_primaries=...) re-encodes or changes the
+primaries - a resize under light= averages light, not code values.  What the library refuses raises capi.HmError.
 
 Planar YCbCr stays planar: decode_to_planes / decode_sequence_to_planes / decode_batch_to_planes return (Y, Cb, Cr[, A]) ("planar":
 I420 and its kin) or (Y, CbCr[, A]) ("semiplanar": NV12, P010 with msb_aligned=True) as coded or at the chroma format asked for.
@@ -112,6 +114,37 @@ def _view_of(crop, size, filter, w, h):
     return v, w, h
 
 
+TRANSFERS = {"linear": 8, "srgb": 13, "bt709": 1, "pq": 16, "hlg": 18}
+PRIMARIES = {"bt709": 1, "srgb": 1, "bt2020": 9, "p3": 12}
+
+
+def _light_of(light):
+    """hm_device_light (or None) of the light= argument: True, or a dict of to_transfer / to_primaries / gain / from_transfer /
+    from_primaries with H.273 codes or names"""
+    if light is None or light is False:
+        return None
+    if light is True:
+        light = {}
+    if not isinstance(light, dict):
+        raise ValueError(f"light {light!r}: True or a dict")
+    keys = {"to_transfer", "to_primaries", "gain", "from_transfer", "from_primaries"}
+    if set(light) - keys:
+        raise ValueError(f"light: unknown keys {sorted(set(light) - keys)}, known are {sorted(keys)}")
+
+    def code(key, names, default):
+        v = light.get(key, default)
+        if isinstance(v, str):
+            if v.lower() not in names:
+                raise ValueError(f"light[{key!r}] = {v!r}: one of {sorted(names)} or an H.273 code")
+            return names[v.lower()]
+        return int(v)
+    d = capi.DeviceLight()
+    d.from_transfer, d.from_primaries = code("from_transfer", TRANSFERS, 0), code("from_primaries", PRIMARIES, 0)
+    d.to_transfer, d.to_primaries = code("to_transfer", TRANSFERS, capi.HM_LIGHT_LINEAR), code("to_primaries", PRIMARIES, 0)
+    d.gain = float(light.get("gain", 1.0))
+    return d
+
+
 def _default_threads():
     return max(1, min(16, os.cpu_count() or 1))
 
@@ -135,12 +168,13 @@ class _File:
 
 
 def decode_to_tensor(data, item_id=0, out_format="rgb", layout="chw", dtype=None, scale=None, bias=None, out=None, stream=None,
-                     host_threads=None, crop=None, size=None, filter="triangle"):
+                     host_threads=None, crop=None, size=None, filter="triangle", light=None):
     """Decode one image of a HEIF file (bytes; item_id 0 = the primary item) into a CUDA tensor: C x H x W ("chw") or H x W x C
     ("hwc").  dtype defaults to torch.float32 (out's dtype when out is given).  out: a CUDA tensor of that shape to write into;
     its row (and plane) stride is honoured, bytes between rows are left alone.  stream: a torch.cuda.Stream or a raw stream
     handle (default: the current stream).  crop: (x, y, w, h), a rectangle of the image; size: (w, h), what it is resampled to
-    (H and W of the tensor are then the size's, or the crop's); filter: "triangle", "bicubic", "lanczos3" or "nearest".  Returns when the pixels are in place."""
+    (H and W of the tensor are then the size's, or the crop's); filter: "triangle", "bicubic", "lanczos3" or "nearest".  light: True (linear
+    light) or a dict (see the module's text): the light step in the write of the tensor.  Returns when the pixels are in place."""
     import torch
     L = capi.image_lib()
     fmt, lay = _out_format(out_format), _layout(layout)
@@ -151,6 +185,7 @@ def decode_to_tensor(data, item_id=0, out_format="rgb", layout="chw", dtype=None
     try:
         iid, w, h = f.size(item_id)
         view, w, h = _view_of(crop, size, filter, w, h)
+        lit = _light_of(light)
         shape = _shape(lay, c, h, w)
         if out is None:
             out = torch.empty(shape, dtype=dtype, device="cuda")
@@ -166,7 +201,10 @@ def decode_to_tensor(data, item_id=0, out_format="rgb", layout="chw", dtype=None
         prm = capi.DecodeParams(fmt, host_threads or _default_threads(), 0, 0, handle or None, None, 0, 0, 0, 0)
         d = capi.Decoded()
         with torch.cuda.device(out.device):
-            if view is None:
+            if lit is not None:
+                capi.check_image(L.hm_decode_item_to_device_light(f.h, iid, C.byref(prm), C.byref(view) if view is not None else None, C.byref(lit), C.byref(dest),
+                                                                  C.byref(d)))
+            elif view is None:
                 capi.check_image(L.hm_decode_item_to_device(f.h, iid, C.byref(prm), C.byref(dest), C.byref(d)))
             else:
                 capi.check_image(L.hm_decode_item_to_device_view(f.h, iid, C.byref(prm), C.byref(view), C.byref(dest), C.byref(d)))
@@ -179,12 +217,12 @@ def decode_to_tensor(data, item_id=0, out_format="rgb", layout="chw", dtype=None
 
 
 def decode_batch_to_tensor(files, item_id=0, out_format="rgb", layout="chw", dtype=None, scale=None, bias=None, out=None,
-                           host_threads=None, max_in_flight=4, size=None, crops=None, filter="triangle"):
+                           host_threads=None, max_in_flight=4, size=None, crops=None, filter="triangle", light=None):
     """Decode N equally sized HEIF files through ONE hm_pipeline (the entropy decode of one file runs under the kernels of
     another) into one N x C x H x W ("chw") or N x H x W x C ("hwc") CUDA tensor, each image into its slice.  files: bytes
     objects or paths.  A file of another size than the first (or than `out`) raises ValueError naming it.
     size: (w, h) - files of different sizes are accepted then, each resampled into its slice; crops: one (x, y, w, h) or None per
-    file, the rectangle of that file that is resampled (needs size)."""
+    file, the rectangle of that file that is resampled (needs size).  light: as decode_to_tensor, the same step for every file."""
     import torch
     L = capi.image_lib()
     fmt, lay = _out_format(out_format), _layout(layout)
@@ -192,6 +230,7 @@ def decode_batch_to_tensor(files, item_id=0, out_format="rgb", layout="chw", dty
         dtype = out.dtype if out is not None else torch.float32
     code, c = _dtype_code(dtype), _channels(fmt)
     sc, bi = _per_channel(scale, 1.0), _per_channel(bias, 0.0)
+    lit = _light_of(light)
     names, datas = [], []
     for k, entry in enumerate(files):
         if isinstance(entry, (bytes, bytearray, memoryview)):
@@ -252,7 +291,10 @@ def decode_batch_to_tensor(files, item_id=0, out_format="rgb", layout="chw", dty
             for k, data in enumerate(datas):
                 dest = _dest_of(out[k], lay, code, c, sc, bi)
                 while True:
-                    if views[k] is None:
+                    if lit is not None:
+                        rc = L.hm_pipeline_submit_to_device_light(pipe, data, len(data), ids[k], k, C.byref(views[k]) if views[k] is not None else None,
+                                                                  C.byref(lit), C.byref(dest))
+                    elif views[k] is None:
                         rc = L.hm_pipeline_submit_to_device(pipe, data, len(data), ids[k], k, C.byref(dest))
                     else:
                         rc = L.hm_pipeline_submit_to_device_view(pipe, data, len(data), ids[k], k, C.byref(views[k]), C.byref(dest))
@@ -287,12 +329,13 @@ def _frame_ids(frames, n_frames):
 
 
 def decode_sequence_to_tensor(data, frames=None, out_format="rgb", layout="chw", dtype=None, scale=None, bias=None, out=None, stream=None,
-                              host_threads=None, crop=None, size=None, filter="triangle"):
+                              host_threads=None, crop=None, size=None, filter="triangle", light=None):
     """Decode frames of an image sequence (bytes of a file with a 'moov' track) into one CUDA tensor, T x C x H x W ("chw") or
     T x H x W x C ("hwc"), in ONE device batch (hm_decode_frames_to_device_view).  frames: None (all), a range or a list of 1-based
     frame IDs, in any order, repeats allowed - range(1, n + 1, 4) is every fourth frame.  crop / size / filter: the same rectangle
     of every frame, resampled, as in decode_to_tensor; without them every frame must have the size of the first.  out: a CUDA
-    tensor of that shape; the row and plane strides of each of its slices are honoured.  Returns when the pixels are in place."""
+    tensor of that shape; the row and plane strides of each of its slices are honoured.  light: as decode_to_tensor, the same step for
+    every frame (hm_decode_frames_to_device_light).  Returns when the pixels are in place."""
     import torch
     L = capi.image_lib()
     fmt, lay = _out_format(out_format), _layout(layout)
@@ -331,9 +374,14 @@ def decode_sequence_to_tensor(data, frames=None, out_format="rgb", layout="chw",
         prm = capi.DecodeParams(fmt, host_threads or _default_threads(), 0, 0, handle or None, None, 0, 0, 0, 0)
         res = (capi.Decoded * n)()
         failed = C.c_int32(-1)
+        lit = _light_of(light)
         with torch.cuda.device(out.device):
-            rc = L.hm_decode_frames_to_device_view(f.h, (C.c_uint32 * n)(*ids), n, C.byref(prm), C.byref(view) if view is not None else None, dests, res,
-                                                   C.byref(failed))
+            if lit is not None:
+                rc = L.hm_decode_frames_to_device_light(f.h, (C.c_uint32 * n)(*ids), n, C.byref(prm), C.byref(view) if view is not None else None, C.byref(lit),
+                                                        dests, res, C.byref(failed))
+            else:
+                rc = L.hm_decode_frames_to_device_view(f.h, (C.c_uint32 * n)(*ids), n, C.byref(prm), C.byref(view) if view is not None else None, dests, res,
+                                                       C.byref(failed))
         if rc < 0:
             detail = f"{L.hm_status_string(rc).decode()}: {L.hm_last_error().decode()}"
             k = failed.value

@@ -683,6 +683,72 @@ HM_API int hm_plan_overlay(const hm_file* f, uint32_t id, const hm_decode_params
 HM_API int hm_view_filter_taps(int n_in, int n_out, int filter, int j, int32_t* first, float* weights, int cap);
 
 /* ------------------------------------------------------------------------- */
+/* Light: linear-light output, a change of primaries, views that average light */
+/* ------------------------------------------------------------------------- */
+
+/* The entry points above hand out the transfer-encoded code values of the colour stage.  A light step in the write of the
+ * destination turns them into linear light, optionally changes the primaries, and stores linear floats or re-encodes; a view
+ * then resamples LIGHT, not code values (a one-pixel black / white checkerboard in sRGB halved with HM_VIEW_TRIANGLE is code 188,
+ * not 128).  No transcendental function runs on the device: the transfer functions are tables built on the host in double, the
+ * re-encoding is a search in a threshold table, and every float32 operation is rounded on its own - a float32 restatement on the
+ * host is exact.
+ * Transfer codes (H.273), in both directions: 1, 6, 14, 15 the BT.709 curve with the exact constants alpha = 1.09929682680944,
+ * beta = 0.018053968510807 (E' < 4.5 beta: E' / 4.5, else ((E' + alpha - 1) / alpha)^(1 / 0.45); the rounded 1.099 / 0.081 pair is
+ * not monotone across the knee at 12 bits);  4 gamma 2.2;  5 gamma 2.8;  8 linear;  13 sRGB (IEC 61966-2-1: E' <= 0.04045:
+ * E' / 12.92, else ((E' + 0.055) / 1.055)^2.4);  16 PQ, the ST 2084 EOTF, 1.0 = 10000 cd/m2;  18 HLG, the INVERSE OETF of BT.2100
+ * only: scene light, no OOTF is applied (E' <= 0.5: E'^2 / 3, else (exp((E' - c) / a) + b) / 12).
+ * Primaries: 1, 5, 6, 7, 9, 12 - all with a D65 white; no chromatic adaptation.  Any other code: HM_ERR_UNSUPPORTED.
+ *   bits = the target's sample depth: 8 for HM_OUT_RGB / _RGBA, hm_decoded.bit_depth for the _LE 16-bit targets (at most 12: both
+ *   tables sit in the kernels' local memory; deeper: HM_ERR_UNSUPPORTED);  peak = (1 << bits) - 1;  F_t = the code-to-light function
+ *   of transfer t on [0, 1];  g = (double)gain.
+ *   Tables, in double with the C library's pow / exp / log:  lin[c] = (float)(g * F_from(c / peak)), c = 0 .. peak;
+ *   enc[c] = (float)(g * F_to((c - 0.5) / peak)), c = 1 .. peak.
+ *   Colour channels: a source sample v becomes a = lin[min(v, peak)].  Under a view a replaces (float)v in the sums stated under
+ *   "Views" (same tap tables, horizontal first, tap 0 first, __fmul_rn / __fadd_rn), giving r; without a view, with the crop alone
+ *   or HM_VIEW_NEAREST r = a of the sample that is moved.  The alpha channel is not light: a = (float)v, finished as without a light
+ *   step (no premultiplication).
+ *   Gamut: when to_primaries is non-zero and differs from the source's, per output pixel, after the resampling:
+ *   R' = fadd(fadd(fmul(m0, R), fmul(m1, G)), fmul(m2, B)), G' and B' with m3 .. m5 and m6 .. m8; m = hm_light_matrix's, derived in
+ *   double from the H.273 chromaticities as (to -> XYZ)^-1 (from -> XYZ), then rounded to float32.
+ *   Finish: HM_LIGHT_LINEAR stores fadd(fmul(r, scale[c]), bias[c]), HM_DEV_F16 through __float2half_rn; integer dtypes are refused.
+ *   Otherwise code = |{c in 1 .. peak : enc[c] <= r}| - negative values and overshoot clamp to 0 and peak by themselves -; an integer
+ *   dtype (the target's own) stores code, a float dtype fadd(fmul((float)code, scale[c]), bias[c]).  With to_transfer ==
+ *   from_transfer, no view and no matrix the codes are the source's: enc[c] <= lin[c] < enc[c + 1] holds for every table.
+ * Refused before any work is queued, the destination unwritten: reserved != 0, a gain that is not finite or not above 0,
+ * HM_LIGHT_LINEAR with an integer dtype, a _BE target (all HM_ERR_INVALID_ARG), an unknown or unsupported code
+ * (HM_ERR_UNSUPPORTED), and everything the view and the destination checks refuse.  What depends on the image's own profile or
+ * depth (from_* == 0) is refused before a byte of the destination is written.  Planar targets stay refused: light is an RGB notion. */
+enum { HM_LIGHT_LINEAR = 8 };              /* H.273 transfer code 8 */
+typedef struct hm_device_light {
+  int32_t from_transfer, from_primaries;   /* H.273 codes; 0 = the image's own: what this call's hm_decoded reports
+                                              (has_nclx == 0 or code 2: transfer 13, primaries 1; an ICC profile is not read) */
+  int32_t to_transfer;                     /* HM_LIGHT_LINEAR: linear light, float dtypes only; another supported code: re-encoded */
+  int32_t to_primaries;                    /* 0 = keep the source's */
+  float   gain;                            /* finite, > 0: multiplies linear light (PQ: 1.0 = 10000 cd/m2) */
+  int32_t reserved[3];                     /* 0 */
+} hm_device_light;
+/* hm_decode_item_to_device[_view] with a light step; view NULL: the whole image.  The item is decoded as one job (of a grid under
+ * a view: the tiles hm_plan_view names). */
+HM_API int hm_decode_item_to_device_light(const hm_file* f, uint32_t id, const hm_decode_params* params, const hm_device_view* view,
+                                          const hm_device_light* light, const hm_device_dest* dest, hm_decoded* out);
+/* hm_decode_frames_to_device_view with a light step (view may be NULL): one decode batch; the write is one launch per frame and pass */
+HM_API int hm_decode_frames_to_device_light(const hm_file* f, const uint32_t* frames, int32_t count, const hm_decode_params* params,
+                                            const hm_device_view* view, const hm_device_light* light, const hm_device_dest* dests, hm_decoded* out,
+                                            int32_t* failed_frame);
+/* the pipeline form (view may be NULL) */
+HM_API int hm_pipeline_submit_to_device_light(hm_pipeline* p, const uint8_t* heif, size_t size, uint32_t item_id, uint64_t tag,
+                                              const hm_device_view* view, const hm_device_light* light, const hm_device_dest* dest);
+/* The step on its own, on interleaved pixels of `bits` bits that are on the device already (as hm_to_tensor / hm_resample_to_tensor;
+ * view may be NULL).  from_transfer and from_primaries must be explicit.  Asynchronous on `stream`. */
+HM_API int hm_light_to_tensor(int out_format, int bits, int src_w, int src_h, const void* d_src, int src_stride, const hm_device_view* view,
+                              const hm_device_light* light, const hm_device_dest* dest, void* stream);
+/* Host arithmetic, no device: the 1 << bits entries the kernels use - encode == 0: lin, else enc (entry 0 is 0 and is never looked
+ * at).  bits 8 .. 12.  Returns the count, or a negative status. */
+HM_API int hm_light_table(int transfer, int bits, float gain, int encode, float* out);
+/* Host arithmetic, no device: the row-major float32 matrix from one set of primaries to another (the identity, exactly, for equal codes) */
+HM_API int hm_light_matrix(int from_primaries, int to_primaries, float m[9]);
+
+/* ------------------------------------------------------------------------- */
 /* Planar views: a rectangle of the image, at a size of the caller's choice, into I420 / NV12 / P010 planes */
 /* ------------------------------------------------------------------------- */
 
