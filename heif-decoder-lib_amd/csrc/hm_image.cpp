@@ -36,6 +36,46 @@ int alloc_plane(DevPlane& p, int w, int h, int bps)
   return p.mem.alloc(plane_bytes(p));
 }
 
+int require_device()
+{
+  int n_dev = 0;
+  if (hipGetDeviceCount(&n_dev) != hipSuccess || n_dev == 0) { (void)hipGetLastError(); return hm_fail(HM_ERR_NO_DEVICE, "no HIP device available"); }
+  return HM_OK;
+}
+
+// a device plane of stride x rows (its padding included) into pinned host memory of its own, queued on `s`
+int plane_to_host(const void* src, int stride, int rows, hipStream_t s, uint8_t** host, int32_t* host_stride)
+{
+  const size_t sz = (size_t)stride * mem_rows(rows);
+  *host = (uint8_t*)hm_pool_pinned_alloc(sz);
+  if (!*host) return hm_fail(HM_ERR_NOMEM, "out of memory");
+  *host_stride = stride;
+  return hm_check_hip(hipMemcpyAsync(*host, src, sz, hipMemcpyDeviceToHost, s), "D2H");
+}
+
+// The colour chain's request for a w x h picture of (bd, chroma) with profile `native`: has_nclx is the caller's to say (a grid
+// canvas carries none).  P: the planes whose strides the chain reads - NULL: the packed rule of planes that are not allocated yet.
+// obpp: bytes per pixel of an interleaved target (out_stride), 0 for a planar one; planar_8bit: convert_hdr_to_8bit travels in the
+// planar out_format as HM_OUT_YCBCR_8BIT.  has_alpha stays 0.
+hm_colour_desc colour_desc(const hm_decode_params* params, int w, int h, int bd, int chroma, const hm::NclxProfile& native, int has_nclx, const DevPlane* P, int obpp,
+                           bool planar_8bit = false)
+{
+  hm_colour_desc cd;
+  std::memset(&cd, 0, sizeof(cd));
+  cd.width = w; cd.height = h; cd.bit_depth = bd; cd.chroma = chroma;
+  cd.has_nclx = has_nclx; cd.matrix = native.matrix; cd.primaries = native.primaries; cd.full_range = native.full_range;
+  cd.out_format = params->out_format | (planar_8bit && params->convert_hdr_to_8bit ? HM_OUT_YCBCR_8BIT : 0);
+  cd.chroma_upsampling = params->chroma_upsampling;
+  if (P) { cd.y_stride = P[0].stride; cd.cb_stride = P[1].stride; cd.cr_stride = P[2].stride; }
+  else {
+    const int bps = bd > 8 ? 2 : 1;
+    cd.y_stride = hm_plane_stride(w, bps);
+    cd.cb_stride = cd.cr_stride = chroma ? hm_plane_stride(chroma == 3 ? w : (w + 1) / 2, bps) : 0;
+  }
+  if (obpp > 0) cd.out_stride = hm_plane_stride(w, obpp);
+  return cd;
+}
+
 // Transformative properties of the item, applied to the decoded YCbCr planes in association order
 // (context.cc:1957-2020): irot -> rotate_ccw, imir -> mirror_inplace, clap -> crop.
 // `retired` keeps the replaced buffers alive until the caller has synchronised the stream (the pool may hand a freed
@@ -134,6 +174,26 @@ class Crew {
     std::unique_lock<std::mutex> g(m_);
     job_ = nullptr; // late workers must not start any more
     done_.wait(g, [this] { return running_ == 0; });
+  }
+  // the fan-out of n pieces of work over the crew: f(i, row_threads) for i = 0 .. n - 1, claimed dynamically, on min(host_threads, n)
+  // threads.  Fewer pieces than threads (a single image, or an image and its alpha plane): row_threads > 1 is the share of the
+  // threads left over each piece may use itself - the rows of a WPP-coded picture parsed in parallel (the reference's decoder
+  // threads, decctx.cc:1004-1116).
+  template <class F>
+  static void for_each(int n, int host_threads, F&& f)
+  {
+    if (n <= 0) return;
+    int nthreads = host_threads > 0 ? host_threads : 1;
+    const int row_threads = nthreads > n ? nthreads / n : 1;
+    if (nthreads > n) nthreads = n;
+    std::atomic<int> next{0};
+    instance().run(nthreads, [&]() {
+      for (;;) {
+        const int i = next.fetch_add(1);
+        if (i >= n) break;
+        f(i, row_threads);
+      }
+    });
   }
 
  private:
@@ -572,16 +632,10 @@ int planar_from_blobs(const hm_file* f, ItemPlan& P, const hm_decode_params* par
   I.rgb_attached = false;
   if (attach && params->out_format != 0 && !hm_out_is_planar(params->out_format) && chroma != 0 && own.empty() && own_alpha.empty() && I.tile_alpha_bd == 0 &&
       (params->ignore_transformations || it->props.transforms.empty())) {
-    hm_colour_desc cd; // (exactly the request job_enqueue / run_slab would hand to hm_colour_convert)
-    std::memset(&cd, 0, sizeof(cd));
-    cd.width = canvas_w; cd.height = canvas_h; cd.bit_depth = bd; cd.chroma = chroma;
-    cd.has_nclx = is_grid ? 0 : 1; cd.matrix = native.matrix; cd.primaries = native.primaries; cd.full_range = native.full_range;
-    cd.out_format = params->out_format;
-    cd.chroma_upsampling = params->chroma_upsampling;
     const int obpp = hm_out_bytes_per_pixel(params->out_format);
     if (obpp > 0) {
-      cd.y_stride = Pl[0].stride; cd.cb_stride = Pl[1].stride; cd.cr_stride = Pl[2].stride;
-      cd.out_stride = hm_plane_stride(canvas_w, obpp);
+      // (exactly the request job_enqueue / run_slab would hand to hm_colour_convert)
+      const hm_colour_desc cd = colour_desc(params, canvas_w, canvas_h, bd, chroma, native, is_grid ? 0 : 1, Pl, obpp);
       if (!I.rgb.alloc((size_t)cd.out_stride * mem_rows(canvas_h))) {
         const void* py = Pl[0].mem.p; const void* pcb = Pl[1].mem.p; const void* pcr = Pl[2].mem.p;
         void* po = I.rgb.p;
@@ -721,7 +775,7 @@ int job_plan(DecodeJob& j)
   j.view_dx = j.view_dy = 0;
   j.sub_tiles[0] = 0; j.sub_tiles[1] = j.item[0].rows; j.sub_tiles[2] = 0; j.sub_tiles[3] = j.item[0].cols;
   int sx = 0, sy = 0, sw = 0, sh = 0;
-  if (j.has_view && view_subgrid(j.f, j.id, &j.params, &j.view, j.sub_tiles, &sx, &sy, &sw, &sh, j.has_planes)) {
+  if (j.target.t.view && view_subgrid(j.f, j.id, &j.params, j.target.t.view, j.sub_tiles, &sx, &sy, &sw, &sh, j.target.t.planes != nullptr)) {
     // the sub-grid becomes a grid of its own (what a slab is for tile rows): everything behind sees an ordinary smaller grid
     ItemPlan& P = j.item[0];
     const int32_t* t = j.sub_tiles;
@@ -780,234 +834,269 @@ void parse_picture(const hm_file* f, uint32_t id, bool few_pictures, int strict,
   if (rc) { status = rc; message = hm_last_error(); }
 }
 
-// The output half of decode_image_user (context.cc:1516-1600) for a decoded image on the device: the result's fields, the colour
-// conversion (unless the batch did it: I.rgb_attached), the alpha plane, and the copy to params->ext_dst or to pinned host
-// planes - all queued on `s`.  `dout` and `alpha_sdr` must live until the stream has drained.
-// dest (may be NULL): caller-owned device memory the interleaved pixels go to instead (hm_device_dest); nothing is copied to the host then.
-// view_later (may be NULL, with view): the view is not written here, only described there - the caller writes it with those of other images.
-// planes (may be NULL; a planar result only): caller-owned device memory the planes go to instead (hm_device_planes), one launch of
-// k_planes_to_tensor in place of the pinned allocations and the copies to the host.  With view: the view of every plane of the
-// result (hm_planes_view_write), written here or - planes_later - only described there for the caller's grouped write.
-// light (may be NULL, with dest): the write of the destination runs the light step (hm_light_write, here, on view_scratch); what
-// of it depends on the image's own profile or depth is refused before a byte of the destination is written.
-int emit_image(const hm_decode_params* params, hipStream_t s, PlanarImage& I, const DevPlane* alpha, int alpha_bd, DevMem& dout,
-               DevPlane& alpha_sdr, hm_decoded* out, const hm_device_dest* dest = nullptr, const hm_device_view* view = nullptr,
-               hm_view_scratch* view_scratch = nullptr, hm_view_item* view_later = nullptr, const hm_device_planes* planes = nullptr,
-               hm_planes_view_item* planes_later = nullptr, const hm_device_light* light = nullptr)
+int target_check_shape(const OutputTarget& t)
+{
+  const bool ok = !(t.dest && t.planes) && (!t.light || t.dest) && (!t.view || t.dest || t.planes) && (!t.view_later || (t.view && t.dest)) &&
+                  (!t.planes_later || (t.view && t.planes));
+  return ok ? (int)HM_OK : hm_fail(HM_ERR_INTERNAL, "output target: dest%s view%s planes%s light%s do not go together", t.dest ? "+" : "-", t.view ? "+" : "-",
+                                   t.planes ? "+" : "-", t.light ? "+" : "-");
+}
+
+// the chroma format and depth of a planar result for a decoded image of (chroma, bd): what emit_native / emit_planar hand out
+static void planar_result_format(const hm_decode_params* params, int chroma, int bd, int* rchroma, int* rbits)
+{
+  const bool as_decoded = params->out_format == 0 || (chroma != 0 && chroma == hm_out_planar_chroma(params->out_format));
+  *rchroma = as_decoded ? chroma : hm_out_planar_chroma(params->out_format);
+  *rbits = !as_decoded && params->convert_hdr_to_8bit ? 8 : bd;
+}
+
+// What a converted image reports: the output state's profile - the input one, none for a grid canvas, with undefined values
+// replaced by the sRGB defaults (colorconversion.cc:452-455, 520-527) - and its depth: an 8-bit image becomes 10 bit in an RRGGBB
+// target (:575-585), a deeper one 8 bit in RGB / RGBA; a planar target keeps the depth unless convert_hdr_to_8bit.
+struct Reported {
+  int has_nclx, primaries, transfer, matrix, full_range, bit_depth;
+  void profile_to(hm_decoded* out) const { out->has_nclx = has_nclx; out->primaries = primaries; out->transfer = transfer; out->matrix = matrix; out->full_range = full_range; }
+};
+static Reported converted_report(const hm::NclxProfile& native, bool is_grid, int bd, int out_format, int convert_hdr_to_8bit)
+{
+  Reported r;
+  r.has_nclx = 1;
+  r.primaries = is_grid ? 2 : native.primaries; r.transfer = is_grid ? 2 : native.transfer; r.matrix = is_grid ? 2 : native.matrix;
+  r.full_range = is_grid ? 1 : native.full_range;
+  if (r.primaries == 2) r.primaries = 1;
+  if (r.transfer == 2) r.transfer = 13;
+  if (r.matrix == 2) r.matrix = 6;
+  r.bit_depth = bd;
+  if (hm_out_is_planar(out_format)) { if (convert_hdr_to_8bit) r.bit_depth = 8; }
+  else if (bd == 8 && out_format >= HM_OUT_RRGGBB_BE && out_format <= HM_OUT_RRGGBBAA_LE) r.bit_depth = 10;
+  else if (bd > 8 && (out_format == HM_OUT_RGB || out_format == HM_OUT_RGBA)) r.bit_depth = 8;
+  return r;
+}
+
+// Can the target hold the result of a w x h image of (chroma, bits)?  The one statement of that question: the entry points ask it
+// against what the file declares, the sequence and emit_image again against the decoded picture.  A new kind of destination gets
+// its chain here.
+//   dest:   the view against the image, the destination against the view's output size, its len, the light step against the
+//           profile and depth the image reports (`reported`, may be NULL: not known yet), the pointer
+//   planes: the result's format (planar_result_format), the view against it, the planes against the view's output size - alpha_bits
+//           0: no alpha plane, -1: the decode's to say -, their len, the pointers
+// w <= 0 or h <= 0: the file does not say - only what needs no size is looked at.  pointers: a device must exist and the pointers
+// be its memory.
+static int target_fits(const hm_decode_params* params, const OutputTarget& t, int w, int h, int chroma, int bits, int alpha_bits, const Reported* reported,
+                       bool pointers)
+{
+  int rc;
+  const bool sized = w > 0 && h > 0;
+  if (t.dest) {
+    if (sized) {
+      hm_dest_plan dp;
+      hm_view_plan vp;
+      vp.ow = w; vp.oh = h;
+      if (t.view && (rc = hm_view_resolve(params->out_format, w, h, t.view, &vp))) return rc;
+      if ((rc = hm_dest_resolve(params->out_format, vp.ow, vp.oh, t.dest, &dp)) || (rc = hm_dest_check_len(t.dest, &dp))) return rc;
+      hm_light_plan lp;
+      if (t.light && reported && (rc = hm_light_resolve(params->out_format, reported->bit_depth, reported->transfer, reported->primaries, t.dest, t.light, &lp)))
+        return rc;
+    }
+    if (pointers && ((rc = require_device()) || (rc = hm_dest_check_pointer(t.dest)))) return rc;
+  }
+  if (t.planes) {
+    hm_planes_plan pp;
+    if (sized) {
+      int rchroma, rbits;
+      planar_result_format(params, chroma, bits, &rchroma, &rbits);
+      hm_planes_view_plan pv;
+      pv.ow = w; pv.oh = h;
+      if (t.view && (rc = hm_planes_view_resolve(rchroma, w, h, t.view, &pv))) return rc;
+      if ((rc = hm_planes_resolve(rchroma, rbits, pv.ow, pv.oh, alpha_bits, t.planes, &pp)) || (rc = hm_planes_check_len(t.planes, &pp))) return rc;
+    }
+    // (without a size, hm_planes_write checks the pointers against the decoded result before its launch)
+    if (pointers && ((rc = require_device()) || (sized && (rc = hm_planes_check_pointer(t.planes, &pp))))) return rc;
+  }
+  return HM_OK;
+}
+
+// the planes src[0 .. 2] (Y, Cb, Cr) and src[3] (alpha, abits > 0) of a planar result of (rchroma, rbits) into t.planes (checked against
+// the result's own format before the launch): one launch of k_planes_to_tensor, or with t.view the view of every plane
+// (hm_planes_view_write), written here or - t.planes_later - only described there for the caller's grouped write
+static int write_planes(const hm_decode_params* params, hipStream_t s, const PlanarImage& I, const OutputTarget& t, int rchroma, int rbits, const void* const src[4],
+                        const int32_t stride[4], int abits, hm_decoded* out)
+{
+  int rc;
+  int64_t pitch[4];
+  if (t.view) { // (the entry points have resolved the view against the size the file declares: here it is the decoded result)
+    hm_planes_view_item item;
+    std::memset(&item, 0, sizeof(item));
+    if ((rc = hm_planes_view_resolve(rchroma, I.w, I.h, t.view, &item.pv))) return rc;
+    item.planes = t.planes; item.chroma = rchroma; item.bits = rbits; item.alpha_bits = abits;
+    for (int c = 0; c < 4; c++) { item.src[c] = src[c]; item.stride[c] = stride[c]; }
+    if (t.planes_later) { // the caller's grouped write checks everything again; the pitches in use are known here
+      hm_planes_plan pp;
+      if ((rc = target_fits(params, t, I.w, I.h, I.chroma, I.bd, abits, nullptr, false))) return rc;
+      if ((rc = hm_planes_resolve(rchroma, rbits, item.pv.ow, item.pv.oh, abits, t.planes, &pp))) return rc;
+      for (int c = 0; c < 4; c++) item.pitches[c] = pp.pl[c].present ? pp.pl[c].pitch : 0;
+      *t.planes_later = item;
+    }
+    else if ((rc = hm_planes_view_write(&item, 1, s, t.scratch, nullptr))) return rc;
+    for (int c = 0; c < 4; c++) pitch[c] = item.pitches[c];
+    out->width = item.pv.ow; out->height = item.pv.oh;
+    for (int c = 0; c < 3; c++) { out->plane_width[c] = item.pv.out[c][0]; out->plane_height[c] = item.pv.out[c][1]; }
+  }
+  else if ((rc = hm_planes_write(t.planes, rchroma, rbits, I.w, I.h, abits, src, stride, s, pitch))) return rc;
+  out->used_ext_dst = 1;
+  for (int c = 0; c < 3; c++) out->stride[c] = (int32_t)std::min<int64_t>(pitch[c], 0x7FFFFFFF);
+  out->alpha_stride = (int32_t)std::min<int64_t>(pitch[3], 0x7FFFFFFF);
+  return HM_OK;
+}
+
+// the image as decoded: its planes (Y only for a monochrome image) and the alpha plane, to pinned host memory or to t.planes
+static int emit_native(const hm_decode_params* params, hipStream_t s, PlanarImage& I, const DevPlane* alpha, int alpha_bd, const OutputTarget& t, hm_decoded* out)
 {
   int rc;
   DevPlane (&P)[3] = I.P;
-  const int img_w = I.w, img_h = I.h, chroma = I.chroma, bd = I.bd;
-  const hm::NclxProfile& native = I.native;
-  const bool is_grid = I.is_grid;
+  out->out_format = params->out_format;
+  for (int c = 0; c < 3; c++) {
+    if (!P[c].mem.p) continue; // monochrome image: Y only
+    out->plane_width[c] = P[c].w; out->plane_height[c] = P[c].h;
+    if (!t.planes && (rc = plane_to_host(P[c].mem.p, P[c].stride, P[c].h, s, &out->plane[c], &out->stride[c]))) return rc;
+  }
+  if (t.planes) {
+    const void* src[4] = {P[0].mem.p, P[1].mem.p, P[2].mem.p, alpha ? alpha->mem.p : nullptr};
+    const int32_t stride[4] = {P[0].stride, P[1].stride, P[2].stride, alpha ? alpha->stride : 0};
+    return write_planes(params, s, I, t, I.chroma, I.bd, src, stride, alpha ? alpha_bd : 0, out);
+  }
+  return alpha ? plane_to_host(alpha->mem.p, alpha->stride, alpha->h, s, &out->alpha, &out->alpha_stride) : (int)HM_OK;
+}
 
-  out->width = img_w; out->height = img_h; out->bit_depth = bd; out->chroma = chroma;
+// a planar YCbCr target of another chroma format or colourspace than the image's: the reference's chain to it, operation by
+// operation (colour_planar.cpp), then its planes to pinned host memory or to t.planes
+static int emit_planar(const hm_decode_params* params, hipStream_t s, PlanarImage& I, const DevPlane* alpha, int alpha_bd, const OutputTarget& t, hm_decoded* out)
+{
+  int rc;
+  DevPlane (&P)[3] = I.P;
+  hm_colour_desc cd = colour_desc(params, I.w, I.h, I.bd, I.chroma, I.native, out->has_nclx, P, 0, /*planar_8bit=*/true);
+  cd.has_alpha = alpha ? 1 : 0;
+  hm_planar_image src, res;
+  for (int c = 0; c < 3; c++) { src.p[c] = P[c].mem.p; src.stride[c] = P[c].stride; }
+  if (alpha) { src.p[3] = alpha->mem.p; src.stride[3] = alpha->stride; src.alpha_bits = alpha_bd; }
+  std::vector<void*> temps;
+  rc = hm_planar_convert(&cd, &src, nullptr, &res, temps, 0, s);
+  for (void* tmp : temps) { I.retired.emplace_back(new DevMem()); I.retired.back()->p = tmp; } // (released once the stream has drained)
+  if (rc) return rc;
+  out->out_format = params->out_format;
+  out->chroma = res.chroma; out->bit_depth = res.bits;
+  for (int c = 0; c < 3; c++) { // (planes the chain passed through are copied from where they are: the decoded image's own)
+    const int pw = c == 0 || res.chroma == 3 ? I.w : (I.w + 1) / 2, ph = c == 0 || res.chroma != 1 ? I.h : (I.h + 1) / 2;
+    out->plane_width[c] = pw; out->plane_height[c] = ph;
+    if (!t.planes && (rc = plane_to_host(res.p[c], res.stride[c], ph, s, &out->plane[c], &out->stride[c]))) return rc;
+  }
+  if (t.planes) {
+    const int32_t stride[4] = {res.stride[0], res.stride[1], res.stride[2], res.stride[3]};
+    if ((rc = write_planes(params, s, I, t, res.chroma, res.bits, res.p, stride, res.p[3] ? (res.alpha_bits ? res.alpha_bits : res.bits) : 0, out))) return rc;
+  }
+  else if (res.p[3] && (rc = plane_to_host(res.p[3], res.stride[3], I.h, s, &out->alpha, &out->alpha_stride))) return rc;
+  converted_report(I.native, I.is_grid, I.bd, params->out_format, params->convert_hdr_to_8bit).profile_to(out); // (the depth: the chain's, above)
+  return HM_OK;
+}
+
+// interleaved pixels: the colour conversion (unless the batch did it: I.rgb_attached), the alpha channel, and the pixels to t.dest -
+// directly, through a view, through the light step -, to params->ext_dst or to pinned host memory
+static int emit_interleaved(const hm_decode_params* params, hipStream_t s, PlanarImage& I, const DevPlane* alpha, int alpha_bd, DevMem& dout, DevPlane& alpha_sdr,
+                            const OutputTarget& t, hm_decoded* out)
+{
+  int rc;
+  DevPlane (&P)[3] = I.P;
+  const int img_w = I.w, img_h = I.h, bd = I.bd;
+  const int obpp = hm_out_bytes_per_pixel(params->out_format);
+  if (obpp < 0) return obpp;
+  hm_colour_desc cd = colour_desc(params, img_w, img_h, bd, I.chroma, I.native, out->has_nclx, P, obpp);
+  cd.has_alpha = alpha ? 1 : 0;
+  if (I.rgb_attached && !alpha) dout.swap(I.rgb); // (converted with the batch: planar_from_blobs)
+  else {
+    if ((rc = dout.alloc((size_t)cd.out_stride * mem_rows(img_h)))) return rc;
+    if ((rc = hm_colour_convert(&cd, P[0].mem.p, P[1].mem.p, P[2].mem.p, dout.p, s))) return rc;
+  }
+  // RGB24 / RRGGBB targets have no alpha: Op_drop_alpha_plane, the colour values do not depend on it.  RGBA: the 8-bit
+  // ops copy the plane (yuv2rgb.cc:483-488)
+  if (alpha && params->out_format == HM_OUT_RGBA) {
+    const DevPlane* a8 = alpha;
+    if (alpha_bd > 8) { // (a deeper image only, see above) Op_to_sdr_planes on the alpha plane
+      if ((rc = alloc_plane(alpha_sdr, img_w, img_h, 1))) return rc;
+      if ((rc = hm_launch_to_sdr(alpha->mem.p, alpha->stride, alpha_sdr.mem.p, alpha_sdr.stride, img_w, img_h, alpha_bd, s))) return rc;
+      a8 = &alpha_sdr;
+    }
+    if ((rc = hm_launch_set_alpha(dout.p, cd.out_stride, img_w, img_h, a8->mem.p, a8->stride, s))) return rc;
+  }
+  const bool aa16 = params->out_format == HM_OUT_RRGGBBAA_BE || params->out_format == HM_OUT_RRGGBBAA_LE;
+  if (alpha && aa16)
+    if ((rc = hm_launch_set_alpha16(dout.p, cd.out_stride, img_w, img_h, alpha->mem.p, alpha->stride, alpha_bd, bd > 8 ? bd : 10,
+                                    params->out_format == HM_OUT_RRGGBBAA_BE, s))) return rc;
+  out->out_format = params->out_format;
+  const Reported r = converted_report(I.native, I.is_grid, bd, params->out_format, params->convert_hdr_to_8bit);
+  r.profile_to(out);
+  out->bit_depth = r.bit_depth;
+  out->stride[0] = cd.out_stride;
+  out->plane_width[0] = img_w; out->plane_height[0] = img_h;
+  if (t.dest) { // the image's w x h x C elements and nothing else: a 2-D device copy or k_to_tensor (devdest.cpp)
+    hm_view_plan vp; // view: a rectangle of the image at vp.ow x vp.oh goes to the destination (the resampling step instead of hm_dest_write)
+    std::memset(&vp, 0, sizeof(vp));
+    vp.ow = img_w; vp.oh = img_h;
+    if (t.view && (rc = hm_view_resolve(params->out_format, img_w, img_h, t.view, &vp))) return rc;
+    if (t.light) { // ... through the light step, resolved against the profile and depth this image reports: refused before a byte is written
+      hm_light_plan lp;
+      if ((rc = hm_light_resolve(params->out_format, r.bit_depth, r.transfer, r.primaries, t.dest, t.light, &lp))) return rc;
+      if ((rc = hm_light_write(t.dest, params->out_format, img_w, img_h, t.view ? &vp : nullptr, &lp, dout.p, cd.out_stride, s, t.scratch))) return rc;
+    }
+    else if (t.view) {
+      if (t.view_later) { t.view_later->dest = t.dest; t.view_later->vp = vp; t.view_later->src = dout.p; t.view_later->src_stride = cd.out_stride; } // (a sequence: hm_view_write_batch)
+      else if ((rc = hm_view_write(t.dest, params->out_format, &vp, dout.p, cd.out_stride, s, t.scratch))) return rc;
+    }
+    else if ((rc = hm_dest_write(t.dest, params->out_format, img_w, img_h, 0, img_h, dout.p, cd.out_stride, s))) return rc;
+    if (t.view) {
+      out->width = vp.ow; out->height = vp.oh;
+      out->plane_width[0] = vp.ow; out->plane_height[0] = vp.oh;
+    }
+    hm_dest_plan dp;
+    if ((rc = hm_dest_resolve(params->out_format, vp.ow, vp.oh, t.dest, &dp))) return rc;
+    out->used_ext_dst = 1;
+    out->stride[0] = (int32_t)std::min<int64_t>(dp.row_pitch, 0x7FFFFFFF);
+  }
+  else if (params->ext_dst && params->ext_dst_stride >= (uint32_t)(img_w * obpp) &&
+      (size_t)params->ext_dst_len >= (size_t)params->ext_dst_stride * (size_t)img_h) {
+    // caller-provided destination (fork API heif_decoding_options_add_external_dest)
+    const hipError_t e = hipMemcpy2DAsync(params->ext_dst, params->ext_dst_stride, dout.p, cd.out_stride, (size_t)img_w * obpp, img_h,
+                                          hipMemcpyDeviceToHost, s);
+    if (e != hipSuccess) return hm_check_hip(e, "D2H ext_dst");
+    out->used_ext_dst = 1;
+    out->stride[0] = params->ext_dst_stride;
+  }
+  else if ((rc = plane_to_host(dout.p, cd.out_stride, img_h, s, &out->plane[0], &out->stride[0]))) return rc;
+  return HM_OK;
+}
+
+// The output half of decode_image_user (context.cc:1516-1600) for a decoded image on the device: the result's fields, then one of
+// the three writers above - all queued on `s`.  `dout` and `alpha_sdr` must live until the stream has drained.
+// t: where the result goes (OutputTarget); what of it the entry points have refused against the size the file declares is asked
+// again here of the decoded size, before anything is written.
+int emit_image(const hm_decode_params* params, hipStream_t s, PlanarImage& I, const DevPlane* alpha, int alpha_bd, DevMem& dout, DevPlane& alpha_sdr, hm_decoded* out,
+               const OutputTarget& t = OutputTarget())
+{
+  int rc;
+  out->width = I.w; out->height = I.h; out->bit_depth = I.bd; out->chroma = I.chroma;
   out->warnings = I.warnings;
   // a grid canvas carries no nclx (context.cc:2250-2276); a single image keeps its own
-  out->has_nclx = is_grid ? 0 : 1;
-  out->primaries = native.primaries; out->transfer = native.transfer; out->matrix = native.matrix; out->full_range = native.full_range;
-  hipError_t e;
+  out->has_nclx = I.is_grid ? 0 : 1;
+  out->primaries = I.native.primaries; out->transfer = I.native.transfer; out->matrix = I.native.matrix; out->full_range = I.native.full_range;
   // a planar YCbCr target converts when the image's chroma format or colourspace differs from it, and only then
   // (context.cc:1538-1552: "different_chroma || different_colorspace"; the depth alone - convert_hdr_to_8bit - does not)
   const bool planar_target = hm_out_is_planar(params->out_format);
-  const bool as_decoded = params->out_format == 0 || (planar_target && chroma != 0 && chroma == hm_out_planar_chroma(params->out_format));
-  hm_view_plan vp; // view: a rectangle of the image at vp.ow x vp.oh goes to the destination (the resampling step instead of hm_dest_write)
-  std::memset(&vp, 0, sizeof(vp));
-  vp.ow = img_w; vp.oh = img_h;
-  if (dest) { // (the entry points have refused all of this already, against the size the file declares: here it is the decoded size)
-    hm_dest_plan dp;
-    if (view && (rc = hm_view_resolve(params->out_format, img_w, img_h, view, &vp))) return rc;
-    if ((rc = hm_dest_resolve(params->out_format, vp.ow, vp.oh, dest, &dp)) || (rc = hm_dest_check_len(dest, &dp))) return rc;
-  }
-  if (planes && !as_decoded && !planar_target) return hm_fail(HM_ERR_INTERNAL, "device planes with the interleaved output format %d", params->out_format);
-  // the planes of a planar result into the caller's device memory (checked against the result's own format before the launch)
-  auto write_planes = [&](int rchroma, int rbits, const void* const src[4], const int32_t stride[4], int abits) {
-    int64_t pitch[4];
-    if (view) { // (the entry points have resolved the view against the size the file declares: here it is the decoded result)
-      hm_planes_view_item item;
-      std::memset(&item, 0, sizeof(item));
-      int vrc = hm_planes_view_resolve(rchroma, img_w, img_h, view, &item.pv);
-      if (vrc) return vrc;
-      item.planes = planes; item.chroma = rchroma; item.bits = rbits; item.alpha_bits = abits;
-      for (int c = 0; c < 4; c++) { item.src[c] = src[c]; item.stride[c] = stride[c]; }
-      if (planes_later) { // the caller's grouped write checks everything again; the pitches in use are known here
-        hm_planes_plan pp;
-        if ((vrc = hm_planes_resolve(rchroma, rbits, item.pv.ow, item.pv.oh, abits, planes, &pp)) || (vrc = hm_planes_check_len(planes, &pp))) return vrc;
-        for (int c = 0; c < 4; c++) item.pitches[c] = pp.pl[c].present ? pp.pl[c].pitch : 0;
-        *planes_later = item;
-      }
-      else if ((vrc = hm_planes_view_write(&item, 1, s, view_scratch, nullptr))) return vrc;
-      for (int c = 0; c < 4; c++) pitch[c] = item.pitches[c];
-      out->width = item.pv.ow; out->height = item.pv.oh;
-      for (int c = 0; c < 3; c++) { out->plane_width[c] = item.pv.out[c][0]; out->plane_height[c] = item.pv.out[c][1]; }
-    }
-    else {
-      const int wrc = hm_planes_write(planes, rchroma, rbits, img_w, img_h, abits, src, stride, s, pitch);
-      if (wrc) return wrc;
-    }
-    out->used_ext_dst = 1;
-    for (int c = 0; c < 3; c++) out->stride[c] = (int32_t)std::min<int64_t>(pitch[c], 0x7FFFFFFF);
-    out->alpha_stride = (int32_t)std::min<int64_t>(pitch[3], 0x7FFFFFFF);
-    return (int)HM_OK;
-  };
-  if (as_decoded) { // native planar YCbCr
-    out->out_format = params->out_format;
-    for (int c = 0; c < 3; c++) {
-      if (!P[c].mem.p) continue; // monochrome image: Y only
-      out->plane_width[c] = P[c].w; out->plane_height[c] = P[c].h;
-      if (planes) continue;
-      const size_t sz = plane_bytes(P[c]);
-      out->plane[c] = (uint8_t*)hm_pool_pinned_alloc(sz);
-      if (!out->plane[c]) return hm_fail(HM_ERR_NOMEM, "out of memory");
-      out->stride[c] = P[c].stride;
-      e = hipMemcpyAsync(out->plane[c], P[c].mem.p, sz, hipMemcpyDeviceToHost, s);
-      if (e != hipSuccess) return hm_check_hip(e, "D2H");
-    }
-    if (planes) {
-      const void* src[4] = {P[0].mem.p, P[1].mem.p, P[2].mem.p, alpha ? alpha->mem.p : nullptr};
-      const int32_t stride[4] = {P[0].stride, P[1].stride, P[2].stride, alpha ? alpha->stride : 0};
-      if ((rc = write_planes(chroma, bd, src, stride, alpha ? alpha_bd : 0))) return rc;
-    }
-    else if (alpha) {
-      const size_t sz = plane_bytes(*alpha);
-      out->alpha = (uint8_t*)hm_pool_pinned_alloc(sz);
-      if (!out->alpha) return hm_fail(HM_ERR_NOMEM, "out of memory");
-      out->alpha_stride = alpha->stride;
-      e = hipMemcpyAsync(out->alpha, alpha->mem.p, sz, hipMemcpyDeviceToHost, s);
-      if (e != hipSuccess) return hm_check_hip(e, "D2H");
-    }
-  }
-  else if (planar_target) { // the reference's chain to that chroma format, operation by operation (colour_planar.cpp)
-    hm_colour_desc cd;
-    std::memset(&cd, 0, sizeof(cd));
-    cd.width = img_w; cd.height = img_h; cd.bit_depth = bd; cd.chroma = chroma;
-    cd.has_nclx = out->has_nclx; cd.matrix = native.matrix; cd.primaries = native.primaries; cd.full_range = native.full_range;
-    cd.out_format = params->out_format | (params->convert_hdr_to_8bit ? HM_OUT_YCBCR_8BIT : 0);
-    cd.chroma_upsampling = params->chroma_upsampling;
-    cd.has_alpha = alpha ? 1 : 0;
-    cd.y_stride = P[0].stride; cd.cb_stride = P[1].stride; cd.cr_stride = P[2].stride;
-    hm_planar_image src, res;
-    for (int c = 0; c < 3; c++) { src.p[c] = P[c].mem.p; src.stride[c] = P[c].stride; }
-    if (alpha) { src.p[3] = alpha->mem.p; src.stride[3] = alpha->stride; src.alpha_bits = alpha_bd; }
-    std::vector<void*> temps;
-    rc = hm_planar_convert(&cd, &src, nullptr, &res, temps, 0, s);
-    for (void* t : temps) { I.retired.emplace_back(new DevMem()); I.retired.back()->p = t; } // (released once the stream has drained)
-    if (rc) return rc;
-    out->out_format = params->out_format;
-    out->chroma = res.chroma; out->bit_depth = res.bits;
-    for (int c = 0; c < 3; c++) { // (planes the chain passed through are copied from where they are: the decoded image's own)
-      const int pw = c == 0 || res.chroma == 3 ? img_w : (img_w + 1) / 2, ph = c == 0 || res.chroma != 1 ? img_h : (img_h + 1) / 2;
-      out->plane_width[c] = pw; out->plane_height[c] = ph;
-      if (planes) continue;
-      const size_t sz = (size_t)res.stride[c] * mem_rows(ph);
-      out->plane[c] = (uint8_t*)hm_pool_pinned_alloc(sz);
-      if (!out->plane[c]) return hm_fail(HM_ERR_NOMEM, "out of memory");
-      out->stride[c] = res.stride[c];
-      e = hipMemcpyAsync(out->plane[c], res.p[c], sz, hipMemcpyDeviceToHost, s);
-      if (e != hipSuccess) return hm_check_hip(e, "D2H");
-    }
-    if (planes) {
-      const int32_t stride[4] = {res.stride[0], res.stride[1], res.stride[2], res.stride[3]};
-      if ((rc = write_planes(res.chroma, res.bits, res.p, stride, res.p[3] ? (res.alpha_bits ? res.alpha_bits : res.bits) : 0))) return rc;
-    }
-    else if (res.p[3]) {
-      const size_t sz = (size_t)res.stride[3] * mem_rows(img_h);
-      out->alpha = (uint8_t*)hm_pool_pinned_alloc(sz);
-      if (!out->alpha) return hm_fail(HM_ERR_NOMEM, "out of memory");
-      out->alpha_stride = res.stride[3];
-      e = hipMemcpyAsync(out->alpha, res.p[3], sz, hipMemcpyDeviceToHost, s);
-      if (e != hipSuccess) return hm_check_hip(e, "D2H");
-    }
-    // the converted image carries the output state's profile, as below
-    out->has_nclx = 1;
-    if (is_grid) { out->primaries = 2; out->transfer = 2; out->matrix = 2; out->full_range = 1; }
-    if (out->primaries == 2) out->primaries = 1;
-    if (out->transfer == 2) out->transfer = 13;
-    if (out->matrix == 2) out->matrix = 6;
-  }
-  else {
-    hm_colour_desc cd;
-    std::memset(&cd, 0, sizeof(cd));
-    cd.width = img_w; cd.height = img_h; cd.bit_depth = bd; cd.chroma = chroma;
-    cd.has_nclx = out->has_nclx; cd.matrix = native.matrix; cd.primaries = native.primaries; cd.full_range = native.full_range;
-    cd.out_format = params->out_format;
-    cd.chroma_upsampling = params->chroma_upsampling;
-    cd.has_alpha = alpha ? 1 : 0;
-    const int obpp = hm_out_bytes_per_pixel(params->out_format);
-    if (obpp < 0) return obpp;
-    cd.y_stride = P[0].stride; cd.cb_stride = P[1].stride; cd.cr_stride = P[2].stride;
-    cd.out_stride = hm_plane_stride(img_w, obpp);
-    const size_t obytes = (size_t)cd.out_stride * mem_rows(img_h);
-    if (I.rgb_attached && !alpha) dout.swap(I.rgb); // (converted with the batch: planar_from_blobs)
-    else {
-      if ((rc = dout.alloc(obytes))) return rc;
-      if ((rc = hm_colour_convert(&cd, P[0].mem.p, P[1].mem.p, P[2].mem.p, dout.p, s))) return rc;
-    }
-    // RGB24 / RRGGBB targets have no alpha: Op_drop_alpha_plane, the colour values do not depend on it.  RGBA: the 8-bit
-    // ops copy the plane (yuv2rgb.cc:483-488)
-    if (alpha && params->out_format == HM_OUT_RGBA) {
-      const DevPlane* a8 = alpha;
-      if (alpha_bd > 8) { // (a deeper image only, see above) Op_to_sdr_planes on the alpha plane
-        if ((rc = alloc_plane(alpha_sdr, img_w, img_h, 1))) return rc;
-        if ((rc = hm_launch_to_sdr(alpha->mem.p, alpha->stride, alpha_sdr.mem.p, alpha_sdr.stride, img_w, img_h, alpha_bd, s))) return rc;
-        a8 = &alpha_sdr;
-      }
-      if ((rc = hm_launch_set_alpha(dout.p, cd.out_stride, img_w, img_h, a8->mem.p, a8->stride, s))) return rc;
-    }
-    const bool aa16 = params->out_format == HM_OUT_RRGGBBAA_BE || params->out_format == HM_OUT_RRGGBBAA_LE;
-    if (alpha && aa16)
-      if ((rc = hm_launch_set_alpha16(dout.p, cd.out_stride, img_w, img_h, alpha->mem.p, alpha->stride, alpha_bd, bd > 8 ? bd : 10,
-                                      params->out_format == HM_OUT_RRGGBBAA_BE, s))) return rc;
-    out->out_format = params->out_format;
-    // the converted image carries the output state's profile: the input one with undefined values replaced by the
-    // sRGB defaults (colorconversion.cc:452-455, 520-527); an 8-bit image becomes 10 bit in an RRGGBB target (:575-585)
-    out->has_nclx = 1;
-    if (!is_grid) { out->primaries = native.primaries; out->transfer = native.transfer; out->matrix = native.matrix; out->full_range = native.full_range; }
-    else { out->primaries = 2; out->transfer = 2; out->matrix = 2; out->full_range = 1; }
-    if (out->primaries == 2) out->primaries = 1;
-    if (out->transfer == 2) out->transfer = 13;
-    if (out->matrix == 2) out->matrix = 6;
-    if (bd == 8 && hm_out_bytes_per_pixel(params->out_format) >= 6) out->bit_depth = 10;
-    if (bd > 8 && (params->out_format == HM_OUT_RGB || params->out_format == HM_OUT_RGBA)) out->bit_depth = 8;
-    out->stride[0] = cd.out_stride;
-    out->plane_width[0] = img_w; out->plane_height[0] = img_h;
-    if (dest) { // the image's w x h x C elements and nothing else: a 2-D device copy or k_to_tensor (devdest.cpp)
-      if (light) { // ... through the light step, resolved against the profile and depth this image reports: refused before a byte is written
-        hm_light_plan lp;
-        if ((rc = hm_light_resolve(params->out_format, out->bit_depth, out->transfer, out->primaries, dest, light, &lp))) return rc;
-        if ((rc = hm_light_write(dest, params->out_format, img_w, img_h, view ? &vp : nullptr, &lp, dout.p, cd.out_stride, s, view_scratch))) return rc;
-      }
-      else if (view) {
-        if (view_later) { view_later->dest = dest; view_later->vp = vp; view_later->src = dout.p; view_later->src_stride = cd.out_stride; } // (a sequence: hm_view_write_batch)
-        else if ((rc = hm_view_write(dest, params->out_format, &vp, dout.p, cd.out_stride, s, view_scratch))) return rc;
-      }
-      else if ((rc = hm_dest_write(dest, params->out_format, img_w, img_h, 0, img_h, dout.p, cd.out_stride, s))) return rc;
-      if (view) {
-        out->width = vp.ow; out->height = vp.oh;
-        out->plane_width[0] = vp.ow; out->plane_height[0] = vp.oh;
-      }
-      hm_dest_plan dp;
-      if ((rc = hm_dest_resolve(params->out_format, vp.ow, vp.oh, dest, &dp))) return rc;
-      out->used_ext_dst = 1;
-      out->stride[0] = (int32_t)std::min<int64_t>(dp.row_pitch, 0x7FFFFFFF);
-    }
-    else if (params->ext_dst && params->ext_dst_stride >= (uint32_t)(img_w * obpp) &&
-        (size_t)params->ext_dst_len >= (size_t)params->ext_dst_stride * (size_t)img_h) {
-      // caller-provided destination (fork API heif_decoding_options_add_external_dest)
-      e = hipMemcpy2DAsync(params->ext_dst, params->ext_dst_stride, dout.p, cd.out_stride, (size_t)img_w * obpp, img_h,
-                           hipMemcpyDeviceToHost, s);
-      if (e != hipSuccess) return hm_check_hip(e, "D2H ext_dst");
-      out->used_ext_dst = 1;
-      out->stride[0] = params->ext_dst_stride;
-    }
-    else {
-      out->plane[0] = (uint8_t*)hm_pool_pinned_alloc(obytes);
-      if (!out->plane[0]) return hm_fail(HM_ERR_NOMEM, "out of memory");
-      e = hipMemcpyAsync(out->plane[0], dout.p, obytes, hipMemcpyDeviceToHost, s);
-      if (e != hipSuccess) return hm_check_hip(e, "D2H");
-    }
-  }
-  return HM_OK;
+  const bool as_decoded = params->out_format == 0 || (planar_target && I.chroma != 0 && I.chroma == hm_out_planar_chroma(params->out_format));
+  // (planes are asked of the result's own format, by write_planes; the light step of the profile the conversion reports, by emit_interleaved)
+  if (t.dest && (rc = target_fits(params, t, I.w, I.h, I.chroma, I.bd, 0, nullptr, false))) return rc;
+  if (t.planes && !as_decoded && !planar_target) return hm_fail(HM_ERR_INTERNAL, "device planes with the interleaved output format %d", params->out_format);
+  if (as_decoded) return emit_native(params, s, I, alpha, alpha_bd, t, out);
+  if (planar_target) return emit_planar(params, s, I, alpha, alpha_bd, t, out);
+  return emit_interleaved(params, s, I, alpha, alpha_bd, dout, alpha_sdr, t, out);
 }
 
 // Everything after the host entropy decode, queued on j.s without waiting: GPU batch(es), transforms, alpha, colour
@@ -1055,38 +1144,19 @@ int job_enqueue(DecodeJob& j, hm_decoded* out)
   }
   const int alpha_bd = j.n_items > 1 ? A.bd : I.tile_alpha_bd;
   lap("planar decode queued");
-  hm_device_view shifted = j.view; // (the crop inside the sub-grid that was decoded)
-  if (j.has_view && (shifted.crop_w || shifted.crop_h)) { shifted.crop_x -= j.view_dx; shifted.crop_y -= j.view_dy; }
-  rc = emit_image(params, s, I, alpha, alpha_bd, j.dout, j.alpha_sdr, out, j.has_dest ? &j.dest : nullptr, j.has_view ? &shifted : nullptr, &j.view_scratch, nullptr,
-                  j.has_planes ? &j.planes : nullptr, nullptr, j.has_light ? &j.light : nullptr);
+  OutputTarget t = j.target.t;
+  t.scratch = &j.view_scratch;
+  hm_device_view shifted = j.target.view; // (the crop inside the sub-grid that was decoded)
+  if (t.view && (shifted.crop_w || shifted.crop_h)) { shifted.crop_x -= j.view_dx; shifted.crop_y -= j.view_dy; }
+  if (t.view) t.view = &shifted;
+  rc = emit_image(params, s, I, alpha, alpha_bd, j.dout, j.alpha_sdr, out, t);
   if (rc) return rc;
   lap("colour + D2H queued");
   return HM_OK;
 }
 
-int check_device_request(const hm_file* f, uint32_t id, const hm_decode_params* params, const hm_device_dest* dest, const hm_device_view* view,
-                         const hm_device_light* light)
-{
-  if (params->ext_dst) return hm_fail(HM_ERR_INVALID_ARG, "params->ext_dst must be NULL with a device destination");
-  int rc = hm_dest_check_static(params->out_format, dest);
-  if (rc) return rc;
-  if (light && (rc = hm_light_check_static(params->out_format, dest, light, 0))) return rc;
-  if (!dest->ptr) return hm_fail(HM_ERR_INVALID_ARG, "device destination: null ptr");
-  hm_image_info info;
-  if (hm_file_image_info(f, id, &info) == HM_OK) { // (a file that fails here fails the decode with its own message)
-    const int w = params->ignore_transformations ? info.coded_width : info.width, h = params->ignore_transformations ? info.coded_height : info.height;
-    hm_dest_plan dp;
-    hm_view_plan vp;
-    vp.ow = w; vp.oh = h;
-    if (view && w > 0 && h > 0 && (rc = hm_view_resolve(params->out_format, w, h, view, &vp))) return rc;
-    if (w > 0 && h > 0 && ((rc = hm_dest_resolve(params->out_format, vp.ow, vp.oh, dest, &dp)) || (rc = hm_dest_check_len(dest, &dp)))) return rc;
-  }
-  int n_dev = 0;
-  if (hipGetDeviceCount(&n_dev) != hipSuccess || n_dev == 0) { (void)hipGetLastError(); return hm_fail(HM_ERR_NO_DEVICE, "no HIP device available"); }
-  return hm_dest_check_pointer(dest);
-}
-
-int check_planes_params(const hm_decode_params* params, const hm_device_planes* planes)
+// what of a planar destination needs no file: params (ext_dst, an interleaved target), the planes' static checks, a null pointer of Y
+static int check_planes_params(const hm_decode_params* params, const hm_device_planes* planes)
 {
   if (params->ext_dst) return hm_fail(HM_ERR_INVALID_ARG, "params->ext_dst must be NULL with device planes");
   if (params->out_format != 0 && !hm_out_is_planar(params->out_format)) {
@@ -1101,38 +1171,24 @@ int check_planes_params(const hm_decode_params* params, const hm_device_planes* 
   return HM_OK;
 }
 
-// the chroma format and depth of a planar result for a decoded image of (chroma, bd): what emit_image's branches hand out
-static void planar_result_format(const hm_decode_params* params, int chroma, int bd, int* rchroma, int* rbits)
+int check_target_request(const hm_file* f, uint32_t id, const hm_decode_params* params, const OutputTarget& t)
 {
-  const bool as_decoded = params->out_format == 0 || (chroma != 0 && chroma == hm_out_planar_chroma(params->out_format));
-  *rchroma = as_decoded ? chroma : hm_out_planar_chroma(params->out_format);
-  *rbits = !as_decoded && params->convert_hdr_to_8bit ? 8 : bd;
-}
-
-int check_planes_request(const hm_file* f, uint32_t id, const hm_decode_params* params, const hm_device_planes* planes, const hm_device_view* view)
-{
-  int rc = check_planes_params(params, planes);
+  int rc = target_check_shape(t);
   if (rc) return rc;
-  hm_image_info info;
-  hm_planes_plan pp;
-  bool planned = false;
-  if (hm_file_image_info(f, id, &info) == HM_OK) { // (a file that fails here fails the decode with its own message)
-    const int w = params->ignore_transformations ? info.coded_width : info.width, h = params->ignore_transformations ? info.coded_height : info.height;
-    if (w > 0 && h > 0 && info.bit_depth >= 8 && info.bit_depth <= 16 && info.chroma >= 0 && info.chroma <= 3) {
-      int rchroma, rbits;
-      planar_result_format(params, info.chroma, info.bit_depth, &rchroma, &rbits);
-      hm_planes_view_plan pv; // view: the planes are judged against its output size, the crop against the declared size
-      pv.ow = w; pv.oh = h;
-      if (view && (rc = hm_planes_view_resolve(rchroma, w, h, view, &pv))) return rc;
-      // (whether there is an alpha plane, and of which depth, is the decode's to say: -1)
-      if ((rc = hm_planes_resolve(rchroma, rbits, pv.ow, pv.oh, -1, planes, &pp)) || (rc = hm_planes_check_len(planes, &pp))) return rc;
-      planned = true;
-    }
+  if (t.dest) {
+    if (params->ext_dst) return hm_fail(HM_ERR_INVALID_ARG, "params->ext_dst must be NULL with a device destination");
+    if ((rc = hm_dest_check_static(params->out_format, t.dest))) return rc;
+    if (t.light && (rc = hm_light_check_static(params->out_format, t.dest, t.light, 0))) return rc;
+    if (!t.dest->ptr) return hm_fail(HM_ERR_INVALID_ARG, "device destination: null ptr");
   }
-  int n_dev = 0;
-  if (hipGetDeviceCount(&n_dev) != hipSuccess || n_dev == 0) { (void)hipGetLastError(); return hm_fail(HM_ERR_NO_DEVICE, "no HIP device available"); }
-  if (planned) return hm_planes_check_pointer(planes, &pp);
-  return HM_OK; // (hm_planes_write checks the pointers against the decoded result before its launch)
+  if (t.planes && (rc = check_planes_params(params, t.planes))) return rc;
+  hm_image_info info{};
+  int w = 0, h = 0; // (a file that fails here, or declares nothing usable, fails the decode with its own message)
+  if (hm_file_image_info(f, id, &info) == HM_OK && (!t.planes || (info.bit_depth >= 8 && info.bit_depth <= 16 && info.chroma >= 0 && info.chroma <= 3))) {
+    w = params->ignore_transformations ? info.coded_width : info.width; h = params->ignore_transformations ? info.coded_height : info.height;
+  }
+  // (whether there is an alpha plane, and of which depth, is the decode's to say: -1)
+  return target_fits(params, t, w, h, info.chroma, info.bit_depth, -1, nullptr, true);
 }
 
 int job_complete(DecodeJob& j, hm_decoded*)
@@ -1486,32 +1542,22 @@ int derived_refusal(const hm_file* f, uint32_t id, const hm_decode_params* param
 }
 
 // hm_decode_item and its device forms on a derived item
-int decode_derived(const hm_file* f, uint32_t id, const hm_decode_params* params, const hm_device_dest* dest, const hm_device_view* view, const hm_device_planes* planes,
-                   hm_decoded* out, const hm_device_light* light = nullptr)
+int decode_derived(const hm_file* f, uint32_t id, const hm_decode_params* params, const OutputTarget& target, hm_decoded* out)
 {
   std::memset(out, 0, sizeof(*out));
   Lap lap;
   DerivedRun R;
-  int rc = derived_prepare(R, f, id, params, view, planes != nullptr);
+  int rc = derived_prepare(R, f, id, params, target.view, target.planes != nullptr);
   if (rc) return rc;
+  OutputTarget t = target;
+  t.scratch = &R.view_scratch;
   // ---- host: the entropy decode of every coded picture under the item, one fan-out ----
   std::vector<std::pair<DecodeJob*, int>> work;
   for (DecodeJob* j : R.jobs)
     for (int k = 0, nk = job_tile_count(*j); k < nk; k++) work.push_back({j, k});
   const int nt = (int)work.size();
   for (DecodeJob* j : R.jobs) j->few_pictures = nt <= 64;
-  std::atomic<int> next{0};
-  int nthreads = params->host_threads > 0 ? params->host_threads : 1;
-  const int row_threads = nt > 0 && nthreads > nt ? nthreads / nt : 1;
-  auto worker = [&]() {
-    for (;;) {
-      const int i = next.fetch_add(1);
-      if (i >= nt) break;
-      job_parse_tile(*work[i].first, work[i].second, row_threads);
-    }
-  };
-  if (nthreads > nt) nthreads = nt;
-  if (nt > 0) Crew::instance().run(nthreads, worker);
+  Crew::for_each(nt, params->host_threads, [&](int i, int row_threads) { job_parse_tile(*work[i].first, work[i].second, row_threads); });
   lap("host entropy decode done");
   // what only the pictures say, before anything is queued: the composition is one of 8-bit samples
   for (DecodeJob* j : R.jobs)
@@ -1539,7 +1585,7 @@ int decode_derived(const hm_file* f, uint32_t id, const hm_decode_params* params
     LayerImage L;
     if ((rc = produce_coded(R, root, L))) return rc;
     if (L.alpha) out->has_alpha = 1;
-    rc = emit_image(params, R.s, root.job->I, L.alpha, 8, R.dout, R.alpha_sdr, out, dest, view, &R.view_scratch, nullptr, planes, nullptr, light);
+    rc = emit_image(params, R.s, root.job->I, L.alpha, 8, R.dout, R.alpha_sdr, out, t);
     if (L.alpha && !rc) out->has_alpha = 1;
   }
   else {
@@ -1568,7 +1614,7 @@ int decode_derived(const hm_file* f, uint32_t id, const hm_decode_params* params
     // which carries no profile of its own, like a grid canvas - the converted image then reports the sRGB defaults
     I.w = w; I.h = h; I.chroma = 3; I.bd = 8; I.is_grid = true; I.rgb_attached = true;
     I.native = hm::NclxProfile();
-    rc = emit_image(params, R.s, I, nullptr, 0, R.dout, R.alpha_sdr, out, dest, view, &R.view_scratch, nullptr, nullptr, nullptr, light);
+    rc = emit_image(params, R.s, I, nullptr, 0, R.dout, R.alpha_sdr, out, t); // (planes: refused by derived_prepare)
   }
   return rc;
   }();
@@ -1594,65 +1640,54 @@ extern "C" {
 
 static int decode_grid_cut(const hm_file* f, uint32_t id, const hm_decode_params* params, const int32_t* devices, int n_devices, bool pipelined, hm_decoded* out, bool* applicable,
                            const hm_device_dest* dest = nullptr); // (below, behind the slabs)
-static int decode_item(const hm_file* f, uint32_t id, const hm_decode_params* params, const hm_device_dest* dest, hm_decoded* out, const hm_device_view* view = nullptr,
-                       const hm_device_planes* planes = nullptr, const hm_device_light* light = nullptr);
+static int decode_item(const hm_file* f, uint32_t id, const hm_decode_params* params, const OutputTarget& target, hm_decoded* out);
 
 int hm_decode_item(const hm_file* f, uint32_t id, const hm_decode_params* params, hm_decoded* out)
 {
   if (!f || !params || !out) return hm_fail(HM_ERR_INVALID_ARG, "null argument");
-  return decode_item(f, id, params, nullptr, out);
+  return decode_item(f, id, params, OutputTarget(), out);
+}
+
+// the device forms of hm_decode_item: what can be refused is refused before any work is queued - the destination is not written
+static int decode_item_to(const hm_file* f, uint32_t id, const hm_decode_params* params, const OutputTarget& target, hm_decoded* out)
+{
+  std::memset(out, 0, sizeof(*out));
+  if (is_derived_item(f, id)) { const int drc = derived_refusal(f, id, params, target.planes != nullptr); if (drc) return drc; }
+  const int rc = check_target_request(f, id, params, target);
+  if (rc) return rc;
+  return decode_item(f, id, params, target, out);
 }
 
 int hm_decode_item_to_device(const hm_file* f, uint32_t id, const hm_decode_params* params, const hm_device_dest* dest, hm_decoded* out)
 {
   if (!f || !params || !dest || !out) return hm_fail(HM_ERR_INVALID_ARG, "null argument");
-  std::memset(out, 0, sizeof(*out));
-  if (is_derived_item(f, id)) { const int drc = derived_refusal(f, id, params, false); if (drc) return drc; }
-  const int rc = check_device_request(f, id, params, dest); // refused before any work is queued: the destination is not written
-  if (rc) return rc;
-  return decode_item(f, id, params, dest, out);
+  return decode_item_to(f, id, params, OutputTarget::to_dest(dest), out);
 }
 
 int hm_decode_item_to_device_view(const hm_file* f, uint32_t id, const hm_decode_params* params, const hm_device_view* view, const hm_device_dest* dest, hm_decoded* out)
 {
   if (!f || !params || !view || !dest || !out) return hm_fail(HM_ERR_INVALID_ARG, "null argument");
-  std::memset(out, 0, sizeof(*out));
-  if (is_derived_item(f, id)) { const int drc = derived_refusal(f, id, params, false); if (drc) return drc; }
-  const int rc = check_device_request(f, id, params, dest, view); // refused before any work is queued: the destination is not written
-  if (rc) return rc;
-  return decode_item(f, id, params, dest, out, view);
+  return decode_item_to(f, id, params, OutputTarget::to_dest(dest, view), out);
 }
 
 int hm_decode_item_to_device_light(const hm_file* f, uint32_t id, const hm_decode_params* params, const hm_device_view* view, const hm_device_light* light,
                                    const hm_device_dest* dest, hm_decoded* out)
 {
   if (!f || !params || !light || !dest || !out) return hm_fail(HM_ERR_INVALID_ARG, "null argument");
-  std::memset(out, 0, sizeof(*out));
-  if (is_derived_item(f, id)) { const int drc = derived_refusal(f, id, params, false); if (drc) return drc; }
-  const int rc = check_device_request(f, id, params, dest, view, light); // refused before any work is queued: the destination is not written
-  if (rc) return rc;
-  return decode_item(f, id, params, dest, out, view, nullptr, light);
+  return decode_item_to(f, id, params, OutputTarget::to_dest(dest, view, light), out);
 }
 
 int hm_decode_item_to_device_planes(const hm_file* f, uint32_t id, const hm_decode_params* params, const hm_device_planes* planes, hm_decoded* out)
 {
   if (!f || !params || !planes || !out) return hm_fail(HM_ERR_INVALID_ARG, "null argument");
-  std::memset(out, 0, sizeof(*out));
-  if (is_derived_item(f, id)) { const int drc = derived_refusal(f, id, params, true); if (drc) return drc; }
-  const int rc = check_planes_request(f, id, params, planes); // refused before any work is queued: no plane is written
-  if (rc) return rc;
-  return decode_item(f, id, params, nullptr, out, nullptr, planes);
+  return decode_item_to(f, id, params, OutputTarget::to_planes(planes), out);
 }
 
 int hm_decode_item_to_device_planes_view(const hm_file* f, uint32_t id, const hm_decode_params* params, const hm_device_view* view, const hm_device_planes* planes,
                                          hm_decoded* out)
 {
   if (!f || !params || !view || !planes || !out) return hm_fail(HM_ERR_INVALID_ARG, "null argument");
-  std::memset(out, 0, sizeof(*out));
-  if (is_derived_item(f, id)) { const int drc = derived_refusal(f, id, params, true); if (drc) return drc; }
-  const int rc = check_planes_request(f, id, params, planes, view); // refused before any work is queued: no plane is written
-  if (rc) return rc;
-  return decode_item(f, id, params, nullptr, out, view, planes);
+  return decode_item_to(f, id, params, OutputTarget::to_planes(planes, view), out);
 }
 
 int hm_plan_planes_view(const hm_file* f, uint32_t id, const hm_decode_params* params, const hm_device_view* view, int32_t tiles[4])
@@ -1733,48 +1768,29 @@ int hm_plan_view(const hm_file* f, uint32_t id, const hm_decode_params* params, 
   return HM_OK;
 }
 
-// dest (may be NULL): the pixels go to caller-owned device memory; view (may be NULL, with dest only): a rectangle of them, resampled -
-// always as one job (its plan is reduced to the tiles the crop touches), never slab by slab
-// planes (may be NULL, without dest): a planar result goes to caller-owned device memory plane by plane (planar output is one job: the cut below declines it)
-// light (may be NULL, with dest): the light step in the write of the destination - one job, as with a view
-static int decode_item(const hm_file* f, uint32_t id, const hm_decode_params* params, const hm_device_dest* dest, hm_decoded* out, const hm_device_view* view,
-                       const hm_device_planes* planes, const hm_device_light* light)
+// target: with a view or a light step the item is always decoded as one job (its plan is reduced to the tiles the crop touches), never
+// slab by slab; planar output is one job too (the cut below declines it)
+static int decode_item(const hm_file* f, uint32_t id, const hm_decode_params* params, const OutputTarget& target, hm_decoded* out)
 {
   std::memset(out, 0, sizeof(*out)); // (whatever fails below: nothing of an earlier call is left in it)
-  if (is_derived_item(f, id)) return decode_derived(f, id, params, dest, view, planes, out, light);
-  if (!view && !light) { // (r06) a grid of more tiles than parsing threads, to interleaved pixels: slab by slab under the entropy decode (decode_grid_cut)
+  if (is_derived_item(f, id)) return decode_derived(f, id, params, target, out);
+  if (!target.view && !target.light) { // (r06) a grid of more tiles than parsing threads, to interleaved pixels: slab by slab under the entropy decode (decode_grid_cut)
     bool applicable = false;
-    const int prc = decode_grid_cut(f, id, params, nullptr, 1, /*pipelined=*/true, out, &applicable, dest);
+    const int prc = decode_grid_cut(f, id, params, nullptr, 1, /*pipelined=*/true, out, &applicable, target.dest);
     if (prc || applicable) return prc;
   }
   std::memset(out, 0, sizeof(*out));
   Lap lap;
   DecodeJob job;
   job.f = f; job.id = id; job.params = *params; job.s = (hipStream_t)params->stream;
-  if (dest) { job.dest = *dest; job.has_dest = true; }
-  if (view) { job.view = *view; job.has_view = true; }
-  if (planes) { job.planes = *planes; job.has_planes = true; }
-  if (light) { job.light = *light; job.has_light = true; }
+  job.target.set(target);
   int rc = job_plan(job);
   if (rc) return rc;
   // ---- host: entropy-decode every coded picture (CABAC on the CPU, spread over threads like the reference's
   //      heif_context_set_threads tile fan-out, context.cc:2361-2401) ----
   const int nt = job_tile_count(job);
   job.few_pictures = nt <= 64; // one image at a time: its tiles are the whole batch - split chains for every class (hm_image_job.h)
-  std::atomic<int> next{0};
-  int nthreads = params->host_threads > 0 ? params->host_threads : 1;
-  // fewer coded pictures than threads (a single image, or an image and its alpha plane): the threads left over parse
-  // the rows of a WPP-coded picture in parallel instead (the reference's decoder threads, decctx.cc:1004-1116)
-  const int row_threads = nt > 0 && nthreads > nt ? nthreads / nt : 1;
-  auto worker = [&]() {
-    for (;;) {
-      const int i = next.fetch_add(1);
-      if (i >= nt) break;
-      job_parse_tile(job, i, row_threads);
-    }
-  };
-  if (nthreads > nt) nthreads = nt;
-  Crew::instance().run(nthreads, worker);
+  Crew::for_each(nt, params->host_threads, [&](int i, int row_threads) { job_parse_tile(job, i, row_threads); });
   lap("host entropy decode done");
   rc = job_enqueue(job, out);
   if (!rc) rc = job_complete(job, out);
@@ -1831,21 +1847,20 @@ int hm_file_sequence_info(const hm_file* f, hm_sequence_info* info)
 }
 
 static int decode_sequence(const hm_file* f, const uint32_t* frames, uint32_t first, int32_t count, const hm_decode_params* params, const hm_frame_dest* dests,
-                           const hm_device_dest* ddests, const hm_device_view* view, hm_decoded* out, int32_t* failed_frame, const hm_device_planes* pdests = nullptr,
-                           const hm_device_light* light = nullptr);
+                           const OutputTarget& target, hm_decoded* out, int32_t* failed_frame);
 
 int hm_decode_frames_to_device_planes_view(const hm_file* f, const uint32_t* frames, int32_t count, const hm_decode_params* params, const hm_device_view* view,
                                            const hm_device_planes* planes, hm_decoded* out, int32_t* failed_frame)
 {
   if (failed_frame) *failed_frame = -1;
   if (!frames || !planes || !view) return hm_fail(HM_ERR_INVALID_ARG, "null argument");
-  return decode_sequence(f, frames, 0, count, params, nullptr, nullptr, view, out, failed_frame, planes);
+  return decode_sequence(f, frames, 0, count, params, nullptr, OutputTarget::to_planes(planes, view), out, failed_frame);
 }
 
 int hm_decode_sequence(const hm_file* f, uint32_t first, int32_t count, const hm_decode_params* params, const hm_frame_dest* dests,
                        hm_decoded* out, int32_t* failed_frame)
 {
-  return decode_sequence(f, nullptr, first, count, params, dests, nullptr, nullptr, out, failed_frame);
+  return decode_sequence(f, nullptr, first, count, params, dests, OutputTarget(), out, failed_frame);
 }
 
 int hm_decode_sequence_to_device(const hm_file* f, uint32_t first, int32_t count, const hm_decode_params* params, const hm_device_dest* dests,
@@ -1853,7 +1868,7 @@ int hm_decode_sequence_to_device(const hm_file* f, uint32_t first, int32_t count
 {
   if (failed_frame) *failed_frame = -1;
   if (!dests) return hm_fail(HM_ERR_INVALID_ARG, "null argument");
-  return decode_sequence(f, nullptr, first, count, params, nullptr, dests, nullptr, out, failed_frame);
+  return decode_sequence(f, nullptr, first, count, params, nullptr, OutputTarget::to_dest(dests), out, failed_frame);
 }
 
 int hm_decode_frames_to_device_view(const hm_file* f, const uint32_t* frames, int32_t count, const hm_decode_params* params, const hm_device_view* view,
@@ -1861,7 +1876,7 @@ int hm_decode_frames_to_device_view(const hm_file* f, const uint32_t* frames, in
 {
   if (failed_frame) *failed_frame = -1;
   if (!frames || !dests) return hm_fail(HM_ERR_INVALID_ARG, "null argument");
-  return decode_sequence(f, frames, 0, count, params, nullptr, dests, view, out, failed_frame);
+  return decode_sequence(f, frames, 0, count, params, nullptr, OutputTarget::to_dest(dests, view), out, failed_frame);
 }
 
 int hm_decode_frames_to_device_light(const hm_file* f, const uint32_t* frames, int32_t count, const hm_decode_params* params, const hm_device_view* view,
@@ -1869,7 +1884,7 @@ int hm_decode_frames_to_device_light(const hm_file* f, const uint32_t* frames, i
 {
   if (failed_frame) *failed_frame = -1;
   if (!frames || !dests || !light) return hm_fail(HM_ERR_INVALID_ARG, "null argument");
-  return decode_sequence(f, frames, 0, count, params, nullptr, dests, view, out, failed_frame, nullptr, light);
+  return decode_sequence(f, frames, 0, count, params, nullptr, OutputTarget::to_dest(dests, view, light), out, failed_frame);
 }
 
 int hm_decode_frames_to_device_planes(const hm_file* f, const uint32_t* frames, int32_t count, const hm_decode_params* params, const hm_device_planes* planes,
@@ -1877,21 +1892,30 @@ int hm_decode_frames_to_device_planes(const hm_file* f, const uint32_t* frames, 
 {
   if (failed_frame) *failed_frame = -1;
   if (!frames || !planes) return hm_fail(HM_ERR_INVALID_ARG, "null argument");
-  return decode_sequence(f, frames, 0, count, params, nullptr, nullptr, nullptr, out, failed_frame, planes);
+  return decode_sequence(f, frames, 0, count, params, nullptr, OutputTarget::to_planes(planes), out, failed_frame);
 }
 
 // frames (NULL: first .. first + count - 1): the 1-based IDs of the frames, in any order, repeats allowed.
-// pdests (NULL, or `count` entries, without ddests): every frame's planar result goes to caller-owned device memory (hm_device_planes)
-// ddests (NULL, or `count` entries): every frame goes to caller-owned device memory; view (NULL, or with ddests or pdests): the same
-// rectangle of every frame, resampled, in one batched write behind the frames' conversions (hm_view_write_batch, hm_planes_view_write)
-// light (NULL, or with ddests): every frame's write runs the light step, frame by frame (hm_light_write) - no batched form
+// target: dest or planes are arrays of `count` entries, frame k's at [k] - every frame goes to caller-owned device memory; view: the same
+// rectangle of every frame, resampled, in one batched write behind the frames' conversions (hm_view_write_batch, hm_planes_view_write);
+// light: every frame's write runs the light step, frame by frame (hm_light_write) - no batched form
 static int decode_sequence(const hm_file* f, const uint32_t* frames, uint32_t first, int32_t count, const hm_decode_params* params, const hm_frame_dest* dests,
-                           const hm_device_dest* ddests, const hm_device_view* view, hm_decoded* out, int32_t* failed_frame, const hm_device_planes* pdests,
-                           const hm_device_light* light)
+                           const OutputTarget& target, hm_decoded* out, int32_t* failed_frame)
 {
+  const hm_device_dest* ddests = target.dest;
+  const hm_device_planes* pdests = target.planes;
+  const hm_device_view* view = target.view;
+  const hm_device_light* light = target.light;
+  auto target_of = [&](int k) { // frame k's own
+    OutputTarget t = target;
+    if (t.dest) t.dest += k;
+    if (t.planes) t.planes += k;
+    return t;
+  };
   if (failed_frame) *failed_frame = -1;
   if (!f || !params || !out) return hm_fail(HM_ERR_INVALID_ARG, "null argument");
   if (count <= 0) return hm_fail(HM_ERR_INVALID_ARG, "frame count %d", count);
+  if (const int src = target_check_shape(target)) return src;
   for (int k = 0; k < count; k++) std::memset(&out[k], 0, sizeof(out[k]));
   if (!f->file.is_movie()) return hm_fail(HM_ERR_INVALID_ARG, "the file is not an image sequence");
   const uint32_t n_frames = f->file.movie().frame_count;
@@ -1916,17 +1940,12 @@ static int decode_sequence(const hm_file* f, const uint32_t* frames, uint32_t fi
     if (view) // the view and each destination against the size the track declares (the decoded size: below), as hm_decode_item_to_device_view
       for (int k = 0; k < count; k++) {
         hm_image_info info;
-        if (hm_file_image_info(f, frame_id(k), &info) != HM_OK || info.width <= 0 || info.height <= 0) continue; // (such a frame fails below with its own message)
-        hm_view_plan vp;
-        hm_dest_plan dp;
-        int rc = hm_view_resolve(params->out_format, info.width, info.height, view, &vp);
-        if (!rc && !(rc = hm_dest_resolve(params->out_format, vp.ow, vp.oh, &ddests[k], &dp))) rc = hm_dest_check_len(&ddests[k], &dp);
+        if (hm_file_image_info(f, frame_id(k), &info) != HM_OK) continue; // (such a frame fails below with its own message)
+        const int rc = target_fits(params, target_of(k), info.width, info.height, info.chroma, info.bit_depth, 0, nullptr, false);
         if (rc) { if (failed_frame) *failed_frame = k; return rc; }
       }
-    int n_dev = 0;
-    if (hipGetDeviceCount(&n_dev) != hipSuccess || n_dev == 0) { (void)hipGetLastError(); return hm_fail(HM_ERR_NO_DEVICE, "no HIP device available"); }
-    for (int k = 0; k < count; k++) {
-      const int rc = hm_dest_check_pointer(&ddests[k]);
+    for (int k = 0; k < count; k++) { // a device, the pointers
+      const int rc = target_fits(params, target_of(k), 0, 0, 0, 0, 0, nullptr, true);
       if (rc) return rc;
     }
   }
@@ -1935,26 +1954,16 @@ static int decode_sequence(const hm_file* f, const uint32_t* frames, uint32_t fi
       const int rc = check_planes_params(params, &pdests[k]);
       if (rc) { if (failed_frame) *failed_frame = k; return rc; }
     }
-    std::vector<hm_planes_plan> plans((size_t)count);
-    std::vector<char> planned((size_t)count, 0);
-    for (int k = 0; k < count; k++) { // against what the track declares (the decoded pictures: below)
-      hm_image_info info;
-      if (hm_file_image_info(f, frame_id(k), &info) != HM_OK || info.width <= 0 || info.height <= 0 || info.bit_depth < 8 || info.bit_depth > 16 || info.chroma < 0 || info.chroma > 3) continue;
-      int rchroma, rbits;
-      planar_result_format(params, info.chroma, info.bit_depth, &rchroma, &rbits);
-      hm_planes_view_plan pv;
-      pv.ow = info.width; pv.oh = info.height;
-      int rc = view ? hm_planes_view_resolve(rchroma, info.width, info.height, view, &pv) : HM_OK;
-      if (!rc) rc = hm_planes_resolve(rchroma, rbits, pv.ow, pv.oh, 0, &pdests[k], &plans[k]); // (frames carry no alpha)
-      if (!rc) rc = hm_planes_check_len(&pdests[k], &plans[k]);
-      if (rc) { if (failed_frame) *failed_frame = k; return rc; }
-      planned[k] = 1;
-    }
-    int n_dev = 0;
-    if (hipGetDeviceCount(&n_dev) != hipSuccess || n_dev == 0) { (void)hipGetLastError(); return hm_fail(HM_ERR_NO_DEVICE, "no HIP device available"); }
-    for (int k = 0; k < count; k++) {
-      const int rc = planned[k] ? hm_planes_check_pointer(&pdests[k], &plans[k]) : HM_OK;
-      if (rc) { if (failed_frame) *failed_frame = k; return rc; }
+    std::vector<hm_image_info> declared((size_t)count); // against what the track declares (the decoded pictures: below); width 0: nothing usable
+    for (int pointers = 0; pointers < 2; pointers++) { // every frame's len before a device is asked for and the pointers are looked at
+      if (pointers)
+        if (const int rc = require_device()) return rc; // (names no frame)
+      for (int k = 0; k < count; k++) {
+        hm_image_info& info = declared[k];
+        if (!pointers && (hm_file_image_info(f, frame_id(k), &info) != HM_OK || info.bit_depth < 8 || info.bit_depth > 16 || info.chroma < 0 || info.chroma > 3)) info.width = 0;
+        const int rc = target_fits(params, target_of(k), info.width, info.height, info.chroma, info.bit_depth, 0, nullptr, pointers != 0); // (frames carry no alpha)
+        if (rc) { if (failed_frame) *failed_frame = k; return rc; }
+      }
     }
   }
   const bool planar_target = hm_out_is_planar(params->out_format);
@@ -1974,19 +1983,10 @@ static int decode_sequence(const hm_file* f, const uint32_t* frames, uint32_t fi
     if (rc) { if (failed_frame) *failed_frame = k; return rc; }
   }
   const bool few = count <= 64;
-  int nthreads = params->host_threads > 0 ? params->host_threads : 1;
-  const int row_threads = nthreads > count ? nthreads / count : 1;
-  if (nthreads > count) nthreads = count;
-  std::atomic<int> next{0};
-  auto worker = [&]() {
-    for (;;) {
-      const int k = next.fetch_add(1);
-      if (k >= count) break;
-      ItemPlan& P = F[k]->P;
-      parse_picture(f, P.tiles[0].id, few, params->strict_decoding, row_threads, P.blobs[0], P.status[0], P.messages[0]);
-    }
-  };
-  Crew::instance().run(nthreads, worker);
+  Crew::for_each(count, params->host_threads, [&](int k, int row_threads) {
+    ItemPlan& P = F[k]->P;
+    parse_picture(f, P.tiles[0].id, few, params->strict_decoding, row_threads, P.blobs[0], P.status[0], P.messages[0]);
+  });
   lap("sequence: host entropy decode done");
 
   // ---- every check that can fail on a frame's data, frame by frame in order, before anything is queued: the first broken
@@ -2003,56 +2003,22 @@ static int decode_sequence(const hm_file* f, const uint32_t* frames, uint32_t fi
     I.warnings = warn | (h->concealed_ctbs ? HM_WARN_CONCEALED : 0);
     I.w = h->width - h->crop_left - h->crop_right; I.h = h->height - h->crop_top - h->crop_bottom;
     I.chroma = h->chroma_format; I.bd = h->bit_depth_y; I.is_grid = false;
-    if (ddests) {
-      hm_dest_plan dp;
-      hm_view_plan vp;
-      vp.ow = I.w; vp.oh = I.h;
-      int drc = view ? hm_view_resolve(params->out_format, I.w, I.h, view, &vp) : HM_OK; // (against the frame's own decoded size)
-      if (!drc) drc = hm_dest_resolve(params->out_format, vp.ow, vp.oh, &ddests[k], &dp);
-      if (!drc) drc = hm_dest_check_len(&ddests[k], &dp);
-      if (!drc && light) { // (the profile and depth emit_image will report for this frame)
-        hm_light_plan lp;
-        const int obpp = hm_out_bytes_per_pixel(params->out_format);
-        const int bits = obpp >= 6 && I.bd == 8 ? 10 : I.bd;
-        drc = hm_light_resolve(params->out_format, bits, I.native.transfer == 2 ? 13 : I.native.transfer, I.native.primaries == 2 ? 1 : I.native.primaries, &ddests[k],
-                               light, &lp);
-      }
-      if (drc) return fail(drc);
-    }
-    if (pdests) { // the destination against the picture's own format: the check hm_planes_write repeats before its launch
-      hm_planes_plan pp;
-      int rchroma, rbits;
-      planar_result_format(params, I.chroma, I.bd, &rchroma, &rbits);
-      hm_planes_view_plan pv;
-      pv.ow = I.w; pv.oh = I.h;
-      int drc = view ? hm_planes_view_resolve(rchroma, I.w, I.h, view, &pv) : HM_OK; // (against the frame's own decoded size)
-      if (!drc) drc = hm_planes_resolve(rchroma, rbits, pv.ow, pv.oh, 0, &pdests[k], &pp);
-      if (!drc) drc = hm_planes_check_len(&pdests[k], &pp);
-      if (!drc) drc = hm_planes_check_pointer(&pdests[k], &pp);
+    if (ddests || pdests) { // against the frame's own decoded size and format, the light step against the profile and depth it will report;
+                            // planes with the pointers: the check hm_planes_write repeats before its launch
+      const Reported reported = converted_report(I.native, false, I.bd, params->out_format, params->convert_hdr_to_8bit);
+      const int drc = target_fits(params, target_of(k), I.w, I.h, I.chroma, I.bd, 0, &reported, pdests != nullptr);
       if (drc) return fail(drc);
     }
     if (planar_target) { // converted frame by frame behind the batch (emit_image); its refusals come here, before anything is queued
       if (I.chroma == 0 || I.chroma != hm_out_planar_chroma(params->out_format)) {
-        hm_colour_desc& cd = Fr.cd;
-        cd.width = I.w; cd.height = I.h; cd.bit_depth = I.bd; cd.chroma = I.chroma;
-        cd.has_nclx = 1; cd.matrix = I.native.matrix; cd.primaries = I.native.primaries; cd.full_range = I.native.full_range;
-        cd.out_format = params->out_format | (params->convert_hdr_to_8bit ? HM_OUT_YCBCR_8BIT : 0);
-        cd.chroma_upsampling = params->chroma_upsampling;
-        const int pipe = hm_colour_pipeline(&cd);
+        Fr.cd = colour_desc(params, I.w, I.h, I.bd, I.chroma, I.native, /*has_nclx=*/1, I.P, 0, /*planar_8bit=*/true); // (no planes yet: no strides)
+        const int pipe = hm_colour_pipeline(&Fr.cd);
         if (pipe < 0) return fail(pipe);
       }
     }
     else if (params->out_format) { // (the request job_enqueue hands to the conversion: a single image keeps its own nclx)
-      const int bps = I.bd > 8 ? 2 : 1, cw = I.chroma == 3 ? I.w : (I.w + 1) / 2;
-      hm_colour_desc& cd = Fr.cd;
-      cd.width = I.w; cd.height = I.h; cd.bit_depth = I.bd; cd.chroma = I.chroma;
-      cd.has_nclx = 1; cd.matrix = I.native.matrix; cd.primaries = I.native.primaries; cd.full_range = I.native.full_range;
-      cd.out_format = params->out_format;
-      cd.chroma_upsampling = params->chroma_upsampling;
-      cd.y_stride = hm_plane_stride(I.w, bps);
-      cd.cb_stride = cd.cr_stride = I.chroma ? hm_plane_stride(cw, bps) : 0;
-      cd.out_stride = hm_plane_stride(I.w, hm_out_bytes_per_pixel(params->out_format));
-      const int pipe = hm_colour_pipeline(&cd); // (the conversion's own refusal, with its message)
+      Fr.cd = colour_desc(params, I.w, I.h, I.bd, I.chroma, I.native, /*has_nclx=*/1, nullptr, hm_out_bytes_per_pixel(params->out_format));
+      const int pipe = hm_colour_pipeline(&Fr.cd); // (the conversion's own refusal, with its message)
       if (pipe < 0) return fail(pipe);
       Fr.attach = I.chroma != 0;
     }
@@ -2140,13 +2106,12 @@ static int decode_sequence(const hm_file* f, const uint32_t* frames, uint32_t fi
     SeqFrame& Fr = *F[k];
     hm_decode_params pk = *params;
     if (dests) { pk.ext_dst = dests[k].ext_dst; pk.ext_dst_len = dests[k].ext_dst_len; pk.ext_dst_stride = dests[k].ext_dst_stride; }
-    const bool viewed = view && ddests;
-    const bool pviewed = view && pdests;
-    const bool lit = light && ddests; // (written here, on the frame's own scratch entry: nothing is left for the batched write)
-    if ((rc = emit_image(&pk, s, Fr.I, nullptr, 0, Fr.dout, Fr.alpha_sdr, &out[k], ddests ? &ddests[k] : nullptr, viewed || pviewed ? view : nullptr,
-                         lit ? &view_blocks.sc[(size_t)k] : nullptr, viewed && !lit ? &view_items[(size_t)k] : nullptr, pdests ? &pdests[k] : nullptr,
-                         pviewed ? &planes_items[(size_t)k] : nullptr, lit ? light : nullptr))) {
-      if (failed_frame && (pviewed || lit)) *failed_frame = k;
+    OutputTarget t = target_of(k);
+    if (t.light) t.scratch = &view_blocks.sc[(size_t)k]; // (written here, on the frame's own scratch entry: nothing is left for the batched write)
+    else if (t.view && t.dest) t.view_later = &view_items[(size_t)k];
+    if (t.view && t.planes) t.planes_later = &planes_items[(size_t)k];
+    if ((rc = emit_image(&pk, s, Fr.I, nullptr, 0, Fr.dout, Fr.alpha_sdr, &out[k], t))) {
+      if (failed_frame && (t.planes_later || t.light)) *failed_frame = k;
       return release_all(rc);
     }
   }
@@ -2217,16 +2182,9 @@ void slab_enqueue(const hm_file* f, const hm_decode_params* params, Slab& S, uin
   int rc = planar_from_blobs(f, S.P, params, S.s, I, /*attach=*/true);
   trace_mark("  batch queued", S.row0);
   if (!rc) {
-    hm_colour_desc cd;
-    std::memset(&cd, 0, sizeof(cd));
-    cd.width = canvas_w; cd.height = S.h; cd.bit_depth = I.bd; cd.chroma = I.chroma;
-    cd.has_nclx = 0; // (a grid canvas carries no nclx: context.cc:2250-2276)
-    cd.matrix = I.native.matrix; cd.primaries = I.native.primaries; cd.full_range = I.native.full_range;
-    cd.out_format = params->out_format;
-    cd.chroma_upsampling = params->chroma_upsampling;
     const int obpp = hm_out_bytes_per_pixel(params->out_format);
-    cd.y_stride = I.P[0].stride; cd.cb_stride = I.P[1].stride; cd.cr_stride = I.P[2].stride;
-    cd.out_stride = hm_plane_stride(canvas_w, obpp);
+    // (a grid canvas carries no nclx: context.cc:2250-2276)
+    const hm_colour_desc cd = colour_desc(params, canvas_w, S.h, I.bd, I.chroma, I.native, /*has_nclx=*/0, I.P, obpp);
     if (I.rgb_attached) dout.swap(I.rgb); // (converted with the batch)
     else {
       rc = dout.alloc((size_t)cd.out_stride * mem_rows(S.h));
@@ -2405,23 +2363,10 @@ static int decode_grid_cut(const hm_file* f, uint32_t id, const hm_decode_params
   // ---- host: entropy-decode tiles [t0, t0 + n) (as hm_decode_item), all threads on them; the blobs go to their slab ----
   const int few = nt <= 64;
   int tile_warnings = 0, bd = 8, chroma = 1;
+  // (a cut grid has more tiles than threads: one thread per tile, whatever share of the crew for_each offers)
+  auto parse_tile = [&](int i) { parse_picture(f, plan.tiles[i].id, few != 0, params->strict_decoding, 1, plan.blobs[i], plan.status[i], plan.messages[i]); };
   auto parse_range = [&](int t_first, int t_n) -> int {
-    std::atomic<int> next{0};
-    auto worker = [&]() {
-      for (;;) {
-        const int i = t_first + next.fetch_add(1);
-        if (i >= t_first + t_n) break;
-        std::vector<uint8_t> data;
-        hm::HeifError e;
-        if (!f->file.hevc_data(plan.tiles[i].id, data, e)) { plan.status[i] = e.status; plan.messages[i] = e.message; continue; }
-        hm_parse_options po;
-        po.annexb = 0; po.threads = 1;
-        po.record_order = (few ? HM_RECORDS_SPLIT : HM_RECORDS_AUTO) | (params->strict_decoding ? 0 : HM_PARSE_CONCEAL);
-        const int prc = hm_hevc_parse_opts(data.data(), data.size(), &po, &plan.blobs[i].p, &plan.blobs[i].n);
-        if (prc) { plan.status[i] = prc; plan.messages[i] = hm_last_error(); }
-      }
-    };
-    Crew::instance().run(std::min(nthreads, t_n), worker);
+    Crew::for_each(t_n, nthreads, [&](int k, int) { parse_tile(t_first + k); });
     for (int i = t_first; i < t_first + t_n; i++)
       if (plan.status[i]) return hm_fail(plan.status[i], "tile %d (item %u): %s", i, plan.tiles[i].id, plan.messages[i].c_str());
     for (int i = t_first; i < t_first + t_n; i++)
@@ -2484,30 +2429,15 @@ static int decode_grid_cut(const hm_file* f, uint32_t id, const hm_decode_params
     try { queuer = std::thread(queue_slabs); }
     catch (...) {} // (no thread to be had: the slabs are queued behind the entropy decode, on this thread)
     {
-      std::atomic<int> next{0};
-      auto worker = [&]() {
-        for (;;) {
-          const int i = next.fetch_add(1);
-          if (i >= nt) break;
-          std::vector<uint8_t> data;
-          hm::HeifError e;
-          if (!f->file.hevc_data(plan.tiles[i].id, data, e)) { plan.status[i] = e.status; plan.messages[i] = e.message; }
-          else {
-            hm_parse_options po;
-            po.annexb = 0; po.threads = 1;
-            po.record_order = (few ? HM_RECORDS_SPLIT : HM_RECORDS_AUTO) | (params->strict_decoding ? 0 : HM_PARSE_CONCEAL);
-            const int prc = hm_hevc_parse_opts(data.data(), data.size(), &po, &plan.blobs[i].p, &plan.blobs[i].n);
-            if (prc) { plan.status[i] = prc; plan.messages[i] = hm_last_error(); }
-          }
-          const size_t k = slab_of_tile(i);
-          if (k < slabs.size()) {
-            bool full;
-            { std::lock_guard<std::mutex> lk(mu); full = ++done[k] >= slabs[k]->rows * plan.cols; }
-            if (full) cv.notify_one();
-          }
+      Crew::for_each(nt, nthreads, [&](int i, int) {
+        parse_tile(i);
+        const size_t k = slab_of_tile(i);
+        if (k < slabs.size()) {
+          bool full;
+          { std::lock_guard<std::mutex> lk(mu); full = ++done[k] >= slabs[k]->rows * plan.cols; }
+          if (full) cv.notify_one();
         }
-      };
-      Crew::instance().run(nthreads, worker);
+      });
     }
     if (queuer.joinable()) queuer.join();
     else queue_slabs(); // (every slab is complete by now: no wait)
@@ -2542,9 +2472,9 @@ static int decode_grid_cut(const hm_file* f, uint32_t id, const hm_decode_params
   // ---- what the decoded image says about itself (as job_enqueue for a converted grid canvas) ----
   out->width = img_w; out->height = img_h; out->bit_depth = bd; out->chroma = chroma;
   out->out_format = params->out_format;
-  out->has_nclx = 1; out->primaries = 1; out->transfer = 13; out->matrix = 6; out->full_range = 1;
-  if (bd == 8 && obpp >= 6) out->bit_depth = 10;
-  if (bd > 8 && (params->out_format == HM_OUT_RGB || params->out_format == HM_OUT_RGBA)) out->bit_depth = 8;
+  const Reported r = converted_report(hm::NclxProfile(), /*is_grid=*/true, bd, params->out_format, 0);
+  r.profile_to(out);
+  out->bit_depth = r.bit_depth;
   out->stride[0] = (int32_t)std::min<size_t>(dst_stride, 0x7FFFFFFF);
   out->plane_width[0] = img_w; out->plane_height[0] = img_h;
   out->warnings = tile_warnings;

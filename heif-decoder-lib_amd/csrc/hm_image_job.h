@@ -102,26 +102,65 @@ struct ItemPlan {
   std::vector<std::string> alpha_messages;
 };
 
+// Where the result of a decode goes beside hm_decoded: every function between an entry point and emit_image takes one of these.
+// All null: pinned host memory (or params->ext_dst).  The pointers are the caller's; target_check_shape states what goes together.
+struct OutputTarget {
+  const hm_device_dest* dest = nullptr;        // the interleaved pixels go to caller-owned device memory; nothing is copied to the host
+  const hm_device_view* view = nullptr;        // ... a rectangle of the image, resampled (with dest or planes)
+  const hm_device_planes* planes = nullptr;    // a planar result (out_format 0 / HM_OUT_YCBCR_*) goes to caller-owned device memory, plane by plane
+  const hm_device_light* light = nullptr;      // the light step in the write of dest
+  hm_view_scratch* scratch = nullptr;          // tap tables and the intermediate of the resampling step, the tables of the light step
+  hm_view_item* view_later = nullptr;          // view + dest: the view is not written, only described there - the caller writes it with those of other images
+  hm_planes_view_item* planes_later = nullptr; // the same for view + planes
+  static OutputTarget to_dest(const hm_device_dest* d, const hm_device_view* v = nullptr, const hm_device_light* l = nullptr)
+  {
+    OutputTarget t;
+    t.dest = d; t.view = v; t.light = l;
+    return t;
+  }
+  static OutputTarget to_planes(const hm_device_planes* p, const hm_device_view* v = nullptr)
+  {
+    OutputTarget t;
+    t.planes = p; t.view = v;
+    return t;
+  }
+};
+// dest xor planes (or neither); light only with dest; view only with one of the two; a *_later only with view and its own kind of destination
+int target_check_shape(const OutputTarget& t);
+
+// a job's own copies of the caller's structs (the pipeline outlives them; hm_decode_params keeps its layout, so they travel beside
+// the job's copy of it).  t points into the copies: a null pointer there means "not given".
+struct OwnedTarget {
+  hm_device_dest dest{};
+  hm_device_view view{};
+  hm_device_planes planes{};
+  hm_device_light light{};
+  OutputTarget t;
+  OwnedTarget() = default;
+  OwnedTarget(const OwnedTarget&) = delete;
+  OwnedTarget& operator=(const OwnedTarget&) = delete;
+  void set(const OutputTarget& from)
+  {
+    t = OutputTarget();
+    if (from.dest) { dest = *from.dest; t.dest = &dest; }
+    if (from.view) { view = *from.view; t.view = &view; }
+    if (from.planes) { planes = *from.planes; t.planes = &planes; }
+    if (from.light) { light = *from.light; t.light = &light; }
+  }
+};
+
 struct DecodeJob {
   const hm_file* f = nullptr;
   uint32_t id = 0;
   hm_decode_params params{};
-  hm_device_dest dest{};  // caller-owned device memory the pixels go to instead of pinned host memory (has_dest; hm_decode_params
-  bool has_dest = false;  // keeps its layout, so the destination travels beside the job's copy of it)
-  // a view of the image goes to the destination (hm_device_view): job_plan reduces item[0] to the sub-grid of tiles the crop touches
-  // where that changes no pixel - sub_tiles = its first tile row, row count, first tile column, column count in the whole grid -
-  // and the crop moves by the sub-grid's origin (view_dx, view_dy)
-  hm_device_view view{};
-  bool has_view = false;
+  // where the result goes (target.set): with a light step the item is decoded as one job, never slab by slab.
+  // With a view, job_plan reduces item[0] to the sub-grid of tiles the crop touches where that changes no pixel - sub_tiles = its
+  // first tile row, row count, first tile column, column count in the whole grid - and the crop moves by the sub-grid's origin
+  // (view_dx, view_dy)
+  OwnedTarget target;
   int view_dx = 0, view_dy = 0;
   int32_t sub_tiles[4] = {0, 0, 0, 0};
-  hm_view_scratch view_scratch{}; // tap tables and the intermediate of the resampling step, the tables of the light step
-  // a light step in the write of the destination (hm_device_light; with has_dest): the item is decoded as one job, never slab by slab
-  hm_device_light light{};
-  bool has_light = false;
-  // a planar result (out_format 0 / HM_OUT_YCBCR_*) goes to caller-owned device memory, plane by plane (has_planes; never together with has_dest)
-  hm_device_planes planes{};
-  bool has_planes = false;
+  hm_view_scratch view_scratch{}; // what job_enqueue hands to emit_image as the target's scratch
   bool self_grid = false; // item[0] is planned as the 1 x 1 grid of itself (ItemPlan::self_grid)
   hipStream_t s = nullptr;
   ItemPlan item[2];   // [0] the image, [1] its alpha auxiliary image
@@ -149,18 +188,11 @@ void job_parse_tile(DecodeJob& j, int k, int row_threads = 1); // k = 0 .. job_t
 // the entropy decode of one coded picture (hvc1 item or movie sample `id`) into `blob`, or its failure in status / message
 void parse_picture(const hm_file* f, uint32_t id, bool few_pictures, int strict, int row_threads, Blob& blob, int& status, std::string& message);
 int job_enqueue(DecodeJob& j, hm_decoded* out);
-// everything about a device destination that can be refused before the entropy decode: the request itself, the destination against
-// the size the file declares for the item, a device, the pointer (hm_image.cpp)
-// view (may be NULL): the destination is judged against the view's output size, the crop against the declared size
-// light (may be NULL): what of the light step depends on the request alone
-int check_device_request(const hm_file* f, uint32_t id, const hm_decode_params* params, const hm_device_dest* dest, const hm_device_view* view = nullptr,
-                         const hm_device_light* light = nullptr);
-// the same for a planar destination (hm_device_planes): the request, the planes against what hm_image_info declares (size, and the
-// result's chroma format and depth where the file decides them), a device, the pointers
-// view (may be NULL): the planes are judged against the view's output size, the crop against the declared size and the result's chroma format
-int check_planes_request(const hm_file* f, uint32_t id, const hm_decode_params* params, const hm_device_planes* planes, const hm_device_view* view = nullptr);
-// what of it needs no file: params (ext_dst, an interleaved target), the planes' static checks, null pointers of Y
-int check_planes_params(const hm_decode_params* params, const hm_device_planes* planes);
+// everything about a target (dest or planes, with its view and light step) that can be refused before the entropy decode: the request
+// itself, the target against what hm_image_info declares for the item (target_fits in hm_image.cpp: size, and for planes the result's
+// chroma format and depth where the file decides them; the crop of a view against the declared size, the destination against the
+// view's output size), a device, the pointers
+int check_target_request(const hm_file* f, uint32_t id, const hm_decode_params* params, const OutputTarget& t);
 int job_complete(DecodeJob& j, hm_decoded* out);
 
 } // namespace hm_img

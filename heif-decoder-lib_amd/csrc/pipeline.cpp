@@ -182,54 +182,50 @@ void hm_pipeline_destroy(hm_pipeline* p)
   delete p;
 }
 
-static int submit(hm_pipeline* p, const uint8_t* heif, size_t size, uint32_t item_id, uint64_t tag, const hm_device_dest* dest, const hm_device_view* view = nullptr,
-                  const hm_device_planes* planes = nullptr, const hm_device_light* light = nullptr);
+static int submit(hm_pipeline* p, const uint8_t* heif, size_t size, uint32_t item_id, uint64_t tag, const OutputTarget& target);
 
 int hm_pipeline_submit(hm_pipeline* p, const uint8_t* heif, size_t size, uint32_t item_id, uint64_t tag)
 {
   if (!p || !heif) return hm_fail(HM_ERR_INVALID_ARG, "null argument");
-  return submit(p, heif, size, item_id, tag, nullptr);
+  return submit(p, heif, size, item_id, tag, OutputTarget());
 }
 
 int hm_pipeline_submit_to_device(hm_pipeline* p, const uint8_t* heif, size_t size, uint32_t item_id, uint64_t tag, const hm_device_dest* dest)
 {
   if (!p || !heif || !dest) return hm_fail(HM_ERR_INVALID_ARG, "null argument");
-  return submit(p, heif, size, item_id, tag, dest);
+  return submit(p, heif, size, item_id, tag, OutputTarget::to_dest(dest));
 }
 
 int hm_pipeline_submit_to_device_view(hm_pipeline* p, const uint8_t* heif, size_t size, uint32_t item_id, uint64_t tag, const hm_device_view* view,
                                       const hm_device_dest* dest)
 {
   if (!p || !heif || !view || !dest) return hm_fail(HM_ERR_INVALID_ARG, "null argument");
-  return submit(p, heif, size, item_id, tag, dest, view);
+  return submit(p, heif, size, item_id, tag, OutputTarget::to_dest(dest, view));
 }
 
 int hm_pipeline_submit_to_device_light(hm_pipeline* p, const uint8_t* heif, size_t size, uint32_t item_id, uint64_t tag, const hm_device_view* view,
                                        const hm_device_light* light, const hm_device_dest* dest)
 {
   if (!p || !heif || !light || !dest) return hm_fail(HM_ERR_INVALID_ARG, "null argument");
-  return submit(p, heif, size, item_id, tag, dest, view, nullptr, light);
+  return submit(p, heif, size, item_id, tag, OutputTarget::to_dest(dest, view, light));
 }
 
 int hm_pipeline_submit_to_device_planes(hm_pipeline* p, const uint8_t* heif, size_t size, uint32_t item_id, uint64_t tag, const hm_device_planes* planes)
 {
   if (!p || !heif || !planes) return hm_fail(HM_ERR_INVALID_ARG, "null argument");
-  return submit(p, heif, size, item_id, tag, nullptr, nullptr, planes);
+  return submit(p, heif, size, item_id, tag, OutputTarget::to_planes(planes));
 }
 
 int hm_pipeline_submit_to_device_planes_view(hm_pipeline* p, const uint8_t* heif, size_t size, uint32_t item_id, uint64_t tag, const hm_device_view* view,
                                              const hm_device_planes* planes)
 {
   if (!p || !heif || !view || !planes) return hm_fail(HM_ERR_INVALID_ARG, "null argument");
-  return submit(p, heif, size, item_id, tag, nullptr, view, planes);
+  return submit(p, heif, size, item_id, tag, OutputTarget::to_planes(planes, view));
 }
 
-// dest (may be NULL): the image's pixels go to caller-owned device memory of the pipeline's device; view (may be NULL, with dest or planes):
-// a rectangle of them, resampled - job_plan then queues only the coded pictures the crop touches
-// planes (may be NULL, without dest): the planes of the pipeline's planar out_format go to caller-owned device memory
-// light (may be NULL, with dest): the light step in the write of the destination
-static int submit(hm_pipeline* p, const uint8_t* heif, size_t size, uint32_t item_id, uint64_t tag, const hm_device_dest* dest, const hm_device_view* view,
-                  const hm_device_planes* planes, const hm_device_light* light)
+// target: the image's pixels (dest) or the planes of the pipeline's planar out_format (planes) go to caller-owned device memory of the
+// pipeline's device; with a view, job_plan then queues only the coded pictures the crop touches
+static int submit(hm_pipeline* p, const uint8_t* heif, size_t size, uint32_t item_id, uint64_t tag, const OutputTarget& target)
 {
   hipStream_t stream = nullptr;
   {
@@ -258,24 +254,13 @@ static int submit(hm_pipeline* p, const uint8_t* heif, size_t size, uint32_t ite
     im->job.params.chroma_upsampling = p->cfg.chroma_upsampling;
     im->job.params.ignore_transformations = p->cfg.ignore_transformations;
     im->job.params.strict_decoding = p->cfg.strict_decoding;
-    if (dest) { // refused here, before anything is queued: the destination is not written
+    if (target.dest || target.planes) { // refused here, before anything is queued: the destination is not written
       int prev = -1;
       hipGetDevice(&prev);
-      hipSetDevice(p->cfg.device); // (the pointer must belong to the device the crew works on)
-      rc = check_device_request(im->file, im->job.id, &im->job.params, dest, view, light);
+      hipSetDevice(p->cfg.device); // (the pointers must belong to the device the crew works on)
+      rc = check_target_request(im->file, im->job.id, &im->job.params, target);
       if (prev >= 0) hipSetDevice(prev);
-      im->job.dest = *dest; im->job.has_dest = true;
-      if (view) { im->job.view = *view; im->job.has_view = true; }
-      if (light) { im->job.light = *light; im->job.has_light = true; }
-    }
-    if (planes) { // refused here, before anything is queued: no plane is written
-      int prev = -1;
-      hipGetDevice(&prev);
-      hipSetDevice(p->cfg.device);
-      rc = check_planes_request(im->file, im->job.id, &im->job.params, planes, view);
-      if (prev >= 0) hipSetDevice(prev);
-      im->job.planes = *planes; im->job.has_planes = true;
-      if (view) { im->job.view = *view; im->job.has_view = true; }
+      if (!rc) im->job.target.set(target);
     }
     if (!rc) rc = job_plan(im->job);
   }
