@@ -651,3 +651,193 @@ def sao_tiles():
             (27005, dict(deep, full_range=1, matrix=1)),
             (27006, dict(base, chroma_format=2, full_range=1, matrix=6)),
             (27007, dict(deep, chroma_format=2, full_range=0, matrix=9, primaries=9))]
+
+
+def rext_pcmf8(kw):
+    """8-bit pictures of the "pcmf" deblocking branch (see SIMD_BUILD_ONLY): held to the reference's default build from the deblocking stage on"""
+    return sao_class_pcmf8(kw)
+
+
+def _rext_settle(kw, pcmf8_family=False):
+    if kw.get("chroma_format", 1) != 3:
+        kw["cross_component"] = 0
+    if kw.get("pcm"):
+        kw.setdefault("pcm_bits_y", kw["bit_depth"])
+        kw.setdefault("pcm_bits_c", kw["bit_depth"])
+    if kw["bit_depth"] == 8 and not pcmf8_family:
+        kw.update(tq_bypass=0, pcm_loop_filter_disable=0)  # (the "pcmf" branch runs in a family of its own: see rext_residual_sweep)
+    if kw["log2_ctb"] == 4 and kw["bit_depth"] == 8 and kw.get("chroma_format", 1) in (1, 2):
+        kw["sao"] = 0  # (quirk Q9 is one of SAO on such pictures)
+    return kw
+
+
+def rext_residual_sweep(n, first_seed=28000):
+    """(seed, parameters) of a seeded sweep for the range-extension residual tools (tests/residual_ref.py holds them block by block:
+    implicit RDPCM, transform-skip rotation, cross-component prediction, PCM), pictures of 64x64 to 128x96 samples (128x128 where whole
+    32x32 blocks need full CTBs of 64).  Every picture carries rare syntax, so all of them go out in decode order (k_recon's rare
+    instances).  144 crossed cases over bit depth 8 / 10 / 12, the four chroma formats, CTB 16 / 32 / 64 and the tools - implicit RDPCM
+    in all of them, rotation, log2_max_transform_skip_block_size 2-5, transquant bypass, PCM, scaling lists, whole blocks, modes drawn
+    whole (mode_span: mode 10 is no most-probable mode) -, then ten aimed families (the first nine in turn, more of some of them and the tenth behind), each over the three depths and CTB sizes and, where
+    it draws whole blocks, over 32x32, 16x16 and 8x8 as the largest transform:
+      (0) whole 32x32 blocks (16x16 with CTB 16) of both skip kinds with levels over their whole range: RDPCM runs of 32;
+      (1) 4:4:4 with cross-component prediction over every luma kind, whole and split blocks;
+      (2) the same at 12 bit with every unit bypassed, whole 32x32 blocks and most levels at +-32767 (level_sat): |rY| up to 32 x 32767, the
+          one regime in which the reference's 32-bit shift pair can wrap, at |rY| >= 2^19;
+      (3) 8-bit 4:4:4 split pictures at a low QP with levels over their whole range: 4x4 transform-skip chroma blocks (the reference's
+          16-bit arm) under the largest luma residuals a 4x4 luma block can have;
+      (4) PCM of every size from 8x8 to 32x32 with PCM bit depths from 1 to the sample depth, next to bypass and ordinary units;
+      (5) scaling lists (pinned at 1 and 255 in places) together with skip and RDPCM blocks;
+      (6) 8 bit WITH transquant bypass and unfiltered PCM: the "pcmf" deblocking branch, on which the reference's two builds disagree
+          (see SIMD_BUILD_ONLY) - these pictures are held to its scalar build at the reconstruction stage and to its default build from
+          the deblocking stage on, and draw large levels only where they draw no transform skip (Q10 would make the builds differ at the
+          reconstruction stage too);
+      (7) every unit bypassed, levels over their whole range and many at +-32767 (level_sat): RDPCM run sums beyond 16 bits at every size, bypass luma under bypass chroma blocks
+          with a cross-component term (8 bit: as family 6, without transform skip);
+      (8) 4:4:4 with cross-component prediction and transform skip up to 32x32, modes drawn whole: skip chroma blocks with RDPCM under skip luma
+          blocks with RDPCM.
+      (9) transform skip up to 32x32 without bypass, full blocks of levels at +-32767 (level_sat) at 8 and 12 bit: RDPCM run sums of rounded skip
+          elements beyond 16 bits, and in 4:4:4 at 12 bit the shift pair wrapping behind skip luma blocks of 16x16 and 32x32.
+    Everywhere else 8-bit pictures run without bypass and with filtered PCM."""
+    out = []
+    for seed in range(first_seed, first_seed + n):
+        r = seed * 2654435761 % (1 << 32)
+        r = (r ^ (r >> 15)) * 2246822519 % (1 << 32)
+        r ^= r >> 13
+        i = seed - first_seed
+        pick = lambda k, opts: opts[(r >> k) % len(opts)]
+        fam = None
+        if i < 144:
+            kw = dict(bit_depth=[8, 10, 12][i % 3], chroma_format=[1, 3, 0, 2][(i // 3) % 4], log2_ctb=[5, 4, 6][(i // 12) % 3],
+                      width=pick(0, [64, 96, 128, 72]), height=pick(2, [64, 40, 96, 72]), qp=pick(4, [27, 22, 33, 38]), cu_qp_delta=1,
+                      rext_sps=pick(6, [4, 5, 7, 4 | 128, 5 | 32, 7]), log2_max_ts=pick(9, [5, 3, 4, 5, 0]), tq_bypass=pick(12, [0, 250, 0, 500]),
+                      pcm=pick(14, [0, 0, 200]), pcm_loop_filter_disable=seed % 2, no_split=pick(16, [0, 1, 0]), level_span=pick(18, [0, 300, 0, 1000]),
+                      scaling_list=pick(20, [0, 0, 2]), mode_span=pick(22, [0, 500, 800]), density=pick(24, [60, 100, 30]), wpp=pick(26, [0, 0, 1]),
+                      slices=pick(28, [0, 0, 100]), sign_hiding=pick(30, [1, 0]), cross_component=int(seed % 3 != 0))
+            kw.update(pcm_bits_y=max(1, kw["bit_depth"] - seed % 3), pcm_bits_c=max(1, kw["bit_depth"] - seed % 4))
+        else:
+            j = i - 144
+            fam, k = j % 9, j // 9
+            bd, ctb, cf = [8, 10, 12][k % 3], [5, 4, 6][(k // 3) % 3], [1, 3, 0, 2][(k // 9) % 4]
+            tb = [5, 4, 3][(k // 9) % 3]
+            fill = j >= 9 * 54
+            if fill:
+                # behind the nine families, more 4:4:4 pictures of whole blocks of families 7, 8 and 4 (in that order), two thirds of them 8 bit,
+                # CTB 32 / 64 before CTB 16: the cells of large blocks, which hold few blocks a picture
+                j -= 9 * 54
+                fam, k = [7, 8, 4][j % 3], j // 3
+                bd, ctb, cf, tb = [8, 10, 8, 12, 8][k % 5], [6, 5, 6, 4][(k // 5) % 4], 3, [4, 5, 3, 2][(k // 20) % 4]  # (2: a split picture)
+                if j >= 360:  # ... and behind those, families 8 and 7 at 8 bit alone, CTB 32 / 64
+                    j -= 360
+                    fam, k = [8, 7][j % 2], j // 2
+                    bd, ctb, tb = 8, [6, 5, 6][k % 3], [5, 4, 2, 3, 4, 3][(k // 3) % 6]
+                    if j >= 108:  # ... and last, family 9: 8 and 12 bit, every CTB size, the largest transform 16x16, 32x32, 4x4 (split pictures) and 8x8 in turn
+                        j -= 108
+                        fam, k = 9, j
+                        bd, ctb, tb, cf = [8, 12, 12][k % 3], [5, 6, 4][(k // 3) % 3], [4, 5, 2, 3][(k // 9) % 4], [3, 1, 3, 3][(k // 36) % 4]
+                        if k >= 144:  # (the one cell that 144 cases leave empty: 32x32 chroma skip blocks with RDPCM at 8 bit under CTB 64, 72 blocks a picture)
+                            bd, ctb, tb, cf = 8, 6, 5, 3
+            # whole blocks of 32x32, 16x16 and 8x8 in turn (the largest transform; CTB 16: 16x16 at most)
+            whole = dict(width=128, height=128 if ctb == 6 else 96, no_split=1, log2_max_tb=tb)
+            if ctb > 4 and whole["log2_max_tb"] == 5:
+                whole.update(width=192, height=128)  # (24 blocks of 32x32: mode 10 is one mode in 32 where modes are drawn whole)
+            kw = dict(bit_depth=bd, chroma_format=cf, log2_ctb=ctb, qp=pick(4, [27, 22, 33, 38]), cu_qp_delta=1, density=100)
+            if fam == 0:
+                kw.update(whole, rext_sps=[4, 5, 4 | 128][k % 3], log2_max_ts=5, level_span=[600, 1000][k % 2], level_sat=[0, 500][(k // 2) % 2], tq_bypass=[0, 400][(k // 2) % 2],
+                          mode_span=800, cross_component=(k // 4) % 2)
+            elif fam == 1:
+                kw.update(chroma_format=3, cross_component=1, rext_sps=[0, 4, 5, 7][k % 4], log2_max_ts=[5, 4, 0, 3][(k // 2) % 4], tq_bypass=[0, 300][(k // 4) % 2],
+                          mode_span=[0, 800][k % 2], level_span=[0, 300][(k // 2) % 2], width=[64, 96, 128][k % 3], height=[64, 96][(k // 3) % 2])
+                if k % 2:
+                    kw.update(whole)
+            elif fam == 2:
+                kw.update(whole, bit_depth=12, chroma_format=3, log2_ctb=[5, 6][k % 2], cross_component=1, rext_sps=4, tq_bypass=1000, level_span=1000, level_sat=[1000, 800][(k // 2) % 2],
+                          mode_span=[0, 0, 400][(k // 4) % 3], log2_max_tb=5, width=192, height=128)  # (without mode_span mode 26 is a most-probable mode everywhere)
+            elif fam == 3:
+                kw.update(bit_depth=8, chroma_format=3, cross_component=1, rext_sps=[5, 4, 7][k % 3], log2_max_ts=[0, 3][k % 2], qp=[1, 8, 17][(k // 2) % 3], level_span=[1000, 600][(k // 3) % 2],
+                          width=64, height=64, max_th_depth_intra=2)
+            elif fam == 4:
+                kw.update(pcm=[300, 500, 800][k % 3], pcm_log2_max=[5, 3, 4][(k // 2) % 3], pcm_log2_min=3, pcm_bits_y=1 + (k * 5) % bd, pcm_bits_c=1 + (k * 7 + 3) % bd,
+                          pcm_loop_filter_disable=k % 2, tq_bypass=[200, 0][(k // 3) % 2], rext_sps=[4, 0, 5][(k // 2) % 3], cross_component=k % 2, width=[96, 128, 64][k % 3],
+                          height=[64, 96][(k // 3) % 2], no_split=(k // 2) % 2)
+                if kw["pcm_log2_max"] < min(ctb, 5):
+                    kw["no_split"] = 0  # (whole coding units would be larger than the largest PCM unit: a picture without rare syntax after all)
+                if (k // 9) % 2:
+                    kw.update(pcm_bits_y=[1, bd][k % 2], pcm_bits_c=[bd, 1][k % 2])
+                if fill:
+                    kw.update(whole, log2_max_tb=5, pcm=900, pcm_log2_max=5, pcm_log2_min=[5, 3][k % 2], width=128, height=128, no_split=int(ctb < 6))  # (a PCM unit is 32x32 at most)
+            elif fam == 5:
+                kw.update(scaling_list=[2, 3][k % 2], scaling_span=500, rext_sps=[5, 4, 7][k % 3], log2_max_ts=[5, 4][(k // 2) % 2], level_span=[0, 300, 1000][(k // 2) % 3],
+                          tq_bypass=[0, 200][(k // 4) % 2], mode_span=[800, 0][(k // 3) % 2], cross_component=k % 2, no_split=(k // 3) % 2, width=[96, 128][k % 2], height=[64, 96][(k // 2) % 2])
+            elif fam == 7:
+                kw.update(chroma_format=[3, 1, 3, 2, 0][(k // 9) % 5], cross_component=1, rext_sps=[4, 5][k % 2], tq_bypass=1000, level_span=1000, level_sat=[600, 1000][k % 2],
+                          mode_span=[800, 400][(k // 2) % 2], width=[64, 96][k % 2], height=64)
+                if ((k // 27) % 2 == 0 or k % 2) if not fill else tb > 2:
+                    kw.update(whole)
+                if bd == 8:
+                    kw.update(transform_skip=0)
+            elif fam == 8:
+                kw.update(chroma_format=3, cross_component=1, rext_sps=[4, 5][k % 2], log2_max_ts=5, mode_span=800, level_span=[0, 300][(k // 2) % 2], width=[64, 96][k % 2], height=64)
+                if ((k // 27) % 2 == 0 or k % 2) if not fill else tb > 2:
+                    kw.update(whole)
+            elif fam == 9:
+                kw.update(cross_component=1, rext_sps=[4, 5][k % 2], log2_max_ts=5, level_span=1000, level_sat=[1000, 700][(k // 2) % 2], mode_span=[0, 800][(k // 4) % 2],
+                          width=64, height=64)
+                if tb > 2:
+                    kw.update(whole)
+            else:
+                kw.update(bit_depth=8, log2_ctb=[5, 4, 6][k % 3], chroma_format=[1, 3, 0, 2, 3][(k // 3) % 5], tq_bypass=[300, 600, 1000][k % 3], pcm=[300, 0, 500][(k // 2) % 3],
+                          pcm_loop_filter_disable=1, pcm_bits_y=[8, 5, 1][(k // 3) % 3], pcm_bits_c=[7, 8, 2][(k // 4) % 3], rext_sps=[4, 5, 7][(k // 2) % 3], log2_max_ts=[5, 0, 4][k % 3],
+                          cross_component=1, mode_span=[800, 0][(k // 2) % 2], no_split=(k // 4) % 2, width=[96, 128, 64][k % 3], height=[64, 96][(k // 3) % 2])
+                if kw["no_split"]:
+                    kw.update(width=128, height=128 if kw["log2_ctb"] == 6 else 96)
+                if k % 2:  # no transform skip at all: large levels are then safe (Q10 is one of 8-bit 4x4 transform-skip blocks) - bypass run sums beyond 16 bits
+                    kw.update(transform_skip=0, level_span=1000)
+        out.append((seed, _rext_settle(kw, pcmf8_family=fam == 6 or (fam == 7 and kw["bit_depth"] == 8))))
+    return out
+
+
+def rext_residual_single_ctb_cases(n_per_shape=36, first_seed=32000):
+    """(seed, parameters) of pictures of ONE CTB whose first transform block of every component predicts the constant 1 << (bit_depth - 1): its
+    samples are clip(that + residual), the residual of the range-extension tools alone.  The shapes of single_ctb_cases (first block 4x4, 8x8,
+    16x16, and 32x32 with CTB 32 and CTB 64), every bit depth and chroma format, log2_max_transform_skip_block_size up to 5, rotation on and
+    off, cross-component prediction, PCM, transquant bypass - at 8 bit too: these pictures have no loop filters (sao = 0, deblocking disabled),
+    so the "pcmf" branch on which the reference's builds disagree does not exist in them."""
+    shapes = [dict(width=8, height=8, log2_ctb=4, no_split=0), dict(width=8, height=8, log2_ctb=4, no_split=1),
+              dict(width=16, height=16, log2_ctb=4, no_split=1), dict(width=32, height=32, log2_ctb=5, no_split=1),
+              dict(width=64, height=64, log2_ctb=6, no_split=1)]
+    out = []
+    seed = first_seed
+    for shape in shapes:
+        for k in range(n_per_shape):
+            r = seed * 2654435761 % (1 << 32)
+            r = (r ^ (r >> 15)) * 2246822519 % (1 << 32)
+            r ^= r >> 13
+            pick = lambda s, opts: opts[(r >> s) % len(opts)]
+            bd = [8, 10, 12][k % 3]
+            kw = dict(shape, bit_depth=bd, chroma_format=[1, 3, 2, 0][(k // 3) % 4], qp=pick(3, [1, 17, 26, 35, 44, 51]), density=100, cu_qp_delta=1, diff_cu_qp_delta_depth=0,
+                      level_span=pick(6, [0, 120, 400, 1000]), rext_sps=[4, 5, 7][(k // 12) % 3], log2_max_ts=pick(9, [5, 5, 3]), tq_bypass=pick(11, [0, 0, 300, 1000]),
+                      cross_component=k % 2, pcm=pick(14, [0, 0, 300]), pcm_bits_y=1 + (k * 5) % bd, pcm_bits_c=1 + (k * 7 + 3) % bd, pcm_loop_filter_disable=k % 2,
+                      mode_span=pick(16, [0, 800]), scaling_list=pick(18, [0, 0, 2]), sao=0, deblock_disable=1, sign_hiding=pick(20, [1, 0]))
+            if kw["chroma_format"] != 3:
+                kw["cross_component"] = 0
+            out.append((seed, kw))
+            seed += 1
+    return out
+
+
+def rext_residual_lock_pictures():
+    """pictures whose every CTB row is full of whole 32x32 blocks with residuals (no_split, density 100), 64x128 with CTB 32 and 128x192 with CTB 64:
+    in k_recon every wave of a workgroup takes the workgroup's one 32x32 staging area for such a block - nothing smaller has two waves contend"""
+    base = dict(no_split=1, density=100, cu_qp_delta=1, rext_sps=5, log2_max_ts=5, mode_span=800)
+    return [(30000, dict(base, width=64, height=128, log2_ctb=5, bit_depth=8, chroma_format=3, cross_component=1, qp=27)),
+            (30001, dict(base, width=128, height=192, log2_ctb=6, bit_depth=10, chroma_format=3, cross_component=1, tq_bypass=300, qp=30, level_span=300)),
+            (30002, dict(base, width=128, height=192, log2_ctb=6, bit_depth=12, chroma_format=1, tq_bypass=300, qp=33))]
+
+
+def rext_residual_tiles():
+    """four 192 x 144 tiles with the range-extension residual tools, through the full path"""
+    base = dict(width=SAO_TILE_W, height=SAO_TILE_H, cu_qp_delta=1, sao=1, density=60, log2_max_ts=5)
+    return [(31000, dict(base, log2_ctb=5, bit_depth=8, chroma_format=3, cross_component=1, rext_sps=5, qp=27)),
+            (31001, dict(base, log2_ctb=6, bit_depth=10, chroma_format=3, cross_component=1, rext_sps=7, tq_bypass=200, qp=30, level_span=300)),
+            (31002, dict(base, log2_ctb=4, bit_depth=12, chroma_format=1, rext_sps=4, tq_bypass=200, pcm=200, pcm_bits_y=9, pcm_bits_c=7, pcm_loop_filter_disable=1, qp=33)),
+            (31003, dict(base, log2_ctb=5, bit_depth=10, chroma_format=2, rext_sps=5, pcm=200, pcm_bits_y=10, pcm_bits_c=8, scaling_list=2, qp=25, no_split=1))]

@@ -192,7 +192,7 @@ def predict(rec, planes, pic):
                                     constant=bool((line == line[0]).all()))
             used = smooth_bilinear(line, nT) if bil else smooth_121(line)
             ev["smoothing"] = "bilinear" if bil else "121"
-    edge_filters = not ((pic.flags & rr.PIC_IMPLICIT_RDPCM) and rec["bypass"])
+    edge_filters = not rr.bypass_unit_of_rdpcm_picture(rec, pic.flags)  # (the flag that also makes the unit's levels run sums)
     pred, ev["edge"], ev["edge_clip_lo"], ev["edge_clip_hi"] = predict_from_line(used, mode, nT, cidx, bd, edge_filters)
     if ev["edge"] is None and mode in (1, 10, 26):
         ev["edge"] = "not_chroma" if cidx else "not_32"
@@ -202,26 +202,46 @@ def predict(rec, planes, pic):
     return pred, ev
 
 
-def observable(rec, pic):
-    """whether the picture holds the block's prediction: without a residual (and outside PCM, and without a cross-component
-    term) as it is; with one where residual_ref.residual() restates the unit"""
-    if rec["pcm"]:
-        return False
-    if (pic.flags & rr.PIC_CROSS_COMPONENT) and rec["cidx"] and rec["qpy"] != 0:
-        return False
-    if not rec["cbf"]:
-        return True
-    if (pic.flags & rr.PIC_IMPLICIT_RDPCM) and (rec["tskip"] or rec["bypass"]) and rec["mode"] in (10, 26):
-        return False
+def res_scale(rec, pic):
+    """ResScaleVal of a chroma record (hm_stream.h: chroma records of a cross-component picture carry it in place of QpY)"""
+    return rec["qpy"] if (pic.flags & rr.PIC_CROSS_COMPONENT) and rec["cidx"] and not rec["pcm"] else 0
+
+
+def observable(rec, pic, carry=None):
+    """whether the block's samples can be computed from its record and its neighbours: without a residual the picture holds the
+    prediction itself; with one residual_ref restates the unit - transforms, skip and bypass (residual), implicit RDPCM
+    (unit_residual), PCM (pcm_block).  A chroma block with a cross-component term needs the luma residual of its transform unit:
+    observable where the walk carries it along (carry: a residual_ref.LumaCarry fed by expected_block in decode order)."""
+    if res_scale(rec, pic) != 0:
+        return carry is not None
     return True
 
 
-def expected_block(rec, planes, pic):
-    """(expected samples of an observable block, events); events["rail_lo" / "rail_hi"]: clip(pred + residual) acted"""
+def expected_block(rec, planes, pic, carry=None, quirks=rr.REFERENCE, pcm_bits=None):
+    """(expected samples of an observable block, events); events["rail_lo" / "rail_hi"]: clip(pred + residual) acted;
+    events["tools"]: the events of residual_ref's range-extension tools (own / ccp / pcm, each a dict or None, and luma: the events
+    of the luma block under a cross-component term).  carry: see observable(); with it every record of the picture must pass
+    through here in decode order.  pcm_bits: (luma, chroma) PCM bit depths where the caller knows them."""
+    tools = dict(own=None, ccp=None, pcm=None, luma=None)
+    if rec["pcm"]:
+        v, tools["pcm"] = rr.pcm_block(rec, pic.bit_depth, None if pcm_bits is None else pcm_bits[1 if rec["cidx"] else 0])
+        if carry is not None and rec["cidx"] == 0:
+            carry.keep(rec, None, None)
+        return v, dict(mode=None, rail_lo=False, rail_hi=False, tools=tools)
     pred, ev = predict(rec, planes, pic)
     ev["rail_lo"] = ev["rail_hi"] = False
+    ev["tools"] = tools
+    r = None
     if rec["cbf"]:
-        r, _ = rr.residual(rec, pic.bit_depth, pic.scaling, pic.flags)
+        r, tools["own"] = rr.unit_residual(rec, pic.bit_depth, pic.scaling, pic.flags, quirks)
+    if carry is not None and rec["cidx"] == 0:
+        carry.keep(rec, r, tools["own"])
+    scale = res_scale(rec, pic)
+    if scale != 0:
+        assert pic.chroma_format == 3 and carry is not None
+        r_luma, tools["luma"] = carry.luma_of(rec)
+        r, tools["ccp"] = rr.cross_component(r, tools["own"], r_luma, scale, pic.bit_depth, pic.bit_depth_c, quirks)
+    if r is not None:
         s = pred + r
         mx = (1 << pic.bit_depth) - 1
         ev["rail_lo"], ev["rail_hi"] = bool((s < 0).any()), bool((s > mx).any())

@@ -26,27 +26,34 @@ def describe(seed, rec, ev):
             f"smoothing {ev['smoothing']} edge {ev['edge']}")
 
 
-def first_mismatch(seed, P, planes, note=None):
-    """None, or a description of the first observable block of `planes` (reconstruction stage, one array per component) that is
-    not what intra_ref predicts from the block's neighbours IN THESE PLANES (plus residual_ref's residual).  note(rec, ev,
-    observable) is called for every block that is not PCM."""
+def first_mismatch(seed, P, planes, note=None, quirks=rr.REFERENCE, tools_note=None, pcm_bits=None):
+    """None, or a description of the first block of `planes` (reconstruction stage, one array per component) that is not what
+    intra_ref predicts from the block's neighbours IN THESE PLANES plus residual_ref's residual - implicit RDPCM and the
+    cross-component term included: the walk carries the luma residual of the current transform unit along, so every block is
+    observable - or, for a PCM block, not the record's samples.  note(rec, ev, observable) is called for every block that is
+    not PCM; tools_note(rec, ev) for every block, PCM included (ev["tools"]: residual_ref's range-extension events).  pcm_bits:
+    (luma, chroma) PCM bit depths where the caller knows them (the shift is then restated)."""
     planes = [p.astype(np.int64) for p in planes]
+    carry = rr.LumaCarry()
     for rec in P.records():
-        if rec["pcm"]:
-            continue
-        obs = ir.observable(rec, P)
-        if not obs and note is None:
-            continue
-        exp, ev = ir.expected_block(rec, planes, P) if obs else ir.predict(rec, planes, P)
-        if note is not None:
+        obs = ir.observable(rec, P, carry)
+        assert obs
+        exp, ev = ir.expected_block(rec, planes, P, carry, quirks, pcm_bits)
+        if note is not None and not rec["pcm"]:
             note(rec, ev, obs)
-        if not obs:
-            continue
+        if tools_note is not None:
+            tools_note(rec, ev)
         nT = 1 << rec["log2"]
         got = planes[rec["cidx"]][rec["y"]:rec["y"] + nT, rec["x"]:rec["x"] + nT]
         if not np.array_equal(got, exp):
             y, x = np.argwhere(got != exp)[0]
-            return f"{describe(seed, rec, ev)}: {int((got != exp).sum())} samples differ, first (y,x)=({y},{x}) got {int(got[y, x])} expected {int(exp[y, x])}"
+            what = f"seed {seed} component {rec['cidx']} PCM block (x,y)=({rec['x']},{rec['y']}) {nT}x{nT}" if rec["pcm"] else describe(seed, rec, ev)
+            t = ev["tools"]
+            if t["own"]:
+                what += f" {t['own']['kind']} rdpcm {t['own']['rdpcm']}" + (" rotated" if t["own"]["rotated"] else "")
+            if t["ccp"]:
+                what += f" scale {t['ccp']['scale']} over luma {rr.luma_kind(t['luma'])}"
+            return f"{what}: {int((got != exp).sum())} samples differ, first (y,x)=({y},{x}) got {int(got[y, x])} expected {int(exp[y, x])}"
     return None
 
 

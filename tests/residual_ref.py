@@ -12,7 +12,9 @@ unbounded integers the difference is written out:
     (242 = the largest sum of |weights| over a column of the DST matrix), so that clip never acts - residual() asserts it.
     The DCT's second stage does leave 16 bits at 10 and 12 bit (event "stage2_beyond_int16").
 
-Not restated here (the sweep against the reference decoder holds them): implicit RDPCM, cross-component prediction, PCM.
+The range-extension residual tools follow behind residual(): implicit RDPCM (unit_residual), cross-component prediction
+(cross_component, with LumaCarry for the luma residual of the current transform unit) and PCM (pcm_block); the reference's
+deviations there sit behind the switches of Quirks.
 
 The records are those of a command stream in decode order (include/hm_stream.h: hm_tu, 16 bytes)."""
 import struct
@@ -176,8 +178,8 @@ def dequantise(rec, bit_depth, scaling, events):
 
 
 def residual(rec, bit_depth, scaling=None, pic_flags=0):
-    """(residual[y, x] as int64, events) of a record with a residual.  Not for implicit-RDPCM blocks, PCM or chroma blocks
-    with a cross-component term."""
+    """(residual[y, x] as int64, events) of a record with a residual.  Not for implicit-RDPCM blocks (unit_residual), PCM
+    (pcm_block) or the cross-component term of a chroma block (cross_component)."""
     assert rec["cbf"] and not rec["pcm"]
     nT, log2 = 1 << rec["log2"], rec["log2"]
     pos = rec["levels"]["pos"].astype(np.int64)
@@ -221,3 +223,165 @@ def residual(rec, bit_depth, scaling=None, pic_flags=0):
     else:
         ev["stage2_beyond_int16"] = beyond
     return r, ev
+
+
+# ---- the range-extension residual tools: implicit RDPCM, cross-component prediction, PCM ------------------------------------
+# Written from 7.3.8.12, 8.6.2, 8.6.6, 8.6.8 and 8.4.4.1 of the standard (v2 and later) and, where the reference does something
+# else, from its scalar code (transform.cc:251-285, 427-466, 566-643; fallback-dct.cc:173-299; slice.cc:3774-3805, 4462-4504).
+#
+# Which inverse transforms the reference takes in a cross-component picture: ALL blocks that are neither skipped nor bypassed,
+# luma and chroma alike, go through its "explicit" variants (transform.cc:658-663 -> 288-336: transform_idst_4x4 /
+# transform_idct_NxN into an int32 buffer, fallback-dct.cc:511-550, 737-878).  They clip the first stage to 16 bits like the
+# adding variants and leave the second stage unclipped - for the DCT that is what residual() does anyway (Q4), for the DST the
+# missing clip is one that never acts (residual() asserts it), so residual() restates both.
+class Quirks:
+    """the reference's deviations from the standard's unbounded integers in these tools, each behind a switch (all on: the
+    reference).
+      res16            8-bit 4x4 transform-skip residuals - the block's own values, its RDPCM run sums and, for chroma, the sum
+                       with the cross-component term - are stored through int16 (transform.cc:577-607: residual_luma16,
+                       rdpcm_h16 / rdpcm_v16, cross_comp_pred16)
+      shift_pair_int32 (rY << BitDepthC) >> BitDepthY is taken in a 32-bit int (transform.cc:264-265): it wraps for
+                       |rY| >= 2^(31 - BitDepthC)"""
+
+    def __init__(self, res16=True, shift_pair_int32=True):
+        self.res16, self.shift_pair_int32 = res16, shift_pair_int32
+
+
+REFERENCE = Quirks()
+RES_SCALE_VALUES = (-8, -4, -2, -1, 1, 2, 4, 8)  # 7.4.9.12: (1 << (log2_res_scale_abs_plus1 - 1)) * (1 - 2 * sign)
+
+
+def int16_store(v):
+    """an int64 value as an int16_t holds it"""
+    return ((np.asarray(v, np.int64) + 32768) & 0xFFFF) - 32768
+
+
+def bypass_unit_of_rdpcm_picture(rec, pic_flags):
+    """implicit_rdpcm_enabled_flag && cu_transquant_bypass_flag: the ONE flag that both turns the levels of a mode 10 / 26 block
+    into run sums (8.6.2) and suppresses the boundary filters of those two modes (8.4.4.2.6: disableIntraBoundaryFilter;
+    intrapred.cc:323-326) - intra_ref.predict reads it here"""
+    return bool(pic_flags & PIC_IMPLICIT_RDPCM) and rec["bypass"]
+
+
+def rdpcm_direction(rec, pic_flags):
+    """None, "h" (mode 10: along rows) or "v" (mode 26: along columns) - slice.cc:3774-3779; intra pictures: implicit only"""
+    if not rec["cbf"] or rec["pcm"] or rec["mode"] not in (10, 26):
+        return None
+    if bypass_unit_of_rdpcm_picture(rec, pic_flags) or (bool(pic_flags & PIC_IMPLICIT_RDPCM) and rec["tskip"]):
+        return "v" if rec["mode"] == 26 else "h"
+    return None
+
+
+def unit_residual(rec, bit_depth, scaling=None, pic_flags=0, quirks=REFERENCE):
+    """(the block's OWN residual [y, x] as int64 - before any cross-component term -, events) of a record with levels, implicit
+    RDPCM included.  events beyond those of residual(): rdpcm (None / "h" / "v"), rotated (the 4x4 rotation acted on this
+    block), run_beyond_int16 (an RDPCM run sum left -32768 .. 32767), res16 (the block takes the reference's 16-bit arm),
+    res16_acts (the int16 store changed a value)."""
+    assert rec["cbf"] and not rec["pcm"]
+    nT, log2 = 1 << rec["log2"], rec["log2"]
+    direction = rdpcm_direction(rec, pic_flags)
+    skipping = rec["bypass"] or rec["tskip"]
+    if direction is None:
+        r, ev = residual(rec, bit_depth, scaling, pic_flags)
+    else:
+        # 8.6.2 / 8.6.6 + 8.6.8: the rotation acts on the array of levels / scaled coefficients FIRST (transform.cc:446-448,
+        # 574-576), a transform-skip element is rounded on its own, ((d << tsShift) + rnd) >> bdShift, and only then do the
+        # elements accumulate along the direction of the prediction (fallback-dct.cc:173-255)
+        pos = rec["levels"]["pos"].astype(np.int64)
+        ev = dict(wrap=False, clip_hi=False, clip_lo=False, stage1_clip=False, stage2_beyond_int16=False)
+        ev["dc_only"] = bool(len(pos) and (pos == 0).all())
+        ev["top_left_only"] = bool(len(pos) and ((pos % nT < 4) & (pos // nT < 4)).all())
+        ev["last_group"] = bool(((pos % nT >= nT - 4)).any() and ((pos // nT >= nT - 4)).any())
+        if rec["bypass"]:
+            ev["kind"] = "bypass"
+            e = np.zeros(nT * nT, np.int64)
+            e[pos] = rec["levels"]["value"].astype(np.int64)
+            e = e.reshape(nT, nT)
+        else:
+            ev["kind"] = "tskip"
+            e = dequantise(rec, bit_depth, scaling, ev)
+        if (pic_flags & PIC_TS_ROTATION) and nT == 4:
+            e = e[::-1, ::-1]
+        if not rec["bypass"]:
+            bd_shift = 20 - bit_depth
+            e = (wrap32(e << (5 + log2)) + (1 << (bd_shift - 1))) >> bd_shift
+        r = np.cumsum(e, axis=1 if direction == "h" else 0)
+    ev["rdpcm"] = direction
+    ev["rotated"] = bool(skipping and (pic_flags & PIC_TS_ROTATION) and nT == 4)
+    ev["run_beyond_int16"] = bool(direction is not None and ((r > 32767) | (r < -32768)).any())
+    ev["res16"] = bool(rec["tskip"] and not rec["bypass"] and bit_depth == 8 and nT == 4)
+    ev["res16_acts"] = False
+    if ev["res16"] and quirks.res16:
+        t = int16_store(r)
+        ev["res16_acts"] = bool((t != r).any())
+        r = t
+    return r, ev
+
+
+def luma_kind(ev):
+    """the kind of a luma block as the census of the cross-component term names it"""
+    return ev["kind"] + ("_rdpcm" if ev["rdpcm"] else "")
+
+
+def cross_component(own, own_ev, r_luma, scale, bit_depth_y, bit_depth_c, quirks=REFERENCE):
+    """7.3.8.12 / 8.6.6: (own + ((ResScaleVal * ((rY << BitDepthC) >> BitDepthY)) >> 3), events).  own: the chroma block's own
+    residual, or None for a block without levels (slice.cc:3797-3805: the term alone); own_ev: its events or None.  The shift pair
+    is the reference's int32 one (quirk shift_pair_int32); >> 3 is an arithmetic shift: it rounds a negative product towards minus
+    infinity.  Events: scale, neg_odd (the >> 3 acted on a negative product that is no multiple of 8: a division would round
+    otherwise), wrap (the shift pair wrapped), res16_acts (the 16-bit arm's store of the sum changed a value)."""
+    assert scale in RES_SCALE_VALUES
+    r_luma = np.asarray(r_luma, np.int64)
+    exact = (r_luma << bit_depth_c) >> bit_depth_y
+    taken = (wrap32(r_luma << bit_depth_c) >> bit_depth_y) if quirks.shift_pair_int32 else exact
+    prod = scale * taken
+    term = prod >> 3
+    ev = dict(scale=scale, neg_odd=bool(((prod < 0) & (prod & 7 != 0)).any()), wrap=bool((wrap32(r_luma << bit_depth_c) != (r_luma << bit_depth_c)).any()),
+              res16_acts=False)
+    r = term if own is None else own + term
+    if own_ev is not None and own_ev["res16"] and quirks.res16:  # cross_comp_pred16: the sum goes back into the int16 buffer
+        t = int16_store(r)
+        ev["res16_acts"] = bool((t != r).any())
+        r = t
+    return r, ev
+
+
+class LumaCarry:
+    """tctx->residual_luma while a picture's records are walked in decode order: the residual of the luma block of the current
+    transform unit.  In 4:4:4 - the one format with cross-component prediction - the chroma records of a unit follow its luma record
+    and have its position and size."""
+
+    def __init__(self):
+        self.rec = self.r = self.ev = None
+
+    def keep(self, rec, r, ev):
+        """after a luma record: r / ev of unit_residual, or None where the block has no levels"""
+        self.rec, self.r, self.ev = rec, r, ev
+
+    def luma_of(self, rec):
+        """(residual, events) of the luma block under a chroma record with a non-zero ResScaleVal; asserts what the syntax
+        promises: 7.3.8.12 sends a scale only behind a luma block with cbf_luma, and never (the product's parser refuses it, Q17)
+        behind an 8-bit 4x4 transform-skip luma block, whose residual the reference keeps in another buffer (transform.cc:581)"""
+        L = self.rec
+        assert L is not None and L["cidx"] == 0 and (L["x"], L["y"], L["log2"]) == (rec["x"], rec["y"], rec["log2"]), "a scale without its luma block"
+        assert L["cbf"] and self.r is not None, "a scale behind a luma block without cbf (7.3.8.12)"
+        assert not self.ev["res16"], "Q17: a scale behind an 8-bit 4x4 transform-skip luma block"
+        return self.r, self.ev
+
+
+def pcm_block(rec, bit_depth, pcm_bits=None):
+    """8.4.4.1 (v2+: 8.4.4.1 "decoding process for PCM samples"): recSamples = pcm_sample << (BitDepth - PcmBitDepth), nT x nT in
+    raster order.  The record holds the shifted values; with pcm_bits known the shift is restated: every value is a multiple of
+    1 << shift and at most ((1 << pcm_bits) - 1) << shift.  (samples [y, x] as int64, events)"""
+    assert rec["pcm"]
+    nT = 1 << rec["log2"]
+    assert len(rec["levels"]) == nT * nT and (rec["levels"]["pos"] == np.arange(nT * nT)).all()
+    v = rec["levels"]["value"].astype(np.int64).reshape(nT, nT)
+    assert v.min() >= 0 and v.max() < (1 << bit_depth)
+    ev = dict(size=nT, zero=bool((v == 0).any()), top=False, shift=None)
+    if pcm_bits is not None:
+        assert 1 <= pcm_bits <= bit_depth
+        shift = bit_depth - pcm_bits
+        top = ((1 << pcm_bits) - 1) << shift
+        assert (v % (1 << shift) == 0).all() and v.max() <= top, "PCM samples: not pcm_sample << (BitDepth - PcmBitDepth)"
+        ev.update(top=bool((v == top).any()), shift=shift)
+    return v, ev

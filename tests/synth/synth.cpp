@@ -201,6 +201,11 @@ struct SynthParams {
   // --- SAO at the ends of its tables (0 = the draws of the streams above, byte for byte) ---
   int32_t sao_span;            // per-mille chance, drawn once per offset, that sao_offset_abs is the largest the bit depth allows (every bin of its
                                // truncated-unary code 1), and, once per band position, that sao_band_position is 29, 30 or 31 (bands that wrap)
+  // --- run sums of saturated levels (0 = the draws of the streams above, byte for byte) ---
+  int32_t level_sat;           // per-mille chance that a level drawn whole under level_span is the largest a conforming stream may carry (|level| =
+                               // 32767 less its base level), and, drawn once per block, that the block is full: the last position far out, every
+                               // sub-block coded, every coefficient significant, three signs in four positive - long runs of saturated levels
+                               // of one sign, for the sums of implicit RDPCM
 };
 
 // entropy-coder adaptor for SliceWalker: chooses every bin, encodes it, returns it
@@ -350,13 +355,20 @@ class EncoderEC {
       case K_CHROMA_QP_OFFSET_FLAG: return rng_.chance(600);
       case K_RES_SCALE_ABS: return (idx & 256) ? 0 : rng_.chance(idx == 0 ? 600 : 500); // (bit 8: a unit the product refuses with a scale, Q17)
       case K_LAST_PREFIX:
+        if (P.level_sat) {
+          if ((idx & 255) == 0) full_block_ = rng_.chance(P.level_sat);
+          if (full_block_) return 1;
+        }
         if (P.level_span) { // per coordinate: at the origin (DC-only blocks: half of the draws), as ever, or far out (the last group of four)
           if ((idx & 255) == 0) last_bias_ = (int)(rng_.next() % 4);
           return rng_.chance(last_bias_ <= 1 ? 60 : (last_bias_ == 2 ? 520 : 930));
         }
         return rng_.chance(520);
-      case K_CSBF: return rng_.chance(5 * d);
-      case K_SIG: return rng_.chance(4 * d + 50);
+      case K_CSBF: return (P.level_sat && full_block_) ? 1 : rng_.chance(5 * d);
+      case K_SIG: return (P.level_sat && full_block_) ? 1 : rng_.chance(4 * d + 50);
+      case K_SIGN:
+        if (P.level_sat && full_block_) return !rng_.chance(750);
+        return (int)(rng_.next() & 1);
       // (level_span: a remaining level is coded only behind greater1 [and greater2 for the first such level of a sub-block])
       case K_GT1: return rng_.chance(P.level_span ? 700 : 300);
       case K_GT2: return rng_.chance(P.level_span ? 700 : 300);
@@ -385,6 +397,7 @@ class EncoderEC {
               const int bits = 1 + (int)(rng_.next() % 15);                       // 1 .. 15
               calr_ = (int)(rng_.next() & ((1u << bits) - 1)) | (1 << (bits - 1)); // that many significant bits
               if (calr_ > 32767 - 3) calr_ = 32767 - 3;
+              if (P.level_sat && rng_.chance(P.level_sat)) calr_ = 32767 - 3;
               // 9.3.3.11: prefix and suffix of that value at this Rice parameter
               if ((calr_ >> rice) < 4) { calr_prefix_ = calr_ >> rice; calr_suffix_ = calr_ & ((1 << rice) - 1); }
               else {
@@ -420,7 +433,7 @@ class EncoderEC {
   ContextSet cs_;
   // values drawn whole and written bin by bin (qp_span, level_span)
   int qp_abs_ = 0, last_bias_ = 1;
-  bool calr_run_ = false, cu_calm_ = false, sao_full_ = false;
+  bool calr_run_ = false, cu_calm_ = false, sao_full_ = false, full_block_ = false;
   int sao_wrap_ = 0;
   int calr_ = -1, calr_pos_ = 0, calr_prefix_ = 0, calr_suffix_ = 0;
 };

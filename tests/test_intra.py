@@ -31,6 +31,7 @@ STAGES = (("recon", orc.REF_F_NO_DEBLOCK | orc.REF_F_NO_SAO, 0), ("deblock", orc
 # synthesiser, and the same with both knobs in place
 STREAMS_BEFORE_CALM = "439cd0a6b5f619d907d29857dd1c36d068e00349efc87ed6d3b3b9727b11169a"
 STREAMS_BEFORE_SAO_SPAN = "6103057603e7c4743e1536ad593c6fb68dd5085003eef6a937259337a63136f5"  # (taken at the commit before the knob)
+STREAMS_BEFORE_LEVEL_SAT = "64663fc9c93d9b0e964b33425235dbfbee0226607bcc5d8ea09a90fcd5fdc6f2"  # (taken with the synthesiser of the commit before the knob)
 
 
 def _fp(planes):
@@ -62,6 +63,15 @@ def test_new_knobs_leave_every_existing_stream_alone_and_act():
     assert h.hexdigest() == STREAMS_BEFORE_SAO_SPAN
     assert synthutil.picture(5, width=64, height=64, sao_span=500) != synthutil.picture(5, width=64, height=64)
     assert synthutil.picture(5, width=64, height=64, sao_span=500, sao=0) == synthutil.picture(5, width=64, height=64, sao=0)
+    # the knob level_sat (whole blocks of saturated levels of one sign, for RDPCM run sums) came with the range-extension residual corpora: the streams of the SAO corpora too.
+    # This pin covers the corpora that the two pins above do not; the three together are the guarantee that every earlier stream is byte-identical
+    h = hashlib.sha256()
+    for sweep in (corpus.sao_sweep(660)[::8], corpus.sao_small_cases()[::10], corpus.sao_tiles()):
+        for seed, kw in sweep:
+            h.update(synthutil.picture(seed, **kw))
+    assert h.hexdigest() == STREAMS_BEFORE_LEVEL_SAT
+    assert synthutil.picture(5, width=64, height=64, level_span=1000, level_sat=800) != synthutil.picture(5, width=64, height=64, level_span=1000)
+    assert synthutil.picture(5, width=64, height=64, level_sat=800) != synthutil.picture(5, width=64, height=64)  # (full blocks without level_span too)
 
 
 @pytest.fixture(scope="module")

@@ -16,6 +16,11 @@ and the reference decoder build oracle/_ref):
   tests/golden/sao.json     (`make_fixtures.py sao`, and only that sub-command) fingerprints of all four stages (none, deblocking, SAO alone, both) for
                             corpus.sao_sweep / sao_small_cases / sao_tiles: the reference's scalar build, its default build for 8-bit pictures of the
                             "pcmf" branch; with it profiles/sao_census.txt, the census of tests/saoutil.py
+  tests/golden/rext_residual.json (`make_fixtures.py rext`, and only that sub-command) fingerprints of the three stages for corpus.rext_residual_sweep /
+                            rext_residual_single_ctb_cases / rext_residual_lock_pictures / rext_residual_tiles: the reference's scalar build, its default build from
+                            the deblocking stage on for 8-bit pictures of the "pcmf" branch, and which pictures its builds decode differently at the
+                            reconstruction stage; with it profiles/rext_residual_census.txt, the census of tests/rextutil.py (the model must reproduce
+                            the reference's planes block by block: asserted)
 """
 import json
 import os
@@ -242,8 +247,65 @@ def sao():
     print("sao:", len(cases), "pictures,", C.samples, "samples; required cells still empty:", missing)
 
 
+def rext():
+    """the range-extension residual corpora: fingerprints of the reference decoder at the three stages, which pictures its default build reconstructs otherwise
+    (the class of the first differing block per plane), and the census of tests/rextutil.py taken with residual_ref / intra_ref on the reference's planes"""
+    import collections
+    import numpy as np
+    import corpus
+    import intrautil as iu
+    import residual_ref as rr
+    import rextutil as xu
+    import synthutil
+    import __graft_entry__ as g
+    capi = g.load_package().capi
+    cases, C, classes, differing = {}, xu.Census(), collections.Counter(), []
+    todo = dict(xu.corpora(), tiles=corpus.rext_residual_tiles())
+    for name, lst in todo.items():
+        for seed, kw in lst:
+            data = synthutil.picture(seed, **kw)
+            P = rr.Picture(capi.parse_hevc(data, record_order=xu.DECODE_ORDER))
+            assert str(seed) not in cases
+            entry = {"stream_fnv": f"{orc.load().orc_fnv1a64(data, len(data), 0):016x}"}
+            for stage, flags, bits in xu.STAGES:
+                planes, _ = orc.ref_decode(data, flags | xu.ref_build(name, kw, bits))
+                entry[stage] = fingerprint(planes)
+                if bits:
+                    continue
+                if name != "tiles":
+                    cls = xu.kernel_class(P)
+                    C.count_syntax(cls, P)
+                    bad = iu.first_mismatch(seed, P, planes, tools_note=C.noter(cls), pcm_bits=xu.pcm_bits(kw))
+                    assert bad is None, f"{kw}: the model is not the reference decoder: {bad}"
+                simd, _ = orc.ref_decode(data, flags)
+                if any(not np.array_equal(a, b) for a, b in zip(simd, planes)):
+                    assert not xu.default_build_holds(name, kw), f"seed {seed} {kw}: a picture held to the default build differs from the scalar one at the reconstruction stage"
+                    differing.append(seed)
+                    origin = set()
+                    for rec in P.records():  # per plane, the first block in decode order in which a sample differs
+                        nT = 1 << rec["log2"]
+                        a, b = (p[rec["cidx"]][rec["y"]:rec["y"] + nT, rec["x"]:rec["x"] + nT] for p in (simd, planes))
+                        if rec["cidx"] not in origin and not np.array_equal(a, b):
+                            origin.add(rec["cidx"])
+                            kind = "pcm" if rec["pcm"] else "no residual" if not rec["cbf"] else "bypass" if rec["bypass"] else \
+                                "transform skip" if rec["tskip"] else "DST" if nT == 4 and rec["cidx"] == 0 else "DCT"
+                            classes[f"{P.bit_depth}-bit {nT}x{nT} {kind}"] += 1
+            cases[str(seed)] = entry
+    out = {"sweep_cases": xu.N_SWEEP, "cases": cases,
+           "simd_vs_scalar": {"stage": "recon", "cases": len(cases), "cases_that_differ": len(differing), "seeds": differing,
+                              "first_blocks_that_differ_by_class": dict(sorted(classes.items()))}}
+    json.dump(out, open(os.path.join(ROOT, "tests", "golden", "rext_residual.json"), "w"), indent=0, sort_keys=True, separators=(",", ":"))
+    open(os.path.join(ROOT, "profiles", "rext_residual_census.txt"), "w").write(C.table())
+    missing = [(cls, kind, nT) + cell for cls in xu.CLASSES for kind in xu.KINDS for nT in xu.SIZES for cell in xu.required(cls, kind, nT) if not C.seen(cls, kind, nT, cell)]
+    print("rext:", len(cases), "pictures,", C.blocks, "blocks;", len(differing), "decoded differently by the default build:", dict(sorted(classes.items())),
+          "; required cells still empty:", missing)
+
+
 if __name__ == "__main__":
-    if sys.argv[1:] == ["sao"]:
+    if sys.argv[1:] == ["rext"]:
+        sys.path.insert(0, ROOT)
+        rext()
+    elif sys.argv[1:] == ["sao"]:
         sys.path.insert(0, ROOT)
         sao()
     elif sys.argv[1:] == ["deblock"]:
