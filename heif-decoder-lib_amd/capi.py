@@ -172,6 +172,24 @@ class DeviceLight(C.Structure):
 HM_LIGHT_LINEAR = 8
 
 
+class DeviceTone(C.Structure):
+    """hm_device_tone: the BT.2390 curve inside a light step - peaks and units in cd/m2 (src_peak 0 = the image's own, unit_nits 0 =
+    10000 for PQ, out_unit_nits 0 = dst_peak), out_bits 8 = the 8-bit finish"""
+    _fields_ = [("curve", C.c_int32), ("out_bits", C.c_int32), ("src_peak", C.c_float), ("dst_peak", C.c_float), ("unit_nits", C.c_float),
+                ("out_unit_nits", C.c_float), ("reserved", C.c_int32 * 2)]
+
+
+HM_TONE_BT2390 = 1
+HM_TONE_STEPS = 2048
+
+
+class LightLevels(C.Structure):
+    """hm_light_levels: the raw fields of an item's clli and mdcv properties"""
+    _fields_ = [("has_clli", C.c_int32), ("has_mdcv", C.c_int32), ("max_content_light_level", C.c_uint16), ("max_pic_average_light_level", C.c_uint16),
+                ("display_primaries_x", C.c_uint16 * 3), ("display_primaries_y", C.c_uint16 * 3), ("white_point_x", C.c_uint16), ("white_point_y", C.c_uint16),
+                ("max_display_mastering_luminance", C.c_uint32), ("min_display_mastering_luminance", C.c_uint32)]
+
+
 class OverlayInfo(C.Structure):
     """hm_overlay_info"""
     _fields_ = [("canvas_width", C.c_int32), ("canvas_height", C.c_int32), ("n_children", C.c_int32), ("background", C.c_uint16 * 4)]
@@ -265,6 +283,16 @@ def bind_image(L):
                                      C.c_void_p]
     L.hm_light_table.argtypes = [C.c_int, C.c_int, C.c_float, C.c_int, C.POINTER(C.c_float)]
     L.hm_light_matrix.argtypes = [C.c_int, C.c_int, C.POINTER(C.c_float * 9)]
+    L.hm_decode_item_to_device_tone.argtypes = [C.c_void_p, C.c_uint32, C.POINTER(DecodeParams), C.POINTER(DeviceView), C.POINTER(DeviceLight), C.POINTER(DeviceTone),
+                                                C.POINTER(DeviceDest), C.POINTER(Decoded)]
+    L.hm_decode_frames_to_device_tone.argtypes = [C.c_void_p, C.POINTER(C.c_uint32), C.c_int32, C.POINTER(DecodeParams), C.POINTER(DeviceView), C.POINTER(DeviceLight),
+                                                  C.POINTER(DeviceTone), C.POINTER(DeviceDest), C.POINTER(Decoded), C.POINTER(C.c_int32)]
+    L.hm_pipeline_submit_to_device_tone.argtypes = [C.c_void_p, C.c_char_p, C.c_size_t, C.c_uint32, C.c_uint64, C.POINTER(DeviceView), C.POINTER(DeviceLight),
+                                                    C.POINTER(DeviceTone), C.POINTER(DeviceDest)]
+    L.hm_tone_to_tensor.argtypes = [C.c_int, C.c_int, C.c_int, C.c_int, C.c_void_p, C.c_int, C.POINTER(DeviceView), C.POINTER(DeviceLight), C.POINTER(DeviceTone),
+                                    C.POINTER(DeviceDest), C.c_void_p]
+    L.hm_tone_table.argtypes = [C.POINTER(DeviceTone), C.c_float, C.c_int, C.POINTER(C.c_float)]
+    L.hm_file_item_light_levels.argtypes = [C.c_void_p, C.c_uint32, C.POINTER(LightLevels)]
     L.hm_device_planes_bytes.argtypes = [C.c_int, C.c_int, C.c_int, C.c_int, C.POINTER(DevicePlanes), C.POINTER(C.c_int64 * 4)]
     L.hm_device_planes_bytes.restype = C.c_int64
     L.hm_planes_to_tensor.argtypes = [C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, C.POINTER(C.c_void_p * 4), C.POINTER(C.c_int32 * 4), C.POINTER(DevicePlanes),

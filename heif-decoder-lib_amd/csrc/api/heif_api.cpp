@@ -84,6 +84,9 @@ struct heif_image {
   std::vector<std::pair<heif_error_code, heif_suberror_code>> warnings; // pixelimage.h: m_warnings
   uint32_t icc_type = 0;       // raw colour profile ('prof' / 'rICC'), copied from the file
   std::vector<uint8_t> icc;
+  heif_content_light_level clli{};              // pixelimage.h: m_clli, m_mdcv, m_mdcv_set
+  heif_mastering_display_colour_volume mdcv{};
+  bool mdcv_set = false;
 };
 
 namespace {
@@ -360,6 +363,19 @@ struct heif_error heif_decode_image(const struct heif_image_handle* in, struct h
     uint32_t t = 0; const uint8_t* p = nullptr; size_t n = 0;
     if (hm_file_item_icc(in->ctx->file, in->id, 0, &t, &p, &n) == HM_OK && t) { img->icc_type = t; img->icc.assign(p, p + n); }
   }
+  { // ... and so do the clli / mdcv properties of the item that was decoded (context.cc:2087-2103)
+    hm_light_levels ll;
+    if (hm_file_item_light_levels(in->ctx->file, in->id, &ll) == HM_OK) {
+      if (ll.has_clli) { img->clli.max_content_light_level = ll.max_content_light_level; img->clli.max_pic_average_light_level = ll.max_pic_average_light_level; }
+      if (ll.has_mdcv) {
+        for (int c = 0; c < 3; c++) { img->mdcv.display_primaries_x[c] = ll.display_primaries_x[c]; img->mdcv.display_primaries_y[c] = ll.display_primaries_y[c]; }
+        img->mdcv.white_point_x = ll.white_point_x; img->mdcv.white_point_y = ll.white_point_y;
+        img->mdcv.max_display_mastering_luminance = ll.max_display_mastering_luminance;
+        img->mdcv.min_display_mastering_luminance = ll.min_display_mastering_luminance;
+        img->mdcv_set = true;
+      }
+    }
+  }
   if (dec.warnings & HM_WARN_UNKNOWN_PRIMARIES) img->warnings.emplace_back(heif_error_Invalid_input, heif_suberror_Unknown_NCLX_color_primaries);
   if (dec.warnings & HM_WARN_UNKNOWN_TRANSFER) img->warnings.emplace_back(heif_error_Invalid_input, heif_suberror_Unknown_NCLX_transfer_characteristics);
   if (dec.warnings & HM_WARN_UNKNOWN_MATRIX) img->warnings.emplace_back(heif_error_Invalid_input, heif_suberror_Unknown_NCLX_matrix_coefficients);
@@ -403,6 +419,41 @@ uint8_t* heif_image_get_plane(struct heif_image* i, enum heif_channel ch, int* o
   return const_cast<uint8_t*>(heif_image_get_plane_readonly(i, ch, out_stride));
 }
 void heif_image_release(const struct heif_image* i) { delete i; }
+
+// ---- content light level, mastering display colour volume (heif.cc:1248-1339) ----
+int heif_image_has_content_light_level(const struct heif_image* i)
+{
+  return i && (i->clli.max_content_light_level != 0 || i->clli.max_pic_average_light_level != 0);
+}
+void heif_image_get_content_light_level(const struct heif_image* i, struct heif_content_light_level* out) { if (i && out) *out = i->clli; }
+void heif_image_set_content_light_level(const struct heif_image* i, const struct heif_content_light_level* in)
+{
+  if (i && in) const_cast<heif_image*>(i)->clli = *in;
+}
+int heif_image_has_mastering_display_colour_volume(const struct heif_image* i) { return i && i->mdcv_set; }
+void heif_image_get_mastering_display_colour_volume(const struct heif_image* i, struct heif_mastering_display_colour_volume* out) { if (i && out) *out = i->mdcv; }
+void heif_image_set_mastering_display_colour_volume(const struct heif_image* i, const struct heif_mastering_display_colour_volume* in)
+{
+  if (!i || !in) return;
+  const_cast<heif_image*>(i)->mdcv = *in;
+  const_cast<heif_image*>(i)->mdcv_set = true;
+}
+struct heif_error heif_mastering_display_colour_volume_decode(const struct heif_mastering_display_colour_volume* in,
+                                                              struct heif_decoded_mastering_display_colour_volume* out)
+{
+  if (!in || !out) return err(heif_error_Usage_error, heif_suberror_Null_pointer_argument, "NULL passed");
+  auto coord = [](uint16_t v, int most) { return v < 5 || v > most ? 0.0f : (float)(v * 0.00002); };
+  for (int c = 0; c < 3; c++) {
+    out->display_primaries_x[c] = coord(in->display_primaries_x[c], 37000);
+    out->display_primaries_y[c] = coord(in->display_primaries_y[c], 42000);
+  }
+  out->white_point_x = coord(in->white_point_x, 37000);
+  out->white_point_y = coord(in->white_point_y, 42000);
+  const uint32_t hi = in->max_display_mastering_luminance, lo = in->min_display_mastering_luminance;
+  out->max_display_mastering_luminance = hi < 50000u || hi > 100000000u ? 0.0 : hi * 0.0001;
+  out->min_display_mastering_luminance = lo < 1u || lo > 50000u ? 0.0 : lo * 0.0001;
+  return ok();
+}
 struct heif_error heif_image_create(int width, int height, enum heif_colorspace cs, enum heif_chroma chroma, struct heif_image** out)
 {
   if (!out) return err(heif_error_Usage_error, heif_suberror_Null_pointer_argument, "NULL passed");

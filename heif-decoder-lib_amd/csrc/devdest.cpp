@@ -731,10 +731,11 @@ int hm_light_matrix(int from_primaries, int to_primaries, float m[9])
   return HM_OK;
 }
 
-int hm_light_check_static(int out_format, const hm_device_dest* d, const hm_device_light* l, int explicit_from)
+// dest_format: the target the destination is judged by (hm_tone_dest_format; out_format without a tone step)
+static int light_check(int out_format, int dest_format, const hm_device_dest* d, const hm_device_light* l, int explicit_from)
 {
   if (!l) return hm_fail(HM_ERR_INVALID_ARG, "null light step");
-  int rc = hm_dest_check_static(out_format, d);
+  int rc = hm_dest_check_static(dest_format, d);
   if (rc) return rc;
   if (l->reserved[0] || l->reserved[1] || l->reserved[2]) return hm_fail(HM_ERR_INVALID_ARG, "light: reserved is not 0");
   if (!std::isfinite(l->gain) || !(l->gain > 0.0f)) return hm_fail(HM_ERR_INVALID_ARG, "light: gain %g is not finite and above 0", (double)l->gain);
@@ -751,10 +752,14 @@ int hm_light_check_static(int out_format, const hm_device_dest* d, const hm_devi
   return HM_OK;
 }
 
-int hm_light_resolve(int out_format, int bits, int img_transfer, int img_primaries, const hm_device_dest* d, const hm_device_light* l, hm_light_plan* lp)
+int hm_light_check_static(int out_format, const hm_device_dest* d, const hm_device_light* l, int explicit_from)
 {
-  int rc = hm_light_check_static(out_format, d, l, 0);
-  if (rc) return rc;
+  return light_check(out_format, out_format, d, l, explicit_from);
+}
+
+// the plan of a light step whose static checks have passed (light_check)
+static int light_plan_of(int out_format, int dest_format, int bits, int img_transfer, int img_primaries, const hm_device_light* l, hm_light_plan* lp)
+{
   std::memset(lp, 0, sizeof(*lp));
   lp->from_transfer = l->from_transfer ? l->from_transfer : img_transfer;
   lp->from_primaries = l->from_primaries ? l->from_primaries : img_primaries;
@@ -766,10 +771,135 @@ int hm_light_resolve(int out_format, int bits, int img_transfer, int img_primari
   if (sb == 1) bits = 8;
   if (bits < 8 || bits > HM_LIGHT_MAX_BITS) return hm_fail(HM_ERR_UNSUPPORTED, "light: samples of %d bits (8 .. %d are supported)", bits, (int)HM_LIGHT_MAX_BITS);
   lp->bits = bits;
+  lp->enc_bits = bits; lp->dest_format = dest_format;
   lp->encode = lp->to_transfer != HM_LIGHT_LINEAR;
   lp->matrix = lp->to_primaries != lp->from_primaries;
   lp->gain = l->gain;
   return hm_light_matrix(lp->from_primaries, lp->to_primaries, lp->m);
+}
+
+int hm_light_resolve(int out_format, int bits, int img_transfer, int img_primaries, const hm_device_dest* d, const hm_device_light* l, hm_light_plan* lp)
+{
+  const int rc = light_check(out_format, out_format, d, l, 0);
+  return rc ? rc : light_plan_of(out_format, out_format, bits, img_transfer, img_primaries, l, lp);
+}
+
+// ---- the tone step (hm_device_tone) ----------------------------------------------------------------------------------------------
+
+namespace {
+
+// the inverse of light_of_code(16, .): ST 2084, y = 1.0 at 10000 cd/m2
+double pq_of_light(double y)
+{
+  const double m1 = 2610.0 / 16384.0, m2 = 2523.0 / 4096.0 * 128.0, c1 = 3424.0 / 4096.0, c2 = 2413.0 / 4096.0 * 32.0, c3 = 2392.0 / 4096.0 * 32.0;
+  const double p = std::pow(y, m1);
+  return std::pow((c1 + c2 * p) / (1.0 + c3 * p), m2);
+}
+
+bool nits_ok(float v) { return std::isfinite(v) && v > 0.0f && v <= 10000.0f; }
+
+// KS of the curve src -> dst (cd/m2): the knee start in units of the source's PQ peak
+double tone_knee(double src_peak, double dst_peak) { return 1.5 * (pq_of_light(dst_peak / 10000.0) / pq_of_light(src_peak / 10000.0)) - 0.5; }
+
+// thr[HM_TONE_STEPS], then sg[HM_TONE_STEPS] (include/heif_mi355x.h); every argument resolved
+void fill_tone_tables(double g, double src_peak, double dst_peak, double U, double Uo, float* thr, float* sg)
+{
+  const int n = HM_TONE_STEPS;
+  const double top = (double)(n - 1);
+  if (thr) {
+    thr[0] = 0.0f;
+    for (int i = 1; i < n; i++) thr[i] = (float)(g * (10000.0 / U) * light_of_code(16, ((double)i - 0.5) / top));
+  }
+  if (!sg) return;
+  const double Pw = pq_of_light(src_peak / 10000.0), maxLum = pq_of_light(dst_peak / 10000.0) / Pw, KS = 1.5 * maxLum - 0.5;
+  for (int k = 0; k < n; k++) {
+    const double e = (double)k / top, E1 = std::min(e / Pw, 1.0);
+    double ratio = 1.0;
+    if (!(maxLum >= 1.0 || E1 < KS || k == 0)) {
+      const double T = (E1 - KS) / (1.0 - KS), T2 = T * T, T3 = T2 * T;
+      const double E2 = (2.0 * T3 - 3.0 * T2 + 1.0) * KS + (T3 - 2.0 * T2 + T) * (1.0 - KS) + (-2.0 * T3 + 3.0 * T2) * maxLum;
+      ratio = light_of_code(16, E2 * Pw) / light_of_code(16, e);
+    }
+    sg[k] = (float)(ratio * U / Uo);
+  }
+}
+
+// the tone step's own refusals; defaults: src_peak and unit_nits may be 0 (resolved against the image later)
+int tone_check(const hm_device_tone* t, bool defaults)
+{
+  if (t->curve != HM_TONE_BT2390) return hm_fail(HM_ERR_INVALID_ARG, "tone: unknown curve %d", t->curve);
+  if (t->reserved[0] || t->reserved[1]) return hm_fail(HM_ERR_INVALID_ARG, "tone: reserved is not 0");
+  if (!(defaults && t->src_peak == 0.0f) && !nits_ok(t->src_peak))
+    return hm_fail(HM_ERR_INVALID_ARG, "tone: src_peak %g is not finite, above 0 and at most 10000", (double)t->src_peak);
+  if (!nits_ok(t->dst_peak)) return hm_fail(HM_ERR_INVALID_ARG, "tone: dst_peak %g is not finite, above 0 and at most 10000", (double)t->dst_peak);
+  if (!(defaults && t->unit_nits == 0.0f) && !nits_ok(t->unit_nits))
+    return hm_fail(HM_ERR_INVALID_ARG, "tone: unit_nits %g is not finite, above 0 and at most 10000", (double)t->unit_nits);
+  if (t->out_unit_nits != 0.0f && !nits_ok(t->out_unit_nits))
+    return hm_fail(HM_ERR_INVALID_ARG, "tone: out_unit_nits %g is not finite, above 0 and at most 10000", (double)t->out_unit_nits);
+  if (t->src_peak != 0.0f && tone_knee(t->src_peak, t->dst_peak) < 0.0)
+    return hm_fail(HM_ERR_INVALID_ARG, "tone: the knee of %g -> %g cd/m2 lies below black (KS < 0)", (double)t->src_peak, (double)t->dst_peak);
+  if (t->out_bits != 0 && t->out_bits != 8) return hm_fail(HM_ERR_INVALID_ARG, "tone: out_bits %d is not 0 or 8", t->out_bits);
+  return HM_OK;
+}
+
+} // namespace
+
+int hm_tone_dest_format(int out_format, const hm_device_tone* tone)
+{
+  if (tone && tone->out_bits == 8 && (out_format == HM_OUT_RRGGBB_LE || out_format == HM_OUT_RRGGBB_BE)) return HM_OUT_RGB;
+  return out_format;
+}
+
+float hm_tone_peak_of(int has_clli, unsigned max_cll, int has_mdcv, unsigned mdcv_max)
+{
+  if (has_clli && max_cll != 0) return (float)std::min(max_cll, 10000u); // (the field is 16 bits wide; PQ codes no light above 10000 cd/m2)
+  if (has_mdcv && mdcv_max >= 50000u && mdcv_max <= 100000000u) return (float)((double)mdcv_max * 0.0001);
+  return 1000.0f;
+}
+
+int hm_tone_check_static(int out_format, const hm_device_dest* d, const hm_device_light* l, const hm_device_tone* tone, int explicit_from)
+{
+  if (!tone) return hm_light_check_static(out_format, d, l, explicit_from);
+  if (!l) return hm_fail(HM_ERR_INVALID_ARG, "tone: null light step");
+  if (!d) return hm_fail(HM_ERR_INVALID_ARG, "null device destination");
+  int rc = tone_check(tone, !explicit_from);
+  if (rc) return rc;
+  if (tone->out_bits == 8) {
+    if (d->dtype == HM_DEV_U16) return hm_fail(HM_ERR_INVALID_ARG, "tone: out_bits 8 with HM_DEV_U16 (HM_DEV_U8 holds the codes)");
+    const int obpp = hm_out_bytes_per_pixel(out_format);
+    if (obpp == 4 || obpp == 8) return hm_fail(HM_ERR_UNSUPPORTED, "tone: out_bits 8 with the four-channel output format %d is not supported", out_format);
+  }
+  return light_check(out_format, hm_tone_dest_format(out_format, tone), d, l, explicit_from);
+}
+
+int hm_tone_resolve(int out_format, int bits, int img_transfer, int img_primaries, const hm_device_dest* d, const hm_device_light* l, const hm_device_tone* tone,
+                    hm_light_plan* lp)
+{
+  if (!tone) return hm_light_resolve(out_format, bits, img_transfer, img_primaries, d, l, lp);
+  int rc = hm_tone_check_static(out_format, d, l, tone, 0);
+  if (rc) return rc;
+  if ((rc = light_plan_of(out_format, hm_tone_dest_format(out_format, tone), bits, img_transfer, img_primaries, l, lp))) return rc;
+  if (tone->unit_nits == 0.0f && lp->from_transfer != 16)
+    return hm_fail(HM_ERR_INVALID_ARG, "tone: unit_nits must be given for transfer characteristics %d (only PQ says what 1.0 stands for)", lp->from_transfer);
+  if (tone->src_peak == 0.0f) return hm_fail(HM_ERR_INVALID_ARG, "tone: src_peak must be given: the pixels carry no light levels"); // (else the knee has been judged)
+  lp->tone = 1;
+  if (tone->out_bits == 8) lp->enc_bits = 8;
+  lp->src_peak = tone->src_peak; lp->dst_peak = tone->dst_peak;
+  lp->unit_nits = tone->unit_nits != 0.0f ? tone->unit_nits : 10000.0f;
+  lp->out_unit_nits = tone->out_unit_nits != 0.0f ? tone->out_unit_nits : tone->dst_peak;
+  return HM_OK;
+}
+
+int hm_tone_table(const hm_device_tone* tone, float gain, int which, float* out)
+{
+  if (!tone || !out) return hm_fail(HM_ERR_INVALID_ARG, "null argument");
+  if (which != 0 && which != 1) return hm_fail(HM_ERR_INVALID_ARG, "tone: table %d is not 0 (thr) or 1 (sg)", which);
+  if (!std::isfinite(gain) || !(gain > 0.0f)) return hm_fail(HM_ERR_INVALID_ARG, "light: gain %g is not finite and above 0", (double)gain);
+  const int rc = tone_check(tone, false);
+  if (rc) return rc;
+  if (tone->out_unit_nits == 0.0f) return hm_fail(HM_ERR_INVALID_ARG, "tone: out_unit_nits must be given");
+  fill_tone_tables((double)gain, tone->src_peak, tone->dst_peak, tone->unit_nits, tone->out_unit_nits, which ? nullptr : out, which ? out : nullptr);
+  return HM_TONE_STEPS;
 }
 
 int hm_light_write(const hm_device_dest* d, int out_format, int w, int h, const hm_view_plan* vp, const hm_light_plan* lp, const void* src, int src_stride,
@@ -777,23 +907,26 @@ int hm_light_write(const hm_device_dest* d, int out_format, int w, int h, const 
 {
   if (!sc || sc->pinned || sc->dev[0] || sc->dev[1]) return hm_fail(HM_ERR_INTERNAL, "light: no free scratch for the tables");
   const int ow = vp ? vp->ow : w, oh = vp ? vp->oh : h;
-  hm_dest_plan p;
-  int rc = hm_dest_resolve(out_format, ow, oh, d, &p);
+  hm_dest_plan p; // (of the target the destination is written as: under the 8-bit finish its samples are bytes, the source's are not)
+  int rc = hm_dest_resolve(lp->dest_format, ow, oh, d, &p);
   if (!rc) rc = hm_dest_check_len(d, &p);
   if (rc) return rc;
-  const int obpp = p.channels * p.sample_bytes;
+  const int obpp = hm_out_bytes_per_pixel(out_format), src_bytes = obpp >= 6 ? 2 : 1;
   const int cx = vp ? vp->x : 0, cy = vp ? vp->y : 0, cw = vp ? vp->w : w, ch = vp ? vp->h : h;
   const uint8_t* origin = (const uint8_t*)src + (size_t)cy * src_stride + (size_t)cx * obpp;
-  const size_t n = (size_t)1 << lp->bits, table_bytes = n * sizeof(float) * (lp->encode ? 2 : 1);
+  const size_t n = (size_t)1 << lp->bits, ne = lp->encode ? (size_t)1 << lp->enc_bits : 0, nt = lp->tone ? 2 * (size_t)HM_TONE_STEPS : 0;
+  const size_t table_bytes = (n + ne + nt) * sizeof(float);
   const bool resampled = vp && !vp->crop_only && vp->filter != HM_VIEW_NEAREST;
   hm_light_args la;
   std::memset(&la, 0, sizeof(la));
-  la.bits = lp->bits; la.encode = lp->encode; la.matrix = lp->matrix;
+  la.bits = lp->bits; la.enc_bits = lp->enc_bits; la.src_bytes = src_bytes; la.encode = lp->encode; la.matrix = lp->matrix;
   std::memcpy(la.m, lp->m, sizeof(la.m));
-  auto fill = [&](float* host) { // lin, then enc
+  auto fill = [&](float* host) { // lin, then enc, then thr and sg
     fill_light_table(lp->from_transfer, lp->bits, (double)lp->gain, false, host);
-    if (lp->encode) fill_light_table(lp->to_transfer, lp->bits, (double)lp->gain, true, host + n);
+    if (lp->encode) fill_light_table(lp->to_transfer, lp->enc_bits, (double)lp->gain, true, host + n);
+    if (lp->tone) fill_tone_tables((double)lp->gain, lp->src_peak, lp->dst_peak, lp->unit_nits, lp->out_unit_nits, host + n + ne, host + n + ne + HM_TONE_STEPS);
   };
+  auto point = [&](const float* dev) { la.lin = dev; la.enc = lp->encode ? dev + n : nullptr; la.tone = lp->tone ? dev + n + ne : nullptr; };
   if (!resampled) {
     float* host = (float*)hm_pool_pinned_alloc(table_bytes);
     if (!host) return hm_fail(HM_ERR_NOMEM, "out of memory");
@@ -801,8 +934,7 @@ int hm_light_write(const hm_device_dest* d, int out_format, int w, int h, const 
     fill(host);
     if (!(sc->dev[0] = hm_pool_device_alloc(table_bytes))) return HM_ERR_NO_DEVICE;
     if ((rc = hm_check_hip(hipMemcpyAsync(sc->dev[0], host, table_bytes, hipMemcpyHostToDevice, s), "upload of the light tables"))) return rc;
-    la.lin = (const float*)sc->dev[0];
-    la.enc = lp->encode ? la.lin + n : nullptr;
+    point((const float*)sc->dev[0]);
     if (vp && !vp->crop_only) return hm_launch_light_nearest(&p, &la, origin, src_stride, cw, ch, ow, oh, d->ptr, d->scale, d->bias, s);
     return hm_launch_light_tensor(&p, &la, origin, src_stride, cw, ch, d->ptr, d->scale, d->bias, s);
   }
@@ -820,7 +952,7 @@ int hm_light_write(const hm_device_dest* d, int out_format, int w, int h, const 
   if ((rc = hm_check_hip(hipMemcpyAsync(sc->dev[0], host, bytes, hipMemcpyHostToDevice, s), "upload of the tap and light tables"))) return rc;
   hm_resample_args a;
   std::memset(&a, 0, sizeof(a));
-  a.sample_bytes = p.sample_bytes; a.channels = p.channels;
+  a.sample_bytes = src_bytes; a.channels = p.channels;
   a.src = origin; a.src_stride = src_stride;
   a.n_w = vp->w; a.n_h = vp->h; a.ow = vp->ow; a.oh = vp->oh;
   const int32_t* dx = (const int32_t*)sc->dev[0];
@@ -828,16 +960,15 @@ int hm_light_write(const hm_device_dest* d, int out_format, int w, int h, const 
   a.ax.first = dx; a.ax.count = dx + vp->ow; a.ax.weights = reinterpret_cast<const float*>(dx + 2 * (size_t)vp->ow); a.ax.m = vp->ow; a.ax.taps = tx;
   a.ay.first = dy; a.ay.count = dy + vp->oh; a.ay.weights = reinterpret_cast<const float*>(dy + 2 * (size_t)vp->oh); a.ay.m = vp->oh; a.ay.taps = ty;
   a.tmp = (float*)sc->dev[1]; a.tmp_pitch = pitch; a.tmp_plane = plane;
-  la.lin = reinterpret_cast<const float*>(dy + words_y);
-  la.enc = lp->encode ? la.lin + n : nullptr;
+  point(reinterpret_cast<const float*>(dy + words_y));
   return hm_launch_light_resample(&p, &la, &a, d->ptr, d->scale, d->bias, s);
 }
 
-int hm_light_to_tensor(int out_format, int bits, int src_w, int src_h, const void* d_src, int src_stride, const hm_device_view* view, const hm_device_light* light,
-                       const hm_device_dest* dest, void* stream)
+// hm_light_to_tensor, and with a tone step hm_tone_to_tensor
+static int light_to_tensor(int out_format, int bits, int src_w, int src_h, const void* d_src, int src_stride, const hm_device_view* view, const hm_device_light* light,
+                           const hm_device_tone* tone, const hm_device_dest* dest, void* stream)
 {
-  if (!d_src || !dest || !light) return hm_fail(HM_ERR_INVALID_ARG, "null argument");
-  int rc = hm_light_check_static(out_format, dest, light, 1);
+  int rc = hm_tone_check_static(out_format, dest, light, tone, 1);
   if (rc) return rc;
   if (src_w <= 0 || src_h <= 0 || src_w > 32768 || src_h > 32768) return hm_fail(HM_ERR_INVALID_ARG, "image size %d x %d", src_w, src_h);
   hm_view_plan vp;
@@ -845,11 +976,11 @@ int hm_light_to_tensor(int out_format, int bits, int src_w, int src_h, const voi
   vp.ow = src_w; vp.oh = src_h;
   if (view && (rc = hm_view_resolve(out_format, src_w, src_h, view, &vp))) return rc;
   hm_light_plan lp;
-  if ((rc = hm_light_resolve(out_format, bits, light->from_transfer, light->from_primaries, dest, light, &lp))) return rc;
+  if ((rc = hm_tone_resolve(out_format, bits, light->from_transfer, light->from_primaries, dest, light, tone, &lp))) return rc;
   hm_dest_plan p;
-  if ((rc = hm_dest_resolve(out_format, vp.ow, vp.oh, dest, &p)) || (rc = hm_dest_check_len(dest, &p))) return rc;
+  if ((rc = hm_dest_resolve(lp.dest_format, vp.ow, vp.oh, dest, &p)) || (rc = hm_dest_check_len(dest, &p))) return rc;
   if (src_stride < src_w * hm_out_bytes_per_pixel(out_format)) return hm_fail(HM_ERR_INVALID_ARG, "src_stride %d below the bytes of a row", src_stride);
-  if (p.sample_bytes == 2 && (((uintptr_t)d_src | (unsigned)src_stride) & 1)) return hm_fail(HM_ERR_INVALID_ARG, "16-bit samples at an odd address or stride");
+  if (hm_out_bytes_per_pixel(out_format) >= 6 && (((uintptr_t)d_src | (unsigned)src_stride) & 1)) return hm_fail(HM_ERR_INVALID_ARG, "16-bit samples at an odd address or stride");
   int n_dev = 0;
   if (hipGetDeviceCount(&n_dev) != hipSuccess || n_dev == 0) { (void)hipGetLastError(); return hm_fail(HM_ERR_NO_DEVICE, "no HIP device available"); }
   if ((rc = hm_dest_check_pointer(dest))) return rc;
@@ -865,6 +996,20 @@ int hm_light_to_tensor(int out_format, int bits, int src_w, int src_h, const voi
     delete sc;
   }
   return rc;
+}
+
+int hm_light_to_tensor(int out_format, int bits, int src_w, int src_h, const void* d_src, int src_stride, const hm_device_view* view, const hm_device_light* light,
+                       const hm_device_dest* dest, void* stream)
+{
+  if (!d_src || !dest || !light) return hm_fail(HM_ERR_INVALID_ARG, "null argument");
+  return light_to_tensor(out_format, bits, src_w, src_h, d_src, src_stride, view, light, nullptr, dest, stream);
+}
+
+int hm_tone_to_tensor(int out_format, int bits, int src_w, int src_h, const void* d_src, int src_stride, const hm_device_view* view, const hm_device_light* light,
+                      const hm_device_tone* tone, const hm_device_dest* dest, void* stream)
+{
+  if (!d_src || !dest || !tone) return hm_fail(HM_ERR_INVALID_ARG, "null argument");
+  return light_to_tensor(out_format, bits, src_w, src_h, d_src, src_stride, view, light, tone, dest, stream);
 }
 
 // ---- planar views: every plane an image of its own ------------------------------------------------------------------------------

@@ -306,6 +306,12 @@ bool HeifFile::parse_iprp(const uint8_t* p, size_t n, HeifError& err)
           ip.transforms.push_back(t);
         }
         else if (pb.type == "auxC") { d.skip(4); ip.aux_type = d.cstr(); }
+        else if (pb.type == "clli") { ip.has_clli = true; for (int i = 0; i < 2; i++) ip.clli[i] = (uint16_t)d.u(2); }
+        else if (pb.type == "mdcv") {
+          ip.has_mdcv = true;
+          for (int i = 0; i < 8; i++) ip.mdcv_xy[i] = (uint16_t)d.u(2);
+          for (int i = 0; i < 2; i++) ip.mdcv_lum[i] = (uint32_t)d.u(4);
+        }
         else if (pb.type == "hvcC") {
           HvcC& h = ip.hvcc;
           h.present = true;

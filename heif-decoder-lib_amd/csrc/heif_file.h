@@ -1,7 +1,7 @@
 // heif_file.h — minimal ISOBMFF / HEIF reader for the decode path (host side).
 // Counterpart of the parts of libheif/file.cc, box.cc and codecs/hevc.cc the hot path needs:
 // item locations (iloc), item infos (iinf), references (iref: dimg/auxl/thmb), properties
-// (ipco/ipma: hvcC, ispe, pixi, colr, irot, imir, clap, auxC), primary item (pitm), idat.
+// (ipco/ipma: hvcC, ispe, pixi, colr, irot, imir, clap, auxC, clli, mdcv), primary item (pitm), idat.
 // Movie mode (the fork's image sequences): a 'moov' track of HEVC-intra samples, each sample a top-level image
 // (file.cc:474-483, 1154-1244; context.cc:646-700 of the reference).
 #ifndef HM_HEIF_FILE_H
@@ -54,6 +54,11 @@ struct ItemProps {
   int irot_angle = 0;
   std::vector<Transform> transforms; // irot / imir / clap in association order
   std::string aux_type;
+  // 'clli' / 'mdcv' (box.cc:3120-3178 of the reference: plain boxes, no version word): the raw fields
+  bool has_clli = false, has_mdcv = false;
+  uint16_t clli[2] = {0, 0};   // max_content_light_level, max_pic_average_light_level
+  uint16_t mdcv_xy[8] = {0, 0, 0, 0, 0, 0, 0, 0}; // display_primaries x0 y0 x1 y1 x2 y2, white point x y
+  uint32_t mdcv_lum[2] = {0, 0}; // max / min display mastering luminance, 0.0001 cd/m2
 };
 
 struct Extent { uint64_t offset, length; };

@@ -138,19 +138,37 @@ typedef struct hm_light_plan {
   int32_t matrix;        // to_primaries differs from from_primaries
   float gain;
   float m[9];
+  // the tone step (hm_device_tone) beside it, resolved: nothing left at 0
+  int32_t tone;          // a tone step runs
+  int32_t enc_bits;      // of the codes the finish stores: bits, or 8 under the 8-bit finish
+  int32_t dest_format;   // the target the destination is judged, sized and written as: out_format, or its 8-bit sibling
+  float src_peak, dst_peak, unit_nits, out_unit_nits;
 } hm_light_plan;
 // what depends on the request alone: reserved, gain, the codes (from_* == 0: allowed unless `explicit_from`), the target (no _BE, no
 // planar one), HM_LIGHT_LINEAR with an integer dtype
 int hm_light_check_static(int out_format, const hm_device_dest* d, const hm_device_light* l, int explicit_from);
 // ... and what depends on the image: from_* == 0 become img_transfer / img_primaries (what hm_decoded reports), bits the sample depth
 int hm_light_resolve(int out_format, int bits, int img_transfer, int img_primaries, const hm_device_dest* d, const hm_device_light* l, hm_light_plan* lp);
+// ---- the tone step (hm_device_tone) inside the light step: two tables of HM_TONE_STEPS entries, built in devdest.cpp ----
+// the target the destination of a request is judged by: out_format, or with tone->out_bits == 8 the 8-bit sibling of a 16-bit one
+int hm_tone_dest_format(int out_format, const hm_device_tone* tone);
+// hm_light_check_static with a tone step (tone NULL: that function): the tone step's own refusals first, then the light step's and the
+// destination's, the latter against hm_tone_dest_format.  explicit_from: src_peak and unit_nits must be given too.
+int hm_tone_check_static(int out_format, const hm_device_dest* d, const hm_device_light* l, const hm_device_tone* tone, int explicit_from);
+// hm_light_resolve with a tone step (tone NULL: that function); src_peak == 0 and unit_nits == 0 are refused or resolved here
+int hm_tone_resolve(int out_format, int bits, int img_transfer, int img_primaries, const hm_device_dest* d, const hm_device_light* l, const hm_device_tone* tone,
+                    hm_light_plan* lp);
+// the peak rule of include/heif_mi355x.h on an item's raw properties
+float hm_tone_peak_of(int has_clli, unsigned max_cll, int has_mdcv, unsigned mdcv_max);
+
 // hm_dest_write / hm_view_write under a light step: the w x h image at `src` (vp NULL), or its view vp, into the destination, which
-// has been checked against the size written; asynchronous on `s`.  The tables (and a view's tap tables and intermediate) hang on sc.
+// has been checked against the size written (as lp->dest_format); asynchronous on `s`.  The tables (and a view's tap tables and intermediate) hang on sc.
 int hm_light_write(const hm_device_dest* d, int out_format, int w, int h, const hm_view_plan* vp, const hm_light_plan* lp, const void* src, int src_stride,
                    hipStream_t s, hm_view_scratch* sc);
 
-// what the kernels get: device pointers of lin[1 << bits] and (encode) enc[1 << bits]
-typedef struct hm_light_args { const float* lin; const float* enc; int32_t bits, encode, matrix; float m[9]; } hm_light_args;
+// what the kernels get: device pointers of lin[1 << bits], (encode) enc[1 << enc_bits] and (tone) thr[HM_TONE_STEPS] with sg[HM_TONE_STEPS]
+// behind it; src_bytes: bytes of a source sample (the plan's sample_bytes are the destination's sibling target's)
+typedef struct hm_light_args { const float* lin; const float* enc; const float* tone; int32_t bits, enc_bits, src_bytes, encode, matrix; float m[9]; } hm_light_args;
 int hm_launch_light_tensor(const hm_dest_plan* p, const hm_light_args* la, const void* src, int src_stride, int w, int rows, void* dst, const float scale[4],
                            const float bias[4], hipStream_t s);
 int hm_launch_light_nearest(const hm_dest_plan* p, const hm_light_args* la, const void* src, int src_stride, int n_w, int n_h, int ow, int oh, void* dst,

@@ -836,10 +836,10 @@ void parse_picture(const hm_file* f, uint32_t id, bool few_pictures, int strict,
 
 int target_check_shape(const OutputTarget& t)
 {
-  const bool ok = !(t.dest && t.planes) && (!t.light || t.dest) && (!t.view || t.dest || t.planes) && (!t.view_later || (t.view && t.dest)) &&
+  const bool ok = !(t.dest && t.planes) && (!t.light || t.dest) && (!t.tone || t.light) && (!t.view || t.dest || t.planes) && (!t.view_later || (t.view && t.dest)) &&
                   (!t.planes_later || (t.view && t.planes));
-  return ok ? (int)HM_OK : hm_fail(HM_ERR_INTERNAL, "output target: dest%s view%s planes%s light%s do not go together", t.dest ? "+" : "-", t.view ? "+" : "-",
-                                   t.planes ? "+" : "-", t.light ? "+" : "-");
+  return ok ? (int)HM_OK : hm_fail(HM_ERR_INTERNAL, "output target: dest%s view%s planes%s light%s tone%s do not go together", t.dest ? "+" : "-", t.view ? "+" : "-",
+                                   t.planes ? "+" : "-", t.light ? "+" : "-", t.tone ? "+" : "-");
 }
 
 // the chroma format and depth of a planar result for a decoded image of (chroma, bd): what emit_native / emit_planar hand out
@@ -893,9 +893,9 @@ static int target_fits(const hm_decode_params* params, const OutputTarget& t, in
       hm_view_plan vp;
       vp.ow = w; vp.oh = h;
       if (t.view && (rc = hm_view_resolve(params->out_format, w, h, t.view, &vp))) return rc;
-      if ((rc = hm_dest_resolve(params->out_format, vp.ow, vp.oh, t.dest, &dp)) || (rc = hm_dest_check_len(t.dest, &dp))) return rc;
+      if ((rc = hm_dest_resolve(hm_tone_dest_format(params->out_format, t.tone), vp.ow, vp.oh, t.dest, &dp)) || (rc = hm_dest_check_len(t.dest, &dp))) return rc;
       hm_light_plan lp;
-      if (t.light && reported && (rc = hm_light_resolve(params->out_format, reported->bit_depth, reported->transfer, reported->primaries, t.dest, t.light, &lp)))
+      if (t.light && reported && (rc = hm_tone_resolve(params->out_format, reported->bit_depth, reported->transfer, reported->primaries, t.dest, t.light, t.tone, &lp)))
         return rc;
     }
     if (pointers && ((rc = require_device()) || (rc = hm_dest_check_pointer(t.dest)))) return rc;
@@ -1044,7 +1044,7 @@ static int emit_interleaved(const hm_decode_params* params, hipStream_t s, Plana
     if (t.view && (rc = hm_view_resolve(params->out_format, img_w, img_h, t.view, &vp))) return rc;
     if (t.light) { // ... through the light step, resolved against the profile and depth this image reports: refused before a byte is written
       hm_light_plan lp;
-      if ((rc = hm_light_resolve(params->out_format, r.bit_depth, r.transfer, r.primaries, t.dest, t.light, &lp))) return rc;
+      if ((rc = hm_tone_resolve(params->out_format, r.bit_depth, r.transfer, r.primaries, t.dest, t.light, t.tone, &lp))) return rc;
       if ((rc = hm_light_write(t.dest, params->out_format, img_w, img_h, t.view ? &vp : nullptr, &lp, dout.p, cd.out_stride, s, t.scratch))) return rc;
     }
     else if (t.view) {
@@ -1057,7 +1057,7 @@ static int emit_interleaved(const hm_decode_params* params, hipStream_t s, Plana
       out->plane_width[0] = vp.ow; out->plane_height[0] = vp.oh;
     }
     hm_dest_plan dp;
-    if ((rc = hm_dest_resolve(params->out_format, vp.ow, vp.oh, t.dest, &dp))) return rc;
+    if ((rc = hm_dest_resolve(hm_tone_dest_format(params->out_format, t.tone), vp.ow, vp.oh, t.dest, &dp))) return rc;
     out->used_ext_dst = 1;
     out->stride[0] = (int32_t)std::min<int64_t>(dp.row_pitch, 0x7FFFFFFF);
   }
@@ -1177,8 +1177,11 @@ int check_target_request(const hm_file* f, uint32_t id, const hm_decode_params* 
   if (rc) return rc;
   if (t.dest) {
     if (params->ext_dst) return hm_fail(HM_ERR_INVALID_ARG, "params->ext_dst must be NULL with a device destination");
-    if ((rc = hm_dest_check_static(params->out_format, t.dest))) return rc;
-    if (t.light && (rc = hm_light_check_static(params->out_format, t.dest, t.light, 0))) return rc;
+    if (t.tone) { if ((rc = hm_tone_check_static(params->out_format, t.dest, t.light, t.tone, 0))) return rc; } // (its own refusals, then the two below)
+    else {
+      if ((rc = hm_dest_check_static(params->out_format, t.dest))) return rc;
+      if (t.light && (rc = hm_light_check_static(params->out_format, t.dest, t.light, 0))) return rc;
+    }
     if (!t.dest->ptr) return hm_fail(HM_ERR_INVALID_ARG, "device destination: null ptr");
   }
   if (t.planes && (rc = check_planes_params(params, t.planes))) return rc;
@@ -1189,6 +1192,15 @@ int check_target_request(const hm_file* f, uint32_t id, const hm_decode_params* 
   }
   // (whether there is an alpha plane, and of which depth, is the decode's to say: -1)
   return target_fits(params, t, w, h, info.chroma, info.bit_depth, -1, nullptr, true);
+}
+
+hm_device_tone tone_for_item(const hm_file* f, uint32_t id, const hm_device_tone* tone)
+{
+  hm_device_tone t = *tone;
+  if (t.src_peak != 0.0f) return t;
+  const hm::Item* it = f && id && !f->file.is_movie() ? f->file.item(id) : nullptr;
+  t.src_peak = it ? hm_tone_peak_of(it->props.has_clli, it->props.clli[0], it->props.has_mdcv, it->props.mdcv_lum[0]) : 1000.0f;
+  return t;
 }
 
 int job_complete(DecodeJob& j, hm_decoded*)
@@ -1677,6 +1689,30 @@ int hm_decode_item_to_device_light(const hm_file* f, uint32_t id, const hm_decod
   return decode_item_to(f, id, params, OutputTarget::to_dest(dest, view, light), out);
 }
 
+int hm_decode_item_to_device_tone(const hm_file* f, uint32_t id, const hm_decode_params* params, const hm_device_view* view, const hm_device_light* light,
+                                  const hm_device_tone* tone, const hm_device_dest* dest, hm_decoded* out)
+{
+  if (!f || !params || !tone || !dest || !out) return hm_fail(HM_ERR_INVALID_ARG, "null argument");
+  if (!light) return hm_fail(HM_ERR_INVALID_ARG, "tone: null light step");
+  const hm_device_tone own = tone_for_item(f, id, tone);
+  return decode_item_to(f, id, params, OutputTarget::to_dest(dest, view, light, &own), out);
+}
+
+int hm_file_item_light_levels(const hm_file* f, uint32_t id, hm_light_levels* out)
+{
+  if (!f || !out) return hm_fail(HM_ERR_INVALID_ARG, "null argument");
+  std::memset(out, 0, sizeof(*out));
+  const hm::Item* it = f->file.item(id);
+  if (!it) return hm_fail(HM_ERR_INVALID_ARG, "no item %u", id);
+  const hm::ItemProps& ip = it->props;
+  out->has_clli = ip.has_clli ? 1 : 0; out->has_mdcv = ip.has_mdcv ? 1 : 0;
+  out->max_content_light_level = ip.clli[0]; out->max_pic_average_light_level = ip.clli[1];
+  for (int c = 0; c < 3; c++) { out->display_primaries_x[c] = ip.mdcv_xy[2 * c]; out->display_primaries_y[c] = ip.mdcv_xy[2 * c + 1]; }
+  out->white_point_x = ip.mdcv_xy[6]; out->white_point_y = ip.mdcv_xy[7];
+  out->max_display_mastering_luminance = ip.mdcv_lum[0]; out->min_display_mastering_luminance = ip.mdcv_lum[1];
+  return HM_OK;
+}
+
 int hm_decode_item_to_device_planes(const hm_file* f, uint32_t id, const hm_decode_params* params, const hm_device_planes* planes, hm_decoded* out)
 {
   if (!f || !params || !planes || !out) return hm_fail(HM_ERR_INVALID_ARG, "null argument");
@@ -1887,6 +1923,16 @@ int hm_decode_frames_to_device_light(const hm_file* f, const uint32_t* frames, i
   return decode_sequence(f, frames, 0, count, params, nullptr, OutputTarget::to_dest(dests, view, light), out, failed_frame);
 }
 
+int hm_decode_frames_to_device_tone(const hm_file* f, const uint32_t* frames, int32_t count, const hm_decode_params* params, const hm_device_view* view,
+                                    const hm_device_light* light, const hm_device_tone* tone, const hm_device_dest* dests, hm_decoded* out, int32_t* failed_frame)
+{
+  if (failed_frame) *failed_frame = -1;
+  if (!frames || !dests || !tone) return hm_fail(HM_ERR_INVALID_ARG, "null argument");
+  if (!light) return hm_fail(HM_ERR_INVALID_ARG, "tone: null light step");
+  const hm_device_tone own = tone_for_item(f, 0, tone); // (a frame carries no properties)
+  return decode_sequence(f, frames, 0, count, params, nullptr, OutputTarget::to_dest(dests, view, light, &own), out, failed_frame);
+}
+
 int hm_decode_frames_to_device_planes(const hm_file* f, const uint32_t* frames, int32_t count, const hm_decode_params* params, const hm_device_planes* planes,
                                       hm_decoded* out, int32_t* failed_frame)
 {
@@ -1932,8 +1978,8 @@ static int decode_sequence(const hm_file* f, const uint32_t* frames, uint32_t fi
   if (params->ext_dst) return hm_fail(HM_ERR_INVALID_ARG, "params->ext_dst: a sequence takes its caller buffers from dests");
   if (ddests) { // what can be refused without the frames' sizes (those: below, behind the entropy decode, before anything is queued)
     for (int k = 0; k < count; k++) {
-      int rc = hm_dest_check_static(params->out_format, &ddests[k]);
-      if (!rc && light) rc = hm_light_check_static(params->out_format, &ddests[k], light, 0);
+      int rc = target.tone ? hm_tone_check_static(params->out_format, &ddests[k], light, target.tone, 0) : hm_dest_check_static(params->out_format, &ddests[k]);
+      if (!rc && light && !target.tone) rc = hm_light_check_static(params->out_format, &ddests[k], light, 0);
       if (rc) return rc;
       if (!ddests[k].ptr) return hm_fail(HM_ERR_INVALID_ARG, "device destination of frame %d: null ptr", k);
     }

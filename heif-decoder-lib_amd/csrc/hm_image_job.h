@@ -109,13 +109,14 @@ struct OutputTarget {
   const hm_device_view* view = nullptr;        // ... a rectangle of the image, resampled (with dest or planes)
   const hm_device_planes* planes = nullptr;    // a planar result (out_format 0 / HM_OUT_YCBCR_*) goes to caller-owned device memory, plane by plane
   const hm_device_light* light = nullptr;      // the light step in the write of dest
+  const hm_device_tone* tone = nullptr;        // ... with a tone step inside it (src_peak resolved by the entry point: never 0 here)
   hm_view_scratch* scratch = nullptr;          // tap tables and the intermediate of the resampling step, the tables of the light step
   hm_view_item* view_later = nullptr;          // view + dest: the view is not written, only described there - the caller writes it with those of other images
   hm_planes_view_item* planes_later = nullptr; // the same for view + planes
-  static OutputTarget to_dest(const hm_device_dest* d, const hm_device_view* v = nullptr, const hm_device_light* l = nullptr)
+  static OutputTarget to_dest(const hm_device_dest* d, const hm_device_view* v = nullptr, const hm_device_light* l = nullptr, const hm_device_tone* tn = nullptr)
   {
     OutputTarget t;
-    t.dest = d; t.view = v; t.light = l;
+    t.dest = d; t.view = v; t.light = l; t.tone = tn;
     return t;
   }
   static OutputTarget to_planes(const hm_device_planes* p, const hm_device_view* v = nullptr)
@@ -125,7 +126,7 @@ struct OutputTarget {
     return t;
   }
 };
-// dest xor planes (or neither); light only with dest; view only with one of the two; a *_later only with view and its own kind of destination
+// dest xor planes (or neither); light only with dest; tone only with light; view only with one of the two; a *_later only with view and its own kind of destination
 int target_check_shape(const OutputTarget& t);
 
 // a job's own copies of the caller's structs (the pipeline outlives them; hm_decode_params keeps its layout, so they travel beside
@@ -135,6 +136,7 @@ struct OwnedTarget {
   hm_device_view view{};
   hm_device_planes planes{};
   hm_device_light light{};
+  hm_device_tone tone{};
   OutputTarget t;
   OwnedTarget() = default;
   OwnedTarget(const OwnedTarget&) = delete;
@@ -146,6 +148,7 @@ struct OwnedTarget {
     if (from.view) { view = *from.view; t.view = &view; }
     if (from.planes) { planes = *from.planes; t.planes = &planes; }
     if (from.light) { light = *from.light; t.light = &light; }
+    if (from.tone) { tone = *from.tone; t.tone = &tone; }
   }
 };
 
@@ -193,6 +196,9 @@ int job_enqueue(DecodeJob& j, hm_decoded* out);
 // chroma format and depth where the file decides them; the crop of a view against the declared size, the destination against the
 // view's output size), a device, the pointers
 int check_target_request(const hm_file* f, uint32_t id, const hm_decode_params* params, const OutputTarget& t);
+// the tone step an entry point hands on: the caller's, with src_peak == 0 replaced by the peak of item `id` (its clli, its mdcv, 1000;
+// id 0 or a frame of a sequence: 1000).  The other refusals are check_target_request's.
+hm_device_tone tone_for_item(const hm_file* f, uint32_t id, const hm_device_tone* tone);
 int job_complete(DecodeJob& j, hm_decoded* out);
 
 } // namespace hm_img

@@ -10,9 +10,12 @@
 //                    conversion as it was).  The unstaged form, for all three filters.
 //   k_light_v        the vertical sums of ONE pixel per lane - the matrix needs R, G and B together: a CHW intermediate is read at
 //                    one index of three planes -, then matrix and finish.
-// LDS: lin[1 << bits] and, when re-encoding, enc[1 << bits] behind it (1 KB each at 8 bits, 16 KB each at 12), filled once per
-// workgroup.  The lookups are data-dependent ds_read_b32: lanes that meet the same entry are served by one broadcast, different
-// entries of one bank serialise - a flat image is the best case, noise the worst; no layout of a table changes that.
+// The tone step (hm_device_tone) sits between matrix and finish: the max of R, G, B is searched in thr[2048] like a code in enc, and
+// the pixel is scaled by sg[] at the count - a wave-uniform branch, like `encode` and `matrix`.
+// LDS: lin[1 << bits], when re-encoding enc[1 << enc_bits] behind it (1 KB each at 8 bits, 16 KB each at 12), with a tone step thr
+// and sg (8 KB each) behind those - at most 48 KB -, filled once per workgroup.  The lookups are data-dependent ds_read_b32: lanes
+// that meet the same entry are served by one broadcast, different entries of one bank serialise - a flat image is the best case,
+// noise the worst; no layout of a table changes that.
 // The matrix and the scalars of the step are kernel arguments (SGPRs).  -ffp-contract=off, __fmul_rn / __fadd_rn throughout.
 #include <hip/hip_runtime.h>
 #include <hip/hip_fp16.h>
@@ -25,13 +28,17 @@
 namespace {
 
 struct Affine { float scale[4], bias[4]; };
-struct Light { const float* lin; const float* enc; int bits, encode, matrix; float m[9]; };
+// ebits: of the codes of enc (bits, or 8 under the 8-bit finish); tone: thr[TONE_STEPS], then sg[TONE_STEPS] (NULL: no tone step)
+struct Light { const float* lin; const float* enc; const float* tone; int bits, ebits, encode, matrix; float m[9]; };
+constexpr int TONE_STEPS = HM_TONE_STEPS;
 
-// a (may be NULL) -> lds[0 .. n), b (may be NULL) -> lds[n .. 2 n); every thread of the workgroup comes here
-__device__ __forceinline__ void fill_tables(float* lds, const float* __restrict__ a, const float* __restrict__ b, int n)
+// a[na], b[nb], c[nc] (each may be NULL: nothing is copied, its place stays) -> lds, one behind the other; every thread of the
+// workgroup comes here
+__device__ __forceinline__ void fill_tables(float* lds, const float* __restrict__ a, int na, const float* __restrict__ b, int nb, const float* __restrict__ c, int nc)
 {
-  if (a) for (int i = threadIdx.x; i < n; i += 256) lds[i] = a[i];
-  if (b) for (int i = threadIdx.x; i < n; i += 256) lds[n + i] = b[i];
+  if (a) for (int i = threadIdx.x; i < na; i += 256) lds[i] = a[i];
+  if (b) for (int i = threadIdx.x; i < nb; i += 256) lds[na + i] = b[i];
+  if (c) for (int i = threadIdx.x; i < nc; i += 256) lds[na + nb + i] = c[i];
   __syncthreads();
 }
 
@@ -74,14 +81,27 @@ __device__ __forceinline__ void gamut(const Light& L, float r[3])
   r[2] = __fadd_rn(__fadd_rn(__fmul_rn(L.m[6], R), __fmul_rn(L.m[7], G)), __fmul_rn(L.m[8], B));
 }
 
+// the tone step on one pixel's linear light; tl: thr, then sg, in LDS
+__device__ __forceinline__ void tone_map(const float* tl, float r[3])
+{
+  const float N = fmaxf(fmaxf(r[0], r[1]), r[2]);
+  int k = 0;
+  for (int step = TONE_STEPS >> 1; step; step >>= 1) { // (k + step <= TONE_STEPS - 1: the steps sum to it)
+    const int t = k + step;
+    if (tl[t] <= N) k = t;
+  }
+  const float g = tl[TONE_STEPS + k];
+  r[0] = __fmul_rn(r[0], g); r[1] = __fmul_rn(r[1], g); r[2] = __fmul_rn(r[2], g);
+}
+
 // linear light r of a colour channel to an element of the destination; enc: the threshold table in LDS
 template <typename OutT> __device__ __forceinline__ OutT colour_out(const Light& L, const float* enc, float r, float sc, float bi)
 {
-  if (L.encode) return moved<OutT>(encode_of(enc, L.bits, r), sc, bi);
+  if (L.encode) return moved<OutT>(encode_of(enc, L.ebits, r), sc, bi);
   return linear_out<OutT>(r, sc, bi);
 }
 
-// one pixel that is moved, not resampled: v0 .. v2 its colour samples, v3 its alpha sample (C == 4); lds = lin, then enc
+// one pixel that is moved, not resampled: v0 .. v2 its colour samples, v3 its alpha sample (C == 4); lds = lin, then enc, then thr and sg
 template <int C, typename OutT>
 __device__ __forceinline__ void pixel(const Light& L, const float* lds, unsigned v0, unsigned v1, unsigned v2, unsigned v3, const Affine& a, OutT o[C])
 {
@@ -89,6 +109,7 @@ __device__ __forceinline__ void pixel(const Light& L, const float* lds, unsigned
   float r[3] = {lds[min(v0, peak)], lds[min(v1, peak)], lds[min(v2, peak)]};
   gamut(L, r);
   const float* enc = lds + (1 << L.bits);
+  if (L.tone) tone_map(enc + (L.encode ? 1 << L.ebits : 0), r);
   o[0] = colour_out<OutT>(L, enc, r[0], a.scale[0], a.bias[0]);
   o[1] = colour_out<OutT>(L, enc, r[1], a.scale[1], a.bias[1]);
   o[2] = colour_out<OutT>(L, enc, r[2], a.scale[2], a.bias[2]);
@@ -109,7 +130,7 @@ __global__ __launch_bounds__(256) void k_light_tensor(const uint8_t* __restrict_
   typedef typename std::conditional<SB == 1, uint8_t, uint16_t>::type InT;
   constexpr int P = 16 / (int)sizeof(OutT); // pixels per lane
   constexpr int NB = P * C * SB;            // input bytes per lane
-  fill_tables(lds, L.lin, L.encode ? L.enc : nullptr, 1 << L.bits);
+  fill_tables(lds, L.lin, 1 << L.bits, L.enc, L.encode ? 1 << L.ebits : 0, L.tone, 2 * TONE_STEPS);
   const int lane = threadIdx.x & 63, y = blockIdx.y * 4 + (threadIdx.x >> 6);
   if (y >= h) return;
   uint8_t* orow = dst + (long long)y * row_pitch;
@@ -185,7 +206,7 @@ __global__ __launch_bounds__(256) void k_light_nearest(const uint8_t* __restrict
                                                        uint8_t* __restrict__ dst, long long row_pitch, long long plane_pitch, Affine a, Light L)
 {
   extern __shared__ __attribute__((aligned(16))) float lds[];
-  fill_tables(lds, L.lin, L.encode ? L.enc : nullptr, 1 << L.bits);
+  fill_tables(lds, L.lin, 1 << L.bits, L.enc, L.encode ? 1 << L.ebits : 0, L.tone, 2 * TONE_STEPS);
   const int j = blockIdx.x * 64 + (threadIdx.x & 63), k = blockIdx.y * 4 + (threadIdx.x >> 6);
   if (j >= ow || k >= oh) return;
   const int sx = j * n_w / ow, sy = k * n_h / oh;
@@ -209,7 +230,7 @@ __global__ __launch_bounds__(256) void k_light_h(const uint8_t* __restrict__ src
 {
   extern __shared__ __attribute__((aligned(16))) float lds[];
   typedef typename std::conditional<SB == 1, uint8_t, uint16_t>::type InT;
-  fill_tables(lds, lin, nullptr, 1 << bits);
+  fill_tables(lds, lin, 1 << bits, nullptr, 0, nullptr, 0);
   const unsigned peak = (1u << bits) - 1u;
   const int j = blockIdx.x * 64 + (threadIdx.x & 63), y = blockIdx.y * 4 + (threadIdx.x >> 6);
   if (j >= ow || y >= n_h) return;
@@ -237,14 +258,15 @@ __global__ __launch_bounds__(256) void k_light_h(const uint8_t* __restrict__ src
 
 // The vertical pass: a lane is ONE output pixel, a wave 64 consecutive pixels of one output row, so the taps are wave-uniform and
 // the reads of a CHW intermediate coalesce per plane (an HWC one: the wave reads 64 * C consecutive floats in C instructions).
-// grid: x = groups of 64 columns, y = groups of 4 output rows; dynamic LDS: enc when re-encoding.
+// grid: x = groups of 64 columns, y = groups of 4 output rows; dynamic LDS: enc when re-encoding, then thr and sg with a tone step.
 template <typename OutT, bool CHW, int C>
 __global__ __launch_bounds__(256) void k_light_v(const float* __restrict__ tmp, long long pitch, long long plane, int ow, int oh,
                                                  const int32_t* __restrict__ first, const int32_t* __restrict__ count, const float* __restrict__ wts,
                                                  uint8_t* __restrict__ dst, long long row_pitch, long long plane_pitch, Affine a, Light L)
 {
   extern __shared__ __attribute__((aligned(16))) float lds[];
-  if (L.encode) fill_tables(lds, L.enc, nullptr, 1 << L.bits); // (uniform: the barrier inside is met by every thread or by none)
+  const int ne = L.encode ? 1 << L.ebits : 0;
+  if (L.encode || L.tone) fill_tables(lds, L.enc, ne, L.tone, 2 * TONE_STEPS, nullptr, 0); // (uniform: the barrier inside is met by every thread or by none)
   const int j = blockIdx.x * 64 + (threadIdx.x & 63), k = blockIdx.y * 4 + (threadIdx.x >> 6);
   if (j >= ow || k >= oh) return;
   const int y0 = first[k], n = count[k]; // (the same in every lane of the wave)
@@ -259,6 +281,7 @@ __global__ __launch_bounds__(256) void k_light_v(const float* __restrict__ tmp, 
     col += pitch;
   }
   gamut(L, acc);
+  if (L.tone) tone_map(lds + ne, acc);
   OutT o[C];
 #pragma unroll
   for (int c = 0; c < 3; c++) o[c] = colour_out<OutT>(L, lds, acc[c], a.scale[c], a.bias[c]);
@@ -285,6 +308,11 @@ const void* const g_instances[] = {
   (const void*)k_light_h<2, 3, true>, (const void*)k_light_h<2, 3, false>, (const void*)k_light_h<2, 4, true>, (const void*)k_light_h<2, 4, false>,
   HM_LV_SET(uint8_t), HM_LV_SET(uint16_t), HM_LV_SET(__half), HM_LV_SET(float),
 };
+// ... and the five of the 8-bit finish from 16-bit samples (hm_device_tone.out_bits == 8): 4 pointwise, 1 nearest
+const void* const g_finish8_instances[] = {
+  (const void*)k_light_tensor<2, 3, uint8_t, true, true>, (const void*)k_light_tensor<2, 3, uint8_t, true, false>, (const void*)k_light_tensor<2, 3, uint8_t, false, true>,
+  (const void*)k_light_tensor<2, 3, uint8_t, false, false>, (const void*)k_light_nearest<uint16_t, 3, uint8_t>,
+};
 #undef HM_LT_SET
 #undef HM_LN_SET
 #undef HM_LV_SET
@@ -299,13 +327,18 @@ Affine affine_of(const float scale[4], const float bias[4])
 Light light_of(const hm_light_args* la)
 {
   Light L;
-  L.lin = la->lin; L.enc = la->enc; L.bits = la->bits; L.encode = la->encode; L.matrix = la->matrix;
+  L.lin = la->lin; L.enc = la->enc; L.tone = la->tone; L.bits = la->bits; L.ebits = la->enc_bits; L.encode = la->encode; L.matrix = la->matrix;
   for (int i = 0; i < 9; i++) L.m[i] = la->m[i];
   return L;
 }
 
 // the tables a pointwise kernel holds in LDS
-size_t tables_bytes(const hm_light_args* la) { return ((size_t)4 << la->bits) * (la->encode ? 2 : 1); }
+// the dynamic LDS of a launch: the pointwise and nearest kernels hold lin, enc and the tone tables, k_light_h lin, k_light_v enc and the
+// tone tables (hm_light_lds_bytes hands these out to the tests)
+size_t tone_bytes(const hm_light_args* la) { return la->tone ? 2 * (size_t)TONE_STEPS * sizeof(float) : 0; }
+size_t h_bytes(const hm_light_args* la) { return (size_t)4 << la->bits; }
+size_t v_bytes(const hm_light_args* la) { return (la->encode ? (size_t)4 << la->enc_bits : 0) + tone_bytes(la); }
+size_t tables_bytes(const hm_light_args* la) { return h_bytes(la) + v_bytes(la); }
 
 template <int SB, int C, typename OutT, bool CHW>
 int launch_tensor(const hm_dest_plan* p, const hm_light_args* la, const uint8_t* src, int src_stride, int w, int rows, uint8_t* dst, const Affine& a, hipStream_t s)
@@ -334,6 +367,9 @@ int launch_tensor_dtype(const hm_dest_plan* p, const hm_light_args* la, const ui
   if (p->dtype == HM_DEV_F16) return chw ? launch_tensor<SB, C, __half, true>(p, la, src, src_stride, w, rows, dst, a, s) : launch_tensor<SB, C, __half, false>(p, la, src, src_stride, w, rows, dst, a, s);
   if (p->dtype == (SB == 1 ? HM_DEV_U8 : HM_DEV_U16))
     return chw ? launch_tensor<SB, C, IntT, true>(p, la, src, src_stride, w, rows, dst, a, s) : launch_tensor<SB, C, IntT, false>(p, la, src, src_stride, w, rows, dst, a, s);
+  if constexpr (SB == 2 && C == 3) // the 8-bit finish of a deeper image
+    if (p->dtype == HM_DEV_U8)
+      return chw ? launch_tensor<2, 3, uint8_t, true>(p, la, src, src_stride, w, rows, dst, a, s) : launch_tensor<2, 3, uint8_t, false>(p, la, src, src_stride, w, rows, dst, a, s);
   return hm_fail(HM_ERR_INTERNAL, "k_light_tensor: no kernel for dtype %d on %d-byte samples", p->dtype, SB);
 }
 
@@ -357,7 +393,7 @@ void launch_h(bool chw, const hm_resample_args* r, const hm_light_args* la, hipS
 {
   const dim3 grid((unsigned)((r->ow + 63) / 64), (unsigned)((r->n_h + 3) / 4)), block(256);
   const uint8_t* src = (const uint8_t*)r->src;
-  const size_t lds = (size_t)4 << la->bits;
+  const size_t lds = h_bytes(la);
   if (chw)
     hipLaunchKernelGGL((k_light_h<SB, C, true>), grid, block, lds, s, src, r->src_stride, r->n_h, r->ow, r->ax.first, r->ax.count, r->ax.weights, r->tmp,
                        (long long)r->tmp_pitch, (long long)r->tmp_plane, la->lin, la->bits);
@@ -370,7 +406,7 @@ template <typename OutT>
 void launch_v(const hm_dest_plan* p, const hm_resample_args* r, const hm_light_args* la, uint8_t* dst, const Affine& a, hipStream_t s)
 {
   const dim3 grid((unsigned)((r->ow + 63) / 64), (unsigned)((r->oh + 3) / 4)), block(256);
-  const size_t lds = la->encode ? (size_t)4 << la->bits : 0;
+  const size_t lds = v_bytes(la);
   const Light L = light_of(la);
   const bool chw = p->layout == HM_DEV_LAYOUT_CHW;
 #define HM_LV_GO(CHW_, C_) \
@@ -384,7 +420,12 @@ void launch_v(const hm_dest_plan* p, const hm_resample_args* r, const hm_light_a
 int check_args(const hm_dest_plan* p, const hm_light_args* la)
 {
   if (!la->lin || (la->encode && !la->enc) || la->bits < 8 || la->bits > 12) return hm_fail(HM_ERR_INTERNAL, "k_light: tables of %d bits", la->bits);
+  if (la->enc_bits != la->bits && la->enc_bits != 8) return hm_fail(HM_ERR_INTERNAL, "k_light: codes of %d bits from tables of %d", la->enc_bits, la->bits);
+  if (la->src_bytes != (la->bits > 8 ? 2 : 1)) return hm_fail(HM_ERR_INTERNAL, "k_light: %d-byte samples of %d bits", la->src_bytes, la->bits);
   if (p->channels != 3 && p->channels != 4) return hm_fail(HM_ERR_INTERNAL, "k_light: %d channels", p->channels);
+  // (p is the plan of the target the destination is written as: under the 8-bit finish its samples are bytes, the source's are not)
+  if (p->sample_bytes != (la->enc_bits > 8 ? 2 : 1) || (p->sample_bytes != la->src_bytes && p->channels != 3))
+    return hm_fail(HM_ERR_INTERNAL, "k_light: a %d-byte target of %d channels from %d-byte samples, codes of %d bits", p->sample_bytes, p->channels, la->src_bytes, la->enc_bits);
   const bool integer = p->dtype == HM_DEV_U8 || p->dtype == HM_DEV_U16;
   if (integer && (!la->encode || p->dtype != (p->sample_bytes == 1 ? HM_DEV_U8 : HM_DEV_U16)))
     return hm_fail(HM_ERR_INTERNAL, "k_light: integer dtype %d on %d-byte samples, %s", p->dtype, p->sample_bytes, la->encode ? "re-encoded" : "linear");
@@ -398,6 +439,21 @@ extern "C" const void* hm_light_kernel_of(int index) // (test_hooks.cpp: hm_debu
   return index >= 0 && index < (int)(sizeof(g_instances) / sizeof(g_instances[0])) ? g_instances[index] : nullptr;
 }
 
+extern "C" const void* hm_light_finish8_kernel_of(int index) // (test_hooks.cpp: hm_debug_kernel_regs)
+{
+  return index >= 0 && index < (int)(sizeof(g_finish8_instances) / sizeof(g_finish8_instances[0])) ? g_finish8_instances[index] : nullptr;
+}
+
+// what the launchers ask for as dynamic LDS (test_hooks.cpp: hm_debug_light_lds); pass 0: k_light_tensor / k_light_nearest, 1: k_light_h,
+// 2: k_light_v
+extern "C" long long hm_light_lds_bytes(int bits, int enc_bits, int encode, int tone, int pass)
+{
+  static const float some = 0.0f;
+  hm_light_args la = {};
+  la.bits = bits; la.enc_bits = enc_bits; la.encode = encode; la.tone = tone ? &some : nullptr;
+  return (long long)(pass == 0 ? tables_bytes(&la) : pass == 1 ? h_bytes(&la) : v_bytes(&la));
+}
+
 // rows [0, rows) of `src` through the light step to `dst` = the destination's first element; asynchronous on `s`
 extern "C" int hm_launch_light_tensor(const hm_dest_plan* p, const hm_light_args* la, const void* src, int src_stride, int w, int rows, void* dst,
                                       const float scale[4], const float bias[4], hipStream_t s)
@@ -408,7 +464,7 @@ extern "C" int hm_launch_light_tensor(const hm_dest_plan* p, const hm_light_args
   const Affine a = affine_of(scale, bias);
   const uint8_t* in = (const uint8_t*)src;
   uint8_t* out = (uint8_t*)dst;
-  if (p->sample_bytes == 1) return p->channels == 3 ? launch_tensor_dtype<1, 3>(p, la, in, src_stride, w, rows, out, a, s) : launch_tensor_dtype<1, 4>(p, la, in, src_stride, w, rows, out, a, s);
+  if (la->src_bytes == 1) return p->channels == 3 ? launch_tensor_dtype<1, 3>(p, la, in, src_stride, w, rows, out, a, s) : launch_tensor_dtype<1, 4>(p, la, in, src_stride, w, rows, out, a, s);
   return p->channels == 3 ? launch_tensor_dtype<2, 3>(p, la, in, src_stride, w, rows, out, a, s) : launch_tensor_dtype<2, 4>(p, la, in, src_stride, w, rows, out, a, s);
 }
 
@@ -421,8 +477,13 @@ extern "C" int hm_launch_light_nearest(const hm_dest_plan* p, const hm_light_arg
   const Affine a = affine_of(scale, bias);
   const uint8_t* in = (const uint8_t*)src;
   uint8_t* out = (uint8_t*)dst;
-  const bool wide = p->sample_bytes == 2;
-  if (p->dtype == HM_DEV_U8) launch_nearest<uint8_t, uint8_t>(p, la, in, src_stride, n_w, n_h, ow, oh, out, a, s);
+  const bool wide = la->src_bytes == 2;
+  if (p->dtype == HM_DEV_U8 && wide) { // the 8-bit finish of a deeper image (three channels: check_args)
+    const dim3 grid((unsigned)((ow + 63) / 64), (unsigned)((oh + 3) / 4)), block(256);
+    hipLaunchKernelGGL((k_light_nearest<uint16_t, 3, uint8_t>), grid, block, tables_bytes(la), s, in, src_stride, n_w, n_h, ow, oh, p->layout == HM_DEV_LAYOUT_CHW ? 1 : 0, out,
+                       (long long)p->row_pitch, (long long)p->plane_pitch, a, light_of(la));
+  }
+  else if (p->dtype == HM_DEV_U8) launch_nearest<uint8_t, uint8_t>(p, la, in, src_stride, n_w, n_h, ow, oh, out, a, s);
   else if (p->dtype == HM_DEV_U16) launch_nearest<uint16_t, uint16_t>(p, la, in, src_stride, n_w, n_h, ow, oh, out, a, s);
   else if (p->dtype == HM_DEV_F16) { if (wide) launch_nearest<uint16_t, __half>(p, la, in, src_stride, n_w, n_h, ow, oh, out, a, s); else launch_nearest<uint8_t, __half>(p, la, in, src_stride, n_w, n_h, ow, oh, out, a, s); }
   else { if (wide) launch_nearest<uint16_t, float>(p, la, in, src_stride, n_w, n_h, ow, oh, out, a, s); else launch_nearest<uint8_t, float>(p, la, in, src_stride, n_w, n_h, ow, oh, out, a, s); }

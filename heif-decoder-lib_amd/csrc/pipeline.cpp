@@ -210,6 +210,15 @@ int hm_pipeline_submit_to_device_light(hm_pipeline* p, const uint8_t* heif, size
   return submit(p, heif, size, item_id, tag, OutputTarget::to_dest(dest, view, light));
 }
 
+// (src_peak == 0, the image's own peak, is read once the file is open: submit)
+int hm_pipeline_submit_to_device_tone(hm_pipeline* p, const uint8_t* heif, size_t size, uint32_t item_id, uint64_t tag, const hm_device_view* view,
+                                      const hm_device_light* light, const hm_device_tone* tone, const hm_device_dest* dest)
+{
+  if (!p || !heif || !tone || !dest) return hm_fail(HM_ERR_INVALID_ARG, "null argument");
+  if (!light) return hm_fail(HM_ERR_INVALID_ARG, "tone: null light step");
+  return submit(p, heif, size, item_id, tag, OutputTarget::to_dest(dest, view, light, tone));
+}
+
 int hm_pipeline_submit_to_device_planes(hm_pipeline* p, const uint8_t* heif, size_t size, uint32_t item_id, uint64_t tag, const hm_device_planes* planes)
 {
   if (!p || !heif || !planes) return hm_fail(HM_ERR_INVALID_ARG, "null argument");
@@ -258,9 +267,12 @@ static int submit(hm_pipeline* p, const uint8_t* heif, size_t size, uint32_t ite
       int prev = -1;
       hipGetDevice(&prev);
       hipSetDevice(p->cfg.device); // (the pointers must belong to the device the crew works on)
-      rc = check_target_request(im->file, im->job.id, &im->job.params, target);
+      OutputTarget t = target;
+      hm_device_tone own{};
+      if (t.tone) { own = tone_for_item(im->file, im->job.id, t.tone); t.tone = &own; } // (the image's own peak, before the curve is judged)
+      rc = check_target_request(im->file, im->job.id, &im->job.params, t);
       if (prev >= 0) hipSetDevice(prev);
-      if (!rc) im->job.target.set(target);
+      if (!rc) im->job.target.set(t);
     }
     if (!rc) rc = job_plan(im->job);
   }

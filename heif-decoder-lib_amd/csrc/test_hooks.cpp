@@ -24,6 +24,8 @@ extern "C" const void* hm_resample_batch_kernel_of(int index);                  
 extern "C" const void* hm_planes_view_kernel_of(int index);                                 // planes_view.hip: NULL behind the last instance
 extern "C" const void* hm_overlay_kernel_of(int index);                                     // overlay.hip: NULL behind the last instance
 extern "C" const void* hm_light_kernel_of(int index);                                       // light.hip: NULL behind the last instance
+extern "C" const void* hm_light_finish8_kernel_of(int index);                               // ... the instances of the 8-bit finish from 16-bit samples
+extern "C" long long hm_light_lds_bytes(int bits, int enc_bits, int encode, int tone, int pass); // ... the dynamic LDS its launchers ask for
 
 extern "C" {
 
@@ -55,11 +57,19 @@ __attribute__((visibility("default"))) int hm_debug_kernel_regs(int which, int a
   else if (which == 7) fn = hm_planes_view_kernel_of(a); // (k_planes_resample_h, k_planes_resample_v, k_planes_view_nearest)
   else if (which == 8) fn = hm_overlay_kernel_of(a); // (k_overlay: RGB24, RGBA32, planes)
   else if (which == 9) fn = hm_light_kernel_of(a); // (k_light_tensor, k_light_nearest, k_light_h, k_light_v; out[1] counts scratch, not LDS)
+  else if (which == 10) fn = hm_light_finish8_kernel_of(a); // (k_light_tensor<2, 3, uint8_t, ...>, k_light_nearest<uint16_t, 3, uint8_t>)
   hipFuncAttributes fa;
   if (!fn || !out || hipFuncGetAttributes(&fa, fn) != hipSuccess) return -1;
   out[0] = fa.numRegs;
   out[1] = (int)fa.localSizeBytes;
   return 0;
+}
+
+// the dynamic LDS, in bytes, a launch of the light kernels asks for with tables of (bits, enc_bits), re-encoding or not, with a tone step or
+// not; pass 0: the pointwise and nearest kernels, 1: k_light_h, 2: k_light_v (hipFuncGetAttributes does not see dynamic LDS)
+__attribute__((visibility("default"))) long long hm_debug_light_lds(int bits, int enc_bits, int encode, int tone, int pass)
+{
+  return hm_light_lds_bytes(bits, enc_bits, encode, tone, pass);
 }
 
 // k_overlay on its own (measurement scripts: tools/bench_overlay.py): the layer table is uploaded and the kernel queued on `stream`;

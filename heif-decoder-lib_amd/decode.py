@@ -10,7 +10,10 @@ floats are sample * scale[c] + bias[c], rounded after each step.  crop=(x, y, w,
 resampled (filter "triangle": antialiased bilinear, "bicubic", "lanczos3" or "nearest") in the step that writes the tensor; of a grid only the tiles the
 rectangle touches are decoded.  light=True asks for linear light (the image's own transfer function undone by a table, floats only);
 light=dict(to_transfer="srgb", to_primaries="bt709", gain=1.0, from_transfer=..., from_primaries=...) re-encodes or changes the
-primaries - a resize under light= averages light, not code values.  What the library refuses raises capi.HmError.
+primaries - a resize under light= averages light, not code values.  tone=dict(dst_peak=203.0, src_peak=None, unit_nits=None,
+out_unit_nits=None, out_bits=None) beside light= maps the content's peak (None: the file's clli / mdcv, else 1000 cd/m2) to the
+display's with the BT.2390 curve; out_bits=8 finishes a deeper image in 8-bit codes (torch.uint8 is then accepted for it).
+What the library refuses raises capi.HmError.
 
 Planar YCbCr stays planar: decode_to_planes / decode_sequence_to_planes / decode_batch_to_planes return (Y, Cb, Cr[, A]) ("planar":
 I420 and its kin) or (Y, CbCr[, A]) ("semiplanar": NV12, P010 with msb_aligned=True) as coded or at the chroma format asked for.
@@ -145,6 +148,32 @@ def _light_of(light):
     return d
 
 
+def _tone_of(tone, lit):
+    """hm_device_tone (or None) of the tone= argument: a dict of dst_peak (needed) / src_peak / unit_nits / out_unit_nits / out_bits,
+    None standing for the library's default; needs a light step"""
+    if tone is None or tone is False:
+        return None
+    if not isinstance(tone, dict):
+        raise ValueError(f"tone {tone!r}: a dict")
+    keys = {"dst_peak", "src_peak", "unit_nits", "out_unit_nits", "out_bits"}
+    if set(tone) - keys:
+        raise ValueError(f"tone: unknown keys {sorted(set(tone) - keys)}, known are {sorted(keys)}")
+    if lit is None:
+        raise ValueError("tone: needs light= (the curve acts on linear light)")
+    if tone.get("dst_peak") is None:
+        raise ValueError("tone: dst_peak (cd/m2 of the display's peak) is needed")
+    d = capi.DeviceTone()
+    d.curve = capi.HM_TONE_BT2390
+    d.dst_peak = float(tone["dst_peak"])
+    for key in ("src_peak", "unit_nits", "out_unit_nits"):
+        v = tone.get(key)
+        if v is not None and float(v) == 0.0:
+            raise ValueError(f"tone[{key!r}] = {v!r}: None asks for the default")
+        setattr(d, key, 0.0 if v is None else float(v))
+    d.out_bits = 0 if tone.get("out_bits") is None else int(tone["out_bits"])
+    return d
+
+
 def _default_threads():
     return max(1, min(16, os.cpu_count() or 1))
 
@@ -168,13 +197,14 @@ class _File:
 
 
 def decode_to_tensor(data, item_id=0, out_format="rgb", layout="chw", dtype=None, scale=None, bias=None, out=None, stream=None,
-                     host_threads=None, crop=None, size=None, filter="triangle", light=None):
+                     host_threads=None, crop=None, size=None, filter="triangle", light=None, tone=None):
     """Decode one image of a HEIF file (bytes; item_id 0 = the primary item) into a CUDA tensor: C x H x W ("chw") or H x W x C
     ("hwc").  dtype defaults to torch.float32 (out's dtype when out is given).  out: a CUDA tensor of that shape to write into;
     its row (and plane) stride is honoured, bytes between rows are left alone.  stream: a torch.cuda.Stream or a raw stream
     handle (default: the current stream).  crop: (x, y, w, h), a rectangle of the image; size: (w, h), what it is resampled to
     (H and W of the tensor are then the size's, or the crop's); filter: "triangle", "bicubic", "lanczos3" or "nearest".  light: True (linear
-    light) or a dict (see the module's text): the light step in the write of the tensor.  Returns when the pixels are in place."""
+    light) or a dict (see the module's text): the light step in the write of the tensor; tone: a dict (see the module's text), the tone
+    step inside it.  Returns when the pixels are in place."""
     import torch
     L = capi.image_lib()
     fmt, lay = _out_format(out_format), _layout(layout)
@@ -186,6 +216,7 @@ def decode_to_tensor(data, item_id=0, out_format="rgb", layout="chw", dtype=None
         iid, w, h = f.size(item_id)
         view, w, h = _view_of(crop, size, filter, w, h)
         lit = _light_of(light)
+        ton = _tone_of(tone, lit)
         shape = _shape(lay, c, h, w)
         if out is None:
             out = torch.empty(shape, dtype=dtype, device="cuda")
@@ -201,7 +232,10 @@ def decode_to_tensor(data, item_id=0, out_format="rgb", layout="chw", dtype=None
         prm = capi.DecodeParams(fmt, host_threads or _default_threads(), 0, 0, handle or None, None, 0, 0, 0, 0)
         d = capi.Decoded()
         with torch.cuda.device(out.device):
-            if lit is not None:
+            if ton is not None:
+                capi.check_image(L.hm_decode_item_to_device_tone(f.h, iid, C.byref(prm), C.byref(view) if view is not None else None, C.byref(lit), C.byref(ton),
+                                                                 C.byref(dest), C.byref(d)))
+            elif lit is not None:
                 capi.check_image(L.hm_decode_item_to_device_light(f.h, iid, C.byref(prm), C.byref(view) if view is not None else None, C.byref(lit), C.byref(dest),
                                                                   C.byref(d)))
             elif view is None:
@@ -217,12 +251,13 @@ def decode_to_tensor(data, item_id=0, out_format="rgb", layout="chw", dtype=None
 
 
 def decode_batch_to_tensor(files, item_id=0, out_format="rgb", layout="chw", dtype=None, scale=None, bias=None, out=None,
-                           host_threads=None, max_in_flight=4, size=None, crops=None, filter="triangle", light=None):
+                           host_threads=None, max_in_flight=4, size=None, crops=None, filter="triangle", light=None, tone=None):
     """Decode N equally sized HEIF files through ONE hm_pipeline (the entropy decode of one file runs under the kernels of
     another) into one N x C x H x W ("chw") or N x H x W x C ("hwc") CUDA tensor, each image into its slice.  files: bytes
     objects or paths.  A file of another size than the first (or than `out`) raises ValueError naming it.
     size: (w, h) - files of different sizes are accepted then, each resampled into its slice; crops: one (x, y, w, h) or None per
-    file, the rectangle of that file that is resampled (needs size).  light: as decode_to_tensor, the same step for every file."""
+    file, the rectangle of that file that is resampled (needs size).  light, tone: as decode_to_tensor, the same steps for every file
+    (tone's src_peak None: each file's own)."""
     import torch
     L = capi.image_lib()
     fmt, lay = _out_format(out_format), _layout(layout)
@@ -231,6 +266,7 @@ def decode_batch_to_tensor(files, item_id=0, out_format="rgb", layout="chw", dty
     code, c = _dtype_code(dtype), _channels(fmt)
     sc, bi = _per_channel(scale, 1.0), _per_channel(bias, 0.0)
     lit = _light_of(light)
+    ton = _tone_of(tone, lit)
     names, datas = [], []
     for k, entry in enumerate(files):
         if isinstance(entry, (bytes, bytearray, memoryview)):
@@ -291,7 +327,10 @@ def decode_batch_to_tensor(files, item_id=0, out_format="rgb", layout="chw", dty
             for k, data in enumerate(datas):
                 dest = _dest_of(out[k], lay, code, c, sc, bi)
                 while True:
-                    if lit is not None:
+                    if ton is not None:
+                        rc = L.hm_pipeline_submit_to_device_tone(pipe, data, len(data), ids[k], k, C.byref(views[k]) if views[k] is not None else None,
+                                                                 C.byref(lit), C.byref(ton), C.byref(dest))
+                    elif lit is not None:
                         rc = L.hm_pipeline_submit_to_device_light(pipe, data, len(data), ids[k], k, C.byref(views[k]) if views[k] is not None else None,
                                                                   C.byref(lit), C.byref(dest))
                     elif views[k] is None:
@@ -329,13 +368,14 @@ def _frame_ids(frames, n_frames):
 
 
 def decode_sequence_to_tensor(data, frames=None, out_format="rgb", layout="chw", dtype=None, scale=None, bias=None, out=None, stream=None,
-                              host_threads=None, crop=None, size=None, filter="triangle", light=None):
+                              host_threads=None, crop=None, size=None, filter="triangle", light=None, tone=None):
     """Decode frames of an image sequence (bytes of a file with a 'moov' track) into one CUDA tensor, T x C x H x W ("chw") or
     T x H x W x C ("hwc"), in ONE device batch (hm_decode_frames_to_device_view).  frames: None (all), a range or a list of 1-based
     frame IDs, in any order, repeats allowed - range(1, n + 1, 4) is every fourth frame.  crop / size / filter: the same rectangle
     of every frame, resampled, as in decode_to_tensor; without them every frame must have the size of the first.  out: a CUDA
     tensor of that shape; the row and plane strides of each of its slices are honoured.  light: as decode_to_tensor, the same step for
-    every frame (hm_decode_frames_to_device_light).  Returns when the pixels are in place."""
+    every frame (hm_decode_frames_to_device_light); tone: as decode_to_tensor (a frame carries no light levels: src_peak None is 1000).
+    Returns when the pixels are in place."""
     import torch
     L = capi.image_lib()
     fmt, lay = _out_format(out_format), _layout(layout)
@@ -375,8 +415,12 @@ def decode_sequence_to_tensor(data, frames=None, out_format="rgb", layout="chw",
         res = (capi.Decoded * n)()
         failed = C.c_int32(-1)
         lit = _light_of(light)
+        ton = _tone_of(tone, lit)
         with torch.cuda.device(out.device):
-            if lit is not None:
+            if ton is not None:
+                rc = L.hm_decode_frames_to_device_tone(f.h, (C.c_uint32 * n)(*ids), n, C.byref(prm), C.byref(view) if view is not None else None, C.byref(lit),
+                                                       C.byref(ton), dests, res, C.byref(failed))
+            elif lit is not None:
                 rc = L.hm_decode_frames_to_device_light(f.h, (C.c_uint32 * n)(*ids), n, C.byref(prm), C.byref(view) if view is not None else None, C.byref(lit),
                                                         dests, res, C.byref(failed))
             else:

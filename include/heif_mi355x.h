@@ -749,6 +749,82 @@ HM_API int hm_light_table(int transfer, int bits, float gain, int encode, float*
 HM_API int hm_light_matrix(int from_primaries, int to_primaries, float m[9]);
 
 /* ------------------------------------------------------------------------- */
+/* Tone: the BT.2390 curve by table inside the light step, the content's peak from the file, an 8-bit finish */
+/* ------------------------------------------------------------------------- */
+
+/* A tone step exists only beside a light step.  It acts per output pixel on linear light, after the gamut matrix (under a view:
+ * after the resampling sums) and before the finish - the same for the pointwise path, HM_VIEW_NEAREST, the crop alone and a
+ * resampled view:
+ *   N = fmaxf(fmaxf(R, G), B)                   the norm: max RGB in the destination's primaries
+ *   k = |{ i in 1 .. 2047 : thr[i] <= N }|      the light step's binary search, 11 steps; N <= 0 gives k = 0
+ *   R = fmul(R, sg[k]), G and B likewise        one common factor: the hue is kept, no channel rises above the peak
+ * Alpha is untouched.  k is the 11-bit PQ code of the norm's luminance, sg the gain of the curve at that code: the gain is
+ * piecewise constant over HM_TONE_STEPS PQ steps.
+ * Tables, on the host in double with the C library's pow, each rounded once to float32; g = (double)gain of the light step,
+ * U = unit_nits, Uo = out_unit_nits, EOTF the ST 2084 function of transfer 16 above, PQ(y) = ((c1 + c2 y^m1) / (1 + c3 y^m1))^m2
+ * its inverse with the same five constants:
+ *   thr[0] = 0;  thr[i] = (float)(g * (10000 / U) * EOTF((i - 0.5) / 2047)), i = 1 .. 2047
+ *   e = k / 2047, Pw = PQ(src_peak / 10000), E1 = min(e / Pw, 1), maxLum = PQ(dst_peak / 10000) / Pw, KS = 1.5 maxLum - 0.5
+ *   maxLum >= 1, E1 < KS or k == 0: ratio = 1, exactly.  Otherwise, with T = (E1 - KS) / (1 - KS):
+ *     E2 = (2T^3 - 3T^2 + 1) KS + (T^3 - 2T^2 + T)(1 - KS) + (-2T^3 + 3T^2) maxLum,  ratio = EOTF(E2 Pw) / EOTF(e)
+ *   sg[k] = (float)(ratio * U / Uo)
+ * This is the EETF of Report ITU-R BT.2390 with both black levels at 0: the black-lift term b (1 - E2)^4 is NOT modelled.
+ * dst_peak >= src_peak is not an error: the curve is then the clamp at src_peak.
+ * src_peak == 0 is the image's own peak, from the properties of the item that is decoded (of a grid: the grid item): its clli
+ * max_content_light_level if non-zero - the field is 16 bits wide and PQ codes no light above 10000 cd/m2: a larger value counts as
+ * 10000 -; otherwise its mdcv max_display_mastering_luminance * 0.0001 if the raw value lies in 50000 .. 100000000; otherwise 1000.
+ * A frame of a sequence carries no properties: 1000.
+ * out_bits == 8, the 8-bit finish: the source samples, lin[] and the sums stay at the target's depth; enc is
+ * hm_light_table(to_transfer, 8, gain, 1) and the code counts thresholds over 1 .. 255.  The destination is judged, sized and
+ * written as that of the 8-bit sibling target (an HM_OUT_RRGGBB_LE request: hm_device_dest_bytes(HM_OUT_RGB, ...)): HM_DEV_U8 stores
+ * the code, float dtypes fadd(fmul((float)code, scale[c]), bias[c]).  With HM_LIGHT_LINEAR there is no code and out_bits only
+ * selects the sizing rule; with an 8-bit target it changes nothing.  hm_decoded reports out_format as requested, stride[0] is the
+ * row pitch in use.
+ * Refused before any work is queued, the destination unwritten - HM_ERR_INVALID_ARG: a null light step, an unknown curve, reserved
+ * != 0, a peak or unit that is not finite, not above 0 or above 10000 (0 where it stands for a default), KS < 0 (maxLum < 1 / 3: the
+ * knee would lie below black), unit_nits == 0 when the resolved from_transfer is not 16, out_bits other than 0 or 8, out_bits == 8
+ * with HM_DEV_U16; HM_ERR_UNSUPPORTED: out_bits == 8 with a four-channel target (bringing a deeper alpha plane to 8 bits under a view
+ * is a step of its own) - and everything the light, view and destination checks refuse.  One refusal waits for the decoded image, as
+ * the light step's from_* == 0 does: whether the resolved from_transfer is 16 is known once the image reports its profile, so a
+ * missing unit_nits is refused behind the decode, before a byte of the destination is written (with an explicit from_transfer, and in
+ * hm_tone_to_tensor: before any work is queued). */
+enum { HM_TONE_BT2390 = 1 };
+enum { HM_TONE_STEPS = 2048 };           /* 11-bit PQ codes */
+typedef struct hm_device_tone {
+  int32_t curve;          /* HM_TONE_BT2390 */
+  int32_t out_bits;       /* 0: the target's depth; 8: the 8-bit finish */
+  float   src_peak;       /* cd/m2 of the content's peak; 0 = the image's own (rule above) */
+  float   dst_peak;       /* cd/m2 of the display's peak, > 0 */
+  float   unit_nits;      /* cd/m2 that light value 1.0 (before gain) stands for; 0 = 10000 when the resolved from_transfer is 16 */
+  float   out_unit_nits;  /* cd/m2 that light value 1.0 stands for after the step; 0 = dst_peak */
+  int32_t reserved[2];    /* 0 */
+} hm_device_tone;
+/* the light entry points with a tone step */
+HM_API int hm_decode_item_to_device_tone(const hm_file* f, uint32_t id, const hm_decode_params* params, const hm_device_view* view,
+                                         const hm_device_light* light, const hm_device_tone* tone, const hm_device_dest* dest, hm_decoded* out);
+HM_API int hm_decode_frames_to_device_tone(const hm_file* f, const uint32_t* frames, int32_t count, const hm_decode_params* params,
+                                           const hm_device_view* view, const hm_device_light* light, const hm_device_tone* tone,
+                                           const hm_device_dest* dests, hm_decoded* out, int32_t* failed_frame);
+HM_API int hm_pipeline_submit_to_device_tone(hm_pipeline* p, const uint8_t* heif, size_t size, uint32_t item_id, uint64_t tag,
+                                             const hm_device_view* view, const hm_device_light* light, const hm_device_tone* tone,
+                                             const hm_device_dest* dest);
+/* The step on its own (as hm_light_to_tensor): src_peak, unit_nits and the light step's from_* must be explicit. */
+HM_API int hm_tone_to_tensor(int out_format, int bits, int src_w, int src_h, const void* d_src, int src_stride, const hm_device_view* view,
+                             const hm_device_light* light, const hm_device_tone* tone, const hm_device_dest* dest, void* stream);
+/* Host arithmetic, no device: the HM_TONE_STEPS entries of thr (which == 0) or sg (1) for the light step's gain.  Nothing of the
+ * tone step may be left at 0 except out_bits.  Returns HM_TONE_STEPS, or a negative status. */
+HM_API int hm_tone_table(const hm_device_tone* tone, float gain, int which, float* out);
+/* The raw fields of an item's clli and mdcv properties (ISO/IEC 23008-12; zero where the property is absent) */
+typedef struct hm_light_levels {
+  int32_t  has_clli, has_mdcv;
+  uint16_t max_content_light_level, max_pic_average_light_level;
+  uint16_t display_primaries_x[3], display_primaries_y[3];
+  uint16_t white_point_x, white_point_y;
+  uint32_t max_display_mastering_luminance, min_display_mastering_luminance;
+} hm_light_levels;
+HM_API int hm_file_item_light_levels(const hm_file* f, uint32_t id, hm_light_levels* out);
+
+/* ------------------------------------------------------------------------- */
 /* Planar views: a rectangle of the image, at a size of the caller's choice, into I420 / NV12 / P010 planes */
 /* ------------------------------------------------------------------------- */
 

@@ -187,6 +187,40 @@ HMC_API struct heif_error heif_nclx_color_profile_set_transfer_characteristics(s
 HMC_API struct heif_error heif_nclx_color_profile_set_matrix_coefficients(struct heif_color_profile_nclx* nclx, uint16_t mc);
 HMC_API struct heif_error heif_image_set_nclx_color_profile(struct heif_image* image, const struct heif_color_profile_nclx* color_profile);
 HMC_API struct heif_error heif_image_get_nclx_color_profile(const struct heif_image* image, struct heif_color_profile_nclx** out_data);
+
+/* Content light level ('clli') and mastering display colour volume ('mdcv') of a decoded image: the properties of the item that was
+ * decoded (context.cc:2087-2103), raw.  A value of 0 means undefined; has_content_light_level is "either field non-zero"
+ * (pixelimage.h:167).  The setters change the image they are handed, const or not, as the reference's do. */
+struct heif_content_light_level {
+  uint16_t max_content_light_level;
+  uint16_t max_pic_average_light_level;
+};
+struct heif_mastering_display_colour_volume {
+  uint16_t display_primaries_x[3];
+  uint16_t display_primaries_y[3];
+  uint16_t white_point_x;
+  uint16_t white_point_y;
+  uint32_t max_display_mastering_luminance;
+  uint32_t min_display_mastering_luminance;
+};
+struct heif_decoded_mastering_display_colour_volume {
+  float display_primaries_x[3];
+  float display_primaries_y[3];
+  float white_point_x;
+  float white_point_y;
+  double max_display_mastering_luminance;
+  double min_display_mastering_luminance;
+};
+HMC_API int heif_image_has_content_light_level(const struct heif_image*);
+HMC_API void heif_image_get_content_light_level(const struct heif_image*, struct heif_content_light_level* out);
+HMC_API void heif_image_set_content_light_level(const struct heif_image*, const struct heif_content_light_level* in);
+HMC_API int heif_image_has_mastering_display_colour_volume(const struct heif_image*);
+HMC_API void heif_image_get_mastering_display_colour_volume(const struct heif_image*, struct heif_mastering_display_colour_volume* out);
+HMC_API void heif_image_set_mastering_display_colour_volume(const struct heif_image*, const struct heif_mastering_display_colour_volume* in);
+/* raw -> normalised values; out-of-range fields decode to 0 = undefined: x outside 5 .. 37000, y outside 5 .. 42000 (units of 0.00002),
+ * the maximum outside 50000 .. 100000000, the minimum outside 1 .. 50000 (units of 0.0001 cd/m2) */
+HMC_API struct heif_error heif_mastering_display_colour_volume_decode(const struct heif_mastering_display_colour_volume* in,
+                                                                      struct heif_decoded_mastering_display_colour_volume* out);
 /* heif.h:1333-1360, heif.cc:1768-1793, 1931-2003: colour profile type and raw (ICC) profile of handles and images */
 enum heif_color_profile_type {
   heif_color_profile_type_not_present = 0, heif_color_profile_type_nclx = 0x6E636C78 /* 'nclx' */,
