@@ -448,6 +448,29 @@ static int view_tables(const hm_view_plan* vp, size_t extra, hm_view_scratch* sc
   return HM_OK;
 }
 
+// The arguments of both passes of a resampled view: the view vp of samples of `sample_bytes` bytes (origin: the crop's first sample,
+// NULL for a batch), the device tap block `taps` as view_tables lays it out (words_x words of the x axis, then the y axis; tx and ty
+// taps) and the destination plan p, which also decides the float32 intermediate: laid out like the destination, its pitch a
+// multiple of 16 elements, one plane of vp->h rows per channel for CHW.  tmp stays NULL: the caller sizes it by tmp_plane.
+static hm_resample_args resample_args_of(const hm_view_plan* vp, int sample_bytes, const void* origin, int src_stride, const void* taps, size_t words_x, int tx,
+                                         int ty, const hm_dest_plan& p)
+{
+  hm_resample_args a;
+  std::memset(&a, 0, sizeof(a));
+  a.sample_bytes = sample_bytes; a.channels = p.channels;
+  a.src = origin; a.src_stride = src_stride;
+  a.n_w = vp->w; a.n_h = vp->h; a.ow = vp->ow; a.oh = vp->oh;
+  const int32_t* dx = (const int32_t*)taps;
+  const int32_t* dy = dx + words_x;
+  a.ax.first = dx; a.ax.count = dx + vp->ow; a.ax.weights = reinterpret_cast<const float*>(dx + 2 * (size_t)vp->ow); a.ax.m = vp->ow; a.ax.taps = tx;
+  a.ay.first = dy; a.ay.count = dy + vp->oh; a.ay.weights = reinterpret_cast<const float*>(dy + 2 * (size_t)vp->oh); a.ay.m = vp->oh; a.ay.taps = ty;
+  const int64_t E = p.layout == HM_DEV_LAYOUT_CHW ? vp->ow : (int64_t)vp->ow * p.channels;
+  a.tmp_pitch = (E + 15) / 16 * 16; a.tmp_plane = a.tmp_pitch * vp->h;
+  return a;
+}
+// ... and the floats of that intermediate for one frame
+static size_t resample_tmp_floats(const hm_resample_args& a, const hm_dest_plan& p) { return (size_t)a.tmp_plane * (p.layout == HM_DEV_LAYOUT_CHW ? p.channels : 1); }
+
 int hm_view_write(const hm_device_dest* d, int out_format, const hm_view_plan* vp, const void* src, int src_stride, hipStream_t s, hm_view_scratch* sc)
 {
   hm_dest_plan p;
@@ -466,20 +489,11 @@ int hm_view_write(const hm_device_dest* d, int out_format, const hm_view_plan* v
   if ((rc = view_tables(vp, 0, sc, &words_x, &words_y, &tx, &ty, &staged))) return rc;
   const size_t bytes = (words_x + words_y) * 4;
   int32_t* host = (int32_t*)sc->pinned;
-  const bool chw = p.layout == HM_DEV_LAYOUT_CHW;
-  const int64_t E = chw ? vp->ow : (int64_t)vp->ow * p.channels, pitch = (E + 15) / 16 * 16, plane = pitch * vp->h;
-  if (!(sc->dev[0] = hm_pool_device_alloc(bytes)) || !(sc->dev[1] = hm_pool_device_alloc((size_t)plane * (chw ? p.channels : 1) * sizeof(float)))) return HM_ERR_NO_DEVICE;
+  if (!(sc->dev[0] = hm_pool_device_alloc(bytes))) return HM_ERR_NO_DEVICE;
+  hm_resample_args a = resample_args_of(vp, p.sample_bytes, origin, src_stride, sc->dev[0], words_x, tx, ty, p);
+  if (!(sc->dev[1] = hm_pool_device_alloc(resample_tmp_floats(a, p) * sizeof(float)))) return HM_ERR_NO_DEVICE;
   if ((rc = hm_check_hip(hipMemcpyAsync(sc->dev[0], host, bytes, hipMemcpyHostToDevice, s), "upload of the tap tables"))) return rc;
-  hm_resample_args a;
-  std::memset(&a, 0, sizeof(a));
-  a.sample_bytes = p.sample_bytes; a.channels = p.channels;
-  a.src = origin; a.src_stride = src_stride;
-  a.n_w = vp->w; a.n_h = vp->h; a.ow = vp->ow; a.oh = vp->oh;
-  const int32_t* dx = (const int32_t*)sc->dev[0];
-  const int32_t* dy = dx + words_x;
-  a.ax.first = dx; a.ax.count = dx + vp->ow; a.ax.weights = reinterpret_cast<const float*>(dx + 2 * (size_t)vp->ow); a.ax.m = vp->ow; a.ax.taps = tx;
-  a.ay.first = dy; a.ay.count = dy + vp->oh; a.ay.weights = reinterpret_cast<const float*>(dy + 2 * (size_t)vp->oh); a.ay.m = vp->oh; a.ay.taps = ty;
-  a.tmp = (float*)sc->dev[1]; a.tmp_pitch = pitch; a.tmp_plane = plane;
+  a.tmp = (float*)sc->dev[1];
   a.staged = staged ? 1 : 0; a.stage_px = hm_knob(HM_KNOB_VIEW_STAGE_PX);
   return hm_launch_resample(&p, &a, d->ptr, d->scale, d->bias, s);
 }
@@ -509,22 +523,15 @@ static int view_write_group(const hm_view_item* it, const int* idx, int m, const
     vec = vec && ((uintptr_t)f.dest->ptr % 16) == 0;
   }
   vec = vec && (p.row_pitch % 16) == 0 && (!chw || (p.plane_pitch % 16) == 0);
+  if (!(sc->dev[0] = hm_pool_device_alloc((size_t)lay.bytes))) return HM_ERR_NO_DEVICE;
+  hm_resample_args a = resample_args_of(vp, p.sample_bytes, nullptr, it[idx[0]].src_stride, sc->dev[0], words_x, tx, ty, p);
   // the intermediate of one chunk of frames, reused chunk after chunk in stream order
-  const int64_t E = chw ? vp->ow : (int64_t)vp->ow * p.channels, pitch = (E + 15) / 16 * 16, plane = pitch * vp->h, frame_stride = plane * planes;
+  const int64_t frame_stride = (int64_t)resample_tmp_floats(a, p);
   const int64_t bound = hm_knob(HM_KNOB_VIEW_BATCH_BYTES);
   const int per_chunk = (int)std::min<int64_t>(m, hm_view_chunk_frames(vp->ow, vp->h, p.channels, planes, bound));
-  if (!(sc->dev[0] = hm_pool_device_alloc((size_t)lay.bytes)) || !(sc->dev[1] = hm_pool_device_alloc((size_t)frame_stride * per_chunk * sizeof(float)))) return HM_ERR_NO_DEVICE;
+  if (!(sc->dev[1] = hm_pool_device_alloc((size_t)frame_stride * per_chunk * sizeof(float)))) return HM_ERR_NO_DEVICE;
   if ((rc = hm_check_hip(hipMemcpyAsync(sc->dev[0], host, (size_t)lay.bytes, hipMemcpyHostToDevice, s), "upload of the tap tables"))) return rc;
-  hm_resample_args a;
-  std::memset(&a, 0, sizeof(a));
-  a.sample_bytes = p.sample_bytes; a.channels = p.channels;
-  a.src = nullptr; a.src_stride = it[idx[0]].src_stride;
-  a.n_w = vp->w; a.n_h = vp->h; a.ow = vp->ow; a.oh = vp->oh;
-  const int32_t* dx = (const int32_t*)sc->dev[0];
-  const int32_t* dy = dx + words_x;
-  a.ax.first = dx; a.ax.count = dx + vp->ow; a.ax.weights = reinterpret_cast<const float*>(dx + 2 * (size_t)vp->ow); a.ax.m = vp->ow; a.ax.taps = tx;
-  a.ay.first = dy; a.ay.count = dy + vp->oh; a.ay.weights = reinterpret_cast<const float*>(dy + 2 * (size_t)vp->oh); a.ay.m = vp->oh; a.ay.taps = ty;
-  a.tmp = (float*)sc->dev[1]; a.tmp_pitch = pitch; a.tmp_plane = plane;
+  a.tmp = (float*)sc->dev[1];
   a.staged = staged ? 1 : 0; a.stage_px = hm_knob(HM_KNOB_VIEW_STAGE_PX);
   const void* const* dsrc = reinterpret_cast<const void* const*>((const uint8_t*)sc->dev[0] + lay.src_off);
   void* const* ddst = reinterpret_cast<void* const*>((uint8_t*)sc->dev[0] + lay.dst_off);
@@ -946,21 +953,12 @@ int hm_light_write(const hm_device_dest* d, int out_format, int w, int h, const 
   const size_t tap_bytes = (words_x + words_y) * 4, bytes = tap_bytes + table_bytes;
   int32_t* host = (int32_t*)sc->pinned;
   fill(reinterpret_cast<float*>(host + words_x + words_y));
-  const bool chw = p.layout == HM_DEV_LAYOUT_CHW;
-  const int64_t E = chw ? vp->ow : (int64_t)vp->ow * p.channels, pitch = (E + 15) / 16 * 16, plane = pitch * vp->h;
-  if (!(sc->dev[0] = hm_pool_device_alloc(bytes)) || !(sc->dev[1] = hm_pool_device_alloc((size_t)plane * (chw ? p.channels : 1) * sizeof(float)))) return HM_ERR_NO_DEVICE;
+  if (!(sc->dev[0] = hm_pool_device_alloc(bytes))) return HM_ERR_NO_DEVICE;
+  hm_resample_args a = resample_args_of(vp, src_bytes, origin, src_stride, sc->dev[0], words_x, tx, ty, p);
+  if (!(sc->dev[1] = hm_pool_device_alloc(resample_tmp_floats(a, p) * sizeof(float)))) return HM_ERR_NO_DEVICE;
   if ((rc = hm_check_hip(hipMemcpyAsync(sc->dev[0], host, bytes, hipMemcpyHostToDevice, s), "upload of the tap and light tables"))) return rc;
-  hm_resample_args a;
-  std::memset(&a, 0, sizeof(a));
-  a.sample_bytes = src_bytes; a.channels = p.channels;
-  a.src = origin; a.src_stride = src_stride;
-  a.n_w = vp->w; a.n_h = vp->h; a.ow = vp->ow; a.oh = vp->oh;
-  const int32_t* dx = (const int32_t*)sc->dev[0];
-  const int32_t* dy = dx + words_x;
-  a.ax.first = dx; a.ax.count = dx + vp->ow; a.ax.weights = reinterpret_cast<const float*>(dx + 2 * (size_t)vp->ow); a.ax.m = vp->ow; a.ax.taps = tx;
-  a.ay.first = dy; a.ay.count = dy + vp->oh; a.ay.weights = reinterpret_cast<const float*>(dy + 2 * (size_t)vp->oh); a.ay.m = vp->oh; a.ay.taps = ty;
-  a.tmp = (float*)sc->dev[1]; a.tmp_pitch = pitch; a.tmp_plane = plane;
-  point(reinterpret_cast<const float*>(dy + words_y));
+  a.tmp = (float*)sc->dev[1];
+  point(reinterpret_cast<const float*>(sc->dev[0]) + words_x + words_y);
   return hm_launch_light_resample(&p, &la, &a, d->ptr, d->scale, d->bias, s);
 }
 

@@ -6,8 +6,8 @@
 //                    group is 16 bytes of output per channel plane, 16-byte stores where pointers and pitches allow, the scalar
 //                    instance (lane l takes pixels l, l + 64, ...) otherwise.  The crop alone runs here on the offset source.
 //   k_light_nearest  HM_VIEW_NEAREST: the pixel at (j * n_w / ow, k * n_h / oh) through the same per-pixel step.
-//   k_light_h        k_resample_h's sums in its order with the table lookup in place of the conversion to float (alpha: the
-//                    conversion as it was).  The unstaged form, for all three filters.
+//   k_light_h        k_resample_h's body (resample_h_body, out_rows.h: its sums in its order) with the table lookup in place of the
+//                    conversion to float (alpha: the conversion as it was).  The unstaged form, for all three filters.
 //   k_light_v        the vertical sums of ONE pixel per lane - the matrix needs R, G and B together: a CHW intermediate is read at
 //                    one index of three planes -, then matrix and finish.
 // The tone step (hm_device_tone) sits between matrix and finish: the max of R, G, B is searched in thr[2048] like a code in enc, and
@@ -17,17 +17,14 @@
 // that meet the same entry are served by one broadcast, different entries of one bank serialise - a flat image is the best case,
 // noise the worst; no layout of a table changes that.
 // The matrix and the scalars of the step are kernel arguments (SGPRs).  -ffp-contract=off, __fmul_rn / __fadd_rn throughout.
-#include <hip/hip_runtime.h>
-#include <hip/hip_fp16.h>
-#include <stdint.h>
-
-#include <type_traits>
-
+// What is stored is out_elem.h's: a code value is `moved`, linear light goes through `linear_out`, a resampled alpha value through
+// `finish`.
 #include "hm_devdest.h"
+#include "out_launch.h"
+#include "out_rows.h"
 
 namespace {
 
-struct Affine { float scale[4], bias[4]; };
 // ebits: of the codes of enc (bits, or 8 under the 8-bit finish); tone: thr[TONE_STEPS], then sg[TONE_STEPS] (NULL: no tone step)
 struct Light { const float* lin; const float* enc; const float* tone; int bits, ebits, encode, matrix; float m[9]; };
 constexpr int TONE_STEPS = HM_TONE_STEPS;
@@ -41,25 +38,6 @@ __device__ __forceinline__ void fill_tables(float* lds, const float* __restrict_
   if (c) for (int i = threadIdx.x; i < nc; i += 256) lds[na + nb + i] = c[i];
   __syncthreads();
 }
-
-// a code value that is stored (k_to_tensor's rule for a sample that is moved)
-template <typename OutT> __device__ __forceinline__ OutT moved(unsigned v, float sc, float bi);
-template <> __device__ __forceinline__ uint8_t moved<uint8_t>(unsigned v, float, float) { return (uint8_t)v; }
-template <> __device__ __forceinline__ uint16_t moved<uint16_t>(unsigned v, float, float) { return (uint16_t)v; }
-template <> __device__ __forceinline__ float moved<float>(unsigned v, float sc, float bi) { return __fadd_rn(__fmul_rn((float)v, sc), bi); }
-template <> __device__ __forceinline__ __half moved<__half>(unsigned v, float sc, float bi) { return __float2half_rn(__fadd_rn(__fmul_rn((float)v, sc), bi)); }
-
-// linear light that is stored (float dtypes: the host refuses HM_LIGHT_LINEAR with an integer one)
-template <typename OutT> __device__ __forceinline__ OutT linear_out(float r, float sc, float bi) { return (OutT)0; }
-template <> __device__ __forceinline__ float linear_out<float>(float r, float sc, float bi) { return __fadd_rn(__fmul_rn(r, sc), bi); }
-template <> __device__ __forceinline__ __half linear_out<__half>(float r, float sc, float bi) { return __float2half_rn(__fadd_rn(__fmul_rn(r, sc), bi)); }
-
-// a resampled alpha value (k_resample_v's finish)
-template <typename OutT> __device__ __forceinline__ OutT alpha_out(float r, float sc, float bi);
-template <> __device__ __forceinline__ uint8_t alpha_out<uint8_t>(float r, float, float) { const int v = (int)__fadd_rn(r, 0.5f); return (uint8_t)min(max(v, 0), 255); }
-template <> __device__ __forceinline__ uint16_t alpha_out<uint16_t>(float r, float, float) { const int v = (int)__fadd_rn(r, 0.5f); return (uint16_t)min(max(v, 0), 65535); }
-template <> __device__ __forceinline__ float alpha_out<float>(float r, float sc, float bi) { return __fadd_rn(__fmul_rn(r, sc), bi); }
-template <> __device__ __forceinline__ __half alpha_out<__half>(float r, float sc, float bi) { return __float2half_rn(__fadd_rn(__fmul_rn(r, sc), bi)); }
 
 // |{c in 1 .. peak : enc[c] <= r}|: enc rises, so the count is the largest c whose threshold r has reached (0: none; a NaN: none)
 __device__ __forceinline__ unsigned encode_of(const float* enc, int bits, float r)
@@ -116,10 +94,6 @@ __device__ __forceinline__ void pixel(const Light& L, const float* lds, unsigned
   if constexpr (C == 4) o[3] = moved<OutT>(v3, a.scale[3], a.bias[3]);
 }
 
-template <int BYTES> struct LoadWord { typedef uint32_t type; };
-template <> struct LoadWord<16> { typedef uint4 type; };
-template <> struct LoadWord<8> { typedef uint2 type; };
-
 // SB: bytes per input sample (1 / 2, little-endian), C: channels, CHW: one plane per channel, VEC: 16-byte accesses allowed (the
 // launcher has checked the alignment of both sides).  grid: x = groups of 64 pixel groups, y = groups of 4 rows; dynamic LDS: the tables.
 template <int SB, int C, typename OutT, bool CHW, bool VEC>
@@ -144,10 +118,7 @@ __global__ __launch_bounds__(256) void k_light_tensor(const uint8_t* __restrict_
       OutT o[C];
       pixel<C, OutT>(L, lds, ip[0], ip[1], ip[2], C == 4 ? ip[C - 1] : 0u, a, o);
 #pragma unroll
-      for (int c = 0; c < C; c++) {
-        OutT* op = CHW ? reinterpret_cast<OutT*>(orow + (long long)c * plane_pitch) + x : reinterpret_cast<OutT*>(orow) + (size_t)x * C + c;
-        *op = o[c];
-      }
+      for (int c = 0; c < C; c++) *elem_at<OutT>(orow, CHW, plane_pitch, x, c, C) = o[c];
     }
     return;
   }
@@ -171,18 +142,12 @@ __global__ __launch_bounds__(256) void k_light_tensor(const uint8_t* __restrict_
         OutT oc[P];
 #pragma unroll
         for (int i = 0; i < P; i++) oc[i] = o[i * C + c];
-        uint4 v;
-        __builtin_memcpy(&v, oc, 16);
-        *reinterpret_cast<uint4*>(orow + (long long)c * plane_pitch + (size_t)x0 * sizeof(OutT)) = v;
+        store16(elem_at<OutT>(orow, true, plane_pitch, x0, c, C), oc);
       }
     }
     else {
 #pragma unroll
-      for (int k = 0; k < C; k++) { // P * C elements in a row: C stores of P elements
-        uint4 v;
-        __builtin_memcpy(&v, &o[k * P], 16);
-        reinterpret_cast<uint4*>(orow + (size_t)x0 * (C * sizeof(OutT)))[k] = v;
-      }
+      for (int k = 0; k < C; k++) store16(elem_at<OutT>(orow, false, 0, x0, 0, C) + k * P, &o[k * P]); // P * C elements in a row: C stores of P elements
     }
     return;
   }
@@ -193,10 +158,7 @@ __global__ __launch_bounds__(256) void k_light_tensor(const uint8_t* __restrict_
     OutT o[C];
     pixel<C, OutT>(L, lds, ip[i * C], ip[i * C + 1], ip[i * C + 2], C == 4 ? ip[i * C + C - 1] : 0u, a, o);
 #pragma unroll
-    for (int c = 0; c < C; c++) {
-      OutT* op = CHW ? reinterpret_cast<OutT*>(orow + (long long)c * plane_pitch) + (x0 + i) : reinterpret_cast<OutT*>(orow) + (size_t)(x0 + i) * C + c;
-      *op = o[c];
-    }
+    for (int c = 0; c < C; c++) *elem_at<OutT>(orow, CHW, plane_pitch, x0 + i, c, C) = o[c];
   }
 }
 
@@ -215,45 +177,25 @@ __global__ __launch_bounds__(256) void k_light_nearest(const uint8_t* __restrict
   pixel<C, OutT>(L, lds, in[0], in[1], in[2], C == 4 ? in[C - 1] : 0u, a, o);
   uint8_t* orow = dst + (long long)k * row_pitch;
 #pragma unroll
-  for (int c = 0; c < C; c++) {
-    OutT* op = chw ? reinterpret_cast<OutT*>(orow + (long long)c * plane_pitch) + j : reinterpret_cast<OutT*>(orow) + (size_t)j * C + c;
-    *op = o[c];
-  }
+  for (int c = 0; c < C; c++) *elem_at<OutT>(orow, chw, plane_pitch, j, c, C) = o[c];
 }
 
-// k_resample_h with lin[min(v, peak)] in place of (float)v on the colour channels.  grid: x = groups of 64 output columns, y = groups
-// of 4 source rows; src points at the crop's origin; dynamic LDS: lin.
+// the sample-to-float step of k_light_h: the colour channels through lin (in LDS), alpha converted as it is
+struct LinLookup {
+  const float* lin; unsigned peak;
+  __device__ __forceinline__ float operator()(unsigned v, int c) const { return c < 3 ? lin[min(v, peak)] : (float)v; }
+};
+
+// resample_h_body (out_rows.h: k_resample_h's sums in its order) with lin[min(v, peak)] in place of (float)v on the colour channels.
+// grid: x = groups of 64 output columns, y = groups of 4 source rows; src points at the crop's origin; dynamic LDS: lin.
 template <int SB, int C, bool CHW>
 __global__ __launch_bounds__(256) void k_light_h(const uint8_t* __restrict__ src, int src_stride, int n_h, int ow, const int32_t* __restrict__ first,
                                                  const int32_t* __restrict__ count, const float* __restrict__ wts, float* __restrict__ tmp,
                                                  long long pitch, long long plane, const float* __restrict__ lin, int bits)
 {
   extern __shared__ __attribute__((aligned(16))) float lds[];
-  typedef typename std::conditional<SB == 1, uint8_t, uint16_t>::type InT;
   fill_tables(lds, lin, 1 << bits, nullptr, 0, nullptr, 0);
-  const unsigned peak = (1u << bits) - 1u;
-  const int j = blockIdx.x * 64 + (threadIdx.x & 63), y = blockIdx.y * 4 + (threadIdx.x >> 6);
-  if (j >= ow || y >= n_h) return;
-  const InT* in = reinterpret_cast<const InT*>(src + (size_t)y * src_stride) + (size_t)first[j] * C;
-  const int n = count[j];
-  float t[C];
-#pragma unroll
-  for (int c = 0; c < C; c++) t[c] = 0.0f;
-  for (int i = 0; i < n; i++) {
-    const float w = wts[(size_t)i * ow + j];
-#pragma unroll
-    for (int c = 0; c < C; c++) {
-      const unsigned v = in[i * C + c];
-      const float a = c < 3 ? lds[min(v, peak)] : (float)v;
-      t[c] = __fadd_rn(t[c], __fmul_rn(w, a));
-    }
-  }
-  float* o = tmp + (long long)y * pitch;
-#pragma unroll
-  for (int c = 0; c < C; c++) {
-    if (CHW) o[(long long)c * plane + j] = t[c];
-    else o[(size_t)j * C + c] = t[c];
-  }
+  resample_h_body<SB, C, CHW>(src, src_stride, n_h, ow, first, count, wts, tmp, pitch, plane, LinLookup{lds, (1u << bits) - 1u});
 }
 
 // The vertical pass: a lane is ONE output pixel, a wave 64 consecutive pixels of one output row, so the taps are wave-uniform and
@@ -285,13 +227,10 @@ __global__ __launch_bounds__(256) void k_light_v(const float* __restrict__ tmp, 
   OutT o[C];
 #pragma unroll
   for (int c = 0; c < 3; c++) o[c] = colour_out<OutT>(L, lds, acc[c], a.scale[c], a.bias[c]);
-  if constexpr (C == 4) o[3] = alpha_out<OutT>(acc[3], a.scale[3], a.bias[3]);
+  if constexpr (C == 4) o[3] = finish<OutT>(acc[3], a.scale[3], a.bias[3], full_peak<OutT>()); // a resampled alpha value: k_resample_v's finish
   uint8_t* orow = dst + (long long)k * row_pitch;
 #pragma unroll
-  for (int c = 0; c < C; c++) {
-    OutT* op = CHW ? reinterpret_cast<OutT*>(orow + (long long)c * plane_pitch) + j : reinterpret_cast<OutT*>(orow) + (size_t)j * C + c;
-    *op = o[c];
-  }
+  for (int c = 0; c < C; c++) *elem_at<OutT>(orow, CHW, plane_pitch, j, c, C) = o[c];
 }
 
 // every instance the launchers below can pick (hm_debug_kernel_regs): 48 pointwise, 12 nearest, 8 horizontal, 16 vertical
@@ -316,13 +255,6 @@ const void* const g_finish8_instances[] = {
 #undef HM_LT_SET
 #undef HM_LN_SET
 #undef HM_LV_SET
-
-Affine affine_of(const float scale[4], const float bias[4])
-{
-  Affine a;
-  for (int c = 0; c < 4; c++) { a.scale[c] = scale[c]; a.bias[c] = bias[c]; }
-  return a;
-}
 
 Light light_of(const hm_light_args* la)
 {
@@ -358,34 +290,37 @@ int launch_tensor(const hm_dest_plan* p, const hm_light_args* la, const uint8_t*
   return hm_check_hip(hipGetLastError(), "k_light_tensor launch");
 }
 
+// a float type, the integer type of the samples' own width, or bytes from a deeper three-channel image (the 8-bit finish); nothing else
 template <int SB, int C>
 int launch_tensor_dtype(const hm_dest_plan* p, const hm_light_args* la, const uint8_t* src, int src_stride, int w, int rows, uint8_t* dst, const Affine& a, hipStream_t s)
 {
-  typedef typename std::conditional<SB == 1, uint8_t, uint16_t>::type IntT;
   const bool chw = p->layout == HM_DEV_LAYOUT_CHW;
-  if (p->dtype == HM_DEV_F32) return chw ? launch_tensor<SB, C, float, true>(p, la, src, src_stride, w, rows, dst, a, s) : launch_tensor<SB, C, float, false>(p, la, src, src_stride, w, rows, dst, a, s);
-  if (p->dtype == HM_DEV_F16) return chw ? launch_tensor<SB, C, __half, true>(p, la, src, src_stride, w, rows, dst, a, s) : launch_tensor<SB, C, __half, false>(p, la, src, src_stride, w, rows, dst, a, s);
-  if (p->dtype == (SB == 1 ? HM_DEV_U8 : HM_DEV_U16))
-    return chw ? launch_tensor<SB, C, IntT, true>(p, la, src, src_stride, w, rows, dst, a, s) : launch_tensor<SB, C, IntT, false>(p, la, src, src_stride, w, rows, dst, a, s);
-  if constexpr (SB == 2 && C == 3) // the 8-bit finish of a deeper image
-    if (p->dtype == HM_DEV_U8)
-      return chw ? launch_tensor<2, 3, uint8_t, true>(p, la, src, src_stride, w, rows, dst, a, s) : launch_tensor<2, 3, uint8_t, false>(p, la, src, src_stride, w, rows, dst, a, s);
+  const int rc = with_dtype(p->dtype, [&](auto tag) -> int {
+    typedef typename decltype(tag)::type OutT;
+    if constexpr (!std::is_integral<OutT>::value || sizeof(OutT) == SB || (SB == 2 && C == 3))
+      return chw ? launch_tensor<SB, C, OutT, true>(p, la, src, src_stride, w, rows, dst, a, s) : launch_tensor<SB, C, OutT, false>(p, la, src, src_stride, w, rows, dst, a, s);
+    return NO_KERNEL_INSTANCE;
+  });
+  if (rc != NO_KERNEL_INSTANCE) return rc;
   return hm_fail(HM_ERR_INTERNAL, "k_light_tensor: no kernel for dtype %d on %d-byte samples", p->dtype, SB);
 }
 
 template <typename InT, typename OutT>
-void launch_nearest(const hm_dest_plan* p, const hm_light_args* la, const uint8_t* src, int src_stride, int n_w, int n_h, int ow, int oh, uint8_t* dst, const Affine& a,
+int launch_nearest(const hm_dest_plan* p, const hm_light_args* la, const uint8_t* src, int src_stride, int n_w, int n_h, int ow, int oh, uint8_t* dst, const Affine& a,
                     hipStream_t s)
 {
   const dim3 grid((unsigned)((ow + 63) / 64), (unsigned)((oh + 3) / 4)), block(256);
   const int chw = p->layout == HM_DEV_LAYOUT_CHW ? 1 : 0;
   const Light L = light_of(la);
+  constexpr bool finish8 = sizeof(InT) == 2 && sizeof(OutT) == 1; // the 8-bit finish of a deeper image: three channels only (check_args)
   if (p->channels == 3)
     hipLaunchKernelGGL((k_light_nearest<InT, 3, OutT>), grid, block, tables_bytes(la), s, src, src_stride, n_w, n_h, ow, oh, chw, dst, (long long)p->row_pitch,
                        (long long)p->plane_pitch, a, L);
+  else if constexpr (finish8) return NO_KERNEL_INSTANCE;
   else
     hipLaunchKernelGGL((k_light_nearest<InT, 4, OutT>), grid, block, tables_bytes(la), s, src, src_stride, n_w, n_h, ow, oh, chw, dst, (long long)p->row_pitch,
                        (long long)p->plane_pitch, a, L);
+  return HM_OK;
 }
 
 template <int SB, int C>
@@ -478,15 +413,14 @@ extern "C" int hm_launch_light_nearest(const hm_dest_plan* p, const hm_light_arg
   const uint8_t* in = (const uint8_t*)src;
   uint8_t* out = (uint8_t*)dst;
   const bool wide = la->src_bytes == 2;
-  if (p->dtype == HM_DEV_U8 && wide) { // the 8-bit finish of a deeper image (three channels: check_args)
-    const dim3 grid((unsigned)((ow + 63) / 64), (unsigned)((oh + 3) / 4)), block(256);
-    hipLaunchKernelGGL((k_light_nearest<uint16_t, 3, uint8_t>), grid, block, tables_bytes(la), s, in, src_stride, n_w, n_h, ow, oh, p->layout == HM_DEV_LAYOUT_CHW ? 1 : 0, out,
-                       (long long)p->row_pitch, (long long)p->plane_pitch, a, light_of(la));
-  }
-  else if (p->dtype == HM_DEV_U8) launch_nearest<uint8_t, uint8_t>(p, la, in, src_stride, n_w, n_h, ow, oh, out, a, s);
-  else if (p->dtype == HM_DEV_U16) launch_nearest<uint16_t, uint16_t>(p, la, in, src_stride, n_w, n_h, ow, oh, out, a, s);
-  else if (p->dtype == HM_DEV_F16) { if (wide) launch_nearest<uint16_t, __half>(p, la, in, src_stride, n_w, n_h, ow, oh, out, a, s); else launch_nearest<uint8_t, __half>(p, la, in, src_stride, n_w, n_h, ow, oh, out, a, s); }
-  else { if (wide) launch_nearest<uint16_t, float>(p, la, in, src_stride, n_w, n_h, ow, oh, out, a, s); else launch_nearest<uint8_t, float>(p, la, in, src_stride, n_w, n_h, ow, oh, out, a, s); }
+  // 16-bit elements from 16-bit samples only; bytes from either width (from 16-bit samples: the 8-bit finish); floats from either
+  const int found = with_dtype(p->dtype, [&](auto tag) -> int {
+    typedef typename decltype(tag)::type OutT;
+    if (wide) return launch_nearest<uint16_t, OutT>(p, la, in, src_stride, n_w, n_h, ow, oh, out, a, s);
+    if constexpr (!std::is_same<OutT, uint16_t>::value) return launch_nearest<uint8_t, OutT>(p, la, in, src_stride, n_w, n_h, ow, oh, out, a, s);
+    return NO_KERNEL_INSTANCE;
+  });
+  if (found == NO_KERNEL_INSTANCE) return hm_fail(HM_ERR_INTERNAL, "k_light_nearest: no kernel for dtype %d on %d-byte samples", p->dtype, la->src_bytes);
   return hm_check_hip(hipGetLastError(), "k_light_nearest launch");
 }
 
@@ -503,12 +437,7 @@ extern "C" int hm_launch_light_resample(const hm_dest_plan* p, const hm_light_ar
   if ((rc = hm_check_hip(hipGetLastError(), "k_light_h launch"))) return rc;
   const Affine a = affine_of(scale, bias);
   uint8_t* out = (uint8_t*)dst;
-  switch (p->dtype) {
-    case HM_DEV_U8: launch_v<uint8_t>(p, r, la, out, a, s); break;
-    case HM_DEV_U16: launch_v<uint16_t>(p, r, la, out, a, s); break;
-    case HM_DEV_F16: launch_v<__half>(p, r, la, out, a, s); break;
-    case HM_DEV_F32: launch_v<float>(p, r, la, out, a, s); break;
-    default: return hm_fail(HM_ERR_INTERNAL, "k_light_v: no kernel for dtype %d", p->dtype);
-  }
+  const int found = with_dtype(p->dtype, [&](auto tag) -> int { launch_v<typename decltype(tag)::type>(p, r, la, out, a, s); return HM_OK; });
+  if (found == NO_KERNEL_INSTANCE) return hm_fail(HM_ERR_INTERNAL, "k_light_v: no kernel for dtype %d", p->dtype);
   return hm_check_hip(hipGetLastError(), "k_light_v launch");
 }

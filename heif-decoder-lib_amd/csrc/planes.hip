@@ -1,7 +1,7 @@
 // planes.hip — the planes of a decoded image (Y, Cb, Cr, alpha: the library's own device planes) to planar or semi-planar YCbCr in
 // caller-owned device memory (hm_device_planes, gfx950):
-//   k_planes_to_tensor  u8 / u16 samples -> u8 / u16 (sample << shift) / f16 / f32 (sample * scale[c] + bias[c] in two rounded steps, as
-//                       k_to_tensor), every plane its own pitch; HM_DEV_PLANES_SEMI interleaves Cb and Cr (Cb first) into one plane
+//   k_planes_to_tensor  u8 / u16 samples -> u8 / u16 (sample << shift) / f16 / f32 (sample * scale[c] + bias[c]): `moved` of out_elem.h
+//                       with the plane's shift; every plane its own pitch; HM_DEV_PLANES_SEMI interleaves Cb and Cr (Cb first) into one plane
 // A pure streaming kernel in the style of k_to_tensor (tensor.hip): no LDS, every sample read once and written once.  ONE launch
 // covers all planes of an image: the descriptors travel by value in the kernel arguments, and blockIdx.y - a range of 4-row
 // groups per plane - decides the plane, so the plane, its sample width and its instance are wave-uniform.  A wave takes 64
@@ -13,38 +13,11 @@
 // 16-byte aligned takes the element-wise path for that plane alone: the same span of a row per wave, lane l takes elements (pairs)
 // l, l + 64, ... of it, so every load and store instruction of the wave covers 64 consecutive elements.
 // Reads: exactly the `width` samples of every source row, never the row's pitch padding.  Writes: exactly the elements of the planes.
-#include <hip/hip_runtime.h>
-#include <hip/hip_fp16.h>
-#include <stdint.h>
-
-#include <type_traits>
-
 #include "hm_devdest.h"
+#include "out_elem.h"
+#include "out_launch.h"
 
 namespace {
-
-template <typename OutT> __device__ __forceinline__ OutT to_out(unsigned v, float sc, float bi, int shift);
-template <> __device__ __forceinline__ uint8_t to_out<uint8_t>(unsigned v, float, float, int) { return (uint8_t)v; }
-template <> __device__ __forceinline__ uint16_t to_out<uint16_t>(unsigned v, float, float, int shift) { return (uint16_t)(v << shift); }
-template <> __device__ __forceinline__ float to_out<float>(unsigned v, float sc, float bi, int) { return __fadd_rn(__fmul_rn((float)v, sc), bi); }
-template <> __device__ __forceinline__ __half to_out<__half>(unsigned v, float sc, float bi, int) { return __float2half_rn(__fadd_rn(__fmul_rn((float)v, sc), bi)); }
-
-template <int BYTES> struct LoadWord { typedef uint32_t type; };
-template <> struct LoadWord<16> { typedef uint4 type; };
-template <> struct LoadWord<8> { typedef uint2 type; };
-
-// N samples of SB bytes at `in` (aligned to their N * SB bytes) with one load
-template <int SB, int N> __device__ __forceinline__ void load_samples(const uint8_t* in, unsigned (&v)[N])
-{
-  typedef typename std::conditional<SB == 1, uint8_t, uint16_t>::type InT;
-  typedef typename LoadWord<N * SB>::type LW;
-  static_assert(N * SB == 4 || N * SB == 8 || N * SB == 16, "one load of 4, 8 or 16 bytes");
-  const LW lw = *reinterpret_cast<const LW*>(in);
-  InT smp[N];
-  __builtin_memcpy(smp, &lw, N * SB);
-#pragma unroll
-  for (int i = 0; i < N; i++) v[i] = smp[i];
-}
 
 // one plane, one component per element.  x-group gx of 64 groups, row y
 template <int SB, typename OutT, bool VEC>
@@ -61,7 +34,7 @@ __device__ __forceinline__ void plane_single(const hm_plane_desc& d, int gx, int
     for (int i = 0; i < P; i++) {
       const int x = (gx * P + i) * 64 + lane;
       if (x >= w) break;
-      orow[x] = to_out<OutT>(irow[x], sc, bi, d.shift);
+      orow[x] = moved<OutT>(irow[x], sc, bi, d.shift);
     }
     return;
   }
@@ -72,13 +45,11 @@ __device__ __forceinline__ void plane_single(const hm_plane_desc& d, int gx, int
     load_samples<SB, P>(reinterpret_cast<const uint8_t*>(irow + x0), v);
     OutT o[P];
 #pragma unroll
-    for (int i = 0; i < P; i++) o[i] = to_out<OutT>(v[i], sc, bi, d.shift);
-    uint4 q;
-    __builtin_memcpy(&q, o, 16);
-    *reinterpret_cast<uint4*>(orow + x0) = q;
+    for (int i = 0; i < P; i++) o[i] = moved<OutT>(v[i], sc, bi, d.shift);
+    store16(orow + x0, o);
     return;
   }
-  for (int x = x0; x < w; x++) orow[x] = to_out<OutT>(irow[x], sc, bi, d.shift);
+  for (int x = x0; x < w; x++) orow[x] = moved<OutT>(irow[x], sc, bi, d.shift);
 }
 
 // the interleaved chroma plane: element 2 x of a row is Cb[x], element 2 x + 1 is Cr[x]
@@ -96,8 +67,8 @@ __device__ __forceinline__ void plane_pair(const hm_plane_desc& d, int gx, int y
     for (int i = 0; i < N; i++) {
       const int x = (gx * N + i) * 64 + lane;
       if (x >= w) break;
-      orow[2 * (size_t)x] = to_out<OutT>(brow[x], d.scale0, d.bias0, d.shift);
-      orow[2 * (size_t)x + 1] = to_out<OutT>(rrow[x], d.scale1, d.bias1, d.shift);
+      orow[2 * (size_t)x] = moved<OutT>(brow[x], d.scale0, d.bias0, d.shift);
+      orow[2 * (size_t)x + 1] = moved<OutT>(rrow[x], d.scale1, d.bias1, d.shift);
     }
     return;
   }
@@ -121,20 +92,18 @@ __device__ __forceinline__ void plane_pair(const hm_plane_desc& d, int gx, int y
       OutT o[2 * N];
 #pragma unroll
       for (int i = 0; i < N; i++) {
-        o[2 * i] = to_out<OutT>(vb[i], d.scale0, d.bias0, d.shift);
-        o[2 * i + 1] = to_out<OutT>(vr[i], d.scale1, d.bias1, d.shift);
+        o[2 * i] = moved<OutT>(vb[i], d.scale0, d.bias0, d.shift);
+        o[2 * i + 1] = moved<OutT>(vr[i], d.scale1, d.bias1, d.shift);
       }
-      constexpr int STORES = 2 * N * (int)sizeof(OutT) / 16;
-      uint4 q[STORES];
-      __builtin_memcpy(q, o, sizeof(q));
+      constexpr int P = 16 / (int)sizeof(OutT); // elements of one store
 #pragma unroll
-      for (int k = 0; k < STORES; k++) op[k] = q[k];
+      for (int k = 0; k < 2 * N / P; k++) store16(op + k, o + k * P);
     }
     return;
   }
   for (int x = x0; x < w; x++) {
-    orow[2 * (size_t)x] = to_out<OutT>(brow[x], d.scale0, d.bias0, d.shift);
-    orow[2 * (size_t)x + 1] = to_out<OutT>(rrow[x], d.scale1, d.bias1, d.shift);
+    orow[2 * (size_t)x] = moved<OutT>(brow[x], d.scale0, d.bias0, d.shift);
+    orow[2 * (size_t)x + 1] = moved<OutT>(rrow[x], d.scale1, d.bias1, d.shift);
   }
 }
 
@@ -185,12 +154,10 @@ extern "C" int hm_launch_planes_to_tensor(const hm_planes_args* a, int dtype, hi
   const int gy = a->y_end[3];
   if (gx <= 0 || gy <= 0) return HM_OK;
   const dim3 grid((unsigned)gx, (unsigned)gy), block(256);
-  switch (dtype) {
-    case HM_DEV_U8: hipLaunchKernelGGL(k_planes_to_tensor<uint8_t>, grid, block, 0, s, *a); break;
-    case HM_DEV_U16: hipLaunchKernelGGL(k_planes_to_tensor<uint16_t>, grid, block, 0, s, *a); break;
-    case HM_DEV_F16: hipLaunchKernelGGL(k_planes_to_tensor<__half>, grid, block, 0, s, *a); break;
-    case HM_DEV_F32: hipLaunchKernelGGL(k_planes_to_tensor<float>, grid, block, 0, s, *a); break;
-    default: return hm_fail(HM_ERR_INTERNAL, "k_planes_to_tensor: no kernel for dtype %d", dtype);
-  }
+  const int found = with_dtype(dtype, [&](auto tag) -> int {
+    hipLaunchKernelGGL(k_planes_to_tensor<typename decltype(tag)::type>, grid, block, 0, s, *a);
+    return HM_OK;
+  });
+  if (found == NO_KERNEL_INSTANCE) return hm_fail(HM_ERR_INTERNAL, "k_planes_to_tensor: no kernel for dtype %d", dtype);
   return hm_check_hip(hipGetLastError(), "k_planes_to_tensor launch");
 }

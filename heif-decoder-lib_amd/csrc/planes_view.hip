@@ -17,17 +17,15 @@
 // decides the plane, so plane, sample width and path are wave-uniform; blockIdx.z is the frame of the chunk, whose pointers are
 // read once as scalar loads and typed as pointers to global memory (as k_resample_*_batch, resample.hip).  The sums run tap by tap
 // in float32 with separately rounded multiply and add (-ffp-contract=off, __fmul_rn / __fadd_rn), tap 0 first, horizontal pass
-// first: resample.hip's sums.  No LDS (the staged horizontal pass of resample.hip has no sibling here), no scratch.
+// first: resample.hip's sums.  A sum becomes an element by `finish` with the plane's own peak and msb_aligned shift, a sample that is
+// only moved by `moved` with that shift (out_elem.h).  No LDS (the staged horizontal pass of resample.hip has no sibling here), no scratch.
 // Reads: the samples of the crops.  Writes: exactly the elements of the planes.
-#include <hip/hip_runtime.h>
-#include <hip/hip_fp16.h>
-#include <stdint.h>
-
 #include <algorithm>
-#include <type_traits>
 
 #include "hm_devdest.h"
 #include "hm_planes_view.h"
+#include "out_elem.h"
+#include "out_launch.h"
 
 namespace {
 
@@ -41,20 +39,6 @@ __device__ __forceinline__ uint8_t* rec_dst(const void* recs, int frame, int pla
 {
   return (uint8_t*)(GlobalBytes*)static_cast<const hm_pv_rec*>(recs)[frame].dst[plane];
 }
-
-// the vertical sum r to an element of the destination: the plane's own peak, then the msb_aligned shift
-template <typename OutT> __device__ __forceinline__ OutT finish(float r, float sc, float bi, int peak, int shift);
-template <> __device__ __forceinline__ uint8_t finish<uint8_t>(float r, float, float, int peak, int) { const int v = (int)__fadd_rn(r, 0.5f); return (uint8_t)min(max(v, 0), peak); }
-template <> __device__ __forceinline__ uint16_t finish<uint16_t>(float r, float, float, int peak, int shift) { const int v = (int)__fadd_rn(r, 0.5f); return (uint16_t)(min(max(v, 0), peak) << shift); }
-template <> __device__ __forceinline__ float finish<float>(float r, float sc, float bi, int, int) { return __fadd_rn(__fmul_rn(r, sc), bi); }
-template <> __device__ __forceinline__ __half finish<__half>(float r, float sc, float bi, int, int) { return __float2half_rn(__fadd_rn(__fmul_rn(r, sc), bi)); }
-
-// a sample that is moved, not computed (k_planes_to_tensor's rule)
-template <typename OutT> __device__ __forceinline__ OutT moved(unsigned v, float sc, float bi, int shift);
-template <> __device__ __forceinline__ uint8_t moved<uint8_t>(unsigned v, float, float, int) { return (uint8_t)v; }
-template <> __device__ __forceinline__ uint16_t moved<uint16_t>(unsigned v, float, float, int shift) { return (uint16_t)(v << shift); }
-template <> __device__ __forceinline__ float moved<float>(unsigned v, float sc, float bi, int) { return __fadd_rn(__fmul_rn((float)v, sc), bi); }
-template <> __device__ __forceinline__ __half moved<__half>(unsigned v, float sc, float bi, int) { return __float2half_rn(__fadd_rn(__fmul_rn((float)v, sc), bi)); }
 
 // ---- horizontal ----
 template <int SB>
@@ -124,9 +108,7 @@ __device__ __forceinline__ void v_single(const hm_pv_dst_desc& d, const float* _
 #pragma unroll
     for (int q = 0; q < P; q++) o[q] = finish<OutT>(acc[q], d.scale0, d.bias0, d.peak, d.shift);
     if (cnt == P) {
-      uint4 pk;
-      __builtin_memcpy(&pk, o, 16);
-      *reinterpret_cast<uint4*>(orow + x0) = pk;
+      store16(orow + x0, o);
       return;
     }
 #pragma unroll
@@ -195,11 +177,9 @@ __device__ __forceinline__ void v_pair(const hm_pv_dst_desc& d, const float* __r
     }
     OutT* op = orow + 2 * (size_t)x0;
     if (cnt == N) {
-      constexpr int STORES = 2 * N * (int)sizeof(OutT) / 16;
-      uint4 pk[STORES];
-      __builtin_memcpy(pk, o, sizeof(pk));
+      constexpr int P = 16 / (int)sizeof(OutT); // elements of one store
 #pragma unroll
-      for (int q = 0; q < STORES; q++) reinterpret_cast<uint4*>(op)[q] = pk[q];
+      for (int q = 0; q < 2 * N / P; q++) store16(op + q * P, o + q * P);
       return;
     }
 #pragma unroll
@@ -329,13 +309,11 @@ extern "C" int hm_launch_planes_resample(const hm_pv_h_args* h, const hm_pv_v_ar
   else hipLaunchKernelGGL(k_planes_resample_h<2>, hgrid, block, 0, s, *h);
   const int rc = hm_check_hip(hipGetLastError(), "k_planes_resample_h launch");
   if (rc) return rc;
-  switch (dtype) {
-    case HM_DEV_U8: hipLaunchKernelGGL(k_planes_resample_v<uint8_t>, vgrid, block, 0, s, *v); break;
-    case HM_DEV_U16: hipLaunchKernelGGL(k_planes_resample_v<uint16_t>, vgrid, block, 0, s, *v); break;
-    case HM_DEV_F16: hipLaunchKernelGGL(k_planes_resample_v<__half>, vgrid, block, 0, s, *v); break;
-    case HM_DEV_F32: hipLaunchKernelGGL(k_planes_resample_v<float>, vgrid, block, 0, s, *v); break;
-    default: return hm_fail(HM_ERR_INTERNAL, "k_planes_resample_v: no kernel for dtype %d", dtype);
-  }
+  const int found = with_dtype(dtype, [&](auto tag) -> int {
+    hipLaunchKernelGGL(k_planes_resample_v<typename decltype(tag)::type>, vgrid, block, 0, s, *v);
+    return HM_OK;
+  });
+  if (found == NO_KERNEL_INSTANCE) return hm_fail(HM_ERR_INTERNAL, "k_planes_resample_v: no kernel for dtype %d", dtype);
   return hm_check_hip(hipGetLastError(), "k_planes_resample_v launch");
 }
 
@@ -349,12 +327,10 @@ extern "C" int hm_launch_planes_view_nearest(const hm_pv_v_args* v, int dtype, i
   const int gy = v->y_end[3];
   if (gx <= 0 || gy <= 0) return HM_OK;
   const dim3 block(256), grid((unsigned)gx, (unsigned)gy, (unsigned)frames);
-  switch (dtype) {
-    case HM_DEV_U8: hipLaunchKernelGGL(k_planes_view_nearest<uint8_t>, grid, block, 0, s, *v); break;
-    case HM_DEV_U16: hipLaunchKernelGGL(k_planes_view_nearest<uint16_t>, grid, block, 0, s, *v); break;
-    case HM_DEV_F16: hipLaunchKernelGGL(k_planes_view_nearest<__half>, grid, block, 0, s, *v); break;
-    case HM_DEV_F32: hipLaunchKernelGGL(k_planes_view_nearest<float>, grid, block, 0, s, *v); break;
-    default: return hm_fail(HM_ERR_INTERNAL, "k_planes_view_nearest: no kernel for dtype %d", dtype);
-  }
+  const int found = with_dtype(dtype, [&](auto tag) -> int {
+    hipLaunchKernelGGL(k_planes_view_nearest<typename decltype(tag)::type>, grid, block, 0, s, *v);
+    return HM_OK;
+  });
+  if (found == NO_KERNEL_INSTANCE) return hm_fail(HM_ERR_INTERNAL, "k_planes_view_nearest: no kernel for dtype %d", dtype);
   return hm_check_hip(hipGetLastError(), "k_planes_view_nearest launch");
 }

@@ -1,9 +1,7 @@
 // resample.hip — a view (hm_device_view) of the colour stage's interleaved pixels into a tensor in caller-owned device memory (gfx950):
 // a rectangle of the image, resampled to the size the caller asks for, as u8 / u16 / f16 / f32 in CHW or HWC.
-//   k_resample_h     the horizontal pass: rows of the crop -> float32 rows of out_w.  A lane sits on one (output column, source row)
-//                    pair and walks its taps over contiguous source bytes; a wave is 64 consecutive columns of ONE row, and the tap
-//                    table is tap-major (weights[tap][column]), so the wave's weight reads and its stores are contiguous.  The
-//                    intermediate is laid out like the destination: one plane per channel for CHW, interleaved for HWC.
+//   k_resample_h     the horizontal pass: rows of the crop -> float32 rows of out_w, a lane per (output column, source row) pair.  The
+//                    body is resample_h_body (out_rows.h, where the mapping is described), here with the plain conversion of a sample.
 //   k_resample_h_staged  the same sums in the same order for HM_VIEW_CUBIC / HM_VIEW_LANCZOS3 (2 and 3 times the taps): the contiguous run of
 //                    source bytes a wave's 64 columns read goes to LDS once, in 16-byte loads, and the lanes take their taps from there.
 //   k_resample_v     the vertical pass, fused with dtype, layout, scale and bias: a wave is 64 consecutive element groups of ONE output
@@ -13,73 +11,27 @@
 //                    each (grid z): the per-frame pointers come from arrays, everything else is shared.  Same sums, same order, same bytes.
 //   k_view_nearest   HM_VIEW_NEAREST: the sample at j * n / m is moved (through scale and bias for float destinations), no intermediate.
 // The sums run tap by tap in float32 with separately rounded multiply and add (-ffp-contract=off, __fmul_rn / __fadd_rn): a float32
-// restatement on the host is exact.  Nothing but the out_w x out_h x C elements of the view is ever stored.
-#include <hip/hip_runtime.h>
-#include <hip/hip_fp16.h>
-#include <stdint.h>
-
-#include <type_traits>
-
+// restatement on the host is exact.  A sum becomes an element by `finish`, a sample that is only moved by `moved` (out_elem.h).
+// Nothing but the out_w x out_h x C elements of the view is ever stored.
 #include "hm_devdest.h"
 #include "hm_view_batch.h"
+#include "out_launch.h"
+#include "out_rows.h"
 
 namespace {
-
-struct Affine { float scale[4], bias[4]; };
 
 // A pointer a kernel loads from memory is a generic one to the compiler (a kernel argument is known to point to global memory):
 // the batched kernels read their per-frame pointers as pointers to global memory, so that the loads and stores through them are
 // the global ones of the unbatched kernels, not flat ones that might alias LDS.
 typedef __attribute__((address_space(1))) uint8_t GlobalBytes;
 
-// the vertical sum r to an element of the destination
-template <typename OutT> __device__ __forceinline__ OutT finish(float r, float sc, float bi);
-template <> __device__ __forceinline__ uint8_t finish<uint8_t>(float r, float, float) { const int v = (int)__fadd_rn(r, 0.5f); return (uint8_t)min(max(v, 0), 255); }
-template <> __device__ __forceinline__ uint16_t finish<uint16_t>(float r, float, float) { const int v = (int)__fadd_rn(r, 0.5f); return (uint16_t)min(max(v, 0), 65535); }
-template <> __device__ __forceinline__ float finish<float>(float r, float sc, float bi) { return __fadd_rn(__fmul_rn(r, sc), bi); }
-template <> __device__ __forceinline__ __half finish<__half>(float r, float sc, float bi) { return __float2half_rn(__fadd_rn(__fmul_rn(r, sc), bi)); }
-
-// a sample that is moved, not computed (k_to_tensor's rule)
-template <typename OutT> __device__ __forceinline__ OutT moved(unsigned v, float sc, float bi);
-template <> __device__ __forceinline__ uint8_t moved<uint8_t>(unsigned v, float, float) { return (uint8_t)v; }
-template <> __device__ __forceinline__ uint16_t moved<uint16_t>(unsigned v, float, float) { return (uint16_t)v; }
-template <> __device__ __forceinline__ float moved<float>(unsigned v, float sc, float bi) { return __fadd_rn(__fmul_rn((float)v, sc), bi); }
-template <> __device__ __forceinline__ __half moved<__half>(unsigned v, float sc, float bi) { return __float2half_rn(__fadd_rn(__fmul_rn((float)v, sc), bi)); }
-
-// SB: bytes per source sample (little-endian), C: channels, CHW: the intermediate has one plane per channel.
-// grid: x = groups of 64 output columns, y = groups of 4 source rows.  src points at the crop's origin.
-template <int SB, int C, bool CHW>
-__device__ __forceinline__ void resample_h_body(const uint8_t* __restrict__ src, int src_stride, int n_h, int ow, const int32_t* __restrict__ first,
-                                                const int32_t* __restrict__ count, const float* __restrict__ wts, float* __restrict__ tmp,
-                                                long long pitch, long long plane)
-{
-  typedef typename std::conditional<SB == 1, uint8_t, uint16_t>::type InT;
-  const int j = blockIdx.x * 64 + (threadIdx.x & 63), y = blockIdx.y * 4 + (threadIdx.x >> 6);
-  if (j >= ow || y >= n_h) return;
-  const InT* in = reinterpret_cast<const InT*>(src + (size_t)y * src_stride) + (size_t)first[j] * C;
-  const int n = count[j];
-  float t[C];
-#pragma unroll
-  for (int c = 0; c < C; c++) t[c] = 0.0f;
-  for (int i = 0; i < n; i++) {
-    const float w = wts[(size_t)i * ow + j];
-#pragma unroll
-    for (int c = 0; c < C; c++) t[c] = __fadd_rn(t[c], __fmul_rn(w, (float)in[i * C + c]));
-  }
-  float* o = tmp + (long long)y * pitch;
-#pragma unroll
-  for (int c = 0; c < C; c++) {
-    if (CHW) o[(long long)c * plane + j] = t[c];
-    else o[(size_t)j * C + c] = t[c];
-  }
-}
-
+// resample_h_body (out_rows.h) with the plain conversion of a sample
 template <int SB, int C, bool CHW>
 __global__ __launch_bounds__(256) void k_resample_h(const uint8_t* __restrict__ src, int src_stride, int n_h, int ow, const int32_t* __restrict__ first,
                                                     const int32_t* __restrict__ count, const float* __restrict__ wts, float* __restrict__ tmp,
                                                     long long pitch, long long plane)
 {
-  resample_h_body<SB, C, CHW>(src, src_stride, n_h, ow, first, count, wts, tmp, pitch, plane);
+  resample_h_body<SB, C, CHW>(src, src_stride, n_h, ow, first, count, wts, tmp, pitch, plane, SampleToFloat());
 }
 
 // The batched form (hm_view_write_batch: the frames of a sequence under one view): blockIdx.z is the frame within the chunk.  Its
@@ -93,7 +45,7 @@ __global__ __launch_bounds__(256) void k_resample_h_batch(const uint8_t* const* 
                                                           long long frame_stride)
 {
   const uint8_t* src = (const uint8_t*)(const GlobalBytes*)reinterpret_cast<const uintptr_t*>(srcs)[blockIdx.z];
-  resample_h_body<SB, C, CHW>(src, src_stride, n_h, ow, first, count, wts, tmp + (long long)blockIdx.z * frame_stride, pitch, plane);
+  resample_h_body<SB, C, CHW>(src, src_stride, n_h, ow, first, count, wts, tmp + (long long)blockIdx.z * frame_stride, pitch, plane, SampleToFloat());
 }
 
 // k_resample_h with the source run staged in LDS.  The 64 columns of a wave read the pixels first[c0] .. first[c63] + count[c63] of
@@ -261,15 +213,14 @@ __device__ __forceinline__ void resample_v_body(int pl, const float* __restrict_
 #pragma unroll
   for (int q = 0; q < P; q++) {
     const int c = C == 0 ? pl : (e0 + q) % (C == 0 ? 1 : C);
-    o[q] = finish<OutT>(acc[q], a.scale[c], a.bias[c]);
+    o[q] = finish<OutT>(acc[q], a.scale[c], a.bias[c], full_peak<OutT>());
   }
   OutT* op = reinterpret_cast<OutT*>(dst + (long long)pl * plane_pitch + (long long)k * row_pitch) + e0;
-  if (P > 1 && e0 + P <= E) {
-    uint4 pk;
-    __builtin_memcpy(&pk, o, 16);
-    *reinterpret_cast<uint4*>(op) = pk;
-    return;
-  }
+  if constexpr (P > 1)
+    if (e0 + P <= E) {
+      store16(op, o);
+      return;
+    }
   const int left = E - e0 < P ? E - e0 : P;
   for (int q = 0; q < left; q++) op[q] = o[q];
 }
@@ -310,8 +261,7 @@ __global__ __launch_bounds__(256) void k_view_nearest(const uint8_t* __restrict_
   uint8_t* orow = dst + (long long)k * row_pitch;
   for (int c = 0; c < C; c++) {
     const OutT o = moved<OutT>(in[c], a.scale[c], a.bias[c]);
-    OutT* op = chw ? reinterpret_cast<OutT*>(orow + (long long)c * plane_pitch) + j : reinterpret_cast<OutT*>(orow) + (size_t)j * C + c;
-    *op = o;
+    *elem_at<OutT>(orow, chw, plane_pitch, j, c, C) = o;
   }
 }
 
@@ -395,11 +345,12 @@ void launch_v(const hm_dest_plan* p, const hm_resample_args* r, uint8_t* dst, co
 }
 
 template <typename InT, typename OutT>
-void launch_nearest(const hm_dest_plan* p, const uint8_t* src, int src_stride, int n_w, int n_h, int ow, int oh, uint8_t* dst, const Affine& a, hipStream_t s)
+int launch_nearest(const hm_dest_plan* p, const uint8_t* src, int src_stride, int n_w, int n_h, int ow, int oh, uint8_t* dst, const Affine& a, hipStream_t s)
 {
   const dim3 grid((unsigned)((ow + 63) / 64), (unsigned)((oh + 3) / 4)), block(256);
   hipLaunchKernelGGL((k_view_nearest<InT, OutT>), grid, block, 0, s, src, src_stride, n_w, n_h, ow, oh, p->channels, p->layout == HM_DEV_LAYOUT_CHW ? 1 : 0, dst,
                      (long long)p->row_pitch, (long long)p->plane_pitch, a);
+  return HM_OK;
 }
 
 // the batched launches: grid z = the frames of the chunk (horizontal), frames x planes (vertical)
@@ -445,13 +396,6 @@ void launch_v_batch(const hm_dest_plan* p, const hm_resample_args* r, const hm_r
   else { if (vec) launch_v_batch_inst<OutT, P, 4>(p, r, b, a, s); else launch_v_batch_inst<OutT, 1, 4>(p, r, b, a, s); }
 }
 
-Affine affine_of(const float scale[4], const float bias[4])
-{
-  Affine a;
-  for (int c = 0; c < 4; c++) { a.scale[c] = scale[c]; a.bias[c] = bias[c]; }
-  return a;
-}
-
 } // namespace
 
 extern "C" const void* hm_resample_kernel_of(int index) // (test_hooks.cpp: hm_debug_kernel_regs)
@@ -486,13 +430,8 @@ extern "C" int hm_launch_resample(const hm_dest_plan* p, const hm_resample_args*
   if (rc) return rc;
   const Affine a = affine_of(scale, bias);
   uint8_t* out = (uint8_t*)dst;
-  switch (p->dtype) {
-    case HM_DEV_U8: launch_v<uint8_t>(p, r, out, a, s); break;
-    case HM_DEV_U16: launch_v<uint16_t>(p, r, out, a, s); break;
-    case HM_DEV_F16: launch_v<__half>(p, r, out, a, s); break;
-    case HM_DEV_F32: launch_v<float>(p, r, out, a, s); break;
-    default: return hm_fail(HM_ERR_INTERNAL, "k_resample_v: no kernel for dtype %d", p->dtype);
-  }
+  const int found = with_dtype(p->dtype, [&](auto tag) -> int { launch_v<typename decltype(tag)::type>(p, r, out, a, s); return HM_OK; });
+  if (found == NO_KERNEL_INSTANCE) return hm_fail(HM_ERR_INTERNAL, "k_resample_v: no kernel for dtype %d", p->dtype);
   return hm_check_hip(hipGetLastError(), "k_resample_v launch");
 }
 
@@ -510,13 +449,8 @@ extern "C" int hm_launch_resample_batch(const hm_dest_plan* p, const hm_resample
   int rc = hm_check_hip(hipGetLastError(), "k_resample_h_batch launch");
   if (rc) return rc;
   const Affine a = affine_of(scale, bias);
-  switch (p->dtype) {
-    case HM_DEV_U8: launch_v_batch<uint8_t>(p, r, b, a, s); break;
-    case HM_DEV_U16: launch_v_batch<uint16_t>(p, r, b, a, s); break;
-    case HM_DEV_F16: launch_v_batch<__half>(p, r, b, a, s); break;
-    case HM_DEV_F32: launch_v_batch<float>(p, r, b, a, s); break;
-    default: return hm_fail(HM_ERR_INTERNAL, "k_resample_v: no kernel for dtype %d", p->dtype);
-  }
+  const int found = with_dtype(p->dtype, [&](auto tag) -> int { launch_v_batch<typename decltype(tag)::type>(p, r, b, a, s); return HM_OK; });
+  if (found == NO_KERNEL_INSTANCE) return hm_fail(HM_ERR_INTERNAL, "k_resample_v: no kernel for dtype %d", p->dtype);
   return hm_check_hip(hipGetLastError(), "k_resample_v_batch launch");
 }
 
@@ -528,10 +462,15 @@ extern "C" int hm_launch_view_nearest(const hm_dest_plan* p, const void* src, in
   const uint8_t* in = (const uint8_t*)src;
   uint8_t* out = (uint8_t*)dst;
   const bool wide = p->sample_bytes == 2;
-  if (p->dtype == HM_DEV_U8 && !wide) launch_nearest<uint8_t, uint8_t>(p, in, src_stride, n_w, n_h, ow, oh, out, a, s);
-  else if (p->dtype == HM_DEV_U16 && wide) launch_nearest<uint16_t, uint16_t>(p, in, src_stride, n_w, n_h, ow, oh, out, a, s);
-  else if (p->dtype == HM_DEV_F16) { if (wide) launch_nearest<uint16_t, __half>(p, in, src_stride, n_w, n_h, ow, oh, out, a, s); else launch_nearest<uint8_t, __half>(p, in, src_stride, n_w, n_h, ow, oh, out, a, s); }
-  else if (p->dtype == HM_DEV_F32) { if (wide) launch_nearest<uint16_t, float>(p, in, src_stride, n_w, n_h, ow, oh, out, a, s); else launch_nearest<uint8_t, float>(p, in, src_stride, n_w, n_h, ow, oh, out, a, s); }
-  else return hm_fail(HM_ERR_INTERNAL, "k_view_nearest: no kernel for dtype %d on %d-byte samples", p->dtype, p->sample_bytes);
+  // an integer element from samples of its own width only; floats from either
+  const int found = with_dtype(p->dtype, [&](auto tag) -> int {
+    typedef typename decltype(tag)::type OutT;
+    if constexpr (!std::is_same<OutT, uint8_t>::value)
+      if (wide) return launch_nearest<uint16_t, OutT>(p, in, src_stride, n_w, n_h, ow, oh, out, a, s);
+    if constexpr (!std::is_same<OutT, uint16_t>::value)
+      if (!wide) return launch_nearest<uint8_t, OutT>(p, in, src_stride, n_w, n_h, ow, oh, out, a, s);
+    return NO_KERNEL_INSTANCE;
+  });
+  if (found == NO_KERNEL_INSTANCE) return hm_fail(HM_ERR_INTERNAL, "k_view_nearest: no kernel for dtype %d on %d-byte samples", p->dtype, p->sample_bytes);
   return hm_check_hip(hipGetLastError(), "k_view_nearest launch");
 }

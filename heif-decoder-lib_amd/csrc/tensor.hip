@@ -8,28 +8,13 @@
 // CHW float32 tensor of a width that is no multiple of 4, say) the whole image takes the scalar instance: the same span of a row
 // per wave, but lane l takes pixels l, l + 64, l + 128 ... of it, so every load and store instruction of the wave still covers 64
 // consecutive pixels.  Nothing but the w x h x C elements of the image is ever stored.  HWC with the target's own integer type
-// is a 2-D device copy and never comes here.
-#include <hip/hip_runtime.h>
-#include <hip/hip_fp16.h>
-#include <stdint.h>
-
-#include <type_traits>
-
+// is a 2-D device copy and never comes here.  The rule for a moved sample, the address of an element and the 16-byte store are
+// out_elem.h's.
 #include "hm_devdest.h"
+#include "out_elem.h"
+#include "out_launch.h"
 
 namespace {
-
-struct Affine { float scale[4], bias[4]; };
-
-template <typename OutT> __device__ __forceinline__ OutT to_out(unsigned v, float sc, float bi);
-template <> __device__ __forceinline__ uint8_t to_out<uint8_t>(unsigned v, float, float) { return (uint8_t)v; }
-template <> __device__ __forceinline__ uint16_t to_out<uint16_t>(unsigned v, float, float) { return (uint16_t)v; }
-template <> __device__ __forceinline__ float to_out<float>(unsigned v, float sc, float bi) { return __fadd_rn(__fmul_rn((float)v, sc), bi); }
-template <> __device__ __forceinline__ __half to_out<__half>(unsigned v, float sc, float bi) { return __float2half_rn(__fadd_rn(__fmul_rn((float)v, sc), bi)); }
-
-template <int BYTES> struct LoadWord { typedef uint32_t type; };
-template <> struct LoadWord<16> { typedef uint4 type; };
-template <> struct LoadWord<8> { typedef uint2 type; };
 
 // SB: bytes per input sample (1 / 2, little-endian), C: channels, CHW: one plane per channel, VEC: 16-byte accesses allowed
 // (the launcher has checked the alignment of both sides), else the scalar instance.  grid: x = groups of 64 pixel groups, y = groups of 4 rows.
@@ -51,9 +36,8 @@ __global__ __launch_bounds__(256) void k_to_tensor(const uint8_t* __restrict__ s
       if (x >= w) break;
 #pragma unroll
       for (int c = 0; c < C; c++) {
-        const OutT o = to_out<OutT>(irow[(size_t)x * C + c], a.scale[c], a.bias[c]);
-        OutT* op = CHW ? reinterpret_cast<OutT*>(orow + (long long)c * plane_pitch) + x : reinterpret_cast<OutT*>(orow) + (size_t)x * C + c;
-        *op = o;
+        const OutT o = moved<OutT>(irow[(size_t)x * C + c], a.scale[c], a.bias[c]);
+        *elem_at<OutT>(orow, CHW, plane_pitch, x, c, C) = o;
       }
     }
     return;
@@ -74,10 +58,8 @@ __global__ __launch_bounds__(256) void k_to_tensor(const uint8_t* __restrict__ s
       for (int c = 0; c < C; c++) {
         OutT o[P];
 #pragma unroll
-        for (int i = 0; i < P; i++) o[i] = to_out<OutT>(smp[i * C + c], a.scale[c], a.bias[c]);
-        uint4 v;
-        __builtin_memcpy(&v, o, 16);
-        *reinterpret_cast<uint4*>(orow + (long long)c * plane_pitch + (size_t)x0 * sizeof(OutT)) = v;
+        for (int i = 0; i < P; i++) o[i] = moved<OutT>(smp[i * C + c], a.scale[c], a.bias[c]);
+        store16(elem_at<OutT>(orow, true, plane_pitch, x0, c, C), o);
       }
     }
     else {
@@ -85,10 +67,8 @@ __global__ __launch_bounds__(256) void k_to_tensor(const uint8_t* __restrict__ s
       for (int k = 0; k < C; k++) { // P * C elements in a row: C stores of P elements
         OutT o[P];
 #pragma unroll
-        for (int i = 0; i < P; i++) o[i] = to_out<OutT>(smp[k * P + i], a.scale[(k * P + i) % C], a.bias[(k * P + i) % C]);
-        uint4 v;
-        __builtin_memcpy(&v, o, 16);
-        reinterpret_cast<uint4*>(orow + (size_t)x0 * (C * sizeof(OutT)))[k] = v;
+        for (int i = 0; i < P; i++) o[i] = moved<OutT>(smp[k * P + i], a.scale[(k * P + i) % C], a.bias[(k * P + i) % C]);
+        store16(elem_at<OutT>(orow, false, 0, x0, 0, C) + k * P, o);
       }
     }
     return;
@@ -98,10 +78,8 @@ __global__ __launch_bounds__(256) void k_to_tensor(const uint8_t* __restrict__ s
   for (int i = 0; i < n; i++) {
 #pragma unroll
     for (int c = 0; c < C; c++) {
-      const OutT o = to_out<OutT>(ip[i * C + c], a.scale[c], a.bias[c]);
-      OutT* op = CHW ? reinterpret_cast<OutT*>(orow + (long long)c * plane_pitch) + (x0 + i)
-                     : reinterpret_cast<OutT*>(orow) + (size_t)(x0 + i) * C + c;
-      *op = o;
+      const OutT o = moved<OutT>(ip[i * C + c], a.scale[c], a.bias[c]);
+      *elem_at<OutT>(orow, CHW, plane_pitch, x0 + i, c, C) = o;
     }
   }
 }
@@ -121,20 +99,20 @@ int launch(const hm_dest_plan* p, const uint8_t* src, int src_stride, int w, int
   return hm_check_hip(hipGetLastError(), "k_to_tensor launch");
 }
 
+// float dtypes in both layouts; the integer type of the samples' own width as CHW only (HWC is the 2-D copy); nothing else
 template <int SB, int C>
 int launch_dtype(const hm_dest_plan* p, const uint8_t* src, int src_stride, int w, int rows, uint8_t* dst, const Affine& a, hipStream_t s)
 {
   const bool chw = p->layout == HM_DEV_LAYOUT_CHW;
-  switch (p->dtype) {
-    case HM_DEV_F32: return chw ? launch<SB, C, float, true>(p, src, src_stride, w, rows, dst, a, s) : launch<SB, C, float, false>(p, src, src_stride, w, rows, dst, a, s);
-    case HM_DEV_F16: return chw ? launch<SB, C, __half, true>(p, src, src_stride, w, rows, dst, a, s) : launch<SB, C, __half, false>(p, src, src_stride, w, rows, dst, a, s);
-    case HM_DEV_U8:
-      if constexpr (SB == 1) if (chw) return launch<SB, C, uint8_t, true>(p, src, src_stride, w, rows, dst, a, s);
-      break;
-    case HM_DEV_U16:
-      if constexpr (SB == 2) if (chw) return launch<SB, C, uint16_t, true>(p, src, src_stride, w, rows, dst, a, s);
-      break;
-  }
+  const int rc = with_dtype(p->dtype, [&](auto tag) -> int {
+    typedef typename decltype(tag)::type OutT;
+    if constexpr (!std::is_integral<OutT>::value)
+      return chw ? launch<SB, C, OutT, true>(p, src, src_stride, w, rows, dst, a, s) : launch<SB, C, OutT, false>(p, src, src_stride, w, rows, dst, a, s);
+    else if constexpr (sizeof(OutT) == SB)
+      if (chw) return launch<SB, C, OutT, true>(p, src, src_stride, w, rows, dst, a, s);
+    return NO_KERNEL_INSTANCE;
+  });
+  if (rc != NO_KERNEL_INSTANCE) return rc;
   return hm_fail(HM_ERR_INTERNAL, "k_to_tensor: no kernel for dtype %d, layout %d on %d-byte samples", p->dtype, p->layout, SB);
 }
 
@@ -146,8 +124,7 @@ extern "C" int hm_launch_to_tensor(const hm_dest_plan* p, const void* src, int s
                                    hipStream_t s)
 {
   if (w <= 0 || rows <= 0) return HM_OK;
-  Affine a;
-  for (int c = 0; c < 4; c++) { a.scale[c] = scale[c]; a.bias[c] = bias[c]; }
+  const Affine a = affine_of(scale, bias);
   const uint8_t* in = (const uint8_t*)src;
   uint8_t* out = (uint8_t*)dst;
   if (p->sample_bytes == 1) return p->channels == 3 ? launch_dtype<1, 3>(p, in, src_stride, w, rows, out, a, s) : launch_dtype<1, 4>(p, in, src_stride, w, rows, out, a, s);
