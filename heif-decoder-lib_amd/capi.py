@@ -183,6 +183,14 @@ HM_TONE_BT2390 = 1
 HM_TONE_STEPS = 2048
 
 
+class DeviceAlpha(C.Structure):
+    """hm_device_alpha: the mode, and for HM_ALPHA_MATTE the background's R, G, B code values at the target's sample depth"""
+    _fields_ = [("mode", C.c_int32), ("background", C.c_uint16 * 4), ("reserved", C.c_int32 * 3)]
+
+
+HM_ALPHA_STRAIGHT, HM_ALPHA_PREMULTIPLIED, HM_ALPHA_MATTE = 1, 2, 3
+
+
 class LightLevels(C.Structure):
     """hm_light_levels: the raw fields of an item's clli and mdcv properties"""
     _fields_ = [("has_clli", C.c_int32), ("has_mdcv", C.c_int32), ("max_content_light_level", C.c_uint16), ("max_pic_average_light_level", C.c_uint16),
@@ -293,6 +301,13 @@ def bind_image(L):
                                     C.POINTER(DeviceDest), C.c_void_p]
     L.hm_tone_table.argtypes = [C.POINTER(DeviceTone), C.c_float, C.c_int, C.POINTER(C.c_float)]
     L.hm_file_item_light_levels.argtypes = [C.c_void_p, C.c_uint32, C.POINTER(LightLevels)]
+    L.hm_alpha_dest_format.argtypes = [C.c_int, C.POINTER(DeviceAlpha), C.POINTER(DeviceTone)]
+    L.hm_decode_item_to_device_alpha.argtypes = [C.c_void_p, C.c_uint32, C.POINTER(DecodeParams), C.POINTER(DeviceView), C.POINTER(DeviceLight), C.POINTER(DeviceTone),
+                                                 C.POINTER(DeviceAlpha), C.POINTER(DeviceDest), C.POINTER(Decoded)]
+    L.hm_pipeline_submit_to_device_alpha.argtypes = [C.c_void_p, C.c_char_p, C.c_size_t, C.c_uint32, C.c_uint64, C.POINTER(DeviceView), C.POINTER(DeviceLight),
+                                                     C.POINTER(DeviceTone), C.POINTER(DeviceAlpha), C.POINTER(DeviceDest)]
+    L.hm_alpha_to_tensor.argtypes = [C.c_int, C.c_int, C.c_int, C.c_int, C.c_void_p, C.c_int, C.POINTER(DeviceView), C.POINTER(DeviceLight), C.POINTER(DeviceTone),
+                                     C.POINTER(DeviceAlpha), C.POINTER(DeviceDest), C.c_void_p]
     L.hm_device_planes_bytes.argtypes = [C.c_int, C.c_int, C.c_int, C.c_int, C.POINTER(DevicePlanes), C.POINTER(C.c_int64 * 4)]
     L.hm_device_planes_bytes.restype = C.c_int64
     L.hm_planes_to_tensor.argtypes = [C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, C.POINTER(C.c_void_p * 4), C.POINTER(C.c_int32 * 4), C.POINTER(DevicePlanes),

@@ -879,13 +879,23 @@ int hm_tone_check_static(int out_format, const hm_device_dest* d, const hm_devic
   return light_check(out_format, hm_tone_dest_format(out_format, tone), d, l, explicit_from);
 }
 
+static int tone_plan_of(int out_format, int dest_format, int bits, int img_transfer, int img_primaries, const hm_device_light* l, const hm_device_tone* tone,
+                        hm_light_plan* lp);
+
 int hm_tone_resolve(int out_format, int bits, int img_transfer, int img_primaries, const hm_device_dest* d, const hm_device_light* l, const hm_device_tone* tone,
                     hm_light_plan* lp)
 {
   if (!tone) return hm_light_resolve(out_format, bits, img_transfer, img_primaries, d, l, lp);
-  int rc = hm_tone_check_static(out_format, d, l, tone, 0);
+  const int rc = hm_tone_check_static(out_format, d, l, tone, 0);
+  return rc ? rc : tone_plan_of(out_format, hm_tone_dest_format(out_format, tone), bits, img_transfer, img_primaries, l, tone, lp);
+}
+
+// the plan of a light step with a tone step whose static checks have passed
+static int tone_plan_of(int out_format, int dest_format, int bits, int img_transfer, int img_primaries, const hm_device_light* l, const hm_device_tone* tone,
+                        hm_light_plan* lp)
+{
+  const int rc = light_plan_of(out_format, dest_format, bits, img_transfer, img_primaries, l, lp);
   if (rc) return rc;
-  if ((rc = light_plan_of(out_format, hm_tone_dest_format(out_format, tone), bits, img_transfer, img_primaries, l, lp))) return rc;
   if (tone->unit_nits == 0.0f && lp->from_transfer != 16)
     return hm_fail(HM_ERR_INVALID_ARG, "tone: unit_nits must be given for transfer characteristics %d (only PQ says what 1.0 stands for)", lp->from_transfer);
   if (tone->src_peak == 0.0f) return hm_fail(HM_ERR_INVALID_ARG, "tone: src_peak must be given: the pixels carry no light levels"); // (else the knee has been judged)
@@ -909,6 +919,40 @@ int hm_tone_table(const hm_device_tone* tone, float gain, int which, float* out)
   return HM_TONE_STEPS;
 }
 
+namespace {
+
+// the tables a light plan's kernels read, one behind the other: lin, then enc, then thr and sg (hm_light_write, hm_alpha_write: there
+// the plan may be NULL - no light step, no tables)
+struct LightTables {
+  const hm_light_plan* lp;
+  size_t n, ne, nt;
+  explicit LightTables(const hm_light_plan* plan)
+    : lp(plan), n(plan ? (size_t)1 << plan->bits : 0), ne(plan && plan->encode ? (size_t)1 << plan->enc_bits : 0), nt(plan && plan->tone ? 2 * (size_t)HM_TONE_STEPS : 0) {}
+  size_t bytes() const { return (n + ne + nt) * sizeof(float); }
+  void fill(float* host) const
+  {
+    if (!lp) return;
+    fill_light_table(lp->from_transfer, lp->bits, (double)lp->gain, false, host);
+    if (lp->encode) fill_light_table(lp->to_transfer, lp->enc_bits, (double)lp->gain, true, host + n);
+    if (lp->tone) fill_tone_tables((double)lp->gain, lp->src_peak, lp->dst_peak, lp->unit_nits, lp->out_unit_nits, host + n + ne, host + n + ne + HM_TONE_STEPS);
+  }
+  // the kernels' arguments, the table pointers still NULL ...
+  hm_light_args args(int src_bytes) const
+  {
+    hm_light_args la;
+    std::memset(&la, 0, sizeof(la));
+    la.src_bytes = src_bytes;
+    if (!lp) return la;
+    la.bits = lp->bits; la.enc_bits = lp->enc_bits; la.src_bytes = src_bytes; la.encode = lp->encode; la.matrix = lp->matrix;
+    std::memcpy(la.m, lp->m, sizeof(la.m));
+    return la;
+  }
+  // ... and pointed at the device copy of what fill wrote
+  void point(hm_light_args* la, const float* dev) const { if (!lp) return; la->lin = dev; la->enc = lp->encode ? dev + n : nullptr; la->tone = lp->tone ? dev + n + ne : nullptr; }
+};
+
+} // namespace
+
 int hm_light_write(const hm_device_dest* d, int out_format, int w, int h, const hm_view_plan* vp, const hm_light_plan* lp, const void* src, int src_stride,
                    hipStream_t s, hm_view_scratch* sc)
 {
@@ -921,19 +965,12 @@ int hm_light_write(const hm_device_dest* d, int out_format, int w, int h, const 
   const int obpp = hm_out_bytes_per_pixel(out_format), src_bytes = obpp >= 6 ? 2 : 1;
   const int cx = vp ? vp->x : 0, cy = vp ? vp->y : 0, cw = vp ? vp->w : w, ch = vp ? vp->h : h;
   const uint8_t* origin = (const uint8_t*)src + (size_t)cy * src_stride + (size_t)cx * obpp;
-  const size_t n = (size_t)1 << lp->bits, ne = lp->encode ? (size_t)1 << lp->enc_bits : 0, nt = lp->tone ? 2 * (size_t)HM_TONE_STEPS : 0;
-  const size_t table_bytes = (n + ne + nt) * sizeof(float);
+  const LightTables T(lp);
+  const size_t table_bytes = T.bytes();
   const bool resampled = vp && !vp->crop_only && vp->filter != HM_VIEW_NEAREST;
-  hm_light_args la;
-  std::memset(&la, 0, sizeof(la));
-  la.bits = lp->bits; la.enc_bits = lp->enc_bits; la.src_bytes = src_bytes; la.encode = lp->encode; la.matrix = lp->matrix;
-  std::memcpy(la.m, lp->m, sizeof(la.m));
-  auto fill = [&](float* host) { // lin, then enc, then thr and sg
-    fill_light_table(lp->from_transfer, lp->bits, (double)lp->gain, false, host);
-    if (lp->encode) fill_light_table(lp->to_transfer, lp->enc_bits, (double)lp->gain, true, host + n);
-    if (lp->tone) fill_tone_tables((double)lp->gain, lp->src_peak, lp->dst_peak, lp->unit_nits, lp->out_unit_nits, host + n + ne, host + n + ne + HM_TONE_STEPS);
-  };
-  auto point = [&](const float* dev) { la.lin = dev; la.enc = lp->encode ? dev + n : nullptr; la.tone = lp->tone ? dev + n + ne : nullptr; };
+  hm_light_args la = T.args(src_bytes);
+  auto fill = [&](float* host) { T.fill(host); };
+  auto point = [&](const float* dev) { T.point(&la, dev); };
   if (!resampled) {
     float* host = (float*)hm_pool_pinned_alloc(table_bytes);
     if (!host) return hm_fail(HM_ERR_NOMEM, "out of memory");
@@ -1008,6 +1045,168 @@ int hm_tone_to_tensor(int out_format, int bits, int src_w, int src_h, const void
 {
   if (!d_src || !dest || !tone) return hm_fail(HM_ERR_INVALID_ARG, "null argument");
   return light_to_tensor(out_format, bits, src_w, src_h, d_src, src_stride, view, light, tone, dest, stream);
+}
+
+// ---- the alpha step (hm_device_alpha) --------------------------------------------------------------------------------------------
+
+int hm_alpha_dest_format(int out_format, const hm_device_alpha* a, const hm_device_tone* tone)
+{
+  if (!a) return hm_fail(HM_ERR_INVALID_ARG, "null alpha step");
+  if (a->mode != HM_ALPHA_STRAIGHT && a->mode != HM_ALPHA_PREMULTIPLIED && a->mode != HM_ALPHA_MATTE) return hm_fail(HM_ERR_INVALID_ARG, "alpha: unknown mode %d", a->mode);
+  if (a->reserved[0] || a->reserved[1] || a->reserved[2]) return hm_fail(HM_ERR_INVALID_ARG, "alpha: reserved is not 0");
+  const bool matte = a->mode == HM_ALPHA_MATTE;
+  if (!matte && (a->background[0] || a->background[1] || a->background[2])) return hm_fail(HM_ERR_INVALID_ARG, "alpha: a background outside HM_ALPHA_MATTE");
+  if (a->background[3]) return hm_fail(HM_ERR_INVALID_ARG, "alpha: background[3] is %d, not 0", (int)a->background[3]);
+  if (out_format == 0 || hm_out_is_planar(out_format)) return hm_fail(HM_ERR_UNSUPPORTED, "planar YCbCr output (format %d) is not supported with a device destination", out_format);
+  const int obpp = hm_out_bytes_per_pixel(out_format);
+  if (obpp < 0) return obpp;
+  if (out_format == HM_OUT_RRGGBB_BE || out_format == HM_OUT_RRGGBBAA_BE)
+    return hm_fail(HM_ERR_INVALID_ARG, "alpha: a big-endian target has no sample values to multiply: ask for the _LE format");
+  if (out_format != HM_OUT_RGBA && out_format != HM_OUT_RRGGBBAA_LE) return hm_fail(HM_ERR_INVALID_ARG, "alpha: the three-channel output format %d carries no alpha", out_format);
+  if (out_format == HM_OUT_RGBA)
+    for (int c = 0; c < 3; c++)
+      if (a->background[c] > 255) return hm_fail(HM_ERR_INVALID_ARG, "alpha: background[%d] = %d above the peak 255", c, (int)a->background[c]);
+  if (a->mode == HM_ALPHA_PREMULTIPLIED && tone) return hm_fail(HM_ERR_INVALID_ARG, "alpha: HM_ALPHA_PREMULTIPLIED beside a tone step (tone-mapped premultiplied light is not a defined result)");
+  if (!matte) return out_format;
+  if (tone && tone->out_bits == 8) return HM_OUT_RGB;
+  return out_format == HM_OUT_RGBA ? HM_OUT_RGB : HM_OUT_RRGGBB_LE;
+}
+
+int hm_alpha_check_static(int out_format, const hm_device_dest* d, const hm_device_light* l, const hm_device_tone* tone, const hm_device_alpha* a, int explicit_from)
+{
+  const int dest_format = hm_alpha_dest_format(out_format, a, tone);
+  if (dest_format < 0) return dest_format;
+  if (!d) return hm_fail(HM_ERR_INVALID_ARG, "null device destination");
+  if (tone && !l) return hm_fail(HM_ERR_INVALID_ARG, "tone: null light step");
+  if (a->mode == HM_ALPHA_PREMULTIPLIED && l && l->to_transfer != HM_LIGHT_LINEAR)
+    return hm_fail(HM_ERR_INVALID_ARG, "alpha: HM_ALPHA_PREMULTIPLIED beside a light step that re-encodes (transfer %d; encoded premultiplied light is not a defined result)", l->to_transfer);
+  if (!l) return hm_dest_check_static(dest_format, d);
+  if (tone) {
+    const int rc = tone_check(tone, !explicit_from);
+    if (rc) return rc;
+    if (tone->out_bits == 8 && d->dtype == HM_DEV_U16) return hm_fail(HM_ERR_INVALID_ARG, "tone: out_bits 8 with HM_DEV_U16 (HM_DEV_U8 holds the codes)");
+    if (tone->out_bits == 8 && a->mode != HM_ALPHA_MATTE) // (a matte has three channels: the 8-bit finish takes it)
+      return hm_fail(HM_ERR_UNSUPPORTED, "tone: out_bits 8 with the four-channel output format %d is not supported", out_format);
+  }
+  return light_check(out_format, dest_format, d, l, explicit_from);
+}
+
+int hm_alpha_resolve(int out_format, int bits, int img_transfer, int img_primaries, const hm_device_dest* d, const hm_device_light* l, const hm_device_tone* tone,
+                     const hm_device_alpha* a, hm_light_plan* lp, hm_alpha_plan* ap)
+{
+  int rc = hm_alpha_check_static(out_format, d, l, tone, a, 0);
+  if (rc) return rc;
+  std::memset(ap, 0, sizeof(*ap));
+  ap->mode = a->mode;
+  ap->dest_format = hm_alpha_dest_format(out_format, a, tone);
+  if (out_format == HM_OUT_RGBA) bits = 8;
+  if (bits < 8 || bits > 16 || (bits == 8) != (out_format == HM_OUT_RGBA)) return hm_fail(HM_ERR_UNSUPPORTED, "alpha: samples of %d bits in output format %d", bits, out_format);
+  ap->bits = bits;
+  for (int c = 0; c < 3; c++) {
+    if (a->background[c] > (1 << bits) - 1) return hm_fail(HM_ERR_INVALID_ARG, "alpha: background[%d] = %d above the peak %d", c, (int)a->background[c], (1 << bits) - 1);
+    ap->background[c] = a->background[c];
+  }
+  if (!l) return HM_OK;
+  if (tone) return tone_plan_of(out_format, ap->dest_format, bits, img_transfer, img_primaries, l, tone, lp);
+  return light_plan_of(out_format, ap->dest_format, bits, img_transfer, img_primaries, l, lp);
+}
+
+int hm_alpha_write(const hm_device_dest* d, int out_format, int w, int h, const hm_view_plan* vp, const hm_light_plan* lp, const hm_alpha_plan* ap, const void* src,
+                   int src_stride, hipStream_t s, hm_view_scratch* sc)
+{
+  if (!sc || sc->pinned || sc->dev[0] || sc->dev[1]) return hm_fail(HM_ERR_INTERNAL, "alpha: no free scratch for the tables");
+  const bool summed = vp && !vp->crop_only && vp->filter != HM_VIEW_NEAREST;
+  if (ap->mode == HM_ALPHA_STRAIGHT && !summed) { // r_c = x_c: the write without the step
+    if (lp) return hm_light_write(d, out_format, w, h, vp, lp, src, src_stride, s, sc);
+    if (vp) return hm_view_write(d, out_format, vp, src, src_stride, s, sc);
+    return hm_dest_write(d, out_format, w, h, 0, h, src, src_stride, s);
+  }
+  const int ow = vp ? vp->ow : w, oh = vp ? vp->oh : h;
+  hm_dest_plan p; // (of the target the destination is written as: three channels under HM_ALPHA_MATTE)
+  int rc = hm_dest_resolve(ap->dest_format, ow, oh, d, &p);
+  if (!rc) rc = hm_dest_check_len(d, &p);
+  if (rc) return rc;
+  const int obpp = hm_out_bytes_per_pixel(out_format), src_bytes = obpp / 4;
+  if (obpp != 4 && obpp != 8) return hm_fail(HM_ERR_INTERNAL, "alpha: output format %d has no four channels", out_format);
+  const int cx = vp ? vp->x : 0, cy = vp ? vp->y : 0, cw = vp ? vp->w : w, ch = vp ? vp->h : h;
+  const uint8_t* origin = (const uint8_t*)src + (size_t)cy * src_stride + (size_t)cx * obpp;
+  const LightTables T(lp);
+  const size_t table_bytes = T.bytes();
+  hm_light_args la = T.args(src_bytes);
+  hm_alpha_args aa;
+  std::memset(&aa, 0, sizeof(aa));
+  aa.mode = ap->mode; aa.bits = ap->bits; aa.src_bytes = src_bytes; aa.P = (float)((1 << ap->bits) - 1);
+  // the background as the kernels take it: b_c = (float)background[c], with a light step lin[background[c]] of the table at `lin`
+  auto background = [&](const float* lin) { for (int c = 0; c < 3; c++) aa.bg[c] = lin ? lin[ap->background[c]] : (float)ap->background[c]; };
+  if (!summed) {
+    if (lp) {
+      float* host = (float*)hm_pool_pinned_alloc(table_bytes);
+      if (!host) return hm_fail(HM_ERR_NOMEM, "out of memory");
+      sc->pinned = host;
+      T.fill(host);
+      background(host);
+      if (!(sc->dev[0] = hm_pool_device_alloc(table_bytes))) return HM_ERR_NO_DEVICE;
+      if ((rc = hm_check_hip(hipMemcpyAsync(sc->dev[0], host, table_bytes, hipMemcpyHostToDevice, s), "upload of the light tables"))) return rc;
+      T.point(&la, (const float*)sc->dev[0]);
+    }
+    else background(nullptr);
+    if (vp && !vp->crop_only) return hm_launch_alpha_nearest(&p, lp ? &la : nullptr, &aa, origin, src_stride, cw, ch, ow, oh, d->ptr, d->scale, d->bias, s);
+    return hm_launch_alpha_tensor(&p, lp ? &la : nullptr, &aa, origin, src_stride, cw, ch, d->ptr, d->scale, d->bias, s);
+  }
+  // ONE pinned block and one upload: the tap tables of both axes, then the light tables
+  size_t words_x = 0, words_y = 0;
+  int tx = 0, ty = 0;
+  bool staged = false;
+  if ((rc = view_tables(vp, table_bytes, sc, &words_x, &words_y, &tx, &ty, &staged))) return rc;
+  const size_t tap_bytes = (words_x + words_y) * 4, bytes = tap_bytes + table_bytes;
+  int32_t* host = (int32_t*)sc->pinned;
+  float* host_tables = reinterpret_cast<float*>(host + words_x + words_y);
+  T.fill(host_tables);
+  background(lp ? host_tables : nullptr);
+  if (!(sc->dev[0] = hm_pool_device_alloc(bytes))) return HM_ERR_NO_DEVICE;
+  hm_dest_plan p4 = p; // the intermediate holds four sums per pixel, whatever the destination's channel count
+  p4.channels = 4;
+  hm_resample_args r = resample_args_of(vp, src_bytes, origin, src_stride, sc->dev[0], words_x, tx, ty, p4);
+  if (!(sc->dev[1] = hm_pool_device_alloc(resample_tmp_floats(r, p4) * sizeof(float)))) return HM_ERR_NO_DEVICE;
+  if ((rc = hm_check_hip(hipMemcpyAsync(sc->dev[0], host, bytes, hipMemcpyHostToDevice, s), "upload of the tap and light tables"))) return rc;
+  r.tmp = (float*)sc->dev[1];
+  T.point(&la, reinterpret_cast<const float*>(sc->dev[0]) + words_x + words_y);
+  return hm_launch_alpha_resample(&p, lp ? &la : nullptr, &aa, &r, d->ptr, d->scale, d->bias, s);
+}
+
+int hm_alpha_to_tensor(int out_format, int bits, int src_w, int src_h, const void* d_src, int src_stride, const hm_device_view* view, const hm_device_light* light,
+                       const hm_device_tone* tone, const hm_device_alpha* alpha, const hm_device_dest* dest, void* stream)
+{
+  if (!d_src || !dest || !alpha) return hm_fail(HM_ERR_INVALID_ARG, "null argument");
+  int rc = hm_alpha_check_static(out_format, dest, light, tone, alpha, 1);
+  if (rc) return rc;
+  if (src_w <= 0 || src_h <= 0 || src_w > 32768 || src_h > 32768) return hm_fail(HM_ERR_INVALID_ARG, "image size %d x %d", src_w, src_h);
+  hm_view_plan vp;
+  std::memset(&vp, 0, sizeof(vp));
+  vp.ow = src_w; vp.oh = src_h;
+  if (view && (rc = hm_view_resolve(out_format, src_w, src_h, view, &vp))) return rc;
+  hm_light_plan lp;
+  hm_alpha_plan ap;
+  if ((rc = hm_alpha_resolve(out_format, bits, light ? light->from_transfer : 0, light ? light->from_primaries : 0, dest, light, tone, alpha, &lp, &ap))) return rc;
+  hm_dest_plan p;
+  if ((rc = hm_dest_resolve(ap.dest_format, vp.ow, vp.oh, dest, &p)) || (rc = hm_dest_check_len(dest, &p))) return rc;
+  if (src_stride < src_w * hm_out_bytes_per_pixel(out_format)) return hm_fail(HM_ERR_INVALID_ARG, "src_stride %d below the bytes of a row", src_stride);
+  if (out_format == HM_OUT_RRGGBBAA_LE && (((uintptr_t)d_src | (unsigned)src_stride) & 1)) return hm_fail(HM_ERR_INVALID_ARG, "16-bit samples at an odd address or stride");
+  int n_dev = 0;
+  if (hipGetDeviceCount(&n_dev) != hipSuccess || n_dev == 0) { (void)hipGetLastError(); return hm_fail(HM_ERR_NO_DEVICE, "no HIP device available"); }
+  if ((rc = hm_dest_check_pointer(dest))) return rc;
+  release_done();
+  hm_view_scratch* sc = new (std::nothrow) hm_view_scratch();
+  if (!sc) return hm_fail(HM_ERR_NOMEM, "out of memory");
+  rc = hm_alpha_write(dest, out_format, src_w, src_h, view ? &vp : nullptr, light ? &lp : nullptr, &ap, d_src, src_stride, (hipStream_t)stream, sc);
+  if (!sc->dev[0] && !sc->dev[1] && !sc->pinned) { delete sc; return rc; }
+  if (hipLaunchHostFunc((hipStream_t)stream, scratch_done, sc) != hipSuccess) { // (never on a healthy runtime: wait, then release here)
+    (void)hipGetLastError();
+    hipStreamSynchronize((hipStream_t)stream);
+    hm_view_scratch_free(sc);
+    delete sc;
+  }
+  return rc;
 }
 
 // ---- planar views: every plane an image of its own ------------------------------------------------------------------------------

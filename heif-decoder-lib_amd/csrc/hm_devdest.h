@@ -176,6 +176,38 @@ int hm_launch_light_nearest(const hm_dest_plan* p, const hm_light_args* la, cons
 int hm_launch_light_resample(const hm_dest_plan* p, const hm_light_args* la, const hm_resample_args* r, void* dst, const float scale[4], const float bias[4],
                              hipStream_t s);
 
+// ---- the alpha step (hm_device_alpha): premultiplied sums, a straight / premultiplied / matte result, alone or beside the light and
+//      tone steps.  devdest.cpp holds the checks and the write step, alpha.hip the kernels ----
+typedef struct hm_alpha_plan {
+  int32_t mode;          // HM_ALPHA_*
+  int32_t bits;          // of the target's samples: P = (1 << bits) - 1
+  int32_t dest_format;   // the target the destination is judged, sized and written as (hm_alpha_dest_format)
+  uint16_t background[3];
+} hm_alpha_plan;
+// what depends on the request alone: the step's own refusals, then those of the tone, light and destination checks against
+// hm_alpha_dest_format (l and tone may be NULL).  A background above the peak of an 8-bit target is refused here, of a 16-bit one in
+// hm_alpha_resolve.
+int hm_alpha_check_static(int out_format, const hm_device_dest* d, const hm_device_light* l, const hm_device_tone* tone, const hm_device_alpha* a, int explicit_from);
+// ... and what depends on the image: bits, the background against the peak, and with a light step hm_tone_resolve's work into *lp (its
+// dest_format: the alpha step's)
+int hm_alpha_resolve(int out_format, int bits, int img_transfer, int img_primaries, const hm_device_dest* d, const hm_device_light* l, const hm_device_tone* tone,
+                     const hm_device_alpha* a, hm_light_plan* lp, hm_alpha_plan* ap);
+// hm_dest_write / hm_view_write / hm_light_write under an alpha step: the w x h four-channel image at `src` (vp NULL), or its view vp,
+// into the destination, which has been checked against the size written (as ap->dest_format); lp NULL: no light step.  HM_ALPHA_STRAIGHT
+// without sums is the write without the step.  Asynchronous on `s`; tables and the intermediate hang on sc.
+int hm_alpha_write(const hm_device_dest* d, int out_format, int w, int h, const hm_view_plan* vp, const hm_light_plan* lp, const hm_alpha_plan* ap, const void* src,
+                   int src_stride, hipStream_t s, hm_view_scratch* sc);
+
+// what the kernels get beside hm_light_args (la NULL: no light step): bytes of a source sample, P, and the background as the floats b_c
+typedef struct hm_alpha_args { int32_t mode, bits, src_bytes; float P; float bg[3]; } hm_alpha_args;
+int hm_launch_alpha_tensor(const hm_dest_plan* p, const hm_light_args* la, const hm_alpha_args* aa, const void* src, int src_stride, int w, int rows, void* dst,
+                           const float scale[4], const float bias[4], hipStream_t s);
+int hm_launch_alpha_nearest(const hm_dest_plan* p, const hm_light_args* la, const hm_alpha_args* aa, const void* src, int src_stride, int n_w, int n_h, int ow, int oh,
+                            void* dst, const float scale[4], const float bias[4], hipStream_t s);
+// r: of a FOUR-channel intermediate (the sums of p_R, p_G, p_B and a), whatever the destination's channel count
+int hm_launch_alpha_resample(const hm_dest_plan* p, const hm_light_args* la, const hm_alpha_args* aa, const hm_resample_args* r, void* dst, const float scale[4],
+                             const float bias[4], hipStream_t s);
+
 // ---- planar views: a view (hm_device_view) into planar YCbCr (hm_device_planes), every plane an image of its own.  devdest.cpp
 //      holds the checks and the write step, hm_planes_view.h the index arithmetic, planes_view.hip the kernels ----
 typedef struct hm_planes_view_plan {

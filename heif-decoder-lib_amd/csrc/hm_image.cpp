@@ -836,10 +836,10 @@ void parse_picture(const hm_file* f, uint32_t id, bool few_pictures, int strict,
 
 int target_check_shape(const OutputTarget& t)
 {
-  const bool ok = !(t.dest && t.planes) && (!t.light || t.dest) && (!t.tone || t.light) && (!t.view || t.dest || t.planes) && (!t.view_later || (t.view && t.dest)) &&
+  const bool ok = !(t.dest && t.planes) && (!t.light || t.dest) && (!t.tone || t.light) && (!t.alpha || (t.dest && !t.view_later)) && (!t.view || t.dest || t.planes) && (!t.view_later || (t.view && t.dest)) &&
                   (!t.planes_later || (t.view && t.planes));
-  return ok ? (int)HM_OK : hm_fail(HM_ERR_INTERNAL, "output target: dest%s view%s planes%s light%s tone%s do not go together", t.dest ? "+" : "-", t.view ? "+" : "-",
-                                   t.planes ? "+" : "-", t.light ? "+" : "-", t.tone ? "+" : "-");
+  return ok ? (int)HM_OK : hm_fail(HM_ERR_INTERNAL, "output target: dest%s view%s planes%s light%s tone%s alpha%s do not go together", t.dest ? "+" : "-", t.view ? "+" : "-",
+                                   t.planes ? "+" : "-", t.light ? "+" : "-", t.tone ? "+" : "-", t.alpha ? "+" : "-");
 }
 
 // the chroma format and depth of a planar result for a decoded image of (chroma, bd): what emit_native / emit_planar hand out
@@ -873,6 +873,12 @@ static Reported converted_report(const hm::NclxProfile& native, bool is_grid, in
   return r;
 }
 
+// the target the destination of t.dest is judged, sized and written as (the alpha step's own refusals: check_target_request has made them)
+static int target_dest_format(const hm_decode_params* params, const OutputTarget& t)
+{
+  return t.alpha ? hm_alpha_dest_format(params->out_format, t.alpha, t.tone) : hm_tone_dest_format(params->out_format, t.tone);
+}
+
 // Can the target hold the result of a w x h image of (chroma, bits)?  The one statement of that question: the entry points ask it
 // against what the file declares, the sequence and emit_image again against the decoded picture.  A new kind of destination gets
 // its chain here.
@@ -893,9 +899,14 @@ static int target_fits(const hm_decode_params* params, const OutputTarget& t, in
       hm_view_plan vp;
       vp.ow = w; vp.oh = h;
       if (t.view && (rc = hm_view_resolve(params->out_format, w, h, t.view, &vp))) return rc;
-      if ((rc = hm_dest_resolve(hm_tone_dest_format(params->out_format, t.tone), vp.ow, vp.oh, t.dest, &dp)) || (rc = hm_dest_check_len(t.dest, &dp))) return rc;
+      const int dest_format = target_dest_format(params, t);
+      if (dest_format < 0) return dest_format;
+      if ((rc = hm_dest_resolve(dest_format, vp.ow, vp.oh, t.dest, &dp)) || (rc = hm_dest_check_len(t.dest, &dp))) return rc;
       hm_light_plan lp;
-      if (t.light && reported && (rc = hm_tone_resolve(params->out_format, reported->bit_depth, reported->transfer, reported->primaries, t.dest, t.light, t.tone, &lp)))
+      hm_alpha_plan ap;
+      if (t.alpha && reported && (rc = hm_alpha_resolve(params->out_format, reported->bit_depth, reported->transfer, reported->primaries, t.dest, t.light, t.tone, t.alpha, &lp, &ap)))
+        return rc;
+      if (!t.alpha && t.light && reported && (rc = hm_tone_resolve(params->out_format, reported->bit_depth, reported->transfer, reported->primaries, t.dest, t.light, t.tone, &lp)))
         return rc;
     }
     if (pointers && ((rc = require_device()) || (rc = hm_dest_check_pointer(t.dest)))) return rc;
@@ -1042,7 +1053,13 @@ static int emit_interleaved(const hm_decode_params* params, hipStream_t s, Plana
     std::memset(&vp, 0, sizeof(vp));
     vp.ow = img_w; vp.oh = img_h;
     if (t.view && (rc = hm_view_resolve(params->out_format, img_w, img_h, t.view, &vp))) return rc;
-    if (t.light) { // ... through the light step, resolved against the profile and depth this image reports: refused before a byte is written
+    if (t.alpha) { // ... through the alpha step (and the light step beside it), resolved as the light step below is
+      hm_light_plan lp;
+      hm_alpha_plan ap;
+      if ((rc = hm_alpha_resolve(params->out_format, r.bit_depth, r.transfer, r.primaries, t.dest, t.light, t.tone, t.alpha, &lp, &ap))) return rc;
+      if ((rc = hm_alpha_write(t.dest, params->out_format, img_w, img_h, t.view ? &vp : nullptr, t.light ? &lp : nullptr, &ap, dout.p, cd.out_stride, s, t.scratch))) return rc;
+    }
+    else if (t.light) { // ... through the light step, resolved against the profile and depth this image reports: refused before a byte is written
       hm_light_plan lp;
       if ((rc = hm_tone_resolve(params->out_format, r.bit_depth, r.transfer, r.primaries, t.dest, t.light, t.tone, &lp))) return rc;
       if ((rc = hm_light_write(t.dest, params->out_format, img_w, img_h, t.view ? &vp : nullptr, &lp, dout.p, cd.out_stride, s, t.scratch))) return rc;
@@ -1057,7 +1074,7 @@ static int emit_interleaved(const hm_decode_params* params, hipStream_t s, Plana
       out->plane_width[0] = vp.ow; out->plane_height[0] = vp.oh;
     }
     hm_dest_plan dp;
-    if ((rc = hm_dest_resolve(hm_tone_dest_format(params->out_format, t.tone), vp.ow, vp.oh, t.dest, &dp))) return rc;
+    if ((rc = hm_dest_resolve(target_dest_format(params, t), vp.ow, vp.oh, t.dest, &dp))) return rc;
     out->used_ext_dst = 1;
     out->stride[0] = (int32_t)std::min<int64_t>(dp.row_pitch, 0x7FFFFFFF);
   }
@@ -1177,7 +1194,8 @@ int check_target_request(const hm_file* f, uint32_t id, const hm_decode_params* 
   if (rc) return rc;
   if (t.dest) {
     if (params->ext_dst) return hm_fail(HM_ERR_INVALID_ARG, "params->ext_dst must be NULL with a device destination");
-    if (t.tone) { if ((rc = hm_tone_check_static(params->out_format, t.dest, t.light, t.tone, 0))) return rc; } // (its own refusals, then the two below)
+    if (t.alpha) { if ((rc = hm_alpha_check_static(params->out_format, t.dest, t.light, t.tone, t.alpha, 0))) return rc; } // (its own refusals, then all of those below)
+    else if (t.tone) { if ((rc = hm_tone_check_static(params->out_format, t.dest, t.light, t.tone, 0))) return rc; } // (its own refusals, then the two below)
     else {
       if ((rc = hm_dest_check_static(params->out_format, t.dest))) return rc;
       if (t.light && (rc = hm_light_check_static(params->out_format, t.dest, t.light, 0))) return rc;
@@ -1698,6 +1716,18 @@ int hm_decode_item_to_device_tone(const hm_file* f, uint32_t id, const hm_decode
   return decode_item_to(f, id, params, OutputTarget::to_dest(dest, view, light, &own), out);
 }
 
+int hm_decode_item_to_device_alpha(const hm_file* f, uint32_t id, const hm_decode_params* params, const hm_device_view* view, const hm_device_light* light,
+                                   const hm_device_tone* tone, const hm_device_alpha* alpha, const hm_device_dest* dest, hm_decoded* out)
+{
+  if (!f || !params || !alpha || !dest || !out) return hm_fail(HM_ERR_INVALID_ARG, "null argument");
+  if (tone && !light) return hm_fail(HM_ERR_INVALID_ARG, "tone: null light step");
+  hm_device_tone own{};
+  if (tone) own = tone_for_item(f, id, tone);
+  OutputTarget t = OutputTarget::to_dest(dest, view, light, tone ? &own : nullptr);
+  t.alpha = alpha;
+  return decode_item_to(f, id, params, t, out);
+}
+
 int hm_file_item_light_levels(const hm_file* f, uint32_t id, hm_light_levels* out)
 {
   if (!f || !out) return hm_fail(HM_ERR_INVALID_ARG, "null argument");
@@ -1810,7 +1840,7 @@ static int decode_item(const hm_file* f, uint32_t id, const hm_decode_params* pa
 {
   std::memset(out, 0, sizeof(*out)); // (whatever fails below: nothing of an earlier call is left in it)
   if (is_derived_item(f, id)) return decode_derived(f, id, params, target, out);
-  if (!target.view && !target.light) { // (r06) a grid of more tiles than parsing threads, to interleaved pixels: slab by slab under the entropy decode (decode_grid_cut)
+  if (!target.view && !target.light && !target.alpha) { // (r06) a grid of more tiles than parsing threads, to interleaved pixels: slab by slab under the entropy decode (decode_grid_cut)
     bool applicable = false;
     const int prc = decode_grid_cut(f, id, params, nullptr, 1, /*pipelined=*/true, out, &applicable, target.dest);
     if (prc || applicable) return prc;

@@ -110,6 +110,7 @@ struct OutputTarget {
   const hm_device_planes* planes = nullptr;    // a planar result (out_format 0 / HM_OUT_YCBCR_*) goes to caller-owned device memory, plane by plane
   const hm_device_light* light = nullptr;      // the light step in the write of dest
   const hm_device_tone* tone = nullptr;        // ... with a tone step inside it (src_peak resolved by the entry point: never 0 here)
+  const hm_device_alpha* alpha = nullptr;      // the alpha step in the write of dest (alone, or beside light and tone)
   hm_view_scratch* scratch = nullptr;          // tap tables and the intermediate of the resampling step, the tables of the light step
   hm_view_item* view_later = nullptr;          // view + dest: the view is not written, only described there - the caller writes it with those of other images
   hm_planes_view_item* planes_later = nullptr; // the same for view + planes
@@ -126,7 +127,7 @@ struct OutputTarget {
     return t;
   }
 };
-// dest xor planes (or neither); light only with dest; tone only with light; view only with one of the two; a *_later only with view and its own kind of destination
+// dest xor planes (or neither); light only with dest; tone only with light; alpha only with dest and never with view_later; view only with one of the two; a *_later only with view and its own kind of destination
 int target_check_shape(const OutputTarget& t);
 
 // a job's own copies of the caller's structs (the pipeline outlives them; hm_decode_params keeps its layout, so they travel beside
@@ -137,6 +138,7 @@ struct OwnedTarget {
   hm_device_planes planes{};
   hm_device_light light{};
   hm_device_tone tone{};
+  hm_device_alpha alpha{};
   OutputTarget t;
   OwnedTarget() = default;
   OwnedTarget(const OwnedTarget&) = delete;
@@ -149,6 +151,7 @@ struct OwnedTarget {
     if (from.planes) { planes = *from.planes; t.planes = &planes; }
     if (from.light) { light = *from.light; t.light = &light; }
     if (from.tone) { tone = *from.tone; t.tone = &tone; }
+    if (from.alpha) { alpha = *from.alpha; t.alpha = &alpha; }
   }
 };
 

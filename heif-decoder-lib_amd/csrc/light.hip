@@ -18,66 +18,13 @@
 // noise the worst; no layout of a table changes that.
 // The matrix and the scalars of the step are kernel arguments (SGPRs).  -ffp-contract=off, __fmul_rn / __fadd_rn throughout.
 // What is stored is out_elem.h's: a code value is `moved`, linear light goes through `linear_out`, a resampled alpha value through
-// `finish`.
+// `finish`.  The per-pixel rules - table fill, re-encoding, matrix, tone step, colour_out - are light_step.h's, shared with alpha.hip.
 #include "hm_devdest.h"
+#include "light_step.h"
 #include "out_launch.h"
 #include "out_rows.h"
 
 namespace {
-
-// ebits: of the codes of enc (bits, or 8 under the 8-bit finish); tone: thr[TONE_STEPS], then sg[TONE_STEPS] (NULL: no tone step)
-struct Light { const float* lin; const float* enc; const float* tone; int bits, ebits, encode, matrix; float m[9]; };
-constexpr int TONE_STEPS = HM_TONE_STEPS;
-
-// a[na], b[nb], c[nc] (each may be NULL: nothing is copied, its place stays) -> lds, one behind the other; every thread of the
-// workgroup comes here
-__device__ __forceinline__ void fill_tables(float* lds, const float* __restrict__ a, int na, const float* __restrict__ b, int nb, const float* __restrict__ c, int nc)
-{
-  if (a) for (int i = threadIdx.x; i < na; i += 256) lds[i] = a[i];
-  if (b) for (int i = threadIdx.x; i < nb; i += 256) lds[na + i] = b[i];
-  if (c) for (int i = threadIdx.x; i < nc; i += 256) lds[na + nb + i] = c[i];
-  __syncthreads();
-}
-
-// |{c in 1 .. peak : enc[c] <= r}|: enc rises, so the count is the largest c whose threshold r has reached (0: none; a NaN: none)
-__device__ __forceinline__ unsigned encode_of(const float* enc, int bits, float r)
-{
-  int code = 0;
-  for (int step = 1 << (bits - 1); step; step >>= 1) { // (code + step <= peak: the steps sum to it)
-    const int t = code + step;
-    if (enc[t] <= r) code = t;
-  }
-  return (unsigned)code;
-}
-
-__device__ __forceinline__ void gamut(const Light& L, float r[3])
-{
-  if (!L.matrix) return;
-  const float R = r[0], G = r[1], B = r[2];
-  r[0] = __fadd_rn(__fadd_rn(__fmul_rn(L.m[0], R), __fmul_rn(L.m[1], G)), __fmul_rn(L.m[2], B));
-  r[1] = __fadd_rn(__fadd_rn(__fmul_rn(L.m[3], R), __fmul_rn(L.m[4], G)), __fmul_rn(L.m[5], B));
-  r[2] = __fadd_rn(__fadd_rn(__fmul_rn(L.m[6], R), __fmul_rn(L.m[7], G)), __fmul_rn(L.m[8], B));
-}
-
-// the tone step on one pixel's linear light; tl: thr, then sg, in LDS
-__device__ __forceinline__ void tone_map(const float* tl, float r[3])
-{
-  const float N = fmaxf(fmaxf(r[0], r[1]), r[2]);
-  int k = 0;
-  for (int step = TONE_STEPS >> 1; step; step >>= 1) { // (k + step <= TONE_STEPS - 1: the steps sum to it)
-    const int t = k + step;
-    if (tl[t] <= N) k = t;
-  }
-  const float g = tl[TONE_STEPS + k];
-  r[0] = __fmul_rn(r[0], g); r[1] = __fmul_rn(r[1], g); r[2] = __fmul_rn(r[2], g);
-}
-
-// linear light r of a colour channel to an element of the destination; enc: the threshold table in LDS
-template <typename OutT> __device__ __forceinline__ OutT colour_out(const Light& L, const float* enc, float r, float sc, float bi)
-{
-  if (L.encode) return moved<OutT>(encode_of(enc, L.ebits, r), sc, bi);
-  return linear_out<OutT>(r, sc, bi);
-}
 
 // one pixel that is moved, not resampled: v0 .. v2 its colour samples, v3 its alpha sample (C == 4); lds = lin, then enc, then thr and sg
 template <int C, typename OutT>
@@ -256,22 +203,6 @@ const void* const g_finish8_instances[] = {
 #undef HM_LN_SET
 #undef HM_LV_SET
 
-Light light_of(const hm_light_args* la)
-{
-  Light L;
-  L.lin = la->lin; L.enc = la->enc; L.tone = la->tone; L.bits = la->bits; L.ebits = la->enc_bits; L.encode = la->encode; L.matrix = la->matrix;
-  for (int i = 0; i < 9; i++) L.m[i] = la->m[i];
-  return L;
-}
-
-// the tables a pointwise kernel holds in LDS
-// the dynamic LDS of a launch: the pointwise and nearest kernels hold lin, enc and the tone tables, k_light_h lin, k_light_v enc and the
-// tone tables (hm_light_lds_bytes hands these out to the tests)
-size_t tone_bytes(const hm_light_args* la) { return la->tone ? 2 * (size_t)TONE_STEPS * sizeof(float) : 0; }
-size_t h_bytes(const hm_light_args* la) { return (size_t)4 << la->bits; }
-size_t v_bytes(const hm_light_args* la) { return (la->encode ? (size_t)4 << la->enc_bits : 0) + tone_bytes(la); }
-size_t tables_bytes(const hm_light_args* la) { return h_bytes(la) + v_bytes(la); }
-
 template <int SB, int C, typename OutT, bool CHW>
 int launch_tensor(const hm_dest_plan* p, const hm_light_args* la, const uint8_t* src, int src_stride, int w, int rows, uint8_t* dst, const Affine& a, hipStream_t s)
 {
@@ -282,10 +213,10 @@ int launch_tensor(const hm_dest_plan* p, const hm_light_args* la, const uint8_t*
   const dim3 grid((unsigned)((groups + 63) / 64), (unsigned)((rows + 3) / 4)), block(256);
   const Light L = light_of(la);
   if (vec)
-    hipLaunchKernelGGL((k_light_tensor<SB, C, OutT, CHW, true>), grid, block, tables_bytes(la), s, src, src_stride, w, rows, dst, (long long)p->row_pitch,
+    hipLaunchKernelGGL((k_light_tensor<SB, C, OutT, CHW, true>), grid, block, light_tables_bytes(la), s, src, src_stride, w, rows, dst, (long long)p->row_pitch,
                        (long long)p->plane_pitch, a, L);
   else
-    hipLaunchKernelGGL((k_light_tensor<SB, C, OutT, CHW, false>), grid, block, tables_bytes(la), s, src, src_stride, w, rows, dst, (long long)p->row_pitch,
+    hipLaunchKernelGGL((k_light_tensor<SB, C, OutT, CHW, false>), grid, block, light_tables_bytes(la), s, src, src_stride, w, rows, dst, (long long)p->row_pitch,
                        (long long)p->plane_pitch, a, L);
   return hm_check_hip(hipGetLastError(), "k_light_tensor launch");
 }
@@ -314,11 +245,11 @@ int launch_nearest(const hm_dest_plan* p, const hm_light_args* la, const uint8_t
   const Light L = light_of(la);
   constexpr bool finish8 = sizeof(InT) == 2 && sizeof(OutT) == 1; // the 8-bit finish of a deeper image: three channels only (check_args)
   if (p->channels == 3)
-    hipLaunchKernelGGL((k_light_nearest<InT, 3, OutT>), grid, block, tables_bytes(la), s, src, src_stride, n_w, n_h, ow, oh, chw, dst, (long long)p->row_pitch,
+    hipLaunchKernelGGL((k_light_nearest<InT, 3, OutT>), grid, block, light_tables_bytes(la), s, src, src_stride, n_w, n_h, ow, oh, chw, dst, (long long)p->row_pitch,
                        (long long)p->plane_pitch, a, L);
   else if constexpr (finish8) return NO_KERNEL_INSTANCE;
   else
-    hipLaunchKernelGGL((k_light_nearest<InT, 4, OutT>), grid, block, tables_bytes(la), s, src, src_stride, n_w, n_h, ow, oh, chw, dst, (long long)p->row_pitch,
+    hipLaunchKernelGGL((k_light_nearest<InT, 4, OutT>), grid, block, light_tables_bytes(la), s, src, src_stride, n_w, n_h, ow, oh, chw, dst, (long long)p->row_pitch,
                        (long long)p->plane_pitch, a, L);
   return HM_OK;
 }
@@ -328,7 +259,7 @@ void launch_h(bool chw, const hm_resample_args* r, const hm_light_args* la, hipS
 {
   const dim3 grid((unsigned)((r->ow + 63) / 64), (unsigned)((r->n_h + 3) / 4)), block(256);
   const uint8_t* src = (const uint8_t*)r->src;
-  const size_t lds = h_bytes(la);
+  const size_t lds = light_h_bytes(la);
   if (chw)
     hipLaunchKernelGGL((k_light_h<SB, C, true>), grid, block, lds, s, src, r->src_stride, r->n_h, r->ow, r->ax.first, r->ax.count, r->ax.weights, r->tmp,
                        (long long)r->tmp_pitch, (long long)r->tmp_plane, la->lin, la->bits);
@@ -341,7 +272,7 @@ template <typename OutT>
 void launch_v(const hm_dest_plan* p, const hm_resample_args* r, const hm_light_args* la, uint8_t* dst, const Affine& a, hipStream_t s)
 {
   const dim3 grid((unsigned)((r->ow + 63) / 64), (unsigned)((r->oh + 3) / 4)), block(256);
-  const size_t lds = v_bytes(la);
+  const size_t lds = light_v_bytes(la);
   const Light L = light_of(la);
   const bool chw = p->layout == HM_DEV_LAYOUT_CHW;
 #define HM_LV_GO(CHW_, C_) \
@@ -386,7 +317,7 @@ extern "C" long long hm_light_lds_bytes(int bits, int enc_bits, int encode, int 
   static const float some = 0.0f;
   hm_light_args la = {};
   la.bits = bits; la.enc_bits = enc_bits; la.encode = encode; la.tone = tone ? &some : nullptr;
-  return (long long)(pass == 0 ? tables_bytes(&la) : pass == 1 ? h_bytes(&la) : v_bytes(&la));
+  return (long long)(pass == 0 ? light_tables_bytes(&la) : pass == 1 ? light_h_bytes(&la) : light_v_bytes(&la));
 }
 
 // rows [0, rows) of `src` through the light step to `dst` = the destination's first element; asynchronous on `s`

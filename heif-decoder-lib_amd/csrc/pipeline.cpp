@@ -219,6 +219,16 @@ int hm_pipeline_submit_to_device_tone(hm_pipeline* p, const uint8_t* heif, size_
   return submit(p, heif, size, item_id, tag, OutputTarget::to_dest(dest, view, light, tone));
 }
 
+int hm_pipeline_submit_to_device_alpha(hm_pipeline* p, const uint8_t* heif, size_t size, uint32_t item_id, uint64_t tag, const hm_device_view* view,
+                                       const hm_device_light* light, const hm_device_tone* tone, const hm_device_alpha* alpha, const hm_device_dest* dest)
+{
+  if (!p || !heif || !alpha || !dest) return hm_fail(HM_ERR_INVALID_ARG, "null argument");
+  if (tone && !light) return hm_fail(HM_ERR_INVALID_ARG, "tone: null light step");
+  OutputTarget t = OutputTarget::to_dest(dest, view, light, tone);
+  t.alpha = alpha;
+  return submit(p, heif, size, item_id, tag, t);
+}
+
 int hm_pipeline_submit_to_device_planes(hm_pipeline* p, const uint8_t* heif, size_t size, uint32_t item_id, uint64_t tag, const hm_device_planes* planes)
 {
   if (!p || !heif || !planes) return hm_fail(HM_ERR_INVALID_ARG, "null argument");

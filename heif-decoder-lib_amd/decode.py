@@ -13,6 +13,9 @@ light=dict(to_transfer="srgb", to_primaries="bt709", gain=1.0, from_transfer=...
 primaries - a resize under light= averages light, not code values.  tone=dict(dst_peak=203.0, src_peak=None, unit_nits=None,
 out_unit_nits=None, out_bits=None) beside light= maps the content's peak (None: the file's clli / mdcv, else 1000 cd/m2) to the
 display's with the BT.2390 curve; out_bits=8 finishes a deeper image in 8-bit codes (torch.uint8 is then accepted for it).
+alpha="straight" / "premultiplied" / dict(mode="matte", background=(r, g, b)) with out_format "rgba" / "rrggbbaa_le" uses the alpha
+channel: a resize sums colour times alpha (no dark fringes around a cut-out), and the tensor holds straight colour, premultiplied
+colour, or - three channels - the picture over the background colour (code values at the target's sample depth).
 What the library refuses raises capi.HmError.
 
 Planar YCbCr stays planar: decode_to_planes / decode_sequence_to_planes / decode_batch_to_planes return (Y, Cb, Cr[, A]) ("planar":
@@ -174,6 +177,41 @@ def _tone_of(tone, lit):
     return d
 
 
+ALPHA_MODES = {"straight": capi.HM_ALPHA_STRAIGHT, "premultiplied": capi.HM_ALPHA_PREMULTIPLIED, "matte": capi.HM_ALPHA_MATTE}
+
+
+def _alpha_of(alpha, fmt):
+    """(hm_device_alpha or None, channels of the tensor) of the alpha= argument for the target fmt: "straight", "premultiplied", or a
+    dict of mode and - for "matte" - background=(r, g, b), code values at the target's sample depth; a matte has three channels"""
+    if alpha is None or alpha is False:
+        return None, _channels(fmt)
+    if isinstance(alpha, str):
+        alpha = {"mode": alpha}
+    if not isinstance(alpha, dict):
+        raise ValueError(f"alpha {alpha!r}: 'straight', 'premultiplied' or a dict")
+    keys = {"mode", "background"}
+    if set(alpha) - keys:
+        raise ValueError(f"alpha: unknown keys {sorted(set(alpha) - keys)}, known are {sorted(keys)}")
+    mode = alpha.get("mode")
+    if not isinstance(mode, str) or mode.lower() not in ALPHA_MODES:
+        raise ValueError(f"alpha: mode {mode!r}: one of {sorted(ALPHA_MODES)}")
+    if _channels(fmt) != 4:
+        raise ValueError("alpha: needs a four-channel out_format ('rgba', 'rrggbbaa_le')")
+    d = capi.DeviceAlpha()
+    d.mode = ALPHA_MODES[mode.lower()]
+    bg = alpha.get("background")
+    if d.mode == capi.HM_ALPHA_MATTE:
+        if bg is None or len(tuple(bg)) != 3:
+            raise ValueError("alpha: a matte needs background=(r, g, b)")
+        for k, v in enumerate(bg):
+            if isinstance(v, bool) or not hasattr(v, "__index__") or not 0 <= v.__index__() <= 65535:
+                raise ValueError(f"alpha: background[{k}] = {v!r}: a code value at the target's sample depth")
+            d.background[k] = v.__index__()
+    elif bg is not None:
+        raise ValueError(f"alpha: background with mode {mode!r} (a matte takes one)")
+    return d, 3 if d.mode == capi.HM_ALPHA_MATTE else 4
+
+
 def _default_threads():
     return max(1, min(16, os.cpu_count() or 1))
 
@@ -197,20 +235,22 @@ class _File:
 
 
 def decode_to_tensor(data, item_id=0, out_format="rgb", layout="chw", dtype=None, scale=None, bias=None, out=None, stream=None,
-                     host_threads=None, crop=None, size=None, filter="triangle", light=None, tone=None):
+                     host_threads=None, crop=None, size=None, filter="triangle", light=None, tone=None, alpha=None):
     """Decode one image of a HEIF file (bytes; item_id 0 = the primary item) into a CUDA tensor: C x H x W ("chw") or H x W x C
     ("hwc").  dtype defaults to torch.float32 (out's dtype when out is given).  out: a CUDA tensor of that shape to write into;
     its row (and plane) stride is honoured, bytes between rows are left alone.  stream: a torch.cuda.Stream or a raw stream
     handle (default: the current stream).  crop: (x, y, w, h), a rectangle of the image; size: (w, h), what it is resampled to
     (H and W of the tensor are then the size's, or the crop's); filter: "triangle", "bicubic", "lanczos3" or "nearest".  light: True (linear
     light) or a dict (see the module's text): the light step in the write of the tensor; tone: a dict (see the module's text), the tone
-    step inside it.  Returns when the pixels are in place."""
+    step inside it; alpha: "straight", "premultiplied" or dict(mode="matte", background=(r, g, b)) (see the module's text), the alpha step,
+    for a four-channel out_format - a matte gives a tensor of 3 channels.  Returns when the pixels are in place."""
     import torch
     L = capi.image_lib()
     fmt, lay = _out_format(out_format), _layout(layout)
     if dtype is None:
         dtype = out.dtype if out is not None else torch.float32
-    code, c = _dtype_code(dtype), _channels(fmt)
+    code = _dtype_code(dtype)
+    alp, c = _alpha_of(alpha, fmt)
     f = _File(data)
     try:
         iid, w, h = f.size(item_id)
@@ -232,7 +272,11 @@ def decode_to_tensor(data, item_id=0, out_format="rgb", layout="chw", dtype=None
         prm = capi.DecodeParams(fmt, host_threads or _default_threads(), 0, 0, handle or None, None, 0, 0, 0, 0)
         d = capi.Decoded()
         with torch.cuda.device(out.device):
-            if ton is not None:
+            if alp is not None:
+                capi.check_image(L.hm_decode_item_to_device_alpha(f.h, iid, C.byref(prm), C.byref(view) if view is not None else None,
+                                                                  C.byref(lit) if lit is not None else None, C.byref(ton) if ton is not None else None,
+                                                                  C.byref(alp), C.byref(dest), C.byref(d)))
+            elif ton is not None:
                 capi.check_image(L.hm_decode_item_to_device_tone(f.h, iid, C.byref(prm), C.byref(view) if view is not None else None, C.byref(lit), C.byref(ton),
                                                                  C.byref(dest), C.byref(d)))
             elif lit is not None:
@@ -251,19 +295,20 @@ def decode_to_tensor(data, item_id=0, out_format="rgb", layout="chw", dtype=None
 
 
 def decode_batch_to_tensor(files, item_id=0, out_format="rgb", layout="chw", dtype=None, scale=None, bias=None, out=None,
-                           host_threads=None, max_in_flight=4, size=None, crops=None, filter="triangle", light=None, tone=None):
+                           host_threads=None, max_in_flight=4, size=None, crops=None, filter="triangle", light=None, tone=None, alpha=None):
     """Decode N equally sized HEIF files through ONE hm_pipeline (the entropy decode of one file runs under the kernels of
     another) into one N x C x H x W ("chw") or N x H x W x C ("hwc") CUDA tensor, each image into its slice.  files: bytes
     objects or paths.  A file of another size than the first (or than `out`) raises ValueError naming it.
     size: (w, h) - files of different sizes are accepted then, each resampled into its slice; crops: one (x, y, w, h) or None per
-    file, the rectangle of that file that is resampled (needs size).  light, tone: as decode_to_tensor, the same steps for every file
-    (tone's src_peak None: each file's own)."""
+    file, the rectangle of that file that is resampled (needs size).  light, tone, alpha: as decode_to_tensor, the same steps for every
+    file (tone's src_peak None: each file's own)."""
     import torch
     L = capi.image_lib()
     fmt, lay = _out_format(out_format), _layout(layout)
     if dtype is None:
         dtype = out.dtype if out is not None else torch.float32
-    code, c = _dtype_code(dtype), _channels(fmt)
+    code = _dtype_code(dtype)
+    alp, c = _alpha_of(alpha, fmt)
     sc, bi = _per_channel(scale, 1.0), _per_channel(bias, 0.0)
     lit = _light_of(light)
     ton = _tone_of(tone, lit)
@@ -327,7 +372,11 @@ def decode_batch_to_tensor(files, item_id=0, out_format="rgb", layout="chw", dty
             for k, data in enumerate(datas):
                 dest = _dest_of(out[k], lay, code, c, sc, bi)
                 while True:
-                    if ton is not None:
+                    if alp is not None:
+                        rc = L.hm_pipeline_submit_to_device_alpha(pipe, data, len(data), ids[k], k, C.byref(views[k]) if views[k] is not None else None,
+                                                                  C.byref(lit) if lit is not None else None, C.byref(ton) if ton is not None else None,
+                                                                  C.byref(alp), C.byref(dest))
+                    elif ton is not None:
                         rc = L.hm_pipeline_submit_to_device_tone(pipe, data, len(data), ids[k], k, C.byref(views[k]) if views[k] is not None else None,
                                                                  C.byref(lit), C.byref(ton), C.byref(dest))
                     elif lit is not None:

@@ -623,7 +623,7 @@ HM_API int hm_pipeline_submit_to_device_planes(hm_pipeline* p, const uint8_t* he
  *                     x < 1: (1.5 * x - 2.5) * x * x + 1;  1 <= x < 2: ((-0.5 * x + 2.5) * x - 4) * x + 2;  otherwise 0;
  *   HM_VIEW_LANCZOS3  x == 0: 1;  x < 3: (sin(p) / p) * (sin(q) / q) with p = pi * x (pi = 3.14159265358979323846), q = p / 3 and the
  *                     C library's sin;  otherwise 0.
- * Per channel (alpha like any other, no premultiplication), in float32 without fused multiply-add: horizontally
+ * Per channel (alpha like any other; premultiplication: "Alpha" below), in float32 without fused multiply-add: horizontally
  * t = 0, t = t + w * (float)v for i increasing, then vertically the same over the t, giving r; integer destinations store
  * min(max((int)(r + 0.5f), 0), peak) with peak 255 / 65535, float destinations r * scale[c] + bias[c] (r not rounded first).
  * The cubic and Lanczos weights are negative in places, so r can lie below 0 and above the peak (overshoot at hard edges): the
@@ -706,7 +706,7 @@ HM_API int hm_view_filter_taps(int n_in, int n_out, int filter, int j, int32_t* 
  *   Colour channels: a source sample v becomes a = lin[min(v, peak)].  Under a view a replaces (float)v in the sums stated under
  *   "Views" (same tap tables, horizontal first, tap 0 first, __fmul_rn / __fadd_rn), giving r; without a view, with the crop alone
  *   or HM_VIEW_NEAREST r = a of the sample that is moved.  The alpha channel is not light: a = (float)v, finished as without a light
- *   step (no premultiplication).
+ *   step (no premultiplication; with an alpha step beside the light step: "Alpha" below).
  *   Gamut: when to_primaries is non-zero and differs from the source's, per output pixel, after the resampling:
  *   R' = fadd(fadd(fmul(m0, R), fmul(m1, G)), fmul(m2, B)), G' and B' with m3 .. m5 and m6 .. m8; m = hm_light_matrix's, derived in
  *   double from the H.273 chromaticities as (to -> XYZ)^-1 (from -> XYZ), then rounded to float32.
@@ -784,8 +784,8 @@ HM_API int hm_light_matrix(int from_primaries, int to_primaries, float m[9]);
  * != 0, a peak or unit that is not finite, not above 0 or above 10000 (0 where it stands for a default), KS < 0 (maxLum < 1 / 3: the
  * knee would lie below black), unit_nits == 0 when the resolved from_transfer is not 16, out_bits other than 0 or 8, out_bits == 8
  * with HM_DEV_U16; HM_ERR_UNSUPPORTED: out_bits == 8 with a four-channel target (bringing a deeper alpha plane to 8 bits under a view
- * is a step of its own) - and everything the light, view and destination checks refuse.  One refusal waits for the decoded image, as
- * the light step's from_* == 0 does: whether the resolved from_transfer is 16 is known once the image reports its profile, so a
+ * is a step of its own; the alpha step's matte has three channels and takes it) - and everything the light, view and destination
+ * checks refuse.  One refusal waits for the decoded image, as the light step's from_* == 0 does: whether the resolved from_transfer is 16 is known once the image reports its profile, so a
  * missing unit_nits is refused behind the decode, before a byte of the destination is written (with an explicit from_transfer, and in
  * hm_tone_to_tensor: before any work is queued). */
 enum { HM_TONE_BT2390 = 1 };
@@ -823,6 +823,71 @@ typedef struct hm_light_levels {
   uint32_t max_display_mastering_luminance, min_display_mastering_luminance;
 } hm_light_levels;
 HM_API int hm_file_item_light_levels(const hm_file* f, uint32_t id, hm_light_levels* out);
+
+/* ------------------------------------------------------------------------- */
+/* Alpha: premultiplied sums under a view, straight or premultiplied results, a matte over a colour */
+/* ------------------------------------------------------------------------- */
+
+/* Everything above carries the alpha channel "like any other, no premultiplication": a view averages the colour of fully transparent
+ * pixels into its sums (dark fringes around a cut-out), and a four-channel result is all a caller can ask for.  An alpha step in the
+ * write of a device destination uses alpha: the sums of a view are taken over colour times alpha, and the result is straight colour,
+ * premultiplied colour, or the picture composited over a background colour - three channels.  It works alone, under a view, and beside
+ * a light step and a tone step, for the four-channel interleaved targets HM_OUT_RGBA and HM_OUT_RRGGBBAA_LE.  A call without the step
+ * writes what it wrote before.
+ *   bits = the target's sample depth, as in the light step (8 for HM_OUT_RGBA, hm_decoded.bit_depth for HM_OUT_RRGGBBAA_LE; at most 12
+ *   when a light step is present);  peak = (1 << bits) - 1;  P = (float)peak.  Every operation is float32 and rounded on its own:
+ *   fmul, fadd, fsub, fdiv are __fmul_rn, __fadd_rn, __fsub_rn, __fdiv_rn - never a fused multiply-add, never a reciprocal.
+ *   Per source pixel, vR, vG, vB, vA its samples:  a = (float)vA;  x_c = (float)v_c for c = R, G, B - with a light step
+ *   x_c = lin[min(v_c, peak)] -;  p_c = fmul(x_c, a).
+ *   Where sums are formed - a view with HM_VIEW_TRIANGLE, HM_VIEW_CUBIC or HM_VIEW_LANCZOS3 and out_w, out_h non-zero -, the sums stated
+ *   under "Views" are taken over p_c and over a (same tap tables, horizontal first, tap 0 first), giving S_c and S_a.  Per output pixel:
+ *     HM_ALPHA_STRAIGHT       r_c = S_a > 0 ? fdiv(S_c, S_a) : 0.0f
+ *     HM_ALPHA_PREMULTIPLIED  r_c = fdiv(S_c, P)
+ *     HM_ALPHA_MATTE          cov = fminf(fmaxf(fdiv(S_a, P), 0.0f), 1.0f);  r_c = fadd(fdiv(S_c, P), fmul(b_c, fsub(1.0f, cov)))
+ *                             with b_c = (float)background[c] - with a light step b_c = lin[background[c]].
+ *   Where no sums are formed - no view, the crop alone, HM_VIEW_NEAREST -, S_c = p_c and S_a = a of the pixel that is moved, with one
+ *   exception: HM_ALPHA_STRAIGHT is then r_c = x_c - no product and no quotient are taken, and the call writes the bytes of the same
+ *   call without the step.
+ *   After r_c: without a light step r_c goes through the finish stated under "Views" - an integer dtype stores
+ *   min(max((int)(r + 0.5f), 0), peak) with peak 255 / 65535, a float dtype r * scale[c] + bias[c].  With a light step r_c takes the
+ *   place of the resampled light: gamut matrix, tone step and the light step's finish follow unchanged.
+ *   The alpha element (HM_ALPHA_STRAIGHT, HM_ALPHA_PREMULTIPLIED) is what it is without the step: the sample where the pixel is moved,
+ *   the finish of S_a where it is summed.
+ *   HM_ALPHA_MATTE writes THREE channels: the destination is judged, sized and written as that of the three-channel sibling target -
+ *   HM_OUT_RGB for HM_OUT_RGBA, HM_OUT_RRGGBB_LE for HM_OUT_RRGGBBAA_LE, and HM_OUT_RGB under tone->out_bits == 8 (the tone step's
+ *   8-bit finish, whose refusal of a four-channel target does not hold for a matte: its result has no alpha plane).
+ *   hm_alpha_dest_format names that target; hm_decoded reports out_format as requested.
+ *   A source without an alpha image is accepted: its alpha is peak everywhere.  Alpha that is premultiplied in the file already (a
+ *   'prem' reference) is not recognised: the file layer does not read that reference, the samples are taken as straight.
+ * Refused with HM_ERR_INVALID_ARG before any work is queued, the destination unwritten: an unknown mode, reserved != 0, a non-zero
+ * background outside HM_ALPHA_MATTE, a non-zero background[3], a background value above peak (8-bit targets: at once; 16-bit targets:
+ * behind the decode, before a byte is written, like the light step's from_* == 0), a three-channel target, a _BE target,
+ * HM_ALPHA_PREMULTIPLIED beside a tone step or beside a light step whose to_transfer is not HM_LIGHT_LINEAR (encoding or tone-mapping
+ * premultiplied light is not a defined result) - and everything the view, light, tone and destination checks refuse, for
+ * HM_ALPHA_MATTE judged against the sibling target.  Planar targets stay refused. */
+enum { HM_ALPHA_STRAIGHT = 1, HM_ALPHA_PREMULTIPLIED = 2, HM_ALPHA_MATTE = 3 };
+typedef struct hm_device_alpha {
+  int32_t  mode;
+  uint16_t background[4];   /* HM_ALPHA_MATTE: R, G, B code values at the target's sample depth; [3] = 0; other modes: all 0 */
+  int32_t  reserved[3];     /* 0 */
+} hm_device_alpha;
+/* Host arithmetic, no device: the target the destination of a request is judged and sized by (hm_device_dest_bytes of it) - out_format,
+ * or the three-channel sibling under HM_ALPHA_MATTE -, or the negative status of a request the step itself refuses (tone may be NULL) */
+HM_API int hm_alpha_dest_format(int out_format, const hm_device_alpha* alpha, const hm_device_tone* tone);
+/* hm_decode_item_to_device_tone with an alpha step; view, light and tone may be NULL (a tone step needs a light step).  Tile
+ * reduction under a view stays off for items with alpha images. */
+HM_API int hm_decode_item_to_device_alpha(const hm_file* f, uint32_t id, const hm_decode_params* params, const hm_device_view* view,
+                                          const hm_device_light* light, const hm_device_tone* tone, const hm_device_alpha* alpha,
+                                          const hm_device_dest* dest, hm_decoded* out);
+/* the pipeline form (no frame-list form: a track's frames carry no alpha image) */
+HM_API int hm_pipeline_submit_to_device_alpha(hm_pipeline* p, const uint8_t* heif, size_t size, uint32_t item_id, uint64_t tag,
+                                              const hm_device_view* view, const hm_device_light* light, const hm_device_tone* tone,
+                                              const hm_device_alpha* alpha, const hm_device_dest* dest);
+/* The step on its own, on interleaved four-channel pixels of `bits` bits that are on the device already (as hm_light_to_tensor /
+ * hm_tone_to_tensor, whose explicit from_*, src_peak and unit_nits rules apply; view, light, tone may be NULL).  Asynchronous on `stream`. */
+HM_API int hm_alpha_to_tensor(int out_format, int bits, int src_w, int src_h, const void* d_src, int src_stride, const hm_device_view* view,
+                              const hm_device_light* light, const hm_device_tone* tone, const hm_device_alpha* alpha, const hm_device_dest* dest,
+                              void* stream);
 
 /* ------------------------------------------------------------------------- */
 /* Planar views: a rectangle of the image, at a size of the caller's choice, into I420 / NV12 / P010 planes */
