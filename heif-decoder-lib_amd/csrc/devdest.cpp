@@ -8,6 +8,7 @@
 #include <cmath>
 #include <cstdio>
 #include <cstring>
+#include <functional>
 #include <mutex>
 #include <new>
 #include <vector>
@@ -18,6 +19,14 @@
 #include "hm_view_batch.h"
 
 extern "C" {
+
+static int dtype_elem(int dtype) { return dtype == HM_DEV_U8 ? 1 : dtype == HM_DEV_F32 ? 4 : 2; }
+
+// w and h in 1 .. 32768; prefix: whose message it is ("device destination: ", "" for the stand-alone entries)
+static int check_image_size(const char* prefix, int w, int h)
+{
+  return w <= 0 || h <= 0 || w > 32768 || h > 32768 ? hm_fail(HM_ERR_INVALID_ARG, "%simage size %d x %d", prefix, w, h) : (int)HM_OK;
+}
 
 int hm_dest_check_static(int out_format, const hm_device_dest* d)
 {
@@ -34,7 +43,7 @@ int hm_dest_check_static(int out_format, const hm_device_dest* d)
   const bool raw = integer && d->layout == HM_DEV_LAYOUT_HWC;
   if (!raw && (out_format == HM_OUT_RRGGBB_BE || out_format == HM_OUT_RRGGBBAA_BE))
     return hm_fail(HM_ERR_INVALID_ARG, "device destination: a big-endian target has no sample values for CHW or float output: ask for the _LE format");
-  const int elem = d->dtype == HM_DEV_U8 ? 1 : d->dtype == HM_DEV_F32 ? 4 : 2;
+  const int elem = dtype_elem(d->dtype);
   if (d->row_pitch < 0 || d->plane_pitch < 0) return hm_fail(HM_ERR_INVALID_ARG, "device destination: negative pitch");
   if ((uintptr_t)d->ptr % (unsigned)elem) return hm_fail(HM_ERR_INVALID_ARG, "device destination: ptr is not a multiple of the element size %d", elem);
   if (d->row_pitch % elem) return hm_fail(HM_ERR_INVALID_ARG, "device destination: row_pitch %lld is not a multiple of the element size %d", (long long)d->row_pitch, elem);
@@ -44,15 +53,14 @@ int hm_dest_check_static(int out_format, const hm_device_dest* d)
 
 int hm_dest_resolve(int out_format, int w, int h, const hm_device_dest* d, hm_dest_plan* p)
 {
-  const int rc = hm_dest_check_static(out_format, d);
-  if (rc) return rc;
-  if (w <= 0 || h <= 0 || w > 32768 || h > 32768) return hm_fail(HM_ERR_INVALID_ARG, "device destination: image size %d x %d", w, h);
+  int rc = hm_dest_check_static(out_format, d);
+  if (rc || (rc = check_image_size("device destination: ", w, h))) return rc;
   std::memset(p, 0, sizeof(*p));
   const int obpp = hm_out_bytes_per_pixel(out_format);
   p->layout = d->layout; p->dtype = d->dtype;
   p->sample_bytes = obpp >= 6 ? 2 : 1;
   p->channels = obpp / p->sample_bytes;
-  p->elem = d->dtype == HM_DEV_U8 ? 1 : d->dtype == HM_DEV_F32 ? 4 : 2;
+  p->elem = dtype_elem(d->dtype);
   p->raw = d->layout == HM_DEV_LAYOUT_HWC && (d->dtype == HM_DEV_U8 || d->dtype == HM_DEV_U16);
   const bool chw = d->layout == HM_DEV_LAYOUT_CHW;
   p->tight_row = (int64_t)w * p->elem * (chw ? 1 : p->channels);
@@ -106,21 +114,6 @@ int64_t hm_device_dest_bytes(int out_format, int width, int height, const hm_dev
   return rc ? rc : p.bytes;
 }
 
-int hm_to_tensor(int out_format, int width, int height, const void* d_src, int src_stride, const hm_device_dest* dest, void* stream)
-{
-  if (!d_src || !dest) return hm_fail(HM_ERR_INVALID_ARG, "null argument");
-  hm_dest_plan p;
-  int rc = hm_dest_resolve(out_format, width, height, dest, &p);
-  if (!rc) rc = hm_dest_check_len(dest, &p);
-  if (rc) return rc;
-  if (src_stride < width * hm_out_bytes_per_pixel(out_format)) return hm_fail(HM_ERR_INVALID_ARG, "src_stride %d below the bytes of a row", src_stride);
-  if (p.sample_bytes == 2 && (((uintptr_t)d_src | (unsigned)src_stride) & 1)) return hm_fail(HM_ERR_INVALID_ARG, "16-bit samples at an odd address or stride");
-  int n_dev = 0;
-  if (hipGetDeviceCount(&n_dev) != hipSuccess || n_dev == 0) { (void)hipGetLastError(); return hm_fail(HM_ERR_NO_DEVICE, "no HIP device available"); }
-  if ((rc = hm_dest_check_pointer(dest))) return rc;
-  return hm_dest_write(dest, out_format, width, height, 0, height, d_src, src_stride, (hipStream_t)stream);
-}
-
 int hm_dest_write(const hm_device_dest* d, int out_format, int w, int h, int y0, int rows, const void* src, int src_stride, hipStream_t s)
 {
   hm_dest_plan p;
@@ -138,8 +131,6 @@ int hm_dest_write(const hm_device_dest* d, int out_format, int w, int h, int y0,
 
 // ---- planar YCbCr (hm_device_planes) --------------------------------------------------------------------------------------------
 
-static int planes_elem(int dtype) { return dtype == HM_DEV_U8 ? 1 : dtype == HM_DEV_F32 ? 4 : 2; }
-
 int hm_planes_check_static(const hm_device_planes* d)
 {
   if (!d) return hm_fail(HM_ERR_INVALID_ARG, "null device planes");
@@ -150,7 +141,7 @@ int hm_planes_check_static(const hm_device_planes* d)
   if (d->msb_aligned && d->dtype != HM_DEV_U16) return hm_fail(HM_ERR_INVALID_ARG, "device planes: msb_aligned with dtype %d (HM_DEV_U16 only)", d->dtype);
   if (d->layout == HM_DEV_PLANES_SEMI && (d->plane[2].ptr || d->plane[2].len || d->plane[2].row_pitch))
     return hm_fail(HM_ERR_INVALID_ARG, "device planes: plane[2] must be all zero with HM_DEV_PLANES_SEMI (Cb and Cr share plane[1])");
-  const int elem = planes_elem(d->dtype);
+  const int elem = dtype_elem(d->dtype);
   for (int c = 0; c < 4; c++) {
     const hm_device_plane& pl = d->plane[c];
     if (pl.row_pitch < 0) return hm_fail(HM_ERR_INVALID_ARG, "device planes: plane[%d].row_pitch is negative", c);
@@ -162,14 +153,14 @@ int hm_planes_check_static(const hm_device_planes* d)
 
 int hm_planes_resolve(int chroma, int bits, int w, int h, int alpha_bits, const hm_device_planes* d, hm_planes_plan* p)
 {
-  const int rc = hm_planes_check_static(d);
+  int rc = hm_planes_check_static(d);
   if (rc) return rc;
   if (chroma < HM_CHROMA_MONO || chroma > HM_CHROMA_444) return hm_fail(HM_ERR_INVALID_ARG, "device planes: chroma format %d", chroma);
   if (bits < 8 || bits > 16) return hm_fail(HM_ERR_INVALID_ARG, "device planes: bit depth %d", bits);
   if (alpha_bits > 0 && (alpha_bits < 8 || alpha_bits > 16)) return hm_fail(HM_ERR_INVALID_ARG, "device planes: alpha bit depth %d", alpha_bits);
-  if (w <= 0 || h <= 0 || w > 32768 || h > 32768) return hm_fail(HM_ERR_INVALID_ARG, "device planes: image size %d x %d", w, h);
+  if ((rc = check_image_size("device planes: ", w, h))) return rc;
   std::memset(p, 0, sizeof(*p));
-  p->layout = d->layout; p->dtype = d->dtype; p->elem = planes_elem(d->dtype);
+  p->layout = d->layout; p->dtype = d->dtype; p->elem = dtype_elem(d->dtype);
   p->chroma = chroma; p->bits = bits;
   if (d->dtype == HM_DEV_U8 && bits != 8) return hm_fail(HM_ERR_INVALID_ARG, "device planes: dtype HM_DEV_U8 does not hold the %d-bit samples of the result", bits);
   if (d->dtype == HM_DEV_U16 && bits == 8) return hm_fail(HM_ERR_INVALID_ARG, "device planes: dtype HM_DEV_U16 with the 8-bit samples of the result (HM_DEV_U8 holds them)");
@@ -471,33 +462,6 @@ static hm_resample_args resample_args_of(const hm_view_plan* vp, int sample_byte
 // ... and the floats of that intermediate for one frame
 static size_t resample_tmp_floats(const hm_resample_args& a, const hm_dest_plan& p) { return (size_t)a.tmp_plane * (p.layout == HM_DEV_LAYOUT_CHW ? p.channels : 1); }
 
-int hm_view_write(const hm_device_dest* d, int out_format, const hm_view_plan* vp, const void* src, int src_stride, hipStream_t s, hm_view_scratch* sc)
-{
-  hm_dest_plan p;
-  int rc = hm_dest_resolve(out_format, vp->ow, vp->oh, d, &p);
-  if (!rc) rc = hm_dest_check_len(d, &p);
-  if (rc) return rc;
-  const int obpp = p.channels * p.sample_bytes;
-  const uint8_t* origin = (const uint8_t*)src + (size_t)vp->y * src_stride + (size_t)vp->x * obpp;
-  if (vp->crop_only) // the rectangle's bytes: the 2-D copy or k_to_tensor on the offset source
-    return hm_dest_write(d, out_format, vp->w, vp->h, 0, vp->h, origin, src_stride, s);
-  if (vp->filter == HM_VIEW_NEAREST)
-    return hm_launch_view_nearest(&p, origin, src_stride, vp->w, vp->h, vp->ow, vp->oh, d->ptr, d->scale, d->bias, s);
-  size_t words_x = 0, words_y = 0;
-  int tx = 0, ty = 0;
-  bool staged = false;
-  if ((rc = view_tables(vp, 0, sc, &words_x, &words_y, &tx, &ty, &staged))) return rc;
-  const size_t bytes = (words_x + words_y) * 4;
-  int32_t* host = (int32_t*)sc->pinned;
-  if (!(sc->dev[0] = hm_pool_device_alloc(bytes))) return HM_ERR_NO_DEVICE;
-  hm_resample_args a = resample_args_of(vp, p.sample_bytes, origin, src_stride, sc->dev[0], words_x, tx, ty, p);
-  if (!(sc->dev[1] = hm_pool_device_alloc(resample_tmp_floats(a, p) * sizeof(float)))) return HM_ERR_NO_DEVICE;
-  if ((rc = hm_check_hip(hipMemcpyAsync(sc->dev[0], host, bytes, hipMemcpyHostToDevice, s), "upload of the tap tables"))) return rc;
-  a.tmp = (float*)sc->dev[1];
-  a.staged = staged ? 1 : 0; a.stage_px = hm_knob(HM_KNOB_VIEW_STAGE_PX);
-  return hm_launch_resample(&p, &a, d->ptr, d->scale, d->bias, s);
-}
-
 // one group of a batched view write: frames idx[0 .. m) of `it` share the plan p, the view and everything else of the key
 static int view_write_group(const hm_view_item* it, const int* idx, int m, const hm_dest_plan& p, hipStream_t s, hm_view_scratch* sc)
 {
@@ -561,7 +525,10 @@ int hm_view_write_batch(int out_format, const hm_view_item* it, int n, hipStream
   for (int k = 0; k < n; k++) {
     const hm_view_plan& vp = it[k].vp;
     if (!batched || vp.crop_only || vp.filter == HM_VIEW_NEAREST) { // what exists, frame by frame
-      const int rc = hm_view_write(it[k].dest, out_format, &vp, it[k].src, it[k].src_stride, s, &sc[k]);
+      hm_out_plan one; // the view alone
+      std::memset(&one, 0, sizeof(one));
+      one.out_format = one.dest_format = out_format; one.has_view = 1; one.vp = vp; one.dp = plans[k];
+      const int rc = hm_out_write(it[k].dest, &one, it[k].src, it[k].src_stride, s, &sc[k]);
       if (rc) return rc;
       continue;
     }
@@ -582,7 +549,7 @@ int hm_view_write_batch(int out_format, const hm_view_item* it, int n, hipStream
   return HM_OK;
 }
 
-// hm_resample_to_tensor returns before its kernels have run: the blocks they work on go back to the pools once the stream has
+// The stand-alone entries return before their kernels have run: the blocks they work on go back to the pools once the stream has
 // passed them.  The stream's host function only hands them to this list (no HIP call there); the next call releases them.
 namespace {
 std::mutex g_done_mu;
@@ -599,36 +566,23 @@ void release_done()
   { std::lock_guard<std::mutex> g(g_done_mu); v.swap(g_done); }
   for (hm_view_scratch& sc : v) hm_view_scratch_free(&sc);
 }
-} // namespace
-
-int hm_resample_to_tensor(int out_format, int src_w, int src_h, const void* d_src, int src_stride, const hm_device_view* view, const hm_device_dest* dest, void* stream)
+// `write` on a scratch entry of its own, which follows the stream to release_done
+int with_scratch(hipStream_t s, const std::function<int(hm_view_scratch*)>& write)
 {
-  if (!d_src || !dest || !view) return hm_fail(HM_ERR_INVALID_ARG, "null argument");
-  int rc = hm_dest_check_static(out_format, dest);
-  if (rc) return rc;
-  if (src_w <= 0 || src_h <= 0 || src_w > 32768 || src_h > 32768) return hm_fail(HM_ERR_INVALID_ARG, "image size %d x %d", src_w, src_h);
-  hm_view_plan vp;
-  if ((rc = hm_view_resolve(out_format, src_w, src_h, view, &vp))) return rc;
-  hm_dest_plan p;
-  if ((rc = hm_dest_resolve(out_format, vp.ow, vp.oh, dest, &p)) || (rc = hm_dest_check_len(dest, &p))) return rc;
-  if (src_stride < src_w * hm_out_bytes_per_pixel(out_format)) return hm_fail(HM_ERR_INVALID_ARG, "src_stride %d below the bytes of a row", src_stride);
-  if (p.sample_bytes == 2 && (((uintptr_t)d_src | (unsigned)src_stride) & 1)) return hm_fail(HM_ERR_INVALID_ARG, "16-bit samples at an odd address or stride");
-  int n_dev = 0;
-  if (hipGetDeviceCount(&n_dev) != hipSuccess || n_dev == 0) { (void)hipGetLastError(); return hm_fail(HM_ERR_NO_DEVICE, "no HIP device available"); }
-  if ((rc = hm_dest_check_pointer(dest))) return rc;
   release_done();
   hm_view_scratch* sc = new (std::nothrow) hm_view_scratch();
   if (!sc) return hm_fail(HM_ERR_NOMEM, "out of memory");
-  rc = hm_view_write(dest, out_format, &vp, d_src, src_stride, (hipStream_t)stream, sc);
+  const int rc = write(sc);
   if (!sc->dev[0] && !sc->dev[1] && !sc->pinned) { delete sc; return rc; }
-  if (hipLaunchHostFunc((hipStream_t)stream, scratch_done, sc) != hipSuccess) { // (never on a healthy runtime: wait, then release here)
+  if (hipLaunchHostFunc(s, scratch_done, sc) != hipSuccess) { // (never on a healthy runtime: wait, then release here)
     (void)hipGetLastError();
-    hipStreamSynchronize((hipStream_t)stream);
+    hipStreamSynchronize(s);
     hm_view_scratch_free(sc);
     delete sc;
   }
   return rc;
 }
+} // namespace
 
 // ---- the light step (hm_device_light) -------------------------------------------------------------------------------------------
 
@@ -738,7 +692,7 @@ int hm_light_matrix(int from_primaries, int to_primaries, float m[9])
   return HM_OK;
 }
 
-// dest_format: the target the destination is judged by (hm_tone_dest_format; out_format without a tone step)
+// dest_format: the target the destination is judged by (hm_out_dest_format)
 static int light_check(int out_format, int dest_format, const hm_device_dest* d, const hm_device_light* l, int explicit_from)
 {
   if (!l) return hm_fail(HM_ERR_INVALID_ARG, "null light step");
@@ -759,13 +713,8 @@ static int light_check(int out_format, int dest_format, const hm_device_dest* d,
   return HM_OK;
 }
 
-int hm_light_check_static(int out_format, const hm_device_dest* d, const hm_device_light* l, int explicit_from)
-{
-  return light_check(out_format, out_format, d, l, explicit_from);
-}
-
 // the plan of a light step whose static checks have passed (light_check)
-static int light_plan_of(int out_format, int dest_format, int bits, int img_transfer, int img_primaries, const hm_device_light* l, hm_light_plan* lp)
+static int light_plan_of(int out_format, int bits, int img_transfer, int img_primaries, const hm_device_light* l, hm_light_plan* lp)
 {
   std::memset(lp, 0, sizeof(*lp));
   lp->from_transfer = l->from_transfer ? l->from_transfer : img_transfer;
@@ -778,17 +727,11 @@ static int light_plan_of(int out_format, int dest_format, int bits, int img_tran
   if (sb == 1) bits = 8;
   if (bits < 8 || bits > HM_LIGHT_MAX_BITS) return hm_fail(HM_ERR_UNSUPPORTED, "light: samples of %d bits (8 .. %d are supported)", bits, (int)HM_LIGHT_MAX_BITS);
   lp->bits = bits;
-  lp->enc_bits = bits; lp->dest_format = dest_format;
+  lp->enc_bits = bits;
   lp->encode = lp->to_transfer != HM_LIGHT_LINEAR;
   lp->matrix = lp->to_primaries != lp->from_primaries;
   lp->gain = l->gain;
   return hm_light_matrix(lp->from_primaries, lp->to_primaries, lp->m);
-}
-
-int hm_light_resolve(int out_format, int bits, int img_transfer, int img_primaries, const hm_device_dest* d, const hm_device_light* l, hm_light_plan* lp)
-{
-  const int rc = light_check(out_format, out_format, d, l, 0);
-  return rc ? rc : light_plan_of(out_format, out_format, bits, img_transfer, img_primaries, l, lp);
 }
 
 // ---- the tone step (hm_device_tone) ----------------------------------------------------------------------------------------------
@@ -851,7 +794,8 @@ int tone_check(const hm_device_tone* t, bool defaults)
 
 } // namespace
 
-int hm_tone_dest_format(int out_format, const hm_device_tone* tone)
+// the target the destination is judged by under a tone step (may be NULL): the 8-bit finish writes the 8-bit sibling
+static int tone_dest_format(int out_format, const hm_device_tone* tone)
 {
   if (tone && tone->out_bits == 8 && (out_format == HM_OUT_RRGGBB_LE || out_format == HM_OUT_RRGGBB_BE)) return HM_OUT_RGB;
   return out_format;
@@ -864,38 +808,9 @@ float hm_tone_peak_of(int has_clli, unsigned max_cll, int has_mdcv, unsigned mdc
   return 1000.0f;
 }
 
-int hm_tone_check_static(int out_format, const hm_device_dest* d, const hm_device_light* l, const hm_device_tone* tone, int explicit_from)
+// the tone step into the plan of its light step (light_plan_of); the static checks have passed
+static int tone_plan_of(const hm_device_tone* tone, hm_light_plan* lp)
 {
-  if (!tone) return hm_light_check_static(out_format, d, l, explicit_from);
-  if (!l) return hm_fail(HM_ERR_INVALID_ARG, "tone: null light step");
-  if (!d) return hm_fail(HM_ERR_INVALID_ARG, "null device destination");
-  int rc = tone_check(tone, !explicit_from);
-  if (rc) return rc;
-  if (tone->out_bits == 8) {
-    if (d->dtype == HM_DEV_U16) return hm_fail(HM_ERR_INVALID_ARG, "tone: out_bits 8 with HM_DEV_U16 (HM_DEV_U8 holds the codes)");
-    const int obpp = hm_out_bytes_per_pixel(out_format);
-    if (obpp == 4 || obpp == 8) return hm_fail(HM_ERR_UNSUPPORTED, "tone: out_bits 8 with the four-channel output format %d is not supported", out_format);
-  }
-  return light_check(out_format, hm_tone_dest_format(out_format, tone), d, l, explicit_from);
-}
-
-static int tone_plan_of(int out_format, int dest_format, int bits, int img_transfer, int img_primaries, const hm_device_light* l, const hm_device_tone* tone,
-                        hm_light_plan* lp);
-
-int hm_tone_resolve(int out_format, int bits, int img_transfer, int img_primaries, const hm_device_dest* d, const hm_device_light* l, const hm_device_tone* tone,
-                    hm_light_plan* lp)
-{
-  if (!tone) return hm_light_resolve(out_format, bits, img_transfer, img_primaries, d, l, lp);
-  const int rc = hm_tone_check_static(out_format, d, l, tone, 0);
-  return rc ? rc : tone_plan_of(out_format, hm_tone_dest_format(out_format, tone), bits, img_transfer, img_primaries, l, tone, lp);
-}
-
-// the plan of a light step with a tone step whose static checks have passed
-static int tone_plan_of(int out_format, int dest_format, int bits, int img_transfer, int img_primaries, const hm_device_light* l, const hm_device_tone* tone,
-                        hm_light_plan* lp)
-{
-  const int rc = light_plan_of(out_format, dest_format, bits, img_transfer, img_primaries, l, lp);
-  if (rc) return rc;
   if (tone->unit_nits == 0.0f && lp->from_transfer != 16)
     return hm_fail(HM_ERR_INVALID_ARG, "tone: unit_nits must be given for transfer characteristics %d (only PQ says what 1.0 stands for)", lp->from_transfer);
   if (tone->src_peak == 0.0f) return hm_fail(HM_ERR_INVALID_ARG, "tone: src_peak must be given: the pixels carry no light levels"); // (else the knee has been judged)
@@ -921,8 +836,8 @@ int hm_tone_table(const hm_device_tone* tone, float gain, int which, float* out)
 
 namespace {
 
-// the tables a light plan's kernels read, one behind the other: lin, then enc, then thr and sg (hm_light_write, hm_alpha_write: there
-// the plan may be NULL - no light step, no tables)
+// the tables a light plan's kernels read, one behind the other: lin, then enc, then thr and sg (hm_out_write; the plan may be NULL -
+// no light step, no tables)
 struct LightTables {
   const hm_light_plan* lp;
   size_t n, ne, nt;
@@ -953,100 +868,6 @@ struct LightTables {
 
 } // namespace
 
-int hm_light_write(const hm_device_dest* d, int out_format, int w, int h, const hm_view_plan* vp, const hm_light_plan* lp, const void* src, int src_stride,
-                   hipStream_t s, hm_view_scratch* sc)
-{
-  if (!sc || sc->pinned || sc->dev[0] || sc->dev[1]) return hm_fail(HM_ERR_INTERNAL, "light: no free scratch for the tables");
-  const int ow = vp ? vp->ow : w, oh = vp ? vp->oh : h;
-  hm_dest_plan p; // (of the target the destination is written as: under the 8-bit finish its samples are bytes, the source's are not)
-  int rc = hm_dest_resolve(lp->dest_format, ow, oh, d, &p);
-  if (!rc) rc = hm_dest_check_len(d, &p);
-  if (rc) return rc;
-  const int obpp = hm_out_bytes_per_pixel(out_format), src_bytes = obpp >= 6 ? 2 : 1;
-  const int cx = vp ? vp->x : 0, cy = vp ? vp->y : 0, cw = vp ? vp->w : w, ch = vp ? vp->h : h;
-  const uint8_t* origin = (const uint8_t*)src + (size_t)cy * src_stride + (size_t)cx * obpp;
-  const LightTables T(lp);
-  const size_t table_bytes = T.bytes();
-  const bool resampled = vp && !vp->crop_only && vp->filter != HM_VIEW_NEAREST;
-  hm_light_args la = T.args(src_bytes);
-  auto fill = [&](float* host) { T.fill(host); };
-  auto point = [&](const float* dev) { T.point(&la, dev); };
-  if (!resampled) {
-    float* host = (float*)hm_pool_pinned_alloc(table_bytes);
-    if (!host) return hm_fail(HM_ERR_NOMEM, "out of memory");
-    sc->pinned = host;
-    fill(host);
-    if (!(sc->dev[0] = hm_pool_device_alloc(table_bytes))) return HM_ERR_NO_DEVICE;
-    if ((rc = hm_check_hip(hipMemcpyAsync(sc->dev[0], host, table_bytes, hipMemcpyHostToDevice, s), "upload of the light tables"))) return rc;
-    point((const float*)sc->dev[0]);
-    if (vp && !vp->crop_only) return hm_launch_light_nearest(&p, &la, origin, src_stride, cw, ch, ow, oh, d->ptr, d->scale, d->bias, s);
-    return hm_launch_light_tensor(&p, &la, origin, src_stride, cw, ch, d->ptr, d->scale, d->bias, s);
-  }
-  // ONE pinned block and one upload: the tap tables of both axes, then the light tables
-  size_t words_x = 0, words_y = 0;
-  int tx = 0, ty = 0;
-  bool staged = false;
-  if ((rc = view_tables(vp, table_bytes, sc, &words_x, &words_y, &tx, &ty, &staged))) return rc;
-  const size_t tap_bytes = (words_x + words_y) * 4, bytes = tap_bytes + table_bytes;
-  int32_t* host = (int32_t*)sc->pinned;
-  fill(reinterpret_cast<float*>(host + words_x + words_y));
-  if (!(sc->dev[0] = hm_pool_device_alloc(bytes))) return HM_ERR_NO_DEVICE;
-  hm_resample_args a = resample_args_of(vp, src_bytes, origin, src_stride, sc->dev[0], words_x, tx, ty, p);
-  if (!(sc->dev[1] = hm_pool_device_alloc(resample_tmp_floats(a, p) * sizeof(float)))) return HM_ERR_NO_DEVICE;
-  if ((rc = hm_check_hip(hipMemcpyAsync(sc->dev[0], host, bytes, hipMemcpyHostToDevice, s), "upload of the tap and light tables"))) return rc;
-  a.tmp = (float*)sc->dev[1];
-  point(reinterpret_cast<const float*>(sc->dev[0]) + words_x + words_y);
-  return hm_launch_light_resample(&p, &la, &a, d->ptr, d->scale, d->bias, s);
-}
-
-// hm_light_to_tensor, and with a tone step hm_tone_to_tensor
-static int light_to_tensor(int out_format, int bits, int src_w, int src_h, const void* d_src, int src_stride, const hm_device_view* view, const hm_device_light* light,
-                           const hm_device_tone* tone, const hm_device_dest* dest, void* stream)
-{
-  int rc = hm_tone_check_static(out_format, dest, light, tone, 1);
-  if (rc) return rc;
-  if (src_w <= 0 || src_h <= 0 || src_w > 32768 || src_h > 32768) return hm_fail(HM_ERR_INVALID_ARG, "image size %d x %d", src_w, src_h);
-  hm_view_plan vp;
-  std::memset(&vp, 0, sizeof(vp));
-  vp.ow = src_w; vp.oh = src_h;
-  if (view && (rc = hm_view_resolve(out_format, src_w, src_h, view, &vp))) return rc;
-  hm_light_plan lp;
-  if ((rc = hm_tone_resolve(out_format, bits, light->from_transfer, light->from_primaries, dest, light, tone, &lp))) return rc;
-  hm_dest_plan p;
-  if ((rc = hm_dest_resolve(lp.dest_format, vp.ow, vp.oh, dest, &p)) || (rc = hm_dest_check_len(dest, &p))) return rc;
-  if (src_stride < src_w * hm_out_bytes_per_pixel(out_format)) return hm_fail(HM_ERR_INVALID_ARG, "src_stride %d below the bytes of a row", src_stride);
-  if (hm_out_bytes_per_pixel(out_format) >= 6 && (((uintptr_t)d_src | (unsigned)src_stride) & 1)) return hm_fail(HM_ERR_INVALID_ARG, "16-bit samples at an odd address or stride");
-  int n_dev = 0;
-  if (hipGetDeviceCount(&n_dev) != hipSuccess || n_dev == 0) { (void)hipGetLastError(); return hm_fail(HM_ERR_NO_DEVICE, "no HIP device available"); }
-  if ((rc = hm_dest_check_pointer(dest))) return rc;
-  release_done();
-  hm_view_scratch* sc = new (std::nothrow) hm_view_scratch();
-  if (!sc) return hm_fail(HM_ERR_NOMEM, "out of memory");
-  rc = hm_light_write(dest, out_format, src_w, src_h, view ? &vp : nullptr, &lp, d_src, src_stride, (hipStream_t)stream, sc);
-  if (!sc->dev[0] && !sc->dev[1] && !sc->pinned) { delete sc; return rc; }
-  if (hipLaunchHostFunc((hipStream_t)stream, scratch_done, sc) != hipSuccess) { // (never on a healthy runtime: wait, then release here)
-    (void)hipGetLastError();
-    hipStreamSynchronize((hipStream_t)stream);
-    hm_view_scratch_free(sc);
-    delete sc;
-  }
-  return rc;
-}
-
-int hm_light_to_tensor(int out_format, int bits, int src_w, int src_h, const void* d_src, int src_stride, const hm_device_view* view, const hm_device_light* light,
-                       const hm_device_dest* dest, void* stream)
-{
-  if (!d_src || !dest || !light) return hm_fail(HM_ERR_INVALID_ARG, "null argument");
-  return light_to_tensor(out_format, bits, src_w, src_h, d_src, src_stride, view, light, nullptr, dest, stream);
-}
-
-int hm_tone_to_tensor(int out_format, int bits, int src_w, int src_h, const void* d_src, int src_stride, const hm_device_view* view, const hm_device_light* light,
-                      const hm_device_tone* tone, const hm_device_dest* dest, void* stream)
-{
-  if (!d_src || !dest || !tone) return hm_fail(HM_ERR_INVALID_ARG, "null argument");
-  return light_to_tensor(out_format, bits, src_w, src_h, d_src, src_stride, view, light, tone, dest, stream);
-}
-
 // ---- the alpha step (hm_device_alpha) --------------------------------------------------------------------------------------------
 
 int hm_alpha_dest_format(int out_format, const hm_device_alpha* a, const hm_device_tone* tone)
@@ -1072,141 +893,190 @@ int hm_alpha_dest_format(int out_format, const hm_device_alpha* a, const hm_devi
   return out_format == HM_OUT_RGBA ? HM_OUT_RGB : HM_OUT_RRGGBB_LE;
 }
 
-int hm_alpha_check_static(int out_format, const hm_device_dest* d, const hm_device_light* l, const hm_device_tone* tone, const hm_device_alpha* a, int explicit_from)
+// ---- the device write: one request (hm_out_steps), one plan (hm_out_plan), one writer --------------------------------------------
+
+int hm_out_dest_format(int out_format, const hm_out_steps* st)
 {
-  const int dest_format = hm_alpha_dest_format(out_format, a, tone);
+  return st->alpha ? hm_alpha_dest_format(out_format, st->alpha, st->tone) : tone_dest_format(out_format, st->tone);
+}
+
+int hm_out_check_static(int out_format, const hm_device_dest* d, const hm_out_steps* st, int explicit_from)
+{
+  const hm_device_light* l = st->light;
+  const hm_device_tone* tone = st->tone;
+  const hm_device_alpha* a = st->alpha;
+  const int dest_format = hm_out_dest_format(out_format, st); // (the alpha step's own refusals)
   if (dest_format < 0) return dest_format;
   if (!d) return hm_fail(HM_ERR_INVALID_ARG, "null device destination");
   if (tone && !l) return hm_fail(HM_ERR_INVALID_ARG, "tone: null light step");
-  if (a->mode == HM_ALPHA_PREMULTIPLIED && l && l->to_transfer != HM_LIGHT_LINEAR)
+  if (a && a->mode == HM_ALPHA_PREMULTIPLIED && l && l->to_transfer != HM_LIGHT_LINEAR)
     return hm_fail(HM_ERR_INVALID_ARG, "alpha: HM_ALPHA_PREMULTIPLIED beside a light step that re-encodes (transfer %d; encoded premultiplied light is not a defined result)", l->to_transfer);
-  if (!l) return hm_dest_check_static(dest_format, d);
   if (tone) {
     const int rc = tone_check(tone, !explicit_from);
     if (rc) return rc;
-    if (tone->out_bits == 8 && d->dtype == HM_DEV_U16) return hm_fail(HM_ERR_INVALID_ARG, "tone: out_bits 8 with HM_DEV_U16 (HM_DEV_U8 holds the codes)");
-    if (tone->out_bits == 8 && a->mode != HM_ALPHA_MATTE) // (a matte has three channels: the 8-bit finish takes it)
-      return hm_fail(HM_ERR_UNSUPPORTED, "tone: out_bits 8 with the four-channel output format %d is not supported", out_format);
+    if (tone->out_bits == 8) {
+      if (d->dtype == HM_DEV_U16) return hm_fail(HM_ERR_INVALID_ARG, "tone: out_bits 8 with HM_DEV_U16 (HM_DEV_U8 holds the codes)");
+      const int obpp = hm_out_bytes_per_pixel(out_format);
+      if (a ? a->mode != HM_ALPHA_MATTE : obpp == 4 || obpp == 8) // (a matte has three channels: the 8-bit finish takes it)
+        return hm_fail(HM_ERR_UNSUPPORTED, "tone: out_bits 8 with the four-channel output format %d is not supported", out_format);
+    }
   }
-  return light_check(out_format, dest_format, d, l, explicit_from);
+  return l ? light_check(out_format, dest_format, d, l, explicit_from) : hm_dest_check_static(dest_format, d);
 }
 
-int hm_alpha_resolve(int out_format, int bits, int img_transfer, int img_primaries, const hm_device_dest* d, const hm_device_light* l, const hm_device_tone* tone,
-                     const hm_device_alpha* a, hm_light_plan* lp, hm_alpha_plan* ap)
+// the part of hm_out_resolve that needs the image's profile and depth
+static int out_resolve_profile(int out_format, const hm_out_image* img, const hm_device_dest* d, const hm_out_steps* st, hm_out_plan* p)
 {
-  int rc = hm_alpha_check_static(out_format, d, l, tone, a, 0);
+  if (!st->light && !st->alpha) return HM_OK;
+  int rc = hm_out_check_static(out_format, d, st, 0);
   if (rc) return rc;
-  std::memset(ap, 0, sizeof(*ap));
-  ap->mode = a->mode;
-  ap->dest_format = hm_alpha_dest_format(out_format, a, tone);
-  if (out_format == HM_OUT_RGBA) bits = 8;
-  if (bits < 8 || bits > 16 || (bits == 8) != (out_format == HM_OUT_RGBA)) return hm_fail(HM_ERR_UNSUPPORTED, "alpha: samples of %d bits in output format %d", bits, out_format);
-  ap->bits = bits;
-  for (int c = 0; c < 3; c++) {
-    if (a->background[c] > (1 << bits) - 1) return hm_fail(HM_ERR_INVALID_ARG, "alpha: background[%d] = %d above the peak %d", c, (int)a->background[c], (1 << bits) - 1);
-    ap->background[c] = a->background[c];
+  int bits = img->bits;
+  if (const hm_device_alpha* a = st->alpha) {
+    p->ap.mode = a->mode;
+    if (out_format == HM_OUT_RGBA) bits = 8;
+    if (bits < 8 || bits > 16 || (bits == 8) != (out_format == HM_OUT_RGBA)) return hm_fail(HM_ERR_UNSUPPORTED, "alpha: samples of %d bits in output format %d", bits, out_format);
+    p->ap.bits = bits;
+    for (int c = 0; c < 3; c++) {
+      if (a->background[c] > (1 << bits) - 1) return hm_fail(HM_ERR_INVALID_ARG, "alpha: background[%d] = %d above the peak %d", c, (int)a->background[c], (1 << bits) - 1);
+      p->ap.background[c] = a->background[c];
+    }
   }
-  if (!l) return HM_OK;
-  if (tone) return tone_plan_of(out_format, ap->dest_format, bits, img_transfer, img_primaries, l, tone, lp);
-  return light_plan_of(out_format, ap->dest_format, bits, img_transfer, img_primaries, l, lp);
+  if (!st->light) return HM_OK;
+  if ((rc = light_plan_of(out_format, bits, img->transfer, img->primaries, st->light, &p->lp))) return rc;
+  return st->tone ? tone_plan_of(st->tone, &p->lp) : (int)HM_OK;
 }
 
-int hm_alpha_write(const hm_device_dest* d, int out_format, int w, int h, const hm_view_plan* vp, const hm_light_plan* lp, const hm_alpha_plan* ap, const void* src,
-                   int src_stride, hipStream_t s, hm_view_scratch* sc)
+int hm_out_resolve(int out_format, const hm_out_image* img, int know_profile, const hm_device_dest* d, const hm_out_steps* st, hm_out_plan* p)
 {
-  if (!sc || sc->pinned || sc->dev[0] || sc->dev[1]) return hm_fail(HM_ERR_INTERNAL, "alpha: no free scratch for the tables");
-  const bool summed = vp && !vp->crop_only && vp->filter != HM_VIEW_NEAREST;
-  if (ap->mode == HM_ALPHA_STRAIGHT && !summed) { // r_c = x_c: the write without the step
-    if (lp) return hm_light_write(d, out_format, w, h, vp, lp, src, src_stride, s, sc);
-    if (vp) return hm_view_write(d, out_format, vp, src, src_stride, s, sc);
-    return hm_dest_write(d, out_format, w, h, 0, h, src, src_stride, s);
-  }
-  const int ow = vp ? vp->ow : w, oh = vp ? vp->oh : h;
-  hm_dest_plan p; // (of the target the destination is written as: three channels under HM_ALPHA_MATTE)
-  int rc = hm_dest_resolve(ap->dest_format, ow, oh, d, &p);
-  if (!rc) rc = hm_dest_check_len(d, &p);
-  if (rc) return rc;
-  const int obpp = hm_out_bytes_per_pixel(out_format), src_bytes = obpp / 4;
-  if (obpp != 4 && obpp != 8) return hm_fail(HM_ERR_INTERNAL, "alpha: output format %d has no four channels", out_format);
-  const int cx = vp ? vp->x : 0, cy = vp ? vp->y : 0, cw = vp ? vp->w : w, ch = vp ? vp->h : h;
-  const uint8_t* origin = (const uint8_t*)src + (size_t)cy * src_stride + (size_t)cx * obpp;
+  int rc;
+  std::memset(p, 0, sizeof(*p));
+  p->out_format = out_format; p->w = img->w; p->h = img->h;
+  p->has_view = st->view != nullptr; p->has_light = st->light != nullptr; p->has_alpha = st->alpha != nullptr;
+  if (st->view) { if ((rc = hm_view_resolve(out_format, img->w, img->h, st->view, &p->vp))) return rc; }
+  else { p->vp.w = p->vp.ow = img->w; p->vp.h = p->vp.oh = img->h; p->vp.crop_only = 1; }
+  if (know_profile == HM_OUT_PROFILE_FIRST && (rc = out_resolve_profile(out_format, img, d, st, p))) return rc;
+  if ((p->dest_format = hm_out_dest_format(out_format, st)) < 0) return p->dest_format;
+  if ((rc = hm_dest_resolve(p->dest_format, p->vp.ow, p->vp.oh, d, &p->dp)) || (rc = hm_dest_check_len(d, &p->dp))) return rc;
+  if (know_profile == HM_OUT_PROFILE_LAST && (rc = out_resolve_profile(out_format, img, d, st, p))) return rc;
+  return HM_OK;
+}
+
+int hm_out_write(const hm_device_dest* d, const hm_out_plan* p, const void* src, int src_stride, hipStream_t s, hm_view_scratch* sc)
+{
+  const hm_view_plan* vp = &p->vp;
+  const hm_dest_plan& dp = p->dp;
+  // the kind of move: pointwise, the nearest sample, or sums under the taps of a filter
+  const bool summed = !vp->crop_only && vp->filter != HM_VIEW_NEAREST, nearest = !vp->crop_only && !summed;
+  // the step: plain (0), light (1), alpha with or without light (2).  HM_ALPHA_STRAIGHT without sums is r_c = x_c: the write without the step
+  const hm_light_plan* lp = p->has_light ? &p->lp : nullptr;
+  const bool alpha = p->has_alpha && (p->ap.mode != HM_ALPHA_STRAIGHT || summed);
+  const int step = alpha ? 2 : lp ? 1 : 0;
+  // (bytes of a source sample: of out_format - under an 8-bit finish or a matte dp.sample_bytes is the sibling target's)
+  const int obpp = hm_out_bytes_per_pixel(p->out_format), src_bytes = obpp >= 6 ? 2 : 1;
+  if (alpha && obpp != 4 && obpp != 8) return hm_fail(HM_ERR_INTERNAL, "alpha: output format %d has no four channels", p->out_format);
+  const uint8_t* origin = (const uint8_t*)src + (size_t)vp->y * src_stride + (size_t)vp->x * obpp;
+  if (!step && vp->crop_only) // the rectangle's bytes: the 2-D copy or k_to_tensor on the offset source
+    return hm_dest_write(d, p->out_format, vp->w, vp->h, 0, vp->h, origin, src_stride, s);
   const LightTables T(lp);
   const size_t table_bytes = T.bytes();
   hm_light_args la = T.args(src_bytes);
+  // ONE pinned block and one upload: the tap tables of both axes (summed), then the light tables; neither: no block, sc is not touched
+  size_t words_x = 0, words_y = 0;
+  int tx = 0, ty = 0, rc;
+  bool staged = false;
+  if (summed || table_bytes) {
+    if (!sc || sc->pinned || sc->dev[0] || sc->dev[1]) return hm_fail(HM_ERR_INTERNAL, "device write: no free scratch for the tables");
+    if (summed) { if ((rc = view_tables(vp, table_bytes, sc, &words_x, &words_y, &tx, &ty, &staged))) return rc; }
+    else if (!(sc->pinned = hm_pool_pinned_alloc(table_bytes))) return hm_fail(HM_ERR_NOMEM, "out of memory");
+  }
+  const size_t tap_bytes = (words_x + words_y) * 4, bytes = tap_bytes + table_bytes;
+  const float* host_tables = table_bytes ? reinterpret_cast<const float*>((const uint8_t*)sc->pinned + tap_bytes) : nullptr;
+  if (table_bytes) T.fill(const_cast<float*>(host_tables));
   hm_alpha_args aa;
   std::memset(&aa, 0, sizeof(aa));
-  aa.mode = ap->mode; aa.bits = ap->bits; aa.src_bytes = src_bytes; aa.P = (float)((1 << ap->bits) - 1);
-  // the background as the kernels take it: b_c = (float)background[c], with a light step lin[background[c]] of the table at `lin`
-  auto background = [&](const float* lin) { for (int c = 0; c < 3; c++) aa.bg[c] = lin ? lin[ap->background[c]] : (float)ap->background[c]; };
-  if (!summed) {
-    if (lp) {
-      float* host = (float*)hm_pool_pinned_alloc(table_bytes);
-      if (!host) return hm_fail(HM_ERR_NOMEM, "out of memory");
-      sc->pinned = host;
-      T.fill(host);
-      background(host);
-      if (!(sc->dev[0] = hm_pool_device_alloc(table_bytes))) return HM_ERR_NO_DEVICE;
-      if ((rc = hm_check_hip(hipMemcpyAsync(sc->dev[0], host, table_bytes, hipMemcpyHostToDevice, s), "upload of the light tables"))) return rc;
-      T.point(&la, (const float*)sc->dev[0]);
-    }
-    else background(nullptr);
-    if (vp && !vp->crop_only) return hm_launch_alpha_nearest(&p, lp ? &la : nullptr, &aa, origin, src_stride, cw, ch, ow, oh, d->ptr, d->scale, d->bias, s);
-    return hm_launch_alpha_tensor(&p, lp ? &la : nullptr, &aa, origin, src_stride, cw, ch, d->ptr, d->scale, d->bias, s);
+  if (alpha) {
+    aa.mode = p->ap.mode; aa.bits = p->ap.bits; aa.src_bytes = src_bytes; aa.P = (float)((1 << p->ap.bits) - 1);
+    // the background as the kernels take it: b_c = (float)background[c], with a light step lin[background[c]] of the table just filled
+    for (int c = 0; c < 3; c++) aa.bg[c] = host_tables ? host_tables[p->ap.background[c]] : (float)p->ap.background[c];
   }
-  // ONE pinned block and one upload: the tap tables of both axes, then the light tables
-  size_t words_x = 0, words_y = 0;
-  int tx = 0, ty = 0;
-  bool staged = false;
-  if ((rc = view_tables(vp, table_bytes, sc, &words_x, &words_y, &tx, &ty, &staged))) return rc;
-  const size_t tap_bytes = (words_x + words_y) * 4, bytes = tap_bytes + table_bytes;
-  int32_t* host = (int32_t*)sc->pinned;
-  float* host_tables = reinterpret_cast<float*>(host + words_x + words_y);
-  T.fill(host_tables);
-  background(lp ? host_tables : nullptr);
-  if (!(sc->dev[0] = hm_pool_device_alloc(bytes))) return HM_ERR_NO_DEVICE;
-  hm_dest_plan p4 = p; // the intermediate holds four sums per pixel, whatever the destination's channel count
-  p4.channels = 4;
-  hm_resample_args r = resample_args_of(vp, src_bytes, origin, src_stride, sc->dev[0], words_x, tx, ty, p4);
-  if (!(sc->dev[1] = hm_pool_device_alloc(resample_tmp_floats(r, p4) * sizeof(float)))) return HM_ERR_NO_DEVICE;
-  if ((rc = hm_check_hip(hipMemcpyAsync(sc->dev[0], host, bytes, hipMemcpyHostToDevice, s), "upload of the tap and light tables"))) return rc;
-  r.tmp = (float*)sc->dev[1];
-  T.point(&la, reinterpret_cast<const float*>(sc->dev[0]) + words_x + words_y);
-  return hm_launch_alpha_resample(&p, lp ? &la : nullptr, &aa, &r, d->ptr, d->scale, d->bias, s);
+  if (bytes && !(sc->dev[0] = hm_pool_device_alloc(bytes))) return HM_ERR_NO_DEVICE;
+  hm_resample_args r;
+  std::memset(&r, 0, sizeof(r));
+  if (summed) {
+    hm_dest_plan pi = dp; // the intermediate is laid out like the destination - under the alpha step with four sums per pixel, whatever its channel count
+    if (alpha) pi.channels = 4;
+    r = resample_args_of(vp, src_bytes, origin, src_stride, sc->dev[0], words_x, tx, ty, pi);
+    if (!(sc->dev[1] = hm_pool_device_alloc(resample_tmp_floats(r, pi) * sizeof(float)))) return HM_ERR_NO_DEVICE;
+    r.tmp = (float*)sc->dev[1];
+    if (!step) { r.staged = staged ? 1 : 0; r.stage_px = hm_knob(HM_KNOB_VIEW_STAGE_PX); } // (the light and alpha passes never stage)
+  }
+  const char* what = !summed ? "upload of the light tables" : table_bytes ? "upload of the tap and light tables" : "upload of the tap tables";
+  if (bytes && (rc = hm_check_hip(hipMemcpyAsync(sc->dev[0], sc->pinned, bytes, hipMemcpyHostToDevice, s), what))) return rc;
+  if (table_bytes) T.point(&la, reinterpret_cast<const float*>((const uint8_t*)sc->dev[0] + tap_bytes));
+  const hm_light_args* pla = lp ? &la : nullptr;
+  // one launch: {pointwise, nearest, summed} x {plain, light, alpha}; the plain pointwise one is hm_dest_write above
+  void* dst = d->ptr;
+  const float *sl = d->scale, *bs = d->bias;
+  if (summed)
+    return step == 2 ? hm_launch_alpha_resample(&dp, pla, &aa, &r, dst, sl, bs, s) : step == 1 ? hm_launch_light_resample(&dp, &la, &r, dst, sl, bs, s) : hm_launch_resample(&dp, &r, dst, sl, bs, s);
+  if (nearest)
+    return step == 2   ? hm_launch_alpha_nearest(&dp, pla, &aa, origin, src_stride, vp->w, vp->h, vp->ow, vp->oh, dst, sl, bs, s)
+           : step == 1 ? hm_launch_light_nearest(&dp, &la, origin, src_stride, vp->w, vp->h, vp->ow, vp->oh, dst, sl, bs, s)
+                       : hm_launch_view_nearest(&dp, origin, src_stride, vp->w, vp->h, vp->ow, vp->oh, dst, sl, bs, s);
+  return step == 2 ? hm_launch_alpha_tensor(&dp, pla, &aa, origin, src_stride, vp->w, vp->h, dst, sl, bs, s) : hm_launch_light_tensor(&dp, &la, origin, src_stride, vp->w, vp->h, dst, sl, bs, s);
+}
+
+// ---- the stand-alone entries: pixels that are in device memory already, through the same plan and writer ---------------------------
+
+// size_prefix: of the message about a wrong width or height (hm_to_tensor's speaks of the destination)
+static int out_to_tensor(int out_format, int bits, int w, int h, const void* src, int src_stride, const hm_out_steps& st, const hm_device_dest* dest, void* stream,
+                         const char* size_prefix = "")
+{
+  int rc = hm_out_check_static(out_format, dest, &st, 1);
+  if (rc || (rc = check_image_size(size_prefix, w, h))) return rc;
+  const hm_out_image img = {w, h, bits, st.light ? st.light->from_transfer : 0, st.light ? st.light->from_primaries : 0};
+  hm_out_plan p;
+  if ((rc = hm_out_resolve(out_format, &img, HM_OUT_PROFILE_FIRST, dest, &st, &p))) return rc;
+  const int obpp = hm_out_bytes_per_pixel(out_format);
+  if (src_stride < w * obpp) return hm_fail(HM_ERR_INVALID_ARG, "src_stride %d below the bytes of a row", src_stride);
+  if (obpp >= 6 && (((uintptr_t)src | (unsigned)src_stride) & 1)) return hm_fail(HM_ERR_INVALID_ARG, "16-bit samples at an odd address or stride");
+  int n_dev = 0;
+  if (hipGetDeviceCount(&n_dev) != hipSuccess || n_dev == 0) { (void)hipGetLastError(); return hm_fail(HM_ERR_NO_DEVICE, "no HIP device available"); }
+  if ((rc = hm_dest_check_pointer(dest))) return rc;
+  return with_scratch((hipStream_t)stream, [&](hm_view_scratch* sc) { return hm_out_write(dest, &p, src, src_stride, (hipStream_t)stream, sc); });
+}
+
+int hm_to_tensor(int out_format, int width, int height, const void* d_src, int src_stride, const hm_device_dest* dest, void* stream)
+{
+  if (!d_src || !dest) return hm_fail(HM_ERR_INVALID_ARG, "null argument");
+  return out_to_tensor(out_format, 0, width, height, d_src, src_stride, hm_out_steps{}, dest, stream, "device destination: ");
+}
+
+int hm_resample_to_tensor(int out_format, int src_w, int src_h, const void* d_src, int src_stride, const hm_device_view* view, const hm_device_dest* dest, void* stream)
+{
+  if (!d_src || !dest || !view) return hm_fail(HM_ERR_INVALID_ARG, "null argument");
+  return out_to_tensor(out_format, 0, src_w, src_h, d_src, src_stride, hm_out_steps{view, nullptr, nullptr, nullptr}, dest, stream);
+}
+
+int hm_light_to_tensor(int out_format, int bits, int src_w, int src_h, const void* d_src, int src_stride, const hm_device_view* view, const hm_device_light* light,
+                       const hm_device_dest* dest, void* stream)
+{
+  if (!d_src || !dest || !light) return hm_fail(HM_ERR_INVALID_ARG, "null argument");
+  return out_to_tensor(out_format, bits, src_w, src_h, d_src, src_stride, hm_out_steps{view, light, nullptr, nullptr}, dest, stream);
+}
+
+int hm_tone_to_tensor(int out_format, int bits, int src_w, int src_h, const void* d_src, int src_stride, const hm_device_view* view, const hm_device_light* light,
+                      const hm_device_tone* tone, const hm_device_dest* dest, void* stream)
+{
+  if (!d_src || !dest || !tone) return hm_fail(HM_ERR_INVALID_ARG, "null argument");
+  return out_to_tensor(out_format, bits, src_w, src_h, d_src, src_stride, hm_out_steps{view, light, tone, nullptr}, dest, stream);
 }
 
 int hm_alpha_to_tensor(int out_format, int bits, int src_w, int src_h, const void* d_src, int src_stride, const hm_device_view* view, const hm_device_light* light,
                        const hm_device_tone* tone, const hm_device_alpha* alpha, const hm_device_dest* dest, void* stream)
 {
   if (!d_src || !dest || !alpha) return hm_fail(HM_ERR_INVALID_ARG, "null argument");
-  int rc = hm_alpha_check_static(out_format, dest, light, tone, alpha, 1);
-  if (rc) return rc;
-  if (src_w <= 0 || src_h <= 0 || src_w > 32768 || src_h > 32768) return hm_fail(HM_ERR_INVALID_ARG, "image size %d x %d", src_w, src_h);
-  hm_view_plan vp;
-  std::memset(&vp, 0, sizeof(vp));
-  vp.ow = src_w; vp.oh = src_h;
-  if (view && (rc = hm_view_resolve(out_format, src_w, src_h, view, &vp))) return rc;
-  hm_light_plan lp;
-  hm_alpha_plan ap;
-  if ((rc = hm_alpha_resolve(out_format, bits, light ? light->from_transfer : 0, light ? light->from_primaries : 0, dest, light, tone, alpha, &lp, &ap))) return rc;
-  hm_dest_plan p;
-  if ((rc = hm_dest_resolve(ap.dest_format, vp.ow, vp.oh, dest, &p)) || (rc = hm_dest_check_len(dest, &p))) return rc;
-  if (src_stride < src_w * hm_out_bytes_per_pixel(out_format)) return hm_fail(HM_ERR_INVALID_ARG, "src_stride %d below the bytes of a row", src_stride);
-  if (out_format == HM_OUT_RRGGBBAA_LE && (((uintptr_t)d_src | (unsigned)src_stride) & 1)) return hm_fail(HM_ERR_INVALID_ARG, "16-bit samples at an odd address or stride");
-  int n_dev = 0;
-  if (hipGetDeviceCount(&n_dev) != hipSuccess || n_dev == 0) { (void)hipGetLastError(); return hm_fail(HM_ERR_NO_DEVICE, "no HIP device available"); }
-  if ((rc = hm_dest_check_pointer(dest))) return rc;
-  release_done();
-  hm_view_scratch* sc = new (std::nothrow) hm_view_scratch();
-  if (!sc) return hm_fail(HM_ERR_NOMEM, "out of memory");
-  rc = hm_alpha_write(dest, out_format, src_w, src_h, view ? &vp : nullptr, light ? &lp : nullptr, &ap, d_src, src_stride, (hipStream_t)stream, sc);
-  if (!sc->dev[0] && !sc->dev[1] && !sc->pinned) { delete sc; return rc; }
-  if (hipLaunchHostFunc((hipStream_t)stream, scratch_done, sc) != hipSuccess) { // (never on a healthy runtime: wait, then release here)
-    (void)hipGetLastError();
-    hipStreamSynchronize((hipStream_t)stream);
-    hm_view_scratch_free(sc);
-    delete sc;
-  }
-  return rc;
+  return out_to_tensor(out_format, bits, src_w, src_h, d_src, src_stride, hm_out_steps{view, light, tone, alpha}, dest, stream);
 }
 
 // ---- planar views: every plane an image of its own ------------------------------------------------------------------------------
@@ -1216,10 +1086,10 @@ int hm_planes_view_resolve(int chroma, int w, int h, const hm_device_view* v, hm
   if (!v || !pv) return hm_fail(HM_ERR_INVALID_ARG, "null view");
   std::memset(pv, 0, sizeof(*pv));
   if (chroma < HM_CHROMA_MONO || chroma > HM_CHROMA_444) return hm_fail(HM_ERR_INVALID_ARG, "planar view: chroma format %d", chroma);
-  if (w <= 0 || h <= 0 || w > 32768 || h > 32768) return hm_fail(HM_ERR_INVALID_ARG, "planar view: image size %d x %d", w, h);
-  hm_view_plan vp; // the luma rectangle: hm_device_view's own refusals (no target is big-endian here)
-  int rc = hm_view_resolve(0, w, h, v, &vp);
+  int rc = check_image_size("planar view: ", w, h);
   if (rc) return rc;
+  hm_view_plan vp; // the luma rectangle: hm_device_view's own refusals (no target is big-endian here)
+  if ((rc = hm_view_resolve(0, w, h, v, &vp))) return rc;
   const int bad = hm_pv_geometry(chroma, vp.x, vp.y, vp.w, vp.h, vp.ow, vp.oh, pv->crop, pv->out);
   if (bad == 1) return hm_fail(HM_ERR_INVALID_ARG, "planar view: crop_x %d is odd, the chroma planes of a 4:2:%d result have half the columns", vp.x, chroma == HM_CHROMA_420 ? 0 : 2);
   if (bad == 2) return hm_fail(HM_ERR_INVALID_ARG, "planar view: crop_y %d is odd, the chroma planes of a 4:2:0 result have half the rows", vp.y);
@@ -1450,18 +1320,7 @@ int hm_resample_planes_to_tensor(int chroma, int bits, int width, int height, in
   if (hipGetDeviceCount(&n_dev) != hipSuccess || n_dev == 0) { (void)hipGetLastError(); return hm_fail(HM_ERR_NO_DEVICE, "no HIP device available"); }
   f.planes = planes; f.chroma = chroma; f.bits = bits; f.alpha_bits = alpha_bits;
   for (int c = 0; c < 4; c++) { f.src[c] = d_src[c]; f.stride[c] = src_stride[c]; }
-  release_done();
-  hm_view_scratch* sc = new (std::nothrow) hm_view_scratch();
-  if (!sc) return hm_fail(HM_ERR_NOMEM, "out of memory");
-  rc = hm_planes_view_write(&f, 1, (hipStream_t)stream, sc, nullptr);
-  if (!sc->dev[0] && !sc->dev[1] && !sc->pinned) { delete sc; return rc; }
-  if (hipLaunchHostFunc((hipStream_t)stream, scratch_done, sc) != hipSuccess) { // (never on a healthy runtime: wait, then release here)
-    (void)hipGetLastError();
-    hipStreamSynchronize((hipStream_t)stream);
-    hm_view_scratch_free(sc);
-    delete sc;
-  }
-  return rc;
+  return with_scratch((hipStream_t)stream, [&](hm_view_scratch* sc) { return hm_planes_view_write(&f, 1, (hipStream_t)stream, sc, nullptr); });
 }
 
 } // extern "C"

@@ -92,16 +92,12 @@ typedef struct hm_view_scratch { void* dev[2]; void* pinned; } hm_view_scratch;
 void hm_view_scratch_free(hm_view_scratch* sc);
 // the view against a src_w x src_h image and the target: every refusal of the view itself
 int hm_view_resolve(int out_format, int src_w, int src_h, const hm_device_view* v, hm_view_plan* vp);
-// the rectangle vp of `src` (interleaved pixels of out_format, row 0 = image row 0) into the destination, which has been checked
-// against vp->ow x vp->oh; asynchronous on `s`
-int hm_view_write(const hm_device_dest* d, int out_format, const hm_view_plan* vp, const void* src, int src_stride, hipStream_t s, hm_view_scratch* sc);
-
-// one frame of a batched view write: hm_view_write's arguments
+// one frame of a batched view write: the destination, the view resolved against the frame, the frame's interleaved pixels (row 0 = image row 0)
 typedef struct hm_view_item { const hm_device_dest* dest; hm_view_plan vp; const void* src; int32_t src_stride; } hm_view_item;
-// hm_view_write over n frames (a sequence under one view).  Frames that agree in crop, output size, filter, sample format,
+// The view of n frames (a sequence under one view) into their destinations.  Frames that agree in crop, output size, filter, sample format,
 // source stride, the destination's layout, dtype, pitches, scale, bias and 16-byte alignment form a group: one pair of tap tables,
 // one upload (tables + the frames' pointers), one bounded intermediate, and per chunk of frames one launch per pass
-// (hm_view_batch.h holds the arithmetic).  The crop alone and HM_VIEW_NEAREST stay calls of hm_view_write per frame, and so does
+// (hm_view_batch.h holds the arithmetic).  The crop alone and HM_VIEW_NEAREST stay calls of hm_out_write per frame, and so does
 // everything with knob view_batch = 0.  Every destination is checked before anything is queued.  sc: n zeroed entries.
 int hm_view_write_batch(int out_format, const hm_view_item* items, int n, hipStream_t s, hm_view_scratch* sc);
 
@@ -141,30 +137,12 @@ typedef struct hm_light_plan {
   // the tone step (hm_device_tone) beside it, resolved: nothing left at 0
   int32_t tone;          // a tone step runs
   int32_t enc_bits;      // of the codes the finish stores: bits, or 8 under the 8-bit finish
-  int32_t dest_format;   // the target the destination is judged, sized and written as: out_format, or its 8-bit sibling
   float src_peak, dst_peak, unit_nits, out_unit_nits;
 } hm_light_plan;
-// what depends on the request alone: reserved, gain, the codes (from_* == 0: allowed unless `explicit_from`), the target (no _BE, no
-// planar one), HM_LIGHT_LINEAR with an integer dtype
-int hm_light_check_static(int out_format, const hm_device_dest* d, const hm_device_light* l, int explicit_from);
-// ... and what depends on the image: from_* == 0 become img_transfer / img_primaries (what hm_decoded reports), bits the sample depth
-int hm_light_resolve(int out_format, int bits, int img_transfer, int img_primaries, const hm_device_dest* d, const hm_device_light* l, hm_light_plan* lp);
+// (the step's refusals: hm_out_check_static; its plan: hm_out_resolve)
 // ---- the tone step (hm_device_tone) inside the light step: two tables of HM_TONE_STEPS entries, built in devdest.cpp ----
-// the target the destination of a request is judged by: out_format, or with tone->out_bits == 8 the 8-bit sibling of a 16-bit one
-int hm_tone_dest_format(int out_format, const hm_device_tone* tone);
-// hm_light_check_static with a tone step (tone NULL: that function): the tone step's own refusals first, then the light step's and the
-// destination's, the latter against hm_tone_dest_format.  explicit_from: src_peak and unit_nits must be given too.
-int hm_tone_check_static(int out_format, const hm_device_dest* d, const hm_device_light* l, const hm_device_tone* tone, int explicit_from);
-// hm_light_resolve with a tone step (tone NULL: that function); src_peak == 0 and unit_nits == 0 are refused or resolved here
-int hm_tone_resolve(int out_format, int bits, int img_transfer, int img_primaries, const hm_device_dest* d, const hm_device_light* l, const hm_device_tone* tone,
-                    hm_light_plan* lp);
 // the peak rule of include/heif_mi355x.h on an item's raw properties
 float hm_tone_peak_of(int has_clli, unsigned max_cll, int has_mdcv, unsigned mdcv_max);
-
-// hm_dest_write / hm_view_write under a light step: the w x h image at `src` (vp NULL), or its view vp, into the destination, which
-// has been checked against the size written (as lp->dest_format); asynchronous on `s`.  The tables (and a view's tap tables and intermediate) hang on sc.
-int hm_light_write(const hm_device_dest* d, int out_format, int w, int h, const hm_view_plan* vp, const hm_light_plan* lp, const void* src, int src_stride,
-                   hipStream_t s, hm_view_scratch* sc);
 
 // what the kernels get: device pointers of lin[1 << bits], (encode) enc[1 << enc_bits] and (tone) thr[HM_TONE_STEPS] with sg[HM_TONE_STEPS]
 // behind it; src_bytes: bytes of a source sample (the plan's sample_bytes are the destination's sibling target's)
@@ -181,23 +159,8 @@ int hm_launch_light_resample(const hm_dest_plan* p, const hm_light_args* la, con
 typedef struct hm_alpha_plan {
   int32_t mode;          // HM_ALPHA_*
   int32_t bits;          // of the target's samples: P = (1 << bits) - 1
-  int32_t dest_format;   // the target the destination is judged, sized and written as (hm_alpha_dest_format)
   uint16_t background[3];
 } hm_alpha_plan;
-// what depends on the request alone: the step's own refusals, then those of the tone, light and destination checks against
-// hm_alpha_dest_format (l and tone may be NULL).  A background above the peak of an 8-bit target is refused here, of a 16-bit one in
-// hm_alpha_resolve.
-int hm_alpha_check_static(int out_format, const hm_device_dest* d, const hm_device_light* l, const hm_device_tone* tone, const hm_device_alpha* a, int explicit_from);
-// ... and what depends on the image: bits, the background against the peak, and with a light step hm_tone_resolve's work into *lp (its
-// dest_format: the alpha step's)
-int hm_alpha_resolve(int out_format, int bits, int img_transfer, int img_primaries, const hm_device_dest* d, const hm_device_light* l, const hm_device_tone* tone,
-                     const hm_device_alpha* a, hm_light_plan* lp, hm_alpha_plan* ap);
-// hm_dest_write / hm_view_write / hm_light_write under an alpha step: the w x h four-channel image at `src` (vp NULL), or its view vp,
-// into the destination, which has been checked against the size written (as ap->dest_format); lp NULL: no light step.  HM_ALPHA_STRAIGHT
-// without sums is the write without the step.  Asynchronous on `s`; tables and the intermediate hang on sc.
-int hm_alpha_write(const hm_device_dest* d, int out_format, int w, int h, const hm_view_plan* vp, const hm_light_plan* lp, const hm_alpha_plan* ap, const void* src,
-                   int src_stride, hipStream_t s, hm_view_scratch* sc);
-
 // what the kernels get beside hm_light_args (la NULL: no light step): bytes of a source sample, P, and the background as the floats b_c
 typedef struct hm_alpha_args { int32_t mode, bits, src_bytes; float P; float bg[3]; } hm_alpha_args;
 int hm_launch_alpha_tensor(const hm_dest_plan* p, const hm_light_args* la, const hm_alpha_args* aa, const void* src, int src_stride, int w, int rows, void* dst,
@@ -207,6 +170,35 @@ int hm_launch_alpha_nearest(const hm_dest_plan* p, const hm_light_args* la, cons
 // r: of a FOUR-channel intermediate (the sums of p_R, p_G, p_B and a), whatever the destination's channel count
 int hm_launch_alpha_resample(const hm_dest_plan* p, const hm_light_args* la, const hm_alpha_args* aa, const hm_resample_args* r, void* dst, const float scale[4],
                              const float bias[4], hipStream_t s);
+
+// ---- the device write: the interleaved pixels of one image through the steps of a request - view, light (with tone inside it), alpha -
+//      into a hm_device_dest.  One request (hm_out_steps), one plan (hm_out_plan), one writer (hm_out_write); a further step is a case
+//      inside them ----
+typedef struct hm_out_steps { const hm_device_view* view; const hm_device_light* light; const hm_device_tone* tone; const hm_device_alpha* alpha; } hm_out_steps; // any may be NULL
+typedef struct hm_out_image { int32_t w, h, bits, transfer, primaries; } hm_out_image; // what the image reports (hm_decoded)
+typedef struct hm_out_plan {
+  int32_t out_format, dest_format; // the source's target; the target the destination is judged, sized and written as
+  int32_t w, h;                    // the source image
+  int32_t has_view, has_light, has_alpha;
+  hm_view_plan vp;                 // without a view: the whole image as a crop alone (ow = w, oh = h)
+  hm_light_plan lp; hm_alpha_plan ap;
+  hm_dest_plan dp;                 // against dest_format at vp.ow x vp.oh; d->len has been compared
+} hm_out_plan;
+// the target the destination is judged by: hm_alpha_dest_format with an alpha step (negative: the step's own refusals), else with
+// tone->out_bits == 8 the 8-bit sibling of a 16-bit three-channel target, else out_format
+int hm_out_dest_format(int out_format, const hm_out_steps* st);
+// what depends on the request alone: the alpha step's own refusals, then the tone step's, the light step's (from_* == 0: allowed
+// unless `explicit_from`, which wants src_peak and unit_nits given too) and the destination's, each against hm_out_dest_format
+int hm_out_check_static(int out_format, const hm_device_dest* d, const hm_out_steps* st, int explicit_from);
+// ... and what depends on the image.  The size: the view, the destination against the size written, its len.  The profile
+// (know_profile != 0): hm_out_check_static again, the depth, the alpha step's background against the peak, the light step's from_* == 0
+// as img->transfer / img->primaries, the tone step's units - behind the size (HM_OUT_PROFILE_LAST: the decode entries), or between the
+// view and the destination (HM_OUT_PROFILE_FIRST: the order of the stand-alone entries).  know_profile 0: p->lp and p->ap stay empty.
+enum { HM_OUT_PROFILE_LAST = 1, HM_OUT_PROFILE_FIRST = 2 };
+int hm_out_resolve(int out_format, const hm_out_image* img, int know_profile, const hm_device_dest* d, const hm_out_steps* st, hm_out_plan* p);
+// the image at `src` (interleaved pixels of p->out_format, row 0 = image row 0) through the plan into the destination; asynchronous on
+// `s`.  Tables and the intermediate hang on sc, which must be a free entry (it is not looked at where nothing is uploaded).
+int hm_out_write(const hm_device_dest* d, const hm_out_plan* p, const void* src, int src_stride, hipStream_t s, hm_view_scratch* sc);
 
 // ---- planar views: a view (hm_device_view) into planar YCbCr (hm_device_planes), every plane an image of its own.  devdest.cpp
 //      holds the checks and the write step, hm_planes_view.h the index arithmetic, planes_view.hip the kernels ----

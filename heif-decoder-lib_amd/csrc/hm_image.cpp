@@ -873,17 +873,11 @@ static Reported converted_report(const hm::NclxProfile& native, bool is_grid, in
   return r;
 }
 
-// the target the destination of t.dest is judged, sized and written as (the alpha step's own refusals: check_target_request has made them)
-static int target_dest_format(const hm_decode_params* params, const OutputTarget& t)
-{
-  return t.alpha ? hm_alpha_dest_format(params->out_format, t.alpha, t.tone) : hm_tone_dest_format(params->out_format, t.tone);
-}
-
 // Can the target hold the result of a w x h image of (chroma, bits)?  The one statement of that question: the entry points ask it
 // against what the file declares, the sequence and emit_image again against the decoded picture.  A new kind of destination gets
 // its chain here.
-//   dest:   the view against the image, the destination against the view's output size, its len, the light step against the
-//           profile and depth the image reports (`reported`, may be NULL: not known yet), the pointer
+//   dest:   hm_out_resolve - the view against the image, the destination against the view's output size, its len, the light and alpha
+//           steps against the profile and depth the image reports (`reported`, may be NULL: not known yet) -, the pointer
 //   planes: the result's format (planar_result_format), the view against it, the planes against the view's output size - alpha_bits
 //           0: no alpha plane, -1: the decode's to say -, their len, the pointers
 // w <= 0 or h <= 0: the file does not say - only what needs no size is looked at.  pointers: a device must exist and the pointers
@@ -895,19 +889,10 @@ static int target_fits(const hm_decode_params* params, const OutputTarget& t, in
   const bool sized = w > 0 && h > 0;
   if (t.dest) {
     if (sized) {
-      hm_dest_plan dp;
-      hm_view_plan vp;
-      vp.ow = w; vp.oh = h;
-      if (t.view && (rc = hm_view_resolve(params->out_format, w, h, t.view, &vp))) return rc;
-      const int dest_format = target_dest_format(params, t);
-      if (dest_format < 0) return dest_format;
-      if ((rc = hm_dest_resolve(dest_format, vp.ow, vp.oh, t.dest, &dp)) || (rc = hm_dest_check_len(t.dest, &dp))) return rc;
-      hm_light_plan lp;
-      hm_alpha_plan ap;
-      if (t.alpha && reported && (rc = hm_alpha_resolve(params->out_format, reported->bit_depth, reported->transfer, reported->primaries, t.dest, t.light, t.tone, t.alpha, &lp, &ap)))
-        return rc;
-      if (!t.alpha && t.light && reported && (rc = hm_tone_resolve(params->out_format, reported->bit_depth, reported->transfer, reported->primaries, t.dest, t.light, t.tone, &lp)))
-        return rc;
+      const hm_out_steps st = t.steps();
+      const hm_out_image img = {w, h, reported ? reported->bit_depth : 0, reported ? reported->transfer : 0, reported ? reported->primaries : 0};
+      hm_out_plan plan;
+      if ((rc = hm_out_resolve(params->out_format, &img, reported ? HM_OUT_PROFILE_LAST : 0, t.dest, &st, &plan))) return rc;
     }
     if (pointers && ((rc = require_device()) || (rc = hm_dest_check_pointer(t.dest)))) return rc;
   }
@@ -1048,35 +1033,20 @@ static int emit_interleaved(const hm_decode_params* params, hipStream_t s, Plana
   out->bit_depth = r.bit_depth;
   out->stride[0] = cd.out_stride;
   out->plane_width[0] = img_w; out->plane_height[0] = img_h;
-  if (t.dest) { // the image's w x h x C elements and nothing else: a 2-D device copy or k_to_tensor (devdest.cpp)
-    hm_view_plan vp; // view: a rectangle of the image at vp.ow x vp.oh goes to the destination (the resampling step instead of hm_dest_write)
-    std::memset(&vp, 0, sizeof(vp));
-    vp.ow = img_w; vp.oh = img_h;
-    if (t.view && (rc = hm_view_resolve(params->out_format, img_w, img_h, t.view, &vp))) return rc;
-    if (t.alpha) { // ... through the alpha step (and the light step beside it), resolved as the light step below is
-      hm_light_plan lp;
-      hm_alpha_plan ap;
-      if ((rc = hm_alpha_resolve(params->out_format, r.bit_depth, r.transfer, r.primaries, t.dest, t.light, t.tone, t.alpha, &lp, &ap))) return rc;
-      if ((rc = hm_alpha_write(t.dest, params->out_format, img_w, img_h, t.view ? &vp : nullptr, t.light ? &lp : nullptr, &ap, dout.p, cd.out_stride, s, t.scratch))) return rc;
-    }
-    else if (t.light) { // ... through the light step, resolved against the profile and depth this image reports: refused before a byte is written
-      hm_light_plan lp;
-      if ((rc = hm_tone_resolve(params->out_format, r.bit_depth, r.transfer, r.primaries, t.dest, t.light, t.tone, &lp))) return rc;
-      if ((rc = hm_light_write(t.dest, params->out_format, img_w, img_h, t.view ? &vp : nullptr, &lp, dout.p, cd.out_stride, s, t.scratch))) return rc;
-    }
-    else if (t.view) {
-      if (t.view_later) { t.view_later->dest = t.dest; t.view_later->vp = vp; t.view_later->src = dout.p; t.view_later->src_stride = cd.out_stride; } // (a sequence: hm_view_write_batch)
-      else if ((rc = hm_view_write(t.dest, params->out_format, &vp, dout.p, cd.out_stride, s, t.scratch))) return rc;
-    }
-    else if ((rc = hm_dest_write(t.dest, params->out_format, img_w, img_h, 0, img_h, dout.p, cd.out_stride, s))) return rc;
+  if (t.dest) { // the image, or with a view a rectangle of it at vp.ow x vp.oh, through the steps of the request and nothing else (devdest.cpp): the light and
+                // alpha steps resolved against the profile and depth this image reports - refused before a byte is written
+    const hm_out_steps st = t.steps();
+    const hm_out_image img = {img_w, img_h, r.bit_depth, r.transfer, r.primaries};
+    hm_out_plan plan;
+    if ((rc = hm_out_resolve(params->out_format, &img, HM_OUT_PROFILE_LAST, t.dest, &st, &plan))) return rc;
+    if (t.view_later) { t.view_later->dest = t.dest; t.view_later->vp = plan.vp; t.view_later->src = dout.p; t.view_later->src_stride = cd.out_stride; } // (a sequence: hm_view_write_batch)
+    else if ((rc = hm_out_write(t.dest, &plan, dout.p, cd.out_stride, s, t.scratch))) return rc;
     if (t.view) {
-      out->width = vp.ow; out->height = vp.oh;
-      out->plane_width[0] = vp.ow; out->plane_height[0] = vp.oh;
+      out->width = plan.vp.ow; out->height = plan.vp.oh;
+      out->plane_width[0] = plan.vp.ow; out->plane_height[0] = plan.vp.oh;
     }
-    hm_dest_plan dp;
-    if ((rc = hm_dest_resolve(target_dest_format(params, t), vp.ow, vp.oh, t.dest, &dp))) return rc;
     out->used_ext_dst = 1;
-    out->stride[0] = (int32_t)std::min<int64_t>(dp.row_pitch, 0x7FFFFFFF);
+    out->stride[0] = (int32_t)std::min<int64_t>(plan.dp.row_pitch, 0x7FFFFFFF);
   }
   else if (params->ext_dst && params->ext_dst_stride >= (uint32_t)(img_w * obpp) &&
       (size_t)params->ext_dst_len >= (size_t)params->ext_dst_stride * (size_t)img_h) {
@@ -1194,12 +1164,8 @@ int check_target_request(const hm_file* f, uint32_t id, const hm_decode_params* 
   if (rc) return rc;
   if (t.dest) {
     if (params->ext_dst) return hm_fail(HM_ERR_INVALID_ARG, "params->ext_dst must be NULL with a device destination");
-    if (t.alpha) { if ((rc = hm_alpha_check_static(params->out_format, t.dest, t.light, t.tone, t.alpha, 0))) return rc; } // (its own refusals, then all of those below)
-    else if (t.tone) { if ((rc = hm_tone_check_static(params->out_format, t.dest, t.light, t.tone, 0))) return rc; } // (its own refusals, then the two below)
-    else {
-      if ((rc = hm_dest_check_static(params->out_format, t.dest))) return rc;
-      if (t.light && (rc = hm_light_check_static(params->out_format, t.dest, t.light, 0))) return rc;
-    }
+    const hm_out_steps st = t.steps();
+    if ((rc = hm_out_check_static(params->out_format, t.dest, &st, 0))) return rc;
     if (!t.dest->ptr) return hm_fail(HM_ERR_INVALID_ARG, "device destination: null ptr");
   }
   if (t.planes && (rc = check_planes_params(params, t.planes))) return rc;
@@ -1723,8 +1689,7 @@ int hm_decode_item_to_device_alpha(const hm_file* f, uint32_t id, const hm_decod
   if (tone && !light) return hm_fail(HM_ERR_INVALID_ARG, "tone: null light step");
   hm_device_tone own{};
   if (tone) own = tone_for_item(f, id, tone);
-  OutputTarget t = OutputTarget::to_dest(dest, view, light, tone ? &own : nullptr);
-  t.alpha = alpha;
+  const OutputTarget t = OutputTarget::to_dest(dest, view, light, tone ? &own : nullptr, alpha);
   return decode_item_to(f, id, params, t, out);
 }
 
@@ -1974,7 +1939,7 @@ int hm_decode_frames_to_device_planes(const hm_file* f, const uint32_t* frames, 
 // frames (NULL: first .. first + count - 1): the 1-based IDs of the frames, in any order, repeats allowed.
 // target: dest or planes are arrays of `count` entries, frame k's at [k] - every frame goes to caller-owned device memory; view: the same
 // rectangle of every frame, resampled, in one batched write behind the frames' conversions (hm_view_write_batch, hm_planes_view_write);
-// light: every frame's write runs the light step, frame by frame (hm_light_write) - no batched form
+// light: every frame's write runs the light step, frame by frame (hm_out_write) - no batched form
 static int decode_sequence(const hm_file* f, const uint32_t* frames, uint32_t first, int32_t count, const hm_decode_params* params, const hm_frame_dest* dests,
                            const OutputTarget& target, hm_decoded* out, int32_t* failed_frame)
 {
@@ -2007,9 +1972,9 @@ static int decode_sequence(const hm_file* f, const uint32_t* frames, uint32_t fi
   auto frame_id = [&](int k) { return frames ? frames[k] : first + (uint32_t)k; };
   if (params->ext_dst) return hm_fail(HM_ERR_INVALID_ARG, "params->ext_dst: a sequence takes its caller buffers from dests");
   if (ddests) { // what can be refused without the frames' sizes (those: below, behind the entropy decode, before anything is queued)
+    const hm_out_steps st = target.steps();
     for (int k = 0; k < count; k++) {
-      int rc = target.tone ? hm_tone_check_static(params->out_format, &ddests[k], light, target.tone, 0) : hm_dest_check_static(params->out_format, &ddests[k]);
-      if (!rc && light && !target.tone) rc = hm_light_check_static(params->out_format, &ddests[k], light, 0);
+      const int rc = hm_out_check_static(params->out_format, &ddests[k], &st, 0);
       if (rc) return rc;
       if (!ddests[k].ptr) return hm_fail(HM_ERR_INVALID_ARG, "device destination of frame %d: null ptr", k);
     }

@@ -114,12 +114,14 @@ struct OutputTarget {
   hm_view_scratch* scratch = nullptr;          // tap tables and the intermediate of the resampling step, the tables of the light step
   hm_view_item* view_later = nullptr;          // view + dest: the view is not written, only described there - the caller writes it with those of other images
   hm_planes_view_item* planes_later = nullptr; // the same for view + planes
-  static OutputTarget to_dest(const hm_device_dest* d, const hm_device_view* v = nullptr, const hm_device_light* l = nullptr, const hm_device_tone* tn = nullptr)
+  static OutputTarget to_dest(const hm_device_dest* d, const hm_device_view* v = nullptr, const hm_device_light* l = nullptr, const hm_device_tone* tn = nullptr,
+                              const hm_device_alpha* a = nullptr)
   {
     OutputTarget t;
-    t.dest = d; t.view = v; t.light = l; t.tone = tn;
+    t.dest = d; t.view = v; t.light = l; t.tone = tn; t.alpha = a;
     return t;
   }
+  hm_out_steps steps() const { return hm_out_steps{view, light, tone, alpha}; } // the request of the device write (hm_devdest.h)
   static OutputTarget to_planes(const hm_device_planes* p, const hm_device_view* v = nullptr)
   {
     OutputTarget t;

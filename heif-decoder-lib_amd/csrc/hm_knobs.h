@@ -31,7 +31,7 @@ extern "C" {
 //   stream_interleaved (0) 1: records in decode order (format of the rare-syntax classes) for every picture
 //   view_h_staged (1)      0: HM_VIEW_CUBIC / HM_VIEW_LANCZOS3 run their horizontal pass on the per-lane k_resample_h (A/B measurements, tests)
 //   view_stage_px (0)      > 0: k_resample_h_staged stages at most that many pixels per chunk (tests: several chunks on a short row)
-//   view_batch (1)         0: a sequence under a view (hm_decode_frames_to_device_view) runs hm_view_write once per frame (A/B measurements, tests)
+//   view_batch (1)         0: a sequence under a view (hm_decode_frames_to_device_view) runs hm_out_write once per frame (A/B measurements, tests)
 //   view_batch_bytes (0)   > 0: the bound of a batched view write's intermediate in bytes (0: 64 MiB; tests: several chunks on small frames)
 //   overlap_min_pics (0)   > 0: hm_batch_execute's automatic overlap (hm_overlap_plan.h) engages from that many pictures on, whatever cut the chain launcher takes
 //   overlap_cut (0)        > 0: the image index at which the automatic overlap cuts the batch into its two groups

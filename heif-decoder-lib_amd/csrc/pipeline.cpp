@@ -224,8 +224,7 @@ int hm_pipeline_submit_to_device_alpha(hm_pipeline* p, const uint8_t* heif, size
 {
   if (!p || !heif || !alpha || !dest) return hm_fail(HM_ERR_INVALID_ARG, "null argument");
   if (tone && !light) return hm_fail(HM_ERR_INVALID_ARG, "tone: null light step");
-  OutputTarget t = OutputTarget::to_dest(dest, view, light, tone);
-  t.alpha = alpha;
+  const OutputTarget t = OutputTarget::to_dest(dest, view, light, tone, alpha);
   return submit(p, heif, size, item_id, tag, t);
 }
 

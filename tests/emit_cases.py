@@ -65,10 +65,10 @@ class Device:
         torch.cuda.synchronize()
         self.base = self.t.data_ptr()
 
-    def dest(self, capi, fmt, light, k=0):
+    def dest(self, capi, fmt, light, k=0, dtype=None):
         d = capi.DeviceDest()
         d.ptr, d.len, d.layout = self.base + (k % 4) * SLOT, SLOT, HWC
-        d.dtype = F32 if light else (U16 if fmt >= 12 else U8)
+        d.dtype = dtype if dtype is not None else F32 if light else (U16 if fmt >= 12 else U8)
         for c in range(4):
             d.scale[c], d.bias[c] = 1.0, 0.0
         return d
@@ -142,4 +142,59 @@ def walk(capi, L):
         for fmt, to8 in formats(chroma):
             for kind in KINDS:
                 got[f"{name} | {fmt:#x}{'+8' if to8 else ''} | {kind}"] = one(capi, L, dev, blob, call, chroma, alpha, fmt, to8, kind)
+    return got
+
+
+# ---- the tone and alpha steps (tests/golden/emit_fields_steps.json): the same fields through hm_decode_*_to_device_tone / _alpha ----
+RRGGBBAA_LE = 15
+STEP_KINDS = ("tone", "alpha", "alpha_view", "alpha_light", "alpha_matte_tone8")
+STEP_PICTURES = ("p420_8", "p420_10", "alpha", "grid", "movie", "iovl")  # (movie: a sequence takes no alpha step - tone only)
+STEP_FORMATS = (RGB, RGBA, RRGGBB_LE, RRGGBBAA_LE)
+
+
+def one_step(capi, L, dev, blob, call, fmt, kind):
+    """one decode through the tone or the alpha entry: {"status", "message"[, "failed_frame"], "images": [fields]}"""
+    fh = C.c_void_p()
+    assert L.hm_file_open(blob, len(blob), C.byref(fh)) == 0
+    n = 3 if call == "seq" else 1
+    prm = capi.DecodeParams(fmt, 2, 0, 0, None, None, 0, 0, 0, 0)
+    out = (capi.Decoded * n)()
+    failed = C.c_int32(7)
+    view = C.byref(capi.DeviceView(*VIEW)) if kind == "alpha_view" else None
+    matte8 = kind == "alpha_matte_tone8"
+    # the image's own codes to linear light - re-encoded as sRGB under the 8-bit finish
+    light = C.byref(capi.DeviceLight(0, 0, 13 if matte8 else 8, 0, 1.0, (C.c_int32 * 3)(0, 0, 0))) if kind in ("tone", "alpha_light") or matte8 else None
+    tone = C.byref(capi.DeviceTone(1, 8 if matte8 else 0, 0.0, 100.0, 100.0, 0.0, (C.c_int32 * 2)(0, 0))) if kind == "tone" or matte8 else None
+    mode = {"alpha": 2, "alpha_view": 1, "alpha_light": 2, "alpha_matte_tone8": 3}.get(kind, 0)
+    alpha = capi.DeviceAlpha(mode, (C.c_uint16 * 4)(*((10, 20, 30, 0) if matte8 else (0, 0, 0, 0))), (C.c_int32 * 3)(0, 0, 0))
+    dests = (capi.DeviceDest * n)(*[dev.dest(capi, fmt, light is not None, k, U8 if matte8 else None) for k in range(n)])
+    try:
+        if kind != "tone":
+            rc = L.hm_decode_item_to_device_alpha(fh, L.hm_file_primary_item(fh), C.byref(prm), view, light, tone, C.byref(alpha), dests, out)
+        elif call == "item":
+            rc = L.hm_decode_item_to_device_tone(fh, L.hm_file_primary_item(fh), C.byref(prm), view, light, tone, dests, out)
+        else:
+            rc = L.hm_decode_frames_to_device_tone(fh, (C.c_uint32 * n)(3, 1, 2), n, C.byref(prm), view, light, tone, dests, out, C.byref(failed))
+        got = {"status": rc, "message": L.hm_last_error().decode() if rc else ""}
+        if call == "seq":
+            got["failed_frame"] = failed.value
+        if rc == 0:
+            got["images"] = [fields(out[k]) for k in range(n)]
+        for k in range(n):
+            L.hm_decoded_free(C.byref(out[k]))
+        return got
+    finally:
+        L.hm_file_close(fh)
+
+
+def walk_steps(capi, L):
+    """{"picture | out_format | kind": result}"""
+    dev = Device()
+    pics = pictures()
+    got = {}
+    for name in STEP_PICTURES:
+        blob, call = pics[name][:2]
+        for fmt in STEP_FORMATS:
+            for kind in STEP_KINDS if call == "item" else ("tone",):
+                got[f"{name} | {fmt:#x} | {kind}"] = one_step(capi, L, dev, blob, call, fmt, kind)
     return got

@@ -12,14 +12,17 @@ import synthutil
 
 FAKE = 0x10000000
 HM_ERR_NO_DEVICE = -4
-RGB, RGBA, RRGGBB_BE, RRGGBBAA_BE, RRGGBB_LE = 10, 11, 12, 13, 14
+RGB, RGBA, RRGGBB_BE, RRGGBBAA_BE, RRGGBB_LE, RRGGBBAA_LE = 10, 11, 12, 13, 14, 15
 HWC, CHW = 0, 1
 U8, U16, F16, F32 = 0, 1, 2, 3
 TRIANGLE, NEAREST, CUBIC, LANCZOS3 = 0, 1, 16, 17
+STRAIGHT, PREMULTIPLIED, MATTE = 1, 2, 3
 N_FRAMES = 3
 SENTINEL = 7  # what failed_frame holds before a call
 
-# families: the picture they decode, whether the destination is planes, whether they take a view / a light step / frame IDs
+# families: the picture they decode ("tensor": none - the stand-alone entries, on a source pointer that is never read), whether the
+# destination is planes, whether they take a view / a light step / a tone step / an alpha step / frame IDs.  An alpha family hands
+# on the light and tone steps a case names, and none otherwise.
 FAMILIES = {
     "item_dest":          dict(call="item"),
     "item_view":          dict(call="item", view=True),
@@ -36,6 +39,16 @@ FAMILIES = {
     "pipe_light":         dict(call="pipe", view=True, light=True),
     "pipe_planes":        dict(call="pipe", planes=True),
     "pipe_planes_view":   dict(call="pipe", planes=True, view=True),
+    "item_tone":          dict(call="item", view=True, light=True, tone=True),
+    "item_alpha":         dict(call="item", view=True, alpha=True),
+    "frames_tone":        dict(call="seq", view=True, light=True, tone=True, frames=True),
+    "pipe_tone":          dict(call="pipe", view=True, light=True, tone=True),
+    "pipe_alpha":         dict(call="pipe", view=True, alpha=True),
+    "tensor_dest":        dict(call="tensor"),
+    "tensor_view":        dict(call="tensor", view=True),
+    "tensor_light":       dict(call="tensor", view=True, light=True),
+    "tensor_tone":        dict(call="tensor", view=True, light=True, tone=True),
+    "tensor_alpha":       dict(call="tensor", view=True, alpha=True),
 }
 
 
@@ -46,13 +59,27 @@ def _fam(**want):
 EVERY = list(FAMILIES)
 DEST, PLANES, VIEW, LIGHT = _fam(planes=False), _fam(planes=True), _fam(view=True), _fam(light=True)
 DEST_VIEW = [n for n in DEST if n in VIEW]
+TONE, ALPHA, TENSOR = _fam(tone=True), _fam(alpha=True), _fam(call="tensor")
+WITH_PARAMS = [n for n in EVERY if not n.startswith("pipe_") and n not in TENSOR]  # the entry points that take hm_decode_params
 GOOD_VIEW = ((4, 2, 10, 8), (5, 4), TRIANGLE)  # crop, output size, filter
 GOOD_LIGHT = (0, 0, 8, 0, 1.0)                # the image's own codes to linear light
+LINEAR, ENCODED = (13, 1, 8, 0, 1.0), (13, 1, 13, 0, 1.0)  # sRGB codes, named (the stand-alone entries take no others), to linear light / re-encoded
+GOOD_TONE = (1, 0, 1000.0, 100.0, 100.0, 0.0)  # curve, out_bits, src_peak, dst_peak, unit_nits, out_unit_nits
+BAD_VIEW = ((10, 10, 10, 10), (5, 5), TRIANGLE)
+
+
+def tone(curve=1, out_bits=0, src_peak=1000.0, dst_peak=100.0, unit_nits=100.0):
+    return (curve, out_bits, src_peak, dst_peak, unit_nits, 0.0)
+
+
+def alpha(mode, background=(0, 0, 0, 0), reserved=(0, 0, 0)):
+    return (mode, background, reserved)
 
 # name, families, overrides: fmt (dest families) / pfmt (planes families), dest={} (every_dest={}: of every frame), planes={}, view=, light=, ext_dst, frames=, first=,
-# picture="wide" (176 x 16, the one case a 16 x 16 picture cannot express)
+# picture="wide" (176 x 16, the one case a 16 x 16 picture cannot express); tone=, alpha=; fmt16 (the family's 16-bit _LE target), dest_fmt (the target the
+# destination is sized as, where that is not fmt), and for the stand-alone entries bits= and src_stride= (bytes added to the tight stride)
 CASES = [
-    ("ext_dst set", [n for n in EVERY if not n.startswith("pipe_")], dict(ext_dst=True)),
+    ("ext_dst set", WITH_PARAMS, dict(ext_dst=True)),
     ("unknown layout", DEST, dict(dest=dict(layout=5))),
     ("unknown dtype", DEST, dict(dest=dict(dtype=9))),
     ("planes: unknown layout", PLANES, dict(planes=dict(layout=5))),
@@ -77,7 +104,40 @@ CASES = [
     ("two faults: short len and a bad view", DEST_VIEW, dict(dest=dict(short=1), view=((10, 10, 10, 10), (5, 5), TRIANGLE))),
     ("two faults: short plane and a bad view", [n for n in PLANES if n in VIEW], dict(planes=dict(short=0), view=((10, 10, 10, 10), (5, 5), TRIANGLE))),
     ("two faults: null ptr and an unknown layout", DEST, dict(dest=dict(ptr=None, layout=5))),
-    ("two faults: ext_dst and an unknown dtype", [n for n in DEST if not n.startswith("pipe_")], dict(ext_dst=True, dest=dict(dtype=9))),
+    ("two faults: ext_dst and an unknown dtype", [n for n in DEST if n in WITH_PARAMS], dict(ext_dst=True, dest=dict(dtype=9))),
+    # the stand-alone entries' own: the source
+    ("source: stride below the bytes of a row", TENSOR, dict(src_stride=-1)),
+    ("source: 16-bit samples at an odd stride", TENSOR, dict(fmt16=True, src_stride=+1)),
+    # the tone step's own
+    ("tone: unknown curve", TONE, dict(tone=tone(curve=2))),
+    ("tone: dst_peak 0", TONE, dict(tone=tone(dst_peak=0.0))),
+    ("tone: the knee lies below black", TONE, dict(tone=tone(src_peak=10000.0, dst_peak=1.0))),
+    ("tone: out_bits 8 with HM_DEV_U16", TONE, dict(fmt=RRGGBB_LE, light=ENCODED, tone=tone(out_bits=8), dest=dict(dtype=U16))),
+    ("tone: out_bits 8 on a four-channel target", TONE, dict(fmt=RGBA, light=ENCODED, tone=tone(out_bits=8))),
+    ("alpha: out_bits 8 without a matte", ALPHA, dict(light=ENCODED, tone=tone(out_bits=8), alpha=alpha(STRAIGHT))),
+    ("tone without a light step", TONE + ALPHA, dict(light=None, tone=GOOD_TONE)),
+    ("tone: unit_nits 0 beside a transfer that is not PQ", ["tensor_tone", "tensor_alpha"], dict(light=LINEAR, tone=tone(unit_nits=0.0))),
+    ("tone: src_peak 0", ["tensor_tone", "tensor_alpha"], dict(light=LINEAR, tone=tone(src_peak=0.0))),
+    # the alpha step's own
+    ("alpha: unknown mode", ALPHA, dict(alpha=alpha(9))),
+    ("alpha: reserved not 0", ALPHA, dict(alpha=alpha(STRAIGHT, reserved=(0, 1, 0)))),
+    ("alpha: a background outside MATTE", ALPHA, dict(alpha=alpha(PREMULTIPLIED, (0, 1, 0, 0)))),
+    ("alpha: background[3]", ALPHA, dict(alpha=alpha(MATTE, (0, 0, 0, 1)), dest_fmt=RGB)),
+    ("alpha: a three-channel target", ALPHA, dict(fmt=RGB)),
+    ("alpha: a big-endian target", ALPHA, dict(fmt=RRGGBBAA_BE)),
+    ("alpha: background above 255 on RGBA", ALPHA, dict(alpha=alpha(MATTE, (0, 0, 256, 0)), dest_fmt=RGB)),
+    ("alpha: PREMULTIPLIED beside a tone step", ALPHA, dict(light=LINEAR, tone=GOOD_TONE, alpha=alpha(PREMULTIPLIED))),
+    ("alpha: PREMULTIPLIED beside a light step that re-encodes", ALPHA, dict(light=ENCODED, alpha=alpha(PREMULTIPLIED))),
+    ("alpha: a matte one byte short of the three-channel sibling", ALPHA, dict(alpha=alpha(MATTE, (1, 2, 3, 0)), dest_fmt=RGB, dest=dict(short=1))),
+    ("alpha: a 16-bit background above the peak of a 10-bit image", ["tensor_alpha"], dict(fmt16=True, bits=10, alpha=alpha(MATTE, (1024, 0, 0, 0)), dest_fmt=RRGGBB_LE)),
+    ("two faults: a bad alpha mode and an unknown dtype", ALPHA, dict(alpha=alpha(9), dest=dict(dtype=9))),
+    ("two faults: a bad tone curve and an unknown light transfer", TONE, dict(tone=tone(curve=2), light=(13, 1, 99, 0, 1.0))),
+    ("two faults: a bad view and a matte one byte short", ALPHA, dict(view=BAD_VIEW, alpha=alpha(MATTE, (1, 2, 3, 0)), dest_fmt=RGB, dest=dict(short=1))),
+    ("two faults: null ptr and a bad alpha mode", ALPHA, dict(alpha=alpha(9), dest=dict(ptr=None))),
+    ("two faults: ext_dst and a bad tone", [n for n in TONE if n in WITH_PARAMS], dict(ext_dst=True, tone=tone(curve=2))),
+    ("two faults: an odd source stride with 16-bit samples and a short len", TENSOR, dict(fmt16=True, src_stride=+1, dest=dict(short=1))),
+    # (the stand-alone entries judge the image's depth before the destination's len, the decode entries behind it)
+    ("two faults: samples of 16 bits under a light step and a short len", ["tensor_light", "tensor_tone", "tensor_alpha"], dict(fmt16=True, bits=16, light=LINEAR, dest=dict(short=1))),
 ]
 # Sent through a family, these reach the device probe (no declared-size check stands in front of it there), so what they answer
 # depends on the machine: they stay with the *_gpu tests of that family.
@@ -133,45 +193,76 @@ def make_planes(capi, L, w, h, layout=0, dtype=U8, null=None, short=None):
     return d
 
 
-def run(capi, L, data, family, over, pipelines=None):
+def make_tone(capi, t):
+    return capi.DeviceTone(t[0], t[1], t[2], t[3], t[4], t[5], (C.c_int32 * 2)(0, 0))
+
+
+def make_alpha(capi, a):
+    return capi.DeviceAlpha(a[0], (C.c_uint16 * 4)(*a[1]), (C.c_int32 * 3)(*a[2]))
+
+
+def run(capi, L, data, family, over, pipelines=None, tensor_call=None):
     """one request through one family: [status, message, failed_frame | None]"""
     fam = FAMILIES[family]
-    planes, lit = bool(fam.get("planes")), bool(fam.get("light"))
+    call, planes, with_alpha, tensor = fam["call"], bool(fam.get("planes")), bool(fam.get("alpha")), fam["call"] == "tensor"
     wide = over.get("picture") == "wide"
-    blob = data[("wide" if wide else "") + fam["call"]]
-    fmt = over.get("pfmt", 0) if planes else over.get("fmt", RGB)
+    fmt = over.get("pfmt", 0) if planes else over.get("fmt", RGBA if with_alpha else RGB)
+    if over.get("fmt16"):
+        fmt = RRGGBBAA_LE if with_alpha else RRGGBB_LE
     view = over.get("view", GOOD_VIEW) if fam.get("view") else None
-    w, h = view[1] if view and view[1] != (0, 0) and min(view[1]) > 0 else (176 if wide else 16, 16)
-    pv = C.byref(make_view(capi, view)) if view else None
-    plight = C.byref(make_light(capi, over.get("light", GOOD_LIGHT))) if lit else None
+    src_w = 176 if wide else 16
+    w, h = view[1] if view and view[1] != (0, 0) and min(view[1]) > 0 else (src_w, 16)
+    # the steps this family's entry point takes, in the order of its arguments (an alpha family: light and tone where the case names them)
+    light = over.get("light", LINEAR if tensor else GOOD_LIGHT) if fam.get("light") else over.get("light") if with_alpha else None
+    tone_ = over.get("tone", GOOD_TONE) if fam.get("tone") else over.get("tone") if with_alpha else None
+    steps = []
+    if fam.get("view"):
+        steps.append(C.byref(make_view(capi, view)) if view else None)
+    if fam.get("light") or with_alpha:
+        steps.append(C.byref(make_light(capi, light)) if light else None)
+    if fam.get("tone") or with_alpha:
+        steps.append(C.byref(make_tone(capi, tone_)) if tone_ else None)
+    if with_alpha:
+        steps.append(C.byref(make_alpha(capi, over.get("alpha", alpha(STRAIGHT)))))
     host = (C.c_uint8 * 4096)()
-    n = N_FRAMES if fam["call"] == "seq" else 1
+    n = N_FRAMES if call == "seq" else 1
     bad = 1 if n > 1 else 0  # (a sequence: the wrong destination is that of the second frame)
     if planes:
         arr = (capi.DevicePlanes * n)(*[make_planes(capi, L, w, h, **(over.get("planes", {}) if k == bad else {})) for k in range(n)])
     else:
-        good = dict(dtype=(U16 if fmt >= RRGGBB_BE else U8) if not lit else F32)
+        dest_fmt = over.get("dest_fmt", fmt)
+        good = dict(dtype=(U16 if dest_fmt >= RRGGBB_BE else U8) if not light else F32)
         good.update(over.get("every_dest", {}))
         kw = dict(good)
         kw.update(over.get("dest", {}))
-        arr = (capi.DeviceDest * n)(*[make_dest(capi, L, fmt, w, h, **(kw if k == bad else good)) for k in range(n)])
+        arr = (capi.DeviceDest * n)(*[make_dest(capi, L, dest_fmt, w, h, **(kw if k == bad else good)) for k in range(n)])
+    if tensor:  # no file: a source of src_w x 16 pixels at FAKE
+        bpp = {RGB: 3, RGBA: 4, RRGGBB_BE: 6, RRGGBBAA_BE: 8, RRGGBB_LE: 6, RRGGBBAA_LE: 8}[fmt]
+        bits = () if family in ("tensor_dest", "tensor_view") else (over.get("bits", 8 if bpp < 6 else 10),)
+        if tensor_call:  # (tools/asan/target_walk.py: the same request as plain values, for a program that makes the call itself)
+            return tensor_call(family, fmt, bits[0] if bits else 0, src_w, 16, src_w * bpp + over.get("src_stride", 0), view, light, tone_,
+                               over.get("alpha", alpha(STRAIGHT)) if with_alpha else None, arr[0])
+        fn = {"tensor_dest": L.hm_to_tensor, "tensor_view": L.hm_resample_to_tensor}.get(family) or getattr(L, "hm_" + family[len("tensor_"):] + "_to_tensor")
+        rc = fn(fmt, *bits, src_w, 16, FAKE, src_w * bpp + over.get("src_stride", 0), *steps, arr, None)
+        return [rc, L.hm_last_error().decode(), None]
+    blob = data[("wide" if wide else "") + call]
     prm = capi.DecodeParams(fmt, 1, 0, 0, None, C.cast(host, C.c_void_p) if over.get("ext_dst") else None, 4096 if over.get("ext_dst") else 0,
                             64 if over.get("ext_dst") else 0, 0, 0)
     out = (capi.Decoded * n)()
     failed = C.c_int32(SENTINEL)
-    if fam["call"] == "item":
+    kind = family.split("_", 1)[1]  # dest, view, light, tone, alpha, planes, planes_view
+    if call == "item":
         fh = C.c_void_p()
         assert L.hm_file_open(blob, len(blob), C.byref(fh)) == 0
         try:
             item = L.hm_file_primary_item(fh)
-            args = {"item_dest": (arr,), "item_view": (pv, arr), "item_light": (pv, plight, arr), "item_planes": (arr,), "item_planes_view": (pv, arr)}[family]
-            fn = getattr(L, "hm_decode_item_to_device" + ("" if family == "item_dest" else "_" + family[len("item_"):]))
-            rc = fn(fh, item, C.byref(prm), *args, out)
+            fn = getattr(L, "hm_decode_item_to_device" + ("" if kind == "dest" else "_" + kind))
+            rc = fn(fh, item, C.byref(prm), *steps, arr, out)
             msg = L.hm_last_error().decode()
         finally:
             L.hm_file_close(fh)
         return [rc, msg, None]
-    if fam["call"] == "seq":
+    if call == "seq":
         fh = C.c_void_p()
         assert L.hm_file_open(blob, len(blob), C.byref(fh)) == 0
         try:
@@ -179,8 +270,7 @@ def run(capi, L, data, family, over, pipelines=None):
             if family == "seq_dest":
                 rc = L.hm_decode_sequence_to_device(fh, over.get("first", 1), n, C.byref(prm), arr, out, C.byref(failed))
             else:
-                args = {"frames_view": (pv, arr), "frames_light": (pv, plight, arr), "frames_planes": (arr,), "frames_planes_view": (pv, arr)}[family]
-                rc = getattr(L, "hm_decode_frames_to_device_" + family[len("frames_"):])(fh, ids, n, C.byref(prm), *args, out, C.byref(failed))
+                rc = getattr(L, "hm_decode_frames_to_device_" + kind)(fh, ids, n, C.byref(prm), *steps, arr, out, C.byref(failed))
             msg = L.hm_last_error().decode()
         finally:
             L.hm_file_close(fh)
@@ -188,8 +278,7 @@ def run(capi, L, data, family, over, pipelines=None):
     p = pipelines(fmt)
     if not p:  # (the pipeline itself refuses this out_format)
         return [pipelines.refused[fmt][0], pipelines.refused[fmt][1], None]
-    args = {"pipe_dest": (arr,), "pipe_view": (pv, arr), "pipe_light": (pv, plight, arr), "pipe_planes": (arr,), "pipe_planes_view": (pv, arr)}[family]
-    rc = getattr(L, "hm_pipeline_submit_to_device" + ("" if family == "pipe_dest" else "_" + family[len("pipe_"):]))(p, blob, len(blob), 0, 1, *args)
+    rc = getattr(L, "hm_pipeline_submit_to_device" + ("" if kind == "dest" else "_" + kind))(p, blob, len(blob), 0, 1, *steps, arr)
     return [rc, L.hm_last_error().decode(), None]
 
 

@@ -1,7 +1,8 @@
 """GPU: the fields of hm_decoded (no pixels) for every picture x out_format x destination kind of tests/emit_cases.py - width,
 height, bit_depth, chroma, out_format, the nclx values, has_alpha, used_ext_dst, the strides, the plane sizes, warnings - and
 the status and message where the interface refuses the combination, against tests/golden/emit_fields.json
-(tools/record_target_goldens.py --gpu).  With them, the refusal table of tests/target_cases.py through the pipeline's submit
+(tools/record_target_goldens.py --gpu) - and the same fields through the tone and alpha steps (emit_cases.walk_steps) against
+tests/golden/emit_fields_steps.json.  With them, the refusal table of tests/target_cases.py through the pipeline's submit
 calls, which need a device to exist."""
 import json
 import os
@@ -37,6 +38,17 @@ def test_the_matrix_is_the_one_the_issue_names(recorded):
 def test_fields_of_every_decode(pkg, recorded):
     got = json.loads(json.dumps(emit_cases.walk(pkg.capi, pkg.capi.image_lib())))
     assert not differences(got, recorded["decodes"])
+
+
+def test_fields_of_every_decode_through_the_tone_and_alpha_steps(pkg):
+    with open(os.path.join(os.path.dirname(GOLDEN), "emit_fields_steps.json")) as f:
+        steps = json.load(f)
+    keys = [k.split(" | ") for k in steps]
+    assert {k[0] for k in keys} == set(emit_cases.STEP_PICTURES) and {k[2] for k in keys} == set(emit_cases.STEP_KINDS)
+    assert {k[1] for k in keys} == {"0xa", "0xb", "0xe", "0xf"}
+    assert all(any(v["status"] == 0 for k, v in steps.items() if k.endswith(kind)) for kind in emit_cases.STEP_KINDS)
+    got = json.loads(json.dumps(emit_cases.walk_steps(pkg.capi, pkg.capi.image_lib())))
+    assert not differences(got, steps)
 
 
 def test_pipeline_refusals(pkg, recorded):

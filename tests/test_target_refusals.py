@@ -21,7 +21,7 @@ def recorded():
 
 @pytest.fixture(scope="module")
 def got(pkg):
-    return target_cases.walk(pkg.capi, pkg.capi.image_lib(), ("item", "seq"))
+    return target_cases.walk(pkg.capi, pkg.capi.image_lib(), ("item", "seq", "tensor"))
 
 
 def test_every_case_is_decided_before_the_device_probe(recorded):

@@ -5,7 +5,7 @@
 224 x 224 CHW float32 slices of one T x 3 x 224 x 224 allocation, HM_VIEW_TRIANGLE and HM_VIEW_CUBIC, three ways in the same run in
 alternating rounds:
   batched     hm_decode_frames_to_device_view (one launch per resampling pass and chunk for all frames)
-  per-frame   the same call with the test hook view_batch = 0 (hm_view_write once per frame behind the one decode batch)
+  per-frame   the same call with the test hook view_batch = 0 (hm_out_write once per frame behind the one decode batch)
   items       `count` calls of hm_decode_item_to_device_view (a batch of one picture each)
 Wall clock of the call(s), and the span between two HIP events recorded on the stream in front of and behind them (the calls are
 synchronous: the span holds the host's entropy decode too).  libheif_mi355x_test.so is the library measured throughout: the
@@ -95,7 +95,7 @@ def main():
                 e1.record()
                 e1.synchronize()
                 return (time.perf_counter() - t0) * 1e3, e0.elapsed_time(e1)
-            paths = [("batched (hm_decode_frames_to_device_view)", lambda: frames_call(1)), ("per-frame hm_view_write (view_batch = 0)", lambda: frames_call(0)),
+            paths = [("batched (hm_decode_frames_to_device_view)", lambda: frames_call(1)), ("per-frame hm_out_write (view_batch = 0)", lambda: frames_call(0)),
                      (f"{n} x hm_decode_item_to_device_view", items_call)]
             results = {}
             for name, fn in paths:

@@ -1,6 +1,7 @@
 """Writes the characterisation files of the output-target plumbing from the library as it is built now:
     tests/golden/target_refusals.json   (tests/test_target_refusals.py; needs no GPU)
     tests/golden/emit_fields.json       (tests/test_emit_fields_gpu.py; --gpu, on a machine with one)
+    tests/golden/emit_fields_steps.json (the same test file and switch: the tone and alpha steps)
 Run it on a commit whose behaviour is the one to keep, then commit the files: a refactor must reproduce them byte for byte.
 
     python tools/record_target_goldens.py --record [--gpu] [--out-dir DIR]"""
@@ -32,7 +33,7 @@ def main():
     capi = g.load_package().capi
     L = capi.image_lib()
     if not args.gpu:
-        dump(os.path.join(args.out_dir, "target_refusals.json"), target_cases.walk(capi, L, ("item", "seq")))
+        dump(os.path.join(args.out_dir, "target_refusals.json"), target_cases.walk(capi, L, ("item", "seq", "tensor")))
         return
     pipes = target_cases.Pipelines(capi, L)
     try:
@@ -40,6 +41,7 @@ def main():
     finally:
         pipes.close()
     dump(os.path.join(args.out_dir, "emit_fields.json"), {"decodes": emit_cases.walk(capi, L), "pipeline_refusals": refusals})
+    dump(os.path.join(args.out_dir, "emit_fields_steps.json"), emit_cases.walk_steps(capi, L))
 
 
 if __name__ == "__main__":
