@@ -191,6 +191,25 @@ class DeviceAlpha(C.Structure):
 HM_ALPHA_STRAIGHT, HM_ALPHA_PREMULTIPLIED, HM_ALPHA_MATTE = 1, 2, 3
 
 
+class GainParams(C.Structure):
+    """hm_gain_params: the parameters of a gain map (ISO 21496-1) - headrooms, min and max are log2 values, per colour channel R, G, B"""
+    _fields_ = [("base_headroom", C.c_double), ("alternate_headroom", C.c_double), ("map_min", C.c_double * 3), ("map_max", C.c_double * 3),
+                ("gamma", C.c_double * 3), ("base_offset", C.c_double * 3), ("alternate_offset", C.c_double * 3), ("use_base_primaries", C.c_int32),
+                ("reserved", C.c_int32)]
+
+
+class GainMapInfo(C.Structure):
+    """hm_gain_map_info: a 'tmap' item's base image, gain-map image, parameters and the alternate rendition's nclx profile"""
+    _fields_ = [("base_item", C.c_uint32), ("map_item", C.c_uint32), ("params", GainParams), ("alt_has_nclx", C.c_int32), ("alt_primaries", C.c_int32),
+                ("alt_transfer", C.c_int32)]
+
+
+class DeviceGain(C.Structure):
+    """hm_device_gain: the gain step beside a light step - map_item 0: the decoded item is a 'tmap' item; else the item of the map, with
+    explicit params; headroom = log2(display peak / SDR white)"""
+    _fields_ = [("map_item", C.c_uint32), ("headroom", C.c_float), ("params", GainParams), ("reserved", C.c_int32 * 4)]
+
+
 class LightLevels(C.Structure):
     """hm_light_levels: the raw fields of an item's clli and mdcv properties"""
     _fields_ = [("has_clli", C.c_int32), ("has_mdcv", C.c_int32), ("max_content_light_level", C.c_uint16), ("max_pic_average_light_level", C.c_uint16),
@@ -203,7 +222,7 @@ class OverlayInfo(C.Structure):
     _fields_ = [("canvas_width", C.c_int32), ("canvas_height", C.c_int32), ("n_children", C.c_int32), ("background", C.c_uint16 * 4)]
 
 
-HM_ITEM_OTHER, HM_ITEM_HVC1, HM_ITEM_GRID, HM_ITEM_IDEN, HM_ITEM_IOVL = 0, 1, 2, 3, 4
+HM_ITEM_OTHER, HM_ITEM_HVC1, HM_ITEM_GRID, HM_ITEM_IDEN, HM_ITEM_IOVL, HM_ITEM_TMAP = 0, 1, 2, 3, 4, 5
 
 
 class SequenceInfo(C.Structure):
@@ -308,6 +327,17 @@ def bind_image(L):
                                                      C.POINTER(DeviceTone), C.POINTER(DeviceAlpha), C.POINTER(DeviceDest)]
     L.hm_alpha_to_tensor.argtypes = [C.c_int, C.c_int, C.c_int, C.c_int, C.c_void_p, C.c_int, C.POINTER(DeviceView), C.POINTER(DeviceLight), C.POINTER(DeviceTone),
                                      C.POINTER(DeviceAlpha), C.POINTER(DeviceDest), C.c_void_p]
+    L.hm_file_gain_map_info.argtypes = [C.c_void_p, C.c_uint32, C.POINTER(GainMapInfo)]
+    L.hm_file_gain_map_of.argtypes = [C.c_void_p, C.c_uint32]
+    L.hm_file_gain_map_of.restype = C.c_uint32
+    L.hm_file_item_aux_type.argtypes = [C.c_void_p, C.c_uint32, C.c_char_p, C.c_int]
+    L.hm_decode_item_to_device_gain.argtypes = [C.c_void_p, C.c_uint32, C.POINTER(DecodeParams), C.POINTER(DeviceView), C.POINTER(DeviceLight), C.POINTER(DeviceTone),
+                                                C.POINTER(DeviceGain), C.POINTER(DeviceDest), C.POINTER(Decoded)]
+    L.hm_pipeline_submit_to_device_gain.argtypes = [C.c_void_p, C.c_char_p, C.c_size_t, C.c_uint32, C.c_uint64, C.POINTER(DeviceView), C.POINTER(DeviceLight),
+                                                    C.POINTER(DeviceTone), C.POINTER(DeviceGain), C.POINTER(DeviceDest)]
+    L.hm_gain_to_tensor.argtypes = [C.c_int, C.c_int, C.c_int, C.c_int, C.c_void_p, C.c_int, C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_int, C.POINTER(DeviceView),
+                                    C.POINTER(DeviceLight), C.POINTER(DeviceTone), C.POINTER(DeviceGain), C.POINTER(DeviceDest), C.c_void_p]
+    L.hm_gain_table.argtypes = [C.POINTER(GainParams), C.c_float, C.c_int, C.c_int, C.POINTER(C.c_float)]
     L.hm_device_planes_bytes.argtypes = [C.c_int, C.c_int, C.c_int, C.c_int, C.POINTER(DevicePlanes), C.POINTER(C.c_int64 * 4)]
     L.hm_device_planes_bytes.restype = C.c_int64
     L.hm_planes_to_tensor.argtypes = [C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, C.POINTER(C.c_void_p * 4), C.POINTER(C.c_int32 * 4), C.POINTER(DevicePlanes),

@@ -403,29 +403,51 @@ void hm_view_scratch_free(hm_view_scratch* sc)
   sc->pinned = nullptr;
 }
 
+// the most taps an output index of an axis of n -> m has (or a negative status)
+static int axis_most_taps(int n, int m, int filt)
+{
+  int most = 0, f0;
+  for (int j = 0; j < m; j++) { const int cnt = axis_taps(n, m, filt, j, &f0, nullptr); if (cnt < 0) return cnt; most = std::max(most, cnt); }
+  return most;
+}
+// one axis' table as the kernels read it, m * (2 + taps) words at base: first[m], count[m], weights[taps][m], tap-major
+static void fill_axis(int32_t* base, int n, int m, int filt, int taps)
+{
+  float w[HM_VIEW_MAX_TAPS + 2];
+  float* wt = reinterpret_cast<float*>(base + 2 * (size_t)m);
+  for (int j = 0; j < m; j++) {
+    const int cnt = axis_taps(n, m, filt, j, &base[j], w);
+    base[m + j] = cnt;
+    for (int i = 0; i < taps; i++) wt[(size_t)i * m + j] = i < cnt ? w[i] : 0.0f;
+  }
+}
+
+// one axis of n -> m, n <= m, as 16-byte records (hm_gain_tap): the tap rule gives such an axis at most two taps per output index
+static int fill_axis_records(hm_gain_tap* rec, int n, int m, int filt)
+{
+  float w[HM_VIEW_MAX_TAPS + 2];
+  for (int j = 0; j < m; j++) {
+    int first = 0;
+    const int cnt = axis_taps(n, m, filt, j, &first, w);
+    if (cnt < 1 || cnt > 2) return hm_fail(HM_ERR_INTERNAL, "gain: %d taps at index %d of a map axis of %d -> %d", cnt, j, n, m);
+    rec[j].first = first; rec[j].count = cnt; rec[j].w0 = w[0]; rec[j].w1 = cnt > 1 ? w[1] : 0.0f;
+  }
+  return HM_OK;
+}
+
 // the tap tables of both axes of a resampled view in one pinned block (sc->pinned, `extra` bytes more behind them): first[m],
 // count[m], weights[taps][m] per axis, tap-major.  *staged: the horizontal pass may stage its source run in LDS.
 static int view_tables(const hm_view_plan* vp, size_t extra, hm_view_scratch* sc, size_t* words_x_out, size_t* words_y_out, int* tx_out, int* ty_out, bool* staged_out)
 {
   const int filt = vp->filter;
-  int tx = 0, ty = 0, f0;
-  for (int j = 0; j < vp->ow; j++) { const int cnt = axis_taps(vp->w, vp->ow, filt, j, &f0, nullptr); if (cnt < 0) return cnt; tx = std::max(tx, cnt); }
-  for (int k = 0; k < vp->oh; k++) { const int cnt = axis_taps(vp->h, vp->oh, filt, k, &f0, nullptr); if (cnt < 0) return cnt; ty = std::max(ty, cnt); }
+  const int tx = axis_most_taps(vp->w, vp->ow, filt), ty = axis_most_taps(vp->h, vp->oh, filt);
+  if (tx < 0 || ty < 0) return tx < 0 ? tx : ty;
   const size_t words_x = (size_t)vp->ow * (2 + tx), words_y = (size_t)vp->oh * (2 + ty), bytes = (words_x + words_y) * 4;
   int32_t* host = (int32_t*)hm_pool_pinned_alloc(bytes + extra);
   if (!host) return hm_fail(HM_ERR_NOMEM, "out of memory");
   sc->pinned = host;
-  float w[HM_VIEW_MAX_TAPS + 2];
-  auto fill = [&](int32_t* base, int n, int m, int taps) {
-    float* wt = reinterpret_cast<float*>(base + 2 * (size_t)m);
-    for (int j = 0; j < m; j++) {
-      const int cnt = axis_taps(n, m, filt, j, &base[j], w);
-      base[m + j] = cnt;
-      for (int i = 0; i < taps; i++) wt[(size_t)i * m + j] = i < cnt ? w[i] : 0.0f;
-    }
-  };
-  fill(host, vp->w, vp->ow, tx);
-  fill(host + words_x, vp->h, vp->oh, ty);
+  fill_axis(host, vp->w, vp->ow, filt, tx);
+  fill_axis(host + words_x, vp->h, vp->oh, filt, ty);
   // the staged horizontal pass (k_resample_h_staged) loads the run first[j0] .. first[j63] + count[j63] of a wave's 64 columns: both
   // ends must not fall as j rises, and every window must lie inside the crop
   const bool staged = (filt == HM_VIEW_CUBIC || filt == HM_VIEW_LANCZOS3) && hm_knob(HM_KNOB_VIEW_H_STAGED) != 0;
@@ -528,7 +550,7 @@ int hm_view_write_batch(int out_format, const hm_view_item* it, int n, hipStream
       hm_out_plan one; // the view alone
       std::memset(&one, 0, sizeof(one));
       one.out_format = one.dest_format = out_format; one.has_view = 1; one.vp = vp; one.dp = plans[k];
-      const int rc = hm_out_write(it[k].dest, &one, it[k].src, it[k].src_stride, s, &sc[k]);
+      const int rc = hm_out_write(it[k].dest, &one, it[k].src, it[k].src_stride, nullptr, s, &sc[k]);
       if (rc) return rc;
       continue;
     }
@@ -893,6 +915,102 @@ int hm_alpha_dest_format(int out_format, const hm_device_alpha* a, const hm_devi
   return out_format == HM_OUT_RGBA ? HM_OUT_RGB : HM_OUT_RRGGBB_LE;
 }
 
+// ---- the gain step (hm_device_gain) ------------------------------------------------------------------------------------------------
+
+int hm_gain_check(const hm_gain_params* g, float headroom, int bad)
+{
+  if (!g) return hm_fail(HM_ERR_INVALID_ARG, "null argument");
+  if (std::isnan(headroom) || headroom < 0.0f) return hm_fail(HM_ERR_INVALID_ARG, "gain: headroom %g is NaN or negative", (double)headroom);
+  if (g->reserved) return hm_fail(bad, "gain: reserved is not 0");
+  bool finite = std::isfinite(g->base_headroom) && std::isfinite(g->alternate_headroom);
+  for (int c = 0; c < 3; c++) finite = finite && std::isfinite(g->map_min[c]) && std::isfinite(g->map_max[c]) && std::isfinite(g->base_offset[c]) && std::isfinite(g->alternate_offset[c]);
+  for (int c = 0; c < 3; c++)
+    if (!std::isfinite(g->gamma[c]) || !(g->gamma[c] > 0.0)) return hm_fail(bad, "gain: gamma[%d] = %g is not finite and above 0", c, g->gamma[c]);
+  if (!finite) return hm_fail(bad, "gain: a parameter is not finite");
+  if (g->alternate_headroom == g->base_headroom) return hm_fail(bad, "gain: alternate_headroom == base_headroom (%g): the map has no weight", g->base_headroom);
+  return HM_OK;
+}
+
+double hm_gain_weight(const hm_gain_params* g, float headroom)
+{
+  const double w = ((double)headroom - g->base_headroom) / (g->alternate_headroom - g->base_headroom);
+  return std::min(std::max(w, 0.0), 1.0);
+}
+
+// one table and one M serve the three colour channels
+static bool gain_one_channel(const hm_gain_params* g)
+{
+  for (int c = 1; c < 3; c++)
+    if (g->map_min[c] != g->map_min[0] || g->map_max[c] != g->map_max[0] || g->gamma[c] != g->gamma[0] || g->base_offset[c] != g->base_offset[0] ||
+        g->alternate_offset[c] != g->alternate_offset[0]) return false;
+  return true;
+}
+
+// tab_c of include/heif_mi355x.h: 1 << bits entries
+static void fill_gain_table(const hm_gain_params* g, double wgt, int c, int bits, float* out)
+{
+  const int n = 1 << bits;
+  const double mpeak = (double)(n - 1), lo = g->map_min[c], span = g->map_max[c] - g->map_min[c], gamma = g->gamma[c];
+  for (int v = 0; v < n; v++) {
+    double u = (double)v / mpeak;
+    if (gamma != 1.0) u = std::pow(u, 1.0 / gamma);
+    out[v] = (float)std::exp2(wgt * (lo + span * u));
+  }
+}
+
+int hm_gain_table(const hm_gain_params* params, float headroom, int channel, int map_bits, float* out)
+{
+  if (!params || !out) return hm_fail(HM_ERR_INVALID_ARG, "null argument");
+  if (channel < 0 || channel > 2) return hm_fail(HM_ERR_INVALID_ARG, "gain: channel %d is not 0 .. 2", channel);
+  if (map_bits < 8 || map_bits > HM_GAIN_MAX_BITS) return hm_fail(HM_ERR_UNSUPPORTED, "gain: a map of %d bits (8 .. %d are supported)", map_bits, (int)HM_GAIN_MAX_BITS);
+  const int rc = hm_gain_check(params, headroom, HM_ERR_INVALID_ARG);
+  if (rc) return rc;
+  fill_gain_table(params, hm_gain_weight(params, headroom), channel, map_bits, out);
+  return 1 << map_bits;
+}
+
+// the step's own refusals that need nothing but the request
+static int gain_check(const hm_out_steps* st)
+{
+  const hm_device_gain* g = st->gain;
+  if (!st->light) return hm_fail(HM_ERR_INVALID_ARG, "gain: null light step");
+  if (g->reserved[0] || g->reserved[1] || g->reserved[2] || g->reserved[3]) return hm_fail(HM_ERR_INVALID_ARG, "gain: reserved is not 0");
+  const int rc = hm_gain_check(&g->params, g->headroom, HM_ERR_INVALID_ARG);
+  if (rc) return rc;
+  if (st->alpha) return hm_fail(HM_ERR_UNSUPPORTED, "gain: an alpha step beside the gain step is not supported (the open step)");
+  return HM_OK;
+}
+
+// the gain step into the plan: the weight and the offsets (lp: the light plan beside it), and - once the map's size is known - the geometry
+static int gain_plan_of(const hm_device_gain* g, const hm_out_image* img, const hm_view_plan* vp, const hm_light_plan* lp, hm_gain_plan* gp)
+{
+  std::memset(gp, 0, sizeof(*gp));
+  gp->params = g->params; gp->headroom = g->headroom;
+  gp->active = hm_gain_weight(&g->params, g->headroom) != 0.0;
+  gp->nch = gain_one_channel(&g->params) ? 1 : 3;
+  for (int c = 0; c < 3; c++) { gp->kb[c] = (float)((double)lp->gain * g->params.base_offset[c]); gp->ka[c] = (float)((double)lp->gain * g->params.alternate_offset[c]); }
+  if (img->map_w == 0 && img->map_h == 0) return HM_OK;
+  return hm_gain_geometry(img->w, img->h, img->map_w, img->map_h, img->map_bits, vp, gp);
+}
+
+int hm_gain_geometry(int W, int H, int MW, int MH, int map_bits, const hm_view_plan* vp, hm_gain_plan* gp)
+{
+  gp->filter = !vp->crop_only && vp->filter == HM_VIEW_NEAREST ? HM_VIEW_NEAREST : HM_VIEW_TRIANGLE;
+  if (MW < 1 || MH < 1 || MW > W || MH > H) return hm_fail(HM_ERR_UNSUPPORTED, "gain: a %d x %d map for a %d x %d base image is not supported", MW, MH, W, H);
+  const int sx = (int)(((int64_t)W + MW - 1) / MW), sy = (int)(((int64_t)H + MH - 1) / MH); // (sizes as a file declares them: up to 2^31 - 1)
+  if (MW != ((int64_t)W + sx - 1) / sx || MH != ((int64_t)H + sy - 1) / sy)
+    return hm_fail(HM_ERR_UNSUPPORTED, "gain: a %d x %d map for a %d x %d base image is not supported (no whole factor per axis gives that size)", MW, MH, W, H);
+  if (map_bits < 8 || map_bits > HM_GAIN_MAX_BITS)
+    return hm_fail(HM_ERR_UNSUPPORTED, "gain: a map of %d bits is not supported (8 .. %d are; deeper maps are the open step)", map_bits, (int)HM_GAIN_MAX_BITS);
+  if (vp->x % sx) return hm_fail(HM_ERR_INVALID_ARG, "gain: crop_x %d is no multiple of %d, the map has one column for %d of the base", vp->x, sx, sx);
+  if (vp->y % sy) return hm_fail(HM_ERR_INVALID_ARG, "gain: crop_y %d is no multiple of %d, the map has one row for %d of the base", vp->y, sy, sy);
+  gp->map_w = MW; gp->map_h = MH; gp->map_bits = map_bits; gp->sx = sx; gp->sy = sy;
+  gp->mx = vp->x / sx; gp->my = vp->y / sy; gp->mw = (int)(((int64_t)vp->w + sx - 1) / sx); gp->mh = (int)(((int64_t)vp->h + sy - 1) / sy);
+  int rc;
+  if ((rc = check_axis(gp->mw, vp->ow, gp->filter, "map width")) || (rc = check_axis(gp->mh, vp->oh, gp->filter, "map height"))) return rc;
+  return HM_OK;
+}
+
 // ---- the device write: one request (hm_out_steps), one plan (hm_out_plan), one writer --------------------------------------------
 
 int hm_out_dest_format(int out_format, const hm_out_steps* st)
@@ -909,6 +1027,7 @@ int hm_out_check_static(int out_format, const hm_device_dest* d, const hm_out_st
   if (dest_format < 0) return dest_format;
   if (!d) return hm_fail(HM_ERR_INVALID_ARG, "null device destination");
   if (tone && !l) return hm_fail(HM_ERR_INVALID_ARG, "tone: null light step");
+  if (st->gain) { const int rc = gain_check(st); if (rc) return rc; }
   if (a && a->mode == HM_ALPHA_PREMULTIPLIED && l && l->to_transfer != HM_LIGHT_LINEAR)
     return hm_fail(HM_ERR_INVALID_ARG, "alpha: HM_ALPHA_PREMULTIPLIED beside a light step that re-encodes (transfer %d; encoded premultiplied light is not a defined result)", l->to_transfer);
   if (tone) {
@@ -943,7 +1062,8 @@ static int out_resolve_profile(int out_format, const hm_out_image* img, const hm
   }
   if (!st->light) return HM_OK;
   if ((rc = light_plan_of(out_format, bits, img->transfer, img->primaries, st->light, &p->lp))) return rc;
-  return st->tone ? tone_plan_of(st->tone, &p->lp) : (int)HM_OK;
+  if (st->tone && (rc = tone_plan_of(st->tone, &p->lp))) return rc;
+  return st->gain ? gain_plan_of(st->gain, img, &p->vp, &p->lp, &p->gp) : (int)HM_OK;
 }
 
 int hm_out_resolve(int out_format, const hm_out_image* img, int know_profile, const hm_device_dest* d, const hm_out_steps* st, hm_out_plan* p)
@@ -951,7 +1071,7 @@ int hm_out_resolve(int out_format, const hm_out_image* img, int know_profile, co
   int rc;
   std::memset(p, 0, sizeof(*p));
   p->out_format = out_format; p->w = img->w; p->h = img->h;
-  p->has_view = st->view != nullptr; p->has_light = st->light != nullptr; p->has_alpha = st->alpha != nullptr;
+  p->has_view = st->view != nullptr; p->has_light = st->light != nullptr; p->has_alpha = st->alpha != nullptr; p->has_gain = st->gain != nullptr;
   if (st->view) { if ((rc = hm_view_resolve(out_format, img->w, img->h, st->view, &p->vp))) return rc; }
   else { p->vp.w = p->vp.ow = img->w; p->vp.h = p->vp.oh = img->h; p->vp.crop_only = 1; }
   if (know_profile == HM_OUT_PROFILE_FIRST && (rc = out_resolve_profile(out_format, img, d, st, p))) return rc;
@@ -961,7 +1081,81 @@ int hm_out_resolve(int out_format, const hm_out_image* img, int know_profile, co
   return HM_OK;
 }
 
-int hm_out_write(const hm_device_dest* d, const hm_out_plan* p, const void* src, int src_stride, hipStream_t s, hm_view_scratch* sc)
+// The write under an active gain step (light beside it, no alpha): ONE pinned block and one upload - the base's tap tables (summed),
+// the light tables, the gain tables, the map's tap tables (pointwise, summed) -, one device block for the intermediates of a summed
+// view: the base's horizontal pass, the map's, and the M planes.
+static int gain_write(const hm_device_dest* d, const hm_out_plan* p, const uint8_t* origin, int src_stride, int src_bytes, const hm_out_map* map, hipStream_t s,
+                      hm_view_scratch* sc)
+{
+  const hm_view_plan* vp = &p->vp;
+  const hm_dest_plan& dp = p->dp;
+  const hm_gain_plan& gp = p->gp;
+  const bool summed = !vp->crop_only && vp->filter != HM_VIEW_NEAREST, nearest = !vp->crop_only && !summed;
+  if (!map || !map->plane || gp.map_w <= 0) return hm_fail(HM_ERR_INTERNAL, "gain: no map for the write");
+  if (!p->has_light || p->has_alpha) return hm_fail(HM_ERR_INTERNAL, "gain: light%s alpha%s", p->has_light ? "+" : "-", p->has_alpha ? "+" : "-");
+  const int map_bytes = gp.map_bits > 8 ? 2 : 1;
+  if ((int64_t)map->stride < (int64_t)gp.map_w * map_bytes) return hm_fail(HM_ERR_INVALID_ARG, "gain: map_stride %d below the bytes of a row", map->stride);
+  const LightTables T(&p->lp);
+  const size_t table_bytes = T.bytes(), gain_floats = (size_t)gp.nch << gp.map_bits;
+  int mtx = 0, mty = 0, rc;
+  if (summed && ((mtx = axis_most_taps(gp.mw, vp->ow, gp.filter)) < 0 || (mty = axis_most_taps(gp.mh, vp->oh, gp.filter)) < 0)) return mtx < 0 ? mtx : mty;
+  // the map's taps: tables like the base's (summed), 16-byte records per output index (pointwise: the map is enlarged), none (nearest)
+  const size_t mwords_x = nearest ? 0 : summed ? (size_t)vp->ow * (2 + mtx) : (size_t)vp->ow * 4, mwords_y = nearest ? 0 : summed ? (size_t)vp->oh * (2 + mty) : (size_t)vp->oh * 4;
+  const size_t extra = table_bytes + (gain_floats + mwords_x + mwords_y) * 4;
+  size_t words_x = 0, words_y = 0;
+  int tx = 0, ty = 0;
+  bool staged = false;
+  if (!sc || sc->pinned || sc->dev[0] || sc->dev[1]) return hm_fail(HM_ERR_INTERNAL, "device write: no free scratch for the tables");
+  if (summed) { if ((rc = view_tables(vp, extra, sc, &words_x, &words_y, &tx, &ty, &staged))) return rc; }
+  else if (!(sc->pinned = hm_pool_pinned_alloc(extra))) return hm_fail(HM_ERR_NOMEM, "out of memory");
+  const size_t tap_bytes = (words_x + words_y) * 4, bytes = tap_bytes + extra;
+  float* host_tables = reinterpret_cast<float*>((uint8_t*)sc->pinned + tap_bytes);
+  float* host_gain = host_tables + table_bytes / 4;
+  int32_t* host_mx = reinterpret_cast<int32_t*>(host_gain + gain_floats);
+  T.fill(host_tables);
+  const double wgt = hm_gain_weight(&gp.params, gp.headroom);
+  for (int c = 0; c < gp.nch; c++) fill_gain_table(&gp.params, wgt, c, gp.map_bits, host_gain + ((size_t)c << gp.map_bits));
+  if (summed) { fill_axis(host_mx, gp.mw, vp->ow, gp.filter, mtx); fill_axis(host_mx + mwords_x, gp.mh, vp->oh, gp.filter, mty); }
+  else if (!nearest && ((rc = fill_axis_records(reinterpret_cast<hm_gain_tap*>(host_mx), gp.mw, vp->ow, gp.filter)) ||
+                        (rc = fill_axis_records(reinterpret_cast<hm_gain_tap*>(host_mx + mwords_x), gp.mh, vp->oh, gp.filter)))) return rc;
+  if (!(sc->dev[0] = hm_pool_device_alloc(bytes))) return HM_ERR_NO_DEVICE;
+  hm_light_args la = T.args(src_bytes);
+  hm_gain_args ga;
+  hm_resample_args r;
+  std::memset(&ga, 0, sizeof(ga));
+  std::memset(&r, 0, sizeof(r));
+  ga.pitch = ((int64_t)vp->ow + 15) / 16 * 16;
+  if (summed) {
+    r = resample_args_of(vp, src_bytes, origin, src_stride, sc->dev[0], words_x, tx, ty, dp);
+    const size_t base_floats = resample_tmp_floats(r, dp), mtmp_floats = (size_t)ga.pitch * gp.mh * gp.nch, M_floats = (size_t)ga.pitch * vp->oh * gp.nch;
+    if (!(sc->dev[1] = hm_pool_device_alloc((base_floats + mtmp_floats + M_floats) * sizeof(float)))) return HM_ERR_NO_DEVICE;
+    r.tmp = (float*)sc->dev[1];
+    ga.mtmp = r.tmp + base_floats; ga.M = ga.mtmp + mtmp_floats;
+  }
+  if ((rc = hm_check_hip(hipMemcpyAsync(sc->dev[0], sc->pinned, bytes, hipMemcpyHostToDevice, s), "upload of the tap, light and gain tables"))) return rc;
+  const float* dev_tables = reinterpret_cast<const float*>((const uint8_t*)sc->dev[0] + tap_bytes);
+  T.point(&la, dev_tables);
+  ga.tab = dev_tables + table_bytes / 4;
+  ga.nch = gp.nch; ga.map_bits = gp.map_bits; ga.map_bytes = map_bytes;
+  for (int c = 0; c < 3; c++) { ga.kb[c] = gp.kb[c]; ga.ka[c] = gp.ka[c]; }
+  ga.map = (const uint8_t*)map->plane + (size_t)gp.my * map->stride + (size_t)gp.mx * map_bytes;
+  ga.map_stride = map->stride; ga.mw = gp.mw; ga.mh = gp.mh;
+  if (!summed && !nearest) { // (the records sit 16-byte aligned: the tables before them are multiples of 1 KB, no base taps are uploaded)
+    ga.xrec = reinterpret_cast<const hm_gain_tap*>(ga.tab + gain_floats); ga.yrec = ga.xrec + vp->ow;
+    ga.ax.m = vp->ow; ga.ay.m = vp->oh;
+  }
+  if (summed) {
+    const int32_t* dx = reinterpret_cast<const int32_t*>(ga.tab + gain_floats);
+    const int32_t* dy = dx + mwords_x;
+    ga.ax.first = dx; ga.ax.count = dx + vp->ow; ga.ax.weights = reinterpret_cast<const float*>(dx + 2 * (size_t)vp->ow); ga.ax.m = vp->ow; ga.ax.taps = mtx;
+    ga.ay.first = dy; ga.ay.count = dy + vp->oh; ga.ay.weights = reinterpret_cast<const float*>(dy + 2 * (size_t)vp->oh); ga.ay.m = vp->oh; ga.ay.taps = mty;
+  }
+  if (summed) return hm_launch_gain_resample(&dp, &la, &ga, &r, d->ptr, d->scale, d->bias, s);
+  if (nearest) return hm_launch_gain_nearest(&dp, &la, &ga, origin, src_stride, vp->w, vp->h, vp->ow, vp->oh, d->ptr, d->scale, d->bias, s);
+  return hm_launch_gain_tensor(&dp, &la, &ga, origin, src_stride, vp->w, vp->h, d->ptr, d->scale, d->bias, s);
+}
+
+int hm_out_write(const hm_device_dest* d, const hm_out_plan* p, const void* src, int src_stride, const hm_out_map* map, hipStream_t s, hm_view_scratch* sc)
 {
   const hm_view_plan* vp = &p->vp;
   const hm_dest_plan& dp = p->dp;
@@ -975,6 +1169,7 @@ int hm_out_write(const hm_device_dest* d, const hm_out_plan* p, const void* src,
   const int obpp = hm_out_bytes_per_pixel(p->out_format), src_bytes = obpp >= 6 ? 2 : 1;
   if (alpha && obpp != 4 && obpp != 8) return hm_fail(HM_ERR_INTERNAL, "alpha: output format %d has no four channels", p->out_format);
   const uint8_t* origin = (const uint8_t*)src + (size_t)vp->y * src_stride + (size_t)vp->x * obpp;
+  if (p->has_gain && p->gp.active) return gain_write(d, p, origin, src_stride, src_bytes, map, s, sc); // (a gain step of weight 0: the write without it)
   if (!step && vp->crop_only) // the rectangle's bytes: the 2-D copy or k_to_tensor on the offset source
     return hm_dest_write(d, p->out_format, vp->w, vp->h, 0, vp->h, origin, src_stride, s);
   const LightTables T(lp);
@@ -1029,21 +1224,36 @@ int hm_out_write(const hm_device_dest* d, const hm_out_plan* p, const void* src,
 // ---- the stand-alone entries: pixels that are in device memory already, through the same plan and writer ---------------------------
 
 // size_prefix: of the message about a wrong width or height (hm_to_tensor's speaks of the destination)
+// map, map_w, map_h, map_bits: the gain map of a gain step (hm_gain_to_tensor), else NULL and 0
 static int out_to_tensor(int out_format, int bits, int w, int h, const void* src, int src_stride, const hm_out_steps& st, const hm_device_dest* dest, void* stream,
-                         const char* size_prefix = "")
+                         const char* size_prefix = "", const hm_out_map* map = nullptr, int map_w = 0, int map_h = 0, int map_bits = 0)
 {
   int rc = hm_out_check_static(out_format, dest, &st, 1);
   if (rc || (rc = check_image_size(size_prefix, w, h))) return rc;
-  const hm_out_image img = {w, h, bits, st.light ? st.light->from_transfer : 0, st.light ? st.light->from_primaries : 0};
+  if (map && (rc = check_image_size("gain map: ", map_w, map_h))) return rc;
+  const hm_out_image img = {w, h, bits, st.light ? st.light->from_transfer : 0, st.light ? st.light->from_primaries : 0, map_w, map_h, map_bits};
   hm_out_plan p;
   if ((rc = hm_out_resolve(out_format, &img, HM_OUT_PROFILE_FIRST, dest, &st, &p))) return rc;
   const int obpp = hm_out_bytes_per_pixel(out_format);
   if (src_stride < w * obpp) return hm_fail(HM_ERR_INVALID_ARG, "src_stride %d below the bytes of a row", src_stride);
   if (obpp >= 6 && (((uintptr_t)src | (unsigned)src_stride) & 1)) return hm_fail(HM_ERR_INVALID_ARG, "16-bit samples at an odd address or stride");
+  if (map) {
+    if (map->stride < map_w * (map_bits > 8 ? 2 : 1)) return hm_fail(HM_ERR_INVALID_ARG, "gain: map_stride %d below the bytes of a row", map->stride);
+    if (map_bits > 8 && (((uintptr_t)map->plane | (unsigned)map->stride) & 1)) return hm_fail(HM_ERR_INVALID_ARG, "gain: 16-bit map samples at an odd address or stride");
+  }
   int n_dev = 0;
   if (hipGetDeviceCount(&n_dev) != hipSuccess || n_dev == 0) { (void)hipGetLastError(); return hm_fail(HM_ERR_NO_DEVICE, "no HIP device available"); }
   if ((rc = hm_dest_check_pointer(dest))) return rc;
-  return with_scratch((hipStream_t)stream, [&](hm_view_scratch* sc) { return hm_out_write(dest, &p, src, src_stride, (hipStream_t)stream, sc); });
+  return with_scratch((hipStream_t)stream, [&](hm_view_scratch* sc) { return hm_out_write(dest, &p, src, src_stride, map, (hipStream_t)stream, sc); });
+}
+
+int hm_gain_to_tensor(int out_format, int bits, int src_w, int src_h, const void* d_src, int src_stride, const void* d_map, int map_stride, int map_w, int map_h,
+                      int map_bits, const hm_device_view* view, const hm_device_light* light, const hm_device_tone* tone, const hm_device_gain* gain,
+                      const hm_device_dest* dest, void* stream)
+{
+  if (!d_src || !d_map || !dest || !gain) return hm_fail(HM_ERR_INVALID_ARG, "null argument");
+  const hm_out_map map = {d_map, map_stride};
+  return out_to_tensor(out_format, bits, src_w, src_h, d_src, src_stride, hm_out_steps{view, light, tone, nullptr, gain}, dest, stream, "", &map, map_w, map_h, map_bits);
 }
 
 int hm_to_tensor(int out_format, int width, int height, const void* d_src, int src_stride, const hm_device_dest* dest, void* stream)

@@ -108,8 +108,11 @@ std::vector<uint32_t> HeifFile::top_level_images() const
     bool sub = false;
     for (const Ref& r : refs_) {
       if ((r.type == "thmb" || r.type == "auxl") && r.from == it.id) sub = true;
-      if (r.type == "dimg")
+      if (r.type == "dimg") {
+        const Item* from = item(r.from);
+        if (from && from->type == "tmap") continue; // (base and gain map of a 'tmap' item stay images of their own)
         for (uint32_t t : r.to) if (t == it.id) sub = true;
+      }
     }
     if (!sub && !it.hidden) out.push_back(it.id);
   }
@@ -438,6 +441,66 @@ uint32_t HeifFile::derived_child(uint32_t id, HeifError& err) const
   if (r.size() != 1) { err = {HM_ERR_BITSTREAM, "'iden' image with more than one reference image"}; return 0; } // context.cc:2558-2562 (also: none)
   if (r[0] == id) { err = {HM_ERR_BITSTREAM, "'iden' image referring to itself"}; return 0; }
   return r[0];
+}
+
+bool HeifFile::gain_map_info(uint32_t id, GainMapInfo& g, HeifError& err) const
+{
+  const Item* it = item(id);
+  if (!it || it->type != "tmap") { err = {HM_ERR_INVALID_ARG, "item is not a 'tmap' item"}; return false; }
+  const std::vector<uint32_t> r = references(id, "dimg");
+  if (r.size() != 2) { err = {HM_ERR_BITSTREAM, "'tmap' item with " + std::to_string(r.size()) + " 'dimg' references, not 2 (base image, gain map)"}; return false; }
+  if (r[0] == id || r[1] == id || r[0] == r[1]) { err = {HM_ERR_BITSTREAM, "'tmap' item whose references are not two other items"}; return false; }
+  for (uint32_t to : r)
+    if (!item(to)) { err = {HM_ERR_BITSTREAM, "'tmap' item references the missing item " + std::to_string(to)}; return false; }
+  g = GainMapInfo();
+  g.base = r[0]; g.map = r[1];
+  std::vector<uint8_t> d;
+  if (!item_data(id, d, err)) return false;
+  Rd rd(d.data(), d.size());
+  const unsigned version = (unsigned)rd.u(1);
+  if (rd.ok && version != 0) { err = {HM_ERR_UNSUPPORTED, "'tmap' version " + std::to_string(version) + " is not supported"}; return false; }
+  const unsigned minimum = (unsigned)rd.u(2);
+  if (rd.ok && minimum != 0) { err = {HM_ERR_UNSUPPORTED, "'tmap' minimum_version " + std::to_string(minimum) + " is not supported"}; return false; }
+  g.writer_version = (int)rd.u(2);
+  const unsigned flags = (unsigned)rd.u(1);
+  g.multichannel = (flags & 0x80) != 0;
+  g.use_base_colour_space = (flags & 0x40) != 0;
+  bool zero_den = false;
+  auto fraction = [&](bool is_signed) {
+    const uint32_t n = (uint32_t)rd.u(4), den = (uint32_t)rd.u(4);
+    if (den == 0) { zero_den = true; return 0.0; }
+    return (is_signed ? (double)(int32_t)n : (double)n) / (double)den;
+  };
+  g.base_headroom = fraction(false);
+  g.alternate_headroom = fraction(false);
+  const int channels = g.multichannel ? 3 : 1;
+  for (int c = 0; c < channels; c++) {
+    g.map_min[c] = fraction(true);
+    g.map_max[c] = fraction(true);
+    g.gamma[c] = fraction(false);
+    g.base_offset[c] = fraction(true);
+    g.alternate_offset[c] = fraction(true);
+  }
+  if (!rd.ok) { err = {HM_ERR_BITSTREAM, "'tmap' payload of " + std::to_string(d.size()) + " bytes is truncated"}; return false; }
+  if (zero_den) { err = {HM_ERR_BITSTREAM, "'tmap' payload with a zero denominator"}; return false; }
+  for (int c = 0; c < channels; c++)
+    if (g.gamma[c] == 0.0) { err = {HM_ERR_BITSTREAM, "'tmap' payload with a zero gamma"}; return false; }
+  for (int c = channels; c < 3; c++) {
+    g.map_min[c] = g.map_min[0]; g.map_max[c] = g.map_max[0]; g.gamma[c] = g.gamma[0];
+    g.base_offset[c] = g.base_offset[0]; g.alternate_offset[c] = g.alternate_offset[0];
+  }
+  return true;
+}
+
+uint32_t HeifFile::gain_map_of(uint32_t base) const
+{
+  if (movie_mode_) return 0;
+  for (const auto& kv : items_) {
+    if (kv.second.type != "tmap") continue;
+    const std::vector<uint32_t> r = references(kv.first, "dimg");
+    if (!r.empty() && r[0] == base) return kv.first;
+  }
+  return 0;
 }
 
 // ---- the fork's movie mode ---------------------------------------------------------------------------------------

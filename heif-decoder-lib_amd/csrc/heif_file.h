@@ -1,7 +1,8 @@
 // heif_file.h — minimal ISOBMFF / HEIF reader for the decode path (host side).
 // Counterpart of the parts of libheif/file.cc, box.cc and codecs/hevc.cc the hot path needs:
 // item locations (iloc), item infos (iinf), references (iref: dimg/auxl/thmb), properties
-// (ipco/ipma: hvcC, ispe, pixi, colr, irot, imir, clap, auxC, clli, mdcv), primary item (pitm), idat.
+// (ipco/ipma: hvcC, ispe, pixi, colr, irot, imir, clap, auxC, clli, mdcv), primary item (pitm), idat, and the payload of a 'tmap'
+// item (ISO 21496-1 gain map: include/heif_mi355x.h states its layout).
 // Movie mode (the fork's image sequences): a 'moov' track of HEVC-intra samples, each sample a top-level image
 // (file.cc:474-483, 1154-1244; context.cc:646-700 of the reference).
 #ifndef HM_HEIF_FILE_H
@@ -87,6 +88,15 @@ struct OverlayInfo {
   std::vector<int32_t> dx, dy;
 };
 
+// 'tmap' payload + 'dimg' references (include/heif_mi355x.h states the layout): every fraction as numerator / denominator in double
+struct GainMapInfo {
+  uint32_t base = 0, map = 0; // dimg [0], [1]
+  int writer_version = 0;
+  bool multichannel = false, use_base_colour_space = false;
+  double base_headroom = 0, alternate_headroom = 0;
+  double map_min[3] = {0, 0, 0}, map_max[3] = {0, 0, 0}, gamma[3] = {1, 1, 1}, base_offset[3] = {0, 0, 0}, alternate_offset[3] = {0, 0, 0};
+};
+
 // The fork's movie mode: ftyp lists the compatible brand 'hevc' or 'hevx' and a 'moov' box exists; 'meta' is then
 // ignored.  Every sample of the (first) track is an image: IDs 1..frame_count, ID 1 the primary one.
 struct Movie {
@@ -124,6 +134,10 @@ class HeifFile {
   // the auxiliary image that is the alpha channel of image `id` (0 if none): an 'auxl' reference to `id` from an item
   // whose auxC names an alpha type (context.cc:885-945)
   uint32_t alpha_item_of(uint32_t id) const;
+  // a 'tmap' item: its two 'dimg' references and its payload
+  bool gain_map_info(uint32_t id, GainMapInfo& g, HeifError& err) const;
+  // the first 'tmap' item whose first 'dimg' reference is `base` (0 if none)
+  uint32_t gain_map_of(uint32_t base) const;
   bool is_movie() const { return movie_mode_; }
   const Movie& movie() const { return movie_; }
 

@@ -171,17 +171,66 @@ int hm_launch_alpha_nearest(const hm_dest_plan* p, const hm_light_args* la, cons
 int hm_launch_alpha_resample(const hm_dest_plan* p, const hm_light_args* la, const hm_alpha_args* aa, const hm_resample_args* r, void* dst, const float scale[4],
                              const float bias[4], hipStream_t s);
 
-// ---- the device write: the interleaved pixels of one image through the steps of a request - view, light (with tone inside it), alpha -
-//      into a hm_device_dest.  One request (hm_out_steps), one plan (hm_out_plan), one writer (hm_out_write); a further step is a case
-//      inside them ----
-typedef struct hm_out_steps { const hm_device_view* view; const hm_device_light* light; const hm_device_tone* tone; const hm_device_alpha* alpha; } hm_out_steps; // any may be NULL
-typedef struct hm_out_image { int32_t w, h, bits, transfer, primaries; } hm_out_image; // what the image reports (hm_decoded)
+// ---- the gain step (hm_device_gain) beside the light step: a gain map's samples through a table, summed under the map's own taps,
+//      times the base's linear light.  devdest.cpp holds the tables, the geometry, the checks and the write step, gain.hip the kernels ----
+enum { HM_GAIN_MAX_BITS = 12 };
+typedef struct hm_gain_plan {
+  int32_t active;        // wgt != 0: the map is read.  0: the write is the one without the step
+  int32_t nch;           // 1: one table and one M for the three colour channels; 3: one each
+  int32_t map_w, map_h, map_bits;
+  int32_t sx, sy;        // the geometry's factors
+  int32_t mx, my, mw, mh; // the map's crop
+  int32_t filter;        // of the map's taps: HM_VIEW_TRIANGLE, or HM_VIEW_NEAREST under a nearest view
+  float headroom;
+  float kb[3], ka[3];
+  hm_gain_params params;
+} hm_gain_plan;
+// wgt of include/heif_mi355x.h; the parameters have passed hm_gain_check
+double hm_gain_weight(const hm_gain_params* g, float headroom);
+// the step's own refusals of headroom and parameters; bad: the status of a bad parameter (HM_ERR_INVALID_ARG, a 'tmap' payload's: HM_ERR_BITSTREAM)
+int hm_gain_check(const hm_gain_params* g, float headroom, int bad);
+// the geometry of include/heif_mi355x.h into gp (sx, sy, the map's crop, the filter of its taps): a W x H base under the resolved view
+// vp, an MW x MH map of map_bits bits; every refusal of the geometry and of the map's depth
+int hm_gain_geometry(int W, int H, int MW, int MH, int map_bits, const hm_view_plan* vp, hm_gain_plan* gp);
+// one output index of a map axis in the pointwise path, where the map is enlarged (n <= m: at most two taps): 16 bytes, one load
+typedef struct hm_gain_tap { int32_t first, count; float w0, w1; } hm_gain_tap; // (w1 = 0 where count is 1)
+// The map as the kernels see it (device pointers).  Pointwise: xrec[ow] and yrec[oh], M formed in the kernel.  Nearest: the map's crop
+// alone.  Summed: the taps of both map axes, mtmp[nch planes][mh rows] and M[nch planes][oh rows] of ow floats, rows of `pitch` elements.
+typedef struct hm_gain_args {
+  const float* tab;                       // nch tables of 1 << map_bits entries, one behind the other
+  int32_t nch, map_bits, map_bytes;
+  float kb[3], ka[3];
+  const void* map; int32_t map_stride;    // at the map crop's origin
+  int32_t mw, mh;                         // the map's crop
+  hm_view_axis ax, ay;                    // the map's taps: mw -> ow, mh -> oh (summed; pointwise: m alone)
+  const hm_gain_tap* xrec; const hm_gain_tap* yrec; // (pointwise) 16-byte aligned
+  float* mtmp; float* M; int64_t pitch;   // (summed)
+} hm_gain_args;
+int hm_launch_gain_tensor(const hm_dest_plan* p, const hm_light_args* la, const hm_gain_args* ga, const void* src, int src_stride, int w, int rows, void* dst,
+                          const float scale[4], const float bias[4], hipStream_t s);
+int hm_launch_gain_nearest(const hm_dest_plan* p, const hm_light_args* la, const hm_gain_args* ga, const void* src, int src_stride, int n_w, int n_h, int ow, int oh,
+                           void* dst, const float scale[4], const float bias[4], hipStream_t s);
+// the map's two passes into M, the base's horizontal pass (hm_launch_light_h: k_light_h), then the vertical pass that applies the update
+int hm_launch_gain_resample(const hm_dest_plan* p, const hm_light_args* la, const hm_gain_args* ga, const hm_resample_args* r, void* dst, const float scale[4],
+                            const float bias[4], hipStream_t s);
+// k_light_h alone: the horizontal pass of hm_launch_light_resample (light.hip)
+int hm_launch_light_h(const hm_dest_plan* p, const hm_light_args* la, const hm_resample_args* r, hipStream_t s);
+
+// ---- the device write: the interleaved pixels of one image through the steps of a request - view, light (with tone inside it), alpha,
+//      gain - into a hm_device_dest.  One request (hm_out_steps), one plan (hm_out_plan), one writer (hm_out_write); a further step is
+//      a case inside them ----
+typedef struct hm_out_steps { const hm_device_view* view; const hm_device_light* light; const hm_device_tone* tone; const hm_device_alpha* alpha; const hm_device_gain* gain; } hm_out_steps; // any may be NULL
+// what the image reports (hm_decoded); with a gain step the map beside it (map_w 0: not known yet - the step's geometry is not judged)
+typedef struct hm_out_image { int32_t w, h, bits, transfer, primaries; int32_t map_w, map_h, map_bits; } hm_out_image;
+// the gain map's samples on the device (one channel; one byte per sample at 8 bits, else two), row 0 = the map's row 0
+typedef struct hm_out_map { const void* plane; int32_t stride; } hm_out_map;
 typedef struct hm_out_plan {
   int32_t out_format, dest_format; // the source's target; the target the destination is judged, sized and written as
   int32_t w, h;                    // the source image
-  int32_t has_view, has_light, has_alpha;
+  int32_t has_view, has_light, has_alpha, has_gain;
   hm_view_plan vp;                 // without a view: the whole image as a crop alone (ow = w, oh = h)
   hm_light_plan lp; hm_alpha_plan ap;
+  hm_gain_plan gp;                 // has_gain and a known profile: the tables' weight; and a known map: the geometry
   hm_dest_plan dp;                 // against dest_format at vp.ow x vp.oh; d->len has been compared
 } hm_out_plan;
 // the target the destination is judged by: hm_alpha_dest_format with an alpha step (negative: the step's own refusals), else with
@@ -198,7 +247,8 @@ enum { HM_OUT_PROFILE_LAST = 1, HM_OUT_PROFILE_FIRST = 2 };
 int hm_out_resolve(int out_format, const hm_out_image* img, int know_profile, const hm_device_dest* d, const hm_out_steps* st, hm_out_plan* p);
 // the image at `src` (interleaved pixels of p->out_format, row 0 = image row 0) through the plan into the destination; asynchronous on
 // `s`.  Tables and the intermediate hang on sc, which must be a free entry (it is not looked at where nothing is uploaded).
-int hm_out_write(const hm_device_dest* d, const hm_out_plan* p, const void* src, int src_stride, hipStream_t s, hm_view_scratch* sc);
+// map: the gain map of an active gain step (p->gp.active), else NULL.
+int hm_out_write(const hm_device_dest* d, const hm_out_plan* p, const void* src, int src_stride, const hm_out_map* map, hipStream_t s, hm_view_scratch* sc);
 
 // ---- planar views: a view (hm_device_view) into planar YCbCr (hm_device_planes), every plane an image of its own.  devdest.cpp
 //      holds the checks and the write step, hm_planes_view.h the index arithmetic, planes_view.hip the kernels ----

@@ -431,6 +431,8 @@ int plan_item(const hm_file* f, uint32_t id, ItemPlan& P, bool self_grid = false
   }
   else if (it->type == "iden" || it->type == "iovl")
     return hm_fail(HM_ERR_UNSUPPORTED, "derived image item ('%s') is not supported by the pipeline and sequence calls: decode it with hm_decode_item", it->type.c_str());
+  else if (it->type == "tmap")
+    return hm_fail(HM_ERR_UNSUPPORTED, "a 'tmap' item (a base image with a gain map) is not an image of its own: render it with hm_decode_item_to_device_gain");
   else return hm_fail(HM_ERR_UNSUPPORTED, "item type '%s'", it->type.c_str());
   if (P.canvas_w < 0 || P.canvas_h < 0 || (P.is_grid && (P.canvas_w == 0 || P.canvas_h == 0))) return hm_fail(HM_ERR_BITSTREAM, "bad grid size");
   if (P.tiles.empty()) return hm_fail(HM_ERR_BITSTREAM, "image without coded pictures");
@@ -775,7 +777,18 @@ int job_plan(DecodeJob& j)
   j.view_dx = j.view_dy = 0;
   j.sub_tiles[0] = 0; j.sub_tiles[1] = j.item[0].rows; j.sub_tiles[2] = 0; j.sub_tiles[3] = j.item[0].cols;
   int sx = 0, sy = 0, sw = 0, sh = 0;
-  if (j.target.t.view && view_subgrid(j.f, j.id, &j.params, j.target.t.view, j.sub_tiles, &sx, &sy, &sw, &sh, j.target.t.planes != nullptr)) {
+  // the gain map of a gain step joins the job as a third item - unless its weight is 0: the write is then the one without the step.
+  // Tile reduction under a view stays off with a gain step (the open step: the map's crop would have to follow the sub-grid)
+  j.has_map = false;
+  if (const hm_device_gain* g = j.target.t.gain) {
+    if (hm_gain_weight(&g->params, g->headroom) != 0.0) {
+      ItemPlan& M = j.item[2];
+      if ((rc = plan_item(j.f, g->map_item, M))) return rc;
+      M.tile_alpha.clear(); M.alpha_blobs.clear(); M.alpha_status.clear(); M.alpha_messages.clear(); // (a map has no alpha)
+      j.has_map = true;
+    }
+  }
+  else if (j.target.t.view && view_subgrid(j.f, j.id, &j.params, j.target.t.view, j.sub_tiles, &sx, &sy, &sw, &sh, j.target.t.planes != nullptr)) {
     // the sub-grid becomes a grid of its own (what a slab is for tile rows): everything behind sees an ordinary smaller grid
     ItemPlan& P = j.item[0];
     const int32_t* t = j.sub_tiles;
@@ -803,13 +816,19 @@ int job_tile_count(const DecodeJob& j)
 {
   int n = 0;
   for (int i = 0; i < j.n_items; i++) n += (int)j.item[i].tiles.size();
-  return n + (int)j.item[0].tile_alpha.size(); // (behind the tiles of the image and of its own alpha image: the tiles' alpha pictures)
+  n += (int)j.item[0].tile_alpha.size(); // (behind the tiles of the image and of its own alpha image: the tiles' alpha pictures)
+  return n + (j.has_map ? (int)j.item[2].tiles.size() : 0); // (... and behind those the pictures of the gain map)
 }
 
 // host entropy decode of coded picture k (CABAC on the calling thread, like the reference's std::async tile tasks,
 // context.cc:2361-2401); distinct k may run concurrently
 void job_parse_tile(DecodeJob& j, int k, int row_threads)
 {
+  if (j.has_map) {
+    ItemPlan& M = j.item[2];
+    const int m = k - (job_tile_count(j) - (int)M.tiles.size());
+    if (m >= 0) { parse_picture(j.f, M.tiles[m].id, j.few_pictures != 0, j.params.strict_decoding, row_threads, M.blobs[m], M.status[m], M.messages[m]); return; }
+  }
   int which = 0;
   if (k >= (int)j.item[0].tiles.size()) { which = 1; k -= (int)j.item[0].tiles.size(); }
   const bool tile_alpha = which == 1 && (j.n_items < 2 || k >= (int)j.item[1].tiles.size());
@@ -836,10 +855,10 @@ void parse_picture(const hm_file* f, uint32_t id, bool few_pictures, int strict,
 
 int target_check_shape(const OutputTarget& t)
 {
-  const bool ok = !(t.dest && t.planes) && (!t.light || t.dest) && (!t.tone || t.light) && (!t.alpha || (t.dest && !t.view_later)) && (!t.view || t.dest || t.planes) && (!t.view_later || (t.view && t.dest)) &&
+  const bool ok = !(t.dest && t.planes) && (!t.light || t.dest) && (!t.tone || t.light) && (!t.alpha || (t.dest && !t.view_later)) && (!t.gain || (t.light && !t.view_later)) && (!t.view || t.dest || t.planes) && (!t.view_later || (t.view && t.dest)) &&
                   (!t.planes_later || (t.view && t.planes));
-  return ok ? (int)HM_OK : hm_fail(HM_ERR_INTERNAL, "output target: dest%s view%s planes%s light%s tone%s alpha%s do not go together", t.dest ? "+" : "-", t.view ? "+" : "-",
-                                   t.planes ? "+" : "-", t.light ? "+" : "-", t.tone ? "+" : "-", t.alpha ? "+" : "-");
+  return ok ? (int)HM_OK : hm_fail(HM_ERR_INTERNAL, "output target: dest%s view%s planes%s light%s tone%s alpha%s gain%s do not go together", t.dest ? "+" : "-", t.view ? "+" : "-",
+                                   t.planes ? "+" : "-", t.light ? "+" : "-", t.tone ? "+" : "-", t.alpha ? "+" : "-", t.gain ? "+" : "-");
 }
 
 // the chroma format and depth of a planar result for a decoded image of (chroma, bd): what emit_native / emit_planar hand out
@@ -1036,11 +1055,17 @@ static int emit_interleaved(const hm_decode_params* params, hipStream_t s, Plana
   if (t.dest) { // the image, or with a view a rectangle of it at vp.ow x vp.oh, through the steps of the request and nothing else (devdest.cpp): the light and
                 // alpha steps resolved against the profile and depth this image reports - refused before a byte is written
     const hm_out_steps st = t.steps();
-    const hm_out_image img = {img_w, img_h, r.bit_depth, r.transfer, r.primaries};
+    hm_out_image img = {img_w, img_h, r.bit_depth, r.transfer, r.primaries, 0, 0, 0};
+    hm_out_map map = {nullptr, 0};
+    if (const PlanarImage* G = t.gain_map) { // the gain map as decoded: its Y plane
+      if (G->chroma != 0) return hm_fail(HM_ERR_UNSUPPORTED, "gain: the map decodes to chroma format %d, not 4:0:0 (colour gain maps are the open step)", G->chroma);
+      img.map_w = G->w; img.map_h = G->h; img.map_bits = G->bd;
+      map.plane = G->P[0].mem.p; map.stride = G->P[0].stride;
+    }
     hm_out_plan plan;
     if ((rc = hm_out_resolve(params->out_format, &img, HM_OUT_PROFILE_LAST, t.dest, &st, &plan))) return rc;
     if (t.view_later) { t.view_later->dest = t.dest; t.view_later->vp = plan.vp; t.view_later->src = dout.p; t.view_later->src_stride = cd.out_stride; } // (a sequence: hm_view_write_batch)
-    else if ((rc = hm_out_write(t.dest, &plan, dout.p, cd.out_stride, s, t.scratch))) return rc;
+    else if ((rc = hm_out_write(t.dest, &plan, dout.p, cd.out_stride, t.gain_map ? &map : nullptr, s, t.scratch))) return rc;
     if (t.view) {
       out->width = plan.vp.ow; out->height = plan.vp.oh;
       out->plane_width[0] = plan.vp.ow; out->plane_height[0] = plan.vp.oh;
@@ -1133,6 +1158,10 @@ int job_enqueue(DecodeJob& j, hm_decoded* out)
   lap("planar decode queued");
   OutputTarget t = j.target.t;
   t.scratch = &j.view_scratch;
+  if (j.has_map) { // the gain map: an image decoded like any other, on the job's stream; its own irot / imir / clap apply
+    if ((rc = planar_from_blobs(f, j.item[2], params, s, j.G))) return rc;
+    t.gain_map = &j.G;
+  }
   hm_device_view shifted = j.target.view; // (the crop inside the sub-grid that was decoded)
   if (t.view && (shifted.crop_w || shifted.crop_h)) { shifted.crop_x -= j.view_dx; shifted.crop_y -= j.view_dy; }
   if (t.view) t.view = &shifted;
@@ -1192,7 +1221,7 @@ int job_complete(DecodeJob& j, hm_decoded*)
   const hipError_t e = hipStreamSynchronize(j.s);
   if (e != hipSuccess) return hm_check_hip(e, "kernel execution");
   // (the reconstruction bounds its cross-wave waits: a wave that gave up has flagged its launch)
-  for (PlanarImage* im : {&j.I, &j.A})
+  for (PlanarImage* im : {&j.I, &j.A, &j.G})
     if (im->batch) {
       const int rc = hm_batch_check(im->batch.get());
       if (rc) return rc;
@@ -1739,7 +1768,120 @@ int hm_file_item_kind(const hm_file* f, uint32_t id)
   if (it->type == "grid") return HM_ITEM_GRID;
   if (it->type == "iden") return HM_ITEM_IDEN;
   if (it->type == "iovl") return HM_ITEM_IOVL;
+  if (it->type == "tmap") return HM_ITEM_TMAP;
   return HM_ITEM_OTHER;
+}
+
+static void gain_params_of(const hm::GainMapInfo& g, hm_gain_params* p)
+{
+  std::memset(p, 0, sizeof(*p));
+  p->base_headroom = g.base_headroom; p->alternate_headroom = g.alternate_headroom;
+  for (int c = 0; c < 3; c++) {
+    p->map_min[c] = g.map_min[c]; p->map_max[c] = g.map_max[c]; p->gamma[c] = g.gamma[c];
+    p->base_offset[c] = g.base_offset[c]; p->alternate_offset[c] = g.alternate_offset[c];
+  }
+  p->use_base_primaries = g.use_base_colour_space ? 1 : 0;
+}
+
+int hm_file_gain_map_info(const hm_file* f, uint32_t tmap_id, hm_gain_map_info* info)
+{
+  if (!f || !info) return hm_fail(HM_ERR_INVALID_ARG, "null argument");
+  std::memset(info, 0, sizeof(*info));
+  const hm::Item* it = f->file.item(tmap_id);
+  if (!it) return hm_fail(HM_ERR_INVALID_ARG, "no item %u", tmap_id);
+  hm::GainMapInfo g;
+  hm::HeifError err;
+  if (!f->file.gain_map_info(tmap_id, g, err)) return fail_from(err);
+  info->base_item = g.base; info->map_item = g.map;
+  gain_params_of(g, &info->params);
+  info->alt_has_nclx = it->props.colr.present ? 1 : 0;
+  info->alt_primaries = it->props.colr.present ? it->props.colr.primaries : 0;
+  info->alt_transfer = it->props.colr.present ? it->props.colr.transfer : 0;
+  return HM_OK;
+}
+
+uint32_t hm_file_gain_map_of(const hm_file* f, uint32_t base_id) { return f ? f->file.gain_map_of(base_id) : 0; }
+
+int hm_file_item_aux_type(const hm_file* f, uint32_t id, char* out, int cap)
+{
+  if (!f || (cap > 0 && !out) || cap < 0) return hm_fail(HM_ERR_INVALID_ARG, "null argument");
+  const hm::Item* it = f->file.item(id);
+  if (!it) return hm_fail(HM_ERR_INVALID_ARG, "no item %u", id);
+  const std::string& t = it->props.aux_type;
+  if (cap > 0) {
+    const size_t n = std::min(t.size(), (size_t)cap - 1);
+    std::memcpy(out, t.data(), n);
+    out[n] = 0;
+  }
+  return (int)std::min<size_t>(t.size(), 0x7FFFFFFF);
+}
+
+// The gain step of a decode, resolved before anything is queued: *base = the base image's item, *own = the step with map_item the
+// map's item and explicit parameters.  Everything the file says about the map is judged here: its kind, chroma format and depth, and
+// the geometry against the sizes the file declares (judged again against the decoded sizes by the write).
+int hm_gain_for_item(const hm_file* f, uint32_t id, const hm_decode_params* params, const hm_device_view* view, const hm_device_gain* gain, uint32_t* base,
+                         hm_device_gain* own)
+{
+  *own = *gain;
+  *base = id;
+  const hm::Item* it = f->file.item(id);
+  if (!it) return hm_fail(HM_ERR_INVALID_ARG, "no item %u", id);
+  if (gain->reserved[0] || gain->reserved[1] || gain->reserved[2] || gain->reserved[3]) return hm_fail(HM_ERR_INVALID_ARG, "gain: reserved is not 0");
+  int rc;
+  if (gain->map_item == 0) {
+    if (it->type != "tmap") return hm_fail(HM_ERR_INVALID_ARG, "gain: item %u is not a 'tmap' item (give map_item and the parameters for a base image)", id);
+    hm_gain_map_info info;
+    if ((rc = hm_file_gain_map_info(f, id, &info))) return rc;
+    if ((rc = hm_gain_check(&info.params, gain->headroom, HM_ERR_BITSTREAM))) return rc;
+    own->map_item = info.map_item; own->params = info.params;
+    *base = info.base_item;
+    const hm::Item* bi = f->file.item(info.base_item);
+    if (!bi) return hm_fail(HM_ERR_BITSTREAM, "'tmap' item %u references the missing item %u", id, info.base_item);
+    const int base_primaries = bi->props.colr.present && bi->props.colr.primaries != 2 ? bi->props.colr.primaries : 1;
+    if (!info.params.use_base_primaries && info.alt_has_nclx && info.alt_primaries != 2 && info.alt_primaries != base_primaries)
+      return hm_fail(HM_ERR_UNSUPPORTED, "gain: applying the gain in the alternate primaries (%d, the base has %d) is not supported (the open step)", info.alt_primaries, base_primaries);
+  }
+  else {
+    if (it->type == "tmap") return hm_fail(HM_ERR_INVALID_ARG, "gain: map_item %u with the 'tmap' item %u (a 'tmap' item brings its own map)", gain->map_item, id);
+    if ((rc = hm_gain_check(&gain->params, gain->headroom, HM_ERR_INVALID_ARG))) return rc;
+  }
+  const hm::Item* bi = f->file.item(*base);
+  const hm::Item* mi = f->file.item(own->map_item);
+  if (!mi) return hm_fail(gain->map_item ? HM_ERR_INVALID_ARG : HM_ERR_BITSTREAM, "gain: no item %u for the map", own->map_item);
+  if (!bi || (bi->type != "hvc1" && bi->type != "grid")) return hm_fail(HM_ERR_UNSUPPORTED, "gain: the base image (item %u) is not a coded image or a grid", *base);
+  if (mi->type != "hvc1" && mi->type != "grid") return hm_fail(HM_ERR_UNSUPPORTED, "gain: the map (item %u, '%s') is not a coded image or a grid", own->map_item, mi->type.c_str());
+  if (own->map_item == *base) return hm_fail(HM_ERR_INVALID_ARG, "gain: the map is the base image itself");
+  hm_image_info binfo, minfo;
+  if ((rc = hm_file_image_info(f, own->map_item, &minfo))) return rc;
+  if (minfo.chroma != 0) return hm_fail(HM_ERR_UNSUPPORTED, "gain: a map that is not 4:0:0 (chroma format %d: a colour gain map) is not supported (the open step)", minfo.chroma);
+  if (minfo.bit_depth > HM_GAIN_MAX_BITS) return hm_fail(HM_ERR_UNSUPPORTED, "gain: a map of %d bits is not supported (8 .. %d are; deeper maps are the open step)", minfo.bit_depth, (int)HM_GAIN_MAX_BITS);
+  if (hm_file_image_info(f, *base, &binfo) != HM_OK) return HM_OK; // (the decode fails with its own message)
+  const bool raw = params->ignore_transformations != 0;
+  const int W = raw ? binfo.coded_width : binfo.width, H = raw ? binfo.coded_height : binfo.height;
+  const int MW = raw ? minfo.coded_width : minfo.width, MH = raw ? minfo.coded_height : minfo.height;
+  if (W <= 0 || H <= 0 || MW <= 0 || MH <= 0) return HM_OK;
+  hm_view_plan vp;
+  std::memset(&vp, 0, sizeof(vp));
+  if (view) { if ((rc = hm_view_resolve(params->out_format, W, H, view, &vp))) return rc; }
+  else { vp.w = vp.ow = W; vp.h = vp.oh = H; vp.crop_only = 1; }
+  hm_gain_plan gp;
+  std::memset(&gp, 0, sizeof(gp));
+  return hm_gain_geometry(W, H, MW, MH, minfo.bit_depth, &vp, &gp);
+}
+
+int hm_decode_item_to_device_gain(const hm_file* f, uint32_t id, const hm_decode_params* params, const hm_device_view* view, const hm_device_light* light,
+                                  const hm_device_tone* tone, const hm_device_gain* gain, const hm_device_dest* dest, hm_decoded* out)
+{
+  if (!f || !params || !gain || !dest || !out) return hm_fail(HM_ERR_INVALID_ARG, "null argument");
+  if (!light) return hm_fail(HM_ERR_INVALID_ARG, "gain: null light step");
+  hm_device_tone own_tone{};
+  if (tone) own_tone = tone_for_item(f, id, tone); // (the properties of item `id`: a 'tmap' item's clli describes the alternate rendition)
+  hm_device_gain own{};
+  uint32_t base = 0;
+  std::memset(out, 0, sizeof(*out));
+  const int rc = hm_gain_for_item(f, id, params, view, gain, &base, &own);
+  if (rc) return rc;
+  return decode_item_to(f, base, params, OutputTarget::to_dest(dest, view, light, tone ? &own_tone : nullptr, nullptr, &own), out);
 }
 
 int hm_file_overlay_info(const hm_file* f, uint32_t id, hm_overlay_info* info, uint32_t* children, int32_t* offsets, int max_children)

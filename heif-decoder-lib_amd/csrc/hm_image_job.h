@@ -1,6 +1,6 @@
 // hm_image_job.h — internal: one image decode (HEIF item -> pixels) split into the phases the image-at-a-time entry
 // (hm_decode_item) runs back to back and the pipelined entry (hm_pipeline_*, pipeline.cpp) overlaps across images:
-//   job_plan         which coded pictures (grid tiles, alpha auxiliary image), where they go         host, cheap
+//   job_plan         which coded pictures (grid tiles, alpha auxiliary image, gain map), where they go host, cheap
 //   job_parse_tile   entropy decode of one coded picture -> command stream                          host, the Amdahl term
 //   job_enqueue      H2D, reconstruction, filters, paste, transforms, colour, D2H on the job's stream  asynchronous
 //   job_complete     wait for the stream
@@ -111,17 +111,19 @@ struct OutputTarget {
   const hm_device_light* light = nullptr;      // the light step in the write of dest
   const hm_device_tone* tone = nullptr;        // ... with a tone step inside it (src_peak resolved by the entry point: never 0 here)
   const hm_device_alpha* alpha = nullptr;      // the alpha step in the write of dest (alone, or beside light and tone)
+  const hm_device_gain* gain = nullptr;        // the gain step beside light (resolved by the entry point: map_item is the map's item, params are explicit)
+  const struct PlanarImage* gain_map = nullptr; // ... and its decoded map (job_enqueue sets it; null with a gain step of weight 0)
   hm_view_scratch* scratch = nullptr;          // tap tables and the intermediate of the resampling step, the tables of the light step
   hm_view_item* view_later = nullptr;          // view + dest: the view is not written, only described there - the caller writes it with those of other images
   hm_planes_view_item* planes_later = nullptr; // the same for view + planes
   static OutputTarget to_dest(const hm_device_dest* d, const hm_device_view* v = nullptr, const hm_device_light* l = nullptr, const hm_device_tone* tn = nullptr,
-                              const hm_device_alpha* a = nullptr)
+                              const hm_device_alpha* a = nullptr, const hm_device_gain* g = nullptr)
   {
     OutputTarget t;
-    t.dest = d; t.view = v; t.light = l; t.tone = tn; t.alpha = a;
+    t.dest = d; t.view = v; t.light = l; t.tone = tn; t.alpha = a; t.gain = g;
     return t;
   }
-  hm_out_steps steps() const { return hm_out_steps{view, light, tone, alpha}; } // the request of the device write (hm_devdest.h)
+  hm_out_steps steps() const { return hm_out_steps{view, light, tone, alpha, gain}; } // the request of the device write (hm_devdest.h)
   static OutputTarget to_planes(const hm_device_planes* p, const hm_device_view* v = nullptr)
   {
     OutputTarget t;
@@ -129,7 +131,8 @@ struct OutputTarget {
     return t;
   }
 };
-// dest xor planes (or neither); light only with dest; tone only with light; alpha only with dest and never with view_later; view only with one of the two; a *_later only with view and its own kind of destination
+// dest xor planes (or neither); light only with dest; tone only with light; alpha only with dest and never with view_later; gain only with light and
+// never with view_later; view only with one of the two; a *_later only with view and its own kind of destination
 int target_check_shape(const OutputTarget& t);
 
 // a job's own copies of the caller's structs (the pipeline outlives them; hm_decode_params keeps its layout, so they travel beside
@@ -141,6 +144,7 @@ struct OwnedTarget {
   hm_device_light light{};
   hm_device_tone tone{};
   hm_device_alpha alpha{};
+  hm_device_gain gain{};
   OutputTarget t;
   OwnedTarget() = default;
   OwnedTarget(const OwnedTarget&) = delete;
@@ -154,6 +158,7 @@ struct OwnedTarget {
     if (from.light) { light = *from.light; t.light = &light; }
     if (from.tone) { tone = *from.tone; t.tone = &tone; }
     if (from.alpha) { alpha = *from.alpha; t.alpha = &alpha; }
+    if (from.gain) { gain = *from.gain; t.gain = &gain; }
   }
 };
 
@@ -171,9 +176,10 @@ struct DecodeJob {
   hm_view_scratch view_scratch{}; // what job_enqueue hands to emit_image as the target's scratch
   bool self_grid = false; // item[0] is planned as the 1 x 1 grid of itself (ItemPlan::self_grid)
   hipStream_t s = nullptr;
-  ItemPlan item[2];   // [0] the image, [1] its alpha auxiliary image
-  int n_items = 0;
-  PlanarImage I, A;
+  ItemPlan item[3];   // [0] the image, [1] its alpha auxiliary image, [2] the gain map of a gain step (has_map)
+  int n_items = 0;    // of [0] and [1]
+  bool has_map = false; // item[2] is planned: a gain step whose weight is not 0
+  PlanarImage I, A, G;
   DevPlane alpha_scaled;
   DevPlane alpha_sdr; // a deeper alpha plane brought to 8 bits (Op_to_sdr_planes) for an RGBA target
   DevMem dout;
@@ -191,7 +197,7 @@ struct DecodeJob {
 
 int job_plan(DecodeJob& j);
 int job_tile_count(const DecodeJob& j);
-void job_parse_tile(DecodeJob& j, int k, int row_threads = 1); // k = 0 .. job_tile_count - 1 (main image tiles first, then alpha); thread-safe per tile;
+void job_parse_tile(DecodeJob& j, int k, int row_threads = 1); // k = 0 .. job_tile_count - 1 (main image tiles first, then alpha, then the gain map's); thread-safe per tile;
                                                                 // row_threads > 1: WPP rows of this picture in parallel (hm_hevc_parse_mt)
 // the entropy decode of one coded picture (hvc1 item or movie sample `id`) into `blob`, or its failure in status / message
 void parse_picture(const hm_file* f, uint32_t id, bool few_pictures, int strict, int row_threads, Blob& blob, int& status, std::string& message);
@@ -207,4 +213,10 @@ hm_device_tone tone_for_item(const hm_file* f, uint32_t id, const hm_device_tone
 int job_complete(DecodeJob& j, hm_decoded* out);
 
 } // namespace hm_img
+
+// The gain step of a decode of item `id`, resolved before anything is queued: *base = the base image's item (the item the job decodes),
+// *own = the step with map_item the map's item and explicit parameters (a 'tmap' item's: from its payload).  Everything the file says
+// about the map is judged here: its kind, chroma format and depth, and the geometry against the sizes the file declares.
+extern "C" int hm_gain_for_item(const hm_file* f, uint32_t id, const hm_decode_params* params, const hm_device_view* view, const hm_device_gain* gain, uint32_t* base,
+                                hm_device_gain* own);
 #endif

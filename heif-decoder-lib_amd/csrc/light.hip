@@ -355,17 +355,25 @@ extern "C" int hm_launch_light_nearest(const hm_dest_plan* p, const hm_light_arg
   return hm_check_hip(hipGetLastError(), "k_light_nearest launch");
 }
 
+// the horizontal pass of a resampled view under the light step alone (the gain step's vertical pass is gain.hip's)
+extern "C" int hm_launch_light_h(const hm_dest_plan* p, const hm_light_args* la, const hm_resample_args* r, hipStream_t s)
+{
+  if (r->ow <= 0 || r->oh <= 0 || r->n_w <= 0 || r->n_h <= 0) return HM_OK;
+  const int rc = check_args(p, la);
+  if (rc) return rc;
+  const bool chw = p->layout == HM_DEV_LAYOUT_CHW;
+  if (r->sample_bytes == 1) { if (r->channels == 3) launch_h<1, 3>(chw, r, la, s); else launch_h<1, 4>(chw, r, la, s); }
+  else { if (r->channels == 3) launch_h<2, 3>(chw, r, la, s); else launch_h<2, 4>(chw, r, la, s); }
+  return hm_check_hip(hipGetLastError(), "k_light_h launch");
+}
+
 // both passes of a resampled view under the light step; the intermediate is hm_launch_resample's
 extern "C" int hm_launch_light_resample(const hm_dest_plan* p, const hm_light_args* la, const hm_resample_args* r, void* dst, const float scale[4],
                                         const float bias[4], hipStream_t s)
 {
   if (r->ow <= 0 || r->oh <= 0 || r->n_w <= 0 || r->n_h <= 0) return HM_OK;
-  int rc = check_args(p, la);
+  int rc = hm_launch_light_h(p, la, r, s);
   if (rc) return rc;
-  const bool chw = p->layout == HM_DEV_LAYOUT_CHW;
-  if (r->sample_bytes == 1) { if (r->channels == 3) launch_h<1, 3>(chw, r, la, s); else launch_h<1, 4>(chw, r, la, s); }
-  else { if (r->channels == 3) launch_h<2, 3>(chw, r, la, s); else launch_h<2, 4>(chw, r, la, s); }
-  if ((rc = hm_check_hip(hipGetLastError(), "k_light_h launch"))) return rc;
   const Affine a = affine_of(scale, bias);
   uint8_t* out = (uint8_t*)dst;
   const int found = with_dtype(p->dtype, [&](auto tag) -> int { launch_v<typename decltype(tag)::type>(p, r, la, out, a, s); return HM_OK; });

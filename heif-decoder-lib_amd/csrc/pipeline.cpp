@@ -228,6 +228,15 @@ int hm_pipeline_submit_to_device_alpha(hm_pipeline* p, const uint8_t* heif, size
   return submit(p, heif, size, item_id, tag, t);
 }
 
+// (a 'tmap' item's base, map and parameters are read once the file is open: submit)
+int hm_pipeline_submit_to_device_gain(hm_pipeline* p, const uint8_t* heif, size_t size, uint32_t item_id, uint64_t tag, const hm_device_view* view,
+                                      const hm_device_light* light, const hm_device_tone* tone, const hm_device_gain* gain, const hm_device_dest* dest)
+{
+  if (!p || !heif || !gain || !dest) return hm_fail(HM_ERR_INVALID_ARG, "null argument");
+  if (!light) return hm_fail(HM_ERR_INVALID_ARG, "gain: null light step");
+  return submit(p, heif, size, item_id, tag, OutputTarget::to_dest(dest, view, light, tone, nullptr, gain));
+}
+
 int hm_pipeline_submit_to_device_planes(hm_pipeline* p, const uint8_t* heif, size_t size, uint32_t item_id, uint64_t tag, const hm_device_planes* planes)
 {
   if (!p || !heif || !planes) return hm_fail(HM_ERR_INVALID_ARG, "null argument");
@@ -279,7 +288,14 @@ static int submit(hm_pipeline* p, const uint8_t* heif, size_t size, uint32_t ite
       OutputTarget t = target;
       hm_device_tone own{};
       if (t.tone) { own = tone_for_item(im->file, im->job.id, t.tone); t.tone = &own; } // (the image's own peak, before the curve is judged)
-      rc = check_target_request(im->file, im->job.id, &im->job.params, t);
+      hm_device_gain own_gain{};
+      if (t.gain) { // (a 'tmap' item: the job decodes its base image, the map beside it)
+        uint32_t base = 0;
+        rc = hm_gain_for_item(im->file, im->job.id, &im->job.params, t.view, t.gain, &base, &own_gain);
+        t.gain = &own_gain;
+        if (!rc) im->job.id = base;
+      }
+      if (!rc) rc = check_target_request(im->file, im->job.id, &im->job.params, t);
       if (prev >= 0) hipSetDevice(prev);
       if (!rc) im->job.target.set(t);
     }

@@ -16,6 +16,10 @@ display's with the BT.2390 curve; out_bits=8 finishes a deeper image in 8-bit co
 alpha="straight" / "premultiplied" / dict(mode="matte", background=(r, g, b)) with out_format "rgba" / "rrggbbaa_le" uses the alpha
 channel: a resize sums colour times alpha (no dark fringes around a cut-out), and the tensor holds straight colour, premultiplied
 colour, or - three channels - the picture over the background colour (code values at the target's sample depth).
+gain=dict(headroom=2.0) beside light= renders an SDR image with a gain map (an ISO 21496-1 'tmap' item: item_id is that item, or its
+base image) for a display whose peak is 2 ** headroom times SDR white (math.inf: the full HDR rendition); with
+gain=dict(headroom=..., map_item=id, alternate_headroom=..., map_max=..., ...) any image of the file is the map (a vendor gain map
+among the auxiliary images, its parameters read elsewhere).
 What the library refuses raises capi.HmError.
 
 Planar YCbCr stays planar: decode_to_planes / decode_sequence_to_planes / decode_batch_to_planes return (Y, Cb, Cr[, A]) ("planar":
@@ -212,6 +216,65 @@ def _alpha_of(alpha, fmt):
     return d, 3 if d.mode == capi.HM_ALPHA_MATTE else 4
 
 
+GAIN_FIELDS = ("map_min", "map_max", "gamma", "base_offset", "alternate_offset")
+
+
+def _gain_of(gain, lit):
+    """hm_device_gain (or None) of the gain= argument: a dict of headroom (needed; log2(display peak / SDR white), math.inf allowed) and
+    optionally map_item with the explicit parameters base_headroom, alternate_headroom, map_min, map_max, gamma, base_offset,
+    alternate_offset (a number for all three channels or three numbers) and use_base_primaries; needs a light step"""
+    if gain is None or gain is False:
+        return None
+    if not isinstance(gain, dict):
+        raise ValueError(f"gain {gain!r}: a dict")
+    keys = {"headroom", "map_item", "base_headroom", "alternate_headroom", "use_base_primaries"} | set(GAIN_FIELDS)
+    if set(gain) - keys:
+        raise ValueError(f"gain: unknown keys {sorted(set(gain) - keys)}, known are {sorted(keys)}")
+    if lit is None:
+        raise ValueError("gain: needs light= (the gain acts on linear light)")
+    if gain.get("headroom") is None:
+        raise ValueError("gain: headroom (log2 of the display's peak over SDR white) is needed")
+    d = capi.DeviceGain()
+    d.headroom = float(gain["headroom"])
+    explicit = sorted(k for k in keys - {"headroom", "map_item"} if gain.get(k) is not None)
+    if not gain.get("map_item"):
+        if explicit:
+            raise ValueError(f"gain: {explicit} without map_item (a 'tmap' item brings its own parameters)")
+        return d
+    d.map_item = int(gain["map_item"])
+    p = d.params
+    p.base_headroom = float(gain.get("base_headroom") or 0.0)
+    if gain.get("alternate_headroom") is None:
+        raise ValueError("gain: map_item needs the explicit parameters, alternate_headroom among them")
+    p.alternate_headroom = float(gain["alternate_headroom"])
+    defaults = {"map_min": 0.0, "map_max": None, "gamma": 1.0, "base_offset": 1.0 / 64.0, "alternate_offset": 1.0 / 64.0}
+    for key in GAIN_FIELDS:
+        v = gain.get(key, defaults[key])
+        if v is None:
+            raise ValueError(f"gain: map_item needs the explicit parameters, {key} among them")
+        v = [float(v)] * 3 if not hasattr(v, "__len__") else [float(x) for x in v]
+        if len(v) != 3:
+            raise ValueError(f"gain[{key!r}]: one number or three")
+        for c in range(3):
+            getattr(p, key)[c] = v[c]
+    p.use_base_primaries = 1 if gain.get("use_base_primaries", True) else 0
+    return d
+
+
+def _gain_items(f, iid, gn):
+    """(the item the decode is asked for, the item whose size the tensor has): a 'tmap' item and its base image - iid itself when it
+    is a 'tmap' item, else the 'tmap' item whose base iid is (hm_file_gain_map_of) -, or with an explicit map_item iid twice"""
+    L = f.L
+    if gn.map_item:
+        return iid, iid
+    tmap = iid if L.hm_file_item_kind(f.h, iid) == capi.HM_ITEM_TMAP else L.hm_file_gain_map_of(f.h, iid)
+    if not tmap:
+        raise ValueError(f"gain: item {iid} is no 'tmap' item and no 'tmap' item has it as its base image (give map_item and the parameters)")
+    info = capi.GainMapInfo()
+    capi.check_image(L.hm_file_gain_map_info(f.h, tmap, C.byref(info)))
+    return tmap, info.base_item
+
+
 def _default_threads():
     return max(1, min(16, os.cpu_count() or 1))
 
@@ -235,7 +298,7 @@ class _File:
 
 
 def decode_to_tensor(data, item_id=0, out_format="rgb", layout="chw", dtype=None, scale=None, bias=None, out=None, stream=None,
-                     host_threads=None, crop=None, size=None, filter="triangle", light=None, tone=None, alpha=None):
+                     host_threads=None, crop=None, size=None, filter="triangle", light=None, tone=None, alpha=None, gain=None):
     """Decode one image of a HEIF file (bytes; item_id 0 = the primary item) into a CUDA tensor: C x H x W ("chw") or H x W x C
     ("hwc").  dtype defaults to torch.float32 (out's dtype when out is given).  out: a CUDA tensor of that shape to write into;
     its row (and plane) stride is honoured, bytes between rows are left alone.  stream: a torch.cuda.Stream or a raw stream
@@ -243,7 +306,9 @@ def decode_to_tensor(data, item_id=0, out_format="rgb", layout="chw", dtype=None
     (H and W of the tensor are then the size's, or the crop's); filter: "triangle", "bicubic", "lanczos3" or "nearest".  light: True (linear
     light) or a dict (see the module's text): the light step in the write of the tensor; tone: a dict (see the module's text), the tone
     step inside it; alpha: "straight", "premultiplied" or dict(mode="matte", background=(r, g, b)) (see the module's text), the alpha step,
-    for a four-channel out_format - a matte gives a tensor of 3 channels.  Returns when the pixels are in place."""
+    for a four-channel out_format - a matte gives a tensor of 3 channels.  gain: dict(headroom=...) beside light= (see the module's
+    text), the gain step: the image with its gain map for a display of that headroom - item_id may be the 'tmap' item or its base
+    image; with map_item and the explicit parameters any image of the file is the map.  Returns when the pixels are in place."""
     import torch
     L = capi.image_lib()
     fmt, lay = _out_format(out_format), _layout(layout)
@@ -253,10 +318,17 @@ def decode_to_tensor(data, item_id=0, out_format="rgb", layout="chw", dtype=None
     alp, c = _alpha_of(alpha, fmt)
     f = _File(data)
     try:
-        iid, w, h = f.size(item_id)
-        view, w, h = _view_of(crop, size, filter, w, h)
         lit = _light_of(light)
         ton = _tone_of(tone, lit)
+        gn = _gain_of(gain, lit)
+        if gn is not None and alp is not None:
+            raise capi.HmError(-2, "gain: an alpha step beside the gain step is not supported (the open step)")
+        iid = item_id or L.hm_file_primary_item(f.h)
+        sized = iid
+        if gn is not None:
+            iid, sized = _gain_items(f, iid, gn)
+        _, w, h = f.size(sized)
+        view, w, h = _view_of(crop, size, filter, w, h)
         shape = _shape(lay, c, h, w)
         if out is None:
             out = torch.empty(shape, dtype=dtype, device="cuda")
@@ -272,7 +344,10 @@ def decode_to_tensor(data, item_id=0, out_format="rgb", layout="chw", dtype=None
         prm = capi.DecodeParams(fmt, host_threads or _default_threads(), 0, 0, handle or None, None, 0, 0, 0, 0)
         d = capi.Decoded()
         with torch.cuda.device(out.device):
-            if alp is not None:
+            if gn is not None:
+                capi.check_image(L.hm_decode_item_to_device_gain(f.h, iid, C.byref(prm), C.byref(view) if view is not None else None, C.byref(lit),
+                                                                 C.byref(ton) if ton is not None else None, C.byref(gn), C.byref(dest), C.byref(d)))
+            elif alp is not None:
                 capi.check_image(L.hm_decode_item_to_device_alpha(f.h, iid, C.byref(prm), C.byref(view) if view is not None else None,
                                                                   C.byref(lit) if lit is not None else None, C.byref(ton) if ton is not None else None,
                                                                   C.byref(alp), C.byref(dest), C.byref(d)))
@@ -295,13 +370,13 @@ def decode_to_tensor(data, item_id=0, out_format="rgb", layout="chw", dtype=None
 
 
 def decode_batch_to_tensor(files, item_id=0, out_format="rgb", layout="chw", dtype=None, scale=None, bias=None, out=None,
-                           host_threads=None, max_in_flight=4, size=None, crops=None, filter="triangle", light=None, tone=None, alpha=None):
+                           host_threads=None, max_in_flight=4, size=None, crops=None, filter="triangle", light=None, tone=None, alpha=None, gain=None):
     """Decode N equally sized HEIF files through ONE hm_pipeline (the entropy decode of one file runs under the kernels of
     another) into one N x C x H x W ("chw") or N x H x W x C ("hwc") CUDA tensor, each image into its slice.  files: bytes
     objects or paths.  A file of another size than the first (or than `out`) raises ValueError naming it.
     size: (w, h) - files of different sizes are accepted then, each resampled into its slice; crops: one (x, y, w, h) or None per
-    file, the rectangle of that file that is resampled (needs size).  light, tone, alpha: as decode_to_tensor, the same steps for every
-    file (tone's src_peak None: each file's own)."""
+    file, the rectangle of that file that is resampled (needs size).  light, tone, alpha, gain: as decode_to_tensor, the same steps for
+    every file (tone's src_peak None: each file's own; gain: each file's own 'tmap' item)."""
     import torch
     L = capi.image_lib()
     fmt, lay = _out_format(out_format), _layout(layout)
@@ -312,6 +387,9 @@ def decode_batch_to_tensor(files, item_id=0, out_format="rgb", layout="chw", dty
     sc, bi = _per_channel(scale, 1.0), _per_channel(bias, 0.0)
     lit = _light_of(light)
     ton = _tone_of(tone, lit)
+    gn = _gain_of(gain, lit)
+    if gn is not None and alp is not None:
+        raise capi.HmError(-2, "gain: an alpha step beside the gain step is not supported (the open step)")
     names, datas = [], []
     for k, entry in enumerate(files):
         if isinstance(entry, (bytes, bytearray, memoryview)):
@@ -343,7 +421,11 @@ def decode_batch_to_tensor(files, item_id=0, out_format="rgb", layout="chw", dty
     for k, (name, data) in enumerate(zip(names, datas)):
         f = _File(data)
         try:
-            iid, w, h = f.size(item_id)
+            iid = item_id or L.hm_file_primary_item(f.h)
+            sized = iid
+            if gn is not None:
+                iid, sized = _gain_items(f, iid, gn)
+            _, w, h = f.size(sized)
         finally:
             f.close()
         if resized:
@@ -372,7 +454,10 @@ def decode_batch_to_tensor(files, item_id=0, out_format="rgb", layout="chw", dty
             for k, data in enumerate(datas):
                 dest = _dest_of(out[k], lay, code, c, sc, bi)
                 while True:
-                    if alp is not None:
+                    if gn is not None:
+                        rc = L.hm_pipeline_submit_to_device_gain(pipe, data, len(data), ids[k], k, C.byref(views[k]) if views[k] is not None else None,
+                                                                 C.byref(lit), C.byref(ton) if ton is not None else None, C.byref(gn), C.byref(dest))
+                    elif alp is not None:
                         rc = L.hm_pipeline_submit_to_device_alpha(pipe, data, len(data), ids[k], k, C.byref(views[k]) if views[k] is not None else None,
                                                                   C.byref(lit) if lit is not None else None, C.byref(ton) if ton is not None else None,
                                                                   C.byref(alp), C.byref(dest))

@@ -369,8 +369,43 @@ HM_API uint32_t hm_file_primary_item(const hm_file* f);
 HM_API int      hm_file_top_level_images(const hm_file* f, uint32_t* ids, int max_ids); /* returns the count */
 HM_API int      hm_file_image_info(const hm_file* f, uint32_t id, hm_image_info* info);
 /* what kind of item `id` is: HM_ITEM_*, or a negative status (no such item) */
-enum { HM_ITEM_OTHER = 0, HM_ITEM_HVC1 = 1, HM_ITEM_GRID = 2, HM_ITEM_IDEN = 3, HM_ITEM_IOVL = 4 };
+enum { HM_ITEM_OTHER = 0, HM_ITEM_HVC1 = 1, HM_ITEM_GRID = 2, HM_ITEM_IDEN = 3, HM_ITEM_IOVL = 4,
+       HM_ITEM_TMAP = 5 /* a tone-map derived item (ISO 21496-1 gain map): "Gain" below */ };
 HM_API int      hm_file_item_kind(const hm_file* f, uint32_t id);
+/* A 'tmap' item: an SDR base image, a gain-map image and the parameters that take the base to its alternate (HDR) rendition.  It
+ * has exactly two 'dimg' references, [0] the base image and [1] the gain-map image (anything else: HM_ERR_BITSTREAM).  These
+ * references do not hide their targets: the base stays a top-level image, the map is listed or not as its own hidden flag says, and
+ * the 'tmap' item itself is never listed by hm_file_top_level_images.  hm_decode_item on a 'tmap' id is HM_ERR_UNSUPPORTED: the item
+ * is rendered by hm_decode_item_to_device_gain.
+ * The payload, big-endian (the contract of this reader):
+ *   u8  version                          0, anything else HM_ERR_UNSUPPORTED
+ *   u16 minimum_version                  0, anything else HM_ERR_UNSUPPORTED
+ *   u16 writer_version
+ *   u8  flags                            0x80 is_multichannel, 0x40 use_base_colour_space
+ *   u32 / u32  base_hdr_headroom         numerator / denominator
+ *   u32 / u32  alternate_hdr_headroom
+ *   per channel - 3 channels if is_multichannel, else 1 that stands for all three -, each numerator / u32 denominator:
+ *     s32 gain_map_min, s32 gain_map_max, u32 gamma, s32 base_offset, s32 alternate_offset
+ * HM_ERR_BITSTREAM: a zero denominator, a zero gamma, a truncated payload.  Headrooms, gain_map_min and gain_map_max are log2 values.
+ * Every fraction is handed out as (double)numerator / (double)denominator. */
+typedef struct hm_gain_params {
+  double  base_headroom, alternate_headroom;        /* Hb, Ha: log2 */
+  double  map_min[3], map_max[3], gamma[3];         /* per colour channel R, G, B; min and max are log2 */
+  double  base_offset[3], alternate_offset[3];
+  int32_t use_base_primaries;                       /* the gain is applied in the base image's primaries (flag 0x40) */
+  int32_t reserved;                                 /* 0 */
+} hm_gain_params;
+typedef struct hm_gain_map_info {
+  uint32_t base_item, map_item;
+  hm_gain_params params;
+  int32_t alt_has_nclx, alt_primaries, alt_transfer; /* the 'tmap' item's own colr (nclx): the alternate rendition's profile */
+} hm_gain_map_info;
+HM_API int      hm_file_gain_map_info(const hm_file* f, uint32_t tmap_id, hm_gain_map_info* info);
+/* the first 'tmap' item (in item-ID order) whose base image is `base_id`, 0 if there is none */
+HM_API uint32_t hm_file_gain_map_of(const hm_file* f, uint32_t base_id);
+/* The URN of item `id`'s auxC property as a NUL-terminated string in out[0 .. cap) (cut to cap - 1 characters); returns its full
+ * length, 0 for an item without one, or a negative status.  With it a caller finds a vendor gain map among the 'auxl' items of an image. */
+HM_API int      hm_file_item_aux_type(const hm_file* f, uint32_t id, char* out, int cap);
 /* An 'iovl' item (ImageOverlay, context.cc:318-369): the canvas, the 16-bit R G B A background (the canvas is filled with
  * R G B >> 8; A is ignored) and the layers in reference order, bottom first.  children[i] / offsets[2 i], offsets[2 i + 1]: item ID
  * and signed (x, y) offset of layer i, for i < min(n_children, max_children); either array may be NULL.
@@ -888,6 +923,68 @@ HM_API int hm_pipeline_submit_to_device_alpha(hm_pipeline* p, const uint8_t* hei
 HM_API int hm_alpha_to_tensor(int out_format, int bits, int src_w, int src_h, const void* d_src, int src_stride, const hm_device_view* view,
                               const hm_device_light* light, const hm_device_tone* tone, const hm_device_alpha* alpha, const hm_device_dest* dest,
                               void* stream);
+
+/* ------------------------------------------------------------------------- */
+/* Gain: an SDR base image and its gain map ('tmap', ISO 21496-1) rendered to HDR light for a display's headroom */
+/* ------------------------------------------------------------------------- */
+
+/* A gain step exists only beside a light step; a tone step may follow it.  It multiplies the base image's linear light, pixel by
+ * pixel, by a factor read from a second, usually smaller, single-channel image - the gain map - weighted by how much headroom the
+ * display has.  Targets: HM_OUT_RGB, _RGBA, _RRGGBB_LE, _RRGGBBAA_LE; the alpha element is written as without the step.  A call
+ * without the step writes what it wrote before.
+ *   Geometry (the planar view's chroma rule with a general factor; the sampling of a gain map is not normative in ISO 21496-1 - this
+ *   rule is this library's): the base is W x H, the map MW x MH, both as hm_decode_item hands them out.  sx = (W + MW - 1) / MW must
+ *   satisfy MW == (W + sx - 1) / sx, sy likewise with H and MH; a map that fails this is HM_ERR_UNSUPPORTED.  The base takes the crop
+ *   (x, y, w, h) to ow x oh exactly as without the step (without a view: the whole image, ow x oh = W x H; the crop alone: ow x oh =
+ *   w x h).  x must be a multiple of sx and y of sy, else HM_ERR_INVALID_ARG.  The map takes the crop (x / sx, y / sy,
+ *   (w + sx - 1) / sx, (h + sy - 1) / sy) to the same ow x oh under the tap rule stated under "Views" with HM_VIEW_TRIANGLE - or with
+ *   HM_VIEW_NEAREST's index rule when the view's filter is HM_VIEW_NEAREST -, whatever filter the base is resampled with.
+ *   Tables, on the host in double with the C library's pow / exp2, each entry rounded once to float32:  Hd = (double)headroom,
+ *   Hb = base_headroom, Ha = alternate_headroom,  wgt = min(max((Hd - Hb) / (Ha - Hb), 0), 1)  (headroom +inf: 1 for Ha > Hb, 0 for
+ *   Ha < Hb).  mbits = the map's sample depth (8 .. 12), mpeak = (1 << mbits) - 1.  Per colour channel c and map code v = 0 .. mpeak:
+ *     u = v / mpeak;  when gamma_c != 1: u = pow(u, 1 / gamma_c);  tab_c[v] = (float)exp2(wgt * (min_c + (max_c - min_c) * u)).
+ *   When the three channels' parameter sets (min, max, gamma, both offsets) are equal there is one table and one M for all three.
+ *   Per output pixel:  M_c = the view sum over tab_c[min(map sample, mpeak)] - horizontal first, tap 0 first, t = 0, t = fadd(t,
+ *   fmul(w, a)), then vertically the same over the t; HM_VIEW_NEAREST: tab_c of the sample that is moved.  r_c = the light step's
+ *   resampled (or moved) linear light.  With g = (double)gain of the light step, kb_c = (float)(g * base_offset_c) and
+ *   ka_c = (float)(g * alternate_offset_c):
+ *     r_c = fsub(fmul(fadd(r_c, kb_c), M_c), ka_c)
+ *   The update sits before the gamut matrix; the tone step and the light step's finish follow unchanged.
+ *   wgt == 0 exactly: the map is not decoded, and the call writes the bytes of the same call without the step.
+ * Refused with HM_ERR_UNSUPPORTED, each an open step: an alpha step beside the gain step, a map that is not 4:0:0 (a colour gain
+ * map), a map deeper than 12 bits, use_base_primaries == 0 with alternate primaries that differ from the base's (applying the gain in
+ * the alternate primaries), planar targets.  Refused with HM_ERR_INVALID_ARG (parameters from a 'tmap' payload: HM_ERR_BITSTREAM)
+ * before any work is queued, the destination unwritten: a null light step, a headroom that is NaN or negative, alternate_headroom ==
+ * base_headroom, a gamma that is not finite or not above 0, any field that is not finite, reserved != 0 - and everything the light,
+ * tone, view and destination checks refuse.  Tile reduction under a view stays off with a gain step (the open step, as for alpha
+ * images): the whole base is decoded. */
+typedef struct hm_device_gain {
+  uint32_t map_item;        /* 0: `id` is a 'tmap' item - base, map and parameters come from the file.  Non-zero: `id` is the base
+                               image, map_item any image item of the file (an 'auxl' image with a vendor URN ...), `params` are used */
+  float    headroom;        /* log2(display peak / SDR white): >= 0, +inf allowed */
+  hm_gain_params params;    /* used with map_item != 0 and by hm_gain_to_tensor; otherwise not looked at */
+  int32_t  reserved[4];     /* 0 */
+} hm_device_gain;
+/* hm_decode_item_to_device_tone with a gain step; view and tone may be NULL.  hm_decoded reports the base image's fields; the tone
+ * step's src_peak == 0 reads the properties of item `id`.  Base and map are decoded as ONE job: their pictures share one entropy
+ * decode fan-out; the map's own irot / imir / clap apply, and it may be a grid. */
+HM_API int hm_decode_item_to_device_gain(const hm_file* f, uint32_t id, const hm_decode_params* params, const hm_device_view* view,
+                                         const hm_device_light* light, const hm_device_tone* tone, const hm_device_gain* gain,
+                                         const hm_device_dest* dest, hm_decoded* out);
+/* the pipeline form (no frame-list form: a track carries no 'tmap') */
+HM_API int hm_pipeline_submit_to_device_gain(hm_pipeline* p, const uint8_t* heif, size_t size, uint32_t item_id, uint64_t tag,
+                                             const hm_device_view* view, const hm_device_light* light, const hm_device_tone* tone,
+                                             const hm_device_gain* gain, const hm_device_dest* dest);
+/* The step on its own: interleaved base pixels of `bits` bits and a single-channel map of map_w x map_h samples of map_bits bits (one
+ * byte each at 8 bits, else two, little-endian; map_stride in bytes), both on the device already.  gain->map_item is not looked at;
+ * the light step's from_* and the tone step's src_peak and unit_nits must be explicit, as in hm_tone_to_tensor; view and tone may be
+ * NULL.  Asynchronous on `stream`. */
+HM_API int hm_gain_to_tensor(int out_format, int bits, int src_w, int src_h, const void* d_src, int src_stride, const void* d_map, int map_stride,
+                             int map_w, int map_h, int map_bits, const hm_device_view* view, const hm_device_light* light, const hm_device_tone* tone,
+                             const hm_device_gain* gain, const hm_device_dest* dest, void* stream);
+/* Host arithmetic, no device: the 1 << map_bits entries of tab_channel (channel 0 .. 2) for this headroom.  Returns the count, or a
+ * negative status (the step's own refusals of the parameters). */
+HM_API int hm_gain_table(const hm_gain_params* params, float headroom, int channel, int map_bits, float* out);
 
 /* ------------------------------------------------------------------------- */
 /* Planar views: a rectangle of the image, at a size of the caller's choice, into I420 / NV12 / P010 planes */
