@@ -210,6 +210,15 @@ class DeviceGain(C.Structure):
     _fields_ = [("map_item", C.c_uint32), ("headroom", C.c_float), ("params", GainParams), ("reserved", C.c_int32 * 4)]
 
 
+class DeviceOotf(C.Structure):
+    """hm_device_ootf: the HLG OOTF beside a light step - display_peak in cd/m2, gamma 0 = the system gamma of that peak"""
+    _fields_ = [("kind", C.c_int32), ("display_peak", C.c_float), ("gamma", C.c_float), ("reserved", C.c_int32 * 5)]
+
+
+HM_OOTF_HLG = 1
+HM_OOTF_STEPS = 1024
+
+
 class LightLevels(C.Structure):
     """hm_light_levels: the raw fields of an item's clli and mdcv properties"""
     _fields_ = [("has_clli", C.c_int32), ("has_mdcv", C.c_int32), ("max_content_light_level", C.c_uint16), ("max_pic_average_light_level", C.c_uint16),
@@ -338,6 +347,17 @@ def bind_image(L):
     L.hm_gain_to_tensor.argtypes = [C.c_int, C.c_int, C.c_int, C.c_int, C.c_void_p, C.c_int, C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_int, C.POINTER(DeviceView),
                                     C.POINTER(DeviceLight), C.POINTER(DeviceTone), C.POINTER(DeviceGain), C.POINTER(DeviceDest), C.c_void_p]
     L.hm_gain_table.argtypes = [C.POINTER(GainParams), C.c_float, C.c_int, C.c_int, C.POINTER(C.c_float)]
+    L.hm_decode_item_to_device_ootf.argtypes = [C.c_void_p, C.c_uint32, C.POINTER(DecodeParams), C.POINTER(DeviceView), C.POINTER(DeviceLight), C.POINTER(DeviceOotf),
+                                                C.POINTER(DeviceTone), C.POINTER(DeviceAlpha), C.POINTER(DeviceDest), C.POINTER(Decoded)]
+    L.hm_decode_frames_to_device_ootf.argtypes = [C.c_void_p, C.POINTER(C.c_uint32), C.c_int32, C.POINTER(DecodeParams), C.POINTER(DeviceView), C.POINTER(DeviceLight),
+                                                  C.POINTER(DeviceOotf), C.POINTER(DeviceTone), C.POINTER(DeviceDest), C.POINTER(Decoded), C.POINTER(C.c_int32)]
+    L.hm_pipeline_submit_to_device_ootf.argtypes = [C.c_void_p, C.c_char_p, C.c_size_t, C.c_uint32, C.c_uint64, C.POINTER(DeviceView), C.POINTER(DeviceLight),
+                                                    C.POINTER(DeviceOotf), C.POINTER(DeviceTone), C.POINTER(DeviceAlpha), C.POINTER(DeviceDest)]
+    L.hm_ootf_to_tensor.argtypes = [C.c_int, C.c_int, C.c_int, C.c_int, C.c_void_p, C.c_int, C.POINTER(DeviceView), C.POINTER(DeviceLight), C.POINTER(DeviceOotf),
+                                    C.POINTER(DeviceTone), C.POINTER(DeviceAlpha), C.POINTER(DeviceDest), C.c_void_p]
+    L.hm_ootf_gamma.argtypes = [C.POINTER(DeviceOotf), C.POINTER(C.c_double)]
+    L.hm_ootf_table.argtypes = [C.POINTER(DeviceOotf), C.c_float, C.c_int, C.POINTER(C.c_float)]
+    L.hm_ootf_luma.argtypes = [C.c_int, C.POINTER(C.c_float * 3)]
     L.hm_device_planes_bytes.argtypes = [C.c_int, C.c_int, C.c_int, C.c_int, C.POINTER(DevicePlanes), C.POINTER(C.c_int64 * 4)]
     L.hm_device_planes_bytes.restype = C.c_int64
     L.hm_planes_to_tensor.argtypes = [C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, C.POINTER(C.c_void_p * 4), C.POINTER(C.c_int32 * 4), C.POINTER(DevicePlanes),

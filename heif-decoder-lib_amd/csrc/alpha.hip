@@ -13,8 +13,8 @@
 //                    order.  The unstaged form, for all three filters.
 //   k_alpha_v        the vertical sums of ONE pixel per lane, then the mode's rule, then `finish` or matrix, tone and colour_out;
 //                    3 or 4 channels are written.
-// LDS (LIT only): as light.hip has it - lin, enc, thr and sg in the pointwise kernels, lin in k_alpha_h, enc, thr and sg in k_alpha_v; at
-// most 48 KB.  The mode, P and the background (as floats: lin[] of it under a light step, looked up on the host) are kernel arguments.
+// LDS (LIT only): as light.hip has it - lin, enc, the tone and the OOTF tables in the pointwise kernels, lin in k_alpha_h, enc and the
+// tone and OOTF tables in k_alpha_v; at most 56 KB.  The OOTF step (light_step.h: ootf_map) acts on r_c in front of the matrix.The mode, P and the background (as floats: lin[] of it under a light step, looked up on the host) are kernel arguments.
 // -ffp-contract=off, __fmul_rn / __fadd_rn / __fsub_rn / __fdiv_rn throughout: no fused multiply-add, no reciprocal.
 #include "hm_devdest.h"
 #include "light_step.h"
@@ -48,6 +48,7 @@ template <bool LIT, typename OutT>
 __device__ __forceinline__ void colour_elems(const Light& L, const float* vl, float r[3], const Affine& a, OutT* o)
 {
   if constexpr (LIT) {
+    if (L.ootf) ootf_map(L, ootf_tables(L, vl), r);
     gamut(L, r);
     if (L.tone) tone_map(vl + (L.encode ? 1 << L.ebits : 0), r);
 #pragma unroll
@@ -87,7 +88,7 @@ __global__ __launch_bounds__(256) void k_alpha_tensor(const uint8_t* __restrict_
   typedef typename std::conditional<SB == 1, uint8_t, uint16_t>::type InT;
   constexpr int P = 16 / (int)sizeof(OutT); // pixels per lane
   constexpr int NB = P * 4 * SB;            // input bytes per lane: a multiple of 16
-  if constexpr (LIT) fill_tables(lds, L.lin, 1 << L.bits, L.enc, L.encode ? 1 << L.ebits : 0, L.tone, 2 * TONE_STEPS);
+  if constexpr (LIT) fill_tables(lds, L.lin, 1 << L.bits, L.enc, L.encode ? 1 << L.ebits : 0, L.tone, L.tone ? 2 * TONE_STEPS : 0, L.ootf, 2 * OOTF_STEPS);
   const int lane = threadIdx.x & 63, y = blockIdx.y * 4 + (threadIdx.x >> 6);
   if (y >= h) return;
   uint8_t* orow = dst + (long long)y * row_pitch;
@@ -150,7 +151,7 @@ __global__ __launch_bounds__(256) void k_alpha_nearest(const uint8_t* __restrict
                                                        uint8_t* __restrict__ dst, long long row_pitch, long long plane_pitch, Affine a, Light L, Alpha A)
 {
   extern __shared__ __attribute__((aligned(16))) float lds[];
-  if constexpr (LIT) fill_tables(lds, L.lin, 1 << L.bits, L.enc, L.encode ? 1 << L.ebits : 0, L.tone, 2 * TONE_STEPS);
+  if constexpr (LIT) fill_tables(lds, L.lin, 1 << L.bits, L.enc, L.encode ? 1 << L.ebits : 0, L.tone, L.tone ? 2 * TONE_STEPS : 0, L.ootf, 2 * OOTF_STEPS);
   const int j = blockIdx.x * 64 + (threadIdx.x & 63), k = blockIdx.y * 4 + (threadIdx.x >> 6);
   if (j >= ow || k >= oh) return;
   const int sx = j * n_w / ow, sy = k * n_h / oh;
@@ -223,7 +224,7 @@ __global__ __launch_bounds__(256) void k_alpha_v(const float* __restrict__ tmp, 
 {
   extern __shared__ __attribute__((aligned(16))) float lds[];
   if constexpr (LIT) {
-    if (L.encode || L.tone) fill_tables(lds, L.enc, L.encode ? 1 << L.ebits : 0, L.tone, 2 * TONE_STEPS, nullptr, 0); // (uniform: the barrier inside is met by every thread or by none)
+    if (L.encode || L.tone || L.ootf) fill_tables(lds, L.enc, L.encode ? 1 << L.ebits : 0, L.tone, L.tone ? 2 * TONE_STEPS : 0, L.ootf, 2 * OOTF_STEPS); // (uniform: the barrier inside is met by every thread or by none)
   }
   const int j = blockIdx.x * 64 + (threadIdx.x & 63), k = blockIdx.y * 4 + (threadIdx.x >> 6);
   if (j >= ow || k >= oh) return;

@@ -833,13 +833,16 @@ float hm_tone_peak_of(int has_clli, unsigned max_cll, int has_mdcv, unsigned mdc
 // the tone step into the plan of its light step (light_plan_of); the static checks have passed
 static int tone_plan_of(const hm_device_tone* tone, hm_light_plan* lp)
 {
-  if (tone->unit_nits == 0.0f && lp->from_transfer != 16)
+  // behind an OOTF step (resolved into lp already) light value g stands for display_peak, and nothing brighter comes out of it
+  const float unit_nits = tone->unit_nits != 0.0f ? tone->unit_nits : lp->ootf ? lp->ootf_peak : 0.0f;
+  const float src_peak = tone->src_peak != 0.0f ? tone->src_peak : lp->ootf ? lp->ootf_peak : 0.0f;
+  if (unit_nits == 0.0f && lp->from_transfer != 16)
     return hm_fail(HM_ERR_INVALID_ARG, "tone: unit_nits must be given for transfer characteristics %d (only PQ says what 1.0 stands for)", lp->from_transfer);
-  if (tone->src_peak == 0.0f) return hm_fail(HM_ERR_INVALID_ARG, "tone: src_peak must be given: the pixels carry no light levels"); // (else the knee has been judged)
+  if (src_peak == 0.0f) return hm_fail(HM_ERR_INVALID_ARG, "tone: src_peak must be given: the pixels carry no light levels"); // (else the knee has been judged)
   lp->tone = 1;
   if (tone->out_bits == 8) lp->enc_bits = 8;
-  lp->src_peak = tone->src_peak; lp->dst_peak = tone->dst_peak;
-  lp->unit_nits = tone->unit_nits != 0.0f ? tone->unit_nits : 10000.0f;
+  lp->src_peak = src_peak; lp->dst_peak = tone->dst_peak;
+  lp->unit_nits = unit_nits != 0.0f ? unit_nits : 10000.0f;
   lp->out_unit_nits = tone->out_unit_nits != 0.0f ? tone->out_unit_nits : tone->dst_peak;
   return HM_OK;
 }
@@ -856,22 +859,122 @@ int hm_tone_table(const hm_device_tone* tone, float gain, int which, float* out)
   return HM_TONE_STEPS;
 }
 
+// ---- the OOTF step (hm_device_ootf) ----------------------------------------------------------------------------------------------
+
 namespace {
 
-// the tables a light plan's kernels read, one behind the other: lin, then enc, then thr and sg (hm_out_write; the plan may be NULL -
-// no light step, no tables)
+// the system gamma of BT.2100 Table 5 for a display peak L (cd/m2): note 5e inside 400 .. 2000, note 5f outside; gamma != 0: as given
+double ootf_gamma_of(double L, double gamma)
+{
+  if (gamma != 0.0) return gamma;
+  if (L >= 400.0 && L <= 2000.0) return 1.2 + 0.42 * std::log10(L / 1000.0);
+  return 1.2 * std::pow(1.111, std::log2(L / 1000.0));
+}
+
+// thr[HM_OOTF_STEPS], then sg[HM_OOTF_STEPS] (include/heif_mi355x.h); gamma resolved
+void fill_ootf_tables(double g, double gamma, float* thr, float* sg)
+{
+  const int n = HM_OOTF_STEPS;
+  const double top = (double)(n - 1);
+  if (thr) {
+    thr[0] = 0.0f;
+    for (int i = 1; i < n; i++) thr[i] = (float)(g * light_of_code(18, ((double)i - 0.5) / top));
+  }
+  if (!sg) return;
+  for (int k = 1; k < n; k++) sg[k] = (float)std::pow(light_of_code(18, (double)k / top), gamma - 1.0);
+  sg[0] = sg[1];
+}
+
+// the step's own refusals
+int ootf_check(const hm_device_ootf* o)
+{
+  if (o->kind != HM_OOTF_HLG) return hm_fail(HM_ERR_INVALID_ARG, "ootf: unknown kind %d", o->kind);
+  for (int i = 0; i < 5; i++)
+    if (o->reserved[i]) return hm_fail(HM_ERR_INVALID_ARG, "ootf: reserved is not 0");
+  if (!nits_ok(o->display_peak)) return hm_fail(HM_ERR_INVALID_ARG, "ootf: display_peak %g is not finite, above 0 and at most 10000", (double)o->display_peak);
+  if (!std::isfinite(o->gamma) || o->gamma < 0.0f) return hm_fail(HM_ERR_INVALID_ARG, "ootf: gamma %g is not finite and 0 or above", (double)o->gamma);
+  return HM_OK;
+}
+
+// ... and those of the request around it
+int ootf_check_request(const hm_out_steps* st)
+{
+  const hm_device_ootf* o = st->ootf;
+  const hm_device_light* l = st->light;
+  if (!l) return hm_fail(HM_ERR_INVALID_ARG, "ootf: null light step");
+  const int rc = ootf_check(o);
+  if (rc) return rc;
+  if (st->gain) return hm_fail(HM_ERR_UNSUPPORTED, "ootf: a gain step beside the OOTF step is not supported (a gain map's base is SDR)");
+  if (st->alpha && st->alpha->mode == HM_ALPHA_PREMULTIPLIED)
+    return hm_fail(HM_ERR_INVALID_ARG, "ootf: HM_ALPHA_PREMULTIPLIED beside the OOTF step (the luminance of premultiplied light is not the scene's)");
+  if (l->from_transfer != 0 && l->from_transfer != 18)
+    return hm_fail(HM_ERR_INVALID_ARG, "ootf: from_transfer %d is not 18 (the OOTF of BT.2100 renders HLG scene light)", l->from_transfer);
+  if (l->to_transfer == 18)
+    return hm_fail(HM_ERR_INVALID_ARG, "ootf: to_transfer 18 (display light through the OETF alone is no HLG signal; the inverse OOTF is out of scope)");
+  if (st->tone && st->tone->src_peak == 0.0f && nits_ok(st->tone->dst_peak) && tone_knee(o->display_peak, st->tone->dst_peak) < 0.0) // (src_peak 0: display_peak)
+    return hm_fail(HM_ERR_INVALID_ARG, "tone: the knee of %g -> %g cd/m2 lies below black (KS < 0)", (double)o->display_peak, (double)st->tone->dst_peak);
+  return HM_OK;
+}
+
+} // namespace
+
+int hm_ootf_gamma(const hm_device_ootf* ootf, double* gamma)
+{
+  if (!ootf || !gamma) return hm_fail(HM_ERR_INVALID_ARG, "null argument");
+  const int rc = ootf_check(ootf);
+  if (rc) return rc;
+  *gamma = ootf_gamma_of((double)ootf->display_peak, (double)ootf->gamma);
+  return HM_OK;
+}
+
+int hm_ootf_table(const hm_device_ootf* ootf, float gain, int which, float* out)
+{
+  if (!ootf || !out) return hm_fail(HM_ERR_INVALID_ARG, "null argument");
+  if (which != 0 && which != 1) return hm_fail(HM_ERR_INVALID_ARG, "ootf: table %d is not 0 (thr) or 1 (sg)", which);
+  if (!std::isfinite(gain) || !(gain > 0.0f)) return hm_fail(HM_ERR_INVALID_ARG, "light: gain %g is not finite and above 0", (double)gain);
+  const int rc = ootf_check(ootf);
+  if (rc) return rc;
+  fill_ootf_tables((double)gain, ootf_gamma_of((double)ootf->display_peak, (double)ootf->gamma), which ? nullptr : out, which ? out : nullptr);
+  return HM_OOTF_STEPS;
+}
+
+int hm_ootf_luma(int primaries, float out[3])
+{
+  if (!out) return hm_fail(HM_ERR_INVALID_ARG, "null argument");
+  double M[9];
+  if (!primaries_to_xyz(primaries, M)) return hm_fail(HM_ERR_UNSUPPORTED, "light: colour primaries %d are not supported", primaries);
+  for (int c = 0; c < 3; c++) out[c] = (float)M[3 + c];
+  return HM_OK;
+}
+
+// the OOTF step into the plan of its light step (light_plan_of); the static checks have passed
+static int ootf_plan_of(const hm_device_ootf* o, hm_light_plan* lp)
+{
+  if (lp->from_transfer != 18)
+    return hm_fail(HM_ERR_INVALID_ARG, "ootf: the image's from_transfer %d is not 18 (the OOTF of BT.2100 renders HLG scene light)", lp->from_transfer);
+  lp->ootf = 1;
+  lp->ootf_peak = o->display_peak; lp->ootf_gamma = o->gamma;
+  return hm_ootf_luma(lp->from_primaries, lp->y);
+}
+
+namespace {
+
+// the tables a light plan's kernels read, one behind the other: lin, then enc, then thr and sg of the tone step, then thr and sg of
+// the OOTF step (hm_out_write; the plan may be NULL - no light step, no tables)
 struct LightTables {
   const hm_light_plan* lp;
-  size_t n, ne, nt;
+  size_t n, ne, nt, no;
   explicit LightTables(const hm_light_plan* plan)
-    : lp(plan), n(plan ? (size_t)1 << plan->bits : 0), ne(plan && plan->encode ? (size_t)1 << plan->enc_bits : 0), nt(plan && plan->tone ? 2 * (size_t)HM_TONE_STEPS : 0) {}
-  size_t bytes() const { return (n + ne + nt) * sizeof(float); }
+    : lp(plan), n(plan ? (size_t)1 << plan->bits : 0), ne(plan && plan->encode ? (size_t)1 << plan->enc_bits : 0), nt(plan && plan->tone ? 2 * (size_t)HM_TONE_STEPS : 0),
+      no(plan && plan->ootf ? 2 * (size_t)HM_OOTF_STEPS : 0) {}
+  size_t bytes() const { return (n + ne + nt + no) * sizeof(float); }
   void fill(float* host) const
   {
     if (!lp) return;
     fill_light_table(lp->from_transfer, lp->bits, (double)lp->gain, false, host);
     if (lp->encode) fill_light_table(lp->to_transfer, lp->enc_bits, (double)lp->gain, true, host + n);
     if (lp->tone) fill_tone_tables((double)lp->gain, lp->src_peak, lp->dst_peak, lp->unit_nits, lp->out_unit_nits, host + n + ne, host + n + ne + HM_TONE_STEPS);
+    if (lp->ootf) fill_ootf_tables((double)lp->gain, ootf_gamma_of((double)lp->ootf_peak, (double)lp->ootf_gamma), host + n + ne + nt, host + n + ne + nt + HM_OOTF_STEPS);
   }
   // the kernels' arguments, the table pointers still NULL ...
   hm_light_args args(int src_bytes) const
@@ -882,10 +985,15 @@ struct LightTables {
     if (!lp) return la;
     la.bits = lp->bits; la.enc_bits = lp->enc_bits; la.src_bytes = src_bytes; la.encode = lp->encode; la.matrix = lp->matrix;
     std::memcpy(la.m, lp->m, sizeof(la.m));
+    std::memcpy(la.y, lp->y, sizeof(la.y));
     return la;
   }
   // ... and pointed at the device copy of what fill wrote
-  void point(hm_light_args* la, const float* dev) const { if (!lp) return; la->lin = dev; la->enc = lp->encode ? dev + n : nullptr; la->tone = lp->tone ? dev + n + ne : nullptr; }
+  void point(hm_light_args* la, const float* dev) const
+  {
+    if (!lp) return;
+    la->lin = dev; la->enc = lp->encode ? dev + n : nullptr; la->tone = lp->tone ? dev + n + ne : nullptr; la->ootf = lp->ootf ? dev + n + ne + nt : nullptr;
+  }
 };
 
 } // namespace
@@ -1030,8 +1138,9 @@ int hm_out_check_static(int out_format, const hm_device_dest* d, const hm_out_st
   if (st->gain) { const int rc = gain_check(st); if (rc) return rc; }
   if (a && a->mode == HM_ALPHA_PREMULTIPLIED && l && l->to_transfer != HM_LIGHT_LINEAR)
     return hm_fail(HM_ERR_INVALID_ARG, "alpha: HM_ALPHA_PREMULTIPLIED beside a light step that re-encodes (transfer %d; encoded premultiplied light is not a defined result)", l->to_transfer);
+  if (st->ootf) { const int rc = ootf_check_request(st); if (rc) return rc; }
   if (tone) {
-    const int rc = tone_check(tone, !explicit_from);
+    const int rc = tone_check(tone, !explicit_from || st->ootf); // (beside an OOTF step src_peak and unit_nits have a default of their own: display_peak)
     if (rc) return rc;
     if (tone->out_bits == 8) {
       if (d->dtype == HM_DEV_U16) return hm_fail(HM_ERR_INVALID_ARG, "tone: out_bits 8 with HM_DEV_U16 (HM_DEV_U8 holds the codes)");
@@ -1062,6 +1171,7 @@ static int out_resolve_profile(int out_format, const hm_out_image* img, const hm
   }
   if (!st->light) return HM_OK;
   if ((rc = light_plan_of(out_format, bits, img->transfer, img->primaries, st->light, &p->lp))) return rc;
+  if (st->ootf && (rc = ootf_plan_of(st->ootf, &p->lp))) return rc;
   if (st->tone && (rc = tone_plan_of(st->tone, &p->lp))) return rc;
   return st->gain ? gain_plan_of(st->gain, img, &p->vp, &p->lp, &p->gp) : (int)HM_OK;
 }
@@ -1287,6 +1397,16 @@ int hm_alpha_to_tensor(int out_format, int bits, int src_w, int src_h, const voi
 {
   if (!d_src || !dest || !alpha) return hm_fail(HM_ERR_INVALID_ARG, "null argument");
   return out_to_tensor(out_format, bits, src_w, src_h, d_src, src_stride, hm_out_steps{view, light, tone, alpha}, dest, stream);
+}
+
+int hm_ootf_to_tensor(int out_format, int bits, int src_w, int src_h, const void* d_src, int src_stride, const hm_device_view* view, const hm_device_light* light,
+                      const hm_device_ootf* ootf, const hm_device_tone* tone, const hm_device_alpha* alpha, const hm_device_dest* dest, void* stream)
+{
+  if (!ootf) // the same call without the step
+    return alpha ? hm_alpha_to_tensor(out_format, bits, src_w, src_h, d_src, src_stride, view, light, tone, alpha, dest, stream)
+                 : hm_tone_to_tensor(out_format, bits, src_w, src_h, d_src, src_stride, view, light, tone, dest, stream);
+  if (!d_src || !dest) return hm_fail(HM_ERR_INVALID_ARG, "null argument");
+  return out_to_tensor(out_format, bits, src_w, src_h, d_src, src_stride, hm_out_steps{view, light, tone, alpha, nullptr, ootf}, dest, stream);
 }
 
 // ---- planar views: every plane an image of its own ------------------------------------------------------------------------------

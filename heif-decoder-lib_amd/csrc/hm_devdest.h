@@ -138,15 +138,23 @@ typedef struct hm_light_plan {
   int32_t tone;          // a tone step runs
   int32_t enc_bits;      // of the codes the finish stores: bits, or 8 under the 8-bit finish
   float src_peak, dst_peak, unit_nits, out_unit_nits;
+  // the OOTF step (hm_device_ootf) beside it, resolved
+  int32_t ootf;          // an OOTF step runs
+  float ootf_peak, ootf_gamma; // display_peak and gamma of the request (gamma 0: the system gamma of the peak): what the tables are built from
+  float y[3];            // the luminance weights of from_primaries
 } hm_light_plan;
 // (the step's refusals: hm_out_check_static; its plan: hm_out_resolve)
 // ---- the tone step (hm_device_tone) inside the light step: two tables of HM_TONE_STEPS entries, built in devdest.cpp ----
 // the peak rule of include/heif_mi355x.h on an item's raw properties
 float hm_tone_peak_of(int has_clli, unsigned max_cll, int has_mdcv, unsigned mdcv_max);
 
-// what the kernels get: device pointers of lin[1 << bits], (encode) enc[1 << enc_bits] and (tone) thr[HM_TONE_STEPS] with sg[HM_TONE_STEPS]
-// behind it; src_bytes: bytes of a source sample (the plan's sample_bytes are the destination's sibling target's)
-typedef struct hm_light_args { const float* lin; const float* enc; const float* tone; int32_t bits, enc_bits, src_bytes, encode, matrix; float m[9]; } hm_light_args;
+// what the kernels get: device pointers of lin[1 << bits], (encode) enc[1 << enc_bits], (tone) thr[HM_TONE_STEPS] with sg[HM_TONE_STEPS]
+// behind it and (ootf) thr[HM_OOTF_STEPS] with sg[HM_OOTF_STEPS] behind it, y the step's luminance weights; src_bytes: bytes of a source
+// sample (the plan's sample_bytes are the destination's sibling target's)
+typedef struct hm_light_args {
+  const float* lin; const float* enc; const float* tone; int32_t bits, enc_bits, src_bytes, encode, matrix; float m[9];
+  const float* ootf; float y[3];
+} hm_light_args;
 int hm_launch_light_tensor(const hm_dest_plan* p, const hm_light_args* la, const void* src, int src_stride, int w, int rows, void* dst, const float scale[4],
                            const float bias[4], hipStream_t s);
 int hm_launch_light_nearest(const hm_dest_plan* p, const hm_light_args* la, const void* src, int src_stride, int n_w, int n_h, int ow, int oh, void* dst,
@@ -216,10 +224,13 @@ int hm_launch_gain_resample(const hm_dest_plan* p, const hm_light_args* la, cons
 // k_light_h alone: the horizontal pass of hm_launch_light_resample (light.hip)
 int hm_launch_light_h(const hm_dest_plan* p, const hm_light_args* la, const hm_resample_args* r, hipStream_t s);
 
-// ---- the device write: the interleaved pixels of one image through the steps of a request - view, light (with tone inside it), alpha,
-//      gain - into a hm_device_dest.  One request (hm_out_steps), one plan (hm_out_plan), one writer (hm_out_write); a further step is
+// ---- the device write: the interleaved pixels of one image through the steps of a request - view, light (with tone and the OOTF
+//      inside it), alpha, gain - into a hm_device_dest.  One request (hm_out_steps), one plan (hm_out_plan), one writer (hm_out_write); a further step is
 //      a case inside them ----
-typedef struct hm_out_steps { const hm_device_view* view; const hm_device_light* light; const hm_device_tone* tone; const hm_device_alpha* alpha; const hm_device_gain* gain; } hm_out_steps; // any may be NULL
+typedef struct hm_out_steps {
+  const hm_device_view* view; const hm_device_light* light; const hm_device_tone* tone; const hm_device_alpha* alpha; const hm_device_gain* gain;
+  const hm_device_ootf* ootf;
+} hm_out_steps; // any may be NULL
 // what the image reports (hm_decoded); with a gain step the map beside it (map_w 0: not known yet - the step's geometry is not judged)
 typedef struct hm_out_image { int32_t w, h, bits, transfer, primaries; int32_t map_w, map_h, map_bits; } hm_out_image;
 // the gain map's samples on the device (one channel; one byte per sample at 8 bits, else two), row 0 = the map's row 0
@@ -236,8 +247,9 @@ typedef struct hm_out_plan {
 // the target the destination is judged by: hm_alpha_dest_format with an alpha step (negative: the step's own refusals), else with
 // tone->out_bits == 8 the 8-bit sibling of a 16-bit three-channel target, else out_format
 int hm_out_dest_format(int out_format, const hm_out_steps* st);
-// what depends on the request alone: the alpha step's own refusals, then the tone step's, the light step's (from_* == 0: allowed
-// unless `explicit_from`, which wants src_peak and unit_nits given too) and the destination's, each against hm_out_dest_format
+// what depends on the request alone: the alpha step's own refusals, then the gain, OOTF and tone steps', the light step's (from_* == 0:
+// allowed unless `explicit_from`, which wants src_peak and unit_nits given too - beside an OOTF step both may stay 0: display_peak) and
+// the destination's, each against hm_out_dest_format
 int hm_out_check_static(int out_format, const hm_device_dest* d, const hm_out_steps* st, int explicit_from);
 // ... and what depends on the image.  The size: the view, the destination against the size written, its len.  The profile
 // (know_profile != 0): hm_out_check_static again, the depth, the alpha step's background against the peak, the light step's from_* == 0

@@ -855,7 +855,7 @@ void parse_picture(const hm_file* f, uint32_t id, bool few_pictures, int strict,
 
 int target_check_shape(const OutputTarget& t)
 {
-  const bool ok = !(t.dest && t.planes) && (!t.light || t.dest) && (!t.tone || t.light) && (!t.alpha || (t.dest && !t.view_later)) && (!t.gain || (t.light && !t.view_later)) && (!t.view || t.dest || t.planes) && (!t.view_later || (t.view && t.dest)) &&
+  const bool ok = !(t.dest && t.planes) && (!t.light || t.dest) && (!t.tone || t.light) && (!t.ootf || t.light) &&(!t.alpha || (t.dest && !t.view_later)) && (!t.gain || (t.light && !t.view_later)) && (!t.view || t.dest || t.planes) && (!t.view_later || (t.view && t.dest)) &&
                   (!t.planes_later || (t.view && t.planes));
   return ok ? (int)HM_OK : hm_fail(HM_ERR_INTERNAL, "output target: dest%s view%s planes%s light%s tone%s alpha%s gain%s do not go together", t.dest ? "+" : "-", t.view ? "+" : "-",
                                    t.planes ? "+" : "-", t.light ? "+" : "-", t.tone ? "+" : "-", t.alpha ? "+" : "-", t.gain ? "+" : "-");
@@ -1722,6 +1722,17 @@ int hm_decode_item_to_device_alpha(const hm_file* f, uint32_t id, const hm_decod
   return decode_item_to(f, id, params, t, out);
 }
 
+int hm_decode_item_to_device_ootf(const hm_file* f, uint32_t id, const hm_decode_params* params, const hm_device_view* view, const hm_device_light* light,
+                                  const hm_device_ootf* ootf, const hm_device_tone* tone, const hm_device_alpha* alpha, const hm_device_dest* dest, hm_decoded* out)
+{
+  if (!ootf) // the same call without the step
+    return alpha ? hm_decode_item_to_device_alpha(f, id, params, view, light, tone, alpha, dest, out) : hm_decode_item_to_device_tone(f, id, params, view, light, tone, dest, out);
+  if (!f || !params || !dest || !out) return hm_fail(HM_ERR_INVALID_ARG, "null argument");
+  if (!light) return hm_fail(HM_ERR_INVALID_ARG, "ootf: null light step");
+  // (the tone step's src_peak == 0 is display_peak here: no property of the item is read)
+  return decode_item_to(f, id, params, OutputTarget::to_dest(dest, view, light, tone, alpha, nullptr, ootf), out);
+}
+
 int hm_file_item_light_levels(const hm_file* f, uint32_t id, hm_light_levels* out)
 {
   if (!f || !out) return hm_fail(HM_ERR_INVALID_ARG, "null argument");
@@ -2068,6 +2079,17 @@ int hm_decode_frames_to_device_tone(const hm_file* f, const uint32_t* frames, in
   if (!light) return hm_fail(HM_ERR_INVALID_ARG, "tone: null light step");
   const hm_device_tone own = tone_for_item(f, 0, tone); // (a frame carries no properties)
   return decode_sequence(f, frames, 0, count, params, nullptr, OutputTarget::to_dest(dests, view, light, &own), out, failed_frame);
+}
+
+int hm_decode_frames_to_device_ootf(const hm_file* f, const uint32_t* frames, int32_t count, const hm_decode_params* params, const hm_device_view* view,
+                                    const hm_device_light* light, const hm_device_ootf* ootf, const hm_device_tone* tone, const hm_device_dest* dests, hm_decoded* out,
+                                    int32_t* failed_frame)
+{
+  if (!ootf) return hm_decode_frames_to_device_tone(f, frames, count, params, view, light, tone, dests, out, failed_frame); // the same call without the step
+  if (failed_frame) *failed_frame = -1;
+  if (!frames || !dests) return hm_fail(HM_ERR_INVALID_ARG, "null argument");
+  if (!light) return hm_fail(HM_ERR_INVALID_ARG, "ootf: null light step");
+  return decode_sequence(f, frames, 0, count, params, nullptr, OutputTarget::to_dest(dests, view, light, tone, nullptr, nullptr, ootf), out, failed_frame);
 }
 
 int hm_decode_frames_to_device_planes(const hm_file* f, const uint32_t* frames, int32_t count, const hm_decode_params* params, const hm_device_planes* planes,

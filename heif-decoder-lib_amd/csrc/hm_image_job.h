@@ -113,17 +113,18 @@ struct OutputTarget {
   const hm_device_alpha* alpha = nullptr;      // the alpha step in the write of dest (alone, or beside light and tone)
   const hm_device_gain* gain = nullptr;        // the gain step beside light (resolved by the entry point: map_item is the map's item, params are explicit)
   const struct PlanarImage* gain_map = nullptr; // ... and its decoded map (job_enqueue sets it; null with a gain step of weight 0)
+  const hm_device_ootf* ootf = nullptr;        // the OOTF step beside light (a tone step beside it keeps its zeros: they resolve to display_peak)
   hm_view_scratch* scratch = nullptr;          // tap tables and the intermediate of the resampling step, the tables of the light step
   hm_view_item* view_later = nullptr;          // view + dest: the view is not written, only described there - the caller writes it with those of other images
   hm_planes_view_item* planes_later = nullptr; // the same for view + planes
   static OutputTarget to_dest(const hm_device_dest* d, const hm_device_view* v = nullptr, const hm_device_light* l = nullptr, const hm_device_tone* tn = nullptr,
-                              const hm_device_alpha* a = nullptr, const hm_device_gain* g = nullptr)
+                              const hm_device_alpha* a = nullptr, const hm_device_gain* g = nullptr, const hm_device_ootf* o = nullptr)
   {
     OutputTarget t;
-    t.dest = d; t.view = v; t.light = l; t.tone = tn; t.alpha = a; t.gain = g;
+    t.dest = d; t.view = v; t.light = l; t.tone = tn; t.alpha = a; t.gain = g; t.ootf = o;
     return t;
   }
-  hm_out_steps steps() const { return hm_out_steps{view, light, tone, alpha, gain}; } // the request of the device write (hm_devdest.h)
+  hm_out_steps steps() const { return hm_out_steps{view, light, tone, alpha, gain, ootf}; } // the request of the device write (hm_devdest.h)
   static OutputTarget to_planes(const hm_device_planes* p, const hm_device_view* v = nullptr)
   {
     OutputTarget t;
@@ -131,7 +132,7 @@ struct OutputTarget {
     return t;
   }
 };
-// dest xor planes (or neither); light only with dest; tone only with light; alpha only with dest and never with view_later; gain only with light and
+// dest xor planes (or neither); light only with dest; tone only with light; ootf only with light; alpha only with dest and never with view_later; gain only with light and
 // never with view_later; view only with one of the two; a *_later only with view and its own kind of destination
 int target_check_shape(const OutputTarget& t);
 
@@ -145,6 +146,7 @@ struct OwnedTarget {
   hm_device_tone tone{};
   hm_device_alpha alpha{};
   hm_device_gain gain{};
+  hm_device_ootf ootf{};
   OutputTarget t;
   OwnedTarget() = default;
   OwnedTarget(const OwnedTarget&) = delete;
@@ -159,6 +161,7 @@ struct OwnedTarget {
     if (from.tone) { tone = *from.tone; t.tone = &tone; }
     if (from.alpha) { alpha = *from.alpha; t.alpha = &alpha; }
     if (from.gain) { gain = *from.gain; t.gain = &gain; }
+    if (from.ootf) { ootf = *from.ootf; t.ootf = &ootf; }
   }
 };
 

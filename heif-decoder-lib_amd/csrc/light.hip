@@ -12,8 +12,11 @@
 //                    one index of three planes -, then matrix and finish.
 // The tone step (hm_device_tone) sits between matrix and finish: the max of R, G, B is searched in thr[2048] like a code in enc, and
 // the pixel is scaled by sg[] at the count - a wave-uniform branch, like `encode` and `matrix`.
+// The OOTF step (hm_device_ootf) sits in front of the matrix: the scene luminance Ys = y . RGB is searched in thr[1024], and the pixel is
+// scaled by sg[] at the count - wave-uniform like the others (L.ootf is a kernel argument).
 // LDS: lin[1 << bits], when re-encoding enc[1 << enc_bits] behind it (1 KB each at 8 bits, 16 KB each at 12), with a tone step thr
-// and sg (8 KB each) behind those - at most 48 KB -, filled once per workgroup.  The lookups are data-dependent ds_read_b32: lanes
+// and sg (8 KB each) behind those, with an OOTF step its thr and sg (4 KB each) behind those - at most 56 KB, and nothing more than
+// before for a call without the OOTF step -, filled once per workgroup.  The lookups are data-dependent ds_read_b32: lanes
 // that meet the same entry are served by one broadcast, different entries of one bank serialise - a flat image is the best case,
 // noise the worst; no layout of a table changes that.
 // The matrix and the scalars of the step are kernel arguments (SGPRs).  -ffp-contract=off, __fmul_rn / __fadd_rn throughout.
@@ -32,8 +35,9 @@ __device__ __forceinline__ void pixel(const Light& L, const float* lds, unsigned
 {
   const unsigned peak = (1u << L.bits) - 1u;
   float r[3] = {lds[min(v0, peak)], lds[min(v1, peak)], lds[min(v2, peak)]};
-  gamut(L, r);
   const float* enc = lds + (1 << L.bits);
+  if (L.ootf) ootf_map(L, ootf_tables(L, enc), r);
+  gamut(L, r);
   if (L.tone) tone_map(enc + (L.encode ? 1 << L.ebits : 0), r);
   o[0] = colour_out<OutT>(L, enc, r[0], a.scale[0], a.bias[0]);
   o[1] = colour_out<OutT>(L, enc, r[1], a.scale[1], a.bias[1]);
@@ -51,7 +55,7 @@ __global__ __launch_bounds__(256) void k_light_tensor(const uint8_t* __restrict_
   typedef typename std::conditional<SB == 1, uint8_t, uint16_t>::type InT;
   constexpr int P = 16 / (int)sizeof(OutT); // pixels per lane
   constexpr int NB = P * C * SB;            // input bytes per lane
-  fill_tables(lds, L.lin, 1 << L.bits, L.enc, L.encode ? 1 << L.ebits : 0, L.tone, 2 * TONE_STEPS);
+  fill_tables(lds, L.lin, 1 << L.bits, L.enc, L.encode ? 1 << L.ebits : 0, L.tone, L.tone ? 2 * TONE_STEPS : 0, L.ootf, 2 * OOTF_STEPS);
   const int lane = threadIdx.x & 63, y = blockIdx.y * 4 + (threadIdx.x >> 6);
   if (y >= h) return;
   uint8_t* orow = dst + (long long)y * row_pitch;
@@ -115,7 +119,7 @@ __global__ __launch_bounds__(256) void k_light_nearest(const uint8_t* __restrict
                                                        uint8_t* __restrict__ dst, long long row_pitch, long long plane_pitch, Affine a, Light L)
 {
   extern __shared__ __attribute__((aligned(16))) float lds[];
-  fill_tables(lds, L.lin, 1 << L.bits, L.enc, L.encode ? 1 << L.ebits : 0, L.tone, 2 * TONE_STEPS);
+  fill_tables(lds, L.lin, 1 << L.bits, L.enc, L.encode ? 1 << L.ebits : 0, L.tone, L.tone ? 2 * TONE_STEPS : 0, L.ootf, 2 * OOTF_STEPS);
   const int j = blockIdx.x * 64 + (threadIdx.x & 63), k = blockIdx.y * 4 + (threadIdx.x >> 6);
   if (j >= ow || k >= oh) return;
   const int sx = j * n_w / ow, sy = k * n_h / oh;
@@ -155,7 +159,7 @@ __global__ __launch_bounds__(256) void k_light_v(const float* __restrict__ tmp, 
 {
   extern __shared__ __attribute__((aligned(16))) float lds[];
   const int ne = L.encode ? 1 << L.ebits : 0;
-  if (L.encode || L.tone) fill_tables(lds, L.enc, ne, L.tone, 2 * TONE_STEPS, nullptr, 0); // (uniform: the barrier inside is met by every thread or by none)
+  if (L.encode || L.tone || L.ootf) fill_tables(lds, L.enc, ne, L.tone, L.tone ? 2 * TONE_STEPS : 0, L.ootf, 2 * OOTF_STEPS); // (uniform: the barrier inside is met by every thread or by none)
   const int j = blockIdx.x * 64 + (threadIdx.x & 63), k = blockIdx.y * 4 + (threadIdx.x >> 6);
   if (j >= ow || k >= oh) return;
   const int y0 = first[k], n = count[k]; // (the same in every lane of the wave)
@@ -169,6 +173,7 @@ __global__ __launch_bounds__(256) void k_light_v(const float* __restrict__ tmp, 
     for (int c = 0; c < C; c++) acc[c] = __fadd_rn(acc[c], __fmul_rn(w, CHW ? col[(long long)c * plane] : col[c]));
     col += pitch;
   }
+  if (L.ootf) ootf_map(L, ootf_tables(L, lds), acc);
   gamut(L, acc);
   if (L.tone) tone_map(lds + ne, acc);
   OutT o[C];
@@ -311,12 +316,12 @@ extern "C" const void* hm_light_finish8_kernel_of(int index) // (test_hooks.cpp:
 }
 
 // what the launchers ask for as dynamic LDS (test_hooks.cpp: hm_debug_light_lds); pass 0: k_light_tensor / k_light_nearest, 1: k_light_h,
-// 2: k_light_v
+// 2: k_light_v; tone: bit 0 a tone step, bit 1 an OOTF step
 extern "C" long long hm_light_lds_bytes(int bits, int enc_bits, int encode, int tone, int pass)
 {
   static const float some = 0.0f;
   hm_light_args la = {};
-  la.bits = bits; la.enc_bits = enc_bits; la.encode = encode; la.tone = tone ? &some : nullptr;
+  la.bits = bits; la.enc_bits = enc_bits; la.encode = encode; la.tone = (tone & 1) ? &some : nullptr; la.ootf = (tone & 2) ? &some : nullptr;
   return (long long)(pass == 0 ? light_tables_bytes(&la) : pass == 1 ? light_h_bytes(&la) : light_v_bytes(&la));
 }
 

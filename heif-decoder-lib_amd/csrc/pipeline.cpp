@@ -228,6 +228,19 @@ int hm_pipeline_submit_to_device_alpha(hm_pipeline* p, const uint8_t* heif, size
   return submit(p, heif, size, item_id, tag, t);
 }
 
+// (beside an OOTF step the tone step's src_peak == 0 is display_peak: submit reads no property)
+int hm_pipeline_submit_to_device_ootf(hm_pipeline* p, const uint8_t* heif, size_t size, uint32_t item_id, uint64_t tag, const hm_device_view* view,
+                                      const hm_device_light* light, const hm_device_ootf* ootf, const hm_device_tone* tone, const hm_device_alpha* alpha,
+                                      const hm_device_dest* dest)
+{
+  if (!ootf) // the same call without the step
+    return alpha ? hm_pipeline_submit_to_device_alpha(p, heif, size, item_id, tag, view, light, tone, alpha, dest)
+                 : hm_pipeline_submit_to_device_tone(p, heif, size, item_id, tag, view, light, tone, dest);
+  if (!p || !heif || !dest) return hm_fail(HM_ERR_INVALID_ARG, "null argument");
+  if (!light) return hm_fail(HM_ERR_INVALID_ARG, "ootf: null light step");
+  return submit(p, heif, size, item_id, tag, OutputTarget::to_dest(dest, view, light, tone, alpha, nullptr, ootf));
+}
+
 // (a 'tmap' item's base, map and parameters are read once the file is open: submit)
 int hm_pipeline_submit_to_device_gain(hm_pipeline* p, const uint8_t* heif, size_t size, uint32_t item_id, uint64_t tag, const hm_device_view* view,
                                       const hm_device_light* light, const hm_device_tone* tone, const hm_device_gain* gain, const hm_device_dest* dest)
@@ -287,7 +300,7 @@ static int submit(hm_pipeline* p, const uint8_t* heif, size_t size, uint32_t ite
       hipSetDevice(p->cfg.device); // (the pointers must belong to the device the crew works on)
       OutputTarget t = target;
       hm_device_tone own{};
-      if (t.tone) { own = tone_for_item(im->file, im->job.id, t.tone); t.tone = &own; } // (the image's own peak, before the curve is judged)
+      if (t.tone && !t.ootf) { own = tone_for_item(im->file, im->job.id, t.tone); t.tone = &own; } // (the image's own peak, before the curve is judged)
       hm_device_gain own_gain{};
       if (t.gain) { // (a 'tmap' item: the job decodes its base image, the map beside it)
         uint32_t base = 0;

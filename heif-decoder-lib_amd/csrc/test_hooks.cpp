@@ -68,7 +68,8 @@ __attribute__((visibility("default"))) int hm_debug_kernel_regs(int which, int a
 }
 
 // the dynamic LDS, in bytes, a launch of the light kernels asks for with tables of (bits, enc_bits), re-encoding or not, with a tone step or
-// not; pass 0: the pointwise and nearest kernels, 1: k_light_h, 2: k_light_v (hipFuncGetAttributes does not see dynamic LDS)
+// not (tone: bit 0 the tone step, bit 1 the OOTF step); pass 0: the pointwise and nearest kernels, 1: k_light_h, 2: k_light_v
+// (hipFuncGetAttributes does not see dynamic LDS)
 __attribute__((visibility("default"))) long long hm_debug_light_lds(int bits, int enc_bits, int encode, int tone, int pass)
 {
   return hm_light_lds_bytes(bits, enc_bits, encode, tone, pass);

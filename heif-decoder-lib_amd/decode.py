@@ -20,6 +20,10 @@ gain=dict(headroom=2.0) beside light= renders an SDR image with a gain map (an I
 base image) for a display whose peak is 2 ** headroom times SDR white (math.inf: the full HDR rendition); with
 gain=dict(headroom=..., map_item=id, alternate_headroom=..., map_max=..., ...) any image of the file is the map (a vendor gain map
 among the auxiliary images, its parameters read elsewhere).
+ootf=1000 (or dict(display_peak=1000, gamma=None)) beside light= renders an HLG image's scene light for a display of that peak with
+the reference OOTF of BT.2100 (gamma None: the system gamma of the peak); a tone= behind it then takes the display's peak as the
+content's and as its unit, so light=dict(to_transfer="srgb", to_primaries="bt709"), ootf=1000, tone=dict(dst_peak=203, out_bits=8)
+turns a 10-bit HLG BT.2020 photograph into an sRGB uint8 tensor in one call.
 What the library refuses raises capi.HmError.
 
 Planar YCbCr stays planar: decode_to_planes / decode_sequence_to_planes / decode_batch_to_planes return (Y, Cb, Cr[, A]) ("planar":
@@ -181,6 +185,39 @@ def _tone_of(tone, lit):
     return d
 
 
+def _ootf_of(ootf, lit):
+    """hm_device_ootf (or None) of the ootf= argument: a number (the display's peak in cd/m2) or a dict of display_peak (needed) /
+    gamma (None: the system gamma of that peak); needs a light step"""
+    if ootf is None or ootf is False:
+        return None
+    if isinstance(ootf, bool):
+        raise ValueError(f"ootf {ootf!r}: the display's peak in cd/m2, or a dict")
+    if isinstance(ootf, (int, float)):
+        ootf = {"display_peak": ootf}
+    if not isinstance(ootf, dict):
+        raise ValueError(f"ootf {ootf!r}: the display's peak in cd/m2, or a dict")
+    keys = {"display_peak", "gamma"}
+    if set(ootf) - keys:
+        raise ValueError(f"ootf: unknown keys {sorted(set(ootf) - keys)}, known are {sorted(keys)}")
+    if lit is None:
+        raise ValueError("ootf: needs light= (the OOTF acts on scene light)")
+    if ootf.get("display_peak") is None:
+        raise ValueError("ootf: display_peak (cd/m2 of the display's peak) is needed")
+    d = capi.DeviceOotf()
+    d.kind = capi.HM_OOTF_HLG
+    d.display_peak = float(ootf["display_peak"])
+    g = ootf.get("gamma")
+    if g is not None and float(g) == 0.0:
+        raise ValueError(f"ootf['gamma'] = {g!r}: None asks for the system gamma")
+    d.gamma = 0.0 if g is None else float(g)
+    return d
+
+
+def _ref(s):
+    """a ctypes struct by reference, None as a null pointer"""
+    return C.byref(s) if s is not None else None
+
+
 ALPHA_MODES = {"straight": capi.HM_ALPHA_STRAIGHT, "premultiplied": capi.HM_ALPHA_PREMULTIPLIED, "matte": capi.HM_ALPHA_MATTE}
 
 
@@ -298,7 +335,7 @@ class _File:
 
 
 def decode_to_tensor(data, item_id=0, out_format="rgb", layout="chw", dtype=None, scale=None, bias=None, out=None, stream=None,
-                     host_threads=None, crop=None, size=None, filter="triangle", light=None, tone=None, alpha=None, gain=None):
+                     host_threads=None, crop=None, size=None, filter="triangle", light=None, tone=None, alpha=None, gain=None, ootf=None):
     """Decode one image of a HEIF file (bytes; item_id 0 = the primary item) into a CUDA tensor: C x H x W ("chw") or H x W x C
     ("hwc").  dtype defaults to torch.float32 (out's dtype when out is given).  out: a CUDA tensor of that shape to write into;
     its row (and plane) stride is honoured, bytes between rows are left alone.  stream: a torch.cuda.Stream or a raw stream
@@ -308,7 +345,9 @@ def decode_to_tensor(data, item_id=0, out_format="rgb", layout="chw", dtype=None
     step inside it; alpha: "straight", "premultiplied" or dict(mode="matte", background=(r, g, b)) (see the module's text), the alpha step,
     for a four-channel out_format - a matte gives a tensor of 3 channels.  gain: dict(headroom=...) beside light= (see the module's
     text), the gain step: the image with its gain map for a display of that headroom - item_id may be the 'tmap' item or its base
-    image; with map_item and the explicit parameters any image of the file is the map.  Returns when the pixels are in place."""
+    image; with map_item and the explicit parameters any image of the file is the map.  ootf: the display's peak in cd/m2 or
+    dict(display_peak=..., gamma=None) beside light= (see the module's text), the OOTF step for an HLG image.  Returns when the pixels
+    are in place."""
     import torch
     L = capi.image_lib()
     fmt, lay = _out_format(out_format), _layout(layout)
@@ -321,8 +360,11 @@ def decode_to_tensor(data, item_id=0, out_format="rgb", layout="chw", dtype=None
         lit = _light_of(light)
         ton = _tone_of(tone, lit)
         gn = _gain_of(gain, lit)
+        oo = _ootf_of(ootf, lit)
         if gn is not None and alp is not None:
             raise capi.HmError(-2, "gain: an alpha step beside the gain step is not supported (the open step)")
+        if gn is not None and oo is not None:
+            raise capi.HmError(-2, "ootf: a gain step beside the OOTF step is not supported (a gain map's base is SDR)")
         iid = item_id or L.hm_file_primary_item(f.h)
         sized = iid
         if gn is not None:
@@ -347,6 +389,9 @@ def decode_to_tensor(data, item_id=0, out_format="rgb", layout="chw", dtype=None
             if gn is not None:
                 capi.check_image(L.hm_decode_item_to_device_gain(f.h, iid, C.byref(prm), C.byref(view) if view is not None else None, C.byref(lit),
                                                                  C.byref(ton) if ton is not None else None, C.byref(gn), C.byref(dest), C.byref(d)))
+            elif oo is not None:
+                capi.check_image(L.hm_decode_item_to_device_ootf(f.h, iid, C.byref(prm), _ref(view), C.byref(lit), C.byref(oo), _ref(ton), _ref(alp), C.byref(dest),
+                                                                 C.byref(d)))
             elif alp is not None:
                 capi.check_image(L.hm_decode_item_to_device_alpha(f.h, iid, C.byref(prm), C.byref(view) if view is not None else None,
                                                                   C.byref(lit) if lit is not None else None, C.byref(ton) if ton is not None else None,
@@ -370,13 +415,14 @@ def decode_to_tensor(data, item_id=0, out_format="rgb", layout="chw", dtype=None
 
 
 def decode_batch_to_tensor(files, item_id=0, out_format="rgb", layout="chw", dtype=None, scale=None, bias=None, out=None,
-                           host_threads=None, max_in_flight=4, size=None, crops=None, filter="triangle", light=None, tone=None, alpha=None, gain=None):
+                           host_threads=None, max_in_flight=4, size=None, crops=None, filter="triangle", light=None, tone=None, alpha=None, gain=None,
+                           ootf=None):
     """Decode N equally sized HEIF files through ONE hm_pipeline (the entropy decode of one file runs under the kernels of
     another) into one N x C x H x W ("chw") or N x H x W x C ("hwc") CUDA tensor, each image into its slice.  files: bytes
     objects or paths.  A file of another size than the first (or than `out`) raises ValueError naming it.
     size: (w, h) - files of different sizes are accepted then, each resampled into its slice; crops: one (x, y, w, h) or None per
-    file, the rectangle of that file that is resampled (needs size).  light, tone, alpha, gain: as decode_to_tensor, the same steps for
-    every file (tone's src_peak None: each file's own; gain: each file's own 'tmap' item)."""
+    file, the rectangle of that file that is resampled (needs size).  light, tone, alpha, gain, ootf: as decode_to_tensor, the same steps
+    for every file (tone's src_peak None: each file's own, beside ootf= the display's peak; gain: each file's own 'tmap' item)."""
     import torch
     L = capi.image_lib()
     fmt, lay = _out_format(out_format), _layout(layout)
@@ -388,8 +434,11 @@ def decode_batch_to_tensor(files, item_id=0, out_format="rgb", layout="chw", dty
     lit = _light_of(light)
     ton = _tone_of(tone, lit)
     gn = _gain_of(gain, lit)
+    oo = _ootf_of(ootf, lit)
     if gn is not None and alp is not None:
         raise capi.HmError(-2, "gain: an alpha step beside the gain step is not supported (the open step)")
+    if gn is not None and oo is not None:
+        raise capi.HmError(-2, "ootf: a gain step beside the OOTF step is not supported (a gain map's base is SDR)")
     names, datas = [], []
     for k, entry in enumerate(files):
         if isinstance(entry, (bytes, bytearray, memoryview)):
@@ -457,6 +506,9 @@ def decode_batch_to_tensor(files, item_id=0, out_format="rgb", layout="chw", dty
                     if gn is not None:
                         rc = L.hm_pipeline_submit_to_device_gain(pipe, data, len(data), ids[k], k, C.byref(views[k]) if views[k] is not None else None,
                                                                  C.byref(lit), C.byref(ton) if ton is not None else None, C.byref(gn), C.byref(dest))
+                    elif oo is not None:
+                        rc = L.hm_pipeline_submit_to_device_ootf(pipe, data, len(data), ids[k], k, _ref(views[k]), C.byref(lit), C.byref(oo), _ref(ton), _ref(alp),
+                                                                 C.byref(dest))
                     elif alp is not None:
                         rc = L.hm_pipeline_submit_to_device_alpha(pipe, data, len(data), ids[k], k, C.byref(views[k]) if views[k] is not None else None,
                                                                   C.byref(lit) if lit is not None else None, C.byref(ton) if ton is not None else None,
@@ -502,14 +554,14 @@ def _frame_ids(frames, n_frames):
 
 
 def decode_sequence_to_tensor(data, frames=None, out_format="rgb", layout="chw", dtype=None, scale=None, bias=None, out=None, stream=None,
-                              host_threads=None, crop=None, size=None, filter="triangle", light=None, tone=None):
+                              host_threads=None, crop=None, size=None, filter="triangle", light=None, tone=None, ootf=None):
     """Decode frames of an image sequence (bytes of a file with a 'moov' track) into one CUDA tensor, T x C x H x W ("chw") or
     T x H x W x C ("hwc"), in ONE device batch (hm_decode_frames_to_device_view).  frames: None (all), a range or a list of 1-based
     frame IDs, in any order, repeats allowed - range(1, n + 1, 4) is every fourth frame.  crop / size / filter: the same rectangle
     of every frame, resampled, as in decode_to_tensor; without them every frame must have the size of the first.  out: a CUDA
     tensor of that shape; the row and plane strides of each of its slices are honoured.  light: as decode_to_tensor, the same step for
-    every frame (hm_decode_frames_to_device_light); tone: as decode_to_tensor (a frame carries no light levels: src_peak None is 1000).
-    Returns when the pixels are in place."""
+    every frame (hm_decode_frames_to_device_light); tone: as decode_to_tensor (a frame carries no light levels: src_peak None is 1000);
+    ootf: as decode_to_tensor.  Returns when the pixels are in place."""
     import torch
     L = capi.image_lib()
     fmt, lay = _out_format(out_format), _layout(layout)
@@ -550,8 +602,12 @@ def decode_sequence_to_tensor(data, frames=None, out_format="rgb", layout="chw",
         failed = C.c_int32(-1)
         lit = _light_of(light)
         ton = _tone_of(tone, lit)
+        oo = _ootf_of(ootf, lit)
         with torch.cuda.device(out.device):
-            if ton is not None:
+            if oo is not None:
+                rc = L.hm_decode_frames_to_device_ootf(f.h, (C.c_uint32 * n)(*ids), n, C.byref(prm), _ref(view), C.byref(lit), C.byref(oo), _ref(ton), dests, res,
+                                                       C.byref(failed))
+            elif ton is not None:
                 rc = L.hm_decode_frames_to_device_tone(f.h, (C.c_uint32 * n)(*ids), n, C.byref(prm), C.byref(view) if view is not None else None, C.byref(lit),
                                                        C.byref(ton), dests, res, C.byref(failed))
             elif lit is not None:

@@ -731,7 +731,8 @@ HM_API int hm_view_filter_taps(int n_in, int n_out, int filter, int j, int32_t* 
  * beta = 0.018053968510807 (E' < 4.5 beta: E' / 4.5, else ((E' + alpha - 1) / alpha)^(1 / 0.45); the rounded 1.099 / 0.081 pair is
  * not monotone across the knee at 12 bits);  4 gamma 2.2;  5 gamma 2.8;  8 linear;  13 sRGB (IEC 61966-2-1: E' <= 0.04045:
  * E' / 12.92, else ((E' + 0.055) / 1.055)^2.4);  16 PQ, the ST 2084 EOTF, 1.0 = 10000 cd/m2;  18 HLG, the INVERSE OETF of BT.2100
- * only: scene light, no OOTF is applied (E' <= 0.5: E'^2 / 3, else (exp((E' - c) / a) + b) / 12).
+ * only: scene light, no OOTF is applied - that is a step of its own, "OOTF" below - (E' <= 0.5: E'^2 / 3, else
+ * (exp((E' - c) / a) + b) / 12, a = 0.17883277, b = 1 - 4 a, c = 0.5 - a log(4 a)).
  * Primaries: 1, 5, 6, 7, 9, 12 - all with a D65 white; no chromatic adaptation.  Any other code: HM_ERR_UNSUPPORTED.
  *   bits = the target's sample depth: 8 for HM_OUT_RGB / _RGBA, hm_decoded.bit_depth for the _LE 16-bit targets (at most 12: both
  *   tables sit in the kernels' local memory; deeper: HM_ERR_UNSUPPORTED);  peak = (1 << bits) - 1;  F_t = the code-to-light function
@@ -985,6 +986,77 @@ HM_API int hm_gain_to_tensor(int out_format, int bits, int src_w, int src_h, con
 /* Host arithmetic, no device: the 1 << map_bits entries of tab_channel (channel 0 .. 2) for this headroom.  Returns the count, or a
  * negative status (the step's own refusals of the parameters). */
 HM_API int hm_gain_table(const hm_gain_params* params, float headroom, int channel, int map_bits, float* out);
+
+/* ------------------------------------------------------------------------- */
+/* OOTF: HLG scene light rendered for a display's peak (the reference OOTF of BT.2100, by table) */
+/* ------------------------------------------------------------------------- */
+
+/* The light step turns HLG code values (transfer 18) into SCENE light.  An OOTF step beside it renders that scene light for a display
+ * of peak luminance L_W = display_peak: the reference OOTF of Rec. ITU-R BT.2100, F_D = alpha Ys^(gamma - 1) E, with alpha normalised
+ * to 1 and the black level at 0, the system gamma adapted to the display's peak.  It exists only beside a light step whose resolved
+ * from_transfer is 18.  No transcendental function runs on the device: the factor Ys^(gamma - 1) is a table over the 10-bit HLG codes
+ * of the scene luminance, found by the light step's binary search.  A call without the step writes what it wrote before.
+ *   Gamma, in double, with L = (double)display_peak:  gamma != 0: the system gamma is (double)gamma, as it is.  Otherwise
+ *   400 <= L <= 2000: 1.2 + 0.42 * log10(L / 1000) (BT.2100 Table 5, note 5e); any other L: 1.2 * pow(1.111, log2(L / 1000)) (note 5f).
+ *   Luminance weights: y[0 .. 2] = the Y row of the RGB -> XYZ matrix of the SOURCE primaries (the resolved from_primaries), derived in
+ *   double from the H.273 chromaticities exactly as hm_light_matrix derives its matrices, each entry rounded once to float32
+ *   (primaries 9: 0.2627 / 0.6780 / 0.0593 to four places).
+ *   Tables, on the host in double with the C library's pow / exp / log / log10 / log2, each entry rounded once to float32;
+ *   g = (double)gain of the light step, F = the code-to-light function of transfer 18 stated under "Light":
+ *     thr[0] = 0;  thr[i] = (float)(g * F((i - 0.5) / 1023)), i = 1 .. 1023
+ *     sg[k] = (float)pow(F(k / 1023), gamma - 1), k = 1 .. 1023;  sg[0] = sg[1]
+ *   Per output pixel, on r_c = the light step's resampled (or moved) linear light - with an alpha step: the alpha step's r_c -, BEFORE
+ *   the gamut matrix:
+ *     Ys = fadd(fadd(fmul(y[0], R), fmul(y[1], G)), fmul(y[2], B))
+ *     k = |{ i in 1 .. 1023 : thr[i] <= Ys }|      a binary search of 10 steps; a negative or NaN Ys gives k = 0
+ *     R = fmul(R, sg[k]), G and B likewise
+ *   Gamut matrix, tone step and the light step's finish follow unchanged.  Alpha is untouched.
+ *   Unit of the result: light value g after the step stands for display_peak cd/m2.
+ *   A tone step behind it: unit_nits == 0 resolves to display_peak, src_peak == 0 resolves to display_peak (no file property is
+ *   read); everything else of the tone step is as written under "Tone".
+ *   Accuracy: the factor is piecewise constant over HM_OOTF_STEPS 10-bit HLG steps of the scene luminance.  With gamma - 1 = 0.2 one
+ *   step above E' = 0.5 changes it by about 0.11 %.
+ *   Views: under a view the sums are taken over scene light, which is linear; the step follows the sums, as the tone step does.
+ * Refused before any work is queued, the destination unwritten - HM_ERR_INVALID_ARG: a null light step, an unknown kind, reserved
+ * != 0, a display_peak that is not finite, not above 0 or above 10000, a gamma that is not finite or is negative, a resolved
+ * from_transfer other than 18, to_transfer == 18 (display light re-encoded with the OETF alone is not an HLG signal; the inverse
+ * OOTF is out of scope), HM_ALPHA_PREMULTIPLIED beside the step; HM_ERR_UNSUPPORTED: a gain step beside it (a gain map's base is
+ * SDR) - and everything the light, tone, alpha, view and destination checks refuse.  The from_transfer refusal comes at once where
+ * from_transfer is explicit and in hm_ootf_to_tensor; with from_transfer == 0 it comes behind the decode, before a byte of the
+ * destination is written (the tone step's unit_nits rule). */
+enum { HM_OOTF_HLG = 1 };
+enum { HM_OOTF_STEPS = 1024 };          /* 10-bit HLG codes of the scene luminance */
+typedef struct hm_device_ootf {
+  int32_t kind;            /* HM_OOTF_HLG */
+  float   display_peak;    /* L_W, cd/m2 of the display's peak: finite, > 0, <= 10000 */
+  float   gamma;           /* 0: the system gamma of display_peak (rule above); else finite, > 0: used as it is */
+  int32_t reserved[5];     /* 0 */
+} hm_device_ootf;
+/* hm_decode_item_to_device_alpha with an OOTF step; view, tone and alpha may be NULL.  ootf == NULL: the bytes of the same call
+ * through hm_decode_item_to_device_alpha (alpha given) or hm_decode_item_to_device_tone. */
+HM_API int hm_decode_item_to_device_ootf(const hm_file* f, uint32_t id, const hm_decode_params* params, const hm_device_view* view,
+                                         const hm_device_light* light, const hm_device_ootf* ootf, const hm_device_tone* tone,
+                                         const hm_device_alpha* alpha, const hm_device_dest* dest, hm_decoded* out);
+/* hm_decode_frames_to_device_tone with an OOTF step; view and tone may be NULL.  ootf == NULL: hm_decode_frames_to_device_tone. */
+HM_API int hm_decode_frames_to_device_ootf(const hm_file* f, const uint32_t* frames, int32_t count, const hm_decode_params* params,
+                                           const hm_device_view* view, const hm_device_light* light, const hm_device_ootf* ootf,
+                                           const hm_device_tone* tone, const hm_device_dest* dests, hm_decoded* out, int32_t* failed_frame);
+/* the pipeline form; ootf == NULL: hm_pipeline_submit_to_device_alpha (alpha given) or hm_pipeline_submit_to_device_tone */
+HM_API int hm_pipeline_submit_to_device_ootf(hm_pipeline* p, const uint8_t* heif, size_t size, uint32_t item_id, uint64_t tag,
+                                             const hm_device_view* view, const hm_device_light* light, const hm_device_ootf* ootf,
+                                             const hm_device_tone* tone, const hm_device_alpha* alpha, const hm_device_dest* dest);
+/* The step on its own, on interleaved pixels of `bits` bits that are on the device already (as hm_tone_to_tensor / hm_alpha_to_tensor):
+ * the light step's from_* must be explicit; view, tone and alpha may be NULL.  ootf == NULL: hm_alpha_to_tensor (alpha given) or
+ * hm_tone_to_tensor.  Asynchronous on `stream`. */
+HM_API int hm_ootf_to_tensor(int out_format, int bits, int src_w, int src_h, const void* d_src, int src_stride, const hm_device_view* view,
+                             const hm_device_light* light, const hm_device_ootf* ootf, const hm_device_tone* tone, const hm_device_alpha* alpha,
+                             const hm_device_dest* dest, void* stream);
+/* Host arithmetic, no device: the system gamma of the step (the rule above) */
+HM_API int hm_ootf_gamma(const hm_device_ootf* ootf, double* gamma);
+/* ... the HM_OOTF_STEPS entries of thr (which == 0) or sg (1) for the light step's gain.  Returns HM_OOTF_STEPS, or a negative status. */
+HM_API int hm_ootf_table(const hm_device_ootf* ootf, float gain, int which, float* out);
+/* ... and the luminance weights y[0 .. 2] of a set of primaries (an unknown code: HM_ERR_UNSUPPORTED) */
+HM_API int hm_ootf_luma(int primaries, float out[3]);
 
 /* ------------------------------------------------------------------------- */
 /* Planar views: a rectangle of the image, at a size of the caller's choice, into I420 / NV12 / P010 planes */
