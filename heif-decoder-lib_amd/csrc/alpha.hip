@@ -3,22 +3,23 @@
 // channels.  The source is always four-channel interleaved (RGBA / RRGGBBAA_LE); OC, the channels written, is 3 exactly for
 // HM_ALPHA_MATTE.  LIT: a light step runs beside it - the colour samples go through lin[] before the product, and the result takes the
 // place of the resampled light (light_step.h: matrix, tone step, finish); without one the result goes through out_elem.h's `finish`.
-//   k_alpha_tensor   the pointwise path, k_light_tensor's streaming shape: a wave takes 64 consecutive pixel groups of ONE row, a lane's
-//                    group is 16 bytes of output per channel plane, 16-byte loads and stores where pointers and pitches allow, the
-//                    scalar instance (lane l takes pixels l, l + 64, ...) otherwise.  PREMULTIPLIED (OC 4) and MATTE (OC 3) only:
-//                    STRAIGHT without sums is the write without the step (devdest.cpp).
-//   k_alpha_nearest  HM_VIEW_NEAREST: the pixel at (j * n_w / ow, k * n_h / oh) through the same per-pixel step.
+//   k_alpha_tensor   the pointwise path: pointwise_body (out_rows.h), k_light_tensor's body, with this step as its pixel - four channels
+//                    read, OC written.  PREMULTIPLIED (OC 4) and MATTE (OC 3) only: STRAIGHT without sums is the write without the
+//                    step (devdest.cpp).
+//   k_alpha_nearest  HM_VIEW_NEAREST: nearest_body (out_rows.h) with the same per-pixel step.
 //   k_alpha_h        the horizontal pass: per tap ONE load of the whole pixel (4 bytes at 8 bits, 8 at 16; sample by sample where the
 //                    source is not aligned to its pixels), the products p_c = x_c * a, four sums (p_R, p_G, p_B, a) in k_resample_h's
-//                    order.  The unstaged form, for all three filters.
-//   k_alpha_v        the vertical sums of ONE pixel per lane, then the mode's rule, then `finish` or matrix, tone and colour_out;
-//                    3 or 4 channels are written.
+//                    order.  The unstaged form, for all three filters.  Not resample_h_body: the product stands between lookup and sum.
+//   k_alpha_v        vertical_sums (out_rows.h) of ONE pixel per lane, then the mode's rule, then `finish` or light_out; 3 or 4
+//                    channels are written.
 // LDS (LIT only): as light.hip has it - lin, enc, the tone and the OOTF tables in the pointwise kernels, lin in k_alpha_h, enc and the
-// tone and OOTF tables in k_alpha_v; at most 56 KB.  The OOTF step (light_step.h: ootf_map) acts on r_c in front of the matrix.The mode, P and the background (as floats: lin[] of it under a light step, looked up on the host) are kernel arguments.
+// tone and OOTF tables in k_alpha_v; at most 56 KB.  The OOTF step (light_step.h: light_out) acts on r_c in front of the matrix.
+// The mode, P and the background (as floats: lin[] of it under a light step, looked up on the host) are kernel arguments.
 // -ffp-contract=off, __fmul_rn / __fadd_rn / __fsub_rn / __fdiv_rn throughout: no fused multiply-add, no reciprocal.
 #include "hm_devdest.h"
 #include "light_step.h"
 #include "out_launch.h"
+#include "out_rows.h"
 
 namespace {
 
@@ -42,129 +43,68 @@ __device__ __forceinline__ void alpha_rule(const Alpha& A, const float S[4], flo
   }
 }
 
-// r[0 .. 2] to the colour elements of the destination: through matrix, tone step and the light step's finish (vl: enc, then thr and sg,
-// in LDS), or through `finish` over the destination's whole range
+// r[0 .. 2] to the colour elements of the destination: through light_out (light_step.h: OOTF step, matrix, tone step, the light step's
+// finish), or through `finish` over the destination's whole range
 template <bool LIT, typename OutT>
-__device__ __forceinline__ void colour_elems(const Light& L, const float* vl, float r[3], const Affine& a, OutT* o)
+__device__ __forceinline__ void colour_elems(const Light& L, const LightTables& T, float r[3], const Affine& a, OutT* o)
 {
-  if constexpr (LIT) {
-    if (L.ootf) ootf_map(L, ootf_tables(L, vl), r);
-    gamut(L, r);
-    if (L.tone) tone_map(vl + (L.encode ? 1 << L.ebits : 0), r);
-#pragma unroll
-    for (int c = 0; c < 3; c++) o[c] = colour_out<OutT>(L, vl, r[c], a.scale[c], a.bias[c]);
-  }
+  if constexpr (LIT) light_out(L, T, r, a, o);
   else {
 #pragma unroll
     for (int c = 0; c < 3; c++) o[c] = finish<OutT>(r[c], a.scale[c], a.bias[c], full_peak<OutT>());
   }
 }
 
-// one pixel that is moved, not summed: v0 .. v2 its colour samples, v3 its alpha sample; lds = lin, then enc, then thr and sg (LIT)
+// one pixel that is moved, not summed: v[0 .. 2] its colour samples, v[3] its alpha sample
 template <int OC, bool LIT, typename OutT>
-__device__ __forceinline__ void pixel(const Light& L, const Alpha& A, const float* lds, unsigned v0, unsigned v1, unsigned v2, unsigned v3, const Affine& a, OutT o[OC])
+__device__ __forceinline__ void pixel(const Light& L, const Alpha& A, const LightTables& T, const unsigned (&v)[4], const Affine& a, OutT* o)
 {
-  const float av = (float)v3;
+  const float av = (float)v[3];
   float x[3];
-  if constexpr (LIT) {
-    const unsigned peak = (1u << L.bits) - 1u;
-    x[0] = lds[min(v0, peak)]; x[1] = lds[min(v1, peak)]; x[2] = lds[min(v2, peak)];
-  }
-  else { x[0] = (float)v0; x[1] = (float)v1; x[2] = (float)v2; }
+  if constexpr (LIT) light_in(L, T, v, x);
+  else { x[0] = (float)v[0]; x[1] = (float)v[1]; x[2] = (float)v[2]; }
   const float S[4] = {__fmul_rn(x[0], av), __fmul_rn(x[1], av), __fmul_rn(x[2], av), av};
   float r[3];
   alpha_rule(A, S, r);
-  colour_elems<LIT, OutT>(L, LIT ? lds + (1 << L.bits) : lds, r, a, o);
-  if constexpr (OC == 4) o[3] = moved<OutT>(v3, a.scale[3], a.bias[3]);
+  colour_elems<LIT, OutT>(L, T, r, a, o);
+  if constexpr (OC == 4) o[3] = moved<OutT>(v[3], a.scale[3], a.bias[3]);
 }
 
-// SB: bytes per input sample (1 / 2, little-endian), OC: channels written, CHW: one plane per channel, VEC: 16-byte accesses allowed (the
-// launcher has checked the alignment of both sides).  grid: x = groups of 64 pixel groups, y = groups of 4 rows; dynamic LDS: the tables (LIT).
+// the step's tables into LDS (LIT; all of them, or a vertical pass's); without a light step there are none and nothing looks at the view
+template <bool LIT> __device__ __forceinline__ LightTables fill_lit(float* lds, const Light& L, bool with_lin)
+{
+  if constexpr (LIT) return fill_light(lds, L, with_lin);
+  else return LightTables{};
+}
+
+// pointwise_body (out_rows.h) with the step as its pixel.  SB: bytes per input sample (1 / 2, little-endian), OC: channels written, CHW: one
+// plane per channel, VEC: 16-byte accesses allowed.  grid: x = groups of 64 pixel groups, y = groups of 4 rows; dynamic LDS: the tables (LIT).
 template <int SB, int OC, typename OutT, bool CHW, bool VEC, bool LIT>
 __global__ __launch_bounds__(256) void k_alpha_tensor(const uint8_t* __restrict__ src, int src_stride, int w, int h, uint8_t* __restrict__ dst,
                                                       long long row_pitch, long long plane_pitch, Affine a, Light L, Alpha A)
 {
   extern __shared__ __attribute__((aligned(16))) float lds[];
-  typedef typename std::conditional<SB == 1, uint8_t, uint16_t>::type InT;
-  constexpr int P = 16 / (int)sizeof(OutT); // pixels per lane
-  constexpr int NB = P * 4 * SB;            // input bytes per lane: a multiple of 16
-  if constexpr (LIT) fill_tables(lds, L.lin, 1 << L.bits, L.enc, L.encode ? 1 << L.ebits : 0, L.tone, L.tone ? 2 * TONE_STEPS : 0, L.ootf, 2 * OOTF_STEPS);
-  const int lane = threadIdx.x & 63, y = blockIdx.y * 4 + (threadIdx.x >> 6);
+  const LightTables T = fill_lit<LIT>(lds, L, true);
+  const int y = blockIdx.y * 4 + (threadIdx.x >> 6);
   if (y >= h) return;
-  uint8_t* orow = dst + (long long)y * row_pitch;
-  if (!VEC) { // one pixel per lane and step: pixels lane, lane + 64, ... of the wave's 64 * P
-    const InT* irow = reinterpret_cast<const InT*>(src + (size_t)y * src_stride);
-#pragma unroll 1
-    for (int i = 0; i < P; i++) {
-      const int x = (blockIdx.x * P + i) * 64 + lane;
-      if (x >= w) break;
-      const InT* ip = irow + (size_t)x * 4;
-      OutT o[OC];
-      pixel<OC, LIT, OutT>(L, A, lds, ip[0], ip[1], ip[2], ip[3], a, o);
-#pragma unroll
-      for (int c = 0; c < OC; c++) *elem_at<OutT>(orow, CHW, plane_pitch, x, c, OC) = o[c];
-    }
-    return;
-  }
-  const int x0 = (blockIdx.x * 64 + lane) * P;
-  if (x0 >= w) return;
-  const uint8_t* in = src + (size_t)y * src_stride + (size_t)x0 * (4 * SB);
-  if (x0 + P <= w) {
-    constexpr int NL = NB / 16;
-    uint4 lw[NL];
-#pragma unroll
-    for (int k = 0; k < NL; k++) lw[k] = reinterpret_cast<const uint4*>(in)[k];
-    InT smp[P * 4];
-    __builtin_memcpy(smp, lw, NB);
-    OutT o[P * OC]; // pixel-major: the row's own order
-#pragma unroll
-    for (int i = 0; i < P; i++) pixel<OC, LIT, OutT>(L, A, lds, smp[i * 4], smp[i * 4 + 1], smp[i * 4 + 2], smp[i * 4 + 3], a, &o[i * OC]);
-    if (CHW) {
-#pragma unroll
-      for (int c = 0; c < OC; c++) {
-        OutT oc[P];
-#pragma unroll
-        for (int i = 0; i < P; i++) oc[i] = o[i * OC + c];
-        store16(elem_at<OutT>(orow, true, plane_pitch, x0, c, OC), oc);
-      }
-    }
-    else {
-#pragma unroll
-      for (int k = 0; k < OC; k++) store16(elem_at<OutT>(orow, false, 0, x0, 0, OC) + k * P, &o[k * P]); // P * OC elements in a row: OC stores of P elements
-    }
-    return;
-  }
-  const int n = w - x0 < P ? w - x0 : P; // the ragged last group: element by element
-  const InT* ip = reinterpret_cast<const InT*>(in);
-#pragma unroll 1
-  for (int i = 0; i < n; i++) {
-    OutT o[OC];
-    pixel<OC, LIT, OutT>(L, A, lds, ip[i * 4], ip[i * 4 + 1], ip[i * 4 + 2], ip[i * 4 + 3], a, o);
-#pragma unroll
-    for (int c = 0; c < OC; c++) *elem_at<OutT>(orow, CHW, plane_pitch, x0 + i, c, OC) = o[c];
-  }
+  pointwise_body<SB, 4, OC, OutT, VEC>(src, src_stride, w, y, dst, row_pitch, plane_pitch, CHW,
+                                       [&](int, const unsigned (&v)[4], OutT* o, NoColumn::Rec) { pixel<OC, LIT, OutT>(L, A, T, v, a, o); });
 }
 
-// HM_VIEW_NEAREST: out pixel (j, k) is source pixel (j * n_w / ow, k * n_h / oh).  grid: x = groups of 64 columns, y = groups of 4 rows.
+// nearest_body (out_rows.h) with the step as its pixel.  grid: x = groups of 64 columns, y = groups of 4 rows; dynamic LDS: the tables (LIT).
 template <typename InT, int OC, typename OutT, bool LIT>
 __global__ __launch_bounds__(256) void k_alpha_nearest(const uint8_t* __restrict__ src, int src_stride, int n_w, int n_h, int ow, int oh, int chw,
                                                        uint8_t* __restrict__ dst, long long row_pitch, long long plane_pitch, Affine a, Light L, Alpha A)
 {
   extern __shared__ __attribute__((aligned(16))) float lds[];
-  if constexpr (LIT) fill_tables(lds, L.lin, 1 << L.bits, L.enc, L.encode ? 1 << L.ebits : 0, L.tone, L.tone ? 2 * TONE_STEPS : 0, L.ootf, 2 * OOTF_STEPS);
-  const int j = blockIdx.x * 64 + (threadIdx.x & 63), k = blockIdx.y * 4 + (threadIdx.x >> 6);
-  if (j >= ow || k >= oh) return;
-  const int sx = j * n_w / ow, sy = k * n_h / oh;
-  const InT* in = reinterpret_cast<const InT*>(src + (size_t)sy * src_stride) + (size_t)sx * 4;
-  OutT o[OC];
-  pixel<OC, LIT, OutT>(L, A, lds, in[0], in[1], in[2], in[3], a, o);
-  uint8_t* orow = dst + (long long)k * row_pitch;
-#pragma unroll
-  for (int c = 0; c < OC; c++) *elem_at<OutT>(orow, chw, plane_pitch, j, c, OC) = o[c];
+  const LightTables T = fill_lit<LIT>(lds, L, true);
+  nearest_body<sizeof(InT), 4, OC, OutT>(src, src_stride, n_w, n_h, ow, oh, chw, dst, row_pitch, plane_pitch,
+                                         [&](int, const unsigned (&v)[4], OutT* o, NoColumn::Rec) { pixel<OC, LIT, OutT>(L, A, T, v, a, o); });
 }
 
 // The horizontal pass: rows of the crop -> float32 rows of ow x 4 sums.  k_resample_h's lane mapping, table layout and order of the
-// sums (out_rows.h); a tap's pixel comes with one load when `whole` - the source address and stride are multiples of the pixel's
+// sums, but not resample_h_body (out_rows.h): the product with alpha stands between a sample's lookup and its sum, and a tap is loaded
+// as a whole pixel - a kernel of its own.  A tap's pixel comes with one load when `whole` - the source address and stride are multiples of the pixel's
 // 4 * SB bytes - and sample by sample otherwise.  CHW: the intermediate has one plane per sum.
 // grid: x = groups of 64 output columns, y = groups of 4 source rows; src points at the crop's origin; dynamic LDS: lin (LIT).
 template <int SB, bool CHW, bool LIT>
@@ -174,7 +114,7 @@ __global__ __launch_bounds__(256) void k_alpha_h(const uint8_t* __restrict__ src
 {
   extern __shared__ __attribute__((aligned(16))) float lds[];
   typedef typename std::conditional<SB == 1, uint8_t, uint16_t>::type InT;
-  if constexpr (LIT) fill_tables(lds, lin, 1 << bits, nullptr, 0, nullptr, 0);
+  if constexpr (LIT) fill_tables(lds, lin, 1 << bits);
   const int j = blockIdx.x * 64 + (threadIdx.x & 63), y = blockIdx.y * 4 + (threadIdx.x >> 6);
   if (j >= ow || y >= n_h) return;
   const uint8_t* in = src + (size_t)y * src_stride + (size_t)first[j] * (4 * SB);
@@ -214,46 +154,25 @@ __global__ __launch_bounds__(256) void k_alpha_h(const uint8_t* __restrict__ src
   }
 }
 
-// The vertical pass: a lane is ONE output pixel, a wave 64 consecutive pixels of one output row, so the taps are wave-uniform and
-// the reads of a CHW intermediate coalesce per plane (an HWC one: a lane reads its four sums with one 16-byte load).
-// grid: x = groups of 64 columns, y = groups of 4 output rows; dynamic LDS (LIT): enc when re-encoding, then thr and sg with a tone step.
+// The vertical pass: vertical_sums (out_rows.h) of ONE pixel per lane, then the mode's rule, then `finish` or light_out.
+// grid: x = groups of 64 columns, y = groups of 4 output rows; dynamic LDS (LIT): enc when re-encoding, then the tone and the OOTF tables.
 template <typename OutT, bool CHW, int OC, bool LIT>
 __global__ __launch_bounds__(256) void k_alpha_v(const float* __restrict__ tmp, long long pitch, long long plane, int ow, int oh,
                                                  const int32_t* __restrict__ first, const int32_t* __restrict__ count, const float* __restrict__ wts,
                                                  uint8_t* __restrict__ dst, long long row_pitch, long long plane_pitch, Affine a, Light L, Alpha A)
 {
   extern __shared__ __attribute__((aligned(16))) float lds[];
-  if constexpr (LIT) {
-    if (L.encode || L.tone || L.ootf) fill_tables(lds, L.enc, L.encode ? 1 << L.ebits : 0, L.tone, L.tone ? 2 * TONE_STEPS : 0, L.ootf, 2 * OOTF_STEPS); // (uniform: the barrier inside is met by every thread or by none)
-  }
+  const LightTables T = fill_lit<LIT>(lds, L, false);
   const int j = blockIdx.x * 64 + (threadIdx.x & 63), k = blockIdx.y * 4 + (threadIdx.x >> 6);
   if (j >= ow || k >= oh) return;
-  const int y0 = first[k], n = count[k]; // (the same in every lane of the wave)
-  const float* col = tmp + (long long)y0 * pitch + (CHW ? (long long)j : (long long)j * 4);
-  float S[4] = {0.0f, 0.0f, 0.0f, 0.0f};
-  for (int i = 0; i < n; i++) {
-    const float w = wts[(size_t)i * oh + k];
-    float v[4];
-    if (CHW) {
-#pragma unroll
-      for (int c = 0; c < 4; c++) v[c] = col[(long long)c * plane];
-    }
-    else { // (pitch is a multiple of 16 elements and tmp a pool block: 16-byte aligned)
-      const float4 q = *reinterpret_cast<const float4*>(col);
-      v[0] = q.x; v[1] = q.y; v[2] = q.z; v[3] = q.w;
-    }
-#pragma unroll
-    for (int c = 0; c < 4; c++) S[c] = __fadd_rn(S[c], __fmul_rn(w, v[c]));
-    col += pitch;
-  }
+  float S[4];
+  vertical_sums<4, CHW>(tmp, pitch, plane, j, k, oh, first, count, wts, S);
   float r[3];
   alpha_rule(A, S, r);
   OutT o[OC];
-  colour_elems<LIT, OutT>(L, lds, r, a, o);
+  colour_elems<LIT, OutT>(L, T, r, a, o);
   if constexpr (OC == 4) o[3] = finish<OutT>(S[3], a.scale[3], a.bias[3], full_peak<OutT>()); // a resampled alpha value: k_resample_v's finish
-  uint8_t* orow = dst + (long long)k * row_pitch;
-#pragma unroll
-  for (int c = 0; c < OC; c++) *elem_at<OutT>(orow, CHW, plane_pitch, j, c, OC) = o[c];
+  store_pixel<OC>(dst + (long long)k * row_pitch, CHW, plane_pitch, j, o);
 }
 
 // every instance the launchers below can pick (hm_debug_kernel_regs): 92 pointwise, 23 nearest, 8 horizontal, 32 vertical.
@@ -302,63 +221,46 @@ Alpha alpha_of(const hm_alpha_args* aa)
   return A;
 }
 
-// does an instance exist for elements of OutT from samples of SB bytes, OC channels written, with or without a light step?
-template <typename OutT, int SB, int OC, bool LIT> constexpr bool has_instance()
+// has_instance (out_launch.h), less the integers beside a light step in four channels: PREMULTIPLIED there stores linear light
+template <typename OutT, int SB, int OC, bool LIT> constexpr bool has_alpha_instance()
 {
-  if (!std::is_integral<OutT>::value) return true;
-  if (sizeof(OutT) == SB) return !(LIT && OC == 4);
-  return sizeof(OutT) == 1 && SB == 2 && OC == 3 && LIT; // the 8-bit finish
-}
-
-template <int SB, int OC, typename OutT, bool CHW, bool LIT>
-int launch_tensor(const hm_dest_plan* p, const hm_light_args* la, const hm_alpha_args* aa, const uint8_t* src, int src_stride, int w, int rows, uint8_t* dst,
-                  const Affine& a, hipStream_t s)
-{
-  constexpr int P = 16 / (int)sizeof(OutT);
-  const bool vec = ((uintptr_t)src % 16) == 0 && (src_stride % 16) == 0 && ((uintptr_t)dst % 16) == 0 && (p->row_pitch % 16) == 0 &&
-                   (!CHW || (p->plane_pitch % 16) == 0);
-  const int groups = (w + P - 1) / P;
-  const dim3 grid((unsigned)((groups + 63) / 64), (unsigned)((rows + 3) / 4)), block(256);
-  const Light L = light_or_none(la);
-  const Alpha A = alpha_of(aa);
-  const size_t lds = LIT ? light_tables_bytes(la) : 0;
-  if (vec)
-    hipLaunchKernelGGL((k_alpha_tensor<SB, OC, OutT, CHW, true, LIT>), grid, block, lds, s, src, src_stride, w, rows, dst, (long long)p->row_pitch,
-                       (long long)p->plane_pitch, a, L, A);
-  else
-    hipLaunchKernelGGL((k_alpha_tensor<SB, OC, OutT, CHW, false, LIT>), grid, block, lds, s, src, src_stride, w, rows, dst, (long long)p->row_pitch,
-                       (long long)p->plane_pitch, a, L, A);
-  return hm_check_hip(hipGetLastError(), "k_alpha_tensor launch");
+  return has_instance<OutT, SB, OC, LIT>() && !(std::is_integral<OutT>::value && LIT && OC == 4);
 }
 
 template <int SB, int OC, bool LIT>
-int launch_tensor_dtype(const hm_dest_plan* p, const hm_light_args* la, const hm_alpha_args* aa, const uint8_t* src, int src_stride, int w, int rows, uint8_t* dst,
-                        const Affine& a, hipStream_t s)
+int launch_tensor(const hm_dest_plan* p, const hm_light_args* la, const hm_alpha_args* aa, const uint8_t* src, int src_stride, int w, int rows, uint8_t* dst,
+                  const Affine& a, hipStream_t s)
 {
-  const bool chw = p->layout == HM_DEV_LAYOUT_CHW;
+  const Light L = light_or_none(la);
+  const Alpha A = alpha_of(aa);
+  const size_t lds = LIT ? light_tables_bytes(la) : 0;
   return with_dtype(p->dtype, [&](auto tag) -> int {
     typedef typename decltype(tag)::type OutT;
-    if constexpr (has_instance<OutT, SB, OC, LIT>())
-      return chw ? launch_tensor<SB, OC, OutT, true, LIT>(p, la, aa, src, src_stride, w, rows, dst, a, s)
-                 : launch_tensor<SB, OC, OutT, false, LIT>(p, la, aa, src, src_stride, w, rows, dst, a, s);
+    if constexpr (has_alpha_instance<OutT, SB, OC, LIT>()) {
+      constexpr int P = 16 / (int)sizeof(OutT);
+      with_flags(p->layout == HM_DEV_LAYOUT_CHW, aligned16(src, src_stride, dst, p), [&](auto chw, auto vec) {
+        hipLaunchKernelGGL((k_alpha_tensor<SB, OC, OutT, chw.value, vec.value, LIT>), grid_64x4((w + P - 1) / P, rows), dim3(256), lds, s, src, src_stride, w, rows, dst,
+                           (long long)p->row_pitch, (long long)p->plane_pitch, a, L, A);
+      });
+      return hm_check_hip(hipGetLastError(), "k_alpha_tensor launch");
+    }
     return NO_KERNEL_INSTANCE;
   });
 }
 
 template <int SB, int OC, bool LIT>
-int launch_nearest_dtype(const hm_dest_plan* p, const hm_light_args* la, const hm_alpha_args* aa, const uint8_t* src, int src_stride, int n_w, int n_h, int ow, int oh,
-                         uint8_t* dst, const Affine& a, hipStream_t s)
+int launch_nearest(const hm_dest_plan* p, const hm_light_args* la, const hm_alpha_args* aa, const uint8_t* src, int src_stride, int n_w, int n_h, int ow, int oh,
+                   uint8_t* dst, const Affine& a, hipStream_t s)
 {
   typedef typename std::conditional<SB == 1, uint8_t, uint16_t>::type InT;
-  const dim3 grid((unsigned)((ow + 63) / 64), (unsigned)((oh + 3) / 4)), block(256);
   const int chw = p->layout == HM_DEV_LAYOUT_CHW ? 1 : 0;
   const Light L = light_or_none(la);
   const Alpha A = alpha_of(aa);
   const size_t lds = LIT ? light_tables_bytes(la) : 0;
   return with_dtype(p->dtype, [&](auto tag) -> int {
     typedef typename decltype(tag)::type OutT;
-    if constexpr (has_instance<OutT, SB, OC, LIT>()) {
-      hipLaunchKernelGGL((k_alpha_nearest<InT, OC, OutT, LIT>), grid, block, lds, s, src, src_stride, n_w, n_h, ow, oh, chw, dst, (long long)p->row_pitch,
+    if constexpr (has_alpha_instance<OutT, SB, OC, LIT>()) {
+      hipLaunchKernelGGL((k_alpha_nearest<InT, OC, OutT, LIT>), grid_64x4(ow, oh), dim3(256), lds, s, src, src_stride, n_w, n_h, ow, oh, chw, dst, (long long)p->row_pitch,
                          (long long)p->plane_pitch, a, L, A);
       return hm_check_hip(hipGetLastError(), "k_alpha_nearest launch");
     }
@@ -369,7 +271,7 @@ int launch_nearest_dtype(const hm_dest_plan* p, const hm_light_args* la, const h
 template <int SB, bool LIT>
 void launch_h(bool chw, const hm_resample_args* r, const hm_light_args* la, hipStream_t s)
 {
-  const dim3 grid((unsigned)((r->ow + 63) / 64), (unsigned)((r->n_h + 3) / 4)), block(256);
+  const dim3 grid = grid_64x4(r->ow, r->n_h), block(256);
   const uint8_t* src = (const uint8_t*)r->src;
   const size_t lds = LIT ? light_h_bytes(la) : 0;
   const float* lin = LIT ? la->lin : nullptr;
@@ -386,17 +288,13 @@ void launch_h(bool chw, const hm_resample_args* r, const hm_light_args* la, hipS
 template <typename OutT, bool LIT>
 void launch_v(const hm_dest_plan* p, const hm_resample_args* r, const hm_light_args* la, const hm_alpha_args* aa, uint8_t* dst, const Affine& a, hipStream_t s)
 {
-  const dim3 grid((unsigned)((r->ow + 63) / 64), (unsigned)((r->oh + 3) / 4)), block(256);
-  const size_t lds = LIT ? light_v_bytes(la) : 0;
   const Light L = light_or_none(la);
   const Alpha A = alpha_of(aa);
-  const bool chw = p->layout == HM_DEV_LAYOUT_CHW;
-#define HM_AV_GO(CHW_, OC_) \
-  hipLaunchKernelGGL((k_alpha_v<OutT, CHW_, OC_, LIT>), grid, block, lds, s, (const float*)r->tmp, (long long)r->tmp_pitch, (long long)r->tmp_plane, r->ow, r->oh, \
-                     r->ay.first, r->ay.count, r->ay.weights, dst, (long long)p->row_pitch, (long long)p->plane_pitch, a, L, A)
-  if (chw) { if (p->channels == 3) HM_AV_GO(true, 3); else HM_AV_GO(true, 4); }
-  else { if (p->channels == 3) HM_AV_GO(false, 3); else HM_AV_GO(false, 4); }
-#undef HM_AV_GO
+  with_flags(p->layout == HM_DEV_LAYOUT_CHW, p->channels == 4, [&](auto chw, auto four) {
+    hipLaunchKernelGGL((k_alpha_v<OutT, chw.value, four.value ? 4 : 3, LIT>), grid_64x4(r->ow, r->oh), dim3(256), LIT ? light_v_bytes(la) : 0, s, (const float*)r->tmp,
+                       (long long)r->tmp_pitch, (long long)r->tmp_plane, r->ow, r->oh, r->ay.first, r->ay.count, r->ay.weights, dst, (long long)p->row_pitch,
+                       (long long)p->plane_pitch, a, L, A);
+  });
 }
 
 // p: the plan of the target the destination is written as (three channels exactly under HM_ALPHA_MATTE)
@@ -415,10 +313,9 @@ int check_args(const hm_dest_plan* p, const hm_light_args* la, const hm_alpha_ar
   }
   if (!la->lin || (la->encode && !la->enc) || la->bits != aa->bits || la->bits > HM_LIGHT_MAX_BITS || la->src_bytes != aa->src_bytes)
     return hm_fail(HM_ERR_INTERNAL, "k_alpha: light tables of %d bits beside samples of %d", la->bits, aa->bits);
-  if (la->enc_bits != la->bits && la->enc_bits != 8) return hm_fail(HM_ERR_INTERNAL, "k_alpha: codes of %d bits from tables of %d", la->enc_bits, la->bits);
-  if (p->sample_bytes != (la->enc_bits > 8 ? 2 : 1) || (p->sample_bytes != aa->src_bytes && p->channels != 3))
-    return hm_fail(HM_ERR_INTERNAL, "k_alpha: a %d-byte target of %d channels from %d-byte samples, codes of %d bits", p->sample_bytes, p->channels, aa->src_bytes, la->enc_bits);
   if (integer && !la->encode) return hm_fail(HM_ERR_INTERNAL, "k_alpha: integer dtype %d for linear light", p->dtype);
+  const int rc = check_light_args("k_alpha", p, la); // (what is left of it: the codes' width, the target's samples, the integer dtype's width)
+  if (rc) return rc;
   if (aa->mode == HM_ALPHA_PREMULTIPLIED && (la->encode || la->tone)) return hm_fail(HM_ERR_INTERNAL, "k_alpha: premultiplied light is not encoded or tone-mapped");
   return HM_OK;
 }
@@ -450,7 +347,7 @@ extern "C" int hm_launch_alpha_tensor(const hm_dest_plan* p, const hm_light_args
   const Affine a = affine_of(scale, bias);
   const uint8_t* in = (const uint8_t*)src;
   uint8_t* out = (uint8_t*)dst;
-  const int found = HM_ALPHA_PICK(launch_tensor_dtype, p, la, aa, in, src_stride, w, rows, out, a, s);
+  const int found = HM_ALPHA_PICK(launch_tensor, p, la, aa, in, src_stride, w, rows, out, a, s);
   return found == NO_KERNEL_INSTANCE ? no_instance("k_alpha_tensor", p, aa, la != nullptr) : found;
 }
 
@@ -463,7 +360,7 @@ extern "C" int hm_launch_alpha_nearest(const hm_dest_plan* p, const hm_light_arg
   const Affine a = affine_of(scale, bias);
   const uint8_t* in = (const uint8_t*)src;
   uint8_t* out = (uint8_t*)dst;
-  const int found = HM_ALPHA_PICK(launch_nearest_dtype, p, la, aa, in, src_stride, n_w, n_h, ow, oh, out, a, s);
+  const int found = HM_ALPHA_PICK(launch_nearest, p, la, aa, in, src_stride, n_w, n_h, ow, oh, out, a, s);
   return found == NO_KERNEL_INSTANCE ? no_instance("k_alpha_nearest", p, aa, la != nullptr) : found;
 }
 #undef HM_ALPHA_PICK

@@ -3,20 +3,19 @@
 //   r_c = fsub(fmul(fadd(r_c, kb_c), M_c), ka_c)
 // before the gamut matrix, with M_c the view sum over tab_c[map sample] under the MAP's own taps (include/heif_mi355x.h, "Gain").  No
 // transcendental function runs here: tab is built on the host in double (devdest.cpp), like the light step's tables.
-//   k_gain_tensor   the pointwise path (no view, the crop alone), k_light_tensor's streaming shape: a wave takes 64 consecutive pixel
-//                   groups of ONE row, a lane's group is 16 bytes of output per channel plane, 16-byte stores where pointers and
-//                   pitches allow, the scalar instance otherwise.  The map is enlarged here (n <= m: at most two taps per axis), so
+//   k_gain_tensor   the pointwise path (no view, the crop alone): pointwise_body (out_rows.h), k_light_tensor's body, with this step as
+//                   its pixel and a column's tap record as what it reads per column.  The map is enlarged here (n <= m: at most two taps per axis), so
 //                   M_c is formed in the kernel - horizontal sums per map row first, tap 0 first, then the vertical sum over them:
 //                   the sums of the two-pass form in its order - instead of a full-size float32 intermediate, which at 12 MP CHW
 //                   float32 would add about half the write's traffic again.  The taps come as 16-byte records (hm_gain_tap: first,
 //                   count, w0, w1): a wave is one row, so its row's record is a scalar load, and a lane loads the records of its P
 //                   columns, then their 2 x 2 map samples, as independent loads - no loop whose length is read from memory.
-//   k_gain_nearest  HM_VIEW_NEAREST: base and map sample at (j * n / m) of their own crops.
+//   k_gain_nearest  HM_VIEW_NEAREST: nearest_body (out_rows.h); base and map sample at (j * n / m) of their own crops.
 //   k_gain_map_h    the map's horizontal pass of a resampled view: resample_h_body (out_rows.h) with tab_c[min(v, mpeak)] as the
 //                   sample-to-float step; grid z = the table's channel.
-//   k_gain_map_v    the map's vertical pass into the float32 M planes (nch planes of oh rows).
-//   k_gain_v        k_light_v with the update between the sums and the matrix; the base's horizontal pass stays k_light_h (light.hip).
-// LDS: the light step's tables (light_step.h) and behind them nch tables of 1 << map_bits floats (1 KB each at 8 bits, 16 KB at 12).
+//   k_gain_map_v    the map's vertical pass into the float32 M planes (nch planes of oh rows): vertical_sums (out_rows.h) of one channel.
+//   k_gain_v        k_light_v with the update between the sums and light_out; the base's horizontal pass stays k_light_h (light.hip).
+// LDS: the light step's tables (light_step.h: light_layout) and behind them nch tables of 1 << map_bits floats (1 KB each at 8 bits, 16 KB at 12).
 // Where both together would pass 48 KB (12-bit samples re-encoded, or 12-bit tables beside a tone step), the gain tables are
 // read from global memory instead: the same values.  Every table index is clamped to its table (min(v, peak)), every tap lies inside
 // the map's crop (axis_taps, devdest.cpp).  -ffp-contract=off, __fmul_rn / __fadd_rn / __fsub_rn throughout.
@@ -45,14 +44,24 @@ __device__ __forceinline__ unsigned map_sample(const Gain& G, const uint8_t* row
   return min(v, (1u << G.mbits) - 1u);
 }
 
-// the light step's tables, then the gain tables, into LDS (every thread of the workgroup comes here); returns the gain tables
-__device__ __forceinline__ const float* fill_all(float* lds, const Light& L, const Gain& G)
+// the places of the light step's tables taken once: the pointwise kernels run up to 16 pixels of a lane through them
+struct TablesAt {
+  const float* lin_; const float* enc_; const float* tone_;
+  __device__ __forceinline__ const float* lin() const { return lin_; }
+  __device__ __forceinline__ const float* enc(const Light&) const { return enc_; }
+  __device__ __forceinline__ const float* tone(const Light&) const { return tone_; }
+  __device__ __forceinline__ const float* ootf(const Light&) const { return nullptr; } // (never beside the gain step)
+};
+
+// the light step's tables (fill_light), then the gain tables behind them, into LDS (every thread of the workgroup comes here);
+// *gt: the gain tables, where they are read
+__device__ __forceinline__ TablesAt fill_all(float* lds, const Light& L, const Gain& G, const float** gt)
 {
-  const int nl = (1 << L.bits) + (L.encode ? 1 << L.ebits : 0) + (L.tone ? 2 * TONE_STEPS : 0);
-  fill_tables(lds, L.lin, 1 << L.bits, L.enc, L.encode ? 1 << L.ebits : 0, L.tone, 2 * TONE_STEPS);
-  if (!G.tab_lds) return G.tab; // (uniform)
-  fill_tables(lds + nl, G.tab, G.nch << G.mbits, nullptr, 0, nullptr, 0);
-  return lds + nl;
+  const LightTables T = fill_light(lds, L, true);
+  const int nl = T.at(L).end;
+  *gt = G.tab_lds ? lds + nl : G.tab; // (uniform)
+  if (G.tab_lds) fill_tables(lds + nl, G.tab, G.nch << G.mbits);
+  return TablesAt{T.lin(), T.enc(L), T.tone(L)};
 }
 
 // the taps of an output row or column of the pointwise path (hm_gain_tap): at most two, w1 = 0 where there is one
@@ -81,129 +90,66 @@ __device__ __forceinline__ void gain_M(const Gain& G, const float* gt, const Tap
   }
 }
 
-// the update on one pixel's linear light, then what the light step does behind its sums: matrix, tone step, finish.  enc: the
-// threshold table in LDS, the tone tables behind it
-template <int C, typename OutT>
-__device__ __forceinline__ void gain_out(const Light& L, const float* enc, const Gain& G, float r[3], const float M[3], const Affine& a, OutT o[C])
+// the update on one pixel's linear light, then what the light step does behind its sums (light_out without the OOTF step, which
+// never runs beside the gain step: refused on the host)
+template <typename Tables, typename OutT>
+__device__ __forceinline__ void gain_out(const Light& L, const Tables& T, const Gain& G, float r[3], const float M[3], const Affine& a, OutT* o)
 {
 #pragma unroll
   for (int c = 0; c < 3; c++) r[c] = __fsub_rn(__fmul_rn(__fadd_rn(r[c], G.kb[c]), M[c]), G.ka[c]);
-  gamut(L, r);
-  if (L.tone) tone_map(enc + (L.encode ? 1 << L.ebits : 0), r);
-#pragma unroll
-  for (int c = 0; c < 3; c++) o[c] = colour_out<OutT>(L, enc, r[c], a.scale[c], a.bias[c]);
+  light_out<false>(L, T, r, a, o);
 }
 
-// one pixel that is moved, not resampled: v0 .. v2 its colour samples, v3 its alpha sample (C == 4); lds = lin, then enc, then thr and sg
+// one pixel that is moved, not resampled: v[0 .. 2] its colour samples, v[3] its alpha sample (C == 4)
 template <int C, typename OutT>
-__device__ __forceinline__ void pixel(const Light& L, const float* lds, const Gain& G, const float M[3], unsigned v0, unsigned v1, unsigned v2, unsigned v3,
-                                      const Affine& a, OutT o[C])
+__device__ __forceinline__ void pixel(const Light& L, const TablesAt& T, const Gain& G, const float M[3], const unsigned (&v)[C], const Affine& a, OutT* o)
 {
-  const unsigned peak = (1u << L.bits) - 1u;
-  float r[3] = {lds[min(v0, peak)], lds[min(v1, peak)], lds[min(v2, peak)]};
-  gain_out<C, OutT>(L, lds + (1 << L.bits), G, r, M, a, o);
-  if constexpr (C == 4) o[3] = moved<OutT>(v3, a.scale[3], a.bias[3]);
+  float r[3];
+  light_in(L, T, v, r);
+  gain_out(L, T, G, r, M, a, o);
+  if constexpr (C == 4) o[3] = moved<OutT>(v[3], a.scale[3], a.bias[3]);
 }
 
-// SB: bytes per input sample (1 / 2, little-endian), C: channels, VEC: 16-byte accesses allowed (the launcher has checked the alignment
-// of both sides); chw: one plane per channel.  grid: x = groups of 64 pixel groups, y = groups of 4 rows; dynamic LDS: the tables.
+// pointwise_body (out_rows.h) with the step as its pixel and a column's tap record as what it reads per column.  SB: bytes per input
+// sample (1 / 2, little-endian), C: channels, VEC: 16-byte accesses allowed; chw: one plane per channel.  grid: x = groups of 64 pixel
+// groups, y = groups of 4 rows; dynamic LDS: the tables.
 // The image is the crop itself: output pixel (x, y) is its pixel (x, y), and the map's taps are those of x and y.
 template <int SB, int C, typename OutT, bool VEC>
 __global__ __launch_bounds__(256) void k_gain_tensor(const uint8_t* __restrict__ src, int src_stride, int w, int h, uint8_t* __restrict__ dst, long long row_pitch,
                                                      long long plane_pitch, int chw, Affine a, Light L, Gain G)
 {
   extern __shared__ __attribute__((aligned(16))) float lds[];
-  typedef typename std::conditional<SB == 1, uint8_t, uint16_t>::type InT;
-  constexpr int P = 16 / (int)sizeof(OutT); // pixels per lane
-  constexpr int NB = P * C * SB;            // input bytes per lane
-  const float* gt = fill_all(lds, L, G);
-  const int lane = threadIdx.x & 63, y = __builtin_amdgcn_readfirstlane(blockIdx.y * 4 + (threadIdx.x >> 6)); // (a wave is one row: its taps are scalar loads)
+  const float* gt;
+  const TablesAt T = fill_all(lds, L, G, &gt);
+  const int y = __builtin_amdgcn_readfirstlane(blockIdx.y * 4 + (threadIdx.x >> 6)); // (a wave is one row: its taps are scalar loads)
   if (y >= h) return;
-  uint8_t* orow = dst + (long long)y * row_pitch;
   const Tap2 ty = tap_of(G.yrec[y]);
-  float M[3];
-  if (!VEC) { // one pixel per lane and step: pixels lane, lane + 64, ... of the wave's 64 * P
-    const InT* irow = reinterpret_cast<const InT*>(src + (size_t)y * src_stride);
-#pragma unroll 1
-    for (int i = 0; i < P; i++) {
-      const int x = (blockIdx.x * P + i) * 64 + lane;
-      if (x >= w) break;
-      const InT* ip = irow + (size_t)x * C;
-      OutT o[C];
-      gain_M(G, gt, tap_of(G.xrec[x]), ty, M);
-      pixel<C, OutT>(L, lds, G, M, ip[0], ip[1], ip[2], C == 4 ? ip[C - 1] : 0u, a, o);
-#pragma unroll
-      for (int c = 0; c < C; c++) *elem_at<OutT>(orow, chw, plane_pitch, x, c, C) = o[c];
-    }
-    return;
-  }
-  const int x0 = (blockIdx.x * 64 + lane) * P;
-  if (x0 >= w) return;
-  const uint8_t* in = src + (size_t)y * src_stride + (size_t)x0 * (C * SB);
-  if (x0 + P <= w) {
-    typedef typename LoadWord<(NB % 16 == 0) ? 16 : (NB % 8 == 0) ? 8 : 4>::type LW;
-    constexpr int NL = NB / (int)sizeof(LW);
-    LW lw[NL];
-#pragma unroll
-    for (int k = 0; k < NL; k++) lw[k] = reinterpret_cast<const LW*>(in)[k];
-    InT smp[P * C];
-    __builtin_memcpy(smp, lw, NB);
-    int4 rec[P]; // the columns' taps: P loads of 16 bytes, issued together
-#pragma unroll
-    for (int i = 0; i < P; i++) rec[i] = G.xrec[x0 + i];
-    OutT o[P * C]; // pixel-major: the row's own order
-#pragma unroll
-    for (int i = 0; i < P; i++) {
-      gain_M(G, gt, tap_of(rec[i]), ty, M);
-      pixel<C, OutT>(L, lds, G, M, smp[i * C], smp[i * C + 1], smp[i * C + 2], C == 4 ? smp[i * C + C - 1] : 0u, a, &o[i * C]);
-    }
-    if (chw) {
-#pragma unroll
-      for (int c = 0; c < C; c++) {
-        OutT oc[P];
-#pragma unroll
-        for (int i = 0; i < P; i++) oc[i] = o[i * C + c];
-        store16(elem_at<OutT>(orow, true, plane_pitch, x0, c, C), oc);
-      }
-    }
-    else {
-#pragma unroll
-      for (int k = 0; k < C; k++) store16(elem_at<OutT>(orow, false, 0, x0, 0, C) + k * P, &o[k * P]); // P * C elements in a row: C stores of P elements
-    }
-    return;
-  }
-  const int n = w - x0 < P ? w - x0 : P; // the ragged last group: element by element
-  const InT* ip = reinterpret_cast<const InT*>(in);
-#pragma unroll 1
-  for (int i = 0; i < n; i++) {
-    OutT o[C];
-    gain_M(G, gt, tap_of(G.xrec[x0 + i]), ty, M);
-    pixel<C, OutT>(L, lds, G, M, ip[i * C], ip[i * C + 1], ip[i * C + 2], C == 4 ? ip[i * C + C - 1] : 0u, a, o);
-#pragma unroll
-    for (int c = 0; c < C; c++) *elem_at<OutT>(orow, chw, plane_pitch, x0 + i, c, C) = o[c];
-  }
+  pointwise_body<SB, C, C, OutT, VEC>(
+    src, src_stride, w, y, dst, row_pitch, plane_pitch, chw,
+    [&](int, const unsigned (&v)[C], OutT* o, const int4& rec) {
+      float M[3];
+      gain_M(G, gt, tap_of(rec), ty, M);
+      pixel<C, OutT>(L, T, G, M, v, a, o);
+    },
+    [&](int x) { return G.xrec[x]; });
 }
 
-// HM_VIEW_NEAREST: out pixel (j, k) is base pixel (j * n_w / ow, k * n_h / oh) and map sample (j * mw / ow, k * mh / oh) of the map's crop.
+// nearest_body (out_rows.h): the base pixel it picks, and map sample (j * mw / ow, k * mh / oh) of the map's crop.
 // grid: x = groups of 64 columns, y = groups of 4 rows.
 template <typename InT, int C, typename OutT>
 __global__ __launch_bounds__(256) void k_gain_nearest(const uint8_t* __restrict__ src, int src_stride, int n_w, int n_h, int ow, int oh, int chw,
                                                       uint8_t* __restrict__ dst, long long row_pitch, long long plane_pitch, Affine a, Light L, Gain G)
 {
   extern __shared__ __attribute__((aligned(16))) float lds[];
-  const float* gt = fill_all(lds, L, G);
-  const int j = blockIdx.x * 64 + (threadIdx.x & 63), k = blockIdx.y * 4 + (threadIdx.x >> 6);
-  if (j >= ow || k >= oh) return;
-  const int sx = j * n_w / ow, sy = k * n_h / oh;
-  const InT* in = reinterpret_cast<const InT*>(src + (size_t)sy * src_stride) + (size_t)sx * C;
-  const unsigned v = map_sample(G, G.map + (size_t)(k * G.mh / oh) * G.map_stride, j * G.mw / ow);
-  const int n1 = 1 << G.mbits;
-  const float M[3] = {gt[v], G.nch == 3 ? gt[n1 + v] : gt[v], G.nch == 3 ? gt[2 * n1 + v] : gt[v]};
-  OutT o[C];
-  pixel<C, OutT>(L, lds, G, M, in[0], in[1], in[2], C == 4 ? in[C - 1] : 0u, a, o);
-  uint8_t* orow = dst + (long long)k * row_pitch;
-#pragma unroll
-  for (int c = 0; c < C; c++) *elem_at<OutT>(orow, chw, plane_pitch, j, c, C) = o[c];
+  const float* gt;
+  const TablesAt T = fill_all(lds, L, G, &gt);
+  nearest_body<sizeof(InT), C, C, OutT>(src, src_stride, n_w, n_h, ow, oh, chw, dst, row_pitch, plane_pitch, [&](int j, const unsigned (&v)[C], OutT* o, NoColumn::Rec) {
+    const int k = blockIdx.y * 4 + (threadIdx.x >> 6);
+    const unsigned mv = map_sample(G, G.map + (size_t)(k * G.mh / oh) * G.map_stride, j * G.mw / ow);
+    const int n1 = 1 << G.mbits;
+    const float M[3] = {gt[mv], G.nch == 3 ? gt[n1 + mv] : gt[mv], G.nch == 3 ? gt[2 * n1 + mv] : gt[mv]};
+    pixel<C, OutT>(L, T, G, M, v, a, o);
+  });
 }
 
 // the sample-to-float step of k_gain_map_h: a map code through one channel's table (in LDS)
@@ -220,62 +166,63 @@ __global__ __launch_bounds__(256) void k_gain_map_h(const uint8_t* __restrict__ 
                                                     const float* __restrict__ tab, int mbits)
 {
   extern __shared__ __attribute__((aligned(16))) float lds[];
-  fill_tables(lds, tab + ((size_t)blockIdx.z << mbits), 1 << mbits, nullptr, 0, nullptr, 0);
+  fill_tables(lds, tab + ((size_t)blockIdx.z << mbits), 1 << mbits);
   resample_h_body<SB, 1, true>(map, map_stride, mh, ow, first, count, wts, mtmp + (long long)blockIdx.z * pitch * mh, pitch, 0, TabLookup{lds, (1u << mbits) - 1u});
 }
 
-// The map's vertical pass: plane blockIdx.z of mtmp -> plane blockIdx.z of M (oh rows).  A lane is one output pixel, a wave 64
-// consecutive pixels of one row: the taps are wave-uniform.  grid: x = groups of 64 columns, y = groups of 4 output rows, z = channels.
+// The map's vertical pass: plane blockIdx.z of mtmp -> plane blockIdx.z of M (oh rows), vertical_sums (out_rows.h) of one channel.
+// grid: x = groups of 64 columns, y = groups of 4 output rows, z = channels.
 __global__ __launch_bounds__(256) void k_gain_map_v(const float* __restrict__ mtmp, long long pitch, int mh, int ow, int oh, const int32_t* __restrict__ first,
                                                     const int32_t* __restrict__ count, const float* __restrict__ wts, float* __restrict__ M)
 {
   const int j = blockIdx.x * 64 + (threadIdx.x & 63), k = blockIdx.y * 4 + (threadIdx.x >> 6);
   if (j >= ow || k >= oh) return;
-  const int y0 = first[k], n = count[k];
-  const float* col = mtmp + (long long)blockIdx.z * pitch * mh + (long long)y0 * pitch + j;
-  float acc = 0.0f;
-  for (int i = 0; i < n; i++) {
-    acc = __fadd_rn(acc, __fmul_rn(wts[(size_t)i * oh + k], *col));
-    col += pitch;
-  }
-  M[(long long)blockIdx.z * pitch * oh + (long long)k * pitch + j] = acc;
+  float acc[1];
+  vertical_sums<1, true>(mtmp + (long long)blockIdx.z * pitch * mh, pitch, 0, j, k, oh, first, count, wts, acc);
+  M[(long long)blockIdx.z * pitch * oh + (long long)k * pitch + j] = acc[0];
 }
 
-// The base's vertical pass: k_light_v's sums of ONE pixel per lane, then the update with M (nch planes of oh rows of m_pitch floats),
-// matrix, tone step and finish.  grid: x = groups of 64 columns, y = groups of 4 output rows; dynamic LDS: enc when re-encoding, then
-// thr and sg with a tone step.
+// The base's vertical pass: k_light_v's sums of ONE pixel per lane (vertical_sums), then the update with M (nch planes of oh rows of
+// m_pitch floats) and light_out.  grid: x = groups of 64 columns, y = groups of 4 output rows; dynamic LDS: enc when re-encoding, then
+// the tone tables.
 template <typename OutT, bool CHW, int C>
 __global__ __launch_bounds__(256) void k_gain_v(const float* __restrict__ tmp, long long pitch, long long plane, int ow, int oh, const int32_t* __restrict__ first,
                                                 const int32_t* __restrict__ count, const float* __restrict__ wts, const float* __restrict__ Mp, long long m_pitch,
                                                 uint8_t* __restrict__ dst, long long row_pitch, long long plane_pitch, Affine a, Light L, Gain G)
 {
   extern __shared__ __attribute__((aligned(16))) float lds[];
-  const int ne = L.encode ? 1 << L.ebits : 0;
-  if (L.encode || L.tone) fill_tables(lds, L.enc, ne, L.tone, 2 * TONE_STEPS, nullptr, 0); // (uniform: the barrier inside is met by every thread or by none)
+  const LightTables T = fill_light(lds, L, false);
   const int j = blockIdx.x * 64 + (threadIdx.x & 63), k = blockIdx.y * 4 + (threadIdx.x >> 6);
   if (j >= ow || k >= oh) return;
-  const int y0 = first[k], n = count[k]; // (the same in every lane of the wave)
-  const float* col = tmp + (long long)y0 * pitch + (CHW ? (long long)j : (long long)j * C);
   float acc[C];
-#pragma unroll
-  for (int c = 0; c < C; c++) acc[c] = 0.0f;
-  for (int i = 0; i < n; i++) {
-    const float w = wts[(size_t)i * oh + k];
-#pragma unroll
-    for (int c = 0; c < C; c++) acc[c] = __fadd_rn(acc[c], __fmul_rn(w, CHW ? col[(long long)c * plane] : col[c]));
-    col += pitch;
-  }
+  vertical_sums<C, CHW>(tmp, pitch, plane, j, k, oh, first, count, wts, acc);
   const float* mp = Mp + (long long)k * m_pitch + j;
   const long long m_plane = m_pitch * oh;
   const float m0 = mp[0];
   const float M[3] = {m0, G.nch == 3 ? mp[m_plane] : m0, G.nch == 3 ? mp[2 * m_plane] : m0};
   OutT o[C];
-  gain_out<C, OutT>(L, lds, G, acc, M, a, o);
+  gain_out(L, T, G, acc, M, a, o);
   if constexpr (C == 4) o[3] = finish<OutT>(acc[3], a.scale[3], a.bias[3], full_peak<OutT>()); // a resampled alpha value: k_resample_v's finish
-  uint8_t* orow = dst + (long long)k * row_pitch;
-#pragma unroll
-  for (int c = 0; c < C; c++) *elem_at<OutT>(orow, CHW, plane_pitch, j, c, C) = o[c];
+  store_pixel<C>(dst + (long long)k * row_pitch, CHW, plane_pitch, j, o);
 }
+
+// every instance the launchers below can pick (hm_debug_kernel_regs, code 12): 26 pointwise (the two of the 8-bit finish from 16-bit
+// samples among them), 13 nearest, 3 of the map's two passes, 16 vertical - 58
+#define HM_GT_SET(SB, T) (const void*)k_gain_tensor<SB, 3, T, true>, (const void*)k_gain_tensor<SB, 3, T, false>, (const void*)k_gain_tensor<SB, 4, T, true>, \
+  (const void*)k_gain_tensor<SB, 4, T, false>
+#define HM_GN_SET(IN, T) (const void*)k_gain_nearest<IN, 3, T>, (const void*)k_gain_nearest<IN, 4, T>
+#define HM_GV_SET(T) (const void*)k_gain_v<T, true, 3>, (const void*)k_gain_v<T, true, 4>, (const void*)k_gain_v<T, false, 3>, (const void*)k_gain_v<T, false, 4>
+const void* const g_instances[] = {
+  HM_GT_SET(1, uint8_t), HM_GT_SET(1, __half), HM_GT_SET(1, float), HM_GT_SET(2, uint16_t), HM_GT_SET(2, __half), HM_GT_SET(2, float),
+  (const void*)k_gain_tensor<2, 3, uint8_t, true>, (const void*)k_gain_tensor<2, 3, uint8_t, false>,
+  HM_GN_SET(uint8_t, uint8_t), HM_GN_SET(uint8_t, __half), HM_GN_SET(uint8_t, float), HM_GN_SET(uint16_t, uint16_t), HM_GN_SET(uint16_t, __half), HM_GN_SET(uint16_t, float),
+  (const void*)k_gain_nearest<uint16_t, 3, uint8_t>,
+  (const void*)k_gain_map_h<1>, (const void*)k_gain_map_h<2>, (const void*)k_gain_map_v,
+  HM_GV_SET(uint8_t), HM_GV_SET(uint16_t), HM_GV_SET(__half), HM_GV_SET(float),
+};
+#undef HM_GT_SET
+#undef HM_GN_SET
+#undef HM_GV_SET
 
 Gain gain_of(const hm_gain_args* ga, size_t light_bytes, size_t* lds_bytes)
 {
@@ -290,86 +237,68 @@ Gain gain_of(const hm_gain_args* ga, size_t light_bytes, size_t* lds_bytes)
   return G;
 }
 
-template <int SB, int C, typename OutT>
+// rows through the instance of k_gain_tensor for the plan's dtype and alignment, or NO_KERNEL_INSTANCE
+template <int SB, int C>
 int launch_tensor(const hm_dest_plan* p, const hm_light_args* la, const hm_gain_args* ga, const uint8_t* src, int src_stride, int w, int rows, uint8_t* dst, const Affine& a,
                   hipStream_t s)
 {
-  constexpr int P = 16 / (int)sizeof(OutT);
   const int chw = p->layout == HM_DEV_LAYOUT_CHW ? 1 : 0;
-  const bool vec = ((uintptr_t)src % 16) == 0 && (src_stride % 16) == 0 && ((uintptr_t)dst % 16) == 0 && (p->row_pitch % 16) == 0 && (!chw || (p->plane_pitch % 16) == 0);
-  const int groups = (w + P - 1) / P;
-  const dim3 grid((unsigned)((groups + 63) / 64), (unsigned)((rows + 3) / 4)), block(256);
   const Light L = light_of(la);
   size_t lds = 0;
   const Gain G = gain_of(ga, light_tables_bytes(la), &lds);
-  if (vec)
-    hipLaunchKernelGGL((k_gain_tensor<SB, C, OutT, true>), grid, block, lds, s, src, src_stride, w, rows, dst, (long long)p->row_pitch, (long long)p->plane_pitch, chw, a, L, G);
-  else
-    hipLaunchKernelGGL((k_gain_tensor<SB, C, OutT, false>), grid, block, lds, s, src, src_stride, w, rows, dst, (long long)p->row_pitch, (long long)p->plane_pitch, chw, a, L, G);
-  return hm_check_hip(hipGetLastError(), "k_gain_tensor launch");
-}
-
-// a float type, the integer type of the samples' own width, or bytes from a deeper three-channel image (the 8-bit finish); nothing else
-template <int SB, int C>
-int launch_tensor_dtype(const hm_dest_plan* p, const hm_light_args* la, const hm_gain_args* ga, const uint8_t* src, int src_stride, int w, int rows, uint8_t* dst,
-                        const Affine& a, hipStream_t s)
-{
-  const int rc = with_dtype(p->dtype, [&](auto tag) -> int {
+  return with_dtype(p->dtype, [&](auto tag) -> int {
     typedef typename decltype(tag)::type OutT;
-    if constexpr (!std::is_integral<OutT>::value || sizeof(OutT) == SB || (SB == 2 && C == 3)) return launch_tensor<SB, C, OutT>(p, la, ga, src, src_stride, w, rows, dst, a, s);
+    if constexpr (has_instance<OutT, SB, C, true>()) {
+      constexpr int P = 16 / (int)sizeof(OutT);
+      const dim3 grid = grid_64x4((w + P - 1) / P, rows), block(256);
+      if (aligned16(src, src_stride, dst, p))
+        hipLaunchKernelGGL((k_gain_tensor<SB, C, OutT, true>), grid, block, lds, s, src, src_stride, w, rows, dst, (long long)p->row_pitch, (long long)p->plane_pitch, chw, a, L, G);
+      else
+        hipLaunchKernelGGL((k_gain_tensor<SB, C, OutT, false>), grid, block, lds, s, src, src_stride, w, rows, dst, (long long)p->row_pitch, (long long)p->plane_pitch, chw, a, L, G);
+      return hm_check_hip(hipGetLastError(), "k_gain_tensor launch");
+    }
     return NO_KERNEL_INSTANCE;
   });
-  if (rc != NO_KERNEL_INSTANCE) return rc;
-  return hm_fail(HM_ERR_INTERNAL, "k_gain_tensor: no kernel for dtype %d on %d-byte samples", p->dtype, SB);
 }
 
-template <typename InT, typename OutT>
+template <int SB, int C>
 int launch_nearest(const hm_dest_plan* p, const hm_light_args* la, const hm_gain_args* ga, const uint8_t* src, int src_stride, int n_w, int n_h, int ow, int oh, uint8_t* dst,
                    const Affine& a, hipStream_t s)
 {
-  const dim3 grid((unsigned)((ow + 63) / 64), (unsigned)((oh + 3) / 4)), block(256);
+  typedef typename std::conditional<SB == 1, uint8_t, uint16_t>::type InT;
   const int chw = p->layout == HM_DEV_LAYOUT_CHW ? 1 : 0;
   const Light L = light_of(la);
   size_t lds = 0;
   const Gain G = gain_of(ga, light_tables_bytes(la), &lds);
-  constexpr bool finish8 = sizeof(InT) == 2 && sizeof(OutT) == 1; // the 8-bit finish of a deeper image: three channels only (check_args)
-  if (p->channels == 3)
-    hipLaunchKernelGGL((k_gain_nearest<InT, 3, OutT>), grid, block, lds, s, src, src_stride, n_w, n_h, ow, oh, chw, dst, (long long)p->row_pitch, (long long)p->plane_pitch, a, L, G);
-  else if constexpr (finish8) return NO_KERNEL_INSTANCE;
-  else
-    hipLaunchKernelGGL((k_gain_nearest<InT, 4, OutT>), grid, block, lds, s, src, src_stride, n_w, n_h, ow, oh, chw, dst, (long long)p->row_pitch, (long long)p->plane_pitch, a, L, G);
-  return HM_OK;
+  return with_dtype(p->dtype, [&](auto tag) -> int {
+    typedef typename decltype(tag)::type OutT;
+    if constexpr (has_instance<OutT, SB, C, true>()) {
+      hipLaunchKernelGGL((k_gain_nearest<InT, C, OutT>), grid_64x4(ow, oh), dim3(256), lds, s, src, src_stride, n_w, n_h, ow, oh, chw, dst, (long long)p->row_pitch,
+                         (long long)p->plane_pitch, a, L, G);
+      return hm_check_hip(hipGetLastError(), "k_gain_nearest launch");
+    }
+    return NO_KERNEL_INSTANCE;
+  });
 }
 
 template <typename OutT>
 void launch_v(const hm_dest_plan* p, const hm_resample_args* r, const hm_light_args* la, const hm_gain_args* ga, uint8_t* dst, const Affine& a, hipStream_t s)
 {
-  const dim3 grid((unsigned)((r->ow + 63) / 64), (unsigned)((r->oh + 3) / 4)), block(256);
-  const size_t lds = light_v_bytes(la);
   const Light L = light_of(la);
   const Gain G = gain_of(ga, 0, nullptr);
-  const bool chw = p->layout == HM_DEV_LAYOUT_CHW;
-#define HM_GV_GO(CHW_, C_) \
-  hipLaunchKernelGGL((k_gain_v<OutT, CHW_, C_>), grid, block, lds, s, (const float*)r->tmp, (long long)r->tmp_pitch, (long long)r->tmp_plane, r->ow, r->oh, r->ay.first, \
-                     r->ay.count, r->ay.weights, (const float*)ga->M, (long long)ga->pitch, dst, (long long)p->row_pitch, (long long)p->plane_pitch, a, L, G)
-  if (chw) { if (p->channels == 3) HM_GV_GO(true, 3); else HM_GV_GO(true, 4); }
-  else { if (p->channels == 3) HM_GV_GO(false, 3); else HM_GV_GO(false, 4); }
-#undef HM_GV_GO
+  with_flags(p->layout == HM_DEV_LAYOUT_CHW, p->channels == 4, [&](auto chw, auto four) {
+    hipLaunchKernelGGL((k_gain_v<OutT, chw.value, four.value ? 4 : 3>), grid_64x4(r->ow, r->oh), dim3(256), light_v_bytes(la), s, (const float*)r->tmp, (long long)r->tmp_pitch,
+                       (long long)r->tmp_plane, r->ow, r->oh, r->ay.first, r->ay.count, r->ay.weights, (const float*)ga->M, (long long)ga->pitch, dst, (long long)p->row_pitch,
+                       (long long)p->plane_pitch, a, L, G);
+  });
 }
 
 // the light step's arguments as light.hip's launchers judge them, then the gain step's
 // taps: 0 none (nearest), 1 the records of the pointwise path, 2 the tables of the summed path
 int check_args(const hm_dest_plan* p, const hm_light_args* la, const hm_gain_args* ga, int taps)
 {
-  if (!la->lin || (la->encode && !la->enc) || la->bits < 8 || la->bits > 12) return hm_fail(HM_ERR_INTERNAL, "k_gain: tables of %d bits", la->bits);
-  if (la->enc_bits != la->bits && la->enc_bits != 8) return hm_fail(HM_ERR_INTERNAL, "k_gain: codes of %d bits from tables of %d", la->enc_bits, la->bits);
-  if (la->src_bytes != (la->bits > 8 ? 2 : 1)) return hm_fail(HM_ERR_INTERNAL, "k_gain: %d-byte samples of %d bits", la->src_bytes, la->bits);
-  if (p->channels != 3 && p->channels != 4) return hm_fail(HM_ERR_INTERNAL, "k_gain: %d channels", p->channels);
-  if (p->sample_bytes != (la->enc_bits > 8 ? 2 : 1) || (p->sample_bytes != la->src_bytes && p->channels != 3))
-    return hm_fail(HM_ERR_INTERNAL, "k_gain: a %d-byte target of %d channels from %d-byte samples, codes of %d bits", p->sample_bytes, p->channels, la->src_bytes, la->enc_bits);
-  const bool integer = p->dtype == HM_DEV_U8 || p->dtype == HM_DEV_U16;
-  if (integer && (!la->encode || p->dtype != (p->sample_bytes == 1 ? HM_DEV_U8 : HM_DEV_U16)))
-    return hm_fail(HM_ERR_INTERNAL, "k_gain: integer dtype %d on %d-byte samples, %s", p->dtype, p->sample_bytes, la->encode ? "re-encoded" : "linear");
+  const int rc = check_light_args("k_gain", p, la);
+  if (rc) return rc;
   if (!ga->tab || !ga->map || (ga->nch != 1 && ga->nch != 3) || ga->map_bits < 8 || ga->map_bits > HM_GAIN_MAX_BITS || ga->map_bytes != (ga->map_bits > 8 ? 2 : 1) ||
       ga->mw < 1 || ga->mh < 1 || (int64_t)ga->map_stride < (int64_t)ga->mw * ga->map_bytes)
     return hm_fail(HM_ERR_INTERNAL, "k_gain: a map of %d x %d samples of %d bits in %d bytes, stride %d, %d tables", ga->mw, ga->mh, ga->map_bits, ga->map_bytes, ga->map_stride, ga->nch);
@@ -379,6 +308,11 @@ int check_args(const hm_dest_plan* p, const hm_light_args* la, const hm_gain_arg
 }
 
 } // namespace
+
+extern "C" const void* hm_gain_kernel_of(int index) // (test_hooks.cpp: hm_debug_kernel_regs)
+{
+  return index >= 0 && index < (int)(sizeof(g_instances) / sizeof(g_instances[0])) ? g_instances[index] : nullptr;
+}
 
 // rows [0, rows) of `src` (the crop itself: w x rows) through the light and gain steps to `dst` = the destination's first element;
 // ga->ax / ga->ay: the map's taps onto w and rows.  Asynchronous on `s`.
@@ -392,8 +326,11 @@ extern "C" int hm_launch_gain_tensor(const hm_dest_plan* p, const hm_light_args*
   const Affine a = affine_of(scale, bias);
   const uint8_t* in = (const uint8_t*)src;
   uint8_t* out = (uint8_t*)dst;
-  if (la->src_bytes == 1) return p->channels == 3 ? launch_tensor_dtype<1, 3>(p, la, ga, in, src_stride, w, rows, out, a, s) : launch_tensor_dtype<1, 4>(p, la, ga, in, src_stride, w, rows, out, a, s);
-  return p->channels == 3 ? launch_tensor_dtype<2, 3>(p, la, ga, in, src_stride, w, rows, out, a, s) : launch_tensor_dtype<2, 4>(p, la, ga, in, src_stride, w, rows, out, a, s);
+  const int found = with_flags(la->src_bytes == 2, p->channels == 4, [&](auto wide, auto four) {
+    return launch_tensor<wide.value ? 2 : 1, four.value ? 4 : 3>(p, la, ga, in, src_stride, w, rows, out, a, s);
+  });
+  if (found == NO_KERNEL_INSTANCE) return hm_fail(HM_ERR_INTERNAL, "k_gain_tensor: no kernel for dtype %d on %d-byte samples", p->dtype, la->src_bytes);
+  return found;
 }
 
 extern "C" int hm_launch_gain_nearest(const hm_dest_plan* p, const hm_light_args* la, const hm_gain_args* ga, const void* src, int src_stride, int n_w, int n_h, int ow, int oh,
@@ -405,16 +342,11 @@ extern "C" int hm_launch_gain_nearest(const hm_dest_plan* p, const hm_light_args
   const Affine a = affine_of(scale, bias);
   const uint8_t* in = (const uint8_t*)src;
   uint8_t* out = (uint8_t*)dst;
-  const bool wide = la->src_bytes == 2;
-  // 16-bit elements from 16-bit samples only; bytes from either width (from 16-bit samples: the 8-bit finish); floats from either
-  const int found = with_dtype(p->dtype, [&](auto tag) -> int {
-    typedef typename decltype(tag)::type OutT;
-    if (wide) return launch_nearest<uint16_t, OutT>(p, la, ga, in, src_stride, n_w, n_h, ow, oh, out, a, s);
-    if constexpr (!std::is_same<OutT, uint16_t>::value) return launch_nearest<uint8_t, OutT>(p, la, ga, in, src_stride, n_w, n_h, ow, oh, out, a, s);
-    return NO_KERNEL_INSTANCE;
+  const int found = with_flags(la->src_bytes == 2, p->channels == 4, [&](auto wide, auto four) {
+    return launch_nearest<wide.value ? 2 : 1, four.value ? 4 : 3>(p, la, ga, in, src_stride, n_w, n_h, ow, oh, out, a, s);
   });
   if (found == NO_KERNEL_INSTANCE) return hm_fail(HM_ERR_INTERNAL, "k_gain_nearest: no kernel for dtype %d on %d-byte samples", p->dtype, la->src_bytes);
-  return hm_check_hip(hipGetLastError(), "k_gain_nearest launch");
+  return found;
 }
 
 // a resampled view under the light and gain steps: the map's two passes into M, k_light_h, k_gain_v
@@ -427,7 +359,7 @@ extern "C" int hm_launch_gain_resample(const hm_dest_plan* p, const hm_light_arg
   if (!ga->mtmp || !ga->M || ga->pitch < r->ow || ga->ax.m != r->ow || ga->ay.m != r->oh)
     return hm_fail(HM_ERR_INTERNAL, "k_gain_map: taps for %d x %d, the view writes %d x %d (pitch %lld)", ga->ax.m, ga->ay.m, r->ow, r->oh, (long long)ga->pitch);
   const dim3 block(256);
-  const dim3 grid_h((unsigned)((r->ow + 63) / 64), (unsigned)((ga->mh + 3) / 4), (unsigned)ga->nch), grid_v((unsigned)((r->ow + 63) / 64), (unsigned)((r->oh + 3) / 4), (unsigned)ga->nch);
+  const dim3 grid_h = grid_64x4(r->ow, ga->mh, ga->nch), grid_v = grid_64x4(r->ow, r->oh, ga->nch);
   const size_t lds_h = (size_t)4 << ga->map_bits;
   const uint8_t* map = (const uint8_t*)ga->map;
   if (ga->map_bytes == 1)

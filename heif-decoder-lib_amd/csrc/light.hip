@@ -2,14 +2,14 @@
 // through a table, change primaries through a 3 x 3 matrix, and are stored as linear floats or re-encoded by a search in a
 // threshold table.  No transcendental function runs here: both tables are built on the host in double (devdest.cpp), so a
 // float32 restatement on the host is exact.
-//   k_light_tensor   the pointwise path, k_to_tensor's streaming shape: a wave takes 64 consecutive pixel groups of ONE row, a lane's
-//                    group is 16 bytes of output per channel plane, 16-byte stores where pointers and pitches allow, the scalar
-//                    instance (lane l takes pixels l, l + 64, ...) otherwise.  The crop alone runs here on the offset source.
-//   k_light_nearest  HM_VIEW_NEAREST: the pixel at (j * n_w / ow, k * n_h / oh) through the same per-pixel step.
+//   k_light_tensor   the pointwise path: pointwise_body (out_rows.h), k_to_tensor's streaming shape - a wave takes 64 consecutive pixel
+//                    groups of ONE row, 16-byte stores where pointers and pitches allow, the scalar instance otherwise - with the
+//                    step as its pixel.  The crop alone runs here on the offset source.
+//   k_light_nearest  HM_VIEW_NEAREST: the nearest source pixel through the same per-pixel step (nearest_body's text, out_rows.h).
 //   k_light_h        k_resample_h's body (resample_h_body, out_rows.h: its sums in its order) with the table lookup in place of the
 //                    conversion to float (alpha: the conversion as it was).  The unstaged form, for all three filters.
-//   k_light_v        the vertical sums of ONE pixel per lane - the matrix needs R, G and B together: a CHW intermediate is read at
-//                    one index of three planes -, then matrix and finish.
+//   k_light_v        vertical_sums (out_rows.h) of ONE pixel per lane - the matrix needs R, G and B together: a CHW intermediate is
+//                    read at one index of three planes -, then light_out.
 // The tone step (hm_device_tone) sits between matrix and finish: the max of R, G, B is searched in thr[2048] like a code in enc, and
 // the pixel is scaled by sg[] at the count - a wave-uniform branch, like `encode` and `matrix`.
 // The OOTF step (hm_device_ootf) sits in front of the matrix: the scene luminance Ys = y . RGB is searched in thr[1024], and the pixel is
@@ -21,7 +21,8 @@
 // noise the worst; no layout of a table changes that.
 // The matrix and the scalars of the step are kernel arguments (SGPRs).  -ffp-contract=off, __fmul_rn / __fadd_rn throughout.
 // What is stored is out_elem.h's: a code value is `moved`, linear light goes through `linear_out`, a resampled alpha value through
-// `finish`.  The per-pixel rules - table fill, re-encoding, matrix, tone step, colour_out - are light_step.h's, shared with alpha.hip.
+// `finish`.  The per-pixel rules - the tables' layout and fill, light_in, and light_out: OOTF step, matrix, tone step, colour_out - are
+// light_step.h's, shared with alpha.hip and gain.hip; grids, the 16-byte test and the rule which instances exist are out_launch.h's.
 #include "hm_devdest.h"
 #include "light_step.h"
 #include "out_launch.h"
@@ -29,106 +30,48 @@
 
 namespace {
 
-// one pixel that is moved, not resampled: v0 .. v2 its colour samples, v3 its alpha sample (C == 4); lds = lin, then enc, then thr and sg
+// one pixel that is moved, not resampled: v[0 .. 2] its colour samples, v[3] its alpha sample (C == 4)
 template <int C, typename OutT>
-__device__ __forceinline__ void pixel(const Light& L, const float* lds, unsigned v0, unsigned v1, unsigned v2, unsigned v3, const Affine& a, OutT o[C])
+__device__ __forceinline__ void pixel(const Light& L, const LightTables& T, const unsigned (&v)[C], const Affine& a, OutT* o)
 {
-  const unsigned peak = (1u << L.bits) - 1u;
-  float r[3] = {lds[min(v0, peak)], lds[min(v1, peak)], lds[min(v2, peak)]};
-  const float* enc = lds + (1 << L.bits);
-  if (L.ootf) ootf_map(L, ootf_tables(L, enc), r);
-  gamut(L, r);
-  if (L.tone) tone_map(enc + (L.encode ? 1 << L.ebits : 0), r);
-  o[0] = colour_out<OutT>(L, enc, r[0], a.scale[0], a.bias[0]);
-  o[1] = colour_out<OutT>(L, enc, r[1], a.scale[1], a.bias[1]);
-  o[2] = colour_out<OutT>(L, enc, r[2], a.scale[2], a.bias[2]);
-  if constexpr (C == 4) o[3] = moved<OutT>(v3, a.scale[3], a.bias[3]);
+  float r[3];
+  light_in(L, T, v, r);
+  light_out(L, T, r, a, o);
+  if constexpr (C == 4) o[3] = moved<OutT>(v[3], a.scale[3], a.bias[3]);
 }
 
-// SB: bytes per input sample (1 / 2, little-endian), C: channels, CHW: one plane per channel, VEC: 16-byte accesses allowed (the
-// launcher has checked the alignment of both sides).  grid: x = groups of 64 pixel groups, y = groups of 4 rows; dynamic LDS: the tables.
+// pointwise_body (out_rows.h) with the step as its pixel.  SB: bytes per input sample (1 / 2, little-endian), C: channels, CHW: one plane
+// per channel, VEC: 16-byte accesses allowed.  grid: x = groups of 64 pixel groups, y = groups of 4 rows; dynamic LDS: the tables.
 template <int SB, int C, typename OutT, bool CHW, bool VEC>
 __global__ __launch_bounds__(256) void k_light_tensor(const uint8_t* __restrict__ src, int src_stride, int w, int h, uint8_t* __restrict__ dst,
                                                       long long row_pitch, long long plane_pitch, Affine a, Light L)
 {
   extern __shared__ __attribute__((aligned(16))) float lds[];
-  typedef typename std::conditional<SB == 1, uint8_t, uint16_t>::type InT;
-  constexpr int P = 16 / (int)sizeof(OutT); // pixels per lane
-  constexpr int NB = P * C * SB;            // input bytes per lane
-  fill_tables(lds, L.lin, 1 << L.bits, L.enc, L.encode ? 1 << L.ebits : 0, L.tone, L.tone ? 2 * TONE_STEPS : 0, L.ootf, 2 * OOTF_STEPS);
-  const int lane = threadIdx.x & 63, y = blockIdx.y * 4 + (threadIdx.x >> 6);
+  const LightTables T = fill_light(lds, L, true);
+  const int y = blockIdx.y * 4 + (threadIdx.x >> 6);
   if (y >= h) return;
-  uint8_t* orow = dst + (long long)y * row_pitch;
-  if (!VEC) { // one pixel per lane and step: pixels lane, lane + 64, ... of the wave's 64 * P
-    const InT* irow = reinterpret_cast<const InT*>(src + (size_t)y * src_stride);
-#pragma unroll 1
-    for (int i = 0; i < P; i++) {
-      const int x = (blockIdx.x * P + i) * 64 + lane;
-      if (x >= w) break;
-      const InT* ip = irow + (size_t)x * C;
-      OutT o[C];
-      pixel<C, OutT>(L, lds, ip[0], ip[1], ip[2], C == 4 ? ip[C - 1] : 0u, a, o);
-#pragma unroll
-      for (int c = 0; c < C; c++) *elem_at<OutT>(orow, CHW, plane_pitch, x, c, C) = o[c];
-    }
-    return;
-  }
-  const int x0 = (blockIdx.x * 64 + lane) * P;
-  if (x0 >= w) return;
-  const uint8_t* in = src + (size_t)y * src_stride + (size_t)x0 * (C * SB);
-  if (x0 + P <= w) {
-    typedef typename LoadWord<(NB % 16 == 0) ? 16 : (NB % 8 == 0) ? 8 : 4>::type LW;
-    constexpr int NL = NB / (int)sizeof(LW);
-    LW lw[NL];
-#pragma unroll
-    for (int k = 0; k < NL; k++) lw[k] = reinterpret_cast<const LW*>(in)[k];
-    InT smp[P * C];
-    __builtin_memcpy(smp, lw, NB);
-    OutT o[P * C]; // pixel-major: the row's own order
-#pragma unroll
-    for (int i = 0; i < P; i++) pixel<C, OutT>(L, lds, smp[i * C], smp[i * C + 1], smp[i * C + 2], C == 4 ? smp[i * C + C - 1] : 0u, a, &o[i * C]);
-    if (CHW) {
-#pragma unroll
-      for (int c = 0; c < C; c++) {
-        OutT oc[P];
-#pragma unroll
-        for (int i = 0; i < P; i++) oc[i] = o[i * C + c];
-        store16(elem_at<OutT>(orow, true, plane_pitch, x0, c, C), oc);
-      }
-    }
-    else {
-#pragma unroll
-      for (int k = 0; k < C; k++) store16(elem_at<OutT>(orow, false, 0, x0, 0, C) + k * P, &o[k * P]); // P * C elements in a row: C stores of P elements
-    }
-    return;
-  }
-  const int n = w - x0 < P ? w - x0 : P; // the ragged last group: element by element
-  const InT* ip = reinterpret_cast<const InT*>(in);
-#pragma unroll 1
-  for (int i = 0; i < n; i++) {
-    OutT o[C];
-    pixel<C, OutT>(L, lds, ip[i * C], ip[i * C + 1], ip[i * C + 2], C == 4 ? ip[i * C + C - 1] : 0u, a, o);
-#pragma unroll
-    for (int c = 0; c < C; c++) *elem_at<OutT>(orow, CHW, plane_pitch, x0 + i, c, C) = o[c];
-  }
+  pointwise_body<SB, C, C, OutT, VEC>(src, src_stride, w, y, dst, row_pitch, plane_pitch, CHW,
+                                      [&](int, const unsigned (&v)[C], OutT* o, NoColumn::Rec) { pixel<C, OutT>(L, T, v, a, o); });
 }
 
-// HM_VIEW_NEAREST: out pixel (j, k) is source pixel (j * n_w / ow, k * n_h / oh).  grid: x = groups of 64 columns, y = groups of 4 rows.
+// HM_VIEW_NEAREST: nearest_body's text (out_rows.h) written out - through the shared body k_light_nearest<uint8_t, 4, __half> is 1 - 2 %
+// slower at 4000 x 3000 (profiles/step_kernels_refactor.txt).  grid: x = groups of 64 columns, y = groups of 4 rows; dynamic LDS: the tables.
 template <typename InT, int C, typename OutT>
 __global__ __launch_bounds__(256) void k_light_nearest(const uint8_t* __restrict__ src, int src_stride, int n_w, int n_h, int ow, int oh, int chw,
                                                        uint8_t* __restrict__ dst, long long row_pitch, long long plane_pitch, Affine a, Light L)
 {
   extern __shared__ __attribute__((aligned(16))) float lds[];
-  fill_tables(lds, L.lin, 1 << L.bits, L.enc, L.encode ? 1 << L.ebits : 0, L.tone, L.tone ? 2 * TONE_STEPS : 0, L.ootf, 2 * OOTF_STEPS);
+  const LightTables T = fill_light(lds, L, true);
   const int j = blockIdx.x * 64 + (threadIdx.x & 63), k = blockIdx.y * 4 + (threadIdx.x >> 6);
   if (j >= ow || k >= oh) return;
   const int sx = j * n_w / ow, sy = k * n_h / oh;
   const InT* in = reinterpret_cast<const InT*>(src + (size_t)sy * src_stride) + (size_t)sx * C;
-  OutT o[C];
-  pixel<C, OutT>(L, lds, in[0], in[1], in[2], C == 4 ? in[C - 1] : 0u, a, o);
-  uint8_t* orow = dst + (long long)k * row_pitch;
+  unsigned v[C];
 #pragma unroll
-  for (int c = 0; c < C; c++) *elem_at<OutT>(orow, chw, plane_pitch, j, c, C) = o[c];
+  for (int c = 0; c < C; c++) v[c] = in[c];
+  OutT o[C];
+  pixel<C, OutT>(L, T, v, a, o);
+  store_pixel<C>(dst + (long long)k * row_pitch, chw, plane_pitch, j, o);
 }
 
 // the sample-to-float step of k_light_h: the colour channels through lin (in LDS), alpha converted as it is
@@ -145,44 +88,27 @@ __global__ __launch_bounds__(256) void k_light_h(const uint8_t* __restrict__ src
                                                  long long pitch, long long plane, const float* __restrict__ lin, int bits)
 {
   extern __shared__ __attribute__((aligned(16))) float lds[];
-  fill_tables(lds, lin, 1 << bits, nullptr, 0, nullptr, 0);
+  fill_tables(lds, lin, 1 << bits);
   resample_h_body<SB, C, CHW>(src, src_stride, n_h, ow, first, count, wts, tmp, pitch, plane, LinLookup{lds, (1u << bits) - 1u});
 }
 
-// The vertical pass: a lane is ONE output pixel, a wave 64 consecutive pixels of one output row, so the taps are wave-uniform and
-// the reads of a CHW intermediate coalesce per plane (an HWC one: the wave reads 64 * C consecutive floats in C instructions).
-// grid: x = groups of 64 columns, y = groups of 4 output rows; dynamic LDS: enc when re-encoding, then thr and sg with a tone step.
+// The vertical pass: vertical_sums (out_rows.h) of ONE pixel per lane - the matrix needs R, G and B together -, then light_out.
+// grid: x = groups of 64 columns, y = groups of 4 output rows; dynamic LDS: enc when re-encoding, then the tone and the OOTF tables.
 template <typename OutT, bool CHW, int C>
 __global__ __launch_bounds__(256) void k_light_v(const float* __restrict__ tmp, long long pitch, long long plane, int ow, int oh,
                                                  const int32_t* __restrict__ first, const int32_t* __restrict__ count, const float* __restrict__ wts,
                                                  uint8_t* __restrict__ dst, long long row_pitch, long long plane_pitch, Affine a, Light L)
 {
   extern __shared__ __attribute__((aligned(16))) float lds[];
-  const int ne = L.encode ? 1 << L.ebits : 0;
-  if (L.encode || L.tone || L.ootf) fill_tables(lds, L.enc, ne, L.tone, L.tone ? 2 * TONE_STEPS : 0, L.ootf, 2 * OOTF_STEPS); // (uniform: the barrier inside is met by every thread or by none)
+  const LightTables T = fill_light(lds, L, false);
   const int j = blockIdx.x * 64 + (threadIdx.x & 63), k = blockIdx.y * 4 + (threadIdx.x >> 6);
   if (j >= ow || k >= oh) return;
-  const int y0 = first[k], n = count[k]; // (the same in every lane of the wave)
-  const float* col = tmp + (long long)y0 * pitch + (CHW ? (long long)j : (long long)j * C);
   float acc[C];
-#pragma unroll
-  for (int c = 0; c < C; c++) acc[c] = 0.0f;
-  for (int i = 0; i < n; i++) {
-    const float w = wts[(size_t)i * oh + k];
-#pragma unroll
-    for (int c = 0; c < C; c++) acc[c] = __fadd_rn(acc[c], __fmul_rn(w, CHW ? col[(long long)c * plane] : col[c]));
-    col += pitch;
-  }
-  if (L.ootf) ootf_map(L, ootf_tables(L, lds), acc);
-  gamut(L, acc);
-  if (L.tone) tone_map(lds + ne, acc);
+  vertical_sums<C, CHW>(tmp, pitch, plane, j, k, oh, first, count, wts, acc);
   OutT o[C];
-#pragma unroll
-  for (int c = 0; c < 3; c++) o[c] = colour_out<OutT>(L, lds, acc[c], a.scale[c], a.bias[c]);
+  light_out(L, T, acc, a, o);
   if constexpr (C == 4) o[3] = finish<OutT>(acc[3], a.scale[3], a.bias[3], full_peak<OutT>()); // a resampled alpha value: k_resample_v's finish
-  uint8_t* orow = dst + (long long)k * row_pitch;
-#pragma unroll
-  for (int c = 0; c < C; c++) *elem_at<OutT>(orow, CHW, plane_pitch, j, c, C) = o[c];
+  store_pixel<C>(dst + (long long)k * row_pitch, CHW, plane_pitch, j, o);
 }
 
 // every instance the launchers below can pick (hm_debug_kernel_regs): 48 pointwise, 12 nearest, 8 horizontal, 16 vertical
@@ -208,61 +134,47 @@ const void* const g_finish8_instances[] = {
 #undef HM_LN_SET
 #undef HM_LV_SET
 
-template <int SB, int C, typename OutT, bool CHW>
+// rows through the instance of k_light_tensor for the plan's dtype, layout and alignment, or NO_KERNEL_INSTANCE
+template <int SB, int C>
 int launch_tensor(const hm_dest_plan* p, const hm_light_args* la, const uint8_t* src, int src_stride, int w, int rows, uint8_t* dst, const Affine& a, hipStream_t s)
 {
-  constexpr int P = 16 / (int)sizeof(OutT);
-  const bool vec = ((uintptr_t)src % 16) == 0 && (src_stride % 16) == 0 && ((uintptr_t)dst % 16) == 0 && (p->row_pitch % 16) == 0 &&
-                   (!CHW || (p->plane_pitch % 16) == 0);
-  const int groups = (w + P - 1) / P;
-  const dim3 grid((unsigned)((groups + 63) / 64), (unsigned)((rows + 3) / 4)), block(256);
   const Light L = light_of(la);
-  if (vec)
-    hipLaunchKernelGGL((k_light_tensor<SB, C, OutT, CHW, true>), grid, block, light_tables_bytes(la), s, src, src_stride, w, rows, dst, (long long)p->row_pitch,
-                       (long long)p->plane_pitch, a, L);
-  else
-    hipLaunchKernelGGL((k_light_tensor<SB, C, OutT, CHW, false>), grid, block, light_tables_bytes(la), s, src, src_stride, w, rows, dst, (long long)p->row_pitch,
-                       (long long)p->plane_pitch, a, L);
-  return hm_check_hip(hipGetLastError(), "k_light_tensor launch");
-}
-
-// a float type, the integer type of the samples' own width, or bytes from a deeper three-channel image (the 8-bit finish); nothing else
-template <int SB, int C>
-int launch_tensor_dtype(const hm_dest_plan* p, const hm_light_args* la, const uint8_t* src, int src_stride, int w, int rows, uint8_t* dst, const Affine& a, hipStream_t s)
-{
-  const bool chw = p->layout == HM_DEV_LAYOUT_CHW;
-  const int rc = with_dtype(p->dtype, [&](auto tag) -> int {
+  return with_dtype(p->dtype, [&](auto tag) -> int {
     typedef typename decltype(tag)::type OutT;
-    if constexpr (!std::is_integral<OutT>::value || sizeof(OutT) == SB || (SB == 2 && C == 3))
-      return chw ? launch_tensor<SB, C, OutT, true>(p, la, src, src_stride, w, rows, dst, a, s) : launch_tensor<SB, C, OutT, false>(p, la, src, src_stride, w, rows, dst, a, s);
+    if constexpr (has_instance<OutT, SB, C, true>()) {
+      constexpr int P = 16 / (int)sizeof(OutT);
+      with_flags(p->layout == HM_DEV_LAYOUT_CHW, aligned16(src, src_stride, dst, p), [&](auto chw, auto vec) {
+        hipLaunchKernelGGL((k_light_tensor<SB, C, OutT, chw.value, vec.value>), grid_64x4((w + P - 1) / P, rows), dim3(256), light_tables_bytes(la), s, src, src_stride, w,
+                           rows, dst, (long long)p->row_pitch, (long long)p->plane_pitch, a, L);
+      });
+      return hm_check_hip(hipGetLastError(), "k_light_tensor launch");
+    }
     return NO_KERNEL_INSTANCE;
   });
-  if (rc != NO_KERNEL_INSTANCE) return rc;
-  return hm_fail(HM_ERR_INTERNAL, "k_light_tensor: no kernel for dtype %d on %d-byte samples", p->dtype, SB);
 }
 
-template <typename InT, typename OutT>
+template <int SB, int C>
 int launch_nearest(const hm_dest_plan* p, const hm_light_args* la, const uint8_t* src, int src_stride, int n_w, int n_h, int ow, int oh, uint8_t* dst, const Affine& a,
-                    hipStream_t s)
+                   hipStream_t s)
 {
-  const dim3 grid((unsigned)((ow + 63) / 64), (unsigned)((oh + 3) / 4)), block(256);
+  typedef typename std::conditional<SB == 1, uint8_t, uint16_t>::type InT;
   const int chw = p->layout == HM_DEV_LAYOUT_CHW ? 1 : 0;
   const Light L = light_of(la);
-  constexpr bool finish8 = sizeof(InT) == 2 && sizeof(OutT) == 1; // the 8-bit finish of a deeper image: three channels only (check_args)
-  if (p->channels == 3)
-    hipLaunchKernelGGL((k_light_nearest<InT, 3, OutT>), grid, block, light_tables_bytes(la), s, src, src_stride, n_w, n_h, ow, oh, chw, dst, (long long)p->row_pitch,
-                       (long long)p->plane_pitch, a, L);
-  else if constexpr (finish8) return NO_KERNEL_INSTANCE;
-  else
-    hipLaunchKernelGGL((k_light_nearest<InT, 4, OutT>), grid, block, light_tables_bytes(la), s, src, src_stride, n_w, n_h, ow, oh, chw, dst, (long long)p->row_pitch,
-                       (long long)p->plane_pitch, a, L);
-  return HM_OK;
+  return with_dtype(p->dtype, [&](auto tag) -> int {
+    typedef typename decltype(tag)::type OutT;
+    if constexpr (has_instance<OutT, SB, C, true>()) {
+      hipLaunchKernelGGL((k_light_nearest<InT, C, OutT>), grid_64x4(ow, oh), dim3(256), light_tables_bytes(la), s, src, src_stride, n_w, n_h, ow, oh, chw, dst,
+                         (long long)p->row_pitch, (long long)p->plane_pitch, a, L);
+      return hm_check_hip(hipGetLastError(), "k_light_nearest launch");
+    }
+    return NO_KERNEL_INSTANCE;
+  });
 }
 
 template <int SB, int C>
 void launch_h(bool chw, const hm_resample_args* r, const hm_light_args* la, hipStream_t s)
 {
-  const dim3 grid((unsigned)((r->ow + 63) / 64), (unsigned)((r->n_h + 3) / 4)), block(256);
+  const dim3 grid = grid_64x4(r->ow, r->n_h), block(256);
   const uint8_t* src = (const uint8_t*)r->src;
   const size_t lds = light_h_bytes(la);
   if (chw)
@@ -276,31 +188,11 @@ void launch_h(bool chw, const hm_resample_args* r, const hm_light_args* la, hipS
 template <typename OutT>
 void launch_v(const hm_dest_plan* p, const hm_resample_args* r, const hm_light_args* la, uint8_t* dst, const Affine& a, hipStream_t s)
 {
-  const dim3 grid((unsigned)((r->ow + 63) / 64), (unsigned)((r->oh + 3) / 4)), block(256);
-  const size_t lds = light_v_bytes(la);
   const Light L = light_of(la);
-  const bool chw = p->layout == HM_DEV_LAYOUT_CHW;
-#define HM_LV_GO(CHW_, C_) \
-  hipLaunchKernelGGL((k_light_v<OutT, CHW_, C_>), grid, block, lds, s, (const float*)r->tmp, (long long)r->tmp_pitch, (long long)r->tmp_plane, r->ow, r->oh, \
-                     r->ay.first, r->ay.count, r->ay.weights, dst, (long long)p->row_pitch, (long long)p->plane_pitch, a, L)
-  if (chw) { if (p->channels == 3) HM_LV_GO(true, 3); else HM_LV_GO(true, 4); }
-  else { if (p->channels == 3) HM_LV_GO(false, 3); else HM_LV_GO(false, 4); }
-#undef HM_LV_GO
-}
-
-int check_args(const hm_dest_plan* p, const hm_light_args* la)
-{
-  if (!la->lin || (la->encode && !la->enc) || la->bits < 8 || la->bits > 12) return hm_fail(HM_ERR_INTERNAL, "k_light: tables of %d bits", la->bits);
-  if (la->enc_bits != la->bits && la->enc_bits != 8) return hm_fail(HM_ERR_INTERNAL, "k_light: codes of %d bits from tables of %d", la->enc_bits, la->bits);
-  if (la->src_bytes != (la->bits > 8 ? 2 : 1)) return hm_fail(HM_ERR_INTERNAL, "k_light: %d-byte samples of %d bits", la->src_bytes, la->bits);
-  if (p->channels != 3 && p->channels != 4) return hm_fail(HM_ERR_INTERNAL, "k_light: %d channels", p->channels);
-  // (p is the plan of the target the destination is written as: under the 8-bit finish its samples are bytes, the source's are not)
-  if (p->sample_bytes != (la->enc_bits > 8 ? 2 : 1) || (p->sample_bytes != la->src_bytes && p->channels != 3))
-    return hm_fail(HM_ERR_INTERNAL, "k_light: a %d-byte target of %d channels from %d-byte samples, codes of %d bits", p->sample_bytes, p->channels, la->src_bytes, la->enc_bits);
-  const bool integer = p->dtype == HM_DEV_U8 || p->dtype == HM_DEV_U16;
-  if (integer && (!la->encode || p->dtype != (p->sample_bytes == 1 ? HM_DEV_U8 : HM_DEV_U16)))
-    return hm_fail(HM_ERR_INTERNAL, "k_light: integer dtype %d on %d-byte samples, %s", p->dtype, p->sample_bytes, la->encode ? "re-encoded" : "linear");
-  return HM_OK;
+  with_flags(p->layout == HM_DEV_LAYOUT_CHW, p->channels == 4, [&](auto chw, auto four) {
+    hipLaunchKernelGGL((k_light_v<OutT, chw.value, four.value ? 4 : 3>), grid_64x4(r->ow, r->oh), dim3(256), light_v_bytes(la), s, (const float*)r->tmp, (long long)r->tmp_pitch,
+                       (long long)r->tmp_plane, r->ow, r->oh, r->ay.first, r->ay.count, r->ay.weights, dst, (long long)p->row_pitch, (long long)p->plane_pitch, a, L);
+  });
 }
 
 } // namespace
@@ -330,45 +222,41 @@ extern "C" int hm_launch_light_tensor(const hm_dest_plan* p, const hm_light_args
                                       const float scale[4], const float bias[4], hipStream_t s)
 {
   if (w <= 0 || rows <= 0) return HM_OK;
-  const int rc = check_args(p, la);
+  const int rc = check_light_args("k_light", p, la);
   if (rc) return rc;
   const Affine a = affine_of(scale, bias);
   const uint8_t* in = (const uint8_t*)src;
   uint8_t* out = (uint8_t*)dst;
-  if (la->src_bytes == 1) return p->channels == 3 ? launch_tensor_dtype<1, 3>(p, la, in, src_stride, w, rows, out, a, s) : launch_tensor_dtype<1, 4>(p, la, in, src_stride, w, rows, out, a, s);
-  return p->channels == 3 ? launch_tensor_dtype<2, 3>(p, la, in, src_stride, w, rows, out, a, s) : launch_tensor_dtype<2, 4>(p, la, in, src_stride, w, rows, out, a, s);
+  const int found = with_flags(la->src_bytes == 2, p->channels == 4, [&](auto wide, auto four) {
+    return launch_tensor<wide.value ? 2 : 1, four.value ? 4 : 3>(p, la, in, src_stride, w, rows, out, a, s);
+  });
+  if (found == NO_KERNEL_INSTANCE) return hm_fail(HM_ERR_INTERNAL, "k_light_tensor: no kernel for dtype %d on %d-byte samples", p->dtype, la->src_bytes);
+  return found;
 }
 
 extern "C" int hm_launch_light_nearest(const hm_dest_plan* p, const hm_light_args* la, const void* src, int src_stride, int n_w, int n_h, int ow, int oh, void* dst,
                                        const float scale[4], const float bias[4], hipStream_t s)
 {
   if (ow <= 0 || oh <= 0) return HM_OK;
-  const int rc = check_args(p, la);
+  const int rc = check_light_args("k_light", p, la);
   if (rc) return rc;
   const Affine a = affine_of(scale, bias);
   const uint8_t* in = (const uint8_t*)src;
   uint8_t* out = (uint8_t*)dst;
-  const bool wide = la->src_bytes == 2;
-  // 16-bit elements from 16-bit samples only; bytes from either width (from 16-bit samples: the 8-bit finish); floats from either
-  const int found = with_dtype(p->dtype, [&](auto tag) -> int {
-    typedef typename decltype(tag)::type OutT;
-    if (wide) return launch_nearest<uint16_t, OutT>(p, la, in, src_stride, n_w, n_h, ow, oh, out, a, s);
-    if constexpr (!std::is_same<OutT, uint16_t>::value) return launch_nearest<uint8_t, OutT>(p, la, in, src_stride, n_w, n_h, ow, oh, out, a, s);
-    return NO_KERNEL_INSTANCE;
+  const int found = with_flags(la->src_bytes == 2, p->channels == 4, [&](auto wide, auto four) {
+    return launch_nearest<wide.value ? 2 : 1, four.value ? 4 : 3>(p, la, in, src_stride, n_w, n_h, ow, oh, out, a, s);
   });
   if (found == NO_KERNEL_INSTANCE) return hm_fail(HM_ERR_INTERNAL, "k_light_nearest: no kernel for dtype %d on %d-byte samples", p->dtype, la->src_bytes);
-  return hm_check_hip(hipGetLastError(), "k_light_nearest launch");
+  return found;
 }
 
 // the horizontal pass of a resampled view under the light step alone (the gain step's vertical pass is gain.hip's)
 extern "C" int hm_launch_light_h(const hm_dest_plan* p, const hm_light_args* la, const hm_resample_args* r, hipStream_t s)
 {
   if (r->ow <= 0 || r->oh <= 0 || r->n_w <= 0 || r->n_h <= 0) return HM_OK;
-  const int rc = check_args(p, la);
+  const int rc = check_light_args("k_light", p, la);
   if (rc) return rc;
-  const bool chw = p->layout == HM_DEV_LAYOUT_CHW;
-  if (r->sample_bytes == 1) { if (r->channels == 3) launch_h<1, 3>(chw, r, la, s); else launch_h<1, 4>(chw, r, la, s); }
-  else { if (r->channels == 3) launch_h<2, 3>(chw, r, la, s); else launch_h<2, 4>(chw, r, la, s); }
+  with_flags(r->sample_bytes == 2, r->channels == 4, [&](auto wide, auto four) { launch_h<wide.value ? 2 : 1, four.value ? 4 : 3>(p->layout == HM_DEV_LAYOUT_CHW, r, la, s); });
   return hm_check_hip(hipGetLastError(), "k_light_h launch");
 }
 

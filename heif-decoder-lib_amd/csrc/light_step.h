@@ -1,11 +1,15 @@
-// light_step.h — the per-pixel rules of the light step (hm_device_light) and of the tone step inside it, stated once (included by
-// light.hip and alpha.hip; HIP only; the element rules behind them are out_elem.h's):
-//   fill_tables  the step's tables from global memory into LDS, once per workgroup
+// light_step.h — the per-pixel rules of the light step (hm_device_light) and of the tone and OOTF steps inside it, stated once (included
+// by light.hip, alpha.hip and gain.hip; HIP only; the element rules behind them are out_elem.h's):
+//   light_layout where each of the step's tables sits in LDS (host and device: what a launch asks for is what a kernel lays out)
+//   fill_tables  tables from global memory into LDS, once per workgroup; fill_light: the step's own, by their layout
 //   encode_of    the re-encoding: a count of thresholds by binary search
 //   gamut        the 3 x 3 matrix on one pixel's linear light
 //   tone_map     the tone step on one pixel's linear light
 //   ootf_map     the OOTF step (hm_device_ootf) on one pixel's linear light, in front of the matrix
 //   colour_out   linear light of a colour channel to an element of the destination
+//   light_in     one pixel's colour samples to linear light
+//   light_out    one pixel's linear light to its three colour elements: OOTF step, matrix, tone step, colour_out
+// Behind them, on the host: light_of, the dynamic LDS of a launch, and the one check of hm_light_args against a destination plan.
 // Every product and sum is rounded on its own (-ffp-contract=off, __fmul_rn / __fadd_rn).
 #ifndef HM_LIGHT_STEP_H
 #define HM_LIGHT_STEP_H
@@ -19,16 +23,49 @@ struct Light { const float* lin; const float* enc; const float* tone; const floa
 constexpr int TONE_STEPS = HM_TONE_STEPS;
 constexpr int OOTF_STEPS = HM_OOTF_STEPS;
 
+// The step's tables lie in LDS one behind the other: lin[1 << bits] (with_lin: a vertical pass has none - its sums are of light already),
+// enc[1 << ebits] when re-encoding, thr and sg of the tone step, thr and sg of the OOTF step.  Offsets in floats; end: all of them.
+struct LightLayout { int enc, tone, ootf, end; };
+__host__ __device__ inline LightLayout light_layout(bool with_lin, int bits, int ebits, bool encode, bool tone, bool ootf)
+{
+  LightLayout o;
+  o.enc = with_lin ? 1 << bits : 0;
+  o.tone = o.enc + (encode ? 1 << ebits : 0);
+  o.ootf = o.tone + (tone ? 2 * TONE_STEPS : 0);
+  o.end = o.ootf + (ootf ? 2 * OOTF_STEPS : 0);
+  return o;
+}
+// ... as a kernel sees them: the base in LDS and which layout; a table's place is worked out where the table is used (scalars; a table
+// the step does not have is not looked at), as the kernels did before they shared this.  Taken up front as pointers, k_light_v waits
+// once more on its kernel arguments: 14.8 against 14.1 us (profiles/step_kernels_refactor.txt).
+struct LightTables {
+  const float* lds; bool with_lin;
+  __device__ __forceinline__ LightLayout at(const Light& L) const { return light_layout(with_lin, L.bits, L.ebits, L.encode, L.tone, L.ootf); }
+  __device__ __forceinline__ const float* lin() const { return lds; }
+  __device__ __forceinline__ const float* enc(const Light& L) const { return lds + at(L).enc; }
+  __device__ __forceinline__ const float* tone(const Light& L) const { return lds + at(L).tone; }
+  __device__ __forceinline__ const float* ootf(const Light& L) const { return lds + at(L).ootf; }
+};
+
 // a[na], b[nb], c[nc], d[nd] (each may be NULL: nothing is copied, its place stays) -> lds, one behind the other; every thread of the
 // workgroup comes here
-__device__ __forceinline__ void fill_tables(float* lds, const float* __restrict__ a, int na, const float* __restrict__ b, int nb, const float* __restrict__ c, int nc,
-                                            const float* __restrict__ d = nullptr, int nd = 0)
+__device__ __forceinline__ void fill_tables(float* lds, const float* __restrict__ a, int na, const float* __restrict__ b = nullptr, int nb = 0,
+                                            const float* __restrict__ c = nullptr, int nc = 0, const float* __restrict__ d = nullptr, int nd = 0)
 {
   if (a) for (int i = threadIdx.x; i < na; i += 256) lds[i] = a[i];
   if (b) for (int i = threadIdx.x; i < nb; i += 256) lds[na + i] = b[i];
   if (c) for (int i = threadIdx.x; i < nc; i += 256) lds[na + nb + i] = c[i];
   if (d) for (int i = threadIdx.x; i < nd; i += 256) lds[na + nb + nc + i] = d[i];
   __syncthreads();
+}
+
+// the step's tables into LDS by light_layout, every one or (no lin) a vertical pass's; every thread of the workgroup comes here
+__device__ __forceinline__ LightTables fill_light(float* lds, const Light& L, bool with_lin)
+{
+  const int ne = L.encode ? 1 << L.ebits : 0, nt = L.tone ? 2 * TONE_STEPS : 0;
+  if (with_lin) fill_tables(lds, L.lin, 1 << L.bits, L.enc, ne, L.tone, nt, L.ootf, 2 * OOTF_STEPS);
+  else if (L.encode || L.tone || L.ootf) fill_tables(lds, L.enc, ne, L.tone, nt, L.ootf, 2 * OOTF_STEPS); // (uniform: the barrier inside is met by every thread or by none)
+  return LightTables{lds, with_lin};
 }
 
 // |{c in 1 .. peak : enc[c] <= r}|: enc rises, so the count is the largest c whose threshold r has reached (0: none; a NaN: none)
@@ -77,14 +114,31 @@ __device__ __forceinline__ void ootf_map(const Light& L, const float* ol, float 
   const float g = ol[OOTF_STEPS + k];
   r[0] = __fmul_rn(r[0], g); r[1] = __fmul_rn(r[1], g); r[2] = __fmul_rn(r[2], g);
 }
-// where the OOTF tables sit behind enc (vl: enc, then thr and sg of the tone step, then those of the OOTF step)
-__device__ __forceinline__ const float* ootf_tables(const Light& L, const float* vl) { return vl + (L.encode ? 1 << L.ebits : 0) + (L.tone ? 2 * TONE_STEPS : 0); }
 
 // linear light r of a colour channel to an element of the destination; enc: the threshold table in LDS
 template <typename OutT> __device__ __forceinline__ OutT colour_out(const Light& L, const float* enc, float r, float sc, float bi)
 {
   if (L.encode) return moved<OutT>(encode_of(enc, L.ebits, r), sc, bi);
   return linear_out<OutT>(r, sc, bi);
+}
+
+// a pixel's colour samples to linear light: lin at the sample, clamped to the table
+template <typename Tables> __device__ __forceinline__ void light_in(const Light& L, const Tables& T, const unsigned v[3], float r[3])
+{
+  const unsigned peak = (1u << L.bits) - 1u;
+  r[0] = T.lin()[min(v[0], peak)]; r[1] = T.lin()[min(v[1], peak)]; r[2] = T.lin()[min(v[2], peak)];
+}
+
+// one pixel's linear light r (changed in place) to its three colour elements: what every kernel of the step does behind its lookups or
+// its sums, each part a wave-uniform branch on a kernel argument.  OOTF false: a kernel that never meets the OOTF step (the gain step's:
+// the host refuses the two together) does not carry its search.  Tables: LightTables, or whatever else answers enc(L), tone(L) and ootf(L).
+template <bool OOTF = true, typename Tables, typename OutT> __device__ __forceinline__ void light_out(const Light& L, const Tables& T, float r[3], const Affine& a, OutT o[3])
+{
+  if (OOTF && L.ootf) ootf_map(L, T.ootf(L), r);
+  gamut(L, r);
+  if (L.tone) tone_map(T.tone(L), r);
+#pragma unroll
+  for (int c = 0; c < 3; c++) o[c] = colour_out<OutT>(L, T.enc(L), r[c], a.scale[c], a.bias[c]);
 }
 
 // ---- host ----
@@ -98,10 +152,28 @@ static inline Light light_of(const hm_light_args* la)
 }
 // the dynamic LDS of a launch: the pointwise and nearest kernels hold lin, enc, the tone and the OOTF tables, a horizontal pass lin, a
 // vertical pass enc, the tone and the OOTF tables - at most 16 + 16 + 16 + 8 = 56 KB
-static inline size_t light_tone_bytes(const hm_light_args* la) { return la->tone ? 2 * (size_t)TONE_STEPS * sizeof(float) : 0; }
-static inline size_t light_ootf_bytes(const hm_light_args* la) { return la->ootf ? 2 * (size_t)OOTF_STEPS * sizeof(float) : 0; }
+static inline size_t light_layout_bytes(const hm_light_args* la, bool with_lin)
+{
+  return (size_t)light_layout(with_lin, la->bits, la->enc_bits, la->encode != 0, la->tone != nullptr, la->ootf != nullptr).end * sizeof(float);
+}
 static inline size_t light_h_bytes(const hm_light_args* la) { return (size_t)4 << la->bits; }
-static inline size_t light_v_bytes(const hm_light_args* la) { return (la->encode ? (size_t)4 << la->enc_bits : 0) + light_tone_bytes(la) + light_ootf_bytes(la); }
-static inline size_t light_tables_bytes(const hm_light_args* la) { return light_h_bytes(la) + light_v_bytes(la); }
+static inline size_t light_v_bytes(const hm_light_args* la) { return light_layout_bytes(la, false); }
+static inline size_t light_tables_bytes(const hm_light_args* la) { return light_layout_bytes(la, true); }
+
+// hm_light_args against p, the plan of the target the destination is written as (under the 8-bit finish its samples are bytes, the
+// source's are not); k: the kernel family, for the message
+static inline int check_light_args(const char* k, const hm_dest_plan* p, const hm_light_args* la)
+{
+  if (!la->lin || (la->encode && !la->enc) || la->bits < 8 || la->bits > 12) return hm_fail(HM_ERR_INTERNAL, "%s: tables of %d bits", k, la->bits);
+  if (la->enc_bits != la->bits && la->enc_bits != 8) return hm_fail(HM_ERR_INTERNAL, "%s: codes of %d bits from tables of %d", k, la->enc_bits, la->bits);
+  if (la->src_bytes != (la->bits > 8 ? 2 : 1)) return hm_fail(HM_ERR_INTERNAL, "%s: %d-byte samples of %d bits", k, la->src_bytes, la->bits);
+  if (p->channels != 3 && p->channels != 4) return hm_fail(HM_ERR_INTERNAL, "%s: %d channels", k, p->channels);
+  if (p->sample_bytes != (la->enc_bits > 8 ? 2 : 1) || (p->sample_bytes != la->src_bytes && p->channels != 3))
+    return hm_fail(HM_ERR_INTERNAL, "%s: a %d-byte target of %d channels from %d-byte samples, codes of %d bits", k, p->sample_bytes, p->channels, la->src_bytes, la->enc_bits);
+  const bool integer = p->dtype == HM_DEV_U8 || p->dtype == HM_DEV_U16;
+  if (integer && (!la->encode || p->dtype != (p->sample_bytes == 1 ? HM_DEV_U8 : HM_DEV_U16)))
+    return hm_fail(HM_ERR_INTERNAL, "%s: integer dtype %d on %d-byte samples, %s", k, p->dtype, p->sample_bytes, la->encode ? "re-encoded" : "linear");
+  return HM_OK;
+}
 
 #endif

@@ -1,5 +1,5 @@
-// out_elem.h — the element rules of every device output, stated once (included by tensor.hip, planes.hip, resample.hip,
-// planes_view.hip and light.hip; HIP only).  The tests restate these rules in float32 on the host and compare bit for bit, so
+// out_elem.h — the element rules of every device output, stated once (included by tensor.hip, planes.hip, resample.hip and
+// planes_view.hip, by out_rows.h, and through light_step.h by light.hip, alpha.hip and gain.hip; HIP only).  The tests restate these rules in float32 on the host and compare bit for bit, so
 // every product and sum here is rounded on its own: -ffp-contract=off and explicit __fmul_rn / __fadd_rn, never a fused multiply-add.
 //   linear_out    a float value through the destination's affine: r * scale + bias in two rounded steps, for f16 narrowed once more
 //   moved         a sample that is stored, not computed: the integer itself (u16: << shift, msb_aligned planes), or linear_out of it

@@ -472,3 +472,18 @@ def test_refusals_leave_every_byte_unwritten(capi, L, files):
     d, g, _, _ = base.make_dest(capi, L, RGB, CHW, F32, 64, 64, ONE, ZERO, 0, 0)
     rc, msg, _ = gain_to_device(capi, L, data, item, None, lt, None, gain_of(capi, from_file, 1.0), d)
     assert rc == 0 and not (g.host()[g.start:g.start + 64] == 0xA5).all(), msg
+
+
+def test_gain_kernels_use_no_scratch(pkg):
+    """every instance of the gain kernels as the loaded code object has it (test hook hm_debug_kernel_regs, code 12): no scratch"""
+    pkg.lib()  # (torch's HIP runtime first)
+    T = C.CDLL(pkg.capi.TEST_LIB_PATH)
+    T.hm_debug_kernel_regs.argtypes = [C.c_int, C.c_int, C.c_int, C.c_int, C.POINTER(C.c_int * 2)]
+    out = (C.c_int * 2)()
+    n = 0
+    while T.hm_debug_kernel_regs(12, n, 0, 0, C.byref(out)) == 0:
+        assert out[1] == 0 and 0 < out[0] <= 128, (n, out[0], out[1])
+        n += 1
+    # 26 pointwise (sample width x dtype x channels x store width, the layout being a kernel argument, plus the two of the 8-bit finish),
+    # 13 nearest, 3 of the map's two passes, 16 vertical
+    assert n == 58
