@@ -249,6 +249,40 @@ class PipelineResult(C.Structure):
     _fields_ = [("tag", C.c_uint64), ("status", C.c_int32), ("image", Decoded), ("handle", C.c_void_p)]
 
 
+# ---- the device entries of the item, frames and pipeline families: one table behind their argtypes (bind_image) and behind the choice of
+#      the entry a request goes through (entry_of; decode.py) ----
+STEP_TYPES = {"view": DeviceView, "light": DeviceLight, "tone": DeviceTone, "alpha": DeviceAlpha, "gain": DeviceGain, "ootf": DeviceOotf}
+# the kinds, in the precedence a request picks its entry by: the suffix of the entry's name, the step that picks it, its step arguments in order
+ENTRY_KINDS = (("_gain", "gain", ("view", "light", "tone", "gain")),
+               ("_ootf", "ootf", ("view", "light", "ootf", "tone", "alpha")),
+               ("_alpha", "alpha", ("view", "light", "tone", "alpha")),
+               ("_tone", "tone", ("view", "light", "tone")),
+               ("_light", "light", ("view", "light")),
+               ("_view", "view", ("view",)),
+               ("", None, ()))
+PLANES_KINDS = (("_planes_view", "view", ("view",)), ("_planes", None, ()))
+_FRAMES_TAIL = [C.POINTER(Decoded), C.POINTER(C.c_int32)]
+# family -> argtypes before the steps, behind them (interleaved, planar), the kinds it lacks, the steps none of its entries takes.
+# The last kind a family has is the entry of a request that picks none: the frames family has no plain entry, its _view entry takes a
+# null view.
+ENTRY_FAMILIES = {
+    "hm_decode_item_to_device": ([C.c_void_p, C.c_uint32, C.POINTER(DecodeParams)], [C.POINTER(DeviceDest), C.POINTER(Decoded)],
+                                 [C.POINTER(DevicePlanes), C.POINTER(Decoded)], (), ()),
+    "hm_decode_frames_to_device": ([C.c_void_p, C.POINTER(C.c_uint32), C.c_int32, C.POINTER(DecodeParams)], [C.POINTER(DeviceDest)] + _FRAMES_TAIL,
+                                   [C.POINTER(DevicePlanes)] + _FRAMES_TAIL, ("_gain", "_alpha", ""), ("alpha", "gain")),
+    "hm_pipeline_submit_to_device": ([C.c_void_p, C.c_char_p, C.c_size_t, C.c_uint32, C.c_uint64], [C.POINTER(DeviceDest)], [C.POINTER(DevicePlanes)], (), ()),
+}
+
+
+def entry_of(family, given, planes=False):
+    """(name of the entry of `family` that a request holding the steps `given` - names of STEP_TYPES - goes through, the names of that
+    entry's step arguments in order); planes: the family's entries for planar destinations"""
+    _, _, _, lacks, no_steps = ENTRY_FAMILIES[family]
+    kinds = [k for k in (PLANES_KINDS if planes else ENTRY_KINDS) if k[0] not in lacks or planes]
+    suffix, _, steps = next((k for k in kinds if k[1] in given), kinds[-1])
+    return family + suffix, [s for s in steps if s not in no_steps]
+
+
 _image_lib = None
 
 
@@ -293,66 +327,39 @@ def bind_image(L):
     L.hm_decoded_free.restype = None
     L.hm_device_dest_bytes.argtypes = [C.c_int, C.c_int, C.c_int, C.POINTER(DeviceDest)]
     L.hm_device_dest_bytes.restype = C.c_int64
+    for family, (head, tail, planes_tail, lacks, no_steps) in ENTRY_FAMILIES.items():
+        for kinds, behind in ((ENTRY_KINDS, tail), (PLANES_KINDS, planes_tail)):
+            for suffix, _, steps in kinds:
+                if suffix not in lacks:  # (every other name must be exported: a missing one fails here, by name)
+                    getattr(L, family + suffix).argtypes = head + [C.POINTER(STEP_TYPES[s]) for s in steps if s not in no_steps] + behind
     L.hm_to_tensor.argtypes = [C.c_int, C.c_int, C.c_int, C.c_void_p, C.c_int, C.POINTER(DeviceDest), C.c_void_p]
-    L.hm_decode_item_to_device.argtypes = [C.c_void_p, C.c_uint32, C.POINTER(DecodeParams), C.POINTER(DeviceDest), C.POINTER(Decoded)]
     L.hm_decode_sequence_to_device.argtypes = [C.c_void_p, C.c_uint32, C.c_int32, C.POINTER(DecodeParams), C.POINTER(DeviceDest),
                                                C.POINTER(Decoded), C.POINTER(C.c_int32)]
-    L.hm_decode_frames_to_device_view.argtypes = [C.c_void_p, C.POINTER(C.c_uint32), C.c_int32, C.POINTER(DecodeParams), C.POINTER(DeviceView),
-                                                  C.POINTER(DeviceDest), C.POINTER(Decoded), C.POINTER(C.c_int32)]
     L.hm_pipeline_create.argtypes = [C.POINTER(PipelineConfig), C.POINTER(C.c_void_p)]
     L.hm_pipeline_destroy.argtypes = [C.c_void_p]
     L.hm_pipeline_destroy.restype = None
     L.hm_pipeline_submit.argtypes = [C.c_void_p, C.c_char_p, C.c_size_t, C.c_uint32, C.c_uint64]
-    L.hm_pipeline_submit_to_device.argtypes = [C.c_void_p, C.c_char_p, C.c_size_t, C.c_uint32, C.c_uint64, C.POINTER(DeviceDest)]
-    L.hm_decode_item_to_device_view.argtypes = [C.c_void_p, C.c_uint32, C.POINTER(DecodeParams), C.POINTER(DeviceView), C.POINTER(DeviceDest), C.POINTER(Decoded)]
-    L.hm_pipeline_submit_to_device_view.argtypes = [C.c_void_p, C.c_char_p, C.c_size_t, C.c_uint32, C.c_uint64, C.POINTER(DeviceView), C.POINTER(DeviceDest)]
     L.hm_resample_to_tensor.argtypes = [C.c_int, C.c_int, C.c_int, C.c_void_p, C.c_int, C.POINTER(DeviceView), C.POINTER(DeviceDest), C.c_void_p]
     L.hm_plan_view.argtypes = [C.c_void_p, C.c_uint32, C.POINTER(DecodeParams), C.POINTER(DeviceView), C.POINTER(C.c_int32 * 4)]
     L.hm_view_filter_taps.argtypes = [C.c_int, C.c_int, C.c_int, C.c_int, C.POINTER(C.c_int32), C.POINTER(C.c_float), C.c_int]
-    L.hm_decode_item_to_device_light.argtypes = [C.c_void_p, C.c_uint32, C.POINTER(DecodeParams), C.POINTER(DeviceView), C.POINTER(DeviceLight), C.POINTER(DeviceDest),
-                                                 C.POINTER(Decoded)]
-    L.hm_decode_frames_to_device_light.argtypes = [C.c_void_p, C.POINTER(C.c_uint32), C.c_int32, C.POINTER(DecodeParams), C.POINTER(DeviceView), C.POINTER(DeviceLight),
-                                                   C.POINTER(DeviceDest), C.POINTER(Decoded), C.POINTER(C.c_int32)]
-    L.hm_pipeline_submit_to_device_light.argtypes = [C.c_void_p, C.c_char_p, C.c_size_t, C.c_uint32, C.c_uint64, C.POINTER(DeviceView), C.POINTER(DeviceLight),
-                                                     C.POINTER(DeviceDest)]
     L.hm_light_to_tensor.argtypes = [C.c_int, C.c_int, C.c_int, C.c_int, C.c_void_p, C.c_int, C.POINTER(DeviceView), C.POINTER(DeviceLight), C.POINTER(DeviceDest),
                                      C.c_void_p]
     L.hm_light_table.argtypes = [C.c_int, C.c_int, C.c_float, C.c_int, C.POINTER(C.c_float)]
     L.hm_light_matrix.argtypes = [C.c_int, C.c_int, C.POINTER(C.c_float * 9)]
-    L.hm_decode_item_to_device_tone.argtypes = [C.c_void_p, C.c_uint32, C.POINTER(DecodeParams), C.POINTER(DeviceView), C.POINTER(DeviceLight), C.POINTER(DeviceTone),
-                                                C.POINTER(DeviceDest), C.POINTER(Decoded)]
-    L.hm_decode_frames_to_device_tone.argtypes = [C.c_void_p, C.POINTER(C.c_uint32), C.c_int32, C.POINTER(DecodeParams), C.POINTER(DeviceView), C.POINTER(DeviceLight),
-                                                  C.POINTER(DeviceTone), C.POINTER(DeviceDest), C.POINTER(Decoded), C.POINTER(C.c_int32)]
-    L.hm_pipeline_submit_to_device_tone.argtypes = [C.c_void_p, C.c_char_p, C.c_size_t, C.c_uint32, C.c_uint64, C.POINTER(DeviceView), C.POINTER(DeviceLight),
-                                                    C.POINTER(DeviceTone), C.POINTER(DeviceDest)]
     L.hm_tone_to_tensor.argtypes = [C.c_int, C.c_int, C.c_int, C.c_int, C.c_void_p, C.c_int, C.POINTER(DeviceView), C.POINTER(DeviceLight), C.POINTER(DeviceTone),
                                     C.POINTER(DeviceDest), C.c_void_p]
     L.hm_tone_table.argtypes = [C.POINTER(DeviceTone), C.c_float, C.c_int, C.POINTER(C.c_float)]
     L.hm_file_item_light_levels.argtypes = [C.c_void_p, C.c_uint32, C.POINTER(LightLevels)]
     L.hm_alpha_dest_format.argtypes = [C.c_int, C.POINTER(DeviceAlpha), C.POINTER(DeviceTone)]
-    L.hm_decode_item_to_device_alpha.argtypes = [C.c_void_p, C.c_uint32, C.POINTER(DecodeParams), C.POINTER(DeviceView), C.POINTER(DeviceLight), C.POINTER(DeviceTone),
-                                                 C.POINTER(DeviceAlpha), C.POINTER(DeviceDest), C.POINTER(Decoded)]
-    L.hm_pipeline_submit_to_device_alpha.argtypes = [C.c_void_p, C.c_char_p, C.c_size_t, C.c_uint32, C.c_uint64, C.POINTER(DeviceView), C.POINTER(DeviceLight),
-                                                     C.POINTER(DeviceTone), C.POINTER(DeviceAlpha), C.POINTER(DeviceDest)]
     L.hm_alpha_to_tensor.argtypes = [C.c_int, C.c_int, C.c_int, C.c_int, C.c_void_p, C.c_int, C.POINTER(DeviceView), C.POINTER(DeviceLight), C.POINTER(DeviceTone),
                                      C.POINTER(DeviceAlpha), C.POINTER(DeviceDest), C.c_void_p]
     L.hm_file_gain_map_info.argtypes = [C.c_void_p, C.c_uint32, C.POINTER(GainMapInfo)]
     L.hm_file_gain_map_of.argtypes = [C.c_void_p, C.c_uint32]
     L.hm_file_gain_map_of.restype = C.c_uint32
     L.hm_file_item_aux_type.argtypes = [C.c_void_p, C.c_uint32, C.c_char_p, C.c_int]
-    L.hm_decode_item_to_device_gain.argtypes = [C.c_void_p, C.c_uint32, C.POINTER(DecodeParams), C.POINTER(DeviceView), C.POINTER(DeviceLight), C.POINTER(DeviceTone),
-                                                C.POINTER(DeviceGain), C.POINTER(DeviceDest), C.POINTER(Decoded)]
-    L.hm_pipeline_submit_to_device_gain.argtypes = [C.c_void_p, C.c_char_p, C.c_size_t, C.c_uint32, C.c_uint64, C.POINTER(DeviceView), C.POINTER(DeviceLight),
-                                                    C.POINTER(DeviceTone), C.POINTER(DeviceGain), C.POINTER(DeviceDest)]
     L.hm_gain_to_tensor.argtypes = [C.c_int, C.c_int, C.c_int, C.c_int, C.c_void_p, C.c_int, C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_int, C.POINTER(DeviceView),
                                     C.POINTER(DeviceLight), C.POINTER(DeviceTone), C.POINTER(DeviceGain), C.POINTER(DeviceDest), C.c_void_p]
     L.hm_gain_table.argtypes = [C.POINTER(GainParams), C.c_float, C.c_int, C.c_int, C.POINTER(C.c_float)]
-    L.hm_decode_item_to_device_ootf.argtypes = [C.c_void_p, C.c_uint32, C.POINTER(DecodeParams), C.POINTER(DeviceView), C.POINTER(DeviceLight), C.POINTER(DeviceOotf),
-                                                C.POINTER(DeviceTone), C.POINTER(DeviceAlpha), C.POINTER(DeviceDest), C.POINTER(Decoded)]
-    L.hm_decode_frames_to_device_ootf.argtypes = [C.c_void_p, C.POINTER(C.c_uint32), C.c_int32, C.POINTER(DecodeParams), C.POINTER(DeviceView), C.POINTER(DeviceLight),
-                                                  C.POINTER(DeviceOotf), C.POINTER(DeviceTone), C.POINTER(DeviceDest), C.POINTER(Decoded), C.POINTER(C.c_int32)]
-    L.hm_pipeline_submit_to_device_ootf.argtypes = [C.c_void_p, C.c_char_p, C.c_size_t, C.c_uint32, C.c_uint64, C.POINTER(DeviceView), C.POINTER(DeviceLight),
-                                                    C.POINTER(DeviceOotf), C.POINTER(DeviceTone), C.POINTER(DeviceAlpha), C.POINTER(DeviceDest)]
     L.hm_ootf_to_tensor.argtypes = [C.c_int, C.c_int, C.c_int, C.c_int, C.c_void_p, C.c_int, C.POINTER(DeviceView), C.POINTER(DeviceLight), C.POINTER(DeviceOotf),
                                     C.POINTER(DeviceTone), C.POINTER(DeviceAlpha), C.POINTER(DeviceDest), C.c_void_p]
     L.hm_ootf_gamma.argtypes = [C.POINTER(DeviceOotf), C.POINTER(C.c_double)]
@@ -362,17 +369,7 @@ def bind_image(L):
     L.hm_device_planes_bytes.restype = C.c_int64
     L.hm_planes_to_tensor.argtypes = [C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, C.POINTER(C.c_void_p * 4), C.POINTER(C.c_int32 * 4), C.POINTER(DevicePlanes),
                                       C.c_void_p]
-    L.hm_decode_item_to_device_planes.argtypes = [C.c_void_p, C.c_uint32, C.POINTER(DecodeParams), C.POINTER(DevicePlanes), C.POINTER(Decoded)]
-    L.hm_decode_frames_to_device_planes.argtypes = [C.c_void_p, C.POINTER(C.c_uint32), C.c_int32, C.POINTER(DecodeParams), C.POINTER(DevicePlanes),
-                                                    C.POINTER(Decoded), C.POINTER(C.c_int32)]
-    L.hm_pipeline_submit_to_device_planes.argtypes = [C.c_void_p, C.c_char_p, C.c_size_t, C.c_uint32, C.c_uint64, C.POINTER(DevicePlanes)]
     L.hm_planes_view_geometry.argtypes = [C.c_int, C.c_int, C.c_int, C.POINTER(DeviceView), C.POINTER(C.c_int32 * 4 * 4), C.POINTER(C.c_int32 * 2 * 4)]
-    L.hm_decode_item_to_device_planes_view.argtypes = [C.c_void_p, C.c_uint32, C.POINTER(DecodeParams), C.POINTER(DeviceView), C.POINTER(DevicePlanes),
-                                                       C.POINTER(Decoded)]
-    L.hm_decode_frames_to_device_planes_view.argtypes = [C.c_void_p, C.POINTER(C.c_uint32), C.c_int32, C.POINTER(DecodeParams), C.POINTER(DeviceView),
-                                                         C.POINTER(DevicePlanes), C.POINTER(Decoded), C.POINTER(C.c_int32)]
-    L.hm_pipeline_submit_to_device_planes_view.argtypes = [C.c_void_p, C.c_char_p, C.c_size_t, C.c_uint32, C.c_uint64, C.POINTER(DeviceView),
-                                                           C.POINTER(DevicePlanes)]
     L.hm_resample_planes_to_tensor.argtypes = [C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, C.POINTER(C.c_void_p * 4), C.POINTER(C.c_int32 * 4),
                                                C.POINTER(DeviceView), C.POINTER(DevicePlanes), C.c_void_p]
     L.hm_plan_planes_view.argtypes = [C.c_void_p, C.c_uint32, C.POINTER(DecodeParams), C.POINTER(DeviceView), C.POINTER(C.c_int32 * 4)]

@@ -15,6 +15,7 @@
 
 #include "hm_colour_plan.h"
 #include "hm_devdest.h"
+#include "hm_entry_steps.h"
 #include "hm_planes_view.h"
 #include "hm_view_batch.h"
 
@@ -1333,13 +1334,15 @@ int hm_out_write(const hm_device_dest* d, const hm_out_plan* p, const void* src,
 
 // ---- the stand-alone entries: pixels that are in device memory already, through the same plan and writer ---------------------------
 
+// kind: the entry (hm_entry_steps.h) - this family leaves a null light step to hm_out_check_static, behind the alpha step's own refusals
 // size_prefix: of the message about a wrong width or height (hm_to_tensor's speaks of the destination)
 // map, map_w, map_h, map_bits: the gain map of a gain step (hm_gain_to_tensor), else NULL and 0
-static int out_to_tensor(int out_format, int bits, int w, int h, const void* src, int src_stride, const hm_out_steps& st, const hm_device_dest* dest, void* stream,
+static int out_to_tensor(int kind, int out_format, int bits, int w, int h, const void* src, int src_stride, const hm_out_steps& st, const hm_device_dest* dest, void* stream,
                          const char* size_prefix = "", const hm_out_map* map = nullptr, int map_w = 0, int map_h = 0, int map_bits = 0)
 {
-  int rc = hm_out_check_static(out_format, dest, &st, 1);
-  if (rc || (rc = check_image_size(size_prefix, w, h))) return rc;
+  if (!src || !dest) return hm_fail(HM_ERR_INVALID_ARG, "null argument");
+  int rc = hm_entry_steps(kind, st, false, /*light_judged_later=*/true);
+  if (rc || (rc = hm_out_check_static(out_format, dest, &st, 1)) || (rc = check_image_size(size_prefix, w, h))) return rc;
   if (map && (rc = check_image_size("gain map: ", map_w, map_h))) return rc;
   const hm_out_image img = {w, h, bits, st.light ? st.light->from_transfer : 0, st.light ? st.light->from_primaries : 0, map_w, map_h, map_bits};
   hm_out_plan p;
@@ -1361,52 +1364,43 @@ int hm_gain_to_tensor(int out_format, int bits, int src_w, int src_h, const void
                       int map_bits, const hm_device_view* view, const hm_device_light* light, const hm_device_tone* tone, const hm_device_gain* gain,
                       const hm_device_dest* dest, void* stream)
 {
-  if (!d_src || !d_map || !dest || !gain) return hm_fail(HM_ERR_INVALID_ARG, "null argument");
+  if (!d_map) return hm_fail(HM_ERR_INVALID_ARG, "null argument");
   const hm_out_map map = {d_map, map_stride};
-  return out_to_tensor(out_format, bits, src_w, src_h, d_src, src_stride, hm_out_steps{view, light, tone, nullptr, gain}, dest, stream, "", &map, map_w, map_h, map_bits);
+  return out_to_tensor(HM_ENTRY_GAIN, out_format, bits, src_w, src_h, d_src, src_stride, {view, light, tone, nullptr, gain}, dest, stream, "", &map, map_w, map_h, map_bits);
 }
 
 int hm_to_tensor(int out_format, int width, int height, const void* d_src, int src_stride, const hm_device_dest* dest, void* stream)
 {
-  if (!d_src || !dest) return hm_fail(HM_ERR_INVALID_ARG, "null argument");
-  return out_to_tensor(out_format, 0, width, height, d_src, src_stride, hm_out_steps{}, dest, stream, "device destination: ");
+  return out_to_tensor(HM_ENTRY_DEST, out_format, 0, width, height, d_src, src_stride, {}, dest, stream, "device destination: ");
 }
 
 int hm_resample_to_tensor(int out_format, int src_w, int src_h, const void* d_src, int src_stride, const hm_device_view* view, const hm_device_dest* dest, void* stream)
 {
-  if (!d_src || !dest || !view) return hm_fail(HM_ERR_INVALID_ARG, "null argument");
-  return out_to_tensor(out_format, 0, src_w, src_h, d_src, src_stride, hm_out_steps{view, nullptr, nullptr, nullptr}, dest, stream);
+  return out_to_tensor(HM_ENTRY_VIEW, out_format, 0, src_w, src_h, d_src, src_stride, {view}, dest, stream);
 }
 
 int hm_light_to_tensor(int out_format, int bits, int src_w, int src_h, const void* d_src, int src_stride, const hm_device_view* view, const hm_device_light* light,
                        const hm_device_dest* dest, void* stream)
 {
-  if (!d_src || !dest || !light) return hm_fail(HM_ERR_INVALID_ARG, "null argument");
-  return out_to_tensor(out_format, bits, src_w, src_h, d_src, src_stride, hm_out_steps{view, light, nullptr, nullptr}, dest, stream);
+  return out_to_tensor(HM_ENTRY_LIGHT, out_format, bits, src_w, src_h, d_src, src_stride, {view, light}, dest, stream);
 }
 
 int hm_tone_to_tensor(int out_format, int bits, int src_w, int src_h, const void* d_src, int src_stride, const hm_device_view* view, const hm_device_light* light,
                       const hm_device_tone* tone, const hm_device_dest* dest, void* stream)
 {
-  if (!d_src || !dest || !tone) return hm_fail(HM_ERR_INVALID_ARG, "null argument");
-  return out_to_tensor(out_format, bits, src_w, src_h, d_src, src_stride, hm_out_steps{view, light, tone, nullptr}, dest, stream);
+  return out_to_tensor(HM_ENTRY_TONE, out_format, bits, src_w, src_h, d_src, src_stride, {view, light, tone}, dest, stream);
 }
 
 int hm_alpha_to_tensor(int out_format, int bits, int src_w, int src_h, const void* d_src, int src_stride, const hm_device_view* view, const hm_device_light* light,
                        const hm_device_tone* tone, const hm_device_alpha* alpha, const hm_device_dest* dest, void* stream)
 {
-  if (!d_src || !dest || !alpha) return hm_fail(HM_ERR_INVALID_ARG, "null argument");
-  return out_to_tensor(out_format, bits, src_w, src_h, d_src, src_stride, hm_out_steps{view, light, tone, alpha}, dest, stream);
+  return out_to_tensor(HM_ENTRY_ALPHA, out_format, bits, src_w, src_h, d_src, src_stride, {view, light, tone, alpha}, dest, stream);
 }
 
 int hm_ootf_to_tensor(int out_format, int bits, int src_w, int src_h, const void* d_src, int src_stride, const hm_device_view* view, const hm_device_light* light,
                       const hm_device_ootf* ootf, const hm_device_tone* tone, const hm_device_alpha* alpha, const hm_device_dest* dest, void* stream)
 {
-  if (!ootf) // the same call without the step
-    return alpha ? hm_alpha_to_tensor(out_format, bits, src_w, src_h, d_src, src_stride, view, light, tone, alpha, dest, stream)
-                 : hm_tone_to_tensor(out_format, bits, src_w, src_h, d_src, src_stride, view, light, tone, dest, stream);
-  if (!d_src || !dest) return hm_fail(HM_ERR_INVALID_ARG, "null argument");
-  return out_to_tensor(out_format, bits, src_w, src_h, d_src, src_stride, hm_out_steps{view, light, tone, alpha, nullptr, ootf}, dest, stream);
+  return out_to_tensor(HM_ENTRY_OOTF, out_format, bits, src_w, src_h, d_src, src_stride, {view, light, tone, alpha, nullptr, ootf}, dest, stream);
 }
 
 // ---- planar views: every plane an image of its own ------------------------------------------------------------------------------

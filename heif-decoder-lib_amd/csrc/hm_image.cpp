@@ -1187,7 +1187,9 @@ static int check_planes_params(const hm_decode_params* params, const hm_device_p
   return HM_OK;
 }
 
-int check_target_request(const hm_file* f, uint32_t id, const hm_decode_params* params, const OutputTarget& t)
+// ---- the three phases of check_target_request; a sequence (decode_sequence) loops each over its frames ----
+// the request alone.  frame: of a sequence (its null-ptr message names the frame), else -1
+static int check_request_alone(const hm_decode_params* params, const OutputTarget& t, int frame = -1)
 {
   int rc = target_check_shape(t);
   if (rc) return rc;
@@ -1195,16 +1197,42 @@ int check_target_request(const hm_file* f, uint32_t id, const hm_decode_params* 
     if (params->ext_dst) return hm_fail(HM_ERR_INVALID_ARG, "params->ext_dst must be NULL with a device destination");
     const hm_out_steps st = t.steps();
     if ((rc = hm_out_check_static(params->out_format, t.dest, &st, 0))) return rc;
-    if (!t.dest->ptr) return hm_fail(HM_ERR_INVALID_ARG, "device destination: null ptr");
+    if (!t.dest->ptr)
+      return frame < 0 ? hm_fail(HM_ERR_INVALID_ARG, "device destination: null ptr")
+                       : hm_fail(HM_ERR_INVALID_ARG, "device destination of frame %d: null ptr", frame);
   }
-  if (t.planes && (rc = check_planes_params(params, t.planes))) return rc;
+  return t.planes ? check_planes_params(params, t.planes) : (int)HM_OK;
+}
+
+// the target against what the file declares for `id`, kept in `info` for the pointers.  A file that fails here, or declares nothing usable
+// for planes, is "size unknown" (info.width 0): such an item fails the decode with its own message.
+// alpha_bits: -1, the decode's to say whether there is an alpha plane and of which depth; 0: none (the frames of a sequence)
+// (params->ignore_transformations picks the coded size for a frame of a sequence too, where the sequence's own loops took
+//  info.width: a frame carries no transformations, the two sizes are one)
+static int check_request_declared(const hm_file* f, uint32_t id, const hm_decode_params* params, const OutputTarget& t, int alpha_bits,
+                                  hm_image_info& info)
+{
+  const bool usable = hm_file_image_info(f, id, &info) == HM_OK &&
+                      (!t.planes || (info.bit_depth >= 8 && info.bit_depth <= 16 && info.chroma >= 0 && info.chroma <= 3));
+  if (!usable) info.width = 0;
+  else if (params->ignore_transformations) { info.width = info.coded_width; info.height = info.coded_height; }
+  return target_fits(params, t, info.width, info.height, info.chroma, info.bit_depth, alpha_bits, nullptr, false);
+}
+
+// a device and the pointers: a destination's needs no size; the planes' are judged against the declared result, which target_fits
+// resolves once more for it (view, planes, len: as the sequence always did - for a single item the second pass is new, and repeats
+// what has just passed)
+static int check_request_pointers(const hm_decode_params* params, const OutputTarget& t, int alpha_bits, const hm_image_info& info)
+{
+  return target_fits(params, t, t.planes ? info.width : 0, info.height, info.chroma, info.bit_depth, alpha_bits, nullptr, true);
+}
+
+int check_target_request(const hm_file* f, uint32_t id, const hm_decode_params* params, const OutputTarget& t)
+{
   hm_image_info info{};
-  int w = 0, h = 0; // (a file that fails here, or declares nothing usable, fails the decode with its own message)
-  if (hm_file_image_info(f, id, &info) == HM_OK && (!t.planes || (info.bit_depth >= 8 && info.bit_depth <= 16 && info.chroma >= 0 && info.chroma <= 3))) {
-    w = params->ignore_transformations ? info.coded_width : info.width; h = params->ignore_transformations ? info.coded_height : info.height;
-  }
-  // (whether there is an alpha plane, and of which depth, is the decode's to say: -1)
-  return target_fits(params, t, w, h, info.chroma, info.bit_depth, -1, nullptr, true);
+  int rc;
+  if ((rc = check_request_alone(params, t)) || (rc = check_request_declared(f, id, params, t, -1, info))) return rc;
+  return check_request_pointers(params, t, -1, info);
 }
 
 hm_device_tone tone_for_item(const hm_file* f, uint32_t id, const hm_device_tone* tone)
@@ -1661,6 +1689,22 @@ int decode_derived(const hm_file* f, uint32_t id, const hm_decode_params* params
 
 } // namespace
 
+// A request resolved against the file: the one statement of that order (hm_image_job.h)
+int hm_img::resolve_request(const hm_file* f, uint32_t id, const hm_decode_params* params, const OutputTarget& asked, bool refuse_derived,
+                            ResolvedRequest& r)
+{
+  int rc;
+  r.t = asked;
+  r.id = id;
+  if (asked.tone && !asked.ootf) { r.tone = tone_for_item(f, id, asked.tone); r.t.tone = &r.tone; }
+  if (asked.gain) { // (item `id`'s properties: a 'tmap' item's clli describes the alternate rendition; the job decodes its base image)
+    if ((rc = hm_gain_for_item(f, id, params, asked.view, asked.gain, &r.id, &r.gain))) return rc;
+    r.t.gain = &r.gain;
+  }
+  if (refuse_derived && is_derived_item(f, r.id) && (rc = derived_refusal(f, r.id, params, asked.planes != nullptr))) return rc;
+  return check_target_request(f, r.id, params, r.t);
+}
+
 extern "C" {
 
 static int decode_grid_cut(const hm_file* f, uint32_t id, const hm_decode_params* params, const int32_t* devices, int n_devices, bool pipelined, hm_decoded* out, bool* applicable,
@@ -1674,63 +1718,51 @@ int hm_decode_item(const hm_file* f, uint32_t id, const hm_decode_params* params
 }
 
 // the device forms of hm_decode_item: what can be refused is refused before any work is queued - the destination is not written
-static int decode_item_to(const hm_file* f, uint32_t id, const hm_decode_params* params, const OutputTarget& target, hm_decoded* out)
+static int decode_item_to(int kind, const hm_file* f, uint32_t id, const hm_decode_params* params, const hm_out_steps& st,
+                          const hm_device_dest* dest, const hm_device_planes* planes, hm_decoded* out)
 {
-  std::memset(out, 0, sizeof(*out));
-  if (is_derived_item(f, id)) { const int drc = derived_refusal(f, id, params, target.planes != nullptr); if (drc) return drc; }
-  const int rc = check_target_request(f, id, params, target);
+  if (!f || !params || !out) return hm_fail(HM_ERR_INVALID_ARG, "null argument");
+  OutputTarget asked;
+  int rc = OutputTarget::of_entry(kind, st, dest, planes, asked);
   if (rc) return rc;
-  return decode_item(f, id, params, target, out);
+  std::memset(out, 0, sizeof(*out));
+  ResolvedRequest r;
+  if ((rc = resolve_request(f, id, params, asked, true, r))) return rc;
+  return decode_item(f, r.id, params, r.t, out);
 }
 
 int hm_decode_item_to_device(const hm_file* f, uint32_t id, const hm_decode_params* params, const hm_device_dest* dest, hm_decoded* out)
 {
-  if (!f || !params || !dest || !out) return hm_fail(HM_ERR_INVALID_ARG, "null argument");
-  return decode_item_to(f, id, params, OutputTarget::to_dest(dest), out);
+  return decode_item_to(HM_ENTRY_DEST, f, id, params, {}, dest, nullptr, out);
 }
 
 int hm_decode_item_to_device_view(const hm_file* f, uint32_t id, const hm_decode_params* params, const hm_device_view* view, const hm_device_dest* dest, hm_decoded* out)
 {
-  if (!f || !params || !view || !dest || !out) return hm_fail(HM_ERR_INVALID_ARG, "null argument");
-  return decode_item_to(f, id, params, OutputTarget::to_dest(dest, view), out);
+  return decode_item_to(HM_ENTRY_VIEW, f, id, params, {view}, dest, nullptr, out);
 }
 
 int hm_decode_item_to_device_light(const hm_file* f, uint32_t id, const hm_decode_params* params, const hm_device_view* view, const hm_device_light* light,
                                    const hm_device_dest* dest, hm_decoded* out)
 {
-  if (!f || !params || !light || !dest || !out) return hm_fail(HM_ERR_INVALID_ARG, "null argument");
-  return decode_item_to(f, id, params, OutputTarget::to_dest(dest, view, light), out);
+  return decode_item_to(HM_ENTRY_LIGHT, f, id, params, {view, light}, dest, nullptr, out);
 }
 
 int hm_decode_item_to_device_tone(const hm_file* f, uint32_t id, const hm_decode_params* params, const hm_device_view* view, const hm_device_light* light,
                                   const hm_device_tone* tone, const hm_device_dest* dest, hm_decoded* out)
 {
-  if (!f || !params || !tone || !dest || !out) return hm_fail(HM_ERR_INVALID_ARG, "null argument");
-  if (!light) return hm_fail(HM_ERR_INVALID_ARG, "tone: null light step");
-  const hm_device_tone own = tone_for_item(f, id, tone);
-  return decode_item_to(f, id, params, OutputTarget::to_dest(dest, view, light, &own), out);
+  return decode_item_to(HM_ENTRY_TONE, f, id, params, {view, light, tone}, dest, nullptr, out);
 }
 
 int hm_decode_item_to_device_alpha(const hm_file* f, uint32_t id, const hm_decode_params* params, const hm_device_view* view, const hm_device_light* light,
                                    const hm_device_tone* tone, const hm_device_alpha* alpha, const hm_device_dest* dest, hm_decoded* out)
 {
-  if (!f || !params || !alpha || !dest || !out) return hm_fail(HM_ERR_INVALID_ARG, "null argument");
-  if (tone && !light) return hm_fail(HM_ERR_INVALID_ARG, "tone: null light step");
-  hm_device_tone own{};
-  if (tone) own = tone_for_item(f, id, tone);
-  const OutputTarget t = OutputTarget::to_dest(dest, view, light, tone ? &own : nullptr, alpha);
-  return decode_item_to(f, id, params, t, out);
+  return decode_item_to(HM_ENTRY_ALPHA, f, id, params, {view, light, tone, alpha}, dest, nullptr, out);
 }
 
 int hm_decode_item_to_device_ootf(const hm_file* f, uint32_t id, const hm_decode_params* params, const hm_device_view* view, const hm_device_light* light,
                                   const hm_device_ootf* ootf, const hm_device_tone* tone, const hm_device_alpha* alpha, const hm_device_dest* dest, hm_decoded* out)
 {
-  if (!ootf) // the same call without the step
-    return alpha ? hm_decode_item_to_device_alpha(f, id, params, view, light, tone, alpha, dest, out) : hm_decode_item_to_device_tone(f, id, params, view, light, tone, dest, out);
-  if (!f || !params || !dest || !out) return hm_fail(HM_ERR_INVALID_ARG, "null argument");
-  if (!light) return hm_fail(HM_ERR_INVALID_ARG, "ootf: null light step");
-  // (the tone step's src_peak == 0 is display_peak here: no property of the item is read)
-  return decode_item_to(f, id, params, OutputTarget::to_dest(dest, view, light, tone, alpha, nullptr, ootf), out);
+  return decode_item_to(HM_ENTRY_OOTF, f, id, params, {view, light, tone, alpha, nullptr, ootf}, dest, nullptr, out);
 }
 
 int hm_file_item_light_levels(const hm_file* f, uint32_t id, hm_light_levels* out)
@@ -1750,15 +1782,13 @@ int hm_file_item_light_levels(const hm_file* f, uint32_t id, hm_light_levels* ou
 
 int hm_decode_item_to_device_planes(const hm_file* f, uint32_t id, const hm_decode_params* params, const hm_device_planes* planes, hm_decoded* out)
 {
-  if (!f || !params || !planes || !out) return hm_fail(HM_ERR_INVALID_ARG, "null argument");
-  return decode_item_to(f, id, params, OutputTarget::to_planes(planes), out);
+  return decode_item_to(HM_ENTRY_PLANES, f, id, params, {}, nullptr, planes, out);
 }
 
 int hm_decode_item_to_device_planes_view(const hm_file* f, uint32_t id, const hm_decode_params* params, const hm_device_view* view, const hm_device_planes* planes,
                                          hm_decoded* out)
 {
-  if (!f || !params || !view || !planes || !out) return hm_fail(HM_ERR_INVALID_ARG, "null argument");
-  return decode_item_to(f, id, params, OutputTarget::to_planes(planes, view), out);
+  return decode_item_to(HM_ENTRY_PLANES_VIEW, f, id, params, {view}, nullptr, planes, out);
 }
 
 int hm_plan_planes_view(const hm_file* f, uint32_t id, const hm_decode_params* params, const hm_device_view* view, int32_t tiles[4])
@@ -1880,19 +1910,11 @@ int hm_gain_for_item(const hm_file* f, uint32_t id, const hm_decode_params* para
   return hm_gain_geometry(W, H, MW, MH, minfo.bit_depth, &vp, &gp);
 }
 
+// (*out is zeroed before the gain step is judged: decode_item_to)
 int hm_decode_item_to_device_gain(const hm_file* f, uint32_t id, const hm_decode_params* params, const hm_device_view* view, const hm_device_light* light,
                                   const hm_device_tone* tone, const hm_device_gain* gain, const hm_device_dest* dest, hm_decoded* out)
 {
-  if (!f || !params || !gain || !dest || !out) return hm_fail(HM_ERR_INVALID_ARG, "null argument");
-  if (!light) return hm_fail(HM_ERR_INVALID_ARG, "gain: null light step");
-  hm_device_tone own_tone{};
-  if (tone) own_tone = tone_for_item(f, id, tone); // (the properties of item `id`: a 'tmap' item's clli describes the alternate rendition)
-  hm_device_gain own{};
-  uint32_t base = 0;
-  std::memset(out, 0, sizeof(*out));
-  const int rc = hm_gain_for_item(f, id, params, view, gain, &base, &own);
-  if (rc) return rc;
-  return decode_item_to(f, base, params, OutputTarget::to_dest(dest, view, light, tone ? &own_tone : nullptr, nullptr, &own), out);
+  return decode_item_to(HM_ENTRY_GAIN, f, id, params, {view, light, tone, nullptr, gain}, dest, nullptr, out);
 }
 
 int hm_file_overlay_info(const hm_file* f, uint32_t id, hm_overlay_info* info, uint32_t* children, int32_t* offsets, int max_children)
@@ -2033,71 +2055,70 @@ int hm_file_sequence_info(const hm_file* f, hm_sequence_info* info)
 static int decode_sequence(const hm_file* f, const uint32_t* frames, uint32_t first, int32_t count, const hm_decode_params* params, const hm_frame_dest* dests,
                            const OutputTarget& target, hm_decoded* out, int32_t* failed_frame);
 
-int hm_decode_frames_to_device_planes_view(const hm_file* f, const uint32_t* frames, int32_t count, const hm_decode_params* params, const hm_device_view* view,
-                                           const hm_device_planes* planes, hm_decoded* out, int32_t* failed_frame)
-{
-  if (failed_frame) *failed_frame = -1;
-  if (!frames || !planes || !view) return hm_fail(HM_ERR_INVALID_ARG, "null argument");
-  return decode_sequence(f, frames, 0, count, params, nullptr, OutputTarget::to_planes(planes, view), out, failed_frame);
-}
-
 int hm_decode_sequence(const hm_file* f, uint32_t first, int32_t count, const hm_decode_params* params, const hm_frame_dest* dests,
                        hm_decoded* out, int32_t* failed_frame)
 {
   return decode_sequence(f, nullptr, first, count, params, dests, OutputTarget(), out, failed_frame);
 }
 
+// the device forms: failed_frame is set before any check; f, params and out are decode_sequence's to judge.  The family has no plain
+// entry by frame IDs - its _view entry takes a NULL view -: HM_ENTRY_DEST is hm_decode_sequence_to_device, which counts from `first`.
+// A frame carries no properties: the tone step's src_peak == 0 is 1000 (tone_for_item with id 0).
+static int decode_frames_to(int kind, const hm_file* f, const uint32_t* frames, uint32_t first, int32_t count, const hm_decode_params* params,
+                            const hm_out_steps& st, const hm_device_dest* dests, const hm_device_planes* planes, hm_decoded* out,
+                            int32_t* failed_frame)
+{
+  if (failed_frame) *failed_frame = -1;
+  if (!frames && kind != HM_ENTRY_DEST) return hm_fail(HM_ERR_INVALID_ARG, "null argument");
+  OutputTarget t;
+  const int rc = OutputTarget::of_entry(kind, st, dests, planes, t, /*view_may_be_null=*/true);
+  if (rc) return rc;
+  hm_device_tone own{};
+  if (t.tone && !t.ootf) { own = tone_for_item(f, 0, t.tone); t.tone = &own; }
+  return decode_sequence(f, frames, first, count, params, nullptr, t, out, failed_frame);
+}
+
 int hm_decode_sequence_to_device(const hm_file* f, uint32_t first, int32_t count, const hm_decode_params* params, const hm_device_dest* dests,
                                  hm_decoded* out, int32_t* failed_frame)
 {
-  if (failed_frame) *failed_frame = -1;
-  if (!dests) return hm_fail(HM_ERR_INVALID_ARG, "null argument");
-  return decode_sequence(f, nullptr, first, count, params, nullptr, OutputTarget::to_dest(dests), out, failed_frame);
+  return decode_frames_to(HM_ENTRY_DEST, f, nullptr, first, count, params, {}, dests, nullptr, out, failed_frame);
 }
 
 int hm_decode_frames_to_device_view(const hm_file* f, const uint32_t* frames, int32_t count, const hm_decode_params* params, const hm_device_view* view,
                                     const hm_device_dest* dests, hm_decoded* out, int32_t* failed_frame)
 {
-  if (failed_frame) *failed_frame = -1;
-  if (!frames || !dests) return hm_fail(HM_ERR_INVALID_ARG, "null argument");
-  return decode_sequence(f, frames, 0, count, params, nullptr, OutputTarget::to_dest(dests, view), out, failed_frame);
+  return decode_frames_to(HM_ENTRY_VIEW, f, frames, 0, count, params, {view}, dests, nullptr, out, failed_frame);
 }
 
 int hm_decode_frames_to_device_light(const hm_file* f, const uint32_t* frames, int32_t count, const hm_decode_params* params, const hm_device_view* view,
                                      const hm_device_light* light, const hm_device_dest* dests, hm_decoded* out, int32_t* failed_frame)
 {
-  if (failed_frame) *failed_frame = -1;
-  if (!frames || !dests || !light) return hm_fail(HM_ERR_INVALID_ARG, "null argument");
-  return decode_sequence(f, frames, 0, count, params, nullptr, OutputTarget::to_dest(dests, view, light), out, failed_frame);
+  return decode_frames_to(HM_ENTRY_LIGHT, f, frames, 0, count, params, {view, light}, dests, nullptr, out, failed_frame);
 }
 
 int hm_decode_frames_to_device_tone(const hm_file* f, const uint32_t* frames, int32_t count, const hm_decode_params* params, const hm_device_view* view,
                                     const hm_device_light* light, const hm_device_tone* tone, const hm_device_dest* dests, hm_decoded* out, int32_t* failed_frame)
 {
-  if (failed_frame) *failed_frame = -1;
-  if (!frames || !dests || !tone) return hm_fail(HM_ERR_INVALID_ARG, "null argument");
-  if (!light) return hm_fail(HM_ERR_INVALID_ARG, "tone: null light step");
-  const hm_device_tone own = tone_for_item(f, 0, tone); // (a frame carries no properties)
-  return decode_sequence(f, frames, 0, count, params, nullptr, OutputTarget::to_dest(dests, view, light, &own), out, failed_frame);
+  return decode_frames_to(HM_ENTRY_TONE, f, frames, 0, count, params, {view, light, tone}, dests, nullptr, out, failed_frame);
 }
 
 int hm_decode_frames_to_device_ootf(const hm_file* f, const uint32_t* frames, int32_t count, const hm_decode_params* params, const hm_device_view* view,
                                     const hm_device_light* light, const hm_device_ootf* ootf, const hm_device_tone* tone, const hm_device_dest* dests, hm_decoded* out,
                                     int32_t* failed_frame)
 {
-  if (!ootf) return hm_decode_frames_to_device_tone(f, frames, count, params, view, light, tone, dests, out, failed_frame); // the same call without the step
-  if (failed_frame) *failed_frame = -1;
-  if (!frames || !dests) return hm_fail(HM_ERR_INVALID_ARG, "null argument");
-  if (!light) return hm_fail(HM_ERR_INVALID_ARG, "ootf: null light step");
-  return decode_sequence(f, frames, 0, count, params, nullptr, OutputTarget::to_dest(dests, view, light, tone, nullptr, nullptr, ootf), out, failed_frame);
+  return decode_frames_to(HM_ENTRY_OOTF, f, frames, 0, count, params, {view, light, tone, nullptr, nullptr, ootf}, dests, nullptr, out, failed_frame);
 }
 
 int hm_decode_frames_to_device_planes(const hm_file* f, const uint32_t* frames, int32_t count, const hm_decode_params* params, const hm_device_planes* planes,
                                       hm_decoded* out, int32_t* failed_frame)
 {
-  if (failed_frame) *failed_frame = -1;
-  if (!frames || !planes) return hm_fail(HM_ERR_INVALID_ARG, "null argument");
-  return decode_sequence(f, frames, 0, count, params, nullptr, OutputTarget::to_planes(planes), out, failed_frame);
+  return decode_frames_to(HM_ENTRY_PLANES, f, frames, 0, count, params, {}, nullptr, planes, out, failed_frame);
+}
+
+int hm_decode_frames_to_device_planes_view(const hm_file* f, const uint32_t* frames, int32_t count, const hm_decode_params* params, const hm_device_view* view,
+                                           const hm_device_planes* planes, hm_decoded* out, int32_t* failed_frame)
+{
+  return decode_frames_to(HM_ENTRY_PLANES_VIEW, f, frames, 0, count, params, {view}, nullptr, planes, out, failed_frame);
 }
 
 // frames (NULL: first .. first + count - 1): the 1-based IDs of the frames, in any order, repeats allowed.
@@ -2135,41 +2156,23 @@ static int decode_sequence(const hm_file* f, const uint32_t* frames, uint32_t fi
     return hm_fail(HM_ERR_INVALID_ARG, "frames %u..%llu outside 1..%u", first, (unsigned long long)first + count - 1, n_frames);
   auto frame_id = [&](int k) { return frames ? frames[k] : first + (uint32_t)k; };
   if (params->ext_dst) return hm_fail(HM_ERR_INVALID_ARG, "params->ext_dst: a sequence takes its caller buffers from dests");
-  if (ddests) { // what can be refused without the frames' sizes (those: below, behind the entropy decode, before anything is queued)
-    const hm_out_steps st = target.steps();
-    for (int k = 0; k < count; k++) {
-      const int rc = hm_out_check_static(params->out_format, &ddests[k], &st, 0);
-      if (rc) return rc;
-      if (!ddests[k].ptr) return hm_fail(HM_ERR_INVALID_ARG, "device destination of frame %d: null ptr", k);
-    }
-    if (view) // the view and each destination against the size the track declares (the decoded size: below), as hm_decode_item_to_device_view
-      for (int k = 0; k < count; k++) {
-        hm_image_info info;
-        if (hm_file_image_info(f, frame_id(k), &info) != HM_OK) continue; // (such a frame fails below with its own message)
-        const int rc = target_fits(params, target_of(k), info.width, info.height, info.chroma, info.bit_depth, 0, nullptr, false);
-        if (rc) { if (failed_frame) *failed_frame = k; return rc; }
-      }
-    for (int k = 0; k < count; k++) { // a device, the pointers
-      const int rc = target_fits(params, target_of(k), 0, 0, 0, 0, 0, nullptr, true);
-      if (rc) return rc;
-    }
-  }
-  if (pdests) { // the same for planar destinations
-    for (int k = 0; k < count; k++) {
-      const int rc = check_planes_params(params, &pdests[k]);
-      if (rc) { if (failed_frame) *failed_frame = k; return rc; }
-    }
-    std::vector<hm_image_info> declared((size_t)count); // against what the track declares (the decoded pictures: below); width 0: nothing usable
-    for (int pointers = 0; pointers < 2; pointers++) { // every frame's len before a device is asked for and the pointers are looked at
-      if (pointers)
-        if (const int rc = require_device()) return rc; // (names no frame)
-      for (int k = 0; k < count; k++) {
-        hm_image_info& info = declared[k];
-        if (!pointers && (hm_file_image_info(f, frame_id(k), &info) != HM_OK || info.bit_depth < 8 || info.bit_depth > 16 || info.chroma < 0 || info.chroma > 3)) info.width = 0;
-        const int rc = target_fits(params, target_of(k), info.width, info.height, info.chroma, info.bit_depth, 0, nullptr, pointers != 0); // (frames carry no alpha)
-        if (rc) { if (failed_frame) *failed_frame = k; return rc; }
-      }
-    }
+  if (ddests || pdests) {
+    // check_target_request's phases, each over every frame before the next begins: what can be refused without the frames' sizes, the
+    // target against the size the track declares (the decoded size: below, behind the entropy decode, before anything is queued), a device
+    // and the pointers.  A planar destination names the frame in every phase; an interleaved one only in the second, which it runs
+    // only with a view (as hm_decode_item_to_device_view).  Frames carry no alpha.
+    std::vector<hm_image_info> declared((size_t)count);
+    auto each_frame = [&](bool names_frame, auto&& phase) {
+      for (int k = 0; k < count; k++)
+        if (const int rc = phase(k)) { if (names_frame && failed_frame) *failed_frame = k; return rc; }
+      return (int)HM_OK;
+    };
+    int rc;
+    if ((rc = each_frame(pdests != nullptr, [&](int k) { return check_request_alone(params, target_of(k), k); }))) return rc;
+    auto declared_fits = [&](int k) { return check_request_declared(f, frame_id(k), params, target_of(k), 0, declared[k]); };
+    if ((pdests || view) && (rc = each_frame(true, declared_fits))) return rc;
+    if (pdests && (rc = require_device())) return rc; // (names no frame)
+    if ((rc = each_frame(pdests != nullptr, [&](int k) { return check_request_pointers(params, target_of(k), 0, declared[k]); }))) return rc;
   }
   const bool planar_target = hm_out_is_planar(params->out_format);
   if (params->out_format && !planar_target) {

@@ -14,6 +14,7 @@
 
 #include "heif_file.h"
 #include "hm_devdest.h"
+#include "hm_entry_steps.h"
 #include "hm_internal.h"
 #include "hm_stream.h"
 
@@ -104,33 +105,35 @@ struct ItemPlan {
 
 // Where the result of a decode goes beside hm_decoded: every function between an entry point and emit_image takes one of these.
 // All null: pinned host memory (or params->ext_dst).  The pointers are the caller's; target_check_shape states what goes together.
+// On the way in a target passes one front, each part of it stated once: of_entry (which pointers the entry's kind takes:
+// hm_entry_steps.h), resolve_request (the request against the file: the tone step's peak, the gain step's items) and
+// check_target_request (its three phases: the request alone, against what the file declares, a device and the pointers).
 struct OutputTarget {
   const hm_device_dest* dest = nullptr;        // the interleaved pixels go to caller-owned device memory; nothing is copied to the host
   const hm_device_view* view = nullptr;        // ... a rectangle of the image, resampled (with dest or planes)
   const hm_device_planes* planes = nullptr;    // a planar result (out_format 0 / HM_OUT_YCBCR_*) goes to caller-owned device memory, plane by plane
   const hm_device_light* light = nullptr;      // the light step in the write of dest
-  const hm_device_tone* tone = nullptr;        // ... with a tone step inside it (src_peak resolved by the entry point: never 0 here)
+  const hm_device_tone* tone = nullptr;        // ... with a tone step inside it (src_peak resolved by resolve_request: never 0 here)
   const hm_device_alpha* alpha = nullptr;      // the alpha step in the write of dest (alone, or beside light and tone)
-  const hm_device_gain* gain = nullptr;        // the gain step beside light (resolved by the entry point: map_item is the map's item, params are explicit)
+  const hm_device_gain* gain = nullptr;        // the gain step beside light (resolved by resolve_request: map_item is the map's item, params are explicit)
   const struct PlanarImage* gain_map = nullptr; // ... and its decoded map (job_enqueue sets it; null with a gain step of weight 0)
   const hm_device_ootf* ootf = nullptr;        // the OOTF step beside light (a tone step beside it keeps its zeros: they resolve to display_peak)
   hm_view_scratch* scratch = nullptr;          // tap tables and the intermediate of the resampling step, the tables of the light step
   hm_view_item* view_later = nullptr;          // view + dest: the view is not written, only described there - the caller writes it with those of other images
   hm_planes_view_item* planes_later = nullptr; // the same for view + planes
-  static OutputTarget to_dest(const hm_device_dest* d, const hm_device_view* v = nullptr, const hm_device_light* l = nullptr, const hm_device_tone* tn = nullptr,
-                              const hm_device_alpha* a = nullptr, const hm_device_gain* g = nullptr, const hm_device_ootf* o = nullptr)
+  // the target of a device entry of `kind` (hm_entry_kind): its destination - d or p, whichever the entry has - with the step pointers
+  // the caller passed, or the refusal ("null argument" for a null destination, else hm_entry_steps')
+  static int of_entry(int kind, const hm_out_steps& st, const hm_device_dest* d, const hm_device_planes* p, OutputTarget& t,
+                      bool view_may_be_null = false)
   {
-    OutputTarget t;
-    t.dest = d; t.view = v; t.light = l; t.tone = tn; t.alpha = a; t.gain = g; t.ootf = o;
-    return t;
+    if (!d && !p) return hm_fail(HM_ERR_INVALID_ARG, "null argument");
+    const int rc = hm_entry_steps(kind, st, view_may_be_null);
+    if (rc) return rc;
+    t = OutputTarget();
+    t.dest = d; t.planes = p; t.view = st.view; t.light = st.light; t.tone = st.tone; t.alpha = st.alpha; t.gain = st.gain; t.ootf = st.ootf;
+    return HM_OK;
   }
   hm_out_steps steps() const { return hm_out_steps{view, light, tone, alpha, gain, ootf}; } // the request of the device write (hm_devdest.h)
-  static OutputTarget to_planes(const hm_device_planes* p, const hm_device_view* v = nullptr)
-  {
-    OutputTarget t;
-    t.planes = p; t.view = v;
-    return t;
-  }
 };
 // dest xor planes (or neither); light only with dest; tone only with light; ootf only with light; alpha only with dest and never with view_later; gain only with light and
 // never with view_later; view only with one of the two; a *_later only with view and its own kind of destination
@@ -205,14 +208,31 @@ void job_parse_tile(DecodeJob& j, int k, int row_threads = 1); // k = 0 .. job_t
 // the entropy decode of one coded picture (hvc1 item or movie sample `id`) into `blob`, or its failure in status / message
 void parse_picture(const hm_file* f, uint32_t id, bool few_pictures, int strict, int row_threads, Blob& blob, int& status, std::string& message);
 int job_enqueue(DecodeJob& j, hm_decoded* out);
-// everything about a target (dest or planes, with its view and light step) that can be refused before the entropy decode: the request
-// itself, the target against what hm_image_info declares for the item (target_fits in hm_image.cpp: size, and for planes the result's
-// chroma format and depth where the file decides them; the crop of a view against the declared size, the destination against the
-// view's output size), a device, the pointers
+// everything about a target (dest or planes, with its view and steps) that can be refused before the entropy decode, in three phases
+// (hm_image.cpp: check_request_alone, check_request_declared, check_request_pointers; a sequence loops each over its frames):
+//   the request itself - its shape, params->ext_dst, the static checks of the destination and the steps, a null pointer;
+//   the target against what hm_image_info declares for the item (target_fits: size, and for planes the result's chroma format and depth
+//   where the file decides them; the crop of a view against the declared size, the destination against the view's output size);
+//   a device, the pointers
 int check_target_request(const hm_file* f, uint32_t id, const hm_decode_params* params, const OutputTarget& t);
 // the tone step an entry point hands on: the caller's, with src_peak == 0 replaced by the peak of item `id` (its clli, its mdcv, 1000;
 // id 0 or a frame of a sequence: 1000).  The other refusals are check_target_request's.
 hm_device_tone tone_for_item(const hm_file* f, uint32_t id, const hm_device_tone* tone);
+// A request resolved against the file, in the one order every entry keeps: the tone step's src_peak from the item asked for (only
+// without an OOTF step: beside one 0 is display_peak and no property is read); the gain step from that item too (hm_gain_for_item: a
+// 'tmap' item's own properties) - the item to decode becomes the base image; refuse_derived: what a derived item is refused for without
+// looking at a picture (the item entries; the pipeline leaves it to job_plan); check_target_request.  t points into tone and gain.
+struct ResolvedRequest {
+  hm_device_tone tone{};
+  hm_device_gain gain{};
+  OutputTarget t;
+  uint32_t id = 0; // the item to decode
+  ResolvedRequest() = default;
+  ResolvedRequest(const ResolvedRequest&) = delete;
+  ResolvedRequest& operator=(const ResolvedRequest&) = delete;
+};
+int resolve_request(const hm_file* f, uint32_t id, const hm_decode_params* params, const OutputTarget& asked, bool refuse_derived,
+                    ResolvedRequest& r);
 int job_complete(DecodeJob& j, hm_decoded* out);
 
 } // namespace hm_img

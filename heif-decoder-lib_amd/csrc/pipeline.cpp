@@ -190,77 +190,68 @@ int hm_pipeline_submit(hm_pipeline* p, const uint8_t* heif, size_t size, uint32_
   return submit(p, heif, size, item_id, tag, OutputTarget());
 }
 
+// the device forms.  What only the open file says - the image's own peak for the tone step's src_peak == 0 (beside an OOTF step that is
+// display_peak: no property is read), a 'tmap' item's base, map and parameters - is read in submit (resolve_request)
+static int submit_to(int kind, hm_pipeline* p, const uint8_t* heif, size_t size, uint32_t item_id, uint64_t tag, const hm_out_steps& st,
+                     const hm_device_dest* dest, const hm_device_planes* planes)
+{
+  if (!p || !heif) return hm_fail(HM_ERR_INVALID_ARG, "null argument");
+  OutputTarget t;
+  const int rc = OutputTarget::of_entry(kind, st, dest, planes, t);
+  return rc ? rc : submit(p, heif, size, item_id, tag, t);
+}
+
 int hm_pipeline_submit_to_device(hm_pipeline* p, const uint8_t* heif, size_t size, uint32_t item_id, uint64_t tag, const hm_device_dest* dest)
 {
-  if (!p || !heif || !dest) return hm_fail(HM_ERR_INVALID_ARG, "null argument");
-  return submit(p, heif, size, item_id, tag, OutputTarget::to_dest(dest));
+  return submit_to(HM_ENTRY_DEST, p, heif, size, item_id, tag, {}, dest, nullptr);
 }
 
 int hm_pipeline_submit_to_device_view(hm_pipeline* p, const uint8_t* heif, size_t size, uint32_t item_id, uint64_t tag, const hm_device_view* view,
                                       const hm_device_dest* dest)
 {
-  if (!p || !heif || !view || !dest) return hm_fail(HM_ERR_INVALID_ARG, "null argument");
-  return submit(p, heif, size, item_id, tag, OutputTarget::to_dest(dest, view));
+  return submit_to(HM_ENTRY_VIEW, p, heif, size, item_id, tag, {view}, dest, nullptr);
 }
 
 int hm_pipeline_submit_to_device_light(hm_pipeline* p, const uint8_t* heif, size_t size, uint32_t item_id, uint64_t tag, const hm_device_view* view,
                                        const hm_device_light* light, const hm_device_dest* dest)
 {
-  if (!p || !heif || !light || !dest) return hm_fail(HM_ERR_INVALID_ARG, "null argument");
-  return submit(p, heif, size, item_id, tag, OutputTarget::to_dest(dest, view, light));
+  return submit_to(HM_ENTRY_LIGHT, p, heif, size, item_id, tag, {view, light}, dest, nullptr);
 }
 
-// (src_peak == 0, the image's own peak, is read once the file is open: submit)
 int hm_pipeline_submit_to_device_tone(hm_pipeline* p, const uint8_t* heif, size_t size, uint32_t item_id, uint64_t tag, const hm_device_view* view,
                                       const hm_device_light* light, const hm_device_tone* tone, const hm_device_dest* dest)
 {
-  if (!p || !heif || !tone || !dest) return hm_fail(HM_ERR_INVALID_ARG, "null argument");
-  if (!light) return hm_fail(HM_ERR_INVALID_ARG, "tone: null light step");
-  return submit(p, heif, size, item_id, tag, OutputTarget::to_dest(dest, view, light, tone));
+  return submit_to(HM_ENTRY_TONE, p, heif, size, item_id, tag, {view, light, tone}, dest, nullptr);
 }
 
 int hm_pipeline_submit_to_device_alpha(hm_pipeline* p, const uint8_t* heif, size_t size, uint32_t item_id, uint64_t tag, const hm_device_view* view,
                                        const hm_device_light* light, const hm_device_tone* tone, const hm_device_alpha* alpha, const hm_device_dest* dest)
 {
-  if (!p || !heif || !alpha || !dest) return hm_fail(HM_ERR_INVALID_ARG, "null argument");
-  if (tone && !light) return hm_fail(HM_ERR_INVALID_ARG, "tone: null light step");
-  const OutputTarget t = OutputTarget::to_dest(dest, view, light, tone, alpha);
-  return submit(p, heif, size, item_id, tag, t);
+  return submit_to(HM_ENTRY_ALPHA, p, heif, size, item_id, tag, {view, light, tone, alpha}, dest, nullptr);
 }
 
-// (beside an OOTF step the tone step's src_peak == 0 is display_peak: submit reads no property)
 int hm_pipeline_submit_to_device_ootf(hm_pipeline* p, const uint8_t* heif, size_t size, uint32_t item_id, uint64_t tag, const hm_device_view* view,
                                       const hm_device_light* light, const hm_device_ootf* ootf, const hm_device_tone* tone, const hm_device_alpha* alpha,
                                       const hm_device_dest* dest)
 {
-  if (!ootf) // the same call without the step
-    return alpha ? hm_pipeline_submit_to_device_alpha(p, heif, size, item_id, tag, view, light, tone, alpha, dest)
-                 : hm_pipeline_submit_to_device_tone(p, heif, size, item_id, tag, view, light, tone, dest);
-  if (!p || !heif || !dest) return hm_fail(HM_ERR_INVALID_ARG, "null argument");
-  if (!light) return hm_fail(HM_ERR_INVALID_ARG, "ootf: null light step");
-  return submit(p, heif, size, item_id, tag, OutputTarget::to_dest(dest, view, light, tone, alpha, nullptr, ootf));
+  return submit_to(HM_ENTRY_OOTF, p, heif, size, item_id, tag, {view, light, tone, alpha, nullptr, ootf}, dest, nullptr);
 }
 
-// (a 'tmap' item's base, map and parameters are read once the file is open: submit)
 int hm_pipeline_submit_to_device_gain(hm_pipeline* p, const uint8_t* heif, size_t size, uint32_t item_id, uint64_t tag, const hm_device_view* view,
                                       const hm_device_light* light, const hm_device_tone* tone, const hm_device_gain* gain, const hm_device_dest* dest)
 {
-  if (!p || !heif || !gain || !dest) return hm_fail(HM_ERR_INVALID_ARG, "null argument");
-  if (!light) return hm_fail(HM_ERR_INVALID_ARG, "gain: null light step");
-  return submit(p, heif, size, item_id, tag, OutputTarget::to_dest(dest, view, light, tone, nullptr, gain));
+  return submit_to(HM_ENTRY_GAIN, p, heif, size, item_id, tag, {view, light, tone, nullptr, gain}, dest, nullptr);
 }
 
 int hm_pipeline_submit_to_device_planes(hm_pipeline* p, const uint8_t* heif, size_t size, uint32_t item_id, uint64_t tag, const hm_device_planes* planes)
 {
-  if (!p || !heif || !planes) return hm_fail(HM_ERR_INVALID_ARG, "null argument");
-  return submit(p, heif, size, item_id, tag, OutputTarget::to_planes(planes));
+  return submit_to(HM_ENTRY_PLANES, p, heif, size, item_id, tag, {}, nullptr, planes);
 }
 
 int hm_pipeline_submit_to_device_planes_view(hm_pipeline* p, const uint8_t* heif, size_t size, uint32_t item_id, uint64_t tag, const hm_device_view* view,
                                              const hm_device_planes* planes)
 {
-  if (!p || !heif || !view || !planes) return hm_fail(HM_ERR_INVALID_ARG, "null argument");
-  return submit(p, heif, size, item_id, tag, OutputTarget::to_planes(planes, view));
+  return submit_to(HM_ENTRY_PLANES_VIEW, p, heif, size, item_id, tag, {view}, nullptr, planes);
 }
 
 // target: the image's pixels (dest) or the planes of the pipeline's planar out_format (planes) go to caller-owned device memory of the
@@ -298,19 +289,12 @@ static int submit(hm_pipeline* p, const uint8_t* heif, size_t size, uint32_t ite
       int prev = -1;
       hipGetDevice(&prev);
       hipSetDevice(p->cfg.device); // (the pointers must belong to the device the crew works on)
-      OutputTarget t = target;
-      hm_device_tone own{};
-      if (t.tone && !t.ootf) { own = tone_for_item(im->file, im->job.id, t.tone); t.tone = &own; } // (the image's own peak, before the curve is judged)
-      hm_device_gain own_gain{};
-      if (t.gain) { // (a 'tmap' item: the job decodes its base image, the map beside it)
-        uint32_t base = 0;
-        rc = hm_gain_for_item(im->file, im->job.id, &im->job.params, t.view, t.gain, &base, &own_gain);
-        t.gain = &own_gain;
-        if (!rc) im->job.id = base;
-      }
-      if (!rc) rc = check_target_request(im->file, im->job.id, &im->job.params, t);
+      // (the derived-item refusal is job_plan's here; the job takes the base image's id once the whole request has passed, where it
+      //  used to take it as soon as the gain step had - an image that fails here is deleted either way)
+      hm_img::ResolvedRequest r;
+      rc = resolve_request(im->file, im->job.id, &im->job.params, target, false, r);
       if (prev >= 0) hipSetDevice(prev);
-      if (!rc) im->job.target.set(t);
+      if (!rc) { im->job.id = r.id; im->job.target.set(r.t); }
     }
     if (!rc) rc = job_plan(im->job);
   }

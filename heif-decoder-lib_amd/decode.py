@@ -298,6 +298,37 @@ def _gain_of(gain, lit):
     return d
 
 
+class _Steps:
+    """The steps of a request for the target fmt: alp and c (the channels of the tensor) from the alpha= argument at once, lit, ton, gn
+    and oo from light=, tone=, gain= and ootf= where the caller parses them (parse) - ctypes structs or None.  What does not go together
+    is refused there."""
+
+    def __init__(self, alpha, fmt):
+        self.alp, self.c = _alpha_of(alpha, fmt)
+        self.lit = self.ton = self.gn = self.oo = None
+
+    def parse(self, light, tone, gain, ootf):
+        self.lit = _light_of(light)
+        self.ton = _tone_of(tone, self.lit)
+        self.gn = _gain_of(gain, self.lit)
+        self.oo = _ootf_of(ootf, self.lit)
+        if self.gn is not None and self.alp is not None:
+            raise capi.HmError(-2, "gain: an alpha step beside the gain step is not supported (the open step)")
+        if self.gn is not None and self.oo is not None:
+            raise capi.HmError(-2, "ootf: a gain step beside the OOTF step is not supported (a gain map's base is SDR)")
+        return self
+
+    def entry(self, L, family, view):
+        """(the entry of `family` - hm_decode_item_to_device, hm_decode_frames_to_device, hm_pipeline_submit_to_device - this request with
+        `view` (or None) goes through, its step arguments in the entry's order): capi.ENTRY_KINDS"""
+        return _entry(L, family, dict(view=view, light=self.lit, tone=self.ton, alpha=self.alp, gain=self.gn, ootf=self.oo))
+
+
+def _entry(L, family, steps, planes=False):
+    name, args = capi.entry_of(family, {k for k, v in steps.items() if v is not None}, planes)
+    return getattr(L, name), [_ref(steps[a]) for a in args]
+
+
 def _gain_items(f, iid, gn):
     """(the item the decode is asked for, the item whose size the tensor has): a 'tmap' item and its base image - iid itself when it
     is a 'tmap' item, else the 'tmap' item whose base iid is (hm_file_gain_map_of) -, or with an explicit map_item iid twice"""
@@ -354,21 +385,15 @@ def decode_to_tensor(data, item_id=0, out_format="rgb", layout="chw", dtype=None
     if dtype is None:
         dtype = out.dtype if out is not None else torch.float32
     code = _dtype_code(dtype)
-    alp, c = _alpha_of(alpha, fmt)
+    st = _Steps(alpha, fmt)
+    c = st.c
     f = _File(data)
     try:
-        lit = _light_of(light)
-        ton = _tone_of(tone, lit)
-        gn = _gain_of(gain, lit)
-        oo = _ootf_of(ootf, lit)
-        if gn is not None and alp is not None:
-            raise capi.HmError(-2, "gain: an alpha step beside the gain step is not supported (the open step)")
-        if gn is not None and oo is not None:
-            raise capi.HmError(-2, "ootf: a gain step beside the OOTF step is not supported (a gain map's base is SDR)")
+        st.parse(light, tone, gain, ootf)
         iid = item_id or L.hm_file_primary_item(f.h)
         sized = iid
-        if gn is not None:
-            iid, sized = _gain_items(f, iid, gn)
+        if st.gn is not None:
+            iid, sized = _gain_items(f, iid, st.gn)
         _, w, h = f.size(sized)
         view, w, h = _view_of(crop, size, filter, w, h)
         shape = _shape(lay, c, h, w)
@@ -380,32 +405,11 @@ def decode_to_tensor(data, item_id=0, out_format="rgb", layout="chw", dtype=None
             if tuple(out.shape) != shape:
                 raise ValueError(f"out: shape {tuple(out.shape)} does not match the image's {shape}")
         dest = _dest_of(out, lay, code, c, _per_channel(scale, 1.0), _per_channel(bias, 0.0))
-        if stream is None:
-            stream = torch.cuda.current_stream(out.device)
-        handle = stream.cuda_stream if hasattr(stream, "cuda_stream") else int(stream)
-        prm = capi.DecodeParams(fmt, host_threads or _default_threads(), 0, 0, handle or None, None, 0, 0, 0, 0)
+        prm = capi.DecodeParams(fmt, host_threads or _default_threads(), 0, 0, _stream_handle(stream, out.device), None, 0, 0, 0, 0)
         d = capi.Decoded()
+        fn, steps = st.entry(L, "hm_decode_item_to_device", view)
         with torch.cuda.device(out.device):
-            if gn is not None:
-                capi.check_image(L.hm_decode_item_to_device_gain(f.h, iid, C.byref(prm), C.byref(view) if view is not None else None, C.byref(lit),
-                                                                 C.byref(ton) if ton is not None else None, C.byref(gn), C.byref(dest), C.byref(d)))
-            elif oo is not None:
-                capi.check_image(L.hm_decode_item_to_device_ootf(f.h, iid, C.byref(prm), _ref(view), C.byref(lit), C.byref(oo), _ref(ton), _ref(alp), C.byref(dest),
-                                                                 C.byref(d)))
-            elif alp is not None:
-                capi.check_image(L.hm_decode_item_to_device_alpha(f.h, iid, C.byref(prm), C.byref(view) if view is not None else None,
-                                                                  C.byref(lit) if lit is not None else None, C.byref(ton) if ton is not None else None,
-                                                                  C.byref(alp), C.byref(dest), C.byref(d)))
-            elif ton is not None:
-                capi.check_image(L.hm_decode_item_to_device_tone(f.h, iid, C.byref(prm), C.byref(view) if view is not None else None, C.byref(lit), C.byref(ton),
-                                                                 C.byref(dest), C.byref(d)))
-            elif lit is not None:
-                capi.check_image(L.hm_decode_item_to_device_light(f.h, iid, C.byref(prm), C.byref(view) if view is not None else None, C.byref(lit), C.byref(dest),
-                                                                  C.byref(d)))
-            elif view is None:
-                capi.check_image(L.hm_decode_item_to_device(f.h, iid, C.byref(prm), C.byref(dest), C.byref(d)))
-            else:
-                capi.check_image(L.hm_decode_item_to_device_view(f.h, iid, C.byref(prm), C.byref(view), C.byref(dest), C.byref(d)))
+            capi.check_image(fn(f.h, iid, C.byref(prm), *steps, C.byref(dest), C.byref(d)))
         if (d.width, d.height) != (w, h):  # (the library checked the destination against the decoded size: nothing else was written)
             raise capi.HmError(-3, f"the decoded image is {d.width} x {d.height}, the file declares {w} x {h}")
         L.hm_decoded_free(C.byref(d))
@@ -429,16 +433,9 @@ def decode_batch_to_tensor(files, item_id=0, out_format="rgb", layout="chw", dty
     if dtype is None:
         dtype = out.dtype if out is not None else torch.float32
     code = _dtype_code(dtype)
-    alp, c = _alpha_of(alpha, fmt)
+    st = _Steps(alpha, fmt)
     sc, bi = _per_channel(scale, 1.0), _per_channel(bias, 0.0)
-    lit = _light_of(light)
-    ton = _tone_of(tone, lit)
-    gn = _gain_of(gain, lit)
-    oo = _ootf_of(ootf, lit)
-    if gn is not None and alp is not None:
-        raise capi.HmError(-2, "gain: an alpha step beside the gain step is not supported (the open step)")
-    if gn is not None and oo is not None:
-        raise capi.HmError(-2, "ootf: a gain step beside the OOTF step is not supported (a gain map's base is SDR)")
+    c, gn = st.c, st.parse(light, tone, gain, ootf).gn
     names, datas = [], []
     for k, entry in enumerate(files):
         if isinstance(entry, (bytes, bytearray, memoryview)):
@@ -502,27 +499,9 @@ def decode_batch_to_tensor(files, item_id=0, out_format="rgb", layout="chw", dty
                     raise capi.HmError(status, f"{names[tag]}: {detail}")
             for k, data in enumerate(datas):
                 dest = _dest_of(out[k], lay, code, c, sc, bi)
+                fn, steps = st.entry(L, "hm_pipeline_submit_to_device", views[k])
                 while True:
-                    if gn is not None:
-                        rc = L.hm_pipeline_submit_to_device_gain(pipe, data, len(data), ids[k], k, C.byref(views[k]) if views[k] is not None else None,
-                                                                 C.byref(lit), C.byref(ton) if ton is not None else None, C.byref(gn), C.byref(dest))
-                    elif oo is not None:
-                        rc = L.hm_pipeline_submit_to_device_ootf(pipe, data, len(data), ids[k], k, _ref(views[k]), C.byref(lit), C.byref(oo), _ref(ton), _ref(alp),
-                                                                 C.byref(dest))
-                    elif alp is not None:
-                        rc = L.hm_pipeline_submit_to_device_alpha(pipe, data, len(data), ids[k], k, C.byref(views[k]) if views[k] is not None else None,
-                                                                  C.byref(lit) if lit is not None else None, C.byref(ton) if ton is not None else None,
-                                                                  C.byref(alp), C.byref(dest))
-                    elif ton is not None:
-                        rc = L.hm_pipeline_submit_to_device_tone(pipe, data, len(data), ids[k], k, C.byref(views[k]) if views[k] is not None else None,
-                                                                 C.byref(lit), C.byref(ton), C.byref(dest))
-                    elif lit is not None:
-                        rc = L.hm_pipeline_submit_to_device_light(pipe, data, len(data), ids[k], k, C.byref(views[k]) if views[k] is not None else None,
-                                                                  C.byref(lit), C.byref(dest))
-                    elif views[k] is None:
-                        rc = L.hm_pipeline_submit_to_device(pipe, data, len(data), ids[k], k, C.byref(dest))
-                    else:
-                        rc = L.hm_pipeline_submit_to_device_view(pipe, data, len(data), ids[k], k, C.byref(views[k]), C.byref(dest))
+                    rc = fn(pipe, data, len(data), ids[k], k, *steps, C.byref(dest))
                     if rc < 0:  # refused at submission (e.g. a derived item: the pipeline takes coded images and grids): name the file
                         raise capi.HmError(rc, f"{names[k]}: {L.hm_last_error().decode()}")
                     if rc != capi.HM_PIPELINE_FULL:
@@ -567,7 +546,9 @@ def decode_sequence_to_tensor(data, frames=None, out_format="rgb", layout="chw",
     fmt, lay = _out_format(out_format), _layout(layout)
     if dtype is None:
         dtype = out.dtype if out is not None else torch.float32
-    code, c = _dtype_code(dtype), _channels(fmt)
+    code = _dtype_code(dtype)
+    st = _Steps(None, fmt)
+    c = st.c
     sc, bi = _per_channel(scale, 1.0), _per_channel(bias, 0.0)
     f = _File(data)
     try:
@@ -594,28 +575,12 @@ def decode_sequence_to_tensor(data, frames=None, out_format="rgb", layout="chw",
                 raise ValueError(f"out: a CUDA tensor of dtype {dtype} is needed, got {out.dtype} on {out.device}")
         n = len(ids)
         dests = (capi.DeviceDest * n)(*[_dest_of(out[k], lay, code, c, sc, bi) for k in range(n)])
-        if stream is None:
-            stream = torch.cuda.current_stream(out.device)
-        handle = stream.cuda_stream if hasattr(stream, "cuda_stream") else int(stream)
-        prm = capi.DecodeParams(fmt, host_threads or _default_threads(), 0, 0, handle or None, None, 0, 0, 0, 0)
+        prm = capi.DecodeParams(fmt, host_threads or _default_threads(), 0, 0, _stream_handle(stream, out.device), None, 0, 0, 0, 0)
         res = (capi.Decoded * n)()
         failed = C.c_int32(-1)
-        lit = _light_of(light)
-        ton = _tone_of(tone, lit)
-        oo = _ootf_of(ootf, lit)
+        fn, steps = st.parse(light, tone, None, ootf).entry(L, "hm_decode_frames_to_device", view)
         with torch.cuda.device(out.device):
-            if oo is not None:
-                rc = L.hm_decode_frames_to_device_ootf(f.h, (C.c_uint32 * n)(*ids), n, C.byref(prm), _ref(view), C.byref(lit), C.byref(oo), _ref(ton), dests, res,
-                                                       C.byref(failed))
-            elif ton is not None:
-                rc = L.hm_decode_frames_to_device_tone(f.h, (C.c_uint32 * n)(*ids), n, C.byref(prm), C.byref(view) if view is not None else None, C.byref(lit),
-                                                       C.byref(ton), dests, res, C.byref(failed))
-            elif lit is not None:
-                rc = L.hm_decode_frames_to_device_light(f.h, (C.c_uint32 * n)(*ids), n, C.byref(prm), C.byref(view) if view is not None else None, C.byref(lit),
-                                                        dests, res, C.byref(failed))
-            else:
-                rc = L.hm_decode_frames_to_device_view(f.h, (C.c_uint32 * n)(*ids), n, C.byref(prm), C.byref(view) if view is not None else None, dests, res,
-                                                       C.byref(failed))
+            rc = fn(f.h, (C.c_uint32 * n)(*ids), n, C.byref(prm), *steps, dests, res, C.byref(failed))
         if rc < 0:
             detail = f"{L.hm_status_string(rc).decode()}: {L.hm_last_error().decode()}"
             k = failed.value
@@ -759,11 +724,9 @@ def decode_to_planes(data, item_id=0, chroma=None, layout="planar", dtype=None, 
         planes = _planes_of(out, rchroma, lay, alpha, code, msb_aligned, sc, bi)
         prm = capi.DecodeParams(fmt, host_threads or _default_threads(), 0, 0, _stream_handle(stream, device), None, 0, 0, 0, 1 if to_8bit else 0)
         d = capi.Decoded()
+        fn, steps = _entry(L, "hm_decode_item_to_device", dict(view=view), planes=True)
         with torch.cuda.device(device):
-            if view is None:
-                capi.check_image(L.hm_decode_item_to_device_planes(f.h, iid, C.byref(prm), C.byref(planes), C.byref(d)))
-            else:
-                capi.check_image(L.hm_decode_item_to_device_planes_view(f.h, iid, C.byref(prm), C.byref(view), C.byref(planes), C.byref(d)))
+            capi.check_image(fn(f.h, iid, C.byref(prm), *steps, C.byref(planes), C.byref(d)))
         L.hm_decoded_free(C.byref(d))
         return out
     finally:
@@ -814,11 +777,9 @@ def decode_sequence_to_planes(data, frames=None, chroma=None, layout="planar", d
         prm = capi.DecodeParams(fmt, host_threads or _default_threads(), 0, 0, _stream_handle(stream, device), None, 0, 0, 0, 1 if to_8bit else 0)
         res = (capi.Decoded * n)()
         failed = C.c_int32(-1)
+        fn, steps = _entry(L, "hm_decode_frames_to_device", dict(view=view), planes=True)
         with torch.cuda.device(device):
-            if view is None:
-                rc = L.hm_decode_frames_to_device_planes(f.h, (C.c_uint32 * n)(*ids), n, C.byref(prm), dests, res, C.byref(failed))
-            else:
-                rc = L.hm_decode_frames_to_device_planes_view(f.h, (C.c_uint32 * n)(*ids), n, C.byref(prm), C.byref(view), dests, res, C.byref(failed))
+            rc = fn(f.h, (C.c_uint32 * n)(*ids), n, C.byref(prm), *steps, dests, res, C.byref(failed))
         if rc < 0:
             detail = f"{L.hm_status_string(rc).decode()}: {L.hm_last_error().decode()}"
             k = failed.value
@@ -902,11 +863,9 @@ def decode_batch_to_planes(files, item_id=0, chroma=None, layout="planar", dtype
                     raise capi.HmError(status, f"{names[tag]}: {detail}")
             for k, data in enumerate(datas):
                 planes = _planes_of([t[k] for t in out], rchroma, lay, alpha, code, msb_aligned, sc, bi)
+                fn, steps = _entry(L, "hm_pipeline_submit_to_device", dict(view=views[k]), planes=True)
                 while True:
-                    if views[k] is None:
-                        rc = capi.check_image(L.hm_pipeline_submit_to_device_planes(pipe, data, len(data), ids[k], k, C.byref(planes)))
-                    else:
-                        rc = capi.check_image(L.hm_pipeline_submit_to_device_planes_view(pipe, data, len(data), ids[k], k, C.byref(views[k]), C.byref(planes)))
+                    rc = capi.check_image(fn(pipe, data, len(data), ids[k], k, *steps, C.byref(planes)))
                     if rc != capi.HM_PIPELINE_FULL:
                         break
                     take()
