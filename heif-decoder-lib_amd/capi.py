@@ -232,6 +232,29 @@ class OverlayInfo(C.Structure):
 
 
 HM_ITEM_OTHER, HM_ITEM_HVC1, HM_ITEM_GRID, HM_ITEM_IDEN, HM_ITEM_IOVL, HM_ITEM_TMAP = 0, 1, 2, 3, 4, 5
+HM_ITEM_UNCI = 6
+
+# uncompressed items (ISO/IEC 23001-17): hm_unci_info
+HM_UNCI_MONO, HM_UNCI_YCBCR, HM_UNCI_RGB = 0, 1, 2
+HM_UNCI_MAX_COMPONENTS = 8
+HM_UNCI_TYPE_MONO, HM_UNCI_TYPE_Y, HM_UNCI_TYPE_CB, HM_UNCI_TYPE_CR, HM_UNCI_TYPE_R, HM_UNCI_TYPE_G, HM_UNCI_TYPE_B, HM_UNCI_TYPE_ALPHA = range(8)
+HM_UNCI_TYPE_PADDED = 12
+HM_UNCI_INTERLEAVE_COMPONENT, HM_UNCI_INTERLEAVE_PIXEL, HM_UNCI_INTERLEAVE_MIXED, HM_UNCI_INTERLEAVE_ROW, HM_UNCI_INTERLEAVE_TILE_COMPONENT = range(5)
+HM_UNCI_SAMPLING_NONE, HM_UNCI_SAMPLING_422, HM_UNCI_SAMPLING_420 = 0, 1, 2
+
+
+class UnciComponent(C.Structure):
+    """hm_unci_component"""
+    _fields_ = [("type", C.c_uint16), ("depth", C.c_uint8), ("align_size", C.c_uint8)]
+
+
+class UnciInfo(C.Structure):
+    """hm_unci_info: what the cmpd and uncC properties of an 'unci' item say, and the byte length its layout needs"""
+    _fields_ = [("width", C.c_int32), ("height", C.c_int32), ("colour_space", C.c_int32), ("n_components", C.c_int32),
+                ("comp", UnciComponent * HM_UNCI_MAX_COMPONENTS), ("sampling", C.c_int32), ("interleave", C.c_int32),
+                ("pixel_size", C.c_uint32), ("row_align", C.c_uint32), ("tile_align", C.c_uint32),
+                ("tile_cols", C.c_uint32), ("tile_rows", C.c_uint32), ("tile_width", C.c_uint32), ("tile_height", C.c_uint32),
+                ("payload_bytes", C.c_uint64)]
 
 
 class SequenceInfo(C.Structure):
@@ -373,6 +396,11 @@ def bind_image(L):
     L.hm_resample_planes_to_tensor.argtypes = [C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, C.POINTER(C.c_void_p * 4), C.POINTER(C.c_int32 * 4),
                                                C.POINTER(DeviceView), C.POINTER(DevicePlanes), C.c_void_p]
     L.hm_plan_planes_view.argtypes = [C.c_void_p, C.c_uint32, C.POINTER(DecodeParams), C.POINTER(DeviceView), C.POINTER(C.c_int32 * 4)]
+    L.hm_file_unci_info.argtypes = [C.c_void_p, C.c_uint32, C.POINTER(UnciInfo)]
+    L.hm_unci_sample_bit.argtypes = [C.POINTER(UnciInfo), C.c_int, C.c_int, C.c_int, C.POINTER(C.c_uint64)]
+    L.hm_unci_payload_bytes.argtypes = [C.POINTER(UnciInfo), C.POINTER(C.c_uint64)]
+    L.hm_unci_unpack.argtypes = [C.POINTER(UnciInfo), C.c_void_p, C.c_size_t, C.POINTER(C.c_int32 * 4), C.POINTER(Planes), C.c_int, C.POINTER(DeviceDest),
+                                 C.c_void_p]
     L.hm_pipeline_pending.argtypes = [C.c_void_p]
     L.hm_pipeline_next.argtypes = [C.c_void_p, C.POINTER(PipelineResult)]
     L.hm_pipeline_release.argtypes = [C.c_void_p, C.POINTER(PipelineResult)]

@@ -1,6 +1,7 @@
 // heif_file.cpp — see heif_file.h.  Written from ISO/IEC 14496-12 and 23008-12 box definitions.
 #include "heif_file.h"
 #include "hm_overlay_plan.h"
+#include "hm_unci_layout.h"
 
 #include <cstring>
 
@@ -104,7 +105,7 @@ std::vector<uint32_t> HeifFile::top_level_images() const
   }
   for (const auto& kv : items_) {
     const Item& it = kv.second;
-    if (it.type != "hvc1" && it.type != "grid" && it.type != "iden" && it.type != "iovl") continue;
+    if (it.type != "hvc1" && it.type != "grid" && it.type != "iden" && it.type != "iovl" && it.type != "unci") continue;
     bool sub = false;
     for (const Ref& r : refs_) {
       if ((r.type == "thmb" || r.type == "auxl") && r.from == it.id) sub = true;
@@ -315,6 +316,45 @@ bool HeifFile::parse_iprp(const uint8_t* p, size_t n, HeifError& err)
           for (int i = 0; i < 8; i++) ip.mdcv_xy[i] = (uint16_t)d.u(2);
           for (int i = 0; i < 2; i++) ip.mdcv_lum[i] = (uint32_t)d.u(4);
         }
+        else if (pb.type == "cmpd") {
+          UncC& u = ip.uncc;
+          u.has_cmpd = true;
+          u.cmpd_types.clear();
+          const uint32_t cnt = (uint32_t)d.u(4);
+          for (uint32_t c = 0; c < cnt && d.ok && d.left(); c++) {
+            const uint16_t type = (uint16_t)d.u(2);
+            if (type >= 0x8000) d.cstr(); // component_type_uri
+            u.cmpd_types.push_back(type);
+          }
+        }
+        else if (pb.type == "uncC") {
+          UncC& u = ip.uncc;
+          u.present = true;
+          u.components.clear();
+          u.version = (int)d.u(1); d.skip(3);
+          u.profile = (uint32_t)d.u(4);
+          if (u.version == 0) {
+            const uint32_t cnt = (uint32_t)d.u(4);
+            for (uint32_t c = 0; c < cnt && d.ok && d.left(); c++) {
+              UncC::Component k;
+              k.index = (uint16_t)d.u(2);
+              k.depth = (uint16_t)(d.u(1) + 1);
+              k.format = (uint8_t)d.u(1);
+              k.align_size = (uint8_t)d.u(1);
+              u.components.push_back(k);
+            }
+            u.sampling = (int)d.u(1);
+            u.interleave = (int)d.u(1);
+            u.block_size = (int)d.u(1);
+            u.flags = (int)d.u(1);
+            u.pixel_size = (uint32_t)d.u(4);
+            u.row_align = (uint32_t)d.u(4);
+            u.tile_align = (uint32_t)d.u(4);
+            u.tile_cols = d.u(4) + 1;
+            u.tile_rows = d.u(4) + 1;
+          }
+        }
+        else if (pb.type == "cmpC" || pb.type == "icbr") ip.uncc.generic_compression = true;
         else if (pb.type == "hvcC") {
           HvcC& h = ip.hvcc;
           h.present = true;
@@ -489,6 +529,87 @@ bool HeifFile::gain_map_info(uint32_t id, GainMapInfo& g, HeifError& err) const
     g.map_min[c] = g.map_min[0]; g.map_max[c] = g.map_max[0]; g.gamma[c] = g.gamma[0];
     g.base_offset[c] = g.base_offset[0]; g.alternate_offset[c] = g.alternate_offset[0];
   }
+  return true;
+}
+
+// uncompressed_image_type_is_supported + get_heif_chroma_uncompressed (codecs/uncompressed_image.cc:40-317), with the depths the
+// device unpack takes (1..16) instead of the reference's 8 and 16
+bool HeifFile::unci_info(uint32_t id, hm_unci_info& info, HeifError& err) const
+{
+  const Item* it = item(id);
+  if (!it || it->type != "unci") { err = {HM_ERR_INVALID_ARG, "item is not an 'unci' image"}; return false; }
+  const UncC& u = it->props.uncc;
+  auto unsupported = [&](const std::string& m) { err = {HM_ERR_UNSUPPORTED, m}; return false; };
+  std::memset(&info, 0, sizeof(info));
+  if (it->props.ispe_width <= 0 || it->props.ispe_height <= 0) { err = {HM_ERR_BITSTREAM, "Missing required ispe box for uncompressed codec"}; return false; }
+  if (!u.present) { err = {HM_ERR_BITSTREAM, "Missing required uncC box for uncompressed codec"}; return false; }
+  if (u.generic_compression) return unsupported("unci: generic compression ('cmpC' / 'icbr') is not supported");
+  if (u.version > 1) return unsupported("uncC version " + std::to_string(u.version) + " is not supported");
+  info.width = it->props.ispe_width; info.height = it->props.ispe_height;
+  if (u.version == 1) { // a profile stands for the whole description
+    static const struct { const char* name; int n; uint16_t types[4]; } profiles[] = {
+      {"rgb3", 3, {HM_UNCI_TYPE_R, HM_UNCI_TYPE_G, HM_UNCI_TYPE_B, 0}},
+      {"rgba", 4, {HM_UNCI_TYPE_R, HM_UNCI_TYPE_G, HM_UNCI_TYPE_B, HM_UNCI_TYPE_ALPHA}},
+      {"abgr", 4, {HM_UNCI_TYPE_ALPHA, HM_UNCI_TYPE_B, HM_UNCI_TYPE_G, HM_UNCI_TYPE_R}}};
+    const char fcc[4] = {(char)(u.profile >> 24), (char)(u.profile >> 16), (char)(u.profile >> 8), (char)u.profile};
+    bool found = false;
+    for (const auto& p : profiles) {
+      if (std::memcmp(fcc, p.name, 4)) continue;
+      found = true;
+      info.n_components = p.n;
+      for (int c = 0; c < p.n; c++) info.comp[c] = {p.types[c], 8, 0};
+    }
+    if (!found) return unsupported("uncC version 1 with the profile '" + std::string(fcc, 4) + "' (rgb3, rgba and abgr are supported)");
+    info.sampling = HM_UNCI_SAMPLING_NONE; info.interleave = HM_UNCI_INTERLEAVE_PIXEL;
+    info.tile_cols = info.tile_rows = 1;
+  }
+  else {
+    if (!u.has_cmpd) { err = {HM_ERR_BITSTREAM, "Missing required cmpd or uncC version 1 box for uncompressed codec"}; return false; }
+    if (u.components.empty() || u.components.size() > HM_UNCI_MAX_COMPONENTS)
+      return unsupported("unci: " + std::to_string(u.components.size()) + " components (1.." + std::to_string((int)HM_UNCI_MAX_COMPONENTS) + " are supported)");
+    info.n_components = (int)u.components.size();
+    for (int c = 0; c < info.n_components; c++) {
+      const UncC::Component& k = u.components[c];
+      if (k.index >= u.cmpd_types.size()) { err = {HM_ERR_BITSTREAM, "unci: component index " + std::to_string(k.index) + " outside the cmpd box"}; return false; }
+      const uint16_t type = u.cmpd_types[k.index];
+      if (type > 7 && type != HM_UNCI_TYPE_PADDED) return unsupported("Uncompressed image with component_type " + std::to_string(type) + " is not implemented yet");
+      if (k.format != 0) return unsupported("Uncompressed image with component_format " + std::to_string(k.format) + " is not implemented yet");
+      if (k.depth > 16) return unsupported("Uncompressed image with component_bit_depth " + std::to_string(k.depth) + " is not supported (1..16 are)");
+      info.comp[c] = {type, (uint8_t)k.depth, k.align_size};
+    }
+    if (u.block_size != 0) return unsupported("Uncompressed block_size of " + std::to_string(u.block_size) + " is not implemented yet");
+    if (u.flags & 0x80) return unsupported("Uncompressed components_little_endian == 1 is not implemented yet");
+    if (u.flags & 0x40) return unsupported("Uncompressed block_pad_lsb == 1 is not implemented yet");
+    if (u.flags & 0x20) return unsupported("Uncompressed block_little_endian == 1 is not implemented yet");
+    if (u.flags & 0x10) return unsupported("Uncompressed block_reversed == 1 is not implemented yet");
+    if (u.sampling > HM_UNCI_SAMPLING_420) return unsupported("Uncompressed sampling_type of " + std::to_string(u.sampling) + " is not implemented yet");
+    if (u.interleave > HM_UNCI_INTERLEAVE_TILE_COMPONENT) return unsupported("Uncompressed interleave_type of " + std::to_string(u.interleave) + " is not implemented yet");
+    info.sampling = u.sampling; info.interleave = u.interleave;
+    info.pixel_size = u.pixel_size; info.row_align = u.row_align; info.tile_align = u.tile_align;
+    if (u.tile_cols > (uint64_t)info.width || u.tile_rows > (uint64_t)info.height) return unsupported("unci: more tiles than pixels");
+    info.tile_cols = (uint32_t)u.tile_cols; info.tile_rows = (uint32_t)u.tile_rows;
+  }
+  if (info.width % info.tile_cols || info.height % info.tile_rows)
+    return unsupported("unci: image size " + std::to_string(info.width) + " x " + std::to_string(info.height) + " is not divisible by the tile counts " +
+                       std::to_string(info.tile_cols) + " x " + std::to_string(info.tile_rows));
+  info.tile_width = info.width / info.tile_cols; info.tile_height = info.height / info.tile_rows;
+  // the colour space from the set of component types, padded ones aside; a type twice has no plane of its own
+  unsigned set = 0;
+  for (int c = 0; c < info.n_components; c++) {
+    const int t = info.comp[c].type;
+    if (t == HM_UNCI_TYPE_PADDED) continue;
+    if (set & (1u << t)) return unsupported("unci: component type " + std::to_string(t) + " appears twice");
+    set |= 1u << t;
+  }
+  const unsigned colour = set & ~(1u << HM_UNCI_TYPE_ALPHA);
+  if (colour == (1u << HM_UNCI_TYPE_MONO)) info.colour_space = HM_UNCI_MONO;
+  else if (colour == ((1u << HM_UNCI_TYPE_Y) | (1u << HM_UNCI_TYPE_CB) | (1u << HM_UNCI_TYPE_CR))) info.colour_space = HM_UNCI_YCBCR;
+  else if (colour == ((1u << HM_UNCI_TYPE_R) | (1u << HM_UNCI_TYPE_G) | (1u << HM_UNCI_TYPE_B))) info.colour_space = HM_UNCI_RGB;
+  else return unsupported("unci: could not determine chroma (the components are neither mono, Y Cb Cr nor R G B)");
+  hm_unci_layout L;
+  const int rc = hm_unci_layout_compute(&info, &L);
+  if (rc) { err = {rc, hm_last_error()}; return false; }
+  info.payload_bytes = L.total_bytes;
   return true;
 }
 

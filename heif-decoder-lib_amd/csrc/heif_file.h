@@ -1,8 +1,8 @@
 // heif_file.h — minimal ISOBMFF / HEIF reader for the decode path (host side).
 // Counterpart of the parts of libheif/file.cc, box.cc and codecs/hevc.cc the hot path needs:
 // item locations (iloc), item infos (iinf), references (iref: dimg/auxl/thmb), properties
-// (ipco/ipma: hvcC, ispe, pixi, colr, irot, imir, clap, auxC, clli, mdcv), primary item (pitm), idat, and the payload of a 'tmap'
-// item (ISO 21496-1 gain map: include/heif_mi355x.h states its layout).
+// (ipco/ipma: hvcC, ispe, pixi, colr, irot, imir, clap, auxC, clli, mdcv, cmpd, uncC), primary item (pitm), idat, and the payload of a 'tmap'
+// item (ISO 21496-1 gain map: include/heif_mi355x.h states its layout).  'unci' items (ISO/IEC 23001-17): libheif/codecs/uncompressed_box.cc.
 // Movie mode (the fork's image sequences): a 'moov' track of HEVC-intra samples, each sample a top-level image
 // (file.cc:474-483, 1154-1244; context.cc:646-700 of the reference).
 #ifndef HM_HEIF_FILE_H
@@ -12,6 +12,8 @@
 #include <map>
 #include <string>
 #include <vector>
+
+#include "heif_mi355x.h"
 
 namespace hm {
 
@@ -43,8 +45,23 @@ struct Transform {
   int32_t voff_n = 0; uint32_t voff_d = 1;
 };
 
+// 'cmpd' + 'uncC' of an 'unci' item as the boxes state them (uncompressed_box.cc:131-279); HeifFile::unci_info judges them
+struct UncC {
+  bool present = false, has_cmpd = false;
+  int version = 0;
+  uint32_t profile = 0;                 // fourcc as a big-endian number
+  std::vector<uint16_t> cmpd_types;     // component_type per cmpd entry
+  struct Component { uint16_t index; uint16_t depth; uint8_t format, align_size; };
+  std::vector<Component> components;
+  int sampling = 0, interleave = 0, block_size = 0, flags = 0;
+  uint32_t pixel_size = 0, row_align = 0, tile_align = 0;
+  uint64_t tile_cols = 1, tile_rows = 1;
+  bool generic_compression = false;     // a 'cmpC' or 'icbr' property is associated
+};
+
 struct ItemProps {
   HvcC hvcc;
+  UncC uncc;
   int ispe_width = 0, ispe_height = 0;
   NclxProfile colr;
   // raw colour profile of a 'colr' box of type 'prof' / 'rICC' (ICC data, passed through untouched: box.cc Box_colr,
@@ -138,6 +155,8 @@ class HeifFile {
   bool gain_map_info(uint32_t id, GainMapInfo& g, HeifError& err) const;
   // the first 'tmap' item whose first 'dimg' reference is `base` (0 if none)
   uint32_t gain_map_of(uint32_t base) const;
+  // an 'unci' item: its cmpd / uncC / ispe judged and turned into the description the layout starts from (hm_unci_layout.h)
+  bool unci_info(uint32_t id, hm_unci_info& info, HeifError& err) const;
   bool is_movie() const { return movie_mode_; }
   const Movie& movie() const { return movie_; }
 

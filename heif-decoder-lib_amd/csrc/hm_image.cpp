@@ -23,6 +23,7 @@
 #include "hm_image_job.h"
 #include "hm_overlay.h"
 #include "hm_planar.h"
+#include "hm_unci_layout.h"
 
 using namespace hm_img;
 
@@ -302,12 +303,33 @@ int hm_file_image_info(const hm_file* f, uint32_t id, hm_image_info* info)
     }
     if (first->type != "hvc1") return hm_fail(HM_ERR_UNSUPPORTED, "item type '%s' under a derived image is not an HEVC image", first->type.c_str());
   }
-  else return hm_fail(HM_ERR_UNSUPPORTED, "item type '%s' is not an HEVC image, a grid or a derived image", it->type.c_str());
-  if (!first->props.hvcc.present) return hm_fail(HM_ERR_BITSTREAM, "image without hvcC");
-  info->bit_depth = first->props.hvcc.bit_depth_luma;
-  info->chroma = first->props.hvcc.chroma_format;
+  else if (it->type == "unci") {
+    hm_unci_info u;
+    if (!f->file.unci_info(id, u, err)) return fail_from(err);
+    info->width = u.width; info->height = u.height;
+    // the depth of the Y component, otherwise the largest of the M / R / G / B depths (get_luma_bits_per_pixel_from_configuration_unci,
+    // codecs/uncompressed_image.cc:320-370)
+    int luma = 0, other = 0;
+    for (int c = 0; c < u.n_components; c++) {
+      const int t = u.comp[c].type, d = u.comp[c].depth;
+      if (t == HM_UNCI_TYPE_Y) luma = std::max(luma, d);
+      else if (t == HM_UNCI_TYPE_MONO || (t >= HM_UNCI_TYPE_R && t <= HM_UNCI_TYPE_B)) other = std::max(other, d);
+      if (t == HM_UNCI_TYPE_ALPHA) info->has_alpha = 1;
+    }
+    info->bit_depth = luma ? luma : other ? other : 8;
+    info->chroma = u.colour_space == HM_UNCI_MONO ? HM_CHROMA_MONO : u.colour_space == HM_UNCI_RGB ? HM_CHROMA_444 :
+                   u.sampling == HM_UNCI_SAMPLING_420 ? HM_CHROMA_420 : u.sampling == HM_UNCI_SAMPLING_422 ? HM_CHROMA_422 : HM_CHROMA_444;
+    info->tile_width = (int32_t)u.tile_width; info->tile_height = (int32_t)u.tile_height;
+  }
+  else return hm_fail(HM_ERR_UNSUPPORTED, "item type '%s' is not an HEVC image, a grid, a derived image or an uncompressed image", it->type.c_str());
+  const bool unci = it->type == "unci";
+  if (!unci) {
+    if (!first->props.hvcc.present) return hm_fail(HM_ERR_BITSTREAM, "image without hvcC");
+    info->bit_depth = first->props.hvcc.bit_depth_luma;
+    info->chroma = first->props.hvcc.chroma_format;
+  }
   info->has_transforms = (it->props.has_irot || it->props.has_imir || it->props.has_clap) ? 1 : 0;
-  info->has_alpha = f->file.alpha_item_of(id) != 0;
+  if (!unci) info->has_alpha = f->file.alpha_item_of(id) != 0;
   if (it->type == "iden" || it->type == "iovl") info->has_alpha = 0; // (context.cc:1370-1373)
   if (!info->has_alpha && it->type == "grid") { // (context.cc:1303-1368: a grid has alpha if one of its tiles has)
     hm::GridInfo g;
@@ -423,7 +445,11 @@ int plan_item(const hm_file* f, uint32_t id, ItemPlan& P, bool self_grid = false
     P.canvas_h = (int)g.height;
     P.cols = g.cols; P.rows = g.rows;
     P.tiles.resize(g.tiles.size());
-    for (size_t i = 0; i < g.tiles.size(); i++) P.tiles[i].id = g.tiles[i];
+    for (size_t i = 0; i < g.tiles.size(); i++) {
+      P.tiles[i].id = g.tiles[i];
+      const hm::Item* ti = f->file.item(g.tiles[i]);
+      if (ti && ti->type == "unci") return hm_fail(HM_ERR_UNSUPPORTED, "grid tile %zu (item %u) is an uncompressed ('unci') item: only coded HEVC images are grid tiles here", i, g.tiles[i]);
+    }
   }
   else if (it->type == "hvc1") {
     P.tiles.resize(1); P.tiles[0].id = id; P.cols = P.rows = 1;
@@ -732,11 +758,34 @@ namespace hm_img {
 // planes_view: the view goes to planar YCbCr (hm_device_planes).  Then the reduction covers out_format 0 alone, the picture as coded -
 // a grid's planes are its tiles' planes side by side, so the sub-grid's planes are the rectangle of the whole grid's -, and the
 // HM_OUT_YCBCR_* chains, whose up- and down-sampling operations read neighbours across tile borders, decode the whole item.
+// ... and for an 'unci' item the sub-grid of its INTERNAL tiles, under the same conditions (a sub-sampled item has even tile sizes, so
+// the sub-grid's origin is even by itself): only those tiles' byte ranges are uploaded and unpacked
+static bool unci_view_subgrid(const hm_file* f, uint32_t id, const hm_decode_params* params, const hm_device_view* v, int32_t t[4], int* x0, int* y0, int* w, int* h,
+                              bool planes_view)
+{
+  const hm::Item* it = f->file.item(id);
+  hm_unci_info u;
+  hm::HeifError err;
+  if (!f->file.unci_info(id, u, err)) return false;
+  t[1] = (int32_t)u.tile_rows; t[3] = (int32_t)u.tile_cols;
+  if (!v || (v->crop_w == 0 && v->crop_h == 0)) return false;
+  if (planes_view ? params->out_format != 0 : (hm_out_is_planar(params->out_format) || params->out_format == 0)) return false;
+  if (!planes_view && u.colour_space == HM_UNCI_YCBCR && params->chroma_upsampling != 0) return false;
+  if (!params->ignore_transformations && !it->props.transforms.empty()) return false;
+  if (v->crop_w <= 0 || v->crop_h <= 0 || v->crop_x < 0 || v->crop_y < 0 || (int64_t)v->crop_x + v->crop_w > u.width || (int64_t)v->crop_y + v->crop_h > u.height) return false;
+  const int tw = (int)u.tile_width, th = (int)u.tile_height;
+  const int c0 = v->crop_x / tw, c1 = (v->crop_x + v->crop_w - 1) / tw, r0 = v->crop_y / th, r1 = (v->crop_y + v->crop_h - 1) / th;
+  t[0] = r0; t[1] = r1 - r0 + 1; t[2] = c0; t[3] = c1 - c0 + 1;
+  *x0 = c0 * tw; *y0 = r0 * th; *w = t[3] * tw; *h = t[1] * th;
+  return true;
+}
+
 bool view_subgrid(const hm_file* f, uint32_t id, const hm_decode_params* params, const hm_device_view* v, int32_t t[4], int* x0, int* y0, int* w, int* h,
                   bool planes_view = false)
 {
   t[0] = 0; t[1] = 1; t[2] = 0; t[3] = 1;
   const hm::Item* it = f->file.item(id);
+  if (it && it->type == "unci") return unci_view_subgrid(f, id, params, v, t, x0, y0, w, h, planes_view);
   if (!it || it->type != "grid") return false;
   hm::GridInfo g;
   hm::HeifError err;
@@ -769,8 +818,73 @@ bool view_subgrid(const hm_file* f, uint32_t id, const hm_decode_params* params,
   return true;
 }
 
+// the depths of an 'unci' item's colour components: *lo / *hi = the smallest and the largest
+static void unci_colour_depths(const hm_unci_info& u, int* lo, int* hi)
+{
+  *lo = 16; *hi = 0;
+  for (int c = 0; c < u.n_components; c++) {
+    const int p = hm_unci_plane_of(u.colour_space, u.comp[c].type);
+    if (p < 0 || p > 2) continue;
+    *lo = std::min<int>(*lo, u.comp[c].depth); *hi = std::max<int>(*hi, u.comp[c].depth);
+  }
+}
+static int unci_alpha_depth(const hm_unci_info& u)
+{
+  for (int c = 0; c < u.n_components; c++)
+    if (u.comp[c].type == HM_UNCI_TYPE_ALPHA) return u.comp[c].depth;
+  return 0;
+}
+
+// An 'unci' item as a job: no coded pictures, and everything the item or the request is refused for - before anything is queued.
+static int plan_unci(DecodeJob& j)
+{
+  const hm_decode_params& prm = j.params;
+  if (!j.allow_unci)
+    return hm_fail(HM_ERR_UNSUPPORTED, "an uncompressed ('unci') item is not supported by the pipeline, batch and sequence calls: decode it with hm_decode_item");
+  hm::HeifError err;
+  hm_unci_info& u = j.unci_info;
+  if (!j.f->file.unci_info(j.id, u, err)) return fail_from(err);
+  if (j.f->file.alpha_item_of(j.id)) return hm_fail(HM_ERR_UNSUPPORTED, "an alpha auxiliary image attached to an 'unci' item is not supported (an alpha component is its alpha plane)");
+  if (j.target.t.gain) return hm_fail(HM_ERR_UNSUPPORTED, "a gain step on an 'unci' item is not supported");
+  int lo, hi;
+  unci_colour_depths(u, &lo, &hi);
+  const int fmt = prm.out_format;
+  const bool planar = hm_out_is_planar(fmt);
+  if (u.colour_space == HM_UNCI_RGB) {
+    if (planar) return hm_fail(HM_ERR_UNSUPPORTED, "an 'unci' item of R G B components has no chroma format to convert to: out_format 0 hands out its R, G, B planes");
+    if (fmt != 0) { // the interleaved targets of a uniform depth; the reference finds no chain for anything else either
+      const bool wide = fmt == HM_OUT_RRGGBB_LE || fmt == HM_OUT_RRGGBBAA_LE, four = fmt == HM_OUT_RGBA || fmt == HM_OUT_RRGGBBAA_LE;
+      const int want = wide ? 16 : 8, ad = unci_alpha_depth(u);
+      if ((!wide && fmt != HM_OUT_RGB && fmt != HM_OUT_RGBA) || lo != want || hi != want || (four && ad && ad != want))
+        return hm_fail_detail(HM_ERR_UNSUPPORTED, HM_DETAIL_NO_COLOUR_CHAIN,
+                              "unci: no colour chain from these R G B component depths to this target (8 bits: HM_OUT_RGB / _RGBA, 16 bits: HM_OUT_RRGGBB_LE / _RRGGBBAA_LE)");
+    }
+    else if (j.target.t.planes && (lo > 8) != (hi > 8)) return hm_fail(HM_ERR_UNSUPPORTED, "unci: R G B planes of byte and word samples do not go to one set of device planes");
+  }
+  else {
+    if (lo != hi) return hm_fail(HM_ERR_UNSUPPORTED, "unci: Y Cb Cr components of different depths (%d, %d) are not supported", lo, hi);
+    const int chroma = u.colour_space == HM_UNCI_MONO ? 0 : u.sampling == HM_UNCI_SAMPLING_420 ? 1 : u.sampling == HM_UNCI_SAMPLING_422 ? 2 : 3;
+    const bool as_decoded = fmt == 0 || (planar && chroma != 0 && chroma == hm_out_planar_chroma(fmt));
+    if (!as_decoded && (hi < 8 || hi > 12))
+      return hm_fail(HM_ERR_UNSUPPORTED, "unci: a %d-bit item is handed out as coded only (out_format 0); the colour chains take 8..12 bits", hi);
+  }
+  ItemPlan& P = j.item[0];
+  P = ItemPlan();
+  P.id = j.id; P.rows = (int)u.tile_rows; P.cols = (int)u.tile_cols; P.canvas_w = u.width; P.canvas_h = u.height;
+  j.n_items = 1; j.has_map = false;
+  j.view_dx = j.view_dy = 0;
+  j.sub_tiles[0] = 0; j.sub_tiles[1] = P.rows; j.sub_tiles[2] = 0; j.sub_tiles[3] = P.cols;
+  int sw = 0, sh = 0;
+  j.unci_sub = j.target.t.view && view_subgrid(j.f, j.id, &j.params, j.target.t.view, j.sub_tiles, &j.view_dx, &j.view_dy, &sw, &sh, j.target.t.planes != nullptr);
+  if (!j.unci_sub) { j.view_dx = j.view_dy = 0; j.sub_tiles[0] = 0; j.sub_tiles[1] = P.rows; j.sub_tiles[2] = 0; j.sub_tiles[3] = P.cols; }
+  return HM_OK;
+}
+
 int job_plan(DecodeJob& j)
 {
+  const hm::Item* it0 = j.f->file.item(j.id);
+  j.unci = it0 && it0->type == "unci";
+  if (j.unci) return plan_unci(j);
   int rc = plan_item(j.f, j.id, j.item[0], j.self_grid);
   if (rc) return rc;
   j.n_items = 1;
@@ -1111,6 +1225,124 @@ int emit_image(const hm_decode_params* params, hipStream_t s, PlanarImage& I, co
   return emit_interleaved(params, s, I, alpha, alpha_bd, dout, alpha_sdr, t, out);
 }
 
+// An 'unci' item: the payload - under a view the byte ranges of the internal tiles in j.sub_tiles - goes to the device and ONE launch
+// of the unpack (unci.hip) leaves planes, or for an R G B item without transformations the interleaved pixels of the target; from there
+// the image is an ordinary PlanarImage (an R G B item: tagged rgb_planes, its pixels in the slot a batch's attached conversion fills).
+static int enqueue_unci(DecodeJob& j, hm_decoded* out)
+{
+  const hm_file* f = j.f;
+  const hm_decode_params* params = &j.params;
+  hipStream_t s = j.s;
+  const hm_unci_info& u = j.unci_info;
+  const hm::Item* it = f->file.item(j.id);
+  PlanarImage& I = j.I;
+  int rc;
+  // ---- the bytes: checked against the layout before anything is queued ----
+  std::vector<uint8_t> payload;
+  hm::HeifError err;
+  if (!f->file.item_data(j.id, payload, err)) return fail_from(err);
+  if (payload.size() < u.payload_bytes)
+    return hm_fail(HM_ERR_BITSTREAM, "unci: the item has %zu bytes of data, its layout needs %llu", payload.size(), (unsigned long long)u.payload_bytes);
+  const int32_t* tiles = j.unci_sub ? j.sub_tiles : nullptr;
+  hm_unci_info sub;
+  std::vector<uint64_t> ranges;
+  if ((rc = hm_unci_subgrid(&u, tiles, &sub)) || (rc = hm_unci_subgrid_ranges(&u, tiles, ranges))) return rc;
+  const size_t n_bytes = (size_t)sub.payload_bytes;
+  if ((rc = require_device())) return rc;
+  j.unci_staging = hm_pool_pinned_alloc(n_bytes ? n_bytes : 1);
+  if (!j.unci_staging) return hm_fail(HM_ERR_NOMEM, "out of memory");
+  size_t at = 0;
+  for (size_t k = 0; k + 1 < ranges.size(); k += 2) { std::memcpy((uint8_t*)j.unci_staging + at, payload.data() + ranges[k], (size_t)ranges[k + 1]); at += (size_t)ranges[k + 1]; }
+  if (at != n_bytes) return hm_fail(HM_ERR_INTERNAL, "unci: the tile ranges hold %zu bytes, the sub-grid's layout %zu", at, n_bytes);
+  if ((rc = j.unci_bytes.alloc((n_bytes + 3) & ~(size_t)3))) return hm_fail(rc, "out of device memory");
+  if ((rc = hm_check_hip(hipMemcpyAsync(j.unci_bytes.p, j.unci_staging, n_bytes, hipMemcpyHostToDevice, s), "H2D unci payload"))) return rc;
+  // ---- the image ----
+  int lo, hi;
+  unci_colour_depths(u, &lo, &hi);
+  const int alpha_depth = unci_alpha_depth(u);
+  const bool rgb = u.colour_space == HM_UNCI_RGB;
+  I.w = sub.width; I.h = sub.height; I.bd = hi; I.rgb_planes = rgb;
+  I.chroma = u.colour_space == HM_UNCI_MONO ? 0 : rgb ? 3 : u.sampling == HM_UNCI_SAMPLING_420 ? 1 : u.sampling == HM_UNCI_SAMPLING_422 ? 2 : 3;
+  I.native = it->props.colr;
+  I.is_grid = !it->props.colr.present; // (an image that carries no nclx: what a grid canvas is to the output rules - no profile handed out, the defaults converted with)
+  const std::vector<hm::Transform> none;
+  const std::vector<hm::Transform>& transforms = params->ignore_transformations ? none : it->props.transforms;
+  const int fmt = params->out_format;
+  const bool pixels = rgb && fmt != 0;
+  const bool wide = fmt == HM_OUT_RRGGBB_LE || fmt == HM_OUT_RRGGBBAA_LE, four = fmt == HM_OUT_RGBA || fmt == HM_OUT_RRGGBBAA_LE;
+  const int obpp = pixels ? hm_out_bytes_per_pixel(fmt) : 0;
+  const bool direct = pixels && transforms.empty(); // the kernel writes the target's pixels itself
+  hm_planes planes;
+  std::memset(&planes, 0, sizeof(planes));
+  if (!direct) {
+    for (int c = 0; c < u.n_components; c++) {
+      const int p = hm_unci_plane_of(u.colour_space, u.comp[c].type);
+      if (p < 0) continue;
+      DevPlane& D = p == 3 ? j.unci_alpha : I.P[p];
+      const bool ch = p == 1 || p == 2;
+      const int pw = ch && (I.chroma == 1 || I.chroma == 2) ? I.w / 2 : I.w, ph = ch && I.chroma == 1 ? I.h / 2 : I.h;
+      if ((rc = alloc_plane(D, pw, ph, u.comp[c].depth > 8 ? 2 : 1))) return hm_fail(rc, "out of device memory");
+      planes.plane[p] = D.mem.p; planes.stride[p] = D.stride;
+    }
+  }
+  hm_device_dest px;
+  std::memset(&px, 0, sizeof(px));
+  int px_stride = 0;
+  if (pixels) {
+    px_stride = hm_plane_stride(I.w, obpp);
+    if (direct) {
+      if ((rc = I.rgb.alloc((size_t)px_stride * mem_rows(I.h)))) return hm_fail(rc, "out of device memory");
+      px.ptr = I.rgb.p; px.len = (uint64_t)px_stride * I.h; px.layout = HM_DEV_LAYOUT_HWC; px.dtype = wide ? HM_DEV_U16 : HM_DEV_U8; px.row_pitch = px_stride;
+    }
+  }
+  if ((rc = hm_unci_unpack(&u, j.unci_bytes.p, n_bytes, tiles, direct ? nullptr : &planes, fmt, direct ? &px : nullptr, s))) return rc;
+  const DevPlane* alpha = alpha_depth && !direct ? &j.unci_alpha : nullptr;
+  if (!transforms.empty()) {
+    // every plane of an R G B item on its own (their depths may differ), the planes of a YCbCr item together, the alpha plane like a luma plane
+    if (rgb) {
+      for (int c = 0; c < 3; c++) {
+        DevPlane one[3];
+        int w = I.w, h = I.h;
+        one[0].mem.swap(I.P[c].mem); one[0].w = I.P[c].w; one[0].h = I.P[c].h; one[0].stride = I.P[c].stride;
+        int depth = 8;
+        for (int k = 0; k < u.n_components; k++) if (hm_unci_plane_of(u.colour_space, u.comp[k].type) == c) depth = u.comp[k].depth;
+        rc = apply_transforms(transforms, one, w, h, 0, depth > 8 ? 16 : 8, s, I.retired);
+        I.P[c].mem.swap(one[0].mem); I.P[c].w = one[0].w; I.P[c].h = one[0].h; I.P[c].stride = one[0].stride;
+        if (rc) return rc;
+        if (c == 2) { I.w = w; I.h = h; }
+      }
+    }
+    else if ((rc = apply_transforms(transforms, I.P, I.w, I.h, I.chroma, I.bd > 8 ? 16 : 8, s, I.retired))) return rc;
+    if (alpha) {
+      DevPlane one[3];
+      int w = sub.width, h = sub.height;
+      one[0].mem.swap(j.unci_alpha.mem); one[0].w = j.unci_alpha.w; one[0].h = j.unci_alpha.h; one[0].stride = j.unci_alpha.stride;
+      rc = apply_transforms(transforms, one, w, h, 0, alpha_depth > 8 ? 16 : 8, s, I.retired);
+      j.unci_alpha.mem.swap(one[0].mem); j.unci_alpha.w = one[0].w; j.unci_alpha.h = one[0].h; j.unci_alpha.stride = one[0].stride;
+      if (rc) return rc;
+    }
+  }
+  if (pixels && !direct) { // through the planes and an interleave
+    px_stride = hm_plane_stride(I.w, obpp);
+    if ((rc = I.rgb.alloc((size_t)px_stride * mem_rows(I.h)))) return hm_fail(rc, "out of device memory");
+    const void* src[4] = {I.P[0].mem.p, I.P[1].mem.p, I.P[2].mem.p, four && alpha ? alpha->mem.p : nullptr};
+    const int32_t stride[4] = {I.P[0].stride, I.P[1].stride, I.P[2].stride, alpha ? alpha->stride : 0};
+    if ((rc = hm_launch_unci_interleave(src, stride, wide, I.w, I.h, four ? 4 : 3, I.rgb.p, px_stride, s))) return rc;
+  }
+  if (pixels) { I.rgb_attached = true; alpha = nullptr; } // (the alpha component is in the pixels already)
+  out->has_alpha = alpha_depth ? 1 : 0;
+  // what the colour ops refuse of an alpha plane (job_enqueue states the reasons)
+  if (alpha && fmt == HM_OUT_RGBA && alpha_depth != 8 && I.bd == 8) return hm_fail(HM_ERR_UNSUPPORTED, "alpha plane of %d bits with an 8-bit image and an RGBA target", alpha_depth);
+  if (alpha && (fmt == HM_OUT_RRGGBBAA_BE || fmt == HM_OUT_RRGGBBAA_LE) && (alpha_depth > 8) != (I.bd > 8))
+    return hm_fail(HM_ERR_UNSUPPORTED, "alpha plane of %d bits with a %d-bit image and an RRGGBBAA target", alpha_depth, I.bd);
+  OutputTarget t = j.target.t;
+  t.scratch = &j.view_scratch;
+  hm_device_view shifted = j.target.view; // (the crop inside the sub-grid that was unpacked)
+  if (t.view && (shifted.crop_w || shifted.crop_h)) { shifted.crop_x -= j.view_dx; shifted.crop_y -= j.view_dy; }
+  if (t.view) t.view = &shifted;
+  return emit_image(params, s, I, alpha, alpha_depth, j.dout, j.alpha_sdr, out, t);
+}
+
 // Everything after the host entropy decode, queued on j.s without waiting: GPU batch(es), transforms, alpha, colour
 // conversion (HeifContext::decode_image_user, context.cc:1516-1600) and the copy to (pinned) host memory.
 int job_enqueue(DecodeJob& j, hm_decoded* out)
@@ -1120,6 +1352,7 @@ int job_enqueue(DecodeJob& j, hm_decoded* out)
   hipStream_t s = j.s;
   std::memset(out, 0, sizeof(*out));
   j.enqueued = true; // from here on the destructor drains the stream before buffers are released
+  if (j.unci) return enqueue_unci(j, out);
   Lap lap;
   PlanarImage &I = j.I, &A = j.A;
   int rc = planar_from_blobs(f, j.item[0], params, s, I, /*attach=*/j.n_items == 1);
@@ -1810,7 +2043,16 @@ int hm_file_item_kind(const hm_file* f, uint32_t id)
   if (it->type == "iden") return HM_ITEM_IDEN;
   if (it->type == "iovl") return HM_ITEM_IOVL;
   if (it->type == "tmap") return HM_ITEM_TMAP;
+  if (it->type == "unci") return HM_ITEM_UNCI;
   return HM_ITEM_OTHER;
+}
+
+int hm_file_unci_info(const hm_file* f, uint32_t id, hm_unci_info* info)
+{
+  if (!f || !info) return hm_fail(HM_ERR_INVALID_ARG, "null argument");
+  if (!f->file.item(id)) return hm_fail(HM_ERR_INVALID_ARG, "no item %u", id);
+  hm::HeifError err;
+  return f->file.unci_info(id, *info, err) ? (int)HM_OK : fail_from(err);
 }
 
 static void gain_params_of(const hm::GainMapInfo& g, hm_gain_params* p)
@@ -1980,7 +2222,9 @@ static int decode_item(const hm_file* f, uint32_t id, const hm_decode_params* pa
 {
   std::memset(out, 0, sizeof(*out)); // (whatever fails below: nothing of an earlier call is left in it)
   if (is_derived_item(f, id)) return decode_derived(f, id, params, target, out);
-  if (!target.view && !target.light && !target.alpha) { // (r06) a grid of more tiles than parsing threads, to interleaved pixels: slab by slab under the entropy decode (decode_grid_cut)
+  const hm::Item* item = f->file.item(id);
+  const bool unci = item && item->type == "unci"; // (a leaf without coded pictures: nothing to cut into slabs)
+  if (!unci && !target.view && !target.light && !target.alpha) { // (r06) a grid of more tiles than parsing threads, to interleaved pixels: slab by slab under the entropy decode (decode_grid_cut)
     bool applicable = false;
     const int prc = decode_grid_cut(f, id, params, nullptr, 1, /*pipelined=*/true, out, &applicable, target.dest);
     if (prc || applicable) return prc;
@@ -1990,6 +2234,7 @@ static int decode_item(const hm_file* f, uint32_t id, const hm_decode_params* pa
   DecodeJob job;
   job.f = f; job.id = id; job.params = *params; job.s = (hipStream_t)params->stream;
   job.target.set(target);
+  job.allow_unci = true;
   int rc = job_plan(job);
   if (rc) return rc;
   // ---- host: entropy-decode every coded picture (CABAC on the CPU, spread over threads like the reference's

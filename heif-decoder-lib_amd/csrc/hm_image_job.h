@@ -80,6 +80,9 @@ struct PlanarImage {
   // where the pictures allow them, else the same kernels as hm_colour_convert) - planar_from_blobs, `attach`
   DevMem rgb;
   bool rgb_attached = false;
+  // the colour-space tag: P[0..2] are R, G, B planes (an 'unci' item of R G B components, each plane at its own depth) - handed out
+  // as decoded, or as the interleaved pixels in `rgb`; no colour chain starts from them
+  bool rgb_planes = false;
 };
 
 struct TilePlan { uint32_t id = 0; int x0 = 0, y0 = 0; };
@@ -192,12 +195,21 @@ struct DecodeJob {
   int few_pictures = 0; // the job's pictures are a whole (small) batch: HM_RECORDS_SPLIT - with few pictures the rows of a picture are
                         // the parallel work, which only the split-chain kernels offer (profiles/r03_class_shape_sweeps.txt)
   bool enqueued = false;
+  // An 'unci' item (ISO/IEC 23001-17): a leaf without coded pictures - job_plan plans zero entropy decodes, job_enqueue uploads the
+  // payload (under a view: the byte ranges of the internal tiles in sub_tiles) and launches the unpack (unci.hip).  allow_unci: the
+  // entry takes such items (hm_decode_item and its device forms; the pipeline, batch and sequence entries refuse them in job_plan).
+  bool allow_unci = false, unci = false, unci_sub = false;
+  hm_unci_info unci_info{};
+  void* unci_staging = nullptr; // pinned: the bytes on their way to the device
+  DevMem unci_bytes;
+  DevPlane unci_alpha;          // the plane of an alpha component
   // everything above is touched by asynchronous work: the stream is drained before any of it is released (the pool may
   // hand a freed block to another thread at once)
   ~DecodeJob()
   {
     if (enqueued) hipStreamSynchronize(s);
     hm_view_scratch_free(&view_scratch);
+    if (unci_staging) hm_pool_pinned_free(unci_staging);
   }
 };
 

@@ -40,6 +40,10 @@ int hm_launch_paste_bytes(const void* in, int in_stride, void* out, int out_stri
                           int is_chroma, hipStream_t s);
 int hm_launch_mirror(const void* in, int in_stride, int w, int h, int horizontal, void* out, int out_stride, hipStream_t s);
 
+// unci.hip: R, G, B [, A] planes of one sample width (wide: 16-bit words) to interleaved pixels; plane[3] NULL: opaque alpha
+int hm_launch_unci_interleave(const void* const plane[4], const int32_t stride[4], int wide, int w, int h, int channels, void* dst, int dst_stride,
+                              hipStream_t s);
+
 // devpool.cpp: size-bucketed cache of device / pinned-host allocations (hipMalloc + hipFree cost more
 // than the kernels of a 12 MP image).  Device blocks: one pool per GPU, served from / returned to the pool of the
 // device that was current at allocation; pinned blocks: portable, one pool

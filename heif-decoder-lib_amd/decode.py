@@ -378,7 +378,8 @@ def decode_to_tensor(data, item_id=0, out_format="rgb", layout="chw", dtype=None
     text), the gain step: the image with its gain map for a display of that headroom - item_id may be the 'tmap' item or its base
     image; with map_item and the explicit parameters any image of the file is the map.  ootf: the display's peak in cd/m2 or
     dict(display_peak=..., gamma=None) beside light= (see the module's text), the OOTF step for an HLG image.  Returns when the pixels
-    are in place."""
+    are in place.  Uncompressed ('unci') items are taken like any image - an R G B item to the targets of its own depth ("rgb" / "rgba"
+    from 8-bit components, "rrggbb_le" / "rrggbbaa_le" from 16-bit ones); under crop= only the internal tiles it touches are unpacked."""
     import torch
     L = capi.image_lib()
     fmt, lay = _out_format(out_format), _layout(layout)
@@ -700,7 +701,8 @@ def decode_to_planes(data, item_id=0, chroma=None, layout="planar", dtype=None, 
     integer dtype for an image whose alpha plane is of the other depth class (8 bits beside more than 8), which is refused otherwise.
     crop: (x, y, w, h) inside the image, x (and y for 4:2:0) even where the chroma is sub-sampled; size: (w, h), the luma size every
     plane is resampled for, each plane as an image of its own; filter: as decode_to_tensor.  Only the tiles of a grid the crop touches
-    are decoded where the picture is taken as coded."""
+    are decoded where the picture is taken as coded.
+    An uncompressed ('unci') item of R G B components, taken as coded (chroma=None), returns (R, G, B[, A]), each H x W."""
     import torch
     L = capi.image_lib()
     fmt, lay = _planes_request(chroma, layout, to_8bit)

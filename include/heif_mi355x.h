@@ -370,7 +370,8 @@ HM_API int      hm_file_top_level_images(const hm_file* f, uint32_t* ids, int ma
 HM_API int      hm_file_image_info(const hm_file* f, uint32_t id, hm_image_info* info);
 /* what kind of item `id` is: HM_ITEM_*, or a negative status (no such item) */
 enum { HM_ITEM_OTHER = 0, HM_ITEM_HVC1 = 1, HM_ITEM_GRID = 2, HM_ITEM_IDEN = 3, HM_ITEM_IOVL = 4,
-       HM_ITEM_TMAP = 5 /* a tone-map derived item (ISO 21496-1 gain map): "Gain" below */ };
+       HM_ITEM_TMAP = 5 /* a tone-map derived item (ISO 21496-1 gain map): "Gain" below */,
+       HM_ITEM_UNCI = 6 /* an uncompressed image (ISO/IEC 23001-17): "Uncompressed items" below */ };
 HM_API int      hm_file_item_kind(const hm_file* f, uint32_t id);
 /* A 'tmap' item: an SDR base image, a gain-map image and the parameters that take the base to its alternate (HDR) rendition.  It
  * has exactly two 'dimg' references, [0] the base image and [1] the gain-map image (anything else: HM_ERR_BITSTREAM).  These
@@ -428,7 +429,8 @@ HM_API uint32_t hm_file_alpha_item(const hm_file* f, uint32_t id);
 HM_API int      hm_file_item_icc(const hm_file* f, uint32_t id, int for_handle, uint32_t* type, const uint8_t** data, size_t* size);
 /* the byte string a decoder plugin gets through push_data for an hvc1 item (free with hm_free) */
 HM_API int      hm_file_item_hevc_data(const hm_file* f, uint32_t id, uint8_t** out, size_t* out_size);
-/* decode an hvc1 image, a grid or a derived item.  Replaces heif_decode_image (heif.cc:1150-1186 ->
+/* decode an hvc1 image, a grid, a derived item or an uncompressed ('unci') item - "Uncompressed items" at the end of this header says
+ * what such an item decodes to.  Replaces heif_decode_image (heif.cc:1150-1186 ->
  * context.cc:1516-1600, 2120-2404, 2542-2675).  Free the result with hm_decoded_free.
  * Derived items: an 'iden' item is its child decoded with the transformation list child ++ iden; an 'iovl' item is composed on the
  * device (its layers clipped to the canvas; layers off the canvas are not decoded) and decodes to HM_OUT_RGB / HM_OUT_RGBA only.
@@ -1105,6 +1107,80 @@ HM_API int hm_resample_planes_to_tensor(int chroma, int bits, int width, int hei
                                         const hm_device_view* view, const hm_device_planes* planes, void* stream);
 /* hm_plan_view for a planar view decode of this item (hm_plan_view's own answers for planar formats stay "the whole grid") */
 HM_API int hm_plan_planes_view(const hm_file* f, uint32_t id, const hm_decode_params* params, const hm_device_view* view, int32_t tiles[4]);
+
+/* ------------------------------------------------------------------------- */
+/* Uncompressed items: ISO/IEC 23001-17 'unci' (cmpd + uncC)                  */
+/* ------------------------------------------------------------------------- */
+
+/* An 'unci' item stores its samples uncompressed, in one of five interleave modes, optionally cut into a grid of equally sized
+ * internal tiles.  hm_file_unci_info hands out what its 'cmpd' and 'uncC' properties say, checked; hm_unci_layout.h states the byte
+ * layout that follows from it (ISO/IEC 23001-17 5.2) in closed form; hm_unci_unpack gathers the samples on the device.
+ * uncC version 1 carries a profile only: 'rgb3' (R, G, B), 'rgba' (R, G, B, A), 'abgr' (A, B, G, R) - 8-bit, pixel-interleaved, one
+ * tile, no padding; no cmpd is needed.
+ * HM_ERR_UNSUPPORTED: block_size != 0, any of the components_little_endian / block_pad_lsb / block_little_endian / block_reversed
+ * flags, a component format other than unsigned, interleave modes above 4 (multi-Y), sampling types above 4:2:0 (4:1:1), a component
+ * type above 7 other than padded (12), mixed interleave without sub-sampling, sub-sampling outside component / mixed interleave,
+ * generic compression ('cmpC' / 'icbr'), an image size that the tile counts do not divide, pixel_size outside pixel interleave,
+ * a component align size below the component's depth, depths above 16, more than HM_UNCI_MAX_COMPONENTS components, a component set
+ * that is neither mono [+ alpha], Y Cb Cr [+ alpha] nor R G B [+ alpha] (padded components aside).
+ * HM_ERR_BITSTREAM: no uncC / cmpd / ispe, a component index outside cmpd, a size that overflows.
+ * Through hm_decode_item and its device forms (not the pipeline, batch and sequence calls; not as a grid tile, a derived item's child,
+ * an auxiliary image or a gain map: HM_ERR_UNSUPPORTED) such an item is a leaf without coded pictures:
+ *   Y Cb Cr / monochrome items of 8..12 bits are ordinary images of their chroma format and depth - transformations, every HM_OUT_*
+ *   chain, ext_dst, device tensors, planes, views and the light / tone / OOTF / alpha steps; an item without a 'colr' nclx converts with
+ *   the defaults of an image that carries none.  Other depths are handed out as coded only (out_format 0), any conversion is
+ *   HM_ERR_UNSUPPORTED.  Y, Cb and Cr of different depths: HM_ERR_UNSUPPORTED.
+ *   R G B items: out_format 0 hands out R, G, B in plane[0..2] and A in alpha, each at its own depth (hm_decoded.bit_depth: the largest;
+ *   chroma: HM_CHROMA_444); HM_OUT_YCBCR_* is refused.  R, G, B (and A, for a four-channel target) all 8 bits deep: HM_OUT_RGB / _RGBA;
+ *   all 16: HM_OUT_RRGGBB_LE / _RRGGBBAA_LE; opaque alpha where the item has none.  Any other combination: HM_ERR_UNSUPPORTED with
+ *   HM_DETAIL_NO_COLOUR_CHAIN.
+ *   An alpha component is the image's alpha plane; an alpha auxiliary image attached to the item is HM_ERR_UNSUPPORTED.
+ *   hm_plan_view / hm_plan_planes_view answer with the sub-grid of INTERNAL tiles a crop touches; only their bytes are uploaded.
+ *   A payload shorter than the layout needs: HM_ERR_BITSTREAM, before anything is queued. */
+enum { HM_UNCI_MONO = 0, HM_UNCI_YCBCR = 1, HM_UNCI_RGB = 2 };
+enum { HM_UNCI_MAX_COMPONENTS = 8 };
+/* component types of ISO/IEC 23001-17 table 1 */
+enum { HM_UNCI_TYPE_MONO = 0, HM_UNCI_TYPE_Y = 1, HM_UNCI_TYPE_CB = 2, HM_UNCI_TYPE_CR = 3, HM_UNCI_TYPE_R = 4, HM_UNCI_TYPE_G = 5,
+       HM_UNCI_TYPE_B = 6, HM_UNCI_TYPE_ALPHA = 7, HM_UNCI_TYPE_PADDED = 12 };
+enum { HM_UNCI_INTERLEAVE_COMPONENT = 0, HM_UNCI_INTERLEAVE_PIXEL = 1, HM_UNCI_INTERLEAVE_MIXED = 2, HM_UNCI_INTERLEAVE_ROW = 3,
+       HM_UNCI_INTERLEAVE_TILE_COMPONENT = 4 };
+enum { HM_UNCI_SAMPLING_NONE = 0, HM_UNCI_SAMPLING_422 = 1, HM_UNCI_SAMPLING_420 = 2 };
+typedef struct hm_unci_component {
+  uint16_t type;         /* HM_UNCI_TYPE_* */
+  uint8_t  depth;        /* 1..16 */
+  uint8_t  align_size;   /* bytes, 0 = packed */
+} hm_unci_component;
+typedef struct hm_unci_info {
+  int32_t  width, height;        /* 'ispe': tile_width * tile_cols, tile_height * tile_rows */
+  int32_t  colour_space;         /* HM_UNCI_MONO / _YCBCR / _RGB */
+  int32_t  n_components;
+  hm_unci_component comp[HM_UNCI_MAX_COMPONENTS]; /* in the order of the uncC box: the order of the data */
+  int32_t  sampling, interleave; /* HM_UNCI_SAMPLING_*, HM_UNCI_INTERLEAVE_* */
+  uint32_t pixel_size, row_align, tile_align;
+  uint32_t tile_cols, tile_rows, tile_width, tile_height;
+  uint64_t payload_bytes;        /* the byte length the layout needs */
+} hm_unci_info;
+HM_API int hm_file_unci_info(const hm_file* f, uint32_t id, hm_unci_info* info);
+/* The closed form of the layout, on the host: the position, in bits from the start of the payload, of the most significant bit of
+ * sample (x, y) of component `component` (x, y in that component's own plane: chroma planes are sub-sampled).  HM_ERR_INVALID_ARG for
+ * a component or a coordinate outside the item; info->payload_bytes is not looked at. */
+HM_API int hm_unci_sample_bit(const hm_unci_info* info, int component, int x, int y, uint64_t* bit);
+/* info->payload_bytes from the other fields (what hm_file_unci_info stores there), or the refusal of a layout */
+HM_API int hm_unci_payload_bytes(const hm_unci_info* info, uint64_t* bytes);
+/* The unpack on its own: the item's payload in device memory (d_bytes, 4-byte aligned, n_bytes long) to planes and / or interleaved
+ * pixels, ONE launch, asynchronous on `stream`.
+ *   tiles: NULL, or first tile row, row count, first tile column, column count of a sub-grid of the internal tiles: d_bytes then holds
+ *   only that sub-grid's byte ranges laid end to end in the order of the layout (modes 0..3: its tiles row by row; mode 4: per
+ *   component, its tiles row by row), and the output has the sub-grid's size.
+ *   out (may be NULL): the mapped components at their own depth - bytes up to 8 bits, little-endian 16-bit words above -, plane[0..2] =
+ *   Y Cb Cr / R G B / Y (mono), plane[3] = alpha (not written when NULL or when the item has none).  Strides are multiples of 4 and
+ *   pointers 4-byte aligned: rows are written in whole dwords, up to 3 bytes of row padding behind the last sample are zeroed.
+ *   interleaved (may be NULL) with out_format: HM_OUT_RGB / _RGBA of an RGB item whose R, G, B (and A) are all 8 bits deep,
+ *   HM_OUT_RRGGBB_LE / _RRGGBBAA_LE where they are all 16; HWC with HM_DEV_U8 / HM_DEV_U16 only.  An item without an alpha component
+ *   gets opaque alpha.  Only width x height pixels are written.  Anything else: HM_ERR_UNSUPPORTED with HM_DETAIL_NO_COLOUR_CHAIN.
+ * n_bytes below what the layout needs: HM_ERR_BITSTREAM, before the launch; nothing behind d_bytes + n_bytes is ever read. */
+HM_API int hm_unci_unpack(const hm_unci_info* info, const void* d_bytes, size_t n_bytes, const int32_t tiles[4], const hm_planes* out,
+                          int out_format, const hm_device_dest* interleaved, void* stream);
 
 #ifdef __cplusplus
 }

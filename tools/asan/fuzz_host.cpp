@@ -9,6 +9,7 @@
 
 #include "heif_file.h"
 #include "heif_mi355x.h"
+#include "hm_unci_layout.h"
 
 static uint64_t rng_state = 0x9E3779B97F4A7C15ull;
 static uint32_t rnd()
@@ -52,12 +53,12 @@ int main(int argc, char** argv)
 {
   int iterations = 2000;
   if (const char* e = std::getenv("HM_FUZZ_ITER")) iterations = std::atoi(e);
-  long heif_ok = 0, heif_err = 0, hevc_ok = 0, hevc_err = 0, stream_ok = 0, stream_err = 0;
+  long unci_ok = 0, heif_ok = 0, heif_err = 0, hevc_ok = 0, hevc_err = 0, stream_ok = 0, stream_err = 0;
   for (int a = 1; a < argc; a++) {
     const std::string path = argv[a];
     const std::vector<uint8_t> seed = slurp(argv[a]);
     if (seed.empty()) { std::fprintf(stderr, "cannot read %s\n", argv[a]); return 2; }
-    const bool is_heif = path.size() > 5 && path.substr(path.size() - 5) == ".heic";
+    const bool is_heif = path.size() > 5 && (path.substr(path.size() - 5) == ".heic" || path.substr(path.size() - 5) == ".heif");
     for (int it = 0; it < iterations; it++) {
       std::vector<uint8_t> b = seed;
       if (it) mutate(b, is_heif ? 4096 : b.size());
@@ -70,6 +71,30 @@ int main(int argc, char** argv)
           const uint32_t id = kv.first;
           const hm::Item* item = &kv.second;
           if (item->type == "grid") { hm::GridInfo g; f.grid_info(id, g, err); }
+          else if (item->type == "unci") {
+            // whatever description survives the checks: no sample of its layout lies outside the length the layout states, and the byte
+            // ranges of its last tile lie inside it too
+            hm_unci_info u;
+            hm_unci_layout L;
+            if (!f.unci_info(id, u, err) || hm_unci_layout_compute(&u, &L) != 0) continue;
+            unci_ok++;
+            for (int c = 0; c < L.n; c++) {
+              const hm_unci_comp_layout& k = L.c[c];
+              const uint32_t xs[2] = {0, k.tw * L.tile_cols - 1}, ys[2] = {0, k.th * L.tile_rows - 1};
+              for (uint32_t x : xs)
+                for (uint32_t y : ys)
+                  if (hm_unci_bit_of(k, L.tile_cols, x, y) + k.depth > L.total_bytes * 8) {
+                    std::fprintf(stderr, "unci: sample (%u, %u) of component %d lies outside the layout's %llu bytes (%s, mutation %d)\n", x, y, c,
+                                 (unsigned long long)L.total_bytes, argv[a], it);
+                    return 4;
+                  }
+            }
+            const int32_t last[4] = {(int32_t)u.tile_rows - 1, 1, (int32_t)u.tile_cols - 1, 1};
+            std::vector<uint64_t> r;
+            if (hm_unci_subgrid_ranges(&u, last, r) != 0) { std::fprintf(stderr, "unci: no ranges for the last tile (%s, mutation %d)\n", argv[a], it); return 4; }
+            for (size_t i = 0; i + 1 < r.size(); i += 2)
+              if (r[i] + r[i + 1] > L.total_bytes) { std::fprintf(stderr, "unci: a tile range ends outside the layout (%s, mutation %d)\n", argv[a], it); return 4; }
+          }
           else if (item->type == "hvc1") {
             std::vector<uint8_t> data;
             if (f.hevc_data(id, data, err)) {
@@ -109,7 +134,7 @@ int main(int argc, char** argv)
       }
     }
   }
-  std::printf("heif ok %ld err %ld | hevc ok %ld err %ld | mutated command streams accepted %ld rejected %ld\n", heif_ok, heif_err, hevc_ok, hevc_err,
+  std::printf("unci layouts checked %ld | heif ok %ld err %ld | hevc ok %ld err %ld | mutated command streams accepted %ld rejected %ld\n", unci_ok, heif_ok, heif_err, hevc_ok, hevc_err,
               stream_ok, stream_err);
   return 0;
 }
