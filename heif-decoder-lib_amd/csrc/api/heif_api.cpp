@@ -17,6 +17,7 @@
 
 #include "heif_mi355x.h"
 #include "heif_mi355x_compat.h"
+#include "hm_plane_geom.h"
 
 namespace {
 
@@ -101,9 +102,7 @@ bool alloc_plane(heif_image* img, heif_channel ch, int w, int h, int bit_depth)
   p->width = w; p->height = h; p->bit_depth = bit_depth;
   const int bpp = interleaved_components(img->chroma) * ((bit_depth + 7) / 8);
   p->stride = hm_plane_stride(w, bpp);
-  int mem_h = (h + 1) & ~1;
-  if (mem_h < 64) mem_h = 64;
-  p->allocated = (uint8_t*)std::malloc((size_t)p->stride * mem_h + 15);
+  p->allocated = (uint8_t*)std::malloc((size_t)p->stride * hm_padded_rows(h) + 15);
   if (!p->allocated) return false;
   p->mem = (uint8_t*)(((uintptr_t)p->allocated + 15) & ~(uintptr_t)15);
   img->planes[ch] = std::move(p);

@@ -19,6 +19,7 @@
 #include "hm_device.h"
 #include "hm_internal.h"
 #include "hm_overlap_plan.h"
+#include "hm_plane_geom.h"
 
 namespace {
 
@@ -116,11 +117,14 @@ size_t mops_bytes(const hm_pic& h) { return (h.flags & HM_PIC_SPLIT_CHAINS) ? (s
 size_t hand_bytes(const hm_pic& h)
 {
   if (!(h.flags & HM_PIC_SPLIT_CHAINS)) return 0;
-  const size_t ctb = (size_t)1 << h.log2_ctb, bps = h.bit_depth_y > 8 ? 2 : 1;
+  const size_t ctb = (size_t)1 << h.log2_ctb, bps = hm_sample_bytes(h.bit_depth_y);
   return (size_t)h.ctb_h * (h.chroma_format == 0 ? 1 : 2) * (size_t)h.ctb_w * ctb * bps; // (one line per CTB row: the finest cut)
 }
 
 } // namespace
+
+// a tile whose origin is not inside a channel of its canvas (hm_place_tile): what every site that refuses it returns
+int hm_tile_origin_refused() { return hm_fail(HM_ERR_INVALID_ARG, "tile origin outside the canvas (invalid grid data)"); }
 
 struct hm_batch {
   std::vector<Item> items;
@@ -395,7 +399,7 @@ static int batch_prepare(hm_batch* b, size_t* blob_bytes_out)
     blob_off[i] = b->items[i].stage_off;
     blob_bytes = b->items[i].stage_off + h.total_bytes;
     work_off[i] = work_bytes;
-    const int bps = h.bit_depth_y > 8 ? 2 : 1;
+    const int bps = hm_sample_bytes(h.bit_depth_y);
     const int sh = h.chroma_format == 1 ? 2 : 1;
     const int swc = h.chroma_format == 3 ? 1 : 2;
     const size_t py = align_up((size_t)h.width * bps, 64), pc = align_up((size_t)(h.width / swc) * bps, 64);
@@ -429,7 +433,7 @@ static int batch_prepare(hm_batch* b, size_t* blob_bytes_out)
       const hm_pic& h = it.hdr;
       hm_dev_pic d;
       std::memset(&d, 0, sizeof(d));
-      const int bps = h.bit_depth_y > 8 ? 2 : 1;
+      const int bps = hm_sample_bytes(h.bit_depth_y);
       const int sh = h.chroma_format == 1 ? 2 : 1;
       const int sw = h.chroma_format == 3 ? 1 : 2;
       const size_t py = align_up((size_t)h.width * bps, 64), pc = align_up((size_t)(h.width / sw) * bps, 64);
@@ -461,26 +465,22 @@ static int batch_prepare(hm_batch* b, size_t* blob_bytes_out)
       d.n_slices = (int32_t)h.n_slices;
       d.slices = (const hm_slice*)(d.blob + h.off_slices);
       d.ctbs = (const hm_ctb*)(d.blob + h.off_ctbs);
-      // destination = tile paste geometry of context.cc:2457-2502
+      // destination = the tile paste: the picture's conformance window, placed channel by channel (hm_plane_geom.h)
       const hm_tile_dest& t = it.dest;
       for (int p = 0; p < (h.chroma_format == 0 ? 1 : 3); p++) { // monochrome: copy_w/h of the chroma planes stay 0
-        int chan_w = t.canvas_width, chan_h = t.canvas_height, cx0 = t.x0, cy0 = t.y0;
-        // the decoder plugin hands libheif the conformance-window crop of the coded picture
-        // (de265_get_image_width/height, decoder_libde265.cc:88-157)
-        int pw = h.width - h.crop_left - h.crop_right, ph = h.height - h.crop_top - h.crop_bottom;
+        int pw = hm_window_w(h), ph = hm_window_h(h);
         d.src_x[p] = h.crop_left; d.src_y[p] = h.crop_top;
         if (pw <= 0 || ph <= 0) return hm_fail(HM_ERR_BITSTREAM, "empty conformance window");
-        if (p > 0) {
-          if (h.chroma_format != 3) { chan_w = (t.canvas_width + 1) / 2; cx0 = (t.x0 + 1) / 2; }
-          if (h.chroma_format == 1) { chan_h = (t.canvas_height + 1) / 2; cy0 = (t.y0 + 1) / 2; }
+        if (p > 0) { // (the window's chroma samples: rounded down, unlike the size of a plane)
           pw /= sw; ph /= sh;
           d.src_x[p] /= sw; d.src_y[p] /= sh;
         }
-        if (chan_w <= cx0 || chan_h <= cy0) return hm_fail(HM_ERR_INVALID_ARG, "tile origin outside the canvas (invalid grid data)");
-        d.copy_w[p] = std::min(pw, chan_w - cx0);
-        d.copy_h[p] = std::min(ph, chan_h - cy0);
+        const hm_tile_place at = hm_place_tile(h.chroma_format, p, t.canvas_width, t.canvas_height, t.x0, t.y0);
+        if (!at.inside) return hm_tile_origin_refused();
+        d.copy_w[p] = hm_copy_extent(pw, at.chan_w, at.x0);
+        d.copy_h[p] = hm_copy_extent(ph, at.chan_h, at.y0);
         d.dst_pitch[p] = t.pitch[p];
-        d.dst[p] = (uint8_t*)t.plane[p] + (size_t)cy0 * t.pitch[p] + (size_t)cx0 * bps;
+        d.dst[p] = (uint8_t*)t.plane[p] + (size_t)at.y0 * t.pitch[p] + (size_t)at.x0 * bps;
       }
       // context.cc:2504-2509: rescale iff the tile carries an nclx with !full_range && matrix != 0
       d.rescale = (t.tile_has_nclx && !t.tile_full_range && t.tile_matrix != 0) ? 1 : 0;
@@ -944,7 +944,7 @@ int hm_batch_algorithmic_bytes(const hm_batch* b, uint64_t* stream_bytes, uint64
   uint64_t sb = 0, pb = 0;
   for (const Item& it : b->items) {
     sb += it.hdr.total_bytes;
-    const uint64_t bps = it.hdr.bit_depth_y > 8 ? 2 : 1;
+    const uint64_t bps = hm_sample_bytes(it.hdr.bit_depth_y);
     const uint64_t luma = (uint64_t)it.hdr.width * it.hdr.height;
     const uint64_t chroma = it.hdr.chroma_format == 0 ? 0 : (it.hdr.chroma_format == 1 ? luma / 4 : (it.hdr.chroma_format == 2 ? luma / 2 : luma));
     pb += bps * (luma + 2 * chroma);

@@ -11,6 +11,7 @@
 
 #include "hm_colour_plan.h"
 #include "hm_internal.h"
+#include "hm_plane_geom.h"
 
 namespace {
 
@@ -273,12 +274,11 @@ int hm_colour_convert(const hm_colour_desc* d, const void* d_y, const void* d_cb
   hipStream_t s = (hipStream_t)stream;
   if (plan.core == HM_CORE_MONO) { // Op_mono_to_RGB24_32 (monochrome.cc:160-273), behind Op_to_sdr_planes for a deeper image
     if (!d_y || !d_out) return hm_fail(HM_ERR_INVALID_ARG, "null device pointer");
-    const int bps = d->bit_depth > 8 ? 2 : 1, obpp = hm_out_bytes_per_pixel(d->out_format);
+    const int bps = hm_sample_bytes(d->bit_depth), obpp = hm_out_bytes_per_pixel(d->out_format);
     if (d->y_stride < d->width * bps || d->out_stride < d->width * obpp) return hm_fail(HM_ERR_INVALID_ARG, "stride smaller than row");
     if (!plan.pre) return hm_launch_mono_to_rgb(d_y, d->y_stride, d_out, d->out_stride, d->width, d->height, obpp, s);
     const int ys1 = hm_plane_stride(d->width, 1);
-    const int r = (d->height + 1) & ~1;
-    uint8_t* tmp = (uint8_t*)hm_pool_device_alloc((size_t)ys1 * (r < 64 ? 64 : r));
+    uint8_t* tmp = (uint8_t*)hm_pool_device_alloc((size_t)ys1 * hm_padded_rows(d->height));
     if (!tmp) return hm_fail(HM_ERR_NOMEM, "8-bit luma plane: out of device memory");
     rc = hm_launch_to_sdr(d_y, d->y_stride, tmp, ys1, d->width, d->height, d->bit_depth, s);
     if (!rc) rc = hm_launch_mono_to_rgb(tmp, ys1, d_out, d->out_stride, d->width, d->height, obpp, s);
@@ -287,17 +287,16 @@ int hm_colour_convert(const hm_colour_desc* d, const void* d_y, const void* d_cb
     return rc ? rc : hm_check_hip(e, "monochrome colour chain");
   }
   if (!d_y || !d_out || (!plan.mono_expand && (!d_cb || !d_cr))) return hm_fail(HM_ERR_INVALID_ARG, "null device pointer");
-  const int bps0 = d->bit_depth > 8 ? 2 : 1;
+  const int bps0 = hm_sample_bytes(d->bit_depth);
   if (plan.mono_expand) { // Op_mono_to_YCbCr420 (monochrome.cc:26-155): Cb = Cr = 128 << (depth - 8) at 4:2:0 size, then a plain 4:2:0 chain
     hm_colour_desc e = *d;
     e.chroma = HM_CHROMA_420;
-    const int ecw = (d->width + 1) / 2, ech = (d->height + 1) / 2;
+    const int ecw = hm_plane_w(HM_CHROMA_420, 1, d->width), ech = hm_plane_h(HM_CHROMA_420, 1, d->height);
     e.cb_stride = e.cr_stride = hm_plane_stride(ecw, bps0);
     // the op's output image carries the profile of a fresh ColorState: the sRGB defaults (colorconversion.cc:452-455,
     // nclx.h:124), whatever the monochrome image declared
     e.has_nclx = 1; e.matrix = 6; e.primaries = 1; e.full_range = 1;
-    const int erows = ((ech + 1) & ~1) < 64 ? 64 : ((ech + 1) & ~1);
-    const size_t cbytes = (size_t)e.cb_stride * erows;
+    const size_t cbytes = (size_t)e.cb_stride * hm_padded_rows(ech);
     uint8_t* neutral = (uint8_t*)hm_pool_device_alloc(cbytes); // one plane serves as Cb and as Cr
     if (!neutral) return hm_fail(HM_ERR_NOMEM, "neutral chroma plane: %zu bytes of device memory", cbytes);
     hipError_t he = bps0 == 1 ? hipMemsetAsync(neutral, 128, cbytes, s) : hipMemsetD16Async((hipDeviceptr_t)neutral, (unsigned short)(128 << (d->bit_depth - 8)), cbytes / 2, s);
@@ -318,22 +317,20 @@ static int convert_planes(const hm_colour_desc* d, const hm_colour_plan& plan, b
                           void* d_out, hipStream_t s)
 {
   int rc;
-  const int bps0 = d->bit_depth > 8 ? 2 : 1;
+  const int bps0 = hm_sample_bytes(d->bit_depth);
   // the vector fast paths need 16 B aligned rows (true for every libheif-style plane)
   if ((d->y_stride % 16) || (d->cb_stride % 8) || (d->cr_stride % 8) || (d->out_stride % 16) ||
       ((uintptr_t)d_y % 16) || ((uintptr_t)d_cb % 16) || ((uintptr_t)d_cr % 16) || ((uintptr_t)d_out % 16))
     return hm_fail(HM_ERR_INVALID_ARG, "planes must be 16-byte aligned with 16-byte multiple strides");
   if (d->y_stride < d->width * bps0 || d->out_stride < d->width * hm_out_bytes_per_pixel(d->out_format))
     return hm_fail(HM_ERR_INVALID_ARG, "stride smaller than row");
-  const int cw = d->chroma == HM_CHROMA_444 ? d->width : (d->width + 1) / 2;
-  const int chh = d->chroma == HM_CHROMA_420 ? (d->height + 1) / 2 : d->height;
+  const int cw = hm_plane_w(d->chroma, 1, d->width), chh = hm_plane_h(d->chroma, 1, d->height);
   if (d->cb_stride < cw * bps0 || d->cr_stride < cw * bps0) return hm_fail(HM_ERR_INVALID_ARG, "stride smaller than row");
 
   // The op that turns YCbCr into RGB sees the image's own nclx only when it is the chain's first step; behind another
   // op it sees the intermediate state's profile (second_step_desc).  Its planes: the image's, or temporaries.
   hm_colour_desc cur = own_profile_gone ? second_step_desc(d) : *d;
   const void* py = d_y; const void* pcb = d_cb; const void* pcr = d_cr;
-  auto rows = [](int h) { const int r = (h + 1) & ~1; return r < 64 ? 64 : r; };
   uint8_t* tmp_depth = nullptr;
   uint8_t* tmp_up = nullptr;
   auto finish = [&](int status, const char* what) {
@@ -346,9 +343,9 @@ static int convert_planes(const hm_colour_desc* d, const hm_colour_plan& plan, b
     return status;
   };
   if (plan.pre) { // Op_to_hdr_planes / Op_to_sdr_planes on Y, Cb, Cr
-    const int nbps = plan.pre_bits > 8 ? 2 : 1;
+    const int nbps = hm_sample_bytes(plan.pre_bits);
     const int ys2 = hm_plane_stride(d->width, nbps), cs2 = hm_plane_stride(cw, nbps);
-    const size_t yb = (size_t)ys2 * rows(d->height), cb = (size_t)cs2 * rows(chh);
+    const size_t yb = (size_t)ys2 * hm_padded_rows(d->height), cb = (size_t)cs2 * hm_padded_rows(chh);
     tmp_depth = (uint8_t*)hm_pool_device_alloc(yb + 2 * cb);
     if (!tmp_depth) return hm_fail(HM_ERR_NOMEM, "%d -> %d bit planes: %zu bytes of device memory", d->bit_depth, plan.pre_bits, yb + 2 * cb);
     auto depth = [&](const void* in, int is, void* out, int os, int w, int h) {
@@ -363,7 +360,7 @@ static int convert_planes(const hm_colour_desc* d, const hm_colour_plan& plan, b
     cur.y_stride = ys2; cur.cb_stride = cur.cr_stride = cs2;
   }
   if (plan.bilinear) { // Op_YCbCr420/422_bilinear_to_YCbCr444 on Cb, Cr
-    const int nbps = cur.bit_depth > 8 ? 2 : 1;
+    const int nbps = hm_sample_bytes(cur.bit_depth);
     const int ts = hm_plane_stride(d->width, nbps);
     const size_t tbytes = (size_t)ts * d->height;
     tmp_up = (uint8_t*)hm_pool_device_alloc(2 * tbytes);

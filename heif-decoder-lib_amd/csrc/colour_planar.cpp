@@ -8,13 +8,9 @@
 #include <cstring>
 
 #include "hm_planar.h"
+#include "hm_plane_geom.h"
 
 namespace {
-
-int rows_of(int h) { const int r = (h + 1) & ~1; return r < 64 ? 64 : r; } // (the row padding of every plane of this library)
-int bps_of(int bits) { return bits > 8 ? 2 : 1; }
-int chroma_w(int chroma, int w) { return chroma == HM_CHROMA_444 ? w : (w + 1) / 2; }
-int chroma_h(int chroma, int h) { return chroma == HM_CHROMA_420 ? (h + 1) / 2 : h; }
 
 // the profile an operation finds on the image it is handed
 struct Seen { int has_nclx, matrix, primaries, full_range; };
@@ -27,13 +23,13 @@ struct Run {
   // where plane c of the image an operation produces goes: the caller's plane if this is the last operation, else a pool block
   int out_plane(hm_planar_image& img, int c, int w, int h, int bits)
   {
-    const int stride = hm_plane_stride(w, bps_of(bits));
+    const int stride = hm_plane_stride(w, hm_sample_bytes(bits));
     if (last && dst && dst->p[c]) {
-      if (dst->stride[c] < w * bps_of(bits)) return hm_fail(HM_ERR_INVALID_ARG, "stride smaller than row");
+      if (dst->stride[c] < w * hm_sample_bytes(bits)) return hm_fail(HM_ERR_INVALID_ARG, "stride smaller than row");
       img.p[c] = dst->p[c]; img.stride[c] = dst->stride[c];
       return HM_OK;
     }
-    const size_t bytes = (size_t)stride * rows_of(h);
+    const size_t bytes = (size_t)stride * hm_padded_rows(h);
     void* p = hm_pool_device_alloc(bytes);
     if (!p) return hm_fail(HM_ERR_NOMEM, "planar colour chain: %zu bytes of device memory", bytes);
     temps->push_back(p);
@@ -88,9 +84,9 @@ int hm_planar_convert(const hm_colour_desc* d, const hm_planar_image* src, const
   else if (!cur.alpha_bits) cur.alpha_bits = cur.bits;
   if (!cur.p[0] || (cur.chroma != HM_CHROMA_MONO && (!cur.p[1] || !cur.p[2]))) return hm_fail(HM_ERR_INVALID_ARG, "null device pointer");
   if ((d->has_alpha != 0) != (cur.p[3] != nullptr)) return hm_fail(HM_ERR_INVALID_ARG, "has_alpha and the alpha plane disagree");
-  if (cur.stride[0] < cur.w * bps_of(cur.bits) ||
-      (cur.chroma != HM_CHROMA_MONO && (cur.stride[1] < chroma_w(cur.chroma, cur.w) * bps_of(cur.bits) || cur.stride[2] < chroma_w(cur.chroma, cur.w) * bps_of(cur.bits))) ||
-      (cur.p[3] && cur.stride[3] < cur.w * bps_of(cur.alpha_bits)))
+  if (cur.stride[0] < cur.w * hm_sample_bytes(cur.bits) ||
+      (cur.chroma != HM_CHROMA_MONO && (cur.stride[1] < hm_plane_w(cur.chroma, 1, cur.w) * hm_sample_bytes(cur.bits) || cur.stride[2] < hm_plane_w(cur.chroma, 1, cur.w) * hm_sample_bytes(cur.bits))) ||
+      (cur.p[3] && cur.stride[3] < cur.w * hm_sample_bytes(cur.alpha_bits)))
     return hm_fail(HM_ERR_INVALID_ARG, "stride smaller than row");
   // the ops that copy the alpha plane copy it as samples of the picture's width (chroma_sampling.cc:223-231, yuv2rgb.cc:248-251),
   // Op_RGB_to_YCbCr refuses another depth (rgb2yuv.cc:111-113): one answer for every chain that does anything
@@ -113,14 +109,14 @@ int hm_planar_convert(const hm_colour_desc* d, const hm_planar_image* src, const
   for (int i = 0; i < n && !rc; i++) {
     run.last = i == n - 1;
     hm_planar_image out = cur;
-    const int bps = bps_of(cur.bits);
+    const int bps = hm_sample_bytes(cur.bits);
     switch (ops[i]) {
       case HM_OP_DROP_ALPHA_PLANE: // alpha.cc:25-52 (never on this path: a planar target keeps the alpha plane)
         out.p[3] = nullptr; out.alpha_bits = 0;
         break;
       case HM_OP_MONO_TO_YCBCR420: { // monochrome.cc:52-156: neutral chroma planes, Y and alpha copied
         out.chroma = HM_CHROMA_420;
-        const int cw = chroma_w(out.chroma, cur.w), chh = chroma_h(out.chroma, cur.h);
+        const int cw = hm_plane_w(out.chroma, 1, cur.w), chh = hm_plane_h(out.chroma, 1, cur.h);
         for (int c = 1; c <= 2 && !rc; c++) {
           if ((rc = run.out_plane(out, c, cw, chh, cur.bits))) break;
           const size_t bytes = (size_t)out.stride[c] * chh;
@@ -137,7 +133,7 @@ int hm_planar_convert(const hm_colour_desc* d, const hm_planar_image* src, const
         if (up ? cur.bits != 8 : cur.bits == 8) { rc = hm_fail(HM_ERR_INTERNAL, "depth change on planes of %d bits", cur.bits); break; }
         for (int c = 0; c < 4 && !rc; c++) {
           if (!cur.p[c]) continue;
-          const int pw = (c == 0 || c == 3) ? cur.w : chroma_w(cur.chroma, cur.w), ph = (c == 0 || c == 3) ? cur.h : chroma_h(cur.chroma, cur.h);
+          const int pw = (c == 0 || c == 3) ? cur.w : hm_plane_w(cur.chroma, 1, cur.w), ph = (c == 0 || c == 3) ? cur.h : hm_plane_h(cur.chroma, 1, cur.h);
           if ((rc = run.out_plane(out, c, pw, ph, nb))) break;
           rc = up ? hm_launch_to_hdr(cur.p[c], cur.stride[c], (void*)out.p[c], out.stride[c], pw, ph, nb, s)
                   : hm_launch_to_sdr(cur.p[c], cur.stride[c], (void*)out.p[c], out.stride[c], pw, ph, cur.bits, s);
@@ -157,7 +153,7 @@ int hm_planar_convert(const hm_colour_desc* d, const hm_planar_image* src, const
       case HM_OP_AVERAGE_420_8: case HM_OP_AVERAGE_420_16: case HM_OP_AVERAGE_422_8: case HM_OP_AVERAGE_422_16: { // chroma_sampling.cc:77-236, 295-434
         const bool v420 = ops[i] == HM_OP_AVERAGE_420_8 || ops[i] == HM_OP_AVERAGE_420_16;
         out.chroma = v420 ? HM_CHROMA_420 : HM_CHROMA_422;
-        const int cw = chroma_w(out.chroma, cur.w), chh = chroma_h(out.chroma, cur.h);
+        const int cw = hm_plane_w(out.chroma, 1, cur.w), chh = hm_plane_h(out.chroma, 1, cur.h);
         if ((rc = run.out_plane(out, 1, cw, chh, cur.bits)) || (rc = run.out_plane(out, 2, cw, chh, cur.bits))) break;
         rc = hm_launch_average_down(cur.bits, v420, cur.p[1], cur.stride[1], cur.p[2], cur.stride[2], (void*)out.p[1], out.stride[1], (void*)out.p[2], out.stride[2],
                                     cur.w, cur.h, s);
@@ -191,7 +187,7 @@ int hm_planar_convert(const hm_colour_desc* d, const hm_planar_image* src, const
         i++;
         run.last = i == n - 1;
         out.chroma = rgb_to_ycbcr_chroma(d);
-        const int cw = chroma_w(out.chroma, cur.w), chh = chroma_h(out.chroma, cur.h);
+        const int cw = hm_plane_w(out.chroma, 1, cur.w), chh = hm_plane_h(out.chroma, 1, cur.h);
         if ((rc = run.out_plane(out, 0, cur.w, cur.h, cur.bits)) || (rc = run.out_plane(out, 1, cw, chh, cur.bits)) || (rc = run.out_plane(out, 2, cw, chh, cur.bits))) break;
         hm_to_ycbcr a;
         std::memset(&a, 0, sizeof(a));
@@ -204,7 +200,7 @@ int hm_planar_convert(const hm_colour_desc* d, const hm_planar_image* src, const
       }
       case HM_OP_RGB_TO_YCBCR_8: case HM_OP_RGB_TO_YCBCR_16: { // rgb2yuv.cc:88-275: the target's chroma format and profile
         out.chroma = rgb_to_ycbcr_chroma(d);
-        const int cw = chroma_w(out.chroma, cur.w), chh = chroma_h(out.chroma, cur.h);
+        const int cw = hm_plane_w(out.chroma, 1, cur.w), chh = hm_plane_h(out.chroma, 1, cur.h);
         if ((rc = run.out_plane(out, 0, cur.w, cur.h, cur.bits)) || (rc = run.out_plane(out, 1, cw, chh, cur.bits)) || (rc = run.out_plane(out, 2, cw, chh, cur.bits))) break;
         hm_to_ycbcr a;
         std::memset(&a, 0, sizeof(a));
@@ -226,8 +222,8 @@ int hm_planar_convert(const hm_colour_desc* d, const hm_planar_image* src, const
       if (!cur.p[c]) continue;
       if (!dst->p[c]) return hm_fail(HM_ERR_INVALID_ARG, "null device pointer (output plane %d)", c);
       if (cur.p[c] == dst->p[c]) continue;
-      const int pw = (c == 0 || c == 3) ? cur.w : chroma_w(cur.chroma, cur.w), ph = (c == 0 || c == 3) ? cur.h : chroma_h(cur.chroma, cur.h);
-      const size_t row = (size_t)pw * bps_of(c == 3 ? cur.alpha_bits : cur.bits);
+      const int pw = (c == 0 || c == 3) ? cur.w : hm_plane_w(cur.chroma, 1, cur.w), ph = (c == 0 || c == 3) ? cur.h : hm_plane_h(cur.chroma, 1, cur.h);
+      const size_t row = (size_t)pw * hm_sample_bytes(c == 3 ? cur.alpha_bits : cur.bits);
       if ((size_t)dst->stride[c] < row) return hm_fail(HM_ERR_INVALID_ARG, "stride smaller than row");
       const hipError_t e = hipMemcpy2DAsync((void*)dst->p[c], (size_t)dst->stride[c], cur.p[c], (size_t)cur.stride[c], row, (size_t)ph, hipMemcpyDeviceToDevice, s);
       if (e != hipSuccess) return hm_check_hip(e, "plane copy");

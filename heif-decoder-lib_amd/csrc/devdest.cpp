@@ -16,6 +16,7 @@
 #include "hm_colour_plan.h"
 #include "hm_devdest.h"
 #include "hm_entry_steps.h"
+#include "hm_plane_geom.h"
 #include "hm_planes_view.h"
 #include "hm_view_batch.h"
 
@@ -175,14 +176,13 @@ int hm_planes_resolve(int chroma, int bits, int w, int h, int alpha_bits, const 
   if (want_alpha && alpha_bits > 0 && (d->dtype == HM_DEV_U8 || d->dtype == HM_DEV_U16) && (alpha_bits > 8) != (d->dtype == HM_DEV_U16))
     return hm_fail(HM_ERR_UNSUPPORTED, "device planes: alpha plane of %d bits with integer dtype %d", alpha_bits, d->dtype);
   p->alpha_bits = want_alpha && alpha_bits > 0 ? alpha_bits : 0;
-  const int cw = chroma == HM_CHROMA_444 ? w : (w + 1) / 2, ch = chroma == HM_CHROMA_420 ? (h + 1) / 2 : h;
   for (int c = 0; c < 4; c++) {
     auto& pl = p->pl[c];
     // (the alpha plane is sized whether it is written or not: hm_device_planes_bytes reports it)
     pl.present = c == 0 || (c == 3 ? want_alpha : chroma != HM_CHROMA_MONO && !(semi && c == 2));
     if (c != 3 && !pl.present) continue;
-    pl.width = c == 0 || c == 3 ? w : cw;
-    pl.height = c == 0 || c == 3 ? h : ch;
+    pl.width = hm_plane_w(chroma, c == 3 ? 0 : c, w);
+    pl.height = hm_plane_h(chroma, c == 3 ? 0 : c, h);
     pl.elems = semi && c == 1 ? 2 * pl.width : pl.width;
     pl.tight = (int64_t)pl.elems * p->elem;
     pl.pitch = d->plane[c].row_pitch ? d->plane[c].row_pitch : pl.tight;
@@ -251,7 +251,7 @@ int hm_planes_write(const hm_device_planes* d, int chroma, int bits, int w, int 
     if (pitches) pitches[c] = p.pl[c].present ? p.pl[c].pitch : 0;
     if (p.pl[c].present) {
       hm_plane_desc& pd = a.pl[c];
-      const int sbits = c == 3 ? p.alpha_bits : bits, sb = sbits > 8 ? 2 : 1;
+      const int sbits = c == 3 ? p.alpha_bits : bits, sb = hm_sample_bytes(sbits);
       const bool pair = semi && c == 1;
       for (int k = c; k <= (pair ? 2 : c); k++) {
         if (!src[k]) return hm_fail(HM_ERR_INVALID_ARG, "device planes: source plane %d is null", k);
@@ -1204,7 +1204,7 @@ static int gain_write(const hm_device_dest* d, const hm_out_plan* p, const uint8
   const bool summed = !vp->crop_only && vp->filter != HM_VIEW_NEAREST, nearest = !vp->crop_only && !summed;
   if (!map || !map->plane || gp.map_w <= 0) return hm_fail(HM_ERR_INTERNAL, "gain: no map for the write");
   if (!p->has_light || p->has_alpha) return hm_fail(HM_ERR_INTERNAL, "gain: light%s alpha%s", p->has_light ? "+" : "-", p->has_alpha ? "+" : "-");
-  const int map_bytes = gp.map_bits > 8 ? 2 : 1;
+  const int map_bytes = hm_sample_bytes(gp.map_bits);
   if ((int64_t)map->stride < (int64_t)gp.map_w * map_bytes) return hm_fail(HM_ERR_INVALID_ARG, "gain: map_stride %d below the bytes of a row", map->stride);
   const LightTables T(&p->lp);
   const size_t table_bytes = T.bytes(), gain_floats = (size_t)gp.nch << gp.map_bits;
@@ -1351,7 +1351,7 @@ static int out_to_tensor(int kind, int out_format, int bits, int w, int h, const
   if (src_stride < w * obpp) return hm_fail(HM_ERR_INVALID_ARG, "src_stride %d below the bytes of a row", src_stride);
   if (obpp >= 6 && (((uintptr_t)src | (unsigned)src_stride) & 1)) return hm_fail(HM_ERR_INVALID_ARG, "16-bit samples at an odd address or stride");
   if (map) {
-    if (map->stride < map_w * (map_bits > 8 ? 2 : 1)) return hm_fail(HM_ERR_INVALID_ARG, "gain: map_stride %d below the bytes of a row", map->stride);
+    if (map->stride < map_w * hm_sample_bytes(map_bits)) return hm_fail(HM_ERR_INVALID_ARG, "gain: map_stride %d below the bytes of a row", map->stride);
     if (map_bits > 8 && (((uintptr_t)map->plane | (unsigned)map->stride) & 1)) return hm_fail(HM_ERR_INVALID_ARG, "gain: 16-bit map samples at an odd address or stride");
   }
   int n_dev = 0;
@@ -1447,7 +1447,7 @@ int planes_view_check(const hm_planes_view_item& f, hm_planes_plan* p)
   for (int c = 0; c < 4; c++) {
     const bool need = c == 0 || (c == 3 ? p->pl[3].present != 0 : f.chroma != HM_CHROMA_MONO);
     if (!need) continue;
-    const int sb = (c == 3 ? p->alpha_bits : f.bits) > 8 ? 2 : 1;
+    const int sb = hm_sample_bytes(c == 3 ? p->alpha_bits : f.bits);
     if (!f.src[c]) return hm_fail(HM_ERR_INVALID_ARG, "device planes: source plane %d is null", c);
     if ((int64_t)f.stride[c] < ((int64_t)f.pv.crop[c][0] + f.pv.crop[c][2]) * sb) return hm_fail(HM_ERR_INVALID_ARG, "device planes: source stride %d of plane %d below the bytes of a row", f.stride[c], c);
     if (sb == 2 && (((uintptr_t)f.src[c] | (unsigned)f.stride[c]) & 1)) return hm_fail(HM_ERR_INVALID_ARG, "16-bit samples at an odd address or stride");
@@ -1473,7 +1473,7 @@ int planes_view_group(const hm_planes_view_item* it, const int* idx, int m, cons
   const bool semi = p.layout == HM_DEV_PLANES_SEMI, nearest = pv.filter == HM_VIEW_NEAREST;
   const int present[4] = {1, p.chroma != HM_CHROMA_MONO, p.chroma != HM_CHROMA_MONO, p.pl[3].present};
   int sb[4];
-  for (int c = 0; c < 4; c++) sb[c] = (c == 3 ? p.alpha_bits : p.bits) > 8 ? 2 : 1;
+  for (int c = 0; c < 4; c++) sb[c] = hm_sample_bytes(c == 3 ? p.alpha_bits : p.bits);
   // the tap tables: one per distinct (n -> m) axis - luma x, luma y, chroma x, chroma y at the most (alpha has luma's)
   struct Axis { int n, m, taps; size_t at; };
   std::vector<Axis> axes;
@@ -1595,7 +1595,7 @@ int hm_planes_view_write(hm_planes_view_item* it, int n, hipStream_t s, hm_view_
       const void* src[4] = {nullptr, nullptr, nullptr, nullptr};
       for (int c = 0; c < 4; c++) {
         const bool need = c == 0 || (c == 3 ? p.pl[3].present != 0 : f.chroma != HM_CHROMA_MONO);
-        if (need) src[c] = plane_origin(f, c, (c == 3 ? p.alpha_bits : f.bits) > 8 ? 2 : 1);
+        if (need) src[c] = plane_origin(f, c, hm_sample_bytes(c == 3 ? p.alpha_bits : f.bits));
       }
       const int rc = hm_planes_write(f.planes, f.chroma, f.bits, f.pv.ow, f.pv.oh, p.alpha_bits, src, f.stride, s, nullptr);
       if (rc) { if (failed) *failed = k; return rc; }

@@ -23,19 +23,38 @@
 #include "hm_image_job.h"
 #include "hm_overlay.h"
 #include "hm_planar.h"
+#include "hm_plane_geom.h"
 #include "hm_unci_layout.h"
 
 using namespace hm_img;
 
 namespace {
 
-int mem_rows(int hgt) { const int r = (hgt + 1) & ~1; return r < 64 ? 64 : r; }
-size_t plane_bytes(const DevPlane& p) { return (size_t)p.stride * mem_rows(p.h); }
+size_t plane_bytes(const DevPlane& p) { return (size_t)p.stride * hm_padded_rows(p.h); }
 int alloc_plane(DevPlane& p, int w, int h, int bps)
 {
   p.w = w; p.h = h; p.stride = hm_plane_stride(w, bps);
   return p.mem.alloc(plane_bytes(p));
 }
+// the planes of a w x h image of `chroma` at `bits`: Y, then Cb and Cr unless it is 4:0:0 (luma only)
+int alloc_planes(DevPlane (&P)[3], int w, int h, int chroma, int bits)
+{
+  int rc = HM_OK;
+  for (int c = 0; c < (chroma == 0 ? 1 : 3) && !rc; c++) rc = alloc_plane(P[c], hm_plane_w(chroma, c, w), hm_plane_h(chroma, c, h), hm_sample_bytes(bits));
+  return rc;
+}
+// a batch picture's destination: planes P as a canvas_w x canvas_h canvas, the picture at its origin; x0, y0 and the nclx fields are the caller's to set
+hm_tile_dest tile_dest_of(const DevPlane (&P)[3], int canvas_w, int canvas_h)
+{
+  hm_tile_dest d;
+  std::memset(&d, 0, sizeof(d));
+  for (int c = 0; c < 3; c++) { d.plane[c] = P[c].mem.p; d.pitch[c] = P[c].stride; }
+  d.canvas_width = canvas_w; d.canvas_height = canvas_h;
+  return d;
+}
+// A buffer that queued work may still use leaves its owner: `retired` keeps it alive until the caller has synchronised the stream
+// (the pool may hand a freed buffer to another thread at once).
+void retire(std::vector<std::unique_ptr<DevMem>>& retired, DevMem& m) { retired.emplace_back(new DevMem()); retired.back()->swap(m); }
 
 int require_device()
 {
@@ -47,7 +66,7 @@ int require_device()
 // a device plane of stride x rows (its padding included) into pinned host memory of its own, queued on `s`
 int plane_to_host(const void* src, int stride, int rows, hipStream_t s, uint8_t** host, int32_t* host_stride)
 {
-  const size_t sz = (size_t)stride * mem_rows(rows);
+  const size_t sz = (size_t)stride * hm_padded_rows(rows);
   *host = (uint8_t*)hm_pool_pinned_alloc(sz);
   if (!*host) return hm_fail(HM_ERR_NOMEM, "out of memory");
   *host_stride = stride;
@@ -69,9 +88,9 @@ hm_colour_desc colour_desc(const hm_decode_params* params, int w, int h, int bd,
   cd.chroma_upsampling = params->chroma_upsampling;
   if (P) { cd.y_stride = P[0].stride; cd.cb_stride = P[1].stride; cd.cr_stride = P[2].stride; }
   else {
-    const int bps = bd > 8 ? 2 : 1;
+    const int bps = hm_sample_bytes(bd);
     cd.y_stride = hm_plane_stride(w, bps);
-    cd.cb_stride = cd.cr_stride = chroma ? hm_plane_stride(chroma == 3 ? w : (w + 1) / 2, bps) : 0;
+    cd.cb_stride = cd.cr_stride = chroma ? hm_plane_stride(hm_plane_w(chroma, 1, w), bps) : 0;
   }
   if (obpp > 0) cd.out_stride = hm_plane_stride(w, obpp);
   return cd;
@@ -79,13 +98,11 @@ hm_colour_desc colour_desc(const hm_decode_params* params, int w, int h, int bd,
 
 // Transformative properties of the item, applied to the decoded YCbCr planes in association order
 // (context.cc:1957-2020): irot -> rotate_ccw, imir -> mirror_inplace, clap -> crop.
-// `retired` keeps the replaced buffers alive until the caller has synchronised the stream (the pool may hand a freed
-// buffer to another thread at once).
+// The replaced buffers go to `retired` (retire).
 int apply_transforms(const std::vector<hm::Transform>& list, DevPlane (&P)[3], int& img_w, int& img_h, int chroma, int bd, hipStream_t s,
                      std::vector<std::unique_ptr<DevMem>>& retired)
 {
-  auto retire = [&](DevMem& m) { retired.emplace_back(new DevMem()); retired.back()->swap(m); };
-  const int bps = bd > 8 ? 2 : 1;
+  const int bps = hm_sample_bytes(bd);
   for (const hm::Transform& t : list) {
     if (t.kind == hm::Transform::Rotate) {
       if (t.angle == 0) continue;
@@ -100,7 +117,7 @@ int apply_transforms(const std::vector<hm::Transform>& list, DevPlane (&P)[3], i
         if (rc) return rc;
         if ((rc = hm_launch_rotate_ccw(bps, t.angle, P[c].mem.p, P[c].stride, P[c].w, P[c].h, n.mem.p, n.stride, s))) return rc;
         P[c].mem.swap(n.mem); P[c].w = n.w; P[c].h = n.h; P[c].stride = n.stride;
-        retire(n.mem);
+        retire(retired, n.mem);
       }
       if (t.angle != 180) { const int tmp = img_w; img_w = img_h; img_h = tmp; }
     }
@@ -113,7 +130,7 @@ int apply_transforms(const std::vector<hm::Transform>& list, DevPlane (&P)[3], i
         if (rc) return rc;
         if ((rc = hm_launch_mirror(P[c].mem.p, P[c].stride, P[c].w, P[c].h, t.horizontal, n.mem.p, n.stride, s))) return rc;
         P[c].mem.swap(n.mem);
-        retire(n.mem);
+        retire(retired, n.mem);
       }
     }
     else {
@@ -144,7 +161,7 @@ int apply_transforms(const std::vector<hm::Transform>& list, DevPlane (&P)[3], i
                                               P[k].stride, (size_t)n.w * bps, n.h, hipMemcpyDeviceToDevice, s);
         if (e != hipSuccess) return hm_check_hip(e, "clap copy");
         P[k].mem.swap(n.mem); P[k].w = n.w; P[k].h = n.h; P[k].stride = n.stride;
-        retire(n.mem);
+        retire(retired, n.mem);
       }
       img_w = right - left + 1;
       img_h = bottom - top + 1;
@@ -405,6 +422,16 @@ void hm_decoded_free(hm_decoded* d)
 
 namespace {
 
+// apply_transforms on ONE plane of a w x h image (an alpha plane, a plane at a depth of its own): as the luma plane of a monochrome image
+int apply_transforms_plane(const std::vector<hm::Transform>& list, DevPlane& p, int& w, int& h, int bd, hipStream_t s, std::vector<std::unique_ptr<DevMem>>& retired)
+{
+  DevPlane one[3];
+  one[0].mem.swap(p.mem); one[0].w = p.w; one[0].h = p.h; one[0].stride = p.stride;
+  const int rc = apply_transforms(list, one, w, h, 0, bd, s, retired);
+  p.mem.swap(one[0].mem); p.w = one[0].w; p.h = one[0].h; p.stride = one[0].stride;
+  return rc;
+}
+
 // HM_TRACE=1: wall-clock laps of the phases on stderr (diagnostics; the environment is read once)
 bool trace_enabled()
 {
@@ -463,9 +490,6 @@ int plan_item(const hm_file* f, uint32_t id, ItemPlan& P, bool self_grid = false
   if (P.canvas_w < 0 || P.canvas_h < 0 || (P.is_grid && (P.canvas_w == 0 || P.canvas_h == 0))) return hm_fail(HM_ERR_BITSTREAM, "bad grid size");
   if (P.tiles.empty()) return hm_fail(HM_ERR_BITSTREAM, "image without coded pictures");
   const size_t nt = P.tiles.size();
-  P.blobs.clear(); P.blobs.resize(nt);
-  P.status.assign(nt, HM_OK);
-  P.messages.assign(nt, std::string());
   // alpha auxiliary images of grid tile items: decode_image_planar attaches them to the tile image (context.cc:2029-2078)
   P.tile_alpha.clear();
   if (P.is_grid && !P.self_grid)
@@ -476,14 +500,40 @@ int plan_item(const hm_file* f, uint32_t id, ItemPlan& P, bool self_grid = false
       if (!ai || ai->type != "hvc1") return hm_fail(HM_ERR_UNSUPPORTED, "alpha image of grid tile %zu is not a coded HEVC image", i);
       P.tile_alpha.push_back({(int)i, a});
     }
-  P.alpha_blobs.clear(); P.alpha_blobs.resize(P.tile_alpha.size());
-  P.alpha_status.assign(P.tile_alpha.size(), HM_OK);
-  P.alpha_messages.assign(P.tile_alpha.size(), std::string());
+  P.reset_slots();
   return HM_OK;
 }
 
-// the failure of a coded picture whose entropy decode (or data) failed, as the image decode reports it
-int tile_failure(const ItemPlan& P, int i) { return hm_fail(P.status[i], "tile %d (item %u): %s", i, P.tiles[i].id, P.messages[i].c_str()); }
+// the failure of a coded picture whose entropy decode (or data) failed, as the image decode reports it: its wording, and the failure
+std::string tile_failure_text(const ItemPlan& P, int i) { return "tile " + std::to_string(i) + " (item " + std::to_string(P.tiles[i].id) + "): " + P.messages[i]; }
+int tile_failure(const ItemPlan& P, int i) { return hm_fail(P.status[i], "%s", tile_failure_text(P, i).c_str()); }
+// HM_WARN_CONCEALED if one of the parsed pictures [first, first + n) of P holds concealed CTBs (damaged slice data, HM_PARSE_CONCEAL)
+int concealed_warning(const ItemPlan& P, int first, int n)
+{
+  for (int i = first; i < first + n; i++)
+    if (P.blobs[i].p && hm_pic_of(P.blobs[i].p)->concealed_ctbs) return HM_WARN_CONCEALED;
+  return 0;
+}
+
+// The grid-wide checks of decode_full_grid_image and decode_and_paste_tile_image, with the reference's messages: tile i of grid P as
+// its item declares it ('ispe'; iw x ih: what tile 0 declares) - context.cc:2299-2359: positions advance by the DECLARED size, all
+// tiles must be equally sized and cover the output ...
+int grid_tile_declared(const hm_file* f, const ItemPlan& P, int i, int iw, int ih)
+{
+  if (P.canvas_w > 32768 || P.canvas_h > 32768) return hm_fail(HM_ERR_BITSTREAM, "Image size exceeds the maximum of 32768x32768 (security limit)");
+  const hm::Item* ti = f->file.item(P.tiles[i].id);
+  const int sw = ti ? ti->props.ispe_width : 0, sh = ti ? ti->props.ispe_height : 0;
+  if (sw < P.canvas_w / P.cols || sh < P.canvas_h / P.rows) return hm_fail(HM_ERR_BITSTREAM, "Grid tiles do not cover whole image");
+  if (sw != iw || sh != ih) return hm_fail(HM_ERR_BITSTREAM, "Grid tiles have different sizes");
+  return HM_OK;
+}
+// ... and a tile's decoded picture h against the canvas, which has the chroma format and depth of the grid's tile 0 (context.cc:2430-2492)
+int grid_tile_picture(const hm_pic* h, int chroma, int bd)
+{
+  if (h->chroma_format != chroma) return hm_fail(HM_ERR_BITSTREAM, "Image tile has different chroma format than combined image");
+  if (h->bit_depth_y != bd) return hm_fail(HM_ERR_BITSTREAM, "Image tile has different pixel depth than combined image");
+  return HM_OK;
+}
 
 // The colour profile a decoded picture carries: what the libde265 plugin attaches from the VUI (decoder_libde265.cc:339-362),
 // unless the item has a 'colr' nclx (context.cc:1844-1852).  heif_nclx_color_profile_set_* (heif.cc:1811-1905) stores
@@ -523,54 +573,42 @@ int planar_from_blobs(const hm_file* f, ItemPlan& P, const hm_decode_params* par
   int canvas_w = P.canvas_w, canvas_h = P.canvas_h;
 
   // ---- geometry ----
-  const hm_pic* h0 = reinterpret_cast<const hm_pic*>(P.blobs[0].p);
+  const hm_pic* h0 = hm_pic_of(P.blobs[0].p);
   const int chroma = h0->chroma_format, bd = h0->bit_depth_y;
-  const int tile_w = h0->width - h0->crop_left - h0->crop_right, tile_h = h0->height - h0->crop_top - h0->crop_bottom;
+  int rc;
   if (is_grid) {
-    // geometry checks and tile origins follow context.cc:2299-2359: positions advance by the tiles'
-    // *declared* ('ispe') size; all tiles must be equally sized and cover the output
+    // the grid-wide checks, tile by tile, and the tile origins: positions advance by the size tile 0 declares
     const hm::Item* t0 = f->file.item(P.tiles[0].id);
     const int iw = t0 ? t0->props.ispe_width : 0, ih = t0 ? t0->props.ispe_height : 0;
-    if (canvas_w > 32768 || canvas_h > 32768) return hm_fail(HM_ERR_BITSTREAM, "Image size exceeds the maximum of 32768x32768 (security limit)");
     for (int i = 0; i < nt; i++) {
-      const hm_pic* h = reinterpret_cast<const hm_pic*>(P.blobs[i].p);
-      const hm::Item* ti = f->file.item(P.tiles[i].id);
       // (a tile item with its own irot / imir / clap: decode_image_planar applies them to the tile image before the
       //  paste, context.cc:1957-2020 - handled below by decoding such a tile to planes of its own)
-      const int sw_ = ti ? ti->props.ispe_width : 0, sh_ = ti ? ti->props.ispe_height : 0;
-      if (sw_ < canvas_w / P.cols || sh_ < canvas_h / P.rows) return hm_fail(HM_ERR_BITSTREAM, "Grid tiles do not cover whole image");
-      if (sw_ != iw || sh_ != ih) return hm_fail(HM_ERR_BITSTREAM, "Grid tiles have different sizes");
-      if (h->chroma_format != chroma) return hm_fail(HM_ERR_BITSTREAM, "Image tile has different chroma format than combined image");
-      if (h->bit_depth_y != bd) return hm_fail(HM_ERR_BITSTREAM, "Image tile has different pixel depth than combined image");
+      if ((rc = grid_tile_declared(f, P, i, iw, ih)) || (rc = grid_tile_picture(hm_pic_of(P.blobs[i].p), chroma, bd))) return rc;
       P.tiles[i].x0 = (i % P.cols) * iw;
       P.tiles[i].y0 = (i / P.cols) * ih;
     }
   }
-  else { canvas_w = tile_w; canvas_h = tile_h; }
-  const int bps = bd > 8 ? 2 : 1;
-  const int cw = chroma == 3 ? canvas_w : (canvas_w + 1) / 2, chh = chroma == 1 ? (canvas_h + 1) / 2 : canvas_h;
+  else { canvas_w = hm_window_w(*h0); canvas_h = hm_window_h(*h0); }
+  const int bps = hm_sample_bytes(bd);
 
   // colour profile of the decoded (native) image and the per-tile paste parameters; every check that can fail on file
   // data comes before the first asynchronous call
   hm::NclxProfile native;
   std::vector<hm::NclxProfile> tile_profile(nt);
   for (int i = 0; i < nt; i++) {
-    const hm_pic* h = reinterpret_cast<const hm_pic*>(P.blobs[i].p);
     const hm::Item* ti = f->file.item(P.tiles[i].id);
     hm::NclxProfile tp;
     int warn = 0;
-    const int prc = picture_profile(h, ti, params->strict_decoding, tp, warn);
+    const int prc = picture_profile(hm_pic_of(P.blobs[i].p), ti, params->strict_decoding, tp, warn);
     if (prc) return prc;
     if (!is_grid) I.warnings |= warn; // (the warnings of grid tiles die with the tile images)
-    if (h->concealed_ctbs) I.warnings |= HM_WARN_CONCEALED; // (damaged slice data, HM_PARSE_CONCEAL: of a grid's tiles too - the image is the caller's)
     if (i == 0) native = tp;
     tile_profile[i] = tp;
   }
+  I.warnings |= concealed_warning(P, 0, nt); // (of a grid's tiles too - the image is the caller's)
 
   DevPlane (&Pl)[3] = I.P;
-  int rc;
-  if ((rc = alloc_plane(Pl[0], canvas_w, canvas_h, bps))) return rc;
-  if (chroma != 0 && ((rc = alloc_plane(Pl[1], cw, chh, bps)) || (rc = alloc_plane(Pl[2], cw, chh, bps)))) return rc; // 4:0:0: luma only
+  if ((rc = alloc_planes(Pl, canvas_w, canvas_h, chroma, bd))) return rc;
   hm_batch* batch = nullptr;
   if ((rc = hm_batch_create(&batch))) return rc;
   I.batch.reset(batch);
@@ -580,37 +618,23 @@ int planar_from_blobs(const hm_file* f, ItemPlan& P, const hm_decode_params* par
   std::vector<std::unique_ptr<OwnTile>>& own = I.own;
   own.clear();
   for (int i = 0; i < nt; i++) {
-    hm_tile_dest d;
-    std::memset(&d, 0, sizeof(d));
     const hm::Item* ti = is_grid && !P.self_grid ? f->file.item(P.tiles[i].id) : nullptr; // (self_grid: the transformations are the item's, below)
     if (ti && !ti->props.transforms.empty() && !params->ignore_transformations) {
-      const hm_pic* h = reinterpret_cast<const hm_pic*>(P.blobs[i].p);
+      const hm_pic* h = hm_pic_of(P.blobs[i].p);
       std::unique_ptr<OwnTile> o(new OwnTile());
       o->index = i;
-      o->w = h->width - h->crop_left - h->crop_right; o->h = h->height - h->crop_top - h->crop_bottom;
-      // (file data is checked before anything is queued: the tile's origin inside the canvas, per channel, context.cc:2466-2483)
-      for (int c = 0; c < (chroma == 0 ? 1 : 3); c++) {
-        int chan_w = canvas_w, chan_h = canvas_h, cx0 = P.tiles[i].x0, cy0 = P.tiles[i].y0;
-        if (c > 0) {
-          if (chroma != 3) { chan_w = (canvas_w + 1) / 2; cx0 = (cx0 + 1) / 2; }
-          if (chroma == 1) { chan_h = (canvas_h + 1) / 2; cy0 = (cy0 + 1) / 2; }
-        }
-        if (chan_w <= cx0 || chan_h <= cy0) return hm_fail(HM_ERR_INVALID_ARG, "tile origin outside the canvas (invalid grid data)");
-      }
-      const int tcw = chroma == 3 ? o->w : (o->w + 1) / 2, tch = chroma == 1 ? (o->h + 1) / 2 : o->h;
-      if ((rc = alloc_plane(o->P[0], o->w, o->h, bps))) return rc;
-      if (chroma != 0 && ((rc = alloc_plane(o->P[1], tcw, tch, bps)) || (rc = alloc_plane(o->P[2], tcw, tch, bps)))) return rc;
-      for (int c = 0; c < 3; c++) { d.plane[c] = o->P[c].mem.p; d.pitch[c] = o->P[c].stride; }
-      d.canvas_width = o->w; d.canvas_height = o->h;
-      d.x0 = d.y0 = 0;
-      d.tile_has_nclx = 0; // (the range rescale happens in the paste)
+      o->w = hm_window_w(*h); o->h = hm_window_h(*h);
+      // (file data is checked before anything is queued: the tile's origin inside the canvas, channel by channel)
+      for (int c = 0; c < (chroma == 0 ? 1 : 3); c++)
+        if (!hm_place_tile(chroma, c, canvas_w, canvas_h, P.tiles[i].x0, P.tiles[i].y0).inside) return hm_tile_origin_refused();
+      if ((rc = alloc_planes(o->P, o->w, o->h, chroma, bd))) return rc;
+      const hm_tile_dest d = tile_dest_of(o->P, o->w, o->h); // (no nclx: the range rescale happens in the paste)
       const int idx = hm_batch_add_trusted(batch, P.blobs[i].p, P.blobs[i].n, &d);
       if (idx < 0) return idx;
       own.push_back(std::move(o));
       continue;
     }
-    for (int c = 0; c < 3; c++) { d.plane[c] = Pl[c].mem.p; d.pitch[c] = Pl[c].stride; }
-    d.canvas_width = canvas_w; d.canvas_height = canvas_h;
+    hm_tile_dest d = tile_dest_of(Pl, canvas_w, canvas_h);
     d.x0 = P.tiles[i].x0; d.y0 = P.tiles[i].y0;
     // the range rescale belongs to the grid paste only (context.cc:2504-2528)
     d.tile_has_nclx = is_grid ? 1 : 0; d.tile_full_range = tile_profile[i].full_range; d.tile_matrix = tile_profile[i].matrix;
@@ -623,29 +647,23 @@ int planar_from_blobs(const hm_file* f, ItemPlan& P, const hm_decode_params* par
   own_alpha.clear();
   I.tile_alpha_bd = 0;
   for (size_t k = 0; k < P.tile_alpha.size(); k++) {
-    const hm_pic* h = reinterpret_cast<const hm_pic*>(P.alpha_blobs[k].p);
+    const hm_pic* h = hm_pic_of(P.alpha_blobs[k].p);
     const int i = P.tile_alpha[k].tile;
     if (I.tile_alpha_bd == 0) I.tile_alpha_bd = h->bit_depth_y;
     else if (h->bit_depth_y != I.tile_alpha_bd) return hm_fail(HM_ERR_BITSTREAM, "Image tile has different pixel depth than combined image (alpha plane)");
-    if (canvas_w <= P.tiles[i].x0 || canvas_h <= P.tiles[i].y0) return hm_fail(HM_ERR_INVALID_ARG, "tile origin outside the canvas (invalid grid data)");
+    if (!hm_place_tile(0, 0, canvas_w, canvas_h, P.tiles[i].x0, P.tiles[i].y0).inside) return hm_tile_origin_refused(); // (pasted like a luma plane)
     std::unique_ptr<OwnTile> o(new OwnTile());
     o->index = (int)k;
     o->chroma = h->chroma_format; o->bd = h->bit_depth_y;
-    o->w = h->width - h->crop_left - h->crop_right; o->h = h->height - h->crop_top - h->crop_bottom;
-    const int abps = o->bd > 8 ? 2 : 1;
-    const int acw = o->chroma == 3 ? o->w : (o->w + 1) / 2, ach = o->chroma == 1 ? (o->h + 1) / 2 : o->h;
-    if ((rc = alloc_plane(o->P[0], o->w, o->h, abps))) return rc;
-    if (o->chroma != 0 && ((rc = alloc_plane(o->P[1], acw, ach, abps)) || (rc = alloc_plane(o->P[2], acw, ach, abps)))) return rc;
-    hm_tile_dest d;
-    std::memset(&d, 0, sizeof(d));
-    for (int c = 0; c < 3; c++) { d.plane[c] = o->P[c].mem.p; d.pitch[c] = o->P[c].stride; }
-    d.canvas_width = o->w; d.canvas_height = o->h;
+    o->w = hm_window_w(*h); o->h = hm_window_h(*h);
+    if ((rc = alloc_planes(o->P, o->w, o->h, o->chroma, o->bd))) return rc;
+    const hm_tile_dest d = tile_dest_of(o->P, o->w, o->h);
     const int idx = hm_batch_add_trusted(batch, P.alpha_blobs[k].p, P.alpha_blobs[k].n, &d);
     if (idx < 0) return idx;
     own_alpha.push_back(std::move(o));
   }
   if (I.tile_alpha_bd) {
-    const int abps = I.tile_alpha_bd > 8 ? 2 : 1;
+    const int abps = hm_sample_bytes(I.tile_alpha_bd);
     if ((rc = alloc_plane(I.tile_alpha, canvas_w, canvas_h, abps))) return rc;
     const size_t bytes = plane_bytes(I.tile_alpha);
     const hipError_t e = abps == 1 ? hipMemsetAsync(I.tile_alpha.mem.p, 0xFF, bytes, s)
@@ -664,7 +682,7 @@ int planar_from_blobs(const hm_file* f, ItemPlan& P, const hm_decode_params* par
     if (obpp > 0) {
       // (exactly the request job_enqueue / run_slab would hand to hm_colour_convert)
       const hm_colour_desc cd = colour_desc(params, canvas_w, canvas_h, bd, chroma, native, is_grid ? 0 : 1, Pl, obpp);
-      if (!I.rgb.alloc((size_t)cd.out_stride * mem_rows(canvas_h))) {
+      if (!I.rgb.alloc((size_t)cd.out_stride * hm_padded_rows(canvas_h))) {
         const void* py = Pl[0].mem.p; const void* pcb = Pl[1].mem.p; const void* pcr = Pl[2].mem.p;
         void* po = I.rgb.p;
         // (a request the colour chain refuses is refused by the caller's own conversion in a moment: not an error here)
@@ -680,20 +698,15 @@ int planar_from_blobs(const hm_file* f, ItemPlan& P, const hm_decode_params* par
     o->w = tw; o->h = th; // (the tile image's size from here on: what an alpha image of the tile is scaled to)
     const hm::NclxProfile& tp = tile_profile[o->index];
     const int rescale = (tp.present && !tp.full_range && tp.matrix != 0) ? 1 : 0; // context.cc:2504-2509
-    const int x0 = P.tiles[o->index].x0, y0 = P.tiles[o->index].y0;
     for (int c = 0; c < 3; c++) {
       if (!o->P[c].mem.p) continue;
-      int chan_w = canvas_w, chan_h = canvas_h, cx0 = x0, cy0 = y0; // context.cc:2466-2483
-      if (c > 0) {
-        if (chroma != 3) { chan_w = (canvas_w + 1) / 2; cx0 = (x0 + 1) / 2; }
-        if (chroma == 1) { chan_h = (canvas_h + 1) / 2; cy0 = (y0 + 1) / 2; }
-      }
-      if (chan_w <= cx0 || chan_h <= cy0) return hm_fail(HM_ERR_INVALID_ARG, "tile origin outside the canvas (invalid grid data)");
-      const int copy_w = std::min(o->P[c].w, chan_w - cx0), copy_h = std::min(o->P[c].h, chan_h - cy0);
-      if ((rc = hm_launch_paste_bytes(o->P[c].mem.p, o->P[c].stride, (uint8_t*)Pl[c].mem.p + (size_t)cy0 * Pl[c].stride + (size_t)cx0 * bps,
+      const hm_tile_place at = hm_place_tile(chroma, c, canvas_w, canvas_h, P.tiles[o->index].x0, P.tiles[o->index].y0);
+      if (!at.inside) return hm_tile_origin_refused();
+      const int copy_w = hm_copy_extent(o->P[c].w, at.chan_w, at.x0), copy_h = hm_copy_extent(o->P[c].h, at.chan_h, at.y0);
+      if ((rc = hm_launch_paste_bytes(o->P[c].mem.p, o->P[c].stride, (uint8_t*)Pl[c].mem.p + (size_t)at.y0 * Pl[c].stride + (size_t)at.x0 * bps,
                                       Pl[c].stride, copy_w * bps, copy_h, rescale, bd, c > 0, s))) return rc;
     }
-    for (int c = 0; c < 3; c++) { I.retired.emplace_back(new DevMem()); I.retired.back()->swap(o->P[c].mem); }
+    for (int c = 0; c < 3; c++) retire(I.retired, o->P[c].mem);
   }
 
   // ---- the tiles' alpha images: the alpha item's own transformations, its Y plane scaled (nearest neighbour) to the
@@ -706,11 +719,11 @@ int planar_from_blobs(const hm_file* f, ItemPlan& P, const hm_decode_params* par
     if (ai && !params->ignore_transformations && !ai->props.transforms.empty())
       if ((rc = apply_transforms(ai->props.transforms, o->P, aw, ah, o->chroma, o->bd, s, I.retired))) return rc;
     // the tile image's size: its picture's conformance window, or what its own transformations made of it
-    const hm_pic* th = reinterpret_cast<const hm_pic*>(P.blobs[ta.tile].p);
-    int tw = th->width - th->crop_left - th->crop_right, thh = th->height - th->crop_top - th->crop_bottom;
+    const hm_pic* th = hm_pic_of(P.blobs[ta.tile].p);
+    int tw = hm_window_w(*th), thh = hm_window_h(*th);
     for (const std::unique_ptr<OwnTile>& t : own)
       if (t->index == ta.tile) { tw = t->w; thh = t->h; }
-    const int abps = o->bd > 8 ? 2 : 1;
+    const int abps = hm_sample_bytes(o->bd);
     const DevPlane* ap = &o->P[0];
     DevPlane scaled;
     if (aw != tw || ah != thh) {
@@ -720,11 +733,11 @@ int planar_from_blobs(const hm_file* f, ItemPlan& P, const hm_decode_params* par
     }
     const hm::NclxProfile& tp = tile_profile[ta.tile];
     const int rescale = (tp.present && !tp.full_range && tp.matrix != 0) ? 1 : 0;
-    const int x0 = P.tiles[ta.tile].x0, y0 = P.tiles[ta.tile].y0;
-    const int copy_w = std::min(tw, canvas_w - x0), copy_h = std::min(thh, canvas_h - y0);
+    const int x0 = P.tiles[ta.tile].x0, y0 = P.tiles[ta.tile].y0; // (inside the canvas: checked above)
+    const int copy_w = hm_copy_extent(tw, canvas_w, x0), copy_h = hm_copy_extent(thh, canvas_h, y0);
     rc = hm_launch_paste_bytes(ap->mem.p, ap->stride, (uint8_t*)I.tile_alpha.mem.p + (size_t)y0 * I.tile_alpha.stride + (size_t)x0 * abps,
                                I.tile_alpha.stride, copy_w * abps, copy_h, rescale, o->bd, 0, s);
-    if (scaled.mem.p) { I.retired.emplace_back(new DevMem()); I.retired.back()->swap(scaled.mem); }
+    if (scaled.mem.p) retire(I.retired, scaled.mem);
     if (rc) return rc;
   }
 
@@ -732,14 +745,8 @@ int planar_from_blobs(const hm_file* f, ItemPlan& P, const hm_decode_params* par
   int img_w = canvas_w, img_h = canvas_h;
   if (!params->ignore_transformations && !it->props.transforms.empty()) {
     if ((rc = apply_transforms(it->props.transforms, Pl, img_w, img_h, chroma, bd, s, I.retired))) return rc;
-    if (I.tile_alpha_bd) { // (the alpha plane is a plane of the canvas: the grid's transformations move it along)
-      DevPlane ap[3];
-      ap[0].mem.swap(I.tile_alpha.mem); ap[0].w = I.tile_alpha.w; ap[0].h = I.tile_alpha.h; ap[0].stride = I.tile_alpha.stride;
-      int aw = canvas_w, ah = canvas_h;
-      rc = apply_transforms(it->props.transforms, ap, aw, ah, 0, I.tile_alpha_bd, s, I.retired);
-      I.tile_alpha.mem.swap(ap[0].mem); I.tile_alpha.w = ap[0].w; I.tile_alpha.h = ap[0].h; I.tile_alpha.stride = ap[0].stride;
-      if (rc) return rc;
-    }
+    int aw = canvas_w, ah = canvas_h; // (the alpha plane is a plane of the canvas: the grid's transformations move it along)
+    if (I.tile_alpha_bd && (rc = apply_transforms_plane(it->props.transforms, I.tile_alpha, aw, ah, I.tile_alpha_bd, s, I.retired))) return rc;
   }
   I.w = img_w; I.h = img_h; I.chroma = chroma; I.bd = bd; I.native = native; I.is_grid = is_grid;
   return HM_OK;
@@ -903,17 +910,8 @@ int job_plan(DecodeJob& j)
     }
   }
   else if (j.target.t.view && view_subgrid(j.f, j.id, &j.params, j.target.t.view, j.sub_tiles, &sx, &sy, &sw, &sh, j.target.t.planes != nullptr)) {
-    // the sub-grid becomes a grid of its own (what a slab is for tile rows): everything behind sees an ordinary smaller grid
-    ItemPlan& P = j.item[0];
     const int32_t* t = j.sub_tiles;
-    std::vector<TilePlan> sub;
-    for (int r = t[0]; r < t[0] + t[1]; r++)
-      for (int c = t[2]; c < t[2] + t[3]; c++) sub.push_back(P.tiles[(size_t)r * P.cols + c]);
-    P.tiles.swap(sub);
-    P.rows = t[1]; P.cols = t[3]; P.canvas_w = sw; P.canvas_h = sh;
-    P.blobs.clear(); P.blobs.resize(P.tiles.size());
-    P.status.assign(P.tiles.size(), HM_OK);
-    P.messages.assign(P.tiles.size(), std::string());
+    j.item[0] = j.item[0].sub_grid(t[0], t[1], t[2], t[3], sw, sh);
     j.view_dx = sx; j.view_dy = sy;
     return HM_OK; // (no alpha image on the item: view_subgrid)
   }
@@ -1115,7 +1113,7 @@ static int emit_planar(const hm_decode_params* params, hipStream_t s, PlanarImag
   out->out_format = params->out_format;
   out->chroma = res.chroma; out->bit_depth = res.bits;
   for (int c = 0; c < 3; c++) { // (planes the chain passed through are copied from where they are: the decoded image's own)
-    const int pw = c == 0 || res.chroma == 3 ? I.w : (I.w + 1) / 2, ph = c == 0 || res.chroma != 1 ? I.h : (I.h + 1) / 2;
+    const int pw = hm_plane_w(res.chroma, c, I.w), ph = hm_plane_h(res.chroma, c, I.h);
     out->plane_width[c] = pw; out->plane_height[c] = ph;
     if (!t.planes && (rc = plane_to_host(res.p[c], res.stride[c], ph, s, &out->plane[c], &out->stride[c]))) return rc;
   }
@@ -1142,7 +1140,7 @@ static int emit_interleaved(const hm_decode_params* params, hipStream_t s, Plana
   cd.has_alpha = alpha ? 1 : 0;
   if (I.rgb_attached && !alpha) dout.swap(I.rgb); // (converted with the batch: planar_from_blobs)
   else {
-    if ((rc = dout.alloc((size_t)cd.out_stride * mem_rows(img_h)))) return rc;
+    if ((rc = dout.alloc((size_t)cd.out_stride * hm_padded_rows(img_h)))) return rc;
     if ((rc = hm_colour_convert(&cd, P[0].mem.p, P[1].mem.p, P[2].mem.p, dout.p, s))) return rc;
   }
   // RGB24 / RRGGBB targets have no alpha: Op_drop_alpha_plane, the colour values do not depend on it.  RGBA: the 8-bit
@@ -1281,7 +1279,7 @@ static int enqueue_unci(DecodeJob& j, hm_decoded* out)
       DevPlane& D = p == 3 ? j.unci_alpha : I.P[p];
       const bool ch = p == 1 || p == 2;
       const int pw = ch && (I.chroma == 1 || I.chroma == 2) ? I.w / 2 : I.w, ph = ch && I.chroma == 1 ? I.h / 2 : I.h;
-      if ((rc = alloc_plane(D, pw, ph, u.comp[c].depth > 8 ? 2 : 1))) return hm_fail(rc, "out of device memory");
+      if ((rc = alloc_plane(D, pw, ph, hm_sample_bytes(u.comp[c].depth)))) return hm_fail(rc, "out of device memory");
       planes.plane[p] = D.mem.p; planes.stride[p] = D.stride;
     }
   }
@@ -1291,7 +1289,7 @@ static int enqueue_unci(DecodeJob& j, hm_decoded* out)
   if (pixels) {
     px_stride = hm_plane_stride(I.w, obpp);
     if (direct) {
-      if ((rc = I.rgb.alloc((size_t)px_stride * mem_rows(I.h)))) return hm_fail(rc, "out of device memory");
+      if ((rc = I.rgb.alloc((size_t)px_stride * hm_padded_rows(I.h)))) return hm_fail(rc, "out of device memory");
       px.ptr = I.rgb.p; px.len = (uint64_t)px_stride * I.h; px.layout = HM_DEV_LAYOUT_HWC; px.dtype = wide ? HM_DEV_U16 : HM_DEV_U8; px.row_pitch = px_stride;
     }
   }
@@ -1301,30 +1299,20 @@ static int enqueue_unci(DecodeJob& j, hm_decoded* out)
     // every plane of an R G B item on its own (their depths may differ), the planes of a YCbCr item together, the alpha plane like a luma plane
     if (rgb) {
       for (int c = 0; c < 3; c++) {
-        DevPlane one[3];
         int w = I.w, h = I.h;
-        one[0].mem.swap(I.P[c].mem); one[0].w = I.P[c].w; one[0].h = I.P[c].h; one[0].stride = I.P[c].stride;
         int depth = 8;
         for (int k = 0; k < u.n_components; k++) if (hm_unci_plane_of(u.colour_space, u.comp[k].type) == c) depth = u.comp[k].depth;
-        rc = apply_transforms(transforms, one, w, h, 0, depth > 8 ? 16 : 8, s, I.retired);
-        I.P[c].mem.swap(one[0].mem); I.P[c].w = one[0].w; I.P[c].h = one[0].h; I.P[c].stride = one[0].stride;
-        if (rc) return rc;
+        if ((rc = apply_transforms_plane(transforms, I.P[c], w, h, depth > 8 ? 16 : 8, s, I.retired))) return rc;
         if (c == 2) { I.w = w; I.h = h; }
       }
     }
     else if ((rc = apply_transforms(transforms, I.P, I.w, I.h, I.chroma, I.bd > 8 ? 16 : 8, s, I.retired))) return rc;
-    if (alpha) {
-      DevPlane one[3];
-      int w = sub.width, h = sub.height;
-      one[0].mem.swap(j.unci_alpha.mem); one[0].w = j.unci_alpha.w; one[0].h = j.unci_alpha.h; one[0].stride = j.unci_alpha.stride;
-      rc = apply_transforms(transforms, one, w, h, 0, alpha_depth > 8 ? 16 : 8, s, I.retired);
-      j.unci_alpha.mem.swap(one[0].mem); j.unci_alpha.w = one[0].w; j.unci_alpha.h = one[0].h; j.unci_alpha.stride = one[0].stride;
-      if (rc) return rc;
-    }
+    int aw = sub.width, ah = sub.height;
+    if (alpha && (rc = apply_transforms_plane(transforms, j.unci_alpha, aw, ah, alpha_depth > 8 ? 16 : 8, s, I.retired))) return rc;
   }
   if (pixels && !direct) { // through the planes and an interleave
     px_stride = hm_plane_stride(I.w, obpp);
-    if ((rc = I.rgb.alloc((size_t)px_stride * mem_rows(I.h)))) return hm_fail(rc, "out of device memory");
+    if ((rc = I.rgb.alloc((size_t)px_stride * hm_padded_rows(I.h)))) return hm_fail(rc, "out of device memory");
     const void* src[4] = {I.P[0].mem.p, I.P[1].mem.p, I.P[2].mem.p, four && alpha ? alpha->mem.p : nullptr};
     const int32_t stride[4] = {I.P[0].stride, I.P[1].stride, I.P[2].stride, alpha ? alpha->stride : 0};
     if ((rc = hm_launch_unci_interleave(src, stride, wide, I.w, I.h, four ? 4 : 3, I.rgb.p, px_stride, s))) return rc;
@@ -1372,8 +1360,8 @@ int job_enqueue(DecodeJob& j, hm_decoded* out)
       return hm_fail(HM_ERR_UNSUPPORTED, "alpha plane of %d bits with a %d-bit image and an RRGGBBAA target", A.bd, I.bd);
     alpha = &A.P[0];
     if (A.w != I.w || A.h != I.h) {
-      if ((rc = alloc_plane(j.alpha_scaled, I.w, I.h, A.bd > 8 ? 2 : 1))) return rc;
-      if ((rc = hm_launch_scale_nn(A.bd > 8 ? 2 : 1, A.P[0].mem.p, A.P[0].stride, A.w, A.h, j.alpha_scaled.mem.p, j.alpha_scaled.stride, I.w, I.h, s))) return rc;
+      if ((rc = alloc_plane(j.alpha_scaled, I.w, I.h, hm_sample_bytes(A.bd)))) return rc;
+      if ((rc = hm_launch_scale_nn(hm_sample_bytes(A.bd), A.P[0].mem.p, A.P[0].stride, A.w, A.h, j.alpha_scaled.mem.p, j.alpha_scaled.stride, I.w, I.h, s))) return rc;
       alpha = &j.alpha_scaled;
     }
     out->has_alpha = 1;
@@ -1732,14 +1720,8 @@ int produce_coded(DerivedRun& R, DerivedNode& n, LayerImage& L)
   if (!n.list.empty()) {
     int w = j.I.w, h = j.I.h;
     if ((rc = apply_transforms(n.list, j.I.P, w, h, j.I.chroma, j.I.bd, s, j.I.retired))) return rc;
-    if (alpha) {
-      DevPlane ap[3];
-      ap[0].mem.swap(alpha->mem); ap[0].w = alpha->w; ap[0].h = alpha->h; ap[0].stride = alpha->stride;
-      int aw = j.I.w, ah = j.I.h;
-      rc = apply_transforms(n.list, ap, aw, ah, 0, 8, s, j.I.retired);
-      alpha->mem.swap(ap[0].mem); alpha->w = ap[0].w; alpha->h = ap[0].h; alpha->stride = ap[0].stride;
-      if (rc) return rc;
-    }
+    int aw = j.I.w, ah = j.I.h;
+    if (alpha && (rc = apply_transforms_plane(n.list, *alpha, aw, ah, 8, s, j.I.retired))) return rc;
     j.I.w = w; j.I.h = h;
   }
   for (int c = 0; c < 3; c++) L.P[c] = j.I.P[c].mem.p ? &j.I.P[c] : nullptr;
@@ -1851,7 +1833,7 @@ int decode_derived(const hm_file* f, uint32_t id, const hm_decode_params* params
       ItemPlan& P = j->item[i];
       for (size_t k = 0; k < P.blobs.size(); k++) {
         if (P.status[k]) return tile_failure(P, (int)k);
-        const hm_pic* h = reinterpret_cast<const hm_pic*>(P.blobs[k].p);
+        const hm_pic* h = hm_pic_of(P.blobs[k].p);
         if (h->bit_depth_y > 8 || h->bit_depth_c > 8)
           return hm_fail(HM_ERR_UNSUPPORTED, "derived images over pictures or alpha planes deeper than 8 bits (item %u: %d bits) are not supported", P.tiles[k].id, (int)h->bit_depth_y);
         if (i == 0 && P.self_grid != (h->chroma_format != 3) && !P.is_grid)
@@ -1859,7 +1841,7 @@ int decode_derived(const hm_file* f, uint32_t id, const hm_decode_params* params
       }
       for (size_t k = 0; k < P.alpha_blobs.size(); k++) {
         if (P.alpha_status[k]) return hm_fail(P.alpha_status[k], "alpha image of tile %d (item %u): %s", P.tile_alpha[k].tile, P.tile_alpha[k].id, P.alpha_messages[k].c_str());
-        if (reinterpret_cast<const hm_pic*>(P.alpha_blobs[k].p)->bit_depth_y > 8)
+        if (hm_pic_of(P.alpha_blobs[k].p)->bit_depth_y > 8)
           return hm_fail(HM_ERR_UNSUPPORTED, "derived images over pictures or alpha planes deeper than 8 bits (item %u) are not supported", P.tile_alpha[k].id);
       }
     }
@@ -1880,7 +1862,7 @@ int decode_derived(const hm_file* f, uint32_t id, const hm_decode_params* params
     int w = (int)root.info.width, h = (int)root.info.height;
     if (root.list.empty()) { // the kernel writes the interleaved result directly
       const int pitch = hm_plane_stride(w, obpp);
-      if ((rc = I.rgb.alloc((size_t)pitch * mem_rows(h)))) return rc;
+      if ((rc = I.rgb.alloc((size_t)pitch * hm_padded_rows(h)))) return rc;
       if ((rc = compose_overlay(R, root, kind, I.rgb.p, pitch))) return rc;
     }
     else { // planes, the transformations (as a 4:4:4 image), then the same kernel with that one opaque layer interleaves
@@ -1888,7 +1870,7 @@ int decode_derived(const hm_file* f, uint32_t id, const hm_decode_params* params
       if ((rc = produce_node(R, root, L))) return rc;
       w = L.w; h = L.h;
       const int pitch = hm_plane_stride(w, obpp);
-      if ((rc = I.rgb.alloc((size_t)pitch * mem_rows(h)))) return rc;
+      if ((rc = I.rgb.alloc((size_t)pitch * hm_padded_rows(h)))) return rc;
       std::vector<hm_overlay_layer> one(1);
       layer_of(L, hm::overlay_clip(w, h, w, h, 0, 0, true), one[0]);
       hm_overlay_job job;
@@ -2448,13 +2430,13 @@ static int decode_sequence(const hm_file* f, const uint32_t* frames, uint32_t fi
     SeqFrame& Fr = *F[k];
     auto fail = [&](int rc) { if (failed_frame) *failed_frame = k; return rc; };
     if (Fr.P.status[0]) return fail(tile_failure(Fr.P, 0));
-    const hm_pic* h = reinterpret_cast<const hm_pic*>(Fr.P.blobs[0].p);
+    const hm_pic* h = hm_pic_of(Fr.P.blobs[0].p);
     PlanarImage& I = Fr.I;
     int warn = 0;
     const int prc = picture_profile(h, f->file.item(Fr.P.id), params->strict_decoding, I.native, warn);
     if (prc) return fail(prc);
-    I.warnings = warn | (h->concealed_ctbs ? HM_WARN_CONCEALED : 0);
-    I.w = h->width - h->crop_left - h->crop_right; I.h = h->height - h->crop_top - h->crop_bottom;
+    I.warnings = warn | concealed_warning(Fr.P, 0, 1);
+    I.w = hm_window_w(*h); I.h = hm_window_h(*h);
     I.chroma = h->chroma_format; I.bd = h->bit_depth_y; I.is_grid = false;
     if (ddests || pdests) { // against the frame's own decoded size and format, the light step against the profile and depth it will report;
                             // planes with the pointers: the check hm_planes_write repeats before its launch
@@ -2527,21 +2509,15 @@ static int decode_sequence(const hm_file* f, const uint32_t* frames, uint32_t fi
     for (int k : G->frames) {
       SeqFrame& Fr = *F[k];
       PlanarImage& I = Fr.I;
-      const int bps = I.bd > 8 ? 2 : 1;
-      const int cw = I.chroma == 3 ? I.w : (I.w + 1) / 2, chh = I.chroma == 1 ? (I.h + 1) / 2 : I.h;
-      if ((rc = alloc_plane(I.P[0], I.w, I.h, bps))) return release_all(rc);
-      if (I.chroma != 0 && ((rc = alloc_plane(I.P[1], cw, chh, bps)) || (rc = alloc_plane(I.P[2], cw, chh, bps)))) return release_all(rc);
-      hm_tile_dest d;
-      std::memset(&d, 0, sizeof(d));
-      for (int c = 0; c < 3; c++) { d.plane[c] = I.P[c].mem.p; d.pitch[c] = I.P[c].stride; }
-      d.canvas_width = I.w; d.canvas_height = I.h;
+      if ((rc = alloc_planes(I.P, I.w, I.h, I.chroma, I.bd))) return release_all(rc);
+      const hm_tile_dest d = tile_dest_of(I.P, I.w, I.h);
       const int idx = hm_batch_add_trusted(b, Fr.P.blobs[0].p, Fr.P.blobs[0].n, &d);
       if (idx < 0) return release_all(idx);
       drain.on = true;
       for (int c = 0; c < 3; c++) // (as hm_decode_item does: the planes' padding leaves the device zeroed)
         if (I.P[c].mem.p) hipMemsetAsync(I.P[c].mem.p, 0, plane_bytes(I.P[c]), s);
       if (G->attach) {
-        if ((rc = I.rgb.alloc((size_t)Fr.cd.out_stride * mem_rows(I.h)))) return release_all(rc);
+        if ((rc = I.rgb.alloc((size_t)Fr.cd.out_stride * hm_padded_rows(I.h)))) return release_all(rc);
         ys.push_back(I.P[0].mem.p); cbs.push_back(I.P[1].mem.p); crs.push_back(I.P[2].mem.p); outs.push_back(I.rgb.p);
       }
     }
@@ -2640,7 +2616,7 @@ void slab_enqueue(const hm_file* f, const hm_decode_params* params, Slab& S, uin
     const hm_colour_desc cd = colour_desc(params, canvas_w, S.h, I.bd, I.chroma, I.native, /*has_nclx=*/0, I.P, obpp);
     if (I.rgb_attached) dout.swap(I.rgb); // (converted with the batch)
     else {
-      rc = dout.alloc((size_t)cd.out_stride * mem_rows(S.h));
+      rc = dout.alloc((size_t)cd.out_stride * hm_padded_rows(S.h));
       if (!rc) rc = hm_colour_convert(&cd, I.P[0].mem.p, I.P[1].mem.p, I.P[2].mem.p, dout.p, S.s);
     }
     if (!rc && ddest) {
@@ -2724,19 +2700,17 @@ static int decode_grid_cut(const hm_file* f, uint32_t id, const hm_decode_params
   const bool cut = (pipelined || n_devices > 1) && plan.is_grid && plan.rows >= 2 && params->out_format != 0 && !hm_out_is_planar(params->out_format) && hm_out_bytes_per_pixel(params->out_format) > 0 &&
                    params->chroma_upsampling == 0 && !f->file.alpha_item_of(id) && plan.tile_alpha.empty() &&
                    (params->ignore_transformations || !it || it->props.transforms.empty()) && ih > 0 && (ih % 2) == 0 && params->stream == nullptr;
-  // The whole-grid geometry checks of the one-device path (planar_from_blobs: context.cc:2299-2359) look at the grid BEFORE it is
-  // cut - a slab only ever sees its own reduced canvas: tiles of one declared size that cover the canvas, and every tile's origin
-  // inside it.  A grid that fails one is not cut: hm_decode_item on the first device reports it exactly as it always does
-  // (r04 advice: such a grid came back HM_OK with rows of the destination never written).
+  // The checks of the declared grid (grid_tile_declared) look at the grid BEFORE it is cut - a slab only ever sees its own reduced
+  // canvas - and so does every tile's luma origin inside the canvas.  A grid that fails one is not cut: hm_decode_item on the first
+  // device reports it exactly as it always does, its message over the one left here (r04 advice: such a grid came back HM_OK with
+  // rows of the destination never written).
   bool geometry_ok = cut;
   if (cut) {
     const int iw = t0->props.ispe_width;
-    if (plan.canvas_w > 32768 || plan.canvas_h > 32768 || iw <= 0) geometry_ok = false;
-    for (size_t i = 0; geometry_ok && i < plan.tiles.size(); i++) {
-      const hm::Item* ti = f->file.item(plan.tiles[i].id);
-      const int sw_ = ti ? ti->props.ispe_width : 0, sh_ = ti ? ti->props.ispe_height : 0;
-      const long x0 = (long)((int)i % plan.cols) * iw, y0 = (long)((int)i / plan.cols) * ih;
-      if (sw_ != iw || sh_ != ih || sw_ < plan.canvas_w / plan.cols || sh_ < plan.canvas_h / plan.rows || x0 >= plan.canvas_w || y0 >= plan.canvas_h) geometry_ok = false;
+    if (iw <= 0) geometry_ok = false;
+    for (int i = 0; geometry_ok && i < nt; i++) {
+      const long x0 = (long)(i % plan.cols) * iw, y0 = (long)(i / plan.cols) * ih;
+      if (grid_tile_declared(f, plan, i, iw, ih) || x0 >= plan.canvas_w || y0 >= plan.canvas_h) geometry_ok = false;
     }
   }
   // pipelined: up to eight slabs of whole tile rows (each costs a batch and a launch of every kernel; what is left behind the
@@ -2774,13 +2748,7 @@ static int decode_grid_cut(const hm_file* f, uint32_t id, const hm_decode_params
     if (y1 <= y0) continue; // (tile rows below the canvas: nothing of them is visible)
     std::unique_ptr<Slab> S(new Slab());
     S->device = dev_of[d]; S->row0 = first[d]; S->rows = count[d]; S->y0 = y0; S->h = y1 - y0;
-    ItemPlan& P = S->P;
-    P.id = plan.id; P.is_grid = true; P.canvas_w = plan.canvas_w; P.canvas_h = S->h; P.cols = plan.cols; P.rows = count[d];
-    const int t_first = first[d] * plan.cols, t_n = count[d] * plan.cols;
-    P.tiles.assign(plan.tiles.begin() + t_first, plan.tiles.begin() + t_first + t_n);
-    P.blobs.resize(t_n);
-    P.status.assign(t_n, HM_OK);
-    P.messages.assign(t_n, std::string());
+    S->P = plan.sub_grid(first[d], count[d], 0, plan.cols, plan.canvas_w, S->h);
     slabs.push_back(std::move(S));
   }
   if (slabs.empty()) return hm_fail(HM_ERR_BITSTREAM, "grid without visible tile rows");
@@ -2808,7 +2776,7 @@ static int decode_grid_cut(const hm_file* f, uint32_t id, const hm_decode_params
   }
   else {
     dst_stride = (size_t)hm_plane_stride(img_w, obpp);
-    out->plane[0] = (uint8_t*)hm_pool_pinned_alloc(dst_stride * mem_rows(img_h)); // (portable pinned memory: every device copies into it)
+    out->plane[0] = (uint8_t*)hm_pool_pinned_alloc(dst_stride * hm_padded_rows(img_h)); // (portable pinned memory: every device copies into it)
     if (!out->plane[0]) return hm_fail(HM_ERR_NOMEM, "out of memory");
     dst = out->plane[0];
   }
@@ -2821,25 +2789,20 @@ static int decode_grid_cut(const hm_file* f, uint32_t id, const hm_decode_params
   auto parse_range = [&](int t_first, int t_n) -> int {
     Crew::for_each(t_n, nthreads, [&](int k, int) { parse_tile(t_first + k); });
     for (int i = t_first; i < t_first + t_n; i++)
-      if (plan.status[i]) return hm_fail(plan.status[i], "tile %d (item %u): %s", i, plan.tiles[i].id, plan.messages[i].c_str());
-    for (int i = t_first; i < t_first + t_n; i++)
-      if (plan.blobs[i].p && reinterpret_cast<const hm_pic*>(plan.blobs[i].p)->concealed_ctbs) tile_warnings |= HM_WARN_CONCEALED;
+      if (plan.status[i]) return tile_failure(plan, i);
+    tile_warnings |= concealed_warning(plan, t_first, t_n);
     return HM_OK;
   };
   // (slabs are taken in order: slab 0 - tile 0 of the grid - first)
   auto take_blobs = [&](Slab& S) -> int {
     const int t_first = S.row0 * plan.cols, t_n = S.rows * plan.cols;
     for (int k = 0; k < t_n; k++) { S.P.blobs[k].p = plan.blobs[t_first + k].p; S.P.blobs[k].n = plan.blobs[t_first + k].n; plan.blobs[t_first + k].p = nullptr; plan.blobs[t_first + k].n = 0; }
-    const hm_pic* h0 = reinterpret_cast<const hm_pic*>(S.P.blobs[0].p);
-    if (&S == slabs[0].get()) { bd = h0->bit_depth_y; chroma = h0->chroma_format; }
-    // every tile against tile 0 of the WHOLE grid, in the order and with the messages of the one-batch decode (planar_from_blobs
-    // compares a slab's tiles with the slab's own first tile only: a later tile row of another depth or chroma format would
-    // otherwise come back HM_OK under slab 0's metadata)
-    for (int k = 0; k < t_n; k++) {
-      const hm_pic* h = reinterpret_cast<const hm_pic*>(S.P.blobs[k].p);
-      if (h->chroma_format != chroma) return hm_fail(HM_ERR_BITSTREAM, "Image tile has different chroma format than combined image");
-      if (h->bit_depth_y != bd) return hm_fail(HM_ERR_BITSTREAM, "Image tile has different pixel depth than combined image");
-    }
+    if (&S == slabs[0].get()) { bd = hm_pic_of(S.P.blobs[0].p)->bit_depth_y; chroma = hm_pic_of(S.P.blobs[0].p)->chroma_format; }
+    // every tile against tile 0 of the WHOLE grid, in the order of the one-batch decode (planar_from_blobs compares a slab's tiles with
+    // the slab's own first tile only: a later tile row of another depth or chroma format would otherwise come back HM_OK under slab 0's
+    // metadata)
+    for (int k = 0; k < t_n; k++)
+      if (const int trc = grid_tile_picture(hm_pic_of(S.P.blobs[k].p), chroma, bd)) return trc;
     return HM_OK;
   };
   auto give_up = [&](int src) { // (whatever is in flight is waited for before the destination goes back)
@@ -2868,10 +2831,9 @@ static int decode_grid_cut(const hm_file* f, uint32_t id, const hm_decode_params
           cv.wait(lk, [&] { return done[k] >= t_n; });
         }
         for (int i = t_first; i < t_first + t_n && !parse_rc; i++)
-          if (plan.status[i]) { parse_rc = plan.status[i]; parse_msg = "tile " + std::to_string(i) + " (item " + std::to_string(plan.tiles[i].id) + "): " + plan.messages[i]; }
+          if (plan.status[i]) { parse_rc = plan.status[i]; parse_msg = tile_failure_text(plan, i); }
         if (parse_rc) return; // (this slab and the ones behind it are not queued)
-        for (int i = t_first; i < t_first + t_n; i++)
-          if (plan.blobs[i].p && reinterpret_cast<const hm_pic*>(plan.blobs[i].p)->concealed_ctbs) tile_warnings |= HM_WARN_CONCEALED;
+        tile_warnings |= concealed_warning(plan, t_first, t_n);
         trace_mark("slab parsed, row", S.row0);
         if (const int trc = take_blobs(S)) { parse_rc = trc; parse_msg = hm_last_error(); return; } // (the slabs in front are drained below)
         slab_enqueue(f, params, S, ddest ? nullptr : dst + (size_t)S.y0 * dst_stride, dst_stride, img_w, ddest, img_h, dest_ready.e);

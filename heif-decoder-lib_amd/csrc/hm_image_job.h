@@ -104,6 +104,27 @@ struct ItemPlan {
   std::vector<Blob> alpha_blobs;
   std::vector<int> alpha_status;
   std::vector<std::string> alpha_messages;
+  // a slot (command stream, status, message) per coded picture of `tiles` and of `tile_alpha`, empty: nothing parsed yet
+  void reset_slots()
+  {
+    blobs.clear(); blobs.resize(tiles.size());
+    status.assign(tiles.size(), HM_OK);
+    messages.assign(tiles.size(), std::string());
+    alpha_blobs.clear(); alpha_blobs.resize(tile_alpha.size());
+    alpha_status.assign(tile_alpha.size(), HM_OK);
+    alpha_messages.assign(tile_alpha.size(), std::string());
+  }
+  // tile rows [r0, r0 + n) and columns [c0, c0 + m) of this grid as a grid of its own on a canvas of w x h, nothing parsed yet:
+  // everything behind sees an ordinary smaller grid (a view's sub-grid, a slab of tile rows).  For grids without tile alpha images.
+  ItemPlan sub_grid(int r0, int n, int c0, int m, int w, int h) const
+  {
+    ItemPlan S;
+    S.id = id; S.is_grid = true; S.rows = n; S.cols = m; S.canvas_w = w; S.canvas_h = h;
+    for (int r = r0; r < r0 + n; r++)
+      for (int c = c0; c < c0 + m; c++) S.tiles.push_back(tiles[(size_t)r * cols + c]);
+    S.reset_slots();
+    return S;
+  }
 };
 
 // Where the result of a decode goes beside hm_decoded: every function between an entry point and emit_image takes one of these.

@@ -59,6 +59,7 @@ void hm_pool_stream_put(hipStream_t s, int device);
 // recon.hip / filters.hip
 struct hm_dev_pic;
 int hm_batch_add_trusted(hm_batch* b, const uint8_t* blob, size_t size, const hm_tile_dest* dest); // no structural validation
+int hm_tile_origin_refused(void); // batch.cpp: HM_ERR_INVALID_ARG, the message of a tile whose origin is outside its canvas (hm_plane_geom.h: hm_place_tile)
 int hm_launch_recon(const struct hm_dev_pic* d_pics, int n_pics, int log2_ctb, int chroma_format, int bit_depth, int rare_syntax,
                     int max_ctb_w, int max_ctb_h, hipStream_t s);
 // residual.hip + chain.hip: the reconstruction of pictures with split chains as two kernels on the same stream -

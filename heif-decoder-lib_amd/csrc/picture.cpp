@@ -19,7 +19,7 @@
 #include <vector>
 
 #include "hm_internal.h"
-#include "hm_stream.h"
+#include "hm_plane_geom.h"
 
 struct hm_picture {
   uint8_t* blob = nullptr;
@@ -52,13 +52,13 @@ int hm_picture_parse_opts(const uint8_t* data, size_t size, int strict, hm_pictu
   po.annexb = 0; po.threads = 1; po.record_order = HM_RECORDS_SPLIT | (strict ? 0 : HM_PARSE_CONCEAL);
   const int rc = hm_hevc_parse_opts(data, size, &po, &p->blob, &p->blob_size);
   if (rc) { delete p; return rc; }
-  const hm_pic* h = reinterpret_cast<const hm_pic*>(p->blob);
+  const hm_pic* h = hm_pic_of(p->blob);
   if (concealed_ctbs) *concealed_ctbs = (int32_t)h->concealed_ctbs;
   hm_picture_info& I = p->info;
   std::memset(&I, 0, sizeof(I));
   // de265_get_image_width/height(img, c): the conformance window, chroma planes divided by SubWidthC / SubHeightC
   // (image.h of the reference: chroma_width_confwin = width_confwin / WinUnitX)
-  const int w = h->width - h->crop_left - h->crop_right, hh = h->height - h->crop_top - h->crop_bottom;
+  const int w = hm_window_w(*h), hh = hm_window_h(*h);
   const int sw = (h->chroma_format == 1 || h->chroma_format == 2) ? 2 : 1, sh = h->chroma_format == 1 ? 2 : 1;
   I.chroma = h->chroma_format;
   I.bit_depth = h->bit_depth_y;
@@ -301,7 +301,7 @@ int hm_picture_decode_begin(hm_picture* p, void* stream, hm_picture_job** out)
   if (!p || !out) return hm_fail(HM_ERR_INVALID_ARG, "null argument");
   *out = nullptr;
   const hm_picture_info& I = p->info;
-  const int bps = I.bit_depth > 8 ? 2 : 1;
+  const int bps = hm_sample_bytes(I.bit_depth);
   hm_picture_job* j = new (std::nothrow) hm_picture_job();
   if (!j) return hm_fail(HM_ERR_NOMEM, "out of memory");
   Request& r = j->r;
@@ -334,7 +334,7 @@ int hm_picture_decode_finish(hm_picture_job* j, uint8_t* const plane[3], const i
   Request& r = j->r;
   hm_picture* p = j->pic;
   const hm_picture_info& I = p->info;
-  const int bps = I.bit_depth > 8 ? 2 : 1;
+  const int bps = hm_sample_bytes(I.bit_depth);
   int rc = HM_OK;
   if (j->queued) rc = static_cast<DeviceWorker*>(j->worker)->wait(r);
   if (!rc && plane && stride) {
@@ -378,7 +378,7 @@ int hm_picture_decode_to_host(hm_picture* p, uint8_t* const plane[3], const int3
 {
   if (!p || !plane || !stride) return hm_fail(HM_ERR_INVALID_ARG, "null argument");
   const hm_picture_info& I = p->info;
-  const int bps = I.bit_depth > 8 ? 2 : 1;
+  const int bps = hm_sample_bytes(I.bit_depth);
   for (int c = 0; c < I.n_planes; c++)
     if (!plane[c] || stride[c] < I.plane_width[c] * bps) return hm_fail(HM_ERR_INVALID_ARG, "plane %d: null or stride too small", c);
   hm_picture_job* j = nullptr;

@@ -170,8 +170,9 @@ class Pipeline:
 
 
 def cpu_decode(hm, tiles, tile_w, tile_h, canvas_w, canvas_h, cols, is_grid, out_fmt, tile_colr=None, decoder="oracle", bilinear=False, transforms=None,
-               has_alpha=False, tile_transforms=None):
-    """tiles: list of [len][NAL] strings.  Returns (rgb array, stride) following the reference flow."""
+               has_alpha=False, tile_transforms=None, step=None):
+    """tiles: list of [len][NAL] strings.  Returns (rgb array, stride) following the reference flow.
+    step: (w, h) the tile items declare where it is not the pictures' own size - what the tile positions advance by (context.cc:2339-2359)."""
     o = orc.load()
     first = None
     canv = None
@@ -194,7 +195,7 @@ def cpu_decode(hm, tiles, tile_w, tile_h, canvas_w, canvas_h, cols, is_grid, out
             cw = canvas_w if cf == 3 else (canvas_w + 1) // 2
             ch = (canvas_h + 1) // 2 if cf == 1 else canvas_h
             canv = [orc.alloc_plane(canvas_w, canvas_h, bps), orc.alloc_plane(cw, ch, bps), orc.alloc_plane(cw, ch, bps)]
-        x0, y0 = (i % cols) * tile_w, (i // cols) * tile_h
+        x0, y0 = (i % cols) * (step[0] if step else tile_w), (i // cols) * (step[1] if step else tile_h)
         if tile_transforms and i in tile_transforms:
             # the tile item's own irot / imir / clap: applied to the tile image before the paste (context.cc:1957-2020, 2407-2415)
             tcw0 = tile_w if cf == 3 else (tile_w + 1) // 2

@@ -213,9 +213,9 @@ def test_truncated_heif_is_an_error(hm):
         pipeline.HeifFile(hm, b"\x00\x00\x00\x10ftypheic\x00\x00\x00\x00")  # no meta box
 
 
-def _decode_status(hm, data):
+def _decode_status(hm, data, host_threads=1):
     f = pipeline.HeifFile(hm, data)
-    prm = pipeline.DecodeParams(10, 1, 0, 0, None, None, 0, 0)
+    prm = pipeline.DecodeParams(10, host_threads, 0, 0, None, None, 0, 0)
     d = pipeline.Decoded()
     rc = hm.hm_decode_item(f.h, f.primary(), C.byref(prm), C.byref(d))
     msg = hm.hm_last_error().decode()
@@ -238,6 +238,69 @@ def test_invalid_grids_report_reference_errors(hm):
     data = heifwriter.write_heic(mixed, (64, 64), grid=(2, 2, 128, 128), sizes=[(64, 64)] * 3 + [(64, 72)])
     rc, msg = _decode_status(hm, data)
     assert rc == -3 and "different sizes" in msg
+
+
+def mixed_tile_grid(case):
+    """Grids of 64x64 tiles whose tiles disagree with tile 0 (context.cc:2333-2337, 2430-2492): (file, expected status, expected text).
+    Tiles are compared with tile 0 of the WHOLE grid one by one, the declared size first, then the chroma format, then the depth: the first
+    tile that fails names the error."""
+    import synthutil
+    odd = {"depth": dict(bit_depth=10), "chroma": dict(chroma_format=3), "both": dict(bit_depth=10, chroma_format=3)}
+
+    def grid(rows, cols, other, sizes=None):  # other: {tile index: key of odd}
+        n = rows * cols
+        pics = [synthutil.picture(300 + i, width=64, height=72 if sizes and sizes[i] == (64, 72) else 64, **odd.get(other.get(i), {})) for i in range(n)]
+        return heifwriter.write_heic(pics, (64, 64), grid=(rows, cols, 64 * cols, 64 * rows), sizes=sizes,
+                                     bit_depth=[odd.get(other.get(i), {}).get("bit_depth", 8) for i in range(n)],
+                                     chroma_format=[odd.get(other.get(i), {}).get("chroma_format", 1) for i in range(n)])
+    tall = [(64, 64)] * 3 + [(64, 72)]
+    return {
+        "depth_last_row": lambda: (grid(4, 2, {6: "depth"}), -3, "different pixel depth"),
+        "chroma_last_row": lambda: (grid(4, 2, {6: "chroma"}), -3, "different chroma format"),
+        # a whole tile row unlike tile 0: as a slab of its own it is consistent in itself, only the comparison with tile 0 of the grid refuses it
+        "depth_whole_last_row": lambda: (grid(4, 2, {6: "depth", 7: "depth"}), -3, "different pixel depth"),
+        "chroma_whole_last_row": lambda: (grid(4, 2, {6: "chroma", 7: "chroma"}), -3, "different chroma format"),
+        "chroma_and_depth_same_tile": lambda: (grid(2, 2, {1: "both"}), -3, "different chroma format"),
+        "depth_then_size": lambda: (grid(2, 2, {1: "depth"}, sizes=tall), -3, "different pixel depth"),
+        "size_then_depth": lambda: (grid(2, 2, {3: "depth"}, sizes=[(64, 64), (64, 72), (64, 64), (64, 64)]), -3, "Grid tiles have different sizes"),
+    }[case]()
+
+
+@pytest.mark.parametrize("case", ["depth_last_row", "chroma_last_row", "depth_whole_last_row", "chroma_whole_last_row", "chroma_and_depth_same_tile", "depth_then_size",
+                                  "size_then_depth"])
+def test_mixed_tile_grids_report_reference_errors(hm, case):
+    """host_threads=16: no more tiles than threads, the one-batch decode.  (With fewer threads than tiles the first five grids are cut
+    into slabs of tile rows, which needs a device: the test below.)"""
+    data, want_rc, want_msg = mixed_tile_grid(case)
+    rc, msg = _decode_status(hm, data, host_threads=16)
+    assert rc == want_rc and want_msg in msg, (rc, msg)
+
+
+@pytest.mark.gpu
+@pytest.mark.parametrize("case", ["depth_last_row", "chroma_last_row", "depth_whole_last_row", "chroma_whole_last_row", "chroma_and_depth_same_tile"])
+def test_mixed_tile_grids_are_refused_slab_by_slab(hm, case):
+    """ADVICE.md (round 6), first item: host_threads=1, more tiles than threads - the grid is decoded in slabs of one tile row, each queued
+    as soon as it is parsed, and every tile is still compared with tile 0 of the WHOLE grid: the status and message of the one-batch decode,
+    nothing handed out, and the next decode in the same process unharmed.  The two *_whole_last_row grids are the ones that need that
+    comparison (grid_tile_picture in decode_grid_cut's take_blobs): rows 0-2 as tile 0, row 3 another depth or chroma format throughout, so
+    the last slab agrees with itself and its own decode finds nothing wrong - without the comparison the call returned HM_OK with mixed
+    content under tile 0's metadata.  In the other three the odd tile shares a slab with an ordinary one, and the slab's decode refuses too."""
+    data, want_rc, want_msg = mixed_tile_grid(case)
+    f = pipeline.HeifFile(hm, data)
+    prm = pipeline.DecodeParams(10, 1, 0, 0, None, None, 0, 0)
+    d = pipeline.Decoded()
+    rc = hm.hm_decode_item(f.h, f.primary(), C.byref(prm), C.byref(d))
+    msg = hm.hm_last_error().decode()
+    f.close()
+    assert rc == want_rc and want_msg in msg, (rc, msg)
+    assert not d.plane[0]
+    import numpy as np
+    g = pipeline.HeifFile(hm, heifwriter.write_heic(_tiles(8), (64, 64), grid=(4, 2, 128, 256)))
+    slabs, meta = g.decode(g.primary(), 10, threads=1)
+    batch, _ = g.decode(g.primary(), 10, threads=16)
+    g.close()
+    assert (meta["width"], meta["height"]) == (128, 256)
+    np.testing.assert_array_equal(slabs[0][:256, :384], batch[0][:256, :384])
 
 
 def test_no_gpu_means_loud_failure_not_cpu_fallback(hm):

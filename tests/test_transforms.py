@@ -317,6 +317,38 @@ def test_grid_tiles_with_their_own_transforms(hm, variant):
 
 
 @pytest.mark.gpu
+def test_own_transform_tiles_at_odd_origins(hm):
+    """The reference's rounding of a chroma origin, (x0 + 1) / 2 (context.cc:2466-2483; csrc/hm_plane_geom.h: hm_place_tile), where it
+    shows: a 4:2:0 grid of 64x64 pictures whose items declare 63x63, so column 1 starts at x = 63 and row 1 at y = 63, chroma at 32 -
+    one sample further than the luma origin halved.  Tile 1 (odd x) and tile 3 (odd x and y) carry an irot of their own and are pasted
+    from planes of their own, tile 2 (odd y) goes straight into the canvas.  Tiles 0, 1 and 3 also carry a clap to 63x63, the size
+    they declare: no two tiles then overlap but tiles 2 and 3 in one column, where the paste of tile 3 comes behind the batch that
+    pastes tile 2 - the order of the reference's sequential paste (tiles that overlap inside one batch have no defined order).
+    Expected: the fingerprints of tests/golden/grid_odd_origin.json, recorded from the commit named there - and the CPU flow of the
+    reference, which agrees with them."""
+    import json
+    import os
+    gold = json.load(open(os.path.join(os.path.dirname(os.path.abspath(__file__)), "golden", "grid_odd_origin.json")))
+    tiles = [synthutil.picture(9500 + i, width=64, height=64, vui=1, full_range=1, matrix=6) for i in range(4)]
+    c63 = ("clap", (63, 1, 63, 1, 0, 1, 0, 1))
+    tt = {0: [c63], 1: [("irot", 2), c63], 3: [("irot", 1), c63]}
+    data = heifwriter.write_heic(tiles, (64, 64), grid=(2, 2, 120, 100), sizes=[(63, 63)] * 4, tile_transforms=tt)
+    f = pipeline.HeifFile(hm, data)
+    rgb, meta = f.decode(f.primary(), 10)
+    planes, _ = f.decode(f.primary(), 0)
+    f.close()
+    assert (meta["width"], meta["height"]) == (120, 100)
+    got = {"rgb": pipeline.survey_fnv(rgb[0], meta["stride"][0], 120 * 3, 100)}
+    for c, (w, h) in enumerate(((120, 100), (60, 50), (60, 50))):
+        got["y cb cr".split()[c]] = pipeline.survey_fnv(planes[c], planes[c].shape[1], w, h)
+    exp, _, canv = pipeline.cpu_decode(hm, tiles, 64, 64, 120, 100, 2, True, 10, tile_transforms=tt, step=(63, 63))
+    np.testing.assert_array_equal(rgb[0][:100, :360], exp[:100, :360])
+    for c, (w, h) in enumerate(((120, 100), (60, 50), (60, 50))):
+        np.testing.assert_array_equal(planes[c][:h, :w], canv[c][0][:h, :w])
+    assert got == gold["fingerprints"]
+
+
+@pytest.mark.gpu
 def test_own_transform_tile_outside_the_canvas_is_refused_before_anything_runs(hm):
     """A crafted grid: tiles with their own irot, a canvas narrower than one tile column, so that the second column's origin
     lies at / beyond the canvas edge (the reference: context.cc:2466-2483 returns an error for it).  The image must be
