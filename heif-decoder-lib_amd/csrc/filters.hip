@@ -242,10 +242,24 @@ __device__ __forceinline__ uint32_t meta_at(const hm_dev_pic& dp, int x, int y)
   const int bx = x < 0 ? 0 : ((x >> 2) < dp.w4 ? (x >> 2) : dp.w4 - 1), by = y < 0 ? 0 : ((y >> 2) < dp.h4 ? (y >> 2) : dp.h4 - 1);
   return gptr<uint16_t>(dp.meta)[(uint32_t)(bx + mul24_raw(by, dp.w4))]; // (32-bit index: at most 4096 x 4096 blocks; 64-bit multiplies run at a quarter of the rate)
 }
+// beta / tc of one edge unit of boundary strength 2 - all units are intra - from QpY on its Q / P side (8.7.2.5.3; luma: deblock.cc:731-753,
+// chroma: 1650-1716, which has no beta and takes QpC from Table 8-10 where the plane is 4:2:0: map420).  beta_off / tc_off: the slice's
+// offsets (x 2); qp_off: the plane's chroma QP offset; bd_shift = bit depth - 8 (both scale with the depth)
+template <typename Tab>
+__device__ __forceinline__ void edge_unit_params(const Tab& tab, bool luma, bool map420, int qp_q, int qp_p, int beta_off, int tc_off, int qp_off, int bd_shift, int& beta, int& tc)
+{
+  const int avg = (qp_q + qp_p + 1) >> 1;
+  int qt = avg;
+  if (luma) beta = tab.beta(clip3i(0, 51, avg + beta_off)) << bd_shift;
+  else {
+    const int qPi = avg + qp_off;
+    qt = map420 ? chroma_qp_map(qPi) : (qPi < 51 ? qPi : 51);
+  }
+  tc = tab.tc(clip3i(0, 53, qt + 2 + tc_off)) << bd_shift; // (bS 2: + 2 (bS - 1))
+}
 template <typename Pix, bool PCMF, typename Tab>
 __device__ __forceinline__ bool window_edges(const hm_dev_pic& dp, const PicView& v, int c, int kx, int ky, int sw, int sh, WindowEdges<PCMF>& E, const Tab& tab)
 {
-  const int bd = dp.bit_depth, bdscale = 1 << (bd - 8);
   const int PW = dp.width >> (sw >> 1), PH = dp.height >> (sh >> 1);  // plane size (sw, sh are 1 or 2: a shift, not a division)
   const int ex = kx << 3, ey = ky << 3, ox = ex - 4, oy = ey - 4;   // the crossing and the window origin (plane samples)
   // the four edge units: vertical edge x = ex, rows oy.. (j = 0) and ey.. (j = 1); horizontal edge y = ey, columns ox.. / ex..
@@ -296,17 +310,8 @@ __device__ __forceinline__ bool window_edges(const hm_dev_pic& dp, const PicView
       __builtin_memcpy(&sl, w3, sizeof(sl));
     }
     else sl = slice_at(dp, v, lsx, lsy);
-    const int QP_Q = qq[vertical][j], QP_P = qp[vertical][j];
-    if (c == 0) {
-      const int qPL = (QP_Q + QP_P + 1) >> 1;
-      beta = tab.beta(clip3i(0, 51, qPL + sl.beta_offset_div2 * 2)) * bdscale;
-      tc = tab.tc(clip3i(0, 53, qPL + 2 * (bs - 1) + sl.tc_offset_div2 * 2)) * bdscale;
-    }
-    else {
-      const int qPi = ((QP_Q + QP_P + 1) >> 1) + qp_off;
-      const int QP_C = dp.chroma_format == 1 ? chroma_qp_map(qPi) : (qPi < 51 ? qPi : 51);
-      tc = tab.tc(clip3i(0, 53, QP_C + 2 + sl.tc_offset_div2 * 2)) * bdscale;
-    }
+    // (bs is 0 or 2 here - every unit is intra, bsV / bsH above -, which edge_unit_params' "+ 2" = 2 (bS - 1) relies on)
+    edge_unit_params(tab, c == 0, dp.chroma_format == 1, qq[vertical][j], qp[vertical][j], sl.beta_offset_div2 * 2, sl.tc_offset_div2 * 2, qp_off, dp.bit_depth - 8, beta, tc);
     if (PCMF && (dp.flags & HM_PIC_PCMF)) {
       if (c == 0) {
         // deblock.cc:755-786 + fallback-postfilter.h:60-125 as the reference's SIMD build behaves: per unit a flag per side
@@ -644,13 +649,6 @@ __global__ __launch_bounds__(256, sizeof(Pix) == 1 ? 8 : HM_DEBLOCK16_WGS) void 
   }
 }
 
-// common_utils.h:73-79 on the device (no FMA, trunc(x + 0.5f))
-__device__ __forceinline__ int clip_f_u8(float fx)
-{
-  const int x = (int)__fadd_rn(fx, 0.5f);
-  return x < 0 ? 0 : (x > 255 ? 255 : x);
-}
-
 // SAO + paste.  blockIdx.y = picture, blockIdx.z = plane.  One lane = 8 consecutive samples of one
 // row (8 | every CTB width, so a group never straddles CTBs when the conformance-window offset is a
 // multiple of 8 - the common case; otherwise the generic per-sample path runs).
@@ -708,8 +706,6 @@ __device__ __forceinline__ int sao_sample(const hm_dev_pic& dp, const PicView& v
   return val;
 }
 
-// Edge offset of one group of G samples for one SaoEoClass (compile-time neighbour direction): neighbour a of
-// sample x is (x + HX, yy + VY), neighbour b is (x - HX, yy - VY) (sao.cc:336-424).
 // ---- SAO arithmetic on pairs of samples (two 16-bit halves per register, v_pk_* / v_perm_b32) ----
 // The per-sample version of this kernel was bound by VALU issue (~38 instructions per sample); here a group of 8
 // samples is 4 registers of sample pairs and the offset table is a byte lookup (v_perm_b32), ~8 per sample.
@@ -740,19 +736,24 @@ struct SaoRow {
   uint32_t l, r;
   __device__ __forceinline__ uint32_t left() const { return l >> (32 - 8 * (int)sizeof(Pix)); }
   __device__ __forceinline__ uint32_t right() const { return r & ((1u << (8 * (int)sizeof(Pix))) - 1); }
+  // p[] from the 8 samples at q, as they lie in memory
+  __device__ __forceinline__ void unpack(const Pix* q)
+  {
+    if (sizeof(Pix) == 1) {
+      uint32_t d[2];
+      __builtin_memcpy(d, q, 8);
+      p[0] = __builtin_amdgcn_perm(0, d[0], 0x0c010c00u); p[1] = __builtin_amdgcn_perm(0, d[0], 0x0c030c02u);
+      p[2] = __builtin_amdgcn_perm(0, d[1], 0x0c010c00u); p[3] = __builtin_amdgcn_perm(0, d[1], 0x0c030c02u);
+    }
+    else __builtin_memcpy(p, q, 16);
+  }
   // row y clamped into the picture; the side dwords fall back to the group itself at the picture's left / right end
   // (their samples are not used there)
   __device__ __forceinline__ void load(const uint8_t* plane, int pitch, int xs, int y, int W, int Hh)
   {
     constexpr int PER = 4 / (int)sizeof(Pix);
     const Pix* row = reinterpret_cast<const Pix*>(plane + (size_t)(y < 0 ? 0 : (y < Hh ? y : Hh - 1)) * pitch);
-    if (sizeof(Pix) == 1) {
-      uint32_t d[2];
-      __builtin_memcpy(d, row + xs, 8);
-      p[0] = __builtin_amdgcn_perm(0, d[0], 0x0c010c00u); p[1] = __builtin_amdgcn_perm(0, d[0], 0x0c030c02u);
-      p[2] = __builtin_amdgcn_perm(0, d[1], 0x0c010c00u); p[3] = __builtin_amdgcn_perm(0, d[1], 0x0c030c02u);
-    }
-    else __builtin_memcpy(p, row + xs, 16);
+    unpack(row + xs);
     __builtin_memcpy(&l, row + (xs > 0 ? xs - PER : xs), 4);
     __builtin_memcpy(&r, row + (xs + 8 < W ? xs + 8 : xs), 4);
   }
@@ -826,6 +827,95 @@ __device__ __forceinline__ void sao_edge_group(int xs, int yy, int W, int Hh, in
   }
 }
 
+// SAO of one group of 8 samples of row yy of plane c: out = the samples of `cur` with the offsets of the group's CTB.  enable: SAO runs at all
+// (the caller's stage and the picture's flag); cflags, s0, s1: dword 2 of the CTB's hm_ctb (flags | sao_nb_mask << 8 | sao_nb_mask_c << 16 |
+// sao_ring_c << 24) and the plane's hm_sao (type, eo_class, band_position, offset[0] | offset[1..3], reserved); band_shift = bit depth - 5;
+// maxv2: the largest sample value in both halves.  Returns the SAO type that was applied (0: none).
+template <typename Pix>
+__device__ __forceinline__ int sao_group(bool enable, int c, uint32_t cflags, uint32_t s0, uint32_t s1, int band_shift, uint32_t maxv2, int xs, int yy, int W, int Hh,
+                                         int l2w, int l2h, int cx, int cy, const SaoRow<Pix>& up, const SaoRow<Pix>& cur, const SaoRow<Pix>& dn, uint32_t (&out)[4],
+                                         bool all_ok = false)
+{
+  const bool sao_on = enable && (cflags & (c == 0 ? HM_CTB_SAO_LUMA : HM_CTB_SAO_CHROMA));
+  const int type = sao_on ? (int)(s0 & 0xFF) : 0;
+  const uint32_t offs = (s0 >> 24) | (s1 << 8); // the four int8 offsets in one register
+  // neighbour-CTB mask of this component (chroma: with the reference's quirk Q13)
+  const uint32_t nbm = c == 0 ? (cflags >> 8) & 0xFF : (cflags >> 16) & 0xFF;
+#pragma unroll
+  for (int j = 0; j < 4; j++) out[j] = cur.p[j];
+  if (type == 1) { // band offset (fallback-postfilter.h:218-241): table index = band - band_position, 4 = none
+    const uint32_t bp = (s0 >> 16) & 0xFF;
+    const uint32_t biased = offs ^ 0x80808080u;
+#pragma unroll
+    for (int j = 0; j < 4; j++) {
+      u16x2 bi = (as_u(cur.p[j]) >> (u16x2)((unsigned short)band_shift)) - (u16x2)((unsigned short)bp);
+      bi = __builtin_elementwise_min(bi & (u16x2)(31), (u16x2)(4));
+      out[j] = pk_apply(cur.p[j], as_w(bi) | 0x0c000c00u, 0x80u, biased, maxv2);
+    }
+  }
+  else if (type == 2) { // edge offset: SaoEoClass 0 horizontal, 1 vertical, 2 135 degrees, 3 45 degrees
+    const int cl = (s0 >> 8) & 0xFF;
+    if (cl == 0) sao_edge_group<Pix, -1, 0>(xs, yy, W, Hh, l2w, l2h, cx, cy, nbm, offs, maxv2, up, cur, dn, out, all_ok);
+    else if (cl == 1) sao_edge_group<Pix, 0, -1>(xs, yy, W, Hh, l2w, l2h, cx, cy, nbm, offs, maxv2, up, cur, dn, out, all_ok);
+    else if (cl == 2) sao_edge_group<Pix, -1, -1>(xs, yy, W, Hh, l2w, l2h, cx, cy, nbm, offs, maxv2, up, cur, dn, out, all_ok);
+    else sao_edge_group<Pix, 1, -1>(xs, yy, W, Hh, l2w, l2h, cx, cy, nbm, offs, maxv2, up, cur, dn, out, all_ok);
+  }
+  return type;
+}
+
+// common_utils.h:73-79 on the device (no FMA, trunc(x + 0.5f))
+__device__ __forceinline__ int clip_f_u8(float fx)
+{
+  const int x = (int)__fadd_rn(fx, 0.5f);
+  return x < 0 ? 0 : (x > 255 ? 255 : x);
+}
+// The limited -> full range rescale of the grid paste (context.cc:2504-2528: clip_f_u8((v - 16) * k), k = 1.1689f for luma,
+// 1.1429f for chroma - with luma's offset, quirk Q2 - in float, trunc(x + 0.5f)) on 8-bit samples, in integers: with
+// t = max(v, 16) - 16 the result is min(255, t + ((t * A + B) >> S)) for (A, B, S) = (173, 507, 10) / (73, 256, 9) - every
+// intermediate fits 16 bits, so sample pairs travel as the halves of one register.  Exact for all 256 values: checked here at
+// compile time against the float expression (constant evaluation is IEEE round-to-nearest, no contraction), and by
+// tests/test_oracle_colour.py against the oracle's float code.
+constexpr int rescale_float_u8(int v, float k)
+{
+  const float fx = ((float)v - 16.0f) * k;
+  const int x = (int)(fx + 0.5f);
+  return x < 0 ? 0 : (x > 255 ? 255 : x);
+}
+constexpr int rescale_int_u8(int v, int A, int B, int S)
+{
+  const int t = (v > 16 ? v : 16) - 16, o = t + ((t * A + B) >> S);
+  return o > 255 ? 255 : o;
+}
+constexpr bool rescale_forms_agree()
+{
+  for (int v = 0; v < 256; v++)
+    if (rescale_int_u8(v, 173, 507, 10) != rescale_float_u8(v, 1.1689f) || rescale_int_u8(v, 73, 256, 9) != rescale_float_u8(v, 1.1429f) ||
+        (v - 16) * 173 + 507 >= 65536)
+      return false;
+  return true;
+}
+static_assert(rescale_forms_agree(), "integer form of the paste rescale");
+template <bool CHROMA>
+__device__ __forceinline__ uint32_t pk_rescale(uint32_t pair)
+{
+  const u16x2 t = __builtin_elementwise_sub_sat(as_u(pair), (u16x2)(16));
+  const u16x2 o = t + ((t * (u16x2)(CHROMA ? 73 : 173) + (u16x2)(CHROMA ? 256 : 507)) >> (u16x2)(CHROMA ? 9 : 10));
+  return as_w(__builtin_elementwise_min(o, (u16x2)(255)));
+}
+// ... of a pair of samples as they lie in memory: 8-bit samples as above; 16-bit storage byte by byte (quirk Q1: the reference's
+// loop runs over the BYTES of the plane, context.cc:2499-2525) with the offset of the picture's depth, 16 << (depth - 8) - the
+// float expression itself (rare: a grid of deeper limited-range tiles)
+template <typename Pix, bool CHROMA>
+__device__ __forceinline__ uint32_t pk_rescale_stored(uint32_t pair, int bd)
+{
+  if (sizeof(Pix) == 1) return pk_rescale<CHROMA>(pair);
+  const float off = (float)(16 << (bd - 8)), ratio = CHROMA ? 1.1429f : 1.1689f;
+  uint32_t o = 0;
+#pragma unroll
+  for (int k = 0; k < 4; k++) o |= (uint32_t)clip_f_u8(__fmul_rn(__fsub_rn((float)((pair >> (8 * k)) & 0xFF), off), ratio)) << (8 * k);
+  return o;
+}
+
 // RARE: the variant for the rare-syntax classes: samples of transquant-bypass units and, with
 // pcm_loop_filter_disable_flag, of PCM units keep their deblocked value (sao.cc:356-363, 452-456).
 template <typename Pix, bool RARE>
@@ -882,6 +972,8 @@ __global__ __launch_bounds__(256) void k_sao_paste(const hm_dev_pic* __restrict_
     for (int r = 0; r < R; r++) {
       const int yy = yy0 + r, cy = yy >> l2h;
       const SaoRow<Pix>&up = rows[r], &cur = rows[r + 1], &dn = rows[r + 2];
+      // (sao_group's rule, written out - a fix to the band or edge rule is made there AND here, keep the two in step: through the shared function
+      //  the 8-bit instance ran 0.5 - 0.8 % slower on CTBs of 32 and 64, 0.489 - 0.491 instead of 0.484 - 0.488 ms, profiles/filters_refactor.txt)
       const bool sao_on = apply_sao && (dp.flags & HM_PIC_SAO_ENABLED) && (cflags[r] & (c == 0 ? HM_CTB_SAO_LUMA : HM_CTB_SAO_CHROMA));
       const int type = sao_on ? (int)(s0[r] & 0xFF) : 0;
       const uint32_t offs = (s0[r] >> 24) | (s1[r] << 8); // the four int8 offsets in one register
@@ -937,26 +1029,9 @@ __global__ __launch_bounds__(256) void k_sao_paste(const hm_dev_pic* __restrict_
 #pragma unroll
   for (int r = 0; r < R; r++) {
     if (yd0 + r >= chh) break;
-    if (dp.rescale) { // limited -> full range of a tile pasted into a canvas without nclx, per sample in float
-      const float off = (float)(16 << (bd - 8));
-      const float ratio = c ? 1.1429f : 1.1689f;
+    if (dp.rescale) { // limited -> full range of a tile pasted into a canvas without nclx
 #pragma unroll
-      for (int j = 0; j < 4; j++) {
-        uint32_t pair = 0;
-#pragma unroll
-        for (int h = 0; h < 2; h++) {
-          const int val = (int)((res[r][j] >> (16 * h)) & 0xFFFF);
-          int o;
-          if (sizeof(Pix) == 1) o = clip_f_u8(__fmul_rn(__fsub_rn((float)val, off), ratio));
-          else { // the reference rescales BYTES of the 16-bit storage (quirk Q1)
-            const int lo = clip_f_u8(__fmul_rn(__fsub_rn((float)(val & 0xFF), off), ratio));
-            const int hi = clip_f_u8(__fmul_rn(__fsub_rn((float)(val >> 8), off), ratio));
-            o = lo | (hi << 8);
-          }
-          pair |= (uint32_t)o << (16 * h);
-        }
-        res[r][j] = pair;
-      }
+      for (int j = 0; j < 4; j++) res[r][j] = c ? pk_rescale_stored<Pix, true>(res[r][j], bd) : pk_rescale_stored<Pix, false>(res[r][j], bd);
     }
     Pix* drow = reinterpret_cast<Pix*>(dp.dst[c] + (size_t)(yd0 + r) * dp.dst_pitch[c]) + x8;
     if (x8 + G <= cw) {
@@ -1001,22 +1076,10 @@ __device__ __forceinline__ bool tail_window_edges(const uint16_t* m, int MP, int
   // Q / P side of: vertical edge upper, lower unit; horizontal edge left, right unit
   const int q[4] = {qpy(c422 ? m01 : m02), qpy(m00), qpy(m20), qpy(m00)}, p[4] = {qpy(c422 ? m11 : m12), qpy(m10), qpy(m21), qpy(m01)};
   const bool bs[4] = {bV0, bV1, bH0, bH1};
-  int beta[4], tc[4];
+  int beta[4] = {0, 0, 0, 0}, tc[4] = {0, 0, 0, 0};
 #pragma unroll
-  for (int u = 0; u < 4; u++) {
-    const int avg = (q[u] + p[u] + 1) >> 1;
-    int qt;
-    if (c == 0) {
-      beta[u] = bs[u] ? (int)tab[clip3i(0, 51, avg + beta_off)] << bd_shift : 0;
-      qt = avg;
-    }
-    else {
-      beta[u] = 0;
-      const int qPi = avg + qp_off;
-      qt = CF == 1 ? chroma_qp_map(qPi) : (qPi < 51 ? qPi : 51); // (4:2:0: Table 8-10; deblock.cc:1690-1696)
-    }
-    tc[u] = bs[u] ? (int)tab[52 + clip3i(0, 53, qt + 2 + tc_off)] << bd_shift : 0; // (bS 2: + 2 (bS - 1))
-  }
+  for (int u = 0; u < 4; u++)
+    if (bs[u]) edge_unit_params(TabLds{tab}, c == 0, CF == 1, q[u], p[u], beta_off, tc_off, qp_off, bd_shift, beta[u], tc[u]);
   E.betaV[0] = beta[0]; E.betaV[1] = beta[1]; E.betaH[0] = beta[2]; E.betaH[1] = beta[3];
   E.tcV[0] = tc[0]; E.tcV[1] = tc[1]; E.tcH[0] = tc[2]; E.tcH[1] = tc[3];
   return true;
@@ -1062,13 +1125,7 @@ template <typename Pix>
 __device__ __forceinline__ void tile_row(SaoRow<Pix>& R, const Pix* tile, int pitch, int row, int xo)
 {
   const Pix* q = tile + (mul24_raw(row, pitch) + xo);
-  if (sizeof(Pix) == 1) {
-    uint32_t d[2];
-    __builtin_memcpy(d, q, 8);
-    R.p[0] = __builtin_amdgcn_perm(0, d[0], 0x0c010c00u); R.p[1] = __builtin_amdgcn_perm(0, d[0], 0x0c030c02u);
-    R.p[2] = __builtin_amdgcn_perm(0, d[1], 0x0c010c00u); R.p[3] = __builtin_amdgcn_perm(0, d[1], 0x0c030c02u);
-  }
-  else __builtin_memcpy(R.p, q, 16);
+  R.unpack(q);
   // (the tile starts 8 columns left of the workgroup's samples and ends 8 behind them: both side dwords lie inside it)
   __builtin_memcpy(&R.l, reinterpret_cast<const uint8_t*>(q) - 4, 4);
   __builtin_memcpy(&R.r, q + 8, 4);
@@ -1083,6 +1140,11 @@ __device__ __forceinline__ void tail_sao(const hm_dev_pic& dp, const PicView& v,
                                          int xs, int yy0, int W, int Hh, int l2w, int l2h, int apply_sao, uint32_t (&res)[NR][4], uint32_t rec_flags = 0, uint32_t rec_s0 = 0,
                                          uint32_t rec_s1 = 0, int bd = 8)
 {
+#if defined(HM_T_PROBE) && (HM_T_PROBE & 2)
+  const bool enable = false; // probe: no SAO arithmetic
+#else
+  const bool enable = apply_sao && (dp.flags & HM_PIC_SAO_ENABLED);
+#endif
   SaoRow<Pix> rows[NR + 2];
   // UNI: the CTB's parameters are known (scalars) before anything is read - the row above the group's first and the row below
   // its last are only looked at by the edge classes with a vertical component (r05: they were fetched unconditionally, as in
@@ -1101,94 +1163,19 @@ __device__ __forceinline__ void tail_sao(const hm_dev_pic& dp, const PicView& v,
   const int cx = xs >> l2w;
 #pragma unroll
   for (int r = 0; r < NR; r++) {
-    const int yy = yy0 + r, yc = yy < Hh ? yy : Hh - 1, cy = yy >> l2h;
+    const int yy = yy0 + r, yc = yy < Hh ? yy : Hh - 1;
     uint32_t cflags, s0, s1;
     if (UNI) { cflags = rec_flags; s0 = rec_s0; s1 = rec_s1; (void)yc; }
     else {
-      int ctb_index = cx + mul24_raw(yc >> l2h, dp.ctb_w);
-      if (UNI) ctb_index = __builtin_amdgcn_readfirstlane(ctb_index);
+      const int ctb_index = cx + mul24_raw(yc >> l2h, dp.ctb_w);
       const GLOBAL_AS uint32_t* cbq = gptr<uint32_t>(reinterpret_cast<const uint8_t*>(v.ctbs) + (uint32_t)mul24_raw(ctb_index, (int)sizeof(hm_ctb))); // hm_ctb as dwords (32-bit offset)
       cflags = cbq[2]; s0 = cbq[3 + 2 * c]; s1 = cbq[4 + 2 * c];
     }
-    const SaoRow<Pix>&up = rows[r], &cur = rows[r + 1], &dn = rows[r + 2];
-    const bool sao_on = apply_sao && (dp.flags & HM_PIC_SAO_ENABLED) && (cflags & (c == 0 ? HM_CTB_SAO_LUMA : HM_CTB_SAO_CHROMA));
-#if defined(HM_T_PROBE) && (HM_T_PROBE & 2)
-    const int type = 0; (void)sao_on; // probe: no SAO arithmetic
-#else
-    const int type = sao_on ? (int)(s0 & 0xFF) : 0;
-#endif
-    const uint32_t offs = (s0 >> 24) | (s1 << 8);
     const uint32_t nbm = c == 0 ? (cflags >> 8) & 0xFF : (cflags >> 16) & 0xFF;
-    const uint32_t maxv2 = sizeof(Pix) == 1 ? 0x00FF00FFu : ((1u << bd) - 1) * 0x10001u; // (bd: the picture's bit depth; 8-bit samples: a constant)
-#pragma unroll
-    for (int j = 0; j < 4; j++) res[r][j] = cur.p[j];
-    if (type == 1) { // band offset (fallback-postfilter.h:218-241)
-      const uint32_t bp = (s0 >> 16) & 0xFF;
-      const uint32_t biased = offs ^ 0x80808080u;
-#pragma unroll
-      for (int j = 0; j < 4; j++) {
-        u16x2 bi = (as_u(cur.p[j]) >> (u16x2)((unsigned short)(sizeof(Pix) == 1 ? 3 : bd - 5))) - (u16x2)((unsigned short)bp);
-        bi = __builtin_elementwise_min(bi & (u16x2)(31), (u16x2)(4));
-        res[r][j] = pk_apply(cur.p[j], as_w(bi) | 0x0c000c00u, 0x80u, biased, maxv2);
-      }
-    }
-    else if (type == 2) {
-      const int cl = (s0 >> 8) & 0xFF;
-      const bool all_ok = UNI && nbm == 0xFFu; // (the CTB's eight neighbours exist and may be read: nothing to mask)
-      if (cl == 0) sao_edge_group<Pix, -1, 0>(xs, yy, W, Hh, l2w, l2h, cx, cy, nbm, offs, maxv2, up, cur, dn, res[r], all_ok);
-      else if (cl == 1) sao_edge_group<Pix, 0, -1>(xs, yy, W, Hh, l2w, l2h, cx, cy, nbm, offs, maxv2, up, cur, dn, res[r], all_ok);
-      else if (cl == 2) sao_edge_group<Pix, -1, -1>(xs, yy, W, Hh, l2w, l2h, cx, cy, nbm, offs, maxv2, up, cur, dn, res[r], all_ok);
-      else sao_edge_group<Pix, 1, -1>(xs, yy, W, Hh, l2w, l2h, cx, cy, nbm, offs, maxv2, up, cur, dn, res[r], all_ok);
-    }
+    // (8-bit samples: band shift and largest value are constants; UNI, the CTB's eight neighbours exist and may be read: nothing to mask)
+    sao_group<Pix>(enable, c, cflags, s0, s1, sizeof(Pix) == 1 ? 3 : bd - 5, sizeof(Pix) == 1 ? 0x00FF00FFu : ((1u << bd) - 1) * 0x10001u, xs, yy, W, Hh, l2w, l2h, cx, yy >> l2h,
+                   rows[r], rows[r + 1], rows[r + 2], res[r], UNI && nbm == 0xFFu);
   }
-}
-
-// The limited -> full range rescale of the grid paste (context.cc:2504-2528: clip_f_u8((v - 16) * k), k = 1.1689f for luma,
-// 1.1429f for chroma - with luma's offset, quirk Q2 - in float, trunc(x + 0.5f)) on 8-bit samples, in integers: with
-// t = max(v, 16) - 16 the result is min(255, t + ((t * A + B) >> S)) for (A, B, S) = (173, 507, 10) / (73, 256, 9) - every
-// intermediate fits 16 bits, so sample pairs travel as the halves of one register.  Exact for all 256 values: checked here at
-// compile time against the float expression (constant evaluation is IEEE round-to-nearest, no contraction), and by
-// tests/test_oracle_colour.py against the oracle's float code.
-constexpr int rescale_float_u8(int v, float k)
-{
-  const float fx = ((float)v - 16.0f) * k;
-  const int x = (int)(fx + 0.5f);
-  return x < 0 ? 0 : (x > 255 ? 255 : x);
-}
-constexpr int rescale_int_u8(int v, int A, int B, int S)
-{
-  const int t = (v > 16 ? v : 16) - 16, o = t + ((t * A + B) >> S);
-  return o > 255 ? 255 : o;
-}
-constexpr bool rescale_forms_agree()
-{
-  for (int v = 0; v < 256; v++)
-    if (rescale_int_u8(v, 173, 507, 10) != rescale_float_u8(v, 1.1689f) || rescale_int_u8(v, 73, 256, 9) != rescale_float_u8(v, 1.1429f) ||
-        (v - 16) * 173 + 507 >= 65536)
-      return false;
-  return true;
-}
-static_assert(rescale_forms_agree(), "integer form of the paste rescale");
-template <bool CHROMA>
-__device__ __forceinline__ uint32_t pk_rescale(uint32_t pair)
-{
-  const u16x2 t = __builtin_elementwise_sub_sat(as_u(pair), (u16x2)(16));
-  const u16x2 o = t + ((t * (u16x2)(CHROMA ? 73 : 173) + (u16x2)(CHROMA ? 256 : 507)) >> (u16x2)(CHROMA ? 9 : 10));
-  return as_w(__builtin_elementwise_min(o, (u16x2)(255)));
-}
-
-// ... of a pair of samples as they lie in memory: 8-bit samples as above; 16-bit storage byte by byte (quirk Q1: the reference's
-// loop runs over the BYTES of the plane, context.cc:2499-2525) with the offset of the picture's depth, 16 << (depth - 8) - the
-// float expression itself, as k_sao_paste evaluates it (rare: a grid of deeper limited-range tiles)
-template <typename Pix, bool CHROMA>
-__device__ __forceinline__ uint32_t pk_rescale_stored(uint32_t pair, int bd)
-{
-  if (sizeof(Pix) == 1) return pk_rescale<CHROMA>(pair);
-  const float off = (float)(16 << (bd - 8)), ratio = CHROMA ? 1.1429f : 1.1689f;
-  uint32_t o = 0;
-#pragma unroll
-  for (int k = 0; k < 4; k++) o |= (uint32_t)clip_f_u8(__fmul_rn(__fsub_rn((float)((pair >> (8 * k)) & 0xFF), off), ratio)) << (8 * k);
-  return o;
 }
 
 // N bytes of LDS at an address known to be a multiple of ALIGN (a byte pointer alone would make the compiler split the access)
@@ -1196,6 +1183,102 @@ template <int ALIGN, int N>
 __device__ __forceinline__ void lds_get(uint32_t* d, const uint8_t* p) { __builtin_memcpy(d, __builtin_assume_aligned(p, ALIGN), N); }
 template <int ALIGN, int N>
 __device__ __forceinline__ void lds_put(uint8_t* p, const uint32_t* d) { __builtin_memcpy(__builtin_assume_aligned(p, ALIGN), d, N); }
+
+// ---- what the two fused tails (k_tail420, k_tailf) share before their phase 2 ----
+// The tile of a workgroup.  Workgroups go to the 8 XCDs in turn (linear id % 8) and every XCD has an L2 of its own: neighbouring tiles
+// share the cache lines at their common border (the windows overlap by 4 samples, rows are read in 128-byte lines), so each XCD
+// gets a contiguous run of the picture's tiles - gridDim.x = 8 * chunk, tail_grid_x() - instead of every eighth tile.
+__device__ __forceinline__ int tail_tile() { return (int)(blockIdx.x & 7) * (int)(gridDim.x >> 3) + (int)(blockIdx.x >> 3); }
+inline int tail_grid_x(int n_tiles) { return (n_tiles + 7) / 8 * 8; }
+// the deblocking offsets (x 2: slice_beta_offset_div2 / slice_tc_offset_div2) of a picture of one slice
+__device__ __forceinline__ void one_slice_offsets(const PicView& v, int& beta_off, int& tc_off)
+{
+  const uint32_t w1 = gptr<uint32_t>(v.slices)[1]; // hm_slice: slice_addr | beta_offset_div2, tc_offset_div2, deblocking_disabled, sao_luma | ...
+  beta_off = 2 * (int)(int8_t)(w1 & 0xFF);
+  tc_off = 2 * (int)(int8_t)((w1 >> 8) & 0xFF);
+}
+// the tile's part of the block map into LDS (MR rows of MP 4x4 luma blocks from x0 / 4 - 2, y0 / 4 - 2: what the windows of the tile can
+// ask for), cells outside the picture clamped into it (tail_window_edges)
+template <int MP, int MR, int THREADS>
+__device__ __forceinline__ void tail_meta_copy(uint16_t* s_meta, const hm_dev_pic& dp, int x0, int y0, int tid)
+{
+  const GLOBAL_AS uint16_t* const meta = gptr<uint16_t>(dp.meta);
+  const int bx0 = (x0 >> 2) - 2, by0 = (y0 >> 2) - 2, w4 = dp.w4, h4 = dp.h4;
+  for (int i = tid; i < MR * MP; i += THREADS) {
+    const int my = i / MP, mx = i - my * MP;
+    const int bx = bx0 + mx < 0 ? 0 : (bx0 + mx < w4 ? bx0 + mx : w4 - 1), by = by0 + my < 0 ? 0 : (by0 + my < h4 ? by0 + my : h4 - 1);
+    s_meta[i] = meta[(uint32_t)(bx + mul24_raw(by, w4))];
+  }
+}
+// the edge parameters of the lane's window (kxl, kyl of the tile = kx, ky of plane c): one slice - from the copy of the block map, at the
+// crossing's block: luma (2 kx, 2 ky); chroma (4 kx, 4 ky) for 4:2:0, (4 kx, 2 ky) for 4:2:2 -, several slices - the general window_edges
+template <typename Pix, int CF>
+__device__ __forceinline__ bool tail_edges(const hm_dev_pic& dp, const PicView& v, bool one_slice, const uint16_t* s_meta, int MP, const uint8_t* s_tab, int c, int kxl, int kyl,
+                                           int kx, int ky, int PW, int PH, int beta_off, int tc_off, WindowEdges<false>& E)
+{
+  if (!one_slice) return window_edges<Pix, false>(dp, v, c, kx, ky, c ? 2 : 1, c ? (CF == 1 ? 2 : 1) : 1, E, TabLds{s_tab});
+  const int mby = c ? (CF == 1 ? 4 : 2) * kyl : 2 * kyl, mbx = c ? 4 * kxl : 2 * kxl;
+  return tail_window_edges<CF>(s_meta + (mby + 2) * MP + mbx + 2, MP, c, kx, ky, PW, PH, beta_off, tc_off, c == 0 ? 0 : (c == 1 ? dp.cb_qp_offset : dp.cr_qp_offset), s_tab, E,
+                               sizeof(Pix) == 1 ? 0 : (int)dp.bit_depth - 8); // (8-bit storage holds 8-bit pictures)
+}
+// the place of window (kxl, kyl) in an LDS tile of pitch_bytes, which starts xo samples left of the workgroup's samples and 4 rows above
+// them (bytes), and the window into it.  ALIGN: what the kernel lets the compiler know about the place - k_tail420 the four samples it is a
+// multiple of, k_tailf the sample alone (16-bit samples: one 16-byte store per row; told "8", the compiler makes it two)
+template <typename Pix>
+__device__ __forceinline__ uint32_t tail_window_place(int pitch_bytes, int xo, int kxl, int kyl) { return (uint32_t)((8 * kyl) * pitch_bytes + (8 * kxl + (xo - 4)) * (int)sizeof(Pix)); }
+template <int ALIGN, typename Pix>
+__device__ __forceinline__ void tail_window_store(uint8_t* q, int pitch_bytes, const Window<Pix>& win)
+{
+#pragma unroll
+  for (int r = 0; r < 8; r++) lds_put<ALIGN, 8 * (int)sizeof(Pix)>(q + r * pitch_bytes, win.w[r]);
+}
+
+// ---- ... and in it: the integer matrix of Op_YCbCr420_to_RGB24 / _RGB32 (yuv2rgb.cc:359-364) on sample pairs ----
+// two signed 16-bit halves -> two bytes clipped to 0..255, upper half 0
+__device__ __forceinline__ uint32_t sat_pk(uint32_t x)
+{
+  uint32_t d;
+  asm("v_sat_pk_u8_i16 %0, %1" : "=v"(d) : "v"(x));
+  return d;
+}
+// the term of both pixels of a pair: its low half on both halves of the packed add - v_pk_add_u16 with op_sel_hi:[1,0] takes it
+// from there, no splat instruction
+__device__ __forceinline__ uint32_t add_lo(uint32_t y2, int t)
+{
+  uint32_t d;
+  asm("v_pk_add_u16 %0, %1, %2 op_sel_hi:[1,0]" : "=v"(d) : "v"(y2), "v"(t));
+  return d;
+}
+// two pixels with the luma samples y2 (a pair) and the chroma sample (u, w) under them, 8 bits each: rg = R0 R1 G0 G1, bb = B0 B1 0 0
+// (24-bit multiplies: 8-bit samples x coefficients below 2^11 - as plain C the compiler picks v_mul_lo_u32, a quarter-rate
+//  instruction: the sixteen of them per lane were a tenth of k_tail420's vector issue time, r05)
+__device__ __forceinline__ void matrix_pair(uint32_t y2, int u, int w, const TailCoef& k, uint32_t& rg, uint32_t& bb)
+{
+  const int Kr = 128 - 128 * k.r_cr, Kg = 128 - 128 * (k.g_cb + k.g_cr), Kb = 128 - 128 * k.b_cb; // (x - 128) * k + 128 = x * k + K
+  const int rt = (__mul24(k.r_cr, w) + Kr) >> 8;                        // yuv2rgb.cc:359
+  const int gt = (__mul24(k.g_cb, u) + __mul24(k.g_cr, w) + Kg) >> 8;   // :360
+  const int bt = (__mul24(k.b_cb, u) + Kb) >> 8;                        // :361
+  rg = sat_pk(add_lo(y2, rt)) | (sat_pk(add_lo(y2, gt)) << 16);
+  bb = sat_pk(add_lo(y2, bt));
+}
+// four pixels (two pairs of matrix_pair) as they lie in memory: BPP 3 - R G B, three dwords; BPP 4 - R G B 255, four
+template <int BPP>
+__device__ __forceinline__ void pack_rgb(const uint32_t (&rg)[2], const uint32_t (&bb)[2], uint32_t* o)
+{
+  if (BPP == 3) {
+    const uint32_t x01 = rg[0], x23 = rg[1], b4 = bb[0] | (bb[1] << 16);
+    o[0] = __builtin_amdgcn_perm(b4, x01, 0x01040200u);                                          // R0 G0 B0 R1
+    o[1] = __builtin_amdgcn_perm(b4, __builtin_amdgcn_perm(x23, x01, 0x06040003u), 0x03020500u); // G1 B1 R2 G2
+    o[2] = __builtin_amdgcn_perm(b4, x23, 0x07030106u);                                          // B2 R3 G3 B3
+  }
+  else {
+#pragma unroll
+    for (int q = 0; q < 2; q++) {
+      o[2 * q + 0] = __builtin_amdgcn_perm(bb[q], rg[q], 0x0d040200u); // R0 G0 B0 255
+      o[2 * q + 1] = __builtin_amdgcn_perm(bb[q], rg[q], 0x0d050301u); // R1 G1 B1 255
+    }
+  }
+}
 
 // Pix = uint16_t (r06): the class of HDR photographs - 4:2:0 pictures of 9..11 bits to RGB24 / RGBA32 through the reference's shift to 8 bits and
 // the same integer matrix (hdr_sdr.cc:176-195, then yuv2rgb.cc:359-364; colour_float.h "mode 4") - on this kernel's cells, unit lists and scalar
@@ -1211,11 +1294,7 @@ __global__ __launch_bounds__(TAIL_THREADS, MINW) void k_tail420(const hm_dev_pic
   uint8_t* const s_c1 = s_c0 + TAIL_CR * CPB;
   const int bd = BPS == 1 ? 8 : (int)pics[blockIdx.y].bit_depth, maxv = (1 << bd) - 1, pre_shift = bd - 8;
   const hm_dev_pic& dp = pics[blockIdx.y];
-  // Workgroups go to the 8 XCDs in turn (linear id % 8) and every XCD has an L2 of its own: neighbouring tiles share the
-  // cache lines at their common border (the windows overlap by 4 samples, rows are read in 128-byte lines), so each XCD
-  // gets a contiguous run of the picture's tiles - gridDim.x = 8 * chunk - instead of every eighth tile.
-  const int chunk = gridDim.x >> 3;
-  const int tile = (int)(blockIdx.x & 7) * chunk + (int)(blockIdx.x >> 3);
+  const int tile = tail_tile();
   if (tile >= n_tiles) return;
   // (r06, tried and dropped: several consecutive tiles per workgroup in a loop, so that the next tile's window loads are in flight with
   //  this tile's pixel stores - 2 / 4 / 8 tiles: 8.09 -> 12.0 / 12.1 / 19.2 ms.  A wave that ENDS does not wait for its stores, a wave that
@@ -1264,6 +1343,8 @@ __global__ __launch_bounds__(TAIL_THREADS, MINW) void k_tail420(const hm_dev_pic
 #else
       if (ox >= 0) window_load(win, dp.plane[c], dp.pitch[c], ox, oy, PH);
       else { // left picture border: the window's left half does not exist (k_deblock never loads the corner window)
+        // (stated here and in k_tailf - keep the two in step: as one shared function the load cost k_tail420<16-bit> 1.7 % and k_tailf 2 %,
+        //  profiles/filters_refactor.txt)
         constexpr int HW = Window<Pix>::WORDS / 2;
 #pragma unroll
         for (int r = 0; r < 8; r++) {
@@ -1278,20 +1359,10 @@ __global__ __launch_bounds__(TAIL_THREADS, MINW) void k_tail420(const hm_dev_pic
   }
   if (tid < 106) s_tab[tid] = tid < 52 ? c_beta[tid] : c_tc[tid - 52];
   if (tid < 4) s_cnt[tid] = 0;
-  // the tile's part of the block map (4x4 luma blocks x0 / 4 - 2 .. x0 / 4 + TW / 4, y0 / 4 - 2 .. y0 / 4 + TH / 4: what the windows of
-  // the tile can ask for), cells outside the picture clamped into it (tail_window_edges)
-  constexpr int MP = TAIL_TW / 4 + 4, MR = TAIL_TH / 4 + 3;
+  constexpr int MP = TAIL_TW / 4 + 4, MR = TAIL_TH / 4 + 3; // the tile's part of the block map
   __shared__ uint16_t s_meta[MR * MP];
   const bool one_slice = dp.n_slices == 1; // (pictures of several slices: the general window_edges)
-  if (one_slice && (stages & 1) && (dp.flags & HM_PIC_DEBLOCK_ANY)) {
-    const GLOBAL_AS uint16_t* const meta = gptr<uint16_t>(dp.meta);
-    const int bx0 = (x0 >> 2) - 2, by0 = (y0 >> 2) - 2, w4 = dp.w4, h4 = dp.h4;
-    for (int i = tid; i < MR * MP; i += TAIL_THREADS) {
-      const int my = i / MP, mx = i - my * MP;
-      const int bx = bx0 + mx < 0 ? 0 : (bx0 + mx < w4 ? bx0 + mx : w4 - 1), by = by0 + my < 0 ? 0 : (by0 + my < h4 ? by0 + my : h4 - 1);
-      s_meta[i] = meta[(uint32_t)(bx + mul24_raw(by, w4))];
-    }
-  }
+  if (one_slice && (stages & 1) && (dp.flags & HM_PIC_DEBLOCK_ANY)) tail_meta_copy<MP, MR, TAIL_THREADS>(s_meta, dp, x0, y0, tid);
   // The SAO parameters of the two cells this wave converts in phase 2 (cells of 32 x 32 inside ONE CTB: UNI), requested now:
   // they arrive under phase 1, and phase 2 has no load left between its pixel stores - a wait for a load is a wait for every
   // store before it (one counter), which put the whole write latency of a cell's pixels in front of the next cell (r05: 9.2 ms
@@ -1346,45 +1417,10 @@ __global__ __launch_bounds__(TAIL_THREADS, MINW) void k_tail420(const hm_dev_pic
     }
   };
   // the filters on the listed units: strong ones (padded to whole waves), then normal ones
-#ifndef HM_TAIL_HALF_UNITS
-#define HM_TAIL_HALF_UNITS 0 // (r06 A/B: bit-exact, 53.7 instead of 52.3 lanes per vector instruction, but 231.5 k instead of 230.7 k instructions per tile
-#endif                       //  and 8.04 instead of 7.95 ms - a half unit's own set-up costs what the fuller waves save; profiles/r06_tail_probes.txt)
+  // (r06, measured and dropped: a lane per HALF unit, one pair of lines - fuller waves, 53.7 instead of 52.3 lanes per vector instruction, but more
+  //  instructions per tile and 8.04 instead of 7.95 ms: a half unit's own set-up costs what the fuller waves save; profiles/r06_tail_probes.txt)
   auto apply_units = [&](auto vertical, const uint32_t* cnt) {
     constexpr bool VV = decltype(vertical)::value;
-#if HM_TAIL_HALF_UNITS
-    static_assert(BPS == 1, "the half-unit A/B path is 8-bit only");
-    // (r06, measured and left off) a lane per HALF unit - one pair of lines, what the filters work on anyway: the ~27 strong units of a
-    // tile's direction fill one wave pass at half its cost instead of 27 of 64 lanes at the full one, the normal ones waste half a pass less
-    const uint32_t ns2 = 2u * cnt[0], nn2 = 2u * cnt[1], ns_pad = (ns2 + 63u) & ~63u;
-    for (uint32_t item = (uint32_t)tid; item < ns_pad + nn2; item += TAIL_THREADS) {
-      const bool strong = item < ns_pad;
-      if (strong && item >= ns2) continue;
-      const uint32_t idx = strong ? item : item - ns_pad, half = idx & 1u;
-      const uint32_t e = ulist[strong ? (idx >> 1) : LIST_N - 1 - (idx >> 1)];
-      const uint32_t dec = e >> 16;
-      uint32_t X[8];
-      if (VV) { // lines = rows 2 half, 2 half + 1 of the unit: eight samples across the vertical edge each
-        uint8_t* const q = s_l + (e & 0xFFFFu) + half * (2 * TAIL_LP);
-        Window<uint8_t> W; // (rows 0 and 1 only)
-        W.w[0][0] = *reinterpret_cast<const uint32_t*>(q); W.w[0][1] = *reinterpret_cast<const uint32_t*>(q + 4);
-        W.w[1][0] = *reinterpret_cast<const uint32_t*>(q + TAIL_LP); W.w[1][1] = *reinterpret_cast<const uint32_t*>(q + TAIL_LP + 4);
-        pk_gather<true, 0>(W, X);
-        if (strong) { luma_pair_strong(X, (int)(dec & 0xFF)); pk_scatter<true, 0, 1, 7>(W, X); }
-        else { luma_pair_normal(X, dec, 255); pk_scatter<true, 0, 2, 6>(W, X); }
-        *reinterpret_cast<uint32_t*>(q) = W.w[0][0]; *reinterpret_cast<uint32_t*>(q + 4) = W.w[0][1];
-        *reinterpret_cast<uint32_t*>(q + TAIL_LP) = W.w[1][0]; *reinterpret_cast<uint32_t*>(q + TAIL_LP + 4) = W.w[1][1];
-      }
-      else { // lines = columns 2 half, 2 half + 1 of the unit: eight rows across the horizontal edge, two bytes each
-        uint8_t* const q = s_l + (e & 0xFFFFu) + 2u * half;
-#pragma unroll
-        for (int r = 0; r < 8; r++) X[r] = __builtin_amdgcn_perm(0u, (uint32_t)*reinterpret_cast<const uint16_t*>(q + r * TAIL_LP), 0x0c010c00u);
-        if (strong) luma_pair_strong(X, (int)(dec & 0xFF));
-        else luma_pair_normal(X, dec, 255);
-#pragma unroll
-        for (int r = 1; r < 7; r++) *reinterpret_cast<uint16_t*>(q + r * TAIL_LP) = (uint16_t)__builtin_amdgcn_perm(0u, X[r], 0x0c0c0200u); // (p3 and q3 stay as they are)
-      }
-    }
-#else
     const uint32_t ns = cnt[0], nn = cnt[1], ns_pad = (ns + 63u) & ~63u;
     for (uint32_t item = (uint32_t)tid; item < ns_pad + nn; item += TAIL_THREADS) {
       const bool strong = item < ns_pad;
@@ -1407,14 +1443,9 @@ __global__ __launch_bounds__(TAIL_THREADS, MINW) void k_tail420(const hm_dev_pic
         for (int r = 1; r < 7; r++) lds_put<4 * BPS, 4 * BPS>(q + r * LPB, W.w[r]); // (p3 and q3 stay as they are)
       }
     }
-#endif
   };
-  int slice_beta_off = 0, slice_tc_off = 0; // one slice: its deblocking offsets (x 2: slice_beta_offset_div2 / slice_tc_offset_div2)
-  if (one_slice) {
-    const uint32_t w1 = gptr<uint32_t>(v.slices)[1]; // hm_slice: slice_addr | beta_offset_div2, tc_offset_div2, deblocking_disabled, sao_luma | ...
-    slice_beta_off = 2 * (int)(int8_t)(w1 & 0xFF);
-    slice_tc_off = 2 * (int)(int8_t)((w1 >> 8) & 0xFF);
-  }
+  int slice_beta_off = 0, slice_tc_off = 0;
+  if (one_slice) one_slice_offsets(v, slice_beta_off, slice_tc_off);
   bool luma_window = false;  // this lane holds a luma window with an edge to filter
   uint32_t woff = 0;         // ... at this place of the luma tile
   uint32_t decV0 = 0, decV1 = 0;
@@ -1426,13 +1457,7 @@ __global__ __launch_bounds__(TAIL_THREADS, MINW) void k_tail420(const hm_dev_pic
         if ((stages & 1) && (dp.flags & HM_PIC_DEBLOCK_ANY)) {
           WindowEdges<false> E;
           HM_MARK("edges_begin");
-          bool any_edge;
-          if (one_slice) {
-            // (the crossing's block: luma (2 kx, 2 ky), chroma (4 kx, 4 ky) = 2 kxl / 4 kxl columns right of the tile's first block)
-            const uint16_t* const mw = s_meta + ((c ? 4 * kyl : 2 * kyl) + 2) * MP + (c ? 4 * kxl : 2 * kxl) + 2;
-            any_edge = tail_window_edges(mw, MP, c, kx, ky, PW, PH, slice_beta_off, slice_tc_off, c == 0 ? 0 : (c == 1 ? dp.cb_qp_offset : dp.cr_qp_offset), s_tab, E, bd - 8);
-          }
-          else any_edge = window_edges<Pix, false>(dp, v, c, kx, ky, c ? 2 : 1, c ? 2 : 1, E, TabLds{s_tab});
+          const bool any_edge = tail_edges<Pix, 1>(dp, v, one_slice, s_meta, MP, s_tab, c, kxl, kyl, kx, ky, PW, PH, slice_beta_off, slice_tc_off, E);
           HM_MARK("edges_end");
           if (any_edge && c == 0) {
             luma_window = true;
@@ -1449,10 +1474,8 @@ __global__ __launch_bounds__(TAIL_THREADS, MINW) void k_tail420(const hm_dev_pic
 #endif
         uint8_t* const t0 = c == 0 ? s_l : (c == 1 ? s_c0 : s_c1);
         const int tp = c == 0 ? LPB : CPB;
-        uint8_t* q = t0 + (8 * kyl) * tp + (8 * kxl + (TAIL_XO - 4)) * BPS;
-        woff = (uint32_t)((8 * kyl) * LPB + (8 * kxl + (TAIL_XO - 4)) * BPS);
-#pragma unroll
-        for (int r = 0; r < 8; r++) lds_put<4 * BPS, 8 * BPS>(q + r * tp, win.w[r]);
+        woff = tail_window_place<Pix>(LPB, TAIL_XO, kxl, kyl);
+        tail_window_store<4 * BPS>(t0 + tail_window_place<Pix>(tp, TAIL_XO, kxl, kyl), tp, win);
       }
     }
   }
@@ -1492,7 +1515,6 @@ __global__ __launch_bounds__(TAIL_THREADS, MINW) void k_tail420(const hm_dev_pic
   const int wave = tid >> 6, lane = tid & 63;
   const bool rescale = dp.rescale != 0; // (the same for every lane of the workgroup)
   const TailDst D = dsts[blockIdx.y];
-  const int Kr = 128 - 128 * k.r_cr, Kg = 128 - 128 * (k.g_cb + k.g_cr), Kb = 128 - 128 * k.b_cb; // (x - 128) * k + 128 = x * k + K
 #pragma unroll
   for (int it = 0; it < 2; it++) {
     const int cell = wave + it * NWAVES; // 4 cells per row of the tile
@@ -1549,59 +1571,25 @@ __global__ __launch_bounds__(TAIL_THREADS, MINW) void k_tail420(const hm_dev_pic
       __builtin_memcpy(crw, &s_x[wave][1][rp][4 * BPS * gx], 4 * BPS);
       constexpr int OW = 2 * BPP; // dwords of 8 pixels
       uint32_t o[2][OW];
-      auto sat_pk = [](uint32_t x) -> uint32_t { // two signed 16-bit halves -> two bytes clipped to 0..255, upper half 0
-        uint32_t d;
-        asm("v_sat_pk_u8_i16 %0, %1" : "=v"(d) : "v"(x));
-        return d;
-      };
 #pragma unroll
       for (int h = 0; h < 2; h++) { // two chroma samples = 4 pixels of both rows
-        uint32_t rg[2][2], bb[2][2]; // [row][pair]: R0 R1 G0 G1 / B0 B1 0 0
+        uint32_t rg[2][2], bb[2][2]; // [row][pair]
 #pragma unroll
         for (int q = 0; q < 2; q++) {
           const int c = 2 * h + q;
           const int u = BPS == 1 ? (int)((cbw[0] >> (8 * c)) & 0xFF) : (int)((cbw[c >> 1] >> (16 * (c & 1))) & 0xFFFF);
           const int w = BPS == 1 ? (int)((crw[0] >> (8 * c)) & 0xFF) : (int)((crw[c >> 1] >> (16 * (c & 1))) & 0xFFFF);
+#pragma unroll
+          for (int r = 0; r < 2; r++) { // the pixels 2c, 2c + 1 of the row (the chroma terms are the same for both rows: worked out once)
 #if defined(HM_T_PROBE) && (HM_T_PROBE & 4)
-          const int rt = u, gt = w, bt = u; // probe: no matrix
+            rg[r][q] = sat_pk(add_lo(ry[r][c], u)) | (sat_pk(add_lo(ry[r][c], w)) << 16); bb[r][q] = sat_pk(add_lo(ry[r][c], u)); // probe: no matrix
 #else
-          // (24-bit multiplies: 8-bit samples x coefficients below 2^11 - as plain C the compiler picks v_mul_lo_u32, a quarter-rate
-          //  instruction: the sixteen of them per lane were a tenth of the kernel's vector issue time, r05)
-          const int rt = (__mul24(k.r_cr, w) + Kr) >> 8;                        // yuv2rgb.cc:359
-          const int gt = (__mul24(k.g_cb, u) + __mul24(k.g_cr, w) + Kg) >> 8;   // :360
-          const int bt = (__mul24(k.b_cb, u) + Kb) >> 8;                        // :361
+            matrix_pair(ry[r][c], u, w, k, rg[r][q], bb[r][q]);
 #endif
-          // (the term of both pixels of a pair: its low half on both halves of the packed add - v_pk_add_u16 with op_sel_hi:[1,0]
-          //  takes it from there, no splat instruction)
-          auto add_lo = [](uint32_t y2, int t) -> uint32_t {
-            uint32_t d;
-            asm("v_pk_add_u16 %0, %1, %2 op_sel_hi:[1,0]" : "=v"(d) : "v"(y2), "v"(t));
-            return d;
-          };
-#pragma unroll
-          for (int r = 0; r < 2; r++) {
-            const uint32_t y2 = ry[r][c]; // the pixels 2c, 2c + 1 of the row
-            const uint32_t R = sat_pk(add_lo(y2, rt)), G = sat_pk(add_lo(y2, gt)), B = sat_pk(add_lo(y2, bt));
-            rg[r][q] = R | (G << 16);
-            bb[r][q] = B;
           }
         }
 #pragma unroll
-        for (int r = 0; r < 2; r++) {
-          if (BPP == 3) {
-            const uint32_t x01 = rg[r][0], x23 = rg[r][1], b4 = bb[r][0] | (bb[r][1] << 16);
-            o[r][3 * h + 0] = __builtin_amdgcn_perm(b4, x01, 0x01040200u);                                          // R0 G0 B0 R1
-            o[r][3 * h + 1] = __builtin_amdgcn_perm(b4, __builtin_amdgcn_perm(x23, x01, 0x06040003u), 0x03020500u); // G1 B1 R2 G2
-            o[r][3 * h + 2] = __builtin_amdgcn_perm(b4, x23, 0x07030106u);                                          // B2 R3 G3 B3
-          }
-          else {
-#pragma unroll
-            for (int q = 0; q < 2; q++) {
-              o[r][4 * h + 2 * q + 0] = __builtin_amdgcn_perm(bb[r][q], rg[r][q], 0x0d040200u); // R0 G0 B0 255
-              o[r][4 * h + 2 * q + 1] = __builtin_amdgcn_perm(bb[r][q], rg[r][q], 0x0d050301u); // R1 G1 B1 255
-            }
-          }
-        }
+        for (int r = 0; r < 2; r++) pack_rgb<BPP>(rg[r], bb[r], o[r] + BPP * h);
       }
       uint8_t* o0 = D.rgb + (uint32_t)(mul24_raw(ly, D.pitch) + lx * BPP); // (an image is smaller than 4 GiB)
 #if defined(HM_T_PROBE) && (HM_T_PROBE & 32)
@@ -1654,33 +1642,8 @@ __device__ __forceinline__ void tile_sao(const hm_dev_pic& dp, const uint32_t* r
     const int y = yy - 1 + r;
     tile_row(rows[r], tile, pitch, (y < 0 ? 0 : (y < Hh ? y : Hh - 1)) - ty0, xs - tx0);
   }
-  const int cx = xs >> l2w, cy = yy >> l2h;
-  const uint32_t cflags = rec[0], s0 = rec[1 + 2 * c], s1 = rec[2 + 2 * c];
-  const SaoRow<Pix>&up = rows[0], &cur = rows[1], &dn = rows[2];
-  const bool sao_on = apply_sao && (dp.flags & HM_PIC_SAO_ENABLED) && (cflags & (c == 0 ? HM_CTB_SAO_LUMA : HM_CTB_SAO_CHROMA));
-  const int type = sao_on ? (int)(s0 & 0xFF) : 0;
-  const uint32_t offs = (s0 >> 24) | (s1 << 8);
-  const uint32_t nbm = c == 0 ? (cflags >> 8) & 0xFF : (cflags >> 16) & 0xFF;
-  const uint32_t maxv2 = ((1u << bd) - 1) * 0x10001u;
-#pragma unroll
-  for (int j = 0; j < 4; j++) res[j] = cur.p[j];
-  if (type == 1) { // band offset (fallback-postfilter.h:218-241)
-    const uint32_t bp = (s0 >> 16) & 0xFF;
-    const uint32_t biased = offs ^ 0x80808080u;
-#pragma unroll
-    for (int j = 0; j < 4; j++) {
-      u16x2 bi = (as_u(cur.p[j]) >> (u16x2)((unsigned short)(bd - 5))) - (u16x2)((unsigned short)bp);
-      bi = __builtin_elementwise_min(bi & (u16x2)(31), (u16x2)(4));
-      res[j] = pk_apply(cur.p[j], as_w(bi) | 0x0c000c00u, 0x80u, biased, maxv2);
-    }
-  }
-  else if (type == 2) {
-    const int cl = (s0 >> 8) & 0xFF;
-    if (cl == 0) sao_edge_group<Pix, -1, 0>(xs, yy, W, Hh, l2w, l2h, cx, cy, nbm, offs, maxv2, up, cur, dn, res);
-    else if (cl == 1) sao_edge_group<Pix, 0, -1>(xs, yy, W, Hh, l2w, l2h, cx, cy, nbm, offs, maxv2, up, cur, dn, res);
-    else if (cl == 2) sao_edge_group<Pix, -1, -1>(xs, yy, W, Hh, l2w, l2h, cx, cy, nbm, offs, maxv2, up, cur, dn, res);
-    else sao_edge_group<Pix, 1, -1>(xs, yy, W, Hh, l2w, l2h, cx, cy, nbm, offs, maxv2, up, cur, dn, res);
-  }
+  sao_group<Pix>(apply_sao && (dp.flags & HM_PIC_SAO_ENABLED), c, rec[0], rec[1 + 2 * c], rec[2 + 2 * c], bd - 5, ((1u << bd) - 1) * 0x10001u, xs, yy, W, Hh, l2w, l2h, xs >> l2w, yy >> l2h,
+                 rows[0], rows[1], rows[2], res);
 }
 
 // Tile height by chroma format (r06): a lane of phase 2 takes 16 luma samples of TWO rows of a 4:2:0 picture - tiles of 32 rows gave it 128
@@ -1711,8 +1674,7 @@ __global__ __launch_bounds__(TF_THREADS) void k_tailf(const hm_dev_pic* __restri
   __shared__ uint16_t s_meta[MR * MP];
   __shared__ uint32_t s_rec[NREC][8];
   const hm_dev_pic& dp = pics[blockIdx.y];
-  const int chunk = gridDim.x >> 3; // (workgroups go to the XCDs in turn: a contiguous run of tiles per XCD, as in k_tail420)
-  const int tile = (int)(blockIdx.x & 7) * chunk + (int)(blockIdx.x >> 3);
+  const int tile = tail_tile();
   if (tile >= n_tiles) return;
   const int ty = tile / tiles_x, tx = tile - ty * tiles_x;
   const int x0 = tx * TF_TW, y0 = ty * TF_TH;
@@ -1727,11 +1689,7 @@ __global__ __launch_bounds__(TF_THREADS) void k_tailf(const hm_dev_pic* __restri
   const bool one_slice = dp.n_slices == 1; // (pictures of several slices: the general window_edges)
   const bool deblock = (stages & 1) && (dp.flags & HM_PIC_DEBLOCK_ANY);
   int slice_beta_off = 0, slice_tc_off = 0;
-  if (one_slice) {
-    const uint32_t w1 = gptr<uint32_t>(v.slices)[1]; // hm_slice: slice_addr | beta_offset_div2, tc_offset_div2, ...
-    slice_beta_off = 2 * (int)(int8_t)(w1 & 0xFF);
-    slice_tc_off = 2 * (int)(int8_t)((w1 >> 8) & 0xFF);
-  }
+  if (one_slice) one_slice_offsets(v, slice_beta_off, slice_tc_off);
   // ---- phase 1: deblocked samples of the tile (+ 4 around it) into LDS, one lane per window ----
   // The lane's window loads go out first; the records of the tile's CTBs and the block map are requested behind them: one trip to
   // memory for all of it.
@@ -1755,6 +1713,8 @@ __global__ __launch_bounds__(TF_THREADS) void k_tailf(const hm_dev_pic* __restri
     if (kx <= ((PW + 7) >> 3) && ky <= ((PH + 7) >> 3)) {
       have_window = true;
       const int ox = (kx << 3) - 4, oy = (ky << 3) - 4;
+      // (as in k_tail420 - keep the two in step: through one shared function this kernel's 10-bit 4:2:2 -> RRGGBB instance ran at 0.462 instead
+      //  of 0.453 ms, profiles/filters_refactor.txt)
       if (ox >= 0) window_load(win, dp.plane[c], dp.pitch[c], ox, oy, PH);
       else { // left picture border: the window's left half does not exist
         constexpr int HW = Window<Pix>::WORDS / 2;
@@ -1780,35 +1740,16 @@ __global__ __launch_bounds__(TF_THREADS) void k_tailf(const hm_dev_pic* __restri
       rec_word = gptr<uint32_t>(reinterpret_cast<const uint8_t*>(v.ctbs) + (uint32_t)(qx + qy * dp.ctb_w) * (uint32_t)sizeof(hm_ctb))[2 + k];
     }
   }
-  if (one_slice && deblock) {
-    const GLOBAL_AS uint16_t* const meta = gptr<uint16_t>(dp.meta);
-    const int bx0 = (x0 >> 2) - 2, by0 = (y0 >> 2) - 2, w4 = dp.w4, h4 = dp.h4;
-    for (int i = tid; i < MR * MP; i += TF_THREADS) {
-      const int my = i / MP, mx = i - my * MP;
-      const int bx = bx0 + mx < 0 ? 0 : (bx0 + mx < w4 ? bx0 + mx : w4 - 1), by = by0 + my < 0 ? 0 : (by0 + my < h4 ? by0 + my : h4 - 1);
-      s_meta[i] = meta[(uint32_t)(bx + mul24_raw(by, w4))];
-    }
-  }
+  if (one_slice && deblock) tail_meta_copy<MP, MR, TF_THREADS>(s_meta, dp, x0, y0, tid);
   __syncthreads(); // (the block map and the tables are there)
   if (tid < NREC * 8) s_rec[tid >> 3][tid & 7] = rec_word;
   if (have_window) {
     if (deblock) {
       WindowEdges<false> E;
-      bool any_edge;
-      if (one_slice) {
-        // (the crossing's block: luma (2 kx, 2 ky); chroma (4 kx, 4 ky) for 4:2:0, (4 kx, 2 ky) for 4:2:2)
-        const int mby = c ? (CF == 1 ? 4 : 2) * kyl : 2 * kyl, mbx = c ? 4 * kxl : 2 * kxl;
-        any_edge = tail_window_edges<CF>(s_meta + (mby + 2) * MP + mbx + 2, MP, c, kx, ky, PW, PH, slice_beta_off, slice_tc_off,
-                                         c == 0 ? 0 : (c == 1 ? dp.cb_qp_offset : dp.cr_qp_offset), s_tab, E, bd - 8);
-      }
-      else any_edge = window_edges<Pix, false>(dp, v, c, kx, ky, c ? 2 : 1, c ? (CF == 1 ? 2 : 1) : 1, E, TabLds{s_tab});
-      if (any_edge) window_filter<Pix, false>(win, c, E, maxv);
+      if (tail_edges<Pix, CF>(dp, v, one_slice, s_meta, MP, s_tab, c, kxl, kyl, kx, ky, PW, PH, slice_beta_off, slice_tc_off, E)) window_filter<Pix, false>(win, c, E, maxv);
     }
-    Pix* const t0 = c == 0 ? s_l : s_c[c - 1];
-    const int tp = c == 0 ? LP : CP;
-    Pix* const q = t0 + (8 * kyl) * tp + 8 * kxl + (TF_XO - 4);
-#pragma unroll
-    for (int r = 0; r < 8; r++) __builtin_memcpy(q + r * tp, win.w[r], 8 * sizeof(Pix));
+    const int tp = (c == 0 ? LP : CP) * (int)sizeof(Pix);
+    tail_window_store<(int)sizeof(Pix)>(reinterpret_cast<uint8_t*>(c == 0 ? s_l : s_c[c - 1]) + tail_window_place<Pix>(tp, TF_XO, kxl, kyl), tp, win);
   }
   // (said explicitly: no load is outstanding when phase 2 begins - nothing in it refers to one any more, and the compiler's wait
   //  insertion must not guard register reuse there with waits for "everything", i.e. for the pixel stores of the lane's previous group)
@@ -1860,9 +1801,7 @@ __global__ __launch_bounds__(TF_THREADS) void k_tailf(const hm_dev_pic* __restri
           if (fp.mode == 4 && fp.post == 0 && nvalid == 8) { // (the same for every lane but the last group of a cropped row)
             constexpr int OW = 2 * OBPP;
             uint32_t wd[OW];
-            auto sat_pk = [](uint32_t x) -> uint32_t { uint32_t d; asm("v_sat_pk_u8_i16 %0, %1" : "=v"(d) : "v"(x)); return d; };
-            auto add_lo = [](uint32_t y2, int t) -> uint32_t { uint32_t d; asm("v_pk_add_u16 %0, %1, %2 op_sel_hi:[1,0]" : "=v"(d) : "v"(y2), "v"(t)); return d; };
-            const int Kr = 128 - 128 * fp.i_r_cr, Kg = 128 - 128 * (fp.i_g_cb + fp.i_g_cr), Kb = 128 - 128 * fp.i_b_cb; // (x - 128) * k + 128 = x * k + K
+            const TailCoef k{fp.i_r_cr, fp.i_g_cb, fp.i_g_cr, fp.i_b_cb};
 #pragma unroll
             for (int h = 0; h < 2; h++) { // two chroma samples = 4 pixels
               uint32_t rg[2], bb[2];
@@ -1870,27 +1809,9 @@ __global__ __launch_bounds__(TF_THREADS) void k_tailf(const hm_dev_pic* __restri
               for (int q = 0; q < 2; q++) {
                 const int j = 2 * h + q, ci = 4 * half + j; // the pair of pixels 2 j, 2 j + 1 and its chroma sample
                 const int u = (int)(((cbs[ci >> 1] >> (16 * (ci & 1))) & 0xFFFF) >> fp.pre_shift), w = (int)(((crs[ci >> 1] >> (16 * (ci & 1))) & 0xFFFF) >> fp.pre_shift);
-                const int rt = (__mul24(fp.i_r_cr, w) + Kr) >> 8;
-                const int gt = (__mul24(fp.i_g_cb, u) + __mul24(fp.i_g_cr, w) + Kg) >> 8;
-                const int bt = (__mul24(fp.i_b_cb, u) + Kb) >> 8;
-                const uint32_t y2 = as_w(as_u(ry[j]) >> (u16x2)((unsigned short)fp.pre_shift));
-                const uint32_t R = sat_pk(add_lo(y2, rt)), G = sat_pk(add_lo(y2, gt)), B = sat_pk(add_lo(y2, bt));
-                rg[q] = R | (G << 16);
-                bb[q] = B;
+                matrix_pair(as_w(as_u(ry[j]) >> (u16x2)((unsigned short)fp.pre_shift)), u, w, k, rg[q], bb[q]);
               }
-              if (OBPP == 3) {
-                const uint32_t x01 = rg[0], x23 = rg[1], b4 = bb[0] | (bb[1] << 16);
-                wd[3 * h + 0] = __builtin_amdgcn_perm(b4, x01, 0x01040200u);                                          // R0 G0 B0 R1
-                wd[3 * h + 1] = __builtin_amdgcn_perm(b4, __builtin_amdgcn_perm(x23, x01, 0x06040003u), 0x03020500u); // G1 B1 R2 G2
-                wd[3 * h + 2] = __builtin_amdgcn_perm(b4, x23, 0x07030106u);                                          // B2 R3 G3 B3
-              }
-              else {
-#pragma unroll
-                for (int q = 0; q < 2; q++) {
-                  wd[4 * h + 2 * q + 0] = __builtin_amdgcn_perm(bb[q], rg[q], 0x0d040200u); // R0 G0 B0 255
-                  wd[4 * h + 2 * q + 1] = __builtin_amdgcn_perm(bb[q], rg[q], 0x0d050301u); // R1 G1 B1 255
-                }
-              }
+              pack_rgb<OBPP>(rg, bb, wd + OBPP * h);
             }
             __builtin_memcpy(gptr_w<uint8_t>(o0), wd, 8 * OBPP);
             continue;
@@ -1997,7 +1918,7 @@ static int launch_tail420(const hm_dev_pic* d_pics, const void* d_dsts, int n_pi
   if (n_pics <= 0) return HM_OK;
   __atomic_store_n(&g_tail_last_launch, sizeof(Pix) == 1 ? 1 : 2, __ATOMIC_RELAXED);
   const int tiles_x = (max_w + TAIL_TW - 1) / TAIL_TW, tiles_y = (max_h + TAIL_TH - 1) / TAIL_TH;
-  const dim3 grid((tiles_x * tiles_y + 7) / 8 * 8, n_pics); // (a multiple of 8: see the tile mapping in the kernel)
+  const dim3 grid(tail_grid_x(tiles_x * tiles_y), n_pics);
   const TailCoef k{coef[0], coef[1], coef[2], coef[3]};
   const TailDst* dd = (const TailDst*)d_dsts;
   // (8-bit samples: 59 VGPRs and 20 KB of LDS - eight workgroups per CU; 16-bit samples: 70 VGPRs, 39 KB - four.  tests/test_chain_modes_gpu.py holds the
@@ -2026,8 +1947,8 @@ extern "C" int hm_launch_tail420(const hm_dev_pic* d_pics, const void* d_dsts, i
 template <typename Pix, int CF>
 static int launch_tailf(const hm_dev_pic* d_pics, const TailDst* dd, int n_pics, int tiles_x, int tiles_y, int out_format, int stages, const FloatParams& fp, hipStream_t s)
 {
-  const dim3 grid((tiles_x * tiles_y + 7) / 8 * 8, n_pics);
   const int nt = tiles_x * tiles_y;
+  const dim3 grid(tail_grid_x(nt), n_pics);
   __atomic_store_n(&g_tail_last_launch, 3 + 2 * (CF - 1) + (sizeof(Pix) == 1 ? 0 : 1), __ATOMIC_RELAXED);
   switch (out_format) {
     case HM_OUT_RGB: hipLaunchKernelGGL((k_tailf<Pix, CF, OF_RGB24>), grid, dim3(TF_THREADS), 0, s, d_pics, dd, tiles_x, nt, stages, fp); break;
