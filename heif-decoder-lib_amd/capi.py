@@ -170,6 +170,21 @@ class DeviceLight(C.Structure):
 
 
 HM_LIGHT_LINEAR = 8
+HM_LIGHT_FROM_ICC = -1  # in from_transfer AND from_primaries: the item's ICC profile is the source
+HM_ICC_RGB, HM_ICC_GRAY = 1, 2
+HM_ICC_CURVE_IDENTITY, HM_ICC_CURVE_GAMMA, HM_ICC_CURVE_TABLE, HM_ICC_CURVE_PARA = 0, 1, 2, 3
+HM_ICC_NO_PROFILE = 1   # hm_file_item_icc_info: the item has none
+
+
+class IccCurve(C.Structure):
+    """hm_icc_curve: kind (HM_ICC_CURVE_*), count ('curv': entries, 'para': function type), p = g a b c d e f"""
+    _fields_ = [("kind", C.c_int32), ("count", C.c_int32), ("p", C.c_double * 7)]
+
+
+class IccInfo(C.Structure):
+    """hm_icc_info: what hm_icc_parse reports of a matrix/TRC profile"""
+    _fields_ = [("version_major", C.c_int32), ("version_minor", C.c_int32), ("colour_space", C.c_int32), ("same_curves", C.c_int32), ("has_cicp", C.c_int32),
+                ("cicp", C.c_int32 * 4), ("cicp_known", C.c_int32), ("colorant", C.c_double * 9), ("curve", IccCurve * 3)]
 
 
 class DeviceTone(C.Structure):
@@ -369,6 +384,12 @@ def bind_image(L):
                                      C.c_void_p]
     L.hm_light_table.argtypes = [C.c_int, C.c_int, C.c_float, C.c_int, C.POINTER(C.c_float)]
     L.hm_light_matrix.argtypes = [C.c_int, C.c_int, C.POINTER(C.c_float * 9)]
+    L.hm_icc_parse.argtypes = [C.c_char_p, C.c_size_t, C.POINTER(IccInfo)]
+    L.hm_icc_table.argtypes = [C.c_char_p, C.c_size_t, C.c_int, C.c_int, C.c_float, C.POINTER(C.c_float)]
+    L.hm_icc_matrix.argtypes = [C.c_char_p, C.c_size_t, C.c_int, C.POINTER(C.c_float * 9)]
+    L.hm_file_item_icc_info.argtypes = [C.c_void_p, C.c_uint32, C.POINTER(IccInfo)]
+    L.hm_icc_to_tensor.argtypes = [C.c_int, C.c_int, C.c_int, C.c_int, C.c_void_p, C.c_int, C.POINTER(DeviceView), C.c_char_p, C.c_size_t, C.POINTER(DeviceLight),
+                                   C.POINTER(DeviceTone), C.POINTER(DeviceAlpha), C.POINTER(DeviceDest), C.c_void_p]
     L.hm_tone_to_tensor.argtypes = [C.c_int, C.c_int, C.c_int, C.c_int, C.c_void_p, C.c_int, C.POINTER(DeviceView), C.POINTER(DeviceLight), C.POINTER(DeviceTone),
                                     C.POINTER(DeviceDest), C.c_void_p]
     L.hm_tone_table.argtypes = [C.POINTER(DeviceTone), C.c_float, C.c_int, C.POINTER(C.c_float)]

@@ -110,42 +110,47 @@ __global__ __launch_bounds__(256) void k_alpha_nearest(const uint8_t* __restrict
 template <int SB, bool CHW, bool LIT>
 __global__ __launch_bounds__(256) void k_alpha_h(const uint8_t* __restrict__ src, int src_stride, int n_h, int ow, const int32_t* __restrict__ first,
                                                  const int32_t* __restrict__ count, const float* __restrict__ wts, float* __restrict__ tmp,
-                                                 long long pitch, long long plane, const float* __restrict__ lin, int bits, int whole)
+                                                 long long pitch, long long plane, const float* __restrict__ lin, int bits, int whole, int lin3)
 {
   extern __shared__ __attribute__((aligned(16))) float lds[];
   typedef typename std::conditional<SB == 1, uint8_t, uint16_t>::type InT;
-  if constexpr (LIT) fill_tables(lds, lin, 1 << bits);
+  if constexpr (LIT) fill_tables(lds, lin, (lin3 ? 3 : 1) << bits);
   const int j = blockIdx.x * 64 + (threadIdx.x & 63), y = blockIdx.y * 4 + (threadIdx.x >> 6);
   if (j >= ow || y >= n_h) return;
   const uint8_t* in = src + (size_t)y * src_stride + (size_t)first[j] * (4 * SB);
   const int n = count[j];
   const unsigned peak = (1u << bits) - 1u;
   float t[4] = {0.0f, 0.0f, 0.0f, 0.0f};
-  auto tap = [&](float w, const unsigned (&v)[4]) {
-    const float av = (float)v[3];
+  // look: a colour sample to the float that is summed (LIT: LinLookup / LinLookup3 of light_step.h)
+  auto sums = [&](auto look) {
+    auto tap = [&](float w, const unsigned (&v)[4]) {
+      const float av = (float)v[3];
 #pragma unroll
-    for (int c = 0; c < 3; c++) {
-      float x;
-      if constexpr (LIT) x = lds[min(v[c], peak)];
-      else x = (float)v[c];
-      t[c] = __fadd_rn(t[c], __fmul_rn(w, __fmul_rn(x, av)));
+      for (int c = 0; c < 3; c++) {
+        float x;
+        if constexpr (LIT) x = look.colour(v[c], c);
+        else x = (float)v[c];
+        t[c] = __fadd_rn(t[c], __fmul_rn(w, __fmul_rn(x, av)));
+      }
+      t[3] = __fadd_rn(t[3], __fmul_rn(w, av));
+    };
+    if (whole) { // (wave-uniform)
+      for (int i = 0; i < n; i++) {
+        unsigned v[4];
+        load_samples<SB, 4>(in + (size_t)i * (4 * SB), v);
+        tap(wts[(size_t)i * ow + j], v);
+      }
     }
-    t[3] = __fadd_rn(t[3], __fmul_rn(w, av));
+    else {
+      const InT* ip = reinterpret_cast<const InT*>(in);
+      for (int i = 0; i < n; i++) {
+        const unsigned v[4] = {ip[i * 4], ip[i * 4 + 1], ip[i * 4 + 2], ip[i * 4 + 3]};
+        tap(wts[(size_t)i * ow + j], v);
+      }
+    }
   };
-  if (whole) { // (wave-uniform)
-    for (int i = 0; i < n; i++) {
-      unsigned v[4];
-      load_samples<SB, 4>(in + (size_t)i * (4 * SB), v);
-      tap(wts[(size_t)i * ow + j], v);
-    }
-  }
-  else {
-    const InT* ip = reinterpret_cast<const InT*>(in);
-    for (int i = 0; i < n; i++) {
-      const unsigned v[4] = {ip[i * 4], ip[i * 4 + 1], ip[i * 4 + 2], ip[i * 4 + 3]};
-      tap(wts[(size_t)i * ow + j], v);
-    }
-  }
+  if (LIT && lin3) sums(LinLookup3{lds, peak, bits}); // (wave-uniform: a table per channel)
+  else sums(LinLookup{lds, peak});
   float* o = tmp + (long long)y * pitch;
 #pragma unroll
   for (int c = 0; c < 4; c++) {
@@ -275,14 +280,14 @@ void launch_h(bool chw, const hm_resample_args* r, const hm_light_args* la, hipS
   const uint8_t* src = (const uint8_t*)r->src;
   const size_t lds = LIT ? light_h_bytes(la) : 0;
   const float* lin = LIT ? la->lin : nullptr;
-  const int bits = LIT ? la->bits : 8;
+  const int bits = LIT ? la->bits : 8, lin3 = LIT ? la->lin3 : 0;
   const int whole = ((uintptr_t)src % (4 * SB)) == 0 && (r->src_stride % (4 * SB)) == 0 ? 1 : 0;
   if (chw)
     hipLaunchKernelGGL((k_alpha_h<SB, true, LIT>), grid, block, lds, s, src, r->src_stride, r->n_h, r->ow, r->ax.first, r->ax.count, r->ax.weights, r->tmp,
-                       (long long)r->tmp_pitch, (long long)r->tmp_plane, lin, bits, whole);
+                       (long long)r->tmp_pitch, (long long)r->tmp_plane, lin, bits, whole, lin3);
   else
     hipLaunchKernelGGL((k_alpha_h<SB, false, LIT>), grid, block, lds, s, src, r->src_stride, r->n_h, r->ow, r->ax.first, r->ax.count, r->ax.weights, r->tmp,
-                       (long long)r->tmp_pitch, (long long)r->tmp_plane, lin, bits, whole);
+                       (long long)r->tmp_pitch, (long long)r->tmp_plane, lin, bits, whole, lin3);
 }
 
 template <typename OutT, bool LIT>
@@ -314,8 +319,8 @@ int check_args(const hm_dest_plan* p, const hm_light_args* la, const hm_alpha_ar
   if (!la->lin || (la->encode && !la->enc) || la->bits != aa->bits || la->bits > HM_LIGHT_MAX_BITS || la->src_bytes != aa->src_bytes)
     return hm_fail(HM_ERR_INTERNAL, "k_alpha: light tables of %d bits beside samples of %d", la->bits, aa->bits);
   if (integer && !la->encode) return hm_fail(HM_ERR_INTERNAL, "k_alpha: integer dtype %d for linear light", p->dtype);
-  const int rc = check_light_args("k_alpha", p, la); // (what is left of it: the codes' width, the target's samples, the integer dtype's width)
-  if (rc) return rc;
+  int rc = check_light_args("k_alpha", p, la); // (what is left of it: the codes' width, the target's samples, the integer dtype's width)
+  if (rc || (rc = summed ? check_light_lds(la, 1) : check_light_lds(la, 0)) || (summed && (rc = check_light_lds(la, 2)))) return rc;
   if (aa->mode == HM_ALPHA_PREMULTIPLIED && (la->encode || la->tone)) return hm_fail(HM_ERR_INTERNAL, "k_alpha: premultiplied light is not encoded or tone-mapped");
   return HM_OK;
 }

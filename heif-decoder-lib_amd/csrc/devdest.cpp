@@ -16,8 +16,10 @@
 #include "hm_colour_plan.h"
 #include "hm_devdest.h"
 #include "hm_entry_steps.h"
+#include "hm_icc.h"
 #include "hm_plane_geom.h"
 #include "hm_planes_view.h"
+#include "hm_primaries.h"
 #include "hm_view_batch.h"
 
 extern "C" {
@@ -611,8 +613,7 @@ int with_scratch(hipStream_t s, const std::function<int(hm_view_scratch*)>& writ
 
 namespace {
 
-bool transfer_known(int t) { return t == 1 || t == 4 || t == 5 || t == 6 || t == 8 || t == 13 || t == 14 || t == 15 || t == 16 || t == 18; }
-bool primaries_known(int p) { return p == 1 || p == 5 || p == 6 || p == 7 || p == 9 || p == 12; }
+using hm_light::transfer_known; using hm_light::primaries_known; using hm_light::primaries_to_xyz; using hm_light::invert3; // (hm_primaries.h)
 
 // F_t: the code-to-light function of transfer t at e in [0, 1] (include/heif_mi355x.h), in double
 double light_of_code(int t, double e)
@@ -647,44 +648,6 @@ void fill_light_table(int transfer, int bits, double g, bool encode, float* out)
   for (int c = 1; c < n; c++) out[c] = (float)(g * light_of_code(transfer, ((double)c - 0.5) / peak));
 }
 
-// RGB -> XYZ of a set of primaries (H.273 chromaticities, D65 white), row-major
-bool primaries_to_xyz(int code, double M[9])
-{
-  double x[3], y[3];
-  switch (code) {
-    case 1: x[0] = 0.640; y[0] = 0.330; x[1] = 0.300; y[1] = 0.600; x[2] = 0.150; y[2] = 0.060; break;
-    case 5: x[0] = 0.640; y[0] = 0.330; x[1] = 0.290; y[1] = 0.600; x[2] = 0.150; y[2] = 0.060; break;
-    case 6: case 7: x[0] = 0.630; y[0] = 0.340; x[1] = 0.310; y[1] = 0.595; x[2] = 0.155; y[2] = 0.070; break;
-    case 9: x[0] = 0.708; y[0] = 0.292; x[1] = 0.170; y[1] = 0.797; x[2] = 0.131; y[2] = 0.046; break;
-    case 12: x[0] = 0.680; y[0] = 0.320; x[1] = 0.265; y[1] = 0.690; x[2] = 0.150; y[2] = 0.060; break;
-    default: return false;
-  }
-  const double xw = 0.3127, yw = 0.3290;
-  double P[9]; // columns: the primaries' XYZ at Y = 1
-  for (int k = 0; k < 3; k++) { P[k] = x[k] / y[k]; P[3 + k] = 1.0; P[6 + k] = (1.0 - x[k] - y[k]) / y[k]; }
-  const double W[3] = {xw / yw, 1.0, (1.0 - xw - yw) / yw};
-  // S = P^-1 W by Cramer's rule
-  auto det3 = [](const double* a) { return a[0] * (a[4] * a[8] - a[5] * a[7]) - a[1] * (a[3] * a[8] - a[5] * a[6]) + a[2] * (a[3] * a[7] - a[4] * a[6]); };
-  const double d = det3(P);
-  for (int k = 0; k < 3; k++) {
-    double Q[9];
-    std::memcpy(Q, P, sizeof(Q));
-    for (int r = 0; r < 3; r++) Q[3 * r + k] = W[r];
-    const double S = det3(Q) / d;
-    for (int r = 0; r < 3; r++) M[3 * r + k] = P[3 * r + k] * S;
-  }
-  return true;
-}
-
-void invert3(const double a[9], double inv[9])
-{
-  const double c00 = a[4] * a[8] - a[5] * a[7], c01 = a[5] * a[6] - a[3] * a[8], c02 = a[3] * a[7] - a[4] * a[6];
-  const double d = a[0] * c00 + a[1] * c01 + a[2] * c02;
-  inv[0] = c00 / d; inv[1] = (a[2] * a[7] - a[1] * a[8]) / d; inv[2] = (a[1] * a[5] - a[2] * a[4]) / d;
-  inv[3] = c01 / d; inv[4] = (a[0] * a[8] - a[2] * a[6]) / d; inv[5] = (a[2] * a[3] - a[0] * a[5]) / d;
-  inv[6] = c02 / d; inv[7] = (a[1] * a[6] - a[0] * a[7]) / d; inv[8] = (a[0] * a[4] - a[1] * a[3]) / d;
-}
-
 } // namespace
 
 int hm_light_table(int transfer, int bits, float gain, int encode, float* out)
@@ -716,8 +679,9 @@ int hm_light_matrix(int from_primaries, int to_primaries, float m[9])
 }
 
 // dest_format: the target the destination is judged by (hm_out_dest_format)
-static int light_check(int out_format, int dest_format, const hm_device_dest* d, const hm_device_light* l, int explicit_from)
+static int light_check(int out_format, int dest_format, const hm_device_dest* d, const hm_out_steps* st, int explicit_from)
 {
+  const hm_device_light* l = st->light;
   if (!l) return hm_fail(HM_ERR_INVALID_ARG, "null light step");
   int rc = hm_dest_check_static(dest_format, d);
   if (rc) return rc;
@@ -725,9 +689,12 @@ static int light_check(int out_format, int dest_format, const hm_device_dest* d,
   if (!std::isfinite(l->gain) || !(l->gain > 0.0f)) return hm_fail(HM_ERR_INVALID_ARG, "light: gain %g is not finite and above 0", (double)l->gain);
   if (explicit_from && (l->from_transfer == 0 || l->from_primaries == 0))
     return hm_fail(HM_ERR_INVALID_ARG, "light: from_transfer and from_primaries must be given: the pixels carry no profile");
-  if (l->from_transfer != 0 && !transfer_known(l->from_transfer)) return hm_fail(HM_ERR_UNSUPPORTED, "light: transfer characteristics %d are not supported", l->from_transfer);
+  const bool from_icc = hm_light_from_icc(l);
+  if (const int rc = hm_entry_icc(*st, nullptr)) return rc; // (the sentinel in one field only)
+  if (from_icc && !st->icc) return hm_fail(HM_ERR_UNSUPPORTED, "light: HM_LIGHT_FROM_ICC without a profile to read");
+  if (!from_icc && l->from_transfer != 0 && !transfer_known(l->from_transfer)) return hm_fail(HM_ERR_UNSUPPORTED, "light: transfer characteristics %d are not supported", l->from_transfer);
   if (!transfer_known(l->to_transfer)) return hm_fail(HM_ERR_UNSUPPORTED, "light: transfer characteristics %d are not supported", l->to_transfer);
-  if (l->from_primaries != 0 && !primaries_known(l->from_primaries)) return hm_fail(HM_ERR_UNSUPPORTED, "light: colour primaries %d are not supported", l->from_primaries);
+  if (!from_icc && l->from_primaries != 0 && !primaries_known(l->from_primaries)) return hm_fail(HM_ERR_UNSUPPORTED, "light: colour primaries %d are not supported", l->from_primaries);
   if (l->to_primaries != 0 && !primaries_known(l->to_primaries)) return hm_fail(HM_ERR_UNSUPPORTED, "light: colour primaries %d are not supported", l->to_primaries);
   if (out_format == HM_OUT_RRGGBB_BE || out_format == HM_OUT_RRGGBBAA_BE)
     return hm_fail(HM_ERR_INVALID_ARG, "light: a big-endian target has no sample values to look up: ask for the _LE format");
@@ -737,11 +704,39 @@ static int light_check(int out_format, int dest_format, const hm_device_dest* d,
 }
 
 // the plan of a light step whose static checks have passed (light_check)
-static int light_plan_of(int out_format, int bits, int img_transfer, int img_primaries, const hm_device_light* l, hm_light_plan* lp)
+// icc, icc_size: the request's profile (hm_out_steps), read when l carries HM_LIGHT_FROM_ICC
+static int light_plan_of(int out_format, int bits, int img_transfer, int img_primaries, const hm_device_light* l, const uint8_t* icc, size_t icc_size, hm_light_plan* lp)
 {
   std::memset(lp, 0, sizeof(*lp));
   lp->from_transfer = l->from_transfer ? l->from_transfer : img_transfer;
   lp->from_primaries = l->from_primaries ? l->from_primaries : img_primaries;
+  hm_icc::Profile prof;
+  if (hm_light_from_icc(l)) {
+    if (!icc) return hm_fail(HM_ERR_UNSUPPORTED, "light: HM_LIGHT_FROM_ICC without a profile to read");
+    const int rc = hm_icc::parse(icc, icc_size, &prof);
+    if (rc) return rc;
+    if (prof.cicp_known) { lp->from_primaries = prof.cicp[0]; lp->from_transfer = prof.cicp[1]; } // the cicp tag stands for the profile: the path of the codes, unchanged
+    else { lp->icc = 1; lp->icc_data = icc; lp->icc_size = icc_size; }
+  }
+  if (lp->icc) {
+    lp->to_transfer = l->to_transfer;
+    lp->to_primaries = l->to_primaries; // (0: the profile's own primaries, which have no code)
+    const int sb = hm_out_bytes_per_pixel(out_format) >= 6 ? 2 : 1;
+    if (sb == 1) bits = 8;
+    if (bits < 8 || bits > HM_LIGHT_MAX_BITS) return hm_fail(HM_ERR_UNSUPPORTED, "light: samples of %d bits (8 .. %d are supported)", bits, (int)HM_LIGHT_MAX_BITS);
+    lp->bits = bits; lp->enc_bits = bits;
+    lp->encode = lp->to_transfer != HM_LIGHT_LINEAR;
+    lp->gain = l->gain;
+    if (!prof.same_curves) { // three tables only where they differ at this depth
+      std::vector<float> t((size_t)3 << bits);
+      for (int c = 0; c < 3; c++) hm_icc::fill_table(prof.curve[c], bits, (double)l->gain, t.data() + ((size_t)c << bits));
+      const size_t n = (size_t)sizeof(float) << bits;
+      lp->lin3 = std::memcmp(t.data(), t.data() + ((size_t)1 << bits), n) != 0 || std::memcmp(t.data(), t.data() + ((size_t)2 << bits), n) != 0;
+    }
+    lp->matrix = lp->to_primaries != 0;
+    if (lp->matrix) hm_icc::matrix_to(prof, lp->to_primaries, lp->m);
+    return HM_OK;
+  }
   if (!transfer_known(lp->from_transfer)) return hm_fail(HM_ERR_UNSUPPORTED, "light: the image's transfer characteristics %d are not supported", lp->from_transfer);
   if (!primaries_known(lp->from_primaries)) return hm_fail(HM_ERR_UNSUPPORTED, "light: the image's colour primaries %d are not supported", lp->from_primaries);
   lp->to_transfer = l->to_transfer;
@@ -837,6 +832,7 @@ static int tone_plan_of(const hm_device_tone* tone, hm_light_plan* lp)
   // behind an OOTF step (resolved into lp already) light value g stands for display_peak, and nothing brighter comes out of it
   const float unit_nits = tone->unit_nits != 0.0f ? tone->unit_nits : lp->ootf ? lp->ootf_peak : 0.0f;
   const float src_peak = tone->src_peak != 0.0f ? tone->src_peak : lp->ootf ? lp->ootf_peak : 0.0f;
+  if (unit_nits == 0.0f && lp->icc) return hm_fail(HM_ERR_INVALID_ARG, "tone: unit_nits must be given for an ICC profile as the source (no profile says what 1.0 stands for)");
   if (unit_nits == 0.0f && lp->from_transfer != 16)
     return hm_fail(HM_ERR_INVALID_ARG, "tone: unit_nits must be given for transfer characteristics %d (only PQ says what 1.0 stands for)", lp->from_transfer);
   if (src_peak == 0.0f) return hm_fail(HM_ERR_INVALID_ARG, "tone: src_peak must be given: the pixels carry no light levels"); // (else the knee has been judged)
@@ -905,6 +901,8 @@ int ootf_check_request(const hm_out_steps* st)
   if (!l) return hm_fail(HM_ERR_INVALID_ARG, "ootf: null light step");
   const int rc = ootf_check(o);
   if (rc) return rc;
+  if (l->from_transfer == HM_LIGHT_FROM_ICC || l->from_primaries == HM_LIGHT_FROM_ICC)
+    return hm_fail(HM_ERR_UNSUPPORTED, "ootf: HM_LIGHT_FROM_ICC beside the OOTF step (it renders HLG scene light, which no matrix/TRC profile describes)");
   if (st->gain) return hm_fail(HM_ERR_UNSUPPORTED, "ootf: a gain step beside the OOTF step is not supported (a gain map's base is SDR)");
   if (st->alpha && st->alpha->mode == HM_ALPHA_PREMULTIPLIED)
     return hm_fail(HM_ERR_INVALID_ARG, "ootf: HM_ALPHA_PREMULTIPLIED beside the OOTF step (the luminance of premultiplied light is not the scene's)");
@@ -960,19 +958,24 @@ static int ootf_plan_of(const hm_device_ootf* o, hm_light_plan* lp)
 
 namespace {
 
-// the tables a light plan's kernels read, one behind the other: lin, then enc, then thr and sg of the tone step, then thr and sg of
+// the tables a light plan's kernels read, one behind the other: lin (three of them under lp->lin3), then enc, then thr and sg of the tone step, then thr and sg of
 // the OOTF step (hm_out_write; the plan may be NULL - no light step, no tables)
 struct LightTables {
   const hm_light_plan* lp;
   size_t n, ne, nt, no;
   explicit LightTables(const hm_light_plan* plan)
-    : lp(plan), n(plan ? (size_t)1 << plan->bits : 0), ne(plan && plan->encode ? (size_t)1 << plan->enc_bits : 0), nt(plan && plan->tone ? 2 * (size_t)HM_TONE_STEPS : 0),
+    : lp(plan), n(plan ? (size_t)(plan->lin3 ? 3 : 1) << plan->bits : 0), ne(plan && plan->encode ? (size_t)1 << plan->enc_bits : 0), nt(plan && plan->tone ? 2 * (size_t)HM_TONE_STEPS : 0),
       no(plan && plan->ootf ? 2 * (size_t)HM_OOTF_STEPS : 0) {}
   size_t bytes() const { return (n + ne + nt + no) * sizeof(float); }
   void fill(float* host) const
   {
     if (!lp) return;
-    fill_light_table(lp->from_transfer, lp->bits, (double)lp->gain, false, host);
+    if (lp->icc) { // (parsed when the plan was made: it parses again)
+      hm_icc::Profile prof;
+      if (hm_icc::parse(lp->icc_data, lp->icc_size, &prof)) return;
+      for (int c = 0; c < (lp->lin3 ? 3 : 1); c++) hm_icc::fill_table(prof.curve[c], lp->bits, (double)lp->gain, host + ((size_t)c << lp->bits));
+    }
+    else fill_light_table(lp->from_transfer, lp->bits, (double)lp->gain, false, host);
     if (lp->encode) fill_light_table(lp->to_transfer, lp->enc_bits, (double)lp->gain, true, host + n);
     if (lp->tone) fill_tone_tables((double)lp->gain, lp->src_peak, lp->dst_peak, lp->unit_nits, lp->out_unit_nits, host + n + ne, host + n + ne + HM_TONE_STEPS);
     if (lp->ootf) fill_ootf_tables((double)lp->gain, ootf_gamma_of((double)lp->ootf_peak, (double)lp->ootf_gamma), host + n + ne + nt, host + n + ne + nt + HM_OOTF_STEPS);
@@ -984,7 +987,7 @@ struct LightTables {
     std::memset(&la, 0, sizeof(la));
     la.src_bytes = src_bytes;
     if (!lp) return la;
-    la.bits = lp->bits; la.enc_bits = lp->enc_bits; la.src_bytes = src_bytes; la.encode = lp->encode; la.matrix = lp->matrix;
+    la.bits = lp->bits; la.enc_bits = lp->enc_bits; la.src_bytes = src_bytes; la.encode = lp->encode; la.matrix = lp->matrix; la.lin3 = lp->lin3;
     std::memcpy(la.m, lp->m, sizeof(la.m));
     std::memcpy(la.y, lp->y, sizeof(la.y));
     return la;
@@ -1150,7 +1153,7 @@ int hm_out_check_static(int out_format, const hm_device_dest* d, const hm_out_st
         return hm_fail(HM_ERR_UNSUPPORTED, "tone: out_bits 8 with the four-channel output format %d is not supported", out_format);
     }
   }
-  return l ? light_check(out_format, dest_format, d, l, explicit_from) : hm_dest_check_static(dest_format, d);
+  return l ? light_check(out_format, dest_format, d, st, explicit_from) : hm_dest_check_static(dest_format, d);
 }
 
 // the part of hm_out_resolve that needs the image's profile and depth
@@ -1171,9 +1174,15 @@ static int out_resolve_profile(int out_format, const hm_out_image* img, const hm
     }
   }
   if (!st->light) return HM_OK;
-  if ((rc = light_plan_of(out_format, bits, img->transfer, img->primaries, st->light, &p->lp))) return rc;
+  if ((rc = light_plan_of(out_format, bits, img->transfer, img->primaries, st->light, st->icc, st->icc_size, &p->lp))) return rc;
   if (st->ootf && (rc = ootf_plan_of(st->ootf, &p->lp))) return rc;
   if (st->tone && (rc = tone_plan_of(st->tone, &p->lp))) return rc;
+  { // no launch of the write asks for more local memory than a workgroup gets (light_step.h: check_light_lds) - only three tables get there
+    const hm_light_plan& lp = p->lp;
+    const bool summed = !p->vp.crop_only && p->vp.filter != HM_VIEW_NEAREST;
+    const int steps = (lp.tone ? 1 : 0) | (lp.ootf ? 2 : 0);
+    if ((rc = hm_light_lds_check(lp.bits, lp.enc_bits, lp.encode, steps, lp.lin3, summed ? 1 : 0)) || (summed && (rc = hm_light_lds_check(lp.bits, lp.enc_bits, lp.encode, steps, lp.lin3, 2)))) return rc;
+  }
   return st->gain ? gain_plan_of(st->gain, img, &p->vp, &p->lp, &p->gp) : (int)HM_OK;
 }
 
@@ -1303,7 +1312,7 @@ int hm_out_write(const hm_device_dest* d, const hm_out_plan* p, const void* src,
   if (alpha) {
     aa.mode = p->ap.mode; aa.bits = p->ap.bits; aa.src_bytes = src_bytes; aa.P = (float)((1 << p->ap.bits) - 1);
     // the background as the kernels take it: b_c = (float)background[c], with a light step lin[background[c]] of the table just filled
-    for (int c = 0; c < 3; c++) aa.bg[c] = host_tables ? host_tables[p->ap.background[c]] : (float)p->ap.background[c];
+    for (int c = 0; c < 3; c++) aa.bg[c] = host_tables ? host_tables[(lp->lin3 ? (size_t)c << lp->bits : 0) + p->ap.background[c]] : (float)p->ap.background[c]; // (lin3: its channel's table)
   }
   if (bytes && !(sc->dev[0] = hm_pool_device_alloc(bytes))) return HM_ERR_NO_DEVICE;
   hm_resample_args r;
@@ -1342,6 +1351,9 @@ static int out_to_tensor(int kind, int out_format, int bits, int w, int h, const
 {
   if (!src || !dest) return hm_fail(HM_ERR_INVALID_ARG, "null argument");
   int rc = hm_entry_steps(kind, st, false, /*light_judged_later=*/true);
+  if (!rc && kind != HM_ENTRY_ICC) rc = hm_entry_icc(st, "in a stand-alone entry that has no item: hm_icc_to_tensor takes a profile");
+  if (!rc && kind == HM_ENTRY_ICC && !hm_light_from_icc(st.light) && !(rc = hm_entry_icc(st, nullptr)))
+    rc = hm_fail(HM_ERR_INVALID_ARG, "light: hm_icc_to_tensor takes HM_LIGHT_FROM_ICC in from_transfer and from_primaries (they are %d and %d)", st.light->from_transfer, st.light->from_primaries);
   if (rc || (rc = hm_out_check_static(out_format, dest, &st, 1)) || (rc = check_image_size(size_prefix, w, h))) return rc;
   if (map && (rc = check_image_size("gain map: ", map_w, map_h))) return rc;
   const hm_out_image img = {w, h, bits, st.light ? st.light->from_transfer : 0, st.light ? st.light->from_primaries : 0, map_w, map_h, map_bits};
@@ -1395,6 +1407,12 @@ int hm_alpha_to_tensor(int out_format, int bits, int src_w, int src_h, const voi
                        const hm_device_tone* tone, const hm_device_alpha* alpha, const hm_device_dest* dest, void* stream)
 {
   return out_to_tensor(HM_ENTRY_ALPHA, out_format, bits, src_w, src_h, d_src, src_stride, {view, light, tone, alpha}, dest, stream);
+}
+
+int hm_icc_to_tensor(int out_format, int bits, int src_w, int src_h, const void* d_src, int src_stride, const hm_device_view* view, const uint8_t* icc, size_t icc_size,
+                     const hm_device_light* light, const hm_device_tone* tone, const hm_device_alpha* alpha, const hm_device_dest* dest, void* stream)
+{
+  return out_to_tensor(HM_ENTRY_ICC, out_format, bits, src_w, src_h, d_src, src_stride, {view, light, tone, alpha, nullptr, nullptr, icc, icc_size}, dest, stream);
 }
 
 int hm_ootf_to_tensor(int out_format, int bits, int src_w, int src_h, const void* d_src, int src_stride, const hm_device_view* view, const hm_device_light* light,

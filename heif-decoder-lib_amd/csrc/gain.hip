@@ -297,8 +297,8 @@ void launch_v(const hm_dest_plan* p, const hm_resample_args* r, const hm_light_a
 // taps: 0 none (nearest), 1 the records of the pointwise path, 2 the tables of the summed path
 int check_args(const hm_dest_plan* p, const hm_light_args* la, const hm_gain_args* ga, int taps)
 {
-  const int rc = check_light_args("k_gain", p, la);
-  if (rc) return rc;
+  int rc = check_light_args("k_gain", p, la);
+  if (rc || (rc = taps == 2 ? check_light_lds(la, 2) : check_light_lds(la, 0))) return rc; // (the summed path's horizontal pass: hm_launch_light_h asks)
   if (!ga->tab || !ga->map || (ga->nch != 1 && ga->nch != 3) || ga->map_bits < 8 || ga->map_bits > HM_GAIN_MAX_BITS || ga->map_bytes != (ga->map_bits > 8 ? 2 : 1) ||
       ga->mw < 1 || ga->mh < 1 || (int64_t)ga->map_stride < (int64_t)ga->mw * ga->map_bytes)
     return hm_fail(HM_ERR_INTERNAL, "k_gain: a map of %d x %d samples of %d bits in %d bytes, stride %d, %d tables", ga->mw, ga->mh, ga->map_bits, ga->map_bytes, ga->map_stride, ga->nch);

@@ -142,19 +142,28 @@ typedef struct hm_light_plan {
   int32_t ootf;          // an OOTF step runs
   float ootf_peak, ootf_gamma; // display_peak and gamma of the request (gamma 0: the system gamma of the peak): what the tables are built from
   float y[3];            // the luminance weights of from_primaries
+  // the source is an ICC profile (HM_LIGHT_FROM_ICC, no known cicp tag in it): from_transfer and from_primaries stay HM_LIGHT_FROM_ICC,
+  // lin comes from the profile's curves, m from its colorants (hm_icc.h).  The bytes are the request's (hm_out_steps): they outlive the write.
+  int32_t icc;
+  int32_t lin3;          // the three curves give distinct tables at `bits`: three are uploaded, red, green, blue
+  const uint8_t* icc_data; size_t icc_size;
 } hm_light_plan;
 // (the step's refusals: hm_out_check_static; its plan: hm_out_resolve)
 // ---- the tone step (hm_device_tone) inside the light step: two tables of HM_TONE_STEPS entries, built in devdest.cpp ----
 // the peak rule of include/heif_mi355x.h on an item's raw properties
 float hm_tone_peak_of(int has_clli, unsigned max_cll, int has_mdcv, unsigned mdcv_max);
 
-// what the kernels get: device pointers of lin[1 << bits], (encode) enc[1 << enc_bits], (tone) thr[HM_TONE_STEPS] with sg[HM_TONE_STEPS]
+// what the kernels get: device pointers of lin[1 << bits] (lin3: three of them, one behind the other), (encode) enc[1 << enc_bits], (tone) thr[HM_TONE_STEPS] with sg[HM_TONE_STEPS]
 // behind it and (ootf) thr[HM_OOTF_STEPS] with sg[HM_OOTF_STEPS] behind it, y the step's luminance weights; src_bytes: bytes of a source
 // sample (the plan's sample_bytes are the destination's sibling target's)
 typedef struct hm_light_args {
   const float* lin; const float* enc; const float* tone; int32_t bits, enc_bits, src_bytes, encode, matrix; float m[9];
   const float* ootf; float y[3];
+  int32_t lin3;          // lin is three tables of 1 << bits entries - red, green, blue: an ICC profile with distinct curves -, not one
 } hm_light_args;
+// The one host check of a launch's dynamic LDS (light_step.h: check_light_lds) for the plan, which asks before anything is queued.
+// tone: bit 0 a tone step, bit 1 an OOTF step; pass 0: a pointwise or nearest kernel, 1: a horizontal pass, 2: a vertical pass
+int hm_light_lds_check(int bits, int enc_bits, int encode, int tone, int lin3, int pass);
 int hm_launch_light_tensor(const hm_dest_plan* p, const hm_light_args* la, const void* src, int src_stride, int w, int rows, void* dst, const float scale[4],
                            const float bias[4], hipStream_t s);
 int hm_launch_light_nearest(const hm_dest_plan* p, const hm_light_args* la, const void* src, int src_stride, int n_w, int n_h, int ow, int oh, void* dst,
@@ -230,6 +239,9 @@ int hm_launch_light_h(const hm_dest_plan* p, const hm_light_args* la, const hm_r
 typedef struct hm_out_steps {
   const hm_device_view* view; const hm_device_light* light; const hm_device_tone* tone; const hm_device_alpha* alpha; const hm_device_gain* gain;
   const hm_device_ootf* ootf;
+  // the profile a light step with HM_LIGHT_FROM_ICC reads: the item's (resolve_request), hm_icc_to_tensor's; it must live until the
+  // write has been queued.  NULL: the request has none - the sentinel is refused
+  const uint8_t* icc; size_t icc_size;
 } hm_out_steps; // any may be NULL
 // what the image reports (hm_decoded); with a gain step the map beside it (map_w 0: not known yet - the step's geometry is not judged)
 typedef struct hm_out_image { int32_t w, h, bits, transfer, primaries; int32_t map_w, map_h, map_bits; } hm_out_image;

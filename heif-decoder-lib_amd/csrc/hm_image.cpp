@@ -1917,6 +1917,13 @@ int hm_img::resolve_request(const hm_file* f, uint32_t id, const hm_decode_param
     r.t.gain = &r.gain;
   }
   if (refuse_derived && is_derived_item(f, r.id) && (rc = derived_refusal(f, r.id, params, asked.planes != nullptr))) return rc;
+  if (hm_light_from_icc(asked.light)) { // the profile of the item that is decoded (with a gain step: the base image), read before anything is queued
+    uint32_t type = 0;
+    hm_icc_info info;
+    if ((rc = hm_file_item_icc(f, r.id, 1, &type, &r.t.icc, &r.t.icc_size))) return rc;
+    if (!type) return hm_fail(HM_ERR_INVALID_ARG, "light: HM_LIGHT_FROM_ICC, and item %u has no ICC profile", r.id);
+    if ((rc = hm_icc_parse(r.t.icc, r.t.icc_size, &info))) return rc;
+  }
   return check_target_request(f, r.id, params, r.t);
 }
 
@@ -1978,6 +1985,18 @@ int hm_decode_item_to_device_ootf(const hm_file* f, uint32_t id, const hm_decode
                                   const hm_device_ootf* ootf, const hm_device_tone* tone, const hm_device_alpha* alpha, const hm_device_dest* dest, hm_decoded* out)
 {
   return decode_item_to(HM_ENTRY_OOTF, f, id, params, {view, light, tone, alpha, nullptr, ootf}, dest, nullptr, out);
+}
+
+int hm_file_item_icc_info(const hm_file* f, uint32_t id, hm_icc_info* out)
+{
+  if (!f || !out) return hm_fail(HM_ERR_INVALID_ARG, "null argument");
+  std::memset(out, 0, sizeof(*out));
+  uint32_t type = 0;
+  const uint8_t* data = nullptr;
+  size_t size = 0;
+  const int rc = hm_file_item_icc(f, id, 1, &type, &data, &size);
+  if (rc) return rc;
+  return type ? hm_icc_parse(data, size, out) : (int)HM_ICC_NO_PROFILE;
 }
 
 int hm_file_item_light_levels(const hm_file* f, uint32_t id, hm_light_levels* out)
@@ -2298,8 +2317,8 @@ static int decode_frames_to(int kind, const hm_file* f, const uint32_t* frames, 
   if (failed_frame) *failed_frame = -1;
   if (!frames && kind != HM_ENTRY_DEST) return hm_fail(HM_ERR_INVALID_ARG, "null argument");
   OutputTarget t;
-  const int rc = OutputTarget::of_entry(kind, st, dests, planes, t, /*view_may_be_null=*/true);
-  if (rc) return rc;
+  int rc = OutputTarget::of_entry(kind, st, dests, planes, t, /*view_may_be_null=*/true);
+  if (rc || (rc = hm_entry_icc(st, "in the frames family: the profile of a track's sample entry is not read"))) return rc;
   hm_device_tone own{};
   if (t.tone && !t.ootf) { own = tone_for_item(f, 0, t.tone); t.tone = &own; }
   return decode_sequence(f, frames, first, count, params, nullptr, t, out, failed_frame);

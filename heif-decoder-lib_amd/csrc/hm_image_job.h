@@ -142,6 +142,8 @@ struct OutputTarget {
   const hm_device_gain* gain = nullptr;        // the gain step beside light (resolved by resolve_request: map_item is the map's item, params are explicit)
   const struct PlanarImage* gain_map = nullptr; // ... and its decoded map (job_enqueue sets it; null with a gain step of weight 0)
   const hm_device_ootf* ootf = nullptr;        // the OOTF step beside light (a tone step beside it keeps its zeros: they resolve to display_peak)
+  const uint8_t* icc = nullptr;                // the ICC profile a light step with HM_LIGHT_FROM_ICC reads (resolve_request: the item's own, inside the
+  size_t icc_size = 0;                         // open file, which outlives the job)
   hm_view_scratch* scratch = nullptr;          // tap tables and the intermediate of the resampling step, the tables of the light step
   hm_view_item* view_later = nullptr;          // view + dest: the view is not written, only described there - the caller writes it with those of other images
   hm_planes_view_item* planes_later = nullptr; // the same for view + planes
@@ -157,7 +159,7 @@ struct OutputTarget {
     t.dest = d; t.planes = p; t.view = st.view; t.light = st.light; t.tone = st.tone; t.alpha = st.alpha; t.gain = st.gain; t.ootf = st.ootf;
     return HM_OK;
   }
-  hm_out_steps steps() const { return hm_out_steps{view, light, tone, alpha, gain, ootf}; } // the request of the device write (hm_devdest.h)
+  hm_out_steps steps() const { return hm_out_steps{view, light, tone, alpha, gain, ootf, icc, icc_size}; } // the request of the device write (hm_devdest.h)
 };
 // dest xor planes (or neither); light only with dest; tone only with light; ootf only with light; alpha only with dest and never with view_later; gain only with light and
 // never with view_later; view only with one of the two; a *_later only with view and its own kind of destination
@@ -189,6 +191,7 @@ struct OwnedTarget {
     if (from.alpha) { alpha = *from.alpha; t.alpha = &alpha; }
     if (from.gain) { gain = *from.gain; t.gain = &gain; }
     if (from.ootf) { ootf = *from.ootf; t.ootf = &ootf; }
+    t.icc = from.icc; t.icc_size = from.icc_size; // (the file's bytes: the job holds the file)
   }
 };
 
@@ -252,7 +255,8 @@ int check_target_request(const hm_file* f, uint32_t id, const hm_decode_params* 
 // id 0 or a frame of a sequence: 1000).  The other refusals are check_target_request's.
 hm_device_tone tone_for_item(const hm_file* f, uint32_t id, const hm_device_tone* tone);
 // A request resolved against the file, in the one order every entry keeps: the tone step's src_peak from the item asked for (only
-// without an OOTF step: beside one 0 is display_peak and no property is read); the gain step from that item too (hm_gain_for_item: a
+// without an OOTF step: beside one 0 is display_peak and no property is read); the ICC profile of a light step with HM_LIGHT_FROM_ICC - of
+// the item that is decoded, parsed here: an item without one, or with one the reader refuses, fails -; the gain step from that item too (hm_gain_for_item: a
 // 'tmap' item's own properties) - the item to decode becomes the base image; refuse_derived: what a derived item is refused for without
 // looking at a picture (the item entries; the pipeline leaves it to job_plan); check_target_request.  t points into tone and gain.
 struct ResolvedRequest {

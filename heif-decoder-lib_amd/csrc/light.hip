@@ -14,7 +14,7 @@
 // the pixel is scaled by sg[] at the count - a wave-uniform branch, like `encode` and `matrix`.
 // The OOTF step (hm_device_ootf) sits in front of the matrix: the scene luminance Ys = y . RGB is searched in thr[1024], and the pixel is
 // scaled by sg[] at the count - wave-uniform like the others (L.ootf is a kernel argument).
-// LDS: lin[1 << bits], when re-encoding enc[1 << enc_bits] behind it (1 KB each at 8 bits, 16 KB each at 12), with a tone step thr
+// LDS: lin[1 << bits] (three of them for an ICC profile with distinct curves: light_step.h, lin3), when re-encoding enc[1 << enc_bits] behind it (1 KB each at 8 bits, 16 KB each at 12), with a tone step thr
 // and sg (8 KB each) behind those, with an OOTF step its thr and sg (4 KB each) behind those - at most 56 KB, and nothing more than
 // before for a call without the OOTF step -, filled once per workgroup.  The lookups are data-dependent ds_read_b32: lanes
 // that meet the same entry are served by one broadcast, different entries of one bank serialise - a flat image is the best case,
@@ -74,22 +74,18 @@ __global__ __launch_bounds__(256) void k_light_nearest(const uint8_t* __restrict
   store_pixel<C>(dst + (long long)k * row_pitch, chw, plane_pitch, j, o);
 }
 
-// the sample-to-float step of k_light_h: the colour channels through lin (in LDS), alpha converted as it is
-struct LinLookup {
-  const float* lin; unsigned peak;
-  __device__ __forceinline__ float operator()(unsigned v, int c) const { return c < 3 ? lin[min(v, peak)] : (float)v; }
-};
-
-// resample_h_body (out_rows.h: k_resample_h's sums in its order) with lin[min(v, peak)] in place of (float)v on the colour channels.
+// resample_h_body (out_rows.h: k_resample_h's sums in its order) with lin[min(v, peak)] in place of (float)v on the colour channels
+// (LinLookup, light_step.h; lin3 - wave-uniform -: a table per channel, LinLookup3).
 // grid: x = groups of 64 output columns, y = groups of 4 source rows; src points at the crop's origin; dynamic LDS: lin.
 template <int SB, int C, bool CHW>
 __global__ __launch_bounds__(256) void k_light_h(const uint8_t* __restrict__ src, int src_stride, int n_h, int ow, const int32_t* __restrict__ first,
                                                  const int32_t* __restrict__ count, const float* __restrict__ wts, float* __restrict__ tmp,
-                                                 long long pitch, long long plane, const float* __restrict__ lin, int bits)
+                                                 long long pitch, long long plane, const float* __restrict__ lin, int bits, int lin3)
 {
   extern __shared__ __attribute__((aligned(16))) float lds[];
-  fill_tables(lds, lin, 1 << bits);
-  resample_h_body<SB, C, CHW>(src, src_stride, n_h, ow, first, count, wts, tmp, pitch, plane, LinLookup{lds, (1u << bits) - 1u});
+  fill_tables(lds, lin, (lin3 ? 3 : 1) << bits);
+  if (lin3) resample_h_body<SB, C, CHW>(src, src_stride, n_h, ow, first, count, wts, tmp, pitch, plane, LinLookup3{lds, (1u << bits) - 1u, bits});
+  else resample_h_body<SB, C, CHW>(src, src_stride, n_h, ow, first, count, wts, tmp, pitch, plane, LinLookup{lds, (1u << bits) - 1u});
 }
 
 // The vertical pass: vertical_sums (out_rows.h) of ONE pixel per lane - the matrix needs R, G and B together -, then light_out.
@@ -179,10 +175,10 @@ void launch_h(bool chw, const hm_resample_args* r, const hm_light_args* la, hipS
   const size_t lds = light_h_bytes(la);
   if (chw)
     hipLaunchKernelGGL((k_light_h<SB, C, true>), grid, block, lds, s, src, r->src_stride, r->n_h, r->ow, r->ax.first, r->ax.count, r->ax.weights, r->tmp,
-                       (long long)r->tmp_pitch, (long long)r->tmp_plane, la->lin, la->bits);
+                       (long long)r->tmp_pitch, (long long)r->tmp_plane, la->lin, la->bits, la->lin3);
   else
     hipLaunchKernelGGL((k_light_h<SB, C, false>), grid, block, lds, s, src, r->src_stride, r->n_h, r->ow, r->ax.first, r->ax.count, r->ax.weights, r->tmp,
-                       (long long)r->tmp_pitch, (long long)r->tmp_plane, la->lin, la->bits);
+                       (long long)r->tmp_pitch, (long long)r->tmp_plane, la->lin, la->bits, la->lin3);
 }
 
 template <typename OutT>
@@ -214,7 +210,15 @@ extern "C" long long hm_light_lds_bytes(int bits, int enc_bits, int encode, int 
   static const float some = 0.0f;
   hm_light_args la = {};
   la.bits = bits; la.enc_bits = enc_bits; la.encode = encode; la.tone = (tone & 1) ? &some : nullptr; la.ootf = (tone & 2) ? &some : nullptr;
-  return (long long)(pass == 0 ? light_tables_bytes(&la) : pass == 1 ? light_h_bytes(&la) : light_v_bytes(&la));
+  return (long long)light_pass_bytes(&la, pass);
+}
+
+extern "C" int hm_light_lds_check(int bits, int enc_bits, int encode, int tone, int lin3, int pass)
+{
+  static const float some = 0.0f;
+  hm_light_args la = {};
+  la.bits = bits; la.enc_bits = enc_bits; la.encode = encode; la.tone = (tone & 1) ? &some : nullptr; la.ootf = (tone & 2) ? &some : nullptr; la.lin3 = lin3;
+  return check_light_lds(&la, pass);
 }
 
 // rows [0, rows) of `src` through the light step to `dst` = the destination's first element; asynchronous on `s`
@@ -222,8 +226,8 @@ extern "C" int hm_launch_light_tensor(const hm_dest_plan* p, const hm_light_args
                                       const float scale[4], const float bias[4], hipStream_t s)
 {
   if (w <= 0 || rows <= 0) return HM_OK;
-  const int rc = check_light_args("k_light", p, la);
-  if (rc) return rc;
+  int rc = check_light_args("k_light", p, la);
+  if (rc || (rc = check_light_lds(la, 0))) return rc;
   const Affine a = affine_of(scale, bias);
   const uint8_t* in = (const uint8_t*)src;
   uint8_t* out = (uint8_t*)dst;
@@ -238,8 +242,8 @@ extern "C" int hm_launch_light_nearest(const hm_dest_plan* p, const hm_light_arg
                                        const float scale[4], const float bias[4], hipStream_t s)
 {
   if (ow <= 0 || oh <= 0) return HM_OK;
-  const int rc = check_light_args("k_light", p, la);
-  if (rc) return rc;
+  int rc = check_light_args("k_light", p, la);
+  if (rc || (rc = check_light_lds(la, 0))) return rc;
   const Affine a = affine_of(scale, bias);
   const uint8_t* in = (const uint8_t*)src;
   uint8_t* out = (uint8_t*)dst;
@@ -254,8 +258,8 @@ extern "C" int hm_launch_light_nearest(const hm_dest_plan* p, const hm_light_arg
 extern "C" int hm_launch_light_h(const hm_dest_plan* p, const hm_light_args* la, const hm_resample_args* r, hipStream_t s)
 {
   if (r->ow <= 0 || r->oh <= 0 || r->n_w <= 0 || r->n_h <= 0) return HM_OK;
-  const int rc = check_light_args("k_light", p, la);
-  if (rc) return rc;
+  int rc = check_light_args("k_light", p, la);
+  if (rc || (rc = check_light_lds(la, 1))) return rc;
   with_flags(r->sample_bytes == 2, r->channels == 4, [&](auto wide, auto four) { launch_h<wide.value ? 2 : 1, four.value ? 4 : 3>(p->layout == HM_DEV_LAYOUT_CHW, r, la, s); });
   return hm_check_hip(hipGetLastError(), "k_light_h launch");
 }
@@ -266,7 +270,7 @@ extern "C" int hm_launch_light_resample(const hm_dest_plan* p, const hm_light_ar
 {
   if (r->ow <= 0 || r->oh <= 0 || r->n_w <= 0 || r->n_h <= 0) return HM_OK;
   int rc = hm_launch_light_h(p, la, r, s);
-  if (rc) return rc;
+  if (rc || (rc = check_light_lds(la, 2))) return rc;
   const Affine a = affine_of(scale, bias);
   uint8_t* out = (uint8_t*)dst;
   const int found = with_dtype(p->dtype, [&](auto tag) -> int { launch_v<typename decltype(tag)::type>(p, r, la, out, a, s); return HM_OK; });

@@ -18,18 +18,19 @@
 #include "out_elem.h"
 
 // ebits: of the codes of enc (bits, or 8 under the 8-bit finish); tone: thr[TONE_STEPS], then sg[TONE_STEPS] (NULL: no tone step);
-// ootf: thr[OOTF_STEPS], then sg[OOTF_STEPS] (NULL: no OOTF step), y: the luminance weights of the source primaries
-struct Light { const float* lin; const float* enc; const float* tone; const float* ootf; int bits, ebits, encode, matrix; float m[9]; float y[3]; };
+// ootf: thr[OOTF_STEPS], then sg[OOTF_STEPS] (NULL: no OOTF step), y: the luminance weights of the source primaries;
+// lin3: lin is three tables of 1 << bits entries, one per colour channel (an ICC profile with distinct curves), not one
+struct Light { const float* lin; const float* enc; const float* tone; const float* ootf; int bits, ebits, encode, matrix; float m[9]; float y[3]; int lin3; };
 constexpr int TONE_STEPS = HM_TONE_STEPS;
 constexpr int OOTF_STEPS = HM_OOTF_STEPS;
 
-// The step's tables lie in LDS one behind the other: lin[1 << bits] (with_lin: a vertical pass has none - its sums are of light already),
-// enc[1 << ebits] when re-encoding, thr and sg of the tone step, thr and sg of the OOTF step.  Offsets in floats; end: all of them.
+// The step's tables lie in LDS one behind the other: lin[1 << bits] (lin3: three of them, red, green, blue; with_lin: a vertical pass has
+// none - its sums are of light already), enc[1 << ebits] when re-encoding, thr and sg of the tone step, thr and sg of the OOTF step.  Offsets in floats; end: all of them.
 struct LightLayout { int enc, tone, ootf, end; };
-__host__ __device__ inline LightLayout light_layout(bool with_lin, int bits, int ebits, bool encode, bool tone, bool ootf)
+__host__ __device__ inline LightLayout light_layout(bool with_lin, int bits, int ebits, bool encode, bool tone, bool ootf, bool lin3)
 {
   LightLayout o;
-  o.enc = with_lin ? 1 << bits : 0;
+  o.enc = with_lin ? (lin3 ? 3 : 1) << bits : 0;
   o.tone = o.enc + (encode ? 1 << ebits : 0);
   o.ootf = o.tone + (tone ? 2 * TONE_STEPS : 0);
   o.end = o.ootf + (ootf ? 2 * OOTF_STEPS : 0);
@@ -40,7 +41,7 @@ __host__ __device__ inline LightLayout light_layout(bool with_lin, int bits, int
 // once more on its kernel arguments: 14.8 against 14.1 us (profiles/step_kernels_refactor.txt).
 struct LightTables {
   const float* lds; bool with_lin;
-  __device__ __forceinline__ LightLayout at(const Light& L) const { return light_layout(with_lin, L.bits, L.ebits, L.encode, L.tone, L.ootf); }
+  __device__ __forceinline__ LightLayout at(const Light& L) const { return light_layout(with_lin, L.bits, L.ebits, L.encode, L.tone, L.ootf, L.lin3); }
   __device__ __forceinline__ const float* lin() const { return lds; }
   __device__ __forceinline__ const float* enc(const Light& L) const { return lds + at(L).enc; }
   __device__ __forceinline__ const float* tone(const Light& L) const { return lds + at(L).tone; }
@@ -63,7 +64,7 @@ __device__ __forceinline__ void fill_tables(float* lds, const float* __restrict_
 __device__ __forceinline__ LightTables fill_light(float* lds, const Light& L, bool with_lin)
 {
   const int ne = L.encode ? 1 << L.ebits : 0, nt = L.tone ? 2 * TONE_STEPS : 0;
-  if (with_lin) fill_tables(lds, L.lin, 1 << L.bits, L.enc, ne, L.tone, nt, L.ootf, 2 * OOTF_STEPS);
+  if (with_lin) fill_tables(lds, L.lin, (L.lin3 ? 3 : 1) << L.bits, L.enc, ne, L.tone, nt, L.ootf, 2 * OOTF_STEPS);
   else if (L.encode || L.tone || L.ootf) fill_tables(lds, L.enc, ne, L.tone, nt, L.ootf, 2 * OOTF_STEPS); // (uniform: the barrier inside is met by every thread or by none)
   return LightTables{lds, with_lin};
 }
@@ -122,12 +123,30 @@ template <typename OutT> __device__ __forceinline__ OutT colour_out(const Light&
   return linear_out<OutT>(r, sc, bi);
 }
 
-// a pixel's colour samples to linear light: lin at the sample, clamped to the table
+// a pixel's colour samples to linear light: lin at the sample, clamped to the table; lin3 (wave-uniform, as the step's other options
+// are): channel c in its own table, lin[(c << bits) + min(v, peak)]
 template <typename Tables> __device__ __forceinline__ void light_in(const Light& L, const Tables& T, const unsigned v[3], float r[3])
 {
   const unsigned peak = (1u << L.bits) - 1u;
+  if (L.lin3) {
+    r[0] = T.lin()[min(v[0], peak)]; r[1] = T.lin()[(1u << L.bits) + min(v[1], peak)]; r[2] = T.lin()[(2u << L.bits) + min(v[2], peak)];
+    return;
+  }
   r[0] = T.lin()[min(v[0], peak)]; r[1] = T.lin()[min(v[1], peak)]; r[2] = T.lin()[min(v[2], peak)];
 }
+
+// the sample-to-float step of a horizontal pass (k_light_h, k_alpha_h), which holds lin alone: the colour channels through lin (in LDS)
+struct LinLookup {
+  const float* lin; unsigned peak;
+  __device__ __forceinline__ float colour(unsigned v, int) const { return lin[min(v, peak)]; }
+  __device__ __forceinline__ float operator()(unsigned v, int c) const { return c < 3 ? colour(v, c) : (float)v; } // (alpha: converted as it is)
+};
+// ... with a table per channel
+struct LinLookup3 {
+  const float* lin; unsigned peak; int bits;
+  __device__ __forceinline__ float colour(unsigned v, int c) const { return lin[((unsigned)c << bits) + min(v, peak)]; }
+  __device__ __forceinline__ float operator()(unsigned v, int c) const { return c < 3 ? colour(v, c) : (float)v; }
+};
 
 // one pixel's linear light r (changed in place) to its three colour elements: what every kernel of the step does behind its lookups or
 // its sums, each part a wave-uniform branch on a kernel argument.  OOTF false: a kernel that never meets the OOTF step (the gain step's:
@@ -145,26 +164,41 @@ template <bool OOTF = true, typename Tables, typename OutT> __device__ __forcein
 static inline Light light_of(const hm_light_args* la)
 {
   Light L;
-  L.lin = la->lin; L.enc = la->enc; L.tone = la->tone; L.ootf = la->ootf; L.bits = la->bits; L.ebits = la->enc_bits; L.encode = la->encode; L.matrix = la->matrix;
+  L.lin = la->lin; L.enc = la->enc; L.tone = la->tone; L.ootf = la->ootf; L.bits = la->bits; L.ebits = la->enc_bits; L.encode = la->encode; L.matrix = la->matrix; L.lin3 = la->lin3;
   for (int i = 0; i < 9; i++) L.m[i] = la->m[i];
   for (int i = 0; i < 3; i++) L.y[i] = la->y[i];
   return L;
 }
 // the dynamic LDS of a launch: the pointwise and nearest kernels hold lin, enc, the tone and the OOTF tables, a horizontal pass lin, a
-// vertical pass enc, the tone and the OOTF tables - at most 16 + 16 + 16 + 8 = 56 KB
+// vertical pass enc, the tone and the OOTF tables - with one lin at most 16 + 16 + 16 + 8 = 56 KB; with three, what check_light_lds lets pass
 static inline size_t light_layout_bytes(const hm_light_args* la, bool with_lin)
 {
-  return (size_t)light_layout(with_lin, la->bits, la->enc_bits, la->encode != 0, la->tone != nullptr, la->ootf != nullptr).end * sizeof(float);
+  return (size_t)light_layout(with_lin, la->bits, la->enc_bits, la->encode != 0, la->tone != nullptr, la->ootf != nullptr, la->lin3 != 0).end * sizeof(float);
 }
-static inline size_t light_h_bytes(const hm_light_args* la) { return (size_t)4 << la->bits; }
+static inline size_t light_h_bytes(const hm_light_args* la) { return (size_t)(la->lin3 ? 12 : 4) << la->bits; }
 static inline size_t light_v_bytes(const hm_light_args* la) { return light_layout_bytes(la, false); }
 static inline size_t light_tables_bytes(const hm_light_args* la) { return light_layout_bytes(la, true); }
+
+// What a launch may ask for as dynamic LDS: 64 KB, what a workgroup gets without the launch opting in to more (the CU has 160 KB; no
+// launch here opts in).  Only three lin tables reach it: 12-bit samples with a 12-bit re-encoding and a tone step are 48 + 16 + 16 KB.
+// The one host check of it - the plan asks before anything is queued (hm_light_lds_check), every launcher asks again.
+// pass 0: k_*_tensor / k_*_nearest, 1: a horizontal pass, 2: a vertical pass
+enum { LIGHT_LDS_MOST = 64 * 1024 };
+static inline size_t light_pass_bytes(const hm_light_args* la, int pass) { return pass == 0 ? light_tables_bytes(la) : pass == 1 ? light_h_bytes(la) : light_v_bytes(la); }
+static inline int check_light_lds(const hm_light_args* la, int pass)
+{
+  const size_t bytes = light_pass_bytes(la, pass);
+  if (bytes <= (size_t)LIGHT_LDS_MOST) return HM_OK;
+  return hm_fail(HM_ERR_UNSUPPORTED, "light: %d-bit samples through %s with%s%s%s in one kernel need %zu bytes of local memory for their tables (%d fit): not supported", la->bits,
+                 la->lin3 ? "three distinct curves of the ICC profile" : "one curve", la->encode ? (la->enc_bits == 8 ? " a re-encoding to 8-bit codes," : " a re-encoding,") : "",
+                 la->tone ? " a tone step," : "", la->ootf ? " an OOTF step," : " no OOTF step,", bytes, (int)LIGHT_LDS_MOST);
+}
 
 // hm_light_args against p, the plan of the target the destination is written as (under the 8-bit finish its samples are bytes, the
 // source's are not); k: the kernel family, for the message
 static inline int check_light_args(const char* k, const hm_dest_plan* p, const hm_light_args* la)
 {
-  if (!la->lin || (la->encode && !la->enc) || la->bits < 8 || la->bits > 12) return hm_fail(HM_ERR_INTERNAL, "%s: tables of %d bits", k, la->bits);
+  if (!la->lin || (la->encode && !la->enc) || la->bits < 8 || la->bits > 12 || (la->lin3 != 0 && la->lin3 != 1)) return hm_fail(HM_ERR_INTERNAL, "%s: tables of %d bits", k, la->bits);
   if (la->enc_bits != la->bits && la->enc_bits != 8) return hm_fail(HM_ERR_INTERNAL, "%s: codes of %d bits from tables of %d", k, la->enc_bits, la->bits);
   if (la->src_bytes != (la->bits > 8 ? 2 : 1)) return hm_fail(HM_ERR_INTERNAL, "%s: %d-byte samples of %d bits", k, la->src_bytes, la->bits);
   if (p->channels != 3 && p->channels != 4) return hm_fail(HM_ERR_INTERNAL, "%s: %d channels", k, p->channels);

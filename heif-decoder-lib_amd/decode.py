@@ -10,7 +10,8 @@ floats are sample * scale[c] + bias[c], rounded after each step.  crop=(x, y, w,
 resampled (filter "triangle": antialiased bilinear, "bicubic", "lanczos3" or "nearest") in the step that writes the tensor; of a grid only the tiles the
 rectangle touches are decoded.  light=True asks for linear light (the image's own transfer function undone by a table, floats only);
 light=dict(to_transfer="srgb", to_primaries="bt709", gain=1.0, from_transfer=..., from_primaries=...) re-encodes or changes the
-primaries - a resize under light= averages light, not code values.  tone=dict(dst_peak=203.0, src_peak=None, unit_nits=None,
+primaries - a resize under light= averages light, not code values.  light={"from": "icc", ...} reads the code values through the item's
+ICC profile (a matrix/TRC profile: a phone's Display P3) instead of its nclx codes.  tone=dict(dst_peak=203.0, src_peak=None, unit_nits=None,
 out_unit_nits=None, out_bits=None) beside light= maps the content's peak (None: the file's clli / mdcv, else 1000 cd/m2) to the
 display's with the BT.2390 curve; out_bits=8 finishes a deeper image in 8-bit codes (torch.uint8 is then accepted for it).
 alpha="straight" / "premultiplied" / dict(mode="matte", background=(r, g, b)) with out_format "rgba" / "rrggbbaa_le" uses the alpha
@@ -134,20 +135,31 @@ PRIMARIES = {"bt709": 1, "srgb": 1, "bt2020": 9, "p3": 12}
 
 def _light_of(light):
     """hm_device_light (or None) of the light= argument: True, or a dict of to_transfer / to_primaries / gain / from_transfer /
-    from_primaries with H.273 codes or names"""
+    from_primaries with H.273 codes or names; "from": "icc" (or "icc" as the value of from_transfer / from_primaries) makes the item's ICC
+    profile the source - the library refuses it set in one of the two only"""
     if light is None or light is False:
         return None
     if light is True:
         light = {}
     if not isinstance(light, dict):
         raise ValueError(f"light {light!r}: True or a dict")
-    keys = {"to_transfer", "to_primaries", "gain", "from_transfer", "from_primaries"}
+    keys = {"to_transfer", "to_primaries", "gain", "from_transfer", "from_primaries", "from"}
     if set(light) - keys:
         raise ValueError(f"light: unknown keys {sorted(set(light) - keys)}, known are {sorted(keys)}")
+
+    if "from" in light:
+        if light["from"] != "icc":
+            raise ValueError(f"light['from'] = {light['from']!r}: 'icc' (codes go to from_transfer / from_primaries)")
+        if "from_transfer" in light or "from_primaries" in light:
+            raise ValueError("light: 'from' beside from_transfer / from_primaries")
+        light = dict(light, from_transfer="icc", from_primaries="icc")
+        del light["from"]
 
     def code(key, names, default):
         v = light.get(key, default)
         if isinstance(v, str):
+            if v.lower() == "icc" and key.startswith("from_"):
+                return capi.HM_LIGHT_FROM_ICC
             if v.lower() not in names:
                 raise ValueError(f"light[{key!r}] = {v!r}: one of {sorted(names)} or an H.273 code")
             return names[v.lower()]

@@ -759,7 +759,8 @@ HM_API int hm_view_filter_taps(int n_in, int n_out, int filter, int j, int32_t* 
 enum { HM_LIGHT_LINEAR = 8 };              /* H.273 transfer code 8 */
 typedef struct hm_device_light {
   int32_t from_transfer, from_primaries;   /* H.273 codes; 0 = the image's own: what this call's hm_decoded reports
-                                              (has_nclx == 0 or code 2: transfer 13, primaries 1; an ICC profile is not read) */
+                                              (has_nclx == 0 or code 2: transfer 13, primaries 1; an ICC profile is not read);
+                                              HM_LIGHT_FROM_ICC in BOTH: the item's ICC profile ("ICC" below) */
   int32_t to_transfer;                     /* HM_LIGHT_LINEAR: linear light, float dtypes only; another supported code: re-encoded */
   int32_t to_primaries;                    /* 0 = keep the source's */
   float   gain;                            /* finite, > 0: multiplies linear light (PQ: 1.0 = 10000 cd/m2) */
@@ -785,6 +786,76 @@ HM_API int hm_light_to_tensor(int out_format, int bits, int src_w, int src_h, co
 HM_API int hm_light_table(int transfer, int bits, float gain, int encode, float* out);
 /* Host arithmetic, no device: the row-major float32 matrix from one set of primaries to another (the identity, exactly, for equal codes) */
 HM_API int hm_light_matrix(int from_primaries, int to_primaries, float m[9]);
+
+/* ------------------------------------------------------------------------- */
+/* ICC: the item's matrix/TRC profile as the source colour description of the light step */
+/* ------------------------------------------------------------------------- */
+
+/* HM_LIGHT_FROM_ICC in from_transfer AND from_primaries of hm_device_light (in one only: HM_ERR_INVALID_ARG) makes the light step read
+ * the RGB code values through the ICC profile of the item - the profile hm_file_item_icc(f, id, 1, ...) reports, 'prof' or 'rICC'; with
+ * a gain step: of the base image.  Every value that was valid before keeps its meaning; 0 still is "the nclx or the default, the profile
+ * not read".  An nclx beside the profile keeps deciding the YCbCr -> RGB chain; only the light step's reading of the RGB codes changes.
+ * The profile is parsed before anything is queued: an item without one (HM_ERR_INVALID_ARG) or with one the reader refuses (its status)
+ * fails there, the destination unwritten.
+ * What is read: ICC.1 versions 2.x and 4.x, header signature 'acsp', class 'mntr', 'scnr' or 'spac', connection space 'XYZ ', data
+ * colour space 'RGB ' with rXYZ, gXYZ, bXYZ ('XYZ ' type) and rTRC, gTRC, bTRC, or 'GRAY' with kTRC (it stands for all three channels);
+ * TRC tags of type 'curv' or 'para'.  Every offset and size is checked against the profile's size field, the size field against the bytes
+ * given; nothing outside them is read.  The 'chad' tag is not used: the colorants of a conforming profile are in D50 already.
+ * Curves, in double with the C library's pow, X in [0, 1]:
+ *   'curv', count 0: Y = X;  count 1: Y = pow(X, g), g = the u8Fixed8 entry / 256;  count n >= 2: t[k] = entry k / 65535.0,
+ *   pos = X * (n - 1), i = min((int)pos, n - 2), Y = t[i] + (pos - i) * (t[i + 1] - t[i]).
+ *   'para', function type 0 .. 4, parameters g a b c d e f as s15Fixed16 / 65536.0, P(X) = pow(max(a * X + b, 0), g):
+ *   0: pow(X, g);  1: X >= -b / a ? P(X) : 0;  2: X >= -b / a ? P(X) + c : c;  3: X >= d ? P(X) : c * X;  4: X >= d ? P(X) + e : c * X + f.
+ *   g <= 0, or a == 0 in types 1 and 2: malformed.  Y is clamped to [0, 1].
+ *   lin_c[v] = (float)(g * Y_c(v / peak)), v = 0 .. peak, g = (double)gain: hm_icc_table.
+ * Matrix (hm_icc_matrix): m = (A T)^-1 M in double, each entry rounded once to float32.  M: the colorant columns (s15Fixed16 / 65536.0).
+ *   T: RGB -> XYZ of to_primaries exactly as hm_light_matrix derives it, white xy (0.3127, 0.3290), W = (xw / yw, 1, (1 - xw - yw) / yw).
+ *   A: the linear Bradford adaptation from W to the connection-space illuminant I = (0xF6D6, 0x10000, 0xD32D) / 65536:
+ *   A = B^-1 diag((B I)_k / (B W)_k) B, B = [0.8951 0.2664 -0.1614; -0.7502 1.7135 0.0367; 0.0389 -0.0685 1.0296].
+ *   to_primaries == 0 keeps the profile's own primaries: no matrix.  GRAY: the identity.
+ * A 'cicp' tag whose primaries and transfer codes are both ones the light step knows stands for the profile: the source is those H.273
+ * codes and the step runs as with explicit codes.  Any other cicp: the curves and colorants are read.
+ * Tables on the device: when the three tables are identical at the depth in use one is uploaded and the kernels run as without a profile;
+ * otherwise three - red, green, blue - and channel c of a pixel looks up lin[(c << bits) + min(v, peak)].  Everything behind the lookup
+ * (sums, matrix, tone step, finish, the alpha and gain steps beside it) is as stated above; an alpha step's background colour goes
+ * through its channel's table.  The tone step's rule holds: unit_nits must be given (no profile says what 1.0 stands for).
+ * A launch's tables must fit 64 KB of local memory: three distinct 12-bit curves with a 12-bit re-encoding AND a tone step, or any
+ * combination above that, is HM_ERR_UNSUPPORTED (the message names the depth and the steps), before a byte of the destination is written.
+ * Refused (HM_ERR_UNSUPPORTED, the message names the reason): major version 5 or any other than 2 and 4, connection space Lab, device
+ * link, abstract, named-colour and every other class, CMYK and other data spaces, profiles with only A2B0 / lookup-table tags and no
+ * matrix/TRC set; an OOTF step beside the profile (it renders HLG scene light, which no matrix/TRC profile describes); the frames family
+ * (a track's sample entry profile is not read); the stand-alone forms other than hm_icc_to_tensor (they have no item); a profile as the
+ * destination and planar targets stay out of scope.  Malformed (HM_ERR_BITSTREAM): a size field above the bytes given or below the
+ * header, a tag table that runs off the end, a tag that overlaps the header or the tag table or runs past the end, a missing tag of the
+ * set, a tag whose type signature is not the one its use needs, a bad curve. */
+enum { HM_LIGHT_FROM_ICC = -1 };
+enum { HM_ICC_RGB = 1, HM_ICC_GRAY = 2 };
+enum { HM_ICC_CURVE_IDENTITY = 0, HM_ICC_CURVE_GAMMA = 1, HM_ICC_CURVE_TABLE = 2, HM_ICC_CURVE_PARA = 3 };
+typedef struct hm_icc_curve {
+  int32_t kind;                            /* HM_ICC_CURVE_* */
+  int32_t count;                           /* 'curv': its entry count; 'para': the function type 0 .. 4 */
+  double  p[7];                            /* 'para': g a b c d e f (those the type has, the rest 0); GAMMA: p[0] = g; else 0 */
+} hm_icc_curve;
+typedef struct hm_icc_info {
+  int32_t version_major, version_minor;
+  int32_t colour_space;                    /* HM_ICC_RGB / HM_ICC_GRAY */
+  int32_t same_curves;                     /* the three TRC tags are the same tag data (one offset, or equal bytes); GRAY: 1 */
+  int32_t has_cicp;                        /* the profile has a 'cicp' tag: cicp[] = primaries, transfer, matrix, full range */
+  int32_t cicp[4];
+  int32_t cicp_known;                      /* ... and both its primaries and its transfer are codes the light step knows */
+  double  colorant[9];                     /* row-major: column k = the XYZ of r / g / b; GRAY: 0 */
+  hm_icc_curve curve[3];                   /* r, g, b; GRAY: kTRC three times */
+} hm_icc_info;
+/* Host arithmetic, no device.  HM_OK, or the refusal. */
+HM_API int hm_icc_parse(const uint8_t* icc, size_t size, hm_icc_info* out);
+/* lin_c of channel 0 .. 2 (GRAY: 0) at bits 8 .. 12: 1 << bits floats.  Returns the count, or a negative status. */
+HM_API int hm_icc_table(const uint8_t* icc, size_t size, int channel, int bits, float gain, float* out);
+/* the row-major float32 matrix from the profile's colorants to to_primaries (a code hm_light_matrix knows) */
+HM_API int hm_icc_matrix(const uint8_t* icc, size_t size, int to_primaries, float m[9]);
+/* hm_icc_parse on the profile hm_file_item_icc(f, id, 1, ...) reports.  HM_ICC_NO_PROFILE (out zeroed): the item has none. */
+enum { HM_ICC_NO_PROFILE = 1 };
+HM_API int hm_file_item_icc_info(const hm_file* f, uint32_t id, hm_icc_info* out);
+/* (hm_icc_to_tensor, the step on its own with a profile as the source: behind hm_alpha_to_tensor, whose steps it takes) */
 
 /* ------------------------------------------------------------------------- */
 /* Tone: the BT.2390 curve by table inside the light step, the content's peak from the file, an 8-bit finish */
@@ -926,6 +997,11 @@ HM_API int hm_pipeline_submit_to_device_alpha(hm_pipeline* p, const uint8_t* hei
 HM_API int hm_alpha_to_tensor(int out_format, int bits, int src_w, int src_h, const void* d_src, int src_stride, const hm_device_view* view,
                               const hm_device_light* light, const hm_device_tone* tone, const hm_device_alpha* alpha, const hm_device_dest* dest,
                               void* stream);
+/* The light step on its own with a profile as the source (as hm_alpha_to_tensor; view, tone and alpha may be NULL): light must carry
+ * HM_LIGHT_FROM_ICC in both fields.  The profile is read before the call returns.  Asynchronous on `stream`. */
+HM_API int hm_icc_to_tensor(int out_format, int bits, int src_w, int src_h, const void* d_src, int src_stride, const hm_device_view* view,
+                            const uint8_t* icc, size_t icc_size, const hm_device_light* light, const hm_device_tone* tone,
+                            const hm_device_alpha* alpha, const hm_device_dest* dest, void* stream);
 
 /* ------------------------------------------------------------------------- */
 /* Gain: an SDR base image and its gain map ('tmap', ISO 21496-1) rendered to HDR light for a display's headroom */
