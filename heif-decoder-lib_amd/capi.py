@@ -248,6 +248,36 @@ class OverlayInfo(C.Structure):
 
 HM_ITEM_OTHER, HM_ITEM_HVC1, HM_ITEM_GRID, HM_ITEM_IDEN, HM_ITEM_IOVL, HM_ITEM_TMAP = 0, 1, 2, 3, 4, 5
 HM_ITEM_UNCI = 6
+HM_ITEM_MSKI = 7
+
+# regions and masks ('rgan' / 'mski'): hm_region, hm_regions_dest
+HM_REGION_POINT, HM_REGION_RECTANGLE, HM_REGION_ELLIPSE, HM_REGION_POLYGON, HM_REGION_REFERENCED_MASK, HM_REGION_INLINE_MASK, HM_REGION_POLYLINE = range(7)
+REGION_TYPE_NAMES = ("point", "rectangle", "ellipse", "polygon", "referenced_mask", "inline_mask", "polyline")
+HM_REGIONS_STACK, HM_REGIONS_LABELS = 0, 1
+
+
+class RegionItemInfo(C.Structure):
+    """hm_region_item_info"""
+    _fields_ = [("reference_width", C.c_uint32), ("reference_height", C.c_uint32), ("n_regions", C.c_int32), ("field_bits", C.c_int32)]
+
+
+class Region(C.Structure):
+    """hm_region: x, y, w, h are centre and radii for an ellipse"""
+    _fields_ = [("type", C.c_int32), ("x", C.c_int32), ("y", C.c_int32), ("w", C.c_uint32), ("h", C.c_uint32), ("n_points", C.c_uint32),
+                ("mask_item", C.c_uint32), ("mask_bytes", C.c_uint64)]
+
+
+class RegionsDest(C.Structure):
+    """hm_regions_dest: caller-owned device memory the planes of a region raster go to"""
+    _fields_ = [("ptr", C.c_void_p), ("len", C.c_uint64), ("dtype", C.c_int32), ("reserved", C.c_int32), ("row_pitch", C.c_int64),
+                ("plane_pitch", C.c_int64), ("scale", C.c_float), ("bias", C.c_float)]
+
+
+class RegionsOut(C.Structure):
+    """hm_regions_out"""
+    _fields_ = [("width", C.c_int32), ("height", C.c_int32), ("n_regions", C.c_int32), ("planes", C.c_int32), ("bytes", C.c_int64),
+                ("reference_width", C.c_uint32), ("reference_height", C.c_uint32)]
+
 
 # uncompressed items (ISO/IEC 23001-17): hm_unci_info
 HM_UNCI_MONO, HM_UNCI_YCBCR, HM_UNCI_RGB = 0, 1, 2
@@ -422,6 +452,17 @@ def bind_image(L):
     L.hm_unci_payload_bytes.argtypes = [C.POINTER(UnciInfo), C.POINTER(C.c_uint64)]
     L.hm_unci_unpack.argtypes = [C.POINTER(UnciInfo), C.c_void_p, C.c_size_t, C.POINTER(C.c_int32 * 4), C.POINTER(Planes), C.c_int, C.POINTER(DeviceDest),
                                  C.c_void_p]
+    L.hm_file_region_items.argtypes = [C.c_void_p, C.c_uint32, C.POINTER(C.c_uint32), C.c_int]
+    L.hm_file_region_item_info.argtypes = [C.c_void_p, C.c_uint32, C.POINTER(RegionItemInfo)]
+    L.hm_file_region.argtypes = [C.c_void_p, C.c_uint32, C.c_int, C.POINTER(Region)]
+    L.hm_file_region_points.argtypes = [C.c_void_p, C.c_uint32, C.c_int, C.POINTER(C.c_int32), C.c_int]
+    L.hm_file_region_inline_mask.argtypes = [C.c_void_p, C.c_uint32, C.c_int, C.POINTER(C.POINTER(C.c_uint8)), C.POINTER(C.c_size_t)]
+    L.hm_regions_dest_bytes.argtypes = [C.c_int, C.c_int, C.c_int, C.c_int, C.POINTER(RegionsDest)]
+    L.hm_regions_dest_bytes.restype = C.c_int64
+    L.hm_rasterise_regions.argtypes = [C.POINTER(Region), C.POINTER(C.c_void_p), C.c_int, C.c_int, C.c_int, C.POINTER(DeviceView), C.c_int,
+                                       C.POINTER(RegionsDest), C.c_void_p]
+    L.hm_regions_to_device.argtypes = [C.c_void_p, C.POINTER(C.c_uint32), C.c_int, C.POINTER(DeviceView), C.c_int, C.POINTER(RegionsDest),
+                                       C.POINTER(RegionsOut)]
     L.hm_pipeline_pending.argtypes = [C.c_void_p]
     L.hm_pipeline_next.argtypes = [C.c_void_p, C.POINTER(PipelineResult)]
     L.hm_pipeline_release.argtypes = [C.c_void_p, C.POINTER(PipelineResult)]

@@ -607,7 +607,33 @@ int with_scratch(hipStream_t s, const std::function<int(hm_view_scratch*)>& writ
   }
   return rc;
 }
+struct Retired { std::vector<hm_view_scratch> v; };
+void retired_done(void* arg)
+{
+  Retired* r = static_cast<Retired*>(arg);
+  { std::lock_guard<std::mutex> g(g_done_mu); g_done.insert(g_done.end(), r->v.begin(), r->v.end()); }
+  delete r;
+}
 } // namespace
+
+// with_scratch for a stand-alone entry outside this file (regions.hip) that works on several entries: the blocks of sc[0 .. n) follow
+// the stream to release_done, which this call runs first; the entries are emptied
+void hm_view_scratch_retire(hipStream_t s, hm_view_scratch* sc, int n)
+{
+  release_done();
+  Retired* r = new (std::nothrow) Retired();
+  for (int i = 0; i < n; i++)
+    if (r && (sc[i].dev[0] || sc[i].dev[1] || sc[i].pinned)) r->v.push_back(sc[i]);
+  if (r && r->v.empty()) { delete r; return; }
+  if (!r || hipLaunchHostFunc(s, retired_done, r) != hipSuccess) { // (never on a healthy runtime: wait, then release here)
+    (void)hipGetLastError();
+    hipStreamSynchronize(s);
+    for (int i = 0; i < n; i++) hm_view_scratch_free(&sc[i]);
+    delete r;
+    return;
+  }
+  for (int i = 0; i < n; i++) sc[i] = hm_view_scratch{{nullptr, nullptr}, nullptr};
+}
 
 // ---- the light step (hm_device_light) -------------------------------------------------------------------------------------------
 

@@ -3,6 +3,7 @@
 #include "hm_overlay_plan.h"
 #include "hm_unci_layout.h"
 
+#include <algorithm>
 #include <cstring>
 
 #include "heif_mi355x.h"
@@ -105,9 +106,11 @@ std::vector<uint32_t> HeifFile::top_level_images() const
   }
   for (const auto& kv : items_) {
     const Item& it = kv.second;
-    if (it.type != "hvc1" && it.type != "grid" && it.type != "iden" && it.type != "iovl" && it.type != "unci") continue;
+    if (it.type != "hvc1" && it.type != "grid" && it.type != "iden" && it.type != "iovl" && it.type != "unci" && !it.is_mask()) continue;
     bool sub = false;
     for (const Ref& r : refs_) {
+      if (r.type == "mask") // (the mask of a region is no image of its own: context.cc:1230, remove_top_level_image)
+        for (uint32_t t : r.to) if (t == it.id) sub = true;
       if ((r.type == "thmb" || r.type == "auxl") && r.from == it.id) sub = true;
       if (r.type == "dimg") {
         const Item* from = item(r.from);
@@ -126,6 +129,7 @@ bool HeifFile::parse(const uint8_t* data, size_t size, HeifError& err)
   size_ = size;
   items_.clear();
   refs_.clear();
+  regions_.clear();
   idat_.clear();
   primary_ = 0;
   movie_mode_ = false;
@@ -158,6 +162,10 @@ bool HeifFile::parse(const uint8_t* data, size_t size, HeifError& err)
   if (!have_ftyp) { err = {HM_ERR_BITSTREAM, "no ftyp box: not a HEIF file"}; return false; }
   if (metas.empty()) { err = {HM_ERR_BITSTREAM, "no meta box"}; return false; }
   if (!primary_ || !items_.count(primary_)) { err = {HM_ERR_BITSTREAM, "no primary item"}; return false; }
+  // the region items: read now, judged by the calls that read them (a damaged one does not fail the file)
+  regions_.clear();
+  for (const auto& kv : items_)
+    if (kv.second.type == "rgan") parse_region_item(kv.first, regions_[kv.first]);
   return true;
 }
 
@@ -355,6 +363,9 @@ bool HeifFile::parse_iprp(const uint8_t* p, size_t n, HeifError& err)
           }
         }
         else if (pb.type == "cmpC" || pb.type == "icbr") ip.uncc.generic_compression = true;
+        else if (pb.type == "mskC") { // (a box too short to hold its byte is no mskC: the item stays what it was without one)
+          if (pb.size >= 5) { ip.has_mskc = true; ip.mskc_bits = pb.body[4]; }
+        }
         else if (pb.type == "hvcC") {
           HvcC& h = ip.hvcc;
           h.present = true;
@@ -537,10 +548,24 @@ bool HeifFile::gain_map_info(uint32_t id, GainMapInfo& g, HeifError& err) const
 bool HeifFile::unci_info(uint32_t id, hm_unci_info& info, HeifError& err) const
 {
   const Item* it = item(id);
-  if (!it || it->type != "unci") { err = {HM_ERR_INVALID_ARG, "item is not an 'unci' image"}; return false; }
+  if (!it || !it->is_raw_leaf()) { err = {HM_ERR_INVALID_ARG, "item is not an 'unci' image"}; return false; }
   const UncC& u = it->props.uncc;
   auto unsupported = [&](const std::string& m) { err = {HM_ERR_UNSUPPORTED, m}; return false; };
   std::memset(&info, 0, sizeof(info));
+  if (it->is_mask()) { // the payload's bytes, row after row, tight (MaskImageCodec::decode_mask_image): one 8-bit monochrome component
+    if (it->props.ispe_width <= 0 || it->props.ispe_height <= 0) { err = {HM_ERR_BITSTREAM, "Missing required ispe box for mask codec"}; return false; }
+    if (it->props.mskc_bits != 8) return unsupported("mski: bits_per_pixel " + std::to_string(it->props.mskc_bits) + " is not supported (8 is)");
+    info.width = it->props.ispe_width; info.height = it->props.ispe_height;
+    info.colour_space = HM_UNCI_MONO; info.n_components = 1;
+    info.comp[0] = {HM_UNCI_TYPE_MONO, 8, 0};
+    info.sampling = HM_UNCI_SAMPLING_NONE; info.interleave = HM_UNCI_INTERLEAVE_COMPONENT;
+    info.tile_cols = info.tile_rows = 1; info.tile_width = (uint32_t)info.width; info.tile_height = (uint32_t)info.height;
+    hm_unci_layout L;
+    const int rc = hm_unci_layout_compute(&info, &L);
+    if (rc) { err = {rc, hm_last_error()}; return false; }
+    info.payload_bytes = L.total_bytes;
+    return true;
+  }
   if (it->props.ispe_width <= 0 || it->props.ispe_height <= 0) { err = {HM_ERR_BITSTREAM, "Missing required ispe box for uncompressed codec"}; return false; }
   if (!u.present) { err = {HM_ERR_BITSTREAM, "Missing required uncC box for uncompressed codec"}; return false; }
   if (u.generic_compression) return unsupported("unci: generic compression ('cmpC' / 'icbr') is not supported");
@@ -610,6 +635,113 @@ bool HeifFile::unci_info(uint32_t id, hm_unci_info& info, HeifError& err) const
   const int rc = hm_unci_layout_compute(&info, &L);
   if (rc) { err = {rc, hm_last_error()}; return false; }
   info.payload_bytes = L.total_bytes;
+  return true;
+}
+
+// ---- region items ------------------------------------------------------------------------------------------------------------------
+// RegionItem::parse (region.cc:30-116) with the departures include/heif_mi355x.h states: an unknown geometry type is refused (the
+// reference goes on without skipping the region's bytes), an inline mask holds (w * h + 7) / 8 bytes and the regions behind it start
+// behind those bytes (the reference takes w * h / 8 and does not step over them), and the magnitude limits.
+void HeifFile::parse_region_item(uint32_t id, RegionItem& r) const
+{
+  r = RegionItem();
+  std::vector<uint8_t> d;
+  if (!item_data(id, d, r.err)) return;
+  auto fail = [&](int status, const std::string& m) { r.err = {status, "region item " + std::to_string(id) + ": " + m}; r.regions.clear(); };
+  if (d.size() < 8) return fail(HM_ERR_BITSTREAM, "Less than 8 bytes of data");
+  Rd q(d.data(), d.size());
+  q.skip(1); // version: unused
+  const int fb = (q.u(1) & 1) ? 4 : 2;
+  r.field_bits = fb * 8;
+  const int64_t lim = HM_REGION_COORD_LIMIT;
+  bool over = false;
+  auto us = [&]() { const uint64_t v = q.u(fb); if (v >= (uint64_t)lim) over = true; return (uint32_t)v; };
+  auto sg = [&]() { const uint64_t v = q.u(fb); const int64_t s = fb == 4 ? (int64_t)(int32_t)(uint32_t)v : (int64_t)(int16_t)(uint16_t)v; if (s < -lim || s >= lim) over = true; return (int32_t)s; };
+  r.reference_width = us(); r.reference_height = us();
+  const int count = (int)q.u(1);
+  if (!q.ok) return fail(HM_ERR_BITSTREAM, "Region data incomplete");
+  const std::vector<uint32_t> masks = references(id, "mask");
+  size_t next_mask = 0;
+  for (int i = 0; i < count; i++) {
+    Region g;
+    g.type = (int)q.u(1);
+    if (!q.ok) return fail(HM_ERR_BITSTREAM, "Region data incomplete");
+    const std::string where = "region " + std::to_string(i);
+    switch (g.type) {
+      case HM_REGION_POINT: g.x = sg(); g.y = sg(); break;
+      case HM_REGION_RECTANGLE: case HM_REGION_ELLIPSE: case HM_REGION_REFERENCED_MASK: case HM_REGION_INLINE_MASK:
+        g.x = sg(); g.y = sg(); g.w = us(); g.h = us(); break;
+      case HM_REGION_POLYGON: case HM_REGION_POLYLINE: {
+        const uint64_t n = q.u(fb);
+        if (!q.ok || n * 2 * (uint64_t)fb > q.left()) return fail(HM_ERR_BITSTREAM, where + ": insufficient data remaining for the points of a polygon");
+        g.points.resize((size_t)n * 2);
+        for (size_t k = 0; k < g.points.size(); k++) g.points[k] = sg();
+        break;
+      }
+      default:
+        return fail(HM_ERR_UNSUPPORTED, where + " has the unknown geometry type " + std::to_string(g.type) + " (0..6 are defined)");
+    }
+    if (!q.ok) return fail(HM_ERR_BITSTREAM, where + ": insufficient data remaining for a region of type " + std::to_string(g.type));
+    if (over) return fail(HM_ERR_UNSUPPORTED, where + ": a coordinate outside -2^28 <= v < 2^28 or a size of 2^28 or more (the limits of the rasteriser's exact arithmetic)");
+    if (g.type == HM_REGION_ELLIPSE && (g.w > HM_REGION_MAX_RADIUS || g.h > HM_REGION_MAX_RADIUS))
+      return fail(HM_ERR_UNSUPPORTED, where + ": an ellipse radius above 32767 (the limit of the rasteriser's exact arithmetic)");
+    if (g.type == HM_REGION_INLINE_MASK) {
+      const unsigned method = (unsigned)q.u(1);
+      if (!q.ok) return fail(HM_ERR_BITSTREAM, where + ": insufficient data remaining for inline mask region");
+      if (method != 0) return fail(HM_ERR_UNSUPPORTED, where + ": Deflate compressed inline mask is not yet supported (mask_coding_method " + std::to_string(method) + ")");
+      const uint64_t bytes = ((uint64_t)g.w * g.h + 7) / 8;
+      if (bytes > q.left()) return fail(HM_ERR_BITSTREAM, where + ": insufficient data remaining for inline mask region data[]");
+      g.bits.assign(q.p + q.pos, q.p + q.pos + bytes);
+      q.skip((size_t)bytes);
+    }
+    if (g.type == HM_REGION_REFERENCED_MASK) {
+      if (next_mask >= masks.size()) return fail(HM_ERR_BITSTREAM, where + " is referenced mask " + std::to_string(next_mask) + ", the 'mask' reference has " + std::to_string(masks.size()) + " entries");
+      g.mask_item = masks[next_mask++];
+      const Item* m = item(g.mask_item);
+      if (!m || !m->is_mask()) return fail(HM_ERR_UNSUPPORTED, where + ": the 'mask' reference names item " + std::to_string(g.mask_item) + ", which is not a mask image ('mski' with mskC)");
+      const uint32_t mw = (uint32_t)std::max(0, m->props.ispe_width), mh = (uint32_t)std::max(0, m->props.ispe_height);
+      if (!g.w) g.w = mw;
+      if (!g.h) g.h = mh;
+      if (g.w != mw || g.h != mh)
+        return fail(HM_ERR_UNSUPPORTED, where + ": a referenced mask of " + std::to_string(g.w) + " x " + std::to_string(g.h) + " on a mask item of " + std::to_string(mw) + " x " + std::to_string(mh) + " (masks are not scaled)");
+      if (mw >= (uint64_t)lim || mh >= (uint64_t)lim) return fail(HM_ERR_UNSUPPORTED, where + ": a mask size of 2^28 or more");
+    }
+    r.regions.push_back(std::move(g));
+  }
+}
+
+const RegionItem* HeifFile::region_item(uint32_t id, HeifError& err) const
+{
+  auto it = regions_.find(id);
+  if (it == regions_.end()) { err = {HM_ERR_INVALID_ARG, "item " + std::to_string(id) + " is not a region item ('rgan')"}; return nullptr; }
+  if (it->second.err.status) { err = it->second.err; return nullptr; }
+  return &it->second;
+}
+
+std::vector<uint32_t> HeifFile::region_items_of(uint32_t image) const
+{
+  std::vector<uint32_t> out;
+  for (const auto& kv : regions_) // (item-id order)
+    for (const Ref& r : refs_) {
+      if (r.type != "cdsc" || r.from != kv.first) continue;
+      bool names = false;
+      for (uint32_t t : r.to) names |= t == image;
+      if (names) { out.push_back(kv.first); break; }
+    }
+  return out;
+}
+
+bool HeifFile::item_span(uint32_t id, const uint8_t** p, size_t* n, HeifError& err) const
+{
+  const Item* it = item(id);
+  if (!it || it->extents.size() != 1 || it->construction_method > 1) { err = {HM_ERR_UNSUPPORTED, "item data in several extents"}; return false; }
+  const uint8_t* src = it->construction_method == 1 ? idat_.data() : data_;
+  const size_t avail = it->construction_method == 1 ? idat_.size() : size_;
+  const uint64_t off = it->base_offset + it->extents[0].offset;
+  uint64_t len = it->extents[0].length;
+  if (len == 0 && off <= avail) len = avail - off;
+  if (off > avail || len > avail - off) { err = {HM_ERR_BITSTREAM, "item extent outside the file"}; return false; }
+  *p = src + off; *n = (size_t)len;
   return true;
 }
 

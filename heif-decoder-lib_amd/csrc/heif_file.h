@@ -1,8 +1,10 @@
 // heif_file.h — minimal ISOBMFF / HEIF reader for the decode path (host side).
 // Counterpart of the parts of libheif/file.cc, box.cc and codecs/hevc.cc the hot path needs:
 // item locations (iloc), item infos (iinf), references (iref: dimg/auxl/thmb), properties
-// (ipco/ipma: hvcC, ispe, pixi, colr, irot, imir, clap, auxC, clli, mdcv, cmpd, uncC), primary item (pitm), idat, and the payload of a 'tmap'
+// (ipco/ipma: hvcC, ispe, pixi, colr, irot, imir, clap, auxC, clli, mdcv, cmpd, uncC, mskC), primary item (pitm), idat, and the payload of a 'tmap'
 // item (ISO 21496-1 gain map: include/heif_mi355x.h states its layout).  'unci' items (ISO/IEC 23001-17): libheif/codecs/uncompressed_box.cc.
+// Region items ('rgan') and mask items ('mski' + mskC): libheif/region.cc, codecs/mask_image.cc, context.cc:1166-1237; the rules of
+// include/heif_mi355x.h, "Regions and masks".
 // Movie mode (the fork's image sequences): a 'moov' track of HEVC-intra samples, each sample a top-level image
 // (file.cc:474-483, 1154-1244; context.cc:646-700 of the reference).
 #ifndef HM_HEIF_FILE_H
@@ -77,6 +79,9 @@ struct ItemProps {
   uint16_t clli[2] = {0, 0};   // max_content_light_level, max_pic_average_light_level
   uint16_t mdcv_xy[8] = {0, 0, 0, 0, 0, 0, 0, 0}; // display_primaries x0 y0 x1 y1 x2 y2, white point x y
   uint32_t mdcv_lum[2] = {0, 0}; // max / min display mastering luminance, 0.0001 cd/m2
+  // 'mskC' (codecs/mask_image.cc:33-45): a full box holding bits_per_pixel
+  bool has_mskc = false;
+  int mskc_bits = 0;
 };
 
 struct Extent { uint64_t offset, length; };
@@ -89,6 +94,27 @@ struct Item {
   std::vector<Extent> extents;
   ItemProps props;
   bool hidden = false;
+  // a mask image: an 'mski' item that carries its 'mskC' (one without is no image: "Missing required box for mask codec")
+  bool is_mask() const { return type == "mski" && props.has_mskc; }
+  // a leaf without coded pictures whose samples lie uncompressed in its payload: an 'unci' item, or a mask image as a monochrome one
+  bool is_raw_leaf() const { return type == "unci" || is_mask(); }
+};
+
+// One region of an 'rgan' item as its payload states it (RegionGeometry::parse, region.cc:203-422)
+struct Region {
+  int type = 0;                  // HM_REGION_*
+  int32_t x = 0, y = 0;
+  uint32_t w = 0, h = 0;         // size; an ellipse's radii.  A referenced mask: a stated 0 replaced by the mask item's ispe
+  std::vector<int32_t> points;   // x, y pairs (polygon, polyline)
+  std::vector<uint8_t> bits;     // an inline mask's (w * h + 7) / 8 bytes
+  uint32_t mask_item = 0;        // a referenced mask: its entry of the item's 'mask' reference
+};
+// An 'rgan' item read at open; a damaged one keeps its error for the calls that read it
+struct RegionItem {
+  HeifError err{0, ""};          // status 0: the item reads
+  uint32_t reference_width = 0, reference_height = 0;
+  int field_bits = 16;
+  std::vector<Region> regions;
 };
 
 struct GridInfo {
@@ -156,7 +182,14 @@ class HeifFile {
   // the first 'tmap' item whose first 'dimg' reference is `base` (0 if none)
   uint32_t gain_map_of(uint32_t base) const;
   // an 'unci' item: its cmpd / uncC / ispe judged and turned into the description the layout starts from (hm_unci_layout.h)
+  // ... and a mask image ('mski' + mskC, 8 bits) as the monochrome 8-bit item in component interleave its payload is (mask_image.cc:95-125)
   bool unci_info(uint32_t id, hm_unci_info& info, HeifError& err) const;
+  // an 'rgan' item: nullptr and err when `id` is none or the item is damaged
+  const RegionItem* region_item(uint32_t id, HeifError& err) const;
+  // the 'rgan' items whose 'cdsc' reference names `image`, in item-id order
+  std::vector<uint32_t> region_items_of(uint32_t image) const;
+  // where an item's payload lies when it is ONE run of bytes of the file (or of idat): *p, *n; false: several extents (item_data joins them)
+  bool item_span(uint32_t id, const uint8_t** p, size_t* n, HeifError& err) const;
   bool is_movie() const { return movie_mode_; }
   const Movie& movie() const { return movie_; }
 
@@ -165,6 +198,8 @@ class HeifFile {
   bool parse_meta(const uint8_t* p, size_t n, HeifError& err);
   bool parse_iprp(const uint8_t* p, size_t n, HeifError& err);
   bool parse_moov(const uint8_t* p, size_t n, HeifError& err);
+  void parse_region_item(uint32_t id, RegionItem& r) const;
+  std::map<uint32_t, RegionItem> regions_;
   bool movie_sample(uint32_t id, std::vector<uint8_t>& out, HeifError& err) const;
   bool movie_mode_ = false;
   Movie movie_;

@@ -90,6 +90,9 @@ typedef struct hm_view_plan {
 // device / pinned blocks a view write works on; they must live until the stream has passed the write (hm_view_scratch_free)
 typedef struct hm_view_scratch { void* dev[2]; void* pinned; } hm_view_scratch;
 void hm_view_scratch_free(hm_view_scratch* sc);
+// a stand-alone entry that returns before its kernels have run: the blocks of sc[0 .. n) go back to the pools once stream `s` has passed
+// this point (a later stand-alone call releases them); the entries are emptied
+void hm_view_scratch_retire(hipStream_t s, hm_view_scratch* sc, int n);
 // the view against a src_w x src_h image and the target: every refusal of the view itself
 int hm_view_resolve(int out_format, int src_w, int src_h, const hm_device_view* v, hm_view_plan* vp);
 // one frame of a batched view write: the destination, the view resolved against the frame, the frame's interleaved pixels (row 0 = image row 0)

@@ -320,7 +320,7 @@ int hm_file_image_info(const hm_file* f, uint32_t id, hm_image_info* info)
     }
     if (first->type != "hvc1") return hm_fail(HM_ERR_UNSUPPORTED, "item type '%s' under a derived image is not an HEVC image", first->type.c_str());
   }
-  else if (it->type == "unci") {
+  else if (it->is_raw_leaf()) { // (a mask image: the monochrome 8-bit item HeifFile::unci_info makes of it)
     hm_unci_info u;
     if (!f->file.unci_info(id, u, err)) return fail_from(err);
     info->width = u.width; info->height = u.height;
@@ -339,7 +339,7 @@ int hm_file_image_info(const hm_file* f, uint32_t id, hm_image_info* info)
     info->tile_width = (int32_t)u.tile_width; info->tile_height = (int32_t)u.tile_height;
   }
   else return hm_fail(HM_ERR_UNSUPPORTED, "item type '%s' is not an HEVC image, a grid, a derived image or an uncompressed image", it->type.c_str());
-  const bool unci = it->type == "unci";
+  const bool unci = it->is_raw_leaf();
   if (!unci) {
     if (!first->props.hvcc.present) return hm_fail(HM_ERR_BITSTREAM, "image without hvcC");
     info->bit_depth = first->props.hvcc.bit_depth_luma;
@@ -476,6 +476,7 @@ int plan_item(const hm_file* f, uint32_t id, ItemPlan& P, bool self_grid = false
       P.tiles[i].id = g.tiles[i];
       const hm::Item* ti = f->file.item(g.tiles[i]);
       if (ti && ti->type == "unci") return hm_fail(HM_ERR_UNSUPPORTED, "grid tile %zu (item %u) is an uncompressed ('unci') item: only coded HEVC images are grid tiles here", i, g.tiles[i]);
+      if (ti && ti->is_mask()) return hm_fail(HM_ERR_UNSUPPORTED, "grid tile %zu (item %u) is a mask ('mski') item: only coded HEVC images are grid tiles here", i, g.tiles[i]);
     }
   }
   else if (it->type == "hvc1") {
@@ -792,7 +793,7 @@ bool view_subgrid(const hm_file* f, uint32_t id, const hm_decode_params* params,
 {
   t[0] = 0; t[1] = 1; t[2] = 0; t[3] = 1;
   const hm::Item* it = f->file.item(id);
-  if (it && it->type == "unci") return unci_view_subgrid(f, id, params, v, t, x0, y0, w, h, planes_view);
+  if (it && it->is_raw_leaf()) return unci_view_subgrid(f, id, params, v, t, x0, y0, w, h, planes_view);
   if (!it || it->type != "grid") return false;
   hm::GridInfo g;
   hm::HeifError err;
@@ -846,6 +847,8 @@ static int unci_alpha_depth(const hm_unci_info& u)
 static int plan_unci(DecodeJob& j)
 {
   const hm_decode_params& prm = j.params;
+  if (!j.allow_unci && j.f->file.item(j.id)->is_mask())
+    return hm_fail(HM_ERR_UNSUPPORTED, "a mask ('mski') item is not supported by the pipeline, batch and sequence calls: decode it with hm_decode_item");
   if (!j.allow_unci)
     return hm_fail(HM_ERR_UNSUPPORTED, "an uncompressed ('unci') item is not supported by the pipeline, batch and sequence calls: decode it with hm_decode_item");
   hm::HeifError err;
@@ -890,7 +893,7 @@ static int plan_unci(DecodeJob& j)
 int job_plan(DecodeJob& j)
 {
   const hm::Item* it0 = j.f->file.item(j.id);
-  j.unci = it0 && it0->type == "unci";
+  j.unci = it0 && it0->is_raw_leaf();
   if (j.unci) return plan_unci(j);
   int rc = plan_item(j.f, j.id, j.item[0], j.self_grid);
   if (rc) return rc;
@@ -2045,6 +2048,7 @@ int hm_file_item_kind(const hm_file* f, uint32_t id)
   if (it->type == "iovl") return HM_ITEM_IOVL;
   if (it->type == "tmap") return HM_ITEM_TMAP;
   if (it->type == "unci") return HM_ITEM_UNCI;
+  if (it->is_mask()) return HM_ITEM_MSKI;
   return HM_ITEM_OTHER;
 }
 
@@ -2054,6 +2058,134 @@ int hm_file_unci_info(const hm_file* f, uint32_t id, hm_unci_info* info)
   if (!f->file.item(id)) return hm_fail(HM_ERR_INVALID_ARG, "no item %u", id);
   hm::HeifError err;
   return f->file.unci_info(id, *info, err) ? (int)HM_OK : fail_from(err);
+}
+
+// ---- region items ('rgan'): what the file layer read at open, handed out; hm_regions_to_device gathers it for the rasteriser ----
+
+int hm_file_region_items(const hm_file* f, uint32_t image_id, uint32_t* ids, int max_ids)
+{
+  if (!f) return hm_fail(HM_ERR_INVALID_ARG, "null file");
+  const std::vector<uint32_t> v = f->file.region_items_of(image_id);
+  for (int i = 0; i < (int)v.size() && i < max_ids && ids; i++) ids[i] = v[i];
+  return (int)v.size();
+}
+
+int hm_file_region_item_info(const hm_file* f, uint32_t region_item, hm_region_item_info* info)
+{
+  if (!f || !info) return hm_fail(HM_ERR_INVALID_ARG, "null argument");
+  hm::HeifError err;
+  const hm::RegionItem* r = f->file.region_item(region_item, err);
+  if (!r) return fail_from(err);
+  info->reference_width = r->reference_width; info->reference_height = r->reference_height;
+  info->n_regions = (int32_t)r->regions.size(); info->field_bits = r->field_bits;
+  return HM_OK;
+}
+
+static const hm::Region* region_of(const hm_file* f, uint32_t region_item, int index, int* rc)
+{
+  hm::HeifError err;
+  const hm::RegionItem* r = f ? f->file.region_item(region_item, err) : nullptr;
+  if (!f) { *rc = hm_fail(HM_ERR_INVALID_ARG, "null file"); return nullptr; }
+  if (!r) { *rc = fail_from(err); return nullptr; }
+  if (index < 0 || (size_t)index >= r->regions.size()) { *rc = hm_fail(HM_ERR_INVALID_ARG, "region item %u has %zu regions, no region %d", region_item, r->regions.size(), index); return nullptr; }
+  return &r->regions[(size_t)index];
+}
+
+static void region_describe(const hm::Region& g, hm_region* out)
+{
+  std::memset(out, 0, sizeof(*out));
+  out->type = g.type; out->x = g.x; out->y = g.y; out->w = g.w; out->h = g.h;
+  out->n_points = (uint32_t)(g.points.size() / 2);
+  out->mask_item = g.mask_item;
+  out->mask_bytes = g.type == HM_REGION_INLINE_MASK ? (uint64_t)g.bits.size() : g.type == HM_REGION_REFERENCED_MASK ? (uint64_t)g.w * g.h : 0;
+}
+
+int hm_file_region(const hm_file* f, uint32_t region_item, int index, hm_region* out)
+{
+  if (!out) return hm_fail(HM_ERR_INVALID_ARG, "null argument");
+  int rc = HM_OK;
+  const hm::Region* g = region_of(f, region_item, index, &rc);
+  if (!g) return rc;
+  region_describe(*g, out);
+  return HM_OK;
+}
+
+int hm_file_region_points(const hm_file* f, uint32_t region_item, int index, int32_t* xy, int max_points)
+{
+  int rc = HM_OK;
+  const hm::Region* g = region_of(f, region_item, index, &rc);
+  if (!g) return rc;
+  const int n = (int)(g->points.size() / 2);
+  for (int i = 0; i < n && i < max_points && xy; i++) { xy[2 * i] = g->points[2 * (size_t)i]; xy[2 * i + 1] = g->points[2 * (size_t)i + 1]; }
+  return n;
+}
+
+int hm_file_region_inline_mask(const hm_file* f, uint32_t region_item, int index, const uint8_t** bits, size_t* len)
+{
+  if (!bits || !len) return hm_fail(HM_ERR_INVALID_ARG, "null argument");
+  int rc = HM_OK;
+  const hm::Region* g = region_of(f, region_item, index, &rc);
+  if (!g) return rc;
+  if (g->type != HM_REGION_INLINE_MASK) return hm_fail(HM_ERR_INVALID_ARG, "region %d of item %u is not an inline mask (type %d)", index, region_item, g->type);
+  *bits = g->bits.data(); *len = g->bits.size();
+  return HM_OK;
+}
+
+int hm_regions_to_device(const hm_file* f, const uint32_t* region_items, int n, const hm_device_view* view, int mode, const hm_regions_dest* dest,
+                         hm_regions_out* out)
+{
+  if (!f || !region_items || n <= 0 || !dest) return hm_fail(HM_ERR_INVALID_ARG, "null argument");
+  std::vector<hm_region> desc;
+  std::vector<const void*> data;
+  std::vector<std::vector<uint8_t>> joined; // payloads of mask items that lie in several extents
+  uint32_t rw = 0, rh = 0;
+  hm::HeifError err;
+  for (int k = 0; k < n; k++) {
+    const hm::RegionItem* r = f->file.region_item(region_items[k], err);
+    if (!r) return fail_from(err);
+    if (k && (r->reference_width != rw || r->reference_height != rh))
+      return hm_fail(HM_ERR_UNSUPPORTED, "region item %u has the reference size %u x %u, item %u before it %u x %u: one call rasterises one reference space",
+                     region_items[k], r->reference_width, r->reference_height, region_items[0], rw, rh);
+    rw = r->reference_width; rh = r->reference_height;
+    for (const hm::Region& g : r->regions) {
+      hm_region d;
+      region_describe(g, &d);
+      const void* p = nullptr;
+      if (g.type == HM_REGION_POLYGON || g.type == HM_REGION_POLYLINE) p = g.points.data();
+      else if (g.type == HM_REGION_INLINE_MASK) p = g.bits.data();
+      else if (g.type == HM_REGION_REFERENCED_MASK) { // the mask item's payload is its samples: no decode
+        hm_unci_info u;
+        if (!f->file.unci_info(g.mask_item, u, err)) return fail_from(err); // (a depth other than 8)
+        const uint8_t* bytes = nullptr;
+        size_t len = 0;
+        hm::HeifError e2;
+        if (!f->file.item_span(g.mask_item, &bytes, &len, e2)) {
+          joined.emplace_back();
+          if (!f->file.item_data(g.mask_item, joined.back(), err)) return fail_from(err);
+          bytes = joined.back().data(); len = joined.back().size();
+        }
+        if ((uint64_t)len < d.mask_bytes) return hm_fail(HM_ERR_BITSTREAM, "mask item %u has %zu bytes of data, %u x %u samples need %llu", g.mask_item, len, g.w, g.h, (unsigned long long)d.mask_bytes);
+        p = bytes;
+      }
+      desc.push_back(d);
+      data.push_back(p);
+    }
+  }
+  if (out) std::memset(out, 0, sizeof(*out));
+  hm_device_view whole;
+  std::memset(&whole, 0, sizeof(whole));
+  const hm_device_view* v = view ? view : &whole;
+  const bool crop_all = v->crop_w == 0 && v->crop_h == 0;
+  const int ow = v->out_w || v->out_h ? v->out_w : crop_all ? (int)rw : v->crop_w, oh = v->out_w || v->out_h ? v->out_h : crop_all ? (int)rh : v->crop_h;
+  int rc = hm_rasterise_regions(desc.data(), data.data(), (int)desc.size(), (int)rw, (int)rh, view, mode, dest, nullptr);
+  if (rc) return rc;
+  if ((rc = hm_check_hip(hipStreamSynchronize(nullptr), "regions: wait for the rasteriser"))) return rc;
+  if (out) {
+    out->width = ow; out->height = oh; out->n_regions = (int32_t)desc.size(); out->planes = mode == HM_REGIONS_LABELS ? 1 : (int32_t)desc.size();
+    out->bytes = hm_regions_dest_bytes(mode, (int)desc.size(), ow, oh, dest);
+    out->reference_width = rw; out->reference_height = rh;
+  }
+  return HM_OK;
 }
 
 static void gain_params_of(const hm::GainMapInfo& g, hm_gain_params* p)
@@ -2224,7 +2356,7 @@ static int decode_item(const hm_file* f, uint32_t id, const hm_decode_params* pa
   std::memset(out, 0, sizeof(*out)); // (whatever fails below: nothing of an earlier call is left in it)
   if (is_derived_item(f, id)) return decode_derived(f, id, params, target, out);
   const hm::Item* item = f->file.item(id);
-  const bool unci = item && item->type == "unci"; // (a leaf without coded pictures: nothing to cut into slabs)
+  const bool unci = item && item->is_raw_leaf(); // (a leaf without coded pictures: nothing to cut into slabs)
   if (!unci && !target.view && !target.light && !target.alpha) { // (r06) a grid of more tiles than parsing threads, to interleaved pixels: slab by slab under the entropy decode (decode_grid_cut)
     bool applicable = false;
     const int prc = decode_grid_cut(f, id, params, nullptr, 1, /*pipelined=*/true, out, &applicable, target.dest);

@@ -888,3 +888,128 @@ def decode_batch_to_planes(files, item_id=0, chroma=None, layout="planar", dtype
         finally:
             L.hm_pipeline_destroy(pipe)
     return out
+
+
+# ---- regions and masks: what a file says about its pixels ('rgan' region items, 'mski' mask items) ----
+
+REGION_MODES = {"stack": capi.HM_REGIONS_STACK, "labels": capi.HM_REGIONS_LABELS}
+
+
+def _region_item_ids(f, iid, region_items):
+    L = f.L
+    if region_items is not None:
+        return [int(r) for r in region_items]
+    n = capi.check_image(L.hm_file_region_items(f.h, iid, None, 0))
+    ids = (C.c_uint32 * max(n, 1))()
+    capi.check_image(L.hm_file_region_items(f.h, iid, ids, n))
+    return [ids[i] for i in range(n)]
+
+
+def _read_region_item(f, rid):
+    import numpy as np
+    L = f.L
+    info = capi.RegionItemInfo()
+    capi.check_image(L.hm_file_region_item_info(f.h, rid, C.byref(info)))
+    regions = []
+    for k in range(info.n_regions):
+        g = capi.Region()
+        capi.check_image(L.hm_file_region(f.h, rid, k, C.byref(g)))
+        pts = np.zeros((g.n_points, 2), dtype=np.int32)
+        if g.n_points:
+            capi.check_image(L.hm_file_region_points(f.h, rid, k, pts.ctypes.data_as(C.POINTER(C.c_int32)), g.n_points))
+        r = dict(type=capi.REGION_TYPE_NAMES[g.type], x=g.x, y=g.y, w=g.w, h=g.h, points=pts, mask_item=g.mask_item)
+        if g.type == capi.HM_REGION_INLINE_MASK:
+            p, n = C.POINTER(C.c_uint8)(), C.c_size_t()
+            capi.check_image(L.hm_file_region_inline_mask(f.h, rid, k, C.byref(p), C.byref(n)))
+            r["bits"] = C.string_at(p, n.value)
+        regions.append(r)
+    return dict(item_id=rid, reference_size=(info.reference_width, info.reference_height), regions=regions)
+
+
+def read_regions(data, item_id=0):
+    """The region items ('rgan') that annotate image item_id (0 = the primary item) of a HEIF file, in item-id order: a list of
+    dict(item_id=, reference_size=(w, h), regions=[...]), each region a dict(type= "point" / "rectangle" / "ellipse" / "polygon" /
+    "referenced_mask" / "inline_mask" / "polyline", x=, y=, w=, h= (an ellipse: centre and radii), points= an N x 2 int32 array,
+    mask_item= the mask item of a referenced mask (else 0), and for an inline mask bits= its bit string).  Host only: no GPU is needed.
+    A damaged region item raises capi.HmError."""
+    f = _File(data)
+    try:
+        iid = item_id or f.L.hm_file_primary_item(f.h)
+        return [_read_region_item(f, rid) for rid in _region_item_ids(f, iid, None)]
+    finally:
+        f.close()
+
+
+def _regions_view(reference_size, image_size, crop, size, filter):
+    """(hm_device_view or None, width, height written) of a region raster: crop is in the reference space; with neither crop nor size
+    and a reference size that differs from the image's, size defaults to the image's - the planes then line up with decode_to_tensor"""
+    rw, rh = reference_size
+    if tuple(reference_size) != tuple(image_size):
+        if crop is not None and size is None:
+            raise ValueError(f"crop without size: the regions' reference space is {rw} x {rh}, the image {image_size[0]} x {image_size[1]} - a crop is in "
+                             "the reference space, so say which size it is to be written at (size=(w, h))")
+        if crop is None and size is None:
+            size = tuple(image_size)
+    return _view_of(crop, size, filter, rw, rh)
+
+
+def decode_regions_to_tensor(data, item_id=0, region_items=None, mode="stack", crop=None, size=None, filter="triangle", dtype=None, scale=None,
+                             bias=None, out=None, stream=None):
+    """Rasterise the regions that annotate image item_id (0 = the primary item) into a CUDA tensor: R x H x W for mode "stack" (one
+    plane per region, 0 / 255, a referenced mask its samples) or H x W uint8 for "labels" (1 + the index of the last region whose value
+    is >= 128, else 0).  region_items: ids of the region items to take (None: all of the image's, in item-id order; they must share one
+    reference size).  crop: (x, y, w, h) in the regions' reference space; size: (w, h) written - "stack" planes are resampled with
+    `filter` like the planes of decode_to_planes, "labels" takes filter="nearest" only.  With neither, and a reference size that differs
+    from the image's, size defaults to the image's size, so that the planes line up pixel for pixel with decode_to_tensor; with a crop
+    in that case size must be given (ValueError).  dtype: torch.uint8 (the default), torch.float16 / torch.float32 ("stack": value *
+    scale + bias).  out: a CUDA tensor of that shape; its row and plane strides are honoured.  stream: work queued on it is waited for
+    first; the call returns when the planes are in place."""
+    import torch
+    L = capi.image_lib()
+    if str(mode).lower() not in REGION_MODES:
+        raise ValueError(f"mode {mode!r}: 'stack' or 'labels'")
+    m = REGION_MODES[str(mode).lower()]
+    if dtype is None:
+        dtype = out.dtype if out is not None else torch.uint8
+    code = _dtype_code(dtype)
+    f = _File(data)
+    try:
+        iid, iw, ih = f.size(item_id)
+        ids = _region_item_ids(f, iid, region_items)
+        if not ids:
+            raise ValueError(f"item {iid} has no region items")
+        n = 0
+        ref = None
+        for rid in ids:
+            info = capi.RegionItemInfo()
+            capi.check_image(L.hm_file_region_item_info(f.h, rid, C.byref(info)))
+            n += info.n_regions
+            ref = ref or (info.reference_width, info.reference_height)
+        view, w, h = _regions_view(ref, (iw, ih), crop, size, filter)
+        shape = (n, h, w) if m == capi.HM_REGIONS_STACK else (h, w)
+        if out is None:
+            out = torch.empty(shape, dtype=dtype, device="cuda")
+        elif not out.is_cuda or out.dtype != dtype:
+            raise ValueError(f"out: a CUDA tensor of dtype {dtype} is needed, got {out.dtype} on {out.device}")
+        elif tuple(out.shape) != shape:
+            raise ValueError(f"out: shape {tuple(out.shape)} does not match the regions' {shape}")
+        if out.numel() and out.stride(-1) != 1 and out.shape[-1] != 1:
+            raise ValueError("out: the pixels of a row must be contiguous (only the row and plane strides are free)")
+        es = out.element_size()
+        d = capi.RegionsDest()
+        d.ptr = out.data_ptr()
+        d.len = out.untyped_storage().nbytes() - out.storage_offset() * es
+        d.dtype = code
+        d.row_pitch = out.stride(-2) * es
+        d.plane_pitch = out.stride(0) * es if m == capi.HM_REGIONS_STACK and n > 1 else 0
+        d.scale, d.bias = 1.0 if scale is None else float(scale), 0.0 if bias is None else float(bias)
+        arr = (C.c_uint32 * len(ids))(*ids)
+        res = capi.RegionsOut()
+        with torch.cuda.device(out.device):
+            (stream if hasattr(stream, "synchronize") else torch.cuda.current_stream(out.device)).synchronize()
+            capi.check_image(L.hm_regions_to_device(f.h, arr, len(ids), C.byref(view) if view is not None else None, m, C.byref(d), C.byref(res)))
+        if (res.width, res.height) != (w, h):
+            raise capi.HmError(-6, f"the planes written are {res.width} x {res.height}, {w} x {h} were expected")
+        return out
+    finally:
+        f.close()

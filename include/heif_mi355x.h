@@ -371,7 +371,8 @@ HM_API int      hm_file_image_info(const hm_file* f, uint32_t id, hm_image_info*
 /* what kind of item `id` is: HM_ITEM_*, or a negative status (no such item) */
 enum { HM_ITEM_OTHER = 0, HM_ITEM_HVC1 = 1, HM_ITEM_GRID = 2, HM_ITEM_IDEN = 3, HM_ITEM_IOVL = 4,
        HM_ITEM_TMAP = 5 /* a tone-map derived item (ISO 21496-1 gain map): "Gain" below */,
-       HM_ITEM_UNCI = 6 /* an uncompressed image (ISO/IEC 23001-17): "Uncompressed items" below */ };
+       HM_ITEM_UNCI = 6 /* an uncompressed image (ISO/IEC 23001-17): "Uncompressed items" below */,
+       HM_ITEM_MSKI = 7 /* a mask item ('mski') that carries its 'mskC' property: "Regions and masks" below; one without stays HM_ITEM_OTHER */ };
 HM_API int      hm_file_item_kind(const hm_file* f, uint32_t id);
 /* A 'tmap' item: an SDR base image, a gain-map image and the parameters that take the base to its alternate (HDR) rendition.  It
  * has exactly two 'dimg' references, [0] the base image and [1] the gain-map image (anything else: HM_ERR_BITSTREAM).  These
@@ -1257,6 +1258,118 @@ HM_API int hm_unci_payload_bytes(const hm_unci_info* info, uint64_t* bytes);
  * n_bytes below what the layout needs: HM_ERR_BITSTREAM, before the launch; nothing behind d_bytes + n_bytes is ever read. */
 HM_API int hm_unci_unpack(const hm_unci_info* info, const void* d_bytes, size_t n_bytes, const int32_t tiles[4], const hm_planes* out,
                           int out_format, const hm_device_dest* interleaved, void* stream);
+
+/* ------------------------------------------------------------------------- */
+/* Regions and masks: 'rgan' region items and 'mski' mask items (ISO/IEC 23008-12 6.10) */
+/* ------------------------------------------------------------------------- */
+
+/* What a file says ABOUT its pixels.  A region item ('rgan') annotates the images its 'cdsc' reference names with up to 255 regions
+ * on a canvas of reference_width x reference_height; a mask item ('mski' with an 'mskC' property: HM_ITEM_MSKI) is a monochrome image.
+ * File layer (libheif/region.cc, codecs/mask_image.cc, context.cc:1166-1237): the payload of an 'rgan' item is a version byte (not
+ * looked at), a flags byte (bit 0: 32-bit fields, else 16-bit), reference width and height, a one-byte region count and per region a
+ * type byte and its fields - x, y and point coordinates signed, sizes, radii and point counts unsigned.  The k-th referenced-mask
+ * region of an item takes the k-th entry of the item's 'mask' reference; its width or height 0 means the mask item's 'ispe'.
+ * A damaged region item does not fail hm_file_open: the calls below that read that item fail.
+ *   HM_ERR_BITSTREAM    truncated data (an inline mask holds (w * h + 7) / 8 bytes), fewer 'mask' references than referenced-mask regions
+ *   HM_ERR_UNSUPPORTED  a geometry type above 6 (named), an inline mask with mask_coding_method != 0 (deflate), a 'mask' reference to
+ *                       an item that is not HM_ITEM_MSKI, a referenced-mask region whose stated size differs from the mask item's
+ *                       'ispe' (no mask is scaled), a mask item that is not 8 bits deep, and the magnitude limits, named in the message:
+ *                       every coordinate v  -2^28 <= v < 2^28, every size and reference dimension < 2^28, an ellipse radius <= 32767
+ *                       (with them the membership tests below are exact in 64-bit integers).
+ * An HM_ITEM_MSKI item is listed by hm_file_top_level_images unless it is hidden or the target of a 'mask' reference.  Through
+ * hm_decode_item and its device forms an 8-bit mask item is a monochrome 8-bit image whose samples are the payload's bytes, row after
+ * row, tight - a leaf without coded pictures that takes the path of a monochrome 8-bit 'unci' item in component interleave and is
+ * refused where such an item is (the pipeline, batch and sequence calls; as a grid tile, a derived item's child, an auxiliary image,
+ * a gain map).  A payload below width * height bytes: HM_ERR_BITSTREAM before anything is queued.  bits_per_pixel other than 8:
+ * HM_ERR_UNSUPPORTED.
+ *
+ * THE MEMBERSHIP RULES.  The canvas is reference_width x reference_height; pixel (px, py) is the lattice point (px, py).  The reference
+ * space is that of the annotated image AFTER its transformative properties: no irot / imir / clap is applied to a region.  A region's
+ * value at a pixel is 0 or 255; for a referenced mask it is the mask's sample, 0 .. 255.  All arithmetic is int64.
+ *   Point           the pixel (x, y).
+ *   Rectangle       x <= px < x + w  and  y <= py < y + h.
+ *   Ellipse         centre (x, y), radii rx = w, ry = h:  |px - x| <= rx  and  |py - y| <= ry  and
+ *                   (px - x)^2 * ry^2 + (py - y)^2 * rx^2 <= rx^2 * ry^2.  A zero radius gives a line or the centre pixel.
+ *   Segment A -> B  dx = bx - ax, dy = by - ay, m = max(|dx|, |dy|): P is on it iff P is inside the segment's closed bounding box and
+ *                   2 * |dx * (py - ay) - dy * (px - ax)| <= m.  m = 0: P = A.
+ *   Polyline        the union of its n - 1 segments; n = 1: the point; n = 0: empty.
+ *   Polygon         the union of (a) the closed polyline - n segments, the last vertex joined to the first - and (b) the even-odd
+ *                   interior: an edge counts for P iff (ay <= py) != (by <= py) and, with its ends ordered so that ay < by,
+ *                   (px - ax) * (by - ay) < (bx - ax) * (py - ay); P is interior iff the count is odd.
+ *   Inline mask     at (x, y), size w x h: bit i = (py - y) * w + (px - x) of the data, most significant bit first, rows not byte
+ *                   aligned; a set bit gives 255 (heif_regions.cc:677-690).
+ *   Referenced mask at (x, y): the mask item's sample at (px - x, py - y).
+ * Everything is clipped to the canvas; geometry off the canvas is legal.
+ * Two outputs over the view's rectangle of the canvas:
+ *   HM_REGIONS_STACK   one plane per region, in the order given.  HM_DEV_U8 stores the value, HM_DEV_F32 / _F16
+ *                      __fadd_rn(__fmul_rn((float)v, scale), bias), HM_DEV_F16 through __float2half_rn - the tensor step's rule.
+ *   HM_REGIONS_LABELS  ONE uint8 plane: 1 + the index of the LAST region whose value there is >= 128, or 0.  At most 255 regions
+ *                      (more: HM_ERR_INVALID_ARG); HM_DEV_U8 only.
+ * The view (hm_device_view): the crop is a rectangle of the canvas - pixels outside it are never generated -; an output size that
+ * differs from the crop's resamples STACK planes as monochrome 8-bit planes under the rules of "Planar views" above (integer
+ * destinations round and clamp, float ones take r * scale + bias); LABELS takes HM_VIEW_NEAREST's index rule only - averaged labels
+ * mean nothing: any other filter with a size other than the crop's is HM_ERR_INVALID_ARG.
+ * Only width x height elements of each plane are written.  Every refusal - a destination that is not device memory, too short, of a
+ * pitch below the tight value or not a multiple of the element size, an unknown dtype or mode, a bad view, a region beyond the
+ * magnitude limits, a NULL data pointer, an inline mask of fewer than (w * h + 7) / 8 bytes, a mask of fewer than w * h - happens
+ * before anything is queued, with the destination unwritten. */
+enum { HM_REGION_POINT = 0, HM_REGION_RECTANGLE = 1, HM_REGION_ELLIPSE = 2, HM_REGION_POLYGON = 3, HM_REGION_REFERENCED_MASK = 4,
+       HM_REGION_INLINE_MASK = 5, HM_REGION_POLYLINE = 6 };
+enum { HM_REGIONS_STACK = 0, HM_REGIONS_LABELS = 1 };
+enum { HM_REGION_COORD_LIMIT = 1 << 28, HM_REGION_MAX_RADIUS = 32767 };
+typedef struct hm_region_item_info {
+  uint32_t reference_width, reference_height;
+  int32_t  n_regions;
+  int32_t  field_bits;       /* 16 / 32: the field size the payload uses */
+} hm_region_item_info;
+typedef struct hm_region {
+  int32_t  type;             /* HM_REGION_* */
+  int32_t  x, y;             /* point; top-left corner (rectangle, masks); centre (ellipse); 0 for polygon / polyline */
+  uint32_t w, h;             /* size (rectangle, masks: resolved against the mask item's 'ispe'); radii (ellipse) */
+  uint32_t n_points;         /* polygon / polyline */
+  uint32_t mask_item;        /* referenced mask: the HM_ITEM_MSKI item, else 0 */
+  uint64_t mask_bytes;       /* inline mask: (w * h + 7) / 8; referenced mask: w * h; else 0 */
+} hm_region;
+/* the region items whose 'cdsc' reference names `image_id`, in item-ID order: returns their count, ids[0 .. min(count, max_ids)) filled */
+HM_API int hm_file_region_items(const hm_file* f, uint32_t image_id, uint32_t* ids, int max_ids);
+HM_API int hm_file_region_item_info(const hm_file* f, uint32_t region_item, hm_region_item_info* info);
+HM_API int hm_file_region(const hm_file* f, uint32_t region_item, int index, hm_region* out);
+/* xy[2 i], xy[2 i + 1] of point i < min(n_points, max_points); returns n_points or a negative status */
+HM_API int hm_file_region_points(const hm_file* f, uint32_t region_item, int index, int32_t* xy, int max_points);
+/* the bit string of an inline mask (points into the file object, valid until hm_file_close) */
+HM_API int hm_file_region_inline_mask(const hm_file* f, uint32_t region_item, int index, const uint8_t** bits, size_t* len);
+
+typedef struct hm_regions_dest {
+  void*    ptr;          /* device memory of the current device                                         */
+  uint64_t len;          /* bytes available at ptr                                                      */
+  int32_t  dtype;        /* HM_DEV_U8 / _F16 / _F32 (STACK); HM_DEV_U8 (LABELS)                         */
+  int32_t  reserved;     /* 0 */
+  int64_t  row_pitch;    /* bytes between rows; 0 = tight                                               */
+  int64_t  plane_pitch;  /* STACK: bytes between region planes; 0 = row_pitch * height                  */
+  float    scale, bias;  /* float dtypes: out = value * scale + bias                                     */
+} hm_regions_dest;
+/* bytes the destination must hold for n_regions planes (LABELS: one) of width x height: plane_pitch * (planes - 1) + row_pitch *
+ * (height - 1) + width * elem, or the negative status of a combination that is refused.  Host arithmetic; ptr and len are not looked at. */
+HM_API int64_t hm_regions_dest_bytes(int mode, int n_regions, int width, int height, const hm_regions_dest* d);
+/* The rasteriser on its own (the sibling of hm_unci_unpack): n host-side descriptors - for region i, data[i] = its int32 x, y point
+ * pairs (polygon / polyline), its bit string (inline mask, mask_bytes long) or its samples (referenced mask: w * h bytes, rows tight;
+ * mask_item is not looked at), else ignored - on a canvas_w x canvas_h canvas under `view` (NULL: the whole canvas) into `dest`, sized
+ * for the view's output.  Everything travels in one upload; ONE launch rasterises every region.  The host data is copied before the
+ * call returns.  Asynchronous on `stream`. */
+HM_API int hm_rasterise_regions(const hm_region* regions, const void* const* data, int n, int canvas_w, int canvas_h, const hm_device_view* view,
+                                int mode, const hm_regions_dest* dest, void* stream);
+typedef struct hm_regions_out {
+  int32_t width, height;     /* of each plane written */
+  int32_t n_regions;
+  int32_t planes;            /* n_regions (STACK) or 1 (LABELS) */
+  int64_t bytes;             /* hm_regions_dest_bytes of what was written */
+  uint32_t reference_width, reference_height;
+} hm_regions_out;
+/* The regions of the region items region_items[0 .. n), item after item, gathered from the file - the items must share one reference
+ * size, else HM_ERR_UNSUPPORTED; referenced masks are the 'mski' payloads' own bytes - and rasterised as by hm_rasterise_regions on the
+ * default stream; returns when the planes are in place. */
+HM_API int hm_regions_to_device(const hm_file* f, const uint32_t* region_items, int n, const hm_device_view* view, int mode,
+                                const hm_regions_dest* dest, hm_regions_out* out);
 
 #ifdef __cplusplus
 }
