@@ -232,6 +232,14 @@ class DeviceOotf(C.Structure):
 
 HM_OOTF_HLG = 1
 HM_OOTF_STEPS = 1024
+HM_LIGHT_STATS_BINS = 2048
+
+
+class LightStatsC(C.Structure):
+    """hm_light_stats: the light statistics of a rectangle of pixels - the histogram over the tone step's 11-bit PQ codes of the pixels'
+    norms, the largest norm, and what the host reads off them"""
+    _fields_ = [("pixels", C.c_uint64), ("hist", C.c_uint32 * HM_LIGHT_STATS_BINS), ("max_norm", C.c_float), ("max_code", C.c_int32),
+                ("max_nits", C.c_float), ("average_nits", C.c_float), ("reserved", C.c_int32 * 2)]
 
 
 class LightLevels(C.Structure):
@@ -439,6 +447,15 @@ def bind_image(L):
     L.hm_ootf_gamma.argtypes = [C.POINTER(DeviceOotf), C.POINTER(C.c_double)]
     L.hm_ootf_table.argtypes = [C.POINTER(DeviceOotf), C.c_float, C.c_int, C.POINTER(C.c_float)]
     L.hm_ootf_luma.argtypes = [C.c_int, C.POINTER(C.c_float * 3)]
+    L.hm_light_stats_code_nits.argtypes = [C.c_int, C.c_int, C.POINTER(C.c_double)]
+    L.hm_light_stats_percentile.argtypes = [C.POINTER(LightStatsC), C.c_double, C.POINTER(C.c_int32), C.POINTER(C.c_float)]
+    L.hm_light_stats_average.argtypes = [C.POINTER(LightStatsC), C.POINTER(C.c_float)]
+    L.hm_light_stats_of_tensor.argtypes = [C.c_int, C.c_int, C.c_int, C.c_int, C.c_void_p, C.c_int, C.POINTER(DeviceView), C.POINTER(DeviceLight), C.POINTER(DeviceOotf),
+                                           C.c_float, C.POINTER(LightStatsC), C.c_void_p]
+    L.hm_decode_item_light_stats.argtypes = [C.c_void_p, C.c_uint32, C.POINTER(DecodeParams), C.POINTER(DeviceView), C.POINTER(DeviceLight), C.POINTER(DeviceOotf),
+                                             C.c_float, C.POINTER(LightStatsC), C.POINTER(Decoded)]
+    L.hm_decode_item_to_device_measured.argtypes = [C.c_void_p, C.c_uint32, C.POINTER(DecodeParams), C.POINTER(DeviceView), C.POINTER(DeviceLight), C.POINTER(DeviceOotf),
+                                                    C.POINTER(DeviceTone), C.c_double, C.POINTER(DeviceDest), C.POINTER(Decoded), C.POINTER(LightStatsC)]
     L.hm_device_planes_bytes.argtypes = [C.c_int, C.c_int, C.c_int, C.c_int, C.POINTER(DevicePlanes), C.POINTER(C.c_int64 * 4)]
     L.hm_device_planes_bytes.restype = C.c_int64
     L.hm_planes_to_tensor.argtypes = [C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, C.POINTER(C.c_void_p * 4), C.POINTER(C.c_int32 * 4), C.POINTER(DevicePlanes),

@@ -852,20 +852,31 @@ float hm_tone_peak_of(int has_clli, unsigned max_cll, int has_mdcv, unsigned mdc
   return 1000.0f;
 }
 
+// what light value 1.0 (before gain) stands for under the plan lp, cd/m2: as given, or what 0 stands for - behind an OOTF step (resolved
+// into lp already) light value g stands for display_peak; PQ says 10000 - or the refusal; who: the step that asks, for the message
+static int unit_nits_of(const char* who, const hm_light_plan* lp, float given, float* U)
+{
+  const float unit_nits = given != 0.0f ? given : lp->ootf ? lp->ootf_peak : 0.0f;
+  if (unit_nits == 0.0f && lp->icc) return hm_fail(HM_ERR_INVALID_ARG, "%s: unit_nits must be given for an ICC profile as the source (no profile says what 1.0 stands for)", who);
+  if (unit_nits == 0.0f && lp->from_transfer != 16)
+    return hm_fail(HM_ERR_INVALID_ARG, "%s: unit_nits must be given for transfer characteristics %d (only PQ says what 1.0 stands for)", who, lp->from_transfer);
+  *U = unit_nits != 0.0f ? unit_nits : 10000.0f;
+  return HM_OK;
+}
+
 // the tone step into the plan of its light step (light_plan_of); the static checks have passed
 static int tone_plan_of(const hm_device_tone* tone, hm_light_plan* lp)
 {
-  // behind an OOTF step (resolved into lp already) light value g stands for display_peak, and nothing brighter comes out of it
-  const float unit_nits = tone->unit_nits != 0.0f ? tone->unit_nits : lp->ootf ? lp->ootf_peak : 0.0f;
+  // behind an OOTF step nothing brighter than display_peak comes out of it
   const float src_peak = tone->src_peak != 0.0f ? tone->src_peak : lp->ootf ? lp->ootf_peak : 0.0f;
-  if (unit_nits == 0.0f && lp->icc) return hm_fail(HM_ERR_INVALID_ARG, "tone: unit_nits must be given for an ICC profile as the source (no profile says what 1.0 stands for)");
-  if (unit_nits == 0.0f && lp->from_transfer != 16)
-    return hm_fail(HM_ERR_INVALID_ARG, "tone: unit_nits must be given for transfer characteristics %d (only PQ says what 1.0 stands for)", lp->from_transfer);
+  float unit_nits;
+  const int rc = unit_nits_of("tone", lp, tone->unit_nits, &unit_nits);
+  if (rc) return rc;
   if (src_peak == 0.0f) return hm_fail(HM_ERR_INVALID_ARG, "tone: src_peak must be given: the pixels carry no light levels"); // (else the knee has been judged)
   lp->tone = 1;
   if (tone->out_bits == 8) lp->enc_bits = 8;
   lp->src_peak = src_peak; lp->dst_peak = tone->dst_peak;
-  lp->unit_nits = unit_nits != 0.0f ? unit_nits : 10000.0f;
+  lp->unit_nits = unit_nits;
   lp->out_unit_nits = tone->out_unit_nits != 0.0f ? tone->out_unit_nits : tone->dst_peak;
   return HM_OK;
 }
@@ -1207,6 +1218,8 @@ static int out_resolve_profile(int out_format, const hm_out_image* img, const hm
     const hm_light_plan& lp = p->lp;
     const bool summed = !p->vp.crop_only && p->vp.filter != HM_VIEW_NEAREST;
     const int steps = (lp.tone ? 1 : 0) | (lp.ootf ? 2 : 0);
+    if (st->measure && (rc = hm_light_lds_check(lp.bits, lp.enc_bits, lp.encode, steps, lp.lin3, 3))) return rc; // the statistics pass
+    if (st->measure == HM_MEASURE_STATS) return HM_OK; // (nothing is written: no other launch)
     if ((rc = hm_light_lds_check(lp.bits, lp.enc_bits, lp.encode, steps, lp.lin3, summed ? 1 : 0)) || (summed && (rc = hm_light_lds_check(lp.bits, lp.enc_bits, lp.encode, steps, lp.lin3, 2)))) return rc;
   }
   return st->gain ? gain_plan_of(st->gain, img, &p->vp, &p->lp, &p->gp) : (int)HM_OK;
@@ -1445,6 +1458,155 @@ int hm_ootf_to_tensor(int out_format, int bits, int src_w, int src_h, const void
                       const hm_device_ootf* ootf, const hm_device_tone* tone, const hm_device_alpha* alpha, const hm_device_dest* dest, void* stream)
 {
   return out_to_tensor(HM_ENTRY_OOTF, out_format, bits, src_w, src_h, d_src, src_stride, {view, light, tone, alpha, nullptr, ootf}, dest, stream);
+}
+
+// ---- the light statistics (hm_light_stats) ---------------------------------------------------------------------------------------
+
+namespace {
+
+// code_nits of include/heif_mi355x.h
+double stats_code_nits(int k, int edge)
+{
+  const double top = (double)(HM_LIGHT_STATS_BINS - 1), x = edge ? std::min((double)k + 0.5, top) : (double)k;
+  return 10000.0 * light_of_code(16, x / top);
+}
+
+// the pool blocks of one measurement: released when the stream has been waited for, or nothing was queued on them
+struct StatsBlocks {
+  void* pinned = nullptr; void* dev = nullptr;
+  ~StatsBlocks() { if (pinned) hm_pool_pinned_free(pinned); if (dev) hm_pool_device_free(dev); }
+};
+
+} // namespace
+
+int hm_light_stats_code_nits(int k, int edge, double* nits)
+{
+  if (!nits) return hm_fail(HM_ERR_INVALID_ARG, "null argument");
+  if (k < 0 || k >= HM_LIGHT_STATS_BINS) return hm_fail(HM_ERR_INVALID_ARG, "light statistics: code %d is not in 0 .. %d", k, HM_LIGHT_STATS_BINS - 1);
+  if (edge != 0 && edge != 1) return hm_fail(HM_ERR_INVALID_ARG, "light statistics: edge %d is not 0 (the code's light) or 1 (the upper edge of its bin)", edge);
+  *nits = stats_code_nits(k, edge);
+  return HM_OK;
+}
+
+int hm_stats_check_fraction(double fraction)
+{
+  if (!std::isfinite(fraction) || !(fraction > 0.0) || fraction > 1.0) return hm_fail(HM_ERR_INVALID_ARG, "light statistics: fraction %g is not finite and in (0, 1]", fraction);
+  return HM_OK;
+}
+
+int hm_stats_check_unit(float unit_nits)
+{
+  if (unit_nits != 0.0f && !nits_ok(unit_nits)) return hm_fail(HM_ERR_INVALID_ARG, "light statistics: unit_nits %g is not finite, above 0 and at most 10000", (double)unit_nits);
+  return HM_OK;
+}
+
+int hm_stats_unit_nits(const hm_light_plan* lp, float unit_nits, float* U) { return unit_nits_of("light statistics", lp, unit_nits, U); }
+
+int hm_light_stats_percentile(const hm_light_stats* stats, double fraction, int32_t* code, float* nits)
+{
+  if (!stats) return hm_fail(HM_ERR_INVALID_ARG, "null argument");
+  const int rc = hm_stats_check_fraction(fraction);
+  if (rc) return rc;
+  if (stats->pixels == 0) return hm_fail(HM_ERR_INVALID_ARG, "light statistics: a statistic of no pixels has no percentile");
+  const uint64_t rank = std::min(std::max((uint64_t)std::ceil(fraction * (double)stats->pixels), (uint64_t)1), stats->pixels);
+  uint64_t below = 0;
+  int k = 0;
+  for (; k < HM_LIGHT_STATS_BINS - 1; k++)
+    if ((below += stats->hist[k]) >= rank) break; // (a histogram that sums to less than pixels: the last bin)
+  if (code) *code = k;
+  if (nits) *nits = (float)stats_code_nits(k, 1);
+  return HM_OK;
+}
+
+int hm_light_stats_average(const hm_light_stats* stats, float* nits)
+{
+  if (!stats || !nits) return hm_fail(HM_ERR_INVALID_ARG, "null argument");
+  if (stats->pixels == 0) return hm_fail(HM_ERR_INVALID_ARG, "light statistics: a statistic of no pixels has no average");
+  double sum = 0.0;
+  for (int k = 0; k < HM_LIGHT_STATS_BINS; k++) sum += (double)stats->hist[k] * stats_code_nits(k, 0);
+  *nits = (float)(sum / (double)stats->pixels);
+  return HM_OK;
+}
+
+hm_device_dest hm_stats_stand_in_dest(void)
+{
+  hm_device_dest d;
+  std::memset(&d, 0, sizeof(d));
+  d.ptr = reinterpret_cast<void*>((uintptr_t)256); d.len = ~(uint64_t)0 >> 1; // (never written, never asked whether it is device memory)
+  d.layout = HM_DEV_LAYOUT_HWC; d.dtype = HM_DEV_F32;
+  for (int c = 0; c < 4; c++) d.scale[c] = 1.0f;
+  return d;
+}
+
+int hm_launch_light_stats(const hm_out_plan* p, float U, const void* src, int src_stride, hipStream_t s, hm_light_stats* out)
+{
+  if (!p->has_light || !out) return hm_fail(HM_ERR_INTERNAL, "light statistics: no light step in the plan");
+  const hm_view_plan* vp = &p->vp;
+  const int obpp = hm_out_bytes_per_pixel(p->out_format), src_bytes = obpp >= 6 ? 2 : 1, channels = obpp / src_bytes;
+  const uint8_t* origin = (const uint8_t*)src + (size_t)vp->y * src_stride + (size_t)vp->x * obpp;
+  // lin and the OOTF tables as the write has them (of the tone step only thr, and for U: the one filled here behind them)
+  hm_light_plan lp = p->lp;
+  lp.encode = 0; lp.tone = 0;
+  const LightTables T(&lp);
+  const size_t table_floats = T.bytes() / sizeof(float), words = HM_LIGHT_STATS_BINS + 2;
+  const size_t bytes = (table_floats + HM_TONE_STEPS + words) * 4;
+  hm_light_args la = T.args(src_bytes);
+  int rc = hm_light_lds_check(lp.bits, lp.enc_bits, 0, lp.ootf ? 2 : 0, lp.lin3, 3);
+  if (rc) return rc;
+  StatsBlocks b;
+  if (!(b.pinned = hm_pool_pinned_alloc(bytes))) return hm_fail(HM_ERR_NOMEM, "out of memory");
+  if (!(b.dev = hm_pool_device_alloc(bytes))) return HM_ERR_NO_DEVICE;
+  float* host = (float*)b.pinned;
+  T.fill(host);
+  fill_tone_tables((double)lp.gain, 0.0, 0.0, (double)U, 0.0, host + table_floats, nullptr);
+  float* dev = (float*)b.dev;
+  unsigned* dev_words = reinterpret_cast<unsigned*>(dev + table_floats + HM_TONE_STEPS);
+  const uint32_t* host_words = reinterpret_cast<const uint32_t*>(host + table_floats + HM_TONE_STEPS);
+  T.point(&la, dev);
+  la.tone = dev + table_floats;
+  // (from here on the blocks are in use by the stream: every way out waits for it)
+  rc = hm_check_hip(hipMemcpyAsync(dev, host, (table_floats + HM_TONE_STEPS) * 4, hipMemcpyHostToDevice, s), "upload of the statistics' tables");
+  if (!rc) rc = hm_check_hip(hipMemsetAsync(dev_words, 0, words * 4, s), "zeroing of the statistics' counters");
+  if (!rc) rc = hm_launch_light_stats_kernel(&la, channels, origin, src_stride, vp->w, vp->h, dev_words, s);
+  if (!rc) rc = hm_check_hip(hipMemcpyAsync(const_cast<uint32_t*>(host_words), dev_words, words * 4, hipMemcpyDeviceToHost, s), "download of the statistics' counters");
+  const hipError_t e = hipStreamSynchronize(s);
+  if (!rc && e != hipSuccess) rc = hm_check_hip(e, "k_light_stats execution");
+  if (rc) return rc;
+  hm_light_stats st;
+  std::memset(&st, 0, sizeof(st));
+  for (int k = 0; k < HM_LIGHT_STATS_BINS; k++) {
+    st.hist[k] = host_words[k];
+    st.pixels += host_words[k];
+    if (host_words[k]) st.max_code = k;
+  }
+  if (st.pixels != (uint64_t)vp->w * (uint64_t)vp->h)
+    return hm_fail(HM_ERR_INTERNAL, "light statistics: %llu pixels counted of %d x %d", (unsigned long long)st.pixels, vp->w, vp->h);
+  std::memcpy(&st.max_norm, &host_words[HM_LIGHT_STATS_BINS], sizeof(float));
+  st.max_nits = (float)((double)st.max_norm * (double)U / (double)lp.gain);
+  if ((rc = hm_light_stats_average(&st, &st.average_nits))) return rc;
+  *out = st;
+  return HM_OK;
+}
+
+int hm_light_stats_of_tensor(int out_format, int bits, int src_w, int src_h, const void* d_src, int src_stride, const hm_device_view* view, const hm_device_light* light,
+                             const hm_device_ootf* ootf, float unit_nits, hm_light_stats* out, void* stream)
+{
+  if (!d_src || !out) return hm_fail(HM_ERR_INVALID_ARG, "null argument");
+  const hm_out_steps st = {view, light, nullptr, nullptr, nullptr, ootf, nullptr, 0, HM_MEASURE_STATS};
+  const hm_device_dest dest = hm_stats_stand_in_dest();
+  int rc = hm_entry_steps(HM_ENTRY_STATS, st);
+  if (!rc) rc = hm_entry_icc(st, "in a stand-alone entry that has no item: hm_decode_item_light_stats reads the item's profile");
+  if (rc || (rc = hm_stats_check_unit(unit_nits)) || (rc = hm_out_check_static(out_format, &dest, &st, 1)) || (rc = check_image_size("", src_w, src_h))) return rc;
+  const hm_out_image img = {src_w, src_h, bits, light->from_transfer, light->from_primaries, 0, 0, 0};
+  hm_out_plan p;
+  float U = 0.0f;
+  if ((rc = hm_out_resolve(out_format, &img, HM_OUT_PROFILE_FIRST, &dest, &st, &p)) || (rc = hm_stats_unit_nits(&p.lp, unit_nits, &U))) return rc;
+  const int obpp = hm_out_bytes_per_pixel(out_format);
+  if (src_stride < src_w * obpp) return hm_fail(HM_ERR_INVALID_ARG, "src_stride %d below the bytes of a row", src_stride);
+  if (obpp >= 6 && (((uintptr_t)d_src | (unsigned)src_stride) & 1)) return hm_fail(HM_ERR_INVALID_ARG, "16-bit samples at an odd address or stride");
+  int n_dev = 0;
+  if (hipGetDeviceCount(&n_dev) != hipSuccess || n_dev == 0) { (void)hipGetLastError(); return hm_fail(HM_ERR_NO_DEVICE, "no HIP device available"); }
+  return hm_launch_light_stats(&p, U, d_src, src_stride, (hipStream_t)stream, out);
 }
 
 // ---- planar views: every plane an image of its own ------------------------------------------------------------------------------

@@ -245,7 +245,11 @@ typedef struct hm_out_steps {
   // the profile a light step with HM_LIGHT_FROM_ICC reads: the item's (resolve_request), hm_icc_to_tensor's; it must live until the
   // write has been queued.  NULL: the request has none - the sentinel is refused
   const uint8_t* icc; size_t icc_size;
+  // the light statistics (HM_MEASURE_*): STATS - the request is measured, not written: its destination is a stand-in that sizes
+  // nothing real, its pointer is not looked at; TONE - the tone step's src_peak is a stand-in until the measurement replaces it
+  int32_t measure;
 } hm_out_steps; // any may be NULL
+enum { HM_MEASURE_NONE = 0, HM_MEASURE_STATS = 1, HM_MEASURE_TONE = 2 };
 // what the image reports (hm_decoded); with a gain step the map beside it (map_w 0: not known yet - the step's geometry is not judged)
 typedef struct hm_out_image { int32_t w, h, bits, transfer, primaries; int32_t map_w, map_h, map_bits; } hm_out_image;
 // the gain map's samples on the device (one channel; one byte per sample at 8 bits, else two), row 0 = the map's row 0
@@ -276,6 +280,22 @@ int hm_out_resolve(int out_format, const hm_out_image* img, int know_profile, co
 // `s`.  Tables and the intermediate hang on sc, which must be a free entry (it is not looked at where nothing is uploaded).
 // map: the gain map of an active gain step (p->gp.active), else NULL.
 int hm_out_write(const hm_device_dest* d, const hm_out_plan* p, const void* src, int src_stride, const hm_out_map* map, hipStream_t s, hm_view_scratch* sc);
+
+// ---- the light statistics (hm_light_stats): the plan's rectangle - the view's crop at source resolution - of the interleaved pixels
+//      through the light step up to the tone step's search, counted.  devdest.cpp holds the tables and the host arithmetic, stats.hip the kernel ----
+// the destination a statistics request is planned against (HM_MEASURE_STATS): float32 HWC of any size
+hm_device_dest hm_stats_stand_in_dest(void);
+// U of a statistic: unit_nits as given, or what 0 stands for under the plan (the tone step's rule: display_peak beside an OOTF step,
+// 10000 for PQ), or the refusal
+int hm_stats_unit_nits(const hm_light_plan* lp, float unit_nits, float* U);
+// unit_nits itself: 0, or finite, above 0 and at most 10000
+int hm_stats_check_unit(float unit_nits);
+// fraction: finite and in (0, 1]
+int hm_stats_check_fraction(double fraction);
+// The statistic of p's rectangle of the image at `src` for U cd/m2 per unit, into *out: 2048 + 2 words of pool device memory zeroed on
+// `s`, one launch, their copy to pool pinned memory - and the stream is waited for: the numbers are in *out when it returns.
+int hm_launch_light_stats(const hm_out_plan* p, float U, const void* src, int src_stride, hipStream_t s, hm_light_stats* out);
+int hm_launch_light_stats_kernel(const hm_light_args* la, int channels, const void* src, int src_stride, int w, int h, unsigned* out, hipStream_t s);
 
 // ---- planar views: a view (hm_device_view) into planar YCbCr (hm_device_planes), every plane an image of its own.  devdest.cpp
 //      holds the checks and the write step, hm_planes_view.h the index arithmetic, planes_view.hip the kernels ----

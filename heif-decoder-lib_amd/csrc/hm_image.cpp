@@ -8,6 +8,7 @@
 //   one D2H copy   : into a host plane laid out like HeifPixelImage (pixelimage.cc:139-218)
 #include <atomic>
 #include <chrono>
+#include <cmath>
 #include <condition_variable>
 #include <functional>
 #include <mutex>
@@ -1028,7 +1029,8 @@ static int target_fits(const hm_decode_params* params, const OutputTarget& t, in
       hm_out_plan plan;
       if ((rc = hm_out_resolve(params->out_format, &img, reported ? HM_OUT_PROFILE_LAST : 0, t.dest, &st, &plan))) return rc;
     }
-    if (pointers && ((rc = require_device()) || (rc = hm_dest_check_pointer(t.dest)))) return rc;
+    const bool stand_in = t.measure && t.measure->mode == HM_MEASURE_STATS; // (a statistic writes nothing: its destination has no memory)
+    if (pointers && ((rc = require_device()) || (!stand_in && (rc = hm_dest_check_pointer(t.dest))))) return rc;
   }
   if (t.planes) {
     hm_planes_plan pp;
@@ -1169,7 +1171,7 @@ static int emit_interleaved(const hm_decode_params* params, hipStream_t s, Plana
   out->plane_width[0] = img_w; out->plane_height[0] = img_h;
   if (t.dest) { // the image, or with a view a rectangle of it at vp.ow x vp.oh, through the steps of the request and nothing else (devdest.cpp): the light and
                 // alpha steps resolved against the profile and depth this image reports - refused before a byte is written
-    const hm_out_steps st = t.steps();
+    hm_out_steps st = t.steps();
     hm_out_image img = {img_w, img_h, r.bit_depth, r.transfer, r.primaries, 0, 0, 0};
     hm_out_map map = {nullptr, 0};
     if (const PlanarImage* G = t.gain_map) { // the gain map as decoded: its Y plane
@@ -1179,14 +1181,29 @@ static int emit_interleaved(const hm_decode_params* params, hipStream_t s, Plana
     }
     hm_out_plan plan;
     if ((rc = hm_out_resolve(params->out_format, &img, HM_OUT_PROFILE_LAST, t.dest, &st, &plan))) return rc;
-    if (t.view_later) { t.view_later->dest = t.dest; t.view_later->vp = plan.vp; t.view_later->src = dout.p; t.view_later->src_stride = cd.out_stride; } // (a sequence: hm_view_write_batch)
+    hm_device_tone measured_tone;
+    const bool stats_only = t.measure && t.measure->mode == HM_MEASURE_STATS;
+    if (LightMeasure* m = t.measure) { // the plan's rectangle is measured here, where the pixels are; the stream is waited for
+      float U = plan.lp.unit_nits;
+      if (stats_only && (rc = hm_stats_unit_nits(&plan.lp, m->unit_nits, &U))) return rc;
+      if ((rc = hm_launch_light_stats(&plan, U, dout.p, cd.out_stride, s, &m->stats))) return rc;
+      if (!stats_only) { // the tone step with the measured peak in place of the stand-in: the plan again - the knee is judged before a byte is written
+        measured_tone = *st.tone;
+        if ((rc = hm_light_stats_percentile(&m->stats, m->fraction, nullptr, &measured_tone.src_peak))) return rc;
+        st.tone = &measured_tone;
+        if ((rc = hm_out_resolve(params->out_format, &img, HM_OUT_PROFILE_LAST, t.dest, &st, &plan))) return rc;
+      }
+      m->done = true;
+    }
+    if (stats_only) {}
+    else if (t.view_later) { t.view_later->dest = t.dest; t.view_later->vp = plan.vp; t.view_later->src = dout.p; t.view_later->src_stride = cd.out_stride; } // (a sequence: hm_view_write_batch)
     else if ((rc = hm_out_write(t.dest, &plan, dout.p, cd.out_stride, t.gain_map ? &map : nullptr, s, t.scratch))) return rc;
     if (t.view) {
       out->width = plan.vp.ow; out->height = plan.vp.oh;
       out->plane_width[0] = plan.vp.ow; out->plane_height[0] = plan.vp.oh;
     }
     out->used_ext_dst = 1;
-    out->stride[0] = (int32_t)std::min<int64_t>(plan.dp.row_pitch, 0x7FFFFFFF);
+    out->stride[0] = stats_only ? 0 : (int32_t)std::min<int64_t>(plan.dp.row_pitch, 0x7FFFFFFF);
   }
   else if (params->ext_dst && params->ext_dst_stride >= (uint32_t)(img_w * obpp) &&
       (size_t)params->ext_dst_len >= (size_t)params->ext_dst_stride * (size_t)img_h) {
@@ -1988,6 +2005,55 @@ int hm_decode_item_to_device_ootf(const hm_file* f, uint32_t id, const hm_decode
                                   const hm_device_ootf* ootf, const hm_device_tone* tone, const hm_device_alpha* alpha, const hm_device_dest* dest, hm_decoded* out)
 {
   return decode_item_to(HM_ENTRY_OOTF, f, id, params, {view, light, tone, alpha, nullptr, ootf}, dest, nullptr, out);
+}
+
+// The entries that measure (include/heif_mi355x.h "Light statistics").  Everything that can be refused without a picture is refused
+// with *out and *stats as they were: resolve_request runs before anything is cleared.  tone: the caller's (the measured entry), else NULL.
+static int decode_item_measuring(int kind, const hm_file* f, uint32_t id, const hm_decode_params* params, const hm_device_view* view, const hm_device_light* light,
+                                 const hm_device_ootf* ootf, const hm_device_tone* tone, const hm_device_dest* dest, LightMeasure& m, hm_light_stats* stats,
+                                 hm_decoded* out)
+{
+  if (!f || !params || !out) return hm_fail(HM_ERR_INVALID_ARG, "null argument");
+  hm_device_tone stand_in;
+  if (tone) {
+    if (tone->src_peak != 0.0f)
+      return hm_fail(HM_ERR_INVALID_ARG, "tone: src_peak %g in the measured entry, which measures the peak (must be 0): hm_decode_item_to_device_tone takes an explicit peak", (double)tone->src_peak);
+    // until the pixels are measured the step carries a peak whose knee cannot fail: dst_peak itself (KS = 1)
+    stand_in = *tone;
+    stand_in.src_peak = std::isfinite(tone->dst_peak) && tone->dst_peak > 0.0f && tone->dst_peak <= 10000.0f ? tone->dst_peak : 1000.0f;
+  }
+  OutputTarget asked;
+  int rc = OutputTarget::of_entry(kind, {view, light, tone ? &stand_in : nullptr, nullptr, nullptr, ootf}, dest, nullptr, asked);
+  if (rc || (rc = hm_stats_check_fraction(m.fraction)) || (rc = hm_stats_check_unit(m.unit_nits))) return rc;
+  asked.measure = &m;
+  if (!f->file.item(id)) return hm_fail(HM_ERR_INVALID_ARG, "no item %u", id);
+  if (is_derived_item(f, id)) return hm_fail(HM_ERR_UNSUPPORTED, "light statistics: item %u is a derived image ('iden' / 'iovl'), which is not supported", id);
+  ResolvedRequest r;
+  if ((rc = resolve_request(f, id, params, asked, false, r))) return rc;
+  if ((rc = decode_item(f, r.id, params, r.t, out))) return rc;
+  if (!m.done) { hm_decoded_free(out); return hm_fail(HM_ERR_UNSUPPORTED, "light statistics: output format %d has no interleaved pixels to measure", params->out_format); }
+  if (stats) *stats = m.stats;
+  return HM_OK;
+}
+
+int hm_decode_item_light_stats(const hm_file* f, uint32_t id, const hm_decode_params* params, const hm_device_view* view, const hm_device_light* light,
+                               const hm_device_ootf* ootf, float unit_nits, hm_light_stats* stats, hm_decoded* out)
+{
+  if (!stats) return hm_fail(HM_ERR_INVALID_ARG, "null argument");
+  LightMeasure m;
+  m.mode = HM_MEASURE_STATS; m.unit_nits = unit_nits;
+  const hm_device_dest dest = hm_stats_stand_in_dest();
+  return decode_item_measuring(HM_ENTRY_STATS, f, id, params, view, light, ootf, nullptr, &dest, m, stats, out);
+}
+
+int hm_decode_item_to_device_measured(const hm_file* f, uint32_t id, const hm_decode_params* params, const hm_device_view* view, const hm_device_light* light,
+                                      const hm_device_ootf* ootf, const hm_device_tone* tone, double fraction, const hm_device_dest* dest, hm_decoded* out,
+                                      hm_light_stats* stats)
+{
+  if (!tone) return hm_fail(HM_ERR_INVALID_ARG, "null argument");
+  LightMeasure m;
+  m.mode = HM_MEASURE_TONE; m.fraction = fraction;
+  return decode_item_measuring(HM_ENTRY_MEASURED, f, id, params, view, light, ootf, tone, dest, m, stats, out);
 }
 
 int hm_file_item_icc_info(const hm_file* f, uint32_t id, hm_icc_info* out)

@@ -127,6 +127,17 @@ struct ItemPlan {
   }
 };
 
+// The light statistics of a decode (include/heif_mi355x.h "Light statistics"): the entry's request and, behind the decode, its result.
+// mode HM_MEASURE_STATS: the pixels are measured and not written (the target's dest is hm_stats_stand_in_dest); HM_MEASURE_TONE: measured,
+// then written through the tone step with src_peak = the percentile's nits (the target's tone step carries a stand-in peak until then).
+struct LightMeasure {
+  int mode = HM_MEASURE_NONE;
+  float unit_nits = 0.0f;   // STATS: as the caller gave it (TONE: the tone step's)
+  double fraction = 1.0;    // TONE: of the percentile
+  bool done = false;
+  hm_light_stats stats{};   // filled by emit_image
+};
+
 // Where the result of a decode goes beside hm_decoded: every function between an entry point and emit_image takes one of these.
 // All null: pinned host memory (or params->ext_dst).  The pointers are the caller's; target_check_shape states what goes together.
 // On the way in a target passes one front, each part of it stated once: of_entry (which pointers the entry's kind takes:
@@ -144,6 +155,7 @@ struct OutputTarget {
   const hm_device_ootf* ootf = nullptr;        // the OOTF step beside light (a tone step beside it keeps its zeros: they resolve to display_peak)
   const uint8_t* icc = nullptr;                // the ICC profile a light step with HM_LIGHT_FROM_ICC reads (resolve_request: the item's own, inside the
   size_t icc_size = 0;                         // open file, which outlives the job)
+  LightMeasure* measure = nullptr;             // the light statistics of the interleaved pixels (with dest and light), the entry's own: it outlives the decode
   hm_view_scratch* scratch = nullptr;          // tap tables and the intermediate of the resampling step, the tables of the light step
   hm_view_item* view_later = nullptr;          // view + dest: the view is not written, only described there - the caller writes it with those of other images
   hm_planes_view_item* planes_later = nullptr; // the same for view + planes
@@ -159,7 +171,7 @@ struct OutputTarget {
     t.dest = d; t.planes = p; t.view = st.view; t.light = st.light; t.tone = st.tone; t.alpha = st.alpha; t.gain = st.gain; t.ootf = st.ootf;
     return HM_OK;
   }
-  hm_out_steps steps() const { return hm_out_steps{view, light, tone, alpha, gain, ootf, icc, icc_size}; } // the request of the device write (hm_devdest.h)
+  hm_out_steps steps() const { return hm_out_steps{view, light, tone, alpha, gain, ootf, icc, icc_size, measure ? measure->mode : (int)HM_MEASURE_NONE}; } // the request of the device write (hm_devdest.h)
 };
 // dest xor planes (or neither); light only with dest; tone only with light; ootf only with light; alpha only with dest and never with view_later; gain only with light and
 // never with view_later; view only with one of the two; a *_later only with view and its own kind of destination
@@ -192,6 +204,7 @@ struct OwnedTarget {
     if (from.gain) { gain = *from.gain; t.gain = &gain; }
     if (from.ootf) { ootf = *from.ootf; t.ootf = &ootf; }
     t.icc = from.icc; t.icc_size = from.icc_size; // (the file's bytes: the job holds the file)
+    t.measure = from.measure;
   }
 };
 

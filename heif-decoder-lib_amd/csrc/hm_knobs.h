@@ -36,11 +36,12 @@ extern "C" {
 //   overlap_min_pics (0)   > 0: hm_batch_execute's automatic overlap (hm_overlap_plan.h) engages from that many pictures on, whatever cut the chain launcher takes
 //   overlap_cut (0)        > 0: the image index at which the automatic overlap cuts the batch into its two groups
 //   overlay_start (1)      0: k_overlay walks every layer from the bottom (no start layer per span: tests compare the two)
+//   stats_groups (0)       > 0: k_light_stats runs with that many workgroups (0: from the device's CU count; tests: few workgroups on a small picture)
 enum hm_knob_id { HM_KNOB_CHAIN_SPIN_LIMIT, HM_KNOB_CHAIN_TEST_STALL, HM_KNOB_BATCH_FAIL_WIDTH, HM_KNOB_CHAIN_PAIRS, HM_KNOB_CHAIN_SHARE, HM_KNOB_CHAIN_RING,
                   HM_KNOB_CHAIN_ALT, HM_KNOB_CHAIN_NP, HM_KNOB_CHAIN_DEBUG, HM_KNOB_RESID_SEGS, HM_KNOB_RECON_WAVES, HM_KNOB_QUAD_CLASS, HM_KNOB_TAIL_FUSED,
                   HM_KNOB_STREAM_INTERLEAVED, HM_KNOB_CHAIN_SPLIT, HM_KNOB_TAIL_HDR16, HM_KNOB_CHAIN_EARLY, HM_KNOB_GRID_SLAB_ROWS, HM_KNOB_VIEW_H_STAGED,
                   HM_KNOB_VIEW_STAGE_PX, HM_KNOB_VIEW_BATCH, HM_KNOB_VIEW_BATCH_BYTES, HM_KNOB_OVERLAP_MIN_PICS,
-                  HM_KNOB_OVERLAP_CUT, HM_KNOB_OVERLAY_START, HM_KNOB_COUNT };
+                  HM_KNOB_OVERLAP_CUT, HM_KNOB_OVERLAY_START, HM_KNOB_STATS_GROUPS, HM_KNOB_COUNT };
 int hm_knob(int id);
 int hm_knob_set(const char* name, int value); // 0, or -1 for an unknown name (hidden: reached through test_hooks.cpp's hm_debug_set only)
 #ifdef __cplusplus

@@ -26,13 +26,14 @@ constexpr int OOTF_STEPS = HM_OOTF_STEPS;
 
 // The step's tables lie in LDS one behind the other: lin[1 << bits] (lin3: three of them, red, green, blue; with_lin: a vertical pass has
 // none - its sums are of light already), enc[1 << ebits] when re-encoding, thr and sg of the tone step, thr and sg of the OOTF step.  Offsets in floats; end: all of them.
+// thr_only: the statistics pass (stats.hip) searches the tone step's thr and scales by nothing - sg is not laid out (and it never re-encodes).
 struct LightLayout { int enc, tone, ootf, end; };
-__host__ __device__ inline LightLayout light_layout(bool with_lin, int bits, int ebits, bool encode, bool tone, bool ootf, bool lin3)
+__host__ __device__ inline LightLayout light_layout(bool with_lin, int bits, int ebits, bool encode, bool tone, bool ootf, bool lin3, bool thr_only = false)
 {
   LightLayout o;
   o.enc = with_lin ? (lin3 ? 3 : 1) << bits : 0;
   o.tone = o.enc + (encode ? 1 << ebits : 0);
-  o.ootf = o.tone + (tone ? 2 * TONE_STEPS : 0);
+  o.ootf = o.tone + (tone ? (thr_only ? 1 : 2) * TONE_STEPS : 0);
   o.end = o.ootf + (ootf ? 2 * OOTF_STEPS : 0);
   return o;
 }
@@ -40,8 +41,8 @@ __host__ __device__ inline LightLayout light_layout(bool with_lin, int bits, int
 // the step does not have is not looked at), as the kernels did before they shared this.  Taken up front as pointers, k_light_v waits
 // once more on its kernel arguments: 14.8 against 14.1 us (profiles/step_kernels_refactor.txt).
 struct LightTables {
-  const float* lds; bool with_lin;
-  __device__ __forceinline__ LightLayout at(const Light& L) const { return light_layout(with_lin, L.bits, L.ebits, L.encode, L.tone, L.ootf, L.lin3); }
+  const float* lds; bool with_lin; bool thr_only = false;
+  __device__ __forceinline__ LightLayout at(const Light& L) const { return light_layout(with_lin, L.bits, L.ebits, L.encode, L.tone, L.ootf, L.lin3, thr_only); }
   __device__ __forceinline__ const float* lin() const { return lds; }
   __device__ __forceinline__ const float* enc(const Light& L) const { return lds + at(L).enc; }
   __device__ __forceinline__ const float* tone(const Light& L) const { return lds + at(L).tone; }
@@ -61,12 +62,13 @@ __device__ __forceinline__ void fill_tables(float* lds, const float* __restrict_
 }
 
 // the step's tables into LDS by light_layout, every one or (no lin) a vertical pass's; every thread of the workgroup comes here
-__device__ __forceinline__ LightTables fill_light(float* lds, const Light& L, bool with_lin)
+// thr_only (the statistics pass; with_lin): of the tone step thr alone - sg lies behind it in global memory and is not loaded
+__device__ __forceinline__ LightTables fill_light(float* lds, const Light& L, bool with_lin, bool thr_only = false)
 {
-  const int ne = L.encode ? 1 << L.ebits : 0, nt = L.tone ? 2 * TONE_STEPS : 0;
+  const int ne = L.encode ? 1 << L.ebits : 0, nt = L.tone ? (thr_only ? 1 : 2) * TONE_STEPS : 0;
   if (with_lin) fill_tables(lds, L.lin, (L.lin3 ? 3 : 1) << L.bits, L.enc, ne, L.tone, nt, L.ootf, 2 * OOTF_STEPS);
   else if (L.encode || L.tone || L.ootf) fill_tables(lds, L.enc, ne, L.tone, nt, L.ootf, 2 * OOTF_STEPS); // (uniform: the barrier inside is met by every thread or by none)
-  return LightTables{lds, with_lin};
+  return LightTables{lds, with_lin, thr_only};
 }
 
 // |{c in 1 .. peak : enc[c] <= r}|: enc rises, so the count is the largest c whose threshold r has reached (0: none; a NaN: none)
@@ -178,17 +180,30 @@ static inline size_t light_layout_bytes(const hm_light_args* la, bool with_lin)
 static inline size_t light_h_bytes(const hm_light_args* la) { return (size_t)(la->lin3 ? 12 : 4) << la->bits; }
 static inline size_t light_v_bytes(const hm_light_args* la) { return light_layout_bytes(la, false); }
 static inline size_t light_tables_bytes(const hm_light_args* la) { return light_layout_bytes(la, true); }
+// the statistics pass: lin, thr of the tone step, the OOTF tables; behind them its histogram and the word of its maximum (padded to 16 bytes)
+enum { LIGHT_STATS_WORDS = HM_LIGHT_STATS_BINS + 4 };
+static inline size_t light_stats_bytes(const hm_light_args* la)
+{
+  return ((size_t)light_layout(true, la->bits, la->enc_bits, false, true, la->ootf != nullptr, la->lin3 != 0, true).end + LIGHT_STATS_WORDS) * sizeof(float);
+}
 
 // What a launch may ask for as dynamic LDS: 64 KB, what a workgroup gets without the launch opting in to more (the CU has 160 KB; no
 // launch here opts in).  Only three lin tables reach it: 12-bit samples with a 12-bit re-encoding and a tone step are 48 + 16 + 16 KB.
 // The one host check of it - the plan asks before anything is queued (hm_light_lds_check), every launcher asks again.
-// pass 0: k_*_tensor / k_*_nearest, 1: a horizontal pass, 2: a vertical pass
+// pass 0: k_*_tensor / k_*_nearest, 1: a horizontal pass, 2: a vertical pass, 3: the statistics pass (k_light_stats: whatever la says of enc
+// and the tone step, it holds lin, thr, the OOTF tables and its histogram - 12-bit samples through three curves are 48 + 8 + 8 KB and a word)
 enum { LIGHT_LDS_MOST = 64 * 1024 };
-static inline size_t light_pass_bytes(const hm_light_args* la, int pass) { return pass == 0 ? light_tables_bytes(la) : pass == 1 ? light_h_bytes(la) : light_v_bytes(la); }
+static inline size_t light_pass_bytes(const hm_light_args* la, int pass)
+{
+  return pass == 0 ? light_tables_bytes(la) : pass == 1 ? light_h_bytes(la) : pass == 2 ? light_v_bytes(la) : light_stats_bytes(la);
+}
 static inline int check_light_lds(const hm_light_args* la, int pass)
 {
   const size_t bytes = light_pass_bytes(la, pass);
   if (bytes <= (size_t)LIGHT_LDS_MOST) return HM_OK;
+  if (pass == 3)
+    return hm_fail(HM_ERR_UNSUPPORTED, "light statistics: %d-bit samples through %s with%s in one kernel need %zu bytes of local memory for their tables and the histogram (%d fit): not supported",
+                   la->bits, la->lin3 ? "three distinct curves of the ICC profile" : "one curve", la->ootf ? " an OOTF step" : " no OOTF step", bytes, (int)LIGHT_LDS_MOST);
   return hm_fail(HM_ERR_UNSUPPORTED, "light: %d-bit samples through %s with%s%s%s in one kernel need %zu bytes of local memory for their tables (%d fit): not supported", la->bits,
                  la->lin3 ? "three distinct curves of the ICC profile" : "one curve", la->encode ? (la->enc_bits == 8 ? " a re-encoding to 8-bit codes," : " a re-encoding,") : "",
                  la->tone ? " a tone step," : "", la->ootf ? " an OOTF step," : " no OOTF step,", bytes, (int)LIGHT_LDS_MOST);

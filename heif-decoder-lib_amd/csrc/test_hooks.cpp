@@ -27,6 +27,7 @@ extern "C" const void* hm_light_kernel_of(int index);                           
 extern "C" const void* hm_light_finish8_kernel_of(int index);                               // ... the instances of the 8-bit finish from 16-bit samples
 extern "C" const void* hm_alpha_kernel_of(int index);                                       // alpha.hip: NULL behind the last instance
 extern "C" const void* hm_gain_kernel_of(int index);                                        // gain.hip: NULL behind the last instance
+extern "C" const void* hm_stats_kernel_of(int index);                                       // stats.hip: NULL behind the last instance
 extern "C" long long hm_light_lds_bytes(int bits, int enc_bits, int encode, int tone, int pass); // ... the dynamic LDS its launchers ask for
 
 extern "C" {
@@ -62,6 +63,7 @@ __attribute__((visibility("default"))) int hm_debug_kernel_regs(int which, int a
   else if (which == 10) fn = hm_light_finish8_kernel_of(a); // (k_light_tensor<2, 3, uint8_t, ...>, k_light_nearest<uint16_t, 3, uint8_t>)
   else if (which == 11) fn = hm_alpha_kernel_of(a); // (k_alpha_tensor, k_alpha_nearest, k_alpha_h, k_alpha_v; out[1] counts scratch, not LDS)
   else if (which == 12) fn = hm_gain_kernel_of(a); // (k_gain_tensor, k_gain_nearest, k_gain_map_h, k_gain_map_v, k_gain_v; out[1] counts scratch, not LDS)
+  else if (which == 13) fn = hm_stats_kernel_of(a); // (k_light_stats; out[1] counts scratch, not LDS)
   hipFuncAttributes fa;
   if (!fn || !out || hipFuncGetAttributes(&fa, fn) != hipSuccess) return -1;
   out[0] = fa.numRegs;

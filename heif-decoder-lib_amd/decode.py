@@ -14,6 +14,9 @@ primaries - a resize under light= averages light, not code values.  light={"from
 ICC profile (a matrix/TRC profile: a phone's Display P3) instead of its nclx codes.  tone=dict(dst_peak=203.0, src_peak=None, unit_nits=None,
 out_unit_nits=None, out_bits=None) beside light= maps the content's peak (None: the file's clli / mdcv, else 1000 cd/m2) to the
 display's with the BT.2390 curve; out_bits=8 finishes a deeper image in 8-bit codes (torch.uint8 is then accepted for it).
+tone=dict(dst_peak=203.0, src_peak="measured", percentile=0.9999) measures the content's peak on the decoded pixels instead (the
+single-item call only); measure_light(data) and measure_light_of_tensor(pixels, bits, light) return the numbers themselves, a
+LightStats: the histogram over the tone step's 2048 PQ codes of max(R, G, B), the largest norm, percentiles, the average.
 alpha="straight" / "premultiplied" / dict(mode="matte", background=(r, g, b)) with out_format "rgba" / "rrggbbaa_le" uses the alpha
 channel: a resize sums colour times alpha (no dark fringes around a cut-out), and the tensor holds straight colour, premultiplied
 colour, or - three channels - the picture over the background colour (code values at the target's sample depth).
@@ -197,6 +200,31 @@ def _tone_of(tone, lit):
     return d
 
 
+def _measured_of(tone):
+    """(the tone= argument without what asks for a measured peak, the percentile's fraction or None): src_peak="measured" asks for the
+    content's peak to be measured on the decoded pixels (hm_decode_item_to_device_measured), percentile= (default 0.9999) is the share
+    of the pixels that peak covers; percentile is accepted only beside it"""
+    if not isinstance(tone, dict) or ("percentile" not in tone and not isinstance(tone.get("src_peak"), str)):
+        return tone, None
+    if tone.get("src_peak") != "measured":
+        if isinstance(tone.get("src_peak"), str):
+            raise ValueError(f"tone['src_peak'] = {tone['src_peak']!r}: cd/m2, None (the file's own) or 'measured'")
+        raise ValueError("tone: percentile is accepted only beside src_peak='measured'")
+    p = tone.get("percentile")
+    fraction = 0.9999 if p is None else float(p)
+    if not (fraction > 0.0 and fraction <= 1.0):
+        raise ValueError(f"tone['percentile'] = {p!r}: a fraction in (0, 1]")
+    rest = {k: v for k, v in tone.items() if k != "percentile"}
+    rest["src_peak"] = None
+    return rest, fraction
+
+
+def _no_measuring(tone):
+    """the batch and sequence calls: a tone= that asks for a measured peak is refused"""
+    if _measured_of(tone)[1] is not None:
+        raise ValueError("tone: src_peak='measured' - only the single-item call (decode_to_tensor) measures; measure_light gives a clip's or a batch's numbers")
+
+
 def _ootf_of(ootf, lit):
     """hm_device_ootf (or None) of the ootf= argument: a number (the display's peak in cd/m2) or a dict of display_peak (needed) /
     gamma (None: the system gamma of that peak); needs a light step"""
@@ -317,11 +345,17 @@ class _Steps:
 
     def __init__(self, alpha, fmt):
         self.alp, self.c = _alpha_of(alpha, fmt)
-        self.lit = self.ton = self.gn = self.oo = None
+        self.lit = self.ton = self.gn = self.oo = self.fraction = None
 
-    def parse(self, light, tone, gain, ootf):
+    def parse(self, light, tone, gain, ootf, measures=False):
+        """measures: the caller is the single-item call, which can measure the content's peak (tone's src_peak="measured")"""
         self.lit = _light_of(light)
+        if not measures:
+            _no_measuring(tone)
+        tone, self.fraction = _measured_of(tone)
         self.ton = _tone_of(tone, self.lit)
+        if self.fraction is not None and (self.alp is not None or gain is not None):
+            raise ValueError("tone: src_peak='measured' beside alpha= or gain= (the measured entry takes view, light, ootf and tone)")
         self.gn = _gain_of(gain, self.lit)
         self.oo = _ootf_of(ootf, self.lit)
         if self.gn is not None and self.alp is not None:
@@ -402,7 +436,7 @@ def decode_to_tensor(data, item_id=0, out_format="rgb", layout="chw", dtype=None
     c = st.c
     f = _File(data)
     try:
-        st.parse(light, tone, gain, ootf)
+        st.parse(light, tone, gain, ootf, measures=True)
         iid = item_id or L.hm_file_primary_item(f.h)
         sized = iid
         if st.gn is not None:
@@ -422,13 +456,114 @@ def decode_to_tensor(data, item_id=0, out_format="rgb", layout="chw", dtype=None
         d = capi.Decoded()
         fn, steps = st.entry(L, "hm_decode_item_to_device", view)
         with torch.cuda.device(out.device):
-            capi.check_image(fn(f.h, iid, C.byref(prm), *steps, C.byref(dest), C.byref(d)))
+            if st.fraction is not None:  # the content's peak measured on the decoded pixels, in the same call
+                capi.check_image(L.hm_decode_item_to_device_measured(f.h, iid, C.byref(prm), _ref(view), _ref(st.lit), _ref(st.oo), _ref(st.ton), st.fraction,
+                                                                     C.byref(dest), C.byref(d), None))
+            else:
+                capi.check_image(fn(f.h, iid, C.byref(prm), *steps, C.byref(dest), C.byref(d)))
         if (d.width, d.height) != (w, h):  # (the library checked the destination against the decoded size: nothing else was written)
             raise capi.HmError(-3, f"the decoded image is {d.width} x {d.height}, the file declares {w} x {h}")
         L.hm_decoded_free(C.byref(d))
         return out
     finally:
         f.close()
+
+
+class LightStats:
+    """The light statistics of a rectangle of pixels (hm_light_stats): pixels, histogram (numpy uint32[2048]: pixels per 11-bit PQ code of
+    the norm max(R, G, B)), max_norm (the largest norm, in the light step's units), max_code, max_nits, average_nits, and
+    percentile(fraction) -> (code, nits of the upper edge of that code's bin)."""
+
+    def __init__(self, c):
+        import numpy as np
+        self._c = c
+        self.pixels = int(c.pixels)
+        self.histogram = np.ctypeslib.as_array(c.hist).astype(np.uint32)
+        self.max_norm, self.max_code, self.max_nits, self.average_nits = float(c.max_norm), int(c.max_code), float(c.max_nits), float(c.average_nits)
+
+    def percentile(self, fraction):
+        code, nits = C.c_int32(), C.c_float()
+        capi.check_image(capi.image_lib().hm_light_stats_percentile(C.byref(self._c), float(fraction), C.byref(code), C.byref(nits)))
+        return code.value, nits.value
+
+    def __repr__(self):
+        return f"LightStats(pixels={self.pixels}, max_code={self.max_code}, max_nits={self.max_nits:.6g}, average_nits={self.average_nits:.6g})"
+
+
+def _crop_view(crop):
+    """hm_device_view (or None) of a crop alone"""
+    if crop is None:
+        return None
+    return _view_of(crop, None, "triangle", 0, 0)[0]
+
+
+def _unit_nits(unit_nits):
+    if unit_nits is not None and float(unit_nits) == 0.0:
+        raise ValueError(f"unit_nits = {unit_nits!r}: None asks for the default")
+    return 0.0 if unit_nits is None else float(unit_nits)
+
+
+def measure_light(data, item_id=0, out_format=None, crop=None, light=True, ootf=None, unit_nits=None, host_threads=None, stream=None):
+    """Decode one image of a HEIF file and measure its light levels on the device (hm_decode_item_light_stats): a LightStats of the
+    whole image, or of crop=(x, y, w, h) - of a grid only the tiles it touches are decoded.  out_format None: "rgb" for 8-bit items,
+    "rrggbb_le" for deeper ones.  light: True or a dict as in decode_to_tensor (to_primaries picks the primaries the norm is taken in);
+    ootf: as in decode_to_tensor; unit_nits: cd/m2 that light value 1.0 stands for (None: 10000 for PQ, the display's peak beside ootf=)."""
+    import torch
+    L = capi.image_lib()
+    lit = _light_of(light)
+    if lit is None:
+        raise ValueError("measure_light: needs light= (the statistic is one of linear light)")
+    oo = _ootf_of(ootf, lit)
+    unit = _unit_nits(unit_nits)
+    view = _crop_view(crop)
+    f = _File(data)
+    try:
+        iid = item_id or L.hm_file_primary_item(f.h)
+        if out_format is None:
+            info = capi.ImageInfo()
+            capi.check_image(L.hm_file_image_info(f.h, iid, C.byref(info)))
+            out_format = "rgb" if info.bit_depth <= 8 else "rrggbb_le"
+        fmt = _out_format(out_format)
+        device = torch.device("cuda", torch.cuda.current_device())
+        prm = capi.DecodeParams(fmt, host_threads or _default_threads(), 0, 0, _stream_handle(stream, device), None, 0, 0, 0, 0)
+        d, s = capi.Decoded(), capi.LightStatsC()
+        capi.check_image(L.hm_decode_item_light_stats(f.h, iid, C.byref(prm), _ref(view), _ref(lit), _ref(oo), unit, C.byref(s), C.byref(d)))
+        L.hm_decoded_free(C.byref(d))
+        return LightStats(s)
+    finally:
+        f.close()
+
+
+def measure_light_of_tensor(pixels, bits, light, ootf=None, unit_nits=None, crop=None, stream=None):
+    """The light statistics (hm_light_stats_of_tensor) of interleaved pixels on the device: an H x W x 3 or H x W x 4 CUDA tensor of
+    torch.uint8 (bits 8) or torch.uint16 / torch.int16 (bits 9 .. 12) code values; its row stride is honoured.  light: a dict with
+    from_transfer and from_primaries (the pixels carry no profile); ootf, unit_nits, crop: as measure_light."""
+    import torch
+    L = capi.image_lib()
+    if not isinstance(pixels, torch.Tensor) or not pixels.is_cuda or pixels.dim() != 3 or pixels.shape[2] not in (3, 4):
+        raise ValueError("pixels: an H x W x 3 or H x W x 4 CUDA tensor")
+    if pixels.dtype not in (torch.uint8, torch.uint16, torch.int16):
+        raise ValueError(f"pixels: dtype {pixels.dtype} is not torch.uint8, torch.uint16 or torch.int16")
+    wide = pixels.dtype != torch.uint8
+    if (int(bits) > 8) != wide or not 8 <= int(bits) <= 16:
+        raise ValueError(f"bits {bits!r} with dtype {pixels.dtype}: 8 for torch.uint8, 9 and more for 16-bit samples")
+    h, w, c = pixels.shape
+    if h == 0 or w == 0:
+        raise ValueError("pixels: an empty tensor")
+    if not ((pixels.stride(2) == 1) and (pixels.stride(1) == c or w == 1) and pixels.stride(0) >= 0):
+        raise ValueError("pixels: the pixels of a row must be contiguous (only the row stride is free)")
+    lit = _light_of(light)
+    if lit is None:
+        raise ValueError("measure_light_of_tensor: needs light= with from_transfer and from_primaries")
+    oo = _ootf_of(ootf, lit)
+    unit = _unit_nits(unit_nits)
+    view = _crop_view(crop)
+    fmt = {(False, 3): capi.HM_OUT_RGB, (False, 4): capi.HM_OUT_RGBA, (True, 3): capi.HM_OUT_RRGGBB_LE, (True, 4): capi.HM_OUT_RRGGBBAA_LE}[(wide, c)]
+    s = capi.LightStatsC()
+    with torch.cuda.device(pixels.device):
+        capi.check_image(L.hm_light_stats_of_tensor(fmt, int(bits), w, h, pixels.data_ptr(), pixels.stride(0) * pixels.element_size(), _ref(view), _ref(lit), _ref(oo),
+                                                    unit, C.byref(s), _stream_handle(stream, pixels.device)))
+    return LightStats(s)
 
 
 def decode_batch_to_tensor(files, item_id=0, out_format="rgb", layout="chw", dtype=None, scale=None, bias=None, out=None,
@@ -562,6 +697,7 @@ def decode_sequence_to_tensor(data, frames=None, out_format="rgb", layout="chw",
     code = _dtype_code(dtype)
     st = _Steps(None, fmt)
     c = st.c
+    _no_measuring(tone)
     sc, bi = _per_channel(scale, 1.0), _per_channel(bias, 0.0)
     f = _File(data)
     try:

@@ -883,7 +883,7 @@ HM_API int hm_file_item_icc_info(const hm_file* f, uint32_t id, hm_icc_info* out
  * src_peak == 0 is the image's own peak, from the properties of the item that is decoded (of a grid: the grid item): its clli
  * max_content_light_level if non-zero - the field is 16 bits wide and PQ codes no light above 10000 cd/m2: a larger value counts as
  * 10000 -; otherwise its mdcv max_display_mastering_luminance * 0.0001 if the raw value lies in 50000 .. 100000000; otherwise 1000.
- * A frame of a sequence carries no properties: 1000.
+ * A frame of a sequence carries no properties: 1000.  (A file without either property can be measured instead: "Light statistics" below.)
  * out_bits == 8, the 8-bit finish: the source samples, lin[] and the sums stay at the target's depth; enc is
  * hm_light_table(to_transfer, 8, gain, 1) and the code counts thresholds over 1 .. 255.  The destination is judged, sized and
  * written as that of the 8-bit sibling target (an HM_OUT_RRGGBB_LE request: hm_device_dest_bytes(HM_OUT_RGB, ...)): HM_DEV_U8 stores
@@ -1136,6 +1136,79 @@ HM_API int hm_ootf_gamma(const hm_device_ootf* ootf, double* gamma);
 HM_API int hm_ootf_table(const hm_device_ootf* ootf, float gain, int which, float* out);
 /* ... and the luminance weights y[0 .. 2] of a set of primaries (an unknown code: HM_ERR_UNSUPPORTED) */
 HM_API int hm_ootf_luma(int primaries, float out[3]);
+
+/* ------------------------------------------------------------------------- */
+/* Light statistics: a picture's light levels measured on the device, and a tone step fed from them */
+/* ------------------------------------------------------------------------- */
+
+/* The statistic runs over a rectangle of the interleaved pixels: without a view the whole image, with a view the view's crop AT SOURCE
+ * RESOLUTION - the source pixels are measured, not the resampled ones (out_w, out_h and filter are checked as the view entries check
+ * them and otherwise unused).  Every pixel of the rectangle:
+ *   v -> light_in: r_c = lin[min(v_c, peak)]                      the light step's table(s), "Light" above
+ *   with an OOTF step: the OOTF step's factor on r                "OOTF" above
+ *   with to_primaries set: the gamut matrix on r
+ *   N = fmaxf(fmaxf(R, G), B)
+ *   k = |{ i in 1 .. 2047 : thr[i] <= N }|                        the tone step's search in the tone step's own thr[] for the light
+ *                                                                 step's gain g and U = unit_nits; a negative or NaN N gives k = 0
+ * - exactly what the pointwise tone step would compute for that pixel.  Alpha is ignored; to_transfer plays no part.  k is the PQ code
+ * of N * U / g cd/m2: it does not depend on g or U.
+ * Everything below is an integer count or a maximum: no result depends on the order in which the device's workgroups finish, and
+ * two calls give identical structs.
+ *   pixels        of the rectangle; the sum of hist[]
+ *   hist[k]       pixels whose norm has code k
+ *   max_norm      the largest N, bit for bit (0 if no N is above 0)
+ *   max_code      the highest k with hist[k] != 0
+ *   max_nits      (float)((double)max_norm * U / g)
+ *   average_nits  the sum over k, in increasing k, of (double)hist[k] * code_nits(k, 0), in double, divided by pixels, rounded once
+ *                 to float: taken on the host from the histogram
+ * code_nits(k, edge) = 10000 * EOTF(x / 2047), EOTF the ST 2084 function of transfer 16; edge 0: x = k, the code's own light; edge 1:
+ * x = min(k + 0.5, 2047), the upper edge of bin k - no pixel of bin k is brighter.
+ * percentile(fraction), fraction in (0, 1]: rank = min(max((uint64_t)ceil(fraction * (double)pixels), 1), pixels); code = the smallest
+ * k whose cumulative count reaches rank; nits = (float)code_nits(code, 1).  fraction == 1 gives max_code.
+ * unit_nits must be given (finite, above 0, at most 10000), except that 0 stands for 10000 when the resolved from_transfer is 16 and
+ * for display_peak beside an OOTF step - the tone step's rule.
+ * The measured tone step (hm_decode_item_to_device_measured): the item is decoded once, measured, and written through the tone step
+ * with src_peak = the nits of percentile(fraction) - the upper bin edge, always above 0 and at most 10000 - in place of the clli /
+ * mdcv / 1000 rule.  Everything else is hm_decode_item_to_device_ootf (without an alpha step): the same plan, the same write, the
+ * bytes of that entry called with this src_peak.  tone->src_peak must be 0 there: an explicit peak is the _tone entry's.
+ * The gain step has no place in these signatures: the light of a gain-mapped rendition depends on the headroom asked for, and is
+ * measured on that rendition's pixels (hm_light_stats_of_tensor) where it is wanted.  Derived items are not supported.
+ * Refused before anything is queued, *stats and *out untouched - HM_ERR_INVALID_ARG: a null light, out or stats where it is required,
+ * reserved != 0, a fraction that is not finite or outside (0, 1], a unit_nits the tone step would refuse, a _BE target, a src_peak
+ * other than 0 in the measured entry; HM_ERR_UNSUPPORTED: a derived item, tables that do not fit a workgroup's local memory (12-bit
+ * samples through three distinct ICC curves) - and everything the light, OOTF, view and destination checks refuse.  Behind the
+ * decode, before a byte of the destination is written: what waits for the image's profile (the tone step's unit_nits rule), and the
+ * knee of the measured peak (KS < 0). */
+enum { HM_LIGHT_STATS_BINS = 2048 };   /* == HM_TONE_STEPS */
+typedef struct hm_light_stats {
+  uint64_t pixels;                      /* of the rectangle; == the sum of hist[] */
+  uint32_t hist[HM_LIGHT_STATS_BINS];   /* hist[k] = pixels whose norm has code k */
+  float    max_norm;                    /* the largest N (0 if none is above 0), bit-exact */
+  int32_t  max_code;                    /* highest k with hist[k] != 0 */
+  float    max_nits;                    /* (float)((double)max_norm * U / g) */
+  float    average_nits;                /* rule above */
+  int32_t  reserved[2];                 /* 0 */
+} hm_light_stats;
+/* Host arithmetic, no device: code_nits (k in 0 .. 2047, edge 0 or 1) */
+HM_API int hm_light_stats_code_nits(int k, int edge, double* nits);
+/* ... and the percentile of a statistic; code and nits may each be NULL */
+HM_API int hm_light_stats_percentile(const hm_light_stats* stats, double fraction, int32_t* code, float* nits);
+/* ... and average_nits of its histogram and pixels, as the entries below fill it in */
+HM_API int hm_light_stats_average(const hm_light_stats* stats, float* nits);
+/* The statistic of interleaved pixels of `bits` bits that are on the device already (as hm_tone_to_tensor: from_transfer and
+ * from_primaries must be explicit); view and ootf may be NULL.  Returns when the numbers are in *out: `stream` has been waited for. */
+HM_API int hm_light_stats_of_tensor(int out_format, int bits, int src_w, int src_h, const void* d_src, int src_stride,
+                                    const hm_device_view* view, const hm_device_light* light, const hm_device_ootf* ootf, float unit_nits,
+                                    hm_light_stats* out, void* stream);
+/* Decode and measure, with no destination: from_* == 0 and HM_LIGHT_FROM_ICC resolve as in hm_decode_item_to_device_light; under a
+ * view only the tiles hm_plan_view names are decoded.  view and ootf may be NULL.  *out reports the image; it holds no pixels. */
+HM_API int hm_decode_item_light_stats(const hm_file* f, uint32_t id, const hm_decode_params* params, const hm_device_view* view,
+                                      const hm_device_light* light, const hm_device_ootf* ootf, float unit_nits, hm_light_stats* stats,
+                                      hm_decoded* out);
+/* Decode once, measure, tone-map with what was measured, write (rule above); view, ootf and stats may be NULL. */
+HM_API int hm_decode_item_to_device_measured(const hm_file* f, uint32_t id, const hm_decode_params* params, const hm_device_view* view,
+                                             const hm_device_light* light, const hm_device_ootf* ootf, const hm_device_tone* tone,
+                                             double fraction, const hm_device_dest* dest, hm_decoded* out, hm_light_stats* stats);
 
 /* ------------------------------------------------------------------------- */
 /* Planar views: a rectangle of the image, at a size of the caller's choice, into I420 / NV12 / P010 planes */
