@@ -28,6 +28,7 @@ HM_DEV_PLANES_SEPARATE, HM_DEV_PLANES_SEMI = 0, 1
 # views (hm_device_view): a rectangle of the image at a size of the caller's choice
 HM_VIEW_TRIANGLE, HM_VIEW_NEAREST = 0, 1
 HM_VIEW_CUBIC, HM_VIEW_LANCZOS3 = 16, 17
+HM_VIEWS_MOST = 4096  # views of one hm_decode_item_to_device_views / hm_resample_views_to_tensor call
 HM_PIPELINE_FULL = 1
 HM_DETAIL_NO_COLOUR_CHAIN = 2
 
@@ -417,6 +418,11 @@ def bind_image(L):
     L.hm_pipeline_submit.argtypes = [C.c_void_p, C.c_char_p, C.c_size_t, C.c_uint32, C.c_uint64]
     L.hm_resample_to_tensor.argtypes = [C.c_int, C.c_int, C.c_int, C.c_void_p, C.c_int, C.POINTER(DeviceView), C.POINTER(DeviceDest), C.c_void_p]
     L.hm_plan_view.argtypes = [C.c_void_p, C.c_uint32, C.POINTER(DecodeParams), C.POINTER(DeviceView), C.POINTER(C.c_int32 * 4)]
+    L.hm_decode_item_to_device_views.argtypes = [C.c_void_p, C.c_uint32, C.POINTER(DecodeParams), C.POINTER(DeviceView), C.POINTER(DeviceDest), C.c_int32,
+                                                 C.POINTER(DeviceLight), C.POINTER(DeviceTone), C.POINTER(DeviceAlpha), C.POINTER(DeviceOotf), C.POINTER(Decoded),
+                                                 C.POINTER(C.c_int32)]
+    L.hm_resample_views_to_tensor.argtypes = [C.c_int, C.c_int, C.c_int, C.c_void_p, C.c_int, C.POINTER(DeviceView), C.POINTER(DeviceDest), C.c_int32, C.c_void_p]
+    L.hm_plan_views.argtypes = [C.c_void_p, C.c_uint32, C.POINTER(DecodeParams), C.POINTER(DeviceView), C.c_int32, C.POINTER(C.c_int32 * 4)]
     L.hm_view_filter_taps.argtypes = [C.c_int, C.c_int, C.c_int, C.c_int, C.POINTER(C.c_int32), C.POINTER(C.c_float), C.c_int]
     L.hm_light_to_tensor.argtypes = [C.c_int, C.c_int, C.c_int, C.c_int, C.c_void_p, C.c_int, C.POINTER(DeviceView), C.POINTER(DeviceLight), C.POINTER(DeviceDest),
                                      C.c_void_p]

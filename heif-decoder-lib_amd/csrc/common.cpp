@@ -83,7 +83,7 @@ static const struct { const char* name; int def; } k_knobs[HM_KNOB_COUNT] = {
     {"chain_spin_limit", 0}, {"chain_test_stall", 0}, {"batch_fail_width", 0}, {"chain_pairs", -1}, {"chain_share", 0}, {"chain_ring", -1},
     {"chain_alt", 1}, {"chain_np", 0}, {"chain_debug", 0}, {"resid_segs", 0}, {"recon_waves", 0}, {"quad_class", -1}, {"tail_fused", 1},
     {"stream_interleaved", 0}, {"chain_split", 1}, {"tail_hdr16", 1}, {"chain_early", 1}, {"grid_slab_rows", -1}, {"view_h_staged", 1}, {"view_stage_px", 0},
-    {"view_batch", 1}, {"view_batch_bytes", 0}, {"overlap_min_pics", 0}, {"overlap_cut", 0}, {"overlay_start", 1}, {"stats_groups", 0}};
+    {"view_batch", 1}, {"view_batch_bytes", 0}, {"overlap_min_pics", 0}, {"overlap_cut", 0}, {"overlay_start", 1}, {"stats_groups", 0}, {"view_multi", 1}};
 static std::atomic<int> g_knob[HM_KNOB_COUNT];
 static std::atomic<unsigned> g_knob_set{0}; // bit i: knob i has been set (otherwise its default)
 int hm_knob(int id)

@@ -5,12 +5,15 @@
 // Planar views (a view into hm_device_planes): the geometry per plane, the refusals and the write step (kernels: planes_view.hip).
 // Light (hm_device_light): the transfer tables and the gamut matrix in double, the refusals and the write step (kernels: light.hip).
 #include <algorithm>
+#include <array>
 #include <cmath>
 #include <cstdio>
 #include <cstring>
 #include <functional>
+#include <map>
 #include <mutex>
 #include <new>
+#include <string>
 #include <vector>
 
 #include "hm_colour_plan.h"
@@ -21,6 +24,7 @@
 #include "hm_planes_view.h"
 #include "hm_primaries.h"
 #include "hm_view_batch.h"
+#include "hm_view_multi.h"
 
 extern "C" {
 
@@ -1380,6 +1384,174 @@ int hm_out_write(const hm_device_dest* d, const hm_out_plan* p, const void* src,
   return step == 2 ? hm_launch_alpha_tensor(&dp, pla, &aa, origin, src_stride, vp->w, vp->h, dst, sl, bs, s) : hm_launch_light_tensor(&dp, &la, origin, src_stride, vp->w, vp->h, dst, sl, bs, s);
 }
 
+// ---- many views of one picture (hm_views_write; hm_view_multi.h holds the arithmetic, resample.hip the kernels) --------------------
+
+// two destinations whose byte ranges [ptr, ptr + bytes) overlap: bytes as hm_dest_resolve computes them (plans[k].dp), with the pitches as resolved
+int hm_dests_check_overlap(const hm_device_dest* dests, const hm_out_plan* plans, int n)
+{
+  std::vector<int> order((size_t)n);
+  for (int k = 0; k < n; k++) order[(size_t)k] = k;
+  std::sort(order.begin(), order.end(), [&](int a, int b) { return (uintptr_t)dests[a].ptr < (uintptr_t)dests[b].ptr || (dests[a].ptr == dests[b].ptr && a < b); });
+  // (sorted by start: a range that overlaps any earlier one overlaps the earlier one that ends last)
+  int last = order[0];
+  for (int i = 1; i < n; i++) {
+    const int k = order[(size_t)i];
+    const uintptr_t end_last = (uintptr_t)dests[last].ptr + (uintptr_t)plans[last].dp.bytes;
+    if ((uintptr_t)dests[k].ptr < end_last)
+      return hm_fail(HM_ERR_INVALID_ARG, "views: the destinations of views %d and %d overlap (%lld bytes at %p, %lld bytes at %p)", std::min(last, k), std::max(last, k),
+                     (long long)plans[std::min(last, k)].dp.bytes, dests[std::min(last, k)].ptr, (long long)plans[std::max(last, k)].dp.bytes, dests[std::max(last, k)].ptr);
+    if ((uintptr_t)dests[k].ptr + (uintptr_t)plans[k].dp.bytes > end_last) last = k;
+  }
+  return HM_OK;
+}
+
+namespace {
+// one distinct axis of a group's views: n -> m under a filter; its table of m * (2 + taps) words at word `off` of the block
+struct MultiAxis { int n, m, filt, taps; int64_t off; };
+
+// one group of a multi-view write: views idx[0 .. m) share the key (hm_view_multi.h) - ONE pinned block and one upload (every distinct
+// axis' tap table once, the records, the running sums), one intermediate sized for the largest chunk, and per chunk one launch per pass
+int views_write_group(const hm_device_dest* dests, const hm_out_plan* plans, const int* idx, int m, bool staged, const void* src, int src_stride, hipStream_t s,
+                      hm_view_scratch* sc)
+{
+  const hm_dest_plan& p0 = plans[idx[0]].dp;
+  const bool chw = p0.layout == HM_DEV_LAYOUT_CHW;
+  const int C = p0.channels, planes = chw ? C : 1, obpp = C * p0.sample_bytes;
+  // the distinct axes: a table is the same whichever axis, and whichever view, reads it
+  std::map<std::array<int, 3>, int> seen;
+  std::vector<MultiAxis> axes;
+  std::vector<int> ax((size_t)m), ay((size_t)m);
+  int64_t words = 0;
+  auto axis_of = [&](int n, int mm, int filt) -> int {
+    const auto at = seen.find({n, mm, filt});
+    if (at != seen.end()) return at->second;
+    const int taps = axis_most_taps(n, mm, filt);
+    if (taps < 0) return taps;
+    axes.push_back(MultiAxis{n, mm, filt, taps, words});
+    words += (int64_t)mm * (2 + taps);
+    return seen[{n, mm, filt}] = (int)axes.size() - 1;
+  };
+  for (int i = 0; i < m; i++) {
+    const hm_view_plan& vp = plans[idx[i]].vp;
+    if ((ax[(size_t)i] = axis_of(vp.w, vp.ow, vp.filter)) < 0) return ax[(size_t)i];
+    if ((ay[(size_t)i] = axis_of(vp.h, vp.oh, vp.filter)) < 0) return ay[(size_t)i];
+  }
+  if (words > 0x7FFFFFFF) return hm_fail(HM_ERR_NOMEM, "views: %lld words of tap tables in one group", (long long)words);
+  const hm_view_multi_block lay = hm_view_multi_layout(words, m);
+  uint8_t* host = (uint8_t*)hm_pool_pinned_alloc((size_t)lay.bytes);
+  if (!host) return hm_fail(HM_ERR_NOMEM, "out of memory");
+  sc->pinned = host;
+  int32_t* tw = (int32_t*)host;
+  for (const MultiAxis& a : axes) fill_axis(tw + a.off, a.n, a.m, a.filt, a.taps);
+  if (staged) // (view_tables' check of the windows the staged pass loads as one run)
+    for (int i = 0; i < m; i++) {
+      const MultiAxis& a = axes[(size_t)ax[(size_t)i]];
+      const int32_t* t = tw + a.off;
+      for (int j = 0; j < a.m; j++) {
+        const int lo = t[j], hi = lo + t[a.m + j];
+        if (lo < 0 || hi > a.n || hi <= lo || (j && (lo < t[j - 1] || hi < t[j - 1] + t[a.m + j - 1])))
+          return hm_fail(HM_ERR_INTERNAL, "view: the windows of columns %d and %d are not in order", j - 1, j);
+      }
+    }
+  // the records, and what the chunk cut asks of every view
+  hm_view_rec* rec = reinterpret_cast<hm_view_rec*>(host + lay.rec_off);
+  int32_t* hsum = reinterpret_cast<int32_t*>(host + lay.hsum_off);
+  int32_t* vsum = reinterpret_cast<int32_t*>(host + lay.vsum_off);
+  std::vector<int64_t> bytes((size_t)m), floats((size_t)m);
+  std::vector<int32_t> hg((size_t)m), vg((size_t)m);
+  bool vec = true;
+  for (int i = 0; i < m; i++) {
+    const hm_out_plan& pl = plans[idx[i]];
+    const hm_view_plan& vp = pl.vp;
+    const hm_device_dest& d = dests[idx[i]];
+    const MultiAxis &x = axes[(size_t)ax[(size_t)i]], &y = axes[(size_t)ay[(size_t)i]];
+    hm_view_rec& r = rec[i];
+    std::memset(&r, 0, sizeof(r));
+    r.src = (uint64_t)(uintptr_t)((const uint8_t*)src + (size_t)vp.y * src_stride + (size_t)vp.x * obpp);
+    r.dst = (uint64_t)(uintptr_t)d.ptr;
+    r.row_pitch = pl.dp.row_pitch; r.plane_pitch = pl.dp.plane_pitch;
+    r.n_h = vp.h; r.ow = vp.ow; r.oh = vp.oh; r.E = chw ? vp.ow : vp.ow * C;
+    r.tmp_pitch = ((int64_t)r.E + 15) / 16 * 16; r.tmp_plane = r.tmp_pitch * vp.h; // (resample_args_of's intermediate: laid out like the destination)
+    r.x_first = (int32_t)x.off; r.x_count = (int32_t)(x.off + x.m); r.x_weights = (int32_t)(x.off + 2 * (int64_t)x.m);
+    r.y_first = (int32_t)y.off; r.y_count = (int32_t)(y.off + y.m); r.y_weights = (int32_t)(y.off + 2 * (int64_t)y.m);
+    bytes[(size_t)i] = (int64_t)vp.ow * vp.h * C * 4;
+    floats[(size_t)i] = r.tmp_plane * planes;
+    hg[(size_t)i] = hm_view_row_groups(vp.h); vg[(size_t)i] = hm_view_row_groups(vp.oh);
+    vec = vec && ((uintptr_t)d.ptr % 16) == 0 && (pl.dp.row_pitch % 16) == 0 && (!chw || (pl.dp.plane_pitch % 16) == 0);
+  }
+  // the chunks: the running sums and the regions of the intermediate restart with each
+  const int64_t bound = hm_knob(HM_KNOB_VIEW_BATCH_BYTES);
+  int64_t tmp_most = 0;
+  for (int c0 = 0; c0 < m;) {
+    const int n = hm_view_multi_chunk(bytes.data(), hg.data(), vg.data(), c0, m, bound);
+    int64_t off = 0;
+    int32_t h = 0, v = 0;
+    for (int i = c0; i < c0 + n; i++) {
+      rec[i].tmp_off = off; off += floats[(size_t)i];
+      hsum[i] = (h += hg[(size_t)i]); vsum[i] = (v += vg[(size_t)i]);
+    }
+    tmp_most = std::max(tmp_most, off);
+    c0 += n;
+  }
+  int rc;
+  if (!(sc->dev[0] = hm_pool_device_alloc((size_t)lay.bytes))) return HM_ERR_NO_DEVICE;
+  if (!(sc->dev[1] = hm_pool_device_alloc((size_t)tmp_most * sizeof(float)))) return HM_ERR_NO_DEVICE;
+  if ((rc = hm_check_hip(hipMemcpyAsync(sc->dev[0], host, (size_t)lay.bytes, hipMemcpyHostToDevice, s), "upload of the views' tap tables and records"))) return rc;
+  const uint8_t* dev = (const uint8_t*)sc->dev[0];
+  for (int c0 = 0; c0 < m;) {
+    const int n = hm_view_multi_chunk(bytes.data(), hg.data(), vg.data(), c0, m, bound);
+    hm_resample_multi a;
+    std::memset(&a, 0, sizeof(a));
+    a.block = dev;
+    a.recs = dev + lay.rec_off + (size_t)c0 * sizeof(hm_view_rec);
+    a.hsums = reinterpret_cast<const int32_t*>(dev + lay.hsum_off) + c0;
+    a.vsums = reinterpret_cast<const int32_t*>(dev + lay.vsum_off) + c0;
+    a.views = n;
+    a.sample_bytes = p0.sample_bytes; a.channels = C; a.src_stride = src_stride;
+    a.staged = staged ? 1 : 0; a.stage_px = hm_knob(HM_KNOB_VIEW_STAGE_PX);
+    a.vec = vec ? 1 : 0;
+    a.h_groups = hsum[c0 + n - 1]; a.v_groups = vsum[c0 + n - 1];
+    for (int i = c0; i < c0 + n; i++) { a.ow_most = std::max(a.ow_most, rec[i].ow); a.E_most = std::max(a.E_most, rec[i].E); }
+    a.tmp = (float*)sc->dev[1];
+    const hm_device_dest& d0 = dests[idx[0]];
+    if ((rc = hm_launch_resample_multi(&p0, &a, d0.scale, d0.bias, s))) return rc;
+    c0 += n;
+  }
+  return HM_OK;
+}
+} // namespace
+
+int hm_views_write(const hm_device_dest* dests, const hm_out_plan* plans, int n, const void* src, int src_stride, hipStream_t s, hm_view_scratch* sc)
+{
+  if (n <= 0) return HM_OK;
+  const bool multi = hm_knob(HM_KNOB_VIEW_MULTI) != 0;
+  std::vector<hm_view_multi_key> keys;
+  std::vector<std::vector<int>> members;
+  for (int k = 0; k < n; k++) {
+    const hm_out_plan& p = plans[k];
+    const bool plain = !p.has_light && !p.has_alpha && !p.has_gain;
+    if (!multi || !plain || p.vp.crop_only || !filter_resamples(p.vp.filter)) { // what exists, view by view, from the one picture
+      const int rc = hm_out_write(&dests[k], &p, src, src_stride, nullptr, s, &sc[k]);
+      if (rc) return rc;
+      continue;
+    }
+    const bool staged = (p.vp.filter == HM_VIEW_CUBIC || p.vp.filter == HM_VIEW_LANCZOS3) && hm_knob(HM_KNOB_VIEW_H_STAGED) != 0;
+    hm_view_multi_key key;
+    hm_view_multi_key_make(&key, staged, p.dp.sample_bytes, p.dp.channels, p.dp.layout, p.dp.dtype, p.dp.row_pitch, p.dp.plane_pitch, (uintptr_t)dests[k].ptr,
+                           p.dp.layout == HM_DEV_LAYOUT_CHW, dests[k].scale, dests[k].bias);
+    size_t g = 0;
+    while (g < keys.size() && !hm_view_multi_key_equal(&keys[g], &key)) g++;
+    if (g == keys.size()) { keys.push_back(key); members.emplace_back(); }
+    members[g].push_back(k);
+  }
+  for (size_t g = 0; g < members.size(); g++) { // (a group's blocks hang on the scratch entry of its first view: unused otherwise)
+    const std::vector<int>& m = members[g];
+    const int rc = views_write_group(dests, plans, m.data(), (int)m.size(), keys[g].staged != 0, src, src_stride, s, &sc[m[0]]);
+    if (rc) return rc;
+  }
+  return HM_OK;
+}
+
 // ---- the stand-alone entries: pixels that are in device memory already, through the same plan and writer ---------------------------
 
 // kind: the entry (hm_entry_steps.h) - this family leaves a null light step to hm_out_check_static, behind the alpha step's own refusals
@@ -1428,6 +1600,35 @@ int hm_to_tensor(int out_format, int width, int height, const void* d_src, int s
 int hm_resample_to_tensor(int out_format, int src_w, int src_h, const void* d_src, int src_stride, const hm_device_view* view, const hm_device_dest* dest, void* stream)
 {
   return out_to_tensor(HM_ENTRY_VIEW, out_format, 0, src_w, src_h, d_src, src_stride, {view}, dest, stream);
+}
+
+// the multi form of hm_resample_to_tensor: every view and destination is judged, in hm_resample_to_tensor's order, before anything is queued
+int hm_resample_views_to_tensor(int out_format, int src_w, int src_h, const void* d_src, int src_stride, const hm_device_view* views, const hm_device_dest* dests,
+                                int32_t count, void* stream)
+{
+  if (!d_src || !views || !dests) return hm_fail(HM_ERR_INVALID_ARG, "null argument");
+  if (count < 1 || count > HM_VIEWS_MOST) return hm_fail(HM_ERR_INVALID_ARG, "views: count %d outside 1 .. %d", count, (int)HM_VIEWS_MOST);
+  int rc;
+  if ((rc = check_image_size("", src_w, src_h))) return rc;
+  const hm_out_image img = {src_w, src_h, 0, 0, 0, 0, 0, 0};
+  std::vector<hm_out_plan> plans((size_t)count);
+  for (int k = 0; k < count; k++) {
+    const hm_out_steps st = {&views[k]};
+    if ((rc = hm_out_check_static(out_format, &dests[k], &st, 1)) || (rc = hm_out_resolve(out_format, &img, HM_OUT_PROFILE_FIRST, &dests[k], &st, &plans[(size_t)k])))
+      return hm_fail(rc, "view %d: %s", k, std::string(hm_last_error()).c_str());
+  }
+  if ((rc = hm_dests_check_overlap(dests, plans.data(), count))) return rc;
+  const int obpp = hm_out_bytes_per_pixel(out_format);
+  if (src_stride < src_w * obpp) return hm_fail(HM_ERR_INVALID_ARG, "src_stride %d below the bytes of a row", src_stride);
+  if (obpp >= 6 && (((uintptr_t)d_src | (unsigned)src_stride) & 1)) return hm_fail(HM_ERR_INVALID_ARG, "16-bit samples at an odd address or stride");
+  int n_dev = 0;
+  if (hipGetDeviceCount(&n_dev) != hipSuccess || n_dev == 0) { (void)hipGetLastError(); return hm_fail(HM_ERR_NO_DEVICE, "no HIP device available"); }
+  for (int k = 0; k < count; k++)
+    if ((rc = hm_dest_check_pointer(&dests[k]))) return hm_fail(rc, "view %d: %s", k, std::string(hm_last_error()).c_str());
+  std::vector<hm_view_scratch> sc((size_t)count, hm_view_scratch{{nullptr, nullptr}, nullptr});
+  rc = hm_views_write(dests, plans.data(), count, d_src, src_stride, (hipStream_t)stream, sc.data());
+  hm_view_scratch_retire((hipStream_t)stream, sc.data(), count); // (the blocks follow the stream, whatever was queued)
+  return rc;
 }
 
 int hm_light_to_tensor(int out_format, int bits, int src_w, int src_h, const void* d_src, int src_stride, const hm_device_view* view, const hm_device_light* light,

@@ -124,6 +124,20 @@ typedef struct hm_resample_batch {
   int64_t frame_stride;   // elements of the intermediate per frame
 } hm_resample_batch;
 int hm_launch_resample_batch(const hm_dest_plan* p, const hm_resample_args* a, const hm_resample_batch* b, const float scale[4], const float bias[4], hipStream_t s);
+// the views of one chunk of a multi-view write (hm_views_write; hm_view_multi.h holds the arithmetic): device pointers into the group's block
+typedef struct hm_resample_multi {
+  const void* block;                    // the group's block: every tap-table offset of a record counts 32-bit words from here
+  const void* recs;                     // hm_view_rec[views]: the chunk's first record
+  const int32_t* hsums; const int32_t* vsums; // the chunk's running sums of row groups, horizontal and vertical pass
+  int32_t views;
+  int32_t sample_bytes, channels, src_stride; // of the one source picture
+  int32_t staged, stage_px;             // as hm_resample_args
+  int32_t vec;                          // every destination of the group takes 16-byte stores
+  int32_t h_groups, v_groups;           // the chunk's last sums: gridDim.y of the passes
+  int32_t ow_most, E_most;              // of the chunk's widest view: gridDim.x
+  float* tmp;                           // the chunk's intermediate
+} hm_resample_multi;
+int hm_launch_resample_multi(const hm_dest_plan* p, const hm_resample_multi* m, const float scale[4], const float bias[4], hipStream_t s);
 int hm_launch_view_nearest(const hm_dest_plan* p, const void* src, int src_stride, int n_w, int n_h, int ow, int oh, void* dst, const float scale[4],
                            const float bias[4], hipStream_t s);
 
@@ -280,6 +294,21 @@ int hm_out_resolve(int out_format, const hm_out_image* img, int know_profile, co
 // `s`.  Tables and the intermediate hang on sc, which must be a free entry (it is not looked at where nothing is uploaded).
 // map: the gain map of an active gain step (p->gp.active), else NULL.
 int hm_out_write(const hm_device_dest* d, const hm_out_plan* p, const void* src, int src_stride, const hm_out_map* map, hipStream_t s, hm_view_scratch* sc);
+
+// ---- many views of one picture: n plans against the same image, n destinations ----
+// two destinations whose byte ranges overlap (plans[k].dp.bytes from dests[k].ptr: hm_dest_resolve's count, the pitches as resolved): the refusal names both
+int hm_dests_check_overlap(const hm_device_dest* dests, const hm_out_plan* plans, int n);
+// The views plans[0 .. n) of the image at `src` into dests[0 .. n); asynchronous on `s`.  One statement of the rule:
+//   - views whose plan has no step (plain code values) and whose filter is a resampling one are grouped by hm_view_multi_key - staged
+//     horizontal pass or not, sample_bytes, channels, layout, dtype, the 16-byte store instance, scale, bias - and a group goes to the
+//     multi kernels: one pinned block and one upload (every distinct tap table once, the views' records, the running sums), one
+//     bounded intermediate, and per chunk of views one launch per pass (hm_view_multi.h holds the arithmetic);
+//   - the crop alone and HM_VIEW_NEAREST stay one hm_out_write each, as hm_view_write_batch keeps them;
+//   - every view of a request with a light / tone / OOTF / alpha step stays one hm_out_write each too, from the one picture (fusing the
+//     stepped passes is a follow-up);
+//   - knob view_multi = 0: hm_out_write per view for everything.
+// The plans have been resolved and the destinations checked (overlap included) by the caller.  sc: n zeroed entries.
+int hm_views_write(const hm_device_dest* dests, const hm_out_plan* plans, int n, const void* src, int src_stride, hipStream_t s, hm_view_scratch* sc);
 
 // ---- the light statistics (hm_light_stats): the plan's rectangle - the view's crop at source resolution - of the interleaved pixels
 //      through the light step up to the tone step's search, counted.  devdest.cpp holds the tables and the host arithmetic, stats.hip the kernel ----

@@ -10,12 +10,14 @@
 enum hm_entry_kind { HM_ENTRY_DEST, HM_ENTRY_VIEW, HM_ENTRY_LIGHT, HM_ENTRY_TONE, HM_ENTRY_ALPHA, HM_ENTRY_OOTF, HM_ENTRY_GAIN, HM_ENTRY_PLANES, HM_ENTRY_PLANES_VIEW,
                      HM_ENTRY_ICC /* hm_icc_to_tensor: the light step, with a profile as its source */,
                      HM_ENTRY_STATS /* the light statistics: a light step, no destination of the caller's */,
-                     HM_ENTRY_MEASURED /* hm_decode_item_to_device_measured: light and tone steps, the peak measured */ };
+                     HM_ENTRY_MEASURED /* hm_decode_item_to_device_measured: light and tone steps, the peak measured */,
+                     HM_ENTRY_VIEWS /* hm_decode_item_to_device_views: many views of one item; every step may be NULL */ };
 
 // st: the step pointers the caller passed (those the entry does not have: NULL).  HM_OK, or the refusal:
 //   - the step the entry is named after must be given ("null argument"); every other step may be NULL.  An _ootf entry without an OOTF
 //     step is the same call without the step: the _alpha entry's rule if an alpha step is given, else the _tone entry's.
 //     The statistics entries are named after the light step; the measured entry needs the tone step beside it.
+//     The _views entry is named after its arrays, which it judges itself: it takes the steps as the _ootf entry does, each of them optional.
 //     view_may_be_null: the family's _view entry takes a NULL view (the frames family: it has no plain entry); a _planes_view entry never does.
 //   - a tone, gain or OOTF step needs a light step ("<step>: null light step", the OOTF step's before the tone step's).
 //     light_judged_later: the family leaves that to hm_out_check_static, which says it behind the alpha step's own refusals (the
@@ -32,6 +34,7 @@ inline int hm_entry_steps(int kind, const hm_out_steps& st, bool view_may_be_nul
                      : kind == HM_ENTRY_GAIN        ? st.gain != nullptr
                      : kind == HM_ENTRY_STATS       ? st.light != nullptr
                      : kind == HM_ENTRY_MEASURED    ? st.light != nullptr && st.tone != nullptr
+                     : kind == HM_ENTRY_VIEWS       ? !st.view && !st.gain
                                                     : true;
   if (!given) return hm_fail(HM_ERR_INVALID_ARG, "null argument");
   if (st.light || light_judged_later) return HM_OK;

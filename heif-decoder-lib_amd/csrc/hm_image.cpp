@@ -827,6 +827,23 @@ bool view_subgrid(const hm_file* f, uint32_t id, const hm_decode_params* params,
   return true;
 }
 
+// Many views: the bounding rectangle of all their crops as a view of the crop alone - what view_subgrid plans the decode of.
+// false: a view has no crop (it takes the whole image), or the rectangle does not fit the fields: nothing is reduced.
+static bool views_bound(const hm_device_view* views, int32_t count, hm_device_view* bound)
+{
+  int64_t x0 = INT64_MAX, y0 = INT64_MAX, x1 = INT64_MIN, y1 = INT64_MIN;
+  for (int32_t k = 0; k < count; k++) {
+    const hm_device_view& v = views[k];
+    if (v.crop_w <= 0 || v.crop_h <= 0 || v.crop_x < 0 || v.crop_y < 0) return false; // (no crop; or one the view's own check refuses)
+    x0 = std::min<int64_t>(x0, v.crop_x); y0 = std::min<int64_t>(y0, v.crop_y);
+    x1 = std::max<int64_t>(x1, (int64_t)v.crop_x + v.crop_w); y1 = std::max<int64_t>(y1, (int64_t)v.crop_y + v.crop_h);
+  }
+  if (count < 1 || x1 - x0 > INT32_MAX || y1 - y0 > INT32_MAX) return false;
+  std::memset(bound, 0, sizeof(*bound));
+  bound->crop_x = (int32_t)x0; bound->crop_y = (int32_t)y0; bound->crop_w = (int32_t)(x1 - x0); bound->crop_h = (int32_t)(y1 - y0);
+  return true;
+}
+
 // the depths of an 'unci' item's colour components: *lo / *hi = the smallest and the largest
 static void unci_colour_depths(const hm_unci_info& u, int* lo, int* hi)
 {
@@ -905,6 +922,11 @@ int job_plan(DecodeJob& j)
   // the gain map of a gain step joins the job as a third item - unless its weight is 0: the write is then the one without the step.
   // Tile reduction under a view stays off with a gain step (the open step: the map's crop would have to follow the sub-grid)
   j.has_map = false;
+  // the view the sub-grid is planned for: the request's, or with many views the bounding rectangle of all crops, taken as one crop - a
+  // synthetic view of the crop alone
+  hm_device_view bound;
+  const hm_device_view* plan_view = j.target.t.view;
+  if (j.target.t.views) plan_view = views_bound(j.target.t.views->views, j.target.t.views->count, &bound) ? &bound : nullptr;
   if (const hm_device_gain* g = j.target.t.gain) {
     if (hm_gain_weight(&g->params, g->headroom) != 0.0) {
       ItemPlan& M = j.item[2];
@@ -913,7 +935,7 @@ int job_plan(DecodeJob& j)
       j.has_map = true;
     }
   }
-  else if (j.target.t.view && view_subgrid(j.f, j.id, &j.params, j.target.t.view, j.sub_tiles, &sx, &sy, &sw, &sh, j.target.t.planes != nullptr)) {
+  else if (plan_view && view_subgrid(j.f, j.id, &j.params, plan_view, j.sub_tiles, &sx, &sy, &sw, &sh, j.target.t.planes != nullptr)) {
     const int32_t* t = j.sub_tiles;
     j.item[0] = j.item[0].sub_grid(t[0], t[1], t[2], t[3], sw, sh);
     j.view_dx = sx; j.view_dy = sy;
@@ -971,8 +993,10 @@ void parse_picture(const hm_file* f, uint32_t id, bool few_pictures, int strict,
 
 int target_check_shape(const OutputTarget& t)
 {
-  const bool ok = !(t.dest && t.planes) && (!t.light || t.dest) && (!t.tone || t.light) && (!t.ootf || t.light) &&(!t.alpha || (t.dest && !t.view_later)) && (!t.gain || (t.light && !t.view_later)) && (!t.view || t.dest || t.planes) && (!t.view_later || (t.view && t.dest)) &&
-                  (!t.planes_later || (t.view && t.planes));
+  const bool to_dest = t.dest || t.views; // (many views stand where dest stands)
+  const bool ok = !(t.dest && t.planes) && (!t.light || to_dest) && (!t.tone || t.light) && (!t.ootf || t.light) &&(!t.alpha || (to_dest && !t.view_later)) && (!t.gain || (t.light && !t.view_later)) && (!t.view || t.dest || t.planes) && (!t.view_later || (t.view && t.dest)) &&
+                  (!t.planes_later || (t.view && t.planes)) &&
+                  (!t.views || (!t.dest && !t.view && !t.planes && !t.gain && !t.measure && !t.view_later && !t.planes_later && t.views->views && t.views->dests && t.views->count >= 1));
   return ok ? (int)HM_OK : hm_fail(HM_ERR_INTERNAL, "output target: dest%s view%s planes%s light%s tone%s alpha%s gain%s do not go together", t.dest ? "+" : "-", t.view ? "+" : "-",
                                    t.planes ? "+" : "-", t.light ? "+" : "-", t.tone ? "+" : "-", t.alpha ? "+" : "-", t.gain ? "+" : "-");
 }
@@ -1008,6 +1032,29 @@ static Reported converted_report(const hm::NclxProfile& native, bool is_grid, in
   return r;
 }
 
+// a refusal that is view k's: its index goes where the caller looks, its message in front of the check's own
+static int view_refused(const ViewsRequest& V, int k, int rc)
+{
+  if (V.failed) *V.failed = k;
+  const std::string why = hm_last_error();
+  return hm_fail(rc, "view %d: %s", k, why.c_str());
+}
+
+// Many views against one image: plans[k] = the request with view k (moved by the decoded sub-grid's origin) against dests[k] - what the
+// single-view entry resolves, view by view -, then the destinations against each other
+static int views_resolve(const hm_decode_params* params, const OutputTarget& t, const hm_out_image& img, int know_profile, std::vector<hm_out_plan>& plans)
+{
+  const ViewsRequest& V = *t.views;
+  hm_out_steps st = t.steps();
+  int rc;
+  for (int k = 0; k < V.count; k++) {
+    const hm_device_view v = t.view_of(k);
+    st.view = &v;
+    if ((rc = hm_out_resolve(params->out_format, &img, know_profile, &V.dests[k], &st, &plans[(size_t)k]))) return view_refused(V, k, rc);
+  }
+  return hm_dests_check_overlap(V.dests, plans.data(), V.count);
+}
+
 // Can the target hold the result of a w x h image of (chroma, bits)?  The one statement of that question: the entry points ask it
 // against what the file declares, the sequence and emit_image again against the decoded picture.  A new kind of destination gets
 // its chain here.
@@ -1022,6 +1069,19 @@ static int target_fits(const hm_decode_params* params, const OutputTarget& t, in
 {
   int rc;
   const bool sized = w > 0 && h > 0;
+  if (t.views) { // every view against the image and its own destination, then the destinations against each other
+    const ViewsRequest& V = *t.views;
+    if (sized) {
+      const hm_out_image img = {w, h, reported ? reported->bit_depth : 0, reported ? reported->transfer : 0, reported ? reported->primaries : 0};
+      std::vector<hm_out_plan> plans((size_t)V.count);
+      if ((rc = views_resolve(params, t, img, reported ? HM_OUT_PROFILE_LAST : 0, plans))) return rc;
+    }
+    if (pointers) {
+      if ((rc = require_device())) return rc;
+      for (int k = 0; k < V.count; k++)
+        if ((rc = hm_dest_check_pointer(&V.dests[k]))) return view_refused(V, k, rc);
+    }
+  }
   if (t.dest) {
     if (sized) {
       const hm_out_steps st = t.steps();
@@ -1169,7 +1229,20 @@ static int emit_interleaved(const hm_decode_params* params, hipStream_t s, Plana
   out->bit_depth = r.bit_depth;
   out->stride[0] = cd.out_stride;
   out->plane_width[0] = img_w; out->plane_height[0] = img_h;
-  if (t.dest) { // the image, or with a view a rectangle of it at vp.ow x vp.oh, through the steps of the request and nothing else (devdest.cpp): the light and
+  if (t.views) { // many views of this one image: a plan per view, resolved against the profile and depth the image reports - every refusal before a byte
+                 // is written -, then the one writer of them all (hm_views_write: the multi kernels where the views allow them)
+    const ViewsRequest& V = *t.views;
+    const hm_out_image img = {img_w, img_h, r.bit_depth, r.transfer, r.primaries, 0, 0, 0};
+    std::vector<hm_out_plan> plans((size_t)V.count);
+    if ((rc = views_resolve(params, t, img, HM_OUT_PROFILE_LAST, plans))) return rc;
+    if ((rc = hm_views_write(V.dests, plans.data(), V.count, dout.p, cd.out_stride, s, V.scratch))) return rc;
+    for (int k = 0; k < V.count; k++) {
+      V.out[k].width = plans[(size_t)k].vp.ow; V.out[k].height = plans[(size_t)k].vp.oh;
+      V.out[k].stride[0] = (int32_t)std::min<int64_t>(plans[(size_t)k].dp.row_pitch, 0x7FFFFFFF);
+    }
+    out->used_ext_dst = 1;
+  }
+  else if (t.dest) { // the image, or with a view a rectangle of it at vp.ow x vp.oh, through the steps of the request and nothing else (devdest.cpp): the light and
                 // alpha steps resolved against the profile and depth this image reports - refused before a byte is written
     hm_out_steps st = t.steps();
     hm_out_image img = {img_w, img_h, r.bit_depth, r.transfer, r.primaries, 0, 0, 0};
@@ -1236,7 +1309,8 @@ int emit_image(const hm_decode_params* params, hipStream_t s, PlanarImage& I, co
   const bool planar_target = hm_out_is_planar(params->out_format);
   const bool as_decoded = params->out_format == 0 || (planar_target && I.chroma != 0 && I.chroma == hm_out_planar_chroma(params->out_format));
   // (planes are asked of the result's own format, by write_planes; the light step of the profile the conversion reports, by emit_interleaved)
-  if (t.dest && (rc = target_fits(params, t, I.w, I.h, I.chroma, I.bd, 0, nullptr, false))) return rc;
+  if ((t.dest || t.views) && (rc = target_fits(params, t, I.w, I.h, I.chroma, I.bd, 0, nullptr, false))) return rc;
+  if (t.views && (as_decoded || planar_target)) return hm_fail(HM_ERR_UNSUPPORTED, "views take an interleaved output format (HM_OUT_RGB ...): output format %d is a planar one", params->out_format);
   if (t.planes && !as_decoded && !planar_target) return hm_fail(HM_ERR_INTERNAL, "device planes with the interleaved output format %d", params->out_format);
   if (as_decoded) return emit_native(params, s, I, alpha, alpha_bd, t, out);
   if (planar_target) return emit_planar(params, s, I, alpha, alpha_bd, t, out);
@@ -1406,6 +1480,7 @@ int job_enqueue(DecodeJob& j, hm_decoded* out)
   hm_device_view shifted = j.target.view; // (the crop inside the sub-grid that was decoded)
   if (t.view && (shifted.crop_w || shifted.crop_h)) { shifted.crop_x -= j.view_dx; shifted.crop_y -= j.view_dy; }
   if (t.view) t.view = &shifted;
+  t.views_dx = j.view_dx; t.views_dy = j.view_dy; // (many views: each crop moves the same way, view by view)
   rc = emit_image(params, s, I, alpha, alpha_bd, j.dout, j.alpha_sdr, out, t);
   if (rc) return rc;
   lap("colour + D2H queued");
@@ -1434,6 +1509,16 @@ static int check_request_alone(const hm_decode_params* params, const OutputTarge
 {
   int rc = target_check_shape(t);
   if (rc) return rc;
+  if (t.views) { // what the single-view entry asks of a view's request, view by view
+    const ViewsRequest& V = *t.views;
+    if (params->ext_dst) return hm_fail(HM_ERR_INVALID_ARG, "params->ext_dst must be NULL with a device destination");
+    hm_out_steps st = t.steps();
+    for (int k = 0; k < V.count; k++) {
+      st.view = &V.views[k];
+      if ((rc = hm_out_check_static(params->out_format, &V.dests[k], &st, 0))) return view_refused(V, k, rc);
+      if (!V.dests[k].ptr) { hm_fail(HM_ERR_INVALID_ARG, "device destination: null ptr"); return view_refused(V, k, HM_ERR_INVALID_ARG); }
+    }
+  }
   if (t.dest) {
     if (params->ext_dst) return hm_fail(HM_ERR_INVALID_ARG, "params->ext_dst must be NULL with a device destination");
     const hm_out_steps st = t.steps();
@@ -2007,6 +2092,56 @@ int hm_decode_item_to_device_ootf(const hm_file* f, uint32_t id, const hm_decode
   return decode_item_to(HM_ENTRY_OOTF, f, id, params, {view, light, tone, alpha, nullptr, ootf}, dest, nullptr, out);
 }
 
+// Many views of one item: one request front, one decode, one writer (hm_views_write).  The arrays are the entry's to judge; the views
+// themselves go through the phases of check_target_request, which loops over them as a sequence loops over its frames.
+int hm_decode_item_to_device_views(const hm_file* f, uint32_t id, const hm_decode_params* params, const hm_device_view* views, const hm_device_dest* dests,
+                                   int32_t count, const hm_device_light* light, const hm_device_tone* tone, const hm_device_alpha* alpha, const hm_device_ootf* ootf,
+                                   hm_decoded* out, int32_t* failed_view)
+{
+  if (failed_view) *failed_view = -1;
+  if (!f || !params || !out || !views || !dests) return hm_fail(HM_ERR_INVALID_ARG, "null argument");
+  if (count < 1 || count > HM_VIEWS_MOST) return hm_fail(HM_ERR_INVALID_ARG, "views: count %d outside 1 .. %d", count, (int)HM_VIEWS_MOST);
+  const hm_out_steps st = {nullptr, light, tone, alpha, nullptr, ootf};
+  int rc = hm_entry_steps(HM_ENTRY_VIEWS, st);
+  if (rc) return rc;
+  const hm::Item* it = f->file.item(id);
+  if (it && it->is_raw_leaf())
+    return hm_fail(HM_ERR_UNSUPPORTED, "views: an uncompressed ('unci') or mask ('mski') item is not supported by hm_decode_item_to_device_views yet (its views upload by internal tile): "
+                                       "call hm_decode_item_to_device_view per view");
+  std::vector<hm_view_scratch> scratch((size_t)count, hm_view_scratch{{nullptr, nullptr}, nullptr});
+  ViewsRequest V;
+  V.views = views; V.dests = dests; V.count = count; V.out = out; V.scratch = scratch.data(); V.failed = failed_view;
+  OutputTarget asked;
+  asked.views = &V; asked.light = light; asked.tone = tone; asked.alpha = alpha; asked.ootf = ootf;
+  ResolvedRequest r;
+  if ((rc = resolve_request(f, id, params, asked, true, r))) return rc;
+  std::memset(out, 0, sizeof(*out) * (size_t)count);
+  hm_decoded one;
+  rc = decode_item(f, r.id, params, r.t, &one); // (it returns with the stream drained, whatever happened: the scratch entries are free to go)
+  for (hm_view_scratch& sc : scratch) hm_view_scratch_free(&sc);
+  if (rc) { std::memset(out, 0, sizeof(*out) * (size_t)count); return rc; }
+  for (int32_t k = 0; k < count; k++) { // the one decode's fields, with the sizes view k wrote
+    hm_decoded o = one;
+    o.width = out[k].width; o.height = out[k].height; o.stride[0] = out[k].stride[0];
+    o.plane_width[0] = o.width; o.plane_height[0] = o.height;
+    out[k] = o;
+  }
+  return HM_OK;
+}
+
+int hm_plan_views(const hm_file* f, uint32_t id, const hm_decode_params* params, const hm_device_view* views, int32_t count, int32_t tiles[4])
+{
+  if (!f || !params || !views || !tiles) return hm_fail(HM_ERR_INVALID_ARG, "null argument");
+  if (count < 1 || count > HM_VIEWS_MOST) return hm_fail(HM_ERR_INVALID_ARG, "views: count %d outside 1 .. %d", count, (int)HM_VIEWS_MOST);
+  const hm::Item* it = f->file.item(id);
+  if (!it) return hm_fail(HM_ERR_INVALID_ARG, "no item %u", id);
+  hm_device_view bound;
+  const bool reduced = !it->is_raw_leaf() && views_bound(views, count, &bound); // (an 'unci' item is refused by the entry: its whole grid)
+  int x0, y0, w, h;
+  view_subgrid(f, id, params, reduced ? &bound : nullptr, tiles, &x0, &y0, &w, &h);
+  return HM_OK;
+}
+
 // The entries that measure (include/heif_mi355x.h "Light statistics").  Everything that can be refused without a picture is refused
 // with *out and *stats as they were: resolve_request runs before anything is cleared.  tone: the caller's (the measured entry), else NULL.
 static int decode_item_measuring(int kind, const hm_file* f, uint32_t id, const hm_decode_params* params, const hm_device_view* view, const hm_device_light* light,
@@ -2423,7 +2558,7 @@ static int decode_item(const hm_file* f, uint32_t id, const hm_decode_params* pa
   if (is_derived_item(f, id)) return decode_derived(f, id, params, target, out);
   const hm::Item* item = f->file.item(id);
   const bool unci = item && item->is_raw_leaf(); // (a leaf without coded pictures: nothing to cut into slabs)
-  if (!unci && !target.view && !target.light && !target.alpha) { // (r06) a grid of more tiles than parsing threads, to interleaved pixels: slab by slab under the entropy decode (decode_grid_cut)
+  if (!unci && !target.view && !target.views && !target.light && !target.alpha) { // (r06) a grid of more tiles than parsing threads, to interleaved pixels: slab by slab under the entropy decode (decode_grid_cut)
     bool applicable = false;
     const int prc = decode_grid_cut(f, id, params, nullptr, 1, /*pipelined=*/true, out, &applicable, target.dest);
     if (prc || applicable) return prc;

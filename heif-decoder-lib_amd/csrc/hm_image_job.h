@@ -138,6 +138,17 @@ struct LightMeasure {
   hm_light_stats stats{};   // filled by emit_image
 };
 
+// Many views of one item (hm_decode_item_to_device_views): the caller's arrays - views[k] into dests[k], k < count -, out[k] for the sizes
+// written, count zeroed scratch entries the entry owns, and where the index of a view that was refused goes (may be NULL)
+struct ViewsRequest {
+  const hm_device_view* views = nullptr;
+  const hm_device_dest* dests = nullptr;
+  int32_t count = 0;
+  hm_decoded* out = nullptr;
+  hm_view_scratch* scratch = nullptr;
+  int32_t* failed = nullptr;
+};
+
 // Where the result of a decode goes beside hm_decoded: every function between an entry point and emit_image takes one of these.
 // All null: pinned host memory (or params->ext_dst).  The pointers are the caller's; target_check_shape states what goes together.
 // On the way in a target passes one front, each part of it stated once: of_entry (which pointers the entry's kind takes:
@@ -159,6 +170,14 @@ struct OutputTarget {
   hm_view_scratch* scratch = nullptr;          // tap tables and the intermediate of the resampling step, the tables of the light step
   hm_view_item* view_later = nullptr;          // view + dest: the view is not written, only described there - the caller writes it with those of other images
   hm_planes_view_item* planes_later = nullptr; // the same for view + planes
+  const ViewsRequest* views = nullptr;         // many views of the interleaved pixels, each into a destination of its own (in place of dest and view)
+  int views_dx = 0, views_dy = 0;              // ... the origin of the sub-grid that was decoded: every crop moves by it (job_enqueue sets it)
+  hm_device_view view_of(int k) const          // view k of `views` as the decoded image sees it
+  {
+    hm_device_view v = views->views[k];
+    if (v.crop_w || v.crop_h) { v.crop_x -= views_dx; v.crop_y -= views_dy; }
+    return v;
+  }
   // the target of a device entry of `kind` (hm_entry_kind): its destination - d or p, whichever the entry has - with the step pointers
   // the caller passed, or the refusal ("null argument" for a null destination, else hm_entry_steps')
   static int of_entry(int kind, const hm_out_steps& st, const hm_device_dest* d, const hm_device_planes* p, OutputTarget& t,
@@ -173,6 +192,7 @@ struct OutputTarget {
   }
   hm_out_steps steps() const { return hm_out_steps{view, light, tone, alpha, gain, ootf, icc, icc_size, measure ? measure->mode : (int)HM_MEASURE_NONE}; } // the request of the device write (hm_devdest.h)
 };
+// views excludes dest, view, planes, gain, measure and both *_later, and stands where dest stands for light and alpha;
 // dest xor planes (or neither); light only with dest; tone only with light; ootf only with light; alpha only with dest and never with view_later; gain only with light and
 // never with view_later; view only with one of the two; a *_later only with view and its own kind of destination
 int target_check_shape(const OutputTarget& t);
@@ -205,6 +225,7 @@ struct OwnedTarget {
     if (from.ootf) { ootf = *from.ootf; t.ootf = &ootf; }
     t.icc = from.icc; t.icc_size = from.icc_size; // (the file's bytes: the job holds the file)
     t.measure = from.measure;
+    t.views = from.views; // (the caller's arrays: the item entry returns before they go)
   }
 };
 

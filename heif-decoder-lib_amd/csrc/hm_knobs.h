@@ -33,6 +33,7 @@ extern "C" {
 //   view_stage_px (0)      > 0: k_resample_h_staged stages at most that many pixels per chunk (tests: several chunks on a short row)
 //   view_batch (1)         0: a sequence under a view (hm_decode_frames_to_device_view) runs hm_out_write once per frame (A/B measurements, tests)
 //   view_batch_bytes (0)   > 0: the bound of a batched view write's intermediate in bytes (0: 64 MiB; tests: several chunks on small frames)
+//   view_multi (1)         0: many views of one picture (hm_decode_item_to_device_views, hm_resample_views_to_tensor) run hm_out_write once per view (A/B measurements, tests)
 //   overlap_min_pics (0)   > 0: hm_batch_execute's automatic overlap (hm_overlap_plan.h) engages from that many pictures on, whatever cut the chain launcher takes
 //   overlap_cut (0)        > 0: the image index at which the automatic overlap cuts the batch into its two groups
 //   overlay_start (1)      0: k_overlay walks every layer from the bottom (no start layer per span: tests compare the two)
@@ -41,7 +42,7 @@ enum hm_knob_id { HM_KNOB_CHAIN_SPIN_LIMIT, HM_KNOB_CHAIN_TEST_STALL, HM_KNOB_BA
                   HM_KNOB_CHAIN_ALT, HM_KNOB_CHAIN_NP, HM_KNOB_CHAIN_DEBUG, HM_KNOB_RESID_SEGS, HM_KNOB_RECON_WAVES, HM_KNOB_QUAD_CLASS, HM_KNOB_TAIL_FUSED,
                   HM_KNOB_STREAM_INTERLEAVED, HM_KNOB_CHAIN_SPLIT, HM_KNOB_TAIL_HDR16, HM_KNOB_CHAIN_EARLY, HM_KNOB_GRID_SLAB_ROWS, HM_KNOB_VIEW_H_STAGED,
                   HM_KNOB_VIEW_STAGE_PX, HM_KNOB_VIEW_BATCH, HM_KNOB_VIEW_BATCH_BYTES, HM_KNOB_OVERLAP_MIN_PICS,
-                  HM_KNOB_OVERLAP_CUT, HM_KNOB_OVERLAY_START, HM_KNOB_STATS_GROUPS, HM_KNOB_COUNT };
+                  HM_KNOB_OVERLAP_CUT, HM_KNOB_OVERLAY_START, HM_KNOB_STATS_GROUPS, HM_KNOB_VIEW_MULTI, HM_KNOB_COUNT };
 int hm_knob(int id);
 int hm_knob_set(const char* name, int value); // 0, or -1 for an unknown name (hidden: reached through test_hooks.cpp's hm_debug_set only)
 #ifdef __cplusplus

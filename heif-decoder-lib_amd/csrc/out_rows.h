@@ -21,13 +21,14 @@
 // SB: bytes per source sample (little-endian), C: channels, CHW: the intermediate has one plane per channel.  to_float(v, c): sample v
 // of channel c as the float the sum takes.  grid: x = groups of 64 output columns, y = groups of 4 source rows.  src points at the
 // crop's origin.
+// by: the workgroup's group of 4 source rows - blockIdx.y, or its place inside its own view where a launch covers several (k_resample_h_multi).
 template <int SB, int C, bool CHW, typename ToFloat>
-__device__ __forceinline__ void resample_h_body(const uint8_t* __restrict__ src, int src_stride, int n_h, int ow, const int32_t* __restrict__ first,
+__device__ __forceinline__ void resample_h_rows(int by, const uint8_t* __restrict__ src, int src_stride, int n_h, int ow, const int32_t* __restrict__ first,
                                                 const int32_t* __restrict__ count, const float* __restrict__ wts, float* __restrict__ tmp,
                                                 long long pitch, long long plane, ToFloat to_float)
 {
   typedef typename std::conditional<SB == 1, uint8_t, uint16_t>::type InT;
-  const int j = blockIdx.x * 64 + (threadIdx.x & 63), y = blockIdx.y * 4 + (threadIdx.x >> 6);
+  const int j = blockIdx.x * 64 + (threadIdx.x & 63), y = by * 4 + (threadIdx.x >> 6);
   if (j >= ow || y >= n_h) return;
   const InT* in = reinterpret_cast<const InT*>(src + (size_t)y * src_stride) + (size_t)first[j] * C;
   const int n = count[j];
@@ -48,6 +49,14 @@ __device__ __forceinline__ void resample_h_body(const uint8_t* __restrict__ src,
     if (CHW) o[(long long)c * plane + j] = t[c];
     else o[(size_t)j * C + c] = t[c];
   }
+}
+
+template <int SB, int C, bool CHW, typename ToFloat>
+__device__ __forceinline__ void resample_h_body(const uint8_t* __restrict__ src, int src_stride, int n_h, int ow, const int32_t* __restrict__ first,
+                                                const int32_t* __restrict__ count, const float* __restrict__ wts, float* __restrict__ tmp,
+                                                long long pitch, long long plane, ToFloat to_float)
+{
+  resample_h_rows<SB, C, CHW>((int)blockIdx.y, src, src_stride, n_h, ow, first, count, wts, tmp, pitch, plane, to_float);
 }
 
 // the plain sample-to-float step

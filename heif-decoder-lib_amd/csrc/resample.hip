@@ -9,12 +9,16 @@
 //                    group is 16 bytes of output (one 16-byte store) where pointer and pitches allow, one element otherwise.
 //   k_resample_h_batch, k_resample_h_staged_batch, k_resample_v_batch  the same three passes over the frames of a sequence in one launch
 //                    each (grid z): the per-frame pointers come from arrays, everything else is shared.  Same sums, same order, same bytes.
+//   k_resample_h_multi, k_resample_h_staged_multi, k_resample_v_multi  the same three passes over MANY views of ONE picture in one launch
+//                    each (hm_views_write): blockIdx.y is cut by running sums over the views' row groups, and a workgroup reads crop,
+//                    sizes, tap tables, its region of the intermediate and its destination from its view's record.  Same bodies.
 //   k_view_nearest   HM_VIEW_NEAREST: the sample at j * n / m is moved (through scale and bias for float destinations), no intermediate.
 // The sums run tap by tap in float32 with separately rounded multiply and add (-ffp-contract=off, __fmul_rn / __fadd_rn): a float32
 // restatement on the host is exact.  A sum becomes an element by `finish`, a sample that is only moved by `moved` (out_elem.h).
 // Nothing but the out_w x out_h x C elements of the view is ever stored.
 #include "hm_devdest.h"
 #include "hm_view_batch.h"
+#include "hm_view_multi.h"
 #include "out_launch.h"
 #include "out_rows.h"
 
@@ -64,14 +68,14 @@ static_assert(STAGE_ROW <= STAGE_ROW_PITCH && STAGE_DATA % 128 == 0 && STAGE_ROW
 __device__ __forceinline__ int stage_at(int b) { return b + ((b >> 7) << 2); }
 
 template <int SB, int C, bool CHW>
-__device__ __forceinline__ void resample_h_staged_body(uint8_t* lds, const uint8_t* __restrict__ src, int src_stride, int n_h, int ow,
+__device__ __forceinline__ void resample_h_staged_body(int by, uint8_t* lds, const uint8_t* __restrict__ src, int src_stride, int n_h, int ow,
                                                        const int32_t* __restrict__ first, const int32_t* __restrict__ count, const float* __restrict__ wts,
                                                        float* __restrict__ tmp, long long pitch, long long plane, int chunk_px)
 {
   typedef typename std::conditional<SB == 1, uint8_t, uint16_t>::type InT;
   constexpr int PB = SB * C; // bytes per pixel
   const int lane = threadIdx.x & 63, wv = threadIdx.x >> 6;
-  const int j0 = blockIdx.x * 64, j = j0 + lane, y = blockIdx.y * 4 + wv;
+  const int j0 = blockIdx.x * 64, j = j0 + lane, y = by * 4 + wv; // (by: blockIdx.y, or the row group inside its view: k_resample_h_staged_multi)
   const int jl = min(j0 + 63, ow - 1);
   const int p_end = first[jl] + count[jl]; // (the same in every lane of the workgroup, as p below)
   int p = first[j0];
@@ -154,7 +158,7 @@ __global__ __launch_bounds__(256) void k_resample_h_staged(const uint8_t* __rest
                                                            long long pitch, long long plane, int chunk_px)
 {
   __shared__ __attribute__((aligned(16))) uint8_t lds[4 * STAGE_ROW_PITCH];
-  resample_h_staged_body<SB, C, CHW>(lds, src, src_stride, n_h, ow, first, count, wts, tmp, pitch, plane, chunk_px);
+  resample_h_staged_body<SB, C, CHW>((int)blockIdx.y, lds, src, src_stride, n_h, ow, first, count, wts, tmp, pitch, plane, chunk_px);
 }
 
 // The batched form: blockIdx.z is the frame within the chunk, its source origin a scalar load from the pointer array before
@@ -173,7 +177,7 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(8))) void k
 {
   __shared__ __attribute__((aligned(16))) uint8_t lds[4 * STAGE_ROW_PITCH];
   const uint8_t* src = (const uint8_t*)(const GlobalBytes*)reinterpret_cast<const uintptr_t*>(srcs)[blockIdx.z];
-  resample_h_staged_body<SB, C, CHW>(lds, src, src_stride, n_h, ow, first, count, wts, tmp + (long long)blockIdx.z * frame_stride, pitch, plane, chunk_px);
+  resample_h_staged_body<SB, C, CHW>((int)blockIdx.y, lds, src, src_stride, n_h, ow, first, count, wts, tmp + (long long)blockIdx.z * frame_stride, pitch, plane, chunk_px);
 }
 
 // P: elements of one row per lane (16 bytes of output, or 1), C: channels of an interleaved row (HWC), 0 = one plane per channel
@@ -181,11 +185,11 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(8))) void k
 // output rows, z = planes.  The intermediate's pitch is a multiple of 16 elements, so a ragged last group loads whole vectors
 // (of padding nobody stores).
 template <typename OutT, int P, int C>
-__device__ __forceinline__ void resample_v_body(int pl, const float* __restrict__ tmp, long long pitch, long long plane, int E, int oh,
+__device__ __forceinline__ void resample_v_body(int by, int pl, const float* __restrict__ tmp, long long pitch, long long plane, int E, int oh,
                                                 const int32_t* __restrict__ first, const int32_t* __restrict__ count, const float* __restrict__ wts,
                                                 uint8_t* __restrict__ dst, long long row_pitch, long long plane_pitch, const Affine& a)
 {
-  const int k = blockIdx.y * 4 + (threadIdx.x >> 6);
+  const int k = by * 4 + (threadIdx.x >> 6); // (by: blockIdx.y, or the row group inside its view: k_resample_v_multi)
   if (k >= oh) return;
   const int e0 = (blockIdx.x * 64 + (threadIdx.x & 63)) * P;
   if (e0 >= E) return;
@@ -230,7 +234,7 @@ __global__ __launch_bounds__(256) void k_resample_v(const float* __restrict__ tm
                                                     const int32_t* __restrict__ first, const int32_t* __restrict__ count, const float* __restrict__ wts,
                                                     uint8_t* __restrict__ dst, long long row_pitch, long long plane_pitch, Affine a)
 {
-  resample_v_body<OutT, P, C>((int)blockIdx.z, tmp, pitch, plane, E, oh, first, count, wts, dst, row_pitch, plane_pitch, a);
+  resample_v_body<OutT, P, C>((int)blockIdx.y, (int)blockIdx.z, tmp, pitch, plane, E, oh, first, count, wts, dst, row_pitch, plane_pitch, a);
 }
 
 // The batched form: blockIdx.z = frame * planes + plane (planes: the channels of a CHW destination, 1 for HWC).  The frame's
@@ -246,7 +250,69 @@ __global__ __launch_bounds__(256) void k_resample_v_batch(const float* __restric
   int fr = blockIdx.z, pl = 0;
   if (C == 0) hm_view_z_split((int)blockIdx.z, planes, &fr, &pl);
   uint8_t* dst = (uint8_t*)(GlobalBytes*)reinterpret_cast<const uintptr_t*>(dsts)[fr];
-  resample_v_body<OutT, P, C>(pl, tmp + (long long)fr * frame_stride, pitch, plane, E, oh, first, count, wts, dst, row_pitch, plane_pitch, a);
+  resample_v_body<OutT, P, C>((int)blockIdx.y, pl, tmp + (long long)fr * frame_stride, pitch, plane, E, oh, first, count, wts, dst, row_pitch, plane_pitch, a);
+}
+
+// ---- many views of one picture (hm_views_write): the multi forms ----
+// A launch covers the views of one chunk.  `block` is the group's block (hm_view_multi.h): the tap tables of every view, the records,
+// the running sums; recs and sums point at the chunk's first record and first sum, n is its view count.  blockIdx.y runs over the row
+// groups of all the chunk's views one behind the other; hm_view_of_y finds the view by bisection over the sums.  That search, and the
+// record's address, depend on blockIdx.y alone: the loads are scalar ones into SGPRs, made once per workgroup, before the tap loop
+// (the reasoning of k_resample_h_batch).  The pointers inside a record are read as pointers to global memory (GlobalBytes), so the
+// loads and stores through them stay global ones.  blockIdx.x is sized for the widest view of the chunk: the workgroups beyond their
+// own view's width return before any load.
+struct MultiView { const hm_view_rec* r; int by; };
+__device__ __forceinline__ MultiView multi_view_of(const hm_view_rec* __restrict__ recs, const int32_t* __restrict__ sums, int n)
+{
+  int32_t local;
+  const int v = hm_view_of_y(sums, n, (int32_t)blockIdx.y, &local);
+  return MultiView{recs + v, (int)local};
+}
+
+template <int SB, int C, bool CHW>
+__global__ __launch_bounds__(256) void k_resample_h_multi(const int32_t* __restrict__ block, const hm_view_rec* __restrict__ recs, const int32_t* __restrict__ sums, int n,
+                                                          int src_stride, float* __restrict__ tmp)
+{
+  const MultiView m = multi_view_of(recs, sums, n);
+  const hm_view_rec* r = m.r;
+  const int ow = r->ow;
+  if ((int)blockIdx.x * 64 >= ow) return;
+  const uint8_t* src = (const uint8_t*)(const GlobalBytes*)r->src;
+  resample_h_rows<SB, C, CHW>(m.by, src, src_stride, r->n_h, ow, block + r->x_first, block + r->x_count, reinterpret_cast<const float*>(block + r->x_weights),
+                              tmp + r->tmp_off, r->tmp_pitch, r->tmp_plane, SampleToFloat());
+}
+
+// The staged body has barriers: its early return must be taken by the whole workgroup or by none of it.  A workgroup is four rows of
+// the SAME 64 columns (blockIdx.x * 64 ..), and its view is one (blockIdx.y decides it): the condition below is workgroup-uniform.
+// Behind it the trip counts depend on the workgroup's columns and its view's tables alone, as in k_resample_h_staged.
+// waves_per_eu(8): as k_resample_h_staged_batch.
+template <int SB, int C, bool CHW>
+__global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(8))) void k_resample_h_staged_multi(const int32_t* __restrict__ block, const hm_view_rec* __restrict__ recs,
+                                                                 const int32_t* __restrict__ sums, int n, int src_stride, float* __restrict__ tmp, int chunk_px)
+{
+  __shared__ __attribute__((aligned(16))) uint8_t lds[4 * STAGE_ROW_PITCH];
+  const MultiView m = multi_view_of(recs, sums, n);
+  const hm_view_rec* r = m.r;
+  const int ow = r->ow;
+  if ((int)blockIdx.x * 64 >= ow) return;
+  const uint8_t* src = (const uint8_t*)(const GlobalBytes*)r->src;
+  resample_h_staged_body<SB, C, CHW>(m.by, lds, src, src_stride, r->n_h, ow, block + r->x_first, block + r->x_count, reinterpret_cast<const float*>(block + r->x_weights),
+                                     tmp + r->tmp_off, r->tmp_pitch, r->tmp_plane, chunk_px);
+}
+
+// blockIdx.z is the channel for CHW destinations (C == 0), as in k_resample_v.  Scale, bias and the store width P are those of the
+// whole launch: hm_views_write groups views by them.
+template <typename OutT, int P, int C>
+__global__ __launch_bounds__(256) void k_resample_v_multi(const int32_t* __restrict__ block, const hm_view_rec* __restrict__ recs, const int32_t* __restrict__ sums, int n,
+                                                          const float* __restrict__ tmp, Affine a)
+{
+  const MultiView m = multi_view_of(recs, sums, n);
+  const hm_view_rec* r = m.r;
+  const int E = r->E;
+  if ((int)blockIdx.x * 64 * P >= E) return;
+  uint8_t* dst = (uint8_t*)(GlobalBytes*)r->dst;
+  resample_v_body<OutT, P, C>(m.by, (int)blockIdx.z, tmp + r->tmp_off, r->tmp_pitch, r->tmp_plane, E, r->oh, block + r->y_first, block + r->y_count,
+                              reinterpret_cast<const float*>(block + r->y_weights), dst, r->row_pitch, r->plane_pitch, a);
 }
 
 // HM_VIEW_NEAREST: out pixel (j, k) is source pixel (j * n_w / ow, k * n_h / oh).  grid: x = groups of 64 columns, y = groups of 4 rows.
@@ -295,6 +361,19 @@ const void* const g_batch_instances[] = {
   HM_VB_SET(uint8_t), HM_VB_SET(uint16_t), HM_VB_SET(__half), HM_VB_SET(float),
 };
 #undef HM_VB_SET
+
+// ... and of the multi forms (hm_views_write), a list of its own (hm_debug_kernel_regs, code 14): 8 horizontal, 8 staged, 24 vertical
+#define HM_VM_SET(T) \
+  (const void*)k_resample_v_multi<T, 16 / (int)sizeof(T), 0>, (const void*)k_resample_v_multi<T, 16 / (int)sizeof(T), 3>, (const void*)k_resample_v_multi<T, 16 / (int)sizeof(T), 4>, \
+  (const void*)k_resample_v_multi<T, 1, 0>, (const void*)k_resample_v_multi<T, 1, 3>, (const void*)k_resample_v_multi<T, 1, 4>
+const void* const g_multi_instances[] = {
+  (const void*)k_resample_h_multi<1, 3, true>, (const void*)k_resample_h_multi<1, 3, false>, (const void*)k_resample_h_multi<1, 4, true>, (const void*)k_resample_h_multi<1, 4, false>,
+  (const void*)k_resample_h_multi<2, 3, true>, (const void*)k_resample_h_multi<2, 3, false>, (const void*)k_resample_h_multi<2, 4, true>, (const void*)k_resample_h_multi<2, 4, false>,
+  (const void*)k_resample_h_staged_multi<1, 3, true>, (const void*)k_resample_h_staged_multi<1, 3, false>, (const void*)k_resample_h_staged_multi<1, 4, true>, (const void*)k_resample_h_staged_multi<1, 4, false>,
+  (const void*)k_resample_h_staged_multi<2, 3, true>, (const void*)k_resample_h_staged_multi<2, 3, false>, (const void*)k_resample_h_staged_multi<2, 4, true>, (const void*)k_resample_h_staged_multi<2, 4, false>,
+  HM_VM_SET(uint8_t), HM_VM_SET(uint16_t), HM_VM_SET(__half), HM_VM_SET(float),
+};
+#undef HM_VM_SET
 
 template <int SB, int C>
 void launch_h(bool chw, const hm_resample_args* r, hipStream_t s)
@@ -396,7 +475,47 @@ void launch_v_batch(const hm_dest_plan* p, const hm_resample_args* r, const hm_r
   else { if (vec) launch_v_batch_inst<OutT, P, 4>(p, r, b, a, s); else launch_v_batch_inst<OutT, 1, 4>(p, r, b, a, s); }
 }
 
+// the multi launches: grid x = the widest view of the chunk, y = the row groups of all its views, z = planes (vertical, CHW)
+template <int SB, int C>
+void launch_h_multi(bool chw, const hm_resample_multi* m, hipStream_t s)
+{
+  const dim3 grid((unsigned)((m->ow_most + 63) / 64), (unsigned)m->h_groups), block(256);
+  const int32_t* blk = (const int32_t*)m->block;
+  const hm_view_rec* recs = (const hm_view_rec*)m->recs;
+  if (m->staged) {
+    constexpr int most = (STAGE_DATA - 15) / (SB * C); // (as launch_h_staged)
+    const int chunk_px = m->stage_px > 0 && m->stage_px < most ? m->stage_px : most;
+    if (chw) hipLaunchKernelGGL((k_resample_h_staged_multi<SB, C, true>), grid, block, 0, s, blk, recs, m->hsums, m->views, m->src_stride, m->tmp, chunk_px);
+    else hipLaunchKernelGGL((k_resample_h_staged_multi<SB, C, false>), grid, block, 0, s, blk, recs, m->hsums, m->views, m->src_stride, m->tmp, chunk_px);
+  }
+  else if (chw) hipLaunchKernelGGL((k_resample_h_multi<SB, C, true>), grid, block, 0, s, blk, recs, m->hsums, m->views, m->src_stride, m->tmp);
+  else hipLaunchKernelGGL((k_resample_h_multi<SB, C, false>), grid, block, 0, s, blk, recs, m->hsums, m->views, m->src_stride, m->tmp);
+}
+
+template <typename OutT, int P, int C>
+void launch_v_multi_inst(const hm_dest_plan* p, const hm_resample_multi* m, const Affine& a, hipStream_t s)
+{
+  const int groups = (m->E_most + P - 1) / P;
+  const dim3 grid((unsigned)((groups + 63) / 64), (unsigned)m->v_groups, (unsigned)(C == 0 ? p->channels : 1)), block(256);
+  hipLaunchKernelGGL((k_resample_v_multi<OutT, P, C>), grid, block, 0, s, (const int32_t*)m->block, (const hm_view_rec*)m->recs, m->vsums, m->views, (const float*)m->tmp, a);
+}
+
+template <typename OutT>
+void launch_v_multi(const hm_dest_plan* p, const hm_resample_multi* m, const Affine& a, hipStream_t s)
+{
+  constexpr int P = 16 / (int)sizeof(OutT);
+  const bool chw = p->layout == HM_DEV_LAYOUT_CHW, vec = m->vec != 0;
+  if (chw) { if (vec) launch_v_multi_inst<OutT, P, 0>(p, m, a, s); else launch_v_multi_inst<OutT, 1, 0>(p, m, a, s); }
+  else if (p->channels == 3) { if (vec) launch_v_multi_inst<OutT, P, 3>(p, m, a, s); else launch_v_multi_inst<OutT, 1, 3>(p, m, a, s); }
+  else { if (vec) launch_v_multi_inst<OutT, P, 4>(p, m, a, s); else launch_v_multi_inst<OutT, 1, 4>(p, m, a, s); }
+}
+
 } // namespace
+
+extern "C" const void* hm_resample_multi_kernel_of(int index) // (test_hooks.cpp: hm_debug_kernel_regs)
+{
+  return index >= 0 && index < (int)(sizeof(g_multi_instances) / sizeof(g_multi_instances[0])) ? g_multi_instances[index] : nullptr;
+}
 
 extern "C" const void* hm_resample_kernel_of(int index) // (test_hooks.cpp: hm_debug_kernel_regs)
 {
@@ -452,6 +571,25 @@ extern "C" int hm_launch_resample_batch(const hm_dest_plan* p, const hm_resample
   const int found = with_dtype(p->dtype, [&](auto tag) -> int { launch_v_batch<typename decltype(tag)::type>(p, r, b, a, s); return HM_OK; });
   if (found == NO_KERNEL_INSTANCE) return hm_fail(HM_ERR_INTERNAL, "k_resample_v: no kernel for dtype %d", p->dtype);
   return hm_check_hip(hipGetLastError(), "k_resample_v_batch launch");
+}
+
+// both passes over the m->views views of one chunk (hm_views_write): p is the plan of any view of the group - layout, dtype and channels
+// are the group's, its pitches are not looked at (the records hold every view's)
+extern "C" int hm_launch_resample_multi(const hm_dest_plan* p, const hm_resample_multi* m, const float scale[4], const float bias[4], hipStream_t s)
+{
+  if (m->views <= 0) return HM_OK;
+  if (m->h_groups <= 0 || m->v_groups <= 0 || m->h_groups > HM_VIEW_MULTI_Y_MOST || m->v_groups > HM_VIEW_MULTI_Y_MOST || m->ow_most <= 0 || m->E_most <= 0)
+    return hm_fail(HM_ERR_INTERNAL, "k_resample_multi: %d and %d row groups in one launch", m->h_groups, m->v_groups);
+  if (((uintptr_t)m->tmp % 16) || ((uintptr_t)m->recs % 8) || ((uintptr_t)m->block % 8)) return hm_fail(HM_ERR_INTERNAL, "k_resample_multi: misaligned block or intermediate");
+  const bool chw = p->layout == HM_DEV_LAYOUT_CHW;
+  if (m->sample_bytes == 1) { if (m->channels == 3) launch_h_multi<1, 3>(chw, m, s); else launch_h_multi<1, 4>(chw, m, s); }
+  else { if (m->channels == 3) launch_h_multi<2, 3>(chw, m, s); else launch_h_multi<2, 4>(chw, m, s); }
+  int rc = hm_check_hip(hipGetLastError(), "k_resample_h_multi launch");
+  if (rc) return rc;
+  const Affine a = affine_of(scale, bias);
+  const int found = with_dtype(p->dtype, [&](auto tag) -> int { launch_v_multi<typename decltype(tag)::type>(p, m, a, s); return HM_OK; });
+  if (found == NO_KERNEL_INSTANCE) return hm_fail(HM_ERR_INTERNAL, "k_resample_v: no kernel for dtype %d", p->dtype);
+  return hm_check_hip(hipGetLastError(), "k_resample_v_multi launch");
 }
 
 extern "C" int hm_launch_view_nearest(const hm_dest_plan* p, const void* src, int src_stride, int n_w, int n_h, int ow, int oh, void* dst, const float scale[4],

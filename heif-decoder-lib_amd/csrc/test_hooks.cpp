@@ -21,6 +21,7 @@ extern "C" const void* hm_tail420_kernel16();
 extern "C" const void* hm_resample_kernel_of(int index);                                    // resample.hip: NULL behind the last instance
 extern "C" const void* hm_resample_staged_kernel_of(int index);                             // ... the instances of k_resample_h_staged
 extern "C" const void* hm_resample_batch_kernel_of(int index);                              // ... the batched forms of all three passes
+extern "C" const void* hm_resample_multi_kernel_of(int index);                              // ... the multi forms of all three passes
 extern "C" const void* hm_planes_view_kernel_of(int index);                                 // planes_view.hip: NULL behind the last instance
 extern "C" const void* hm_overlay_kernel_of(int index);                                     // overlay.hip: NULL behind the last instance
 extern "C" const void* hm_light_kernel_of(int index);                                       // light.hip: NULL behind the last instance
@@ -64,6 +65,7 @@ __attribute__((visibility("default"))) int hm_debug_kernel_regs(int which, int a
   else if (which == 11) fn = hm_alpha_kernel_of(a); // (k_alpha_tensor, k_alpha_nearest, k_alpha_h, k_alpha_v; out[1] counts scratch, not LDS)
   else if (which == 12) fn = hm_gain_kernel_of(a); // (k_gain_tensor, k_gain_nearest, k_gain_map_h, k_gain_map_v, k_gain_v; out[1] counts scratch, not LDS)
   else if (which == 13) fn = hm_stats_kernel_of(a); // (k_light_stats; out[1] counts scratch, not LDS)
+  else if (which == 14) fn = hm_resample_multi_kernel_of(a); // (k_resample_h_multi, k_resample_h_staged_multi, k_resample_v_multi; out[1] counts scratch, not LDS)
   hipFuncAttributes fa;
   if (!fn || !out || hipFuncGetAttributes(&fa, fn) != hipSuccess) return -1;
   out[0] = fa.numRegs;

@@ -3,6 +3,7 @@
     img = decode_to_tensor(open("a.heic", "rb").read())                           # 3 x H x W float32
     batch = decode_batch_to_tensor(files, dtype=torch.float16, scale=1 / 255)     # N x 3 x H x W
     clip = decode_sequence_to_tensor(movie, frames=range(1, 65, 4), size=(224, 224))   # 16 x 3 x 224 x 224
+    crops = decode_to_views(data, [(c, (96, 96)) for c in boxes])                 # a list of 3 x 96 x 96: ONE decode, many crops
 
 Layouts: "chw" (one plane per channel) and "hwc" (the target's own interleaving).  dtypes: torch.uint8 / torch.uint16 (must be
 the target's own sample type: 8-bit "rgb" / "rgba", 16-bit "rrggbb_le" / "rrggbbaa_le" ...), torch.float16, torch.float32;
@@ -467,6 +468,111 @@ def decode_to_tensor(data, item_id=0, out_format="rgb", layout="chw", dtype=None
         return out
     finally:
         f.close()
+
+
+def decode_to_views(data, views, item_id=0, out_format="rgb", layout="chw", dtype=None, scale=None, bias=None, out=None, stream=None,
+                    host_threads=None, filter="triangle", light=None, tone=None, alpha=None, ootf=None, gain=None):
+    """Many views of ONE image from ONE decode (hm_decode_item_to_device_views): the crops of a multi-crop training step, the thumbnail
+    sizes of one upload, the face rectangles of a region item.  views: a list of (crop, size) or (crop, size, filter) - crop (x, y, w, h)
+    and size (w, h) as in decode_to_tensor, either may be None; filter defaults to the call's.  Returns a list of CUDA tensors, one per
+    view, each equal to decode_to_tensor(data, crop=crop, size=size, filter=filter, ...).  out: a list of tensors, one per view, or ONE
+    4-D tensor whose slices out[k] are the destinations when every view writes the same size (K x C x H x W: the multi-crop case); the
+    destinations must not overlap.  light=, tone=, alpha= and ootf= are decode_to_tensor's and apply to every view; gain= and
+    tone=dict(src_peak="measured") are decode_to_tensor's alone.  Of a grid only the tiles the bounding rectangle of all crops touches are
+    decoded.
+
+        crops = decode_to_views(data, [(c, (96, 96)) for c in crops_of_regions(read_regions(data), image_size)])   # every face, 96 x 96"""
+    import torch
+    L = capi.image_lib()
+    if gain is not None:
+        raise ValueError("gain: decode_to_views takes no gain step - call decode_to_tensor(crop=, size=, gain=) per view")
+    if isinstance(tone, dict) and tone.get("src_peak") == "measured":
+        raise ValueError("tone: decode_to_views does not measure the content's peak - call decode_to_tensor(crop=, size=, tone=dict(src_peak='measured', ...)) per view")
+    views = list(views)
+    if not 1 <= len(views) <= capi.HM_VIEWS_MOST:
+        raise ValueError(f"views: {len(views)} views, 1 .. {capi.HM_VIEWS_MOST} are taken")
+    fmt, lay = _out_format(out_format), _layout(layout)
+    if dtype is None:
+        first = out[0] if out is not None and len(out) else None
+        dtype = first.dtype if first is not None else torch.float32
+    code = _dtype_code(dtype)
+    st = _Steps(alpha, fmt)
+    c = st.c
+    f = _File(data)
+    try:
+        st.parse(light, tone, None, ootf)
+        iid, w, h = f.size(item_id)
+        n = len(views)
+        cviews, shapes = (capi.DeviceView * n)(), []
+        for k, spec in enumerate(views):
+            if len(spec) not in (2, 3):
+                raise ValueError(f"views[{k}]: (crop, size) or (crop, size, filter)")
+            v, vw, vh = _view_of(spec[0], spec[1], spec[2] if len(spec) == 3 else filter, w, h)
+            if v is None:  # (the whole image at its own size: a view of the crop alone)
+                v = capi.DeviceView()
+            cviews[k] = v
+            shapes.append(_shape(lay, c, vh, vw))
+        if out is None:
+            outs = [torch.empty(s, dtype=dtype, device="cuda") for s in shapes]
+        else:
+            if len(out) != n:
+                raise ValueError(f"out: {len(out)} destinations for {n} views")
+            outs = [out[k] for k in range(n)]
+            for k, t in enumerate(outs):
+                if not t.is_cuda or t.dtype != dtype:
+                    raise ValueError(f"out[{k}]: a CUDA tensor of dtype {dtype} is needed, got {t.dtype} on {t.device}")
+                if tuple(t.shape) != shapes[k]:
+                    raise ValueError(f"out[{k}]: shape {tuple(t.shape)} does not match the view's {shapes[k]}")
+        sc, bs = _per_channel(scale, 1.0), _per_channel(bias, 0.0)
+        dests = (capi.DeviceDest * n)(*[_dest_of(t, lay, code, c, sc, bs) for t in outs])
+        prm = capi.DecodeParams(fmt, host_threads or _default_threads(), 0, 0, _stream_handle(stream, outs[0].device), None, 0, 0, 0, 0)
+        d = (capi.Decoded * n)()
+        failed = C.c_int32(-1)
+        with torch.cuda.device(outs[0].device):
+            capi.check_image(L.hm_decode_item_to_device_views(f.h, iid, C.byref(prm), cviews, dests, n, _ref(st.lit), _ref(st.ton), _ref(st.alp), _ref(st.oo), d,
+                                                              C.byref(failed)))
+        for k in range(n):
+            got, want = (d[k].width, d[k].height), (outs[k].shape[2], outs[k].shape[1]) if lay == capi.HM_DEV_LAYOUT_CHW else (outs[k].shape[1], outs[k].shape[0])
+            if got != want:
+                raise capi.HmError(-3, f"view {k} wrote {got[0]} x {got[1]}, its tensor is {want[0]} x {want[1]}")
+        return outs
+    finally:
+        f.close()
+
+
+def crops_of_regions(regions, image_size=None):
+    """The bounding rectangles of read_regions() geometry as crops (x, y, w, h), in order: every region of every region item of the list
+    (or the regions of one item's dict).  image_size=(w, h): the rectangles are brought from the item's reference space to the image
+    (where the two differ) and clipped to it; a region that lies outside, or has no extent, is left out.  Masks count with their
+    rectangle, a point as one pixel.
+
+        faces = decode_to_views(data, [(c, (112, 112)) for c in crops_of_regions(read_regions(data), (w, h))])"""
+    items = [regions] if isinstance(regions, dict) else list(regions)
+    crops = []
+    for item in items:
+        rw, rh = item["reference_size"]
+        for r in item["regions"]:
+            t = r["type"]
+            if t in ("polygon", "polyline"):
+                pts = r["points"]
+                if len(pts) == 0:
+                    continue
+                x0, y0, x1, y1 = int(pts[:, 0].min()), int(pts[:, 1].min()), int(pts[:, 0].max()) + 1, int(pts[:, 1].max()) + 1
+            elif t == "ellipse":
+                x0, y0, x1, y1 = r["x"] - r["w"], r["y"] - r["h"], r["x"] + r["w"] + 1, r["y"] + r["h"] + 1
+            elif t == "point":
+                x0, y0, x1, y1 = r["x"], r["y"], r["x"] + 1, r["y"] + 1
+            else:
+                x0, y0, x1, y1 = r["x"], r["y"], r["x"] + r["w"], r["y"] + r["h"]
+            if image_size is not None:
+                iw, ih = image_size
+                if (rw, rh) != (iw, ih) and rw > 0 and rh > 0:  # the outward rounding of a rectangle scaled from the reference space
+                    x0, x1 = x0 * iw // rw, -(-x1 * iw // rw)
+                    y0, y1 = y0 * ih // rh, -(-y1 * ih // rh)
+                x0, y0, x1, y1 = max(x0, 0), max(y0, 0), min(x1, iw), min(y1, ih)
+            if x1 > x0 and y1 > y0:
+                crops.append((int(x0), int(y0), int(x1 - x0), int(y1 - y0)))
+    return crops
 
 
 class LightStats:

@@ -1138,6 +1138,50 @@ HM_API int hm_ootf_table(const hm_device_ootf* ootf, float gain, int which, floa
 HM_API int hm_ootf_luma(int primaries, float out[3]);
 
 /* ------------------------------------------------------------------------- */
+/* Views, many of one picture: the crops of a multi-crop training step, the thumbnail sizes of one upload, the face rectangles of a
+ * region item - `count` views (hm_device_view, "Views" above) of ONE item from ONE decode.
+ *
+ * The item is decoded ONCE.  views[k] is resolved against the decoded image and written into dests[k], which is sized for that view's
+ * out_w x out_h (the crop's size when out_w == out_h == 0).  out[k].width / height: the sizes written (out[k].stride[0]: the row pitch
+ * in use); the other fields of out[k] are those of the one decode.  The bytes in dests[k] are those of
+ * hm_decode_item_to_device_view(f, id, params, &views[k], &dests[k], ..), or of its _light / _tone / _alpha / _ootf sibling when steps are
+ * given.
+ *
+ * Steps: light, tone, alpha and ootf may each be NULL; the same steps apply to every view, under the rules of
+ * hm_decode_item_to_device_ootf.  HM_LIGHT_FROM_ICC is allowed (the item's profile is at hand).  The entry takes no gain step and no
+ * measured tone: those remain on the single-view entries.
+ *
+ * What is decoded: of a grid, the sub-grid hm_plan_views names - hm_plan_view's rule applied to the bounding rectangle of all crops, taken
+ * as one crop (a view without a crop makes that the whole image); under hm_plan_view's conditions that provably changes no pixel, otherwise
+ * the whole grid is decoded.  A derived item ('iovl', 'iden') is decoded and composed once, whole, and the views are taken of the result.
+ *
+ * How it is written: views without a step whose filter resamples (HM_VIEW_TRIANGLE / _CUBIC / _LANCZOS3) are grouped by what a kernel
+ * launch has one of - the staged horizontal pass or not, sample format, the destination's layout, dtype, scale, bias and 16-byte
+ * alignment - and each group takes one upload and, per bounded chunk of views, ONE launch per resampling pass.  The crop alone and
+ * HM_VIEW_NEAREST are written view by view; with a light / tone / OOTF / alpha step every view is written on its own from the one decoded
+ * image (the decode is shared; fused stepped passes are not built).
+ *
+ * Refused before anything is queued, every destination unwritten: count outside 1 .. HM_VIEWS_MOST; a null array; everything the
+ * single-view entry refuses for views[k] / dests[k] (*failed_view = k; the message starts with "view k: "); two destinations whose
+ * byte ranges - hm_device_dest_bytes of the size written, with row_pitch / plane_pitch as resolved, from ptr - overlap
+ * (HM_ERR_INVALID_ARG, the message names both indices); an 'unci' or 'mski' item (HM_ERR_UNSUPPORTED for now: a view of such an item
+ * uploads by internal tile, a separate piece - use hm_decode_item_to_device_view per view).  *failed_view (may be NULL) = -1 when the
+ * refusal is not one view's. */
+enum { HM_VIEWS_MOST = 4096 };
+HM_API int hm_decode_item_to_device_views(const hm_file* f, uint32_t id, const hm_decode_params* params, const hm_device_view* views,
+                                          const hm_device_dest* dests, int32_t count, const hm_device_light* light, const hm_device_tone* tone,
+                                          const hm_device_alpha* alpha, const hm_device_ootf* ootf, hm_decoded* out /* [count] */,
+                                          int32_t* failed_view);
+/* The step on its own - the multi form of hm_resample_to_tensor -, on interleaved pixels that are on the device already: no steps.
+ * Asynchronous on `stream`.  Refusals as above (a view's message starts with "view k: "). */
+HM_API int hm_resample_views_to_tensor(int out_format, int src_w, int src_h, const void* d_src, int src_stride, const hm_device_view* views,
+                                       const hm_device_dest* dests, int32_t count, void* stream);
+/* Host arithmetic: hm_plan_view for hm_decode_item_to_device_views - tiles[] = first tile row, row count, first tile column, column count
+ * that call will entropy-decode.  count == 1: hm_plan_view's answer. */
+HM_API int hm_plan_views(const hm_file* f, uint32_t id, const hm_decode_params* params, const hm_device_view* views, int32_t count,
+                         int32_t tiles[4]);
+
+/* ------------------------------------------------------------------------- */
 /* Light statistics: a picture's light levels measured on the device, and a tone step fed from them */
 /* ------------------------------------------------------------------------- */
 

@@ -13,6 +13,7 @@
 #                take-overs, 4x4 passes, wave-wide blocks, iterations)
 #   probes       VARIANTS / OBJ / MODE of tools/probe_chain.sh from the environment
 #   classes      tools/bench_classes.py (picture classes x batch sizes)
+#   views        tools/views_clock.py (many views of one 12 MP grid: K single-view calls, the one call per view, the one call) -> profiles/device_views.txt
 #   sh:<file>    any other script, run with bash
 tag=$1; shift
 mkdir -p gpurun_out
@@ -39,6 +40,7 @@ for a in "$@"; do
   probes)  tools/probe_chain.sh > $log 2>&1; cat $log ;;
   classes) { echo "== 1536 tiles per class"; timeout 1200 python3 tools/bench_classes.py 2>/dev/null | tr -d '\n' | sed 's/},/},\n/g'; echo
              echo "== 18432 tiles per class"; HM_CLASS_TILES=18432 timeout 1200 python3 tools/bench_classes.py 2>/dev/null | tr -d '\n' | sed 's/},/},\n/g'; echo; } > $log 2>&1; cat $log ;;
+  views)   timeout 900 python3 tools/views_clock.py --out profiles/device_views.txt > $log 2>&1; cat $log ;;
   sh:*)    bash ${a#sh:} > $log 2>&1; tail -30 $log ;;
   *)       echo "unknown action $a" ;;
   esac
